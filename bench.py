@@ -2,6 +2,7 @@
 """Headline benchmark: SELL-32-512 double-precision SpMV, GFLOP/s and achieved HBM GB/s.
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    (+ y of the last timed step as DIR/*.npy)
 
 A "step" is one SpMV y = A x over the whole (distributed) matrix, inputs resident in HBM.
 Workload at N = 1 (BASELINE.json configs[1]): nlpkkt200-class matrix -- the SuiteSparse file is not
@@ -72,8 +73,36 @@ def parse():
     ap.add_argument("--grid5", type=int, default=304, help="config 5one: stencil grid edge")
     ap.add_argument("--grid3", type=int, default=111, help="config 3: nodes per edge (3 dof per node)")
     ap.add_argument("--n4b", type=int, default=2017169, help="config 4b: rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps write the y of the last timed step to DIR/*.npy (float64, original row order; "
+                         "a fixed, seeded sample of rows when the whole vector would exceed DUMP_BYTES_MAX)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs is available at N = 1 only")
+    return args
+
+
+DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: all files together
+DUMP_SAMPLE_ROWS = 1 << 21     # rows kept when y is larger (y and its row numbers: 2 x 16 MiB)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(d, y, old_to_new, n_rows):
+    """--dump-outputs: y of the timed path in the ORIGINAL row order (y.npy), so that two builds that number the SELL rows differently
+    still compare row for row, and the original row numbers of its entries (exact in float64) in y_rows.npy.  If all n_rows do not fit
+    into DUMP_BYTES_MAX, a fixed seeded sample of rows is written instead."""
+    os.makedirs(d, exist_ok=True)
+    y_orig = y.cpu().numpy()[np.asarray(old_to_new)[:n_rows]]
+    if 2 * y_orig.nbytes <= DUMP_BYTES_MAX:
+        rows = np.arange(n_rows)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, DUMP_SAMPLE_ROWS, replace=False))
+        y_orig = y_orig[rows]
+    np.save(os.path.join(d, "y.npy"), np.ascontiguousarray(y_orig, dtype=np.float64))
+    np.save(os.path.join(d, "y_rows.npy"), rows.astype(np.float64))
 
 
 def stencil_row_counts(nx, ny, nz):
@@ -198,7 +227,7 @@ def other_configs(pkg, B, torch, args, which):
     from oracle import refshim
     from oracle import oracle as orc       # cpu_baseline leg: the port stands in when oracle/_ref did not travel
     t = torch
-    K, W = max(args.steps, 50), 30         # (short loops behind seconds of host work measure the GPU's clock ramp)
+    K, W = args.steps, 30                  # (short loops behind seconds of host work measure the GPU's clock ramp, see DESIGN 7: W stays 30)
     res = []
 
     def measure(call, kind, **kw):
@@ -1157,6 +1186,8 @@ def main():
     elapsed = time.perf_counter() - t0
     ms_per_step = elapsed / args.steps * 1e3
     gflops = 2.0 * total_nnz / (ms_per_step * 1e-3) / 1e9
+    if args.dump_outputs:                         # before anything else writes into y
+        dump_outputs(args.dump_outputs, y, s.arrays()["old_to_new_idx"], s.n_rows)
 
     # ------------------------------------------------------------------ what y's placement alone is worth in THIS process: the same
     #                                                                    kernel, matrix and x, four more output vectors (fresh allocations, all held)

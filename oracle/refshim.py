@@ -1,8 +1,8 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes front-end of oracle/_ref/libuspmv_ref*.so, i.e. the
 GENUINE reference compiled from /root/reference/code by oracle/Makefile (driver: ref_shim.cpp).
 
-Used by oracle/make_golden.py (golden vectors), tests (live cross-check when the prebuilt .so is
-present) and bench.py's cpu_baseline leg (kind "reference").  Never by the product.
+Used by oracle/make_golden.py and oracle/make_golden_random.py (golden vectors under tests/golden/)
+and bench.py's cpu_baseline leg (kind "reference").  Never by the product or the tests.
 """
 import ctypes as C
 import os

@@ -23,7 +23,7 @@ def test_host_layer_is_clean_under_asan_ubsan(tmp_path):
     if r.returncode != 0 and ("asan" in r.stderr.lower() or "ubsan" in r.stderr.lower()):
         pytest.skip("sanitizer runtime not installed")
     assert r.returncode == 0, r.stderr[-2000:]
-    env = dict(os.environ, OMP_NUM_THREADS="4", ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    env = dict(os.environ, OMP_NUM_THREADS="4", ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1", TMPDIR=str(tmp_path))
     mats = [mtx_path(n) for n in ("FDM-2d-16", "bcsstk13", "impcol_e", "matrix1", "myBigMat", "mySymmMat")]
     r = subprocess.run([exe] + mats, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

@@ -74,8 +74,10 @@ int main(int argc, char **argv) {
             uspmv_coo_free(pm);
         }
         uspmv_coo_t *dp, *sp; CK(uspmv_partition_precisions(m, 1.0, &dp, &sp)); uspmv_coo_free(dp); uspmv_coo_free(sp);
-        std::string f = std::string("/tmp/uspmv_sanitize_cache.bin"); CK(uspmv_coo_save(m, f.c_str()));
-        uspmv_coo_t *m2; CK(uspmv_coo_load(f.c_str(), &m2)); uspmv_coo_free(m2);
+        const char *td = getenv("TMPDIR");                                  // (the test points TMPDIR at its own directory)
+        std::string f = std::string(td && *td ? td : "/tmp") + "/uspmv_sanitize_cache_" + std::to_string((int)getpid()) + ".bin";
+        CK(uspmv_coo_save(m, f.c_str()));
+        uspmv_coo_t *m2; CK(uspmv_coo_load(f.c_str(), &m2)); uspmv_coo_free(m2); unlink(f.c_str());
         if (n <= nc) CK(uspmv_coo_equilibrate(m));
         uspmv_coo_free(m);
         printf("ok %s\n", argv[a]);

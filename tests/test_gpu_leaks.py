@@ -1,4 +1,4 @@
-"""Device-memory hygiene: handles with every kind of plan, adaptive-precision pairs and the distributed object (with its optional step
+"""Device-memory hygiene: handles with every kind of plan, one handle re-planned in place, adaptive-precision pairs and the distributed object (with its optional step
 forms and block plans) are created, used and freed repeatedly; the GPU's free memory after five more cycles is what it was after the
 first (hipMemGetInfo through torch; the first cycle absorbs one-time runtime allocations)."""
 import gc
@@ -30,6 +30,21 @@ def _cycle_handles(pkg, t, m):
                 pkg.spmmv(A, X, Y, b, s.n_rows_padded, lay)
             del A
         del X, Y
+    # one handle planned again and again in place: every install replaces the plan of its family, a block plan also its stream
+    # schedule; only the last plans are freed with the handle
+    X = t.ones(8 * s.n_rows_padded, dtype=t.float64, device="cuda"); Y = t.zeros_like(X)
+    A = pkg.DeviceMatrix(s)
+    pkg.set_tuning(spmmv_stream=4)
+    try:
+        for _ in range(2):
+            A.optimize(s); A.optimize_sweep(s); A.optimize_device()
+            A.optimize_block(s, 8); A.optimize_block_device(8)
+            A.optimize_block_sweep(s, 8, wlog=9, tile_rows=1024)
+            pkg.spmv(A, x, y)
+            pkg.spmmv(A, X, Y, 8, s.n_rows_padded, pkg.ROWWISE)
+    finally:
+        pkg.set_tuning(spmmv_stream=0)
+    del A, X, Y
     lay, Ad = pkg.convert_to_scs_device(m, 32, 512, pkg.F64)
     Ad.optimize_device(); pkg.spmv(Ad, x, y)
     del Ad, lay

@@ -225,24 +225,24 @@ int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int 
 
 int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x, const float *d_x_sp, double *d_y,
                    hipStream_t stream) {
-    if (!d_x_sp && dp->sw && sp->sw && dp->sw_tile_ids && dp->sw_idx_b && dp->sw_plan_id == sp->sw_plan_id && g_tune.sweep &&
+    if (!d_x_sp && dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.idx_b && dp->sw.plan_id == sp->sw.plan_id && g_tune.sweep &&
         ((uintptr_t)d_x % 16 == 0)) {
         if (int rc = launch_spmv_sweep_ap(dp, d_x, d_y, stream)) return rc;
-        return launch_spmv_ap_chunks(dp, sp, dp->sw_rest, (long)dp->sw_n_rest, d_x, d_y, stream);
+        return launch_spmv_ap_chunks(dp, sp, dp->sw.rest, (long)dp->sw.n_rest, d_x, d_y, stream);
     }
-    if (!d_x_sp && dp->tlc && sp->tlc && dp->tlc_plan_id != 0 && dp->tlc_plan_id == sp->tlc_plan_id && g_tune.tlc &&
+    if (!d_x_sp && dp->tlc.on && sp->tlc.on && dp->tlc.plan_id != 0 && dp->tlc.plan_id == sp->tlc.plan_id && g_tune.tlc &&
         ((uintptr_t)d_x % 16 == 0)) {
-        const size_t lds = (size_t)dp->tlc_max_lines * 16 * sizeof(double);
+        const size_t lds = (size_t)dp->tlc.max_lines * 16 * sizeof(double);
         const int C = (int)dp->C;
 #define APT_LAUNCH(CTV, NTV)                                                                                          \
     do {                                                                                                              \
         auto kfn = scs_spmv_ap_tlc<CTV, NTV>;                                                                        \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)dp->tlc_n_tiles), dim3(dp->tlc_tile_rows), lds, (hipStream_t)stream,     \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)dp->tlc.n_tiles), dim3(dp->tlc.tile_rows), lds, (hipStream_t)stream,     \
                            (long)dp->n_chunks, C, dp->chunk_ptrs, dp->chunk_lengths, dp->col_idxs, (const double *)dp->values, \
                            sp->chunk_ptrs, sp->chunk_lengths, sp->col_idxs, (const float *)sp->values, d_x, d_y,         \
-                           dp->tlc_line_ptr, dp->tlc_lines, dp->tlc_c16_ptrs, dp->tlc_col16, sp->tlc_c16_ptrs,           \
-                           sp->tlc_col16, (long)dp->tlc_x_len, g_tune.xcd_remap);                                        \
+                           dp->tlc.line_ptr, dp->tlc.lines, dp->tlc.c16_ptrs, dp->tlc.col16, sp->tlc.c16_ptrs,           \
+                           sp->tlc.col16, (long)dp->tlc.x_len, g_tune.xcd_remap);                                        \
     } while (0)
         if (g_tune.nontemporal) { if (C == 32) APT_LAUNCH(32, true); else APT_LAUNCH(0, true); }
         else { if (C == 32) APT_LAUNCH(32, false); else APT_LAUNCH(0, false); }

@@ -209,9 +209,9 @@ __global__ void part_len_fill(const long n_chunks, const int C, const int rows_p
 namespace uspmv_dev {
 
 int launch_block_tile_class(const uspmv_dmat *A, long n_local, unsigned char *d_flags, hipStream_t st) {
-    if (A->pb_n_tiles == 0) return USPMV_OK;
-    hipLaunchKernelGGL(block_tile_class, dim3((unsigned)((A->pb_n_tiles + 255) / 256)), dim3(256), 0, st, (long)A->pb_n_tiles, A->pb_ph_ptr, A->pb_list_ptr,
-                       A->pb_xrows, (int)std::min<long>(n_local, INT32_MAX), d_flags);
+    if (A->pb.n_tiles == 0) return USPMV_OK;
+    hipLaunchKernelGGL(block_tile_class, dim3((unsigned)((A->pb.n_tiles + 255) / 256)), dim3(256), 0, st, (long)A->pb.n_tiles, A->pb.ph_ptr, A->pb.list_ptr,
+                       A->pb.xrows, (int)std::min<long>(n_local, INT32_MAX), d_flags);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }

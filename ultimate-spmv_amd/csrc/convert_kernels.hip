@@ -13,6 +13,7 @@
 // The fixed-permutation form (:1911-1928: the sp struct of an ap[dp_sp] pair takes the dp struct's permutation) skips the ordering.
 #include "uspmv_device.hpp"
 
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -145,17 +146,6 @@ __global__ void perm_kernel(const int *__restrict__ new_pos, const int n_rows, c
     if (p < n_rows) n2o[p] = (int)i;                       // (the reference writes out of bounds otherwise; such slots stay 0)
 }
 
-struct Bufs {   // scoped device scratch
-    std::vector<void *> p;
-    ~Bufs() { for (void *q : p) (void)hipFree(q); }
-    template <typename T> hipError_t get(T **out, size_t n) {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(n * sizeof(T), 16));
-        if (e == hipSuccess) { p.push_back(q); *out = (T *)q; }
-        return e;
-    }
-};
-
 }  // namespace
 
 extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
@@ -174,18 +164,17 @@ extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const
     if (sort_mode == USPMV_SORT_DEVICE_STABLE && !d_fixed_permutation && std::min<int64_t>(sigma, n_pad) > 8192)
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: the device-side stable ordering takes sorting scopes of up to 8192 rows (sigma = %lld): use USPMV_SORT_HOST", who, (long long)sigma);
     hipStream_t st = (hipStream_t)stream;
-    Bufs B;
-    int *start = nullptr, *flag = nullptr, *new_pos = nullptr, *len_new = nullptr;
-    long *elems = nullptr, *part = nullptr, *sums = nullptr, *total = nullptr;
+    DeviceBuf<int> start, flag, new_pos, len_new, o2n_own, n2o_own;
+    DeviceBuf<long> elems, part, sums, total;
     const long nb = (long)((n_chunks + 1023) / 1024);
-    HIP_TRY(B.get(&start, (size_t)n_rows + 1));
-    HIP_TRY(B.get(&flag, 1));
-    HIP_TRY(B.get(&new_pos, (size_t)n_pad));
-    HIP_TRY(B.get(&len_new, (size_t)n_pad));
-    HIP_TRY(B.get(&elems, (size_t)n_chunks));
-    HIP_TRY(B.get(&part, (size_t)n_chunks));
-    HIP_TRY(B.get(&sums, (size_t)nb));
-    HIP_TRY(B.get(&total, 1));
+    HIP_TRY(start.alloc(4 * ((size_t)n_rows + 1)));
+    HIP_TRY(flag.alloc(4));
+    HIP_TRY(new_pos.alloc(4 * (size_t)n_pad));
+    HIP_TRY(len_new.alloc(4 * (size_t)n_pad));
+    HIP_TRY(elems.alloc(8 * (size_t)n_chunks));
+    HIP_TRY(part.alloc(8 * (size_t)n_chunks));
+    HIP_TRY(sums.alloc(8 * (size_t)nb));
+    HIP_TRY(total.alloc(8));
     HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
     HIP_TRY(hipMemsetAsync(len_new, 0, 4 * (size_t)n_pad, st));
 
@@ -231,12 +220,11 @@ extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const
     }
 
     // ---- chunk lengths and pointers (code/utilities.hpp:1949-1966)
-    struct Guard { uspmv_dmat *A; ~Guard() { if (A) uspmv_dmat_free(A); } } guard{new uspmv_dmat};
-    uspmv_dmat *A = guard.A;
-    A->C = C; A->n_chunks = n_chunks; A->dtype = dtype; A->owns = true; A->n_store = (long)n_pad;
-    int *cl = nullptr, *cp = nullptr;
-    hipError_t e = hipMalloc((void **)&cl, 4 * (size_t)n_chunks);
-    if (e == hipSuccess) e = hipMalloc((void **)&cp, 4 * ((size_t)n_chunks + 1));
+    std::unique_ptr<uspmv_dmat> A(new uspmv_dmat);
+    A->C = C; A->n_chunks = n_chunks; A->dtype = dtype; A->n_store = (long)n_pad;
+    hipError_t e = A->own.chunk_lengths.alloc(4 * (size_t)n_chunks);
+    if (e == hipSuccess) e = A->own.chunk_ptrs.alloc(4 * ((size_t)n_chunks + 1));
+    int *cl = A->own.chunk_lengths, *cp = A->own.chunk_ptrs;
     A->chunk_lengths = cl; A->chunk_ptrs = cp;
     if (e != hipSuccess) { return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e)); }
     hipLaunchKernelGGL(chunk_max_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, st, len_new, (long)n_chunks, (int)C, cl, elems);
@@ -261,14 +249,14 @@ extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const
 
     // ---- permutations, then the scatter (padding: value 0, column 0 -- mapped by permute_scs_cols like any local column, :1820-1826)
     int *o2n = d_old_to_new, *n2o = d_new_to_old;
-    if (!o2n) HIP_TRY(B.get(&o2n, (size_t)n_rows));
-    if (!n2o) HIP_TRY(B.get(&n2o, (size_t)n_rows));
+    if (!o2n) { HIP_TRY(o2n_own.alloc(4 * (size_t)n_rows)); o2n = o2n_own; }
+    if (!n2o) { HIP_TRY(n2o_own.alloc(4 * (size_t)n_rows)); n2o = n2o_own; }
     HIP_TRY(hipMemsetAsync(n2o, 0, 4 * (size_t)n_rows, st));
     hipLaunchKernelGGL(perm_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, new_pos, (int)n_rows, d_fixed_permutation != nullptr, o2n, n2o);
     const size_t vsz = dtype == USPMV_F64 ? 8 : 4, ne = (size_t)std::max<int64_t>(h_total, 1);
-    void *ci = nullptr, *va = nullptr;
-    e = hipMalloc(&ci, 4 * ne);
-    if (e == hipSuccess) e = hipMalloc(&va, vsz * ne);
+    e = A->own.col_idxs.alloc(4 * ne);
+    if (e == hipSuccess) e = A->own.values.alloc(vsz * ne);
+    void *ci = A->own.col_idxs, *va = A->own.values;
     A->col_idxs = (const int32_t *)ci; A->values = va;
     int pad_col = 0;
     if (e == hipSuccess && permute_cols) e = hipMemcpyAsync(&pad_col, o2n, 4, hipMemcpyDeviceToHost, st);
@@ -296,7 +284,6 @@ extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const
     }
     e = hipStreamSynchronize(st);                            // (the scratch of this call is released on return)
     if (e != hipSuccess) { if (layout) { delete *layout; *layout = nullptr; } return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
-    guard.A = nullptr;
-    *out = A;
+    *out = A.release();
     return USPMV_OK;
 }

@@ -643,10 +643,10 @@ void launch_spmmv_rowmajor_u(const uspmv_dmat *A, const VT *X, VT *Y, long ld, b
     const unsigned grid = grid_for(A->n_chunks * A->C, block);
     // variant 5: the gather kernel over the block plan's tie-reordered copy of the entries (neighbouring lanes then read
     // neighbouring X rows, which is what L1 can exploit)
-    const bool ro = g_tune.spmmv_variant == 5 && A->bt_values && A->bt_cols && A->bt_row_map && !A->part;
-    const int *cols = ro ? A->bt_cols : A->col_idxs;
-    const VT *vals = (const VT *)(ro ? A->bt_values : A->values);
-    const int *rmap = ro ? A->bt_row_map : nullptr;
+    const bool ro = g_tune.spmmv_variant == 5 && A->bt.values && A->bt.cols && A->bt.row_map && !A->part;
+    const int *cols = ro ? A->bt.cols : A->col_idxs;
+    const VT *vals = (const VT *)(ro ? A->bt.values : A->values);
+    const int *rmap = ro ? A->bt.row_map : nullptr;
 #define RM_LAUNCH(NTV, YC)                                                                                          \
     do {                                                                                                            \
         if (g_tune.spmmv_prefetch)                                                                                  \
@@ -685,17 +685,17 @@ void launch_spmmv_xpose_u(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool
 
 template <typename VT, int B, int G, int CT, int HS, bool SWZ>
 void launch_spmmv_tlc_g(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, hipStream_t st) {
-    const size_t x_bytes = (size_t)A->bt_max_rows * B * sizeof(VT);
-    const size_t lds = x_bytes + (((size_t)A->bt_max_rows * 4 + 15) & ~(size_t)15);   // X rows + the tile's row list
+    const size_t x_bytes = (size_t)A->bt.max_rows * B * sizeof(VT);
+    const size_t lds = x_bytes + (((size_t)A->bt.max_rows * 4 + 15) & ~(size_t)15);   // X rows + the tile's row list
 #define BT_LAUNCH(NTV, YC)                                                                                              \
     do {                                                                                                                \
         auto kfn = scs_spmmv_tlc<VT, B, NTV, YC, G, CT, HS, SWZ>;                                                                \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)A->bt_n_tiles), dim3(64), lds, st, (long)A->n_chunks,                    \
-                           A->chunk_ptrs, A->chunk_lengths, A->bt_cols ? A->bt_cols : A->col_idxs,                       \
-                           (const VT *)(A->bt_values ? A->bt_values : A->values), X, Y, ld, A->bt_line_ptr,                \
-                           A->bt_xrows, A->bt_c16_ptrs, A->bt_col16, ld, g_tune.xcd_remap, (long)A->n_store, (int)x_bytes, \
-                           (const int *)A->bt_row_map);                                                                   \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)A->bt.n_tiles), dim3(64), lds, st, (long)A->n_chunks,                    \
+                           A->chunk_ptrs, A->chunk_lengths, A->bt.cols ? A->bt.cols : A->col_idxs,                       \
+                           (const VT *)(A->bt.values ? A->bt.values : A->values), X, Y, ld, A->bt.line_ptr,                \
+                           A->bt.xrows, A->bt.c16_ptrs, A->bt.col16, ld, g_tune.xcd_remap, (long)A->n_store, (int)x_bytes, \
+                           (const int *)A->bt.row_map);                                                                   \
     } while (0)
     if (g_tune.nontemporal) { if (ycol) BT_LAUNCH(true, true); else BT_LAUNCH(true, false); }
     else { if (ycol) BT_LAUNCH(false, true); else BT_LAUNCH(false, false); }
@@ -711,11 +711,11 @@ void launch_spmmv_quad_m(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool 
     do {                                                                                                                \
         auto kfn = scs_spmmv_quad<VT, B, NTV, YC, CT, SWZ, PD, MAXP>;                                                   \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)A->bt_n_tiles), dim3(256), lds, st, (long)A->n_chunks,                   \
-                           A->chunk_ptrs, A->chunk_lengths, A->bt_cols ? A->bt_cols : A->col_idxs,                       \
-                           (const VT *)(A->bt_values ? A->bt_values : A->values), X, Y, ld, A->bt_line_ptr,                \
-                           A->bt_xrows, A->bt_c16_ptrs, A->bt_col16, g_tune.xcd_remap, (long)A->n_store, (int)x_bytes,    \
-                           (const int *)A->bt_row_map, g_tune.ablate);                                                    \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)A->bt.n_tiles), dim3(256), lds, st, (long)A->n_chunks,                   \
+                           A->chunk_ptrs, A->chunk_lengths, A->bt.cols ? A->bt.cols : A->col_idxs,                       \
+                           (const VT *)(A->bt.values ? A->bt.values : A->values), X, Y, ld, A->bt.line_ptr,                \
+                           A->bt.xrows, A->bt.c16_ptrs, A->bt.col16, g_tune.xcd_remap, (long)A->n_store, (int)x_bytes,    \
+                           (const int *)A->bt.row_map, g_tune.ablate);                                                    \
     } while (0)
     if (g_tune.nontemporal) { if (ycol) QD_LAUNCH(true, true); else QD_LAUNCH(true, false); }
     else { if (ycol) QD_LAUNCH(false, true); else QD_LAUNCH(false, false); }
@@ -724,7 +724,7 @@ void launch_spmmv_quad_m(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool 
 
 template <typename VT, int B, int CT, bool SWZ, int PD>
 void launch_spmmv_quad_g(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, hipStream_t st) {
-    const int pieces = (A->bt_max_rows * 4 + 255) / 256;     // DMA pieces per wave for the largest tile (BT_LDS_CAP = 80 KiB: <= 20)
+    const int pieces = (A->bt.max_rows * 4 + 255) / 256;     // DMA pieces per wave for the largest tile (BT_LDS_CAP = 80 KiB: <= 20)
     if (pieces <= 8) launch_spmmv_quad_m<VT, B, CT, SWZ, PD, 8>(A, X, Y, ld, ycol, st);
     else if (pieces <= 13) launch_spmmv_quad_m<VT, B, CT, SWZ, PD, 13>(A, X, Y, ld, ycol, st);
     else launch_spmmv_quad_m<VT, B, CT, SWZ, PD, 20>(A, X, Y, ld, ycol, st);
@@ -751,7 +751,7 @@ void launch_spmmv_rowmajor(const uspmv_dmat *A, const VT *X, VT *Y, long ld, boo
         // 64-byte rows, phased plan (variant 8; auto when the handle carries one): eight workgroups per CU
         if ((g_tune.spmmv_variant == 8 || (g_tune.spmmv_variant == 0 && !g_tune.ablate)) && launch_spmmv_quadph<VT, B>(A, X, Y, ld, ycol, 0, st)) return;
         // 64-byte rows: the four-lanes-per-row kernel over 64-row tiles of the block plan (variant 6; auto when the plan is there)
-        if (A->bt && !A->part && A->bt_tile_rows == 64 && (g_tune.spmmv_variant == 0 || g_tune.spmmv_variant == 6) && (size_t)A->bt_max_rows * RB <= BT_LDS_CAP) {
+        if (A->bt.on && !A->part && A->bt.tile_rows == 64 && (g_tune.spmmv_variant == 0 || g_tune.spmmv_variant == 6) && (size_t)A->bt.max_rows * RB <= BT_LDS_CAP) {
             // one tile per workgroup, three workgroups per CU (a persistent, software-pipelined form of it -- 222 registers, two workgroups
             // per CU -- measured 5-7 % slower and was removed: profiles/r02/spmmv_variants.txt)
             launch_spmmv_quad<VT, B>(A, X, Y, ld, ycol, st);
@@ -763,9 +763,9 @@ void launch_spmmv_rowmajor(const uspmv_dmat *A, const VT *X, VT *Y, long ld, boo
         // auto takes the plan for rows of <= 32 bytes only: there 4+ tiles fit a CU and the kernel is 12-15 % ahead of
         // the gather form; with 64-byte rows (2-3 tiles per CU) each tile's chain of dependent fetches is exposed and
         // it is 20 % behind (profiles/r01/spmmv_probe13.txt).  Variant 4 forces it.
-        if (A->bt && !A->part && ((g_tune.spmmv_variant == 0 && RB <= 32) || g_tune.spmmv_variant == 4) && (size_t)A->bt_max_rows * RB <= BT_LDS_CAP) {
+        if (A->bt.on && !A->part && ((g_tune.spmmv_variant == 0 && RB <= 32) || g_tune.spmmv_variant == 4) && (size_t)A->bt.max_rows * RB <= BT_LDS_CAP) {
             const bool swz = g_tune.spmmv_swizzle != 0;
-            if (A->bt_tile_rows == 32) {
+            if (A->bt.tile_rows == 32) {
                 if constexpr (RB >= 32) {
                     if (swz) launch_spmmv_tlc_g<VT, B, 4, 32, 2, true>(A, X, Y, ld, ycol, st);
                     else launch_spmmv_tlc_g<VT, B, 4, 32, 2, false>(A, X, Y, ld, ycol, st);
@@ -805,17 +805,16 @@ template <typename VT, int B>
 int relayout_x(const uspmv_dmat *A, const VT *X, long ld, hipStream_t st, int *form, bool plain_only = false) {
     const size_t need = sizeof(VT) * (size_t)B * (size_t)ld;
     if (A->ws_bytes < need) {
-        if (A->ws) (void)hipFree(A->ws);
-        A->ws = nullptr; A->ws_bytes = 0; A->xprep_ptr = nullptr;
-        hipError_t e = hipMalloc(&A->ws, need);
+        A->ws.reset(); A->ws_bytes = 0; A->xprep_ptr = nullptr;
+        hipError_t e = A->ws.alloc(need);
         if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_spmmv: workspace of %zu bytes: %s", need, hipGetErrorString(e));
         A->ws_bytes = need;
     }
     VT *Xr = (VT *)A->ws;
     if constexpr (B * (int)sizeof(VT) == 64) {
         // the re-layout pass undoes the sigma permutation, the kernel runs on the plan over original X-row numbering
-        if (!plain_only && (g_tune.spmmv_variant == 0 || g_tune.spmmv_variant == 8) && !g_tune.ablate && !A->part && g_tune.spmmv_unscramble && A->pu && A->pu_perm && A->pu_n_perm <= ld) {
-            hipLaunchKernelGGL((block_vector_to_rowmajor<VT, B, true>), dim3(grid_for(ld, 256)), dim3(256), 0, st, X, Xr, ld, ld, (const int *)A->pu_perm, (long)A->pu_n_perm);
+        if (!plain_only && (g_tune.spmmv_variant == 0 || g_tune.spmmv_variant == 8) && !g_tune.ablate && !A->part && g_tune.spmmv_unscramble && A->pu.on && A->pu.perm && A->pu.n_perm <= ld) {
+            hipLaunchKernelGGL((block_vector_to_rowmajor<VT, B, true>), dim3(grid_for(ld, 256)), dim3(256), 0, st, X, Xr, ld, ld, (const int *)A->pu.perm, (long)A->pu.n_perm);
             *form = 2;
             return USPMV_OK;
         }
@@ -840,7 +839,7 @@ int spmmv_fast(const uspmv_dmat *A, const VT *X, VT *Y, long ld, int layout, hip
     if constexpr (B * (int)sizeof(VT) == 64) {
         // the block-vector window sweep, when the handle carries its plan (uspmv_dmat_optimize_block_sweep): both layouts straight from
         // the caller's vectors -- column-major X is staged column by column, no re-layout pass
-        if (A->bw && (g_tune.spmmv_variant == 0 || g_tune.spmmv_variant == 9) && !g_tune.ablate) {
+        if (A->bw.on && (g_tune.spmmv_variant == 0 || g_tune.spmmv_variant == 9) && !g_tune.ablate) {
             const int rc = launch_spmmv_sweep<VT>(A, X, Y, B, ld, layout == USPMV_COLWISE, layout == USPMV_COLWISE, st);
             if (rc <= 0) return rc;
         }

@@ -250,45 +250,45 @@ template <typename VT, typename IT, int B, int CT, int MAXP>
 void launch_spmmv_quadph_m(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, int xmode, hipStream_t st) {
     const bool xcol = xmode == 1;
     const size_t lds = xcol ? (size_t)MAXP * 64 * 80 : (size_t)MAXP * 4 * 1024;   // MAXP*64 rows of 64 (row-major X / lines, DMA pieces) or 80 bytes
-#define QH_ARGS(PH, G0, LP, XR, C16) (long)A->n_chunks, A->chunk_ptrs, part_lengths(A, 1), (const VT *)A->pb_values, X, Y, ld, PH, G0, LP, XR, A->pb_c16_ptrs, \
-                           (const IT *)C16, g_tune.xcd_remap, (long)A->n_store, (const int *)A->bt_row_map
+#define QH_ARGS(PH, G0, LP, XR, C16) (long)A->n_chunks, A->chunk_ptrs, part_lengths(A, 1), (const VT *)A->pb.values, X, Y, ld, PH, G0, LP, XR, A->pb.c16_ptrs, \
+                           (const IT *)C16, g_tune.xcd_remap, (long)A->n_store, (const int *)A->bt.row_map
 #define QH_LAUNCH(NTV, YC)                                                                                              \
     do {                                                                                                                \
         auto kfn = xcol ? scs_spmmv_quadph<VT, IT, B, NTV, YC, CT, 8, MAXP, 1> : scs_spmmv_quadph<VT, IT, B, NTV, YC, CT, 8, MAXP, 0>; \
         if (YC && NTV && !xcol && !g_tune.spmmv_ycol_nt) kfn = scs_spmmv_quadph<VT, IT, B, NTV, YC, CT, 8, MAXP, 0, 0, false>;            \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)A->pb_n_tiles), dim3(256), lds, st, QH_ARGS(A->pb_ph_ptr, A->pb_g0, A->pb_list_ptr, A->pb_xrows, A->pb_col16)); \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st, QH_ARGS(A->pb.ph_ptr, A->pb.g0, A->pb.list_ptr, A->pb.xrows, A->pb.col16)); \
     } while (0)
     if constexpr (MAXP == 4 && sizeof(IT) == 1) {
         if (xmode == 3) {   // row-major workspace in ORIGINAL row numbering (the re-layout pass undid the sigma permutation): the handle's third plan
             if (g_tune.nontemporal && g_tune.spmmv_ycol_nt)
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 0>), dim3((unsigned)A->pb_n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pu_ph_ptr, A->pu_g0, A->pu_list_ptr, A->pu_xrows, A->pu_col8));
+                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 0>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
+                                   QH_ARGS(A->pu.ph_ptr, A->pu.g0, A->pu.list_ptr, A->pu.xrows, A->pu.col8));
             else if (g_tune.nontemporal)
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 0, 0, false>), dim3((unsigned)A->pb_n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pu_ph_ptr, A->pu_g0, A->pu_list_ptr, A->pu_xrows, A->pu_col8));
+                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 0, 0, false>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
+                                   QH_ARGS(A->pu.ph_ptr, A->pu.g0, A->pu.list_ptr, A->pu.xrows, A->pu.col8));
             else
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, false, true, CT, 8, MAXP, 0>), dim3((unsigned)A->pb_n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pu_ph_ptr, A->pu_g0, A->pu_list_ptr, A->pu_xrows, A->pu_col8));
+                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, false, true, CT, 8, MAXP, 0>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
+                                   QH_ARGS(A->pu.ph_ptr, A->pu.g0, A->pu.list_ptr, A->pu.xrows, A->pu.col8));
             return;
         }
         if (xmode == 2) {   // column-major X staged by lines (the handle's second phased plan); Y column-major as well
             if (g_tune.nontemporal && g_tune.spmmv_ycol_nt)
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 2>), dim3((unsigned)A->pb_n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pl_ph_ptr, A->pl_g0, A->pl_list_ptr, A->pl_lines, A->pl_col8));
+                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 2>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
+                                   QH_ARGS(A->pl.ph_ptr, A->pl.g0, A->pl.list_ptr, A->pl.lines, A->pl.col8));
             else if (g_tune.nontemporal)
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 2, 0, false>), dim3((unsigned)A->pb_n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pl_ph_ptr, A->pl_g0, A->pl_list_ptr, A->pl_lines, A->pl_col8));
+                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 2, 0, false>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
+                                   QH_ARGS(A->pl.ph_ptr, A->pl.g0, A->pl.list_ptr, A->pl.lines, A->pl.col8));
             else
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, false, true, CT, 8, MAXP, 2>), dim3((unsigned)A->pb_n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pl_ph_ptr, A->pl_g0, A->pl_list_ptr, A->pl_lines, A->pl_col8));
+                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, false, true, CT, 8, MAXP, 2>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
+                                   QH_ARGS(A->pl.ph_ptr, A->pl.g0, A->pl.list_ptr, A->pl.lines, A->pl.col8));
             return;
         }
     }
     if constexpr (sizeof(VT) == 8 && CT == 32 && MAXP == 4 && sizeof(IT) == 1) {
         if (g_tune.ablate >= 1 && !xcol && !ycol) {   // measurement only
-#define QH_ABL(N) case N: hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, false, CT, 8, MAXP, 0, N>), dim3((unsigned)A->pb_n_tiles), dim3(256), lds, st, \
-                           QH_ARGS(A->pb_ph_ptr, A->pb_g0, A->pb_list_ptr, A->pb_xrows, A->pb_col16)); break;
+#define QH_ABL(N) case N: hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, false, CT, 8, MAXP, 0, N>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st, \
+                           QH_ARGS(A->pb.ph_ptr, A->pb.g0, A->pb.list_ptr, A->pb.xrows, A->pb.col16)); break;
             switch (g_tune.ablate) { QH_ABL(1) QH_ABL(2) QH_ABL(4) QH_ABL(8) QH_ABL(17) QH_ABL(14) QH_ABL(3) QH_ABL(19) QH_ABL(32) QH_ABL(64) QH_ABL(78) default: break; }
 #undef QH_ABL
             return;
@@ -304,10 +304,10 @@ void launch_spmmv_quadph_m(const uspmv_dmat *A, const VT *X, VT *Y, long ld, boo
 // registers (measured slower, kept as "spmmv_xcol" 1), 2 = column-major X staged by 128-byte lines (needs the handle's line plan)
 template <typename VT, int B>
 bool launch_spmmv_quadph(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, int xmode, hipStream_t st) {
-    if (!A->pb || !A->pb_values || A->pb_ngp > 8 || !part_ok(A, 1)) return false;
+    if (!A->pb.on || !A->pb.values || A->pb.ngp > 8 || !part_ok(A, 1)) return false;
     if (A->part && xmode != 0) return false;                   // (the two-part form runs on the row-major plan only)
     if (xmode == 3) {
-        if (!A->pu || !ycol || !A->pu_col8 || A->pu_max_rows > 256) return false;
+        if (!A->pu.on || !ycol || !A->pu.col8 || A->pu.max_rows > 256) return false;
 #define QU_C(CTV) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, 4>(A, X, Y, ld, ycol, 3, st)
         if (A->C == 32) QU_C(32); else if (A->C == 64) QU_C(64); else if (A->C == 16) QU_C(16); else return false;
 #undef QU_C
@@ -315,14 +315,14 @@ bool launch_spmmv_quadph(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool 
     }
     if (xmode == 2) {
         constexpr int VW = 16 / (int)sizeof(VT);
-        if (!A->pl || !ycol || !A->pl_col8 || A->pl_max_rows > 256 || ld % VW != 0 || ((uintptr_t)X % 16) != 0) return false;
+        if (!A->pl.on || !ycol || !A->pl.col8 || A->pl.max_rows > 256 || ld % VW != 0 || ((uintptr_t)X % 16) != 0) return false;
 #define QL_C(CTV) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, 4>(A, X, Y, ld, ycol, 2, st)
         if (A->C == 32) QL_C(32); else if (A->C == 64) QL_C(64); else if (A->C == 16) QL_C(16); else return false;
 #undef QL_C
         return true;
     }
-    const int pieces = (A->pb_max_rows * 4 + 255) / 256;
-#define QH_C(CTV) do { if (pieces <= 4 && A->pb_idx8) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, 4>(A, X, Y, ld, ycol, xmode, st); \
+    const int pieces = (A->pb.max_rows * 4 + 255) / 256;
+#define QH_C(CTV) do { if (pieces <= 4 && A->pb.idx8) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, 4>(A, X, Y, ld, ycol, xmode, st); \
         else if (pieces <= 4) launch_spmmv_quadph_m<VT, unsigned short, B, CTV, 4>(A, X, Y, ld, ycol, xmode, st); \
         else if (pieces <= 8) launch_spmmv_quadph_m<VT, unsigned short, B, CTV, 8>(A, X, Y, ld, ycol, xmode, st); else return false; } while (0)
     if (A->C == 32) QH_C(32); else if (A->C == 64) QH_C(64); else if (A->C == 16) QH_C(16); else return false;
@@ -335,11 +335,11 @@ bool launch_spmmv_quadph(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool 
 namespace uspmv_dev {
 
 bool spmmv_phased(const uspmv_dmat *A, const double *X, double *Y, long ld, bool ycol, int xmode, hipStream_t st) {
-    if (xmode == 0 && g_tune.spmmv_stream > 0 && A->ps_desc && spmmv_stream(A, X, Y, ld, ycol, st)) return true;
+    if (xmode == 0 && g_tune.spmmv_stream > 0 && A->ps.desc && spmmv_stream(A, X, Y, ld, ycol, st)) return true;
     return launch_spmmv_quadph<double, 8>(A, X, Y, ld, ycol, xmode, st);
 }
 bool spmmv_phased(const uspmv_dmat *A, const float *X, float *Y, long ld, bool ycol, int xmode, hipStream_t st) {
-    if (xmode == 0 && g_tune.spmmv_stream > 0 && A->ps_desc && spmmv_stream(A, X, Y, ld, ycol, st)) return true;
+    if (xmode == 0 && g_tune.spmmv_stream > 0 && A->ps.desc && spmmv_stream(A, X, Y, ld, ycol, st)) return true;
     return launch_spmmv_quadph<float, 16>(A, X, Y, ld, ycol, xmode, st);
 }
 

@@ -296,13 +296,13 @@ __global__ void __launch_bounds__(256, 3) scs_spmmv_pstream2(const PhDesc *__res
 
 template <typename VT, int B>
 bool launch_pstream(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, hipStream_t st) {
-    if (!A->ps_desc || !A->ps_wg_ptr || A->ps_grid <= 0 || A->part || A->C != 32 || !A->pb_idx8 || A->pb_max_rows > 256 || A->pb_ngp > 8) return false;
+    if (!A->ps.desc || !A->ps.wg_ptr || A->ps.grid <= 0 || A->part || A->C != 32 || !A->pb.idx8 || A->pb.max_rows > 256 || A->pb.ngp > 8) return false;
     const size_t lds = 2 * 16384;
-    const bool per_tile = (int64_t)A->ps_grid == A->pb_n_tiles && A->ps_per_tile;
+    const bool per_tile = (int64_t)A->ps.grid == A->pb.n_tiles && A->ps.per_tile;
     // measurement aid: USPMV_STREAM_CLOCK=<file> -- every workgroup's start and end time (100 MHz counter) of THIS launch, written as text
     static const char *clock_file = getenv("USPMV_STREAM_CLOCK");
     long long *d_clock = nullptr;
-    if (clock_file && hipMalloc((void **)&d_clock, 16 * (size_t)A->ps_grid) != hipSuccess) d_clock = nullptr;
+    if (clock_file && hipMalloc((void **)&d_clock, 16 * (size_t)A->ps.grid) != hipSuccess) d_clock = nullptr;
     struct ClockOut {
         long long *d; int G; hipStream_t st; const char *file;
         ~ClockOut() {
@@ -318,10 +318,10 @@ bool launch_pstream(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol,
             }
             (void)hipFree(d);
         }
-    } clock_out{d_clock, A->ps_grid, st, clock_file};
-#define PS_ARGS (const PhDesc *)A->ps_desc, (const int *)A->ps_wg_ptr, (const VT *)A->pb_values, (const unsigned char *)A->pb_col16, (const int *)A->pb_xrows, X, Y, ld, \
-                (long)(A->n_chunks * A->C), (long)A->n_store, (const int *)A->bt_row_map, d_clock, per_tile ? g_tune.xcd_remap : 0
-#define PS_LAUNCH(NTV, YC, YN, AB) hipLaunchKernelGGL((scs_spmmv_pstream<VT, B, NTV, YC, YN, AB>), dim3((unsigned)A->ps_grid), dim3(256), lds, st, PS_ARGS)
+    } clock_out{d_clock, A->ps.grid, st, clock_file};
+#define PS_ARGS (const PhDesc *)A->ps.desc, (const int *)A->ps.wg_ptr, (const VT *)A->pb.values, (const unsigned char *)A->pb.col16, (const int *)A->pb.xrows, X, Y, ld, \
+                (long)(A->n_chunks * A->C), (long)A->n_store, (const int *)A->bt.row_map, d_clock, per_tile ? g_tune.xcd_remap : 0
+#define PS_LAUNCH(NTV, YC, YN, AB) hipLaunchKernelGGL((scs_spmmv_pstream<VT, B, NTV, YC, YN, AB>), dim3((unsigned)A->ps.grid), dim3(256), lds, st, PS_ARGS)
     if constexpr (sizeof(VT) == 8) {
         if (g_tune.ablate >= 1 && !ycol) {          // measurement only (results wrong by construction)
             switch (g_tune.ablate) {
@@ -338,8 +338,8 @@ bool launch_pstream(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol,
     const bool nt = g_tune.nontemporal != 0, ynt = nt && (!ycol || g_tune.spmmv_ycol_nt);
     if (g_tune.spmmv_stream_depth >= 2) {
         const size_t lds3 = 3 * 16384;
-#define PS2_LAUNCH(NTV, YC, YN) do { if (A->bt_row_map) hipLaunchKernelGGL((scs_spmmv_pstream2<VT, B, NTV, YC, YN, true>), dim3((unsigned)A->ps_grid), dim3(256), lds3, st, PS_ARGS); \
-                                     else hipLaunchKernelGGL((scs_spmmv_pstream2<VT, B, NTV, YC, YN, false>), dim3((unsigned)A->ps_grid), dim3(256), lds3, st, PS_ARGS); } while (0)
+#define PS2_LAUNCH(NTV, YC, YN) do { if (A->bt.row_map) hipLaunchKernelGGL((scs_spmmv_pstream2<VT, B, NTV, YC, YN, true>), dim3((unsigned)A->ps.grid), dim3(256), lds3, st, PS_ARGS); \
+                                     else hipLaunchKernelGGL((scs_spmmv_pstream2<VT, B, NTV, YC, YN, false>), dim3((unsigned)A->ps.grid), dim3(256), lds3, st, PS_ARGS); } while (0)
         if (nt) {
             if (ycol) { if (ynt) PS2_LAUNCH(true, true, true); else PS2_LAUNCH(true, true, false); }
             else PS2_LAUNCH(true, false, true);
@@ -350,7 +350,7 @@ bool launch_pstream(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol,
         return true;
     }
     if (nt && g_tune.spmmv_stream_waves >= 5) {
-#define PS_LAUNCH5(NTV, YC, YN) hipLaunchKernelGGL((scs_spmmv_pstream<VT, B, NTV, YC, YN, 0, 5>), dim3((unsigned)A->ps_grid), dim3(256), lds, st, PS_ARGS)
+#define PS_LAUNCH5(NTV, YC, YN) hipLaunchKernelGGL((scs_spmmv_pstream<VT, B, NTV, YC, YN, 0, 5>), dim3((unsigned)A->ps.grid), dim3(256), lds, st, PS_ARGS)
         if (ycol) { if (ynt) PS_LAUNCH5(true, true, true); else PS_LAUNCH5(true, true, false); }
         else PS_LAUNCH5(true, false, true);
 #undef PS_LAUNCH5
@@ -369,24 +369,19 @@ bool launch_pstream(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol,
 
 namespace uspmv_dev {
 
-void dmat_stream_release(uspmv_dmat *A) {
-    (void)hipFree(A->ps_desc); (void)hipFree(A->ps_wg_ptr);
-    A->ps_desc = nullptr; A->ps_wg_ptr = nullptr; A->ps_grid = 0; A->ps_n_desc = 0; A->ps_per_tile = false;
-}
-
 // The flat schedule of the handle's phased plan for `wgs_per_cu` persistent workgroups per CU: workgroup w walks tiles w, w + G, w + 2G, ...
 // (the whole grid moves through the matrix as one front, like the one-tile-per-workgroup launch), its descriptors contiguous.
 int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu) {
-    dmat_stream_release(A);
-    if (!A->pb || A->C != 32 || !A->pb_idx8 || A->pb_n_tiles <= 0 || wgs_per_cu <= 0) return USPMV_OK;
+    A->ps = {};
+    if (!A->pb.on || A->C != 32 || !A->pb.idx8 || A->pb.n_tiles <= 0 || wgs_per_cu <= 0) return USPMV_OK;
     int dev = 0, cus = 0;
     HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int64_t nt = A->pb_n_tiles;
+    const int64_t nt = A->pb.n_tiles;
     const bool per_tile = wgs_per_cu >= 99 && nt <= INT32_MAX;          // one tile per workgroup: only the phases of a tile are pipelined
     const int G = per_tile ? (int)nt : (int)std::min<int64_t>((int64_t)std::max(cus, 1) * std::min(wgs_per_cu, 5), nt);
     std::vector<int32_t> php((size_t)nt + 1), slot((size_t)nt), wgp((size_t)G + 1, 0);
-    HIP_TRY(hipMemcpy(php.data(), A->pb_ph_ptr, 4 * ((size_t)nt + 1), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(php.data(), A->pb.ph_ptr, 4 * ((size_t)nt + 1), hipMemcpyDeviceToHost));
     // workgroup w runs on XCD w % 8 (round-robin dispatch): with "spmmv_stream_xcd" the G / 8 workgroups of an XCD take CONSECUTIVE tiles of
     // every super-block of G tiles -- neighbouring tiles share most of their X rows, which then meet in one L2 -- otherwise tile t goes to
     // workgroup t % G
@@ -403,24 +398,21 @@ int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu) {
         if (pos > INT32_MAX - 8) return USPMV_OK;
     }
     wgp[(size_t)G] = (int32_t)pos;
-    int32_t *d_slot = nullptr;
-    hipError_t e = hipMalloc((void **)&d_slot, 4 * (size_t)nt);
-    if (e == hipSuccess) e = hipMemcpy(d_slot, slot.data(), 4 * (size_t)nt, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&A->ps_wg_ptr, 4 * ((size_t)G + 1));
-    if (e == hipSuccess) e = hipMemcpy(A->ps_wg_ptr, wgp.data(), 4 * ((size_t)G + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&A->ps_desc, sizeof(PhDesc) * (size_t)pos);
+    DeviceBuf<int32_t> d_slot;
+    hipError_t e = d_slot.upload(slot.data(), 4 * (size_t)nt);
+    if (e == hipSuccess) e = A->ps.wg_ptr.upload(wgp.data(), 4 * ((size_t)G + 1));
+    if (e == hipSuccess) e = A->ps.desc.alloc(sizeof(PhDesc) * (size_t)pos);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(stream_desc_fill, dim3(grid_for(nt, 256)), dim3(256), 0, nullptr, (long)nt, (long)A->n_chunks, A->chunk_lengths,
-                           (const unsigned *)A->pb_c16_ptrs, (const int *)A->pb_ph_ptr, (const int *)A->pb_g0, (const int *)A->pb_list_ptr, (const int *)d_slot, (PhDesc *)A->ps_desc);
+                           (const unsigned *)A->pb.c16_ptrs, (const int *)A->pb.ph_ptr, (const int *)A->pb.g0, (const int *)A->pb.list_ptr, (const int *)d_slot, (PhDesc *)A->ps.desc);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
-    (void)hipFree(d_slot);
     if (e != hipSuccess) {
-        dmat_stream_release(A);
+        A->ps = {};
         return uspmv::fail(USPMV_ERR_HIP, "uspmv_dmat_optimize_block: stream schedule: %s", hipGetErrorString(e));
     }
-    A->ps_grid = G; A->ps_n_desc = pos; A->ps_per_tile = per_tile;
+    A->ps.grid = G; A->ps.n_desc = pos; A->ps.per_tile = per_tile;
     return USPMV_OK;
 }
 

@@ -206,21 +206,21 @@ __global__ void __launch_bounds__(1024) scs_spmmv_sweep(const int wlog, const in
 
 template <typename VT, int B>
 int launch_bsw(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool xcol, bool ycol, hipStream_t st) {
-    const long W = 1L << A->bw_wlog;
+    const long W = 1L << A->bw.wlog;
     const int nbuf = (g_tune.sweep_nbuf == 2 && 2 * (size_t)W * 64 <= 160 * 1024) ? 2 : 1;
     const size_t lds = (size_t)nbuf * (size_t)W * 64;
-    const int threads = std::min<int>(A->bw_tile_rows, 1024);
-    const int rpl = A->bw_tile_rows / threads;
+    const int threads = std::min<int>(A->bw.tile_rows, 1024);
+    const int rpl = A->bw.tile_rows / threads;
     constexpr int VW = 16 / (int)sizeof(VT);
     if (xcol && (ld % VW != 0 || ((uintptr_t)X % 16) != 0 || W < 64 * VW)) return 1;
     if (((uintptr_t)X % 16) != 0 || ((uintptr_t)Y % 16) != 0) return 1;
-    const long x_rows = xcol ? ld : std::max<long>(A->bw_x_rows, ld);      // rows of X that exist (row-major: the caller's padded_vec_size)
+    const long x_rows = xcol ? ld : std::max<long>(A->bw.x_rows, ld);      // rows of X that exist (row-major: the caller's padded_vec_size)
 #define BSW_LAUNCH(XC, YC, NB, RP)                                                                                                    \
     do {                                                                                                                              \
         auto kfn = g_tune.nontemporal ? scs_spmmv_sweep<VT, B, true, XC, YC, NB, 4, RP> : scs_spmmv_sweep<VT, B, false, XC, YC, NB, 4, RP>; \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);       \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)A->bw_n_tiles), dim3(threads), lds, st, A->bw_wlog, A->bw_tile_ids, A->bw_win_ptr, A->bw_wins, \
-                           (const unsigned long long *)A->bw_cnt_off, A->bw_wave_off, A->bw_cnt, (const VT *)A->bw_vals, A->bw_idx, A->bw_pad, \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)A->bw.n_tiles), dim3(threads), lds, st, A->bw.wlog, A->bw.tile_ids, A->bw.win_ptr, A->bw.wins, \
+                           (const unsigned long long *)A->bw.cnt_off, A->bw.wave_off, A->bw.cnt, (const VT *)A->bw.vals, A->bw.idx, A->bw.pad, \
                            X, Y, ld, x_rows, (long)A->n_store, g_tune.sweep_remap);                                                   \
     } while (0)
 #define BSW_R(XC, YC, NB) do { if (rpl == 4) BSW_LAUNCH(XC, YC, NB, 4); else if (rpl == 2) BSW_LAUNCH(XC, YC, NB, 2); else BSW_LAUNCH(XC, YC, NB, 1); } while (0)
@@ -240,8 +240,8 @@ namespace uspmv_dev {
 
 template <typename VT>
 int launch_spmmv_sweep(const uspmv_dmat *A, const VT *X, VT *Y, int b, long ld, bool xcol, bool ycol, hipStream_t st) {
-    if (!A->bw || A->bw_b != b || A->part || A->bw_n_tiles != A->bw_all_tiles) return 1;
-    if (A->bw_n_tiles == 0) return USPMV_OK;
+    if (!A->bw.on || A->bw.b != b || A->part || A->bw.n_tiles != A->bw.all_tiles) return 1;
+    if (A->bw.n_tiles == 0) return USPMV_OK;
     if constexpr (sizeof(VT) == 8) { if (b == 8) return launch_bsw<VT, 8>(A, X, Y, ld, xcol, ycol, st); }
     else { if (b == 16) return launch_bsw<VT, 16>(A, X, Y, ld, xcol, ycol, st); }
     return 1;

@@ -507,19 +507,19 @@ int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, cons
     if (n_tiles == 0) return USPMV_OK;
     const int C = (int)A->C;
     const unsigned grid = (unsigned)n_tiles;
-    const bool elem = A->tlc_elem;
-    const size_t lds = (size_t)A->tlc_max_lines * (elem ? 1 : 16) * sizeof(VT);
-    const bool i12 = A->tlc_col12 != nullptr;                 // (12-bit local indices: uspmv_api.hip tlc_pack12)
-    const unsigned *iptrs = i12 ? A->tlc_c12_ptrs : A->tlc_c16_ptrs;
-    const unsigned short *idata = i12 ? (const unsigned short *)A->tlc_col12 : A->tlc_col16;
+    const bool elem = A->tlc.elem;
+    const size_t lds = (size_t)A->tlc.max_lines * (elem ? 1 : 16) * sizeof(VT);
+    const bool i12 = A->tlc.col12 != nullptr;                 // (12-bit local indices: uspmv_api.hip tlc_pack12)
+    const unsigned *iptrs = i12 ? A->tlc.c12_ptrs : A->tlc.c16_ptrs;
+    const unsigned short *idata = i12 ? (const unsigned short *)A->tlc.col12 : A->tlc.col16;
 #define TLC_LAUNCH(CTV, NTV, IDSV)                                                                                    \
     do {                                                                                                              \
         auto kfn = i12 ? scs_spmv_tlc<VT, CTV, NTV, IDSV, 0, true> : scs_spmv_tlc<VT, CTV, NTV, IDSV>;                \
         if (elem) kfn = i12 ? scs_spmv_tlc<VT, CTV, NTV, IDSV, 0, true, true> : scs_spmv_tlc<VT, CTV, NTV, IDSV, 0, false, true>; \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(A->tlc_tile_rows), lds, st, (long)A->n_chunks, C, A->chunk_ptrs,        \
-                           A->chunk_lengths, A->tlc_cols ? A->tlc_cols : A->col_idxs, (const VT *)(A->tlc_values ? A->tlc_values : A->values), x, y, A->tlc_line_ptr, A->tlc_lines,   \
-                           iptrs, idata, (long)A->tlc_x_len, tile_ids, g_tune.xcd_remap, A->n_store, StepArgs{}, (const int *)A->tlc_row_map);  \
+        hipLaunchKernelGGL(kfn, dim3(grid), dim3(A->tlc.tile_rows), lds, st, (long)A->n_chunks, C, A->chunk_ptrs,        \
+                           A->chunk_lengths, A->tlc.cols ? A->tlc.cols : A->col_idxs, (const VT *)(A->tlc.values ? A->tlc.values : A->values), x, y, A->tlc.line_ptr, A->tlc.lines,   \
+                           iptrs, idata, (long)A->tlc.x_len, tile_ids, g_tune.xcd_remap, A->n_store, StepArgs{}, (const int *)A->tlc.row_map);  \
     } while (0)
 #define TLC_LAUNCH_C(NTV, IDSV) do { if (C == 32) TLC_LAUNCH(32, NTV, IDSV); else TLC_LAUNCH(0, NTV, IDSV); } while (0)
     if (tile_ids) { if (g_tune.nontemporal) TLC_LAUNCH_C(true, true); else TLC_LAUNCH_C(false, true); }
@@ -534,19 +534,19 @@ template <typename VT>
 int launch_spmv_tlc_step(const uspmv_dmat *A, const int *step_ids, const StepArgs &sa, int sync, const VT *x, VT *y, hipStream_t st) {
     const long n = sync == 1 ? sa.n_early + sa.n_real + sa.n_cond : sa.n_real + sa.n_cond;
     if (n == 0) return USPMV_OK;
-    if (A->tlc_elem) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "one-launch distributed step: not on a plan over single x elements");
+    if (A->tlc.elem) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "one-launch distributed step: not on a plan over single x elements");
     const int C = (int)A->C;
-    const size_t lds = (size_t)A->tlc_max_lines * 16 * sizeof(VT);
-    const bool i12 = A->tlc_col12 != nullptr;
-    const unsigned *iptrs = i12 ? A->tlc_c12_ptrs : A->tlc_c16_ptrs;
-    const unsigned short *idata = i12 ? (const unsigned short *)A->tlc_col12 : A->tlc_col16;
+    const size_t lds = (size_t)A->tlc.max_lines * 16 * sizeof(VT);
+    const bool i12 = A->tlc.col12 != nullptr;
+    const unsigned *iptrs = i12 ? A->tlc.c12_ptrs : A->tlc.c16_ptrs;
+    const unsigned short *idata = i12 ? (const unsigned short *)A->tlc.col12 : A->tlc.col16;
 #define TLC_STEP(CTV, SY)                                                                                             \
     do {                                                                                                              \
         auto kfn = i12 ? scs_spmv_tlc<VT, CTV, true, true, SY, true> : scs_spmv_tlc<VT, CTV, true, true, SY>;         \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)n), dim3(A->tlc_tile_rows), lds, st, (long)A->n_chunks, C, A->chunk_ptrs,  \
-                           A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, A->tlc_line_ptr, A->tlc_lines,   \
-                           iptrs, idata, (long)A->tlc_x_len, step_ids, g_tune.xcd_remap, A->n_store, sa, (const int *)nullptr); \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)n), dim3(A->tlc.tile_rows), lds, st, (long)A->n_chunks, C, A->chunk_ptrs,  \
+                           A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, A->tlc.line_ptr, A->tlc.lines,   \
+                           iptrs, idata, (long)A->tlc.x_len, step_ids, g_tune.xcd_remap, A->n_store, sa, (const int *)nullptr); \
     } while (0)
     if (sync == 1) { if (C == 32) TLC_STEP(32, 1); else TLC_STEP(0, 1); }
     else { if (C == 32) TLC_STEP(32, 2); else TLC_STEP(0, 2); }
@@ -562,13 +562,13 @@ int launch_spmv_scs(const uspmv_dmat *A, const int *chunk_ids, long n_ids, const
     if (nwc == 0) return USPMV_OK;
     const int C = (int)A->C;
     const int block = g_tune.block;
-    if (!ids && A->sw && A->sw_tile_ids && !A->sw_idx_b && g_tune.sweep && !g_tune.ablate && g_tune.spmv_variant == 0 && ((uintptr_t)x % 16 == 0)) {
+    if (!ids && A->sw.on && A->sw.tile_ids && !A->sw.idx_b && g_tune.sweep && !g_tune.ablate && g_tune.spmv_variant == 0 && ((uintptr_t)x % 16 == 0)) {
         // column-window sweep over the tiles that qualify, lane-per-row gather kernel over the chunks that are left
         if (int rc = launch_spmv_sweep<VT>(A, x, y, st)) return rc;
-        return A->sw_n_rest ? launch_spmv_scs<VT>(A, A->sw_rest, (long)A->sw_n_rest, x, y, st) : USPMV_OK;
+        return A->sw.n_rest ? launch_spmv_scs<VT>(A, A->sw.rest, (long)A->sw.n_rest, x, y, st) : USPMV_OK;
     }
-    if (!ids && A->tlc && A->tlc_plan_id == 0 && g_tune.tlc && !g_tune.ablate && g_tune.spmv_variant == 0 && ((uintptr_t)x % 16 == 0))
-        return launch_spmv_tlc<VT>(A, nullptr, A->tlc_n_tiles, x, y, st);
+    if (!ids && A->tlc.on && A->tlc.plan_id == 0 && g_tune.tlc && !g_tune.ablate && g_tune.spmv_variant == 0 && ((uintptr_t)x % 16 == 0))
+        return launch_spmv_tlc<VT>(A, nullptr, A->tlc.n_tiles, x, y, st);
     if (!ids && C == 32 && g_tune.spmv_variant == 1) {
         const unsigned grid = grid_for(nwc * 64, block);
         if (g_tune.nontemporal)

@@ -326,27 +326,20 @@ int uspmv_dmat_upload(const uspmv_scs_t *s, uspmv_dmat_t **out) {
     if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_upload: layout-only struct (its entries already live on the device)");
     if (int rc = require_device()) return rc;
     auto *A = new uspmv_dmat;
-    A->C = s->C; A->n_chunks = s->n_chunks; A->n_elements = s->n_elements; A->dtype = s->dtype; A->owns = true;
+    A->C = s->C; A->n_chunks = s->n_chunks; A->n_elements = s->n_elements; A->dtype = s->dtype;
     A->n_store = (long)(s->n_chunks * s->C);
     const size_t vsz = s->dtype == USPMV_F64 ? 8 : 4;
-    void *cp = nullptr, *cl = nullptr, *ci = nullptr, *va = nullptr;
-    const size_t ne = (size_t)std::max<int64_t>(s->n_elements, 1);
-    hipError_t e;
-    if ((e = hipMalloc(&cp, sizeof(int32_t) * (size_t)(s->n_chunks + 1))) != hipSuccess ||
-        (e = hipMalloc(&cl, sizeof(int32_t) * (size_t)std::max<int64_t>(s->n_chunks, 1))) != hipSuccess ||
-        (e = hipMalloc(&ci, sizeof(int32_t) * ne)) != hipSuccess || (e = hipMalloc(&va, vsz * ne)) != hipSuccess) {
-        (void)hipFree(cp); (void)hipFree(cl); (void)hipFree(ci); (void)hipFree(va);
+    hipError_t e = A->own_arrays();
+    if (e != hipSuccess) {
         delete A;
         return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_upload: hipMalloc failed: %s", hipGetErrorString(e));
     }
-    A->chunk_ptrs = (const int32_t *)cp; A->chunk_lengths = (const int32_t *)cl;
-    A->col_idxs = (const int32_t *)ci; A->values = va;
-    e = hipMemcpy(cp, s->chunk_ptrs.data(), sizeof(int32_t) * (size_t)(s->n_chunks + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(cl, s->chunk_lengths.data(), sizeof(int32_t) * (size_t)s->n_chunks, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ci, s->col_idxs.data(), sizeof(int32_t) * (size_t)s->n_elements, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(va, s->values_ptr(), vsz * (size_t)s->n_elements, hipMemcpyHostToDevice);
+    e = hipMemcpy(A->own.chunk_ptrs, s->chunk_ptrs.data(), sizeof(int32_t) * (size_t)(s->n_chunks + 1), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(A->own.chunk_lengths, s->chunk_lengths.data(), sizeof(int32_t) * (size_t)s->n_chunks, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(A->own.col_idxs, s->col_idxs.data(), sizeof(int32_t) * (size_t)s->n_elements, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(A->own.values, s->values_ptr(), vsz * (size_t)s->n_elements, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        uspmv_dmat_free(A);
+        delete A;
         return uspmv::fail(USPMV_ERR_HIP, "uspmv_dmat_upload: hipMemcpy failed: %s", hipGetErrorString(e));
     }
     *out = A;
@@ -362,7 +355,6 @@ int uspmv_dmat_wrap(int64_t C, int64_t n_chunks, int64_t n_elements, int dtype, 
     auto *A = new uspmv_dmat;
     A->C = C; A->n_chunks = n_chunks; A->n_elements = n_elements; A->dtype = dtype; A->n_store = (long)(n_chunks * C);
     A->chunk_ptrs = d_chunk_ptrs; A->chunk_lengths = d_chunk_lengths; A->col_idxs = d_col_idxs; A->values = d_values;
-    A->owns = false;
     *out = A;
     return USPMV_OK;
 }
@@ -383,48 +375,39 @@ int uspmv_convert_to_scs_device(const uspmv_coo_t *m, int64_t C, int64_t sigma, 
     std::vector<int32_t> rs32(row_start.begin(), row_start.end());
     const int32_t *row_map = fixed_permutation ? fixed_permutation : s->old_to_new_idx.data();
     auto *A = new uspmv_dmat;
-    A->C = s->C; A->n_chunks = s->n_chunks; A->n_elements = s->n_elements; A->dtype = dtype; A->owns = true;
+    A->C = s->C; A->n_chunks = s->n_chunks; A->n_elements = s->n_elements; A->dtype = dtype;
     A->n_store = (long)(s->n_chunks * s->C);
     const size_t vsz = dtype == USPMV_F64 ? 8 : 4;
     const size_t ne = (size_t)std::max<int64_t>(s->n_elements, 1), nz = (size_t)std::max<int64_t>(m->nnz, 1);
-    void *cp = nullptr, *cl = nullptr, *ci = nullptr, *va = nullptr;
-    int32_t *dI = nullptr, *dJ = nullptr, *drs = nullptr, *dmap = nullptr, *dperm = nullptr;
-    double *dV = nullptr;
-    hipError_t e = hipSuccess;
-    auto up = [&](const void *h, size_t bytes, void **d) {
-        if (e != hipSuccess) return;
-        e = hipMalloc(d, bytes ? bytes : 4);
-        if (e == hipSuccess && bytes) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-    };
-    up(s->chunk_ptrs.data(), 4 * s->chunk_ptrs.size(), &cp);
-    up(s->chunk_lengths.data(), 4 * s->chunk_lengths.size(), &cl);
-    if (e == hipSuccess) e = hipMalloc(&ci, 4 * ne);
-    if (e == hipSuccess) e = hipMalloc(&va, vsz * ne);
+    hipError_t e = A->own_arrays();
+    void *cp = A->own.chunk_ptrs, *ci = A->own.col_idxs, *va = A->own.values;
+    DeviceBuf<int32_t> dI, dJ, drs, dmap, dperm;
+    DeviceBuf<double> dV;
+    if (e == hipSuccess) e = hipMemcpy(cp, s->chunk_ptrs.data(), 4 * s->chunk_ptrs.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(A->own.chunk_lengths, s->chunk_lengths.data(), 4 * s->chunk_lengths.size(), hipMemcpyHostToDevice);
     // padding: value 0, column 0 -- which permute_scs_cols maps like any other local column (code/utilities.hpp:1820-1826)
     const int pad_col = (permute_cols && m->n_rows > 0) ? s->old_to_new_idx[0] : 0;
     if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)ci, pad_col, ne, nullptr);
     if (e == hipSuccess) e = hipMemsetAsync(va, 0, vsz * ne, nullptr);
-    up(m->I.data(), 4 * (size_t)m->nnz, (void **)&dI);
-    up(m->J.data(), 4 * (size_t)m->nnz, (void **)&dJ);
-    up(m->values.data(), 8 * (size_t)m->nnz, (void **)&dV);
-    up(rs32.data(), 4 * rs32.size(), (void **)&drs);
-    up(row_map, 4 * (size_t)m->n_rows, (void **)&dmap);
-    if (permute_cols) up(s->old_to_new_idx.data(), 4 * (size_t)m->n_rows, (void **)&dperm);
-    A->chunk_ptrs = (const int32_t *)cp; A->chunk_lengths = (const int32_t *)cl; A->col_idxs = (const int32_t *)ci; A->values = va;
+    if (e == hipSuccess) e = dI.upload(m->I.data(), 4 * (size_t)m->nnz);
+    if (e == hipSuccess) e = dJ.upload(m->J.data(), 4 * (size_t)m->nnz);
+    if (e == hipSuccess) e = dV.upload(m->values.data(), 8 * (size_t)m->nnz);
+    if (e == hipSuccess) e = drs.upload(rs32.data(), 4 * rs32.size());
+    if (e == hipSuccess) e = dmap.upload(row_map, 4 * (size_t)m->n_rows);
+    if (e == hipSuccess && permute_cols) e = dperm.upload(s->old_to_new_idx.data(), 4 * (size_t)m->n_rows);
     if (e == hipSuccess && m->nnz > 0) {
         const unsigned grid = (unsigned)((nz + 255) / 256);
         if (dtype == USPMV_F64)
-            hipLaunchKernelGGL(scs_fill_kernel<double>, dim3(grid), dim3(256), 0, nullptr, (long)m->nnz, (int)C, (int)m->n_rows, dI, dJ, dV,
-                               drs, dmap, dperm, (const int *)cp, (int *)ci, (double *)va);
+            hipLaunchKernelGGL(scs_fill_kernel<double>, dim3(grid), dim3(256), 0, nullptr, (long)m->nnz, (int)C, (int)m->n_rows, dI.get(), dJ.get(), dV.get(),
+                               drs.get(), dmap.get(), dperm.get(), (const int *)cp, (int *)ci, (double *)va);
         else
-            hipLaunchKernelGGL(scs_fill_kernel<float>, dim3(grid), dim3(256), 0, nullptr, (long)m->nnz, (int)C, (int)m->n_rows, dI, dJ, dV,
-                               drs, dmap, dperm, (const int *)cp, (int *)ci, (float *)va);
+            hipLaunchKernelGGL(scs_fill_kernel<float>, dim3(grid), dim3(256), 0, nullptr, (long)m->nnz, (int)C, (int)m->n_rows, dI.get(), dJ.get(), dV.get(),
+                               drs.get(), dmap.get(), dperm.get(), (const int *)cp, (int *)ci, (float *)va);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    (void)hipFree(dI); (void)hipFree(dJ); (void)hipFree(dV); (void)hipFree(drs); (void)hipFree(dmap); (void)hipFree(dperm);
     if (e != hipSuccess) {
-        uspmv_dmat_free(A); delete s;
+        delete A; delete s;
         return uspmv::fail(USPMV_ERR_HIP, "uspmv_convert_to_scs_device: %s", hipGetErrorString(e));
     }
     *layout = s;
@@ -435,8 +418,8 @@ int uspmv_convert_to_scs_device(const uspmv_coo_t *m, int64_t C, int64_t sigma, 
 int uspmv_dmat_plan_addresses(const uspmv_dmat_t *A, uint64_t addr[8]) {
     if (!A || !addr) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_plan_addresses: NULL argument");
     const uspmv_dmat *M = A->alt ? A->alt : A;
-    addr[0] = (uint64_t)(uintptr_t)M->tlc_col16; addr[1] = (uint64_t)(uintptr_t)M->tlc_lines; addr[2] = (uint64_t)(uintptr_t)M->tlc_line_ptr;
-    addr[3] = (uint64_t)(uintptr_t)M->tlc_c16_ptrs; addr[4] = (uint64_t)(uintptr_t)M->values; addr[5] = (uint64_t)(uintptr_t)M->col_idxs;
+    addr[0] = (uint64_t)(uintptr_t)M->tlc.col16.get(); addr[1] = (uint64_t)(uintptr_t)M->tlc.lines.get(); addr[2] = (uint64_t)(uintptr_t)M->tlc.line_ptr.get();
+    addr[3] = (uint64_t)(uintptr_t)M->tlc.c16_ptrs.get(); addr[4] = (uint64_t)(uintptr_t)M->values; addr[5] = (uint64_t)(uintptr_t)M->col_idxs;
     addr[6] = (uint64_t)(uintptr_t)M->chunk_ptrs; addr[7] = (uint64_t)(uintptr_t)M->chunk_lengths;
     return USPMV_OK;
 }
@@ -460,19 +443,9 @@ int uspmv_dmat_download(const uspmv_dmat_t *A, int32_t *chunk_ptrs, int32_t *chu
     return USPMV_OK;
 }
 
-static void sw_release(uspmv_dmat_t *A);
 static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who);
 static int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, const uspmv_scs_t *sB, int wlog, int tile_rows,
                               int64_t *n_tiles, int64_t *n_sweep, const char *who);
-static void tlc_release(uspmv_dmat_t *A) {
-    (void)hipFree(A->tlc_line_ptr); (void)hipFree(A->tlc_lines); (void)hipFree(A->tlc_c16_ptrs); (void)hipFree(A->tlc_col16);
-    (void)hipFree(A->tlc_c12_ptrs); (void)hipFree(A->tlc_col12);
-    A->tlc_line_ptr = A->tlc_lines = nullptr; A->tlc_c16_ptrs = nullptr; A->tlc_col16 = nullptr; A->tlc_c12_ptrs = A->tlc_col12 = nullptr;
-    A->tlc_elem = false;
-    (void)hipFree(A->tlc_values); (void)hipFree(A->tlc_row_map); (void)hipFree(A->tlc_cols); A->tlc_values = nullptr; A->tlc_row_map = A->tlc_cols = nullptr;
-    A->tlc = false; A->tlc_plan_id = 0;
-}
-
 // rows per tile of the next tile-local-column plan (g_tune.tlc_tile_rows = 0: by kind)
 static int plan_tile_rows(bool ap) { return g_tune.tlc_tile_rows ? g_tune.tlc_tile_rows : (ap ? 512 : 256); }
 
@@ -509,15 +482,15 @@ static int measured_tile_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, c
         if (kv.first.nc == A->n_chunks && kv.first.ne == A->n_elements && kv.first.ne2 == ne2 && kv.first.C == A->C && kv.first.dtype == A->dtype && kv.first.ml == max_lines)
             return kv.second;
     const size_t vsz = A->dtype == USPMV_F64 ? 8 : 4;
-    void *x = nullptr, *y = nullptr;
+    DeviceBuf<void> x, y;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int best = 0;
     auto done = [&]() {
-        (void)hipFree(x); (void)hipFree(y);
+        x.reset(); y.reset();
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
-        if (A->tlc) tlc_release(A);
-        if (B && B->tlc) tlc_release(B);
+        A->tlc = {};
+        if (B) B->tlc = {};
     };
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { done(); (void)hipGetLastError(); return 0; }
     // the size to beat: 256 rows for one struct, 512 for an ap[dp_sp] pair (two entry streams per row, profiles/r02/ap_tile_rows.txt);
@@ -534,11 +507,11 @@ static int measured_tile_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, c
             if (!beaten) break;
         }
         int64_t nt = 0, ns = 0;
-        if (device_plan_install_rows(A, B, max_lines, R, &nt, &ns, who) != USPMV_OK || !A->tlc) { (void)hipGetLastError(); continue; }
+        if (device_plan_install_rows(A, B, max_lines, R, &nt, &ns, who) != USPMV_OK || !A->tlc.on) { (void)hipGetLastError(); continue; }
         if (!tile_rows_accept(nt, ns)) continue;
         if (!x) {
-            const size_t xb = vsz * (size_t)std::max<int64_t>(A->tlc_x_len + 16, 16), yb = vsz * (size_t)std::max<int64_t>(A->n_chunks * A->C, 1);
-            if (hipMalloc(&x, xb) != hipSuccess || hipMalloc(&y, yb) != hipSuccess || hipMemset(x, 0, xb) != hipSuccess) { done(); (void)hipGetLastError(); return 0; }
+            const size_t xb = vsz * (size_t)std::max<int64_t>(A->tlc.x_len + 16, 16), yb = vsz * (size_t)std::max<int64_t>(A->n_chunks * A->C, 1);
+            if (x.zeros(xb) != hipSuccess || y.alloc(yb) != hipSuccess) { done(); (void)hipGetLastError(); return 0; }
         }
         float ms = 0;
         bool ok = true;
@@ -546,14 +519,14 @@ static int measured_tile_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, c
             ok = hipEventRecord(e0, nullptr) == hipSuccess;
             for (int l = 0; l < 3 && ok; ++l) {
                 if (B) ok = launch_spmv_ap(A, B, (const double *)x, nullptr, (double *)y, nullptr) == USPMV_OK;
-                else ok = (A->dtype == USPMV_F64 ? launch_spmv_tlc<double>(A, nullptr, (long)A->tlc_n_tiles, (const double *)x, (double *)y, nullptr)
-                                                 : launch_spmv_tlc<float>(A, nullptr, (long)A->tlc_n_tiles, (const float *)x, (float *)y, nullptr)) == USPMV_OK;
+                else ok = (A->dtype == USPMV_F64 ? launch_spmv_tlc<double>(A, nullptr, (long)A->tlc.n_tiles, (const double *)x, (double *)y, nullptr)
+                                                 : launch_spmv_tlc<float>(A, nullptr, (long)A->tlc.n_tiles, (const float *)x, (float *)y, nullptr)) == USPMV_OK;
             }
             ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
         }
         if (!ok) { (void)hipGetLastError(); continue; }
         if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] measured tile size%s: %d rows -> %.4f ms per SpMV (%lld of %lld tiles staged, %d lines at most)\n", B ? " (ap pair)" : "",
-                                             R, ms / 3, (long long)ns, (long long)nt, A->tlc_max_lines);
+                                             R, ms / 3, (long long)ns, (long long)nt, A->tlc.max_lines);
         tmin[slot] = tmin[slot] > 0 ? std::min(tmin[slot], ms) : ms;
     }
     // the base size unless another one is more than 3 % ahead of it (the fastest of those that are)
@@ -575,7 +548,7 @@ static int measured_tile_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, c
 // adaptive-precision kernels, uspmv_dmat_plan_download and the plan digests read it).  cl: the chunk lengths when the caller has them on
 // the host, else they are copied back (4 bytes per chunk).
 static int tlc_pack12(uspmv_dmat_t *A, const std::vector<int32_t> *cl, const char *who) {
-    if (!A->tlc || !g_tune.tlc_idx12 || (A->tlc_elem ? A->tlc_max_lines > 4096 : A->tlc_max_lines > 256) || A->C < 2 || A->C % 2 != 0 || A->n_chunks < 1) return USPMV_OK;
+    if (!A->tlc.on || !g_tune.tlc_idx12 || (A->tlc.elem ? A->tlc.max_lines > 4096 : A->tlc.max_lines > 256) || A->C < 2 || A->C % 2 != 0 || A->n_chunks < 1) return USPMV_OK;
     std::vector<int32_t> own;
     if (!cl || (int64_t)cl->size() != A->n_chunks) {
         own.resize((size_t)A->n_chunks);
@@ -592,13 +565,12 @@ static int tlc_pack12(uspmv_dmat_t *A, const std::vector<int32_t> *cl, const cha
         if (tot > (int64_t)UINT32_MAX) return USPMV_OK;          // (too large for 32-bit offsets: the 16-bit array serves)
     }
     p12[(size_t)nc] = (uint32_t)tot;
-    hipError_t e = hipMalloc((void **)&A->tlc_c12_ptrs, 4 * ((size_t)nc + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&A->tlc_col12, 4 * (size_t)std::max<int64_t>(tot, 1));
-    if (e == hipSuccess) e = hipMemcpy(A->tlc_c12_ptrs, p12.data(), 4 * ((size_t)nc + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess && uspmv_dev::launch_plan_pack12(A, A->tlc_c16_ptrs, A->tlc_col16, A->tlc_c12_ptrs, A->tlc_col12, nullptr) != USPMV_OK) e = hipErrorUnknown;
+    hipError_t e = A->tlc.c12_ptrs.upload(p12.data(), 4 * ((size_t)nc + 1));
+    if (e == hipSuccess) e = A->tlc.col12.alloc(4 * (size_t)std::max<int64_t>(tot, 1));
+    if (e == hipSuccess && uspmv_dev::launch_plan_pack12(A, A->tlc.c16_ptrs, A->tlc.col16, A->tlc.c12_ptrs, A->tlc.col12, nullptr) != USPMV_OK) e = hipErrorUnknown;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
-        (void)hipFree(A->tlc_c12_ptrs); (void)hipFree(A->tlc_col12); A->tlc_c12_ptrs = A->tlc_col12 = nullptr;
+        A->tlc.c12_ptrs.reset(); A->tlc.col12.reset();
         return uspmv::fail(USPMV_ERR_HIP, "%s: packing the local indices to 12 bits failed: %s", who, hipGetErrorString(e));
     }
     // Keep it?  Rows of a dozen entries gain or lose a per cent either way (one more load instruction per row for an odd last group), long
@@ -606,9 +578,7 @@ static int tlc_pack12(uspmv_dmat_t *A, const std::vector<int32_t> *cl, const cha
     // 0.700 on a fast one; 304^3 between -15 % and +2 %).  The rule is a fixed one -- mean row length >= 8 -- and not a timing on the spot
     // (which was built first): a bench run, its counter passes and its profiler run must execute the same kernel, and a 1-2 % verdict
     // flips under a profiler's overhead.  "tlc_idx12" 2 keeps it regardless, 0 never builds it.
-    if (g_tune.tlc_idx12 != 2 && (double)A->n_elements < 8.0 * (double)(nc * C)) {
-        (void)hipFree(A->tlc_c12_ptrs); (void)hipFree(A->tlc_col12); A->tlc_c12_ptrs = A->tlc_col12 = nullptr;
-    }
+    if (g_tune.tlc_idx12 != 2 && (double)A->n_elements < 8.0 * (double)(nc * C)) { A->tlc.c12_ptrs.reset(); A->tlc.col12.reset(); }
     return USPMV_OK;
 }
 
@@ -636,7 +606,7 @@ int uspmv_dmat_optimize(uspmv_dmat_t *A, const uspmv_scs_t *s, int max_lines, in
     if (A->C != s->C || A->n_chunks != s->n_chunks || A->dtype != s->dtype)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize: handle and host struct do not describe the same matrix");
     if (int rc = require_device()) return rc;
-    if (A->tlc) tlc_release(A);
+    A->tlc = {};
     if (A->alt) { uspmv_dmat_free(A->alt); A->alt = nullptr; }
     if (s->C < 32 && 32 % s->C == 0 && g_tune.rechunk) {
         // narrow chunks (incl. crs = C 1): run on an internal C = 32 re-chunking with the same row order
@@ -669,7 +639,7 @@ int uspmv_dmat_optimize(uspmv_dmat_t *A, const uspmv_scs_t *s, int max_lines, in
     if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
     if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] tlc plan: tile_rows=%d tiles=%lld staged=%lld max_lines=%d lines_total=%zu col16=%zu\n",
                                          p.tile_rows, (long long)p.n_tiles, (long long)p.n_staged_tiles, p.max_lines_used, p.tile_lines.size(), p.col16.size());
-    if (A->sw) sw_release(A);
+    A->sw = {};
     bool elem = false;
     if (((!own_budget && (!p.valid || p.n_staged_tiles * 10 < p.n_tiles * 9)) || g_tune.tlc_elem == 2) && g_tune.tlc_elem && uspmv_dev::tl_measure_off == 0) {   // (2: measurement aid, always try)
         // columns scattered over many lines (x in a numbering that is only loosely related to the rows'): the line plan leaves a tenth of the tiles or
@@ -727,30 +697,25 @@ int uspmv_dmat_optimize(uspmv_dmat_t *A, const uspmv_scs_t *s, int max_lines, in
         // when it covers at least half of the rows.
         int64_t swt = 0, sws = 0;
         if (int rc = sweep_plan_install(A, nullptr, s, nullptr, 0, 0, &swt, &sws, "uspmv_dmat_optimize")) return rc;
-        if (A->sw && sws * 2 >= swt) return USPMV_OK;
-        if (A->sw) sw_release(A);
+        if (A->sw.on && sws * 2 >= swt) return USPMV_OK;
+        A->sw = {};
     }
     if (!p.valid) return USPMV_OK;                              // nothing worth staging: plain kernel stays
-    auto up = [&](const void *h, size_t bytes, void **d) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes ? bytes : 4);
-        if (e == hipSuccess && bytes) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4, (void **)&A->tlc_line_ptr);
-    if (e == hipSuccess) e = up(p.tile_lines.data(), p.tile_lines.size() * 4, (void **)&A->tlc_lines);
-    if (e == hipSuccess) e = up(p.c16_ptrs.data(), p.c16_ptrs.size() * 4, (void **)&A->tlc_c16_ptrs);
-    if (e == hipSuccess) e = up(p.col16.data(), p.col16.size() * 2, (void **)&A->tlc_col16);
+    hipError_t e = A->tlc.line_ptr.upload(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4);
+    if (e == hipSuccess) e = A->tlc.lines.upload(p.tile_lines.data(), p.tile_lines.size() * 4);
+    if (e == hipSuccess) e = A->tlc.c16_ptrs.upload(p.c16_ptrs.data(), p.c16_ptrs.size() * 4);
+    if (e == hipSuccess) e = A->tlc.col16.upload(p.col16.data(), p.col16.size() * 2);
     if (e == hipSuccess && reordered) {
-        e = up(rr.values_ptr(), (size_t)rr.n_elements * (rr.dtype == USPMV_F64 ? 8 : 4), &A->tlc_values);
-        if (e == hipSuccess) e = up(rr_map.data(), rr_map.size() * 4, (void **)&A->tlc_row_map);
-        if (e == hipSuccess && p.n_staged_tiles < p.n_tiles) e = up(rr.col_idxs.data(), (size_t)rr.n_elements * 4, (void **)&A->tlc_cols);
+        e = A->tlc.values.upload(rr.values_ptr(), (size_t)rr.n_elements * (rr.dtype == USPMV_F64 ? 8 : 4));
+        if (e == hipSuccess) e = A->tlc.row_map.upload(rr_map.data(), rr_map.size() * 4);
+        if (e == hipSuccess && p.n_staged_tiles < p.n_tiles) e = A->tlc.cols.upload(rr.col_idxs.data(), (size_t)rr.n_elements * 4);
     }
     if (e != hipSuccess) {
-        tlc_release(A);
+        A->tlc = {};
         return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize: device copy failed: %s", hipGetErrorString(e));
     }
-    A->tlc = true; A->tlc_tile_rows = p.tile_rows; A->tlc_max_lines = p.max_lines_used; A->tlc_x_len = p.x_len_min; A->tlc_n_tiles = p.n_tiles;
-    A->tlc_staged = p.n_staged_tiles; A->tlc_elem = elem;
+    A->tlc.on = true; A->tlc.tile_rows = p.tile_rows; A->tlc.max_lines = p.max_lines_used; A->tlc.x_len = p.x_len_min; A->tlc.n_tiles = p.n_tiles;
+    A->tlc.staged = p.n_staged_tiles; A->tlc.elem = elem;
     return tlc_pack12(A, &s->chunk_lengths, "uspmv_dmat_optimize");
 }
 
@@ -781,18 +746,18 @@ static int device_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, 
     }
     const int R0 = plan_tile_rows(B != nullptr);
     if (int rc = device_plan_install_rows(A, B, max_lines, R0, n_tiles, n_staged, who)) return rc;
-    if (B || !A->tlc || !tile_rows_grow(R0, A->tlc_max_lines)) return USPMV_OK;
+    if (B || !A->tlc.on || !tile_rows_grow(R0, A->tlc.max_lines)) return USPMV_OK;
     for (int R : {1024, 512}) {
         int64_t nt = 0, ns = 0;
         if (int rc = device_plan_install_rows(A, nullptr, max_lines, R, &nt, &ns, who)) return rc;
-        if (A->tlc && tile_rows_accept(nt, ns)) { if (n_tiles) *n_tiles = nt; if (n_staged) *n_staged = ns; return USPMV_OK; }
+        if (A->tlc.on && tile_rows_accept(nt, ns)) { if (n_tiles) *n_tiles = nt; if (n_staged) *n_staged = ns; return USPMV_OK; }
     }
     return device_plan_install_rows(A, nullptr, max_lines, R0, n_tiles, n_staged, who);
 }
 
 static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, const int R, int64_t *n_tiles, int64_t *n_staged, const char *who) {
-    if (A->tlc) tlc_release(A);
-    if (B && B->tlc) tlc_release(B);
+    A->tlc = {};
+    if (B) B->tlc = {};
     if (n_tiles) *n_tiles = 0;
     if (n_staged) *n_staged = 0;
     const int64_t C = A->C, nc = A->n_chunks;
@@ -810,11 +775,10 @@ static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_li
         HIP_TRY(hipMemcpy(cl.data(), B->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
         if (!c16_offsets(cl, C, &c16p_b, &tot16_b)) return USPMV_OK;
     }
-    int *d_n = nullptr, *d_max = nullptr;
-    hipError_t e = hipMalloc((void **)&d_n, 4 * (size_t)nt);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_max, 4);
-    if (e == hipSuccess) e = hipMemset(d_max, 0, 4);
-    if (e != hipSuccess) { (void)hipFree(d_n); (void)hipFree(d_max); return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e)); }
+    DeviceBuf<int> d_n, d_max;
+    hipError_t e = d_n.alloc(4 * (size_t)nt);
+    if (e == hipSuccess) e = d_max.zeros(4);
+    if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
     int rc = launch_plan_count(A, (long)nt, max_lines, d_n, d_max, nullptr, B, R);
     std::vector<int32_t> lp((size_t)nt + 1, 0);
     int max_col = 0;
@@ -823,7 +787,7 @@ static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_li
         if (e == hipSuccess) e = hipMemcpy(&max_col, d_max, 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
-    (void)hipFree(d_n); (void)hipFree(d_max);
+    d_n.reset(); d_max.reset();
     if (rc) return rc;
     int64_t staged = 0, total = 0;
     int used = 0;
@@ -837,34 +801,29 @@ static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_li
     if (n_tiles) *n_tiles = nt;
     if (n_staged) *n_staged = staged;
     if (staged == 0) return USPMV_OK;
-    e = hipMalloc((void **)&A->tlc_line_ptr, 4 * ((size_t)nt + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&A->tlc_lines, 4 * (size_t)std::max<int64_t>(total, 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&A->tlc_c16_ptrs, 4 * ((size_t)nc + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&A->tlc_col16, 2 * (size_t)std::max<int64_t>(tot16, 1));
-    if (e == hipSuccess) e = hipMemset(A->tlc_col16, 0, 2 * (size_t)std::max<int64_t>(tot16, 1));   // padded slots: index 0
-    if (e == hipSuccess) e = hipMemcpy(A->tlc_line_ptr, lp.data(), 4 * ((size_t)nt + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(A->tlc_c16_ptrs, c16p.data(), 4 * ((size_t)nc + 1), hipMemcpyHostToDevice);
+    e = A->tlc.line_ptr.upload(lp.data(), 4 * ((size_t)nt + 1));
+    if (e == hipSuccess) e = A->tlc.lines.alloc(4 * (size_t)std::max<int64_t>(total, 1));
+    if (e == hipSuccess) e = A->tlc.c16_ptrs.upload(c16p.data(), 4 * ((size_t)nc + 1));
+    if (e == hipSuccess) e = A->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16, 1));   // padded slots: index 0
     if (B) {
-        if (e == hipSuccess) e = hipMalloc((void **)&B->tlc_c16_ptrs, 4 * ((size_t)nc + 1));
-        if (e == hipSuccess) e = hipMalloc((void **)&B->tlc_col16, 2 * (size_t)std::max<int64_t>(tot16_b, 1));
-        if (e == hipSuccess) e = hipMemset(B->tlc_col16, 0, 2 * (size_t)std::max<int64_t>(tot16_b, 1));
-        if (e == hipSuccess) e = hipMemcpy(B->tlc_c16_ptrs, c16p_b.data(), 4 * ((size_t)nc + 1), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = B->tlc.c16_ptrs.upload(c16p_b.data(), 4 * ((size_t)nc + 1));
+        if (e == hipSuccess) e = B->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16_b, 1));
     }
-    if (e == hipSuccess && launch_plan_write(A, (long)nt, A->tlc_line_ptr, A->tlc_c16_ptrs, A->tlc_lines, A->tlc_col16, nullptr, B,
-                                             B ? B->tlc_c16_ptrs : nullptr, B ? B->tlc_col16 : nullptr, R) != USPMV_OK)
+    if (e == hipSuccess && launch_plan_write(A, (long)nt, A->tlc.line_ptr, A->tlc.c16_ptrs, A->tlc.lines, A->tlc.col16, nullptr, B,
+                                             B ? B->tlc.c16_ptrs : nullptr, B ? B->tlc.col16 : nullptr, R) != USPMV_OK)
         e = hipErrorUnknown;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
-        tlc_release(A);
-        if (B) tlc_release(B);
+        A->tlc = {};
+        if (B) B->tlc = {};
         return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     static uint64_t next_dev_plan_id = (uint64_t)1 << 40;
     const uint64_t id = B ? next_dev_plan_id++ : 0;
     for (uspmv_dmat_t *M : {A, B}) {
         if (!M) continue;
-        M->tlc = true; M->tlc_tile_rows = R; M->tlc_max_lines = used; M->tlc_x_len = (int64_t)max_col + 1; M->tlc_n_tiles = nt;
-        M->tlc_staged = staged; M->tlc_plan_id = id;
+        M->tlc.on = true; M->tlc.tile_rows = R; M->tlc.max_lines = used; M->tlc.x_len = (int64_t)max_col + 1; M->tlc.n_tiles = nt;
+        M->tlc.staged = staged; M->tlc.plan_id = id;
     }
     if (!B) return tlc_pack12(A, nullptr, who);
     return USPMV_OK;
@@ -873,17 +832,17 @@ static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_li
 // as uspmv_dmat_optimize[_ap]: when the tile-local-column plan stages fewer than half of the tiles (wide, irregular rows), try the
 // column-window sweep -- built on the device as well -- and let it take over when it covers at least half of the tiles
 static int device_sweep_if_irregular(uspmv_dmat_t *A, uspmv_dmat_t *B, int64_t * /*n_tiles*/, int64_t * /*n_staged*/, const char *who) {
-    if (A->sw) sw_release(A);
-    if (B && B->sw) sw_release(B);
-    if (!g_tune.sweep || (A->tlc && A->tlc_staged * 2 >= A->tlc_n_tiles)) return USPMV_OK;
+    A->sw = {};
+    if (B) B->sw = {};
+    if (!g_tune.sweep || (A->tlc.on && A->tlc.staged * 2 >= A->tlc.n_tiles)) return USPMV_OK;
     int64_t swt = 0, sws = 0;
     if (int rc = sweep_plan_install_device(A, B, 0, 0, &swt, &sws, who)) return rc;
-    if (A->sw && sws * 2 >= swt) {
-        if (A->tlc) tlc_release(A);         // (n_tiles / n_staged keep describing the tile-local-column attempt, as in uspmv_dmat_optimize;
-        if (B && B->tlc) tlc_release(B);    //  uspmv_dmat_plan_info tells which plan the handle ended up with)
+    if (A->sw.on && sws * 2 >= swt) {
+        A->tlc = {};         // (n_tiles / n_staged keep describing the tile-local-column attempt, as in uspmv_dmat_optimize;
+        if (B) B->tlc = {};    //  uspmv_dmat_plan_info tells which plan the handle ended up with)
         return USPMV_OK;
     }
-    if (A->sw) { sw_release(A); if (B) sw_release(B); }
+    if (A->sw.on) { A->sw = {}; if (B) B->sw = {}; }
     return USPMV_OK;
 }
 
@@ -911,24 +870,19 @@ int uspmv_dmat_optimize_device(uspmv_dmat_t *A, int max_lines, int64_t *n_tiles,
         if (fits && (double)cur <= 1.25 * (double)std::max<int64_t>(last, 1) + 4096) {
             cp[(size_t)nc] = (int32_t)cur;
             auto *alt = new uspmv_dmat;
-            alt->C = 32; alt->n_chunks = nc; alt->n_elements = cur; alt->dtype = A->dtype; alt->owns = true;
+            alt->C = 32; alt->n_chunks = nc; alt->n_elements = cur; alt->dtype = A->dtype;
             alt->n_store = (long)(nc_old * C);              // y of the caller has only the original padded rows
             const size_t vsz = A->dtype == USPMV_F64 ? 8 : 4, ne = (size_t)std::max<int64_t>(cur, 1);
-            void *d_cp = nullptr, *d_cl = nullptr, *d_ci = nullptr, *d_va = nullptr;
-            hipError_t e = hipMalloc(&d_cp, 4 * ((size_t)nc + 1));
-            if (e == hipSuccess) e = hipMalloc(&d_cl, 4 * (size_t)nc);
-            if (e == hipSuccess) e = hipMalloc(&d_ci, 4 * ne);
-            if (e == hipSuccess) e = hipMalloc(&d_va, vsz * ne);
-            alt->chunk_ptrs = (const int32_t *)d_cp; alt->chunk_lengths = (const int32_t *)d_cl; alt->col_idxs = (const int32_t *)d_ci; alt->values = d_va;
-            if (e == hipSuccess) e = hipMemcpy(d_cp, cp.data(), 4 * ((size_t)nc + 1), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(d_cl, cl.data(), 4 * (size_t)nc, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemsetAsync(d_ci, 0, 4 * ne, nullptr);
-            if (e == hipSuccess) e = hipMemsetAsync(d_va, 0, vsz * ne, nullptr);
-            int rc = e == hipSuccess ? launch_rechunk32(A, (const int *)d_cp, (int *)d_ci, d_va, nullptr) : uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize_device: %s", hipGetErrorString(e));
+            hipError_t e = alt->own_arrays();
+            if (e == hipSuccess) e = hipMemcpy(alt->own.chunk_ptrs, cp.data(), 4 * ((size_t)nc + 1), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(alt->own.chunk_lengths, cl.data(), 4 * (size_t)nc, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemsetAsync(alt->own.col_idxs, 0, 4 * ne, nullptr);
+            if (e == hipSuccess) e = hipMemsetAsync(alt->own.values, 0, vsz * ne, nullptr);
+            int rc = e == hipSuccess ? launch_rechunk32(A, alt->chunk_ptrs, alt->own.col_idxs, alt->own.values, nullptr) : uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize_device: %s", hipGetErrorString(e));
             if (!rc) rc = device_plan_install(alt, nullptr, max_lines, n_tiles, n_staged, "uspmv_dmat_optimize_device");
             if (!rc) rc = device_sweep_if_irregular(alt, nullptr, n_tiles, n_staged, "uspmv_dmat_optimize_device");
             if (rc) { uspmv_dmat_free(alt); return rc; }
-            if (A->tlc) tlc_release(A);
+            A->tlc = {};
             A->alt = alt;
             return USPMV_OK;
         }
@@ -952,84 +906,58 @@ int uspmv_dmat_plan_download(const uspmv_dmat_t *A, int64_t meta[4], int32_t *ti
     if (int rc = check_dmat(A, "uspmv_dmat_plan_download")) return rc;
     if (!meta) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_plan_download: NULL meta");
     meta[0] = meta[1] = meta[2] = meta[3] = 0;
-    if (!A->tlc) return USPMV_OK;
+    if (!A->tlc.on) return USPMV_OK;
     if (int rc = require_device()) return rc;
     int32_t last = 0; uint32_t last16 = 0;
-    HIP_TRY(hipMemcpy(&last, A->tlc_line_ptr + A->tlc_n_tiles, 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&last16, A->tlc_c16_ptrs + A->n_chunks, 4, hipMemcpyDeviceToHost));
-    meta[0] = A->tlc_n_tiles; meta[1] = last; meta[2] = last16; meta[3] = A->tlc_max_lines;
-    if (tile_line_ptr) HIP_TRY(hipMemcpy(tile_line_ptr, A->tlc_line_ptr, 4 * ((size_t)A->tlc_n_tiles + 1), hipMemcpyDeviceToHost));
-    if (tile_lines && last) HIP_TRY(hipMemcpy(tile_lines, A->tlc_lines, 4 * (size_t)last, hipMemcpyDeviceToHost));
-    if (c16_ptrs) HIP_TRY(hipMemcpy(c16_ptrs, A->tlc_c16_ptrs, 4 * ((size_t)A->n_chunks + 1), hipMemcpyDeviceToHost));
-    if (col16 && last16) HIP_TRY(hipMemcpy(col16, A->tlc_col16, 2 * (size_t)last16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&last, A->tlc.line_ptr + A->tlc.n_tiles, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&last16, A->tlc.c16_ptrs + A->n_chunks, 4, hipMemcpyDeviceToHost));
+    meta[0] = A->tlc.n_tiles; meta[1] = last; meta[2] = last16; meta[3] = A->tlc.max_lines;
+    if (tile_line_ptr) HIP_TRY(hipMemcpy(tile_line_ptr, A->tlc.line_ptr, 4 * ((size_t)A->tlc.n_tiles + 1), hipMemcpyDeviceToHost));
+    if (tile_lines && last) HIP_TRY(hipMemcpy(tile_lines, A->tlc.lines, 4 * (size_t)last, hipMemcpyDeviceToHost));
+    if (c16_ptrs) HIP_TRY(hipMemcpy(c16_ptrs, A->tlc.c16_ptrs, 4 * ((size_t)A->n_chunks + 1), hipMemcpyDeviceToHost));
+    if (col16 && last16) HIP_TRY(hipMemcpy(col16, A->tlc.col16, 2 * (size_t)last16, hipMemcpyDeviceToHost));
     return USPMV_OK;
-}
-
-static void part_release(uspmv_dmat_t *A, int order) {
-    (void)hipFree(A->part_len[order][0]); (void)hipFree(A->part_len[order][1]);
-    A->part_len[order][0] = A->part_len[order][1] = nullptr;
 }
 
 extern "C++" {
 namespace uspmv_dev {
 
-namespace { struct FlagBuf { unsigned char *p = nullptr; ~FlagBuf() { (void)hipFree(p); } }; }
-
 static int part_build(uspmv_dmat *A, int order, int rows_per_flag, const unsigned char *d_flags) {
-    part_release(A, order);
+    auto &len = A->part_len[order];
+    len[0].reset(); len[1].reset();
     const size_t bytes = 4 * (size_t)std::max<int64_t>(A->n_chunks, 1);
-    hipError_t e = hipMalloc((void **)&A->part_len[order][0], bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&A->part_len[order][1], bytes);
+    hipError_t e = len[0].alloc(bytes);
+    if (e == hipSuccess) e = len[1].alloc(bytes);
     int rc = e == hipSuccess ? launch_part_len_fill(A, rows_per_flag, d_flags, A->part_len[order][0], A->part_len[order][1], nullptr)
                              : uspmv::fail(USPMV_ERR_ALLOC, "two-part SpMMV: %s", hipGetErrorString(e));
     if (!rc && (e = hipStreamSynchronize(nullptr)) != hipSuccess) rc = uspmv::fail(USPMV_ERR_HIP, "two-part SpMMV: %s", hipGetErrorString(e));
-    if (rc) part_release(A, order);
+    if (rc) { len[0].reset(); len[1].reset(); }
     return rc;
 }
 
 int dmat_part_set_chunks(uspmv_dmat *A, const unsigned char *h_chunk_flags) {
-    FlagBuf f;
-    HIP_TRY(hipMalloc((void **)&f.p, (size_t)std::max<int64_t>(A->n_chunks, 1)));
-    if (A->n_chunks) HIP_TRY(hipMemcpy(f.p, h_chunk_flags, (size_t)A->n_chunks, hipMemcpyHostToDevice));
-    return part_build(A, 0, (int)A->C, f.p);
+    DeviceBuf<unsigned char> f;
+    HIP_TRY(f.upload(h_chunk_flags, (size_t)A->n_chunks));
+    return part_build(A, 0, (int)A->C, f);
 }
 
 int dmat_part_set_plan(uspmv_dmat *A, long n_local, int64_t *n_boundary_tiles) {
-    part_release(A, 1);
+    A->part_len[1][0].reset(); A->part_len[1][1].reset();
     if (n_boundary_tiles) *n_boundary_tiles = 0;
-    if (!A->pb || A->pb_n_tiles == 0) return USPMV_OK;
-    FlagBuf f;
-    HIP_TRY(hipMalloc((void **)&f.p, (size_t)A->pb_n_tiles));
-    if (int rc = launch_block_tile_class(A, n_local, f.p, nullptr)) return rc;
+    if (!A->pb.on || A->pb.n_tiles == 0) return USPMV_OK;
+    DeviceBuf<unsigned char> f;
+    HIP_TRY(f.alloc((size_t)A->pb.n_tiles));
+    if (int rc = launch_block_tile_class(A, n_local, f, nullptr)) return rc;
     if (n_boundary_tiles) {
-        std::vector<unsigned char> h((size_t)A->pb_n_tiles);
-        HIP_TRY(hipMemcpy(h.data(), f.p, h.size(), hipMemcpyDeviceToHost));
+        std::vector<unsigned char> h((size_t)A->pb.n_tiles);
+        HIP_TRY(hipMemcpy(h.data(), f, h.size(), hipMemcpyDeviceToHost));
         for (unsigned char v : h) *n_boundary_tiles += v;
     }
-    return part_build(A, 1, 64, f.p);
+    return part_build(A, 1, 64, f);
 }
 
 }  // namespace uspmv_dev
 }  // extern "C++"
-
-static void bt_release(uspmv_dmat_t *A) {
-    part_release(A, 1);                                         // (classified per tile of the plan that goes away)
-    (void)hipFree(A->bt_line_ptr); (void)hipFree(A->bt_xrows); (void)hipFree(A->bt_c16_ptrs); (void)hipFree(A->bt_col16);
-    (void)hipFree(A->bt_values); (void)hipFree(A->bt_cols); (void)hipFree(A->bt_row_map);
-    A->bt_values = nullptr; A->bt_cols = A->bt_row_map = nullptr;
-    (void)hipFree(A->pb_ph_ptr); (void)hipFree(A->pb_g0); (void)hipFree(A->pb_list_ptr); (void)hipFree(A->pb_xrows); (void)hipFree(A->pb_c16_ptrs); (void)hipFree(A->pb_col16);
-    (void)hipFree(A->pb_values); A->pb_values = nullptr; A->pb_idx8 = false; A->pb_device_built = false;
-    dmat_stream_release(A);
-    A->pb_ph_ptr = A->pb_g0 = A->pb_list_ptr = A->pb_xrows = nullptr; A->pb_c16_ptrs = nullptr; A->pb_col16 = nullptr; A->pb = false;
-    A->bt_line_ptr = A->bt_xrows = nullptr; A->bt_c16_ptrs = nullptr; A->bt_col16 = nullptr;
-    A->bt = false;
-    (void)hipFree(A->pl_ph_ptr); (void)hipFree(A->pl_g0); (void)hipFree(A->pl_list_ptr); (void)hipFree(A->pl_lines); (void)hipFree(A->pl_col8);
-    A->pl_ph_ptr = A->pl_g0 = A->pl_list_ptr = A->pl_lines = nullptr; A->pl_col8 = nullptr; A->pl = false;
-    (void)hipFree(A->pu_ph_ptr); (void)hipFree(A->pu_g0); (void)hipFree(A->pu_list_ptr); (void)hipFree(A->pu_xrows); (void)hipFree(A->pu_col8); (void)hipFree(A->pu_perm);
-    A->pu_ph_ptr = A->pu_g0 = A->pu_list_ptr = A->pu_xrows = A->pu_perm = nullptr; A->pu_col8 = nullptr; A->pu = false;
-}
-
-extern "C++" { namespace uspmv_dev { void dmat_block_plan_release(uspmv_dmat *A) { if (A->bt || A->pb) bt_release(A); } } }
 
 int uspmv_dmat_optimize_block(uspmv_dmat_t *A, const uspmv_scs_t *s, int block_vec_size, int64_t *n_tiles, int64_t *n_staged) {
     if (!A || !s) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block: NULL argument");
@@ -1038,7 +966,7 @@ int uspmv_dmat_optimize_block(uspmv_dmat_t *A, const uspmv_scs_t *s, int block_v
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block: handle and host struct do not describe the same matrix");
     if (block_vec_size < 1) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block: block_vec_size must be >= 1");
     if (int rc = require_device()) return rc;
-    if (A->bt || A->pb) bt_release(A);
+    block_plan_reset(A);
     if (n_tiles) *n_tiles = 0;
     if (n_staged) *n_staged = 0;
     // a struct rebuilt from the handle's device arrays (uspmv_dmat_optimize_block_device) carries the indices only: the plan's private
@@ -1109,45 +1037,39 @@ int uspmv_dmat_optimize_block(uspmv_dmat_t *A, const uspmv_scs_t *s, int block_v
         if (n_tiles) *n_tiles = pp.n_tiles;
         if (n_staged) *n_staged = pp.n_tiles;
     }
-    auto up = [&](const void *h, size_t bytes, void **d) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes ? bytes : 4);
-        if (e == hipSuccess && bytes) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
     hipError_t e = hipSuccess;
-    if (moved) e = up(row_map.data(), row_map.size() * 4, (void **)&A->bt_row_map);
+    if (moved) e = A->bt.row_map.upload(row_map.data(), row_map.size() * 4);
     if (list_plan && p.valid) {
-        if (e == hipSuccess) e = up(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4, (void **)&A->bt_line_ptr);
-        if (e == hipSuccess) e = up(p.tile_lines.data(), p.tile_lines.size() * 4, (void **)&A->bt_xrows);
-        if (e == hipSuccess) e = up(p.c16_ptrs.data(), p.c16_ptrs.size() * 4, (void **)&A->bt_c16_ptrs);
-        if (e == hipSuccess) e = up(p.col16.data(), p.col16.size() * 2, (void **)&A->bt_col16);
+        if (e == hipSuccess) e = A->bt.line_ptr.upload(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4);
+        if (e == hipSuccess) e = A->bt.xrows.upload(p.tile_lines.data(), p.tile_lines.size() * 4);
+        if (e == hipSuccess) e = A->bt.c16_ptrs.upload(p.c16_ptrs.data(), p.c16_ptrs.size() * 4);
+        if (e == hipSuccess) e = A->bt.col16.upload(p.col16.data(), p.col16.size() * 2);
         if (e == hipSuccess && moved) {
-            if (host_values) e = up(r.values_ptr(), (size_t)r.n_elements * (r.dtype == USPMV_F64 ? 8 : 4), &A->bt_values);
+            if (host_values) e = A->bt.values.upload(r.values_ptr(), (size_t)r.n_elements * (r.dtype == USPMV_F64 ? 8 : 4));
             else {
-                e = hipMalloc(&A->bt_values, std::max<size_t>((size_t)r.n_elements, 1) * (r.dtype == USPMV_F64 ? 8 : 4));
-                if (e == hipSuccess && launch_block_values_gather(A, A->bt_row_map, nullptr, A->bt_values, false, nullptr) != USPMV_OK) e = hipErrorUnknown;
+                e = A->bt.values.alloc(std::max<size_t>((size_t)r.n_elements, 1) * (r.dtype == USPMV_F64 ? 8 : 4));
+                if (e == hipSuccess && launch_block_values_gather(A, A->bt.row_map, nullptr, A->bt.values, false, nullptr) != USPMV_OK) e = hipErrorUnknown;
             }
-            if (e == hipSuccess && (p.n_staged_tiles < p.n_tiles || g_tune.spmmv_variant == 5)) e = up(r.col_idxs.data(), (size_t)r.n_elements * 4, (void **)&A->bt_cols);
+            if (e == hipSuccess && (p.n_staged_tiles < p.n_tiles || g_tune.spmmv_variant == 5)) e = A->bt.cols.upload(r.col_idxs.data(), (size_t)r.n_elements * 4);
         }
     }
     if (e == hipSuccess && pp.valid) {
         {
-            e = up(pp.ph_ptr.data(), pp.ph_ptr.size() * 4, (void **)&A->pb_ph_ptr);
-            if (e == hipSuccess) e = up(pp.ph_g0.data(), pp.ph_g0.size() * 4, (void **)&A->pb_g0);
-            if (e == hipSuccess) e = up(pp.ph_list_ptr.data(), pp.ph_list_ptr.size() * 4, (void **)&A->pb_list_ptr);
-            if (e == hipSuccess) e = up(pp.xrows.data(), pp.xrows.size() * 4, (void **)&A->pb_xrows);
-            if (e == hipSuccess) e = up(pp.c16_ptrs.data(), pp.c16_ptrs.size() * 4, (void **)&A->pb_c16_ptrs);
-            A->pb_idx8 = g_tune.spmmv_idx8 && pp.max_rows_used <= 256;
-            if (e == hipSuccess && A->pb_idx8) {             // same layout, one byte per entry
+            e = A->pb.ph_ptr.upload(pp.ph_ptr.data(), pp.ph_ptr.size() * 4);
+            if (e == hipSuccess) e = A->pb.g0.upload(pp.ph_g0.data(), pp.ph_g0.size() * 4);
+            if (e == hipSuccess) e = A->pb.list_ptr.upload(pp.ph_list_ptr.data(), pp.ph_list_ptr.size() * 4);
+            if (e == hipSuccess) e = A->pb.xrows.upload(pp.xrows.data(), pp.xrows.size() * 4);
+            if (e == hipSuccess) e = A->pb.c16_ptrs.upload(pp.c16_ptrs.data(), pp.c16_ptrs.size() * 4);
+            A->pb.idx8 = g_tune.spmmv_idx8 && pp.max_rows_used <= 256;
+            if (e == hipSuccess && A->pb.idx8) {             // same layout, one byte per entry
                 std::vector<uint8_t> c8(pp.col16.size());
                 for (size_t k = 0; k < c8.size(); ++k) c8[k] = (uint8_t)pp.col16[k];
-                e = up(c8.data(), c8.size(), (void **)&A->pb_col16);
-            } else if (e == hipSuccess) e = up(pp.col16.data(), pp.col16.size() * 2, (void **)&A->pb_col16);
+                e = A->pb.col16.upload(c8.data(), c8.size());
+            } else if (e == hipSuccess) e = A->pb.col16.upload(pp.col16.data(), pp.col16.size() * 2);
             if (e == hipSuccess && !host_values) {
                 const size_t vs = s->dtype == USPMV_F64 ? 8 : 4;
-                e = hipMalloc(&A->pb_values, std::max<size_t>(pp.col16.size(), 1) * vs);
-                if (e == hipSuccess) e = hipMemset(A->pb_values, 0, std::max<size_t>(pp.col16.size(), 1) * vs);     // padded slots of the last group of a chunk
-                if (e == hipSuccess && launch_block_values_gather(A, moved ? A->bt_row_map : nullptr, A->pb_c16_ptrs, A->pb_values, true, nullptr) != USPMV_OK) e = hipErrorUnknown;
+                e = A->pb.values.zeros(std::max<size_t>(pp.col16.size(), 1) * vs);     // padded slots of the last group of a chunk
+                if (e == hipSuccess && launch_block_values_gather(A, moved ? A->bt.row_map : nullptr, A->pb.c16_ptrs, A->pb.values, true, nullptr) != USPMV_OK) e = hipErrorUnknown;
                 if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
             } else if (e == hipSuccess) {
                 // the entries once more, group-major like the indices (what scs_spmmv_quadph streams)
@@ -1165,33 +1087,33 @@ int uspmv_dmat_optimize_block(uspmv_dmat_t *A, const uspmv_scs_t *s, int block_v
                             if (vs == 8) ((double *)gv.data())[dst] = src->values_f64[from]; else ((float *)gv.data())[dst] = src->values_f32[from];
                         }
                 }
-                e = up(gv.data(), gv.size(), &A->pb_values);
+                e = A->pb.values.upload(gv.data(), gv.size());
             }
             if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] phased block plan: tiles=%lld phases=%lld rows_total=%zu max_rows=%d (cap %d)\n",
                                                  (long long)pp.n_tiles, (long long)pp.n_phases, pp.xrows.size(), pp.max_rows_used, pp.cap_rows);
             if (e == hipSuccess && pu.valid) {
-                e = up(pu.ph_ptr.data(), pu.ph_ptr.size() * 4, (void **)&A->pu_ph_ptr);
-                if (e == hipSuccess) e = up(pu.ph_g0.data(), pu.ph_g0.size() * 4, (void **)&A->pu_g0);
-                if (e == hipSuccess) e = up(pu.ph_list_ptr.data(), pu.ph_list_ptr.size() * 4, (void **)&A->pu_list_ptr);
-                if (e == hipSuccess) e = up(pu.xrows.data(), pu.xrows.size() * 4, (void **)&A->pu_xrows);
-                if (e == hipSuccess) e = up(s->old_to_new_idx.data(), (size_t)s->n_rows * 4, (void **)&A->pu_perm);
+                e = A->pu.ph_ptr.upload(pu.ph_ptr.data(), pu.ph_ptr.size() * 4);
+                if (e == hipSuccess) e = A->pu.g0.upload(pu.ph_g0.data(), pu.ph_g0.size() * 4);
+                if (e == hipSuccess) e = A->pu.list_ptr.upload(pu.ph_list_ptr.data(), pu.ph_list_ptr.size() * 4);
+                if (e == hipSuccess) e = A->pu.xrows.upload(pu.xrows.data(), pu.xrows.size() * 4);
+                if (e == hipSuccess) e = A->pu.perm.upload(s->old_to_new_idx.data(), (size_t)s->n_rows * 4);
                 if (e == hipSuccess) {
                     std::vector<uint8_t> c8(pu.col16.size());
                     for (size_t k = 0; k < c8.size(); ++k) c8[k] = (uint8_t)pu.col16[k];
-                    e = up(c8.data(), c8.size(), (void **)&A->pu_col8);
+                    e = A->pu.col8.upload(c8.data(), c8.size());
                 }
                 if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] unscrambled plan (column-major X behind the permuting re-layout): phases=%lld rows_total=%zu (scrambled: %zu) max_rows=%d\n",
                                                      (long long)pu.n_phases, pu.xrows.size(), pp.xrows.size(), pu.max_rows_used);
             }
             if (e == hipSuccess && pl.valid) {
-                e = up(pl.ph_ptr.data(), pl.ph_ptr.size() * 4, (void **)&A->pl_ph_ptr);
-                if (e == hipSuccess) e = up(pl.ph_g0.data(), pl.ph_g0.size() * 4, (void **)&A->pl_g0);
-                if (e == hipSuccess) e = up(pl.ph_list_ptr.data(), pl.ph_list_ptr.size() * 4, (void **)&A->pl_list_ptr);
-                if (e == hipSuccess) e = up(pl.xrows.data(), pl.xrows.size() * 4, (void **)&A->pl_lines);
+                e = A->pl.ph_ptr.upload(pl.ph_ptr.data(), pl.ph_ptr.size() * 4);
+                if (e == hipSuccess) e = A->pl.g0.upload(pl.ph_g0.data(), pl.ph_g0.size() * 4);
+                if (e == hipSuccess) e = A->pl.list_ptr.upload(pl.ph_list_ptr.data(), pl.ph_list_ptr.size() * 4);
+                if (e == hipSuccess) e = A->pl.lines.upload(pl.xrows.data(), pl.xrows.size() * 4);
                 if (e == hipSuccess) {
                     std::vector<uint8_t> c8(pl.col16.size());
                     for (size_t k = 0; k < c8.size(); ++k) c8[k] = (uint8_t)pl.col16[k];
-                    e = up(c8.data(), c8.size(), (void **)&A->pl_col8);
+                    e = A->pl.col8.upload(c8.data(), c8.size());
                 }
                 if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] line plan (column-major X): phases=%lld lines_total=%zu (= %zu rows) max_rows=%d\n",
                                                      (long long)pl.n_phases, pl.xrows.size(), pl.xrows.size() << pl.line_shift, pl.max_rows_used);
@@ -1199,14 +1121,14 @@ int uspmv_dmat_optimize_block(uspmv_dmat_t *A, const uspmv_scs_t *s, int block_v
         }
     }
     if (e != hipSuccess) {
-        bt_release(A);
+        block_plan_reset(A);
         return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize_block: device copy failed: %s", hipGetErrorString(e));
     }
-    if (pp.valid && pu.valid) { A->pu = true; A->pu_max_rows = pu.max_rows_used; A->pu_n_phases = pu.n_phases; A->pu_n_perm = s->n_rows; }
-    if (pp.valid && pl.valid) { A->pl = true; A->pl_shift = pl.line_shift; A->pl_max_rows = pl.max_rows_used; A->pl_n_phases = pl.n_phases; A->pl_rows_staged = (int64_t)pl.xrows.size() << pl.line_shift; }
-    if (pp.valid) { A->pb = true; A->pb_cap_rows = pp.cap_rows; A->pb_ngp = pp.ngp; A->pb_max_rows = pp.max_rows_used; A->pb_n_tiles = pp.n_tiles; A->pb_n_phases = pp.n_phases; A->pb_rows_staged = (int64_t)pp.xrows.size(); }
-    if (list_plan && p.valid) { A->bt = true; A->bt_tile_rows = p.tile_rows; A->bt_max_rows = p.max_lines_used; A->bt_n_tiles = p.n_tiles; A->bt_staged = p.n_staged_tiles; }
-    if (A->pb && g_tune.spmmv_stream > 0) return dmat_stream_schedule(A, g_tune.spmmv_stream);
+    if (pp.valid && pu.valid) { A->pu.on = true; A->pu.max_rows = pu.max_rows_used; A->pu.n_phases = pu.n_phases; A->pu.n_perm = s->n_rows; }
+    if (pp.valid && pl.valid) { A->pl.on = true; A->pl.shift = pl.line_shift; A->pl.max_rows = pl.max_rows_used; A->pl.n_phases = pl.n_phases; A->pl.rows_staged = (int64_t)pl.xrows.size() << pl.line_shift; }
+    if (pp.valid) { A->pb.on = true; A->pb.cap_rows = pp.cap_rows; A->pb.ngp = pp.ngp; A->pb.max_rows = pp.max_rows_used; A->pb.n_tiles = pp.n_tiles; A->pb.n_phases = pp.n_phases; A->pb.rows_staged = (int64_t)pp.xrows.size(); }
+    if (list_plan && p.valid) { A->bt.on = true; A->bt.tile_rows = p.tile_rows; A->bt.max_rows = p.max_lines_used; A->bt.n_tiles = p.n_tiles; A->bt.staged = p.n_staged_tiles; }
+    if (A->pb.on && g_tune.spmmv_stream > 0) return dmat_stream_schedule(A, g_tune.spmmv_stream);
     return USPMV_OK;
 }
 
@@ -1219,71 +1141,65 @@ static int block_plan_install_device(uspmv_dmat_t *A, int block_vec_size, int64_
     if (row_bytes != 64 || (A->C != 32 && A->C != 64) || !g_tune.spmmv_phased || g_tune.spmmv_phase_rows != 256 || g_tune.spmmv_list_plan ||
         (g_tune.spmmv_reorder != 1 && g_tune.spmmv_reorder != 4) || !g_tune.spmmv_idx8 || g_tune.spmmv_tile_rows == 32 || g_tune.spmmv_xline || !g_tune.block_plan_device) return 1;
     const int64_t C = A->C, nc = A->n_chunks, n_pad = nc * C, nt = (n_pad + 63) / 64;
-    if (A->bt || A->pb) bt_release(A);
+    block_plan_reset(A);
     std::vector<int32_t> cl((size_t)nc);
     std::vector<uint32_t> c16p;
     int64_t tot16 = 0;
     HIP_TRY(hipMemcpy(cl.data(), A->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
     if (!c16_offsets(cl, C, &c16p, &tot16)) return USPMV_OK;
-    int *d_changed = nullptr, *d_tph = nullptr, *d_tl = nullptr, *d_max = nullptr;
-    hipError_t e = hipMalloc((void **)&d_changed, 8);
-    d_max = d_changed ? d_changed + 1 : nullptr;
-    if (e == hipSuccess) e = hipMemset(d_changed, 0, 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&A->bt_row_map, 4 * (size_t)std::max<int64_t>(n_pad, 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&A->pb_c16_ptrs, 4 * ((size_t)nc + 1));
-    if (e == hipSuccess) e = hipMemcpy(A->pb_c16_ptrs, c16p.data(), 4 * ((size_t)nc + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tph, 4 * (size_t)nt);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tl, 4 * (size_t)nt);
+    DeviceBuf<int> d_changed, d_tph, d_tl;
+    hipError_t e = d_changed.zeros(8);
+    int *const d_max = d_changed ? d_changed.get() + 1 : nullptr;
+    if (e == hipSuccess) e = A->bt.row_map.alloc(4 * (size_t)std::max<int64_t>(n_pad, 1));
+    if (e == hipSuccess) e = A->pb.c16_ptrs.upload(c16p.data(), 4 * ((size_t)nc + 1));
+    if (e == hipSuccess) e = d_tph.alloc(4 * (size_t)nt);
+    if (e == hipSuccess) e = d_tl.alloc(4 * (size_t)nt);
     auto fail_out = [&](const char *what) {
-        (void)hipFree(d_changed); (void)hipFree(d_tph); (void)hipFree(d_tl);
-        bt_release(A);
+        block_plan_reset(A);
         return uspmv::fail(USPMV_ERR_HIP, "uspmv_dmat_optimize_block_device: %s: %s", what, hipGetErrorString(e));
     };
     if (e != hipSuccess) return fail_out("allocation");
     // ---- row order (ties of the sigma sort undone by first column), then the phases: count, scan, write
-    int rc = launch_block_reorder(A, A->bt_row_map, d_changed, nullptr);
+    int rc = launch_block_reorder(A, A->bt.row_map, d_changed, nullptr);
     int changed = 0;
     if (!rc) { e = hipMemcpy(&changed, d_changed, 4, hipMemcpyDeviceToHost); if (e != hipSuccess) return fail_out("row order"); }
-    const int *rmap = changed ? A->bt_row_map : nullptr;
-    if (!changed) { (void)hipFree(A->bt_row_map); A->bt_row_map = nullptr; }
-    if (!rc) rc = launch_block_phase_plan(A, false, 256, 8, rmap, A->pb_c16_ptrs, d_tph, d_tl, nullptr, nullptr, nullptr, nullptr, d_max, nullptr);
+    const int *rmap = changed ? A->bt.row_map : nullptr;
+    if (!changed) A->bt.row_map.reset();
+    if (!rc) rc = launch_block_phase_plan(A, false, 256, 8, rmap, A->pb.c16_ptrs, d_tph, d_tl, nullptr, nullptr, nullptr, nullptr, d_max, nullptr);
     std::vector<int32_t> tph((size_t)nt + 1, 0), tl((size_t)nt + 1, 0);
     if (!rc) {
         e = hipMemcpy(tph.data(), d_tph, 4 * (size_t)nt, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(tl.data(), d_tl, 4 * (size_t)nt, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail_out("phase counts");
     }
-    if (rc) { (void)hipFree(d_changed); (void)hipFree(d_tph); (void)hipFree(d_tl); bt_release(A); return rc; }
+    if (rc) { block_plan_reset(A); return rc; }
     int64_t n_ph = 0, n_list = 0;
     for (int64_t t = 0; t < nt; ++t) {   // exclusive scans (ph_ptr of the plan; list bases)
         const int32_t a = tph[(size_t)t], b = tl[(size_t)t];
         tph[(size_t)t] = (int32_t)n_ph; tl[(size_t)t] = (int32_t)n_list;
         n_ph += a; n_list += b;
-        if (n_ph > INT32_MAX || n_list > INT32_MAX) { (void)hipFree(d_changed); (void)hipFree(d_tph); (void)hipFree(d_tl); bt_release(A); return USPMV_OK; }
+        if (n_ph > INT32_MAX || n_list > INT32_MAX) { block_plan_reset(A); return USPMV_OK; }
     }
     tph[(size_t)nt] = (int32_t)n_ph; tl[(size_t)nt] = (int32_t)n_list;
     if (n_tiles) *n_tiles = nt;
     if (n_staged) *n_staged = n_ph > 0 ? nt : 0;
-    if (n_ph == 0) { (void)hipFree(d_changed); (void)hipFree(d_tph); (void)hipFree(d_tl); bt_release(A); return USPMV_OK; }
-    e = hipMalloc((void **)&A->pb_ph_ptr, 4 * ((size_t)nt + 1));
-    if (e == hipSuccess) e = hipMemcpy(A->pb_ph_ptr, tph.data(), 4 * ((size_t)nt + 1), hipMemcpyHostToDevice);
+    if (n_ph == 0) { block_plan_reset(A); return USPMV_OK; }
+    e = A->pb.ph_ptr.upload(tph.data(), 4 * ((size_t)nt + 1));
     if (e == hipSuccess) e = hipMemcpy(d_tl, tl.data(), 4 * (size_t)nt, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&A->pb_g0, 4 * (size_t)n_ph);
-    if (e == hipSuccess) e = hipMalloc((void **)&A->pb_list_ptr, 4 * ((size_t)n_ph + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&A->pb_xrows, 4 * (size_t)std::max<int64_t>(n_list, 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&A->pb_col16, (size_t)std::max<int64_t>(tot16, 1));
-    if (e == hipSuccess) e = hipMemset(A->pb_col16, 0, (size_t)std::max<int64_t>(tot16, 1));
-    if (e == hipSuccess) { const int32_t last = (int32_t)n_list; e = hipMemcpy(A->pb_list_ptr + n_ph, &last, 4, hipMemcpyHostToDevice); }
-    if (e == hipSuccess) e = hipMalloc(&A->pb_values, (size_t)std::max<int64_t>(tot16, 1) * vsz);
-    if (e == hipSuccess) e = hipMemset(A->pb_values, 0, (size_t)std::max<int64_t>(tot16, 1) * vsz);
+    if (e == hipSuccess) e = A->pb.g0.alloc(4 * (size_t)n_ph);
+    if (e == hipSuccess) e = A->pb.list_ptr.alloc(4 * ((size_t)n_ph + 1));
+    if (e == hipSuccess) e = A->pb.xrows.alloc(4 * (size_t)std::max<int64_t>(n_list, 1));
+    if (e == hipSuccess) e = A->pb.col16.zeros((size_t)std::max<int64_t>(tot16, 1));
+    if (e == hipSuccess) { const int32_t last = (int32_t)n_list; e = hipMemcpy(A->pb.list_ptr + n_ph, &last, 4, hipMemcpyHostToDevice); }
+    if (e == hipSuccess) e = A->pb.values.zeros((size_t)std::max<int64_t>(tot16, 1) * vsz);
     if (e != hipSuccess) return fail_out("plan arrays");
-    rc = launch_block_phase_plan(A, true, 256, 8, rmap, A->pb_c16_ptrs, A->pb_ph_ptr, d_tl, A->pb_g0, A->pb_list_ptr, A->pb_xrows, (unsigned char *)A->pb_col16, d_max, nullptr);
-    if (!rc) rc = launch_block_values_gather(A, rmap, A->pb_c16_ptrs, A->pb_values, true, nullptr);
+    rc = launch_block_phase_plan(A, true, 256, 8, rmap, A->pb.c16_ptrs, A->pb.ph_ptr, d_tl, A->pb.g0, A->pb.list_ptr, A->pb.xrows, (unsigned char *)A->pb.col16, d_max, nullptr);
+    if (!rc) rc = launch_block_values_gather(A, rmap, A->pb.c16_ptrs, A->pb.values, true, nullptr);
     int max_rows = 0;
     if (!rc) { e = hipMemcpy(&max_rows, d_max, 4, hipMemcpyDeviceToHost); if (e != hipSuccess) return fail_out("plan kernels"); }
-    (void)hipFree(d_changed); (void)hipFree(d_tph); (void)hipFree(d_tl);
-    if (rc) { bt_release(A); return rc; }
-    A->pb = true; A->pb_idx8 = true; A->pb_device_built = true; A->pb_cap_rows = 256; A->pb_ngp = 8; A->pb_max_rows = max_rows; A->pb_n_tiles = nt; A->pb_n_phases = n_ph; A->pb_rows_staged = n_list;
+    d_changed.reset(); d_tph.reset(); d_tl.reset();
+    if (rc) { block_plan_reset(A); return rc; }
+    A->pb.on = true; A->pb.idx8 = true; A->pb.device_built = true; A->pb.cap_rows = 256; A->pb.ngp = 8; A->pb.max_rows = max_rows; A->pb.n_tiles = nt; A->pb.n_phases = n_ph; A->pb.rows_staged = n_list;
     if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] phased block plan (device builder): tiles=%lld phases=%lld rows_total=%lld max_rows=%d rows %s\n",
                                          (long long)nt, (long long)n_ph, (long long)n_list, max_rows, changed ? "re-ordered" : "in the caller's order");
     if (g_tune.spmmv_stream > 0) return dmat_stream_schedule(A, g_tune.spmmv_stream);
@@ -1333,8 +1249,8 @@ int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t
         dp->C != sp->C || dp->n_chunks != sp->n_chunks)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_ap: handles / host structs do not form a dp+sp pair");
     if (int rc = require_device()) return rc;
-    if (dp->tlc) tlc_release(dp);
-    if (sp->tlc) tlc_release(sp);
+    dp->tlc = {};
+    sp->tlc = {};
     if (max_lines <= 0) max_lines = 512;
     if (max_lines > 1280) max_lines = 1280;
     uspmv_tlc_plan p;
@@ -1342,55 +1258,40 @@ int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t
     if (int rc = uspmv_build_tlc_plan(s_dp, s_sp, max_lines, R_meas ? R_meas : plan_tile_rows(true), &p)) return rc;
     if (n_tiles) *n_tiles = p.n_tiles;
     if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
-    if (dp->sw) sw_release(dp);
-    if (sp->sw) sw_release(sp);
+    dp->sw = {};
+    sp->sw = {};
     if ((!p.valid || p.n_staged_tiles * 2 < p.n_tiles) && g_tune.sweep) {   // as in uspmv_dmat_optimize
         int64_t swt = 0, sws = 0;
         if (int rc = sweep_plan_install(dp, sp, s_dp, s_sp, 0, 0, &swt, &sws, "uspmv_dmat_optimize_ap")) return rc;
-        if (dp->sw && sws * 2 >= swt) return USPMV_OK;
-        if (dp->sw) { sw_release(dp); sw_release(sp); }
+        if (dp->sw.on && sws * 2 >= swt) return USPMV_OK;
+        if (dp->sw.on) { dp->sw = {}; sp->sw = {}; }
     }
     if (!p.valid) return USPMV_OK;
-    auto up = [&](const void *h, size_t bytes, void **d) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes ? bytes : 4);
-        if (e == hipSuccess && bytes) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4, (void **)&dp->tlc_line_ptr);
-    if (e == hipSuccess) e = up(p.tile_lines.data(), p.tile_lines.size() * 4, (void **)&dp->tlc_lines);
-    if (e == hipSuccess) e = up(p.c16_ptrs.data(), p.c16_ptrs.size() * 4, (void **)&dp->tlc_c16_ptrs);
-    if (e == hipSuccess) e = up(p.col16.data(), p.col16.size() * 2, (void **)&dp->tlc_col16);
-    if (e == hipSuccess) e = up(p.c16_ptrs_b.data(), p.c16_ptrs_b.size() * 4, (void **)&sp->tlc_c16_ptrs);
-    if (e == hipSuccess) e = up(p.col16_b.data(), p.col16_b.size() * 2, (void **)&sp->tlc_col16);
+    hipError_t e = dp->tlc.line_ptr.upload(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4);
+    if (e == hipSuccess) e = dp->tlc.lines.upload(p.tile_lines.data(), p.tile_lines.size() * 4);
+    if (e == hipSuccess) e = dp->tlc.c16_ptrs.upload(p.c16_ptrs.data(), p.c16_ptrs.size() * 4);
+    if (e == hipSuccess) e = dp->tlc.col16.upload(p.col16.data(), p.col16.size() * 2);
+    if (e == hipSuccess) e = sp->tlc.c16_ptrs.upload(p.c16_ptrs_b.data(), p.c16_ptrs_b.size() * 4);
+    if (e == hipSuccess) e = sp->tlc.col16.upload(p.col16_b.data(), p.col16_b.size() * 2);
     if (e != hipSuccess) {
-        tlc_release(dp); tlc_release(sp);
+        dp->tlc = {}; sp->tlc = {};
         return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize_ap: device copy failed: %s", hipGetErrorString(e));
     }
     static uint64_t next_plan_id = 1;
     const uint64_t id = next_plan_id++;
     for (uspmv_dmat_t *A : {dp, sp}) {
-        A->tlc = true; A->tlc_tile_rows = p.tile_rows; A->tlc_max_lines = p.max_lines_used; A->tlc_x_len = p.x_len_min;
-        A->tlc_n_tiles = p.n_tiles; A->tlc_staged = p.n_staged_tiles; A->tlc_plan_id = id;
+        A->tlc.on = true; A->tlc.tile_rows = p.tile_rows; A->tlc.max_lines = p.max_lines_used; A->tlc.x_len = p.x_len_min;
+        A->tlc.n_tiles = p.n_tiles; A->tlc.staged = p.n_staged_tiles; A->tlc.plan_id = id;
     }
     return USPMV_OK;
 }
 
 
-static void sw_release(uspmv_dmat_t *A) {
-    (void)hipFree(A->sw_tile_ids); (void)hipFree(A->sw_smin); (void)hipFree(A->sw_S); (void)hipFree(A->sw_pad); (void)hipFree(A->sw_pad_b);
-    (void)hipFree(A->sw_rest); (void)hipFree(A->sw_cnt_off); (void)hipFree(A->sw_wave_off); (void)hipFree(A->sw_wave_off_b);
-    (void)hipFree(A->sw_cnt); (void)hipFree(A->sw_cnt_b); (void)hipFree(A->sw_vals); (void)hipFree(A->sw_vals_b); (void)hipFree(A->sw_idx); (void)hipFree(A->sw_idx_b);
-    A->sw_tile_ids = A->sw_smin = A->sw_S = A->sw_pad = A->sw_pad_b = A->sw_rest = nullptr;
-    A->sw_cnt_off = nullptr; A->sw_wave_off = A->sw_wave_off_b = nullptr; A->sw_cnt = A->sw_cnt_b = nullptr;
-    A->sw_vals = nullptr; A->sw_vals_b = nullptr; A->sw_idx = A->sw_idx_b = nullptr;
-    A->sw = false; A->sw_plan_id = 0; A->sw_n_tiles = A->sw_all_tiles = A->sw_n_rest = 0;
-}
-
 // builds and uploads a sweep plan for A (and, when B/sB are given, for the dp+sp pair A/B); returns the number of sweep tiles
 static int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, const uspmv_scs_t *sB, int wlog, int tile_rows,
                               int64_t *n_tiles, int64_t *n_sweep, const char *who) {
-    if (A->sw) sw_release(A);
-    if (B && B->sw) sw_release(B);
+    A->sw = {};
+    if (B) B->sw = {};
     if (n_tiles) *n_tiles = 0;
     if (n_sweep) *n_sweep = 0;
     const size_t vsz = s->dtype == USPMV_F64 ? 8 : 4;
@@ -1419,38 +1320,33 @@ static int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_
                                          p.tile_rows, p.wlog, (long long)p.n_tiles, (long long)p.n_sweep_tiles, p.rest_chunks.size(), p.idx.size(), p.cnt.size());
     if (!p.valid) return USPMV_OK;
     hipError_t e = hipSuccess;
-    auto up = [&](const void *h, size_t bytes, void **d) {
-        if (e != hipSuccess) return;
-        e = hipMalloc(d, bytes ? bytes : 4);
-        if (e == hipSuccess && bytes) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-    };
-    up(p.tile_ids.data(), p.tile_ids.size() * 4, (void **)&A->sw_tile_ids);
-    up(p.t_smin.data(), p.t_smin.size() * 4, (void **)&A->sw_smin);
-    up(p.t_S.data(), p.t_S.size() * 4, (void **)&A->sw_S);
-    up(p.t_cnt_off.data(), p.t_cnt_off.size() * 8, (void **)&A->sw_cnt_off);
-    up(p.wave_off.data(), p.wave_off.size() * 4, (void **)&A->sw_wave_off);
-    up(p.cnt.data(), p.cnt.size(), (void **)&A->sw_cnt);
-    up(vsz == 8 ? (const void *)p.vals_f64.data() : (const void *)p.vals_f32.data(), p.idx.size() * vsz, &A->sw_vals);
-    up(p.idx.data(), p.idx.size() * 2, (void **)&A->sw_idx);
-    up(p.pad_col.data(), p.pad_col.size() * 4, (void **)&A->sw_pad);
-    up(p.rest_chunks.data(), p.rest_chunks.size() * 4, (void **)&A->sw_rest);
+    if (e == hipSuccess) e = A->sw.tile_ids.upload(p.tile_ids.data(), p.tile_ids.size() * 4);
+    if (e == hipSuccess) e = A->sw.smin.upload(p.t_smin.data(), p.t_smin.size() * 4);
+    if (e == hipSuccess) e = A->sw.S.upload(p.t_S.data(), p.t_S.size() * 4);
+    if (e == hipSuccess) e = A->sw.cnt_off.upload(p.t_cnt_off.data(), p.t_cnt_off.size() * 8);
+    if (e == hipSuccess) e = A->sw.wave_off.upload(p.wave_off.data(), p.wave_off.size() * 4);
+    if (e == hipSuccess) e = A->sw.cnt.upload(p.cnt.data(), p.cnt.size());
+    if (e == hipSuccess) e = A->sw.vals.upload(vsz == 8 ? (const void *)p.vals_f64.data() : (const void *)p.vals_f32.data(), p.idx.size() * vsz);
+    if (e == hipSuccess) e = A->sw.idx.upload(p.idx.data(), p.idx.size() * 2);
+    if (e == hipSuccess) e = A->sw.pad.upload(p.pad_col.data(), p.pad_col.size() * 4);
+    if (e == hipSuccess) e = A->sw.rest.upload(p.rest_chunks.data(), p.rest_chunks.size() * 4);
     if (B) {
-        up(p.wave_off_b.data(), p.wave_off_b.size() * 4, (void **)&A->sw_wave_off_b);
-        up(p.cnt_b.data(), p.cnt_b.size(), (void **)&A->sw_cnt_b);
-        up(p.vals_b_f32.data(), p.idx_b.size() * 4, (void **)&A->sw_vals_b);
-        up(p.idx_b.data(), p.idx_b.size() * 2, (void **)&A->sw_idx_b);
-        up(p.pad_col_b.data(), p.pad_col_b.size() * 4, (void **)&A->sw_pad_b);
+        if (e == hipSuccess) e = A->sw.wave_off_b.upload(p.wave_off_b.data(), p.wave_off_b.size() * 4);
+        if (e == hipSuccess) e = A->sw.cnt_b.upload(p.cnt_b.data(), p.cnt_b.size());
+        if (e == hipSuccess) e = A->sw.vals_b.upload(p.vals_b_f32.data(), p.idx_b.size() * 4);
+        if (e == hipSuccess) e = A->sw.idx_b.upload(p.idx_b.data(), p.idx_b.size() * 2);
+        if (e == hipSuccess) e = A->sw.pad_b.upload(p.pad_col_b.data(), p.pad_col_b.size() * 4);
     }
     if (e != hipSuccess) {
-        sw_release(A);
+        A->sw = {};
         return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
     }
     static uint64_t next_sweep_id = 1;
     const uint64_t id = next_sweep_id++;
-    A->sw = true; A->sw_tile_rows = p.tile_rows; A->sw_wlog = p.wlog; A->sw_n_tiles = p.n_sweep_tiles; A->sw_all_tiles = p.n_tiles;
-    A->sw_x_len = p.x_len_min; A->sw_n_rest = (int64_t)p.rest_chunks.size(); A->sw_plan_id = id;
-    A->sw_n_vals = (int64_t)p.idx.size() - 64; A->sw_n_vals_b = B ? (int64_t)p.idx_b.size() - 64 : 0; A->sw_cnt_bytes = (int64_t)p.cnt.size();
-    if (B) { B->sw = true; B->sw_plan_id = id; B->sw_n_tiles = p.n_sweep_tiles; B->sw_all_tiles = p.n_tiles; }
+    A->sw.on = true; A->sw.tile_rows = p.tile_rows; A->sw.wlog = p.wlog; A->sw.n_tiles = p.n_sweep_tiles; A->sw.all_tiles = p.n_tiles;
+    A->sw.x_len = p.x_len_min; A->sw.n_rest = (int64_t)p.rest_chunks.size(); A->sw.plan_id = id;
+    A->sw.n_vals = (int64_t)p.idx.size() - 64; A->sw.n_vals_b = B ? (int64_t)p.idx_b.size() - 64 : 0; A->sw.cnt_bytes = (int64_t)p.cnt.size();
+    if (B) { B->sw.on = true; B->sw.plan_id = id; B->sw.n_tiles = p.n_sweep_tiles; B->sw.all_tiles = p.n_tiles; }
     return USPMV_OK;
 }
 
@@ -1458,8 +1354,8 @@ static int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_
 // offsets on the host (O(n_tiles); 16 bytes per 64-row group come back), a fill kernel per struct.  Same defaults, same criteria and
 // -- by construction of the fill kernel -- the same arrays as sweep_plan_install builds from a host struct.
 static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who) {
-    if (A->sw) sw_release(A);
-    if (B && B->sw) sw_release(B);
+    A->sw = {};
+    if (B) B->sw = {};
     if (n_tiles) *n_tiles = 0;
     if (n_sweep) *n_sweep = 0;
     const int64_t C = A->C, nc = A->n_chunks;
@@ -1483,16 +1379,14 @@ static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog,
     const uspmv_dmat_t *M[2] = {A, B};
     const double max_stage = g_tune.sweep_max_stage > 0 ? (double)g_tune.sweep_max_stage : 24.0;
     // ---- scan
-    int *d_le[2] = {nullptr, nullptr}, *d_pad[2] = {nullptr, nullptr}, *d_grp[2] = {nullptr, nullptr}, *d_max = nullptr;
-    auto scratch_free = [&]() { for (int w = 0; w < 2; ++w) { (void)hipFree(d_le[w]); (void)hipFree(d_pad[w]); (void)hipFree(d_grp[w]); } (void)hipFree(d_max); };
-    hipError_t e = hipMalloc((void **)&d_max, 4);
-    if (e == hipSuccess) e = hipMemset(d_max, 0, 4);
+    DeviceBuf<int> d_le[2], d_pad[2], d_grp[2], d_max;
+    hipError_t e = d_max.zeros(4);
     for (int w = 0; w < ns && e == hipSuccess; ++w) {
-        e = hipMalloc((void **)&d_le[w], 4 * (size_t)n_groups * 64);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_pad[w], 4 * (size_t)n_groups * 64);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_grp[w], 16 * (size_t)n_groups);
+        e = d_le[w].alloc(4 * (size_t)n_groups * 64);
+        if (e == hipSuccess) e = d_pad[w].alloc(4 * (size_t)n_groups * 64);
+        if (e == hipSuccess) e = d_grp[w].alloc(16 * (size_t)n_groups);
     }
-    if (e != hipSuccess) { scratch_free(); return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e)); }
+    if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
     std::vector<int32_t> grp[2];
     int max_col = 0;
     int rc = USPMV_OK;
@@ -1503,7 +1397,7 @@ static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog,
         if (e != hipSuccess) rc = uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     if (!rc && hipMemcpy(&max_col, d_max, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = uspmv::fail(USPMV_ERR_HIP, "%s: scan results", who);
-    if (rc) { scratch_free(); return rc; }
+    if (rc) return rc;
     // ---- which tiles sweep (sweep_plan.cpp pass 1), offsets
     std::vector<int32_t> tile_ids, t_smin, t_S, rest;
     std::vector<uint64_t> t_cnt_off;
@@ -1528,7 +1422,7 @@ static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog,
     if (n_sweep) *n_sweep = nsw;
     if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] sweep plan (device builder): tile_rows=%d wlog=%d tiles=%lld sweep=%lld rest_chunks=%zu cnt_bytes=%lld\n",
                                          tile_rows, wlog, (long long)nt, (long long)nsw, rest.size(), (long long)cnt_bytes);
-    if (nsw == 0) { scratch_free(); return USPMV_OK; }
+    if (nsw == 0) return USPMV_OK;
     std::vector<uint32_t> wave_off[2];
     for (int w = 0; w < ns; ++w) {
         wave_off[w].assign((size_t)(nsw * wpt), 0);
@@ -1538,53 +1432,44 @@ static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog,
                 const int64_t g = (int64_t)tile_ids[(size_t)k] * wpt + v;
                 if (g < n_groups) tot[w] += grp[w][(size_t)g * 4];
             }
-        if (tot[w] > (int64_t)UINT32_MAX) { scratch_free(); return USPMV_OK; }
+        if (tot[w] > (int64_t)UINT32_MAX) return USPMV_OK;
     }
     // ---- device arrays of the plan
     constexpr size_t SPARE = 64;
-    auto up = [&](const void *h, size_t bytes, void **d) {
-        if (e != hipSuccess) return;
-        e = hipMalloc(d, bytes ? bytes : 4);
-        if (e == hipSuccess && bytes) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-    };
-    auto zeroed = [&](size_t bytes, void **d) {
-        if (e != hipSuccess) return;
-        e = hipMalloc(d, bytes ? bytes : 4);
-        if (e == hipSuccess && bytes) e = hipMemset(*d, 0, bytes);
-    };
-    up(tile_ids.data(), tile_ids.size() * 4, (void **)&A->sw_tile_ids);
-    up(t_smin.data(), t_smin.size() * 4, (void **)&A->sw_smin);
-    up(t_S.data(), t_S.size() * 4, (void **)&A->sw_S);
-    up(t_cnt_off.data(), t_cnt_off.size() * 8, (void **)&A->sw_cnt_off);
-    up(wave_off[0].data(), wave_off[0].size() * 4, (void **)&A->sw_wave_off);
-    up(rest.data(), rest.size() * 4, (void **)&A->sw_rest);
-    zeroed((size_t)cnt_bytes, (void **)&A->sw_cnt);
-    zeroed(((size_t)tot[0] + SPARE) * vsz, &A->sw_vals);
-    zeroed(((size_t)tot[0] + SPARE) * 2, (void **)&A->sw_idx);
-    zeroed((size_t)(nsw * R) * 4, (void **)&A->sw_pad);
+    if (e == hipSuccess) e = A->sw.tile_ids.upload(tile_ids.data(), tile_ids.size() * 4);
+    if (e == hipSuccess) e = A->sw.smin.upload(t_smin.data(), t_smin.size() * 4);
+    if (e == hipSuccess) e = A->sw.S.upload(t_S.data(), t_S.size() * 4);
+    if (e == hipSuccess) e = A->sw.cnt_off.upload(t_cnt_off.data(), t_cnt_off.size() * 8);
+    if (e == hipSuccess) e = A->sw.wave_off.upload(wave_off[0].data(), wave_off[0].size() * 4);
+    if (e == hipSuccess) e = A->sw.rest.upload(rest.data(), rest.size() * 4);
+    if (e == hipSuccess) e = A->sw.cnt.zeros((size_t)cnt_bytes);
+    if (e == hipSuccess) e = A->sw.vals.zeros(((size_t)tot[0] + SPARE) * vsz);
+    if (e == hipSuccess) e = A->sw.idx.zeros(((size_t)tot[0] + SPARE) * 2);
+    if (e == hipSuccess) e = A->sw.pad.zeros((size_t)(nsw * R) * 4);
     if (B) {
-        up(wave_off[1].data(), wave_off[1].size() * 4, (void **)&A->sw_wave_off_b);
-        zeroed((size_t)cnt_bytes, (void **)&A->sw_cnt_b);
-        zeroed(((size_t)tot[1] + SPARE) * 4, (void **)&A->sw_vals_b);
-        zeroed(((size_t)tot[1] + SPARE) * 2, (void **)&A->sw_idx_b);
-        zeroed((size_t)(nsw * R) * 4, (void **)&A->sw_pad_b);
+        if (e == hipSuccess) e = A->sw.wave_off_b.upload(wave_off[1].data(), wave_off[1].size() * 4);
+        if (e == hipSuccess) e = A->sw.cnt_b.zeros((size_t)cnt_bytes);
+        if (e == hipSuccess) e = A->sw.vals_b.zeros(((size_t)tot[1] + SPARE) * 4);
+        if (e == hipSuccess) e = A->sw.idx_b.zeros(((size_t)tot[1] + SPARE) * 2);
+        if (e == hipSuccess) e = A->sw.pad_b.zeros((size_t)(nsw * R) * 4);
     }
-    if (e == hipSuccess && launch_sweep_fill(A, wlog, (int)R, (long)nsw, A->sw_tile_ids, A->sw_smin, A->sw_S, (const unsigned long long *)A->sw_cnt_off, A->sw_wave_off,
-                                             d_le[0], d_pad[0], A->sw_cnt, A->sw_vals, A->sw_idx, A->sw_pad, nullptr) != USPMV_OK) e = hipErrorUnknown;
-    if (e == hipSuccess && B && launch_sweep_fill(B, wlog, (int)R, (long)nsw, A->sw_tile_ids, A->sw_smin, A->sw_S, (const unsigned long long *)A->sw_cnt_off, A->sw_wave_off_b,
-                                                  d_le[1], d_pad[1], A->sw_cnt_b, A->sw_vals_b, A->sw_idx_b, A->sw_pad_b, nullptr) != USPMV_OK) e = hipErrorUnknown;
+    if (e == hipSuccess && launch_sweep_fill(A, wlog, (int)R, (long)nsw, A->sw.tile_ids, A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off,
+                                             d_le[0], d_pad[0], A->sw.cnt, A->sw.vals, A->sw.idx, A->sw.pad, nullptr) != USPMV_OK) e = hipErrorUnknown;
+    if (e == hipSuccess && B && launch_sweep_fill(B, wlog, (int)R, (long)nsw, A->sw.tile_ids, A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off_b,
+                                                  d_le[1], d_pad[1], A->sw.cnt_b, A->sw.vals_b, A->sw.idx_b, A->sw.pad_b, nullptr) != USPMV_OK) e = hipErrorUnknown;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    scratch_free();
+    for (int w = 0; w < 2; ++w) { d_le[w].reset(); d_pad[w].reset(); d_grp[w].reset(); }
+    d_max.reset();
     if (e != hipSuccess) {
-        sw_release(A);
+        A->sw = {};
         return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     static uint64_t next_dev_sweep_id = (uint64_t)1 << 41;
     const uint64_t id = next_dev_sweep_id++;
-    A->sw = true; A->sw_tile_rows = tile_rows; A->sw_wlog = wlog; A->sw_n_tiles = nsw; A->sw_all_tiles = nt;
-    A->sw_x_len = (int64_t)max_col + 1; A->sw_n_rest = (int64_t)rest.size(); A->sw_plan_id = id;
-    A->sw_n_vals = tot[0]; A->sw_n_vals_b = B ? tot[1] : 0; A->sw_cnt_bytes = cnt_bytes;
-    if (B) { B->sw = true; B->sw_plan_id = id; B->sw_n_tiles = nsw; B->sw_all_tiles = nt; }
+    A->sw.on = true; A->sw.tile_rows = tile_rows; A->sw.wlog = wlog; A->sw.n_tiles = nsw; A->sw.all_tiles = nt;
+    A->sw.x_len = (int64_t)max_col + 1; A->sw.n_rest = (int64_t)rest.size(); A->sw.plan_id = id;
+    A->sw.n_vals = tot[0]; A->sw.n_vals_b = B ? tot[1] : 0; A->sw.cnt_bytes = cnt_bytes;
+    if (B) { B->sw.on = true; B->sw.plan_id = id; B->sw.n_tiles = nsw; B->sw.all_tiles = nt; }
     return USPMV_OK;
 }
 
@@ -1610,14 +1495,6 @@ int uspmv_dmat_optimize_sweep_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv
     return sweep_plan_install(dp, sp, s_dp, s_sp, wlog, tile_rows, n_tiles, n_sweep, "uspmv_dmat_optimize_sweep_ap");
 }
 
-static void bw_release(uspmv_dmat_t *A) {
-    (void)hipFree(A->bw_tile_ids); (void)hipFree(A->bw_win_ptr); (void)hipFree(A->bw_wins); (void)hipFree(A->bw_pad); (void)hipFree(A->bw_cnt_off);
-    (void)hipFree(A->bw_wave_off); (void)hipFree(A->bw_cnt); (void)hipFree(A->bw_vals); (void)hipFree(A->bw_idx);
-    A->bw_tile_ids = A->bw_win_ptr = A->bw_wins = A->bw_pad = nullptr; A->bw_cnt_off = nullptr; A->bw_wave_off = nullptr; A->bw_cnt = nullptr;
-    A->bw_vals = nullptr; A->bw_idx = nullptr;
-    A->bw = false; A->bw_n_tiles = A->bw_all_tiles = 0; A->bw_b = 0;
-}
-
 // The block-vector column-window sweep plan (host/sweep_plan.cpp: uspmv_build_block_sweep_plan; kernel csrc/spmmv_sweep.hip) for 64-byte X
 // rows.  Installed only when EVERY tile sweeps (rows column-sorted at window granularity, staging within "spmmv_sweep_max_stage" bytes
 // per non-zero); otherwise the handle keeps whatever block plan it has.  wlog / tile_rows 0 = defaults (2^11 rows = 128 KiB windows, one
@@ -1628,7 +1505,7 @@ int uspmv_dmat_optimize_block_sweep(uspmv_dmat_t *A, const uspmv_scs_t *s, int b
     if (A->C != s->C || A->n_chunks != s->n_chunks || A->dtype != s->dtype)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block_sweep: handle and host struct do not describe the same matrix");
     if (int rc = require_device()) return rc;
-    if (A->bw) bw_release(A);
+    A->bw = {};
     if (n_tiles) *n_tiles = 0;
     if (n_sweep) *n_sweep = 0;
     const size_t vsz = s->dtype == USPMV_F64 ? 8 : 4;
@@ -1652,39 +1529,24 @@ int uspmv_dmat_optimize_block_sweep(uspmv_dmat_t *A, const uspmv_scs_t *s, int b
                 (double)p.windows_staged * (double)((int64_t)1 << p.wlog) / (double)std::max<int64_t>(s->n_chunks * s->C, 1), p.cnt.size());
     if (!p.valid || p.n_sweep_tiles != p.n_tiles || !p.rest_chunks.empty()) return USPMV_OK;
     hipError_t e = hipSuccess;
-    auto up = [&](const void *h, size_t bytes, void **d) {
-        if (e != hipSuccess) return;
-        e = hipMalloc(d, bytes ? bytes : 4);
-        if (e == hipSuccess && bytes) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-    };
-    up(p.tile_ids.data(), p.tile_ids.size() * 4, (void **)&A->bw_tile_ids);
-    up(p.t_win_ptr.data(), p.t_win_ptr.size() * 4, (void **)&A->bw_win_ptr);
-    up(p.wins.data(), p.wins.size() * 4, (void **)&A->bw_wins);
-    up(p.t_cnt_off.data(), p.t_cnt_off.size() * 8, (void **)&A->bw_cnt_off);
-    up(p.wave_off.data(), p.wave_off.size() * 4, (void **)&A->bw_wave_off);
-    up(p.cnt.data(), p.cnt.size(), (void **)&A->bw_cnt);
-    up(vsz == 8 ? (const void *)p.vals_f64.data() : (const void *)p.vals_f32.data(), p.idx.size() * vsz, &A->bw_vals);
-    up(p.idx.data(), p.idx.size() * 2, (void **)&A->bw_idx);
-    up(p.pad_col.data(), p.pad_col.size() * 4, (void **)&A->bw_pad);
-    if (e != hipSuccess) { bw_release(A); (void)hipGetLastError(); return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize_block_sweep: %s", hipGetErrorString(e)); }
-    A->bw = true; A->bw_tile_rows = p.tile_rows; A->bw_wlog = p.wlog; A->bw_b = block_vec_size;
-    A->bw_n_tiles = p.n_sweep_tiles; A->bw_all_tiles = p.n_tiles; A->bw_x_rows = p.x_rows_min; A->bw_windows = p.windows_staged;
+    if (e == hipSuccess) e = A->bw.tile_ids.upload(p.tile_ids.data(), p.tile_ids.size() * 4);
+    if (e == hipSuccess) e = A->bw.win_ptr.upload(p.t_win_ptr.data(), p.t_win_ptr.size() * 4);
+    if (e == hipSuccess) e = A->bw.wins.upload(p.wins.data(), p.wins.size() * 4);
+    if (e == hipSuccess) e = A->bw.cnt_off.upload(p.t_cnt_off.data(), p.t_cnt_off.size() * 8);
+    if (e == hipSuccess) e = A->bw.wave_off.upload(p.wave_off.data(), p.wave_off.size() * 4);
+    if (e == hipSuccess) e = A->bw.cnt.upload(p.cnt.data(), p.cnt.size());
+    if (e == hipSuccess) e = A->bw.vals.upload(vsz == 8 ? (const void *)p.vals_f64.data() : (const void *)p.vals_f32.data(), p.idx.size() * vsz);
+    if (e == hipSuccess) e = A->bw.idx.upload(p.idx.data(), p.idx.size() * 2);
+    if (e == hipSuccess) e = A->bw.pad.upload(p.pad_col.data(), p.pad_col.size() * 4);
+    if (e != hipSuccess) { A->bw = {}; (void)hipGetLastError(); return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize_block_sweep: %s", hipGetErrorString(e)); }
+    A->bw.on = true; A->bw.tile_rows = p.tile_rows; A->bw.wlog = p.wlog; A->bw.b = block_vec_size;
+    A->bw.n_tiles = p.n_sweep_tiles; A->bw.all_tiles = p.n_tiles; A->bw.x_rows = p.x_rows_min; A->bw.windows = p.windows_staged;
     return USPMV_OK;
 }
 
 void uspmv_dmat_free(uspmv_dmat_t *A) {
     if (!A) return;
-    if (A->bw) bw_release(A);
-    if (A->sw) sw_release(A);
-    if (A->alt) { uspmv_dmat_free(A->alt); A->alt = nullptr; }
-    if (A->tlc) tlc_release(A);
-    if (A->bt || A->pb) bt_release(A);
-    part_release(A, 0); part_release(A, 1);
-    if (A->ws) (void)hipFree(A->ws);
-    if (A->owns) {
-        (void)hipFree((void *)A->chunk_ptrs); (void)hipFree((void *)A->chunk_lengths);
-        (void)hipFree((void *)A->col_idxs); (void)hipFree((void *)A->values);
-    }
+    uspmv_dmat_free(A->alt);
     delete A;
 }
 
@@ -1728,8 +1590,8 @@ int uspmv_spmv_chunks(const uspmv_dmat_t *A, const int32_t *d_chunk_ids, int64_t
 int uspmv_spmv_tiles(const uspmv_dmat_t *A, const int32_t *d_tile_ids, int64_t n_ids, const void *d_x, void *d_y,
                      void *stream) {
     if (int rc = check_dmat(A, "uspmv_spmv_tiles")) return rc;
-    if (!A->tlc || A->tlc_plan_id != 0) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_tiles: handle has no tile-local-column plan (uspmv_dmat_optimize)");
-    if (n_ids < 0 || n_ids > A->tlc_n_tiles || (n_ids > 0 && !d_tile_ids) || !d_x || !d_y)
+    if (!A->tlc.on || A->tlc.plan_id != 0) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_tiles: handle has no tile-local-column plan (uspmv_dmat_optimize)");
+    if (n_ids < 0 || n_ids > A->tlc.n_tiles || (n_ids > 0 && !d_tile_ids) || !d_x || !d_y)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_tiles: bad argument");
     if ((uintptr_t)d_x % 16) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_tiles: x must be 16-byte aligned");
     if (int rc = require_device()) return rc;
@@ -1753,9 +1615,9 @@ int uspmv_dmat_sweep_plan_digest(const uspmv_dmat_t *A, uint64_t digest[16], int
     if (int rc = check_dmat(A, "uspmv_dmat_sweep_plan_digest")) return rc;
     if (!digest || !meta) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_sweep_plan_digest: NULL argument");
     for (int k = 0; k < 16; ++k) digest[k] = 0;
-    meta[0] = A->sw; meta[1] = A->sw_tile_rows; meta[2] = A->sw_wlog; meta[3] = A->sw_n_tiles; meta[4] = A->sw_all_tiles; meta[5] = A->sw_n_rest;
-    meta[6] = A->sw_n_vals; meta[7] = A->sw_n_vals_b;
-    if (!A->sw || !A->sw_tile_ids) return USPMV_OK;
+    meta[0] = A->sw.on; meta[1] = A->sw.tile_rows; meta[2] = A->sw.wlog; meta[3] = A->sw.n_tiles; meta[4] = A->sw.all_tiles; meta[5] = A->sw.n_rest;
+    meta[6] = A->sw.n_vals; meta[7] = A->sw.n_vals_b;
+    if (!A->sw.on || !A->sw.tile_ids) return USPMV_OK;
     std::vector<unsigned char> buf;
     auto fnv = [&](const void *d, size_t bytes, uint64_t *out) -> int {
         uint64_t h = 1469598103934665603ull;
@@ -1767,23 +1629,23 @@ int uspmv_dmat_sweep_plan_digest(const uspmv_dmat_t *A, uint64_t digest[16], int
         *out = h;
         return USPMV_OK;
     };
-    const size_t nsw = (size_t)A->sw_n_tiles, wpt = (size_t)A->sw_tile_rows / 64, vsz = A->dtype == USPMV_F64 ? 8 : 4;
-    int rc = fnv(A->sw_tile_ids, nsw * 4, &digest[0]);
-    if (!rc) rc = fnv(A->sw_smin, nsw * 4, &digest[1]);
-    if (!rc) rc = fnv(A->sw_S, nsw * 4, &digest[2]);
-    if (!rc) rc = fnv(A->sw_cnt_off, nsw * 8, &digest[3]);
-    if (!rc) rc = fnv(A->sw_wave_off, nsw * wpt * 4, &digest[4]);
-    if (!rc) rc = fnv(A->sw_cnt, (size_t)A->sw_cnt_bytes, &digest[5]);
-    if (!rc) rc = fnv(A->sw_vals, (size_t)A->sw_n_vals * vsz, &digest[6]);
-    if (!rc) rc = fnv(A->sw_idx, (size_t)A->sw_n_vals * 2, &digest[7]);
-    if (!rc) rc = fnv(A->sw_pad, nsw * (size_t)A->sw_tile_rows * 4, &digest[8]);
-    if (!rc) rc = fnv(A->sw_rest, (size_t)A->sw_n_rest * 4, &digest[9]);
-    if (!rc && A->sw_idx_b) {
-        rc = fnv(A->sw_wave_off_b, nsw * wpt * 4, &digest[10]);
-        if (!rc) rc = fnv(A->sw_cnt_b, (size_t)A->sw_cnt_bytes, &digest[11]);
-        if (!rc) rc = fnv(A->sw_vals_b, (size_t)A->sw_n_vals_b * 4, &digest[12]);
-        if (!rc) rc = fnv(A->sw_idx_b, (size_t)A->sw_n_vals_b * 2, &digest[13]);
-        if (!rc) rc = fnv(A->sw_pad_b, nsw * (size_t)A->sw_tile_rows * 4, &digest[14]);
+    const size_t nsw = (size_t)A->sw.n_tiles, wpt = (size_t)A->sw.tile_rows / 64, vsz = A->dtype == USPMV_F64 ? 8 : 4;
+    int rc = fnv(A->sw.tile_ids, nsw * 4, &digest[0]);
+    if (!rc) rc = fnv(A->sw.smin, nsw * 4, &digest[1]);
+    if (!rc) rc = fnv(A->sw.S, nsw * 4, &digest[2]);
+    if (!rc) rc = fnv(A->sw.cnt_off, nsw * 8, &digest[3]);
+    if (!rc) rc = fnv(A->sw.wave_off, nsw * wpt * 4, &digest[4]);
+    if (!rc) rc = fnv(A->sw.cnt, (size_t)A->sw.cnt_bytes, &digest[5]);
+    if (!rc) rc = fnv(A->sw.vals, (size_t)A->sw.n_vals * vsz, &digest[6]);
+    if (!rc) rc = fnv(A->sw.idx, (size_t)A->sw.n_vals * 2, &digest[7]);
+    if (!rc) rc = fnv(A->sw.pad, nsw * (size_t)A->sw.tile_rows * 4, &digest[8]);
+    if (!rc) rc = fnv(A->sw.rest, (size_t)A->sw.n_rest * 4, &digest[9]);
+    if (!rc && A->sw.idx_b) {
+        rc = fnv(A->sw.wave_off_b, nsw * wpt * 4, &digest[10]);
+        if (!rc) rc = fnv(A->sw.cnt_b, (size_t)A->sw.cnt_bytes, &digest[11]);
+        if (!rc) rc = fnv(A->sw.vals_b, (size_t)A->sw.n_vals_b * 4, &digest[12]);
+        if (!rc) rc = fnv(A->sw.idx_b, (size_t)A->sw.n_vals_b * 2, &digest[13]);
+        if (!rc) rc = fnv(A->sw.pad_b, nsw * (size_t)A->sw.tile_rows * 4, &digest[14]);
     }
     return rc;
 }
@@ -1792,8 +1654,8 @@ int uspmv_dmat_plan_info(const uspmv_dmat_t *A, int *kind, int64_t *n_tiles, int
     if (!A) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_plan_info: NULL matrix");
     const uspmv_dmat_t *M = A->alt ? A->alt : A;
     int k = 0; int64_t nt = 0, np = 0;
-    if (M->sw) { k = 2; nt = M->sw_all_tiles; np = M->sw_n_tiles; }
-    else if (M->tlc) { k = 1; nt = M->tlc_n_tiles; np = M->tlc_staged; }
+    if (M->sw.on) { k = 2; nt = M->sw.all_tiles; np = M->sw.n_tiles; }
+    else if (M->tlc.on) { k = 1; nt = M->tlc.n_tiles; np = M->tlc.staged; }
     if (kind) *kind = k;
     if (n_tiles) *n_tiles = nt;
     if (n_planned) *n_planned = np;
@@ -1806,7 +1668,7 @@ int uspmv_dmat_block_plan_digest(const uspmv_dmat_t *A0, uint64_t digest[8]) {
     if (!digest) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_block_plan_digest: NULL argument");
     const uspmv_dmat_t *A = (A0->alt && g_tune.rechunk) ? A0->alt : A0;
     for (int k = 0; k < 8; ++k) digest[k] = 0;
-    if (!A->pb) return USPMV_OK;
+    if (!A->pb.on) return USPMV_OK;
     std::vector<unsigned char> buf;
     auto fnv = [&](const void *d, size_t bytes, uint64_t *out) -> int {
         uint64_t h = 1469598103934665603ull;
@@ -1818,68 +1680,68 @@ int uspmv_dmat_block_plan_digest(const uspmv_dmat_t *A0, uint64_t digest[8]) {
         *out = h;
         return USPMV_OK;
     };
-    const size_t nt = (size_t)A->pb_n_tiles, nph = (size_t)A->pb_n_phases, nc = (size_t)A->n_chunks, vsz = A->dtype == USPMV_F64 ? 8 : 4;
+    const size_t nt = (size_t)A->pb.n_tiles, nph = (size_t)A->pb.n_phases, nc = (size_t)A->n_chunks, vsz = A->dtype == USPMV_F64 ? 8 : 4;
     int32_t n_list = 0;
     uint32_t tot16 = 0;
-    HIP_TRY(hipMemcpy(&n_list, A->pb_list_ptr + nph, 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&tot16, A->pb_c16_ptrs + nc, 4, hipMemcpyDeviceToHost));
-    int rc = fnv(A->pb_ph_ptr, (nt + 1) * 4, &digest[0]);
-    if (!rc) rc = fnv(A->pb_g0, nph * 4, &digest[1]);
-    if (!rc) rc = fnv(A->pb_list_ptr, (nph + 1) * 4, &digest[2]);
-    if (!rc) rc = fnv(A->pb_xrows, (size_t)n_list * 4, &digest[3]);
-    if (!rc) rc = fnv(A->pb_c16_ptrs, (nc + 1) * 4, &digest[4]);
-    if (!rc) rc = fnv(A->pb_col16, (size_t)tot16 * (A->pb_idx8 ? 1 : 2), &digest[5]);
-    if (!rc) rc = fnv(A->pb_values, (size_t)tot16 * vsz, &digest[6]);
-    if (!rc) rc = fnv(A->bt_row_map, A->bt_row_map ? nc * (size_t)A->C * 4 : 0, &digest[7]);
+    HIP_TRY(hipMemcpy(&n_list, A->pb.list_ptr + nph, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&tot16, A->pb.c16_ptrs + nc, 4, hipMemcpyDeviceToHost));
+    int rc = fnv(A->pb.ph_ptr, (nt + 1) * 4, &digest[0]);
+    if (!rc) rc = fnv(A->pb.g0, nph * 4, &digest[1]);
+    if (!rc) rc = fnv(A->pb.list_ptr, (nph + 1) * 4, &digest[2]);
+    if (!rc) rc = fnv(A->pb.xrows, (size_t)n_list * 4, &digest[3]);
+    if (!rc) rc = fnv(A->pb.c16_ptrs, (nc + 1) * 4, &digest[4]);
+    if (!rc) rc = fnv(A->pb.col16, (size_t)tot16 * (A->pb.idx8 ? 1 : 2), &digest[5]);
+    if (!rc) rc = fnv(A->pb.values, (size_t)tot16 * vsz, &digest[6]);
+    if (!rc) rc = fnv(A->bt.row_map, A->bt.row_map ? nc * (size_t)A->C * 4 : 0, &digest[7]);
     return rc;
 }
 
 int uspmv_dmat_block_plan_staged(const uspmv_dmat_t *A, int64_t *rows_staged) {
     if (!A || !rows_staged) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_block_plan_staged: NULL argument");
     const uspmv_dmat_t *M = (A->alt && g_tune.rechunk) ? A->alt : A;
-    *rows_staged = M->pb ? M->pb_rows_staged : 0;
+    *rows_staged = M->pb.on ? M->pb.rows_staged : 0;
     return USPMV_OK;
 }
 
 int uspmv_dmat_block_plan_info(const uspmv_dmat_t *A, int64_t meta[10]) {
     if (!A || !meta) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_block_plan_info: NULL argument");
     const uspmv_dmat_t *M = (A->alt && g_tune.rechunk) ? A->alt : A;
-    meta[0] = M->bt; meta[1] = M->pb; meta[2] = M->pl; meta[3] = M->pb_n_tiles; meta[4] = M->pb_n_phases; meta[5] = M->pl_n_phases;
-    meta[6] = M->pl_rows_staged; meta[7] = M->pb_idx8; meta[8] = M->pb_device_built; meta[9] = M->pb_max_rows;
+    meta[0] = M->bt.on; meta[1] = M->pb.on; meta[2] = M->pl.on; meta[3] = M->pb.n_tiles; meta[4] = M->pb.n_phases; meta[5] = M->pl.n_phases;
+    meta[6] = M->pl.rows_staged; meta[7] = M->pb.idx8; meta[8] = M->pb.device_built; meta[9] = M->pb.max_rows;
     return USPMV_OK;
 }
 
 int uspmv_dmat_plan_granularity(const uspmv_dmat_t *A, int *elements_per_list_entry) {
     if (!A || !elements_per_list_entry) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_plan_granularity: NULL argument");
     const uspmv_dmat_t *M = (A->alt && g_tune.rechunk) ? A->alt : A;
-    *elements_per_list_entry = !M->tlc ? 0 : M->tlc_elem ? 1 : 16;
+    *elements_per_list_entry = !M->tlc.on ? 0 : M->tlc.elem ? 1 : 16;
     return USPMV_OK;
 }
 
 int uspmv_dmat_plan_rows_dealt(const uspmv_dmat_t *A, int *dealt) {
     if (!A || !dealt) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_plan_rows_dealt: NULL argument");
     const uspmv_dmat_t *M = (A->alt && g_tune.rechunk) ? A->alt : A;
-    *dealt = M->tlc && M->tlc_row_map != nullptr;
+    *dealt = M->tlc.on && M->tlc.row_map != nullptr;
     return USPMV_OK;
 }
 
 int uspmv_dmat_stream_info(const uspmv_dmat_t *A, int64_t meta[2]) {
     if (!A || !meta) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_stream_info: NULL argument");
     const uspmv_dmat_t *M = (A->alt && g_tune.rechunk) ? A->alt : A;
-    meta[0] = M->ps_desc ? M->ps_grid : 0; meta[1] = M->ps_desc ? M->ps_n_desc : 0;
+    meta[0] = M->ps.desc ? M->ps.grid : 0; meta[1] = M->ps.desc ? M->ps.n_desc : 0;
     return USPMV_OK;
 }
 
 int uspmv_dmat_tile_rows(const uspmv_dmat_t *A, int *tile_rows) {
     if (!A || !tile_rows) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_tile_rows: NULL argument");
-    *tile_rows = A->tlc ? A->tlc_tile_rows : 0;
+    *tile_rows = A->tlc.on ? A->tlc.tile_rows : 0;
     return USPMV_OK;
 }
 
 int uspmv_dmat_index_bits(const uspmv_dmat_t *A, int *bits) {
     if (!A || !bits) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_index_bits: NULL argument");
     const uspmv_dmat_t *M = (A->alt && g_tune.rechunk) ? A->alt : A;
-    *bits = !M->tlc ? 0 : M->tlc_col12 ? 12 : 16;
+    *bits = !M->tlc.on ? 0 : M->tlc.col12 ? 12 : 16;
     return USPMV_OK;
 }
 

@@ -12,18 +12,83 @@
 
 #include "../host/uspmv_internal.hpp"
 
+// An owned device allocation (host code only): move-only, freed by its destructor or reset().  Every helper frees what the buffer
+// held, allocates at least MIN_BYTES and returns the HIP status; on failure the buffer is empty or holds the new, unfilled allocation.
+template <typename T>
+class DeviceBuf {
+  public:
+    static constexpr size_t MIN_BYTES = 16;
+    DeviceBuf() = default;
+    DeviceBuf(const DeviceBuf &) = delete;
+    DeviceBuf &operator=(const DeviceBuf &) = delete;
+    DeviceBuf(DeviceBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DeviceBuf &operator=(DeviceBuf &&o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~DeviceBuf() { reset(); }
+    void reset() {
+        if (p_) (void)hipFree((void *)p_);
+        p_ = nullptr;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    template <typename U>
+    explicit operator U *() const { return (U *)p_; }   // the launchers' casts: (const VT *)A->pb.values, (const int *)A->ps.wg_ptr, ...
+    hipError_t alloc(size_t bytes) {
+        reset();
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, std::max(bytes, MIN_BYTES));
+        p_ = (T *)q;
+        return e;
+    }
+    hipError_t zeros(size_t bytes) {
+        hipError_t e = alloc(bytes);
+        if (e == hipSuccess && bytes) e = hipMemset((void *)p_, 0, bytes);
+        return e;
+    }
+    hipError_t upload(const void *host, size_t bytes) {
+        hipError_t e = alloc(bytes);
+        if (e == hipSuccess && bytes) e = hipMemcpy((void *)p_, host, bytes, hipMemcpyHostToDevice);
+        return e;
+    }
+
+  private:
+    T *p_ = nullptr;
+};
+
+// The device matrix.  Every plan family is one member struct holding its device arrays and metadata; `on` says the plan is installed,
+// and assigning {} to the member releases the plan and resets every field of it.
 struct uspmv_dmat {
+    uspmv_dmat() = default;
+    uspmv_dmat(const uspmv_dmat &) = delete;
+    uspmv_dmat &operator=(const uspmv_dmat &) = delete;
+
     int64_t C = 0, n_chunks = 0, n_elements = 0;
     int dtype = USPMV_F64;
+    // the SELL-C-sigma arrays: views of `own` (uspmv_dmat_upload and the device conversions) or of the caller's arrays (uspmv_dmat_wrap)
     const int32_t *chunk_ptrs = nullptr, *chunk_lengths = nullptr, *col_idxs = nullptr;
     const void *values = nullptr;
-    bool owns = false;
+    struct {
+        DeviceBuf<int32_t> chunk_ptrs, chunk_lengths, col_idxs;
+        DeviceBuf<void> values;
+    } own;
+    // allocates `own` for the handle's n_chunks / n_elements / dtype and points the views at it
+    hipError_t own_arrays() {
+        const size_t ne = (size_t)std::max<int64_t>(n_elements, 1);
+        hipError_t e = own.chunk_ptrs.alloc(4 * ((size_t)n_chunks + 1));
+        if (e == hipSuccess) e = own.chunk_lengths.alloc(4 * (size_t)std::max<int64_t>(n_chunks, 1));
+        if (e == hipSuccess) e = own.col_idxs.alloc(4 * ne);
+        if (e == hipSuccess) e = own.values.alloc((dtype == USPMV_F64 ? 8 : 4) * ne);
+        chunk_ptrs = own.chunk_ptrs; chunk_lengths = own.chunk_lengths; col_idxs = own.col_idxs; values = own.values;
+        return e;
+    }
     bool crs = false;
     long n_store = 0;              // rows of y the kernels may write (= n_chunks*C unless re-chunked)
     uspmv_dmat *alt = nullptr;     // internal C = 32 re-chunking of a C in {1,2,4,8,16} struct (same row order)
     // scratch for the internal row-major copies of column-major block vectors (uspmv_spmmv); grown
     // on demand, released with the handle.  Not thread-safe per handle, like the reference's kernel object.
-    mutable void *ws = nullptr;
+    mutable DeviceBuf<void> ws;
     mutable size_t ws_bytes = 0;
     // uspmv_spmmv_x_prepared: the workspace holds the re-laid-out copy of THIS column-major X (b, ld; form 1 plain / 2 sigma permutation undone)
     mutable const void *xprep_ptr = nullptr;
@@ -34,97 +99,113 @@ struct uspmv_dmat {
     // row order (gather kernels), order 1 = the phased plan's tie-re-ordered rows (scs_spmmv_quadph), classified per 64-row plan tile.
     // `part` selects around ONE launch: 0 the whole matrix, 1 interior, 2 boundary; column-major callers: part 1 re-lays out X rows
     // [0, part_split) into the workspace, part 2 the rest (the halo rows, after the exchange).
-    int32_t *part_len[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    DeviceBuf<int32_t> part_len[2][2];
     int part = 0;
     long part_split = 0;
-    // tile-local-column plan (host/tlc_plan.cpp), device copies owned by the handle
-    bool tlc = false;
-    bool tlc_elem = false;   // the plan lists single x ELEMENTS instead of 16-element lines (tlc_max_lines counts elements): rows whose columns are scattered
+    // tile-local-column plan (host/tlc_plan.cpp)
+    struct TlcPlan {
+        bool on = false;
+        bool elem = false;   // the plan lists single x ELEMENTS instead of 16-element lines (max_lines counts elements): rows whose columns are scattered
                              // (a numbering that is only locally coherent) -- uspmv_dmat_optimize falls to it when the line plan stages too few tiles
-    int tlc_max_lines = 0, tlc_tile_rows = 256;
-    int64_t tlc_x_len = 0, tlc_n_tiles = 0, tlc_staged = 0;
-    uint64_t tlc_plan_id = 0;   // structs planned together (ap pair) carry the same non-zero id
-    int32_t *tlc_line_ptr = nullptr, *tlc_lines = nullptr;
-    uint32_t *tlc_c16_ptrs = nullptr;
-    uint16_t *tlc_col16 = nullptr;
-    // ... and the same local indices packed to 12 bits (plans of at most 256 lines per tile: 9.5 instead of 10 bytes per non-zero of the stream):
-    // per chunk, at tlc_c12_ptrs[c] dwords: for every PAIR of slot groups [row][3 dwords] (96 bits per row = 8 indices, one 12-byte load per
-    // lane; three planes of C dwords measured 3 % slower), then for an odd last group one plane of C dwords + one of C ushorts (48 bits per
-    // row).  What scs_spmv_tlc reads when present.
-    uint32_t *tlc_c12_ptrs = nullptr, *tlc_col12 = nullptr;
-    // element plan over rows DEALT TO THE TILES BY THE MATRIX GRAPH (uspmv_scs_reorder_rows mode 4, as for the block plan): a private copy of the values in that
-    // order and row_map[plan row] = row of y.  Null when the caller's row order is kept.
-    void *tlc_values = nullptr;
-    int32_t *tlc_row_map = nullptr, *tlc_cols = nullptr;     // (tlc_cols: the column indices in that order, for the few tiles that do not stage)
+        int max_lines = 0, tile_rows = 256;
+        int64_t x_len = 0, n_tiles = 0, staged = 0;
+        uint64_t plan_id = 0;   // structs planned together (ap pair) carry the same non-zero id
+        DeviceBuf<int32_t> line_ptr, lines;
+        DeviceBuf<uint32_t> c16_ptrs;
+        DeviceBuf<uint16_t> col16;
+        // ... and the same local indices packed to 12 bits (plans of at most 256 lines per tile: 9.5 instead of 10 bytes per non-zero of the stream):
+        // per chunk, at c12_ptrs[c] dwords: for every PAIR of slot groups [row][3 dwords] (96 bits per row = 8 indices, one 12-byte load per
+        // lane; three planes of C dwords measured 3 % slower), then for an odd last group one plane of C dwords + one of C ushorts (48 bits per
+        // row).  What scs_spmv_tlc reads when present.
+        DeviceBuf<uint32_t> c12_ptrs, col12;
+        // element plan over rows DEALT TO THE TILES BY THE MATRIX GRAPH (uspmv_scs_reorder_rows mode 4, as for the block plan): a private copy of the values in that
+        // order and row_map[plan row] = row of y.  Null when the caller's row order is kept.
+        DeviceBuf<void> values;
+        DeviceBuf<int32_t> row_map, cols;     // (cols: the column indices in that order, for the few tiles that do not stage)
+    } tlc;
     // block (SpMMV) plan: 64-row tiles, per tile the list of X rows it touches (uspmv_dmat_optimize_block)
-    bool bt = false;
-    int bt_max_rows = 0, bt_tile_rows = 64;
-    int64_t bt_n_tiles = 0, bt_staged = 0;
-    int32_t *bt_line_ptr = nullptr, *bt_xrows = nullptr;
-    uint32_t *bt_c16_ptrs = nullptr;
-    uint16_t *bt_col16 = nullptr;
-    // the plan's private copy of the entries with ties of the sigma sort back in original-row order
-    // (uspmv_scs_reorder_ties): values (+ 32-bit columns when some tile keeps the gather path) and
-    // row_map[plan row] = row of y.  All null when the caller's order is kept.
-    void *bt_values = nullptr;
-    int32_t *bt_cols = nullptr, *bt_row_map = nullptr;
+    struct BlockPlan {
+        bool on = false;
+        int max_rows = 0, tile_rows = 64;
+        int64_t n_tiles = 0, staged = 0;
+        DeviceBuf<int32_t> line_ptr, xrows;
+        DeviceBuf<uint32_t> c16_ptrs;
+        DeviceBuf<uint16_t> col16;
+        // the plan's private copy of the entries with ties of the sigma sort back in original-row order
+        // (uspmv_scs_reorder_ties): values (+ 32-bit columns when some tile keeps the gather path) and
+        // row_map[plan row] = row of y.  All null when the caller's order is kept.
+        DeviceBuf<void> values;
+        DeviceBuf<int32_t> cols, row_map;
+    } bt;
     // phased block plan (uspmv_build_phased_plan; 64-byte X rows): per tile a run of phases, each with its own X-row list
-    bool pb = false;
-    int pb_cap_rows = 0, pb_ngp = 0, pb_max_rows = 0;
-    int64_t pb_n_tiles = 0, pb_n_phases = 0, pb_rows_staged = 0;
-    int32_t *pb_ph_ptr = nullptr, *pb_g0 = nullptr, *pb_list_ptr = nullptr, *pb_xrows = nullptr;
-    void *pb_values = nullptr;          // the entries again, GROUP-major like pb_col16 ([chunk][group of four slots][row][slot % 4])
-    uint32_t *pb_c16_ptrs = nullptr;
-    uint16_t *pb_col16 = nullptr;       // phase-local indices; ONE BYTE each when pb_idx8 (no phase lists more than 256 rows)
-    bool pb_idx8 = false;
-    bool pb_device_built = false;       // the plan's index part was built by csrc/block_plan_kernels.hip
+    struct PhasedPlan {
+        bool on = false;
+        int cap_rows = 0, ngp = 0, max_rows = 0;
+        int64_t n_tiles = 0, n_phases = 0, rows_staged = 0;
+        DeviceBuf<int32_t> ph_ptr, g0, list_ptr, xrows;
+        DeviceBuf<void> values;             // the entries again, GROUP-major like col16 ([chunk][group of four slots][row][slot % 4])
+        DeviceBuf<uint32_t> c16_ptrs;
+        DeviceBuf<uint16_t> col16;          // phase-local indices; ONE BYTE each when idx8 (no phase lists more than 256 rows)
+        bool idx8 = false;
+        bool device_built = false;          // the plan's index part was built by csrc/block_plan_kernels.hip
+    } pb;
     // the phased plan once more as a flat schedule of 32-byte phase descriptors for persistent workgroups (spmmv_stream.hip; "spmmv_stream")
-    int ps_grid = 0;
-    bool ps_per_tile = false;           // the schedule has one tile per workgroup ("spmmv_stream" 99)
-    int64_t ps_n_desc = 0;
-    int32_t *ps_wg_ptr = nullptr;
-    void *ps_desc = nullptr;
+    struct StreamSchedule {
+        int grid = 0;
+        bool per_tile = false;              // the schedule has one tile per workgroup ("spmmv_stream" 99)
+        int64_t n_desc = 0;
+        DeviceBuf<int32_t> wg_ptr;
+        DeviceBuf<void> desc;
+    } ps;
     // the same plan once more with LINE lists (128 bytes of one column: 16 doubles / 32 floats) for column-major block vectors:
-    // shares pb_values / pb_c16_ptrs / the row map; one-byte local indices (line << shift | row in line)
-    bool pl = false;
-    int pl_shift = 0, pl_max_rows = 0;
-    int64_t pl_n_phases = 0, pl_rows_staged = 0;
-    int32_t *pl_ph_ptr = nullptr, *pl_g0 = nullptr, *pl_list_ptr = nullptr, *pl_lines = nullptr;
-    uint8_t *pl_col8 = nullptr;
+    // shares pb.values / pb.c16_ptrs / the row map; one-byte local indices (line << shift | row in line)
+    struct LinePlan {
+        bool on = false;
+        int shift = 0, max_rows = 0;
+        int64_t n_phases = 0, rows_staged = 0;
+        DeviceBuf<int32_t> ph_ptr, g0, list_ptr, lines;
+        DeviceBuf<uint8_t> col8;
+    } pl;
     // ... and once more for column-major block vectors behind the re-layout pass, with the X rows numbered in the ORIGINAL row order:
     // the pass that turns the caller's column-major X into the row-major workspace also undoes the sigma permutation
     // (Xr[r] = X[old_to_new[r]]), so a tile's X rows form long runs again instead of ~30 fragments per phase and a 128-byte line of the
-    // workspace holds two rows the tile needs instead of 1.1 (shares pb_values / pb_c16_ptrs / the row map)
-    bool pu = false;
-    int pu_max_rows = 0;
-    int64_t pu_n_phases = 0, pu_n_perm = 0;
-    int32_t *pu_ph_ptr = nullptr, *pu_g0 = nullptr, *pu_list_ptr = nullptr, *pu_xrows = nullptr, *pu_perm = nullptr;
-    uint8_t *pu_col8 = nullptr;
-    // block-vector column-window sweep plan (uspmv_build_block_sweep_plan, csrc/spmmv_sweep.hip): 64-byte X rows, windows of 2^bw_wlog X rows,
+    // workspace holds two rows the tile needs instead of 1.1 (shares pb.values / pb.c16_ptrs / the row map)
+    struct UnscrambledPlan {
+        bool on = false;
+        int max_rows = 0;
+        int64_t n_phases = 0, n_perm = 0;
+        DeviceBuf<int32_t> ph_ptr, g0, list_ptr, xrows, perm;
+        DeviceBuf<uint8_t> col8;
+    } pu;
+    // block-vector column-window sweep plan (uspmv_build_block_sweep_plan, csrc/spmmv_sweep.hip): 64-byte X rows, windows of 2^wlog X rows,
     // per tile the list of windows its rows touch
-    bool bw = false;
-    int bw_tile_rows = 2048, bw_wlog = 9, bw_b = 0;
-    int64_t bw_n_tiles = 0, bw_all_tiles = 0, bw_x_rows = 0, bw_windows = 0;
-    int32_t *bw_tile_ids = nullptr, *bw_win_ptr = nullptr, *bw_wins = nullptr, *bw_pad = nullptr;
-    uint64_t *bw_cnt_off = nullptr;
-    uint32_t *bw_wave_off = nullptr;
-    uint8_t *bw_cnt = nullptr;
-    void *bw_vals = nullptr;
-    uint16_t *bw_idx = nullptr;
+    struct BlockSweepPlan {
+        bool on = false;
+        int tile_rows = 2048, wlog = 9, b = 0;
+        int64_t n_tiles = 0, all_tiles = 0, x_rows = 0, windows = 0;
+        DeviceBuf<int32_t> tile_ids, win_ptr, wins, pad;
+        DeviceBuf<uint64_t> cnt_off;
+        DeviceBuf<uint32_t> wave_off;
+        DeviceBuf<uint8_t> cnt;
+        DeviceBuf<void> vals;
+        DeviceBuf<uint16_t> idx;
+    } bw;
     // column-window sweep plan (host/sweep_plan.cpp, uspmv_dmat_optimize_sweep[_ap]); the _b arrays are the sp part of
-    // an ap[dp_sp] pair and live on the dp handle, the sp handle only carries the plan id
-    bool sw = false;
-    int sw_tile_rows = 1024, sw_wlog = 13;
-    int64_t sw_n_tiles = 0, sw_all_tiles = 0, sw_x_len = 0, sw_n_rest = 0;
-    int64_t sw_n_vals = 0, sw_n_vals_b = 0, sw_cnt_bytes = 0;   // elements of the compacted streams (without the spare tail), bytes of a count array
-    uint64_t sw_plan_id = 0;
-    int32_t *sw_tile_ids = nullptr, *sw_smin = nullptr, *sw_S = nullptr, *sw_pad = nullptr, *sw_pad_b = nullptr, *sw_rest = nullptr;
-    uint64_t *sw_cnt_off = nullptr;
-    uint32_t *sw_wave_off = nullptr, *sw_wave_off_b = nullptr;
-    uint8_t *sw_cnt = nullptr, *sw_cnt_b = nullptr;
-    void *sw_vals = nullptr;
-    float *sw_vals_b = nullptr;
-    uint16_t *sw_idx = nullptr, *sw_idx_b = nullptr;
+    // an ap[dp_sp] pair and live on the dp handle, the sp handle only carries the plan id and the tile counts
+    struct SweepPlan {
+        bool on = false;
+        int tile_rows = 1024, wlog = 13;
+        int64_t n_tiles = 0, all_tiles = 0, x_len = 0, n_rest = 0;
+        int64_t n_vals = 0, n_vals_b = 0, cnt_bytes = 0;   // elements of the compacted streams (without the spare tail), bytes of a count array
+        uint64_t plan_id = 0;
+        DeviceBuf<int32_t> tile_ids, smin, S, pad, pad_b, rest;
+        DeviceBuf<uint64_t> cnt_off;
+        DeviceBuf<uint32_t> wave_off, wave_off_b;
+        DeviceBuf<uint8_t> cnt, cnt_b;
+        DeviceBuf<void> vals;
+        DeviceBuf<float> vals_b;
+        DeviceBuf<uint16_t> idx, idx_b;
+    } sw;
 };
 
 namespace uspmv_dev {
@@ -272,7 +353,6 @@ bool spmmv_phased(const uspmv_dmat *A, const float *X, float *Y, long ld, bool y
 bool spmmv_stream(const uspmv_dmat *A, const double *X, double *Y, long ld, bool ycol, hipStream_t st);
 bool spmmv_stream(const uspmv_dmat *A, const float *X, float *Y, long ld, bool ycol, hipStream_t st);
 int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu);
-void dmat_stream_release(uspmv_dmat *A);
 int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x, const float *d_x_sp, double *d_y,
                    hipStream_t stream);                                                                           // ap_kernels.hip
 template <typename VT>
@@ -294,9 +374,14 @@ int launch_block_values_gather(const uspmv_dmat *A, const int *d_row_map, const 
 int launch_block_reorder(const uspmv_dmat *A, int *d_row_map, int *d_changed, hipStream_t st);
 int launch_block_tile_class(const uspmv_dmat *A, long n_local, unsigned char *d_flags, hipStream_t st);
 int launch_part_len_fill(const uspmv_dmat *A, int rows_per_flag, const unsigned char *d_flags, int *d_len_int, int *d_len_bnd, hipStream_t st);
+// drops every block plan: the list plan, the phased plan with its stream schedule, the line and unscrambled plans, and the part
+// arrays classified per tile of the phased plan (part_len[1])
+inline void block_plan_reset(uspmv_dmat *A) {
+    A->bt = {}; A->pb = {}; A->ps = {}; A->pl = {}; A->pu = {};
+    A->part_len[1][0].reset(); A->part_len[1][1].reset();
+}
 // two-part SpMMV (uspmv_dmat::part_len): order 0 from per-chunk flags (1 = the chunk touches a halo column), order 1 from the lists of the
 // handle's phased plan (no-op without one); the arrays belong to the handle (order 1 goes with the plan)
-void dmat_block_plan_release(uspmv_dmat *A);
 int dmat_part_set_chunks(uspmv_dmat *A, const unsigned char *h_chunk_flags);
 int dmat_part_set_plan(uspmv_dmat *A, long n_local, int64_t *n_boundary_tiles);
 int launch_block_phase_plan(const uspmv_dmat *A, bool write, int cap, int ngp, const int *d_row_map, const unsigned *d_c16_ptrs, int *d_t_phases,

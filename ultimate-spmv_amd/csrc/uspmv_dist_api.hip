@@ -54,8 +54,8 @@ struct uspmv_dist {
     int64_t n_local = 0, n_halo = 0, n_send = 0, n_int = 0, n_bnd = 0, vec_len = 0, n_rows_padded = 0;
     std::vector<int64_t> send_off, recv_off;
     std::vector<int32_t> recv_counts;
-    int32_t *d_send_idxs = nullptr, *d_perm = nullptr, *d_int = nullptr, *d_bnd = nullptr;
-    int32_t *d_src = nullptr;         // pack: send[i] = x[d_src[i]], d_src = perm[send_idxs] composed once
+    DeviceBuf<int32_t> d_send_idxs, d_perm, d_int, d_bnd;
+    DeviceBuf<int32_t> d_src;         // pack: send[i] = x[d_src[i]], d_src = perm[send_idxs] composed once
     // Padding tiles (tile lists only).  The reference pads chunks with (value +0, column 0); on ranks > 0 column 0 is a halo column
     // (code/mpi_funcs.hpp:279-306), so more than half of a rank's tiles "touch the halo" only through fma(+0, x[pad_col], acc).  Those
     // run with the interior tiles, before the exchange has delivered x[pad_col]: for a finite operand of the same sign the product is
@@ -64,21 +64,21 @@ struct uspmv_dist {
     // signs differ runs the padding tiles AGAIN after the boundary tiles (a conditional tile list: ids or -1).
     // d_early = interior and padding tiles in ascending order (ONE launch before the exchange completes); d_late = the boundary tiles
     // with real halo references followed by n_pad conditional entries (ONE launch after it): the guard writes ids or -1 there
-    int32_t *d_early = nullptr, *d_late = nullptr, *d_pad = nullptr;
+    DeviceBuf<int32_t> d_early, d_late, d_pad;
     // ONE-launch step ("fused_step" 1, the default with tile lists): d_step = [early | real boundary | padding again (conditional)] in one
     // launch on the side stream; late entries that find the exchange unfinished defer themselves to a second, small launch behind it
     // (uspmv_dev::StepSync -- nothing spins).  Saves the second launch's ramp-up and the join in the common case.
-    int32_t *d_step = nullptr, *d_defer = nullptr;
-    uspmv_dev::StepSync *d_ss = nullptr;
+    DeviceBuf<int32_t> d_step, d_defer;
+    DeviceBuf<uspmv_dev::StepSync> d_ss;
     uspmv_dev::StepArgs sa;
     bool fused = false, sync_dirty = false, capturing = false;   // (off by default: 0.222 against 0.209 ms, same file)
     int64_t n_bnd_real = 0, n_pad = 0;
     int32_t pad_col = -1;
     bool pad_split = false;           // (off by default: on one GPU it measures 0.221 against 0.209 ms per step, profiles/r03/dist_step_ab.txt)
-    void *d_stale = nullptr;
-    void *d_send = nullptr;
+    DeviceBuf<void> d_stale;
+    DeviceBuf<void> d_send;
     void *h_send = nullptr, *h_recv = nullptr;   // pinned staging of USPMV_EXCHANGE_HOST
-    int *d_scratch = nullptr;
+    DeviceBuf<int> d_scratch;
     // captured step
     hipGraphExec_t gexec = nullptr;
     void *g_x = nullptr, *g_y = nullptr;
@@ -88,9 +88,9 @@ struct uspmv_dist {
     // block-vector exchange plans, one per (b, layout, mode) used so far
     struct BlockPlan {
         int b = 0, layout = 0, mode = 0;
-        int32_t *d_src = nullptr;                    // wire order of the send buffer: send[i] = X[d_src[i]]
-        std::vector<int32_t *> d_unpack;             // staged receive (bulk, column-wise): per vector, halo slot -> position in d_recv
-        void *d_send = nullptr, *d_recv = nullptr;
+        DeviceBuf<int32_t> d_src;                    // wire order of the send buffer: send[i] = X[d_src[i]]
+        std::vector<DeviceBuf<int32_t>> d_unpack;    // staged receive (bulk, column-wise): per vector, halo slot -> position in d_recv
+        DeviceBuf<void> d_send, d_recv;
         void *h_send = nullptr, *h_recv = nullptr;   // pinned staging of USPMV_EXCHANGE_HOST
     };
     std::vector<BlockPlan> block_plans;
@@ -114,42 +114,36 @@ inline ncclDataType_t nccl_vt(const uspmv_dist *D) { return D->dtype == USPMV_F6
 inline size_t vsize(const uspmv_dist *D) { return D->dtype == USPMV_F64 ? 8 : 4; }
 
 // ---- set-up transports that live in this file: RCCL with device staging, identity for loopback
-struct DevBuf {   // scoped device allocation: freed on every return path
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-};
-
 int rccl_alltoallv(void *ctx, const void *send, const int64_t *so, void *recv, const int64_t *ro) {
     auto *D = (uspmv_dist *)ctx;
     const int P = D->comm_size;
     const int64_t sb = so[P] - so[0], rb = ro[P] - ro[0];
-    DevBuf ds, dr;
+    DeviceBuf<char> ds, dr;
     HIP_TRY(ds.alloc((size_t)sb));
     HIP_TRY(dr.alloc((size_t)rb));
-    if (sb) HIP_TRY(hipMemcpy(ds.p, (const char *)send + so[0], (size_t)sb, hipMemcpyHostToDevice));
+    if (sb) HIP_TRY(hipMemcpy(ds, (const char *)send + so[0], (size_t)sb, hipMemcpyHostToDevice));
     hipStream_t st = D->side_stream;
     NCCL_TRY(ncclGroupStart());
     for (int q = 0; q < P; ++q) {
         const int64_t ns = so[q + 1] - so[q], nr = ro[q + 1] - ro[q];
-        if (nr) NCCL_TRY(ncclRecv((char *)dr.p + (ro[q] - ro[0]), (size_t)nr, ncclInt8, q, D->comm, st));
-        if (ns) NCCL_TRY(ncclSend((const char *)ds.p + (so[q] - so[0]), (size_t)ns, ncclInt8, q, D->comm, st));
+        if (nr) NCCL_TRY(ncclRecv((char *)dr + (ro[q] - ro[0]), (size_t)nr, ncclInt8, q, D->comm, st));
+        if (ns) NCCL_TRY(ncclSend((const char *)ds + (so[q] - so[0]), (size_t)ns, ncclInt8, q, D->comm, st));
     }
     NCCL_TRY(ncclGroupEnd());
     HIP_TRY(hipStreamSynchronize(st));
-    if (rb) HIP_TRY(hipMemcpy((char *)recv + ro[0], dr.p, (size_t)rb, hipMemcpyDeviceToHost));
+    if (rb) HIP_TRY(hipMemcpy((char *)recv + ro[0], dr, (size_t)rb, hipMemcpyDeviceToHost));
     return USPMV_OK;
 }
 int rccl_allgather(void *ctx, const void *send, void *recv, int64_t bytes) {
     auto *D = (uspmv_dist *)ctx;
     if (bytes == 0) return USPMV_OK;
-    DevBuf ds, dr;
+    DeviceBuf<char> ds, dr;
     HIP_TRY(ds.alloc((size_t)bytes));
     HIP_TRY(dr.alloc((size_t)bytes * (size_t)D->comm_size));
-    HIP_TRY(hipMemcpy(ds.p, send, (size_t)bytes, hipMemcpyHostToDevice));
-    NCCL_TRY(ncclAllGather(ds.p, dr.p, (size_t)bytes, ncclInt8, D->comm, D->side_stream));
+    HIP_TRY(hipMemcpy(ds, send, (size_t)bytes, hipMemcpyHostToDevice));
+    NCCL_TRY(ncclAllGather(ds, dr, (size_t)bytes, ncclInt8, D->comm, D->side_stream));
     HIP_TRY(hipStreamSynchronize(D->side_stream));
-    HIP_TRY(hipMemcpy(recv, dr.p, (size_t)bytes * (size_t)D->comm_size, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(recv, dr, (size_t)bytes * (size_t)D->comm_size, hipMemcpyDeviceToHost));
     return USPMV_OK;
 }
 int rccl_barrier(void *ctx) {
@@ -391,14 +385,9 @@ void uspmv_dist_free(uspmv_dist_t *D) {
     if (!D) return;
     drop_graph(D);
     for (auto &bp : D->block_plans) {
-        (void)hipFree(bp.d_src); (void)hipFree(bp.d_send); (void)hipFree(bp.d_recv);
         if (bp.h_send) (void)hipHostFree(bp.h_send);
         if (bp.h_recv) (void)hipHostFree(bp.h_recv);
-        for (int32_t *u : bp.d_unpack) (void)hipFree(u);
     }
-    (void)hipFree(D->d_send_idxs); (void)hipFree(D->d_perm); (void)hipFree(D->d_int); (void)hipFree(D->d_bnd); (void)hipFree(D->d_send); (void)hipFree(D->d_scratch);
-    (void)hipFree(D->d_src); (void)hipFree(D->d_early); (void)hipFree(D->d_late); (void)hipFree(D->d_pad); (void)hipFree(D->d_stale);
-    (void)hipFree(D->d_step); (void)hipFree(D->d_defer); (void)hipFree(D->d_ss);
     if (D->h_send) (void)hipHostFree(D->h_send);
     if (D->h_recv) (void)hipHostFree(D->h_recv);
     if (D->ev_main) (void)hipEventDestroy(D->ev_main);
@@ -450,8 +439,7 @@ int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int 
     D_HIP(hipStreamCreateWithFlags(&D->side_stream, hipStreamNonBlocking));
     D_HIP(hipEventCreateWithFlags(&D->ev_main, hipEventDisableTiming));
     D_HIP(hipEventCreateWithFlags(&D->ev_comm, hipEventDisableTiming));
-    D_HIP(hipMalloc((void **)&D->d_scratch, 256));
-    D_HIP(hipMemset(D->d_scratch, 0, 256));
+    D_HIP(D->d_scratch.zeros(256));
     // ---- who sends what to whom (collect_comm_info, code/mpi_funcs.hpp:1061-1124) over the set-up transport
     if (opt && opt->transport) D->tr = *opt->transport;
     else if (D->loopback) { D->tr.ctx = D; D->tr.rank = rank; D->tr.size = P; D->tr.alltoallv = self_alltoallv; D->tr.allgather = self_allgather; D->tr.barrier = self_barrier; }
@@ -469,23 +457,17 @@ int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int 
     D->h_perm.assign(old_to_new_idx, old_to_new_idx + D->n_local);
     // ---- device state of the step
     const size_t vsz = vsize(D);
-    D_HIP(hipMalloc((void **)&D->d_send_idxs, 4 * (size_t)std::max<int64_t>(D->n_send, 1)));
-    if (D->n_send) D_HIP(hipMemcpy(D->d_send_idxs, D->h_send_idxs.data(), 4 * (size_t)D->n_send, hipMemcpyHostToDevice));
-    D_HIP(hipMalloc((void **)&D->d_perm, 4 * (size_t)std::max<int64_t>(D->n_local, 1)));
-    if (D->n_local) D_HIP(hipMemcpy(D->d_perm, old_to_new_idx, 4 * (size_t)D->n_local, hipMemcpyHostToDevice));
+    D_HIP(D->d_send_idxs.upload(D->h_send_idxs.data(), 4 * (size_t)D->n_send));
+    D_HIP(D->d_perm.upload(old_to_new_idx, 4 * (size_t)D->n_local));
     {
         std::vector<int32_t> src((size_t)D->n_send);
         for (int64_t i = 0; i < D->n_send; ++i) src[(size_t)i] = old_to_new_idx[D->h_send_idxs[(size_t)i]];     // (ids validated in [0, n_local) by the plan)
-        D_HIP(hipMalloc((void **)&D->d_src, 4 * (size_t)std::max<int64_t>(D->n_send, 1)));
-        if (D->n_send) D_HIP(hipMemcpy(D->d_src, src.data(), 4 * (size_t)D->n_send, hipMemcpyHostToDevice));
-        D_HIP(hipMalloc(&D->d_stale, 16));
-        D_HIP(hipMemset(D->d_stale, 0, 16));
+        D_HIP(D->d_src.upload(src.data(), 4 * (size_t)D->n_send));
+        D_HIP(D->d_stale.zeros(16));
     }
-    D_HIP(hipMalloc((void **)&D->d_int, 4 * (size_t)std::max<int64_t>(n_interior, 1)));
-    D_HIP(hipMalloc((void **)&D->d_bnd, 4 * (size_t)std::max<int64_t>(n_boundary, 1)));
-    if (n_interior) D_HIP(hipMemcpy(D->d_int, interior_ids, 4 * (size_t)n_interior, hipMemcpyHostToDevice));
-    if (n_boundary) D_HIP(hipMemcpy(D->d_bnd, boundary_ids, 4 * (size_t)n_boundary, hipMemcpyHostToDevice));
-    D_HIP(hipMalloc(&D->d_send, vsz * (size_t)std::max<int64_t>(D->n_send, 1)));
+    D_HIP(D->d_int.upload(interior_ids, 4 * (size_t)n_interior));
+    D_HIP(D->d_bnd.upload(boundary_ids, 4 * (size_t)n_boundary));
+    D_HIP(D->d_send.alloc(vsz * (size_t)std::max<int64_t>(D->n_send, 1)));
     if (host_ex) {
         D_HIP(hipHostMalloc(&D->h_send, vsz * (size_t)std::max<int64_t>(D->n_send, 1), hipHostMallocDefault));
         D_HIP(hipHostMalloc(&D->h_recv, vsz * (size_t)std::max<int64_t>(D->n_halo, 1), hipHostMallocDefault));
@@ -495,7 +477,7 @@ int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int 
     if (P > 1 && !A->alt && A->n_chunks > 0) {
         // the same split for block vectors: per chunk, does it (or its tile) touch a halo column
         std::vector<unsigned char> flag((size_t)A->n_chunks, 0);
-        const int64_t cpt = ids_are_tiles ? std::max<int64_t>(A->tlc_tile_rows / A->C, 1) : 1;
+        const int64_t cpt = ids_are_tiles ? std::max<int64_t>(A->tlc.tile_rows / A->C, 1) : 1;
         bool ok = true;
         for (int64_t k = 0; k < n_boundary && ok; ++k) {
             const int64_t c0 = (int64_t)boundary_ids[k] * cpt;
@@ -594,17 +576,12 @@ int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_s
         stepl.insert(stepl.end(), ids_pad.begin(), ids_pad.end());
         stepl.insert(stepl.end(), early.begin() + (long)late0, early.end());
         const size_t n_late = late.size();
-        auto up = [](int32_t **d, const std::vector<int32_t> &h) -> hipError_t {
-            hipError_t e = hipMalloc((void **)d, 4 * std::max<size_t>(h.size(), 1));
-            if (e == hipSuccess && !h.empty()) e = hipMemcpy(*d, h.data(), 4 * h.size(), hipMemcpyHostToDevice);
-            return e;
-        };
-        hipError_t e = up(&D->d_step, stepl);
-        if (e == hipSuccess && pads) e = up(&D->d_pad, ids_pad);
-        if (e == hipSuccess && pads) e = up(&D->d_early, early);
-        if (e == hipSuccess && pads) e = up(&D->d_late, late);
-        if (e == hipSuccess) e = hipMalloc((void **)&D->d_defer, 4 * 2 * std::max<size_t>(n_late, 1));
-        if (e == hipSuccess) e = hipMalloc((void **)&D->d_ss, sizeof(uspmv_dev::StepSync));
+        hipError_t e = D->d_step.upload(stepl.data(), 4 * stepl.size());
+        if (e == hipSuccess && pads) e = D->d_pad.upload(ids_pad.data(), 4 * ids_pad.size());
+        if (e == hipSuccess && pads) e = D->d_early.upload(early.data(), 4 * early.size());
+        if (e == hipSuccess && pads) e = D->d_late.upload(late.data(), 4 * late.size());
+        if (e == hipSuccess) e = D->d_defer.alloc(4 * 2 * std::max<size_t>(n_late, 1));
+        if (e == hipSuccess) e = D->d_ss.alloc(sizeof(uspmv_dev::StepSync));
         if (e != hipSuccess) {
             uspmv_dist_free(D); cleanup();
             return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dist_create_from_coo: %s", hipGetErrorString(e));
@@ -649,10 +626,10 @@ int uspmv_dist_set_option(uspmv_dist_t *D, const char *key, int value) {
         if (value < 0) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_set_option: block_plan takes a block width >= 0");
         D->plan_b = 0; D->plan_bnd_tiles = 0;
         int64_t nt = 0, ns = 0;
-        if (value == 0) { uspmv_dev::dmat_block_plan_release(D->A); return USPMV_OK; }
+        if (value == 0) { uspmv_dev::block_plan_reset(D->A); return USPMV_OK; }
         int rc = D->scs ? uspmv_dmat_optimize_block(D->A, D->scs, value, &nt, &ns) : uspmv_dmat_optimize_block_device(D->A, value, &nt, &ns);
         if (rc) return rc;
-        if (D->A->pb) {
+        if (D->A->pb.on) {
             D->plan_b = value;
             if (D->parts) rc = uspmv_dev::dmat_part_set_plan(D->A, (long)D->n_local, &D->plan_bnd_tiles);
         }
@@ -679,15 +656,15 @@ int uspmv_dist_pad_info(const uspmv_dist_t *D, int64_t meta[4]) {
     if (!D || !meta) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_pad_info: NULL argument");
     int reruns = 0, r2 = 0;
     if (D->d_scratch) HIP_TRY(hipMemcpy(&reruns, D->d_scratch + 2, 4, hipMemcpyDeviceToHost));
-    if (D->d_ss) { HIP_TRY(hipMemcpy(&r2, &D->d_ss->reruns, 4, hipMemcpyDeviceToHost)); reruns += r2; }
+    if (D->d_ss) { HIP_TRY(hipMemcpy(&r2, &D->d_ss.get()->reruns, 4, hipMemcpyDeviceToHost)); reruns += r2; }
     meta[0] = D->n_pad; meta[1] = D->n_pad ? D->n_bnd_real : D->n_bnd; meta[2] = D->pad_col; meta[3] = reruns;
     return USPMV_OK;
 }
 
 int uspmv_dist_spmmv_info(const uspmv_dist_t *D, int64_t meta[6]) {
     if (!D || !meta) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv_info: NULL argument");
-    meta[0] = D->spmmv_two_part; meta[1] = D->spmmv_one_part; meta[2] = D->A->pb ? D->plan_b : 0; meta[3] = D->A->pb ? D->A->pb_n_tiles : 0;
-    meta[4] = D->A->pb ? D->plan_bnd_tiles : 0; meta[5] = D->parts && !D->A->alt;
+    meta[0] = D->spmmv_two_part; meta[1] = D->spmmv_one_part; meta[2] = D->A->pb.on ? D->plan_b : 0; meta[3] = D->A->pb.on ? D->A->pb.n_tiles : 0;
+    meta[4] = D->A->pb.on ? D->plan_bnd_tiles : 0; meta[5] = D->parts && !D->A->alt;
     return USPMV_OK;
 }
 
@@ -802,12 +779,12 @@ int uspmv_dist_autotune(uspmv_dist_t *D, void *d_x, void *d_y, int use_graph, co
     // ranks reach the same verdict); otherwise the faster of overlap / plain takes over and ms[] of the rejected form is negated
     if ((best == USPMV_STEP_PAD || best == USPMV_STEP_FUSED) && local && wsa) {
         int64_t mm = 0;
-        DevBuf keep;                                            // (the check runs on its own x: put the caller's local part back afterwards)
+        DeviceBuf<void> keep;                                           // (the check runs on its own x: put the caller's local part back afterwards)
         const size_t xb = vsize(D) * (size_t)std::max<int64_t>(D->n_local, 1);
         HIP_TRY(keep.alloc(xb));
-        HIP_TRY(hipMemcpyAsync(keep.p, d_x, xb, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(keep, d_x, xb, hipMemcpyDeviceToDevice, st));
         const int rc_check = uspmv_dist_check(D, local, wsa, d_x, d_y, use_graph, stream, &mm, nullptr);
-        HIP_TRY(hipMemcpyAsync(d_x, keep.p, xb, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_x, keep, xb, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (rc_check) return rc_check;
         std::vector<int64_t> all((size_t)std::max(D->P, D->comm_size), 0);
@@ -859,13 +836,13 @@ int uspmv_dist_allgather_i64(uspmv_dist_t *D, int64_t value, int64_t *all, void 
         if (!D->tr.allgather) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_allgather_i64: the transport has no all-gather");
         return D->tr.allgather(D->tr.ctx, &value, all, 8);
     }
-    DevBuf d_v, d_all;
+    DeviceBuf<int64_t> d_v, d_all;
     HIP_TRY(d_v.alloc(8));
     HIP_TRY(d_all.alloc(8 * (size_t)D->comm_size));
-    HIP_TRY(hipMemcpy(d_v.p, &value, 8, hipMemcpyHostToDevice));
-    NCCL_TRY(ncclAllGather(d_v.p, d_all.p, 1, ncclInt64, D->comm, (hipStream_t)stream));
+    HIP_TRY(hipMemcpy(d_v, &value, 8, hipMemcpyHostToDevice));
+    NCCL_TRY(ncclAllGather(d_v, d_all, 1, ncclInt64, D->comm, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipMemcpy(all, d_all.p, 8 * (size_t)D->comm_size, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(all, d_all, 8 * (size_t)D->comm_size, hipMemcpyDeviceToHost));
     return USPMV_OK;
 }
 
@@ -940,31 +917,26 @@ uspmv_dist::BlockPlan *block_plan(uspmv_dist *D, int b, int layout, int mode) {
         for (int v = 0; v < b; ++v)
             for (int64_t i = 0; i < ns; ++i) src[(size_t)(v * ns + i)] = (int32_t)(D->h_perm[(size_t)D->h_send_idxs[(size_t)i]] + (int64_t)v * ld);
     }
-    hipError_t e = hipMalloc((void **)&bp.d_src, 4 * std::max<size_t>(src.size(), 1));
-    if (e == hipSuccess && !src.empty()) e = hipMemcpy(bp.d_src, src.data(), 4 * src.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&bp.d_send, vsz * std::max<size_t>((size_t)(ns * b), 1));
+    hipError_t e = bp.d_src.upload(src.data(), 4 * src.size());
+    if (e == hipSuccess) e = bp.d_send.alloc(vsz * std::max<size_t>((size_t)(ns * b), 1));
     if (e == hipSuccess && layout == USPMV_COLWISE && mode == USPMV_BULKVEC) {
-        e = hipMalloc(&bp.d_recv, vsz * std::max<size_t>((size_t)(nh * b), 1));
+        e = bp.d_recv.alloc(vsz * std::max<size_t>((size_t)(nh * b), 1));
         std::vector<int32_t> un((size_t)nh);
         for (int v = 0; v < b && e == hipSuccess; ++v) {
             for (int p = 0; p < D->P; ++p) {
                 const int64_t nr = D->recv_counts[(size_t)p], ro = D->recv_off[(size_t)p];
                 for (int64_t k = 0; k < nr; ++k) un[(size_t)(ro + k)] = (int32_t)((int64_t)b * ro + (int64_t)v * nr + k);
             }
-            int32_t *d_u = nullptr;
-            e = hipMalloc((void **)&d_u, 4 * std::max<size_t>(un.size(), 1));
-            if (e == hipSuccess && nh) e = hipMemcpy(d_u, un.data(), 4 * un.size(), hipMemcpyHostToDevice);
-            bp.d_unpack.push_back(d_u);
+            bp.d_unpack.emplace_back();
+            e = bp.d_unpack.back().upload(un.data(), 4 * un.size());
         }
     }
     if (e != hipSuccess) {   // nothing of a half-built plan stays behind (every failed call would leak it again)
-        (void)hipFree(bp.d_src); (void)hipFree(bp.d_send); (void)hipFree(bp.d_recv);
-        for (int32_t *u : bp.d_unpack) (void)hipFree(u);
         (void)hipGetLastError();
         uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dist_spmmv: %s", hipGetErrorString(e));
         return nullptr;
     }
-    D->block_plans.push_back(bp);
+    D->block_plans.push_back(std::move(bp));
     return &D->block_plans.back();
 }
 
@@ -1048,7 +1020,7 @@ extern "C" int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, in
     if (!(D->P > 1 && comm_halos)) return uspmv_spmmv(D->A, d_X, d_Y, b, D->vec_len, layout, stream);
     // (a handle whose only block plan is the one-list-per-tile one runs that plan's kernels on the whole matrix: they are ahead of the
     //  gather kernels by more than the exchange costs)
-    if (!(D->overlap && D->parts && !D->A->alt) || (D->A->bt && !(D->A->pb && D->A->part_len[1][0]))) {
+    if (!(D->overlap && D->parts && !D->A->alt) || (D->A->bt.on && !(D->A->pb.on && D->A->part_len[1][0]))) {
         // exchange first, then the whole matrix (the reference's order, code/mpi_funcs.hpp:25-60)
         if (int rc = exchange_block(D, d_X, b, layout, mode, main)) return rc;
         if (int rc = uspmv_spmmv(D->A, d_X, d_Y, b, D->vec_len, layout, stream)) return rc;

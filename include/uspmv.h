@@ -483,8 +483,20 @@ int uspmv_dist_create_from_coo(const void *comm_id, int comm_rank, int comm_size
  * staged through host memory over `transport` (pack kernel -> D2H -> all-to-all-v -> H2D into the tail of x), which lets P real
  * processes share ONE GPU: it is how a single-GPU box runs the C++ step with unequal seg-nnz blocks and asymmetric send / recv
  * lists (tests/test_dist_native_gpu.py).  With USPMV_EXCHANGE_HOST no RCCL communicator is created (comm_id may be NULL);
- * transport->size must equal P and transport->rank the block.  The transport must outlive the object. */
-typedef enum { USPMV_EXCHANGE_RCCL = 0, USPMV_EXCHANGE_HOST = 1 } uspmv_exchange;
+ * transport->size must equal P and transport->rank the block.  The transport must outlive the object.
+ * USPMV_EXCHANGE_PEER: peer stores.  Every rank owns a receive window (hipMalloc, double-buffered by step parity, exported through
+ * hipIpcGetMemHandle); one push kernel per step stores the rank's halo contributions straight into its neighbours' windows (opened
+ * through hipIpcOpenMemHandle: across xGMI on a node, device to device when ranks share one GPU), the host waits for it, the ranks
+ * meet in the transport's barrier, and an unpack kernel copies the window into the tail of x.  No communication kernel, no host copy
+ * of the data, no RCCL communicator (comm_id may be NULL; uspmv_dist_comm_count gives 0).  Real ranks (comm_size == P > 1) need a
+ * transport (all-gather and barrier: set-up, per-step barrier, uspmv_dist_barrier / _allreduce_max / _allgather_i64); loopback
+ * (comm_size == 1, P > 1) takes none and pushes into its own window.  Set-up is collective and fails on every rank alike (export /
+ * open failures, inconsistent send / receive counts); a failed set-up (also the window growth of uspmv_dist_spmmv) leaves the object
+ * without windows: its steps then fail with USPMV_ERR_INVALID until uspmv_dist_spmmv on every rank sets them up again.
+ * uspmv_dist_free is collective too (close, barrier, free).  Steps run eagerly:
+ * uspmv_dist_run(use_graph = 1) falls back to eager steps.  Every option and step form applies, with the same bits as the other
+ * exchanges.  On ROCm, IPC between processes needs HSA_ENABLE_IPC_MODE_LEGACY=0 in every rank's environment. */
+typedef enum { USPMV_EXCHANGE_RCCL = 0, USPMV_EXCHANGE_HOST = 1, USPMV_EXCHANGE_PEER = 2 } uspmv_exchange;
 typedef struct uspmv_dist_options {
     const uspmv_transport_t *transport;
     int exchange;
@@ -502,6 +514,8 @@ int uspmv_dist_comm_plan(const uspmv_dist_t *d, int64_t *n_send, const int64_t *
  * MPI_Barrier the reference issues per iteration by default, code/main.cpp:467, :417; part of the captured graph),
  * "capture_mode" 0 global | 1 thread-local | 2 relaxed (hipStreamCaptureMode of uspmv_dist_run's capture),
  * "diag_skip_exchange" 0|1 (diagnosis only: the step skips the RCCL group, results are wrong),
+ * "diag_peer_skew" 0|1 (test only, USPMV_EXCHANGE_PEER: this rank announces one halo element too many from its first neighbour at the
+ *   next window set-up -- the growth in uspmv_dist_spmmv -- which every rank must then refuse alike),
  * "fused_step" 0|1 (default 0; tile lists: the step's tiles in ONE launch -- interior and padding tiles first, the boundary tiles at the end of
  *   the grid, each of which looks once whether the exchange has completed and otherwise defers itself to a small second launch behind
  *   the exchange; nothing spins.  0: interior launch, exchange, boundary launch),
@@ -535,8 +549,10 @@ int uspmv_dist_check_reference(const uspmv_coo_t *local, const int32_t *wsa, int
  * v[0] HIP_VERSION (build), v[1] hipRuntimeGetVersion, v[2] NCCL_VERSION_CODE (build), v[3] ncclGetVersion. */
 int uspmv_runtime_versions(int v[4]);
 /* Ranks of the RCCL communicator the step's exchange runs on (ncclCommCount; the reference prints MPI_Comm_size, code/main.cpp:1838);
- * 0 when the exchange is staged through the host (no communicator exists). */
+ * 0 when the exchange is staged through the host or stored by peers (no communicator exists). */
 int uspmv_dist_comm_count(const uspmv_dist_t *d, int *n_ranks);
+/* the object's exchange (uspmv_exchange) */
+int uspmv_dist_exchange(const uspmv_dist_t *d, int *exchange);
 /* meta[12] = n_local, n_halo, padded_vec_size, n_send, n_interior, n_boundary, ids_are_tiles, n_rows_padded, loopback,
  *            graph captured, graph launches so far, eager steps so far */
 int uspmv_dist_info(const uspmv_dist_t *d, int64_t meta[12]);
@@ -562,7 +578,8 @@ int uspmv_dist_run(uspmv_dist_t *d, void *d_x, void *d_y, int n_steps, int use_g
  * builds the phased block plan of uspmv_dmat_optimize_block on the rank's matrix (64-byte X rows) together with the
  * interior / boundary classes of its tiles; uspmv_dist_set_option(d, "overlap", 0) restores exchange-then-compute.
  * With USPMV_EXCHANGE_HOST the same wire formats travel through pinned host memory and the transport's all-to-all-v (tests: real ranks
- * sharing one GPU on unequal blocks). */
+ * sharing one GPU on unequal blocks).  With USPMV_EXCHANGE_PEER one push stores all b columns into windows sized for n_halo x b, grown
+ * collectively when a wider block first appears; the three patterns share that one wire format. */
 typedef enum { USPMV_BULKVEC = 0, USPMV_MULTIVEC = 1, USPMV_SINGLEVEC = 2 } uspmv_vecmode;
 int uspmv_dist_spmmv(uspmv_dist_t *d, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream);
 /* Padding tiles of the single-vector step (tile lists, "pad_split" 1; an option, off by default -- see DESIGN 6.4 for the A/B).  The reference pads chunks with (value +0, column 0);

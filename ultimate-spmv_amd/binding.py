@@ -145,6 +145,7 @@ _SIGS = {
     "uspmv_spmmv_x_release": (C.c_int, [_vp]),
     "uspmv_dmat_meta": (C.c_int, [_vp, C.POINTER(_i64)]),
     "uspmv_dist_comm_count": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "uspmv_dist_exchange": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "uspmv_dist_autotune": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _i32p, _vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "uspmv_dist_check_reference": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_int, _vp]),
     "uspmv_dist_parts": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
@@ -482,7 +483,8 @@ class DistOptions(C.Structure):
     _fields_ = [("transport", C.POINTER(Transport)), ("exchange", C.c_int)]
 
 
-EXCHANGE_RCCL, EXCHANGE_HOST = 0, 1
+EXCHANGE_RCCL, EXCHANGE_HOST, EXCHANGE_PEER = 0, 1, 2
+EXCHANGES = ("rccl", "host", "peer")
 
 
 class HostComm:
@@ -593,10 +595,13 @@ class DistNative:
     the capture of an RCCL group crashes in hipStreamEndCapture, so it is off by default here."""
 
     def __init__(self, local_coo, wsa, C_, sigma, rank, P, comm_id=None, comm_rank=None, comm_size=None, dtype=F64, tlc=True,
-                 hostcomm=None, host_exchange=False):
+                 hostcomm=None, host_exchange=False, exchange=None):
         """hostcomm: a HostComm that carries the set-up exchanges (default: the RCCL communicator made from comm_id);
         host_exchange=True additionally stages the per-step halo exchange through it (USPMV_EXCHANGE_HOST: no RCCL communicator,
-        P processes may share one GPU)."""
+        P processes may share one GPU).  exchange="rccl" | "host" | "peer" names the per-step exchange instead (host_exchange=True is
+        exchange="host"); "peer" (USPMV_EXCHANGE_PEER) stores the halos into the neighbours' IPC windows, over the HostComm between real
+        ranks, with no transport at all in loopback (comm_size=1).  Peer ranks in separate processes need HSA_ENABLE_IPC_MODE_LEGACY=0
+        in their environment before the HIP runtime starts."""
         import torch
         self.rank, self.P = rank, P
         wsa = np.ascontiguousarray(wsa, np.int32)
@@ -604,15 +609,26 @@ class DistNative:
         h = _vp()
         idbuf = (C.c_ubyte * 128).from_buffer_copy(comm_id) if comm_id is not None else None
         self._hostcomm = hostcomm
+        if exchange is None:
+            exchange = "host" if host_exchange else "rccl"
+        elif exchange not in EXCHANGES or (host_exchange and exchange != "host"):
+            raise ValueError(f"exchange={exchange!r} (host_exchange={host_exchange}): one of {EXCHANGES}")
+        ex = EXCHANGES.index(exchange)
         opt = None
         if hostcomm is not None:
-            self._opt = DistOptions(C.pointer(hostcomm.transport), EXCHANGE_HOST if host_exchange else EXCHANGE_RCCL)
+            self._opt = DistOptions(C.pointer(hostcomm.transport), ex)
             opt = C.byref(self._opt)
-        elif host_exchange:
+        elif ex == EXCHANGE_HOST:
             raise ValueError("host_exchange needs a HostComm")
+        elif ex == EXCHANGE_PEER:
+            self._opt = DistOptions(None, ex)      # no transport: loopback (the library refuses real ranks without one)
+            opt = C.byref(self._opt)
         _ck(lib().uspmv_dist_create_from_coo_ex(idbuf, rank if comm_rank is None else comm_rank, P if comm_size is None else comm_size,
                                                 rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, dtype, int(bool(tlc)), opt, C.byref(h)))
         self.h = h
+        e = C.c_int(0)
+        _ck(lib().uspmv_dist_exchange(h, C.byref(e)))
+        self.exchange = EXCHANGES[e.value]
         s, a, hl = _vp(), _vp(), _vp()
         _ck(lib().uspmv_dist_parts(h, C.byref(s), C.byref(a), C.byref(hl)))
         self.scs = _BorrowedScs(s, self)
@@ -692,7 +708,7 @@ class DistNative:
     STEP_FORMS = ("overlap", "plain", "pad", "fused")
 
     def comm_count(self):
-        """ranks of the RCCL communicator the exchange runs on (ncclCommCount); 0 with the host-staged exchange"""
+        """ranks of the RCCL communicator the exchange runs on (ncclCommCount); 0 with the host-staged or peer-store exchange"""
         n = C.c_int(0)
         _ck(lib().uspmv_dist_comm_count(self.h, C.byref(n)))
         return n.value

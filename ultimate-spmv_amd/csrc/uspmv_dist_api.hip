@@ -22,6 +22,9 @@
 // ids a rank asks block p for index p's rows, and the set-up refuses ids outside this block.
 // USPMV_EXCHANGE_HOST: the per-step exchange staged through host memory over the transport -- P real processes may then share
 // ONE GPU, which is how the step runs with unequal seg-nnz blocks and asymmetric lists on a single-GPU box.
+// USPMV_EXCHANGE_PEER: every rank owns a receive window (hipMalloc, exported by hipIpcGetMemHandle) and one push kernel stores its
+// halo contributions straight into the neighbours' windows; completion is host-ordered (event, transport barrier), then an unpack
+// kernel copies the window into the tail of x.  No communication kernel, no host copy of the data (see exchange_peer).
 //
 // Round 3 additions in this file: optional arrangements of the step around the exchange ("pad_split": tiles that touch the halo only
 // through the reference's padding run before the exchange under a sign / finiteness guard; "fused_step": one launch whose boundary
@@ -38,6 +41,7 @@
 struct uspmv_dist {
     int rank = 0, P = 1, comm_rank = 0, comm_size = 1;
     bool loopback = false, overlap = true, tiles = false, owns_setup = false, no_pack = false, ba_synch = false, host_exchange = false;
+    bool peer_exchange = false;       // USPMV_EXCHANGE_PEER (see "peer-store exchange" below)
     bool diag_skip_exchange = false;
     bool autotune_all = false;        // uspmv_dist_autotune also times the speculative arrangements (pad, fused); off: overlap | plain only
     int diag_spmmv_part = 0;          // diagnosis: the two-part block-vector step runs only its interior (1) or boundary (2) part
@@ -78,6 +82,18 @@ struct uspmv_dist {
     DeviceBuf<void> d_stale;
     DeviceBuf<void> d_send;
     void *h_send = nullptr, *h_recv = nullptr;   // pinned staging of USPMV_EXCHANGE_HOST
+    // peer-store exchange: this rank's receive window = two halves (step parity) of win_half elements, sized for block vectors of up to
+    // win_b columns; the windows of the ranks it sends to, opened through IPC (nullptr: not opened; loopback opens nothing); the push
+    // table (per neighbour q: q's window, its half size, where this rank's block starts in it) and the send offsets it is indexed by
+    DeviceBuf<void> d_win;
+    int64_t win_half = 0;
+    int win_b = 0, parity = 0;
+    std::vector<void *> peer_win;
+    DeviceBuf<void> d_push;
+    DeviceBuf<int64_t> d_seg;
+    hipEvent_t ev_push = nullptr, ev_unpack = nullptr;
+    bool unpack_queued = false;       // ev_unpack marks the last unpack (see peer_complete)
+    bool diag_peer_skew = false;      // test only: the next window set-up announces one element too many (see peer_setup)
     DeviceBuf<int> d_scratch;
     // captured step
     hipGraphExec_t gexec = nullptr;
@@ -259,7 +275,245 @@ int exchange_host(uspmv_dist *D, void *d_x, hipStream_t st) {
     return USPMV_OK;
 }
 
-inline int exchange(uspmv_dist *D, void *d_x, hipStream_t st) { return D->host_exchange ? exchange_host(D, d_x, st) : exchange_rccl(D, d_x, st); }
+// ---- USPMV_EXCHANGE_PEER: peer-store exchange
+// Set-up (peer_setup, collective): every rank hipMallocs a window of 2 x win_half elements (win_half = n_halo x widest block seen so far)
+// and exports it; one all-gather carries every rank's export status, handle, half size, send and receive offsets, so every rank
+// validates EVERY pair (r's send count to q == q's receive count from r, the destination range inside q's window) on the same data and
+// reaches the same verdict before any kernel runs; then each rank opens the windows of the ranks it sends to and a second all-gather
+// agrees on the open status.  Sender r writes its send_off[q] .. send_off[q+1] elements to q's window at recv_off_q[r] + j.
+// Loopback: the destination of every neighbour is this process's own window at its own recv_off[q] (what it asked q for), no IPC.
+struct PeerDst {
+    void *base;      // q's window (opened through IPC; this rank's own in loopback)
+    int64_t half;    // elements per parity half of q's window
+    int64_t off;     // first halo slot of this rank's block in q's numbering
+};
+
+// Stores another process reads once this kernel has completed: system scope (global_store ... sc0 sc1 on gfx950).  They are written
+// through to memory and the line is dropped from this XCD's L2, so neither an L2 of this GPU that the owner's kernels do not flush nor
+// a remote GPU's fabric path can hold the bytes back; the host waits for the kernel's completion before the barrier tells the owner.
+// (Plain stores plus one system-scope release per workgroup would do too, but cost a full L2 write-back per workgroup.)
+__device__ __forceinline__ void st_sys(double *p, double v) {
+    __hip_atomic_store((unsigned long long *)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ void st_sys(float *p, float v) { __hip_atomic_store((unsigned *)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+// Loads of bytes another process wrote: system scope (global_load ... sc0 sc1), served from memory -- the half read here was read
+// two steps ago as well, and this GPU's L1 / L2 may still hold those lines, which the writer's stores did not invalidate.
+__device__ __forceinline__ double ld_sys(const double *p) {
+    return __longlong_as_double((long long)__hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+}
+__device__ __forceinline__ float ld_sys(const float *p) { return __uint_as_float(__hip_atomic_load((const unsigned *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)); }
+
+// One launch over the concatenated send list (all neighbours, all b vectors): thread t = element i = t / b of the list, vector v = t % b.
+// The neighbour q is found by a binary search over the P + 1 send offsets (the largest q with seg[q] <= i: empty ranges are skipped).
+// X column-wise (ld) or row-wise; single vector: b = 1, row-wise.  Window layout: halo slot k of vector v at k * b + v.  Thread 0 also
+// keeps the padding column's value before the exchange overwrites it, as pack_kernel does (uspmv_dist::pad_col).
+template <typename VT>
+__global__ void push_kernel(const VT *__restrict__ x, const int *__restrict__ src, const int64_t *__restrict__ seg, const PeerDst *__restrict__ dst,
+                            const int P, const long n, const int b, const long ld, const int rowwise, const int s, const int pad_col,
+                            VT *__restrict__ stale) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t == 0 && pad_col >= 0) *stale = x[pad_col];
+    if (t >= n * b) return;
+    const long i = t / b;
+    const int v = (int)(t - i * b);
+    int lo = 0, hi = P - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    const PeerDst d = dst[lo];
+    const VT val = x[rowwise ? (long)src[i] * b + v : (long)src[i] + (long)v * ld];
+    st_sys((VT *)d.base + (long)s * d.half + (d.off + (i - seg[lo])) * b + v, val);
+}
+
+// window half -> halo region of X: slot k of vector v to X[(n_local + k) * b + v] (row-wise; b = 1: the tail of x) or X[v * ld + n_local + k]
+template <typename VT>
+__global__ void unpack_kernel(VT *__restrict__ x, const VT *__restrict__ win, const long n_local, const long n, const int b, const long ld,
+                              const int rowwise) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * b) return;
+    const long k = t / b;
+    const int v = (int)(t - k * b);
+    x[rowwise ? n_local * b + t : (long)v * ld + n_local + k] = ld_sys(win + t);
+}
+
+int push(uspmv_dist *D, const void *d_x, int b, long ld, int rowwise, long n, int pad_col, hipStream_t st) {
+    // (a window set-up that failed -- the growth in uspmv_dist_spmmv -- leaves the object without windows: refuse, never launch on them)
+    if (!D->d_win || !D->d_push)
+        return uspmv::fail(USPMV_ERR_INVALID, "USPMV_EXCHANGE_PEER: the receive windows were lost in a failed set-up; uspmv_dist_spmmv on every rank "
+                           "sets them up again, or free the object");
+    if (D->unpack_queued) HIP_TRY(hipStreamWaitEvent(st, D->ev_unpack, 0));   // this step's push (and the host's wait for it) after the last unpack
+    if (n == 0 && pad_col < 0) return USPMV_OK;
+    const unsigned grid = (unsigned)std::max<long>((n * b + 255) / 256, 1);
+    const PeerDst *dst = (const PeerDst *)D->d_push.get();
+    if (D->dtype == USPMV_F64)
+        hipLaunchKernelGGL(push_kernel<double>, dim3(grid), dim3(256), 0, st, (const double *)d_x, D->d_src, D->d_seg, dst, D->P, n, b, ld, rowwise, D->parity,
+                           pad_col, (double *)D->d_stale);
+    else
+        hipLaunchKernelGGL(push_kernel<float>, dim3(grid), dim3(256), 0, st, (const float *)d_x, D->d_src, D->d_seg, dst, D->P, n, b, ld, rowwise, D->parity,
+                           pad_col, (float *)D->d_stale);
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
+// After the push of this step (parity s) has been queued on `st`: real ranks wait for it on the host and meet in the transport barrier
+// (deadline: a dead peer fails every rank with USPMV_ERR_COMM), then every push into this rank's window[s] has completed; the unpack
+// follows on the same stream.  Loopback: stream order alone puts the unpack behind the push.
+// Why no rank overwrites a window half before its owner has unpacked it: rank r pushes into q's half s at step k and, next, at step
+// k + 2, after barrier k + 1.  q reaches barrier k + 1 only after its host has waited for its push of step k + 1, which q queued behind
+// its unpack of step k (same stream, or -- when the caller switches streams between steps -- behind ev_unpack, see push) -- so that
+// unpack has completed before anyone leaves barrier k + 1.  The push of step k + 1 itself goes to the other half, which is what the
+// second half is for: q's unpack of step k may still be queued then.
+int peer_complete(uspmv_dist *D, void *d_X, int b, long ld, int rowwise, hipStream_t st) {
+    const int s = D->parity;
+    D->parity ^= 1;
+    if (!D->loopback) {
+        HIP_TRY(hipEventRecord(D->ev_push, st));
+        HIP_TRY(hipEventSynchronize(D->ev_push));
+        if (int rc = D->tr.barrier(D->tr.ctx)) return rc;
+    }
+    const long n = (long)D->n_halo;
+    if (n == 0) return USPMV_OK;
+    if (!D->d_win) return uspmv::fail(USPMV_ERR_INVALID, "USPMV_EXCHANGE_PEER: no receive window");
+    const unsigned grid = (unsigned)((n * b + 255) / 256);
+    const size_t woff = (size_t)s * (size_t)D->win_half;
+    if (D->dtype == USPMV_F64)
+        hipLaunchKernelGGL(unpack_kernel<double>, dim3(grid), dim3(256), 0, st, (double *)d_X, (const double *)D->d_win.get() + woff, (long)D->n_local, n, b, ld, rowwise);
+    else
+        hipLaunchKernelGGL(unpack_kernel<float>, dim3(grid), dim3(256), 0, st, (float *)d_X, (const float *)D->d_win.get() + woff, (long)D->n_local, n, b, ld, rowwise);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(D->ev_unpack, st));
+    D->unpack_queued = true;
+    return USPMV_OK;
+}
+
+// single vector: the push replaces the pack kernel (no d_send round); -no_pack pushes nothing (the window's stale contents are unpacked),
+// diag_skip_exchange stops after the padding slot's value is kept (the halo tail stays what it was)
+int exchange_peer(uspmv_dist *D, void *d_x, hipStream_t st) {
+    const long n = D->no_pack || D->diag_skip_exchange ? 0 : (long)D->n_send;
+    if (int rc = push(D, d_x, 1, 0, 1, n, pads_on(D) ? D->pad_col : -1, st)) return rc;
+    if (D->diag_skip_exchange) return USPMV_OK;
+    return peer_complete(D, d_x, 1, 0, 1, st);
+}
+
+// close what this rank opened, barrier (no rank frees a window another still has open: the HIP header calls freeing an exported region
+// before the importer's hipIpcCloseMemHandle undefined), free the window.  A peer that is gone fails the barrier on its deadline: the
+// window is freed anyway and the barrier's status returned.
+int peer_release(uspmv_dist *D, bool barrier) {
+    if (!D->d_win) return USPMV_OK;
+    (void)hipDeviceSynchronize();                                    // no push or unpack of this process still touches a window
+    for (void *&w : D->peer_win)
+        if (w) { (void)hipIpcCloseMemHandle(w); w = nullptr; }
+    int rc = USPMV_OK;
+    if (barrier && !D->loopback && D->tr.barrier) rc = D->tr.barrier(D->tr.ctx);
+    D->d_win.reset();
+    D->d_push.reset();
+    D->win_half = 0; D->win_b = 0;
+    return rc;
+}
+
+enum { PEER_OK = 0, PEER_MALLOC = 1, PEER_EXPORT = 2, PEER_OPEN = 3, PEER_UPLOAD = 4 };
+const char *peer_call_name(int c) {
+    return c == PEER_MALLOC ? "hipMalloc of the receive window" : c == PEER_EXPORT ? "hipIpcGetMemHandle" : c == PEER_OPEN ? "hipIpcOpenMemHandle" : "upload of the push table";
+}
+
+// Collective: (re)build the windows for block vectors of up to b columns (see above).  Every failure is agreed on: all ranks return the
+// same status and message, and none waits in a barrier for a rank that has given up.  A failure leaves the object without windows (push
+// then refuses every step); a later call sets them up anew.
+int peer_setup(uspmv_dist *D, int b) {
+    const int P = D->P, me = D->rank;
+    const size_t vsz = vsize(D);
+    if (int rc = peer_release(D, true)) return rc;
+    const int64_t half = std::max<int64_t>(D->n_halo * (int64_t)b, 1);
+    // ---- own window, zeroed (-no_pack unpacks it unwritten) and complete before any peer can write into it
+    int status = PEER_OK;
+    hipError_t err = D->d_win.alloc(2 * (size_t)half * vsz);
+    if (err != hipSuccess) status = PEER_MALLOC;
+    if (!status && (err = hipMemset(D->d_win.get(), 0, 2 * (size_t)half * vsz)) == hipSuccess) err = hipDeviceSynchronize();
+    if (!status && err != hipSuccess) status = PEER_MALLOC;
+    hipIpcMemHandle_t handle;
+    memset(&handle, 0, sizeof handle);
+    if (!status && !D->loopback && (err = hipIpcGetMemHandle(&handle, D->d_win.get())) != hipSuccess) status = PEER_EXPORT;
+    (void)hipGetLastError();
+    // ---- one record per rank: status, HIP error, half, n_halo, recv_off[P+1], send_off[P+1], handle
+    const size_t hw = (sizeof handle + 7) / 8, nrec = 4 + 2 * ((size_t)P + 1) + hw;
+    std::vector<int64_t> rec(nrec, 0), all(nrec * (size_t)P, 0);
+    rec[0] = status; rec[1] = (int64_t)err; rec[2] = half; rec[3] = D->n_halo;
+    for (int p = 0; p <= P; ++p) { rec[4 + (size_t)p] = D->recv_off[(size_t)p]; rec[5 + (size_t)P + (size_t)p] = D->send_off[(size_t)p]; }
+    // (test only, option "diag_peer_skew": this rank announces one element more from its first neighbour than that neighbour sends it)
+    if (D->diag_peer_skew)
+        for (int p = 0; p < P; ++p)
+            if (D->recv_off[(size_t)p + 1] > D->recv_off[(size_t)p]) { for (int j = p + 1; j <= P; ++j) ++rec[4 + (size_t)j]; break; }
+    memcpy(&rec[6 + 2 * (size_t)P], &handle, sizeof handle);
+    auto fail_all = [&](int code, const std::string &msg) { D->d_win.reset(); D->win_half = 0; return uspmv::fail(code, "%s", msg.c_str()); };
+    if (int rc = D->tr.allgather(D->tr.ctx, rec.data(), all.data(), (int64_t)(nrec * 8))) { D->d_win.reset(); return rc; }
+    auto R = [&](int q) { return all.data() + (size_t)q * nrec; };
+    const char *hint = " -- on ROCm, IPC between processes needs HSA_ENABLE_IPC_MODE_LEGACY=0 in the environment of every rank";
+    char buf[512];
+    for (int q = 0; q < P; ++q)
+        if (R(q)[0]) {
+            snprintf(buf, sizeof buf, "USPMV_EXCHANGE_PEER set-up: rank %d: %s failed: %s%s", q, peer_call_name((int)R(q)[0]),
+                     hipGetErrorString((hipError_t)R(q)[1]), R(q)[0] == PEER_EXPORT ? hint : "");
+            return fail_all(R(q)[0] == PEER_MALLOC ? USPMV_ERR_ALLOC : USPMV_ERR_HIP, buf);
+        }
+    // ---- validate every pair on the same data (loopback: the records are all this process's, the destination of "q" is its own block)
+    std::vector<PeerDst> tab((size_t)P, PeerDst{nullptr, 0, 0});
+    for (int r = 0; r < P; ++r)
+        for (int q = 0; q < P && (r == me || !D->loopback); ++q) {
+            // loopback: "q expects from me" := what this process asked q for, in its own window
+            const int64_t *so = R(r) + 5 + P, *ro = D->loopback ? R(me) + 4 + q : R(q) + 4 + r, *qq = D->loopback ? R(me) : R(q);
+            const int64_t ns = so[q + 1] - so[q], nr = ro[1] - ro[0];
+            if (ns != nr) {
+                snprintf(buf, sizeof buf, "USPMV_EXCHANGE_PEER set-up: rank %d sends %ld elements to rank %d, which expects %ld from it", r, (long)ns, q, (long)nr);
+                return fail_all(USPMV_ERR_INVALID, buf);
+            }
+            if (ns && (ro[0] < 0 || ro[1] > qq[4 + P] || qq[4 + P] != qq[3] || qq[3] * b > qq[2])) {
+                snprintf(buf, sizeof buf, "USPMV_EXCHANGE_PEER set-up: rank %d's block [%ld, %ld) lies outside rank %d's window (%ld halo slots, %ld x %d elements)",
+                         r, (long)ro[0], (long)ro[1], q, (long)qq[3], (long)qq[2], b);
+                return fail_all(USPMV_ERR_INVALID, buf);
+            }
+            if (r == me && ns) tab[(size_t)q] = PeerDst{nullptr, qq[2], ro[0]};
+        }
+    // ---- open the windows of the ranks this one sends to; agree on the outcome
+    D->peer_win.assign((size_t)P, nullptr);
+    int64_t ost[3] = {PEER_OK, 0, 0};   // status, HIP error, whose window
+    for (int q = 0; q < P; ++q) {
+        if (!tab[(size_t)q].half) continue;
+        if (D->loopback || q == me) { tab[(size_t)q].base = D->d_win.get(); continue; }
+        hipIpcMemHandle_t hq;
+        memcpy(&hq, R(q) + 6 + 2 * (size_t)P, sizeof hq);
+        const hipError_t e = hipIpcOpenMemHandle(&D->peer_win[(size_t)q], hq, hipIpcMemLazyEnablePeerAccess);
+        if (e != hipSuccess) { (void)hipGetLastError(); D->peer_win[(size_t)q] = nullptr; ost[0] = PEER_OPEN; ost[1] = (int64_t)e; ost[2] = q; break; }
+        tab[(size_t)q].base = D->peer_win[(size_t)q];
+    }
+    if (!ost[0]) {
+        hipError_t e = D->d_push.upload(tab.data(), sizeof(PeerDst) * tab.size());
+        if (e == hipSuccess) e = D->d_seg.upload(D->send_off.data(), 8 * D->send_off.size());
+        if (e != hipSuccess) { (void)hipGetLastError(); D->d_push.reset(); ost[0] = PEER_UPLOAD; ost[1] = (int64_t)e; ost[2] = me; }
+    }
+    std::vector<int64_t> oall(3 * (size_t)P, 0);
+    if (D->loopback) std::copy(ost, ost + 3, oall.begin());
+    else if (int rc = D->tr.allgather(D->tr.ctx, ost, oall.data(), sizeof ost)) { (void)peer_release(D, false); return rc; }
+    for (int q = 0; q < (D->loopback ? 1 : P); ++q)
+        if (const int64_t *o = &oall[3 * (size_t)q]; o[0]) {
+            if (o[0] == PEER_OPEN)
+                snprintf(buf, sizeof buf, "USPMV_EXCHANGE_PEER set-up: rank %d: hipIpcOpenMemHandle of rank %ld's window failed: %s%s", q,
+                         (long)o[2], hipGetErrorString((hipError_t)o[1]), hint);
+            else
+                snprintf(buf, sizeof buf, "USPMV_EXCHANGE_PEER set-up: rank %d: %s failed: %s", q, peer_call_name((int)o[0]), hipGetErrorString((hipError_t)o[1]));
+            const std::string msg = buf;
+            (void)peer_release(D, true);                                 // (every rank is here: close, barrier, free)
+            return uspmv::fail(USPMV_ERR_HIP, "%s", msg.c_str());
+        }
+    D->win_half = half; D->win_b = b; D->parity = 0; D->unpack_queued = false;
+    return USPMV_OK;
+}
+
+inline int exchange(uspmv_dist *D, void *d_x, hipStream_t st) {
+    return D->host_exchange ? exchange_host(D, d_x, st) : D->peer_exchange ? exchange_peer(D, d_x, st) : exchange_rccl(D, d_x, st);
+}
+// steps that block the host inside the exchange (host-staged, peer-store between real ranks) run eagerly: there is nothing to capture
+inline bool eager_only(const uspmv_dist *D) { return D->host_exchange || D->peer_exchange; }
 
 int part(uspmv_dist *D, const int32_t *ids, int64_t n, const void *x, void *y, hipStream_t st) {
     if (n == 0) return USPMV_OK;
@@ -271,7 +525,8 @@ int part(uspmv_dist *D, const int32_t *ids, int64_t n, const void *x, void *y, h
 // finished this one, and the host is not involved (so it is part of the captured graph)
 int step_barrier(uspmv_dist *D, hipStream_t main) {
     if (!D->ba_synch || D->P == 1) return USPMV_OK;
-    if (D->host_exchange) {
+    if (!D->comm) {                                                  // (host-staged / peer-store: over the transport; loopback: stream order)
+        if (D->loopback) return USPMV_OK;
         HIP_TRY(hipStreamSynchronize(main));
         return D->tr.barrier ? D->tr.barrier(D->tr.ctx) : USPMV_OK;
     }
@@ -384,6 +639,7 @@ int uspmv_runtime_versions(int v[4]) {
 void uspmv_dist_free(uspmv_dist_t *D) {
     if (!D) return;
     drop_graph(D);
+    (void)peer_release(D, true);                                    // collective: close, barrier, free (see peer_release)
     for (auto &bp : D->block_plans) {
         if (bp.h_send) (void)hipHostFree(bp.h_send);
         if (bp.h_recv) (void)hipHostFree(bp.h_recv);
@@ -392,6 +648,8 @@ void uspmv_dist_free(uspmv_dist_t *D) {
     if (D->h_recv) (void)hipHostFree(D->h_recv);
     if (D->ev_main) (void)hipEventDestroy(D->ev_main);
     if (D->ev_comm) (void)hipEventDestroy(D->ev_comm);
+    if (D->ev_push) (void)hipEventDestroy(D->ev_push);
+    if (D->ev_unpack) (void)hipEventDestroy(D->ev_unpack);
     if (D->side_stream) (void)hipStreamDestroy(D->side_stream);
     if (D->comm) (void)ncclCommDestroy(D->comm);
     uspmv_comm_plan_free(D->plan);
@@ -399,11 +657,12 @@ void uspmv_dist_free(uspmv_dist_t *D) {
     delete D;
 }
 
-int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, uspmv_dmat_t *A, const uspmv_halo_t *halo,
-                         const int32_t *old_to_new_idx, const int32_t *interior_ids, int64_t n_interior, const int32_t *boundary_ids,
-                         int64_t n_boundary, int ids_are_tiles, const uspmv_dist_options_t *opt, uspmv_dist_t **out) {
-    const bool host_ex = opt && opt->exchange == USPMV_EXCHANGE_HOST;
-    if (opt && opt->exchange != USPMV_EXCHANGE_RCCL && opt->exchange != USPMV_EXCHANGE_HOST)
+// uspmv_dist_create_ex; windows = false leaves the collective window set-up of USPMV_EXCHANGE_PEER to the caller
+static int create_dist(const void *comm_id, int comm_rank, int comm_size, int rank, int P, uspmv_dmat_t *A, const uspmv_halo_t *halo,
+                       const int32_t *old_to_new_idx, const int32_t *interior_ids, int64_t n_interior, const int32_t *boundary_ids,
+                       int64_t n_boundary, int ids_are_tiles, const uspmv_dist_options_t *opt, uspmv_dist_t **out, bool windows) {
+    const bool host_ex = opt && opt->exchange == USPMV_EXCHANGE_HOST, peer_ex = opt && opt->exchange == USPMV_EXCHANGE_PEER;
+    if (opt && opt->exchange != USPMV_EXCHANGE_RCCL && opt->exchange != USPMV_EXCHANGE_HOST && opt->exchange != USPMV_EXCHANGE_PEER)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: unknown exchange %d", opt->exchange);
     if (!A || !halo || !out || P < 1 || rank < 0 || rank >= P || n_interior < 0 || n_boundary < 0 || (n_interior > 0 && !interior_ids) ||
         (n_boundary > 0 && !boundary_ids))
@@ -411,6 +670,16 @@ int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int 
     if (host_ex) {
         if (!opt->transport || !opt->transport->alltoallv) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: USPMV_EXCHANGE_HOST needs a transport");
         comm_rank = rank; comm_size = P;
+    } else if (peer_ex) {
+        // comm_size == P: real ranks, which need a transport (set-up exchanges, per-step barrier); comm_size == 1: loopback, no transport
+        if (comm_size < 1 || comm_rank < 0 || comm_rank >= comm_size) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: bad communicator argument");
+        if (!(comm_size == P && comm_rank == rank) && !(comm_size == 1 && comm_rank == 0))
+            return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: USPMV_EXCHANGE_PEER takes one rank per partition block (comm_size == P) or a single rank (loopback)");
+        if (comm_size == P && P > 1 && (!opt->transport || !opt->transport->allgather || !opt->transport->barrier))
+            return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: USPMV_EXCHANGE_PEER between real ranks needs a transport with all-gather and barrier "
+                               "(it carries the set-up exchanges and the per-step barrier)");
+        if (comm_size == 1 && P > 1 && opt->transport)
+            return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: USPMV_EXCHANGE_PEER in loopback takes no transport");
     } else {
         if (!comm_id || comm_size < 1 || comm_rank < 0 || comm_rank >= comm_size) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: bad communicator argument");
         if (!(comm_size == P && comm_rank == rank) && !(comm_size == 1 && comm_rank == 0))
@@ -424,14 +693,14 @@ int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int 
     if (int rc = uspmv_dev::require_device()) return rc;
     auto *D = new uspmv_dist;
     D->rank = rank; D->P = P; D->comm_rank = comm_rank; D->comm_size = comm_size; D->loopback = !host_ex && comm_size == 1 && P > 1;
-    D->host_exchange = host_ex;
+    D->host_exchange = host_ex; D->peer_exchange = peer_ex;
     D->A = A; D->dtype = A->dtype; D->tiles = ids_are_tiles != 0;
     D->n_local = halo->n_local; D->n_halo = halo->n_halo; D->n_int = n_interior; D->n_bnd = n_boundary;
     D->recv_counts = halo->recv_counts;
     auto bail = [&](int code) { uspmv_dist_free(D); return code; };
 #define D_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bail(uspmv::fail(USPMV_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); } while (0)
 #define D_NCCL(call) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) return bail(uspmv::fail(USPMV_ERR_HIP, "%s failed: %s (%s:%d)", #call, ncclGetErrorString(r_), __FILE__, __LINE__)); } while (0)
-    if (!host_ex) {
+    if (!host_ex && !peer_ex) {
         ncclUniqueId id;
         memcpy(&id, comm_id, sizeof id);
         D_NCCL(ncclCommInitRank(&D->comm, comm_size, id, comm_rank));
@@ -439,6 +708,8 @@ int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int 
     D_HIP(hipStreamCreateWithFlags(&D->side_stream, hipStreamNonBlocking));
     D_HIP(hipEventCreateWithFlags(&D->ev_main, hipEventDisableTiming));
     D_HIP(hipEventCreateWithFlags(&D->ev_comm, hipEventDisableTiming));
+    if (peer_ex) D_HIP(hipEventCreateWithFlags(&D->ev_push, hipEventDisableTiming));
+    if (peer_ex) D_HIP(hipEventCreateWithFlags(&D->ev_unpack, hipEventDisableTiming));
     D_HIP(D->d_scratch.zeros(256));
     // ---- who sends what to whom (collect_comm_info, code/mpi_funcs.hpp:1061-1124) over the set-up transport
     if (opt && opt->transport) D->tr = *opt->transport;
@@ -467,7 +738,7 @@ int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int 
     }
     D_HIP(D->d_int.upload(interior_ids, 4 * (size_t)n_interior));
     D_HIP(D->d_bnd.upload(boundary_ids, 4 * (size_t)n_boundary));
-    D_HIP(D->d_send.alloc(vsz * (size_t)std::max<int64_t>(D->n_send, 1)));
+    if (!peer_ex) D_HIP(D->d_send.alloc(vsz * (size_t)std::max<int64_t>(D->n_send, 1)));   // (peer stores: the push replaces the pack)
     if (host_ex) {
         D_HIP(hipHostMalloc(&D->h_send, vsz * (size_t)std::max<int64_t>(D->n_send, 1), hipHostMallocDefault));
         D_HIP(hipHostMalloc(&D->h_recv, vsz * (size_t)std::max<int64_t>(D->n_halo, 1), hipHostMallocDefault));
@@ -488,10 +759,21 @@ int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int 
         if (int rc = uspmv_dev::dmat_part_set_chunks(A, flag.data())) return bail(rc);
         D->parts = true;
     }
+    // the collective window set-up last, after every check that could fail on one rank alone (that rank's free would then enter a barrier
+    // the others never join); uspmv_dist_create_from_coo_ex runs it after its own rank-local steps instead
+    if (peer_ex && P > 1 && windows)
+        if (int rc = peer_setup(D, 1)) return bail(rc);
 #undef D_HIP
 #undef D_NCCL
     *out = D;
     return USPMV_OK;
+}
+
+int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, uspmv_dmat_t *A, const uspmv_halo_t *halo,
+                         const int32_t *old_to_new_idx, const int32_t *interior_ids, int64_t n_interior, const int32_t *boundary_ids,
+                         int64_t n_boundary, int ids_are_tiles, const uspmv_dist_options_t *opt, uspmv_dist_t **out) {
+    return create_dist(comm_id, comm_rank, comm_size, rank, P, A, halo, old_to_new_idx, interior_ids, n_interior, boundary_ids, n_boundary,
+                       ids_are_tiles, opt, out, true);
 }
 
 int uspmv_dist_create(const void *comm_id, int comm_rank, int comm_size, int rank, int P, uspmv_dmat_t *A, const uspmv_halo_t *halo,
@@ -559,8 +841,8 @@ int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_s
     }
     uspmv_free(interior); uspmv_free(boundary); interior = boundary = nullptr;
     uspmv_dist_t *D = nullptr;
-    rc = uspmv_dist_create_ex(comm_id, comm_rank, comm_size, rank, P, A, halo, o2n, ids_int.data(), (int64_t)ids_int.size(), ids_bnd.data(),
-                              (int64_t)ids_bnd.size(), use_tiles ? 1 : 0, opt, &D);
+    rc = create_dist(comm_id, comm_rank, comm_size, rank, P, A, halo, o2n, ids_int.data(), (int64_t)ids_int.size(), ids_bnd.data(),
+                     (int64_t)ids_bnd.size(), use_tiles ? 1 : 0, opt, &D, false);
     if (rc) { cleanup(); return rc; }
     if (use_tiles && P > 1) {
         const bool pads = pad_col >= 0 && !ids_pad.empty();
@@ -592,6 +874,9 @@ int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_s
         D->sa.ss = D->d_ss; D->sa.defer = D->d_defer; D->sa.stale = D->d_stale; D->sa.pad_col = pads ? pad_col : -1;
         if ((rc = sync_reset(D))) { uspmv_dist_free(D); cleanup(); return rc; }
     }
+    // (the collective window set-up after every step above that could fail on this rank alone)
+    if (D->peer_exchange && P > 1)
+        if ((rc = peer_setup(D, 1))) { uspmv_dist_free(D); cleanup(); return rc; }
     D->owns_setup = true; D->scs = scs; D->halo = halo;
     *out = D;
     return USPMV_OK;
@@ -641,14 +926,21 @@ int uspmv_dist_set_option(uspmv_dist_t *D, const char *key, int value) {
         drop_graph(D); D->graph_failed = false;
     }
     else if (k == "diag_skip_exchange") { drop_graph(D); D->diag_skip_exchange = value != 0; }
+    else if (k == "diag_peer_skew") D->diag_peer_skew = value != 0;
     else return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_set_option: unknown key '%s'", key);
     return USPMV_OK;
 }
 
 int uspmv_dist_comm_count(const uspmv_dist_t *D, int *n_ranks) {
     if (!D || !n_ranks) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_comm_count: NULL argument");
-    *n_ranks = 0;                                                   // (host-staged exchange: no RCCL communicator exists)
+    *n_ranks = 0;                                                   // (host-staged / peer-store exchange: no RCCL communicator exists)
     if (D->comm) NCCL_TRY(ncclCommCount(D->comm, n_ranks));
+    return USPMV_OK;
+}
+
+int uspmv_dist_exchange(const uspmv_dist_t *D, int *exchange) {
+    if (!D || !exchange) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_exchange: NULL argument");
+    *exchange = D->host_exchange ? USPMV_EXCHANGE_HOST : D->peer_exchange ? USPMV_EXCHANGE_PEER : USPMV_EXCHANGE_RCCL;
     return USPMV_OK;
 }
 
@@ -707,7 +999,7 @@ int uspmv_dist_spmv(uspmv_dist_t *D, void *d_x, void *d_y, int comm_halos, void 
 int uspmv_dist_run(uspmv_dist_t *D, void *d_x, void *d_y, int n_steps, int use_graph, void *stream) {
     if (!D || !d_x || !d_y || n_steps < 0) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_run: bad argument");
     hipStream_t main = (hipStream_t)stream;
-    if (use_graph && D->P > 1 && !D->graph_failed && !D->host_exchange) {   // (the host-staged exchange blocks the host: nothing to capture)
+    if (use_graph && D->P > 1 && !D->graph_failed && !eager_only(D)) {   // (the host-staged / peer-store exchange blocks the host: nothing to capture)
         if (!main) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_run: graph replay needs an explicit (non-default) stream");
         if (!D->gexec || D->g_x != d_x || D->g_y != d_y || D->g_stream != main) {
             // RCCL sets up its p2p channels at the first use of a pair: one eager step before the capture
@@ -753,7 +1045,7 @@ int uspmv_dist_autotune(uspmv_dist_t *D, void *d_x, void *d_y, int use_graph, co
     std::vector<int> cand = {USPMV_STEP_OVERLAP, USPMV_STEP_PLAIN};
     if (D->autotune_all) {
         cand.push_back(USPMV_STEP_PAD);
-        if (!use_graph || D->host_exchange) cand.push_back(USPMV_STEP_FUSED);      // (a captured step never takes the one-launch form)
+        if (!use_graph || eager_only(D)) cand.push_back(USPMV_STEP_FUSED);      // (a captured step never takes the one-launch form)
     }
     // every collective the measurement uses once before anything is timed (RCCL sets its channels up lazily, 40 ms the first time), and two
     // rounds over the candidates of which the faster counts: the first candidate must not pay for a cold start
@@ -803,7 +1095,7 @@ int uspmv_dist_autotune(uspmv_dist_t *D, void *d_x, void *d_y, int use_graph, co
 
 int uspmv_dist_barrier(uspmv_dist_t *D, void *stream) {
     if (!D) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_barrier: NULL argument");
-    if (D->host_exchange) {
+    if (!D->comm) {                                                  // no RCCL communicator: over the transport
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
         return D->tr.barrier ? D->tr.barrier(D->tr.ctx) : USPMV_OK;
     }
@@ -814,7 +1106,7 @@ int uspmv_dist_barrier(uspmv_dist_t *D, void *stream) {
 
 int uspmv_dist_allreduce_max(uspmv_dist_t *D, double *value, void *stream) {
     if (!D || !value) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_allreduce_max: NULL argument");
-    if (D->host_exchange) {
+    if (!D->comm) {
         if (!D->tr.allgather) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_allreduce_max: the transport has no all-gather");
         std::vector<double> all((size_t)D->P, *value);
         if (int rc = D->tr.allgather(D->tr.ctx, value, all.data(), 8)) return rc;
@@ -832,7 +1124,7 @@ int uspmv_dist_allreduce_max(uspmv_dist_t *D, double *value, void *stream) {
 int uspmv_dist_allgather_i64(uspmv_dist_t *D, int64_t value, int64_t *all, void *stream) {
     if (!D || !all) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_allgather_i64: NULL argument");
     if (D->loopback) { for (int p = 0; p < D->P; ++p) all[p] = value; return USPMV_OK; }
-    if (D->host_exchange) {
+    if (!D->comm) {
         if (!D->tr.allgather) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_allgather_i64: the transport has no all-gather");
         return D->tr.allgather(D->tr.ctx, &value, all, 8);
     }
@@ -941,6 +1233,17 @@ uspmv_dist::BlockPlan *block_plan(uspmv_dist *D, int b, int layout, int mode) {
 }
 
 int exchange_block(uspmv_dist *D, void *d_X, int b, int layout, int mode, hipStream_t st) {
+    if (D->peer_exchange) {
+        // USPMV_EXCHANGE_PEER: one push of all b columns into windows sized for n_halo x b (grown collectively -- the call is collective --
+        // the first time a wider block appears), one unpack into the halo region of X.  Stores carry no messages, so the three patterns
+        // share this one wire format; the halo region receives the same values as with the other exchanges.
+        if ((int64_t)b * std::max(D->vec_len, (int64_t)1) > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "uspmv_dist_spmmv: b * padded_vec_size exceeds int32");
+        if (b > D->win_b)
+            if (int rc = peer_setup(D, b)) return rc;
+        const int rowwise = layout == USPMV_ROWWISE;
+        if (int rc = push(D, d_X, b, (long)D->vec_len, rowwise, (long)D->n_send, -1, st)) return rc;
+        return peer_complete(D, d_X, b, (long)D->vec_len, rowwise, st);
+    }
     uspmv_dist::BlockPlan *bp = block_plan(D, b, layout, mode);
     if (!bp) return USPMV_ERR_ALLOC;
     const size_t vsz = D->dtype == USPMV_F64 ? 8 : 4;

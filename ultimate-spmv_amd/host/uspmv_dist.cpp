@@ -26,7 +26,9 @@
 // Single-GPU rehearsal of the whole path: USPMV_LOOPBACK=P (with WORLD_SIZE unset) makes this process block
 // $USPMV_LOOPBACK_RANK (default 0) of a P-way partition whose neighbours are itself (RCCL self send/recv); USPMV_EXCHANGE=host
 // with WORLD_SIZE = P real processes stages the halo exchange through the host communicator instead of RCCL, so that the
-// ranks may share one GPU (unequal seg-nnz blocks included).
+// ranks may share one GPU (unequal seg-nnz blocks included).  USPMV_EXCHANGE=peer stores the halos straight into the neighbours'
+// receive windows (IPC handles; real ranks or USPMV_LOOPBACK); it defaults HSA_ENABLE_IPC_MODE_LEGACY=0, which IPC between processes
+// needs on ROCm, before the first HIP call.
 // USPMV_DIST_X=ramp sets x_local[i] = 1 + 1e-3 * (i mod 1000) in ORIGINAL local row order on every rank (the default is the
 // reference's constant 5.0); USPMV_DUMP_Y=<prefix> writes y of the local rows in original order to <prefix>.<rank> (raw
 // doubles) after one step (with -seg_metis also <prefix>.perm: permuted row r = original row perm[r]).  tests/test_dist_native_gpu.py
@@ -109,8 +111,9 @@ int uspmv_run_distributed(const DistConfig &c) {
     if (rank < 0 || rank >= P) die("bad rank");
     g.rank = rank;
     const char *exk = getenv("USPMV_EXCHANGE");
-    const bool host_exchange = exk && !strcmp(exk, "host");
+    const bool host_exchange = exk && !strcmp(exk, "host"), peer_exchange = exk && !strcmp(exk, "peer");
     if (host_exchange && loop_P > 1) die("USPMV_EXCHANGE=host needs real ranks (WORLD_SIZE = P), not USPMV_LOOPBACK");
+    if (peer_exchange) setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);   // (before the first HIP call; a value the caller set stays)
     if (getenv("USPMV_BACKTRACE")) uspmv_debug_backtrace_on_crash(1);
     int ndev = 0;
     CK(uspmv_device_count(&ndev));
@@ -124,7 +127,7 @@ int uspmv_run_distributed(const DistConfig &c) {
     uint64_t nonce = 0;
     CK(uspmv_hostcomm_info(g.hc, nullptr, nullptr, &nonce));
     unsigned char id[USPMV_COMM_ID_BYTES] = {0};
-    if (!host_exchange) {
+    if (!host_exchange && !peer_exchange) {
         if (comm_rank == 0) CK(uspmv_comm_unique_id(id));
         CK(uspmv_hostcomm_bcast(g.hc, id, sizeof id, 0));
     }
@@ -189,9 +192,9 @@ int uspmv_run_distributed(const DistConfig &c) {
     // ---- the distributed object: convert, halo discovery, upload, plan, exchange plan, communicator (init_local_structs + collect_comm_info)
     uspmv_dist_t *D = nullptr;
     uspmv_transport_t tr{};
-    uspmv_dist_options_t opt{nullptr, host_exchange ? USPMV_EXCHANGE_HOST : USPMV_EXCHANGE_RCCL};
+    uspmv_dist_options_t opt{nullptr, host_exchange ? USPMV_EXCHANGE_HOST : peer_exchange ? USPMV_EXCHANGE_PEER : USPMV_EXCHANGE_RCCL};
     const char *stk = getenv("USPMV_SETUP_TRANSPORT");
-    const bool setup_on_rccl = stk && !strcmp(stk, "rccl") && !host_exchange;
+    const bool setup_on_rccl = stk && !strcmp(stk, "rccl") && !host_exchange && !peer_exchange;
     if (comm_size == P && P > 1 && !setup_on_rccl) { CK(uspmv_hostcomm_transport(g.hc, &tr)); opt.transport = &tr; }
     // -rand_x 1 | m: min / max of |values| over the WHOLE matrix, taken before any scaling (extract_matrix_min_mean_max on rank 0 +
     // MPI_Bcast in the reference, code/main.cpp:1096, code/utilities.hpp:2502-2540; here every rank contributes its block)
@@ -211,7 +214,7 @@ int uspmv_run_distributed(const DistConfig &c) {
     // -equilibrate 1: every rank scales ITS block (rows, then columns of the row-scaled block), as the reference does after the
     // segmentation (code/main.cpp:1117-1125 on local_mtx)
     if (c.equilibrate) CK(uspmv_coo_equilibrate(local));
-    CK(uspmv_dist_create_from_coo_ex(host_exchange ? nullptr : id, comm_rank, comm_size, rank, P, local, wsa.data(), c.C, c.sigma, c.sp ? USPMV_F32 : USPMV_F64, c.tlc ? 1 : 0, &opt, &D));
+    CK(uspmv_dist_create_from_coo_ex(host_exchange || peer_exchange ? nullptr : id, comm_rank, comm_size, rank, P, local, wsa.data(), c.C, c.sigma, c.sp ? USPMV_F32 : USPMV_F64, c.tlc ? 1 : 0, &opt, &D));
     // (the block's COO stays until the end: -rand_x reads its values, -step_form auto and -check_y run the self-check against it)
     stage("step object created (communicator up)");
     hipStream_t st = nullptr;
@@ -480,7 +483,7 @@ int uspmv_run_distributed(const DistConfig &c) {
             f << std::endl;
         }
         printf("%d ranks%s, n = %ld, nnz = %ld: Total Gflops: %.4f (%d iterations in %.4f s, %.6f ms per SpMV); rank %d: %.1f GB/s algorithmic, "
-               "%ld halo elements, %ld interior + %ld boundary %s, %s, ba_synch %d%s\n", P, meta[8] ? " (loopback)" : host_exchange ? " (host-staged exchange)" : "", (long)n_rows_g, (long)nnz_g, perf, n_iter, runtime,
+               "%ld halo elements, %ld interior + %ld boundary %s, %s, ba_synch %d%s\n", P, meta[8] ? " (loopback)" : host_exchange ? " (host-staged exchange)" : peer_exchange ? " (peer-store exchange)" : "", (long)n_rows_g, (long)nnz_g, perf, n_iter, runtime,
                runtime / n_iter * 1e3, rank, bytes / (runtime / n_iter) / 1e9, (long)n_halo, (long)meta[4], (long)meta[5], meta[6] ? "tiles" : "chunks",
                meta[9] ? "hipGraph replay" : "eager steps", c.ba_synch && c.comm_halos ? 1 : 0,
                mism_total < 0 ? "" : mism_total == 0 ? ", y checked bitwise on every rank: ok" : ", y CHECK FAILED");
@@ -512,7 +515,7 @@ int uspmv_run_distributed(const DistConfig &c) {
                      "\"rank0\": {\"n_local\": %ld, \"n_halo\": %ld, \"n_send\": %ld, \"interior\": %ld, \"boundary\": %ld, \"tiles\": %s, \"n_elements\": %ld, "
                      "\"n_chunks\": %ld, \"n_rows_padded\": %ld, \"algorithmic_bytes\": %.0f, \"local_kernel_ms\": %.6f}, "
                      "\"rccl_nranks\": %d, \"versions\": {\"hip_build\": %d, \"hip_runtime\": %d, \"rccl_build\": %d, \"rccl_runtime\": %d}",
-                     perf, runtime / n_iter * 1e3, n_iter, warm, runtime, P, meta[8] ? "true" : "false", host_exchange ? "host" : "rccl", (long)n_rows_g, (long)nnz_g,
+                     perf, runtime / n_iter * 1e3, n_iter, warm, runtime, P, meta[8] ? "true" : "false", host_exchange ? "host" : peer_exchange ? "peer" : "rccl", (long)n_rows_g, (long)nnz_g,
                      protocol, c.ba_synch && c.comm_halos ? 1 : 0, meta[9] ? "true" : "false", (long)meta[10], (long)meta[11], form == "plain" ? "false" : "true", form.c_str(), form_report.c_str(), runtime_other / n_iter * 1e3,
                      mism_total < 0 ? "null" : mism_total == 0 ? "true" : "false", (long)mism_total, checksum, (long)n_local, (long)n_halo, (long)n_send,
                      (long)meta[4], (long)meta[5], meta[6] ? "true" : "false", (long)n_el, (long)n_chunks, (long)n_pad, bytes, kernel_ms,

@@ -513,7 +513,7 @@ int uspmv_dist_comm_plan(const uspmv_dist_t *d, int64_t *n_send, const int64_t *
 /* Options by name: "overlap" 1|0, "no_pack" 0|1, "ba_synch" 0|1 (a stream-ordered one-element all-reduce after every step: the
  * MPI_Barrier the reference issues per iteration by default, code/main.cpp:467, :417; part of the captured graph),
  * "capture_mode" 0 global | 1 thread-local | 2 relaxed (hipStreamCaptureMode of uspmv_dist_run's capture),
- * "diag_skip_exchange" 0|1 (diagnosis only: the step skips the RCCL group, results are wrong),
+ * "diag_skip_exchange" 0|1 (diagnosis only: the step skips the halo exchange, results are wrong),
  * "diag_peer_skew" 0|1 (test only, USPMV_EXCHANGE_PEER: this rank announces one halo element too many from its first neighbour at the
  *   next window set-up -- the growth in uspmv_dist_spmmv -- which every rank must then refuse alike),
  * "fused_step" 0|1 (default 0; tile lists: the step's tiles in ONE launch -- interior and padding tiles first, the boundary tiles at the end of
@@ -559,7 +559,8 @@ int uspmv_dist_info(const uspmv_dist_t *d, int64_t meta[12]);
 /* borrowed handles of an object made by uspmv_dist_create_from_coo (NULL scs / halo otherwise) */
 int uspmv_dist_parts(const uspmv_dist_t *d, const uspmv_scs_t **scs, const uspmv_dmat_t **A, const uspmv_halo_t **halo);
 int uspmv_dist_set_overlap(uspmv_dist_t *d, int overlap);
-/* -no_pack 1 of the reference (code/classes_structs.hpp:941): skip the pack kernel, the exchange ships a stale buffer (timing only) */
+/* -no_pack 1 of the reference (code/classes_structs.hpp:941): no element is packed (pushed), every exchange of the object ships a
+ * stale buffer (timing only) */
 int uspmv_dist_set_no_pack(uspmv_dist_t *d, int no_pack);
 /* one step, issued eagerly: d_x (padded_vec_size elements; its halo tail is written), d_y (n_rows_padded written) */
 int uspmv_dist_spmv(uspmv_dist_t *d, void *d_x, void *d_y, int comm_halos, void *stream);

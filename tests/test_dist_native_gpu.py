@@ -212,6 +212,18 @@ def test_native_block_vector_exchange_loopback_bitexact(pkg, orc):
                 col = Yh[v:d.n_rows_padded * b:b] if layout == pkg.ROWWISE else Yh[v * ld:v * ld + d.n_rows_padded]
                 got = pkg.apply_permutation(np.ascontiguousarray(col), d.old_to_new)[:nl]
                 assert np.array_equal(got, refs[v][0][wsa[rank]:wsa[rank + 1]]), (rank, layout, mode, v)
+        # "diag_skip_exchange" reaches the block exchange: the halo region of a fresh X stays zero, so boundary rows differ; the next
+        # step without it fills the halo region again and is bitwise right
+        for skip in (1, 0):
+            d.set_option("diag_skip_exchange", skip)
+            if skip:
+                X = d.new_X(Xo, b, pkg.COLWISE)
+            Y = torch.zeros(b * ld, dtype=torch.float64, device="cuda")
+            d.spmmv(X, Y, b, pkg.COLWISE, 0); d.synchronize()
+            Yh = Y.cpu().numpy()
+            same = [np.array_equal(pkg.apply_permutation(np.ascontiguousarray(Yh[v * ld:v * ld + d.n_rows_padded]), d.old_to_new)[:nl],
+                                   refs[v][0][wsa[rank]:wsa[rank + 1]]) for v in range(b)]
+            assert same == [not skip] * b, (rank, skip, same)
         with pytest.raises(pkg.UspmvError):
             d.spmmv(d.new_X(Xo, b, pkg.ROWWISE), torch.zeros(b * ld, dtype=torch.float64, device="cuda"), b, pkg.ROWWISE, 1)
         d.close()

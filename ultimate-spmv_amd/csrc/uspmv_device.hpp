@@ -57,6 +57,35 @@ class DeviceBuf {
     T *p_ = nullptr;
 };
 
+// An owned pinned host allocation (hipHostMalloc), shaped like DeviceBuf: move-only, freed by its destructor or reset().
+class PinnedBuf {
+  public:
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    PinnedBuf(PinnedBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~PinnedBuf() { reset(); }
+    void reset() {
+        if (p_) (void)hipHostFree(p_);
+        p_ = nullptr;
+    }
+    void *get() const { return p_; }
+    hipError_t alloc(size_t bytes) {
+        reset();
+        void *q = nullptr;
+        const hipError_t e = hipHostMalloc(&q, bytes, hipHostMallocDefault);
+        p_ = q;
+        return e;
+    }
+
+  private:
+    void *p_ = nullptr;
+};
+
 // The device matrix.  Every plan family is one member struct holding its device arrays and metadata; `on` says the plan is installed,
 // and assigning {} to the member releases the plan and resets every field of it.
 struct uspmv_dmat {

@@ -24,7 +24,7 @@
 // ONE GPU, which is how the step runs with unequal seg-nnz blocks and asymmetric lists on a single-GPU box.
 // USPMV_EXCHANGE_PEER: every rank owns a receive window (hipMalloc, exported by hipIpcGetMemHandle) and one push kernel stores its
 // halo contributions straight into the neighbours' windows; completion is host-ordered (event, transport barrier), then an unpack
-// kernel copies the window into the tail of x.  No communication kernel, no host copy of the data (see exchange_peer).
+// kernel copies the window into the tail of x.  No communication kernel, no host copy of the data (see push, peer_complete).
 //
 // Round 3 additions in this file: optional arrangements of the step around the exchange ("pad_split": tiles that touch the halo only
 // through the reference's padding run before the exchange under a sign / finiteness guard; "fused_step": one launch whose boundary
@@ -40,8 +40,8 @@
 
 struct uspmv_dist {
     int rank = 0, P = 1, comm_rank = 0, comm_size = 1;
-    bool loopback = false, overlap = true, tiles = false, owns_setup = false, no_pack = false, ba_synch = false, host_exchange = false;
-    bool peer_exchange = false;       // USPMV_EXCHANGE_PEER (see "peer-store exchange" below)
+    int exchange = USPMV_EXCHANGE_RCCL;   // the per-step exchange (uspmv_exchange; USPMV_EXCHANGE_PEER: see "peer-store exchange" below)
+    bool loopback = false, overlap = true, tiles = false, owns_setup = false, no_pack = false, ba_synch = false;
     bool diag_skip_exchange = false;
     bool autotune_all = false;        // uspmv_dist_autotune also times the speculative arrangements (pad, fused); off: overlap | plain only
     int diag_spmmv_part = 0;          // diagnosis: the two-part block-vector step runs only its interior (1) or boundary (2) part
@@ -59,7 +59,7 @@ struct uspmv_dist {
     std::vector<int64_t> send_off, recv_off;
     std::vector<int32_t> recv_counts;
     DeviceBuf<int32_t> d_send_idxs, d_perm, d_int, d_bnd;
-    DeviceBuf<int32_t> d_src;         // pack: send[i] = x[d_src[i]], d_src = perm[send_idxs] composed once
+    DeviceBuf<int32_t> d_src;         // send[i] = x[d_src[i]], d_src = perm[send_idxs] composed once: the pack of every b = 1 plan, the push
     // Padding tiles (tile lists only).  The reference pads chunks with (value +0, column 0); on ranks > 0 column 0 is a halo column
     // (code/mpi_funcs.hpp:279-306), so more than half of a rank's tiles "touch the halo" only through fma(+0, x[pad_col], acc).  Those
     // run with the interior tiles, before the exchange has delivered x[pad_col]: for a finite operand of the same sign the product is
@@ -80,8 +80,6 @@ struct uspmv_dist {
     int32_t pad_col = -1;
     bool pad_split = false;           // (off by default: on one GPU it measures 0.221 against 0.209 ms per step, profiles/r03/dist_step_ab.txt)
     DeviceBuf<void> d_stale;
-    DeviceBuf<void> d_send;
-    void *h_send = nullptr, *h_recv = nullptr;   // pinned staging of USPMV_EXCHANGE_HOST
     // peer-store exchange: this rank's receive window = two halves (step parity) of win_half elements, sized for block vectors of up to
     // win_b columns; the windows of the ranks it sends to, opened through IPC (nullptr: not opened; loopback opens nothing); the push
     // table (per neighbour q: q's window, its half size, where this rank's block starts in it) and the send offsets it is indexed by
@@ -101,13 +99,14 @@ struct uspmv_dist {
     hipStream_t g_stream = nullptr;
     bool graph_failed = false;
     int64_t graph_launches = 0, eager_steps = 0;
-    // block-vector exchange plans, one per (b, layout, mode) used so far
+    // exchange plans of RCCL and USPMV_EXCHANGE_HOST, one per (b, layout, mode) used so far; the single-vector step's
+    // (1, USPMV_ROWWISE, USPMV_BULKVEC) is built with the object
     struct BlockPlan {
         int b = 0, layout = 0, mode = 0;
-        DeviceBuf<int32_t> d_src;                    // wire order of the send buffer: send[i] = X[d_src[i]]
+        DeviceBuf<int32_t> d_src;                    // wire order of the send buffer: send[i] = X[d_src[i]] (b = 1: uspmv_dist::d_src)
         std::vector<DeviceBuf<int32_t>> d_unpack;    // staged receive (bulk, column-wise): per vector, halo slot -> position in d_recv
         DeviceBuf<void> d_send, d_recv;
-        void *h_send = nullptr, *h_recv = nullptr;   // pinned staging of USPMV_EXCHANGE_HOST
+        PinnedBuf h_send, h_recv;                    // pinned staging of USPMV_EXCHANGE_HOST
     };
     std::vector<BlockPlan> block_plans;
     std::vector<int32_t> h_send_idxs, h_perm;        // host copies for building those plans
@@ -222,15 +221,14 @@ inline bool fused_on(const uspmv_dist *D) { return D->fused && D->overlap && D->
 
 inline bool pads_on(const uspmv_dist *D) { return D->pad_split && D->overlap && D->tiles && D->n_pad > 0 && D->pad_col >= 0; }
 
-int pack(uspmv_dist *D, void *d_x, hipStream_t st) {
-    const long n = D->no_pack ? 0 : (long)D->n_send;           // (-no_pack 1: a stale buffer travels, timing only)
-    const int pc = pads_on(D) ? D->pad_col : -1;
-    if (n == 0 && pc < 0) return USPMV_OK;
+// send[i] = X[src[i]] for i < n, and the padding column's value when pad_col >= 0
+int pack(uspmv_dist *D, void *send, const void *d_X, const int32_t *src, long n, int pad_col, hipStream_t st) {
+    if (n == 0 && pad_col < 0) return USPMV_OK;
     const unsigned grid = (unsigned)std::max<long>((n + 255) / 256, 1);
     if (D->dtype == USPMV_F64)
-        hipLaunchKernelGGL(pack_kernel<double>, dim3(grid), dim3(256), 0, st, (double *)D->d_send, (const double *)d_x, D->d_src, n, pc, (double *)D->d_stale);
+        hipLaunchKernelGGL(pack_kernel<double>, dim3(grid), dim3(256), 0, st, (double *)send, (const double *)d_X, src, n, pad_col, (double *)D->d_stale);
     else
-        hipLaunchKernelGGL(pack_kernel<float>, dim3(grid), dim3(256), 0, st, (float *)D->d_send, (const float *)d_x, D->d_src, n, pc, (float *)D->d_stale);
+        hipLaunchKernelGGL(pack_kernel<float>, dim3(grid), dim3(256), 0, st, (float *)send, (const float *)d_X, src, n, pad_col, (float *)D->d_stale);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }
@@ -244,34 +242,6 @@ int pad_guard(uspmv_dist *D, const void *d_x, hipStream_t st) {
         hipLaunchKernelGGL(pad_guard_kernel<float>, dim3(grid), dim3(256), 0, st, (const float *)d_x, D->pad_col, (const float *)D->d_stale, D->d_pad, D->d_late + D->n_bnd_real,
                            (long)D->n_pad, D->d_scratch + 2);
     HIP_TRY(hipGetLastError());
-    return USPMV_OK;
-}
-
-int exchange_rccl(uspmv_dist *D, void *d_x, hipStream_t st) {
-    const size_t vsz = vsize(D);
-    if (int rc = pack(D, d_x, st)) return rc;
-    if (D->diag_skip_exchange) return USPMV_OK;
-    NCCL_TRY(ncclGroupStart());
-    for (int p = 0; p < D->P; ++p) {
-        const int64_t ns = D->send_off[(size_t)p + 1] - D->send_off[(size_t)p], nr = D->recv_counts[(size_t)p];
-        if (nr) NCCL_TRY(ncclRecv((char *)d_x + (size_t)(D->n_local + D->recv_off[(size_t)p]) * vsz, (size_t)nr, nccl_vt(D), peer(D, p), D->comm, st));
-        if (ns) NCCL_TRY(ncclSend((const char *)D->d_send + (size_t)D->send_off[(size_t)p] * vsz, (size_t)ns, nccl_vt(D), peer(D, p), D->comm, st));
-    }
-    NCCL_TRY(ncclGroupEnd());
-    return USPMV_OK;
-}
-
-// USPMV_EXCHANGE_HOST: pack -> pinned host buffer -> all-to-all-v over the transport -> tail of x.  The host waits for the
-// pack (and returns with the upload queued on `st`), so the caller may queue independent device work on another stream first.
-int exchange_host(uspmv_dist *D, void *d_x, hipStream_t st) {
-    const size_t vsz = vsize(D);
-    if (int rc = pack(D, d_x, st)) return rc;
-    if (D->n_send) HIP_TRY(hipMemcpyAsync(D->h_send, D->d_send, (size_t)D->n_send * vsz, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<int64_t> so((size_t)D->P + 1), ro((size_t)D->P + 1);
-    for (int p = 0; p <= D->P; ++p) { so[(size_t)p] = D->send_off[(size_t)p] * (int64_t)vsz; ro[(size_t)p] = D->recv_off[(size_t)p] * (int64_t)vsz; }
-    if (int rc = D->tr.alltoallv(D->tr.ctx, D->h_send, so.data(), D->h_recv, ro.data())) return rc;
-    if (D->n_halo) HIP_TRY(hipMemcpyAsync((char *)d_x + (size_t)D->n_local * vsz, D->h_recv, (size_t)D->n_halo * vsz, hipMemcpyHostToDevice, st));
     return USPMV_OK;
 }
 
@@ -387,15 +357,6 @@ int peer_complete(uspmv_dist *D, void *d_X, int b, long ld, int rowwise, hipStre
     return USPMV_OK;
 }
 
-// single vector: the push replaces the pack kernel (no d_send round); -no_pack pushes nothing (the window's stale contents are unpacked),
-// diag_skip_exchange stops after the padding slot's value is kept (the halo tail stays what it was)
-int exchange_peer(uspmv_dist *D, void *d_x, hipStream_t st) {
-    const long n = D->no_pack || D->diag_skip_exchange ? 0 : (long)D->n_send;
-    if (int rc = push(D, d_x, 1, 0, 1, n, pads_on(D) ? D->pad_col : -1, st)) return rc;
-    if (D->diag_skip_exchange) return USPMV_OK;
-    return peer_complete(D, d_x, 1, 0, 1, st);
-}
-
 // close what this rank opened, barrier (no rank frees a window another still has open: the HIP header calls freeing an exported region
 // before the importer's hipIpcCloseMemHandle undefined), free the window.  A peer that is gone fails the barrier on its deadline: the
 // window is freed anyway and the barrier's status returned.
@@ -509,11 +470,141 @@ int peer_setup(uspmv_dist *D, int b) {
     return USPMV_OK;
 }
 
-inline int exchange(uspmv_dist *D, void *d_x, hipStream_t st) {
-    return D->host_exchange ? exchange_host(D, d_x, st) : D->peer_exchange ? exchange_peer(D, d_x, st) : exchange_rccl(D, d_x, st);
+// ---- the exchange of b vectors in the reference's three message patterns (the single-vector step: b = 1, row-wise, bulk)
+//   USPMV_BULKVEC   one message per neighbour carrying all b vectors           (code/classes_structs.hpp:909-924, :971-981)
+//   USPMV_MULTIVEC  one message per neighbour and vector, all posted together  (:893-907, :953-960)
+//   USPMV_SINGLEVEC one exchange per vector, one after the other               (:875-891, :943-951; the loop of code/mpi_funcs.hpp:35-60)
+// Row-wise X ([element][v]): a neighbour's bulk block is exactly the row-wise halo region, so it lands in the tail of X directly.
+// Column-wise X: per-vector messages land in the halo region of their column directly; the bulk block ([v][element] per neighbour)
+// lands in a staging buffer and b small gathers move it.  Row-wise X with per-vector messages would need strided receives: refused.
+// The peer-store exchange needs no plan: its stores carry no messages, so one push serves every pattern.
+
+// Appends the plan of (b, layout, mode) to D->block_plans; on failure nothing of it stays behind
+hipError_t add_block_plan(uspmv_dist *D, int b, int layout, int mode) {
+    uspmv_dist::BlockPlan bp;
+    bp.b = b; bp.layout = layout; bp.mode = mode;
+    const int64_t ld = D->vec_len, ns = D->n_send, nh = D->n_halo;
+    const size_t vsz = vsize(D);
+    hipError_t e = hipSuccess;
+    if (b > 1) {                                           // (b = 1: the wire order of every pattern is uspmv_dist::d_src)
+        std::vector<int32_t> src((size_t)(ns * b));
+        if (layout == USPMV_ROWWISE) {                     // wire = [element][v] (bulk only)
+            for (int64_t i = 0; i < ns; ++i)
+                for (int v = 0; v < b; ++v) src[(size_t)(i * b + v)] = (int32_t)((int64_t)D->h_perm[(size_t)D->h_send_idxs[(size_t)i]] * b + v);
+        } else if (mode == USPMV_BULKVEC) {                // wire = per neighbour [v][element]
+            size_t o = 0;
+            for (int p = 0; p < D->P; ++p)
+                for (int v = 0; v < b; ++v)
+                    for (int64_t i = D->send_off[(size_t)p]; i < D->send_off[(size_t)p + 1]; ++i)
+                        src[o++] = (int32_t)(D->h_perm[(size_t)D->h_send_idxs[(size_t)i]] + (int64_t)v * ld);
+        } else {                                           // wire = [v][element over all neighbours]
+            for (int v = 0; v < b; ++v)
+                for (int64_t i = 0; i < ns; ++i) src[(size_t)(v * ns + i)] = (int32_t)(D->h_perm[(size_t)D->h_send_idxs[(size_t)i]] + (int64_t)v * ld);
+        }
+        e = bp.d_src.upload(src.data(), 4 * src.size());
+    }
+    if (e == hipSuccess) e = bp.d_send.alloc(vsz * std::max<size_t>((size_t)(ns * b), 1));
+    if (e == hipSuccess && D->exchange == USPMV_EXCHANGE_HOST) e = bp.h_send.alloc(vsz * std::max<size_t>((size_t)(ns * b), 1));
+    if (e == hipSuccess && D->exchange == USPMV_EXCHANGE_HOST) e = bp.h_recv.alloc(vsz * std::max<size_t>((size_t)(nh * b), 1));
+    if (e == hipSuccess && layout == USPMV_COLWISE && mode == USPMV_BULKVEC) {
+        e = bp.d_recv.alloc(vsz * std::max<size_t>((size_t)(nh * b), 1));
+        std::vector<int32_t> un((size_t)nh);
+        for (int v = 0; v < b && e == hipSuccess; ++v) {
+            for (int p = 0; p < D->P; ++p) {
+                const int64_t nr = D->recv_counts[(size_t)p], ro = D->recv_off[(size_t)p];
+                for (int64_t k = 0; k < nr; ++k) un[(size_t)(ro + k)] = (int32_t)((int64_t)b * ro + (int64_t)v * nr + k);
+            }
+            bp.d_unpack.emplace_back();
+            e = bp.d_unpack.back().upload(un.data(), 4 * un.size());
+        }
+    }
+    if (e == hipSuccess) D->block_plans.push_back(std::move(bp));
+    return e;
+}
+
+// The plan of (b, layout, mode), built at its first use; the pointer is valid until the next plan is added
+uspmv_dist::BlockPlan *block_plan(uspmv_dist *D, int b, int layout, int mode) {
+    for (auto &bp : D->block_plans)
+        if (bp.b == b && bp.layout == layout && bp.mode == mode) return &bp;
+    if (const hipError_t e = add_block_plan(D, b, layout, mode)) {
+        (void)hipGetLastError();
+        uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dist_spmmv: %s", hipGetErrorString(e));
+        return nullptr;
+    }
+    return &D->block_plans.back();
+}
+
+// The per-step halo exchange of b vectors of X in (layout, mode), queued on `st`.  The single-vector step passes (1, USPMV_ROWWISE,
+// USPMV_BULKVEC) and the padding column whose value the pack keeps (pads_on), block vectors -1.  For every transport, -no_pack 1 packs
+// (pushes) no element and a stale buffer travels (timing only, code/classes_structs.hpp:941); diag_skip_exchange packs (pushes) no
+// element and nothing travels: the halo region keeps what it held.
+int exchange(uspmv_dist *D, void *d_X, int b, int layout, int mode, int pad_col, hipStream_t st) {
+    const long n = D->no_pack || D->diag_skip_exchange ? 0 : (long)D->n_send;   // elements packed (pushed) per vector
+    const size_t vsz = vsize(D);
+    const int64_t ld = D->vec_len, ns = D->n_send, nh = D->n_halo;
+    if (D->exchange == USPMV_EXCHANGE_PEER) {
+        // one push of all b columns into the neighbours' windows, one unpack of this rank's window into the halo region of X
+        const int rowwise = layout == USPMV_ROWWISE;
+        if (int rc = push(D, d_X, b, (long)ld, rowwise, n, pad_col, st)) return rc;
+        return D->diag_skip_exchange ? USPMV_OK : peer_complete(D, d_X, b, (long)ld, rowwise, st);
+    }
+    uspmv_dist::BlockPlan *bp = block_plan(D, b, layout, mode);
+    if (!bp) return USPMV_ERR_ALLOC;
+    if (int rc = pack(D, bp->d_send, d_X, b == 1 ? D->d_src.get() : bp->d_src.get(), n * b, pad_col, st)) return rc;
+    if (D->diag_skip_exchange) return USPMV_OK;
+    char *X = (char *)d_X;
+    const char *S = (const char *)bp->d_send.get();
+    const bool bulk = mode == USPMV_BULKVEC;
+    char *R = layout == USPMV_ROWWISE ? X + (size_t)D->n_local * b * vsz : (char *)bp->d_recv.get();   // where a bulk block lands
+    if (D->exchange == USPMV_EXCHANGE_HOST) {
+        // pack -> pinned host buffer -> all-to-all-v over the transport -> X.  The host waits for the pack (and returns with the upload
+        // queued on `st`), so the caller may queue independent device work on another stream first.  One all-to-all-v of b vectors
+        // (bulk) or one per vector (multivec and singlevec differ in posting order only)
+        char *hs = (char *)bp->h_send.get(), *hr = (char *)bp->h_recv.get();
+        if (ns * b > 0) HIP_TRY(hipMemcpyAsync(hs, S, (size_t)(ns * b) * vsz, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const int w = bulk ? b : 1;                          // vectors per message
+        std::vector<int64_t> so((size_t)D->P + 1), ro((size_t)D->P + 1);
+        for (int p = 0; p <= D->P; ++p) { so[(size_t)p] = D->send_off[(size_t)p] * w * (int64_t)vsz; ro[(size_t)p] = D->recv_off[(size_t)p] * w * (int64_t)vsz; }
+        for (int v = 0; v < b / w; ++v) {
+            if (int rc = D->tr.alltoallv(D->tr.ctx, hs + (size_t)(v * ns) * vsz, so.data(), hr + (size_t)(v * nh) * vsz, ro.data())) return rc;
+            char *dst = bulk ? R : X + (size_t)(v * ld + D->n_local) * vsz;
+            if (nh * w > 0) HIP_TRY(hipMemcpyAsync(dst, hr + (size_t)(v * nh) * vsz, (size_t)(nh * w) * vsz, hipMemcpyHostToDevice, st));
+        }
+    } else if (bulk) {
+        NCCL_TRY(ncclGroupStart());
+        for (int p = 0; p < D->P; ++p) {
+            const int64_t nsp = D->send_off[(size_t)p + 1] - D->send_off[(size_t)p], nr = D->recv_counts[(size_t)p];
+            if (nr) NCCL_TRY(ncclRecv(R + (size_t)(D->recv_off[(size_t)p] * b) * vsz, (size_t)(nr * b), nccl_vt(D), peer(D, p), D->comm, st));
+            if (nsp) NCCL_TRY(ncclSend(S + (size_t)(D->send_off[(size_t)p] * b) * vsz, (size_t)(nsp * b), nccl_vt(D), peer(D, p), D->comm, st));
+        }
+        NCCL_TRY(ncclGroupEnd());
+    } else {
+        // per-vector messages: one group of all b vectors (multivec) or one group per vector (singlevec)
+        const int per_group = mode == USPMV_MULTIVEC ? b : 1;
+        for (int v0 = 0; v0 < b; v0 += per_group) {
+            NCCL_TRY(ncclGroupStart());
+            for (int v = v0; v < v0 + per_group; ++v)
+                for (int p = 0; p < D->P; ++p) {
+                    const int64_t nsp = D->send_off[(size_t)p + 1] - D->send_off[(size_t)p], nr = D->recv_counts[(size_t)p];
+                    if (nr) NCCL_TRY(ncclRecv(X + (size_t)(v * ld + D->n_local + D->recv_off[(size_t)p]) * vsz, (size_t)nr, nccl_vt(D), peer(D, p), D->comm, st));
+                    if (nsp) NCCL_TRY(ncclSend(S + (size_t)(v * ns + D->send_off[(size_t)p]) * vsz, (size_t)nsp, nccl_vt(D), peer(D, p), D->comm, st));
+                }
+            NCCL_TRY(ncclGroupEnd());
+        }
+    }
+    if (bulk && layout == USPMV_COLWISE && nh)               // the staged bulk block -> the halo region of every column
+        for (int v = 0; v < b; ++v)
+            if (int rc = uspmv_apply_permutation_dev(X + (size_t)(v * ld + D->n_local) * vsz, bp->d_recv, bp->d_unpack[(size_t)v], nh, D->dtype, st)) return rc;
+    return USPMV_OK;
+}
+
+// the single-vector step's exchange
+inline int exchange_x(uspmv_dist *D, void *d_x, hipStream_t st) {
+    return exchange(D, d_x, 1, USPMV_ROWWISE, USPMV_BULKVEC, pads_on(D) ? D->pad_col : -1, st);
 }
 // steps that block the host inside the exchange (host-staged, peer-store between real ranks) run eagerly: there is nothing to capture
-inline bool eager_only(const uspmv_dist *D) { return D->host_exchange || D->peer_exchange; }
+inline bool eager_only(const uspmv_dist *D) { return D->exchange != USPMV_EXCHANGE_RCCL; }
 
 int part(uspmv_dist *D, const int32_t *ids, int64_t n, const void *x, void *y, hipStream_t st) {
     if (n == 0) return USPMV_OK;
@@ -545,7 +636,7 @@ int step_fused(uspmv_dist *D, void *d_x, void *d_y, hipStream_t main) {
                                    : uspmv_dev::launch_spmv_tlc_step<float>(D->A, D->d_step, D->sa, 1, (const float *)d_x, (float *)d_y, D->side_stream);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(D->ev_comm, D->side_stream));
-    if ((rc = exchange(D, d_x, main))) return rc;                    // (a failure here leaves the counters out of step: sync_dirty stays set)
+    if ((rc = exchange_x(D, d_x, main))) return rc;                  // (a failure here leaves the counters out of step: sync_dirty stays set)
     hipLaunchKernelGGL(exchange_done_kernel, dim3(1), dim3(1), 0, main, D->d_ss);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamWaitEvent(main, D->ev_comm, 0));                // join: the deferred list is complete
@@ -564,7 +655,7 @@ int step_fused(uspmv_dist *D, void *d_x, void *d_y, hipStream_t main) {
 int step(uspmv_dist *D, void *d_x, void *d_y, hipStream_t main, bool comm_halos) {
     if (D->P == 1 || !comm_halos) return uspmv_spmv(D->A, d_x, d_y, main);
     if (!D->overlap) {
-        if (int rc = exchange(D, d_x, main)) return rc;
+        if (int rc = exchange_x(D, d_x, main)) return rc;
         if (int rc = uspmv_spmv(D->A, d_x, d_y, main)) return rc;
         return step_barrier(D, main);
     }
@@ -575,7 +666,7 @@ int step(uspmv_dist *D, void *d_x, void *d_y, hipStream_t main, bool comm_halos)
     HIP_TRY(hipStreamWaitEvent(D->side_stream, D->ev_main, 0));
     if (int rc = pads ? part(D, D->d_early, D->n_int + D->n_pad, d_x, d_y, D->side_stream) : part(D, D->d_int, D->n_int, d_x, d_y, D->side_stream)) return rc;
     HIP_TRY(hipEventRecord(D->ev_comm, D->side_stream));
-    if (int rc = exchange(D, d_x, main)) return rc;                  // pack kernel + grouped send / recv into the tail of x (host mode: blocks the host)
+    if (int rc = exchange_x(D, d_x, main)) return rc;                // pack kernel + grouped send / recv into the tail of x (host mode: blocks the host)
     if (pads) if (int rc = pad_guard(D, d_x, main)) return rc;
     HIP_TRY(hipStreamWaitEvent(main, D->ev_comm, 0));                // join
     // (pads: the conditional entries are switched off by the guard unless x[pad_col] changed sign or is not finite)
@@ -640,12 +731,6 @@ void uspmv_dist_free(uspmv_dist_t *D) {
     if (!D) return;
     drop_graph(D);
     (void)peer_release(D, true);                                    // collective: close, barrier, free (see peer_release)
-    for (auto &bp : D->block_plans) {
-        if (bp.h_send) (void)hipHostFree(bp.h_send);
-        if (bp.h_recv) (void)hipHostFree(bp.h_recv);
-    }
-    if (D->h_send) (void)hipHostFree(D->h_send);
-    if (D->h_recv) (void)hipHostFree(D->h_recv);
     if (D->ev_main) (void)hipEventDestroy(D->ev_main);
     if (D->ev_comm) (void)hipEventDestroy(D->ev_comm);
     if (D->ev_push) (void)hipEventDestroy(D->ev_push);
@@ -661,16 +746,18 @@ void uspmv_dist_free(uspmv_dist_t *D) {
 static int create_dist(const void *comm_id, int comm_rank, int comm_size, int rank, int P, uspmv_dmat_t *A, const uspmv_halo_t *halo,
                        const int32_t *old_to_new_idx, const int32_t *interior_ids, int64_t n_interior, const int32_t *boundary_ids,
                        int64_t n_boundary, int ids_are_tiles, const uspmv_dist_options_t *opt, uspmv_dist_t **out, bool windows) {
-    const bool host_ex = opt && opt->exchange == USPMV_EXCHANGE_HOST, peer_ex = opt && opt->exchange == USPMV_EXCHANGE_PEER;
-    if (opt && opt->exchange != USPMV_EXCHANGE_RCCL && opt->exchange != USPMV_EXCHANGE_HOST && opt->exchange != USPMV_EXCHANGE_PEER)
-        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: unknown exchange %d", opt->exchange);
+    const int ex = opt ? opt->exchange : USPMV_EXCHANGE_RCCL;
+    if (ex != USPMV_EXCHANGE_RCCL && ex != USPMV_EXCHANGE_HOST && ex != USPMV_EXCHANGE_PEER)
+        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: unknown exchange %d", ex);
     if (!A || !halo || !out || P < 1 || rank < 0 || rank >= P || n_interior < 0 || n_boundary < 0 || (n_interior > 0 && !interior_ids) ||
         (n_boundary > 0 && !boundary_ids))
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: bad argument");
-    if (host_ex) {
+    switch (ex) {
+    case USPMV_EXCHANGE_HOST:
         if (!opt->transport || !opt->transport->alltoallv) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: USPMV_EXCHANGE_HOST needs a transport");
         comm_rank = rank; comm_size = P;
-    } else if (peer_ex) {
+        break;
+    case USPMV_EXCHANGE_PEER:
         // comm_size == P: real ranks, which need a transport (set-up exchanges, per-step barrier); comm_size == 1: loopback, no transport
         if (comm_size < 1 || comm_rank < 0 || comm_rank >= comm_size) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: bad communicator argument");
         if (!(comm_size == P && comm_rank == rank) && !(comm_size == 1 && comm_rank == 0))
@@ -680,7 +767,8 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
                                "(it carries the set-up exchanges and the per-step barrier)");
         if (comm_size == 1 && P > 1 && opt->transport)
             return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: USPMV_EXCHANGE_PEER in loopback takes no transport");
-    } else {
+        break;
+    default:
         if (!comm_id || comm_size < 1 || comm_rank < 0 || comm_rank >= comm_size) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: bad communicator argument");
         if (!(comm_size == P && comm_rank == rank) && !(comm_size == 1 && comm_rank == 0))
             return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: the communicator must have one rank per partition block (comm_size == P) or a single rank (loopback)");
@@ -692,15 +780,15 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     if (int rc = uspmv_dev::check_dmat(A, "uspmv_dist_create")) return rc;
     if (int rc = uspmv_dev::require_device()) return rc;
     auto *D = new uspmv_dist;
-    D->rank = rank; D->P = P; D->comm_rank = comm_rank; D->comm_size = comm_size; D->loopback = !host_ex && comm_size == 1 && P > 1;
-    D->host_exchange = host_ex; D->peer_exchange = peer_ex;
+    D->rank = rank; D->P = P; D->comm_rank = comm_rank; D->comm_size = comm_size; D->loopback = comm_size == 1 && P > 1;   // (host: comm_size == P)
+    D->exchange = ex;
     D->A = A; D->dtype = A->dtype; D->tiles = ids_are_tiles != 0;
     D->n_local = halo->n_local; D->n_halo = halo->n_halo; D->n_int = n_interior; D->n_bnd = n_boundary;
     D->recv_counts = halo->recv_counts;
     auto bail = [&](int code) { uspmv_dist_free(D); return code; };
 #define D_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bail(uspmv::fail(USPMV_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); } while (0)
 #define D_NCCL(call) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) return bail(uspmv::fail(USPMV_ERR_HIP, "%s failed: %s (%s:%d)", #call, ncclGetErrorString(r_), __FILE__, __LINE__)); } while (0)
-    if (!host_ex && !peer_ex) {
+    if (ex == USPMV_EXCHANGE_RCCL) {
         ncclUniqueId id;
         memcpy(&id, comm_id, sizeof id);
         D_NCCL(ncclCommInitRank(&D->comm, comm_size, id, comm_rank));
@@ -708,8 +796,8 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     D_HIP(hipStreamCreateWithFlags(&D->side_stream, hipStreamNonBlocking));
     D_HIP(hipEventCreateWithFlags(&D->ev_main, hipEventDisableTiming));
     D_HIP(hipEventCreateWithFlags(&D->ev_comm, hipEventDisableTiming));
-    if (peer_ex) D_HIP(hipEventCreateWithFlags(&D->ev_push, hipEventDisableTiming));
-    if (peer_ex) D_HIP(hipEventCreateWithFlags(&D->ev_unpack, hipEventDisableTiming));
+    if (ex == USPMV_EXCHANGE_PEER) D_HIP(hipEventCreateWithFlags(&D->ev_push, hipEventDisableTiming));
+    if (ex == USPMV_EXCHANGE_PEER) D_HIP(hipEventCreateWithFlags(&D->ev_unpack, hipEventDisableTiming));
     D_HIP(D->d_scratch.zeros(256));
     // ---- who sends what to whom (collect_comm_info, code/mpi_funcs.hpp:1061-1124) over the set-up transport
     if (opt && opt->transport) D->tr = *opt->transport;
@@ -727,7 +815,6 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     D->h_send_idxs = D->plan->send_idxs;
     D->h_perm.assign(old_to_new_idx, old_to_new_idx + D->n_local);
     // ---- device state of the step
-    const size_t vsz = vsize(D);
     D_HIP(D->d_send_idxs.upload(D->h_send_idxs.data(), 4 * (size_t)D->n_send));
     D_HIP(D->d_perm.upload(old_to_new_idx, 4 * (size_t)D->n_local));
     {
@@ -738,13 +825,10 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     }
     D_HIP(D->d_int.upload(interior_ids, 4 * (size_t)n_interior));
     D_HIP(D->d_bnd.upload(boundary_ids, 4 * (size_t)n_boundary));
-    if (!peer_ex) D_HIP(D->d_send.alloc(vsz * (size_t)std::max<int64_t>(D->n_send, 1)));   // (peer stores: the push replaces the pack)
-    if (host_ex) {
-        D_HIP(hipHostMalloc(&D->h_send, vsz * (size_t)std::max<int64_t>(D->n_send, 1), hipHostMallocDefault));
-        D_HIP(hipHostMalloc(&D->h_recv, vsz * (size_t)std::max<int64_t>(D->n_halo, 1), hipHostMallocDefault));
-    }
     D->n_rows_padded = A->n_chunks * A->C;
     D->vec_len = D->n_local + std::max(D->n_rows_padded - D->n_local, D->n_halo);       // padded_vec_size (code/main.cpp:1406-1412)
+    // the single-vector step's exchange plan, here so that no step allocates (a captured one must not); peer stores need none
+    if (ex != USPMV_EXCHANGE_PEER) D_HIP(add_block_plan(D, 1, USPMV_ROWWISE, USPMV_BULKVEC));
     if (P > 1 && !A->alt && A->n_chunks > 0) {
         // the same split for block vectors: per chunk, does it (or its tile) touch a halo column
         std::vector<unsigned char> flag((size_t)A->n_chunks, 0);
@@ -761,7 +845,7 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     }
     // the collective window set-up last, after every check that could fail on one rank alone (that rank's free would then enter a barrier
     // the others never join); uspmv_dist_create_from_coo_ex runs it after its own rank-local steps instead
-    if (peer_ex && P > 1 && windows)
+    if (ex == USPMV_EXCHANGE_PEER && P > 1 && windows)
         if (int rc = peer_setup(D, 1)) return bail(rc);
 #undef D_HIP
 #undef D_NCCL
@@ -875,7 +959,7 @@ int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_s
         if ((rc = sync_reset(D))) { uspmv_dist_free(D); cleanup(); return rc; }
     }
     // (the collective window set-up after every step above that could fail on this rank alone)
-    if (D->peer_exchange && P > 1)
+    if (D->exchange == USPMV_EXCHANGE_PEER && P > 1)
         if ((rc = peer_setup(D, 1))) { uspmv_dist_free(D); cleanup(); return rc; }
     D->owns_setup = true; D->scs = scs; D->halo = halo;
     *out = D;
@@ -940,7 +1024,7 @@ int uspmv_dist_comm_count(const uspmv_dist_t *D, int *n_ranks) {
 
 int uspmv_dist_exchange(const uspmv_dist_t *D, int *exchange) {
     if (!D || !exchange) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_exchange: NULL argument");
-    *exchange = D->host_exchange ? USPMV_EXCHANGE_HOST : D->peer_exchange ? USPMV_EXCHANGE_PEER : USPMV_EXCHANGE_RCCL;
+    *exchange = D->exchange;
     return USPMV_OK;
 }
 
@@ -1176,144 +1260,7 @@ int uspmv_dist_check(uspmv_dist_t *D, const uspmv_coo_t *local, const int32_t *w
     return USPMV_OK;
 }
 
-}  // extern "C"
-
-// ---- block vectors (SpMMV): the halo exchange of b vectors in the reference's three message patterns
-//   USPMV_BULKVEC   one message per neighbour carrying all b vectors           (code/classes_structs.hpp:909-924, :971-981)
-//   USPMV_MULTIVEC  one message per neighbour and vector, all posted together  (:893-907, :953-960)
-//   USPMV_SINGLEVEC one exchange per vector, one after the other               (:875-891, :943-951; the loop of code/mpi_funcs.hpp:35-60)
-// Row-wise X ([element][v]): a neighbour's bulk block is exactly the row-wise halo region, so it lands in the tail of X directly.
-// Column-wise X: per-vector messages land in the halo region of their column directly; the bulk block ([v][element] per neighbour)
-// lands in a staging buffer and b small gathers move it.  Row-wise X with per-vector messages would need strided receives: refused.
-namespace {
-
-uspmv_dist::BlockPlan *block_plan(uspmv_dist *D, int b, int layout, int mode) {
-    for (auto &bp : D->block_plans)
-        if (bp.b == b && bp.layout == layout && bp.mode == mode) return &bp;
-    uspmv_dist::BlockPlan bp;
-    bp.b = b; bp.layout = layout; bp.mode = mode;
-    const int64_t ld = D->vec_len, ns = D->n_send, nh = D->n_halo;
-    const size_t vsz = D->dtype == USPMV_F64 ? 8 : 4;
-    if ((int64_t)b * std::max(ld, (int64_t)1) > INT32_MAX) { uspmv::fail(USPMV_ERR_OVERFLOW, "uspmv_dist_spmmv: b * padded_vec_size exceeds int32"); return nullptr; }
-    std::vector<int32_t> src((size_t)(ns * b));
-    if (layout == USPMV_ROWWISE) {                         // wire = [element][v] (bulk only)
-        for (int64_t i = 0; i < ns; ++i)
-            for (int v = 0; v < b; ++v) src[(size_t)(i * b + v)] = (int32_t)((int64_t)D->h_perm[(size_t)D->h_send_idxs[(size_t)i]] * b + v);
-    } else if (mode == USPMV_BULKVEC) {                    // wire = per neighbour [v][element]
-        size_t o = 0;
-        for (int p = 0; p < D->P; ++p)
-            for (int v = 0; v < b; ++v)
-                for (int64_t i = D->send_off[(size_t)p]; i < D->send_off[(size_t)p + 1]; ++i)
-                    src[o++] = (int32_t)(D->h_perm[(size_t)D->h_send_idxs[(size_t)i]] + (int64_t)v * ld);
-    } else {                                               // wire = [v][element over all neighbours]
-        for (int v = 0; v < b; ++v)
-            for (int64_t i = 0; i < ns; ++i) src[(size_t)(v * ns + i)] = (int32_t)(D->h_perm[(size_t)D->h_send_idxs[(size_t)i]] + (int64_t)v * ld);
-    }
-    hipError_t e = bp.d_src.upload(src.data(), 4 * src.size());
-    if (e == hipSuccess) e = bp.d_send.alloc(vsz * std::max<size_t>((size_t)(ns * b), 1));
-    if (e == hipSuccess && layout == USPMV_COLWISE && mode == USPMV_BULKVEC) {
-        e = bp.d_recv.alloc(vsz * std::max<size_t>((size_t)(nh * b), 1));
-        std::vector<int32_t> un((size_t)nh);
-        for (int v = 0; v < b && e == hipSuccess; ++v) {
-            for (int p = 0; p < D->P; ++p) {
-                const int64_t nr = D->recv_counts[(size_t)p], ro = D->recv_off[(size_t)p];
-                for (int64_t k = 0; k < nr; ++k) un[(size_t)(ro + k)] = (int32_t)((int64_t)b * ro + (int64_t)v * nr + k);
-            }
-            bp.d_unpack.emplace_back();
-            e = bp.d_unpack.back().upload(un.data(), 4 * un.size());
-        }
-    }
-    if (e != hipSuccess) {   // nothing of a half-built plan stays behind (every failed call would leak it again)
-        (void)hipGetLastError();
-        uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dist_spmmv: %s", hipGetErrorString(e));
-        return nullptr;
-    }
-    D->block_plans.push_back(std::move(bp));
-    return &D->block_plans.back();
-}
-
-int exchange_block(uspmv_dist *D, void *d_X, int b, int layout, int mode, hipStream_t st) {
-    if (D->peer_exchange) {
-        // USPMV_EXCHANGE_PEER: one push of all b columns into windows sized for n_halo x b (grown collectively -- the call is collective --
-        // the first time a wider block appears), one unpack into the halo region of X.  Stores carry no messages, so the three patterns
-        // share this one wire format; the halo region receives the same values as with the other exchanges.
-        if ((int64_t)b * std::max(D->vec_len, (int64_t)1) > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "uspmv_dist_spmmv: b * padded_vec_size exceeds int32");
-        if (b > D->win_b)
-            if (int rc = peer_setup(D, b)) return rc;
-        const int rowwise = layout == USPMV_ROWWISE;
-        if (int rc = push(D, d_X, b, (long)D->vec_len, rowwise, (long)D->n_send, -1, st)) return rc;
-        return peer_complete(D, d_X, b, (long)D->vec_len, rowwise, st);
-    }
-    uspmv_dist::BlockPlan *bp = block_plan(D, b, layout, mode);
-    if (!bp) return USPMV_ERR_ALLOC;
-    const size_t vsz = D->dtype == USPMV_F64 ? 8 : 4;
-    const int64_t ld = D->vec_len, ns = D->n_send;
-    if (ns * b > 0)
-        if (int rc = uspmv_apply_permutation_dev(bp->d_send, d_X, bp->d_src, ns * b, D->dtype, st)) return rc;
-    char *X = (char *)d_X;
-    const char *S = (const char *)bp->d_send;
-    if (D->host_exchange) {
-        // USPMV_EXCHANGE_HOST: the same wire formats staged through pinned host memory and the transport's all-to-all-v, so that real
-        // ranks sharing one GPU exercise the block plans on unequal blocks and asymmetric lists (tests); the host waits for the pack
-        const int64_t nh = D->n_halo;
-        if (!bp->h_send) {
-            HIP_TRY(hipHostMalloc(&bp->h_send, vsz * (size_t)std::max<int64_t>(ns * b, 1), hipHostMallocDefault));
-            HIP_TRY(hipHostMalloc(&bp->h_recv, vsz * (size_t)std::max<int64_t>(nh * b, 1), hipHostMallocDefault));
-        }
-        if (ns * b > 0) HIP_TRY(hipMemcpyAsync(bp->h_send, bp->d_send, (size_t)(ns * b) * vsz, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        std::vector<int64_t> so((size_t)D->P + 1), ro((size_t)D->P + 1);
-        if (mode == USPMV_BULKVEC) {                         // one message per neighbour: b * count elements
-            for (int p = 0; p <= D->P; ++p) { so[(size_t)p] = D->send_off[(size_t)p] * b * (int64_t)vsz; ro[(size_t)p] = D->recv_off[(size_t)p] * b * (int64_t)vsz; }
-            if (int rc = D->tr.alltoallv(D->tr.ctx, bp->h_send, so.data(), bp->h_recv, ro.data())) return rc;
-            char *R = layout == USPMV_ROWWISE ? X + (size_t)D->n_local * b * vsz : (char *)bp->d_recv;
-            if (nh * b > 0) HIP_TRY(hipMemcpyAsync(R, bp->h_recv, (size_t)(nh * b) * vsz, hipMemcpyHostToDevice, st));
-            if (layout == USPMV_COLWISE && nh)
-                for (int v = 0; v < b; ++v)
-                    if (int rc = uspmv_apply_permutation_dev(X + (size_t)(v * ld + D->n_local) * vsz, bp->d_recv, bp->d_unpack[(size_t)v], nh, D->dtype, st)) return rc;
-            return USPMV_OK;
-        }
-        for (int p = 0; p <= D->P; ++p) { so[(size_t)p] = D->send_off[(size_t)p] * (int64_t)vsz; ro[(size_t)p] = D->recv_off[(size_t)p] * (int64_t)vsz; }
-        for (int v = 0; v < b; ++v) {                        // per-vector messages (multivec and singlevec differ in posting order only)
-            if (int rc = D->tr.alltoallv(D->tr.ctx, (const char *)bp->h_send + (size_t)(v * ns) * vsz, so.data(), (char *)bp->h_recv + (size_t)(v * nh) * vsz, ro.data())) return rc;
-            if (nh) HIP_TRY(hipMemcpyAsync(X + (size_t)(v * ld + D->n_local) * vsz, (const char *)bp->h_recv + (size_t)(v * nh) * vsz, (size_t)nh * vsz, hipMemcpyHostToDevice, st));
-        }
-        return USPMV_OK;
-    }
-    auto group = [&](int v0, int v1) -> int {                // per-vector messages of vectors [v0, v1)
-        NCCL_TRY(ncclGroupStart());
-        for (int v = v0; v < v1; ++v)
-            for (int p = 0; p < D->P; ++p) {
-                const int64_t nsp = D->send_off[(size_t)p + 1] - D->send_off[(size_t)p], nr = D->recv_counts[(size_t)p];
-                if (nr) NCCL_TRY(ncclRecv(X + (size_t)(v * ld + D->n_local + D->recv_off[(size_t)p]) * vsz, (size_t)nr, nccl_vt(D), peer(D, p), D->comm, st));
-                if (nsp) NCCL_TRY(ncclSend(S + (size_t)(v * ns + D->send_off[(size_t)p]) * vsz, (size_t)nsp, nccl_vt(D), peer(D, p), D->comm, st));
-            }
-        NCCL_TRY(ncclGroupEnd());
-        return USPMV_OK;
-    };
-    if (mode == USPMV_SINGLEVEC) {
-        for (int v = 0; v < b; ++v) if (int rc = group(v, v + 1)) return rc;
-        return USPMV_OK;
-    }
-    if (mode == USPMV_MULTIVEC) return group(0, b);
-    // bulk: one message per neighbour
-    char *R = layout == USPMV_ROWWISE ? X + (size_t)D->n_local * b * vsz : (char *)bp->d_recv;
-    NCCL_TRY(ncclGroupStart());
-    for (int p = 0; p < D->P; ++p) {
-        const int64_t nsp = D->send_off[(size_t)p + 1] - D->send_off[(size_t)p], nr = D->recv_counts[(size_t)p];
-        if (nr) NCCL_TRY(ncclRecv(R + (size_t)(D->recv_off[(size_t)p] * b) * vsz, (size_t)(nr * b), nccl_vt(D), peer(D, p), D->comm, st));
-        if (nsp) NCCL_TRY(ncclSend(S + (size_t)(D->send_off[(size_t)p] * b) * vsz, (size_t)(nsp * b), nccl_vt(D), peer(D, p), D->comm, st));
-    }
-    NCCL_TRY(ncclGroupEnd());
-    if (layout == USPMV_COLWISE && D->n_halo)
-        for (int v = 0; v < b; ++v)
-            if (int rc = uspmv_apply_permutation_dev(X + (size_t)(v * ld + D->n_local) * vsz, bp->d_recv, bp->d_unpack[(size_t)v], D->n_halo, D->dtype, st)) return rc;
-    return USPMV_OK;
-}
-
-}  // namespace
-
-extern "C" int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
+int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
     if (!D || !d_X || !d_Y || b < 1) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: bad argument");
     if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown layout %d", layout);
     if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown mode %d", mode);
@@ -1321,11 +1268,19 @@ extern "C" int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, in
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: row-wise block vectors travel in one message per neighbour (bulkvec) only");
     hipStream_t main = (hipStream_t)stream;
     if (!(D->P > 1 && comm_halos)) return uspmv_spmmv(D->A, d_X, d_Y, b, D->vec_len, layout, stream);
+    // the exchange of block vectors: their gather lists index b * padded_vec_size elements in int32; the peer-store windows grow (collectively,
+    // as the call is) the first time a wider block appears -- never in the single-vector step, which refuses once a failed growth lost them
+    auto grow_and_exchange = [&]() -> int {
+        if ((int64_t)b * std::max(D->vec_len, (int64_t)1) > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "uspmv_dist_spmmv: b * padded_vec_size exceeds int32");
+        if (D->exchange == USPMV_EXCHANGE_PEER && b > D->win_b)
+            if (int rc = peer_setup(D, b)) return rc;
+        return exchange(D, d_X, b, layout, mode, -1, main);
+    };
     // (a handle whose only block plan is the one-list-per-tile one runs that plan's kernels on the whole matrix: they are ahead of the
     //  gather kernels by more than the exchange costs)
     if (!(D->overlap && D->parts && !D->A->alt) || (D->A->bt.on && !(D->A->pb.on && D->A->part_len[1][0]))) {
         // exchange first, then the whole matrix (the reference's order, code/mpi_funcs.hpp:25-60)
-        if (int rc = exchange_block(D, d_X, b, layout, mode, main)) return rc;
+        if (int rc = grow_and_exchange()) return rc;
         if (int rc = uspmv_spmmv(D->A, d_X, d_Y, b, D->vec_len, layout, stream)) return rc;
         ++D->spmmv_one_part;
         return step_barrier(D, main);
@@ -1344,7 +1299,7 @@ extern "C" int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, in
     if (D->diag_spmmv_part != 2)
         if (int rc = uspmv_spmmv(A, d_X, d_Y, b, D->vec_len, layout, D->side_stream)) return rc;
     HIP_TRY(hipEventRecord(D->ev_comm, D->side_stream));
-    if (int rc = exchange_block(D, d_X, b, layout, mode, main)) return rc;
+    if (int rc = grow_and_exchange()) return rc;
     HIP_TRY(hipStreamWaitEvent(main, D->ev_comm, 0));
     A->part = 2;
     if (D->diag_spmmv_part != 1)
@@ -1352,3 +1307,5 @@ extern "C" int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, in
     ++D->spmmv_two_part;
     return step_barrier(D, main);
 }
+
+}  // extern "C"

@@ -41,7 +41,10 @@ typedef enum {
     USPMV_ERR_COMM = 8         /* a peer rank failed, never arrived or disagrees (host communicator / transport) */
 } uspmv_status;
 
-typedef enum { USPMV_F64 = 0, USPMV_F32 = 1 } uspmv_dtype;            /* -dp / -sp              */
+typedef enum { USPMV_F64 = 0, USPMV_F32 = 1, USPMV_F16 = 2 } uspmv_dtype;   /* -dp / -sp / hp part      */
+/* USPMV_F16: IEEE binary16 values (uint16_t bits), the hp part of an adaptive-precision split (uspmv_partition_precisions_hp).
+ * Accepted by uspmv_convert_to_scs, uspmv_dmat_upload and uspmv_dmat_wrap; a one-precision SpMV / SpMMV or plan of an F16 handle
+ * returns USPMV_ERR_UNSUPPORTED (the reference's -hp accumulates in _Float16); such a handle only runs inside uspmv_spmv_ap_hp. */
 typedef enum { USPMV_COLWISE = 0, USPMV_ROWWISE = 1 } uspmv_layout;   /* Makefile:26-31         */
 typedef enum { USPMV_SEG_ROWS = 0, USPMV_SEG_NNZ = 1 } uspmv_seg;     /* -seg_rows / -seg_nnz   */
 
@@ -128,6 +131,16 @@ int uspmv_apply_permutation(void *out, const void *in, const int32_t *perm, int6
 /* partition_precisions, ap[dp_sp] non-equilibrated branch (code/utilities.hpp:2899-2911):
  * |v| >= threshold_1 -> dp, else sp (values rounded to float), COO order kept. */
 int uspmv_partition_precisions(const uspmv_coo_t *m, double threshold_1, uspmv_coo_t **dp, uspmv_coo_t **sp);
+/* partition_precisions with an fp16 part, ap[dp_hp] / ap[sp_hp] / ap[dp_sp_hp] (code/interface.hpp:691-987, non-equilibrated branch), COO
+ * order kept, every part's values stored as doubles holding the rounded value:
+ *   USPMV_AP_DP_HP     |v| >= t1 -> hi (double), |v| < t1 -> hp;                      NaN: USPMV_ERR_INVALID
+ *   USPMV_AP_SP_HP     |v| >= t1 -> hi ((float)v), |v| < t1 -> hp;                    NaN: USPMV_ERR_INVALID
+ *   USPMV_AP_DP_SP_HP  |v| >= t1 -> hi (double), else t2 <= |v| <= t1 -> mid ((float)v), else -> hp (NaN included)
+ * hp values are rounded once to binary16, to nearest even (subnormals kept, overflow to +-inf, bit-equal to numpy's float64 -> float16).
+ * *mid is set to NULL for the two-part kinds (mid may then be NULL). */
+enum { USPMV_AP_DP_HP = 0, USPMV_AP_SP_HP = 1, USPMV_AP_DP_SP_HP = 2 };
+int uspmv_partition_precisions_hp(const uspmv_coo_t *m, int kind, double threshold_1, double threshold_2, uspmv_coo_t **hi,
+                                  uspmv_coo_t **mid, uspmv_coo_t **hp);
 
 /* ------------------------------------------------------------------ L3: device kernels    */
 int uspmv_device_count(int *count);
@@ -189,6 +202,11 @@ int uspmv_dmat_optimize(uspmv_dmat_t *m, const uspmv_scs_t *s, int max_lines, in
  * indices for both structs; uspmv_spmv_ap then streams 10 + 6 instead of 12 + 8 bytes per non-zero. */
 int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t *s_dp, const uspmv_scs_t *s_sp,
                            int max_lines, int64_t *n_tiles, int64_t *n_staged);
+/* Same for the two or three parts of an ap split with an fp16 part (hi: F64 or F32, mid: F32 or NULL, hp: F16; identical row layout):
+ * one line list per tile over every part's columns, 16-bit local indices per part.  No column-window sweep: when the line plan stages
+ * fewer than half of the tiles the handles stay planless and uspmv_spmv_ap_hp runs its lane-per-row kernel. */
+int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
+                              const uspmv_scs_t *s_hp, int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* SpMMV counterpart of uspmv_dmat_optimize (no reference counterpart): plan for block vectors of
  * block_vec_size columns -- per 64-row tile the X rows it touches are staged in LDS once and the
  * kernel reads them with 2-byte local indices.  Used by uspmv_spmmv for b*sizeof(VT) in {16,32,64,128}
@@ -256,6 +274,8 @@ int uspmv_dmat_optimize_block_device(uspmv_dmat_t *m, int block_vec_size, int64_
 int uspmv_dmat_optimize_device(uspmv_dmat_t *m, int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* The shared plan of an ap[dp_sp] pair (uspmv_dmat_optimize_ap) built on the device from the two handles' own arrays. */
 int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_lines, int64_t *n_tiles, int64_t *n_staged);
+/* The plan of uspmv_dmat_optimize_ap_hp built on the device from the handles' own arrays (equal to the host planner's array for array). */
+int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* host copies of a handle's plan (tests): meta = {n_tiles, n_lines_total, n_col16, max_lines_used}; call with NULL
  * arrays first to size them */
 int uspmv_dmat_plan_download(const uspmv_dmat_t *m, int64_t meta[4], int32_t *tile_line_ptr, int32_t *tile_lines,
@@ -307,6 +327,15 @@ int uspmv_spmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const double *
  * to the double accumulator. */
 int uspmv_spmv_ap_generic(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const double *d_x, const float *d_x_sp,
                           double *d_y, void *stream);
+/* Adaptive precision with an fp16 part (the reference's uspmv_scs_apdphp_cpu / _apsphp_cpu / _apdpsphp_cpu, code/interface.hpp:1512-1740;
+ * its GPU path stops at "not yet implemented", code/classes_structs.hpp:553-600).  hi F64 or F32, mid F32 or NULL (hi F64 then), hp F16,
+ * all sharing C and n_chunks.  One set of numerics for every C:
+ *   ap[dp_hp]     (hi F64, no mid): x, y double; a dp and an hp chain in double (hp widened exactly), each an FMA chain in slot order;
+ *                 y = dp + hp
+ *   ap[dp_sp_hp]  (hi F64, mid F32): three such chains; y = (dp + sp) + hp
+ *   ap[sp_hp]     (hi F32, no mid): x, y float; every product sp_v * x and (float)hp_v * x rounded to float, then added to a double
+ *                 accumulator per part; y = (float)(sp + hp) */
+int uspmv_spmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, void *d_y, void *stream);
 
 /* Raw-array forms with the argument lists of the library kernels of code/interface.hpp
  * (uspmv_scs_gpu :1766-1793, uspmv_scs_c_gpu :1835-1867, uspmv_csr_gpu :1741-1760). */

@@ -112,11 +112,49 @@ inline int plan_kind(const void *chunk_ptrs) {
     return -1;
 }
 
+#ifdef HAVE_HALF_MATH
+namespace detail {
+
+// the parts of an ap split with an fp16 part (hi, optional mid, hp), wrapped and planned on the device once per set of arrays
+struct EntryHp {
+    const void *key[6];                   // hi chunk_ptrs / values, mid chunk_ptrs / values (nullptr without mid), hp chunk_ptrs / values
+    uspmv_dmat_t *A[3];                   // hi, mid (nullptr), hp
+};
+inline std::vector<EntryHp> &table_hp() { static std::vector<EntryHp> t; return t; }
+
+inline EntryHp parts(const ST *hC, const ST *hn, const void *hcp, const void *hcl, const void *hci, const void *hva, int hdt,
+                     const ST *mC, const ST *mn, const void *mcp, const void *mcl, const void *mci, const void *mva,
+                     const ST *qC, const ST *qn, const void *qcp, const void *qcl, const void *qci, const void *qva) {
+    std::lock_guard<std::mutex> g(lock());
+    const void *key[6] = {hcp, hva, mcp, mva, qcp, qva};
+    for (const EntryHp &e : table_hp()) {
+        bool same = true;
+        for (int k = 0; k < 6; ++k) same = same && e.key[k] == key[k];
+        if (same) return e;
+    }
+    EntryHp e{{hcp, hva, mcp, mva, qcp, qva}, {nullptr, nullptr, nullptr}};
+    ST c = 0;
+    e.A[0] = wrap(hC, hn, hcp, hcl, hci, hva, hdt, &c);
+    if (mcp) e.A[1] = wrap(mC, mn, mcp, mcl, mci, mva, USPMV_F32, &c);
+    e.A[2] = wrap(qC, qn, qcp, qcl, qci, qva, USPMV_F16, &c);
+    ck(uspmv_dmat_optimize_device_ap_hp(e.A[0], e.A[1], e.A[2], 0, nullptr, nullptr), "uspmv_dmat_optimize_device_ap_hp");
+    table_hp().push_back(e);
+    return table_hp().back();
+}
+
+}  // namespace detail
+#endif  // HAVE_HALF_MATH
+
 // forget (and free) every cached handle -- before the arrays behind them are freed or rewritten
 inline void release() {
     std::lock_guard<std::mutex> g(detail::lock());
     for (detail::Entry &e : detail::table()) { uspmv_dmat_free(e.A); uspmv_dmat_free(e.A2); }
     detail::table().clear();
+#ifdef HAVE_HALF_MATH
+    for (detail::EntryHp &e : detail::table_hp())
+        for (uspmv_dmat_t *A : e.A) uspmv_dmat_free(A);
+    detail::table_hp().clear();
+#endif
 }
 
 // OnePrecFuncPtr (code/classes_structs.hpp:283-299); replaces spmv_gpu_scs_adv_launcher / spmv_gpu_scs_launcher and the
@@ -180,6 +218,58 @@ void spmv_hip_ap_scs_launcher(bool /*warmup_flag*/, const ST *dp_C, const ST *dp
     if (adv) detail::ck(uspmv_spmv_ap(e.A, e.A2, dp_x, dp_y, nullptr), "uspmv_spmv_ap");
     else detail::ck(uspmv_spmv_ap_generic(e.A, e.A2, dp_x, sp_x, dp_y, nullptr), "uspmv_spmv_ap_generic");
 }
+
+#ifdef HAVE_HALF_MATH
+// MultiPrecFuncPtr with HAVE_HALF_MATH (code/classes_structs.hpp:301-333, hp arguments :319-328); fills the launcher slots the
+// reference's GPU path leaves at "not yet implemented" (code/classes_structs.hpp:553-600) with uspmv_spmv_ap_hp, whose numerics are
+// the same for every C.  The parts a kind does not use are ignored, as are hp_x / hp_y (like sp_y): the products run against the
+// double x (ap[dp_hp], ap[dp_sp_hp]: dp_x -> dp_y) or the float x (ap[sp_hp]: sp_x -> sp_y).
+//     multi_prec_kernel_func_ptr = uspmv_launchers::spmv_hip_ap_dp_hp_scs_launcher<IT>;      // ap[dp_hp]
+//     multi_prec_kernel_func_ptr = uspmv_launchers::spmv_hip_ap_sp_hp_scs_launcher<IT>;      // ap[sp_hp]
+//     multi_prec_kernel_func_ptr = uspmv_launchers::spmv_hip_ap_dp_sp_hp_scs_launcher<IT>;   // ap[dp_sp_hp]
+template <typename IT>
+void spmv_hip_ap_dp_hp_scs_launcher(bool /*warmup_flag*/, const ST *dp_C, const ST *dp_n_chunks, const IT *dp_chunk_ptrs, const IT *dp_chunk_lengths,
+                                    const IT *dp_col_idxs, const double *dp_values, double *dp_x, double *dp_y, const ST * /*sp_C*/,
+                                    const ST * /*sp_n_chunks*/, const IT * /*sp_chunk_ptrs*/, const IT * /*sp_chunk_lengths*/, const IT * /*sp_col_idxs*/,
+                                    const float * /*sp_values*/, float * /*sp_x*/, float * /*sp_y*/, const ST *hp_C, const ST *hp_n_chunks,
+                                    const IT *hp_chunk_ptrs, const IT *hp_chunk_lengths, const IT *hp_col_idxs, const _Float16 *hp_values,
+                                    _Float16 * /*hp_x*/, _Float16 * /*hp_y*/, const ST /*n_thread_blocks*/, const int * /*my_rank*/) {
+    static_assert(sizeof(IT) == 4, "IT = int");
+    const detail::EntryHp e = detail::parts(dp_C, dp_n_chunks, dp_chunk_ptrs, dp_chunk_lengths, dp_col_idxs, dp_values, USPMV_F64,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                            hp_C, hp_n_chunks, hp_chunk_ptrs, hp_chunk_lengths, hp_col_idxs, hp_values);
+    detail::ck(uspmv_spmv_ap_hp(e.A[0], nullptr, e.A[2], dp_x, dp_y, nullptr), "uspmv_spmv_ap_hp");
+}
+
+template <typename IT>
+void spmv_hip_ap_sp_hp_scs_launcher(bool /*warmup_flag*/, const ST * /*dp_C*/, const ST * /*dp_n_chunks*/, const IT * /*dp_chunk_ptrs*/,
+                                    const IT * /*dp_chunk_lengths*/, const IT * /*dp_col_idxs*/, const double * /*dp_values*/, double * /*dp_x*/,
+                                    double * /*dp_y*/, const ST *sp_C, const ST *sp_n_chunks, const IT *sp_chunk_ptrs, const IT *sp_chunk_lengths,
+                                    const IT *sp_col_idxs, const float *sp_values, float *sp_x, float *sp_y, const ST *hp_C, const ST *hp_n_chunks,
+                                    const IT *hp_chunk_ptrs, const IT *hp_chunk_lengths, const IT *hp_col_idxs, const _Float16 *hp_values,
+                                    _Float16 * /*hp_x*/, _Float16 * /*hp_y*/, const ST /*n_thread_blocks*/, const int * /*my_rank*/) {
+    static_assert(sizeof(IT) == 4, "IT = int");
+    const detail::EntryHp e = detail::parts(sp_C, sp_n_chunks, sp_chunk_ptrs, sp_chunk_lengths, sp_col_idxs, sp_values, USPMV_F32,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                            hp_C, hp_n_chunks, hp_chunk_ptrs, hp_chunk_lengths, hp_col_idxs, hp_values);
+    detail::ck(uspmv_spmv_ap_hp(e.A[0], nullptr, e.A[2], sp_x, sp_y, nullptr), "uspmv_spmv_ap_hp");
+}
+
+template <typename IT>
+void spmv_hip_ap_dp_sp_hp_scs_launcher(bool /*warmup_flag*/, const ST *dp_C, const ST *dp_n_chunks, const IT *dp_chunk_ptrs,
+                                       const IT *dp_chunk_lengths, const IT *dp_col_idxs, const double *dp_values, double *dp_x, double *dp_y,
+                                       const ST *sp_C, const ST *sp_n_chunks, const IT *sp_chunk_ptrs, const IT *sp_chunk_lengths,
+                                       const IT *sp_col_idxs, const float *sp_values, float * /*sp_x*/, float * /*sp_y*/, const ST *hp_C,
+                                       const ST *hp_n_chunks, const IT *hp_chunk_ptrs, const IT *hp_chunk_lengths, const IT *hp_col_idxs,
+                                       const _Float16 *hp_values, _Float16 * /*hp_x*/, _Float16 * /*hp_y*/, const ST /*n_thread_blocks*/,
+                                       const int * /*my_rank*/) {
+    static_assert(sizeof(IT) == 4, "IT = int");
+    const detail::EntryHp e = detail::parts(dp_C, dp_n_chunks, dp_chunk_ptrs, dp_chunk_lengths, dp_col_idxs, dp_values, USPMV_F64,
+                                            sp_C, sp_n_chunks, sp_chunk_ptrs, sp_chunk_lengths, sp_col_idxs, sp_values,
+                                            hp_C, hp_n_chunks, hp_chunk_ptrs, hp_chunk_lengths, hp_col_idxs, hp_values);
+    detail::ck(uspmv_spmv_ap_hp(e.A[0], e.A[1], e.A[2], dp_x, dp_y, nullptr), "uspmv_spmv_ap_hp");
+}
+#endif  // HAVE_HALF_MATH
 
 }  // namespace uspmv_launchers
 #endif  // USPMV_LAUNCHERS_HPP

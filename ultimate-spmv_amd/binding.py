@@ -14,7 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-F64, F32 = 0, 1
+F64, F32, F16 = 0, 1, 2
+AP_DP_HP, AP_SP_HP, AP_DP_SP_HP = 0, 1, 2     # kinds of uspmv_partition_precisions_hp
 COLWISE, ROWWISE = 0, 1
 SEG_ROWS, SEG_NNZ = 0, 1
 
@@ -71,6 +72,10 @@ _SIGS = {
     "uspmv_scs_free": (None, [_vp]),
     "uspmv_apply_permutation": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int]),
     "uspmv_partition_precisions": (C.c_int, [_vp, C.c_double, C.POINTER(_vp), C.POINTER(_vp)]),
+    "uspmv_partition_precisions_hp": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "uspmv_dmat_optimize_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
+    "uspmv_dmat_optimize_device_ap_hp": (C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
+    "uspmv_spmv_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "uspmv_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "uspmv_set_device": (C.c_int, [C.c_int]),
     "uspmv_stream_synchronize": (C.c_int, [_vp]),
@@ -356,7 +361,7 @@ class Scs:
 
     @property
     def np_dtype(self):
-        return np.float64 if self.dtype == F64 else np.float32
+        return {F64: np.float64, F32: np.float32, F16: np.float16}[self.dtype]
 
     def arrays(self):
         """dict of numpy views borrowed from the library (valid while self lives)."""
@@ -364,12 +369,13 @@ class Scs:
         va = _vp()
         _ck(lib().uspmv_scs_arrays(self.h, C.byref(cp), C.byref(cl), C.byref(ci), C.byref(va), C.byref(o2n),
                                    C.byref(n2o)))
-        vp = C.cast(va, C.POINTER(C.c_double if self.dtype == F64 else C.c_float))
+        vp = C.cast(va, C.POINTER({F64: C.c_double, F32: C.c_float, F16: C.c_uint16}[self.dtype]))
         full = bool(ci) or self.n_elements == 0        # layout-only structs (convert_to_scs_device) carry no host entries
         return dict(chunk_ptrs=_view(cp, self.n_chunks + 1, np.int32, self),
                     chunk_lengths=_view(cl, self.n_chunks, np.int32, self),
                     col_idxs=_view(ci, self.n_elements, np.int32, self) if full else None,
-                    values=_view(vp, self.n_elements, self.np_dtype, self) if full else None,
+                    values=(_view(vp, self.n_elements, np.uint16, self).view(np.float16) if self.dtype == F16
+                            else _view(vp, self.n_elements, self.np_dtype, self)) if full else None,
                     old_to_new_idx=_view(o2n, self.n_rows, np.int32, self),
                     new_to_old_idx=_view(n2o, self.n_rows, np.int32, self))
 
@@ -421,6 +427,18 @@ def partition_precisions(coo, threshold_1):
     dp, sp = _vp(), _vp()
     _ck(lib().uspmv_partition_precisions(coo.h, threshold_1, C.byref(dp), C.byref(sp)))
     return Coo(dp), Coo(sp)
+
+
+_AP_KINDS = {"dp_hp": AP_DP_HP, "sp_hp": AP_SP_HP, "dp_sp_hp": AP_DP_SP_HP}
+
+
+def partition_precisions_hp(coo, kind, threshold_1, threshold_2=0.0):
+    """ap[dp_hp] / ap[sp_hp] / ap[dp_sp_hp] split (kind: AP_* or "dp_hp" | "sp_hp" | "dp_sp_hp"): (hi, mid, hp) Coo parts, mid None
+    for the two-part kinds.  Values are stored as doubles holding the part's rounded value (hp: binary16)."""
+    k = _AP_KINDS.get(kind, kind)
+    hi, mid, hp = _vp(), _vp(), _vp()
+    _ck(lib().uspmv_partition_precisions_hp(coo.h, k, threshold_1, threshold_2, C.byref(hi), C.byref(mid), C.byref(hp)))
+    return Coo(hi), (Coo(mid) if mid.value else None), Coo(hp)
 
 
 # ---------------------------------------------------------------------------------------- halo set-up
@@ -832,6 +850,11 @@ def _dp(t):
     return None if t is None else t.data_ptr()
 
 
+def _torch_dtype(dtype):
+    import torch
+    return {F64: torch.float64, F32: torch.float32, F16: torch.float16}[dtype]
+
+
 class DeviceMatrix:
     """SELL-C-sigma matrix resident in HBM (what assign_spmv_kernel_gpu_data stages,
     code/utilities.hpp:3721-3811).  Arrays are torch tensors owned by this object."""
@@ -841,14 +864,14 @@ class DeviceMatrix:
         if _handle is not None:          # arrays owned by the library (convert_to_scs_device)
             self.C, self.n_chunks, self.n_elements, self.dtype = scs.C, scs.n_chunks, scs.n_elements, scs.dtype
             self.n_rows, self.n_rows_padded, self.nnz = scs.n_rows, scs.n_rows_padded, scs.nnz
-            self.torch_dtype = torch.float64 if scs.dtype == F64 else torch.float32
+            self.torch_dtype = _torch_dtype(scs.dtype)
             self.h = _handle
             self.tlc_tiles = self.tlc_staged = self.tile_rows = self.block_tiles = self.block_staged = 0
             return
         a = scs.arrays()
         self.C, self.n_chunks, self.n_elements, self.dtype = scs.C, scs.n_chunks, scs.n_elements, scs.dtype
         self.n_rows, self.n_rows_padded, self.nnz = scs.n_rows, scs.n_rows_padded, scs.nnz
-        self.torch_dtype = torch.float64 if scs.dtype == F64 else torch.float32
+        self.torch_dtype = _torch_dtype(scs.dtype)
         dev = torch.device(device)
         self.chunk_ptrs = torch.from_numpy(a["chunk_ptrs"].copy()).to(dev)
         self.chunk_lengths = torch.from_numpy(a["chunk_lengths"].copy()).to(dev)
@@ -1042,7 +1065,7 @@ def spmmv_x_release(A):
 def dmat_download(A):
     """Host copies of a DeviceMatrix's arrays (tests / debugging)."""
     cp = np.empty(A.n_chunks + 1, np.int32); cl = np.empty(A.n_chunks, np.int32)
-    ci = np.empty(A.n_elements, np.int32); va = np.empty(A.n_elements, np.float64 if A.dtype == F64 else np.float32)
+    ci = np.empty(A.n_elements, np.int32); va = np.empty(A.n_elements, {F64: np.float64, F32: np.float32, F16: np.float16}[A.dtype])
     _ck(lib().uspmv_dmat_download(A.h, _np_ptr(cp), _np_ptr(cl), _np_ptr(ci), _np_ptr(va)))
     return dict(chunk_ptrs=cp, chunk_lengths=cl, col_idxs=ci, values=va)
 
@@ -1062,6 +1085,22 @@ def optimize_device_ap(A_dp, A_sp, max_lines=0):
     _ck(lib().uspmv_dmat_optimize_device_ap(A_dp.h, A_sp.h, max_lines, C.byref(a), C.byref(b)))
     for A in (A_dp, A_sp):
         A.tlc_tiles, A.tlc_staged = a.value, b.value
+    return a.value, b.value
+
+
+def optimize_ap_hp(A_hi, A_mid, A_hp, scs_hi, scs_mid, scs_hp, max_lines=0):
+    """Shared tile-local-column plan of the two or three parts of an ap split with an fp16 part (A_mid / scs_mid None for two parts);
+    returns (n_tiles, n_staged_tiles).  Fewer than half of the tiles staged: no plan is installed."""
+    a, b = _i64(), _i64()
+    _ck(lib().uspmv_dmat_optimize_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, scs_hi.h,
+                                        scs_mid.h if scs_mid is not None else None, scs_hp.h, max_lines, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def optimize_device_ap_hp(A_hi, A_mid, A_hp, max_lines=0):
+    """The plan of optimize_ap_hp built on the device from the handles' own arrays."""
+    a, b = _i64(), _i64()
+    _ck(lib().uspmv_dmat_optimize_device_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, max_lines, C.byref(a), C.byref(b)))
     return a.value, b.value
 
 
@@ -1102,6 +1141,14 @@ def spmv_ap(A_dp, A_sp, x, y, stream=None, x_sp=None):
         _ck(lib().uspmv_spmv_ap(A_dp.h, A_sp.h, _dp(x), _dp(y), _stream_ptr(stream)))
     else:
         _ck(lib().uspmv_spmv_ap_generic(A_dp.h, A_sp.h, _dp(x), _dp(x_sp), _dp(y), _stream_ptr(stream)))
+    return y
+
+
+def spmv_ap_hp(A_hi, A_mid, A_hp, x, y, stream=None):
+    """Adaptive precision with an fp16 part (uspmv_spmv_ap_hp): x, y float64 when A_hi is F64, float32 when it is F32; A_mid None for
+    the two-part kinds."""
+    assert x.dtype == A_hi.torch_dtype and y.dtype == A_hi.torch_dtype and y.numel() >= A_hi.n_rows_padded
+    _ck(lib().uspmv_spmv_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(x), _dp(y), _stream_ptr(stream)))
     return y
 
 

@@ -203,9 +203,203 @@ __global__ void scs_spmv_ap_rows(const long n_chunks, const int C_rt, const int 
     st_y<NT>(y + row, dt + st);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Adaptive precision with an fp16 part: ap[dp_hp] (HT double, no mid), ap[dp_sp_hp] (HT double, mid float), ap[sp_hp] (HT float, x and
+// y float).  One chain per part, each in slot order; with a double x every product is an FMA in double on the exactly widened value
+// (scs_ap_impl_cpu's convention, hp in the place of sp), with a float x the product is rounded to float and then added to the part's
+// double accumulator (the sp part of spmv_omp_scs_ap).  y = hi + hp, (hi + mid) + hp, or (float)(sp + hp).  hp values arrive as the
+// binary16 bits; v_cvt_f32_f16 widens them exactly.
+__device__ __forceinline__ float hp_val(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
+__device__ __forceinline__ double ap_step(double v, double x, double acc) { return __builtin_fma(v, x, acc); }
+__device__ __forceinline__ double ap_step(float v, double x, double acc) { return __builtin_fma((double)v, x, acc); }
+__device__ __forceinline__ double ap_step(unsigned short v, double x, double acc) { return __builtin_fma((double)hp_val(v), x, acc); }
+__device__ __forceinline__ double ap_step(float v, float x, double acc) { return acc + (double)__fmul_rn(v, x); }
+__device__ __forceinline__ double ap_step(unsigned short v, float x, double acc) { return acc + (double)__fmul_rn(hp_val(v), x); }
+
+// one part's chain over the staged x lines: values one per lane per slot, the 16-bit local indices four slots per 8-byte load
+template <bool NT, typename VT, typename XT>
+__device__ __forceinline__ double tlc_chain(const VT *__restrict__ vp, const unsigned long long *__restrict__ cq, const int L, const int C,
+                                            const XT *xs, double acc) {
+    const int ng = L >> 2;
+    int g = 0;
+    for (; g + 2 <= ng; g += 2) {
+        VT v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = ld_stream<NT>(vp + (long)(4 * g + u) * C);
+        const unsigned long long qa = ld_stream<NT>(cq + (long)g * C), qb = ld_stream<NT>(cq + (long)(g + 1) * C);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = ap_step(v[u], xs[(qa >> (16 * u)) & 0xFFFFu], acc);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = ap_step(v[4 + u], xs[(qb >> (16 * u)) & 0xFFFFu], acc);
+    }
+    for (; g < ng; ++g) {
+        VT v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = ld_stream<NT>(vp + (long)(4 * g + u) * C);
+        const unsigned long long qa = ld_stream<NT>(cq + (long)g * C);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = ap_step(v[u], xs[(qa >> (16 * u)) & 0xFFFFu], acc);
+    }
+    const int rem = L & 3;
+    if (rem) {
+        const unsigned long long qa = ld_stream<NT>(cq + (long)ng * C);
+        for (int u = 0; u < rem; ++u) acc = ap_step(ld_stream<NT>(vp + (long)(4 * ng + u) * C), xs[(qa >> (16 * u)) & 0xFFFFu], acc);
+    }
+    return acc;
+}
+
+// one part's chain with 32-bit columns and global gathers of x, U slots per batch
+template <bool NT, int U, typename VT, typename XT>
+__device__ __forceinline__ double gather_chain(const VT *__restrict__ vp, const int *__restrict__ cp, const int L, const int C,
+                                               const XT *__restrict__ x, double acc) {
+    int j = 0;
+    for (; j + U <= L; j += U) {
+        VT v[U]; int ci[U]; XT xv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { v[u] = ld_stream<NT>(vp + (long)(j + u) * C); ci[u] = ld_stream<NT>(cp + (long)(j + u) * C); }
+#pragma unroll
+        for (int u = 0; u < U; ++u) xv[u] = x[ci[u]];
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc = ap_step(v[u], xv[u], acc);
+    }
+    for (; j < L; ++j) acc = ap_step(ld_stream<NT>(vp + (long)j * C), x[ld_stream<NT>(cp + (long)j * C)], acc);
+    return acc;
+}
+
+template <typename HT, bool MID>
+__device__ __forceinline__ HT ap_hp_y(double h, double m, double q) {
+    if constexpr (sizeof(HT) == 4) return (float)(h + q);
+    else if constexpr (MID) return (h + m) + q;
+    else return h + q;
+}
+
+// the parts' arrays (mid: nullptr unless ap[dp_sp_hp]); c16p / c16: the shared plan's per-part local indices
+struct ApHpParts {
+    const int *cp[3], *cl[3], *ci[3];
+    const void *va[3];
+    const unsigned *c16p[3];
+    const unsigned short *c16[3];
+};
+
+// Tile-local-column form: the tile's x lines (the union over all parts) staged once in LDS, then the parts' chains one after the other,
+// each streaming sizeof(VT) + 2 bytes per non-zero.  Tiles without a line list (footprint over the plan's line budget) gather from x.
+template <int CT, bool NT, typename HT, bool MID>
+__global__ void __launch_bounds__(1024) scs_spmv_ap_hp_tlc(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ x,
+                                                           HT *__restrict__ y, const int *__restrict__ tile_line_ptr,
+                                                           const int *__restrict__ tile_lines, const long x_len, const int xcd_remap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tlc_smem[];
+    HT *xs = (HT *)tlc_smem;
+    typedef HT vec_t __attribute__((ext_vector_type(2)));
+    const int C = CT > 0 ? CT : C_rt;
+    const unsigned tile = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    const int lp0 = tile_line_ptr[tile];
+    const int nl = tile_line_ptr[tile + 1] - lp0;
+    const long row = (long)tile * blockDim.x + threadIdx.x;
+    const long c = row / C;
+    const int i = (int)(row - c * C);
+    const bool valid = c < n_chunks;
+    int cs[3] = {0, 0, 0}, L[3] = {0, 0, 0};
+    unsigned q0[3] = {0, 0, 0};
+    if (valid)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k != 1 || MID) { cs[k] = P.cp[k][c]; L[k] = P.cl[k][c]; q0[k] = P.c16p[k][c]; }
+    double acc[3] = {0.0, 0.0, 0.0};
+    if (nl > 0) {
+        const int sub = threadIdx.x & 7, lk = threadIdx.x >> 3;
+        for (int k = lk; k < nl; k += blockDim.x >> 3) {
+            const long idx = (long)tile_lines[lp0 + k] * 16 + sub * 2;
+            vec_t v;
+            if (idx + 2 <= x_len) v = *(const vec_t *)(x + idx);
+            else { v[0] = idx < x_len ? x[idx] : (HT)0; v[1] = (HT)0; }
+            *(vec_t *)(xs + k * 16 + sub * 2) = v;
+        }
+        __syncthreads();
+        if (L[0] > 0)
+            acc[0] = tlc_chain<NT>((const HT *)P.va[0] + (long)cs[0] + i, (const unsigned long long *)(P.c16[0] + q0[0]) + i, L[0], C, xs, 0.0);
+        if constexpr (MID)
+            if (L[1] > 0)
+                acc[1] = tlc_chain<NT>((const float *)P.va[1] + (long)cs[1] + i, (const unsigned long long *)(P.c16[1] + q0[1]) + i, L[1], C, xs, 0.0);
+        if (L[2] > 0)
+            acc[2] = tlc_chain<NT>((const unsigned short *)P.va[2] + (long)cs[2] + i, (const unsigned long long *)(P.c16[2] + q0[2]) + i, L[2], C,
+                                   xs, 0.0);
+    } else {  // wide-footprint tile: 32-bit columns, global gathers
+        acc[0] = gather_chain<NT, 1>((const HT *)P.va[0] + (long)cs[0] + i, P.ci[0] + (long)cs[0] + i, L[0], C, x, 0.0);
+        if constexpr (MID) acc[1] = gather_chain<NT, 1>((const float *)P.va[1] + (long)cs[1] + i, P.ci[1] + (long)cs[1] + i, L[1], C, x, 0.0);
+        acc[2] = gather_chain<NT, 1>((const unsigned short *)P.va[2] + (long)cs[2] + i, P.ci[2] + (long)cs[2] + i, L[2], C, x, 0.0);
+    }
+    if (valid) st_y<NT>(y + row, ap_hp_y<HT, MID>(acc[0], acc[1], acc[2]));
+}
+
+// Lane per row, any C and handles without a plan: the parts' chains one after the other with global gathers
+template <int U, bool NT, int CT, typename HT, bool MID>
+__global__ void scs_spmv_ap_hp_rows(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ x, HT *__restrict__ y,
+                                    const int xcd_remap) {
+    const int C = CT > 0 ? CT : C_rt;
+    const unsigned lb = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    const long row = (long)lb * blockDim.x + threadIdx.x;
+    const long c = row / C;
+    const int i = (int)(row - c * C);
+    if (c >= n_chunks) return;
+    double acc[3] = {0.0, 0.0, 0.0};
+    long cs = P.cp[0][c];
+    acc[0] = gather_chain<NT, U>((const HT *)P.va[0] + cs + i, P.ci[0] + cs + i, P.cl[0][c], C, x, 0.0);
+    if constexpr (MID) {
+        cs = P.cp[1][c];
+        acc[1] = gather_chain<NT, U>((const float *)P.va[1] + cs + i, P.ci[1] + cs + i, P.cl[1][c], C, x, 0.0);
+    }
+    cs = P.cp[2][c];
+    acc[2] = gather_chain<NT, U>((const unsigned short *)P.va[2] + cs + i, P.ci[2] + cs + i, P.cl[2][c], C, x, 0.0);
+    st_y<NT>(y + row, ap_hp_y<HT, MID>(acc[0], acc[1], acc[2]));
+}
+
+template <typename HT, bool MID>
+int launch_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const HT *d_x, HT *d_y, hipStream_t stream) {
+    ApHpParts P{};
+    const uspmv_dmat *ms[3] = {hi, mid, hp};
+    for (int k = 0; k < 3; ++k) {
+        if (!ms[k]) continue;
+        P.cp[k] = ms[k]->chunk_ptrs; P.cl[k] = ms[k]->chunk_lengths; P.ci[k] = ms[k]->col_idxs; P.va[k] = ms[k]->values;
+        P.c16p[k] = ms[k]->tlc.c16_ptrs; P.c16[k] = ms[k]->tlc.col16;
+    }
+    const uint64_t id = hi->tlc.plan_id;
+    const bool planned = hi->tlc.on && id != 0 && hp->tlc.on && hp->tlc.plan_id == id && (!mid || (mid->tlc.on && mid->tlc.plan_id == id));
+    const bool nt = g_tune.nontemporal != 0;
+    const int C = (int)hi->C;
+    if (planned && g_tune.tlc && (uintptr_t)d_x % 16 == 0) {
+        const size_t lds = (size_t)hi->tlc.max_lines * 16 * sizeof(HT);
+#define APHP_TLC(CTV, NTV)                                                                                                       \
+    do {                                                                                                                         \
+        auto kfn = scs_spmv_ap_hp_tlc<CTV, NTV, HT, MID>;                                                                        \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)hi->tlc.n_tiles), dim3(hi->tlc.tile_rows), lds, stream, (long)hi->n_chunks, C, P,  \
+                           d_x, d_y, hi->tlc.line_ptr.get(), hi->tlc.lines.get(), (long)hi->tlc.x_len, g_tune.xcd_remap);        \
+    } while (0)
+        if (nt) { if (C == 32) APHP_TLC(32, true); else APHP_TLC(0, true); }
+        else { if (C == 32) APHP_TLC(32, false); else APHP_TLC(0, false); }
+#undef APHP_TLC
+    } else {
+        const int block = g_tune.block;
+        const unsigned grid = grid_for(hi->n_chunks * hi->C, block);
+#define APHP_ROWS(CTV, NTV) hipLaunchKernelGGL((scs_spmv_ap_hp_rows<4, NTV, CTV, HT, MID>), dim3(grid), dim3(block), 0, stream, \
+                                               (long)hi->n_chunks, C, P, d_x, d_y, g_tune.xcd_remap)
+        if (nt) { if (C == 32) APHP_ROWS(32, true); else APHP_ROWS(0, true); }
+        else { if (C == 32) APHP_ROWS(32, false); else APHP_ROWS(0, false); }
+#undef APHP_ROWS
+    }
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
 }  // namespace
 
 namespace uspmv_dev {
+
+int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *d_x, void *d_y, hipStream_t stream) {
+    if (hi->dtype == USPMV_F32) return launch_ap_hp<float, false>(hi, nullptr, hp, (const float *)d_x, (float *)d_y, stream);
+    if (mid) return launch_ap_hp<double, true>(hi, mid, hp, (const double *)d_x, (double *)d_y, stream);
+    return launch_ap_hp<double, false>(hi, nullptr, hp, (const double *)d_x, (double *)d_y, stream);
+}
 
 int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *d_x,
                           double *d_y, hipStream_t stream) {

@@ -35,12 +35,14 @@ __device__ __forceinline__ int bit_to_line(int b, int lo, const int *win) {
 
 // Marks the lines of the tile in bits[]; returns (lo line, hi line, window table) through LDS scalars.  *s_hi < 0: empty tile.
 // *s_nwin == 0: contiguous mode (the whole range fits the bitmap); > 0: window mode with s_win[0 .. *s_nwin) sorted.
-// (chunk_ptrs2 != nullptr: a second struct with the same row layout -- the sp part of an ap[dp_sp] pair -- marks the same bitmap)
+// (chunk_ptrs2 != nullptr: a second struct with the same row layout -- the sp part of an ap[dp_sp] pair -- marks the same bitmap;
+//  chunk_ptrs3 likewise a third, the hp part of ap[dp_sp_hp])
 __device__ void tile_bitmap(const long n_chunks, const int C, const int *__restrict__ chunk_ptrs,
                             const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs, const long tile,
                             unsigned *bits, int *s_lo, int *s_hi, int *s_maxcol, int *s_bad, int *s_win, int *s_nwin,
                             const int rpt, const int *__restrict__ chunk_ptrs2 = nullptr, const int *__restrict__ chunk_lengths2 = nullptr,
-                            const int *__restrict__ col_idxs2 = nullptr) {
+                            const int *__restrict__ col_idxs2 = nullptr, const int *__restrict__ chunk_ptrs3 = nullptr,
+                            const int *__restrict__ chunk_lengths3 = nullptr, const int *__restrict__ col_idxs3 = nullptr) {
     // a tile is rpt * 256 rows: thread <-> rows tile*rpt*256 + h*256 + threadIdx.x, h < rpt
     if (threadIdx.x == 0) { *s_lo = INT32_MAX; *s_hi = -1; *s_bad = 0; *s_nwin = 0; }
     if (threadIdx.x < NWIN) s_win[threadIdx.x] = -1;
@@ -58,6 +60,10 @@ __device__ void tile_bitmap(const long n_chunks, const int C, const int *__restr
             if (chunk_ptrs2) {
                 const int cs2 = chunk_ptrs2[c], L2 = chunk_lengths2[c];
                 for (int j = 0; j < L2; ++j) f(col_idxs2[(long)cs2 + (long)j * C + i]);
+            }
+            if (chunk_ptrs3) {
+                const int cs3 = chunk_ptrs3[c], L3 = chunk_lengths3[c];
+                for (int j = 0; j < L3; ++j) f(col_idxs3[(long)cs3 + (long)j * C + i]);
             }
         }
     };
@@ -103,12 +109,14 @@ __device__ void tile_bitmap(const long n_chunks, const int C, const int *__restr
 __global__ void __launch_bounds__(256) plan_count_lines(const long n_chunks, const int C, const int *__restrict__ chunk_ptrs,
         const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs, const int max_lines,
         int *__restrict__ n_lines, int *__restrict__ max_col, const int *__restrict__ chunk_ptrs2, const int *__restrict__ chunk_lengths2,
-        const int *__restrict__ col_idxs2, const int rpt) {
+        const int *__restrict__ col_idxs2, const int rpt, const int *__restrict__ chunk_ptrs3, const int *__restrict__ chunk_lengths3,
+        const int *__restrict__ col_idxs3) {
     __shared__ unsigned bits[PLAN_WORDS];
     __shared__ int s_lo, s_hi, s_cnt, s_maxcol, s_bad, s_nwin, s_win[NWIN];
     if (threadIdx.x == 0) { s_cnt = 0; s_maxcol = 0; }
     const long tile = blockIdx.x;
-    tile_bitmap(n_chunks, C, chunk_ptrs, chunk_lengths, col_idxs, tile, bits, &s_lo, &s_hi, &s_maxcol, &s_bad, s_win, &s_nwin, rpt, chunk_ptrs2, chunk_lengths2, col_idxs2);
+    tile_bitmap(n_chunks, C, chunk_ptrs, chunk_lengths, col_idxs, tile, bits, &s_lo, &s_hi, &s_maxcol, &s_bad, s_win, &s_nwin, rpt, chunk_ptrs2, chunk_lengths2, col_idxs2,
+                chunk_ptrs3, chunk_lengths3, col_idxs3);
     int n = 0;
     if (s_hi >= 0 && !s_bad) {
         int cnt = 0;
@@ -127,7 +135,9 @@ __global__ void __launch_bounds__(256) plan_write(const long n_chunks, const int
         const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs, const int *__restrict__ tile_line_ptr,
         const unsigned *__restrict__ c16_ptrs, int *__restrict__ tile_lines, unsigned short *__restrict__ col16,
         const int *__restrict__ chunk_ptrs2, const int *__restrict__ chunk_lengths2, const int *__restrict__ col_idxs2,
-        const unsigned *__restrict__ c16_ptrs2, unsigned short *__restrict__ col16_2, const int rpt) {
+        const unsigned *__restrict__ c16_ptrs2, unsigned short *__restrict__ col16_2, const int rpt, const int *__restrict__ chunk_ptrs3,
+        const int *__restrict__ chunk_lengths3, const int *__restrict__ col_idxs3, const unsigned *__restrict__ c16_ptrs3,
+        unsigned short *__restrict__ col16_3) {
     __shared__ unsigned bits[PLAN_WORDS];
     __shared__ unsigned short rank0[PLAN_WORDS];   // set bits in the words before this one (< 4096)
     __shared__ int s_lo, s_hi, s_dummy, s_bad, s_nwin, s_win[NWIN];
@@ -136,7 +146,8 @@ __global__ void __launch_bounds__(256) plan_write(const long n_chunks, const int
     const int lp0 = tile_line_ptr[tile];
     if (tile_line_ptr[tile + 1] == lp0) return;   // unstaged or empty tile: col16 stays zero, the kernel gathers
     if (threadIdx.x == 0) s_dummy = 0;
-    tile_bitmap(n_chunks, C, chunk_ptrs, chunk_lengths, col_idxs, tile, bits, &s_lo, &s_hi, &s_dummy, &s_bad, s_win, &s_nwin, rpt, chunk_ptrs2, chunk_lengths2, col_idxs2);
+    tile_bitmap(n_chunks, C, chunk_ptrs, chunk_lengths, col_idxs, tile, bits, &s_lo, &s_hi, &s_dummy, &s_bad, s_win, &s_nwin, rpt, chunk_ptrs2, chunk_lengths2, col_idxs2,
+                chunk_ptrs3, chunk_lengths3, col_idxs3);
     const int *win = s_nwin > 0 ? s_win : nullptr;
     const int nwin = s_nwin;
     // exclusive prefix of the popcounts: 8 consecutive words per thread, then a block scan of the 256 partial sums
@@ -189,6 +200,17 @@ __global__ void __launch_bounds__(256) plan_write(const long n_chunks, const int
                 const unsigned below = bits[l >> 5] & ((1u << (l & 31)) - 1u);
                 const int pos = rank0[l >> 5] + __popc(below);
                 q2[(long)(j >> 2) * 4 * C + i * 4 + (j & 3)] = (unsigned short)((pos << 4) | (col & 15));
+            }
+        }
+        if (chunk_ptrs3) {
+            const int cs3 = chunk_ptrs3[c], L3 = chunk_lengths3[c];
+            unsigned short *q3 = col16_3 + c16_ptrs3[c];
+            for (int j = 0; j < L3; ++j) {
+                const int col = col_idxs3[(long)cs3 + (long)j * C + i];
+                const int l = line_to_bit(col >> 4, tlo, win, nwin);
+                const unsigned below = bits[l >> 5] & ((1u << (l & 31)) - 1u);
+                const int pos = rank0[l >> 5] + __popc(below);
+                q3[(long)(j >> 2) * 4 * C + i * 4 + (j & 3)] = (unsigned short)((pos << 4) | (col & 15));
             }
         }
     }
@@ -248,10 +270,12 @@ __global__ void __launch_bounds__(256) plan_pack12(const long n_chunks, const in
 
 namespace uspmv_dev {
 
-int launch_plan_count(const uspmv_dmat *A, long n_tiles, int max_lines, int *d_n_lines, int *d_max_col, hipStream_t st, const uspmv_dmat *A2, int tile_rows) {
+int launch_plan_count(const uspmv_dmat *A, long n_tiles, int max_lines, int *d_n_lines, int *d_max_col, hipStream_t st, const uspmv_dmat *A2, int tile_rows,
+                      const uspmv_dmat *A3) {
     hipLaunchKernelGGL(plan_count_lines, dim3((unsigned)n_tiles), dim3(256), 0, st, (long)A->n_chunks, (int)A->C, A->chunk_ptrs,
                        A->chunk_lengths, A->col_idxs, max_lines, d_n_lines, d_max_col, A2 ? A2->chunk_ptrs : nullptr,
-                       A2 ? A2->chunk_lengths : nullptr, A2 ? A2->col_idxs : nullptr, tile_rows / 256);
+                       A2 ? A2->chunk_lengths : nullptr, A2 ? A2->col_idxs : nullptr, tile_rows / 256, A3 ? A3->chunk_ptrs : nullptr,
+                       A3 ? A3->chunk_lengths : nullptr, A3 ? A3->col_idxs : nullptr);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }
@@ -266,10 +290,12 @@ int launch_plan_pack12(const uspmv_dmat *A, const unsigned *d_c16_ptrs, const un
 }
 
 int launch_plan_write(const uspmv_dmat *A, long n_tiles, const int *d_tile_line_ptr, const unsigned *d_c16_ptrs, int *d_tile_lines,
-                      unsigned short *d_col16, hipStream_t st, const uspmv_dmat *A2, const unsigned *d_c16_ptrs2, unsigned short *d_col16_2, int tile_rows) {
+                      unsigned short *d_col16, hipStream_t st, const uspmv_dmat *A2, const unsigned *d_c16_ptrs2, unsigned short *d_col16_2, int tile_rows,
+                      const uspmv_dmat *A3, const unsigned *d_c16_ptrs3, unsigned short *d_col16_3) {
     hipLaunchKernelGGL(plan_write, dim3((unsigned)n_tiles), dim3(256), 0, st, (long)A->n_chunks, (int)A->C, A->chunk_ptrs,
                        A->chunk_lengths, A->col_idxs, d_tile_line_ptr, d_c16_ptrs, d_tile_lines, d_col16, A2 ? A2->chunk_ptrs : nullptr,
-                       A2 ? A2->chunk_lengths : nullptr, A2 ? A2->col_idxs : nullptr, d_c16_ptrs2, d_col16_2, tile_rows / 256);
+                       A2 ? A2->chunk_lengths : nullptr, A2 ? A2->col_idxs : nullptr, d_c16_ptrs2, d_col16_2, tile_rows / 256,
+                       A3 ? A3->chunk_ptrs : nullptr, A3 ? A3->chunk_lengths : nullptr, A3 ? A3->col_idxs : nullptr, d_c16_ptrs3, d_col16_3);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }

@@ -29,6 +29,14 @@ int check_dmat(const uspmv_dmat *A, const char *who) {
     return USPMV_OK;
 }
 
+// one-precision entry points (SpMV, SpMMV and their plans): an fp16 handle only runs as the hp part of uspmv_spmv_ap_hp
+static int check_dmat_one_prec(const uspmv_dmat *A, const char *who) {
+    if (int rc = check_dmat(A, who)) return rc;
+    if (A->dtype == USPMV_F16)
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: fp16 handle; fp16 values run only as the hp part of uspmv_spmv_ap_hp", who);
+    return USPMV_OK;
+}
+
 
 }  // namespace uspmv_dev
 
@@ -328,7 +336,7 @@ int uspmv_dmat_upload(const uspmv_scs_t *s, uspmv_dmat_t **out) {
     auto *A = new uspmv_dmat;
     A->C = s->C; A->n_chunks = s->n_chunks; A->n_elements = s->n_elements; A->dtype = s->dtype;
     A->n_store = (long)(s->n_chunks * s->C);
-    const size_t vsz = s->dtype == USPMV_F64 ? 8 : 4;
+    const size_t vsz = uspmv_dtype_bytes(s->dtype);
     hipError_t e = A->own_arrays();
     if (e != hipSuccess) {
         delete A;
@@ -349,7 +357,7 @@ int uspmv_dmat_upload(const uspmv_scs_t *s, uspmv_dmat_t **out) {
 int uspmv_dmat_wrap(int64_t C, int64_t n_chunks, int64_t n_elements, int dtype, const int32_t *d_chunk_ptrs,
                     const int32_t *d_chunk_lengths, const int32_t *d_col_idxs, const void *d_values,
                     uspmv_dmat_t **out) {
-    if (!out || C < 1 || n_chunks < 0 || n_elements < 0 || (dtype != USPMV_F64 && dtype != USPMV_F32) ||
+    if (!out || C < 1 || n_chunks < 0 || n_elements < 0 || (dtype != USPMV_F64 && dtype != USPMV_F32 && dtype != USPMV_F16) ||
         !d_chunk_ptrs || (n_chunks > 0 && !d_chunk_lengths) || (n_elements > 0 && (!d_col_idxs || !d_values)))
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_wrap: bad argument");
     auto *A = new uspmv_dmat;
@@ -362,6 +370,7 @@ int uspmv_dmat_wrap(int64_t C, int64_t n_chunks, int64_t n_elements, int dtype, 
 int uspmv_convert_to_scs_device(const uspmv_coo_t *m, int64_t C, int64_t sigma, int dtype, const int32_t *fixed_permutation,
                                 int permute_cols, uspmv_scs_t **layout, uspmv_dmat_t **out) {
     if (!m || !layout || !out) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_convert_to_scs_device: NULL argument");
+    if (dtype == USPMV_F16) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_convert_to_scs_device: no device-side conversion of fp16 parts (uspmv_convert_to_scs + uspmv_dmat_upload)");
     if (int rc = require_device()) return rc;
     auto *s = new uspmv_scs;
     std::vector<int64_t> row_start;
@@ -433,7 +442,7 @@ int uspmv_dmat_meta(const uspmv_dmat_t *A, int64_t meta[4]) {
 int uspmv_dmat_download(const uspmv_dmat_t *A, int32_t *chunk_ptrs, int32_t *chunk_lengths, int32_t *col_idxs, void *values) {
     if (int rc = check_dmat(A, "uspmv_dmat_download")) return rc;
     if (int rc = require_device()) return rc;
-    const size_t vsz = A->dtype == USPMV_F64 ? 8 : 4;
+    const size_t vsz = uspmv_dtype_bytes(A->dtype);
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess && chunk_ptrs) e = hipMemcpy(chunk_ptrs, A->chunk_ptrs, 4 * (size_t)(A->n_chunks + 1), hipMemcpyDeviceToHost);
     if (e == hipSuccess && chunk_lengths) e = hipMemcpy(chunk_lengths, A->chunk_lengths, 4 * (size_t)A->n_chunks, hipMemcpyDeviceToHost);
@@ -458,7 +467,8 @@ static int plan_tile_rows(bool ap) { return g_tune.tlc_tile_rows ? g_tune.tlc_ti
 static bool tile_rows_grow(int rows, int lines_used) { return g_tune.tlc_auto_tile && g_tune.tlc_tile_rows == 0 && rows == 256 && lines_used > 250; }
 static bool tile_rows_accept(int64_t n_tiles, int64_t n_staged) { return n_staged * 100 >= n_tiles * 99; }
 
-static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, int R, int64_t *n_tiles, int64_t *n_staged, const char *who);
+static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, int R, int64_t *n_tiles, int64_t *n_staged, const char *who,
+                                    uspmv_dmat_t *B3 = nullptr);
 
 // For LARGE single structs the rows per tile are MEASURED (tuning tlc_measure_tile, default on; only when tlc_tile_rows is 0): the plan
 // is built on the device for 256, 512 and 1024 rows (two passes over the column indices each), the kernel timed three times on a zero
@@ -602,6 +612,7 @@ static bool elements_over_cap(const uspmv_scs_t *s, int cap, int tile_rows) { re
 
 int uspmv_dmat_optimize(uspmv_dmat_t *A, const uspmv_scs_t *s, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
     if (!A || !s) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize: NULL argument");
+    if (int rc = check_dmat_one_prec(A, "uspmv_dmat_optimize")) return rc;
     if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize: layout-only struct; the plan builder needs the host column indices");
     if (A->C != s->C || A->n_chunks != s->n_chunks || A->dtype != s->dtype)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize: handle and host struct do not describe the same matrix");
@@ -755,9 +766,12 @@ static int device_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, 
     return device_plan_install_rows(A, nullptr, max_lines, R0, n_tiles, n_staged, who);
 }
 
-static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, const int R, int64_t *n_tiles, int64_t *n_staged, const char *who) {
+// (B3: a third struct sharing the plan -- the hp part of ap[dp_sp_hp]; only with B)
+static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, const int R, int64_t *n_tiles, int64_t *n_staged, const char *who,
+                                    uspmv_dmat_t *B3) {
     A->tlc = {};
     if (B) B->tlc = {};
+    if (B3) B3->tlc = {};
     if (n_tiles) *n_tiles = 0;
     if (n_staged) *n_staged = 0;
     const int64_t C = A->C, nc = A->n_chunks;
@@ -767,19 +781,23 @@ static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_li
     max_lines = std::min(max_lines, B ? 1280 : 4096);
     const int64_t T = R / C, nt = (nc + T - 1) / T;
     std::vector<int32_t> cl((size_t)nc);
-    std::vector<uint32_t> c16p, c16p_b;
-    int64_t tot16 = 0, tot16_b = 0;
+    std::vector<uint32_t> c16p, c16p_b, c16p_c;
+    int64_t tot16 = 0, tot16_b = 0, tot16_c = 0;
     HIP_TRY(hipMemcpy(cl.data(), A->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
     if (!c16_offsets(cl, C, &c16p, &tot16)) return USPMV_OK;
     if (B) {
         HIP_TRY(hipMemcpy(cl.data(), B->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
         if (!c16_offsets(cl, C, &c16p_b, &tot16_b)) return USPMV_OK;
     }
+    if (B3) {
+        HIP_TRY(hipMemcpy(cl.data(), B3->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
+        if (!c16_offsets(cl, C, &c16p_c, &tot16_c)) return USPMV_OK;
+    }
     DeviceBuf<int> d_n, d_max;
     hipError_t e = d_n.alloc(4 * (size_t)nt);
     if (e == hipSuccess) e = d_max.zeros(4);
     if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-    int rc = launch_plan_count(A, (long)nt, max_lines, d_n, d_max, nullptr, B, R);
+    int rc = launch_plan_count(A, (long)nt, max_lines, d_n, d_max, nullptr, B, R, B3);
     std::vector<int32_t> lp((size_t)nt + 1, 0);
     int max_col = 0;
     if (!rc) {
@@ -809,18 +827,24 @@ static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_li
         if (e == hipSuccess) e = B->tlc.c16_ptrs.upload(c16p_b.data(), 4 * ((size_t)nc + 1));
         if (e == hipSuccess) e = B->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16_b, 1));
     }
+    if (B3) {
+        if (e == hipSuccess) e = B3->tlc.c16_ptrs.upload(c16p_c.data(), 4 * ((size_t)nc + 1));
+        if (e == hipSuccess) e = B3->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16_c, 1));
+    }
     if (e == hipSuccess && launch_plan_write(A, (long)nt, A->tlc.line_ptr, A->tlc.c16_ptrs, A->tlc.lines, A->tlc.col16, nullptr, B,
-                                             B ? B->tlc.c16_ptrs : nullptr, B ? B->tlc.col16 : nullptr, R) != USPMV_OK)
+                                             B ? B->tlc.c16_ptrs : nullptr, B ? B->tlc.col16 : nullptr, R, B3,
+                                             B3 ? B3->tlc.c16_ptrs : nullptr, B3 ? B3->tlc.col16 : nullptr) != USPMV_OK)
         e = hipErrorUnknown;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
         A->tlc = {};
         if (B) B->tlc = {};
+        if (B3) B3->tlc = {};
         return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     static uint64_t next_dev_plan_id = (uint64_t)1 << 40;
     const uint64_t id = B ? next_dev_plan_id++ : 0;
-    for (uspmv_dmat_t *M : {A, B}) {
+    for (uspmv_dmat_t *M : {A, B, B3}) {
         if (!M) continue;
         M->tlc.on = true; M->tlc.tile_rows = R; M->tlc.max_lines = used; M->tlc.x_len = (int64_t)max_col + 1; M->tlc.n_tiles = nt;
         M->tlc.staged = staged; M->tlc.plan_id = id;
@@ -847,7 +871,7 @@ static int device_sweep_if_irregular(uspmv_dmat_t *A, uspmv_dmat_t *B, int64_t *
 }
 
 int uspmv_dmat_optimize_device(uspmv_dmat_t *A, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    if (int rc = check_dmat(A, "uspmv_dmat_optimize_device")) return rc;
+    if (int rc = check_dmat_one_prec(A, "uspmv_dmat_optimize_device")) return rc;
     if (int rc = require_device()) return rc;
     if (A->alt) { uspmv_dmat_free(A->alt); A->alt = nullptr; }
     if (A->C < 32 && 32 % A->C == 0 && g_tune.rechunk && A->n_chunks > 0) {
@@ -901,6 +925,91 @@ int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_li
     return device_sweep_if_irregular(dp, sp, n_tiles, n_staged, "uspmv_dmat_optimize_device_ap");
 }
 
+// the parts of an ap split with an fp16 part: hi F64 | F32, mid F32 (hi F64) or NULL, hp F16, one row layout
+static int check_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const char *who) {
+    if (int rc = check_dmat(hi, who)) return rc;
+    if (int rc = check_dmat(hp, who)) return rc;
+    if (mid) if (int rc = check_dmat(mid, who)) return rc;
+    const bool ok = hp->dtype == USPMV_F16 && (mid ? hi->dtype == USPMV_F64 && mid->dtype == USPMV_F32 : hi->dtype == USPMV_F64 || hi->dtype == USPMV_F32);
+    if (!ok) return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts must be (F64, -, F16), (F32, -, F16) or (F64, F32, F16)", who);
+    if (hi->C != hp->C || hi->n_chunks != hp->n_chunks || (mid && (mid->C != hi->C || mid->n_chunks != hi->n_chunks)))
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts must share C and n_chunks", who);
+    return USPMV_OK;
+}
+
+// shared plans of the two or three parts: the line plan where it stages at least half of the tiles, otherwise none (no sweep for hp parts)
+static bool ap_hp_plan_worth(int64_t n_tiles, int64_t n_staged) { return n_staged > 0 && n_staged * 2 >= n_tiles; }
+
+int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
+                              const uspmv_scs_t *s_hp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_ap_hp";
+    if (!s_hi || !s_hp || (mid && !s_mid)) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    const uspmv_scs_t *ss[3] = {s_hi, mid ? s_mid : s_hp, mid ? s_hp : nullptr};
+    uspmv_dmat_t *ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
+    for (int k = 0; k < 3; ++k) {
+        if (!ms[k]) continue;
+        if (!uspmv::scs_has_entries(ss[k]))
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host column indices", who);
+        if (ms[k]->C != ss[k]->C || ms[k]->n_chunks != ss[k]->n_chunks || ms[k]->dtype != ss[k]->dtype)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: handles and host structs do not describe the same parts", who);
+    }
+    if (int rc = require_device()) return rc;
+    for (uspmv_dmat_t *M : ms) if (M) { M->tlc = {}; M->sw = {}; }
+    if (n_tiles) *n_tiles = 0;
+    if (n_staged) *n_staged = 0;
+    if (max_lines <= 0) max_lines = 512;
+    if (max_lines > 1280) max_lines = 1280;
+    uspmv_tlc_plan p;
+    if (int rc = uspmv_build_tlc_plan(ss[0], ss[1], max_lines, plan_tile_rows(true), &p, 4, ss[2])) return rc;
+    if (n_tiles) *n_tiles = p.n_tiles;
+    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
+    if (!p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
+    hipError_t e = hi->tlc.line_ptr.upload(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4);
+    if (e == hipSuccess) e = hi->tlc.lines.upload(p.tile_lines.data(), p.tile_lines.size() * 4);
+    if (e == hipSuccess) e = hi->tlc.c16_ptrs.upload(p.c16_ptrs.data(), p.c16_ptrs.size() * 4);
+    if (e == hipSuccess) e = hi->tlc.col16.upload(p.col16.data(), p.col16.size() * 2);
+    if (e == hipSuccess) e = ms[1]->tlc.c16_ptrs.upload(p.c16_ptrs_b.data(), p.c16_ptrs_b.size() * 4);
+    if (e == hipSuccess) e = ms[1]->tlc.col16.upload(p.col16_b.data(), p.col16_b.size() * 2);
+    if (ms[2] && e == hipSuccess) e = ms[2]->tlc.c16_ptrs.upload(p.c16_ptrs_c.data(), p.c16_ptrs_c.size() * 4);
+    if (ms[2] && e == hipSuccess) e = ms[2]->tlc.col16.upload(p.col16_c.data(), p.col16_c.size() * 2);
+    if (e != hipSuccess) {
+        for (uspmv_dmat_t *M : ms) if (M) M->tlc = {};
+        return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
+    }
+    static uint64_t next_hp_plan_id = (uint64_t)1 << 48;       // (apart from the ids of uspmv_dmat_optimize_ap and the device planner)
+    const uint64_t id = next_hp_plan_id++;
+    for (uspmv_dmat_t *M : ms) {
+        if (!M) continue;
+        M->tlc.on = true; M->tlc.tile_rows = p.tile_rows; M->tlc.max_lines = p.max_lines_used; M->tlc.x_len = p.x_len_min;
+        M->tlc.n_tiles = p.n_tiles; M->tlc.staged = p.n_staged_tiles; M->tlc.plan_id = id;
+    }
+    return USPMV_OK;
+}
+
+int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_device_ap_hp";
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    if (int rc = require_device()) return rc;
+    uspmv_dmat_t *ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
+    for (uspmv_dmat_t *M : ms) if (M) M->sw = {};
+    int64_t nt = 0, ns = 0;
+    if (int rc = device_plan_install_rows(ms[0], ms[1], max_lines, plan_tile_rows(true), &nt, &ns, who, ms[2])) return rc;
+    if (n_tiles) *n_tiles = nt;
+    if (n_staged) *n_staged = ns;
+    if (!ap_hp_plan_worth(nt, ns))
+        for (uspmv_dmat_t *M : ms) if (M) M->tlc = {};
+    return USPMV_OK;
+}
+
+int uspmv_spmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, void *d_y, void *stream) {
+    if (int rc = check_ap_hp(hi, mid, hp, "uspmv_spmv_ap_hp")) return rc;
+    if (!d_x || !d_y) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_ap_hp: NULL vector");
+    if (int rc = require_device()) return rc;
+    if (hi->n_chunks == 0) return USPMV_OK;
+    return launch_spmv_ap_hp(hi, mid, hp, d_x, d_y, (hipStream_t)stream);
+}
+
 int uspmv_dmat_plan_download(const uspmv_dmat_t *A, int64_t meta[4], int32_t *tile_line_ptr, int32_t *tile_lines, uint32_t *c16_ptrs,
                              uint16_t *col16) {
     if (int rc = check_dmat(A, "uspmv_dmat_plan_download")) return rc;
@@ -909,10 +1018,11 @@ int uspmv_dmat_plan_download(const uspmv_dmat_t *A, int64_t meta[4], int32_t *ti
     if (!A->tlc.on) return USPMV_OK;
     if (int rc = require_device()) return rc;
     int32_t last = 0; uint32_t last16 = 0;
-    HIP_TRY(hipMemcpy(&last, A->tlc.line_ptr + A->tlc.n_tiles, 4, hipMemcpyDeviceToHost));
+    // (the second and third part of a shared ap plan hold only their local indices: the line list lives with the first part)
+    if (A->tlc.line_ptr) HIP_TRY(hipMemcpy(&last, A->tlc.line_ptr + A->tlc.n_tiles, 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&last16, A->tlc.c16_ptrs + A->n_chunks, 4, hipMemcpyDeviceToHost));
     meta[0] = A->tlc.n_tiles; meta[1] = last; meta[2] = last16; meta[3] = A->tlc.max_lines;
-    if (tile_line_ptr) HIP_TRY(hipMemcpy(tile_line_ptr, A->tlc.line_ptr, 4 * ((size_t)A->tlc.n_tiles + 1), hipMemcpyDeviceToHost));
+    if (tile_line_ptr && A->tlc.line_ptr) HIP_TRY(hipMemcpy(tile_line_ptr, A->tlc.line_ptr, 4 * ((size_t)A->tlc.n_tiles + 1), hipMemcpyDeviceToHost));
     if (tile_lines && last) HIP_TRY(hipMemcpy(tile_lines, A->tlc.lines, 4 * (size_t)last, hipMemcpyDeviceToHost));
     if (c16_ptrs) HIP_TRY(hipMemcpy(c16_ptrs, A->tlc.c16_ptrs, 4 * ((size_t)A->n_chunks + 1), hipMemcpyDeviceToHost));
     if (col16 && last16) HIP_TRY(hipMemcpy(col16, A->tlc.col16, 2 * (size_t)last16, hipMemcpyDeviceToHost));
@@ -961,6 +1071,7 @@ int dmat_part_set_plan(uspmv_dmat *A, long n_local, int64_t *n_boundary_tiles) {
 
 int uspmv_dmat_optimize_block(uspmv_dmat_t *A, const uspmv_scs_t *s, int block_vec_size, int64_t *n_tiles, int64_t *n_staged) {
     if (!A || !s) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block: NULL argument");
+    if (int rc = check_dmat_one_prec(A, "uspmv_dmat_optimize_block")) return rc;
     if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block: layout-only struct; the plan builder needs the host column indices");
     if (A->C != s->C || A->n_chunks != s->n_chunks || A->dtype != s->dtype)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block: handle and host struct do not describe the same matrix");
@@ -1213,7 +1324,7 @@ static int block_plan_install_device(uspmv_dmat_t *A, int block_vec_size, int64_
 // handle's own array and never cross the bus.  Without the caller's permutation the tie re-ordering orders the rows of equal-length
 // chunks by their first column (uspmv_scs_reorder_ties), which for locally numbered matrices restores the original row order.
 int uspmv_dmat_optimize_block_device(uspmv_dmat_t *A, int block_vec_size, int64_t *n_tiles, int64_t *n_staged) {
-    if (int rc = check_dmat(A, "uspmv_dmat_optimize_block_device")) return rc;
+    if (int rc = check_dmat_one_prec(A, "uspmv_dmat_optimize_block_device")) return rc;
     if (block_vec_size < 1) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block_device: block_vec_size must be >= 1");
     if (int rc = require_device()) return rc;
     uspmv_dmat_t *M = (A->alt && g_tune.rechunk) ? A->alt : A;      // narrow chunks: the internal C = 32 re-chunking is what uspmv_spmmv runs on
@@ -1475,6 +1586,7 @@ static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog,
 
 int uspmv_dmat_optimize_sweep(uspmv_dmat_t *A, const uspmv_scs_t *s, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep) {
     if (!A || !s) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_sweep: NULL argument");
+    if (int rc = check_dmat_one_prec(A, "uspmv_dmat_optimize_sweep")) return rc;
     if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_sweep: layout-only struct; the plan builder needs the host entries");
     if (A->C != s->C || A->n_chunks != s->n_chunks || A->dtype != s->dtype)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_sweep: handle and host struct do not describe the same matrix");
@@ -1501,6 +1613,7 @@ int uspmv_dmat_optimize_sweep_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv
 // buffer; 4 096-row tiles, fewer when the matrix is small).
 int uspmv_dmat_optimize_block_sweep(uspmv_dmat_t *A, const uspmv_scs_t *s, int block_vec_size, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep) {
     if (!A || !s) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block_sweep: NULL argument");
+    if (int rc = check_dmat_one_prec(A, "uspmv_dmat_optimize_block_sweep")) return rc;
     if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block_sweep: layout-only struct; the plan builder needs the host entries");
     if (A->C != s->C || A->n_chunks != s->n_chunks || A->dtype != s->dtype)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block_sweep: handle and host struct do not describe the same matrix");
@@ -1558,7 +1671,7 @@ int uspmv_dmat_set_crs(uspmv_dmat_t *A, int on) {
 }
 
 int uspmv_spmv(const uspmv_dmat_t *A, const void *d_x, void *d_y, void *stream) {
-    if (int rc = check_dmat(A, "uspmv_spmv")) return rc;
+    if (int rc = check_dmat_one_prec(A, "uspmv_spmv")) return rc;
     if (!d_x || !d_y) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv: NULL vector");
     if (int rc = require_device()) return rc;
     if (A->alt && g_tune.tlc && g_tune.rechunk && g_tune.spmv_variant == 0 && !g_tune.ablate) {
@@ -1578,7 +1691,7 @@ int uspmv_spmv(const uspmv_dmat_t *A, const void *d_x, void *d_y, void *stream) 
 
 int uspmv_spmv_chunks(const uspmv_dmat_t *A, const int32_t *d_chunk_ids, int64_t n_ids, const void *d_x, void *d_y,
                       void *stream) {
-    if (int rc = check_dmat(A, "uspmv_spmv_chunks")) return rc;
+    if (int rc = check_dmat_one_prec(A, "uspmv_spmv_chunks")) return rc;
     if (n_ids < 0 || n_ids > A->n_chunks || (n_ids > 0 && !d_chunk_ids) || !d_x || !d_y)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_chunks: bad argument");
     if (int rc = require_device()) return rc;
@@ -1589,7 +1702,7 @@ int uspmv_spmv_chunks(const uspmv_dmat_t *A, const int32_t *d_chunk_ids, int64_t
 
 int uspmv_spmv_tiles(const uspmv_dmat_t *A, const int32_t *d_tile_ids, int64_t n_ids, const void *d_x, void *d_y,
                      void *stream) {
-    if (int rc = check_dmat(A, "uspmv_spmv_tiles")) return rc;
+    if (int rc = check_dmat_one_prec(A, "uspmv_spmv_tiles")) return rc;
     if (!A->tlc.on || A->tlc.plan_id != 0) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_tiles: handle has no tile-local-column plan (uspmv_dmat_optimize)");
     if (n_ids < 0 || n_ids > A->tlc.n_tiles || (n_ids > 0 && !d_tile_ids) || !d_x || !d_y)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_tiles: bad argument");
@@ -1600,7 +1713,7 @@ int uspmv_spmv_tiles(const uspmv_dmat_t *A, const int32_t *d_tile_ids, int64_t n
 }
 
 int uspmv_dmat_optimize_sweep_device(uspmv_dmat_t *A, uspmv_dmat_t *sp, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep) {
-    if (int rc = check_dmat(A, "uspmv_dmat_optimize_sweep_device")) return rc;
+    if (int rc = check_dmat_one_prec(A, "uspmv_dmat_optimize_sweep_device")) return rc;
     if (sp) {
         if (int rc = check_dmat(sp, "uspmv_dmat_optimize_sweep_device")) return rc;
         if (A->dtype != USPMV_F64 || sp->dtype != USPMV_F32 || A->C != sp->C || A->n_chunks != sp->n_chunks)
@@ -1746,7 +1859,7 @@ int uspmv_dmat_index_bits(const uspmv_dmat_t *A, int *bits) {
 }
 
 int uspmv_spmmv(const uspmv_dmat_t *A, const void *d_X, void *d_Y, int b, int64_t ld, int layout, void *stream) {
-    if (int rc = check_dmat(A, "uspmv_spmmv")) return rc;
+    if (int rc = check_dmat_one_prec(A, "uspmv_spmmv")) return rc;
     if (!d_X || !d_Y || b < 1) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv: bad argument");
     if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv: unknown layout %d", layout);
     if (layout == USPMV_COLWISE && ld < A->n_chunks * A->C)
@@ -1761,7 +1874,7 @@ int uspmv_spmmv(const uspmv_dmat_t *A, const void *d_X, void *d_Y, int b, int64_
 }
 
 int uspmv_spmmv_x_prepared(const uspmv_dmat_t *A, const void *d_X, int b, int64_t ld, void *stream) {
-    if (int rc = check_dmat(A, "uspmv_spmmv_x_prepared")) return rc;
+    if (int rc = check_dmat_one_prec(A, "uspmv_spmmv_x_prepared")) return rc;
     if (!d_X || b < 1 || ld < A->n_chunks * A->C) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv_x_prepared: bad argument");
     if (int rc = require_device()) return rc;
     if (A->alt && g_tune.rechunk) A = A->alt;

@@ -108,7 +108,7 @@ struct uspmv_dmat {
         hipError_t e = own.chunk_ptrs.alloc(4 * ((size_t)n_chunks + 1));
         if (e == hipSuccess) e = own.chunk_lengths.alloc(4 * (size_t)std::max<int64_t>(n_chunks, 1));
         if (e == hipSuccess) e = own.col_idxs.alloc(4 * ne);
-        if (e == hipSuccess) e = own.values.alloc((dtype == USPMV_F64 ? 8 : 4) * ne);
+        if (e == hipSuccess) e = own.values.alloc(uspmv_dtype_bytes(dtype) * ne);
         chunk_ptrs = own.chunk_ptrs; chunk_lengths = own.chunk_lengths; col_idxs = own.col_idxs; values = own.values;
         return e;
     }
@@ -384,19 +384,23 @@ bool spmmv_stream(const uspmv_dmat *A, const float *X, float *Y, long ld, bool y
 int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu);
 int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x, const float *d_x_sp, double *d_y,
                    hipStream_t stream);                                                                           // ap_kernels.hip
+// ap with an fp16 part (hi F64 | F32, mid F32 or nullptr, hp F16): the shared tile-local-column plan when all parts carry it, else lane per row
+int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *d_x, void *d_y, hipStream_t stream);   // ap_kernels.hip
 template <typename VT>
 int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st);                                    // sweep_kernels.hip (sweep tiles only)
 int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st);                       // sweep_kernels.hip
 int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *d_x,
                           double *d_y, hipStream_t stream);                                                        // ap_kernels.hip
 
-// (A2 / the *_2 arrays: optional second struct sharing the plan -- the sp part of an ap[dp_sp] pair)
+// (A2 / the *_2 arrays: optional second struct sharing the plan -- the sp part of an ap[dp_sp] pair; A3 / *_3 a third -- the hp part of
+//  ap[dp_sp_hp])
 int launch_plan_count(const uspmv_dmat *A, long n_tiles, int max_lines, int *d_n_lines, int *d_max_col, hipStream_t st,
-                      const uspmv_dmat *A2 = nullptr, int tile_rows = 256);                                               // plan_kernels.hip
+                      const uspmv_dmat *A2 = nullptr, int tile_rows = 256, const uspmv_dmat *A3 = nullptr);                 // plan_kernels.hip
 int launch_plan_pack12(const uspmv_dmat *A, const unsigned *d_c16_ptrs, const unsigned short *d_col16, const unsigned *d_c12_ptrs, unsigned *d_col12, hipStream_t st);   // plan_kernels.hip
 int launch_plan_write(const uspmv_dmat *A, long n_tiles, const int *d_tile_line_ptr, const unsigned *d_c16_ptrs, int *d_tile_lines,
                       unsigned short *d_col16, hipStream_t st, const uspmv_dmat *A2 = nullptr, const unsigned *d_c16_ptrs2 = nullptr,
-                      unsigned short *d_col16_2 = nullptr, int tile_rows = 256);                                           // plan_kernels.hip
+                      unsigned short *d_col16_2 = nullptr, int tile_rows = 256, const uspmv_dmat *A3 = nullptr,
+                      const unsigned *d_c16_ptrs3 = nullptr, unsigned short *d_col16_3 = nullptr);                         // plan_kernels.hip
 int launch_rechunk32(const uspmv_dmat *A, const int *d_cp_new, int *d_ci_new, void *d_va_new, hipStream_t st);             // plan_kernels.hip
 int launch_block_values_gather(const uspmv_dmat *A, const int *d_row_map, const unsigned *d_c16_ptrs, void *d_out, bool group_major, hipStream_t st);   // plan_kernels.hip
 // device-side builder of the phased block plan (block_plan_kernels.hip)

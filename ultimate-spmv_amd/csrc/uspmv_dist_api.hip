@@ -778,6 +778,7 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     if (halo->P != P || halo->rank != rank) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: halo description belongs to another partition");
     if (halo->n_local > 0 && !old_to_new_idx) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: NULL permutation");
     if (int rc = uspmv_dev::check_dmat(A, "uspmv_dist_create")) return rc;
+    if (A->dtype == USPMV_F16) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_create: fp16 handle (no one-precision fp16 SpMV)");
     if (int rc = uspmv_dev::require_device()) return rc;
     auto *D = new uspmv_dist;
     D->rank = rank; D->P = P; D->comm_rank = comm_rank; D->comm_size = comm_size; D->loopback = comm_size == 1 && P > 1;   // (host: comm_size == P)
@@ -872,6 +873,7 @@ int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_s
                                   uspmv_dist_t **out) {
     if (!local || !wsa || !out) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create_from_coo: NULL argument");
     if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create_from_coo: bad rank / P");
+    if (dtype != USPMV_F64 && dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create_from_coo: unknown dtype %d", dtype);
     // every rank sees the whole work_sharing_arr: a block without rows is refused HERE, by all ranks alike, before the first collective
     // (the conversion of that block would fail on its rank alone and leave the others waiting in the set-up exchange)
     for (int p = 0; p < P; ++p)

@@ -229,6 +229,7 @@ int uspmv_scs_classify_chunks(const uspmv_scs_t *s, int64_t n_local, std::vector
     const bool dp = s->dtype == USPMV_F64;
     auto pos_zero = [&](int64_t k) -> bool {
         if (dp) { uint64_t b; memcpy(&b, &s->values_f64[(size_t)k], 8); return b == 0; }
+        if (s->dtype == USPMV_F16) return s->values_f16[(size_t)k] == 0;
         uint32_t b; memcpy(&b, &s->values_f32[(size_t)k], 4); return b == 0;
     };
     // the padding column: the lowest halo column that carries a +0.0 entry

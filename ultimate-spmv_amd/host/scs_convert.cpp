@@ -22,6 +22,53 @@
 
 #include "uspmv_internal.hpp"
 
+// binary16 from a double in ONE rounding step (to nearest, ties to even), with integer operations on the bits (the host compiler has no
+// _Float16 here): subnormal results kept, overflow to +-inf, -0.0 kept, NaN -> quiet NaN with the top mantissa bits (numpy's
+// npy_doublebits_to_halfbits, so that the result equals numpy's float64 -> float16 bit for bit).
+uint16_t uspmv_f64_to_f16(double v) {
+    uint64_t b;
+    std::memcpy(&b, &v, 8);
+    const uint16_t sign = (uint16_t)((b >> 48) & 0x8000u);
+    const int e = (int)((b >> 52) & 0x7FF);
+    const uint64_t m = b & 0xFFFFFFFFFFFFFull;
+    if (e == 0x7FF) {
+        if (m == 0) return (uint16_t)(sign | 0x7C00u);
+        const uint16_t q = (uint16_t)(m >> 42);
+        return (uint16_t)(sign | 0x7C00u | (q ? q : 1u));
+    }
+    const int E = e - 1023;
+    if (E >= 16) return (uint16_t)(sign | 0x7C00u);                   // |v| >= 65536: beyond every rounding to 65504
+    if (e == 0 || E < -26) return sign;                                // below half the smallest subnormal (2^-25): +-0
+    uint64_t q, rem, half;
+    if (E >= -14) {                                                    // normal: 10 mantissa bits kept, 42 rounded away
+        q = ((uint64_t)(E + 15) << 10) | (m >> 42);
+        rem = m & ((1ull << 42) - 1); half = 1ull << 41;
+    } else {                                                           // subnormal: units of 2^-24
+        const uint64_t M = m | (1ull << 52);
+        const int sh = 28 - E;                                         // 43 .. 54
+        q = M >> sh;
+        rem = M & ((1ull << sh) - 1); half = 1ull << (sh - 1);
+    }
+    if (rem > half || (rem == half && (q & 1))) ++q;                   // a carry moves into the exponent (0x7BFF + 1 = inf)
+    return (uint16_t)(sign | q);
+}
+
+double uspmv_f16_to_f64(uint16_t h) {
+    const uint64_t sign = (uint64_t)(h & 0x8000u) << 48;
+    const int e = (h >> 10) & 0x1F;
+    const uint64_t m = h & 0x3FFu;
+    uint64_t b;
+    if (e == 0x1F) b = sign | (0x7FFull << 52) | (m << 42);
+    else if (e == 0) {
+        const double v = std::ldexp((double)m, -24);
+        std::memcpy(&b, &v, 8);
+        b |= sign;
+    } else b = sign | ((uint64_t)(e - 15 + 1023) << 52) | (m << 42);
+    double v;
+    std::memcpy(&v, &b, 8);
+    return v;
+}
+
 // Everything of convert_to_scs except the O(nnz) scatter: row lengths, sigma-window sort (or the
 // fixed permutation), chunk lengths / pointers, both permutations.  `s` comes back with empty
 // col_idxs / values ("layout-only").  row_start (n_rows + 1 offsets into the COO arrays) is filled
@@ -29,7 +76,7 @@
 int uspmv_scs_layout(const uspmv_coo_t *m, int64_t C, int64_t sigma, int dtype, const int32_t *fixed_permutation,
                      uspmv_scs *s, std::vector<int64_t> *row_start, const char *who) {
     if (C < 1 || sigma < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: C and sigma must be >= 1", who);
-    if (dtype != USPMV_F64 && dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+    if (dtype != USPMV_F64 && dtype != USPMV_F32 && dtype != USPMV_F16) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
     if (m->n_rows < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: matrix has no rows", who);
 
     const int64_t n_rows = m->n_rows, nnz = m->nnz;
@@ -147,7 +194,8 @@ int uspmv_convert_to_scs(const uspmv_coo_t *m, int64_t C, int64_t sigma, int dty
     // ---- fill, preserving the COO order inside every row
     s->col_idxs.assign((size_t)cur, 0);  // padding: column 0 (code/utilities.hpp:1991-2002)
     if (dtype == USPMV_F64) s->values_f64.assign((size_t)cur, 0.0);
-    else s->values_f32.assign((size_t)cur, 0.0f);
+    else if (dtype == USPMV_F32) s->values_f32.assign((size_t)cur, 0.0f);
+    else s->values_f16.assign((size_t)cur, 0);
 
     const int32_t *row_map = fixed_permutation ? fixed_permutation : s->old_to_new_idx.data();
     int bad = 0;
@@ -158,7 +206,8 @@ int uspmv_convert_to_scs(const uspmv_coo_t *m, int64_t C, int64_t sigma, int dty
         int64_t idx = (int64_t)s->chunk_ptrs[(size_t)c] + slot * C + row % C;
         s->col_idxs[(size_t)idx] = m->J[(size_t)k];
         if (dtype == USPMV_F64) s->values_f64[(size_t)idx] = m->values[(size_t)k];
-        else s->values_f32[(size_t)idx] = (float)m->values[(size_t)k];
+        else if (dtype == USPMV_F32) s->values_f32[(size_t)idx] = (float)m->values[(size_t)k];
+        else s->values_f16[(size_t)idx] = uspmv_f64_to_f16(m->values[(size_t)k]);
     };
     if (!row_start.empty()) {
 #pragma omp parallel for schedule(static)
@@ -289,6 +338,37 @@ int uspmv_partition_precisions(const uspmv_coo_t *m, double threshold_1, uspmv_c
     }
     d->nnz = (int64_t)d->values.size(); s->nnz = (int64_t)s->values.size();
     *dp = d; *sp = s;
+    return USPMV_OK;
+}
+
+int uspmv_partition_precisions_hp(const uspmv_coo_t *m, int kind, double threshold_1, double threshold_2, uspmv_coo_t **hi,
+                                  uspmv_coo_t **mid, uspmv_coo_t **hp) {
+    // partition_precisions of the library API (code/interface.hpp:691-987), non-equilibrated branch, with the parts' values stored as doubles
+    // holding the rounded value (as uspmv_partition_precisions stores its sp part)
+    const bool three = kind == USPMV_AP_DP_SP_HP;
+    if (!m || !hi || !hp || (three && !mid)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_partition_precisions_hp: NULL argument");
+    if (kind != USPMV_AP_DP_HP && kind != USPMV_AP_SP_HP && !three)
+        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_partition_precisions_hp: unknown kind %d", kind);
+    auto *a = new uspmv_coo, *b = three ? new uspmv_coo : nullptr, *h = new uspmv_coo;
+    for (uspmv_coo *p : {a, b, h})
+        if (p) { p->n_rows = m->n_rows; p->n_cols = m->n_cols; }
+    auto put = [&](uspmv_coo *p, int64_t k, double v) {
+        p->I.push_back(m->I[(size_t)k]); p->J.push_back(m->J[(size_t)k]); p->values.push_back(v);
+    };
+    for (int64_t k = 0; k < m->nnz; ++k) {
+        const double v = m->values[(size_t)k], av = std::fabs(v);
+        if (av >= threshold_1) put(a, k, kind == USPMV_AP_SP_HP ? (double)(float)v : v);
+        else if (three && av <= threshold_1 && av >= threshold_2) put(b, k, (double)(float)v);
+        else if (three || av < threshold_1) put(h, k, uspmv_f16_to_f64(uspmv_f64_to_f16(v)));   // (ap[dp_sp_hp]: the else, NaN included)
+        else {  // NaN fits neither part of a two-part split
+            delete a; delete h;
+            return uspmv::fail(USPMV_ERR_INVALID, "uspmv_partition_precisions_hp: element %lld fits neither struct", (long long)k);
+        }
+    }
+    for (uspmv_coo *p : {a, b, h})
+        if (p) p->nnz = (int64_t)p->values.size();
+    *hi = a; *hp = h;
+    if (mid) *mid = b;
     return USPMV_OK;
 }
 

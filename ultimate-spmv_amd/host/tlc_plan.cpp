@@ -22,9 +22,10 @@
 
 #include "uspmv_internal.hpp"
 
-int uspmv_build_tlc_plan(const uspmv_scs *s, const uspmv_scs *s2, int max_lines, int tile_rows, uspmv_tlc_plan *p, int line_shift) {
-    // s2 (optional): a second struct with the same row layout (the sp part of an ap[dp_sp] pair);
-    // the line list of a tile then covers the columns of both, each struct gets its own col16.
+int uspmv_build_tlc_plan(const uspmv_scs *s, const uspmv_scs *s2, int max_lines, int tile_rows, uspmv_tlc_plan *p, int line_shift,
+                         const uspmv_scs *s3) {
+    // s2, s3 (optional): further structs with the same row layout (the sp part of an ap[dp_sp] pair; the mid and hp parts of an
+    // ap split with an fp16 part); the line list of a tile then covers the columns of all of them, each struct gets its own col16.
     p->valid = false;
     const int64_t C = s->C;
     // line_shift: log2 of the elements per line -- 4 (16-element lines) for SpMV; 0 for the block-vector
@@ -35,6 +36,7 @@ int uspmv_build_tlc_plan(const uspmv_scs *s, const uspmv_scs *s2, int max_lines,
     if (tile_rows != 32 && tile_rows != 64 && tile_rows != 128 && tile_rows != 256 && tile_rows != 512 && tile_rows != 1024) tile_rows = 256;
     if (C < 1 || C > tile_rows || tile_rows % C != 0 || s->n_chunks < 1) return USPMV_OK;  // unsupported shape: no plan
     if (s2 && (s2->C != C || s2->n_chunks != s->n_chunks)) return USPMV_OK;
+    if (s3 && (!s2 || s3->C != C || s3->n_chunks != s->n_chunks)) return USPMV_OK;
     if (max_lines < 1) return USPMV_OK;
     if (max_lines > (65536 >> LS)) max_lines = 65536 >> LS;  // 16-bit local indices
     p->line_shift = LS;
@@ -43,10 +45,10 @@ int uspmv_build_tlc_plan(const uspmv_scs *s, const uspmv_scs *s2, int max_lines,
     const int64_t n_tiles = (s->n_chunks + T - 1) / T;
     p->chunks_per_tile = (int)T;
     p->n_tiles = n_tiles;
-    const uspmv_scs *ss[2] = {s, s2};
-    std::vector<uint32_t> *ptrs[2] = {&p->c16_ptrs, &p->c16_ptrs_b};
-    std::vector<uint16_t> *c16[2] = {&p->col16, &p->col16_b};
-    const int ns = s2 ? 2 : 1;
+    const uspmv_scs *ss[3] = {s, s2, s3};
+    std::vector<uint32_t> *ptrs[3] = {&p->c16_ptrs, &p->c16_ptrs_b, &p->c16_ptrs_c};
+    std::vector<uint16_t> *c16[3] = {&p->col16, &p->col16_b, &p->col16_c};
+    const int ns = s3 ? 3 : s2 ? 2 : 1;
     for (int w = 0; w < ns; ++w) {
         ptrs[w]->assign((size_t)s->n_chunks + 1, 0);
         int64_t tot16 = 0;

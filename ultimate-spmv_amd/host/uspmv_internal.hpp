@@ -43,10 +43,17 @@ struct uspmv_scs {
     std::vector<int32_t> chunk_ptrs, chunk_lengths, col_idxs, old_to_new_idx, new_to_old_idx;
     std::vector<double> values_f64;
     std::vector<float> values_f32;
+    std::vector<uint16_t> values_f16;     // USPMV_F16: binary16 bits
     const void *values_ptr() const {
-        return dtype == USPMV_F64 ? (const void *)values_f64.data() : (const void *)values_f32.data();
+        return dtype == USPMV_F64 ? (const void *)values_f64.data()
+             : dtype == USPMV_F32 ? (const void *)values_f32.data() : (const void *)values_f16.data();
     }
 };
+// bytes per value of a dtype
+inline size_t uspmv_dtype_bytes(int dtype) { return dtype == USPMV_F64 ? 8 : dtype == USPMV_F32 ? 4 : 2; }
+// binary16 <-> double (host/scs_convert.cpp): one round-to-nearest-even step from the double, bit-equal to numpy's float64 -> float16
+uint16_t uspmv_f64_to_f16(double v);
+double uspmv_f16_to_f64(uint16_t h);
 
 // Per-rank halo description (role of ContextData, code/classes_structs.hpp:156-184).
 struct uspmv_halo {
@@ -93,8 +100,11 @@ struct uspmv_tlc_plan {
     std::vector<uint16_t> col16;          // [chunk][slot/4][row][slot%4]
     std::vector<uint32_t> c16_ptrs_b;     // same for the optional second struct (sp part of an ap pair)
     std::vector<uint16_t> col16_b;
+    std::vector<uint32_t> c16_ptrs_c;     // ... and the optional third (the hp part of ap[dp_sp_hp])
+    std::vector<uint16_t> col16_c;
 };
-int uspmv_build_tlc_plan(const uspmv_scs *s, const uspmv_scs *s2, int max_lines, int tile_rows, uspmv_tlc_plan *plan, int line_shift = 4);
+int uspmv_build_tlc_plan(const uspmv_scs *s, const uspmv_scs *s2, int max_lines, int tile_rows, uspmv_tlc_plan *plan, int line_shift = 4,
+                         const uspmv_scs *s3 = nullptr);
 
 // Column-window sweep plan (host copy), see host/sweep_plan.cpp
 struct uspmv_sweep_plan {

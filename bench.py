@@ -3,8 +3,13 @@
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
   python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    (+ y of the last timed step as DIR/*.npy)
+  python bench.py --gpus 1 --steps K --warmup W --full   (+ everything beyond the headline, see below)
 
 A "step" is one SpMV y = A x over the whole (distributed) matrix, inputs resident in HBM.
+At N = 1 a plain run does only what the headline needs: set-up, the kernel's 100 launches that bring the GPU out of the power state
+the set-up left it in (untimed), W warm-up steps, K timed steps, the --dump-outputs files, the line.  --full adds the rest of the line:
+HBM traffic by rocprofv3 PMC passes, the checked launch against the reference CPU kernel, the HIP-event kernel time and roofline, GPU
+state, y placement, stream yardsticks, CPU and rocSPARSE baselines and the other configurations (--other-configs).
 Workload at N = 1 (BASELINE.json configs[1]): nlpkkt200-class matrix -- the SuiteSparse file is not
 available offline, so the deterministic stand-in of SURVEY.md 8(d) is used: 27-point stencil on a
 253^3 grid (n = 16 194 277, nnz = 4.33e8), `uspmv <mtx> scs -c 32 -s 512 -dp`.  A real .mtx can be
@@ -62,13 +67,16 @@ def parse():
     ap.add_argument("--seg", choices=["seg-nnz", "seg-rows"], default="seg-nnz")
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="N > 1: eager C++ steps in the uspmv children")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vendor-baseline", action="store_true", help="N = 1: skip the rocSPARSE child process")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--full", action="store_true", help="N = 1: measure and check everything beyond the headline too (roofline with HBM traffic, GPU state, "
+                                                        "CPU and rocSPARSE baselines, other configurations); without it the run does only what value and "
+                                                        "ms_per_step need.  N > 1 runs are the same with or without it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N = 1: skip the reference CPU kernel")
+    ap.add_argument("--no-vendor-baseline", action="store_true", help="--full, N = 1: skip the rocSPARSE child process")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full, N = 1: seconds of the headline's CPU baseline (a third of it per other configuration)")
     ap.add_argument("--tune", default="", help="key=value,... forwarded to uspmv_set_tuning")
     ap.add_argument("--no-tlc", action="store_true", help="skip the tile-local-column plan (plain gather kernel)")
-    ap.add_argument("--no-traffic", action="store_true", help="N = 1: do not run the two rocprofv3 PMC child passes (roofline.traffic then comes from profiles/traffic.json)")
-    ap.add_argument("--other-configs", default="3,4b,2k,3s,5one", help="N = 1: further configurations measured after the headline and reported under \"other_configs\" (3 = Queen_4147-class SpMMV b = 8, both layouts; 4b = HV15R-class ap[dp_sp] and dp; 2k = nlpkkt200-class KKT matrix; 3s = the Queen-class stencil in a numbering scrambled inside blocks of 20 000 nodes, SpMV; 5one = config 5's 304^3 matrix on one GPU); \"\" = none")
+    ap.add_argument("--no-traffic", action="store_true", help="--full, N = 1: do not run the two rocprofv3 PMC child passes (roofline.traffic then comes from profiles/traffic.json)")
+    ap.add_argument("--other-configs", default="3,4b,2k,3s,5one", help="--full, N = 1: further configurations measured after the headline and reported under \"other_configs\" (3 = Queen_4147-class SpMMV b = 8, both layouts; 4b = HV15R-class ap[dp_sp] and dp; 2k = nlpkkt200-class KKT matrix; 3s = the Queen-class stencil in a numbering scrambled inside blocks of 20 000 nodes, SpMV; 5one = config 5's 304^3 matrix on one GPU); \"\" = none")
     ap.add_argument("--kkt", type=int, default=200, help="config 2k: grid edge N of uspmv_gen_kkt")
     ap.add_argument("--grid5", type=int, default=304, help="config 5one: stencil grid edge")
     ap.add_argument("--grid3", type=int, default=111, help="config 3: nodes per edge (3 dof per node)")
@@ -1118,7 +1126,7 @@ def main():
         return dist_bench(args, pkg, world, 0 if self_launch else rank, self_launch, "library defaults (the uspmv rank processes)")
 
     traffic, traffic_note = None, "not measured"
-    if not args.mtx and not args.no_traffic:
+    if args.full and not args.mtx and not args.no_traffic:
         traffic, traffic_note = measure_traffic(args)      # child processes under rocprofv3, BEFORE this process touches the GPU
     import torch
     import __graft_entry__ as ge
@@ -1156,24 +1164,30 @@ def main():
     bytes_local = s.n_elements * 12 + 8 * s.n_chunks + 8 * s.n_rows + 8 * s.n_rows_padded
     t_setup = time.time() - t_setup
 
-    # ------------------------------------------------------------------ one checked launch on a NON-uniform x (a constant would hide a permutation
-    #                                                                    error): its y is compared bitwise with the CPU kernel's further down
-    x_check = np.zeros(s.n_rows_padded)
-    x_check[:s.n_rows] = pkg.apply_permutation(1.0 + 1e-3 * (np.arange(s.n_rows) % 1000), a["new_to_old_idx"])
-    xc = torch.from_numpy(x_check).to(dev)
-    B.spmv(A, xc, y)
-    torch.cuda.synchronize(dev)
-    y_gpu_check = y.cpu().numpy().copy()
-    del xc
-    card = card_of_device(torch, local_rank)
-    state_idle = gpu_state(card)
+    if args.full:
+        # -------------------------------------------------------------- one checked launch on a NON-uniform x (a constant would hide a permutation
+        #                                                                error): its y is compared bitwise with the CPU kernel's further down
+        x_check = np.zeros(s.n_rows_padded)
+        x_check[:s.n_rows] = pkg.apply_permutation(1.0 + 1e-3 * (np.arange(s.n_rows) % 1000), a["new_to_old_idx"])
+        xc = torch.from_numpy(x_check).to(dev)
+        B.spmv(A, xc, y)
+        torch.cuda.synchronize(dev)
+        y_gpu_check = y.cpu().numpy().copy()
+        del xc
+        card = card_of_device(torch, local_rank)
+        state_idle = gpu_state(card)
 
     # ------------------------------------------------------------------ dominant kernel, HIP events on its stream (first: 100 launches also bring
-    #                                                                    the GPU out of the power state the host-side set-up left it in)
+    #                                                                    the GPU out of the power state the host-side set-up left it in, DESIGN
+    #                                                                    9.1; a plain run makes the same launches for that alone, so that its
+    #                                                                    timed steps start from the same state)
     reps = 100
-    with GpuStateSampler(card) as smp:
-        k_ms = B.time_launches(0, reps, A=A, x=x, y=y)
-    state_load = smp.summary()
+    if args.full:
+        with GpuStateSampler(card) as smp:
+            k_ms = B.time_launches(0, reps, A=A, x=x, y=y)
+        state_load = smp.summary()
+    else:
+        B.time_launches(0, reps, A=A, x=x, y=y)
 
     # ------------------------------------------------------------------ timed region: W warm-up steps, then EXACTLY K steps
     for _ in range(args.warmup):
@@ -1188,6 +1202,23 @@ def main():
     gflops = 2.0 * total_nnz / (ms_per_step * 1e-3) / 1e9
     if args.dump_outputs:                         # before anything else writes into y
         dump_outputs(args.dump_outputs, y, s.arrays()["old_to_new_idx"], s.n_rows)
+    kind, n_tiles, n_planned = A.plan_info()
+    out = {
+        "metric": "SpMV GFLOP/s (SELL-32-512 dp; achieved HBM GB/s in roofline)",
+        "value": round(gflops, 2), "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": None, "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic" if not args.mtx else "file",
+        "config": {"workload": workload, "C": args.chunk, "sigma": args.sigma, "n_rows": n_global, "nnz": total_nnz,
+                   "beta": round(s.nnz / s.n_elements, 6), "x": "5.0 (DefaultValues)", "partition": "none", "halo_overlap": False,
+                   "kernel": {0: "lane-per-row gather", 1: f"tile-local-column (LDS-staged x lines, {A.index_bits()}-bit local indices)",
+                              2: "column-window sweep (LDS-staged x windows, compacted stream)"}[kind],
+                   "plan_tiles_planned": [n_planned, n_tiles], "tuning": tuning},
+        "setup_s": round(t_setup, 1),
+    }
+    if not args.full:
+        out["order"] = "set-up, the kernel's 100 launches (untimed), W warm-up steps, K timed steps (--full: the whole line)"
+        print(json.dumps(out), flush=True)
+        return 0
 
     # ------------------------------------------------------------------ what y's placement alone is worth in THIS process: the same
     #                                                                    kernel, matrix and x, four more output vectors (fresh allocations, all held)
@@ -1206,7 +1237,6 @@ def main():
     achieved = bytes_local / (k_ms * 1e-3) / 1e9
     g_ = args.grid or 253
     stream = stream_rates(B, torch, dev, x_elems=0 if args.mtx else s.n_rows, plane=g_ * g_, line=g_)
-    kind, n_tiles, n_planned = A.plan_info()
     kname = {0: "scs_spmv_rows<double,32,8>", 1: "scs_spmv_tlc<double,32>", 2: "scs_spmv_sweep<double>"}[kind if pkg.get_tuning("tlc") else 0]
     if traffic is None and not args.mtx:
         key = f"stencil27-{args.grid or 253}x{args.grid or 253}x{args.grid or 253}-c{args.chunk}-s{args.sigma}-f64-n1"
@@ -1215,29 +1245,17 @@ def main():
             traffic_note = f"NOT measured in this run ({traffic_note}); value from profiles/traffic.json (rocprofv3 PMC passes of an earlier run of this command)"
         except (OSError, ValueError):
             traffic = None
-    out = {
-        "metric": "SpMV GFLOP/s (SELL-32-512 dp; achieved HBM GB/s in roofline)",
-        "value": round(gflops, 2), "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": None, "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic" if not args.mtx else "file",
-        "config": {"workload": workload, "C": args.chunk, "sigma": args.sigma, "n_rows": n_global, "nnz": total_nnz,
-                   "beta": round(s.nnz / s.n_elements, 6), "x": "5.0 (DefaultValues)", "partition": "none", "halo_overlap": False,
-                   "kernel": {0: "lane-per-row gather", 1: f"tile-local-column (LDS-staged x lines, {A.index_bits()}-bit local indices)",
-                              2: "column-window sweep (LDS-staged x windows, compacted stream)"}[kind],
-                   "plan_tiles_planned": [n_planned, n_tiles], "tuning": tuning},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": traffic, "traffic_source": traffic_note,
-                     "achieved_physical": None if not traffic else round(traffic / (k_ms * 1e-3) / 1e9, 1),
-                     "frac_physical": None if not traffic else round(traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                     "kernel": kname, "kernel_ms": round(k_ms, 5),
-                     "algorithmic_bytes_per_launch": int(bytes_local),
-                     "note": "achieved/frac = algorithmic bytes (SURVEY 8d formula, 12 B per non-zero) / kernel time; achieved_physical/frac_physical = "
-                             "HBM bytes really moved (PMC) / kernel time -- the plan kernels stream 10 B per non-zero",
-                     "stream_same_run_GBs": stream,
-                     "frac_physical_of_stream_read": None if not traffic else round(traffic / (k_ms * 1e-3) / 1e9 / stream["read"], 4)},
-        "setup_s": round(t_setup, 1),
-    }
+    out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(achieved / HBM_PEAK_GBS, 4),
+                       "traffic": traffic, "traffic_source": traffic_note,
+                       "achieved_physical": None if not traffic else round(traffic / (k_ms * 1e-3) / 1e9, 1),
+                       "frac_physical": None if not traffic else round(traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                       "kernel": kname, "kernel_ms": round(k_ms, 5),
+                       "algorithmic_bytes_per_launch": int(bytes_local),
+                       "note": "achieved/frac = algorithmic bytes (SURVEY 8d formula, 12 B per non-zero) / kernel time; achieved_physical/frac_physical = "
+                               "HBM bytes really moved (PMC) / kernel time -- the plan kernels stream 10 B per non-zero",
+                       "stream_same_run_GBs": stream,
+                       "frac_physical_of_stream_read": None if not traffic else round(traffic / (k_ms * 1e-3) / 1e9 / stream["read"], 4)}
     out["gpu_state"] = {"idle_before_timing": state_idle, "during_the_kernel_timing": state_load,
                         "note": "amdgpu sysfs (pp_dpm_* active levels, hwmon sensors in their native units: microwatts, millidegrees, Hz), read only"}
     out["y_placement"] = placement

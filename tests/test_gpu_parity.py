@@ -261,7 +261,7 @@ def C_tile_rows(pkg, A):
 
 def test_tile_rows_follow_the_lines_a_tile_needs(pkg, orc, torch_cuda):
     """uspmv_dmat_optimize[_device] with tlc_tile_rows 0: 256-row tiles, unless the largest of them needs more than 250 x lines and
-    1024-row (or 512-row) tiles still stage >= 99 % of the tiles (csrc/uspmv_api.hip tile_rows_grow).  Host and device planners take the
+    1024-row (or 512-row) tiles still stage >= 99 % of the tiles (csrc/tlc_planner.hip tile_rows_grow).  Host and device planners take the
     same decision and build the same arrays; y has the reference's bits whatever the tile size; tlc_auto_tile 0 keeps 256."""
     t = torch_cuda
     for gen, want in ((lambda: pkg.gen_banded_random(40000, 30, 2000), 1024),      # ~270 lines per 256-row tile, ~320 per 1024-row tile
@@ -324,7 +324,7 @@ def test_device_plan_builder_far_apart_column_clusters(pkg, orc, torch_cuda):
 
 def test_measured_tile_rows_on_a_large_struct(pkg, orc, torch_cuda):
     """Structs of >= 2^20 padded rows: the rows per tile are measured (plans for 256 / 512 / 1024 rows built on the device, the kernel timed,
-    a larger tile kept when > 3 % ahead; uspmv_api.hip measured_tile_rows).  Whatever wins, the host and the device planner of the same
+    a larger tile kept when > 3 % ahead; tlc_planner.hip measured_tile_rows).  Whatever wins, the host and the device planner of the same
     matrix agree (the choice is remembered per shape), the plans are identical, y has the reference's bits; "tlc_measure_tile" 0 gives the
     rule-based 256 rows."""
     t = torch_cuda

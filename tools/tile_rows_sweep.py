@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Rows per tile of the tile-local-column plan (256 | 512 | 1024) against kernel time, per matrix class -- the data behind the
-rule in csrc/uspmv_api.hip (plan_tile_rows).  One line per (matrix, tile_rows): lines staged, the largest tile, kernel ms."""
+rule in csrc/tlc_planner.hip (plan_tile_rows).  One line per (matrix, tile_rows): lines staged, the largest tile, kernel ms."""
 import argparse
 import json
 import os

@@ -509,7 +509,7 @@ int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, cons
     const unsigned grid = (unsigned)n_tiles;
     const bool elem = A->tlc.elem;
     const size_t lds = (size_t)A->tlc.max_lines * (elem ? 1 : 16) * sizeof(VT);
-    const bool i12 = A->tlc.col12 != nullptr;                 // (12-bit local indices: uspmv_api.hip tlc_pack12)
+    const bool i12 = A->tlc.col12 != nullptr;                 // (12-bit local indices: tlc_planner.hip tlc_pack12)
     const unsigned *iptrs = i12 ? A->tlc.c12_ptrs : A->tlc.c16_ptrs;
     const unsigned short *idata = i12 ? (const unsigned short *)A->tlc.col12 : A->tlc.col16;
 #define TLC_LAUNCH(CTV, NTV, IDSV)                                                                                    \

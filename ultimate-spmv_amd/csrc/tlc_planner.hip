@@ -1,0 +1,649 @@
+// The SpMV planner: uspmv_dmat_optimize and its variants (one struct, the ap[dp_sp] pair, the splits with an fp16 part; from a host
+// struct through host/tlc_plan.cpp or from the handle's device arrays through plan_kernels.hip).  Every decision between the plans
+// -- the line budget, the rows per tile, when the element plan or the column-window sweep takes over -- is written once here, so the host
+// and the device planner of one matrix cannot drift apart (tests/test_gpu_parity.py compares their plans array for array).
+#include "uspmv_device.hpp"
+
+#include <mutex>
+
+using namespace uspmv_dev;
+
+namespace {
+
+bool verbose() {
+    static const bool on = getenv("USPMV_VERBOSE") != nullptr;
+    return on;
+}
+
+// Most x lines (of 16 values) a tile may list.  The caller's wish, 512 when it has none (64 KiB of doubles: 2 workgroups per CU at worst)
+// -- the term that binds by default.  A larger wish stops at what 160 KiB of LDS hold in the value type of the first part (1280 lines of
+// doubles, 2560 of floats), and a plan shared by the parts of an ap split at 1280 whatever that type is (binds for a float first part).
+// 4096 lines x 16 values are all that a 16-bit local index can address: below the LDS term for both types, so it never binds.
+int line_budget(int max_lines, int dtype_of_first_part, bool shared) {
+    const int lds = (int)(160 * 1024 / (16 * (dtype_of_first_part == USPMV_F64 ? 8 : 4)));
+    return std::min({max_lines <= 0 ? 512 : max_lines, lds, shared ? 1280 : 4096});
+}
+
+// rows per tile of the next tile-local-column plan (g_tune.tlc_tile_rows = 0: by kind)
+int plan_tile_rows(bool ap) { return g_tune.tlc_tile_rows ? g_tune.tlc_tile_rows : (ap ? 512 : 256); }
+
+// Rows per tile by what the 256-row plan turned out to be (tuning tlc_auto_tile, default on; only when tlc_tile_rows is 0).  The x lines
+// of a tile live in LDS (128 B each): when the largest 256-row tile needs more than 250 of them, at most 4 workgroups = 16 waves fit a
+// CU, too few to cover the staging latency, and every line is fetched by several neighbouring tiles.  1024-row tiles (or 512-row ones)
+// fetch each line fewer times and keep 32 (16) waves per CU when their lines still fit; they are taken when they stage >= 99 % of the
+// tiles.  Measured (tools/tile_rows_sweep.py, profiles/r03/tile_rows_sweep.txt): KKT N = 200 0.82 -> 0.73 ms, banded 30 per row over
+// +-2000 columns 0.27 -> 0.22 ms; matrices whose 256-row tiles need <= 217 lines (all the stencils) are fastest at 256 and stay there.
+bool tile_rows_grow(int rows, int lines_used) { return g_tune.tlc_auto_tile && g_tune.tlc_tile_rows == 0 && rows == 256 && lines_used > 250; }
+bool tile_rows_accept(int64_t n_tiles, int64_t n_staged) { return n_staged * 100 >= n_tiles * 99; }
+
+// How much of a plan stages, by the thresholds the decisions below use: a line plan under nine tenths leaves "a tenth of the tiles or more
+// to the gather path" (the element plans are tried); 19 of 20 is enough for the plan on dealt rows (what would run instead is 2 x
+// slower); under half, the column-window sweep is tried, and a shared plan with an fp16 part is not worth keeping.
+bool stages_nine_tenths(int64_t n_tiles, int64_t n_staged) { return n_staged * 10 >= n_tiles * 9; }
+bool stages_19_of_20(int64_t n_tiles, int64_t n_staged) { return n_staged * 20 >= n_tiles * 19; }
+bool stages_half(int64_t n_tiles, int64_t n_staged) { return n_staged * 2 >= n_tiles; }
+// shared plans of the two or three parts of a split with an fp16 part: the line plan where it stages at least half of the tiles, otherwise
+// none (no sweep for hp parts)
+bool ap_hp_plan_worth(int64_t n_tiles, int64_t n_staged) { return n_staged > 0 && stages_half(n_tiles, n_staged); }
+
+// the internal C = 32 re-chunking of a narrow struct is taken when its padding stays within a quarter (+ 4096) of the entries
+bool rechunk_worth(int64_t new_elements, int64_t old_elements) {
+    return (double)new_elements <= 1.25 * (double)std::max<int64_t>(old_elements, 1) + 4096;
+}
+
+// what a plan built at some rows per tile turned out to be
+struct PlanStats {
+    bool valid = false;
+    int64_t n_tiles = 0, n_staged = 0;
+    int lines = 0;                       // of the fullest tile
+};
+PlanStats stats_of(const uspmv_tlc_plan &p) { return {p.valid, p.n_tiles, p.n_staged_tiles, p.max_lines_used}; }
+
+// The rows per tile, for the host and the device planner alike: the measured verdict when there is one, else the default by kind, else --
+// when tile_rows_grow asks for it -- the first of 1024 and 512 rows that tile_rows_accept takes.  build(R, &stats) builds a candidate at R
+// rows, keep() makes the last candidate the plan; *st describes the plan kept.
+template <typename Build, typename Keep>
+int plan_at_chosen_rows(int R_meas, bool ap, Build build, Keep keep, PlanStats *st) {
+    const int R0 = R_meas ? R_meas : plan_tile_rows(ap);
+    if (int rc = build(R0, st)) return rc;
+    keep();
+    if (R_meas || !st->valid || !tile_rows_grow(R0, st->lines)) return USPMV_OK;
+    for (int R : {1024, 512}) {
+        PlanStats q;
+        if (int rc = build(R, &q)) return rc;
+        if (q.valid && tile_rows_accept(q.n_tiles, q.n_staged)) { keep(); *st = q; break; }
+    }
+    return USPMV_OK;
+}
+
+// The metadata every part of a plan carries.  Parts planned together share one non-zero id (the ap launchers check it); a single struct has 0.
+void stamp_plan(uspmv_dmat *const parts[3], int tile_rows, int max_lines, int64_t x_len, int64_t n_tiles, int64_t staged, bool elem) {
+    static uint64_t next_plan_id = 1;
+    const uint64_t id = parts[1] ? next_plan_id++ : 0;
+    for (int k = 0; k < 3; ++k) {
+        if (!parts[k]) continue;
+        auto &t = parts[k]->tlc;
+        t.on = true; t.elem = elem; t.tile_rows = tile_rows; t.max_lines = max_lines; t.x_len = x_len; t.n_tiles = n_tiles; t.staged = staged; t.plan_id = id;
+    }
+}
+
+// a host-built plan onto the handles: line list and local indices with the first part, the further parts their local indices only
+int install_host_plan(uspmv_dmat *const parts[3], const uspmv_tlc_plan &p, bool elem, const char *who) {
+    auto &t = parts[0]->tlc;
+    hipError_t e = t.line_ptr.upload(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4);
+    if (e == hipSuccess) e = t.lines.upload(p.tile_lines.data(), p.tile_lines.size() * 4);
+    const std::vector<uint32_t> *ptrs[3] = {&p.c16_ptrs, &p.c16_ptrs_b, &p.c16_ptrs_c};
+    const std::vector<uint16_t> *cols[3] = {&p.col16, &p.col16_b, &p.col16_c};
+    for (int k = 0; k < 3; ++k) {
+        if (!parts[k]) continue;
+        if (e == hipSuccess) e = parts[k]->tlc.c16_ptrs.upload(ptrs[k]->data(), ptrs[k]->size() * 4);
+        if (e == hipSuccess) e = parts[k]->tlc.col16.upload(cols[k]->data(), cols[k]->size() * 2);
+    }
+    if (e != hipSuccess) {
+        for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
+        return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
+    }
+    stamp_plan(parts, p.tile_rows, p.max_lines_used, p.x_len_min, p.n_tiles, p.n_staged_tiles, elem);
+    return USPMV_OK;
+}
+
+// Wide, irregular rows: most tiles touch too many x lines to stage them.  When the plan stages fewer than half of its tiles, try the
+// column-window sweep (from the host structs, or -- s == nullptr -- built on the device as well); *took: it covers at least half of its
+// tiles and stays on the handles.
+int sweep_takes_over(uspmv_dmat *A, uspmv_dmat *B, const uspmv_scs *s, const uspmv_scs *sB, const PlanStats &st, const char *who, bool *took) {
+    *took = false;
+    A->sw = {};
+    if (B) B->sw = {};
+    if (!g_tune.sweep || (st.valid && stages_half(st.n_tiles, st.n_staged))) return USPMV_OK;
+    int64_t swt = 0, sws = 0;
+    if (int rc = s ? sweep_plan_install(A, B, s, sB, 0, 0, &swt, &sws, who) : sweep_plan_install_device(A, B, 0, 0, &swt, &sws, who)) return rc;
+    *took = A->sw.on && stages_half(swt, sws);
+    if (!*took) { A->sw = {}; if (B) B->sw = {}; }
+    return USPMV_OK;
+}
+
+// The plan's local indices once more in 12 bits (single structs whose tiles list at most 256 lines, i.e. local indices below 4096; even C):
+// what scs_spmv_tlc then streams instead of the 16-bit array -- 1.5 instead of 2 bytes per non-zero.  The 16-bit array stays (the
+// adaptive-precision kernels, uspmv_dmat_plan_download and the plan digests read it).  cl: the chunk lengths when the caller has them on
+// the host, else they are copied back (4 bytes per chunk).
+int tlc_pack12(uspmv_dmat *A, const std::vector<int32_t> *cl, const char *who) {
+    if (!A->tlc.on || !g_tune.tlc_idx12 || (A->tlc.elem ? A->tlc.max_lines > 4096 : A->tlc.max_lines > 256) || A->C < 2 || A->C % 2 != 0 || A->n_chunks < 1) return USPMV_OK;
+    std::vector<int32_t> own;
+    if (!cl || (int64_t)cl->size() != A->n_chunks) {
+        own.resize((size_t)A->n_chunks);
+        HIP_TRY(hipMemcpy(own.data(), A->chunk_lengths, 4 * (size_t)A->n_chunks, hipMemcpyDeviceToHost));
+        cl = &own;
+    }
+    const int64_t C = A->C, nc = A->n_chunks;
+    std::vector<uint32_t> p12((size_t)nc + 1);
+    int64_t tot = 0;                                             // dwords
+    for (int64_t c = 0; c < nc; ++c) {
+        p12[(size_t)c] = (uint32_t)tot;
+        const int64_t ngt = ((int64_t)(*cl)[(size_t)c] + 3) / 4;
+        tot += (ngt / 2) * 3 * C + (ngt & 1) * (C + C / 2);
+        if (tot > (int64_t)UINT32_MAX) return USPMV_OK;          // (too large for 32-bit offsets: the 16-bit array serves)
+    }
+    p12[(size_t)nc] = (uint32_t)tot;
+    hipError_t e = A->tlc.c12_ptrs.upload(p12.data(), 4 * ((size_t)nc + 1));
+    if (e == hipSuccess) e = A->tlc.col12.alloc(4 * (size_t)std::max<int64_t>(tot, 1));
+    if (e == hipSuccess && launch_plan_pack12(A, A->tlc.c16_ptrs, A->tlc.col16, A->tlc.c12_ptrs, A->tlc.col12, nullptr) != USPMV_OK) e = hipErrorUnknown;
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        A->tlc.c12_ptrs.reset(); A->tlc.col12.reset();
+        return uspmv::fail(USPMV_ERR_HIP, "%s: packing the local indices to 12 bits failed: %s", who, hipGetErrorString(e));
+    }
+    // Keep it?  Rows of a dozen entries gain or lose a per cent either way (one more load instruction per row for an odd last group), long
+    // rows gain 1-15 % depending on matrix and box (profiles/r04/idx12_probe_*.txt: the 253^3 stencil 0.763 -> 0.691 ms on a slow box, 0.710 ->
+    // 0.700 on a fast one; 304^3 between -15 % and +2 %).  The rule is a fixed one -- mean row length >= 8 -- and not a timing on the spot
+    // (which was built first): a bench run, its counter passes and its profiler run must execute the same kernel, and a 1-2 % verdict
+    // flips under a profiler's overhead.  "tlc_idx12" 2 keeps it regardless, 0 never builds it.
+    if (g_tune.tlc_idx12 != 2 && (double)A->n_elements < 8.0 * (double)(nc * C)) { A->tlc.c12_ptrs.reset(); A->tlc.col12.reset(); }
+    return USPMV_OK;
+}
+
+// The tile-local-column plan of parts[0] at R rows per tile, built on the device; parts[1] (the sp part of an ap pair, or the hp part of a
+// two-part split) and parts[2] (the hp part of ap[dp_sp_hp]; only with parts[1]) share its line list.  No plan (and USPMV_OK) for shapes
+// without one, arrays beyond 32-bit offsets and matrices of which no tile stages.
+int device_plan_install_rows(uspmv_dmat *const parts[3], int max_lines, const int R, PlanStats *st, const char *who) {
+    uspmv_dmat *const A = parts[0], *const B = parts[1], *const B3 = parts[2];
+    for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
+    *st = {};
+    const int64_t C = A->C, nc = A->n_chunks;
+    if (C > 256 || 256 % C != 0 || nc < 1) return USPMV_OK;                    // shape without a plan
+    max_lines = line_budget(max_lines, A->dtype, B != nullptr);
+    const int64_t T = R / C, nt = (nc + T - 1) / T;
+    std::vector<int32_t> cl((size_t)nc);
+    std::vector<uint32_t> c16p[3];
+    int64_t tot16[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) {                                               // (a single struct: cl keeps its lengths for tlc_pack12)
+        if (!parts[k]) continue;
+        HIP_TRY(hipMemcpy(cl.data(), parts[k]->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
+        if (!c16_offsets(cl, C, &c16p[k], &tot16[k])) return USPMV_OK;
+    }
+    DeviceBuf<int> d_n, d_max;
+    hipError_t e = d_n.alloc(4 * (size_t)nt);
+    if (e == hipSuccess) e = d_max.zeros(4);
+    if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
+    int rc = launch_plan_count(A, (long)nt, max_lines, d_n, d_max, nullptr, B, R, B3);
+    std::vector<int32_t> lp((size_t)nt + 1, 0);
+    int max_col = 0;
+    if (!rc) {
+        e = hipMemcpy(lp.data() + 1, d_n, 4 * (size_t)nt, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(&max_col, d_max, 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    d_n.reset(); d_max.reset();
+    if (rc) return rc;
+    int64_t staged = 0, total = 0;
+    int used = 0;
+    for (int64_t t = 0; t < nt; ++t) {
+        const int n = lp[(size_t)t + 1];
+        staged += n > 0; used = std::max(used, n);
+        total += n;
+        if (total > INT32_MAX) return USPMV_OK;
+        lp[(size_t)t + 1] = (int32_t)total;
+    }
+    st->n_tiles = nt; st->n_staged = staged;
+    if (staged == 0) return USPMV_OK;
+    e = A->tlc.line_ptr.upload(lp.data(), 4 * ((size_t)nt + 1));
+    if (e == hipSuccess) e = A->tlc.lines.alloc(4 * (size_t)std::max<int64_t>(total, 1));
+    for (int k = 0; k < 3; ++k) {
+        if (!parts[k]) continue;
+        if (e == hipSuccess) e = parts[k]->tlc.c16_ptrs.upload(c16p[k].data(), 4 * ((size_t)nc + 1));
+        if (e == hipSuccess) e = parts[k]->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16[k], 1));   // padded slots: index 0
+    }
+    if (e == hipSuccess && launch_plan_write(A, (long)nt, A->tlc.line_ptr, A->tlc.c16_ptrs, A->tlc.lines, A->tlc.col16, nullptr, B,
+                                             B ? B->tlc.c16_ptrs : nullptr, B ? B->tlc.col16 : nullptr, R, B3,
+                                             B3 ? B3->tlc.c16_ptrs : nullptr, B3 ? B3->tlc.col16 : nullptr) != USPMV_OK)
+        e = hipErrorUnknown;
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
+        return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    stamp_plan(parts, R, used, (int64_t)max_col + 1, nt, staged, /*elem=*/false);
+    st->valid = true; st->lines = used;
+    if (!B) return tlc_pack12(A, &cl, who);
+    return USPMV_OK;
+}
+
+// For LARGE single structs the rows per tile are MEASURED (tuning tlc_measure_tile, default on; only when tlc_tile_rows is 0): the plan
+// is built on the device for 256, 512 and 1024 rows (two passes over the column indices each), the kernel timed three times on a zero
+// vector, and a larger tile kept when it is more than 3 % ahead of 256.  Why: which size wins depends on how far apart the x lines of
+// neighbouring tiles lie -- the 27-point stencil on 253^3 is fastest at 256 rows, the same stencil on 304^3 (planes of 739 instead of
+// 512 KB: more of the x lines miss the XCD's L2) at 512 (1.249 against 1.341 ms, profiles/r03/tile_rows_sweep.txt).  The choice is
+// remembered per (shape, size) for the life of the process, so the host and the device planner of one matrix agree.  0 = no opinion.
+int measured_tile_rows(uspmv_dmat *A, uspmv_dmat *B, int max_lines, const char *who) {
+    // one measurement at a time, and the verdict table only read / written under the lock (the verdict is keyed on the struct's shape and
+    // size, not its content: two matrices with equal counts share it -- the price of host and device planner of ONE matrix agreeing)
+    static std::mutex mtx;
+    std::lock_guard<std::mutex> lock(mtx);
+    if (!g_tune.tlc_measure_tile || g_tune.tlc_tile_rows != 0 || A->alt || A->C > 256 || 256 % A->C != 0) return 0;
+    if (A->n_chunks * A->C < (int64_t)1 << 20) return 0;
+    if (B && (B->alt || B->C != A->C || B->n_chunks != A->n_chunks || A->dtype != USPMV_F64 || B->dtype != USPMV_F32)) return 0;
+    struct Key { int64_t nc, ne, ne2, C; int dtype, ml; };
+    static std::vector<std::pair<Key, int>> seen;
+    const int64_t ne2 = B ? B->n_elements : -1;
+    for (auto &kv : seen)
+        if (kv.first.nc == A->n_chunks && kv.first.ne == A->n_elements && kv.first.ne2 == ne2 && kv.first.C == A->C && kv.first.dtype == A->dtype && kv.first.ml == max_lines)
+            return kv.second;
+    const size_t vsz = A->dtype == USPMV_F64 ? 8 : 4;
+    DeviceBuf<void> x, y;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int best = 0;
+    auto done = [&]() {
+        x.reset(); y.reset();
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        A->tlc = {};
+        if (B) B->tlc = {};
+    };
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { done(); (void)hipGetLastError(); return 0; }
+    // the size to beat: 256 rows for one struct, 512 for an ap[dp_sp] pair (two entry streams per row, profiles/r02/ap_tile_rows.txt);
+    // it is timed first and once more at the end (the first candidate may have met a cold clock)
+    const int base = B ? 512 : 256;
+    const int order[4] = {base, base == 256 ? 512 : 256, 1024, base};
+    float tmin[3] = {0, 0, 0};                                  // best time seen for 256 / 512 / 1024 rows (0: not usable)
+    auto slot_of = [](int R) { return R == 256 ? 0 : R == 512 ? 1 : 2; };
+    uspmv_dmat *const parts[3] = {A, B, nullptr};
+    for (int k = 0; k < 4; ++k) {
+        const int R = order[k], slot = slot_of(R), bs = slot_of(base);
+        if (k == 3) {                                           // re-check the base only when something is about to beat it
+            bool beaten = false;
+            for (int o = 0; o < 3; ++o) beaten |= o != bs && tmin[o] > 0 && tmin[bs] > 0 && tmin[o] < 0.97f * tmin[bs];
+            if (!beaten) break;
+        }
+        PlanStats c;
+        if (device_plan_install_rows(parts, max_lines, R, &c, who) != USPMV_OK || !A->tlc.on) { (void)hipGetLastError(); continue; }
+        if (!tile_rows_accept(c.n_tiles, c.n_staged)) continue;
+        if (!x) {
+            const size_t xb = vsz * (size_t)std::max<int64_t>(A->tlc.x_len + 16, 16), yb = vsz * (size_t)std::max<int64_t>(A->n_chunks * A->C, 1);
+            if (x.zeros(xb) != hipSuccess || y.alloc(yb) != hipSuccess) { done(); (void)hipGetLastError(); return 0; }
+        }
+        float ms = 0;
+        bool ok = true;
+        for (int rep = 0; rep < 2 && ok; ++rep) {             // (first round warms up)
+            ok = hipEventRecord(e0, nullptr) == hipSuccess;
+            for (int l = 0; l < 3 && ok; ++l) {
+                if (B) ok = launch_spmv_ap(A, B, (const double *)x, nullptr, (double *)y, nullptr) == USPMV_OK;
+                else ok = (A->dtype == USPMV_F64 ? launch_spmv_tlc<double>(A, nullptr, (long)A->tlc.n_tiles, (const double *)x, (double *)y, nullptr)
+                                                 : launch_spmv_tlc<float>(A, nullptr, (long)A->tlc.n_tiles, (const float *)x, (float *)y, nullptr)) == USPMV_OK;
+            }
+            ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+        }
+        if (!ok) { (void)hipGetLastError(); continue; }
+        if (verbose()) fprintf(stderr, "[uspmv] measured tile size%s: %d rows -> %.4f ms per SpMV (%lld of %lld tiles staged, %d lines at most)\n", B ? " (ap pair)" : "",
+                               R, ms / 3, (long long)c.n_staged, (long long)c.n_tiles, A->tlc.max_lines);
+        tmin[slot] = tmin[slot] > 0 ? std::min(tmin[slot], ms) : ms;
+    }
+    // the base size unless another one is more than 3 % ahead of it (the fastest of those that are)
+    {
+        const int bs = slot_of(base);
+        float tbest = tmin[bs] > 0 ? 0.97f * tmin[bs] : 1e30f;
+        best = tmin[bs] > 0 ? base : 0;
+        const int sizes[3] = {256, 512, 1024};
+        for (int o = 0; o < 3; ++o)
+            if (o != bs && tmin[o] > 0 && tmin[o] < tbest) { best = sizes[o]; tbest = tmin[o]; }
+    }
+    done();
+    seen.push_back({Key{A->n_chunks, A->n_elements, ne2, A->C, A->dtype, max_lines}, best});
+    return best;
+}
+
+// A quick look before an element plan is built in full (a sort per tile over all entries): of ~64 tiles spread over the struct, how many list more distinct
+// columns than `cap`?  More than a tenth of them: the element plan would be turned down anyway (wide irregular rows: the sweep's matrices).
+double elements_over_cap_frac(const uspmv_scs *s, int cap, int tile_rows) {
+    const int64_t C = s->C, T = std::max<int64_t>(1, tile_rows / C), nt = (s->n_chunks + T - 1) / T;
+    const int64_t step = std::max<int64_t>(1, nt / 64);
+    int64_t seen = 0, over = 0;
+    std::vector<int32_t> cols;
+    for (int64_t t = step / 2; t < nt; t += step) {
+        const int64_t c0 = t * T, c1 = std::min<int64_t>(c0 + T, s->n_chunks);
+        cols.assign(s->col_idxs.begin() + s->chunk_ptrs[(size_t)c0], s->col_idxs.begin() + s->chunk_ptrs[(size_t)c1]);
+        std::sort(cols.begin(), cols.end());
+        const int64_t n = (int64_t)(std::unique(cols.begin(), cols.end()) - cols.begin());
+        ++seen; over += n > cap;
+    }
+    return seen > 0 ? (double)over / (double)seen : 1.0;
+}
+
+// the device planner of one struct or an ap[dp_sp] pair: the plan at the rows per tile uspmv_dmat_optimize[_ap] chooses, then its sweep rule
+int device_plan_install(uspmv_dmat *A, uspmv_dmat *B, int max_lines, int64_t *n_tiles, int64_t *n_staged, const char *who) {
+    uspmv_dmat *const parts[3] = {A, B, nullptr};
+    const int R_meas = measured_tile_rows(A, B, line_budget(max_lines, A->dtype, B != nullptr), who);
+    uspmv_dmat::TlcPlan kept[2];
+    PlanStats st;
+    const int rc = plan_at_chosen_rows(R_meas, B != nullptr, [&](int R, PlanStats *o) { return device_plan_install_rows(parts, max_lines, R, o, who); },
+                                       [&]() { kept[0] = std::move(A->tlc); if (B) kept[1] = std::move(B->tlc); }, &st);
+    if (n_tiles) *n_tiles = st.n_tiles;
+    if (n_staged) *n_staged = st.n_staged;
+    if (rc) return rc;
+    A->tlc = std::move(kept[0]);
+    if (B) B->tlc = std::move(kept[1]);
+    bool swept = false;
+    if (int rc2 = sweep_takes_over(A, B, nullptr, nullptr, st, who, &swept)) return rc2;
+    if (swept) {             // (n_tiles / n_staged keep describing the tile-local-column attempt, as in uspmv_dmat_optimize;
+        A->tlc = {};         //  uspmv_dmat_plan_info tells which plan the handle ended up with)
+        if (B) B->tlc = {};
+    }
+    return USPMV_OK;
+}
+
+}  // namespace
+
+namespace uspmv_dev {
+
+int check_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const char *who) {
+    if (int rc = check_dmat(hi, who)) return rc;
+    if (int rc = check_dmat(hp, who)) return rc;
+    if (mid) if (int rc = check_dmat(mid, who)) return rc;
+    const bool ok = hp->dtype == USPMV_F16 && (mid ? hi->dtype == USPMV_F64 && mid->dtype == USPMV_F32 : hi->dtype == USPMV_F64 || hi->dtype == USPMV_F32);
+    if (!ok) return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts must be (F64, -, F16), (F32, -, F16) or (F64, F32, F16)", who);
+    if (hi->C != hp->C || hi->n_chunks != hp->n_chunks || (mid && (mid->C != hi->C || mid->n_chunks != hi->n_chunks)))
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts must share C and n_chunks", who);
+    return USPMV_OK;
+}
+
+bool c16_offsets(const std::vector<int32_t> &cl, int64_t C, std::vector<uint32_t> *c16p, int64_t *tot16) {
+    const int64_t nc = (int64_t)cl.size();
+    c16p->assign((size_t)nc + 1, 0);
+    int64_t tot = 0;
+    for (int64_t c = 0; c < nc; ++c) {
+        (*c16p)[(size_t)c] = (uint32_t)tot;
+        tot += ((int64_t)(cl[(size_t)c] + 3) / 4) * 4 * C;
+        if (tot > (int64_t)UINT32_MAX) return false;
+    }
+    (*c16p)[(size_t)nc] = (uint32_t)tot;
+    *tot16 = tot;
+    return true;
+}
+
+int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize";
+    if (!A || !s) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (int rc = check_dmat_one_prec(A, who)) return rc;
+    if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host column indices", who);
+    if (A->C != s->C || A->n_chunks != s->n_chunks || A->dtype != s->dtype)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: handle and host struct do not describe the same matrix", who);
+    if (int rc = require_device()) return rc;
+    A->tlc = {};
+    if (A->alt) { uspmv_dmat_free(A->alt); A->alt = nullptr; }
+    if (s->C < 32 && 32 % s->C == 0 && g_tune.rechunk) {
+        // narrow chunks (incl. crs = C 1): run on an internal C = 32 re-chunking with the same row order
+        uspmv_scs r;
+        int rc = uspmv_scs_rechunk32(s, &r);
+        if (rc == USPMV_OK && rechunk_worth(r.n_elements, s->n_elements)) {
+            uspmv_dmat_t *alt = nullptr;
+            if (int rc2 = uspmv_dmat_upload(&r, &alt)) return rc2;
+            alt->n_store = (long)(s->n_chunks * s->C);      // y of the caller has only the original padded rows
+            rc = dmat_optimize(alt, &r, max_lines, opts, n_tiles, n_staged);   // (C = 32: does not re-enter this branch)
+            if (rc) { uspmv_dmat_free(alt); return rc; }
+            A->alt = alt;
+            return USPMV_OK;
+        }
+    }
+    const bool own_budget = max_lines > 0;                     // (a caller with a line budget of its own keeps the line plan: no element fallback)
+    max_lines = line_budget(max_lines, s->dtype, false);
+    uspmv_tlc_plan p, q;
+    PlanStats st;
+    auto build = [&](int R, PlanStats *o) {
+        q = {};
+        const int rc = uspmv_build_tlc_plan(s, nullptr, max_lines, R, &q);
+        *o = stats_of(q);
+        return rc;
+    };
+    if (int rc = plan_at_chosen_rows(opts.measure ? measured_tile_rows(A, nullptr, max_lines, who) : 0, false, build, [&]() { p = std::move(q); }, &st)) return rc;
+    auto report = [&]() {
+        if (n_tiles) *n_tiles = p.n_tiles;
+        if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
+    };
+    report();
+    if (verbose()) fprintf(stderr, "[uspmv] tlc plan: tile_rows=%d tiles=%lld staged=%lld max_lines=%d lines_total=%zu col16=%zu\n",
+                           p.tile_rows, (long long)p.n_tiles, (long long)p.n_staged_tiles, p.max_lines_used, p.tile_lines.size(), p.col16.size());
+    A->sw = {};
+    // the element plans below: most elements a tile may list, and "an element serves four entries or more on average"
+    const int ecap = std::min(g_tune.tlc_elem_cap, (int)(64 * 1024 / (s->dtype == USPMV_F64 ? 8 : 4)));
+    auto elements_pay = [&](const uspmv_tlc_plan &e) { return (double)e.tile_lines.size() * 4.0 <= (double)s->n_elements; };
+    const bool line_plan_short = !own_budget && (!p.valid || !stages_nine_tenths(p.n_tiles, p.n_staged_tiles));
+    bool elem = false;
+    if ((line_plan_short || g_tune.tlc_elem == 2) && g_tune.tlc_elem && opts.elements) {   // (2: measurement aid, always try)
+        // columns scattered over many lines (x in a numbering that is only loosely related to the rows'): the line plan leaves a tenth of the tiles or
+        // more to the gather path.  List the tile's distinct ELEMENTS instead -- taken when (nearly) every tile fits and an element serves four
+        // entries or more on average (else the line plan stays, or the column-window sweep takes over below).  Measured (tools/numbering_probe.py,
+        // profiles/r04/numbering_probe_*.txt): 27-point x 3 dof stencil with x renumbered at random inside blocks of 1 000 / 5 000 / 20 000 nodes 0.97 / 0.90 /
+        // 0.89 of the roofline against 0.74 (line plan, 69 % of the tiles staged) / 0.70 / 0.61 (sweep); 1 dof, 4.2 entries per element: 0.65 against 0.59;
+        // on a regular numbering the line plan is 20 % ahead (0.683 against 0.819 ms on the 253^3 stencil), which is why this is a fallback only.
+        q = {};
+        if (elements_over_cap_frac(s, ecap, 256) <= 0.1)
+            if (int rc = uspmv_build_tlc_plan(s, nullptr, ecap, 256, &q, /*line_shift=*/0)) return rc;
+        if (q.valid && tile_rows_accept(q.n_tiles, q.n_staged_tiles) && (elements_pay(q) || g_tune.tlc_elem == 2)) {
+            p = std::move(q); elem = true;
+            report();
+            if (verbose()) fprintf(stderr, "[uspmv] tlc plan over single x elements: tiles=%lld staged=%lld max_elements=%d elements_total=%zu (%.1f entries per element)\n",
+                                   (long long)p.n_tiles, (long long)p.n_staged_tiles, p.max_lines_used, p.tile_lines.size(), (double)s->n_elements / (double)std::max<size_t>(p.tile_lines.size(), 1));
+        }
+    }
+    // ... and when the ROWS of a tile are scattered as well (rows and columns renumbered alike: a tile of 256 consecutive rows is no compact piece of the
+    // mesh any more): deal the rows to the tiles by the matrix graph first, as the block plan does (uspmv_scs_reorder_rows mode 4: rows change places
+    // only with rows of equal-length chunks, every row keeps its slot sequence), then the element plan on that order -- a private copy of the values
+    // (8 / 4 bytes per element of HBM), of the column indices (for the few tiles that do not stage) and a row map for y.
+    uspmv_scs rr;
+    std::vector<int32_t> rr_map;
+    bool reordered = false;
+    if (!elem && line_plan_short && g_tune.tlc_elem && g_tune.tlc_elem_rows && opts.deal_rows && s->n_rows == s->n_cols) {
+        // first with the clusters confined to segments of tlc_elem_seg_rows rows (64 Ki: many segments in parallel, and a trial on a sample of them that stops
+        // irregular matrices early); when that leaves some, but not most, of the sampled tiles over the cap -- related rows further apart than a segment --
+        // once more with segments of 2^20 rows (a second or more of clustering per million rows on few threads: only where it looks promising)
+        const int64_t seg_stage[2] = {(int64_t)g_tune.tlc_elem_seg_rows, (int64_t)1 << 20};
+        for (int stage = 0; stage < 2 && !reordered; ++stage) {
+            if (stage == 1 && seg_stage[1] <= seg_stage[0]) break;
+            if (uspmv_scs_reorder_rows(s, g_tune.tlc_elem_rows == 4 ? 4 : 2, &rr, &rr_map, g_tune.tlc_elem_rows == 4 ? 64 : 256, seg_stage[stage]) != 1) break;
+            const double over = elements_over_cap_frac(&rr, ecap, 256);
+            q = {};
+            if (over <= 0.1)
+                if (int rc = uspmv_build_tlc_plan(&rr, nullptr, ecap, 256, &q, /*line_shift=*/0)) return rc;
+            if (verbose()) fprintf(stderr, "[uspmv] element plan on the graph-dealt rows (segments of %lld rows): %.0f %% of the sampled tiles over the cap; valid=%d tiles=%lld staged=%lld max_elements=%d (cap %d) elements_total=%zu\n",
+                                   (long long)seg_stage[stage], 100.0 * over, (int)q.valid, (long long)q.n_tiles, (long long)q.n_staged_tiles, q.max_lines_used, ecap, q.tile_lines.size());
+            // (19 of 20 tiles staged is enough here: what would run instead -- sweep or gather kernel -- is 2 x slower on such matrices)
+            if (q.valid && stages_19_of_20(q.n_tiles, q.n_staged_tiles) && elements_pay(q)) {
+                p = std::move(q); elem = true; reordered = true;
+                report();
+                if (verbose()) fprintf(stderr, "[uspmv] tlc plan over single x elements, rows dealt to the tiles by the matrix graph: tiles=%lld max_elements=%d elements_total=%zu (%.1f entries per element)\n",
+                                       (long long)p.n_tiles, p.max_lines_used, p.tile_lines.size(), (double)s->n_elements / (double)std::max<size_t>(p.tile_lines.size(), 1));
+            } else if (over > 0.6) break;                    // most tiles far over the cap: larger segments will not repair that
+        }
+    }
+    if (!elem) {
+        bool swept = false;
+        if (int rc = sweep_takes_over(A, nullptr, s, nullptr, stats_of(p), who, &swept)) return rc;
+        if (swept) return USPMV_OK;
+    }
+    if (!p.valid) return USPMV_OK;                              // nothing worth staging: plain kernel stays
+    uspmv_dmat *const parts[3] = {A, nullptr, nullptr};
+    if (int rc = install_host_plan(parts, p, elem, who)) return rc;
+    if (reordered) {
+        hipError_t e = A->tlc.values.upload(rr.values_ptr(), (size_t)rr.n_elements * (rr.dtype == USPMV_F64 ? 8 : 4));
+        if (e == hipSuccess) e = A->tlc.row_map.upload(rr_map.data(), rr_map.size() * 4);
+        if (e == hipSuccess && p.n_staged_tiles < p.n_tiles) e = A->tlc.cols.upload(rr.col_idxs.data(), (size_t)rr.n_elements * 4);
+        if (e != hipSuccess) {
+            A->tlc = {};
+            return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
+        }
+    }
+    return tlc_pack12(A, &s->chunk_lengths, who);
+}
+
+}  // namespace uspmv_dev
+
+extern "C" {
+
+int uspmv_dmat_optimize(uspmv_dmat_t *A, const uspmv_scs_t *s, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    return dmat_optimize(A, s, max_lines, TlcPlanOpts{}, n_tiles, n_staged);
+}
+
+int uspmv_dmat_optimize_device(uspmv_dmat_t *A, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_device";
+    if (int rc = check_dmat_one_prec(A, who)) return rc;
+    if (int rc = require_device()) return rc;
+    if (A->alt) { uspmv_dmat_free(A->alt); A->alt = nullptr; }
+    if (A->C < 32 && 32 % A->C == 0 && g_tune.rechunk && A->n_chunks > 0) {
+        // narrow chunks (incl. crs = C 1): the internal C = 32 re-chunking of uspmv_dmat_optimize, built on the device --
+        // O(n_chunks) layout on the host, the O(n_elements) copy by rechunk32_kernel
+        const int64_t C = A->C, nc_old = A->n_chunks, per = 32 / C, nc = (nc_old + per - 1) / per;
+        std::vector<int32_t> cl_old((size_t)nc_old), cl((size_t)nc, 0), cp((size_t)nc + 1, 0);
+        int32_t last = 0;
+        HIP_TRY(hipMemcpy(cl_old.data(), A->chunk_lengths, 4 * (size_t)nc_old, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&last, A->chunk_ptrs + nc_old, 4, hipMemcpyDeviceToHost));
+        int64_t cur = 0;
+        bool fits = true;
+        for (int64_t k = 0; k < nc && fits; ++k) {
+            int32_t L = 0;
+            for (int64_t c = k * per; c < std::min((k + 1) * per, nc_old); ++c) L = std::max(L, cl_old[(size_t)c]);
+            cl[(size_t)k] = L; cp[(size_t)k] = (int32_t)cur;
+            cur += (int64_t)L * 32;
+            fits = cur <= INT32_MAX;
+        }
+        if (fits && rechunk_worth(cur, last)) {
+            cp[(size_t)nc] = (int32_t)cur;
+            auto *alt = new uspmv_dmat;
+            alt->C = 32; alt->n_chunks = nc; alt->n_elements = cur; alt->dtype = A->dtype;
+            alt->n_store = (long)(nc_old * C);              // y of the caller has only the original padded rows
+            const size_t vsz = A->dtype == USPMV_F64 ? 8 : 4, ne = (size_t)std::max<int64_t>(cur, 1);
+            hipError_t e = alt->own_arrays();
+            if (e == hipSuccess) e = hipMemcpy(alt->own.chunk_ptrs, cp.data(), 4 * ((size_t)nc + 1), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(alt->own.chunk_lengths, cl.data(), 4 * (size_t)nc, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemsetAsync(alt->own.col_idxs, 0, 4 * ne, nullptr);
+            if (e == hipSuccess) e = hipMemsetAsync(alt->own.values, 0, vsz * ne, nullptr);
+            int rc = e == hipSuccess ? launch_rechunk32(A, alt->chunk_ptrs, alt->own.col_idxs, alt->own.values, nullptr) : uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
+            if (!rc) rc = device_plan_install(alt, nullptr, max_lines, n_tiles, n_staged, who);
+            if (rc) { uspmv_dmat_free(alt); return rc; }
+            A->tlc = {};
+            A->alt = alt;
+            return USPMV_OK;
+        }
+    }
+    return device_plan_install(A, nullptr, max_lines, n_tiles, n_staged, who);
+}
+
+int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t *s_dp, const uspmv_scs_t *s_sp,
+                           int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_ap";
+    if (!dp || !sp || !s_dp || !s_sp) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (!uspmv::scs_has_entries(s_dp) || !uspmv::scs_has_entries(s_sp))
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host column indices", who);
+    if (dp->C != s_dp->C || dp->n_chunks != s_dp->n_chunks || dp->dtype != USPMV_F64 || s_dp->dtype != USPMV_F64 ||
+        sp->C != s_sp->C || sp->n_chunks != s_sp->n_chunks || sp->dtype != USPMV_F32 || s_sp->dtype != USPMV_F32 ||
+        dp->C != sp->C || dp->n_chunks != sp->n_chunks)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: handles / host structs do not form a dp+sp pair", who);
+    if (int rc = require_device()) return rc;
+    dp->tlc = {};
+    sp->tlc = {};
+    max_lines = line_budget(max_lines, USPMV_F64, true);
+    uspmv_tlc_plan p;
+    PlanStats st;
+    auto build = [&](int R, PlanStats *o) {
+        const int rc = uspmv_build_tlc_plan(s_dp, s_sp, max_lines, R, &p);
+        *o = stats_of(p);
+        return rc;
+    };
+    if (int rc = plan_at_chosen_rows(measured_tile_rows(dp, sp, max_lines, who), true, build, []() {}, &st)) return rc;
+    if (n_tiles) *n_tiles = p.n_tiles;
+    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
+    bool swept = false;
+    if (int rc = sweep_takes_over(dp, sp, s_dp, s_sp, st, who, &swept)) return rc;
+    if (swept || !p.valid) return USPMV_OK;
+    uspmv_dmat *const parts[3] = {dp, sp, nullptr};
+    return install_host_plan(parts, p, /*elem=*/false, who);
+}
+
+int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_device_ap";
+    if (int rc = check_dmat(dp, who)) return rc;
+    if (int rc = check_dmat(sp, who)) return rc;
+    if (dp->dtype != USPMV_F64 || sp->dtype != USPMV_F32 || dp->C != sp->C || dp->n_chunks != sp->n_chunks)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: handles do not form a dp+sp pair", who);
+    if (int rc = require_device()) return rc;
+    return device_plan_install(dp, sp, max_lines, n_tiles, n_staged, who);
+}
+
+int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
+                              const uspmv_scs_t *s_hp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_ap_hp";
+    if (!s_hi || !s_hp || (mid && !s_mid)) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    const uspmv_scs_t *ss[3] = {s_hi, mid ? s_mid : s_hp, mid ? s_hp : nullptr};
+    uspmv_dmat_t *const ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
+    for (int k = 0; k < 3; ++k) {
+        if (!ms[k]) continue;
+        if (!uspmv::scs_has_entries(ss[k]))
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host column indices", who);
+        if (ms[k]->C != ss[k]->C || ms[k]->n_chunks != ss[k]->n_chunks || ms[k]->dtype != ss[k]->dtype)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: handles and host structs do not describe the same parts", who);
+    }
+    if (int rc = require_device()) return rc;
+    for (uspmv_dmat_t *M : ms) if (M) { M->tlc = {}; M->sw = {}; }
+    if (n_tiles) *n_tiles = 0;
+    if (n_staged) *n_staged = 0;
+    uspmv_tlc_plan p;
+    if (int rc = uspmv_build_tlc_plan(ss[0], ss[1], line_budget(max_lines, hi->dtype, true), plan_tile_rows(true), &p, 4, ss[2])) return rc;
+    if (n_tiles) *n_tiles = p.n_tiles;
+    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
+    if (!p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
+    return install_host_plan(ms, p, /*elem=*/false, who);
+}
+
+int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_device_ap_hp";
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    if (int rc = require_device()) return rc;
+    uspmv_dmat_t *const ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
+    for (uspmv_dmat_t *M : ms) if (M) M->sw = {};
+    PlanStats st;
+    if (int rc = device_plan_install_rows(ms, max_lines, plan_tile_rows(true), &st, who)) return rc;
+    if (n_tiles) *n_tiles = st.n_tiles;
+    if (n_staged) *n_staged = st.n_staged;
+    if (!ap_hp_plan_worth(st.n_tiles, st.n_staged))
+        for (uspmv_dmat_t *M : ms) if (M) M->tlc = {};
+    return USPMV_OK;
+}
+
+int uspmv_dmat_plan_download(const uspmv_dmat_t *A, int64_t meta[4], int32_t *tile_line_ptr, int32_t *tile_lines, uint32_t *c16_ptrs,
+                             uint16_t *col16) {
+    if (int rc = check_dmat(A, "uspmv_dmat_plan_download")) return rc;
+    if (!meta) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_plan_download: NULL meta");
+    meta[0] = meta[1] = meta[2] = meta[3] = 0;
+    if (!A->tlc.on) return USPMV_OK;
+    if (int rc = require_device()) return rc;
+    int32_t last = 0; uint32_t last16 = 0;
+    // (the second and third part of a shared ap plan hold only their local indices: the line list lives with the first part)
+    if (A->tlc.line_ptr) HIP_TRY(hipMemcpy(&last, A->tlc.line_ptr + A->tlc.n_tiles, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&last16, A->tlc.c16_ptrs + A->n_chunks, 4, hipMemcpyDeviceToHost));
+    meta[0] = A->tlc.n_tiles; meta[1] = last; meta[2] = last16; meta[3] = A->tlc.max_lines;
+    if (tile_line_ptr && A->tlc.line_ptr) HIP_TRY(hipMemcpy(tile_line_ptr, A->tlc.line_ptr, 4 * ((size_t)A->tlc.n_tiles + 1), hipMemcpyDeviceToHost));
+    if (tile_lines && last) HIP_TRY(hipMemcpy(tile_lines, A->tlc.lines, 4 * (size_t)last, hipMemcpyDeviceToHost));
+    if (c16_ptrs) HIP_TRY(hipMemcpy(c16_ptrs, A->tlc.c16_ptrs, 4 * ((size_t)A->n_chunks + 1), hipMemcpyDeviceToHost));
+    if (col16 && last16) HIP_TRY(hipMemcpy(col16, A->tlc.col16, 2 * (size_t)last16, hipMemcpyDeviceToHost));
+    return USPMV_OK;
+}
+
+}  // extern "C"

@@ -1,12 +1,12 @@
-// Device half of the C ABI (include/uspmv.h): handles, tuning, plans, GPU-side conversion, the small gather /
-// stream kernels and the entry points that dispatch into spmv_kernels.hip, spmmv_kernels.hip and ap_kernels.hip.
+// Device half of the C ABI (include/uspmv.h): handles, tuning, the sweep and block plans, GPU-side conversion, the small gather /
+// stream kernels and the entry points that dispatch into spmv_kernels.hip, spmmv_kernels.hip and ap_kernels.hip.  The SpMV planner
+// (uspmv_dmat_optimize and its variants) is csrc/tlc_planner.hip.
 #include "uspmv_device.hpp"
 
 #include <mutex>
 
 using namespace uspmv_dev;
 
-namespace uspmv_dev { thread_local int tl_measure_off = 0; }
 namespace uspmv_dev {
 
 Tuning g_tune;
@@ -30,7 +30,7 @@ int check_dmat(const uspmv_dmat *A, const char *who) {
 }
 
 // one-precision entry points (SpMV, SpMMV and their plans): an fp16 handle only runs as the hp part of uspmv_spmv_ap_hp
-static int check_dmat_one_prec(const uspmv_dmat *A, const char *who) {
+int check_dmat_one_prec(const uspmv_dmat *A, const char *who) {
     if (int rc = check_dmat(A, who)) return rc;
     if (A->dtype == USPMV_F16)
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: fp16 handle; fp16 values run only as the hp part of uspmv_spmv_ap_hp", who);
@@ -148,6 +148,90 @@ __global__ void __launch_bounds__(256) stream_gather_lines_kernel(const double2 
     if ((threadIdx.x & 63) == 0) partial[(long)blockIdx.x * 4 + (threadIdx.x >> 6)] = acc;
 }
 
+// The tuning keys of uspmv_set_tuning / uspmv_get_tuning: the field of Tuning (uspmv_device.hpp: meaning and default) and the rule a
+// value passes on its way in.  A rule adjusts the value in place and returns false to refuse it (`refusal` is then the error text).
+bool any(int &) { return true; }
+bool flag(int &v) { v = v != 0; return true; }
+template <int LO, int HI = INT32_MAX>
+bool clamped(int &v) { v = v < LO ? LO : v > HI ? HI : v; return true; }
+template <int LO, int HI>
+bool within(int &v) { return v >= LO && v <= HI; }
+template <int... SET>
+bool one_of(int &v) { return ((v == SET) || ...); }
+template <int ELSE, int... SET>
+bool one_of_or(int &v) { if (!((v == SET) || ...)) v = ELSE; return true; }
+
+struct TuneKey {
+    const char *key;
+    int Tuning::*field;
+    bool (*rule)(int &);
+    const char *refusal = nullptr;
+    int (*unpack)(int word) = nullptr;           // keys that share a field with another one (xcd_remap: bits 0-19 the group size, 20+ the stagger)
+    int (*pack)(int word, int v) = nullptr;
+};
+const TuneKey TUNE_KEYS[] = {
+    {"unroll", &Tuning::unroll, one_of<1, 2, 4, 8>, "unroll must be 1|2|4|8"},
+    {"nontemporal", &Tuning::nontemporal, flag},
+    {"xcd_remap", &Tuning::xcd_remap, within<0, 65536>, "xcd_remap must be 0, 1 or a group size <= 65536",
+     [](int w) { return w & 0xFFFFF; }, [](int w, int v) { return (w & ~0xFFFFF) | v; }},
+    // XCD k starts its group value*k tiles in (remap_block); 0 = all XCDs in step
+    {"xcd_stagger", &Tuning::xcd_remap, within<0, 2047>, "xcd_stagger must be in [0, 2047]",
+     [](int w) { return w >> 20; }, [](int w, int v) { return (w & 0xFFFFF) | (v << 20); }},
+    {"block", &Tuning::block, one_of<64, 128, 256, 512, 1024>, "block must be 64|128|256|512|1024"},
+    {"spmv_variant", &Tuning::spmv_variant, within<0, 2>, "spmv_variant must be 0|1|2"},
+    {"csr_lanes", &Tuning::csr_lanes, [](int &v) { return v >= 0 && v <= 64 && !(v & (v - 1)); }, "csr_lanes must be 0 or a power of two <= 64"},
+    {"ablate", &Tuning::ablate, any},
+    {"tlc", &Tuning::tlc, flag},
+    {"rechunk", &Tuning::rechunk, flag},
+    {"tlc_tile_rows", &Tuning::tlc_tile_rows, one_of<0, 256, 512, 1024>, "tlc_tile_rows must be 0|256|512|1024"},
+    {"tlc_auto_tile", &Tuning::tlc_auto_tile, flag},
+    {"tlc_measure_tile", &Tuning::tlc_measure_tile, flag},
+    {"tlc_idx12", &Tuning::tlc_idx12, clamped<0, 2>},
+    {"tlc_elem", &Tuning::tlc_elem, clamped<0, 2>},
+    {"tlc_elem_rows", &Tuning::tlc_elem_rows, clamped<0>},
+    {"tlc_elem_seg_rows", &Tuning::tlc_elem_seg_rows, clamped<65536>},
+    {"tlc_elem_cap", &Tuning::tlc_elem_cap, clamped<64, 16384>},
+    {"tail_batch", &Tuning::tail_batch, flag},
+    {"raw_plan_cache", &Tuning::raw_plan_cache, flag},
+    {"sweep", &Tuning::sweep, flag},
+    {"sweep_nbuf", &Tuning::sweep_nbuf, one_of_or<2, 1>},
+    {"sweep_unroll", &Tuning::sweep_unroll, [](int &v) { v = v >= 8 ? 8 : v >= 4 ? 4 : 2; return true; }},
+    {"sweep_pair", &Tuning::sweep_pair, clamped<0, 2>},
+    {"sweep_remap", &Tuning::sweep_remap, clamped<0>},
+    {"sweep_wlog", &Tuning::sweep_wlog, [](int &v) { return v == 0 || (v >= 8 && v <= 16); }, "sweep_wlog must be 0 or 8..16"},
+    {"sweep_tile_rows", &Tuning::sweep_tile_rows, one_of<0, 256, 512, 1024, 2048, 4096>, "sweep_tile_rows must be 0|256|512|1024|2048|4096"},
+    {"sweep_threads", &Tuning::sweep_threads, one_of_or<0, 256, 512, 1024>},
+    {"sweep_max_stage", &Tuning::sweep_max_stage, clamped<0>},
+    {"spmmv_variant", &Tuning::spmmv_variant, [](int &v) { return v >= 0 && v <= 9 && v != 7; }, "spmmv_variant must be 0..6, 8 or 9 (9: the block-vector window sweep only)"},
+    {"spmmv_unroll", &Tuning::spmmv_unroll, any},
+    {"spmmv_prefetch", &Tuning::spmmv_prefetch, flag},
+    {"spmmv_swizzle", &Tuning::spmmv_swizzle, flag},
+    {"spmmv_reorder", &Tuning::spmmv_reorder, clamped<0, 4>},
+    {"spmmv_brick_stride", &Tuning::spmmv_brick_stride, clamped<0>},
+    {"spmmv_brick_lines", &Tuning::spmmv_brick_lines, clamped<1>},
+    {"spmmv_phase_dp", &Tuning::spmmv_phase_dp, clamped<0>},
+    {"spmmv_stream", &Tuning::spmmv_stream, [](int &v) { v = v < 0 ? 0 : v >= 99 ? 99 : v > 5 ? 5 : v; return true; }},
+    {"spmmv_stream_waves", &Tuning::spmmv_stream_waves, clamped<4, 5>},
+    {"spmmv_stream_xcd", &Tuning::spmmv_stream_xcd, flag},
+    {"spmmv_stream_depth", &Tuning::spmmv_stream_depth, clamped<1, 2>},
+    {"spmmv_phased", &Tuning::spmmv_phased, flag},
+    {"spmmv_phase_rows", &Tuning::spmmv_phase_rows, one_of_or<256, 512>},
+    {"spmmv_xcol", &Tuning::spmmv_xcol, flag},
+    {"spmmv_ycol_nt", &Tuning::spmmv_ycol_nt, flag},
+    {"spmmv_xline", &Tuning::spmmv_xline, flag},
+    {"spmmv_unscramble", &Tuning::spmmv_unscramble, flag},
+    {"spmmv_idx8", &Tuning::spmmv_idx8, flag},
+    {"spmmv_list_plan", &Tuning::spmmv_list_plan, flag},
+    {"spmmv_tile_rows", &Tuning::spmmv_tile_rows, one_of_or<0, 64, 32>},
+    {"spmmv_lds_kb", &Tuning::spmmv_lds_kb, clamped<0>},
+    {"block_plan_device", &Tuning::block_plan_device, flag},
+};
+const TuneKey *find_tune_key(const char *key) {
+    for (const TuneKey &k : TUNE_KEYS)
+        if (!strcmp(key, k.key)) return &k;
+    return nullptr;
+}
+
 }  // namespace
 
 namespace uspmv_dev {
@@ -190,142 +274,18 @@ int uspmv_stream_synchronize(void *stream) {
 
 int uspmv_set_tuning(const char *key, int value) {
     if (!key) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_set_tuning: NULL key");
-    if (!strcmp(key, "unroll")) {
-        if (value != 1 && value != 2 && value != 4 && value != 8) return uspmv::fail(USPMV_ERR_INVALID, "unroll must be 1|2|4|8");
-        g_tune.unroll = value;
-    } else if (!strcmp(key, "nontemporal")) g_tune.nontemporal = value != 0;
-    else if (!strcmp(key, "xcd_remap")) {
-        if (value < 0 || value > 65536) return uspmv::fail(USPMV_ERR_INVALID, "xcd_remap must be 0, 1 or a group size <= 65536");
-        g_tune.xcd_remap = (g_tune.xcd_remap & ~0xFFFFF) | value;
-    } else if (!strcmp(key, "xcd_stagger")) {     // XCD k starts its group value*k tiles in (remap_block); 0 = all XCDs in step
-        if (value < 0 || value > 2047) return uspmv::fail(USPMV_ERR_INVALID, "xcd_stagger must be in [0, 2047]");
-        g_tune.xcd_remap = (g_tune.xcd_remap & 0xFFFFF) | (value << 20);
-    } else if (!strcmp(key, "ablate")) g_tune.ablate = value;
-    else if (!strcmp(key, "spmmv_prefetch")) g_tune.spmmv_prefetch = value != 0;
-    else if (!strcmp(key, "spmmv_swizzle")) g_tune.spmmv_swizzle = value != 0;
-    else if (!strcmp(key, "spmmv_reorder")) g_tune.spmmv_reorder = value < 0 ? 0 : value > 4 ? 4 : (int)value;
-    else if (!strcmp(key, "spmmv_brick_stride")) g_tune.spmmv_brick_stride = value < 0 ? 0 : (long)value;
-    else if (!strcmp(key, "spmmv_brick_lines")) g_tune.spmmv_brick_lines = value < 1 ? 1 : (int)value;
-    else if (!strcmp(key, "spmmv_phase_dp")) g_tune.spmmv_phase_dp = value < 0 ? 0 : (int)value;
-    else if (!strcmp(key, "tlc_elem")) g_tune.tlc_elem = value < 0 ? 0 : value > 2 ? 2 : (int)value;
-    else if (!strcmp(key, "tlc_elem_rows")) g_tune.tlc_elem_rows = value < 0 ? 0 : (int)value;
-    else if (!strcmp(key, "tlc_elem_seg_rows")) g_tune.tlc_elem_seg_rows = value < 65536 ? 65536 : (int)value;
-    else if (!strcmp(key, "tlc_elem_cap")) g_tune.tlc_elem_cap = value < 64 ? 64 : value > 16384 ? 16384 : (int)value;
-    else if (!strcmp(key, "spmmv_stream")) g_tune.spmmv_stream = value < 0 ? 0 : value >= 99 ? 99 : value > 5 ? 5 : (int)value;
-    else if (!strcmp(key, "spmmv_stream_waves")) g_tune.spmmv_stream_waves = value >= 5 ? 5 : 4;
-    else if (!strcmp(key, "spmmv_stream_xcd")) g_tune.spmmv_stream_xcd = value != 0;
-    else if (!strcmp(key, "spmmv_stream_depth")) g_tune.spmmv_stream_depth = value >= 2 ? 2 : 1;
-    else if (!strcmp(key, "spmmv_phased")) g_tune.spmmv_phased = value != 0;
-    else if (!strcmp(key, "spmmv_xcol")) g_tune.spmmv_xcol = value != 0;
-    else if (!strcmp(key, "spmmv_ycol_nt")) g_tune.spmmv_ycol_nt = value != 0;
-    else if (!strcmp(key, "spmmv_xline")) g_tune.spmmv_xline = value != 0;
-    else if (!strcmp(key, "block_plan_device")) g_tune.block_plan_device = value != 0;
-    else if (!strcmp(key, "spmmv_unscramble")) g_tune.spmmv_unscramble = value != 0;
-    else if (!strcmp(key, "spmmv_phase_rows")) g_tune.spmmv_phase_rows = value == 512 ? 512 : 256;
-    else if (!strcmp(key, "spmmv_idx8")) g_tune.spmmv_idx8 = value != 0;
-    else if (!strcmp(key, "spmmv_list_plan")) g_tune.spmmv_list_plan = value != 0;
-    else if (!strcmp(key, "sweep")) g_tune.sweep = value != 0;
-    else if (!strcmp(key, "sweep_nbuf")) g_tune.sweep_nbuf = value == 1 ? 1 : 2;
-    else if (!strcmp(key, "sweep_unroll")) g_tune.sweep_unroll = value >= 8 ? 8 : value >= 4 ? 4 : 2;
-    else if (!strcmp(key, "sweep_pair")) g_tune.sweep_pair = value < 0 ? 0 : value > 2 ? 2 : value;
-    else if (!strcmp(key, "sweep_remap")) g_tune.sweep_remap = value < 0 ? 0 : value;
-    else if (!strcmp(key, "sweep_wlog")) {
-        if (value != 0 && (value < 8 || value > 16)) return uspmv::fail(USPMV_ERR_INVALID, "sweep_wlog must be 0 or 8..16");
-        g_tune.sweep_wlog = value;
-    }
-    else if (!strcmp(key, "sweep_tile_rows")) {
-        if (value != 0 && value != 256 && value != 512 && value != 1024 && value != 2048 && value != 4096) return uspmv::fail(USPMV_ERR_INVALID, "sweep_tile_rows must be 0|256|512|1024|2048|4096");
-        g_tune.sweep_tile_rows = value;
-    }
-    else if (!strcmp(key, "sweep_threads")) g_tune.sweep_threads = (value == 256 || value == 512 || value == 1024) ? (int)value : 0;
-    else if (!strcmp(key, "sweep_max_stage")) g_tune.sweep_max_stage = value < 0 ? 0 : value;
-    else if (!strcmp(key, "raw_plan_cache")) g_tune.raw_plan_cache = value != 0;
-    else if (!strcmp(key, "spmmv_tile_rows")) g_tune.spmmv_tile_rows = value == 64 ? 64 : value == 32 ? 32 : 0;
-    else if (!strcmp(key, "spmmv_lds_kb")) g_tune.spmmv_lds_kb = value < 0 ? 0 : value;
-    else if (!strcmp(key, "spmmv_variant")) {
-        if (value < 0 || value > 9 || value == 7) return uspmv::fail(USPMV_ERR_INVALID, "spmmv_variant must be 0..6, 8 or 9 (9: the block-vector window sweep only)");
-        g_tune.spmmv_variant = value;
-    }
-    else if (!strcmp(key, "tail_batch")) g_tune.tail_batch = value != 0;
-    else if (!strcmp(key, "spmmv_unroll")) g_tune.spmmv_unroll = value;
-    else if (!strcmp(key, "tlc")) g_tune.tlc = value != 0;
-    else if (!strcmp(key, "rechunk")) g_tune.rechunk = value != 0;
-    else if (!strcmp(key, "tlc_auto_tile")) g_tune.tlc_auto_tile = value != 0;
-    else if (!strcmp(key, "tlc_measure_tile")) g_tune.tlc_measure_tile = value != 0;
-    else if (!strcmp(key, "tlc_idx12")) g_tune.tlc_idx12 = value < 0 ? 0 : value > 2 ? 2 : (int)value;
-    else if (!strcmp(key, "tlc_tile_rows")) {
-        if (value != 0 && value != 256 && value != 512 && value != 1024) return uspmv::fail(USPMV_ERR_INVALID, "tlc_tile_rows must be 0|256|512|1024");
-        g_tune.tlc_tile_rows = value;
-    }
-    else if (!strcmp(key, "block")) {
-        if (value != 64 && value != 128 && value != 256 && value != 512 && value != 1024)
-            return uspmv::fail(USPMV_ERR_INVALID, "block must be 64|128|256|512|1024");
-        g_tune.block = value;
-    } else if (!strcmp(key, "spmv_variant")) {
-        if (value < 0 || value > 2) return uspmv::fail(USPMV_ERR_INVALID, "spmv_variant must be 0|1|2");
-        g_tune.spmv_variant = value;
-    } else if (!strcmp(key, "csr_lanes")) {
-        if (value < 0 || value > 64 || (value & (value - 1))) return uspmv::fail(USPMV_ERR_INVALID, "csr_lanes must be 0 or a power of two <= 64");
-        g_tune.csr_lanes = value;
-    } else return uspmv::fail(USPMV_ERR_INVALID, "uspmv_set_tuning: unknown key '%s'", key);
+    const TuneKey *k = find_tune_key(key);
+    if (!k) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_set_tuning: unknown key '%s'", key);
+    if (!k->rule(value)) return uspmv::fail(USPMV_ERR_INVALID, "%s", k->refusal);
+    g_tune.*k->field = k->pack ? k->pack(g_tune.*k->field, value) : value;
     return USPMV_OK;
 }
 
 int uspmv_get_tuning(const char *key, int *value) {
     if (!key || !value) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_get_tuning: NULL argument");
-    if (!strcmp(key, "unroll")) *value = g_tune.unroll;
-    else if (!strcmp(key, "nontemporal")) *value = g_tune.nontemporal;
-    else if (!strcmp(key, "xcd_remap")) *value = g_tune.xcd_remap & 0xFFFFF;
-    else if (!strcmp(key, "xcd_stagger")) *value = g_tune.xcd_remap >> 20;
-    else if (!strcmp(key, "block")) *value = g_tune.block;
-    else if (!strcmp(key, "spmv_variant")) *value = g_tune.spmv_variant;
-    else if (!strcmp(key, "csr_lanes")) *value = g_tune.csr_lanes;
-    else if (!strcmp(key, "ablate")) *value = g_tune.ablate;
-    else if (!strcmp(key, "spmmv_prefetch")) *value = g_tune.spmmv_prefetch;
-    else if (!strcmp(key, "spmmv_swizzle")) *value = g_tune.spmmv_swizzle;
-    else if (!strcmp(key, "spmmv_reorder")) *value = g_tune.spmmv_reorder;
-    else if (!strcmp(key, "spmmv_brick_stride")) *value = g_tune.spmmv_brick_stride;
-    else if (!strcmp(key, "spmmv_brick_lines")) *value = g_tune.spmmv_brick_lines;
-    else if (!strcmp(key, "spmmv_phase_dp")) *value = g_tune.spmmv_phase_dp;
-    else if (!strcmp(key, "tlc_elem")) *value = g_tune.tlc_elem;
-    else if (!strcmp(key, "tlc_elem_rows")) *value = g_tune.tlc_elem_rows;
-    else if (!strcmp(key, "tlc_elem_seg_rows")) *value = g_tune.tlc_elem_seg_rows;
-    else if (!strcmp(key, "tlc_elem_cap")) *value = g_tune.tlc_elem_cap;
-    else if (!strcmp(key, "spmmv_stream")) *value = g_tune.spmmv_stream;
-    else if (!strcmp(key, "spmmv_stream_xcd")) *value = g_tune.spmmv_stream_xcd;
-    else if (!strcmp(key, "spmmv_stream_waves")) *value = g_tune.spmmv_stream_waves;
-    else if (!strcmp(key, "spmmv_stream_depth")) *value = g_tune.spmmv_stream_depth;
-    else if (!strcmp(key, "spmmv_phased")) *value = g_tune.spmmv_phased;
-    else if (!strcmp(key, "spmmv_xcol")) *value = g_tune.spmmv_xcol;
-    else if (!strcmp(key, "spmmv_ycol_nt")) *value = g_tune.spmmv_ycol_nt;
-    else if (!strcmp(key, "spmmv_xline")) *value = g_tune.spmmv_xline;
-    else if (!strcmp(key, "block_plan_device")) *value = g_tune.block_plan_device;
-    else if (!strcmp(key, "spmmv_unscramble")) *value = g_tune.spmmv_unscramble;
-    else if (!strcmp(key, "spmmv_phase_rows")) *value = g_tune.spmmv_phase_rows;
-    else if (!strcmp(key, "spmmv_idx8")) *value = g_tune.spmmv_idx8;
-    else if (!strcmp(key, "spmmv_list_plan")) *value = g_tune.spmmv_list_plan;
-    else if (!strcmp(key, "sweep")) *value = g_tune.sweep;
-    else if (!strcmp(key, "sweep_nbuf")) *value = g_tune.sweep_nbuf;
-    else if (!strcmp(key, "sweep_unroll")) *value = g_tune.sweep_unroll;
-    else if (!strcmp(key, "sweep_pair")) *value = g_tune.sweep_pair;
-    else if (!strcmp(key, "sweep_remap")) *value = g_tune.sweep_remap;
-    else if (!strcmp(key, "sweep_wlog")) *value = g_tune.sweep_wlog;
-    else if (!strcmp(key, "sweep_tile_rows")) *value = g_tune.sweep_tile_rows;
-    else if (!strcmp(key, "sweep_threads")) *value = g_tune.sweep_threads;
-    else if (!strcmp(key, "sweep_max_stage")) *value = g_tune.sweep_max_stage;
-    else if (!strcmp(key, "raw_plan_cache")) *value = g_tune.raw_plan_cache;
-    else if (!strcmp(key, "spmmv_tile_rows")) *value = g_tune.spmmv_tile_rows;
-    else if (!strcmp(key, "spmmv_lds_kb")) *value = g_tune.spmmv_lds_kb;
-    else if (!strcmp(key, "spmmv_variant")) *value = g_tune.spmmv_variant;
-    else if (!strcmp(key, "tail_batch")) *value = g_tune.tail_batch;
-    else if (!strcmp(key, "spmmv_unroll")) *value = g_tune.spmmv_unroll;
-    else if (!strcmp(key, "tlc")) *value = g_tune.tlc;
-    else if (!strcmp(key, "rechunk")) *value = g_tune.rechunk;
-    else if (!strcmp(key, "tlc_tile_rows")) *value = g_tune.tlc_tile_rows;
-    else if (!strcmp(key, "tlc_auto_tile")) *value = g_tune.tlc_auto_tile;
-    else if (!strcmp(key, "tlc_measure_tile")) *value = g_tune.tlc_measure_tile;
-    else if (!strcmp(key, "tlc_idx12")) *value = g_tune.tlc_idx12;
-    else return uspmv::fail(USPMV_ERR_INVALID, "uspmv_get_tuning: unknown key '%s'", key);
+    const TuneKey *k = find_tune_key(key);
+    if (!k) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_get_tuning: unknown key '%s'", key);
+    *value = k->unpack ? k->unpack(g_tune.*k->field) : g_tune.*k->field;
     return USPMV_OK;
 }
 
@@ -452,581 +412,12 @@ int uspmv_dmat_download(const uspmv_dmat_t *A, int32_t *chunk_ptrs, int32_t *chu
     return USPMV_OK;
 }
 
-static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who);
-static int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, const uspmv_scs_t *sB, int wlog, int tile_rows,
-                              int64_t *n_tiles, int64_t *n_sweep, const char *who);
-// rows per tile of the next tile-local-column plan (g_tune.tlc_tile_rows = 0: by kind)
-static int plan_tile_rows(bool ap) { return g_tune.tlc_tile_rows ? g_tune.tlc_tile_rows : (ap ? 512 : 256); }
-
-// Rows per tile by what the 256-row plan turned out to be (tuning tlc_auto_tile, default on; only when tlc_tile_rows is 0).  The x lines
-// of a tile live in LDS (128 B each): when the largest 256-row tile needs more than 250 of them, at most 4 workgroups = 16 waves fit a
-// CU, too few to cover the staging latency, and every line is fetched by several neighbouring tiles.  1024-row tiles (or 512-row ones)
-// fetch each line fewer times and keep 32 (16) waves per CU when their lines still fit; they are taken when they stage >= 99 % of the
-// tiles.  Measured (tools/tile_rows_sweep.py, profiles/r03/tile_rows_sweep.txt): KKT N = 200 0.82 -> 0.73 ms, banded 30 per row over
-// +-2000 columns 0.27 -> 0.22 ms; matrices whose 256-row tiles need <= 217 lines (all the stencils) are fastest at 256 and stay there.
-static bool tile_rows_grow(int rows, int lines_used) { return g_tune.tlc_auto_tile && g_tune.tlc_tile_rows == 0 && rows == 256 && lines_used > 250; }
-static bool tile_rows_accept(int64_t n_tiles, int64_t n_staged) { return n_staged * 100 >= n_tiles * 99; }
-
-static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, int R, int64_t *n_tiles, int64_t *n_staged, const char *who,
-                                    uspmv_dmat_t *B3 = nullptr);
-
-// For LARGE single structs the rows per tile are MEASURED (tuning tlc_measure_tile, default on; only when tlc_tile_rows is 0): the plan
-// is built on the device for 256, 512 and 1024 rows (two passes over the column indices each), the kernel timed three times on a zero
-// vector, and a larger tile kept when it is more than 3 % ahead of 256.  Why: which size wins depends on how far apart the x lines of
-// neighbouring tiles lie -- the 27-point stencil on 253^3 is fastest at 256 rows, the same stencil on 304^3 (planes of 739 instead of
-// 512 KB: more of the x lines miss the XCD's L2) at 512 (1.249 against 1.341 ms, profiles/r03/tile_rows_sweep.txt).  The choice is
-// remembered per (shape, size) for the life of the process, so the host and the device planner of one matrix agree.  0 = no opinion.
-static int measured_tile_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, const char *who) {
-    if (uspmv_dev::tl_measure_off > 0) return 0;
-    // one measurement at a time, and the verdict table only read / written under the lock (the verdict is keyed on the struct's shape and
-    // size, not its content: two matrices with equal counts share it -- the price of host and device planner of ONE matrix agreeing)
-    static std::mutex mtx;
-    std::lock_guard<std::mutex> lock(mtx);
-    if (!g_tune.tlc_measure_tile || g_tune.tlc_tile_rows != 0 || A->alt || A->C > 256 || 256 % A->C != 0) return 0;
-    if (A->n_chunks * A->C < (int64_t)1 << 20) return 0;
-    if (B && (B->alt || B->C != A->C || B->n_chunks != A->n_chunks || A->dtype != USPMV_F64 || B->dtype != USPMV_F32)) return 0;
-    struct Key { int64_t nc, ne, ne2, C; int dtype, ml; };
-    static std::vector<std::pair<Key, int>> seen;
-    const int64_t ne2 = B ? B->n_elements : -1;
-    for (auto &kv : seen)
-        if (kv.first.nc == A->n_chunks && kv.first.ne == A->n_elements && kv.first.ne2 == ne2 && kv.first.C == A->C && kv.first.dtype == A->dtype && kv.first.ml == max_lines)
-            return kv.second;
-    const size_t vsz = A->dtype == USPMV_F64 ? 8 : 4;
-    DeviceBuf<void> x, y;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int best = 0;
-    auto done = [&]() {
-        x.reset(); y.reset();
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        A->tlc = {};
-        if (B) B->tlc = {};
-    };
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { done(); (void)hipGetLastError(); return 0; }
-    // the size to beat: 256 rows for one struct, 512 for an ap[dp_sp] pair (two entry streams per row, profiles/r02/ap_tile_rows.txt);
-    // it is timed first and once more at the end (the first candidate may have met a cold clock)
-    const int base = B ? 512 : 256;
-    const int order[4] = {base, base == 256 ? 512 : 256, 1024, base};
-    float tmin[3] = {0, 0, 0};                                  // best time seen for 256 / 512 / 1024 rows (0: not usable)
-    auto slot_of = [](int R) { return R == 256 ? 0 : R == 512 ? 1 : 2; };
-    for (int k = 0; k < 4; ++k) {
-        const int R = order[k], slot = slot_of(R), bs = slot_of(base);
-        if (k == 3) {                                           // re-check the base only when something is about to beat it
-            bool beaten = false;
-            for (int o = 0; o < 3; ++o) beaten |= o != bs && tmin[o] > 0 && tmin[bs] > 0 && tmin[o] < 0.97f * tmin[bs];
-            if (!beaten) break;
-        }
-        int64_t nt = 0, ns = 0;
-        if (device_plan_install_rows(A, B, max_lines, R, &nt, &ns, who) != USPMV_OK || !A->tlc.on) { (void)hipGetLastError(); continue; }
-        if (!tile_rows_accept(nt, ns)) continue;
-        if (!x) {
-            const size_t xb = vsz * (size_t)std::max<int64_t>(A->tlc.x_len + 16, 16), yb = vsz * (size_t)std::max<int64_t>(A->n_chunks * A->C, 1);
-            if (x.zeros(xb) != hipSuccess || y.alloc(yb) != hipSuccess) { done(); (void)hipGetLastError(); return 0; }
-        }
-        float ms = 0;
-        bool ok = true;
-        for (int rep = 0; rep < 2 && ok; ++rep) {             // (first round warms up)
-            ok = hipEventRecord(e0, nullptr) == hipSuccess;
-            for (int l = 0; l < 3 && ok; ++l) {
-                if (B) ok = launch_spmv_ap(A, B, (const double *)x, nullptr, (double *)y, nullptr) == USPMV_OK;
-                else ok = (A->dtype == USPMV_F64 ? launch_spmv_tlc<double>(A, nullptr, (long)A->tlc.n_tiles, (const double *)x, (double *)y, nullptr)
-                                                 : launch_spmv_tlc<float>(A, nullptr, (long)A->tlc.n_tiles, (const float *)x, (float *)y, nullptr)) == USPMV_OK;
-            }
-            ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-        }
-        if (!ok) { (void)hipGetLastError(); continue; }
-        if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] measured tile size%s: %d rows -> %.4f ms per SpMV (%lld of %lld tiles staged, %d lines at most)\n", B ? " (ap pair)" : "",
-                                             R, ms / 3, (long long)ns, (long long)nt, A->tlc.max_lines);
-        tmin[slot] = tmin[slot] > 0 ? std::min(tmin[slot], ms) : ms;
-    }
-    // the base size unless another one is more than 3 % ahead of it (the fastest of those that are)
-    {
-        const int bs = slot_of(base);
-        float tbest = tmin[bs] > 0 ? 0.97f * tmin[bs] : 1e30f;
-        best = tmin[bs] > 0 ? base : 0;
-        const int sizes[3] = {256, 512, 1024};
-        for (int o = 0; o < 3; ++o)
-            if (o != bs && tmin[o] > 0 && tmin[o] < tbest) { best = sizes[o]; tbest = tmin[o]; }
-    }
-    done();
-    seen.push_back({Key{A->n_chunks, A->n_elements, ne2, A->C, A->dtype, max_lines}, best});
-    return best;
-}
-
-// The plan's local indices once more in 12 bits (single structs whose tiles list at most 256 lines, i.e. local indices below 4096; even C):
-// what scs_spmv_tlc then streams instead of the 16-bit array -- 1.5 instead of 2 bytes per non-zero.  The 16-bit array stays (the
-// adaptive-precision kernels, uspmv_dmat_plan_download and the plan digests read it).  cl: the chunk lengths when the caller has them on
-// the host, else they are copied back (4 bytes per chunk).
-static int tlc_pack12(uspmv_dmat_t *A, const std::vector<int32_t> *cl, const char *who) {
-    if (!A->tlc.on || !g_tune.tlc_idx12 || (A->tlc.elem ? A->tlc.max_lines > 4096 : A->tlc.max_lines > 256) || A->C < 2 || A->C % 2 != 0 || A->n_chunks < 1) return USPMV_OK;
-    std::vector<int32_t> own;
-    if (!cl || (int64_t)cl->size() != A->n_chunks) {
-        own.resize((size_t)A->n_chunks);
-        HIP_TRY(hipMemcpy(own.data(), A->chunk_lengths, 4 * (size_t)A->n_chunks, hipMemcpyDeviceToHost));
-        cl = &own;
-    }
-    const int64_t C = A->C, nc = A->n_chunks;
-    std::vector<uint32_t> p12((size_t)nc + 1);
-    int64_t tot = 0;                                             // dwords
-    for (int64_t c = 0; c < nc; ++c) {
-        p12[(size_t)c] = (uint32_t)tot;
-        const int64_t ngt = ((int64_t)(*cl)[(size_t)c] + 3) / 4;
-        tot += (ngt / 2) * 3 * C + (ngt & 1) * (C + C / 2);
-        if (tot > (int64_t)UINT32_MAX) return USPMV_OK;          // (too large for 32-bit offsets: the 16-bit array serves)
-    }
-    p12[(size_t)nc] = (uint32_t)tot;
-    hipError_t e = A->tlc.c12_ptrs.upload(p12.data(), 4 * ((size_t)nc + 1));
-    if (e == hipSuccess) e = A->tlc.col12.alloc(4 * (size_t)std::max<int64_t>(tot, 1));
-    if (e == hipSuccess && uspmv_dev::launch_plan_pack12(A, A->tlc.c16_ptrs, A->tlc.col16, A->tlc.c12_ptrs, A->tlc.col12, nullptr) != USPMV_OK) e = hipErrorUnknown;
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        A->tlc.c12_ptrs.reset(); A->tlc.col12.reset();
-        return uspmv::fail(USPMV_ERR_HIP, "%s: packing the local indices to 12 bits failed: %s", who, hipGetErrorString(e));
-    }
-    // Keep it?  Rows of a dozen entries gain or lose a per cent either way (one more load instruction per row for an odd last group), long
-    // rows gain 1-15 % depending on matrix and box (profiles/r04/idx12_probe_*.txt: the 253^3 stencil 0.763 -> 0.691 ms on a slow box, 0.710 ->
-    // 0.700 on a fast one; 304^3 between -15 % and +2 %).  The rule is a fixed one -- mean row length >= 8 -- and not a timing on the spot
-    // (which was built first): a bench run, its counter passes and its profiler run must execute the same kernel, and a 1-2 % verdict
-    // flips under a profiler's overhead.  "tlc_idx12" 2 keeps it regardless, 0 never builds it.
-    if (g_tune.tlc_idx12 != 2 && (double)A->n_elements < 8.0 * (double)(nc * C)) { A->tlc.c12_ptrs.reset(); A->tlc.col12.reset(); }
-    return USPMV_OK;
-}
-
-// A quick look before an element plan is built in full (a sort per tile over all entries): of ~64 tiles spread over the struct, how many list more distinct
-// columns than `cap`?  true: more than a tenth of them -- the element plan would be turned down anyway (wide irregular rows: the sweep's matrices).
-static double elements_over_cap_frac(const uspmv_scs_t *s, int cap, int tile_rows) {
-    const int64_t C = s->C, T = std::max<int64_t>(1, tile_rows / C), nt = (s->n_chunks + T - 1) / T;
-    const int64_t step = std::max<int64_t>(1, nt / 64);
-    int64_t seen = 0, over = 0;
-    std::vector<int32_t> cols;
-    for (int64_t t = step / 2; t < nt; t += step) {
-        const int64_t c0 = t * T, c1 = std::min<int64_t>(c0 + T, s->n_chunks);
-        cols.assign(s->col_idxs.begin() + s->chunk_ptrs[(size_t)c0], s->col_idxs.begin() + s->chunk_ptrs[(size_t)c1]);
-        std::sort(cols.begin(), cols.end());
-        const int64_t n = (int64_t)(std::unique(cols.begin(), cols.end()) - cols.begin());
-        ++seen; over += n > cap;
-    }
-    return seen > 0 ? (double)over / (double)seen : 1.0;
-}
-static bool elements_over_cap(const uspmv_scs_t *s, int cap, int tile_rows) { return elements_over_cap_frac(s, cap, tile_rows) > 0.1; }
-
-int uspmv_dmat_optimize(uspmv_dmat_t *A, const uspmv_scs_t *s, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    if (!A || !s) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize: NULL argument");
-    if (int rc = check_dmat_one_prec(A, "uspmv_dmat_optimize")) return rc;
-    if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize: layout-only struct; the plan builder needs the host column indices");
-    if (A->C != s->C || A->n_chunks != s->n_chunks || A->dtype != s->dtype)
-        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize: handle and host struct do not describe the same matrix");
-    if (int rc = require_device()) return rc;
-    A->tlc = {};
-    if (A->alt) { uspmv_dmat_free(A->alt); A->alt = nullptr; }
-    if (s->C < 32 && 32 % s->C == 0 && g_tune.rechunk) {
-        // narrow chunks (incl. crs = C 1): run on an internal C = 32 re-chunking with the same row order
-        uspmv_scs r;
-        int rc = uspmv_scs_rechunk32(s, &r);
-        if (rc == USPMV_OK && (double)r.n_elements <= 1.25 * (double)std::max<int64_t>(s->n_elements, 1) + 4096) {
-            uspmv_dmat_t *alt = nullptr;
-            if (int rc2 = uspmv_dmat_upload(&r, &alt)) return rc2;
-            alt->n_store = (long)(s->n_chunks * s->C);      // y of the caller has only the original padded rows
-            rc = uspmv_dmat_optimize(alt, &r, max_lines, n_tiles, n_staged);   // (C = 32: does not re-enter this branch)
-            if (rc) { uspmv_dmat_free(alt); return rc; }
-            A->alt = alt;
-            return USPMV_OK;
-        }
-    }
-    const bool own_budget = max_lines > 0;                     // (a caller with a line budget of its own keeps the line plan: no element fallback)
-    if (max_lines <= 0) max_lines = 512;                       // 64 KiB of doubles: 2 workgroups per CU at worst
-    const int cap = (int)(160 * 1024 / (16 * (s->dtype == USPMV_F64 ? 8 : 4)));
-    if (max_lines > cap) max_lines = cap;
-    uspmv_tlc_plan p;
-    const int R_meas = measured_tile_rows(A, nullptr, max_lines, "uspmv_dmat_optimize");
-    if (int rc = uspmv_build_tlc_plan(s, nullptr, max_lines, R_meas ? R_meas : plan_tile_rows(false), &p)) return rc;
-    if (!R_meas && p.valid && tile_rows_grow(p.tile_rows, p.max_lines_used))
-        for (int R : {1024, 512}) {
-            uspmv_tlc_plan q;
-            if (int rc = uspmv_build_tlc_plan(s, nullptr, max_lines, R, &q)) return rc;
-            if (q.valid && tile_rows_accept(q.n_tiles, q.n_staged_tiles)) { p = std::move(q); break; }
-        }
-    if (n_tiles) *n_tiles = p.n_tiles;
-    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
-    if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] tlc plan: tile_rows=%d tiles=%lld staged=%lld max_lines=%d lines_total=%zu col16=%zu\n",
-                                         p.tile_rows, (long long)p.n_tiles, (long long)p.n_staged_tiles, p.max_lines_used, p.tile_lines.size(), p.col16.size());
-    A->sw = {};
-    bool elem = false;
-    if (((!own_budget && (!p.valid || p.n_staged_tiles * 10 < p.n_tiles * 9)) || g_tune.tlc_elem == 2) && g_tune.tlc_elem && uspmv_dev::tl_measure_off == 0) {   // (2: measurement aid, always try)
-        // columns scattered over many lines (x in a numbering that is only loosely related to the rows'): the line plan leaves a tenth of the tiles or
-        // more to the gather path.  List the tile's distinct ELEMENTS instead -- taken when (nearly) every tile fits and an element serves four
-        // entries or more on average (else the line plan stays, or the column-window sweep takes over below).  Measured (tools/numbering_probe.py,
-        // profiles/r04/numbering_probe_*.txt): 27-point x 3 dof stencil with x renumbered at random inside blocks of 1 000 / 5 000 / 20 000 nodes 0.97 / 0.90 /
-        // 0.89 of the roofline against 0.74 (line plan, 69 % of the tiles staged) / 0.70 / 0.61 (sweep); 1 dof, 4.2 entries per element: 0.65 against 0.59;
-        // on a regular numbering the line plan is 20 % ahead (0.683 against 0.819 ms on the 253^3 stencil), which is why this is a fallback only.
-        uspmv_tlc_plan q;
-        const int ecap = std::min(g_tune.tlc_elem_cap, (int)(64 * 1024 / (s->dtype == USPMV_F64 ? 8 : 4)));
-        if (!elements_over_cap(s, ecap, 256))
-            if (int rc = uspmv_build_tlc_plan(s, nullptr, ecap, 256, &q, /*line_shift=*/0)) return rc;
-        if (q.valid && tile_rows_accept(q.n_tiles, q.n_staged_tiles) && ((double)q.tile_lines.size() * 4.0 <= (double)s->n_elements || g_tune.tlc_elem == 2)) {
-            p = std::move(q); elem = true;
-            if (n_tiles) *n_tiles = p.n_tiles;
-            if (n_staged) *n_staged = p.n_staged_tiles;
-            if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] tlc plan over single x elements: tiles=%lld staged=%lld max_elements=%d elements_total=%zu (%.1f entries per element)\n",
-                                                 (long long)p.n_tiles, (long long)p.n_staged_tiles, p.max_lines_used, p.tile_lines.size(), (double)s->n_elements / (double)std::max<size_t>(p.tile_lines.size(), 1));
-        }
-    }
-    // ... and when the ROWS of a tile are scattered as well (rows and columns renumbered alike: a tile of 256 consecutive rows is no compact piece of the
-    // mesh any more): deal the rows to the tiles by the matrix graph first, as the block plan does (uspmv_scs_reorder_rows mode 4: rows change places
-    // only with rows of equal-length chunks, every row keeps its slot sequence), then the element plan on that order -- a private copy of the values
-    // (8 / 4 bytes per element of HBM), of the column indices (for the few tiles that do not stage) and a row map for y.
-    uspmv_scs rr;
-    std::vector<int32_t> rr_map;
-    bool reordered = false;
-    if (!elem && !own_budget && (!p.valid || p.n_staged_tiles * 10 < p.n_tiles * 9) && g_tune.tlc_elem && g_tune.tlc_elem_rows && uspmv_dev::tl_measure_off == 0 && s->n_rows == s->n_cols) {
-        const int ecap = std::min(g_tune.tlc_elem_cap, (int)(64 * 1024 / (s->dtype == USPMV_F64 ? 8 : 4)));
-        // first with the clusters confined to segments of tlc_elem_seg_rows rows (64 Ki: many segments in parallel, and a trial on a sample of them that stops
-        // irregular matrices early); when that leaves some, but not most, of the sampled tiles over the cap -- related rows further apart than a segment --
-        // once more with segments of 2^20 rows (a second or more of clustering per million rows on few threads: only where it looks promising)
-        const int64_t seg_stage[2] = {(int64_t)g_tune.tlc_elem_seg_rows, (int64_t)1 << 20};
-        for (int stage = 0; stage < 2 && !reordered; ++stage) {
-            if (stage == 1 && seg_stage[1] <= seg_stage[0]) break;
-            if (uspmv_scs_reorder_rows(s, g_tune.tlc_elem_rows == 4 ? 4 : 2, &rr, &rr_map, g_tune.tlc_elem_rows == 4 ? 64 : 256, seg_stage[stage]) != 1) break;
-            const double over = elements_over_cap_frac(&rr, ecap, 256);
-            uspmv_tlc_plan q;
-            if (over <= 0.1)
-                if (int rc = uspmv_build_tlc_plan(&rr, nullptr, ecap, 256, &q, /*line_shift=*/0)) return rc;
-            if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] element plan on the graph-dealt rows (segments of %lld rows): %.0f %% of the sampled tiles over the cap; valid=%d tiles=%lld staged=%lld max_elements=%d (cap %d) elements_total=%zu\n",
-                                                 (long long)seg_stage[stage], 100.0 * over, (int)q.valid, (long long)q.n_tiles, (long long)q.n_staged_tiles, q.max_lines_used, ecap, q.tile_lines.size());
-            // (19 of 20 tiles staged is enough here: what would run instead -- sweep or gather kernel -- is 2 x slower on such matrices)
-            if (q.valid && q.n_staged_tiles * 20 >= q.n_tiles * 19 && (double)q.tile_lines.size() * 4.0 <= (double)s->n_elements) {
-                p = std::move(q); elem = true; reordered = true;
-                if (n_tiles) *n_tiles = p.n_tiles;
-                if (n_staged) *n_staged = p.n_staged_tiles;
-                if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] tlc plan over single x elements, rows dealt to the tiles by the matrix graph: tiles=%lld max_elements=%d elements_total=%zu (%.1f entries per element)\n",
-                                                     (long long)p.n_tiles, p.max_lines_used, p.tile_lines.size(), (double)s->n_elements / (double)std::max<size_t>(p.tile_lines.size(), 1));
-            } else if (over > 0.6) break;                    // most tiles far over the cap: larger segments will not repair that
-        }
-    }
-    if (!elem && (!p.valid || p.n_staged_tiles * 2 < p.n_tiles) && g_tune.sweep) {
-        // wide, irregular rows: most tiles touch too many x lines to stage them.  Try the column-window sweep; it takes over
-        // when it covers at least half of the rows.
-        int64_t swt = 0, sws = 0;
-        if (int rc = sweep_plan_install(A, nullptr, s, nullptr, 0, 0, &swt, &sws, "uspmv_dmat_optimize")) return rc;
-        if (A->sw.on && sws * 2 >= swt) return USPMV_OK;
-        A->sw = {};
-    }
-    if (!p.valid) return USPMV_OK;                              // nothing worth staging: plain kernel stays
-    hipError_t e = A->tlc.line_ptr.upload(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4);
-    if (e == hipSuccess) e = A->tlc.lines.upload(p.tile_lines.data(), p.tile_lines.size() * 4);
-    if (e == hipSuccess) e = A->tlc.c16_ptrs.upload(p.c16_ptrs.data(), p.c16_ptrs.size() * 4);
-    if (e == hipSuccess) e = A->tlc.col16.upload(p.col16.data(), p.col16.size() * 2);
-    if (e == hipSuccess && reordered) {
-        e = A->tlc.values.upload(rr.values_ptr(), (size_t)rr.n_elements * (rr.dtype == USPMV_F64 ? 8 : 4));
-        if (e == hipSuccess) e = A->tlc.row_map.upload(rr_map.data(), rr_map.size() * 4);
-        if (e == hipSuccess && p.n_staged_tiles < p.n_tiles) e = A->tlc.cols.upload(rr.col_idxs.data(), (size_t)rr.n_elements * 4);
-    }
-    if (e != hipSuccess) {
-        A->tlc = {};
-        return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize: device copy failed: %s", hipGetErrorString(e));
-    }
-    A->tlc.on = true; A->tlc.tile_rows = p.tile_rows; A->tlc.max_lines = p.max_lines_used; A->tlc.x_len = p.x_len_min; A->tlc.n_tiles = p.n_tiles;
-    A->tlc.staged = p.n_staged_tiles; A->tlc.elem = elem;
-    return tlc_pack12(A, &s->chunk_lengths, "uspmv_dmat_optimize");
-}
-
-// 16-bit index offsets per chunk from the chunk lengths (O(n_chunks) on the host); false: too large for 32-bit offsets
-static bool c16_offsets(const std::vector<int32_t> &cl, int64_t C, std::vector<uint32_t> *c16p, int64_t *tot16) {
-    const int64_t nc = (int64_t)cl.size();
-    c16p->assign((size_t)nc + 1, 0);
-    int64_t tot = 0;
-    for (int64_t c = 0; c < nc; ++c) {
-        (*c16p)[(size_t)c] = (uint32_t)tot;
-        tot += ((int64_t)(cl[(size_t)c] + 3) / 4) * 4 * C;
-        if (tot > (int64_t)UINT32_MAX) return false;
-    }
-    (*c16p)[(size_t)nc] = (uint32_t)tot;
-    *tot16 = tot;
-    return true;
-}
-
-// the tile-local-column plan of A (and of the pair A + B sharing one line list when B != nullptr), built on the device
-// ... with the rows per tile chosen as uspmv_dmat_optimize chooses them (measured_tile_rows / tile_rows_grow above)
-static int device_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, int64_t *n_tiles, int64_t *n_staged, const char *who) {
-    if (!B) {
-        const int ml = std::min(std::min(max_lines <= 0 ? 512 : max_lines, (int)(160 * 1024 / (16 * (A->dtype == USPMV_F64 ? 8 : 4)))), 4096);
-        if (const int R_meas = measured_tile_rows(A, nullptr, ml, who)) return device_plan_install_rows(A, nullptr, max_lines, R_meas, n_tiles, n_staged, who);
-    } else {
-        const int ml = std::min(std::min(max_lines <= 0 ? 512 : max_lines, (int)(160 * 1024 / (16 * 8))), 1280);
-        if (const int R_meas = measured_tile_rows(A, B, ml, who)) return device_plan_install_rows(A, B, max_lines, R_meas, n_tiles, n_staged, who);
-    }
-    const int R0 = plan_tile_rows(B != nullptr);
-    if (int rc = device_plan_install_rows(A, B, max_lines, R0, n_tiles, n_staged, who)) return rc;
-    if (B || !A->tlc.on || !tile_rows_grow(R0, A->tlc.max_lines)) return USPMV_OK;
-    for (int R : {1024, 512}) {
-        int64_t nt = 0, ns = 0;
-        if (int rc = device_plan_install_rows(A, nullptr, max_lines, R, &nt, &ns, who)) return rc;
-        if (A->tlc.on && tile_rows_accept(nt, ns)) { if (n_tiles) *n_tiles = nt; if (n_staged) *n_staged = ns; return USPMV_OK; }
-    }
-    return device_plan_install_rows(A, nullptr, max_lines, R0, n_tiles, n_staged, who);
-}
-
-// (B3: a third struct sharing the plan -- the hp part of ap[dp_sp_hp]; only with B)
-static int device_plan_install_rows(uspmv_dmat_t *A, uspmv_dmat_t *B, int max_lines, const int R, int64_t *n_tiles, int64_t *n_staged, const char *who,
-                                    uspmv_dmat_t *B3) {
-    A->tlc = {};
-    if (B) B->tlc = {};
-    if (B3) B3->tlc = {};
-    if (n_tiles) *n_tiles = 0;
-    if (n_staged) *n_staged = 0;
-    const int64_t C = A->C, nc = A->n_chunks;
-    if (C > 256 || 256 % C != 0 || nc < 1) return USPMV_OK;                    // shape without a plan
-    if (max_lines <= 0) max_lines = 512;
-    max_lines = std::min(max_lines, (int)(160 * 1024 / (16 * (A->dtype == USPMV_F64 ? 8 : 4))));
-    max_lines = std::min(max_lines, B ? 1280 : 4096);
-    const int64_t T = R / C, nt = (nc + T - 1) / T;
-    std::vector<int32_t> cl((size_t)nc);
-    std::vector<uint32_t> c16p, c16p_b, c16p_c;
-    int64_t tot16 = 0, tot16_b = 0, tot16_c = 0;
-    HIP_TRY(hipMemcpy(cl.data(), A->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
-    if (!c16_offsets(cl, C, &c16p, &tot16)) return USPMV_OK;
-    if (B) {
-        HIP_TRY(hipMemcpy(cl.data(), B->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
-        if (!c16_offsets(cl, C, &c16p_b, &tot16_b)) return USPMV_OK;
-    }
-    if (B3) {
-        HIP_TRY(hipMemcpy(cl.data(), B3->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
-        if (!c16_offsets(cl, C, &c16p_c, &tot16_c)) return USPMV_OK;
-    }
-    DeviceBuf<int> d_n, d_max;
-    hipError_t e = d_n.alloc(4 * (size_t)nt);
-    if (e == hipSuccess) e = d_max.zeros(4);
-    if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-    int rc = launch_plan_count(A, (long)nt, max_lines, d_n, d_max, nullptr, B, R, B3);
-    std::vector<int32_t> lp((size_t)nt + 1, 0);
-    int max_col = 0;
-    if (!rc) {
-        e = hipMemcpy(lp.data() + 1, d_n, 4 * (size_t)nt, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(&max_col, d_max, 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    d_n.reset(); d_max.reset();
-    if (rc) return rc;
-    int64_t staged = 0, total = 0;
-    int used = 0;
-    for (int64_t t = 0; t < nt; ++t) {
-        const int n = lp[(size_t)t + 1];
-        staged += n > 0; used = std::max(used, n);
-        total += n;
-        if (total > INT32_MAX) return USPMV_OK;
-        lp[(size_t)t + 1] = (int32_t)total;
-    }
-    if (n_tiles) *n_tiles = nt;
-    if (n_staged) *n_staged = staged;
-    if (staged == 0) return USPMV_OK;
-    e = A->tlc.line_ptr.upload(lp.data(), 4 * ((size_t)nt + 1));
-    if (e == hipSuccess) e = A->tlc.lines.alloc(4 * (size_t)std::max<int64_t>(total, 1));
-    if (e == hipSuccess) e = A->tlc.c16_ptrs.upload(c16p.data(), 4 * ((size_t)nc + 1));
-    if (e == hipSuccess) e = A->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16, 1));   // padded slots: index 0
-    if (B) {
-        if (e == hipSuccess) e = B->tlc.c16_ptrs.upload(c16p_b.data(), 4 * ((size_t)nc + 1));
-        if (e == hipSuccess) e = B->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16_b, 1));
-    }
-    if (B3) {
-        if (e == hipSuccess) e = B3->tlc.c16_ptrs.upload(c16p_c.data(), 4 * ((size_t)nc + 1));
-        if (e == hipSuccess) e = B3->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16_c, 1));
-    }
-    if (e == hipSuccess && launch_plan_write(A, (long)nt, A->tlc.line_ptr, A->tlc.c16_ptrs, A->tlc.lines, A->tlc.col16, nullptr, B,
-                                             B ? B->tlc.c16_ptrs : nullptr, B ? B->tlc.col16 : nullptr, R, B3,
-                                             B3 ? B3->tlc.c16_ptrs : nullptr, B3 ? B3->tlc.col16 : nullptr) != USPMV_OK)
-        e = hipErrorUnknown;
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        A->tlc = {};
-        if (B) B->tlc = {};
-        if (B3) B3->tlc = {};
-        return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    static uint64_t next_dev_plan_id = (uint64_t)1 << 40;
-    const uint64_t id = B ? next_dev_plan_id++ : 0;
-    for (uspmv_dmat_t *M : {A, B, B3}) {
-        if (!M) continue;
-        M->tlc.on = true; M->tlc.tile_rows = R; M->tlc.max_lines = used; M->tlc.x_len = (int64_t)max_col + 1; M->tlc.n_tiles = nt;
-        M->tlc.staged = staged; M->tlc.plan_id = id;
-    }
-    if (!B) return tlc_pack12(A, nullptr, who);
-    return USPMV_OK;
-}
-
-// as uspmv_dmat_optimize[_ap]: when the tile-local-column plan stages fewer than half of the tiles (wide, irregular rows), try the
-// column-window sweep -- built on the device as well -- and let it take over when it covers at least half of the tiles
-static int device_sweep_if_irregular(uspmv_dmat_t *A, uspmv_dmat_t *B, int64_t * /*n_tiles*/, int64_t * /*n_staged*/, const char *who) {
-    A->sw = {};
-    if (B) B->sw = {};
-    if (!g_tune.sweep || (A->tlc.on && A->tlc.staged * 2 >= A->tlc.n_tiles)) return USPMV_OK;
-    int64_t swt = 0, sws = 0;
-    if (int rc = sweep_plan_install_device(A, B, 0, 0, &swt, &sws, who)) return rc;
-    if (A->sw.on && sws * 2 >= swt) {
-        A->tlc = {};         // (n_tiles / n_staged keep describing the tile-local-column attempt, as in uspmv_dmat_optimize;
-        if (B) B->tlc = {};    //  uspmv_dmat_plan_info tells which plan the handle ended up with)
-        return USPMV_OK;
-    }
-    if (A->sw.on) { A->sw = {}; if (B) B->sw = {}; }
-    return USPMV_OK;
-}
-
-int uspmv_dmat_optimize_device(uspmv_dmat_t *A, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    if (int rc = check_dmat_one_prec(A, "uspmv_dmat_optimize_device")) return rc;
-    if (int rc = require_device()) return rc;
-    if (A->alt) { uspmv_dmat_free(A->alt); A->alt = nullptr; }
-    if (A->C < 32 && 32 % A->C == 0 && g_tune.rechunk && A->n_chunks > 0) {
-        // narrow chunks (incl. crs = C 1): the internal C = 32 re-chunking of uspmv_dmat_optimize, built on the device --
-        // O(n_chunks) layout on the host, the O(n_elements) copy by rechunk32_kernel
-        const int64_t C = A->C, nc_old = A->n_chunks, per = 32 / C, nc = (nc_old + per - 1) / per;
-        std::vector<int32_t> cl_old((size_t)nc_old), cl((size_t)nc, 0), cp((size_t)nc + 1, 0);
-        int32_t last = 0;
-        HIP_TRY(hipMemcpy(cl_old.data(), A->chunk_lengths, 4 * (size_t)nc_old, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&last, A->chunk_ptrs + nc_old, 4, hipMemcpyDeviceToHost));
-        int64_t cur = 0;
-        bool fits = true;
-        for (int64_t k = 0; k < nc && fits; ++k) {
-            int32_t L = 0;
-            for (int64_t c = k * per; c < std::min((k + 1) * per, nc_old); ++c) L = std::max(L, cl_old[(size_t)c]);
-            cl[(size_t)k] = L; cp[(size_t)k] = (int32_t)cur;
-            cur += (int64_t)L * 32;
-            fits = cur <= INT32_MAX;
-        }
-        if (fits && (double)cur <= 1.25 * (double)std::max<int64_t>(last, 1) + 4096) {
-            cp[(size_t)nc] = (int32_t)cur;
-            auto *alt = new uspmv_dmat;
-            alt->C = 32; alt->n_chunks = nc; alt->n_elements = cur; alt->dtype = A->dtype;
-            alt->n_store = (long)(nc_old * C);              // y of the caller has only the original padded rows
-            const size_t vsz = A->dtype == USPMV_F64 ? 8 : 4, ne = (size_t)std::max<int64_t>(cur, 1);
-            hipError_t e = alt->own_arrays();
-            if (e == hipSuccess) e = hipMemcpy(alt->own.chunk_ptrs, cp.data(), 4 * ((size_t)nc + 1), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(alt->own.chunk_lengths, cl.data(), 4 * (size_t)nc, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemsetAsync(alt->own.col_idxs, 0, 4 * ne, nullptr);
-            if (e == hipSuccess) e = hipMemsetAsync(alt->own.values, 0, vsz * ne, nullptr);
-            int rc = e == hipSuccess ? launch_rechunk32(A, alt->chunk_ptrs, alt->own.col_idxs, alt->own.values, nullptr) : uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize_device: %s", hipGetErrorString(e));
-            if (!rc) rc = device_plan_install(alt, nullptr, max_lines, n_tiles, n_staged, "uspmv_dmat_optimize_device");
-            if (!rc) rc = device_sweep_if_irregular(alt, nullptr, n_tiles, n_staged, "uspmv_dmat_optimize_device");
-            if (rc) { uspmv_dmat_free(alt); return rc; }
-            A->tlc = {};
-            A->alt = alt;
-            return USPMV_OK;
-        }
-    }
-    if (int rc = device_plan_install(A, nullptr, max_lines, n_tiles, n_staged, "uspmv_dmat_optimize_device")) return rc;
-    return device_sweep_if_irregular(A, nullptr, n_tiles, n_staged, "uspmv_dmat_optimize_device");
-}
-
-int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    if (int rc = check_dmat(dp, "uspmv_dmat_optimize_device_ap")) return rc;
-    if (int rc = check_dmat(sp, "uspmv_dmat_optimize_device_ap")) return rc;
-    if (dp->dtype != USPMV_F64 || sp->dtype != USPMV_F32 || dp->C != sp->C || dp->n_chunks != sp->n_chunks)
-        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_device_ap: handles do not form a dp+sp pair");
-    if (int rc = require_device()) return rc;
-    if (int rc = device_plan_install(dp, sp, max_lines, n_tiles, n_staged, "uspmv_dmat_optimize_device_ap")) return rc;
-    return device_sweep_if_irregular(dp, sp, n_tiles, n_staged, "uspmv_dmat_optimize_device_ap");
-}
-
-// the parts of an ap split with an fp16 part: hi F64 | F32, mid F32 (hi F64) or NULL, hp F16, one row layout
-static int check_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const char *who) {
-    if (int rc = check_dmat(hi, who)) return rc;
-    if (int rc = check_dmat(hp, who)) return rc;
-    if (mid) if (int rc = check_dmat(mid, who)) return rc;
-    const bool ok = hp->dtype == USPMV_F16 && (mid ? hi->dtype == USPMV_F64 && mid->dtype == USPMV_F32 : hi->dtype == USPMV_F64 || hi->dtype == USPMV_F32);
-    if (!ok) return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts must be (F64, -, F16), (F32, -, F16) or (F64, F32, F16)", who);
-    if (hi->C != hp->C || hi->n_chunks != hp->n_chunks || (mid && (mid->C != hi->C || mid->n_chunks != hi->n_chunks)))
-        return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts must share C and n_chunks", who);
-    return USPMV_OK;
-}
-
-// shared plans of the two or three parts: the line plan where it stages at least half of the tiles, otherwise none (no sweep for hp parts)
-static bool ap_hp_plan_worth(int64_t n_tiles, int64_t n_staged) { return n_staged > 0 && n_staged * 2 >= n_tiles; }
-
-int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
-                              const uspmv_scs_t *s_hp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    const char *who = "uspmv_dmat_optimize_ap_hp";
-    if (!s_hi || !s_hp || (mid && !s_mid)) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
-    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
-    const uspmv_scs_t *ss[3] = {s_hi, mid ? s_mid : s_hp, mid ? s_hp : nullptr};
-    uspmv_dmat_t *ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
-    for (int k = 0; k < 3; ++k) {
-        if (!ms[k]) continue;
-        if (!uspmv::scs_has_entries(ss[k]))
-            return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host column indices", who);
-        if (ms[k]->C != ss[k]->C || ms[k]->n_chunks != ss[k]->n_chunks || ms[k]->dtype != ss[k]->dtype)
-            return uspmv::fail(USPMV_ERR_INVALID, "%s: handles and host structs do not describe the same parts", who);
-    }
-    if (int rc = require_device()) return rc;
-    for (uspmv_dmat_t *M : ms) if (M) { M->tlc = {}; M->sw = {}; }
-    if (n_tiles) *n_tiles = 0;
-    if (n_staged) *n_staged = 0;
-    if (max_lines <= 0) max_lines = 512;
-    if (max_lines > 1280) max_lines = 1280;
-    uspmv_tlc_plan p;
-    if (int rc = uspmv_build_tlc_plan(ss[0], ss[1], max_lines, plan_tile_rows(true), &p, 4, ss[2])) return rc;
-    if (n_tiles) *n_tiles = p.n_tiles;
-    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
-    if (!p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
-    hipError_t e = hi->tlc.line_ptr.upload(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4);
-    if (e == hipSuccess) e = hi->tlc.lines.upload(p.tile_lines.data(), p.tile_lines.size() * 4);
-    if (e == hipSuccess) e = hi->tlc.c16_ptrs.upload(p.c16_ptrs.data(), p.c16_ptrs.size() * 4);
-    if (e == hipSuccess) e = hi->tlc.col16.upload(p.col16.data(), p.col16.size() * 2);
-    if (e == hipSuccess) e = ms[1]->tlc.c16_ptrs.upload(p.c16_ptrs_b.data(), p.c16_ptrs_b.size() * 4);
-    if (e == hipSuccess) e = ms[1]->tlc.col16.upload(p.col16_b.data(), p.col16_b.size() * 2);
-    if (ms[2] && e == hipSuccess) e = ms[2]->tlc.c16_ptrs.upload(p.c16_ptrs_c.data(), p.c16_ptrs_c.size() * 4);
-    if (ms[2] && e == hipSuccess) e = ms[2]->tlc.col16.upload(p.col16_c.data(), p.col16_c.size() * 2);
-    if (e != hipSuccess) {
-        for (uspmv_dmat_t *M : ms) if (M) M->tlc = {};
-        return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
-    }
-    static uint64_t next_hp_plan_id = (uint64_t)1 << 48;       // (apart from the ids of uspmv_dmat_optimize_ap and the device planner)
-    const uint64_t id = next_hp_plan_id++;
-    for (uspmv_dmat_t *M : ms) {
-        if (!M) continue;
-        M->tlc.on = true; M->tlc.tile_rows = p.tile_rows; M->tlc.max_lines = p.max_lines_used; M->tlc.x_len = p.x_len_min;
-        M->tlc.n_tiles = p.n_tiles; M->tlc.staged = p.n_staged_tiles; M->tlc.plan_id = id;
-    }
-    return USPMV_OK;
-}
-
-int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    const char *who = "uspmv_dmat_optimize_device_ap_hp";
-    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
-    if (int rc = require_device()) return rc;
-    uspmv_dmat_t *ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
-    for (uspmv_dmat_t *M : ms) if (M) M->sw = {};
-    int64_t nt = 0, ns = 0;
-    if (int rc = device_plan_install_rows(ms[0], ms[1], max_lines, plan_tile_rows(true), &nt, &ns, who, ms[2])) return rc;
-    if (n_tiles) *n_tiles = nt;
-    if (n_staged) *n_staged = ns;
-    if (!ap_hp_plan_worth(nt, ns))
-        for (uspmv_dmat_t *M : ms) if (M) M->tlc = {};
-    return USPMV_OK;
-}
-
 int uspmv_spmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, void *d_y, void *stream) {
     if (int rc = check_ap_hp(hi, mid, hp, "uspmv_spmv_ap_hp")) return rc;
     if (!d_x || !d_y) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_ap_hp: NULL vector");
     if (int rc = require_device()) return rc;
     if (hi->n_chunks == 0) return USPMV_OK;
     return launch_spmv_ap_hp(hi, mid, hp, d_x, d_y, (hipStream_t)stream);
-}
-
-int uspmv_dmat_plan_download(const uspmv_dmat_t *A, int64_t meta[4], int32_t *tile_line_ptr, int32_t *tile_lines, uint32_t *c16_ptrs,
-                             uint16_t *col16) {
-    if (int rc = check_dmat(A, "uspmv_dmat_plan_download")) return rc;
-    if (!meta) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_plan_download: NULL meta");
-    meta[0] = meta[1] = meta[2] = meta[3] = 0;
-    if (!A->tlc.on) return USPMV_OK;
-    if (int rc = require_device()) return rc;
-    int32_t last = 0; uint32_t last16 = 0;
-    // (the second and third part of a shared ap plan hold only their local indices: the line list lives with the first part)
-    if (A->tlc.line_ptr) HIP_TRY(hipMemcpy(&last, A->tlc.line_ptr + A->tlc.n_tiles, 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&last16, A->tlc.c16_ptrs + A->n_chunks, 4, hipMemcpyDeviceToHost));
-    meta[0] = A->tlc.n_tiles; meta[1] = last; meta[2] = last16; meta[3] = A->tlc.max_lines;
-    if (tile_line_ptr && A->tlc.line_ptr) HIP_TRY(hipMemcpy(tile_line_ptr, A->tlc.line_ptr, 4 * ((size_t)A->tlc.n_tiles + 1), hipMemcpyDeviceToHost));
-    if (tile_lines && last) HIP_TRY(hipMemcpy(tile_lines, A->tlc.lines, 4 * (size_t)last, hipMemcpyDeviceToHost));
-    if (c16_ptrs) HIP_TRY(hipMemcpy(c16_ptrs, A->tlc.c16_ptrs, 4 * ((size_t)A->n_chunks + 1), hipMemcpyDeviceToHost));
-    if (col16 && last16) HIP_TRY(hipMemcpy(col16, A->tlc.col16, 2 * (size_t)last16, hipMemcpyDeviceToHost));
-    return USPMV_OK;
 }
 
 extern "C++" {
@@ -1350,56 +741,11 @@ int uspmv_dmat_optimize_block_device(uspmv_dmat_t *A, int block_vec_size, int64_
     return uspmv_dmat_optimize_block(M, &s, block_vec_size, n_tiles, n_staged);
 }
 
-int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t *s_dp, const uspmv_scs_t *s_sp,
-                           int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    if (!dp || !sp || !s_dp || !s_sp) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_ap: NULL argument");
-    if (!uspmv::scs_has_entries(s_dp) || !uspmv::scs_has_entries(s_sp))
-        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_ap: layout-only struct; the plan builder needs the host column indices");
-    if (dp->C != s_dp->C || dp->n_chunks != s_dp->n_chunks || dp->dtype != USPMV_F64 || s_dp->dtype != USPMV_F64 ||
-        sp->C != s_sp->C || sp->n_chunks != s_sp->n_chunks || sp->dtype != USPMV_F32 || s_sp->dtype != USPMV_F32 ||
-        dp->C != sp->C || dp->n_chunks != sp->n_chunks)
-        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_ap: handles / host structs do not form a dp+sp pair");
-    if (int rc = require_device()) return rc;
-    dp->tlc = {};
-    sp->tlc = {};
-    if (max_lines <= 0) max_lines = 512;
-    if (max_lines > 1280) max_lines = 1280;
-    uspmv_tlc_plan p;
-    const int R_meas = measured_tile_rows(dp, sp, max_lines, "uspmv_dmat_optimize_ap");
-    if (int rc = uspmv_build_tlc_plan(s_dp, s_sp, max_lines, R_meas ? R_meas : plan_tile_rows(true), &p)) return rc;
-    if (n_tiles) *n_tiles = p.n_tiles;
-    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
-    dp->sw = {};
-    sp->sw = {};
-    if ((!p.valid || p.n_staged_tiles * 2 < p.n_tiles) && g_tune.sweep) {   // as in uspmv_dmat_optimize
-        int64_t swt = 0, sws = 0;
-        if (int rc = sweep_plan_install(dp, sp, s_dp, s_sp, 0, 0, &swt, &sws, "uspmv_dmat_optimize_ap")) return rc;
-        if (dp->sw.on && sws * 2 >= swt) return USPMV_OK;
-        if (dp->sw.on) { dp->sw = {}; sp->sw = {}; }
-    }
-    if (!p.valid) return USPMV_OK;
-    hipError_t e = dp->tlc.line_ptr.upload(p.tile_line_ptr.data(), p.tile_line_ptr.size() * 4);
-    if (e == hipSuccess) e = dp->tlc.lines.upload(p.tile_lines.data(), p.tile_lines.size() * 4);
-    if (e == hipSuccess) e = dp->tlc.c16_ptrs.upload(p.c16_ptrs.data(), p.c16_ptrs.size() * 4);
-    if (e == hipSuccess) e = dp->tlc.col16.upload(p.col16.data(), p.col16.size() * 2);
-    if (e == hipSuccess) e = sp->tlc.c16_ptrs.upload(p.c16_ptrs_b.data(), p.c16_ptrs_b.size() * 4);
-    if (e == hipSuccess) e = sp->tlc.col16.upload(p.col16_b.data(), p.col16_b.size() * 2);
-    if (e != hipSuccess) {
-        dp->tlc = {}; sp->tlc = {};
-        return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dmat_optimize_ap: device copy failed: %s", hipGetErrorString(e));
-    }
-    static uint64_t next_plan_id = 1;
-    const uint64_t id = next_plan_id++;
-    for (uspmv_dmat_t *A : {dp, sp}) {
-        A->tlc.on = true; A->tlc.tile_rows = p.tile_rows; A->tlc.max_lines = p.max_lines_used; A->tlc.x_len = p.x_len_min;
-        A->tlc.n_tiles = p.n_tiles; A->tlc.staged = p.n_staged_tiles; A->tlc.plan_id = id;
-    }
-    return USPMV_OK;
-}
-
+extern "C++" {
+namespace uspmv_dev {
 
 // builds and uploads a sweep plan for A (and, when B/sB are given, for the dp+sp pair A/B); returns the number of sweep tiles
-static int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, const uspmv_scs_t *sB, int wlog, int tile_rows,
+int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, const uspmv_scs_t *sB, int wlog, int tile_rows,
                               int64_t *n_tiles, int64_t *n_sweep, const char *who) {
     A->sw = {};
     if (B) B->sw = {};
@@ -1464,7 +810,7 @@ static int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_
 // The same plan from the handle's DEVICE arrays (csrc/sweep_plan_kernels.hip): a scan kernel per struct, the tile decisions and the
 // offsets on the host (O(n_tiles); 16 bytes per 64-row group come back), a fill kernel per struct.  Same defaults, same criteria and
 // -- by construction of the fill kernel -- the same arrays as sweep_plan_install builds from a host struct.
-static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who) {
+int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who) {
     A->sw = {};
     if (B) B->sw = {};
     if (n_tiles) *n_tiles = 0;
@@ -1583,6 +929,9 @@ static int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog,
     if (B) { B->sw.on = true; B->sw.plan_id = id; B->sw.n_tiles = nsw; B->sw.all_tiles = nt; }
     return USPMV_OK;
 }
+
+}  // namespace uspmv_dev
+}  // extern "C++"
 
 int uspmv_dmat_optimize_sweep(uspmv_dmat_t *A, const uspmv_scs_t *s, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep) {
     if (!A || !s) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_sweep: NULL argument");

@@ -239,9 +239,13 @@ struct uspmv_dmat {
 
 namespace uspmv_dev {
 
-// "do not MEASURE the rows per tile" (tlc_measure_tile) for the planner calls of the current thread, as a scope
-extern thread_local int tl_measure_off;
-struct MeasureOff { MeasureOff() { ++tl_measure_off; } ~MeasureOff() { --tl_measure_off; } };
+// What the SpMV planner (csrc/tlc_planner.hip) may do beyond the line plan at the default rows per tile.  Each is on when the option
+// AND its tuning key say so: measure -- time 256 / 512 / 1024 rows per tile on large structs ("tlc_measure_tile"); elements -- fall to
+// the plan over single x elements ("tlc_elem"); deal_rows -- ... on rows dealt to the tiles by the matrix graph ("tlc_elem_rows"),
+// after which tile t no longer covers rows [t * tile_rows, (t + 1) * tile_rows) of the caller's order.
+struct TlcPlanOpts { bool measure = true, elements = true, deal_rows = true; };
+// uspmv_dmat_optimize with the options spelled out
+int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged);
 
 // One-launch distributed step (csrc/uspmv_dist_api.hip): the tile list of a step is [early | late | conditional | early].  Early entries
 // (interior + padding tiles) run at once.  A late entry (a tile with real halo references) looks ONCE at the exchange counter: if the
@@ -289,7 +293,7 @@ struct Tuning {
     int tlc_auto_tile = 1;    // with tlc_tile_rows 0 and one struct: 1024- or 512-row tiles when the largest 256-row tile needs > 250 x lines
                               // (<= 16 waves per CU) and the larger tiles still stage >= 99 % of the tiles (profiles/r03/tile_rows_sweep.txt)
     int tlc_measure_tile = 1; // large single structs (>= 2^20 padded rows): build the plan for 256 / 512 / 1024 rows on the device, time the kernel, keep
-                              // a larger tile when it is > 3 % ahead (uspmv_api.hip measured_tile_rows; the 304^3 stencil: 512 rows, 7 % ahead)
+                              // a larger tile when it is > 3 % ahead (tlc_planner.hip measured_tile_rows; the 304^3 stencil: 512 rows, 7 % ahead)
     int tail_batch = 0;     // ragged tail of a chunk as one predicated batch
     int spmmv_unroll = 0;   // 0 = auto (256 bytes of X rows per lane and batch)
     int spmmv_lds_kb = 0;    // block plan: LDS budget per tile in KiB for the NEXT uspmv_dmat_optimize_block (0 = 80)
@@ -339,7 +343,7 @@ struct Tuning {
                             // around the diagonal: 7.9 instead of 11.9 staged X rows per row on config 3; kept only where a sample of tiles
                             // confirms it); 2 = the same with balls over all slots (fewer distinct X rows per tile, but more per phase); 0 = as is.
                             // The device-side builder (handles without a host struct) always does 1.
-    long spmmv_brick_stride = 0;  // spmmv_reorder 3 (measurement aid): rows of a mesh line in ORIGINAL numbering; tiles = flat bricks of spmmv_brick_lines lines
+    int spmmv_brick_stride = 0;   // spmmv_reorder 3 (measurement aid): rows of a mesh line in ORIGINAL numbering; tiles = flat bricks of spmmv_brick_lines lines
     int spmmv_brick_lines = 4;
     int spmmv_phase_dp = 24;  // NEXT optimize_block (host planner): > 0 = phase cuts by dynamic programming (least staged rows + this many rows' worth per
                               // phase), 0 = every phase filled to the brim (what the device-side builder does)
@@ -354,6 +358,15 @@ extern Tuning g_tune;   // uspmv_api.hip
 
 int require_device();                                    // uspmv_api.hip
 int check_dmat(const uspmv_dmat *A, const char *who);    // uspmv_api.hip
+int check_dmat_one_prec(const uspmv_dmat *A, const char *who);   // uspmv_api.hip: ... and not an fp16 handle
+// the parts of an ap split with an fp16 part: hi F64 | F32, mid F32 (hi F64) or NULL, hp F16, one row layout
+int check_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const char *who);   // tlc_planner.hip
+// 16-bit index offsets per chunk from the chunk lengths (O(n_chunks) on the host); false: too large for 32-bit offsets
+bool c16_offsets(const std::vector<int32_t> &cl, int64_t C, std::vector<uint32_t> *c16p, int64_t *tot16);   // tlc_planner.hip
+// the column-window sweep plan from a host struct / from the handle's device arrays (uspmv_api.hip); wlog, tile_rows 0: defaults
+int sweep_plan_install(uspmv_dmat *A, uspmv_dmat *B, const uspmv_scs *s, const uspmv_scs *sB, int wlog, int tile_rows, int64_t *n_tiles,
+                       int64_t *n_sweep, const char *who);
+int sweep_plan_install_device(uspmv_dmat *A, uspmv_dmat *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who);
 inline unsigned grid_for(long work_items, int block) { return (unsigned)((work_items + block - 1) / block); }
 
 constexpr size_t BT_LDS_CAP = 80 * 1024;  // LDS per single-wave SpMMV tile (block plan): two tiles per CU at worst

@@ -896,9 +896,11 @@ int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_s
     int64_t n_tiles = 0, n_staged = 0;
     if (!rc && tlc) {
         // (a rank's block keeps the 256-row tiles unless its lines ask for more: larger tiles measured level on a block of the 304^3 stencil
-        //  -- 0.1785 / 0.1791 / 0.1822 ms -- and a 512-row tile = a whole sigma window always holds a padded chunk, i.e. no interior tile is left)
-        uspmv_dev::MeasureOff no_measure;                     // (this thread's planner calls only: no global tuning state is flipped)
-        rc = uspmv_dmat_optimize(A, scs, 0, &n_tiles, &n_staged);
+        //  -- 0.1785 / 0.1791 / 0.1822 ms -- and a 512-row tile = a whole sigma window always holds a padded chunk, i.e. no interior tile is left.
+        //  Line tiles in the caller's row order: the tile classes below take tile t for rows [t * tile_rows, (t + 1) * tile_rows), and the
+        //  step kernel has no element plan.)
+        const uspmv_dev::TlcPlanOpts as_is{/*measure=*/false, /*elements=*/false, /*deal_rows=*/false};
+        rc = uspmv_dev::dmat_optimize(A, scs, 0, as_is, &n_tiles, &n_staged);
     }
     int tile_rows = 0;
     if (!rc) rc = uspmv_dmat_tile_rows(A, &tile_rows);

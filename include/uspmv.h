@@ -203,8 +203,10 @@ int uspmv_dmat_optimize(uspmv_dmat_t *m, const uspmv_scs_t *s, int max_lines, in
 int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t *s_dp, const uspmv_scs_t *s_sp,
                            int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* Same for the two or three parts of an ap split with an fp16 part (hi: F64 or F32, mid: F32 or NULL, hp: F16; identical row layout):
- * one line list per tile over every part's columns, 16-bit local indices per part.  No column-window sweep: when the line plan stages
- * fewer than half of the tiles the handles stay planless and uspmv_spmv_ap_hp runs its lane-per-row kernel. */
+ * one line list per tile over every part's columns, 16-bit local indices per part.  When the line plan stages fewer than half of the
+ * tiles the column-window sweep shared by the parts is tried (uspmv_dmat_optimize_sweep_ap_hp with its defaults) and kept when it covers
+ * at least half of its tiles; else the handles stay planless and uspmv_spmv_ap_hp runs its lane-per-row kernel.  n_tiles / n_staged
+ * report the line plan's outcome either way; uspmv_dmat_plan_info tells which plan the handles carry. */
 int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
                               const uspmv_scs_t *s_hp, int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* SpMMV counterpart of uspmv_dmat_optimize (no reference counterpart): plan for block vectors of
@@ -225,6 +227,14 @@ int uspmv_dmat_optimize_block(uspmv_dmat_t *m, const uspmv_scs_t *s, int block_v
 int uspmv_dmat_optimize_sweep(uspmv_dmat_t *m, const uspmv_scs_t *s, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep);
 int uspmv_dmat_optimize_sweep_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t *s_dp, const uspmv_scs_t *s_sp, int wlog,
                                  int tile_rows, int64_t *n_tiles, int64_t *n_sweep);
+/* ... for the two or three parts of a split with an fp16 part (hi: F64 or F32, mid: F32 or NULL, hp: F16): one set of tile decisions
+ * over all parts, per part its own padding-free stream -- 10 / 6 / 4 bytes per dp / sp / hp entry plus a count byte per (row, window).
+ * The windows hold x in the type of the hi part (the default window of ap[sp_hp] holds twice the elements).  uspmv_spmv_ap_hp runs the
+ * tiles that do not qualify on its lane-per-row kernel in the same call.  _device: built from the handles' own arrays, equal bit for bit. */
+int uspmv_dmat_optimize_sweep_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
+                                    const uspmv_scs_t *s_hp, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep);
+int uspmv_dmat_optimize_sweep_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, int wlog, int tile_rows, int64_t *n_tiles,
+                                           int64_t *n_sweep);
 /* Which single-vector plan uspmv_spmv / uspmv_spmv_ap will use: kind 0 none (gather kernel), 1 tile-local-column, 2 column-window
  * sweep; tiles of that plan and how many of them it covers (any pointer may be NULL). */
 /* The column-window sweep plan built on the DEVICE from the handle's own arrays (csrc/sweep_plan_kernels.hip): what
@@ -235,6 +245,10 @@ int uspmv_dmat_optimize_sweep_device(uspmv_dmat_t *m, uspmv_dmat_t *sp, int wlog
 /* FNV-1a digests of the sweep plan's device arrays and meta[8] = present, rows per tile, log2 window, sweep tiles, tiles, chunks
  * left to the gather kernel, elements of the dp / sp stream (tests) */
 int uspmv_dmat_sweep_plan_digest(const uspmv_dmat_t *m, uint64_t digest[16], int64_t meta[8]);
+/* ... and of the arrays of ONE part of a shared sweep plan (m: the first part's handle; part 0, 1 or 2 in the order of the split):
+ * digest[5] = wave offsets, counts, values, indices, padding columns; *n_vals = elements of the part's stream (may be NULL).  Zeros
+ * when the handle has no such part (tests) */
+int uspmv_dmat_sweep_plan_digest_part(const uspmv_dmat_t *m, int part, uint64_t digest[5], int64_t *n_vals);
 int uspmv_dmat_plan_info(const uspmv_dmat_t *m, int *kind, int64_t *n_tiles, int64_t *n_planned);
 /* block-vector plans of the handle: meta[10] = one-list-per-tile plan present, phased plan present, line plan present (column-major
  * block vectors staged by 128-byte lines, no re-layout pass), tiles, phases of the phased plan, phases of the line plan, X rows the

@@ -108,6 +108,9 @@ _SIGS = {
     "uspmv_dmat_plan_rows_dealt": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "uspmv_dmat_optimize_sweep_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_dmat_sweep_plan_digest": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(_i64)]),
+    "uspmv_dmat_sweep_plan_digest_part": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(_i64)]),
+    "uspmv_dmat_optimize_sweep_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
+    "uspmv_dmat_optimize_sweep_device_ap_hp": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_spmmv": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
     "uspmv_spmv_ap": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "uspmv_spmv_ap_generic": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -973,6 +976,12 @@ class DeviceMatrix:
         _ck(lib().uspmv_dmat_sweep_plan_digest(self.h, d, m))
         return [int(v) for v in d], [int(v) for v in m]
 
+    def sweep_plan_digest_part(self, part):
+        """(digests of wave offsets, counts, values, indices, padding columns; stream length) of part 0 | 1 | 2 of a shared sweep plan"""
+        d, n = (C.c_uint64 * 5)(), _i64(0)
+        _ck(lib().uspmv_dmat_sweep_plan_digest_part(self.h, int(part), d, C.byref(n)))
+        return [int(v) for v in d], n.value
+
     def block_plan_info(self):
         """dict of the handle's block-vector plans (uspmv_dmat_block_plan_info)"""
         m = (_i64 * 10)()
@@ -1090,7 +1099,8 @@ def optimize_device_ap(A_dp, A_sp, max_lines=0):
 
 def optimize_ap_hp(A_hi, A_mid, A_hp, scs_hi, scs_mid, scs_hp, max_lines=0):
     """Shared tile-local-column plan of the two or three parts of an ap split with an fp16 part (A_mid / scs_mid None for two parts);
-    returns (n_tiles, n_staged_tiles).  Fewer than half of the tiles staged: no plan is installed."""
+    returns (n_tiles, n_staged_tiles) of that plan.  Fewer than half of the tiles staged: the shared column-window sweep is tried instead
+    (plan_info() kind 2 when it took over), else no plan is installed."""
     a, b = _i64(), _i64()
     _ck(lib().uspmv_dmat_optimize_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, scs_hi.h,
                                         scs_mid.h if scs_mid is not None else None, scs_hp.h, max_lines, C.byref(a), C.byref(b)))
@@ -1101,6 +1111,24 @@ def optimize_device_ap_hp(A_hi, A_mid, A_hp, max_lines=0):
     """The plan of optimize_ap_hp built on the device from the handles' own arrays."""
     a, b = _i64(), _i64()
     _ck(lib().uspmv_dmat_optimize_device_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, max_lines, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def optimize_sweep_ap_hp(A_hi, A_mid, A_hp, scs_hi, scs_mid, scs_hp, wlog=0, tile_rows=0):
+    """Shared column-window sweep plan for the parts of an ap split with an fp16 part (A_mid / scs_mid None unless ap[dp_sp_hp]);
+    returns (n_tiles, n_sweep_tiles)."""
+    a, b = _i64(0), _i64(0)
+    _ck(lib().uspmv_dmat_optimize_sweep_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, scs_hi.h,
+                                              scs_mid.h if scs_mid is not None else None, scs_hp.h, int(wlog), int(tile_rows),
+                                              C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def optimize_sweep_device_ap_hp(A_hi, A_mid, A_hp, wlog=0, tile_rows=0):
+    """The plan of optimize_sweep_ap_hp built on the device from the handles' own arrays."""
+    a, b = _i64(0), _i64(0)
+    _ck(lib().uspmv_dmat_optimize_sweep_device_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, int(wlog), int(tile_rows),
+                                                     C.byref(a), C.byref(b)))
     return a.value, b.value
 
 

@@ -207,14 +207,8 @@ __global__ void scs_spmv_ap_rows(const long n_chunks, const int C_rt, const int 
 // Adaptive precision with an fp16 part: ap[dp_hp] (HT double, no mid), ap[dp_sp_hp] (HT double, mid float), ap[sp_hp] (HT float, x and
 // y float).  One chain per part, each in slot order; with a double x every product is an FMA in double on the exactly widened value
 // (scs_ap_impl_cpu's convention, hp in the place of sp), with a float x the product is rounded to float and then added to the part's
-// double accumulator (the sp part of spmv_omp_scs_ap).  y = hi + hp, (hi + mid) + hp, or (float)(sp + hp).  hp values arrive as the
-// binary16 bits; v_cvt_f32_f16 widens them exactly.
-__device__ __forceinline__ float hp_val(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ double ap_step(double v, double x, double acc) { return __builtin_fma(v, x, acc); }
-__device__ __forceinline__ double ap_step(float v, double x, double acc) { return __builtin_fma((double)v, x, acc); }
-__device__ __forceinline__ double ap_step(unsigned short v, double x, double acc) { return __builtin_fma((double)hp_val(v), x, acc); }
-__device__ __forceinline__ double ap_step(float v, float x, double acc) { return acc + (double)__fmul_rn(v, x); }
-__device__ __forceinline__ double ap_step(unsigned short v, float x, double acc) { return acc + (double)__fmul_rn(hp_val(v), x); }
+// double accumulator (the sp part of spmv_omp_scs_ap).  y = hi + hp, (hi + mid) + hp, or (float)(sp + hp).  The steps (ap_step,
+// ap_hp_y) are shared with the column-window sweep form (sweep_ap_hp_kernels.hip) and live in uspmv_device.hpp.
 
 // one part's chain over the staged x lines: values one per lane per slot, the 16-bit local indices four slots per 8-byte load
 template <bool NT, typename VT, typename XT>
@@ -264,13 +258,6 @@ __device__ __forceinline__ double gather_chain(const VT *__restrict__ vp, const 
     }
     for (; j < L; ++j) acc = ap_step(ld_stream<NT>(vp + (long)j * C), x[ld_stream<NT>(cp + (long)j * C)], acc);
     return acc;
-}
-
-template <typename HT, bool MID>
-__device__ __forceinline__ HT ap_hp_y(double h, double m, double q) {
-    if constexpr (sizeof(HT) == 4) return (float)(h + q);
-    else if constexpr (MID) return (h + m) + q;
-    else return h + q;
 }
 
 // the parts' arrays (mid: nullptr unless ap[dp_sp_hp]); c16p / c16: the shared plan's per-part local indices
@@ -331,16 +318,19 @@ __global__ void __launch_bounds__(1024) scs_spmv_ap_hp_tlc(const long n_chunks, 
     if (valid) st_y<NT>(y + row, ap_hp_y<HT, MID>(acc[0], acc[1], acc[2]));
 }
 
-// Lane per row, any C and handles without a plan: the parts' chains one after the other with global gathers
-template <int U, bool NT, int CT, typename HT, bool MID>
+// Lane per row, any C and handles without a plan: the parts' chains one after the other with global gathers.  IDS: virtual chunk vc ->
+// chunk_ids[vc] (the chunks a sweep plan leaves over)
+template <int U, bool NT, int CT, typename HT, bool MID, bool IDS = false>
 __global__ void scs_spmv_ap_hp_rows(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ x, HT *__restrict__ y,
-                                    const int xcd_remap) {
+                                    const int xcd_remap, const int *__restrict__ chunk_ids = nullptr) {
     const int C = CT > 0 ? CT : C_rt;
     const unsigned lb = remap_block(blockIdx.x, gridDim.x, xcd_remap);
-    const long row = (long)lb * blockDim.x + threadIdx.x;
-    const long c = row / C;
-    const int i = (int)(row - c * C);
-    if (c >= n_chunks) return;
+    const long vrow = (long)lb * blockDim.x + threadIdx.x;
+    const long vc = vrow / C;
+    const int i = (int)(vrow - vc * C);
+    if (vc >= n_chunks) return;
+    const long c = IDS ? (long)chunk_ids[vc] : vc;
+    const long row = c * C + i;
     double acc[3] = {0.0, 0.0, 0.0};
     long cs = P.cp[0][c];
     acc[0] = gather_chain<NT, U>((const HT *)P.va[0] + cs + i, P.ci[0] + cs + i, P.cl[0][c], C, x, 0.0);
@@ -353,8 +343,7 @@ __global__ void scs_spmv_ap_hp_rows(const long n_chunks, const int C_rt, const A
     st_y<NT>(y + row, ap_hp_y<HT, MID>(acc[0], acc[1], acc[2]));
 }
 
-template <typename HT, bool MID>
-int launch_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const HT *d_x, HT *d_y, hipStream_t stream) {
+ApHpParts ap_hp_parts(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp) {
     ApHpParts P{};
     const uspmv_dmat *ms[3] = {hi, mid, hp};
     for (int k = 0; k < 3; ++k) {
@@ -362,6 +351,36 @@ int launch_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *
         P.cp[k] = ms[k]->chunk_ptrs; P.cl[k] = ms[k]->chunk_lengths; P.ci[k] = ms[k]->col_idxs; P.va[k] = ms[k]->values;
         P.c16p[k] = ms[k]->tlc.c16_ptrs; P.c16[k] = ms[k]->tlc.col16;
     }
+    return P;
+}
+
+// the chunks in chunk_ids through the lane-per-row kernel
+template <typename HT, bool MID>
+int launch_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids, const HT *d_x,
+                        HT *d_y, hipStream_t stream) {
+    const ApHpParts P = ap_hp_parts(hi, mid, hp);
+    const unsigned grid = grid_for(n_ids * hi->C, 256);
+    if (g_tune.nontemporal)
+        hipLaunchKernelGGL((scs_spmv_ap_hp_rows<4, true, 0, HT, MID, true>), dim3(grid), dim3(256), 0, stream, n_ids, (int)hi->C, P, d_x, d_y,
+                           g_tune.xcd_remap, chunk_ids);
+    else
+        hipLaunchKernelGGL((scs_spmv_ap_hp_rows<4, false, 0, HT, MID, true>), dim3(grid), dim3(256), 0, stream, n_ids, (int)hi->C, P, d_x, d_y,
+                           g_tune.xcd_remap, chunk_ids);
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
+template <typename HT, bool MID>
+int launch_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const HT *d_x, HT *d_y, hipStream_t stream) {
+    // a column-window sweep plan shared by all parts first (its arrays live on hi), then the shared line plan, then lane per row
+    const uint64_t sid = hi->sw.plan_id;
+    if (hi->sw.on && hi->sw.tile_ids && hi->sw.n_parts == (MID ? 3 : 2) && hp->sw.on && hp->sw.plan_id == sid &&
+        (!mid || (mid->sw.on && mid->sw.plan_id == sid)) && g_tune.sweep && (uintptr_t)d_x % 16 == 0) {
+        if (int rc = launch_spmv_sweep_ap_hp(hi, MID, d_x, d_y, stream)) return rc;
+        if (hi->sw.n_rest == 0) return USPMV_OK;
+        return launch_ap_hp_chunks<HT, MID>(hi, mid, hp, hi->sw.rest, (long)hi->sw.n_rest, d_x, d_y, stream);
+    }
+    const ApHpParts P = ap_hp_parts(hi, mid, hp);
     const uint64_t id = hi->tlc.plan_id;
     const bool planned = hi->tlc.on && id != 0 && hp->tlc.on && hp->tlc.plan_id == id && (!mid || (mid->tlc.on && mid->tlc.plan_id == id));
     const bool nt = g_tune.nontemporal != 0;
@@ -399,6 +418,14 @@ int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_d
     if (hi->dtype == USPMV_F32) return launch_ap_hp<float, false>(hi, nullptr, hp, (const float *)d_x, (float *)d_y, stream);
     if (mid) return launch_ap_hp<double, true>(hi, mid, hp, (const double *)d_x, (double *)d_y, stream);
     return launch_ap_hp<double, false>(hi, nullptr, hp, (const double *)d_x, (double *)d_y, stream);
+}
+
+int launch_spmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
+                             const void *d_x, void *d_y, hipStream_t stream) {
+    if (n_ids == 0) return USPMV_OK;
+    if (hi->dtype == USPMV_F32) return launch_ap_hp_chunks<float, false>(hi, nullptr, hp, chunk_ids, n_ids, (const float *)d_x, (float *)d_y, stream);
+    if (mid) return launch_ap_hp_chunks<double, true>(hi, mid, hp, chunk_ids, n_ids, (const double *)d_x, (double *)d_y, stream);
+    return launch_ap_hp_chunks<double, false>(hi, nullptr, hp, chunk_ids, n_ids, (const double *)d_x, (double *)d_y, stream);
 }
 
 int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *d_x,

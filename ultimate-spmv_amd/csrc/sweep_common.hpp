@@ -1,0 +1,113 @@
+// What the column-window sweep kernels share (sweep_kernels.hip: one struct and the ap[dp_sp] pair; sweep_ap_hp_kernels.hip: the
+// splits with an fp16 part): the address-space types of the LDS-DMA, the lane's place in a ballot, and the batches of accumulator
+// updates under the rounds' lane masks.
+#pragma once
+#include "uspmv_device.hpp"
+
+namespace {
+
+typedef __attribute__((address_space(3))) void lds_void_t;
+typedef __attribute__((address_space(1))) const void glb_cvoid_t;
+
+// active lanes strictly below this one
+__device__ __forceinline__ unsigned lanes_below(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// A batch of U fused multiply-adds, each under ITS round's lane mask: EXEC is set to the round's ballot, so that a lane that sits the
+// round out keeps its accumulator -- not even a signed zero is added -- without the copy + two selects per round that the
+// select form costs (v_mov_b64, v_fmac_f64, 2 x v_cndmask_b32: the rounds are issue-bound, profiles/r03/config4b.txt).  All lanes
+// of the wave are active around the call (the kernel's control flow is wave-uniform); EXEC is saved and restored regardless.
+template <int U>
+__device__ __forceinline__ void masked_fma_batch(double &acc, const double (&v)[U], const double (&x)[U], const unsigned long long (&m)[U]) {
+    static_assert(U == 4 || U == 8, "batch of 4 or 8 rounds");
+    unsigned long long save;
+    if constexpr (U == 8)
+        asm volatile("s_mov_b64 %[sv], exec\n\t"
+                     "s_mov_b64 exec, %[m0]\n\tv_fmac_f64 %[a], %[v0], %[x0]\n\t"
+                     "s_mov_b64 exec, %[m1]\n\tv_fmac_f64 %[a], %[v1], %[x1]\n\t"
+                     "s_mov_b64 exec, %[m2]\n\tv_fmac_f64 %[a], %[v2], %[x2]\n\t"
+                     "s_mov_b64 exec, %[m3]\n\tv_fmac_f64 %[a], %[v3], %[x3]\n\t"
+                     "s_mov_b64 exec, %[m4]\n\tv_fmac_f64 %[a], %[v4], %[x4]\n\t"
+                     "s_mov_b64 exec, %[m5]\n\tv_fmac_f64 %[a], %[v5], %[x5]\n\t"
+                     "s_mov_b64 exec, %[m6]\n\tv_fmac_f64 %[a], %[v6], %[x6]\n\t"
+                     "s_mov_b64 exec, %[m7]\n\tv_fmac_f64 %[a], %[v7], %[x7]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a] "+v"(acc), [sv] "=&s"(save)
+                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]), [m4] "s"(m[4]), [m5] "s"(m[5]), [m6] "s"(m[6]), [m7] "s"(m[7]),
+                       [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [v4] "v"(v[4]), [v5] "v"(v[5]), [v6] "v"(v[6]), [v7] "v"(v[7]),
+                       [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]), [x5] "v"(x[5]), [x6] "v"(x[6]), [x7] "v"(x[7]));
+    else
+        asm volatile("s_mov_b64 %[sv], exec\n\t"
+                     "s_mov_b64 exec, %[m0]\n\tv_fmac_f64 %[a], %[v0], %[x0]\n\t"
+                     "s_mov_b64 exec, %[m1]\n\tv_fmac_f64 %[a], %[v1], %[x1]\n\t"
+                     "s_mov_b64 exec, %[m2]\n\tv_fmac_f64 %[a], %[v2], %[x2]\n\t"
+                     "s_mov_b64 exec, %[m3]\n\tv_fmac_f64 %[a], %[v3], %[x3]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a] "+v"(acc), [sv] "=&s"(save)
+                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]),
+                       [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]));
+}
+template <int U>
+__device__ __forceinline__ void masked_fma_batch(float &acc, const float (&v)[U], const float (&x)[U], const unsigned long long (&m)[U]) {
+    static_assert(U == 4 || U == 8, "batch of 4 or 8 rounds");
+    unsigned long long save;
+    if constexpr (U == 8)
+        asm volatile("s_mov_b64 %[sv], exec\n\t"
+                     "s_mov_b64 exec, %[m0]\n\tv_fmac_f32 %[a], %[v0], %[x0]\n\t"
+                     "s_mov_b64 exec, %[m1]\n\tv_fmac_f32 %[a], %[v1], %[x1]\n\t"
+                     "s_mov_b64 exec, %[m2]\n\tv_fmac_f32 %[a], %[v2], %[x2]\n\t"
+                     "s_mov_b64 exec, %[m3]\n\tv_fmac_f32 %[a], %[v3], %[x3]\n\t"
+                     "s_mov_b64 exec, %[m4]\n\tv_fmac_f32 %[a], %[v4], %[x4]\n\t"
+                     "s_mov_b64 exec, %[m5]\n\tv_fmac_f32 %[a], %[v5], %[x5]\n\t"
+                     "s_mov_b64 exec, %[m6]\n\tv_fmac_f32 %[a], %[v6], %[x6]\n\t"
+                     "s_mov_b64 exec, %[m7]\n\tv_fmac_f32 %[a], %[v7], %[x7]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a] "+v"(acc), [sv] "=&s"(save)
+                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]), [m4] "s"(m[4]), [m5] "s"(m[5]), [m6] "s"(m[6]), [m7] "s"(m[7]),
+                       [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [v4] "v"(v[4]), [v5] "v"(v[5]), [v6] "v"(v[6]), [v7] "v"(v[7]),
+                       [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]), [x5] "v"(x[5]), [x6] "v"(x[6]), [x7] "v"(x[7]));
+    else
+        asm volatile("s_mov_b64 %[sv], exec\n\t"
+                     "s_mov_b64 exec, %[m0]\n\tv_fmac_f32 %[a], %[v0], %[x0]\n\t"
+                     "s_mov_b64 exec, %[m1]\n\tv_fmac_f32 %[a], %[v1], %[x1]\n\t"
+                     "s_mov_b64 exec, %[m2]\n\tv_fmac_f32 %[a], %[v2], %[x2]\n\t"
+                     "s_mov_b64 exec, %[m3]\n\tv_fmac_f32 %[a], %[v3], %[x3]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a] "+v"(acc), [sv] "=&s"(save)
+                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]),
+                       [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]));
+}
+
+// The same for the chains whose step is not an FMA (ap[sp_hp]: the product is rounded to float first): a batch of U additions of the
+// finished terms t[u], each under its round's lane mask.
+template <int U>
+__device__ __forceinline__ void masked_add_batch(double &acc, const double (&t)[U], const unsigned long long (&m)[U]) {
+    static_assert(U == 4 || U == 8, "batch of 4 or 8 rounds");
+    unsigned long long save;
+    if constexpr (U == 8)
+        asm volatile("s_mov_b64 %[sv], exec\n\t"
+                     "s_mov_b64 exec, %[m0]\n\tv_add_f64 %[a], %[a], %[t0]\n\t"
+                     "s_mov_b64 exec, %[m1]\n\tv_add_f64 %[a], %[a], %[t1]\n\t"
+                     "s_mov_b64 exec, %[m2]\n\tv_add_f64 %[a], %[a], %[t2]\n\t"
+                     "s_mov_b64 exec, %[m3]\n\tv_add_f64 %[a], %[a], %[t3]\n\t"
+                     "s_mov_b64 exec, %[m4]\n\tv_add_f64 %[a], %[a], %[t4]\n\t"
+                     "s_mov_b64 exec, %[m5]\n\tv_add_f64 %[a], %[a], %[t5]\n\t"
+                     "s_mov_b64 exec, %[m6]\n\tv_add_f64 %[a], %[a], %[t6]\n\t"
+                     "s_mov_b64 exec, %[m7]\n\tv_add_f64 %[a], %[a], %[t7]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a] "+v"(acc), [sv] "=&s"(save)
+                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]), [m4] "s"(m[4]), [m5] "s"(m[5]), [m6] "s"(m[6]), [m7] "s"(m[7]),
+                       [t0] "v"(t[0]), [t1] "v"(t[1]), [t2] "v"(t[2]), [t3] "v"(t[3]), [t4] "v"(t[4]), [t5] "v"(t[5]), [t6] "v"(t[6]), [t7] "v"(t[7]));
+    else
+        asm volatile("s_mov_b64 %[sv], exec\n\t"
+                     "s_mov_b64 exec, %[m0]\n\tv_add_f64 %[a], %[a], %[t0]\n\t"
+                     "s_mov_b64 exec, %[m1]\n\tv_add_f64 %[a], %[a], %[t1]\n\t"
+                     "s_mov_b64 exec, %[m2]\n\tv_add_f64 %[a], %[a], %[t2]\n\t"
+                     "s_mov_b64 exec, %[m3]\n\tv_add_f64 %[a], %[a], %[t3]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a] "+v"(acc), [sv] "=&s"(save)
+                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]), [t0] "v"(t[0]), [t1] "v"(t[1]), [t2] "v"(t[2]), [t3] "v"(t[3]));
+}
+
+}  // namespace

@@ -12,18 +12,11 @@
 // s_bcnt1, one v_mbcnt pair).  The stream is therefore contiguous per wave and free of padding: sizeof(VT) + 2
 // bytes per non-zero, read once, non-temporally; the x operand is a ds_read from the staged window.
 #include "uspmv_device.hpp"
+#include "sweep_common.hpp"
 
 using namespace uspmv_dev;
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_cvoid_t;
-
-// active lanes strictly below this one
-__device__ __forceinline__ unsigned lanes_below(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 
 // One window of one wave: batches of U rounds.  AT = type of the stored values (float for the sp part of ap[dp_sp]), XT = type
 // of x and of the accumulator.  vp / ip point at the wave's next element of the compacted stream and stay WAVE-UNIFORM (scalar
@@ -69,71 +62,6 @@ __device__ __forceinline__ void sweep_window(const XT *__restrict__ xs, const in
         vp += first[U];
         ip += first[U];
     }
-}
-
-// A batch of U fused multiply-adds, each under ITS round's lane mask: EXEC is set to the round's ballot, so that a lane that sits the
-// round out keeps its accumulator -- not even a signed zero is added -- without the copy + two selects per round that the
-// select form costs (v_mov_b64, v_fmac_f64, 2 x v_cndmask_b32: the rounds are issue-bound, profiles/r03/config4b.txt).  All lanes
-// of the wave are active around the call (the kernel's control flow is wave-uniform); EXEC is saved and restored regardless.
-template <int U>
-__device__ __forceinline__ void masked_fma_batch(double &acc, const double (&v)[U], const double (&x)[U], const unsigned long long (&m)[U]) {
-    static_assert(U == 4 || U == 8, "batch of 4 or 8 rounds");
-    unsigned long long save;
-    if constexpr (U == 8)
-        asm volatile("s_mov_b64 %[sv], exec\n\t"
-                     "s_mov_b64 exec, %[m0]\n\tv_fmac_f64 %[a], %[v0], %[x0]\n\t"
-                     "s_mov_b64 exec, %[m1]\n\tv_fmac_f64 %[a], %[v1], %[x1]\n\t"
-                     "s_mov_b64 exec, %[m2]\n\tv_fmac_f64 %[a], %[v2], %[x2]\n\t"
-                     "s_mov_b64 exec, %[m3]\n\tv_fmac_f64 %[a], %[v3], %[x3]\n\t"
-                     "s_mov_b64 exec, %[m4]\n\tv_fmac_f64 %[a], %[v4], %[x4]\n\t"
-                     "s_mov_b64 exec, %[m5]\n\tv_fmac_f64 %[a], %[v5], %[x5]\n\t"
-                     "s_mov_b64 exec, %[m6]\n\tv_fmac_f64 %[a], %[v6], %[x6]\n\t"
-                     "s_mov_b64 exec, %[m7]\n\tv_fmac_f64 %[a], %[v7], %[x7]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a] "+v"(acc), [sv] "=&s"(save)
-                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]), [m4] "s"(m[4]), [m5] "s"(m[5]), [m6] "s"(m[6]), [m7] "s"(m[7]),
-                       [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [v4] "v"(v[4]), [v5] "v"(v[5]), [v6] "v"(v[6]), [v7] "v"(v[7]),
-                       [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]), [x5] "v"(x[5]), [x6] "v"(x[6]), [x7] "v"(x[7]));
-    else
-        asm volatile("s_mov_b64 %[sv], exec\n\t"
-                     "s_mov_b64 exec, %[m0]\n\tv_fmac_f64 %[a], %[v0], %[x0]\n\t"
-                     "s_mov_b64 exec, %[m1]\n\tv_fmac_f64 %[a], %[v1], %[x1]\n\t"
-                     "s_mov_b64 exec, %[m2]\n\tv_fmac_f64 %[a], %[v2], %[x2]\n\t"
-                     "s_mov_b64 exec, %[m3]\n\tv_fmac_f64 %[a], %[v3], %[x3]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a] "+v"(acc), [sv] "=&s"(save)
-                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]),
-                       [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]));
-}
-template <int U>
-__device__ __forceinline__ void masked_fma_batch(float &acc, const float (&v)[U], const float (&x)[U], const unsigned long long (&m)[U]) {
-    static_assert(U == 4 || U == 8, "batch of 4 or 8 rounds");
-    unsigned long long save;
-    if constexpr (U == 8)
-        asm volatile("s_mov_b64 %[sv], exec\n\t"
-                     "s_mov_b64 exec, %[m0]\n\tv_fmac_f32 %[a], %[v0], %[x0]\n\t"
-                     "s_mov_b64 exec, %[m1]\n\tv_fmac_f32 %[a], %[v1], %[x1]\n\t"
-                     "s_mov_b64 exec, %[m2]\n\tv_fmac_f32 %[a], %[v2], %[x2]\n\t"
-                     "s_mov_b64 exec, %[m3]\n\tv_fmac_f32 %[a], %[v3], %[x3]\n\t"
-                     "s_mov_b64 exec, %[m4]\n\tv_fmac_f32 %[a], %[v4], %[x4]\n\t"
-                     "s_mov_b64 exec, %[m5]\n\tv_fmac_f32 %[a], %[v5], %[x5]\n\t"
-                     "s_mov_b64 exec, %[m6]\n\tv_fmac_f32 %[a], %[v6], %[x6]\n\t"
-                     "s_mov_b64 exec, %[m7]\n\tv_fmac_f32 %[a], %[v7], %[x7]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a] "+v"(acc), [sv] "=&s"(save)
-                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]), [m4] "s"(m[4]), [m5] "s"(m[5]), [m6] "s"(m[6]), [m7] "s"(m[7]),
-                       [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [v4] "v"(v[4]), [v5] "v"(v[5]), [v6] "v"(v[6]), [v7] "v"(v[7]),
-                       [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]), [x5] "v"(x[5]), [x6] "v"(x[6]), [x7] "v"(x[7]));
-    else
-        asm volatile("s_mov_b64 %[sv], exec\n\t"
-                     "s_mov_b64 exec, %[m0]\n\tv_fmac_f32 %[a], %[v0], %[x0]\n\t"
-                     "s_mov_b64 exec, %[m1]\n\tv_fmac_f32 %[a], %[v1], %[x1]\n\t"
-                     "s_mov_b64 exec, %[m2]\n\tv_fmac_f32 %[a], %[v2], %[x2]\n\t"
-                     "s_mov_b64 exec, %[m3]\n\tv_fmac_f32 %[a], %[v3], %[x3]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a] "+v"(acc), [sv] "=&s"(save)
-                     : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]),
-                       [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]));
 }
 
 // TWO independent chains of one lane through the same window in one loop -- two of the lane's rows (dp / sp kernels with several rows
@@ -350,7 +278,7 @@ int launch_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st) {
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(kfn, dim3((unsigned)A->sw.n_tiles), dim3(threads), lds, st, A->sw.wlog, A->sw.tile_ids,           \
                            A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off, A->sw.cnt,        \
-                           (const VT *)A->sw.vals, A->sw.idx, A->sw.pad, A->sw.wave_off_b, A->sw.cnt_b, A->sw.vals_b,        \
+                           (const VT *)A->sw.vals, A->sw.idx, A->sw.pad, A->sw.wave_off_b, A->sw.cnt_b, (const float *)A->sw.vals_b,        \
                            A->sw.idx_b, A->sw.pad_b, x, y, (long)A->sw.x_len, (long)A->n_store, remap);                      \
     } while (0)
 #define SW_LAUNCH_R(NTV, NB, UU) do { if (rpl == 4) SW_LAUNCH(NTV, NB, UU, 4); else if (rpl == 2) SW_LAUNCH(NTV, NB, UU, 2); else SW_LAUNCH(NTV, NB, UU, 1); } while (0)

@@ -8,7 +8,9 @@
 //   sweep_fill : one wave per 64-row group of a sweep tile.  Count bytes per (window, row), then the compacted entry stream by the
 //                very traversal the compute kernel performs (csrc/sweep_kernels.hip: windows ascending, rounds, one ballot per round,
 //                a lane's element at base + active lanes below it) -- writing where that one reads, so the layout agrees by construction.
-// The arrays are bit-identical to the host planner's (tests/test_gpu_sweep.py compares them).
+// The arrays are bit-identical to the host planner's (tests/test_gpu_sweep.py compares them).  Both kernels run once per struct of a
+// shared plan -- the pair of ap[dp_sp], the two or three parts of a split with an fp16 part (values: the binary16 bits, compared and
+// copied as such) --; the tile decisions in between are taken over all of them.
 #include "uspmv_device.hpp"
 
 using namespace uspmv_dev;
@@ -17,6 +19,7 @@ namespace {
 
 __device__ __forceinline__ bool is_pos_zero(double v) { return __double_as_longlong(v) == 0ll; }
 __device__ __forceinline__ bool is_pos_zero(float v) { return __float_as_int(v) == 0; }
+__device__ __forceinline__ bool is_pos_zero(unsigned short v) { return v == 0; }
 
 __device__ __forceinline__ unsigned lanes_below_m(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
@@ -131,9 +134,12 @@ int launch_sweep_scan(const uspmv_dmat *A, int wlog, int *d_row_le, int *d_row_p
     if (A->dtype == USPMV_F64)
         hipLaunchKernelGGL(sweep_scan<double>, grid, block, 0, st, (long)A->n_chunks, (int)A->C, wlog, A->chunk_ptrs, A->chunk_lengths, A->col_idxs,
                            (const double *)A->values, d_row_le, d_row_pad, d_grp, d_max_col);
-    else
+    else if (A->dtype == USPMV_F32)
         hipLaunchKernelGGL(sweep_scan<float>, grid, block, 0, st, (long)A->n_chunks, (int)A->C, wlog, A->chunk_ptrs, A->chunk_lengths, A->col_idxs,
                            (const float *)A->values, d_row_le, d_row_pad, d_grp, d_max_col);
+    else
+        hipLaunchKernelGGL(sweep_scan<unsigned short>, grid, block, 0, st, (long)A->n_chunks, (int)A->C, wlog, A->chunk_ptrs, A->chunk_lengths,
+                           A->col_idxs, (const unsigned short *)A->values, d_row_le, d_row_pad, d_grp, d_max_col);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }
@@ -147,9 +153,13 @@ int launch_sweep_fill(const uspmv_dmat *A, int wlog, int R, long n_sweep_tiles, 
     if (A->dtype == USPMV_F64)
         hipLaunchKernelGGL(sweep_fill<double>, grid, block, 0, st, (long)A->n_chunks, (int)A->C, wlog, R, n_groups, A->chunk_ptrs, A->col_idxs,
                            (const double *)A->values, d_tile_ids, d_smin, d_S, d_cnt_off, d_wave_off, d_row_le, d_row_pad, d_cnt, (double *)d_vals, d_idx, d_pad_col);
-    else
+    else if (A->dtype == USPMV_F32)
         hipLaunchKernelGGL(sweep_fill<float>, grid, block, 0, st, (long)A->n_chunks, (int)A->C, wlog, R, n_groups, A->chunk_ptrs, A->col_idxs,
                            (const float *)A->values, d_tile_ids, d_smin, d_S, d_cnt_off, d_wave_off, d_row_le, d_row_pad, d_cnt, (float *)d_vals, d_idx, d_pad_col);
+    else
+        hipLaunchKernelGGL(sweep_fill<unsigned short>, grid, block, 0, st, (long)A->n_chunks, (int)A->C, wlog, R, n_groups, A->chunk_ptrs, A->col_idxs,
+                           (const unsigned short *)A->values, d_tile_ids, d_smin, d_S, d_cnt_off, d_wave_off, d_row_le, d_row_pad, d_cnt,
+                           (unsigned short *)d_vals, d_idx, d_pad_col);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }

@@ -38,12 +38,11 @@ bool tile_rows_accept(int64_t n_tiles, int64_t n_staged) { return n_staged * 100
 
 // How much of a plan stages, by the thresholds the decisions below use: a line plan under nine tenths leaves "a tenth of the tiles or more
 // to the gather path" (the element plans are tried); 19 of 20 is enough for the plan on dealt rows (what would run instead is 2 x
-// slower); under half, the column-window sweep is tried, and a shared plan with an fp16 part is not worth keeping.
+// slower); under half, the column-window sweep is tried (sweep_takes_over), and a shared plan with an fp16 part is not worth keeping.
 bool stages_nine_tenths(int64_t n_tiles, int64_t n_staged) { return n_staged * 10 >= n_tiles * 9; }
 bool stages_19_of_20(int64_t n_tiles, int64_t n_staged) { return n_staged * 20 >= n_tiles * 19; }
 bool stages_half(int64_t n_tiles, int64_t n_staged) { return n_staged * 2 >= n_tiles; }
-// shared plans of the two or three parts of a split with an fp16 part: the line plan where it stages at least half of the tiles, otherwise
-// none (no sweep for hp parts)
+// shared line plan of the two or three parts of a split with an fp16 part: kept where it stages at least half of the tiles
 bool ap_hp_plan_worth(int64_t n_tiles, int64_t n_staged) { return n_staged > 0 && stages_half(n_tiles, n_staged); }
 
 // the internal C = 32 re-chunking of a narrow struct is taken when its padding stays within a quarter (+ 4096) of the entries
@@ -109,16 +108,17 @@ int install_host_plan(uspmv_dmat *const parts[3], const uspmv_tlc_plan &p, bool 
 
 // Wide, irregular rows: most tiles touch too many x lines to stage them.  When the plan stages fewer than half of its tiles, try the
 // column-window sweep (from the host structs, or -- s == nullptr -- built on the device as well); *took: it covers at least half of its
-// tiles and stays on the handles.
-int sweep_takes_over(uspmv_dmat *A, uspmv_dmat *B, const uspmv_scs *s, const uspmv_scs *sB, const PlanStats &st, const char *who, bool *took) {
+// tiles and stays on the handles.  One struct, the ap[dp_sp] pair (B) and the splits with an fp16 part (B, B3) alike.
+int sweep_takes_over(uspmv_dmat *A, uspmv_dmat *B, const uspmv_scs *s, const uspmv_scs *sB, const PlanStats &st, const char *who, bool *took,
+                     uspmv_dmat *B3 = nullptr, const uspmv_scs *sB3 = nullptr) {
     *took = false;
-    A->sw = {};
-    if (B) B->sw = {};
+    uspmv_dmat *const ms[3] = {A, B, B3};
+    for (uspmv_dmat *M : ms) if (M) M->sw = {};
     if (!g_tune.sweep || (st.valid && stages_half(st.n_tiles, st.n_staged))) return USPMV_OK;
     int64_t swt = 0, sws = 0;
-    if (int rc = s ? sweep_plan_install(A, B, s, sB, 0, 0, &swt, &sws, who) : sweep_plan_install_device(A, B, 0, 0, &swt, &sws, who)) return rc;
+    if (int rc = s ? sweep_plan_install(A, B, s, sB, 0, 0, &swt, &sws, who, B3, sB3) : sweep_plan_install_device(A, B, 0, 0, &swt, &sws, who, B3)) return rc;
     *took = A->sw.on && stages_half(swt, sws);
-    if (!*took) { A->sw = {}; if (B) B->sw = {}; }
+    if (!*took) for (uspmv_dmat *M : ms) if (M) M->sw = {};
     return USPMV_OK;
 }
 
@@ -606,9 +606,11 @@ int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t 
     if (n_staged) *n_staged = 0;
     uspmv_tlc_plan p;
     if (int rc = uspmv_build_tlc_plan(ss[0], ss[1], line_budget(max_lines, hi->dtype, true), plan_tile_rows(true), &p, 4, ss[2])) return rc;
-    if (n_tiles) *n_tiles = p.n_tiles;
+    if (n_tiles) *n_tiles = p.n_tiles;              // (the line plan's outcome also when the sweep takes over, as in uspmv_dmat_optimize_ap)
     if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
-    if (!p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
+    bool swept = false;
+    if (int rc = sweep_takes_over(ms[0], ms[1], ss[0], ss[1], stats_of(p), who, &swept, ms[2], ss[2])) return rc;
+    if (swept || !p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
     return install_host_plan(ms, p, /*elem=*/false, who);
 }
 
@@ -622,7 +624,9 @@ int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_
     if (int rc = device_plan_install_rows(ms, max_lines, plan_tile_rows(true), &st, who)) return rc;
     if (n_tiles) *n_tiles = st.n_tiles;
     if (n_staged) *n_staged = st.n_staged;
-    if (!ap_hp_plan_worth(st.n_tiles, st.n_staged))
+    bool swept = false;
+    if (int rc = sweep_takes_over(ms[0], ms[1], nullptr, nullptr, st, who, &swept, ms[2])) return rc;
+    if (swept || !ap_hp_plan_worth(st.n_tiles, st.n_staged))
         for (uspmv_dmat_t *M : ms) if (M) M->tlc = {};
     return USPMV_OK;
 }

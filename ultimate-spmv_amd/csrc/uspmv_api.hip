@@ -744,11 +744,13 @@ int uspmv_dmat_optimize_block_device(uspmv_dmat_t *A, int block_vec_size, int64_
 extern "C++" {
 namespace uspmv_dev {
 
-// builds and uploads a sweep plan for A (and, when B/sB are given, for the dp+sp pair A/B); returns the number of sweep tiles
+// builds and uploads a sweep plan for A (and, when B/sB [and B3/sB3] are given, for the parts A/B[/B3] of an ap split); returns the
+// number of sweep tiles.  A plan on the handles is replaced.
 int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, const uspmv_scs_t *sB, int wlog, int tile_rows,
-                              int64_t *n_tiles, int64_t *n_sweep, const char *who) {
+                              int64_t *n_tiles, int64_t *n_sweep, const char *who, uspmv_dmat_t *B3, const uspmv_scs_t *sB3) {
     A->sw = {};
     if (B) B->sw = {};
+    if (B3) B3->sw = {};
     if (n_tiles) *n_tiles = 0;
     if (n_sweep) *n_sweep = 0;
     const size_t vsz = s->dtype == USPMV_F64 ? 8 : 4;
@@ -770,7 +772,7 @@ int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, c
     }
     uspmv_sweep_plan p;
     const double max_stage = g_tune.sweep_max_stage > 0 ? (double)g_tune.sweep_max_stage : 24.0;
-    if (int rc = uspmv_build_sweep_plan(s, sB, wlog, tile_rows, max_stage, &p)) return rc;
+    if (int rc = uspmv_build_sweep_plan(s, sB, wlog, tile_rows, max_stage, &p, sB3)) return rc;
     if (n_tiles) *n_tiles = p.n_tiles;
     if (n_sweep) *n_sweep = p.valid ? p.n_sweep_tiles : 0;
     if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] sweep plan: tile_rows=%d wlog=%d tiles=%lld sweep=%lld rest_chunks=%zu elements=%zu cnt_bytes=%zu\n",
@@ -790,9 +792,17 @@ int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, c
     if (B) {
         if (e == hipSuccess) e = A->sw.wave_off_b.upload(p.wave_off_b.data(), p.wave_off_b.size() * 4);
         if (e == hipSuccess) e = A->sw.cnt_b.upload(p.cnt_b.data(), p.cnt_b.size());
-        if (e == hipSuccess) e = A->sw.vals_b.upload(p.vals_b_f32.data(), p.idx_b.size() * 4);
+        if (e == hipSuccess) e = sB->dtype == USPMV_F16 ? A->sw.vals_b.upload(p.vals_b_f16.data(), p.idx_b.size() * 2)
+                                                        : A->sw.vals_b.upload(p.vals_b_f32.data(), p.idx_b.size() * 4);
         if (e == hipSuccess) e = A->sw.idx_b.upload(p.idx_b.data(), p.idx_b.size() * 2);
         if (e == hipSuccess) e = A->sw.pad_b.upload(p.pad_col_b.data(), p.pad_col_b.size() * 4);
+    }
+    if (B3) {
+        if (e == hipSuccess) e = A->sw.wave_off_c.upload(p.wave_off_c.data(), p.wave_off_c.size() * 4);
+        if (e == hipSuccess) e = A->sw.cnt_c.upload(p.cnt_c.data(), p.cnt_c.size());
+        if (e == hipSuccess) e = A->sw.vals_c.upload(p.vals_c_f16.data(), p.idx_c.size() * 2);
+        if (e == hipSuccess) e = A->sw.idx_c.upload(p.idx_c.data(), p.idx_c.size() * 2);
+        if (e == hipSuccess) e = A->sw.pad_c.upload(p.pad_col_c.data(), p.pad_col_c.size() * 4);
     }
     if (e != hipSuccess) {
         A->sw = {};
@@ -803,16 +813,22 @@ int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, c
     A->sw.on = true; A->sw.tile_rows = p.tile_rows; A->sw.wlog = p.wlog; A->sw.n_tiles = p.n_sweep_tiles; A->sw.all_tiles = p.n_tiles;
     A->sw.x_len = p.x_len_min; A->sw.n_rest = (int64_t)p.rest_chunks.size(); A->sw.plan_id = id;
     A->sw.n_vals = (int64_t)p.idx.size() - 64; A->sw.n_vals_b = B ? (int64_t)p.idx_b.size() - 64 : 0; A->sw.cnt_bytes = (int64_t)p.cnt.size();
-    if (B) { B->sw.on = true; B->sw.plan_id = id; B->sw.n_tiles = p.n_sweep_tiles; B->sw.all_tiles = p.n_tiles; }
+    A->sw.n_vals_c = B3 ? (int64_t)p.idx_c.size() - 64 : 0;
+    A->sw.n_parts = B3 ? 3 : B ? 2 : 1;
+    if (B) A->sw.dtype_b = sB->dtype;
+    for (uspmv_dmat_t *M : {B, B3})
+        if (M) { M->sw.on = true; M->sw.plan_id = id; M->sw.n_tiles = p.n_sweep_tiles; M->sw.all_tiles = p.n_tiles; }
     return USPMV_OK;
 }
 
 // The same plan from the handle's DEVICE arrays (csrc/sweep_plan_kernels.hip): a scan kernel per struct, the tile decisions and the
 // offsets on the host (O(n_tiles); 16 bytes per 64-row group come back), a fill kernel per struct.  Same defaults, same criteria and
 // -- by construction of the fill kernel -- the same arrays as sweep_plan_install builds from a host struct.
-int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who) {
+int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who,
+                              uspmv_dmat_t *B3) {
     A->sw = {};
     if (B) B->sw = {};
+    if (B3) B3->sw = {};
     if (n_tiles) *n_tiles = 0;
     if (n_sweep) *n_sweep = 0;
     const int64_t C = A->C, nc = A->n_chunks;
@@ -830,13 +846,13 @@ int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int ti
     }
     if (tile_rows != 256 && tile_rows != 512 && tile_rows != 1024 && tile_rows != 2048 && tile_rows != 4096) tile_rows = 1024;
     if (C < 1 || C > 64 || 64 % C != 0 || nc < 1 || wlog < 8 || wlog > 16) return USPMV_OK;
-    if (A->n_elements > (int64_t)UINT32_MAX || (B && B->n_elements > (int64_t)UINT32_MAX)) return USPMV_OK;
+    if (A->n_elements > (int64_t)UINT32_MAX || (B && B->n_elements > (int64_t)UINT32_MAX) || (B3 && B3->n_elements > (int64_t)UINT32_MAX)) return USPMV_OK;
     const int64_t R = tile_rows, nt = (n_pad + R - 1) / R, wpt = R / 64, n_groups = (n_pad + 63) / 64;
-    const int ns = B ? 2 : 1;
-    const uspmv_dmat_t *M[2] = {A, B};
+    const int ns = B3 ? 3 : B ? 2 : 1;
+    const uspmv_dmat_t *M[3] = {A, B, B3};
     const double max_stage = g_tune.sweep_max_stage > 0 ? (double)g_tune.sweep_max_stage : 24.0;
     // ---- scan
-    DeviceBuf<int> d_le[2], d_pad[2], d_grp[2], d_max;
+    DeviceBuf<int> d_le[3], d_pad[3], d_grp[3], d_max;
     hipError_t e = d_max.zeros(4);
     for (int w = 0; w < ns && e == hipSuccess; ++w) {
         e = d_le[w].alloc(4 * (size_t)n_groups * 64);
@@ -844,7 +860,7 @@ int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int ti
         if (e == hipSuccess) e = d_grp[w].alloc(16 * (size_t)n_groups);
     }
     if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-    std::vector<int32_t> grp[2];
+    std::vector<int32_t> grp[3];
     int max_col = 0;
     int rc = USPMV_OK;
     for (int w = 0; w < ns && !rc; ++w) rc = launch_sweep_scan(M[w], wlog, d_le[w], d_pad[w], d_grp[w], d_max, nullptr);
@@ -858,7 +874,7 @@ int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int ti
     // ---- which tiles sweep (sweep_plan.cpp pass 1), offsets
     std::vector<int32_t> tile_ids, t_smin, t_S, rest;
     std::vector<uint64_t> t_cnt_off;
-    int64_t cnt_bytes = 0, tot[2] = {0, 0};
+    int64_t cnt_bytes = 0, tot[3] = {0, 0, 0};
     for (int64_t t = 0; t < nt; ++t) {
         int32_t lo = INT32_MAX, hi = -1;
         bool good = true;
@@ -880,7 +896,7 @@ int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int ti
     if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] sweep plan (device builder): tile_rows=%d wlog=%d tiles=%lld sweep=%lld rest_chunks=%zu cnt_bytes=%lld\n",
                                          tile_rows, wlog, (long long)nt, (long long)nsw, rest.size(), (long long)cnt_bytes);
     if (nsw == 0) return USPMV_OK;
-    std::vector<uint32_t> wave_off[2];
+    std::vector<uint32_t> wave_off[3];
     for (int w = 0; w < ns; ++w) {
         wave_off[w].assign((size_t)(nsw * wpt), 0);
         for (int64_t k = 0; k < nsw; ++k)
@@ -906,16 +922,25 @@ int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int ti
     if (B) {
         if (e == hipSuccess) e = A->sw.wave_off_b.upload(wave_off[1].data(), wave_off[1].size() * 4);
         if (e == hipSuccess) e = A->sw.cnt_b.zeros((size_t)cnt_bytes);
-        if (e == hipSuccess) e = A->sw.vals_b.zeros(((size_t)tot[1] + SPARE) * 4);
+        if (e == hipSuccess) e = A->sw.vals_b.zeros(((size_t)tot[1] + SPARE) * uspmv_dtype_bytes(B->dtype));
         if (e == hipSuccess) e = A->sw.idx_b.zeros(((size_t)tot[1] + SPARE) * 2);
         if (e == hipSuccess) e = A->sw.pad_b.zeros((size_t)(nsw * R) * 4);
+    }
+    if (B3) {
+        if (e == hipSuccess) e = A->sw.wave_off_c.upload(wave_off[2].data(), wave_off[2].size() * 4);
+        if (e == hipSuccess) e = A->sw.cnt_c.zeros((size_t)cnt_bytes);
+        if (e == hipSuccess) e = A->sw.vals_c.zeros(((size_t)tot[2] + SPARE) * uspmv_dtype_bytes(B3->dtype));
+        if (e == hipSuccess) e = A->sw.idx_c.zeros(((size_t)tot[2] + SPARE) * 2);
+        if (e == hipSuccess) e = A->sw.pad_c.zeros((size_t)(nsw * R) * 4);
     }
     if (e == hipSuccess && launch_sweep_fill(A, wlog, (int)R, (long)nsw, A->sw.tile_ids, A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off,
                                              d_le[0], d_pad[0], A->sw.cnt, A->sw.vals, A->sw.idx, A->sw.pad, nullptr) != USPMV_OK) e = hipErrorUnknown;
     if (e == hipSuccess && B && launch_sweep_fill(B, wlog, (int)R, (long)nsw, A->sw.tile_ids, A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off_b,
                                                   d_le[1], d_pad[1], A->sw.cnt_b, A->sw.vals_b, A->sw.idx_b, A->sw.pad_b, nullptr) != USPMV_OK) e = hipErrorUnknown;
+    if (e == hipSuccess && B3 && launch_sweep_fill(B3, wlog, (int)R, (long)nsw, A->sw.tile_ids, A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off_c,
+                                                   d_le[2], d_pad[2], A->sw.cnt_c, A->sw.vals_c, A->sw.idx_c, A->sw.pad_c, nullptr) != USPMV_OK) e = hipErrorUnknown;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    for (int w = 0; w < 2; ++w) { d_le[w].reset(); d_pad[w].reset(); d_grp[w].reset(); }
+    for (int w = 0; w < 3; ++w) { d_le[w].reset(); d_pad[w].reset(); d_grp[w].reset(); }
     d_max.reset();
     if (e != hipSuccess) {
         A->sw = {};
@@ -925,8 +950,11 @@ int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int ti
     const uint64_t id = next_dev_sweep_id++;
     A->sw.on = true; A->sw.tile_rows = tile_rows; A->sw.wlog = wlog; A->sw.n_tiles = nsw; A->sw.all_tiles = nt;
     A->sw.x_len = (int64_t)max_col + 1; A->sw.n_rest = (int64_t)rest.size(); A->sw.plan_id = id;
-    A->sw.n_vals = tot[0]; A->sw.n_vals_b = B ? tot[1] : 0; A->sw.cnt_bytes = cnt_bytes;
-    if (B) { B->sw.on = true; B->sw.plan_id = id; B->sw.n_tiles = nsw; B->sw.all_tiles = nt; }
+    A->sw.n_vals = tot[0]; A->sw.n_vals_b = B ? tot[1] : 0; A->sw.n_vals_c = B3 ? tot[2] : 0; A->sw.cnt_bytes = cnt_bytes;
+    A->sw.n_parts = ns;
+    if (B) A->sw.dtype_b = B->dtype;
+    for (uspmv_dmat_t *Q : {B, B3})
+        if (Q) { Q->sw.on = true; Q->sw.plan_id = id; Q->sw.n_tiles = nsw; Q->sw.all_tiles = nt; }
     return USPMV_OK;
 }
 
@@ -954,6 +982,31 @@ int uspmv_dmat_optimize_sweep_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_sweep_ap: handles / host structs do not form a dp+sp pair");
     if (int rc = require_device()) return rc;
     return sweep_plan_install(dp, sp, s_dp, s_sp, wlog, tile_rows, n_tiles, n_sweep, "uspmv_dmat_optimize_sweep_ap");
+}
+
+int uspmv_dmat_optimize_sweep_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
+                                    const uspmv_scs_t *s_hp, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep) {
+    const char *who = "uspmv_dmat_optimize_sweep_ap_hp";
+    if (!s_hi || !s_hp || (mid && !s_mid)) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    const uspmv_scs_t *ss[3] = {s_hi, mid ? s_mid : s_hp, mid ? s_hp : nullptr};
+    uspmv_dmat_t *const ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
+    for (int k = 0; k < 3; ++k) {
+        if (!ms[k]) continue;
+        if (!uspmv::scs_has_entries(ss[k])) return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host entries", who);
+        if (ms[k]->C != ss[k]->C || ms[k]->n_chunks != ss[k]->n_chunks || ms[k]->dtype != ss[k]->dtype)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: handles and host structs do not describe the same parts", who);
+    }
+    if (int rc = require_device()) return rc;
+    return sweep_plan_install(ms[0], ms[1], ss[0], ss[1], wlog, tile_rows, n_tiles, n_sweep, who, ms[2], ss[2]);
+}
+
+int uspmv_dmat_optimize_sweep_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, int wlog, int tile_rows, int64_t *n_tiles,
+                                           int64_t *n_sweep) {
+    const char *who = "uspmv_dmat_optimize_sweep_device_ap_hp";
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    if (int rc = require_device()) return rc;
+    return sweep_plan_install_device(hi, mid ? mid : hp, wlog, tile_rows, n_tiles, n_sweep, who, mid ? hp : nullptr);
 }
 
 // The block-vector column-window sweep plan (host/sweep_plan.cpp: uspmv_build_block_sweep_plan; kernel csrc/spmmv_sweep.hip) for 64-byte X
@@ -1105,10 +1158,46 @@ int uspmv_dmat_sweep_plan_digest(const uspmv_dmat_t *A, uint64_t digest[16], int
     if (!rc && A->sw.idx_b) {
         rc = fnv(A->sw.wave_off_b, nsw * wpt * 4, &digest[10]);
         if (!rc) rc = fnv(A->sw.cnt_b, (size_t)A->sw.cnt_bytes, &digest[11]);
-        if (!rc) rc = fnv(A->sw.vals_b, (size_t)A->sw.n_vals_b * 4, &digest[12]);
+        if (!rc) rc = fnv(A->sw.vals_b, (size_t)A->sw.n_vals_b * uspmv_dtype_bytes(A->sw.dtype_b), &digest[12]);
         if (!rc) rc = fnv(A->sw.idx_b, (size_t)A->sw.n_vals_b * 2, &digest[13]);
         if (!rc) rc = fnv(A->sw.pad_b, nsw * (size_t)A->sw.tile_rows * 4, &digest[14]);
     }
+    return rc;
+}
+
+// ... and of one part's arrays: wave offsets, counts, values, indices, padding columns
+int uspmv_dmat_sweep_plan_digest_part(const uspmv_dmat_t *A, int part, uint64_t digest[5], int64_t *n_vals) {
+    if (int rc = check_dmat(A, "uspmv_dmat_sweep_plan_digest_part")) return rc;
+    if (!digest || part < 0 || part > 2) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_sweep_plan_digest_part: bad argument");
+    for (int k = 0; k < 5; ++k) digest[k] = 0;
+    if (n_vals) *n_vals = 0;
+    const auto &w = A->sw;
+    if (!w.on || !w.tile_ids || part >= w.n_parts) return USPMV_OK;
+    const void *wo = part == 0 ? (const void *)w.wave_off : part == 1 ? (const void *)w.wave_off_b : (const void *)w.wave_off_c;
+    const void *cn = part == 0 ? (const void *)w.cnt : part == 1 ? (const void *)w.cnt_b : (const void *)w.cnt_c;
+    const void *va = part == 0 ? (const void *)w.vals : part == 1 ? (const void *)w.vals_b : (const void *)w.vals_c;
+    const void *ix = part == 0 ? (const void *)w.idx : part == 1 ? (const void *)w.idx_b : (const void *)w.idx_c;
+    const void *pd = part == 0 ? (const void *)w.pad : part == 1 ? (const void *)w.pad_b : (const void *)w.pad_c;
+    const size_t nv = (size_t)(part == 0 ? w.n_vals : part == 1 ? w.n_vals_b : w.n_vals_c);
+    const size_t vsz = uspmv_dtype_bytes(part == 0 ? A->dtype : part == 1 ? w.dtype_b : w.dtype_c);
+    const size_t nsw = (size_t)w.n_tiles, wpt = (size_t)w.tile_rows / 64;
+    if (n_vals) *n_vals = (int64_t)nv;
+    std::vector<unsigned char> buf;
+    auto fnv = [&](const void *d, size_t bytes, uint64_t *out) -> int {
+        uint64_t h = 1469598103934665603ull;
+        if (d && bytes) {
+            buf.resize(bytes);
+            HIP_TRY(hipMemcpy(buf.data(), d, bytes, hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < bytes; ++k) { h ^= buf[k]; h *= 1099511628211ull; }
+        }
+        *out = h;
+        return USPMV_OK;
+    };
+    int rc = fnv(wo, nsw * wpt * 4, &digest[0]);
+    if (!rc) rc = fnv(cn, (size_t)w.cnt_bytes, &digest[1]);
+    if (!rc) rc = fnv(va, nv * vsz, &digest[2]);
+    if (!rc) rc = fnv(ix, nv * 2, &digest[3]);
+    if (!rc) rc = fnv(pd, nsw * (size_t)w.tile_rows * 4, &digest[4]);
     return rc;
 }
 

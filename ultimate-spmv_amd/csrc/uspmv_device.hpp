@@ -219,21 +219,23 @@ struct uspmv_dmat {
         DeviceBuf<void> vals;
         DeviceBuf<uint16_t> idx;
     } bw;
-    // column-window sweep plan (host/sweep_plan.cpp, uspmv_dmat_optimize_sweep[_ap]); the _b arrays are the sp part of
-    // an ap[dp_sp] pair and live on the dp handle, the sp handle only carries the plan id and the tile counts
+    // column-window sweep plan (host/sweep_plan.cpp, uspmv_dmat_optimize_sweep[_ap | _ap_hp]); the _b arrays are the second part (the sp
+    // part of an ap[dp_sp] pair; the mid or the hp part of a split with an fp16 part), the _c arrays the third (the hp part of
+    // ap[dp_sp_hp]).  All live on the first part's handle; the other handles only carry the plan id and the tile counts.  n_parts and
+    // dtype_b / dtype_c say what the streams hold (vals_b: float, or binary16 bits; vals_c: binary16 bits)
     struct SweepPlan {
         bool on = false;
         int tile_rows = 1024, wlog = 13;
         int64_t n_tiles = 0, all_tiles = 0, x_len = 0, n_rest = 0;
-        int64_t n_vals = 0, n_vals_b = 0, cnt_bytes = 0;   // elements of the compacted streams (without the spare tail), bytes of a count array
+        int64_t n_vals = 0, n_vals_b = 0, n_vals_c = 0, cnt_bytes = 0;   // elements of the compacted streams (without the spare tail), bytes of a count array
+        int n_parts = 1, dtype_b = USPMV_F32, dtype_c = USPMV_F16;
         uint64_t plan_id = 0;
-        DeviceBuf<int32_t> tile_ids, smin, S, pad, pad_b, rest;
+        DeviceBuf<int32_t> tile_ids, smin, S, pad, pad_b, pad_c, rest;
         DeviceBuf<uint64_t> cnt_off;
-        DeviceBuf<uint32_t> wave_off, wave_off_b;
-        DeviceBuf<uint8_t> cnt, cnt_b;
-        DeviceBuf<void> vals;
-        DeviceBuf<float> vals_b;
-        DeviceBuf<uint16_t> idx, idx_b;
+        DeviceBuf<uint32_t> wave_off, wave_off_b, wave_off_c;
+        DeviceBuf<uint8_t> cnt, cnt_b, cnt_c;
+        DeviceBuf<void> vals, vals_b, vals_c;
+        DeviceBuf<uint16_t> idx, idx_b, idx_c;
     } sw;
 };
 
@@ -364,9 +366,11 @@ int check_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *h
 // 16-bit index offsets per chunk from the chunk lengths (O(n_chunks) on the host); false: too large for 32-bit offsets
 bool c16_offsets(const std::vector<int32_t> &cl, int64_t C, std::vector<uint32_t> *c16p, int64_t *tot16);   // tlc_planner.hip
 // the column-window sweep plan from a host struct / from the handle's device arrays (uspmv_api.hip); wlog, tile_rows 0: defaults
+// (B / B3: the further parts of an ap split sharing the plan, see uspmv_dmat::SweepPlan)
 int sweep_plan_install(uspmv_dmat *A, uspmv_dmat *B, const uspmv_scs *s, const uspmv_scs *sB, int wlog, int tile_rows, int64_t *n_tiles,
-                       int64_t *n_sweep, const char *who);
-int sweep_plan_install_device(uspmv_dmat *A, uspmv_dmat *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who);
+                       int64_t *n_sweep, const char *who, uspmv_dmat *B3 = nullptr, const uspmv_scs *sB3 = nullptr);
+int sweep_plan_install_device(uspmv_dmat *A, uspmv_dmat *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who,
+                              uspmv_dmat *B3 = nullptr);
 inline unsigned grid_for(long work_items, int block) { return (unsigned)((work_items + block - 1) / block); }
 
 constexpr size_t BT_LDS_CAP = 80 * 1024;  // LDS per single-wave SpMMV tile (block plan): two tiles per CU at worst
@@ -404,6 +408,10 @@ int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st); 
 int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st);                       // sweep_kernels.hip
 int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *d_x,
                           double *d_y, hipStream_t stream);                                                        // ap_kernels.hip
+// the sweep tiles of a plan shared by the parts of a split with an fp16 part (sweep_ap_hp_kernels.hip) and the chunks it leaves over
+int launch_spmv_sweep_ap_hp(const uspmv_dmat *hi, bool mid, const void *x, void *y, hipStream_t st);
+int launch_spmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
+                             const void *d_x, void *d_y, hipStream_t stream);                                      // ap_kernels.hip
 
 // (A2 / the *_2 arrays: optional second struct sharing the plan -- the sp part of an ap[dp_sp] pair; A3 / *_3 a third -- the hp part of
 //  ap[dp_sp_hp])
@@ -475,6 +483,24 @@ __device__ __forceinline__ void st_y(T *p, T v) {
 }
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// Adaptive precision with an fp16 part (ap_kernels.hip, sweep_ap_hp_kernels.hip): one step of a part's chain.  With a double x every
+// product is an FMA in double on the exactly widened value (scs_ap_impl_cpu's convention, hp in the place of sp), with a float x the
+// product is rounded to float and then added to the part's double accumulator (the sp part of spmv_omp_scs_ap).  hp values arrive
+// as the binary16 bits; v_cvt_f32_f16 widens them exactly.
+__device__ __forceinline__ float hp_val(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
+__device__ __forceinline__ double ap_step(double v, double x, double acc) { return __builtin_fma(v, x, acc); }
+__device__ __forceinline__ double ap_step(float v, double x, double acc) { return __builtin_fma((double)v, x, acc); }
+__device__ __forceinline__ double ap_step(unsigned short v, double x, double acc) { return __builtin_fma((double)hp_val(v), x, acc); }
+__device__ __forceinline__ double ap_step(float v, float x, double acc) { return acc + (double)__fmul_rn(v, x); }
+__device__ __forceinline__ double ap_step(unsigned short v, float x, double acc) { return acc + (double)__fmul_rn(hp_val(v), x); }
+// y = hi + hp, (hi + mid) + hp, or (float)(sp + hp)
+template <typename HT, bool MID>
+__device__ __forceinline__ HT ap_hp_y(double h, double m, double q) {
+    if constexpr (sizeof(HT) == 4) return (float)(h + q);
+    else if constexpr (MID) return (h + m) + q;
+    else return h + q;
+}
 
 // DPP quad broadcast: every lane of a quad gets lane U's value (the four-lanes-per-row SpMMV kernels)
 template <int U>

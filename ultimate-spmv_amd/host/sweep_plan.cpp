@@ -22,6 +22,14 @@
 // Trailing padding of a row (value +0, one repeated column; code/utilities.hpp:1991-2002) is not stored: k >= 1
 // applications of acc = fma(+0, x[c], acc) equal one application (the second adds the same signed zero again, or
 // meets the NaN the first one made), so the kernel applies it once per row that had any (pad_col >= 0).
+//
+// Up to three structs with one row layout share a plan: the dp and the sp part of ap[dp_sp], or the two or three parts of a split with
+// an fp16 part (hi F64 | F32, [mid F32,] hp F16 -- binary16 bits, compacted as such).  The tile decisions are taken once per tile over
+// all parts (windows ascending and at most 255 entries per window in every row of every part; staging cost against the tile's entries
+// of all parts together, in bytes of x -- the first part's type); every part gets its own wave offsets, counts, stream and padding
+// columns.  The padding rule holds for every part in its own type: +0 of binary16 widens to +0.0, so with a double x the stripped step
+// is fma(+0, x[c], acc) again; with a float x (ap[sp_hp]) it is acc + (double)(0.0f * x[c]), and 0.0f * x[c] is a signed zero or NaN
+// whatever k is -- acc + z + z = acc + z for a signed zero z (acc + z is already -0 only if both were), and NaN stays NaN.
 #include <algorithm>
 #include <cstring>
 
@@ -32,6 +40,7 @@ namespace {
 template <typename VT>
 inline bool is_pos_zero(VT v) {
     if (sizeof(VT) == 8) { uint64_t b; std::memcpy(&b, &v, 8); return b == 0; }
+    if (sizeof(VT) == 2) { uint16_t b; std::memcpy(&b, &v, 2); return b == 0; }
     uint32_t b; std::memcpy(&b, &v, 4); return b == 0;
 }
 
@@ -47,27 +56,36 @@ inline int64_t effective_len(const int32_t *ci, const VT *va, int64_t cs, int64_
     return le;
 }
 
+inline int64_t effective_len(const uspmv_scs *m, int64_t cs, int64_t L, int64_t i, int32_t *pad_col) {
+    const int32_t *ci = m->col_idxs.data();
+    return m->dtype == USPMV_F64   ? effective_len(ci, m->values_f64.data(), cs, L, i, m->C, pad_col)
+           : m->dtype == USPMV_F32 ? effective_len(ci, m->values_f32.data(), cs, L, i, m->C, pad_col)
+                                   : effective_len(ci, m->values_f16.data(), cs, L, i, m->C, pad_col);
+}
+
 }  // namespace
 
 int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, int tile_rows, double max_stage_bytes_per_nnz,
-                           uspmv_sweep_plan *p) {
+                           uspmv_sweep_plan *p, const uspmv_scs *s3) {
     p->valid = false;
     const int64_t C = s->C, nc = s->n_chunks;
     if (tile_rows != 256 && tile_rows != 512 && tile_rows != 1024 && tile_rows != 2048 && tile_rows != 4096) tile_rows = 1024;
     if (C < 1 || C > 64 || 64 % C != 0 || nc < 1) return USPMV_OK;          // a wave covers whole chunks
-    if (s2 && (s2->C != C || s2->n_chunks != nc)) return USPMV_OK;
+    if (s3 && !s2) return USPMV_OK;
+    if (s->dtype == USPMV_F16) return USPMV_OK;                              // (x has the first part's type)
+    const int ns = s3 ? 3 : s2 ? 2 : 1;
+    const uspmv_scs *ss[3] = {s, s2, s3};
+    for (int w = 1; w < ns; ++w) if (ss[w]->C != C || ss[w]->n_chunks != nc) return USPMV_OK;
     if (wlog < 8 || wlog > 16) return USPMV_OK;                              // 16-bit local indices
-    if (s->n_elements > (int64_t)UINT32_MAX || (s2 && s2->n_elements > (int64_t)UINT32_MAX)) return USPMV_OK;
+    for (int w = 0; w < ns; ++w) if (ss[w]->n_elements > (int64_t)UINT32_MAX) return USPMV_OK;
     const int64_t R = tile_rows, n_pad = nc * C, n_tiles = (n_pad + R - 1) / R, wpt = R / 64;
-    const int ns = s2 ? 2 : 1;
-    const uspmv_scs *ss[2] = {s, s2};
-    const size_t vsz = s->dtype == USPMV_F64 ? 8 : 4;
+    const size_t vsz = s->dtype == USPMV_F64 ? 8 : 4;                        // bytes of an x element
     p->tile_rows = tile_rows; p->wlog = wlog; p->n_tiles = n_tiles;
 
     // ---- pass 1: which tiles sweep, their window range, entries per wave
     std::vector<int32_t> smin((size_t)n_tiles, 0), S((size_t)n_tiles, 0);
     std::vector<char> ok((size_t)n_tiles, 0);
-    std::vector<int64_t> wave_n[2];
+    std::vector<int64_t> wave_n[3];
     for (int w = 0; w < ns; ++w) wave_n[w].assign((size_t)(n_tiles * wpt), 0);
     int32_t max_col = 0;
 #pragma omp parallel
@@ -84,8 +102,7 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
                 for (int64_t q = q0; q < q1 && good; ++q) {
                     const int64_t c = q / C, i = q % C, cs = ss[w]->chunk_ptrs[(size_t)c], L = ss[w]->chunk_lengths[(size_t)c];
                     int32_t pc;
-                    const int64_t le = ss[w]->dtype == USPMV_F64 ? effective_len(ci, ss[w]->values_f64.data(), cs, L, i, C, &pc)
-                                                                 : effective_len(ci, ss[w]->values_f32.data(), cs, L, i, C, &pc);
+                    const int64_t le = effective_len(ss[w], cs, L, i, &pc);
                     if (pc >= 0) my_max = std::max(my_max, pc);
                     int32_t prev = -1;
                     int run = 0;
@@ -115,7 +132,7 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
     }
     // ---- compact list of sweep tiles, offsets
     p->tile_ids.clear(); p->t_smin.clear(); p->t_S.clear(); p->t_cnt_off.clear();
-    int64_t cnt_bytes = 0, tot[2] = {0, 0};
+    int64_t cnt_bytes = 0, tot[3] = {0, 0, 0};
     for (int64_t t = 0; t < n_tiles; ++t) {
         if (!ok[(size_t)t]) continue;
         p->tile_ids.push_back((int32_t)t); p->t_smin.push_back(smin[(size_t)t]); p->t_S.push_back(S[(size_t)t]);
@@ -131,8 +148,12 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
         if (!ok[(size_t)t])
             for (int64_t c = t * R / C; c < std::min((t + 1) * R / C, nc); ++c) p->rest_chunks.push_back((int32_t)c);
     if (nsw == 0) return USPMV_OK;
+    std::vector<uint32_t> *const wave_off[3] = {&p->wave_off, &p->wave_off_b, &p->wave_off_c};
+    std::vector<uint8_t> *const cnts[3] = {&p->cnt, &p->cnt_b, &p->cnt_c};
+    std::vector<uint16_t> *const idxs[3] = {&p->idx, &p->idx_b, &p->idx_c};
+    std::vector<int32_t> *const pads[3] = {&p->pad_col, &p->pad_col_b, &p->pad_col_c};
     for (int w = 0; w < ns; ++w) {
-        auto &wo = w == 0 ? p->wave_off : p->wave_off_b;
+        auto &wo = *wave_off[w];
         wo.assign((size_t)(nsw * wpt), 0);
         for (int64_t k = 0; k < nsw; ++k)
             for (int64_t v = 0; v < wpt; ++v) {
@@ -141,16 +162,16 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
             }
         if (tot[w] > (int64_t)UINT32_MAX) return USPMV_OK;
     }
-    p->cnt.assign((size_t)cnt_bytes, 0);
     constexpr size_t SPARE = 64;   // inactive lanes of the kernel load the batch's first element: keep that address valid at the very end
-    p->idx.assign((size_t)tot[0] + SPARE, 0);
-    p->pad_col.assign((size_t)(nsw * R), -1);
-    if (s->dtype == USPMV_F64) p->vals_f64.assign((size_t)tot[0] + SPARE, 0.0); else p->vals_f32.assign((size_t)tot[0] + SPARE, 0.0f);
-    if (s2) {
-        p->cnt_b.assign((size_t)cnt_bytes, 0);
-        p->idx_b.assign((size_t)tot[1] + SPARE, 0);
-        p->pad_col_b.assign((size_t)(nsw * R), -1);
-        if (s2->dtype == USPMV_F64) p->vals_b_f64.assign((size_t)tot[1] + SPARE, 0.0); else p->vals_b_f32.assign((size_t)tot[1] + SPARE, 0.0f);
+    void *vals[3] = {nullptr, nullptr, nullptr};                              // the part's stream in its own type
+    for (int w = 0; w < ns; ++w) {
+        cnts[w]->assign((size_t)cnt_bytes, 0);
+        idxs[w]->assign((size_t)tot[w] + SPARE, 0);
+        pads[w]->assign((size_t)(nsw * R), -1);
+        const size_t nv = (size_t)tot[w] + SPARE;
+        if (ss[w]->dtype == USPMV_F64) { auto &v = w == 0 ? p->vals_f64 : p->vals_b_f64; v.assign(nv, 0.0); vals[w] = v.data(); }
+        else if (ss[w]->dtype == USPMV_F32) { auto &v = w == 0 ? p->vals_f32 : p->vals_b_f32; v.assign(nv, 0.0f); vals[w] = v.data(); }
+        else { auto &v = w == 1 ? p->vals_b_f16 : p->vals_c_f16; v.assign(nv, 0); vals[w] = v.data(); }
     }
     // ---- pass 2: counts and the compacted entry stream
 #pragma omp parallel
@@ -164,15 +185,14 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
             for (int w = 0; w < ns; ++w) {
                 const uspmv_scs *m = ss[w];
                 const int32_t *ci = m->col_idxs.data();
-                uint8_t *cnt = (w == 0 ? p->cnt.data() : p->cnt_b.data()) + p->t_cnt_off[(size_t)k];
-                int32_t *padc = (w == 0 ? p->pad_col.data() : p->pad_col_b.data()) + k * R;
-                uint16_t *idx = w == 0 ? p->idx.data() : p->idx_b.data();
-                const auto &wo = w == 0 ? p->wave_off : p->wave_off_b;
+                uint8_t *cnt = cnts[w]->data() + p->t_cnt_off[(size_t)k];
+                int32_t *padc = pads[w]->data() + k * R;
+                uint16_t *idx = idxs[w]->data();
+                const auto &wo = *wave_off[w];
                 for (int64_t q = q0; q < q1; ++q) {
                     const int64_t c = q / C, i = q % C, cs = m->chunk_ptrs[(size_t)c], L = m->chunk_lengths[(size_t)c];
                     int32_t pc;
-                    le[(size_t)(q - q0)] = m->dtype == USPMV_F64 ? effective_len(ci, m->values_f64.data(), cs, L, i, C, &pc)
-                                                                  : effective_len(ci, m->values_f32.data(), cs, L, i, C, &pc);
+                    le[(size_t)(q - q0)] = effective_len(m, cs, L, i, &pc);
                     padc[q - q0] = pc;
                     pos[(size_t)(q - q0)] = 0;
                     for (int64_t j = 0; j < le[(size_t)(q - q0)]; ++j) ++cnt[(size_t)(((ci[cs + j * C + i] >> wlog) - lo) * R + (q - q0))];
@@ -191,8 +211,9 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
                                 const int64_t j = pos[(size_t)r]++;
                                 const int64_t src = cs + j * C + i;
                                 idx[(size_t)out] = (uint16_t)(ci[src] - ((int32_t)(lo + sw) << wlog));
-                                if (m->dtype == USPMV_F64) (w == 0 ? p->vals_f64 : p->vals_b_f64)[(size_t)out] = m->values_f64[(size_t)src];
-                                else (w == 0 ? p->vals_f32 : p->vals_b_f32)[(size_t)out] = m->values_f32[(size_t)src];
+                                if (m->dtype == USPMV_F64) ((double *)vals[w])[out] = m->values_f64[(size_t)src];
+                                else if (m->dtype == USPMV_F32) ((float *)vals[w])[out] = m->values_f32[(size_t)src];
+                                else ((uint16_t *)vals[w])[out] = m->values_f16[(size_t)src];
                                 ++out;
                             }
                     }

@@ -284,7 +284,12 @@ int uspmv_dmat_optimize_block_device(uspmv_dmat_t *m, int block_vec_size, int64_
  * (uspmv_dmat_wrap around the reference's cudaMalloc'ed arrays, uspmv_convert_to_scs_device).  Chunk heights that
  * divide 256; tiles whose line range exceeds 65 536 lines stay on the gather path (the host planner may still
  * stage those); otherwise the plan is identical to uspmv_dmat_optimize's.  Narrow chunks (C in {1,2,4,8,16}, incl. crs) get the
- * same internal C = 32 re-chunking as in uspmv_dmat_optimize, copied on the device. */
+ * same internal C = 32 re-chunking as in uspmv_dmat_optimize, copied on the device.
+ * The order of the plans is uspmv_dmat_optimize's: the line plan, then -- max_lines 0 and a line plan that is invalid or stages under
+ * nine tenths of its tiles -- the plan over single x elements on 256-row tiles, built on the device as well (a set of the tile's columns
+ * in LDS, sorted; equal to the host planner's element plan array for array, *n_tiles / *n_staged then describe it and
+ * uspmv_dmat_plan_granularity answers 1), then the column-window sweep.  Same tuning keys ("tlc_elem", "tlc_elem_cap").  Not here:
+ * the element plan on rows dealt to the tiles by the matrix graph ("tlc_elem_rows"), which needs the host struct. */
 int uspmv_dmat_optimize_device(uspmv_dmat_t *m, int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* The shared plan of an ap[dp_sp] pair (uspmv_dmat_optimize_ap) built on the device from the two handles' own arrays. */
 int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_lines, int64_t *n_tiles, int64_t *n_staged);

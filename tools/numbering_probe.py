@@ -46,7 +46,8 @@ for K in Ks:
     # ---- SpMV
     x = torch.rand(npad, dtype=torch.float64, device="cuda"); y = torch.zeros_like(x); yr = torch.zeros_like(x)
     pkg.set_tuning(tlc=0); A0 = pkg.DeviceMatrix(s); pkg.spmv(A0, x, yr); pkg.set_tuning(tlc=1)
-    A = pkg.DeviceMatrix(s, tlc=True)
+    A = pkg.DeviceMatrix(s)
+    t1 = time.perf_counter(); A.optimize(s); host_plan_ms = (time.perf_counter() - t1) * 1e3
     pkg.spmv(A, x, y)
     same = bool(torch.equal(y[: s.n_rows], yr[: s.n_rows]))
     B.time_launches(0, 20, A=A, x=x, y=y)
@@ -55,6 +56,53 @@ for K in Ks:
     kind = dict(tiles=A.tlc_tiles, staged=A.tlc_staged, index_bits=A.index_bits(), elements_per_list_entry=A.plan_granularity())
     print(json.dumps(dict(K=K, cols_only=cols_only, tlc_elem=pkg.get_tuning("tlc_elem"), op="spmv", n=n, nnz=int(len(I)), prep_s=round(prep_s, 1), plan=kind, tile_rows=getattr(A, "tile_rows", None), bitexact=same, ms=round(ms, 4),
                           frac=round(byts / ms / 1e6 / 8000, 3))), flush=True)
+    # ---- the same matrix planned from the handle's device arrays alone (uspmv_dmat_optimize_device: what uspmv_dmat_wrap, the device conversions and the raw-array
+    # entry points get): the build end to end, the SpMV alternating with the host-planned handle, the raw-array call through the plan cache; tlc_elem 0: the
+    # device planner without its element plan (lines, then the sweep)
+    if os.environ.get("NUMBERING_DEVICE_PLAN", "1") == "1":
+        elem_setting = pkg.get_tuning("tlc_elem")
+        def device_planned(elem):
+            pkg.set_tuning(tlc_elem=elem)
+            try:
+                H = pkg.DeviceMatrix(s); torch.cuda.synchronize()
+                t1 = time.perf_counter(); H.optimize_device(); torch.cuda.synchronize()
+                return H, (time.perf_counter() - t1) * 1e3
+            finally:
+                pkg.set_tuning(tlc_elem=elem_setting)
+        def raw_ms(H, elem):
+            pkg.set_tuning(tlc_elem=elem, raw_plan_cache=1)
+            try:
+                for _ in range(20): pkg.uspmv_scs_gpu(32, nch, H.chunk_ptrs, H.chunk_lengths, H.col_idxs, H.values, x, yd)      # (the first call plans)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                best = 1e30
+                for _ in range(3):
+                    e0.record()
+                    for _ in range(40): pkg.uspmv_scs_gpu(32, nch, H.chunk_ptrs, H.chunk_lengths, H.col_idxs, H.values, x, yd)
+                    e1.record(); torch.cuda.synchronize()
+                    best = min(best, e0.elapsed_time(e1) / 40)
+                return best
+            finally:
+                pkg.set_tuning(tlc_elem=elem_setting, raw_plan_cache=0); pkg.lib().uspmv_raw_plan_cache_clear()
+        yd = torch.zeros_like(x)
+        Ad, dev_plan_ms = device_planned(elem_setting)
+        pkg.spmv(Ad, x, yd)
+        same_d = bool(torch.equal(yd[: s.n_rows], yr[: s.n_rows]))
+        ms_h, ms_d = 1e30, 1e30
+        for _ in range(3):                                                   # alternating A/B of the two handles
+            ms_h = min(ms_h, B.time_launches(0, 40, A=A, x=x, y=y)); ms_d = min(ms_d, B.time_launches(0, 40, A=Ad, x=x, y=yd))
+        A0d, dev_plan0_ms = device_planned(0)
+        B.time_launches(0, 20, A=A0d, x=x, y=yd)
+        ms_0 = min(B.time_launches(0, 40, A=A0d, x=x, y=yd) for _ in range(3))
+        kind_d = dict(tiles=Ad.tlc_tiles, staged=Ad.tlc_staged, index_bits=Ad.index_bits(), elements_per_list_entry=Ad.plan_granularity())
+        kind_0 = dict(kind=A0d.plan_info()[0], staged=A0d.tlc_staged, elements_per_list_entry=A0d.plan_granularity())
+        raw1, raw0 = raw_ms(Ad, elem_setting), raw_ms(Ad, 0)
+        fr = lambda v: round(byts / v / 1e6 / 8000, 3)
+        print(json.dumps(dict(K=K, cols_only=cols_only, op="spmv planned on the device", plan=kind_d, bitexact=same_d, host_plan_ms=round(host_plan_ms, 1),
+                              device_plan_ms=round(dev_plan_ms, 1), ms_host_planned=round(ms_h, 4), ms_device_planned=round(ms_d, 4), frac_host_planned=fr(ms_h),
+                              frac_device_planned=fr(ms_d), raw_plan_cache_ms=round(raw1, 4), raw_plan_cache_frac=fr(raw1),
+                              without_element_plan=dict(plan=kind_0, device_plan_ms=round(dev_plan0_ms, 1), ms=round(ms_0, 4), frac=fr(ms_0),
+                                                        raw_plan_cache_ms=round(raw0, 4), raw_plan_cache_frac=fr(raw0)))), flush=True)
+        del Ad, A0d, yd
     del A, A0
     if os.environ.get("NUMBERING_SPMV_ONLY") == "1":
         del m, s

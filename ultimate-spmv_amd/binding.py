@@ -901,7 +901,10 @@ class DeviceMatrix:
         return a.value, n.value
 
     def optimize_device(self, max_lines=0):
-        """Build the tile-local-column plan on the device from the handle's own arrays (uspmv_dmat_optimize_device)."""
+        """Build the tile-local-column plan on the device from the handle's own arrays (uspmv_dmat_optimize_device); returns (n_tiles,
+        n_staged_tiles).  The plans are tried in optimize()'s order -- 16-element lines, then (max_lines 0, under nine tenths of the tiles staged)
+        single x elements, then the column-window sweep -- and equal the host planner's array for array; plan_granularity() and plan_info()
+        tell which one the handle ended up with.  Rows are never dealt by the matrix graph here (that needs the host struct)."""
         a, b = _i64(), _i64()
         _ck(lib().uspmv_dmat_optimize_device(self.h, max_lines, C.byref(a), C.byref(b)))
         self.tlc_tiles, self.tlc_staged = a.value, b.value

@@ -10,6 +10,8 @@
 // columns apart (round 3: before, only one cluster at either end of the range was representable and the KKT matrix of
 // uspmv_gen_kkt came out almost unstaged).  Tiles that need more than 16 windows are left unstaged (the host planner sorts those),
 // which changes the plan, never y; everywhere else the plan is identical to the host planner's.
+// The plan over single x elements has two kernels of its own further down (plan_count_elems, plan_write_elems): a set in LDS and a
+// sort instead of the bitmap, identical to the host planner's element plan for every tile.
 #include "uspmv_device.hpp"
 
 using namespace uspmv_dev;
@@ -216,6 +218,113 @@ __global__ void __launch_bounds__(256) plan_write(const long n_chunks, const int
     }
 }
 
+// ---- the plan over single x ELEMENTS (uspmv_build_tlc_plan with line_shift 0, 256-row tiles) -------------------------------------------
+// A tile of a scattered numbering lists a thousand or two distinct columns spread over a range of 10^5: dozens of 4 096-entry windows,
+// which no bitmap of the form above holds.  So the tile's distinct columns are collected in an open-addressing SET in LDS (2^log2n
+// slots, linear probing, atomicCAS on the slot; a column enters exactly once whichever lane brings it first), and the write pass sorts
+// the table in place (bitonic, empty slots = INT32_MAX sink to the end): table[0 .. n) is then the tile's ascending element list and a
+// slot's local index the column's rank in it, found by binary search.  Neither the count nor the sorted list depends on the order in
+// which lanes or atomics arrive.  One workgroup per tile, thread <-> row, padding slots counted like the host planner counts them.
+constexpr int ELEM_EMPTY = INT32_MAX;          // (no column index reaches it: n_cols <= INT32_MAX)
+
+// The set of the tile's columns in set[0 .. 2^log2n); *s_cnt = distinct columns entered.  Lanes stop entering once *s_cnt exceeds `cap`
+// (every lane can pass that test at most once more: at most cap + 256 entries, and the launchers size the table beyond that), so
+// min(*s_cnt, cap + 1) is exact.  Returns the largest column of the lane's row.
+__device__ __forceinline__ int tile_elem_set(const long n_chunks, const int C, const int *__restrict__ chunk_ptrs, const int *__restrict__ chunk_lengths,
+                                             const int *__restrict__ col_idxs, const long tile, int *set, const int log2n, const int cap, int *s_cnt) {
+    const unsigned mask = (1u << log2n) - 1u;
+    for (unsigned w = threadIdx.x; w <= mask; w += 256) set[w] = ELEM_EMPTY;
+    if (threadIdx.x == 0) *s_cnt = 0;
+    __syncthreads();
+    const long row = tile * 256 + threadIdx.x;
+    const long c = row / C;
+    const int i = (int)(row - c * C);
+    int mx = 0;
+    if (c < n_chunks) {
+        const int cs = chunk_ptrs[c], L = chunk_lengths[c];
+        int last = -1;
+        for (int j = 0; j < L; ++j) {
+            const int col = col_idxs[(long)cs + (long)j * C + i];
+            mx = max(mx, col);
+            if (col == last) continue;                      // (the padding slots of a row repeat one column)
+            last = col;
+            if (__atomic_load_n(s_cnt, __ATOMIC_RELAXED) > cap) continue;
+            unsigned h = ((unsigned)col * 2654435761u) >> (32 - log2n);
+            for (unsigned probe = 0; probe <= mask; ++probe, h = (h + 1u) & mask) {
+                int old = __atomic_load_n(&set[h], __ATOMIC_RELAXED);
+                if (old == ELEM_EMPTY) {
+                    old = atomicCAS(&set[h], ELEM_EMPTY, col);
+                    if (old == ELEM_EMPTY) { atomicAdd(s_cnt, 1); break; }
+                }
+                if (old == col) break;
+            }
+        }
+    }
+    __syncthreads();
+    return mx;
+}
+
+// count pass: n_elems[tile] = distinct columns of the tile, clipped at cap + 1 ("over the cap" stays visible); *max_col as plan_count_lines
+__global__ void __launch_bounds__(256) plan_count_elems(const long n_chunks, const int C, const int *__restrict__ chunk_ptrs,
+        const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs, const int cap, const int log2n, int *__restrict__ n_elems,
+        int *__restrict__ max_col) {
+    extern __shared__ int elem_set[];
+    __shared__ int s_cnt, s_maxcol;
+    if (threadIdx.x == 0) s_maxcol = 0;
+    const long tile = blockIdx.x;
+    const int mx = tile_elem_set(n_chunks, C, chunk_ptrs, chunk_lengths, col_idxs, tile, elem_set, log2n, cap, &s_cnt);
+    if (mx > 0) atomicMax(&s_maxcol, mx);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        n_elems[tile] = min(s_cnt, cap + 1);
+        atomicMax(max_col, s_maxcol);
+    }
+}
+
+// write pass: the tile's sorted element list at tile_line_ptr[tile] and every slot's rank in it as its 16-bit local index (col16 layout
+// [group of four slots][row i][slot % 4]; zero-filled before, so slots beyond the chunk length, tiles over the cap and empty tiles stay zero)
+__global__ void __launch_bounds__(256) plan_write_elems(const long n_chunks, const int C, const int *__restrict__ chunk_ptrs,
+        const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs, const int *__restrict__ tile_line_ptr,
+        const unsigned *__restrict__ c16_ptrs, int *__restrict__ tile_lines, unsigned short *__restrict__ col16, const int log2n) {
+    extern __shared__ int elem_set[];
+    __shared__ int s_cnt;
+    const long tile = blockIdx.x;
+    const int lp0 = tile_line_ptr[tile], n = tile_line_ptr[tile + 1] - lp0;
+    if (n == 0) return;                                     // over the cap or empty: the kernel gathers
+    (void)tile_elem_set(n_chunks, C, chunk_ptrs, chunk_lengths, col_idxs, tile, elem_set, log2n, INT32_MAX - 1, &s_cnt);
+    const int N = 1 << log2n;                               // (>= 1024: every stage has work for all 256 threads)
+    for (int k = 2; k <= N; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int q = threadIdx.x; q < N / 2; q += 256) {
+                const int a = ((q & ~(j - 1)) << 1) | (q & (j - 1)), b = a | j;
+                const int va = elem_set[a], vb = elem_set[b];
+                if ((va > vb) == ((a & k) == 0)) { elem_set[a] = vb; elem_set[b] = va; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int r = threadIdx.x; r < n; r += 256) tile_lines[lp0 + r] = elem_set[r];
+    const long row = tile * 256 + threadIdx.x;
+    const long c = row / C;
+    const int i = (int)(row - c * C);
+    if (c >= n_chunks) return;
+    const int cs = chunk_ptrs[c], L = chunk_lengths[c];
+    unsigned short *q = col16 + c16_ptrs[c];
+    int last = -1, rank = 0;
+    for (int j = 0; j < L; ++j) {
+        const int col = col_idxs[(long)cs + (long)j * C + i];
+        if (col != last) {
+            int lo = 0, hi = n;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (elem_set[mid] < col) lo = mid + 1; else hi = mid;
+            }
+            last = col; rank = min(lo, n - 1);
+        }
+        q[(long)(j >> 2) * 4 * C + i * 4 + (j & 3)] = (unsigned short)rank;
+    }
+}
+
 // uspmv_scs_rechunk32 (host/tlc_plan.cpp) on the device: new chunk k = old chunks [k*32/C, (k+1)*32/C), row order untouched;
 // thread <-> row of the new struct, whose arrays were zero-filled before (padding = value 0, column 0)
 template <typename VT>
@@ -296,6 +405,37 @@ int launch_plan_write(const uspmv_dmat *A, long n_tiles, const int *d_tile_line_
                        A->chunk_lengths, A->col_idxs, d_tile_line_ptr, d_c16_ptrs, d_tile_lines, d_col16, A2 ? A2->chunk_ptrs : nullptr,
                        A2 ? A2->chunk_lengths : nullptr, A2 ? A2->col_idxs : nullptr, d_c16_ptrs2, d_col16_2, tile_rows / 256,
                        A3 ? A3->chunk_ptrs : nullptr, A3 ? A3->chunk_lengths : nullptr, A3 ? A3->col_idxs : nullptr, d_c16_ptrs3, d_col16_3);
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
+// slots of the element set in LDS: a power of two, at least twice `most` distinct columns (and >= most + 257, see tile_elem_set)
+static int elem_set_log2(int most) {
+    int l = 10;
+    while ((1 << l) < 2 * most) ++l;
+    return l;
+}
+
+int launch_plan_count_elems(const uspmv_dmat *A, long n_tiles, int cap, int *d_n_elems, int *d_max_col, hipStream_t st) {
+    if (cap < 1 || cap > 16384) return uspmv::fail(USPMV_ERR_INVALID, "element plan: cap %d outside 1 .. 16384", cap);   // 2^15 slots: 128 of the CU's 160 KiB
+    const int log2n = elem_set_log2(cap);
+    const size_t lds = (size_t)4 << log2n;
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)plan_count_elems, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(plan_count_elems, dim3((unsigned)n_tiles), dim3(256), lds, st, (long)A->n_chunks, (int)A->C, A->chunk_ptrs, A->chunk_lengths,
+                       A->col_idxs, cap, log2n, d_n_elems, d_max_col);
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
+// most_listed: the longest list of tile_line_ptr (the set is sized by it, not by the cap: a shorter sort)
+int launch_plan_write_elems(const uspmv_dmat *A, long n_tiles, int most_listed, const int *d_tile_line_ptr, const unsigned *d_c16_ptrs,
+                            int *d_tile_lines, unsigned short *d_col16, hipStream_t st) {
+    if (most_listed < 1 || most_listed > 16384) return uspmv::fail(USPMV_ERR_INVALID, "element plan: %d elements per tile outside 1 .. 16384", most_listed);
+    const int log2n = elem_set_log2(most_listed);
+    const size_t lds = (size_t)4 << log2n;
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)plan_write_elems, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(plan_write_elems, dim3((unsigned)n_tiles), dim3(256), lds, st, (long)A->n_chunks, (int)A->C, A->chunk_ptrs, A->chunk_lengths,
+                       A->col_idxs, d_tile_line_ptr, d_c16_ptrs, d_tile_lines, d_col16, log2n);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }

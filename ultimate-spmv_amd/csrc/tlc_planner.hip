@@ -1,7 +1,8 @@
 // The SpMV planner: uspmv_dmat_optimize and its variants (one struct, the ap[dp_sp] pair, the splits with an fp16 part; from a host
 // struct through host/tlc_plan.cpp or from the handle's device arrays through plan_kernels.hip).  Every decision between the plans
 // -- the line budget, the rows per tile, when the element plan or the column-window sweep takes over -- is written once here, so the host
-// and the device planner of one matrix cannot drift apart (tests/test_gpu_parity.py compares their plans array for array).
+// and the device planner of one matrix cannot drift apart (tests/test_gpu_parity.py and tests/test_gpu_elem_plan_device.py compare their
+// plans array for array).  Host-only is the element plan on rows dealt to the tiles by the matrix graph.
 #include "uspmv_device.hpp"
 
 #include <mutex>
@@ -312,22 +313,136 @@ int measured_tile_rows(uspmv_dmat *A, uspmv_dmat *B, int max_lines, const char *
 
 // A quick look before an element plan is built in full (a sort per tile over all entries): of ~64 tiles spread over the struct, how many list more distinct
 // columns than `cap`?  More than a tenth of them: the element plan would be turned down anyway (wide irregular rows: the sweep's matrices).
+// The sampled tiles are t = step/2, step/2 + step, ... with step = max(1, n_tiles / 64); over(t): tile t lists more than the cap.  The host
+// planner sorts those tiles' columns, the device planner reads its count pass's array at the same indices.
+template <typename Over>
+double sampled_over_cap_frac(int64_t nt, Over over) {
+    const int64_t step = std::max<int64_t>(1, nt / 64);
+    int64_t seen = 0, n_over = 0;
+    for (int64_t t = step / 2; t < nt; t += step) { ++seen; n_over += over(t) ? 1 : 0; }
+    return seen > 0 ? (double)n_over / (double)seen : 1.0;
+}
 double elements_over_cap_frac(const uspmv_scs *s, int cap, int tile_rows) {
     const int64_t C = s->C, T = std::max<int64_t>(1, tile_rows / C), nt = (s->n_chunks + T - 1) / T;
-    const int64_t step = std::max<int64_t>(1, nt / 64);
-    int64_t seen = 0, over = 0;
     std::vector<int32_t> cols;
-    for (int64_t t = step / 2; t < nt; t += step) {
+    return sampled_over_cap_frac(nt, [&](int64_t t) {
         const int64_t c0 = t * T, c1 = std::min<int64_t>(c0 + T, s->n_chunks);
         cols.assign(s->col_idxs.begin() + s->chunk_ptrs[(size_t)c0], s->col_idxs.begin() + s->chunk_ptrs[(size_t)c1]);
         std::sort(cols.begin(), cols.end());
-        const int64_t n = (int64_t)(std::unique(cols.begin(), cols.end()) - cols.begin());
-        ++seen; over += n > cap;
-    }
-    return seen > 0 ? (double)over / (double)seen : 1.0;
+        return (int64_t)(std::unique(cols.begin(), cols.end()) - cols.begin()) > cap;
+    });
 }
 
-// the device planner of one struct or an ap[dp_sp] pair: the plan at the rows per tile uspmv_dmat_optimize[_ap] chooses, then its sweep rule
+// The element plans: most elements a tile may list (64 KiB of the value type at most), "an element serves four entries or more on
+// average", and when they are tried at all: the caller gave no line budget of its own and the line plan is invalid or leaves a tenth
+// of the tiles or more to the gather path.
+int element_cap(int dtype) { return std::min(g_tune.tlc_elem_cap, (int)(64 * 1024 / (dtype == USPMV_F64 ? 8 : 4))); }
+bool elements_pay(int64_t listed, int64_t n_elements) { return (double)listed * 4.0 <= (double)n_elements; }
+bool line_plan_short(bool own_budget, const PlanStats &line) { return !own_budget && (!line.valid || !stages_nine_tenths(line.n_tiles, line.n_staged)); }
+
+// what an element plan candidate turned out to be
+struct ElemStats {
+    bool valid = false;
+    int64_t n_tiles = 0, n_staged = 0, listed = 0;     // listed: elements of all lists together
+    int most = 0;                                      // of the fullest tile
+};
+
+// The fallback from the line plan to the plan over single x elements on the caller's row order, for the host and the device planner alike.
+// Columns scattered over many lines (x in a numbering that is only loosely related to the rows'): the line plan leaves a tenth of the tiles
+// or more to the gather path.  List the tile's distinct ELEMENTS instead -- taken when (nearly) every tile fits and an element serves
+// four entries or more on average (else the line plan stays, or the column-window sweep takes over).  Measured (tools/numbering_probe.py,
+// profiles/r04/numbering_probe_*.txt): 27-point x 3 dof stencil with x renumbered at random inside blocks of 1 000 / 5 000 / 20 000 nodes
+// 0.97 / 0.90 / 0.89 of the roofline against 0.74 (line plan, 69 % of the tiles staged) / 0.70 / 0.61 (sweep); 1 dof, 4.2 entries per
+// element: 0.65 against 0.59; on a regular numbering the line plan is 20 % ahead (0.683 against 0.819 ms on the 253^3 stencil), which is
+// why this is a fallback only ("tlc_elem" 2, a measurement aid, always tries).
+// sample(cap, &frac): the share of the sampled tiles over the cap; build(cap, &stats): the candidate, in full (a sort per tile) -- the
+// caller keeps it when *took, and the call then reports the element plan's tiles.
+template <typename Sample, typename Build>
+int elements_take_over(bool own_budget, const PlanStats &line, bool allowed, int dtype, int64_t n_elements, Sample sample, Build build, bool *took,
+                       int64_t *n_tiles, int64_t *n_staged) {
+    *took = false;
+    if (!(line_plan_short(own_budget, line) || g_tune.tlc_elem == 2) || !g_tune.tlc_elem || !allowed) return USPMV_OK;
+    const int ecap = element_cap(dtype);
+    double over = 1.0;
+    if (int rc = sample(ecap, &over)) return rc;
+    if (over > 0.1) return USPMV_OK;                   // would be turned down anyway (wide irregular rows: the sweep's matrices)
+    ElemStats e;
+    if (int rc = build(ecap, &e)) return rc;
+    if (!e.valid || !tile_rows_accept(e.n_tiles, e.n_staged) || !(elements_pay(e.listed, n_elements) || g_tune.tlc_elem == 2)) return USPMV_OK;
+    *took = true;
+    if (n_tiles) *n_tiles = e.n_tiles;
+    if (n_staged) *n_staged = e.n_staged;
+    if (verbose()) fprintf(stderr, "[uspmv] tlc plan over single x elements: tiles=%lld staged=%lld max_elements=%d elements_total=%lld (%.1f entries per element)\n",
+                           (long long)e.n_tiles, (long long)e.n_staged, e.most, (long long)e.listed, (double)n_elements / (double)std::max<int64_t>(e.listed, 1));
+    return USPMV_OK;
+}
+
+// The element plan's count pass on the device (plan_kernels.hip): per 256-row tile the distinct columns clipped at cap + 1, and the
+// struct's largest column.  O(n_tiles) comes back to the host.  Shapes without a plan: no tiles.
+struct ElemCounts {
+    int cap = 0, max_col = 0;
+    std::vector<int32_t> n;
+};
+int device_elem_count(const uspmv_dmat *A, int cap, ElemCounts *o, const char *who) {
+    *o = {};
+    o->cap = cap;
+    const int64_t C = A->C, nc = A->n_chunks;
+    if (C > 256 || 256 % C != 0 || nc < 1) return USPMV_OK;
+    const int64_t T = 256 / C, nt = (nc + T - 1) / T;
+    DeviceBuf<int> d_n, d_max;
+    hipError_t e = d_n.alloc(4 * (size_t)nt);
+    if (e == hipSuccess) e = d_max.zeros(4);
+    if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
+    if (int rc = launch_plan_count_elems(A, (long)nt, cap, d_n, d_max, nullptr)) return rc;
+    o->n.resize((size_t)nt);
+    e = hipMemcpy(o->n.data(), d_n, 4 * (size_t)nt, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&o->max_col, d_max, 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { o->n.clear(); return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
+    return USPMV_OK;
+}
+
+// ... and its write pass, installed on the (plan-less) handle as device_plan_install_rows installs the line plan: owned buffers, O(n_chunks)
+// + O(n_tiles) on the host.  No plan (and USPMV_OK) for arrays beyond 32-bit offsets and when no tile stages; on a failure the handle has none either.
+int device_elem_install(uspmv_dmat *A, const ElemCounts &cnt, ElemStats *st, const char *who) {
+    A->tlc = {};
+    *st = {};
+    const int64_t C = A->C, nc = A->n_chunks, nt = (int64_t)cnt.n.size();
+    if (nt == 0) return USPMV_OK;
+    std::vector<int32_t> lp((size_t)nt + 1, 0);
+    int64_t staged = 0, total = 0;
+    int used = 0;
+    for (int64_t t = 0; t < nt; ++t) {
+        const int n = cnt.n[(size_t)t] <= cnt.cap ? cnt.n[(size_t)t] : 0;     // over the cap: the tile gathers
+        staged += n > 0; used = std::max(used, n);
+        total += n;
+        if (total > INT32_MAX) return USPMV_OK;
+        lp[(size_t)t + 1] = (int32_t)total;
+    }
+    st->n_tiles = nt; st->n_staged = staged;
+    if (staged == 0) return USPMV_OK;
+    std::vector<int32_t> cl((size_t)nc);
+    std::vector<uint32_t> c16p;
+    int64_t tot16 = 0;
+    HIP_TRY(hipMemcpy(cl.data(), A->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
+    if (!c16_offsets(cl, C, &c16p, &tot16)) return USPMV_OK;
+    hipError_t e = A->tlc.line_ptr.upload(lp.data(), 4 * ((size_t)nt + 1));
+    if (e == hipSuccess) e = A->tlc.lines.alloc(4 * (size_t)std::max<int64_t>(total, 1));
+    if (e == hipSuccess) e = A->tlc.c16_ptrs.upload(c16p.data(), 4 * ((size_t)nc + 1));
+    if (e == hipSuccess) e = A->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16, 1));
+    if (e == hipSuccess && launch_plan_write_elems(A, (long)nt, used, A->tlc.line_ptr, A->tlc.c16_ptrs, A->tlc.lines, A->tlc.col16, nullptr) != USPMV_OK) e = hipErrorUnknown;
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        A->tlc = {};
+        return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    uspmv_dmat *const parts[3] = {A, nullptr, nullptr};
+    stamp_plan(parts, 256, used, (int64_t)cnt.max_col + 1, nt, staged, /*elem=*/true);
+    *st = {true, nt, staged, total, used};
+    return USPMV_OK;
+}
+
+// the device planner of one struct or an ap[dp_sp] pair: the plan at the rows per tile uspmv_dmat_optimize[_ap] chooses, then -- one
+// struct only -- its fallback to the plan over single x elements, then its sweep rule
 int device_plan_install(uspmv_dmat *A, uspmv_dmat *B, int max_lines, int64_t *n_tiles, int64_t *n_staged, const char *who) {
     uspmv_dmat *const parts[3] = {A, B, nullptr};
     const int R_meas = measured_tile_rows(A, B, line_budget(max_lines, A->dtype, B != nullptr), who);
@@ -338,8 +453,25 @@ int device_plan_install(uspmv_dmat *A, uspmv_dmat *B, int max_lines, int64_t *n_
     if (n_tiles) *n_tiles = st.n_tiles;
     if (n_staged) *n_staged = st.n_staged;
     if (rc) return rc;
-    A->tlc = std::move(kept[0]);
-    if (B) B->tlc = std::move(kept[1]);
+    if (!B) {
+        // (the line plan waits in kept[0]: the handle gets it back unless the element plan is taken, also when the attempt fails)
+        ElemCounts cnt;
+        bool elem = false;
+        int rc2 = elements_take_over(max_lines > 0, st, true, A->dtype, A->n_elements,
+                                     [&](int cap, double *over) {
+                                         const int r = device_elem_count(A, cap, &cnt, who);
+                                         *over = sampled_over_cap_frac((int64_t)cnt.n.size(), [&](int64_t t) { return cnt.n[(size_t)t] > cap; });
+                                         return r;
+                                     },
+                                     [&](int, ElemStats *o) { return device_elem_install(A, cnt, o, who); }, &elem, n_tiles, n_staged);
+        if (!rc2 && elem) rc2 = tlc_pack12(A, nullptr, who);
+        if (rc2 || !elem) A->tlc = std::move(kept[0]);
+        if (rc2) return rc2;
+        if (elem) { A->sw = {}; return USPMV_OK; }
+    } else {
+        A->tlc = std::move(kept[0]);
+        B->tlc = std::move(kept[1]);
+    }
     bool swept = false;
     if (int rc2 = sweep_takes_over(A, B, nullptr, nullptr, st, who, &swept)) return rc2;
     if (swept) {             // (n_tiles / n_staged keep describing the tile-local-column attempt, as in uspmv_dmat_optimize;
@@ -421,28 +553,20 @@ int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPla
     if (verbose()) fprintf(stderr, "[uspmv] tlc plan: tile_rows=%d tiles=%lld staged=%lld max_lines=%d lines_total=%zu col16=%zu\n",
                            p.tile_rows, (long long)p.n_tiles, (long long)p.n_staged_tiles, p.max_lines_used, p.tile_lines.size(), p.col16.size());
     A->sw = {};
-    // the element plans below: most elements a tile may list, and "an element serves four entries or more on average"
-    const int ecap = std::min(g_tune.tlc_elem_cap, (int)(64 * 1024 / (s->dtype == USPMV_F64 ? 8 : 4)));
-    auto elements_pay = [&](const uspmv_tlc_plan &e) { return (double)e.tile_lines.size() * 4.0 <= (double)s->n_elements; };
-    const bool line_plan_short = !own_budget && (!p.valid || !stages_nine_tenths(p.n_tiles, p.n_staged_tiles));
+    // the element plan on the caller's row order (elements_take_over: the policy the device planner shares)
+    const PlanStats line = stats_of(p);
+    const int ecap = element_cap(s->dtype);
     bool elem = false;
-    if ((line_plan_short || g_tune.tlc_elem == 2) && g_tune.tlc_elem && opts.elements) {   // (2: measurement aid, always try)
-        // columns scattered over many lines (x in a numbering that is only loosely related to the rows'): the line plan leaves a tenth of the tiles or
-        // more to the gather path.  List the tile's distinct ELEMENTS instead -- taken when (nearly) every tile fits and an element serves four
-        // entries or more on average (else the line plan stays, or the column-window sweep takes over below).  Measured (tools/numbering_probe.py,
-        // profiles/r04/numbering_probe_*.txt): 27-point x 3 dof stencil with x renumbered at random inside blocks of 1 000 / 5 000 / 20 000 nodes 0.97 / 0.90 /
-        // 0.89 of the roofline against 0.74 (line plan, 69 % of the tiles staged) / 0.70 / 0.61 (sweep); 1 dof, 4.2 entries per element: 0.65 against 0.59;
-        // on a regular numbering the line plan is 20 % ahead (0.683 against 0.819 ms on the 253^3 stencil), which is why this is a fallback only.
-        q = {};
-        if (elements_over_cap_frac(s, ecap, 256) <= 0.1)
-            if (int rc = uspmv_build_tlc_plan(s, nullptr, ecap, 256, &q, /*line_shift=*/0)) return rc;
-        if (q.valid && tile_rows_accept(q.n_tiles, q.n_staged_tiles) && (elements_pay(q) || g_tune.tlc_elem == 2)) {
-            p = std::move(q); elem = true;
-            report();
-            if (verbose()) fprintf(stderr, "[uspmv] tlc plan over single x elements: tiles=%lld staged=%lld max_elements=%d elements_total=%zu (%.1f entries per element)\n",
-                                   (long long)p.n_tiles, (long long)p.n_staged_tiles, p.max_lines_used, p.tile_lines.size(), (double)s->n_elements / (double)std::max<size_t>(p.tile_lines.size(), 1));
-        }
-    }
+    if (int rc = elements_take_over(own_budget, line, opts.elements, s->dtype, s->n_elements,
+                                    [&](int cap, double *over) { *over = elements_over_cap_frac(s, cap, 256); return USPMV_OK; },
+                                    [&](int cap, ElemStats *o) {
+                                        q = {};
+                                        const int rc2 = uspmv_build_tlc_plan(s, nullptr, cap, 256, &q, /*line_shift=*/0);
+                                        *o = {q.valid, q.n_tiles, q.n_staged_tiles, (int64_t)q.tile_lines.size(), q.max_lines_used};
+                                        return rc2;
+                                    }, &elem, n_tiles, n_staged))
+        return rc;
+    if (elem) p = std::move(q);
     // ... and when the ROWS of a tile are scattered as well (rows and columns renumbered alike: a tile of 256 consecutive rows is no compact piece of the
     // mesh any more): deal the rows to the tiles by the matrix graph first, as the block plan does (uspmv_scs_reorder_rows mode 4: rows change places
     // only with rows of equal-length chunks, every row keeps its slot sequence), then the element plan on that order -- a private copy of the values
@@ -450,7 +574,7 @@ int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPla
     uspmv_scs rr;
     std::vector<int32_t> rr_map;
     bool reordered = false;
-    if (!elem && line_plan_short && g_tune.tlc_elem && g_tune.tlc_elem_rows && opts.deal_rows && s->n_rows == s->n_cols) {
+    if (!elem && line_plan_short(own_budget, line) && g_tune.tlc_elem && g_tune.tlc_elem_rows && opts.deal_rows && s->n_rows == s->n_cols) {
         // first with the clusters confined to segments of tlc_elem_seg_rows rows (64 Ki: many segments in parallel, and a trial on a sample of them that stops
         // irregular matrices early); when that leaves some, but not most, of the sampled tiles over the cap -- related rows further apart than a segment --
         // once more with segments of 2^20 rows (a second or more of clustering per million rows on few threads: only where it looks promising)
@@ -465,7 +589,7 @@ int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPla
             if (verbose()) fprintf(stderr, "[uspmv] element plan on the graph-dealt rows (segments of %lld rows): %.0f %% of the sampled tiles over the cap; valid=%d tiles=%lld staged=%lld max_elements=%d (cap %d) elements_total=%zu\n",
                                    (long long)seg_stage[stage], 100.0 * over, (int)q.valid, (long long)q.n_tiles, (long long)q.n_staged_tiles, q.max_lines_used, ecap, q.tile_lines.size());
             // (19 of 20 tiles staged is enough here: what would run instead -- sweep or gather kernel -- is 2 x slower on such matrices)
-            if (q.valid && stages_19_of_20(q.n_tiles, q.n_staged_tiles) && elements_pay(q)) {
+            if (q.valid && stages_19_of_20(q.n_tiles, q.n_staged_tiles) && elements_pay((int64_t)q.tile_lines.size(), s->n_elements)) {
                 p = std::move(q); elem = true; reordered = true;
                 report();
                 if (verbose()) fprintf(stderr, "[uspmv] tlc plan over single x elements, rows dealt to the tiles by the matrix graph: tiles=%lld max_elements=%d elements_total=%zu (%.1f entries per element)\n",

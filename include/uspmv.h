@@ -340,6 +340,21 @@ int uspmv_spmmv_x_release(const uspmv_dmat_t *m);
  * kernel scs_ap_impl_cpu (code/ap_kernels.hpp:24-82): both parts accumulated in double from the
  * double x, y = dp_sum + sp_sum.  dp and sp must share C and n_chunks. */
 int uspmv_spmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const double *d_x, double *d_y, void *stream);
+/* Adaptive precision dp+sp on block vectors: Y = (A_dp + A_sp) X, b right-hand sides, X and Y double.  The reference has no such path
+ * (its CLI stops at "SpMMV is not yet implemented for AP kernels", code/utilities.hpp:1389).  For every C, column v of Y is bitwise what
+ * uspmv_spmv_ap gives for column v of X: per (row, v) the dp FMA chain and the sp FMA chain of scs_ap_impl_cpu, each in slot order,
+ * Y(r, v) = dp + sp.  Layouts and ld as uspmv_spmmv; all n_rows_padded rows of every vector are written and nothing else of Y.
+ * b = 1 is uspmv_spmv_ap.  uspmv_spmmv_x_prepared(dp, ...) / uspmv_spmmv_x_release(dp) are honoured for column-major X as by uspmv_spmmv:
+ * the re-layout workspace of the pair lives on the dp handle.  b in {2, 4, 8, 16} with 16-byte-aligned X and Y: a pair that carries one
+ * shared tile-local-column plan (uspmv_dmat_optimize_ap / _device_ap) of at most uspmv_spmmv_ap_plan_lines(b) lines per tile runs the
+ * kernel that stages the tile's X rows in LDS and streams 10 + 6 bytes per non-zero and pass over the vectors; without such a plan (none,
+ * a column-window sweep plan, tuning "tlc" 0) the gather kernel runs on the original arrays.  Any other b or alignment: the generic kernel. */
+int uspmv_spmmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const void *d_X, void *d_Y, int b, int64_t ld, int layout,
+                   void *stream);
+/* The largest max_lines a caller can pass to uspmv_dmat_optimize_ap / _device_ap for which the staged kernel of uspmv_spmmv_ap applies
+ * to width b whatever the matrix: 640 for b in {2, 4, 8, 16} (two vectors of 640 lines x 16 X rows fill the 160 KiB of LDS a workgroup
+ * can have; fewer lines leave room for 4 or 8 vectors per pass), 0 where no staged kernel exists for that b. */
+int uspmv_spmmv_ap_plan_lines(int b, int *max_lines);
 /* Generic-C variant of the reference, spmv_omp_scs_ap / spmv_gpu_ap_scs (code/ap_kernels.hpp:562-634,
  * :721-816; selected for C outside {2,4,...,128}, code/classes_structs.hpp:630-636): the sp part
  * multiplies with the FLOAT copy of x (d_x_sp), the float product being rounded before it is added
@@ -659,7 +674,7 @@ int uspmv_stream_read(const double *d_b, int64_t n, double *d_partial, void *str
 int uspmv_stream_gather_lines(const double *d_x, int64_t n, int64_t plane, int64_t line, int rows, double *d_partial, void *stream, int64_t *bytes);
 /* Time `reps` back-to-back launches of one entry point with HIP events on `stream`;
  * what: 0 spmv(A,x,y) 1 stream_copy 2 stream_triad 3 stream_read 4 spmv_ap(A,B,x,y)
- *       5 spmmv(A,X,Y,b,ld,layout) 6 stream_gather_lines(x, n, plane = ld, line = b, rows = layout).  Two untimed launches precede the timed ones; returns the average milliseconds per launch.
+ *       5 spmmv(A,X,Y,b,ld,layout) 6 stream_gather_lines(x, n, plane = ld, line = b, rows = layout) 7 spmmv_ap(A,B,X,Y,b,ld,layout).  Two untimed launches precede the timed ones; returns the average milliseconds per launch.
  * For the STREAM kinds d_x is the source (n doubles; 2n for the triad: b = d_x, c = d_x + n) and d_y
  * the destination (n doubles; 8192 for the read kernel's partial sums). */
 int uspmv_time_launches(int what, int reps, const uspmv_dmat_t *A, const uspmv_dmat_t *B, const void *d_x,

@@ -233,4 +233,10 @@ private:
     ST n_rows_padded_ = 0;
 };
 
+// adaptive precision dp+sp on a block of b vectors (uspmv_spmmv_ap): dp holds the double part, sp the float part of one split, both in
+// one row layout; X and Y double.  dp.x_prepared / dp.x_released serve a column-major X that does not change between calls.
+inline void spmmv_ap(const DeviceScs &dp, const DeviceScs &sp, const void *d_X, void *d_Y, int b, ST ld, bool rowwise, void *stream = nullptr) {
+    uspmv_detail::check(uspmv_spmmv_ap(dp.handle(), sp.handle(), d_X, d_Y, b, ld, rowwise ? USPMV_ROWWISE : USPMV_COLWISE, stream), "uspmv_spmmv_ap");
+}
+
 #endif  // USPMV_INTERFACE_HPP

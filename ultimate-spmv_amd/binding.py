@@ -113,6 +113,8 @@ _SIGS = {
     "uspmv_dmat_optimize_sweep_device_ap_hp": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_spmmv": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
     "uspmv_spmv_ap": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "uspmv_spmmv_ap": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
+    "uspmv_spmmv_ap_plan_lines": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "uspmv_spmv_ap_generic": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "uspmv_scs_gpu_f64": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "uspmv_scs_gpu_f32": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1173,6 +1175,22 @@ def spmv_ap(A_dp, A_sp, x, y, stream=None, x_sp=None):
     else:
         _ck(lib().uspmv_spmv_ap_generic(A_dp.h, A_sp.h, _dp(x), _dp(x_sp), _dp(y), _stream_ptr(stream)))
     return y
+
+
+def spmmv_ap(A_dp, A_sp, X, Y, b, ld, layout=COLWISE, stream=None):
+    """Adaptive precision dp+sp on a block of b vectors (uspmv_spmmv_ap): X, Y float64, layouts and ld as spmmv; column v of Y is
+    bitwise spmv_ap of column v of X.  spmmv_x_prepared(A_dp, X, b, ld) / spmmv_x_release(A_dp) work as for spmmv."""
+    assert X.dtype == _torch_dtype(F64) and Y.dtype == _torch_dtype(F64)      # (the order of the handles is the library's to check)
+    _ck(lib().uspmv_spmmv_ap(A_dp.h, A_sp.h, _dp(X), _dp(Y), b, ld, layout, _stream_ptr(stream)))
+    return Y
+
+
+def spmmv_ap_plan_lines(b):
+    """Largest max_lines for optimize_ap / optimize_device_ap at which the staged kernel serves spmmv_ap of width b (640 for b in
+    {2, 4, 8, 16}); 0: no staged kernel for that b."""
+    n = C.c_int()
+    _ck(lib().uspmv_spmmv_ap_plan_lines(int(b), C.byref(n)))
+    return n.value
 
 
 def spmv_ap_hp(A_hi, A_mid, A_hp, x, y, stream=None):

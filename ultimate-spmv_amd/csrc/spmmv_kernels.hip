@@ -919,6 +919,18 @@ int prepare_x(const uspmv_dmat *A, const VT *X, int b, long ld, hipStream_t st) 
     if (rc == USPMV_OK) { A->xprep_ptr = X; A->xprep_b = b; A->xprep_ld = ld; A->xprep_form = form; }
     return rc;
 }
+// the plain re-layout (form 1) of a column-major double X of width b in {2, 4, 8, 16} into A's workspace: what the ap pair's launcher
+// (ap_spmmv_kernels.hip) runs per call; the caller keeps A->xprep_* in order
+int relayout_x_plain(const uspmv_dmat *A, const double *X, int b, long ld, hipStream_t st) {
+    int form = 0;
+    switch (b) {
+        case 2: return relayout_x<double, 2>(A, X, ld, st, &form, true);
+        case 4: return relayout_x<double, 4>(A, X, ld, st, &form, true);
+        case 8: return relayout_x<double, 8>(A, X, ld, st, &form, true);
+        case 16: return relayout_x<double, 16>(A, X, ld, st, &form, true);
+        default: return uspmv::fail(USPMV_ERR_INVALID, "relayout_x_plain: no re-layout pass for b=%d", b);
+    }
+}
 template int prepare_x<double>(const uspmv_dmat *, const double *, int, long, hipStream_t);
 template int prepare_x<float>(const uspmv_dmat *, const float *, int, long, hipStream_t);
 

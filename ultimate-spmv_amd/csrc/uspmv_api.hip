@@ -1356,6 +1356,31 @@ int uspmv_spmv_ap_generic(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const 
     return spmv_ap_impl(dp, sp, d_x, d_x_sp, d_y, stream, "uspmv_spmv_ap_generic");
 }
 
+int uspmv_spmmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const void *d_X, void *d_Y, int b, int64_t ld, int layout, void *stream) {
+    const char *who = "uspmv_spmmv_ap";
+    if (int rc = check_dmat(dp, who)) return rc;
+    if (int rc = check_dmat(sp, who)) return rc;
+    if (dp->dtype != USPMV_F64 || sp->dtype != USPMV_F32)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: expects a double and a float struct", who);
+    if (dp->C != sp->C || dp->n_chunks != sp->n_chunks)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: dp and sp structs must share C and n_chunks", who);
+    if (!d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL vector", who);
+    if (b < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: b=%d", who, b);
+    if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown layout %d", who, layout);
+    if (layout == USPMV_COLWISE && ld < dp->n_chunks * dp->C)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: ld=%lld smaller than n_rows_padded=%lld", who, (long long)ld,
+                           (long long)(dp->n_chunks * dp->C));
+    if (int rc = require_device()) return rc;
+    if (dp->n_chunks == 0) return USPMV_OK;
+    return launch_spmmv_ap(dp, sp, (const double *)d_X, (double *)d_Y, b, (long)ld, layout, (hipStream_t)stream);
+}
+
+int uspmv_spmmv_ap_plan_lines(int b, int *max_lines) {
+    if (b < 1 || !max_lines) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv_ap_plan_lines: bad argument");
+    *max_lines = spmmv_ap_plan_lines(b);
+    return USPMV_OK;
+}
+
 // Opt-in plan cache of the raw-array entry points (tuning key "raw_plan_cache"): the reference's function-pointer
 // seam passes the same device arrays on every call (code/classes_structs.hpp:997-1034), so the first call wraps them,
 // builds the tile-local-column plan on the device and later calls run the plan kernel.  Keyed on the array
@@ -1521,6 +1546,7 @@ int uspmv_time_launches(int what, int reps, const uspmv_dmat_t *A, const uspmv_d
             case 4: rc = uspmv_spmv_ap(A, B, (const double *)d_x, (double *)d_y, stream); break;
             case 5: rc = uspmv_spmmv(A, d_x, d_y, b, ld, layout, stream); break;
             case 6: rc = uspmv_stream_gather_lines((const double *)d_x, n, ld, (int64_t)b, layout, (double *)d_y, stream, nullptr); break;
+            case 7: rc = uspmv_spmmv_ap(A, B, d_x, d_y, b, ld, layout, stream); break;
             default: rc = uspmv::fail(USPMV_ERR_INVALID, "uspmv_time_launches: unknown kind %d", what);
         }
     }

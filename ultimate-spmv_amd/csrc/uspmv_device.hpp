@@ -1,6 +1,6 @@
 // Shared declarations of the device half of libuspmv: the matrix handle, the tuning knobs, the
 // device helpers every kernel file uses and the launch entry points the C ABI (uspmv_api.hip) calls.
-// Kernels live in spmv_kernels.hip, spmmv_kernels.hip and ap_kernels.hip.
+// Kernels live in spmv_kernels.hip, spmmv_kernels.hip, ap_kernels.hip and ap_spmmv_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -391,6 +391,7 @@ template <typename VT>
 int launch_spmmv_sweep(const uspmv_dmat *A, const VT *X, VT *Y, int b, long ld, bool xcol, bool ycol, hipStream_t st);   // spmmv_sweep.hip; false-y: USPMV_OK when launched, > 0 when the plan does not apply
 template <typename VT>
 int prepare_x(const uspmv_dmat *A, const VT *X, int b, long ld, hipStream_t st);                                    // spmmv_kernels.hip
+int relayout_x_plain(const uspmv_dmat *A, const double *X, int b, long ld, hipStream_t st);                       // spmmv_kernels.hip
 // phased block plan, 64-byte X rows (spmmv_phased.hip); false: no plan / schedule on the handle or it does not fit the compiled shapes
 // xmode: 0 = row-major X, 1 = column-major X assembled through registers, 2 = column-major X staged by 128-byte lines (line plan)
 bool spmmv_phased(const uspmv_dmat *A, const double *X, double *Y, long ld, bool ycol, int xmode, hipStream_t st);
@@ -401,6 +402,11 @@ bool spmmv_stream(const uspmv_dmat *A, const float *X, float *Y, long ld, bool y
 int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu);
 int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x, const float *d_x_sp, double *d_y,
                    hipStream_t stream);                                                                           // ap_kernels.hip
+// ap[dp_sp] on block vectors: b = 1 forwards to launch_spmv_ap; B in {2, 4, 8, 16} the row-major kernel (column-major X through the dp
+// handle's workspace), else lane per row with VB vectors per pass
+int launch_spmmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, int layout,
+                    hipStream_t st);                                                                              // ap_spmmv_kernels.hip
+int spmmv_ap_plan_lines(int b);   // most lines per tile of a shared plan the staged block kernel takes at width b (0: no such kernel)
 // ap with an fp16 part (hi F64 | F32, mid F32 or nullptr, hp F16): the shared tile-local-column plan when all parts carry it, else lane per row
 int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *d_x, void *d_y, hipStream_t stream);   // ap_kernels.hip
 template <typename VT>

@@ -345,16 +345,38 @@ int uspmv_spmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const double *
  * uspmv_spmv_ap gives for column v of X: per (row, v) the dp FMA chain and the sp FMA chain of scs_ap_impl_cpu, each in slot order,
  * Y(r, v) = dp + sp.  Layouts and ld as uspmv_spmmv; all n_rows_padded rows of every vector are written and nothing else of Y.
  * b = 1 is uspmv_spmv_ap.  uspmv_spmmv_x_prepared(dp, ...) / uspmv_spmmv_x_release(dp) are honoured for column-major X as by uspmv_spmmv:
- * the re-layout workspace of the pair lives on the dp handle.  b in {2, 4, 8, 16} with 16-byte-aligned X and Y: a pair that carries one
- * shared tile-local-column plan (uspmv_dmat_optimize_ap / _device_ap) of at most uspmv_spmmv_ap_plan_lines(b) lines per tile runs the
- * kernel that stages the tile's X rows in LDS and streams 10 + 6 bytes per non-zero and pass over the vectors; without such a plan (none,
- * a column-window sweep plan, tuning "tlc" 0) the gather kernel runs on the original arrays.  Any other b or alignment: the generic kernel. */
+ * the re-layout workspace of the pair lives on the dp handle.  b in {2, 4, 8, 16} with 16-byte-aligned X and Y (and an even ld for
+ * column-major vectors): a pair that carries the column-window sweep plan (uspmv_dmat_optimize_ap / _device_ap on wide irregular rows,
+ * uspmv_dmat_optimize_sweep_ap / _device) whose windows leave room for two vectors in LDS (uspmv_spmmv_ap_sweep_vectors(b, wlog) >= 2:
+ * wlog <= 13) runs the block form of the sweep kernel, except for row-major X in more than two passes: the plan's compacted dp and sp
+ * streams are walked once per uspmv_spmmv_ap_sweep_vectors(b, wlog) vectors, the windows of X staged in LDS straight from either layout (no workspace is used or
+ * grown, and uspmv_spmmv_x_prepared has nothing to skip there); tiles that do not sweep run lane per row.  A pair that carries one shared
+ * tile-local-column plan (uspmv_dmat_optimize_ap / _device_ap) of at most uspmv_spmmv_ap_plan_lines(b) lines per tile runs the kernel
+ * that stages the tile's X rows in LDS and streams 10 + 6 bytes per non-zero and pass over the vectors; without a plan (none, or tuning
+ * "sweep" / "tlc" 0) the gather kernel runs on the original arrays.  Any other b or alignment: the generic kernel.
+ * uspmv_spmmv_ap_path reports which of these a call would take. */
 int uspmv_spmmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const void *d_X, void *d_Y, int b, int64_t ld, int layout,
                    void *stream);
 /* The largest max_lines a caller can pass to uspmv_dmat_optimize_ap / _device_ap for which the staged kernel of uspmv_spmmv_ap applies
  * to width b whatever the matrix: 640 for b in {2, 4, 8, 16} (two vectors of 640 lines x 16 X rows fill the 160 KiB of LDS a workgroup
  * can have; fewer lines leave room for 4 or 8 vectors per pass), 0 where no staged kernel exists for that b. */
 int uspmv_spmmv_ap_plan_lines(int b, int *max_lines);
+/* What uspmv_spmmv_ap(dp, sp, X, Y, b, ld, layout) would run for 16-byte-aligned X and Y, under the current tuning.  *path: 0 the generic
+ * lane-per-row kernel, 1 the gather kernel on the original arrays, 2 the staged kernel over the shared tile-local-column plan, 3 the
+ * column-window sweep kernel.  *vectors_per_pass: the vectors the sweep kernel (path 3) or the staged kernel (path 2) serves per pass over
+ * the matrix entries, else 0.  b = 1 reports uspmv_spmv_ap's choice: 3 its sweep kernel, 2 its staged kernel (one vector per pass), 0
+ * lane per row.  Same argument checks and error texts as uspmv_spmmv_ap (under this function's name); nothing is launched. */
+int uspmv_spmmv_ap_path(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, int b, int64_t ld, int layout, int *path, int *vectors_per_pass);
+/* The vectors per pass the sweep kernel of uspmv_spmmv_ap takes at width b on a plan whose windows hold 2^wlog doubles: the largest of
+ * {8, 4, 2} that is at most b, divides b and fits 160 KiB of LDS with one window (2^wlog * 8 bytes per vector); 0 where the kernel does not
+ * apply (b not in {2, 4, 8, 16}, or wlog >= 14: two vectors of a window do not fit).  A pure function: callers use it to choose wlog for
+ * uspmv_dmat_optimize_sweep_ap / _device when they want all b vectors in one pass (wlog 13 serves 2, 12 serves 4, 11 serves 8).
+ * Narrower windows win from b = 4 on (banded-random 500 k x 140 pair: b = 4 0.347 ms at wlog 12 against 0.450 at 13; b = 8 0.704-0.777 at
+ * wlog 11 against 0.878-1.170 at 13), the opposite of uspmv_spmv_ap, whose best window is the planner's default: 2^14 doubles under
+ * "sweep_nbuf" 1 (no block kernel there), 2^13 under "sweep_nbuf" 2.  Row-major X in more than two passes (b / vectors > 2) keeps the
+ * gather kernel whatever this function says: uspmv_spmmv_ap_path reports it.
+ * b < 1, wlog outside 8..16 or a NULL pointer is refused. */
+int uspmv_spmmv_ap_sweep_vectors(int b, int wlog, int *vectors);
 /* Generic-C variant of the reference, spmv_omp_scs_ap / spmv_gpu_ap_scs (code/ap_kernels.hpp:562-634,
  * :721-816; selected for C outside {2,4,...,128}, code/classes_structs.hpp:630-636): the sp part
  * multiplies with the FLOAT copy of x (d_x_sp), the float product being rounded before it is added
@@ -417,7 +439,8 @@ int uspmv_apply_permutation_dev(void *d_out, const void *d_in, const int32_t *d_
  *   "spmmv_idx8" 1|0 NEXT uspmv_dmat_optimize_block: one-byte phase-local indices when no phase lists more than 256 X rows,
  *   "spmmv_list_plan" 0|1 NEXT uspmv_dmat_optimize_block: also build the one-list-per-tile plan of variants 4-6 (and its column-major copy
  *   of the entries) when the phased kernel can take the matrix,
- *   "sweep" 1|0 use a handle's column-window sweep plan, "sweep_nbuf" 1|2 LDS buffers, "sweep_unroll" 2|4|8, "sweep_remap" tiles per XCD group,
+ *   "sweep" 1|0 use a handle's column-window sweep plan (uspmv_spmv, uspmv_spmv_ap, uspmv_spmv_ap_hp, uspmv_spmmv, and uspmv_spmmv_ap at b in {2, 4, 8, 16}: 0 there = the gather kernel),
+ *   "sweep_nbuf" 1|2 LDS buffers, "sweep_unroll" 2|4|8, "sweep_remap" tiles per XCD group,
  *   "sweep_threads" 0|256|512|1024 threads per sweep workgroup (0 = min(tile rows, 1024); fewer threads = more rows per lane, at most 4),
  *   "sweep_wlog" / "sweep_tile_rows" / "sweep_max_stage" defaults of the NEXT sweep plan (window = 2^wlog elements; rows per tile;
  *   largest staging cost in bytes per non-zero for a tile to qualify, 0 = 24),

@@ -239,4 +239,19 @@ inline void spmmv_ap(const DeviceScs &dp, const DeviceScs &sp, const void *d_X, 
     uspmv_detail::check(uspmv_spmmv_ap(dp.handle(), sp.handle(), d_X, d_Y, b, ld, rowwise ? USPMV_ROWWISE : USPMV_COLWISE, stream), "uspmv_spmmv_ap");
 }
 
+// what spmmv_ap would run for 16-byte-aligned X / Y (uspmv_spmmv_ap_path): 0 generic, 1 gather, 2 staged over the shared line plan, 3 column-window
+// sweep; *vectors_per_pass (may be null) = vectors per pass of the sweep / staged kernel
+inline int spmmv_ap_path(const DeviceScs &dp, const DeviceScs &sp, int b, ST ld, bool rowwise, int *vectors_per_pass = nullptr) {
+    int path = 0, vec = 0;
+    uspmv_detail::check(uspmv_spmmv_ap_path(dp.handle(), sp.handle(), b, ld, rowwise ? USPMV_ROWWISE : USPMV_COLWISE, &path, &vec), "uspmv_spmmv_ap_path");
+    if (vectors_per_pass) *vectors_per_pass = vec;
+    return path;
+}
+// vectors per pass of spmmv_ap's sweep kernel at width b on windows of 2^wlog doubles (uspmv_spmmv_ap_sweep_vectors); 0: it does not apply
+inline int spmmv_ap_sweep_vectors(int b, int wlog) {
+    int v = 0;
+    uspmv_detail::check(uspmv_spmmv_ap_sweep_vectors(b, wlog, &v), "uspmv_spmmv_ap_sweep_vectors");
+    return v;
+}
+
 #endif  // USPMV_INTERFACE_HPP

@@ -17,6 +17,7 @@ really moves through HBM at least (the same plus the re-layout pass of a column-
 time over 8 TB/s as a fraction of its own name, and the X bytes the gathers request from the caches (8 * b per stored entry).
 
     python tools/ap_spmmv_probe.py --matrix stencil74 --b 4 --b 8 [--reps 200 --rounds 3 --no-unsplit --out probe.jsonl]
+    python tools/ap_spmmv_probe.py --matrix banded --sweep [--out probe.jsonl]      # sweep_vs_gather: see that function
 """
 import argparse
 import json
@@ -90,6 +91,69 @@ def staged_vs_gather(pkg, B, t, a, name, b, ds, ss, X, Y, n, alg, out):
         del Pd, Ps
 
 
+def sweep_vs_gather(pkg, B, t, a, name, widths, ds, ss, n, n_cols, out):
+    """the block sweep kernel over the pair's column-window sweep plan against the gather kernel and against b x spmv_ap, alternated
+    on the SAME handles (tuning "sweep" 1 / 0): (a) spmmv_ap, (g) spmmv_ap with "sweep" 0, (b) b x spmv_ap, (a) once more.  Plans: what
+    uspmv_dmat_optimize_ap installs by default (windows of 2^14 doubles: one vector fills the LDS, the block kernel does not apply and
+    (a) is (g)); the same planned for two LDS buffers (2^13); and every narrower window at which uspmv_spmmv_ap_sweep_vectors names
+    more vectors of this b per pass.  (b0): b x spmv_ap on the DEFAULT plan, the single-vector kernel at its best, measured in the same rounds."""
+    D0, S0 = pkg.DeviceMatrix(ds), pkg.DeviceMatrix(ss)
+    pkg.optimize_ap(D0, S0, ds, ss)
+    if D0.plan_info()[0] != 2:
+        rec = dict(matrix=name, config="sweep_vs_gather", result="not measured", why=f"optimize_ap installs plan kind {D0.plan_info()[0]}, not the sweep")
+        print(json.dumps(rec), flush=True)
+        if out: out.write(json.dumps(rec) + "\n"); out.flush()
+        return
+    for b in widths:
+        plans = [("default", 0, 1), ("default, planned for two buffers", 0, 2)]
+        for w in (12, 11):          # every narrower window that puts more vectors into a pass, down to the one that takes the most
+            if pkg.spmmv_ap_sweep_vectors(b, w) > pkg.spmmv_ap_sweep_vectors(b, w + 1): plans.append((f"wlog {w}", w, 1))
+        X = t.ones(b * n, dtype=t.float64, device="cuda"); Y = t.zeros_like(X)
+        alg = ds.n_elements * 12 + ss.n_elements * 8 + 16 * ds.n_chunks + 8 * b * (n_cols + n)
+        for plan_name, wlog_arg, plan_nbuf in plans:
+            Pd, Ps = pkg.DeviceMatrix(ds), pkg.DeviceMatrix(ss)
+            pkg.set_tuning(sweep_nbuf=plan_nbuf)
+            try:
+                if wlog_arg: pkg.optimize_sweep_ap(Pd, Ps, ds, ss, wlog_arg, 0)
+                else: pkg.optimize_ap(Pd, Ps, ds, ss)
+            finally:
+                pkg.set_tuning(sweep_nbuf=1)
+            meta = Pd.sweep_plan_digest()[1]
+            tile_rows, wlog, tiles, swept = int(meta[1]), int(meta[2]), int(meta[4]), int(meta[3])
+            for layout in ("rowwise", "colwise"):
+                lay = pkg.ROWWISE if layout == "rowwise" else pkg.COLWISE
+                path, vec = pkg.spmmv_ap_path(Pd, Ps, b, n, lay)
+                ta, tg, tb, tb0, ta2 = [], [], [], [], []
+                for _ in range(a.rounds):
+                    ta.append(B.time_launches(7, a.reps, A=Pd, B=Ps, x=X, y=Y, b=b, ld=n, layout=lay))
+                    pkg.set_tuning(sweep=0)
+                    try:
+                        tg.append(B.time_launches(7, a.reps, A=Pd, B=Ps, x=X, y=Y, b=b, ld=n, layout=lay))
+                    finally:
+                        pkg.set_tuning(sweep=1)
+                    tb.append(b * B.time_launches(4, a.reps, A=Pd, B=Ps, x=X, y=Y))
+                    tb0.append(b * B.time_launches(4, a.reps, A=D0, B=S0, x=X, y=Y))
+                    ta2.append(B.time_launches(7, a.reps, A=Pd, B=Ps, x=X, y=Y, b=b, ld=n, layout=lay))
+                ms_a, ms_g, ms_b, ms_b0 = (float(np.median(v)) for v in (ta, tg, tb, tb0))
+                spread = max(ta + ta2) - min(ta + ta2)
+                rec = dict(matrix=name, config="sweep_vs_gather", b=b, layout=layout, plan=plan_name, wlog=wlog, tile_rows=tile_rows, tiles=tiles, tiles_swept=swept,
+                           path=path, vectors_per_pass=vec, kernel=("generic", "gather", "staged", "sweep")[path], reps=a.reps, rounds=a.rounds,
+                           ms_a_spmmv_ap=round(ms_a, 4), ms_g_spmmv_ap_sweep_off=round(ms_g, 4), ms_b_times_spmv_ap=round(ms_b, 4),
+                           ms_b0_times_spmv_ap_default_plan=round(ms_b0, 4), ms_a_again=round(float(np.median(ta2)), 4), aa_spread_ms=round(spread, 4),
+                           g_over_a=round(ms_g / ms_a, 3), b_over_a=round(ms_b / ms_a, 3), b0_over_a=round(ms_b0 / ms_a, 3),
+                           a_ahead_of_g_by_more_than_spread=bool(ms_g - ms_a > spread), a_ahead_of_b_by_more_than_spread=bool(ms_b - ms_a > spread),
+                           a_ahead_of_b0_by_more_than_spread=bool(ms_b0 - ms_a > spread),
+                           algorithmic_bytes=alg, algorithmic_bytes_over_time_over_8TBs=round(alg / (ms_a * 1e-3) / HBM, 3),
+                           ms_rounds=dict(a=[round(v, 4) for v in ta], g=[round(v, 4) for v in tg], b=[round(v, 4) for v in tb], b0=[round(v, 4) for v in tb0],
+                                          a_again=[round(v, 4) for v in ta2]))
+                print(json.dumps(rec), flush=True)
+                if out: out.write(json.dumps(rec) + "\n"); out.flush()
+            del Pd, Ps
+        del X, Y
+        t.cuda.synchronize()
+        t.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--matrix", action="append", default=[])
@@ -98,6 +162,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--no-unsplit", action="store_true", help="skip (c), the block plan of the unsplit matrix")
     ap.add_argument("--staged", action="store_true", help="also: the staged kernel over the shared plan against the gather kernel on the same handles")
+    ap.add_argument("--sweep", action="store_true", help="only: the block sweep kernel over the pair's sweep plan against the gather kernel and b x spmv_ap "
+                                                         "on the same handles (sweep_vs_gather; --matrix banded)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch as t
@@ -115,6 +181,11 @@ def main():
         ss = pkg.convert_to_scs(sp, 32, 512, pkg.F32, fixed_permutation=perm)
         del dp, sp
         pkg.permute_scs_cols(ds, perm); pkg.permute_scs_cols(ss, perm)
+        if a.sweep:
+            del m
+            sweep_vs_gather(pkg, B, t, a, name, widths, ds, ss, ds.n_rows_padded, n_cols, out)
+            del ds, ss
+            continue
         Ad, As = pkg.DeviceMatrix(ds), pkg.DeviceMatrix(ss)
         pkg.optimize_ap(Ad, As, ds, ss)
         plan_kind = Ad.plan_info()[0]

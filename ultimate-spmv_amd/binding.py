@@ -115,6 +115,8 @@ _SIGS = {
     "uspmv_spmv_ap": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "uspmv_spmmv_ap": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
     "uspmv_spmmv_ap_plan_lines": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
+    "uspmv_spmmv_ap_path": (C.c_int, [_vp, _vp, C.c_int, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "uspmv_spmmv_ap_sweep_vectors": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "uspmv_spmv_ap_generic": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "uspmv_scs_gpu_f64": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "uspmv_scs_gpu_f32": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1190,6 +1192,21 @@ def spmmv_ap_plan_lines(b):
     {2, 4, 8, 16}); 0: no staged kernel for that b."""
     n = C.c_int()
     _ck(lib().uspmv_spmmv_ap_plan_lines(int(b), C.byref(n)))
+    return n.value
+
+
+def spmmv_ap_path(A_dp, A_sp, b, ld, layout=COLWISE):
+    """(path, vectors) that spmmv_ap would take for 16-byte-aligned X / Y under the current tuning (uspmv_spmmv_ap_path): path 0 generic
+    lane per row, 1 gather, 2 staged over the shared line plan, 3 column-window sweep; vectors per pass of the sweep / staged kernel, else 0."""
+    path, vec = C.c_int(), C.c_int()
+    _ck(lib().uspmv_spmmv_ap_path(A_dp.h, A_sp.h, int(b), int(ld), int(layout), C.byref(path), C.byref(vec)))
+    return path.value, vec.value
+
+
+def spmmv_ap_sweep_vectors(b, wlog):
+    """Vectors per pass of spmmv_ap's sweep kernel at width b on a plan with windows of 2^wlog doubles; 0: it does not apply there."""
+    n = C.c_int()
+    _ck(lib().uspmv_spmmv_ap_sweep_vectors(int(b), int(wlog), C.byref(n)))
     return n.value
 
 

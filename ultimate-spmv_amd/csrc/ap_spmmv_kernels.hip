@@ -11,16 +11,19 @@ namespace {
 // Any b, either layout, 8-byte-aligned pointers: the ap twin of scs_spmmv_rows, VB vectors per pass held in registers (2 * VB
 // accumulators), the dp chain and then the sp chain of the pass.
 // colwise: X[col + v*ld], Y[row + v*ld];  rowwise: X[col*b + v], Y[row*b + v].
-template <int VB, bool ROWWISE, bool NT>
+// IDS: the chunks chunk_ids[0 .. n_chunks) instead of all (the rest chunks of a column-window sweep plan).
+template <int VB, bool ROWWISE, bool NT, bool IDS = false>
 __global__ void scs_spmmv_ap_rows(const long n_chunks, const int C, const int *__restrict__ dp_cp, const int *__restrict__ dp_cl,
                                   const int *__restrict__ dp_ci, const double *__restrict__ dp_va, const int *__restrict__ sp_cp,
                                   const int *__restrict__ sp_cl, const int *__restrict__ sp_ci, const float *__restrict__ sp_va,
-                                  const double *__restrict__ X, double *__restrict__ Y, const int b, const long ld, const int xcd_remap) {
+                                  const double *__restrict__ X, double *__restrict__ Y, const int b, const long ld, const int xcd_remap,
+                                  const int *__restrict__ chunk_ids) {
     const unsigned lb = remap_block(blockIdx.x, gridDim.x, xcd_remap);
-    const long row = (long)lb * blockDim.x + threadIdx.x;
-    const long c = row / C;
+    long row = (long)lb * blockDim.x + threadIdx.x;
+    long c = row / C;
     const int i = (int)(row - c * C);
     if (c >= n_chunks) return;
+    if constexpr (IDS) { c = chunk_ids[c]; row = c * C + i; }
     const long dcs = dp_cp[c], scs_ = sp_cp[c];
     const int Ld = dp_cl[c], Ls = sp_cl[c];
     const double *dvp = dp_va + dcs + i;
@@ -295,16 +298,35 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_tlc(const long n_chunks, co
     (long)(dp)->n_chunks, (int)(dp)->C, (dp)->chunk_ptrs, (dp)->chunk_lengths, (dp)->col_idxs, (const double *)(dp)->values,    \
         (sp)->chunk_ptrs, (sp)->chunk_lengths, (sp)->col_idxs, (const float *)(sp)->values
 
+// ids: the chunks to run (n_ids of them), or nullptr for all
 template <int VB>
-void launch_ap_vb(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, int layout, hipStream_t st) {
+void launch_ap_vb(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, int layout, hipStream_t st,
+                  const int *ids = nullptr, long n_ids = 0) {
     const int block = g_tune.block;
-    const unsigned grid = grid_for(dp->n_chunks * dp->C, block);
+    const long n_chunks = ids ? n_ids : (long)dp->n_chunks;
+    const unsigned grid = grid_for(n_chunks * dp->C, block);
     const bool nt = g_tune.nontemporal != 0;
-#define APV_LAUNCH(RW, NTV) \
-    hipLaunchKernelGGL((scs_spmmv_ap_rows<VB, RW, NTV>), dim3(grid), dim3(block), 0, st, AP_PAIR_ARGS(dp, sp), X, Y, b, ld, g_tune.xcd_remap)
+#define APV_LAUNCH(RW, NTV)                                                                                                          \
+    do {                                                                                                                             \
+        if (ids)                                                                                                                     \
+            hipLaunchKernelGGL((scs_spmmv_ap_rows<VB, RW, NTV, true>), dim3(grid), dim3(block), 0, st, n_chunks, (int)dp->C, dp->chunk_ptrs,  \
+                               dp->chunk_lengths, dp->col_idxs, (const double *)dp->values, sp->chunk_ptrs, sp->chunk_lengths, sp->col_idxs,  \
+                               (const float *)sp->values, X, Y, b, ld, g_tune.xcd_remap, ids);                                      \
+        else                                                                                                                         \
+            hipLaunchKernelGGL((scs_spmmv_ap_rows<VB, RW, NTV, false>), dim3(grid), dim3(block), 0, st, AP_PAIR_ARGS(dp, sp), X, Y, b, ld,    \
+                               g_tune.xcd_remap, (const int *)nullptr);                                                             \
+    } while (0)
     if (layout == USPMV_ROWWISE) { if (nt) APV_LAUNCH(true, true); else APV_LAUNCH(true, false); }
     else { if (nt) APV_LAUNCH(false, true); else APV_LAUNCH(false, false); }
 #undef APV_LAUNCH
+}
+
+// any b through the lane-per-row kernel, VB vectors per pass
+void launch_ap_generic(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, int layout, hipStream_t st,
+                       const int *ids = nullptr, long n_ids = 0) {
+    if (b <= 2) launch_ap_vb<2>(dp, sp, X, Y, b, ld, layout, st, ids, n_ids);
+    else if (b <= 4) launch_ap_vb<4>(dp, sp, X, Y, b, ld, layout, st, ids, n_ids);
+    else launch_ap_vb<8>(dp, sp, X, Y, b, ld, layout, st, ids, n_ids);
 }
 
 template <int B, int U>
@@ -371,18 +393,48 @@ void launch_ap_tlc_bs(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *
 }
 
 // as many of the B vectors per pass as the plan's fullest tile leaves room for in LDS (at most 8: 2 * 8 accumulators per lane)
+int ap_tlc_bs(const uspmv_dmat *dp, int b) {
+    const size_t line_bytes = (size_t)dp->tlc.max_lines * 128;
+    if (b >= 8 && line_bytes * 8 <= AP_TLC_LDS) return 8;
+    if (b >= 4 && line_bytes * 4 <= AP_TLC_LDS) return 4;
+    return 2;
+}
+
 template <int B>
 void launch_ap_tlc(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, long ld, bool ycol, hipStream_t st) {
-    const size_t line_bytes = (size_t)dp->tlc.max_lines * 128;
-    if constexpr (B >= 8) { if (line_bytes * 8 <= AP_TLC_LDS) { launch_ap_tlc_bs<B, 8>(dp, sp, X, Y, ld, ycol, st); return; } }
-    if constexpr (B >= 4) { if (line_bytes * 4 <= AP_TLC_LDS) { launch_ap_tlc_bs<B, 4>(dp, sp, X, Y, ld, ycol, st); return; } }
+    const int bs = ap_tlc_bs(dp, B);
+    if constexpr (B >= 8) { if (bs == 8) { launch_ap_tlc_bs<B, 8>(dp, sp, X, Y, ld, ycol, st); return; } }
+    if constexpr (B >= 4) { if (bs == 4) { launch_ap_tlc_bs<B, 4>(dp, sp, X, Y, ld, ycol, st); return; } }
     launch_ap_tlc_bs<B, 2>(dp, sp, X, Y, ld, ycol, st);
 }
 
-// the staged kernel over the shared plan where it applies, else the gather kernel on the original arrays
+// What uspmv_spmmv_ap runs for b >= 2: the ONE predicate behind the launch and behind uspmv_spmmv_ap_path.
+// bs: vectors per pass of the sweep kernel (path 3) or of the staged kernel (path 2), else 0.
+enum { AP_PATH_GENERIC = 0, AP_PATH_GATHER = 1, AP_PATH_STAGED = 2, AP_PATH_SWEEP = 3 };
+struct ApBlockPath { int path, bs; };
+
+ApBlockPath ap_block_path(const uspmv_dmat *dp, const uspmv_dmat *sp, int b, long ld, int layout, bool aligned16) {
+    const uspmv_dmat *W = (dp->alt && g_tune.rechunk) ? dp->alt : dp;      // (the workspace of the pair: where uspmv_spmmv_x_prepared(dp, ...) put it)
+    const bool col = layout != USPMV_ROWWISE;
+    if (g_tune.spmmv_variant == 1 || !aligned16 || (b != 2 && b != 4 && b != 8 && b != 16)) return {AP_PATH_GENERIC, 0};
+    // the pair's column-window sweep plan, under the conditions of launch_spmv_ap plus the block ones: the float second part, column-major
+    // pieces of 16 bytes, no part of a distributed two-part step, and at least two vectors of a window in LDS
+    if (g_tune.sweep && dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.idx_b && dp->sw.plan_id == sp->sw.plan_id && dp->sw.n_parts == 2 &&
+        dp->sw.dtype_b == USPMV_F32 && !(col && (ld & 1)) && !dp->part && !sp->part && !W->part) {
+        const int bs = spmmv_ap_sweep_bs(dp, b);
+        // row-major X in more than two passes keeps the gather kernel: a pass stages bs * 8 bytes out of every b * 8-byte X row, so the rows'
+        // sectors are read b / bs times (banded-random 500 k x 140 pair: 1.17 / 2.23 / 3.89 ms against 0.89 / 2.05 / 2.05 ms)
+        if (bs >= 2 && (col || b / bs <= 2)) return {AP_PATH_SWEEP, bs};
+    }
+    if (col && W->part) return {AP_PATH_GENERIC, 0};         // (a handle inside a two-part distributed step: no whole re-layout)
+    if (ap_tlc_applies(dp, sp)) return {AP_PATH_STAGED, ap_tlc_bs(dp, b)};
+    return {AP_PATH_GATHER, 0};
+}
+
+// the staged kernel over the shared plan or the gather kernel on the original arrays, as ap_block_path chose
 template <int B>
-void launch_ap_block(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, long ld, bool ycol, hipStream_t st) {
-    if (ap_tlc_applies(dp, sp)) launch_ap_tlc<B>(dp, sp, X, Y, ld, ycol, st);
+void launch_ap_block(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, long ld, bool ycol, bool staged, hipStream_t st) {
+    if (staged) launch_ap_tlc<B>(dp, sp, X, Y, ld, ycol, st);
     else launch_ap_rowmajor<B>(dp, sp, X, Y, ld, ycol, st);
 }
 
@@ -390,18 +442,17 @@ void launch_ap_block(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X
 // uspmv_spmmv_x_prepared(dp, ...)), Y written column-major by the kernel.  W: the handle that owns the workspace.
 template <int B>
 int spmmv_ap_fast(const uspmv_dmat *dp, const uspmv_dmat *sp, const uspmv_dmat *W, const double *X, double *Y, long ld, int layout,
-                  hipStream_t st) {
+                  bool staged, hipStream_t st) {
     if (layout == USPMV_ROWWISE) {
-        launch_ap_block<B>(dp, sp, X, Y, ld, false, st);
+        launch_ap_block<B>(dp, sp, X, Y, ld, false, staged, st);
         return USPMV_OK;
     }
-    if (W->part) return -1;                                   // (a handle inside a two-part distributed step: no whole re-layout)
     const bool prepared = W->xprep_ptr == (const void *)X && W->xprep_b == B && W->xprep_ld == ld && W->xprep_form == 1 && W->ws;
     if (!prepared) {
         W->xprep_ptr = nullptr;                               // (the workspace is about to hold another X)
         if (int rc = relayout_x_plain(W, X, B, ld, st)) return rc;
     }
-    launch_ap_block<B>(dp, sp, (const double *)W->ws, Y, ld, true, st);
+    launch_ap_block<B>(dp, sp, (const double *)W->ws, Y, ld, true, staged, st);
     return USPMV_OK;
 }
 
@@ -412,26 +463,37 @@ namespace uspmv_dev {
 // the staged kernel takes a shared plan at every B-specialised width as long as two vectors of the fullest tile's X rows fit LDS
 int spmmv_ap_plan_lines(int b) { return (b == 2 || b == 4 || b == 8 || b == 16) ? (int)(AP_TLC_LDS / (128 * 2)) : 0; }
 
+void spmmv_ap_path(const uspmv_dmat *dp, const uspmv_dmat *sp, int b, long ld, int layout, int *path, int *vectors) {
+    const ApBlockPath p = ap_block_path(dp, sp, b, ld, layout, true);
+    *path = p.path; *vectors = p.bs;
+}
+
+int launch_spmmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *X, double *Y, int b,
+                           long ld, int layout, hipStream_t st) {
+    if (n_ids == 0) return USPMV_OK;
+    launch_ap_generic(dp, sp, X, Y, b, ld, layout, st, chunk_ids, n_ids);
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
 int launch_spmmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, int layout, hipStream_t st) {
     if (dp->n_chunks == 0) return USPMV_OK;
     if (b == 1) return launch_spmv_ap(dp, sp, X, nullptr, Y, st);
-    // the workspace of the pair lives where uspmv_spmmv_x_prepared(dp, ...) put it
     const uspmv_dmat *W = (dp->alt && g_tune.rechunk) ? dp->alt : dp;
-    int rc = -1;
-    if (g_tune.spmmv_variant != 1 && ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0)) {
+    const ApBlockPath p = ap_block_path(dp, sp, b, ld, layout, ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0));
+    if (p.path == AP_PATH_SWEEP) return launch_spmmv_ap_sweep(dp, sp, X, Y, b, ld, layout != USPMV_ROWWISE, p.bs, st);
+    if (p.path == AP_PATH_GENERIC) {  // generic width / layout / alignment
+        launch_ap_generic(dp, sp, X, Y, b, ld, layout, st);
+    } else {
+        const bool staged = p.path == AP_PATH_STAGED;
+        int rc = USPMV_OK;
         switch (b) {
-            case 2: rc = spmmv_ap_fast<2>(dp, sp, W, X, Y, ld, layout, st); break;
-            case 4: rc = spmmv_ap_fast<4>(dp, sp, W, X, Y, ld, layout, st); break;
-            case 8: rc = spmmv_ap_fast<8>(dp, sp, W, X, Y, ld, layout, st); break;
-            case 16: rc = spmmv_ap_fast<16>(dp, sp, W, X, Y, ld, layout, st); break;
-            default: break;
+            case 2: rc = spmmv_ap_fast<2>(dp, sp, W, X, Y, ld, layout, staged, st); break;
+            case 4: rc = spmmv_ap_fast<4>(dp, sp, W, X, Y, ld, layout, staged, st); break;
+            case 8: rc = spmmv_ap_fast<8>(dp, sp, W, X, Y, ld, layout, staged, st); break;
+            default: rc = spmmv_ap_fast<16>(dp, sp, W, X, Y, ld, layout, staged, st); break;
         }
-    }
-    if (rc > 0) return rc;
-    if (rc < 0) {  // generic width / layout / alignment
-        if (b <= 2) launch_ap_vb<2>(dp, sp, X, Y, b, ld, layout, st);
-        else if (b <= 4) launch_ap_vb<4>(dp, sp, X, Y, b, ld, layout, st);
-        else launch_ap_vb<8>(dp, sp, X, Y, b, ld, layout, st);
+        if (rc) return rc;
     }
     HIP_TRY(hipGetLastError());
     return USPMV_OK;

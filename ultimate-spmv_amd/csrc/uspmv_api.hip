@@ -1375,6 +1375,37 @@ int uspmv_spmmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const void *d
     return launch_spmmv_ap(dp, sp, (const double *)d_X, (double *)d_Y, b, (long)ld, layout, (hipStream_t)stream);
 }
 
+int uspmv_spmmv_ap_path(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, int b, int64_t ld, int layout, int *path, int *vectors_per_pass) {
+    const char *who = "uspmv_spmmv_ap_path";
+    if (int rc = check_dmat(dp, who)) return rc;
+    if (int rc = check_dmat(sp, who)) return rc;
+    if (dp->dtype != USPMV_F64 || sp->dtype != USPMV_F32)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: expects a double and a float struct", who);
+    if (dp->C != sp->C || dp->n_chunks != sp->n_chunks)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: dp and sp structs must share C and n_chunks", who);
+    if (!path || !vectors_per_pass) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL result pointer", who);
+    if (b < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: b=%d", who, b);
+    if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown layout %d", who, layout);
+    if (layout == USPMV_COLWISE && ld < dp->n_chunks * dp->C)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: ld=%lld smaller than n_rows_padded=%lld", who, (long long)ld,
+                           (long long)(dp->n_chunks * dp->C));
+    *path = 0; *vectors_per_pass = 0;
+    if (b == 1) {  // uspmv_spmv_ap: its sweep kernel, its staged kernel or lane per row, one vector each
+        if (dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.idx_b && dp->sw.plan_id == sp->sw.plan_id && g_tune.sweep) *path = 3;
+        else if (dp->tlc.on && sp->tlc.on && dp->tlc.plan_id != 0 && dp->tlc.plan_id == sp->tlc.plan_id && g_tune.tlc) *path = 2;
+        *vectors_per_pass = *path ? 1 : 0;
+        return USPMV_OK;
+    }
+    spmmv_ap_path(dp, sp, b, (long)ld, layout, path, vectors_per_pass);
+    return USPMV_OK;
+}
+
+int uspmv_spmmv_ap_sweep_vectors(int b, int wlog, int *vectors) {
+    if (b < 1 || wlog < 8 || wlog > 16 || !vectors) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv_ap_sweep_vectors: bad argument");
+    *vectors = spmmv_ap_sweep_vectors(b, wlog);
+    return USPMV_OK;
+}
+
 int uspmv_spmmv_ap_plan_lines(int b, int *max_lines) {
     if (b < 1 || !max_lines) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv_ap_plan_lines: bad argument");
     *max_lines = spmmv_ap_plan_lines(b);

@@ -402,11 +402,23 @@ bool spmmv_stream(const uspmv_dmat *A, const float *X, float *Y, long ld, bool y
 int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu);
 int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x, const float *d_x_sp, double *d_y,
                    hipStream_t stream);                                                                           // ap_kernels.hip
-// ap[dp_sp] on block vectors: b = 1 forwards to launch_spmv_ap; B in {2, 4, 8, 16} the row-major kernel (column-major X through the dp
-// handle's workspace), else lane per row with VB vectors per pass
+// ap[dp_sp] on block vectors: b = 1 forwards to launch_spmv_ap; B in {2, 4, 8, 16} the pair's column-window sweep plan where it carries one,
+// else the row-major kernels (column-major X through the dp handle's workspace); any other b lane per row with VB vectors per pass
 int launch_spmmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, int layout,
                     hipStream_t st);                                                                              // ap_spmmv_kernels.hip
 int spmmv_ap_plan_lines(int b);   // most lines per tile of a shared plan the staged block kernel takes at width b (0: no such kernel)
+// what launch_spmmv_ap runs for 16-byte-aligned X / Y (b >= 2): 0 generic lane per row, 1 gather, 2 staged over the shared line plan,
+// 3 column-window sweep; vectors: per pass of the sweep / staged kernel, else 0
+void spmmv_ap_path(const uspmv_dmat *dp, const uspmv_dmat *sp, int b, long ld, int layout, int *path, int *vectors);   // ap_spmmv_kernels.hip
+// lane per row over a list of chunks (the rest chunks of the pair's sweep plan), any b
+int launch_spmmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *X, double *Y, int b,
+                           long ld, int layout, hipStream_t st);                                                    // ap_spmmv_kernels.hip
+// the block sweep kernel (ap_spmmv_sweep.hip): vectors per pass at width b on windows of 2^wlog doubles (0: does not apply) / on this
+// handle's plan and threads per workgroup (capped by the accumulators a lane can hold); the launch: sweep tiles, then the rest chunks
+int spmmv_ap_sweep_vectors(int b, int wlog);
+int spmmv_ap_sweep_bs(const uspmv_dmat *dp, int b);
+int launch_spmmv_ap_sweep(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, bool colwise, int bs,
+                          hipStream_t st);
 // ap with an fp16 part (hi F64 | F32, mid F32 or nullptr, hp F16): the shared tile-local-column plan when all parts carry it, else lane per row
 int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *d_x, void *d_y, hipStream_t stream);   // ap_kernels.hip
 template <typename VT>

@@ -191,7 +191,7 @@ extern "C" {
 
 const char *uspmv_last_error(void) { return g_last_error.c_str(); }
 
-const char *uspmv_version(void) { return "uspmv-mi355x 0.1 (gfx950)"; }
+const char *uspmv_version(void) { return "uspmv-mi355x 0.2 (gfx950)"; }
 
 const char *uspmv_status_string(int s) {
     switch (s) {

@@ -392,6 +392,31 @@ int uspmv_spmv_ap_generic(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const 
  *   ap[sp_hp]     (hi F32, no mid): x, y float; every product sp_v * x and (float)hp_v * x rounded to float, then added to a double
  *                 accumulator per part; y = (float)(sp + hp) */
 int uspmv_spmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, void *d_y, void *stream);
+/* Adaptive precision with an fp16 part on block vectors: b right-hand sides, X and Y in the type of the hi part (double for ap[dp_hp] and
+ * ap[dp_sp_hp], float for ap[sp_hp]), handles as for uspmv_spmv_ap_hp, layouts and ld as uspmv_spmmv / uspmv_spmmv_ap (column-major
+ * X[col + v*ld] with ld >= n_rows_padded, row-major X[col*b + v]).  The reference has no such path.  For every C, both layouts and every
+ * b >= 1, column v of Y is bit for bit what uspmv_spmv_ap_hp writes for column v of X: per (row, v) one chain per part in slot order with
+ * the numerics above, then y = hi + hp, (hi + mid) + hp or (float)(sp + hp).  All n_rows_padded rows of every vector are written and
+ * nothing else of Y; b = 1 is uspmv_spmv_ap_hp.  No workspace is used on any handle (uspmv_spmmv_x_prepared has nothing to skip here).
+ * b in {2, 4, 8, 16} with 16-byte-aligned X and Y (and, column-major, ld * sizeof(element) a multiple of 16) on parts that carry one
+ * shared tile-local-column plan (uspmv_dmat_optimize_ap_hp / _device_ap_hp) whose fullest tile fits the 160 KiB of LDS with two vectors
+ * runs the staged kernel: per pass over the matrix entries the tile's X rows of BS vectors are staged in LDS straight from either layout
+ * and every part streams sizeof(value) + 2 bytes per entry; BS is the largest of {8, 4, 2} that is at most b and fits the fullest tile,
+ * b / BS passes inside one launch.  Everything else -- planless handles, handles with the column-window sweep plan, tuning "tlc" 0 or
+ * "spmmv_variant" 1, other widths, unaligned vectors -- runs the generic lane-per-row kernel.  uspmv_spmmv_ap_hp_path reports which. */
+int uspmv_spmmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_X, void *d_Y, int b, int64_t ld,
+                      int layout, void *stream);
+/* What uspmv_spmmv_ap_hp(hi, mid, hp, X, Y, b, ld, layout) would run for 16-byte-aligned X and Y, under the current tuning; the codes keep
+ * the meaning they have in uspmv_spmmv_ap_path.  *path: 0 the generic lane-per-row kernel, 2 the staged kernel over the shared
+ * tile-local-column plan (1 and 3 are not returned by this function yet).  *vectors_per_pass: the vectors per pass of the staged kernel,
+ * else 0.  b = 1 reports uspmv_spmv_ap_hp's own choice with one vector per pass: 3 its sweep kernel, 2 its staged kernel, 0 lane per row.
+ * Same argument checks and error texts as uspmv_spmmv_ap_hp (under this function's name); nothing is launched. */
+int uspmv_spmmv_ap_hp_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout, int *path,
+                           int *vectors_per_pass);
+/* The largest max_lines a caller can pass to uspmv_dmat_optimize_ap_hp / _device_ap_hp for which the staged kernel of uspmv_spmmv_ap_hp
+ * applies at width b whatever the matrix: two vectors of the fullest tile (16 X rows per line) in the 160 KiB of LDS -- 640 for
+ * x_dtype USPMV_F64 and 1280 for USPMV_F32 at b in {2, 4, 8, 16}, 0 for every other b.  b < 1, another dtype or a NULL pointer is refused. */
+int uspmv_spmmv_ap_hp_plan_lines(int b, int x_dtype, int *max_lines);
 
 /* Raw-array forms with the argument lists of the library kernels of code/interface.hpp
  * (uspmv_scs_gpu :1766-1793, uspmv_scs_c_gpu :1835-1867, uspmv_csr_gpu :1741-1760). */

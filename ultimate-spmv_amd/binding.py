@@ -76,6 +76,9 @@ _SIGS = {
     "uspmv_dmat_optimize_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_dmat_optimize_device_ap_hp": (C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_spmv_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "uspmv_spmmv_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
+    "uspmv_spmmv_ap_hp_path": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "uspmv_spmmv_ap_hp_plan_lines": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "uspmv_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "uspmv_set_device": (C.c_int, [C.c_int]),
     "uspmv_stream_synchronize": (C.c_int, [_vp]),
@@ -1216,6 +1219,32 @@ def spmv_ap_hp(A_hi, A_mid, A_hp, x, y, stream=None):
     assert x.dtype == A_hi.torch_dtype and y.dtype == A_hi.torch_dtype and y.numel() >= A_hi.n_rows_padded
     _ck(lib().uspmv_spmv_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(x), _dp(y), _stream_ptr(stream)))
     return y
+
+
+def spmmv_ap_hp(A_hi, A_mid, A_hp, X, Y, b, ld, layout=COLWISE, stream=None):
+    """Adaptive precision with an fp16 part on a block of b vectors (uspmv_spmmv_ap_hp): X, Y float64 when A_hi is F64, float32 when it
+    is F32; A_mid None for the two-part kinds; layouts and ld as spmmv.  Column v of Y is bitwise spmv_ap_hp of column v of X."""
+    assert X.dtype == A_hi.torch_dtype and Y.dtype == A_hi.torch_dtype      # (the order of the handles is the library's to check)
+    _ck(lib().uspmv_spmmv_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(X), _dp(Y), b, ld, layout, _stream_ptr(stream)))
+    return Y
+
+
+def spmmv_ap_hp_path(A_hi, A_mid, A_hp, b, ld, layout=COLWISE):
+    """(path, vectors) that spmmv_ap_hp would take for 16-byte-aligned X / Y under the current tuning (uspmv_spmmv_ap_hp_path): path 0
+    generic lane per row, 2 staged over the shared line plan (b = 1: spmv_ap_hp's own 3 sweep / 2 staged / 0); vectors per pass of the
+    staged kernel, else 0."""
+    path, vec = C.c_int(), C.c_int()
+    _ck(lib().uspmv_spmmv_ap_hp_path(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, int(b), int(ld), int(layout), C.byref(path),
+                                     C.byref(vec)))
+    return path.value, vec.value
+
+
+def spmmv_ap_hp_plan_lines(b, dtype):
+    """Largest max_lines for optimize_ap_hp / optimize_device_ap_hp at which the staged kernel serves spmmv_ap_hp of width b on X of
+    `dtype` (640 for F64, 1280 for F32 at b in {2, 4, 8, 16}); 0: no staged kernel for that b."""
+    n = C.c_int()
+    _ck(lib().uspmv_spmmv_ap_hp_plan_lines(int(b), int(dtype), C.byref(n)))
+    return n.value
 
 
 def uspmv_scs_gpu(Cc, n_chunks, chunk_ptrs, chunk_lengths, col_idxs, values, x, y, stream=None):

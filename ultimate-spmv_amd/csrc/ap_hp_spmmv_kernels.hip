@@ -1,0 +1,400 @@
+// Adaptive precision with an fp16 part on block vectors: uspmv_spmmv_ap_hp for ap[dp_hp], ap[sp_hp] and ap[dp_sp_hp].  The reference has
+// no twin (its CLI stops at "SpMMV is not yet implemented for AP kernels", code/utilities.hpp:1389, and its GPU path has no hp kernels at
+// all, code/classes_structs.hpp:553-600); the numerics are those of uspmv_spmv_ap_hp applied to every column of X: per (row, v) one chain
+// per part in slot order (ap_step), then ap_hp_y.  One lane per row everywhere and no chain is ever re-associated, so column v of Y is
+// bitwise uspmv_spmv_ap_hp of column v of X.  See DESIGN.md 5.8.
+#include "uspmv_device.hpp"
+
+using namespace uspmv_dev;
+
+namespace {
+
+// y from the folded sum of the leading parts and the hp chain: hi + hp, (hi + mid) + hp, or (float)(sp + hp) -- ap_hp_y with the
+// (hi + mid) already taken
+template <typename HT>
+__device__ __forceinline__ HT ap_hp_fold_y(double s, double q) { return ap_hp_y<HT, false>(s, 0.0, q); }
+
+// Any b, either layout, any C, no alignment demands: the hp twin of scs_spmmv_ap_rows.  VB vectors per pass held in registers; per
+// vector the parts' chains run one after the other with global gathers of X, (hi + mid) folded before the hp chain starts.
+// colwise: X[col + v*ld], Y[row + v*ld];  rowwise: X[col*b + v], Y[row*b + v].
+// IDS: the chunks chunk_ids[0 .. n_chunks) instead of all (the rest chunks of a column-window sweep plan).
+template <int VB, bool ROWWISE, bool NT, typename HT, bool MID, bool IDS = false>
+__global__ void scs_spmmv_ap_hp_rows(const long n_chunks, const int C, const ApHpParts P, const HT *__restrict__ X, HT *__restrict__ Y,
+                                     const int b, const long ld, const int xcd_remap, const int *__restrict__ chunk_ids) {
+    const unsigned lb = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    long row = (long)lb * blockDim.x + threadIdx.x;
+    long c = row / C;
+    const int i = (int)(row - c * C);
+    if (c >= n_chunks) return;
+    if constexpr (IDS) { c = chunk_ids[c]; row = c * C + i; }
+    auto chain = [&](auto vtag, const int k, const int v0, double (&acc)[VB]) {
+        typedef decltype(vtag) VT;
+        const long cs = P.cp[k][c];
+        const int L = P.cl[k][c];
+        const VT *vp = (const VT *)P.va[k] + cs + i;
+        const int *cp = P.ci[k] + cs + i;
+        for (int j = 0; j < L; ++j) {
+            const VT a = ld_stream<NT>(vp + (long)j * C);
+            const long col = ld_stream<NT>(cp + (long)j * C);
+#pragma unroll
+            for (int v = 0; v < VB; ++v)
+                if (v0 + v < b) acc[v] = ap_step(a, ROWWISE ? X[col * b + v0 + v] : X[col + (long)(v0 + v) * ld], acc[v]);
+        }
+    };
+    for (int v0 = 0; v0 < b; v0 += VB) {
+        double s[VB], q[VB];
+#pragma unroll
+        for (int v = 0; v < VB; ++v) { s[v] = 0.0; q[v] = 0.0; }
+        chain(HT(), 0, v0, s);
+        if constexpr (MID) {
+            chain(float(), 1, v0, q);
+#pragma unroll
+            for (int v = 0; v < VB; ++v) { s[v] = s[v] + q[v]; q[v] = 0.0; }
+        }
+        chain((unsigned short)0, 2, v0, q);
+#pragma unroll
+        for (int v = 0; v < VB; ++v) {
+            if (v0 + v < b) {
+                if (ROWWISE) st_y<NT>(Y + (row * b + v0 + v), ap_hp_fold_y<HT>(s[v], q[v]));
+                else st_y<NT>(Y + (row + (long)(v0 + v) * ld), ap_hp_fold_y<HT>(s[v], q[v]));
+            }
+        }
+    }
+}
+
+// A staged X row: BS elements of HT, moved in pieces of 16 bytes (8 bytes for two floats)
+template <typename HT, int BS>
+struct XRow {
+    static constexpr int PE = (int)(16 / sizeof(HT)) < BS ? (int)(16 / sizeof(HT)) : BS;   // elements per piece
+    static constexpr int NP = BS / PE;                                                      // pieces per row
+    typedef HT piece_t __attribute__((ext_vector_type(PE)));
+};
+
+// One part's chain of the staged kernel: values one per lane and slot, the 16-bit local indices four slots per 8-byte load (the streams of
+// scs_spmv_ap_hp_tlc: sizeof(VT) + 2 bytes per entry), the X row of a slot BS elements from LDS.  W: slots per batch, 8 or 4.
+template <int BS, bool NT, int W, typename VT, typename HT>
+__device__ __forceinline__ void tlc_hp_block_chain(const VT *__restrict__ vp, const unsigned long long *__restrict__ cq, const int L,
+                                                   const int C, const HT *xs, double (&acc)[BS]) {
+    typedef XRow<HT, BS> R;
+    auto step = [&](const VT a, const unsigned li) {
+        const typename R::piece_t *xp = (const typename R::piece_t *)(xs + li * BS);
+#pragma unroll
+        for (int k = 0; k < R::NP; ++k) {
+            const typename R::piece_t xv = xp[k];
+#pragma unroll
+            for (int e = 0; e < R::PE; ++e) acc[k * R::PE + e] = ap_step(a, xv[e], acc[k * R::PE + e]);
+        }
+    };
+    const int ng = L >> 2;
+    int g = 0;
+    if constexpr (W >= 8) {
+        for (; g + 2 <= ng; g += 2) {
+            VT v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = ld_stream<NT>(vp + (long)(4 * g + u) * C);
+            const unsigned long long qa = ld_stream<NT>(cq + (long)g * C), qb = ld_stream<NT>(cq + (long)(g + 1) * C);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) step(v[u], (unsigned)(qa >> (16 * u)) & 0xFFFFu);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) step(v[4 + u], (unsigned)(qb >> (16 * u)) & 0xFFFFu);
+        }
+    }
+    for (; g < ng; ++g) {
+        VT v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = ld_stream<NT>(vp + (long)(4 * g + u) * C);
+        const unsigned long long qa = ld_stream<NT>(cq + (long)g * C);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) step(v[u], (unsigned)(qa >> (16 * u)) & 0xFFFFu);
+    }
+    const int rem = L & 3;
+    if (rem) {
+        const unsigned long long qa = ld_stream<NT>(cq + (long)ng * C);
+        for (int u = 0; u < rem; ++u) step(ld_stream<NT>(vp + (long)(4 * ng + u) * C), (unsigned)(qa >> (16 * u)) & 0xFFFFu);
+    }
+}
+
+// ... and with 32-bit columns and X gathered from global memory in the caller's layout (tiles without a line list).
+// X points at vector v0 of the pass: row-major X[col * xstride + v], column-major X[col + v * xstride].
+template <int BS, bool NT, bool XCOL, typename VT, typename HT>
+__device__ __forceinline__ void gather_hp_block_chain(const VT *__restrict__ vp, const int *__restrict__ cp, const int L, const int C,
+                                                      const HT *__restrict__ X, const long xstride, double (&acc)[BS]) {
+    typedef XRow<HT, BS> R;
+    for (int j = 0; j < L; ++j) {
+        const VT a = ld_stream<NT>(vp + (long)j * C);
+        const long col = ld_stream<NT>(cp + (long)j * C);
+        if constexpr (XCOL) {
+#pragma unroll
+            for (int v = 0; v < BS; ++v) acc[v] = ap_step(a, X[col + v * xstride], acc[v]);
+        } else {
+            const typename R::piece_t *xp = (const typename R::piece_t *)(X + col * xstride);
+#pragma unroll
+            for (int k = 0; k < R::NP; ++k) {
+                const typename R::piece_t xv = xp[k];
+#pragma unroll
+                for (int e = 0; e < R::PE; ++e) acc[k * R::PE + e] = ap_step(a, xv[e], acc[k * R::PE + e]);
+            }
+        }
+    }
+}
+
+// The parts' shared tile-local-column plan on block vectors of width B: the block twin of scs_spmv_ap_hp_tlc and the three-part sibling
+// of scs_spmmv_ap_tlc.  A line of the plan (16 consecutive x elements there) is 16 consecutive X rows here.  Per pass BS of the B vectors:
+// the tile's lines are staged once in LDS as [X row][BS] in the type of X, then every part runs its chain from its own streams
+// (sizeof(value) + 2 bytes per entry and pass) with BS accumulators and the X operands from LDS.  (hi + mid) is folded per vector before
+// the hp chain starts -- exactly the (dp + sp) + hp of ap_hp_y -- so at most two sets of BS double accumulators are live.
+// XCOL: X column-major (X[col + v*ld]), staged straight from the caller's columns: per line and vector 16 consecutive elements (128 or
+// 64 contiguous bytes), read in 16-byte pieces and stored element by element into the rows of LDS; else row-major (X[col*B + v]), read
+// and stored in 16-byte pieces (8 bytes for float X at BS = 2).  Rows at or beyond x_rows are staged as zeros.  Tiles without a line
+// list gather from global X.  YCOL: Y[row + v*ld], else Y[row*B + v].
+template <int B, int BS, int CT, bool NT, typename HT, bool MID, bool XCOL, bool YCOL>
+__global__ void __launch_bounds__(1024) scs_spmmv_ap_hp_tlc(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ X,
+                                                            HT *__restrict__ Y, const long ld, const int *__restrict__ tile_line_ptr,
+                                                            const int *__restrict__ tile_lines, const long x_rows, const int xcd_remap) {
+    static_assert(BS >= 2 && BS <= B && B % BS == 0, "whole passes");
+    extern __shared__ __attribute__((aligned(16))) unsigned char tlc_smem[];
+    HT *xs = (HT *)tlc_smem;
+    typedef XRow<HT, BS> R;
+    typedef typename R::piece_t piece_t;
+    // slots per batch of the chains: four where the pass loop or eight vectors' accumulators leave no room for eight (<8, 8> spilled 2-3 VGPRs)
+    constexpr int W = (BS >= 8 || (BS < B && BS >= 4)) ? 4 : 8;
+    const int C = CT > 0 ? CT : C_rt;
+    const unsigned tile = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    const int lp0 = tile_line_ptr[tile];
+    const int nl = tile_line_ptr[tile + 1] - lp0;
+    const long row = (long)tile * blockDim.x + threadIdx.x;
+    const long c = row / C;
+    const int i = (int)(row - c * C);
+    const bool valid = c < n_chunks;
+    int cs[3] = {0, 0, 0}, L[3] = {0, 0, 0};
+    unsigned q0[3] = {0, 0, 0};
+    if (valid)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k != 1 || MID) { cs[k] = P.cp[k][c]; L[k] = P.cl[k][c]; q0[k] = P.c16p[k][c]; }
+#pragma unroll 1
+    for (int v0 = 0; v0 < B; v0 += BS) {
+        double s[BS], q[BS];
+#pragma unroll
+        for (int v = 0; v < BS; ++v) { s[v] = 0.0; q[v] = 0.0; }
+        if (nl > 0) {
+            if (v0) __syncthreads();              // (the previous pass has read its X rows)
+            if constexpr (XCOL) {
+                // piece p of the tile: vector v fastest, then the piece of the line's 16 rows, then the line
+                constexpr int XE = (int)(16 / sizeof(HT));    // consecutive X rows of one vector per 16-byte piece
+                constexpr int PPL = BS * (16 / XE);
+                typedef HT xpiece_t __attribute__((ext_vector_type(XE)));
+                for (int p = threadIdx.x; p < nl * PPL; p += blockDim.x) {
+                    const int k = p / PPL, w = p - k * PPL;
+                    const int v = w % BS, r0 = (w / BS) * XE;
+                    const long xrow = (long)tile_lines[lp0 + k] * 16 + r0;
+                    const HT *xp = X + xrow + (long)(v0 + v) * ld;
+                    xpiece_t t;
+                    if (xrow + XE <= x_rows) t = *(const xpiece_t *)xp;
+                    else {
+#pragma unroll
+                        for (int e = 0; e < XE; ++e) t[e] = xrow + e < x_rows ? xp[e] : (HT)0;
+                    }
+                    HT *dst = xs + ((long)k * 16 + r0) * BS + v;
+#pragma unroll
+                    for (int e = 0; e < XE; ++e) dst[e * BS] = t[e];
+                }
+            } else {
+                constexpr int PPL = 16 * R::NP;
+                for (int p = threadIdx.x; p < nl * PPL; p += blockDim.x) {     // piece p of the tile: LDS position = p
+                    const int k = p / PPL, w = p - k * PPL;
+                    const long xrow = (long)tile_lines[lp0 + k] * 16 + w / R::NP;
+                    piece_t t = (piece_t)(HT)0;
+                    if (xrow < x_rows) t = *(const piece_t *)(X + xrow * B + v0 + R::PE * (w % R::NP));
+                    *(piece_t *)(xs + (long)p * R::PE) = t;
+                }
+            }
+            __syncthreads();
+            if (L[0] > 0)
+                tlc_hp_block_chain<BS, NT, W>((const HT *)P.va[0] + (long)cs[0] + i, (const unsigned long long *)(P.c16[0] + q0[0]) + i, L[0], C, xs, s);
+            if constexpr (MID) {
+                if (L[1] > 0)
+                    tlc_hp_block_chain<BS, NT, W>((const float *)P.va[1] + (long)cs[1] + i, (const unsigned long long *)(P.c16[1] + q0[1]) + i, L[1], C,
+                                                  xs, q);
+#pragma unroll
+                for (int v = 0; v < BS; ++v) { s[v] = s[v] + q[v]; q[v] = 0.0; }
+            }
+            if (L[2] > 0)
+                tlc_hp_block_chain<BS, NT, W>((const unsigned short *)P.va[2] + (long)cs[2] + i, (const unsigned long long *)(P.c16[2] + q0[2]) + i,
+                                              L[2], C, xs, q);
+        } else {  // wide-footprint tile: 32-bit columns, global gathers
+            const HT *Xv = XCOL ? X + (long)v0 * ld : X + v0;
+            const long xstride = XCOL ? ld : (long)B;
+            gather_hp_block_chain<BS, NT, XCOL>((const HT *)P.va[0] + (long)cs[0] + i, P.ci[0] + (long)cs[0] + i, L[0], C, Xv, xstride, s);
+            if constexpr (MID) {
+                gather_hp_block_chain<BS, NT, XCOL>((const float *)P.va[1] + (long)cs[1] + i, P.ci[1] + (long)cs[1] + i, L[1], C, Xv, xstride, q);
+#pragma unroll
+                for (int v = 0; v < BS; ++v) { s[v] = s[v] + q[v]; q[v] = 0.0; }
+            }
+            gather_hp_block_chain<BS, NT, XCOL>((const unsigned short *)P.va[2] + (long)cs[2] + i, P.ci[2] + (long)cs[2] + i, L[2], C, Xv, xstride, q);
+        }
+        if (valid) {
+            if constexpr (YCOL) {
+#pragma unroll
+                for (int v = 0; v < BS; ++v) st_y<NT>(Y + (row + (long)(v0 + v) * ld), ap_hp_fold_y<HT>(s[v], q[v]));
+            } else {
+                piece_t *yp = (piece_t *)(Y + row * B + v0);
+#pragma unroll
+                for (int k = 0; k < R::NP; ++k) {
+                    piece_t t;
+#pragma unroll
+                    for (int e = 0; e < R::PE; ++e) t[e] = ap_hp_fold_y<HT>(s[k * R::PE + e], q[k * R::PE + e]);
+                    st_y<NT>(yp + k, t);
+                }
+            }
+        }
+    }
+}
+
+// ids: the chunks to run (n_ids of them), or nullptr for all
+template <int VB, typename HT, bool MID>
+void launch_ap_hp_vb(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, int b, long ld, int layout, hipStream_t st, const int *ids,
+                     long n_ids) {
+    const int block = g_tune.block;
+    const long n_chunks = ids ? n_ids : (long)hi->n_chunks;
+    const unsigned grid = grid_for(n_chunks * hi->C, block);
+    const bool nt = g_tune.nontemporal != 0;
+#define APHV_LAUNCH(RW, NTV)                                                                                                              \
+    do {                                                                                                                                  \
+        if (ids)                                                                                                                          \
+            hipLaunchKernelGGL((scs_spmmv_ap_hp_rows<VB, RW, NTV, HT, MID, true>), dim3(grid), dim3(block), 0, st, n_chunks, (int)hi->C, P, X, Y, \
+                               b, ld, g_tune.xcd_remap, ids);                                                                            \
+        else                                                                                                                              \
+            hipLaunchKernelGGL((scs_spmmv_ap_hp_rows<VB, RW, NTV, HT, MID, false>), dim3(grid), dim3(block), 0, st, n_chunks, (int)hi->C, P, X, Y, \
+                               b, ld, g_tune.xcd_remap, (const int *)nullptr);                                                           \
+    } while (0)
+    if (layout == USPMV_ROWWISE) { if (nt) APHV_LAUNCH(true, true); else APHV_LAUNCH(true, false); }
+    else { if (nt) APHV_LAUNCH(false, true); else APHV_LAUNCH(false, false); }
+#undef APHV_LAUNCH
+}
+
+// any b through the lane-per-row kernel, VB vectors per pass
+template <typename HT, bool MID>
+void launch_ap_hp_generic(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, int b, long ld, int layout, hipStream_t st,
+                          const int *ids = nullptr, long n_ids = 0) {
+    if (b <= 2) launch_ap_hp_vb<2, HT, MID>(hi, P, X, Y, b, ld, layout, st, ids, n_ids);
+    else if (b <= 4) launch_ap_hp_vb<4, HT, MID>(hi, P, X, Y, b, ld, layout, st, ids, n_ids);
+    else launch_ap_hp_vb<8, HT, MID>(hi, P, X, Y, b, ld, layout, st, ids, n_ids);
+}
+
+constexpr size_t AP_HP_TLC_LDS = 160 * 1024;   // LDS budget of the staged kernel: all a gfx950 workgroup can have
+
+size_t hp_x_bytes(const uspmv_dmat *hi) { return hi->dtype == USPMV_F32 ? 4 : 8; }
+
+// as many of the b vectors per pass as the plan's fullest tile leaves room for in LDS (at most 8: 2 * 8 accumulators per lane); 0: not two
+int ap_hp_tlc_bs(const uspmv_dmat *hi, int b) {
+    const size_t line_bytes = (size_t)hi->tlc.max_lines * 16 * hp_x_bytes(hi);
+    for (int bs = 8; bs >= 2; bs >>= 1)
+        if (bs <= b && b % bs == 0 && line_bytes * bs <= AP_HP_TLC_LDS) return bs;
+    return 0;
+}
+
+template <int B, int BS, typename HT, bool MID>
+void launch_ap_hp_tlc_bs(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool col, hipStream_t st) {
+    const size_t lds = (size_t)hi->tlc.max_lines * 16 * sizeof(HT) * BS;     // (what the fullest tile lists, not the budget)
+    const int C = (int)hi->C;
+#define APHT_LAUNCH(CTV, NTV, COLV)                                                                                                  \
+    do {                                                                                                                             \
+        auto kfn = scs_spmmv_ap_hp_tlc<B, BS, CTV, NTV, HT, MID, COLV, COLV>;                                                        \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)hi->tlc.n_tiles), dim3(hi->tlc.tile_rows), lds, st, (long)hi->n_chunks, C, P, X, Y, ld, \
+                           hi->tlc.line_ptr.get(), hi->tlc.lines.get(), (long)hi->tlc.x_len, g_tune.xcd_remap);                      \
+    } while (0)
+#define APHT_NT(CTV, NTV) do { if (col) APHT_LAUNCH(CTV, NTV, true); else APHT_LAUNCH(CTV, NTV, false); } while (0)
+    if (g_tune.nontemporal) { if (C == 32) APHT_NT(32, true); else APHT_NT(0, true); }
+    else { if (C == 32) APHT_NT(32, false); else APHT_NT(0, false); }
+#undef APHT_NT
+#undef APHT_LAUNCH
+}
+
+template <int B, typename HT, bool MID>
+void launch_ap_hp_tlc(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool col, int bs, hipStream_t st) {
+    if constexpr (B >= 8) { if (bs == 8) { launch_ap_hp_tlc_bs<B, 8, HT, MID>(hi, P, X, Y, ld, col, st); return; } }
+    if constexpr (B >= 4) { if (bs == 4) { launch_ap_hp_tlc_bs<B, 4, HT, MID>(hi, P, X, Y, ld, col, st); return; } }
+    launch_ap_hp_tlc_bs<B, 2, HT, MID>(hi, P, X, Y, ld, col, st);
+}
+
+// What uspmv_spmmv_ap_hp runs for b >= 2: the ONE predicate behind the launch and behind uspmv_spmmv_ap_hp_path.  The codes are
+// uspmv_spmmv_ap_path's: 0 the generic lane-per-row kernel, 2 the staged kernel (bs: its vectors per pass, else 0); 1 and 3 have no hp
+// kernel yet.
+enum { AP_HP_PATH_GENERIC = 0, AP_HP_PATH_STAGED = 2 };
+struct ApHpBlockPath { int path, bs; };
+
+ApHpBlockPath ap_hp_block_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, int b, long ld, int layout, bool aligned16) {
+    if (g_tune.spmmv_variant == 1 || !aligned16 || (b != 2 && b != 4 && b != 8 && b != 16)) return {AP_HP_PATH_GENERIC, 0};
+    if (layout != USPMV_ROWWISE && ((size_t)ld * hp_x_bytes(hi)) % 16 != 0) return {AP_HP_PATH_GENERIC, 0};   // (16-byte pieces of the columns)
+    if (hi->sw.on) return {AP_HP_PATH_GENERIC, 0};           // the column-window sweep plan has no block form for hp parts
+    const uint64_t id = hi->tlc.plan_id;
+    const bool planned = hi->tlc.on && id != 0 && hp->tlc.on && hp->tlc.plan_id == id && (!mid || (mid->tlc.on && mid->tlc.plan_id == id));
+    if (!planned || !g_tune.tlc || hi->tlc.max_lines < 1) return {AP_HP_PATH_GENERIC, 0};
+    const int bs = ap_hp_tlc_bs(hi, b);
+    if (bs < 2) return {AP_HP_PATH_GENERIC, 0};              // not even two vectors of the fullest tile fit LDS
+    return {AP_HP_PATH_STAGED, bs};
+}
+
+template <typename HT, bool MID>
+int launch_ap_hp_block(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const HT *X, HT *Y, int b, long ld, int layout,
+                       hipStream_t st) {
+    const ApHpParts P = ap_hp_parts(hi, mid, hp);
+    const ApHpBlockPath p = ap_hp_block_path(hi, mid, hp, b, ld, layout, ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0));
+    if (p.path == AP_HP_PATH_STAGED) {
+        const bool col = layout != USPMV_ROWWISE;
+        switch (b) {
+            case 2: launch_ap_hp_tlc<2, HT, MID>(hi, P, X, Y, ld, col, p.bs, st); break;
+            case 4: launch_ap_hp_tlc<4, HT, MID>(hi, P, X, Y, ld, col, p.bs, st); break;
+            case 8: launch_ap_hp_tlc<8, HT, MID>(hi, P, X, Y, ld, col, p.bs, st); break;
+            default: launch_ap_hp_tlc<16, HT, MID>(hi, P, X, Y, ld, col, p.bs, st); break;
+        }
+    } else {
+        launch_ap_hp_generic<HT, MID>(hi, P, X, Y, b, ld, layout, st);
+    }
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
+}  // namespace
+
+namespace uspmv_dev {
+
+// two vectors of the fullest tile's X rows (16 per line) in LDS: the staged kernel then takes a shared plan at every specialised width
+int spmmv_ap_hp_plan_lines(int b, int x_dtype) {
+    const size_t xb = x_dtype == USPMV_F32 ? 4 : 8;
+    return (b == 2 || b == 4 || b == 8 || b == 16) ? (int)(AP_HP_TLC_LDS / (16 * 2 * xb)) : 0;
+}
+
+void spmmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, int b, long ld, int layout, int *path, int *vectors) {
+    if (b == 1) {       // uspmv_spmv_ap_hp's own choice, one vector per pass
+        *path = spmv_ap_hp_path(hi, mid, hp, true);
+        *vectors = *path ? 1 : 0;
+        return;
+    }
+    const ApHpBlockPath p = ap_hp_block_path(hi, mid, hp, b, ld, layout, true);
+    *path = p.path; *vectors = p.bs;
+}
+
+int launch_spmmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
+                              const void *X, void *Y, int b, long ld, int layout, hipStream_t st) {
+    if (n_ids == 0) return USPMV_OK;
+    const ApHpParts P = ap_hp_parts(hi, mid, hp);
+    if (hi->dtype == USPMV_F32) launch_ap_hp_generic<float, false>(hi, P, (const float *)X, (float *)Y, b, ld, layout, st, chunk_ids, n_ids);
+    else if (mid) launch_ap_hp_generic<double, true>(hi, P, (const double *)X, (double *)Y, b, ld, layout, st, chunk_ids, n_ids);
+    else launch_ap_hp_generic<double, false>(hi, P, (const double *)X, (double *)Y, b, ld, layout, st, chunk_ids, n_ids);
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
+int launch_spmmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *X, void *Y, int b, long ld, int layout,
+                       hipStream_t st) {
+    if (hi->n_chunks == 0) return USPMV_OK;
+    if (b == 1) return launch_spmv_ap_hp(hi, mid, hp, X, Y, st);
+    if (hi->dtype == USPMV_F32) return launch_ap_hp_block<float, false>(hi, nullptr, hp, (const float *)X, (float *)Y, b, ld, layout, st);
+    if (mid) return launch_ap_hp_block<double, true>(hi, mid, hp, (const double *)X, (double *)Y, b, ld, layout, st);
+    return launch_ap_hp_block<double, false>(hi, nullptr, hp, (const double *)X, (double *)Y, b, ld, layout, st);
+}
+
+}  // namespace uspmv_dev

@@ -260,14 +260,6 @@ __device__ __forceinline__ double gather_chain(const VT *__restrict__ vp, const 
     return acc;
 }
 
-// the parts' arrays (mid: nullptr unless ap[dp_sp_hp]); c16p / c16: the shared plan's per-part local indices
-struct ApHpParts {
-    const int *cp[3], *cl[3], *ci[3];
-    const void *va[3];
-    const unsigned *c16p[3];
-    const unsigned short *c16[3];
-};
-
 // Tile-local-column form: the tile's x lines (the union over all parts) staged once in LDS, then the parts' chains one after the other,
 // each streaming sizeof(VT) + 2 bytes per non-zero.  Tiles without a line list (footprint over the plan's line budget) gather from x.
 template <int CT, bool NT, typename HT, bool MID>
@@ -343,17 +335,6 @@ __global__ void scs_spmv_ap_hp_rows(const long n_chunks, const int C_rt, const A
     st_y<NT>(y + row, ap_hp_y<HT, MID>(acc[0], acc[1], acc[2]));
 }
 
-ApHpParts ap_hp_parts(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp) {
-    ApHpParts P{};
-    const uspmv_dmat *ms[3] = {hi, mid, hp};
-    for (int k = 0; k < 3; ++k) {
-        if (!ms[k]) continue;
-        P.cp[k] = ms[k]->chunk_ptrs; P.cl[k] = ms[k]->chunk_lengths; P.ci[k] = ms[k]->col_idxs; P.va[k] = ms[k]->values;
-        P.c16p[k] = ms[k]->tlc.c16_ptrs; P.c16[k] = ms[k]->tlc.col16;
-    }
-    return P;
-}
-
 // the chunks in chunk_ids through the lane-per-row kernel
 template <typename HT, bool MID>
 int launch_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids, const HT *d_x,
@@ -372,20 +353,16 @@ int launch_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv
 
 template <typename HT, bool MID>
 int launch_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const HT *d_x, HT *d_y, hipStream_t stream) {
-    // a column-window sweep plan shared by all parts first (its arrays live on hi), then the shared line plan, then lane per row
-    const uint64_t sid = hi->sw.plan_id;
-    if (hi->sw.on && hi->sw.tile_ids && hi->sw.n_parts == (MID ? 3 : 2) && hp->sw.on && hp->sw.plan_id == sid &&
-        (!mid || (mid->sw.on && mid->sw.plan_id == sid)) && g_tune.sweep && (uintptr_t)d_x % 16 == 0) {
+    const int path = spmv_ap_hp_path(hi, mid, hp, (uintptr_t)d_x % 16 == 0);
+    if (path == 3) {
         if (int rc = launch_spmv_sweep_ap_hp(hi, MID, d_x, d_y, stream)) return rc;
         if (hi->sw.n_rest == 0) return USPMV_OK;
         return launch_ap_hp_chunks<HT, MID>(hi, mid, hp, hi->sw.rest, (long)hi->sw.n_rest, d_x, d_y, stream);
     }
     const ApHpParts P = ap_hp_parts(hi, mid, hp);
-    const uint64_t id = hi->tlc.plan_id;
-    const bool planned = hi->tlc.on && id != 0 && hp->tlc.on && hp->tlc.plan_id == id && (!mid || (mid->tlc.on && mid->tlc.plan_id == id));
     const bool nt = g_tune.nontemporal != 0;
     const int C = (int)hi->C;
-    if (planned && g_tune.tlc && (uintptr_t)d_x % 16 == 0) {
+    if (path == 2) {
         const size_t lds = (size_t)hi->tlc.max_lines * 16 * sizeof(HT);
 #define APHP_TLC(CTV, NTV)                                                                                                       \
     do {                                                                                                                         \
@@ -413,6 +390,17 @@ int launch_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *
 }  // namespace
 
 namespace uspmv_dev {
+
+int spmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, bool x_aligned16) {
+    // a column-window sweep plan shared by all parts first (its arrays live on hi), then the shared line plan, then lane per row
+    const uint64_t sid = hi->sw.plan_id;
+    if (hi->sw.on && hi->sw.tile_ids && hi->sw.n_parts == (mid ? 3 : 2) && hp->sw.on && hp->sw.plan_id == sid &&
+        (!mid || (mid->sw.on && mid->sw.plan_id == sid)) && g_tune.sweep && x_aligned16)
+        return 3;
+    const uint64_t id = hi->tlc.plan_id;
+    const bool planned = hi->tlc.on && id != 0 && hp->tlc.on && hp->tlc.plan_id == id && (!mid || (mid->tlc.on && mid->tlc.plan_id == id));
+    return planned && g_tune.tlc && x_aligned16 ? 2 : 0;
+}
 
 int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *d_x, void *d_y, hipStream_t stream) {
     if (hi->dtype == USPMV_F32) return launch_ap_hp<float, false>(hi, nullptr, hp, (const float *)d_x, (float *)d_y, stream);

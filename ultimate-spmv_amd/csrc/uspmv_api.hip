@@ -420,6 +420,43 @@ int uspmv_spmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspm
     return launch_spmv_ap_hp(hi, mid, hp, d_x, d_y, (hipStream_t)stream);
 }
 
+// the argument checks uspmv_spmmv_ap_hp and uspmv_spmmv_ap_hp_path share
+static int check_spmmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout, const char *who) {
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    if (b < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: b=%d", who, b);
+    if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown layout %d", who, layout);
+    if (layout == USPMV_COLWISE && ld < hi->n_chunks * hi->C)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: ld=%lld smaller than n_rows_padded=%lld", who, (long long)ld,
+                           (long long)(hi->n_chunks * hi->C));
+    return USPMV_OK;
+}
+
+int uspmv_spmmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_X, void *d_Y, int b, int64_t ld,
+                      int layout, void *stream) {
+    const char *who = "uspmv_spmmv_ap_hp";
+    if (int rc = check_spmmv_ap_hp(hi, mid, hp, b, ld, layout, who)) return rc;
+    if (!d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL vector", who);
+    if (int rc = require_device()) return rc;
+    if (hi->n_chunks == 0) return USPMV_OK;
+    return launch_spmmv_ap_hp(hi, mid, hp, d_X, d_Y, b, (long)ld, layout, (hipStream_t)stream);
+}
+
+int uspmv_spmmv_ap_hp_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout, int *path,
+                           int *vectors_per_pass) {
+    const char *who = "uspmv_spmmv_ap_hp_path";
+    if (int rc = check_spmmv_ap_hp(hi, mid, hp, b, ld, layout, who)) return rc;
+    if (!path || !vectors_per_pass) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL result pointer", who);
+    spmmv_ap_hp_path(hi, mid, hp, b, (long)ld, layout, path, vectors_per_pass);
+    return USPMV_OK;
+}
+
+int uspmv_spmmv_ap_hp_plan_lines(int b, int x_dtype, int *max_lines) {
+    if (b < 1 || (x_dtype != USPMV_F64 && x_dtype != USPMV_F32) || !max_lines)
+        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv_ap_hp_plan_lines: bad argument");
+    *max_lines = spmmv_ap_hp_plan_lines(b, x_dtype);
+    return USPMV_OK;
+}
+
 extern "C++" {
 namespace uspmv_dev {
 

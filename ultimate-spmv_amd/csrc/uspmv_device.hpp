@@ -421,6 +421,20 @@ int launch_spmmv_ap_sweep(const uspmv_dmat *dp, const uspmv_dmat *sp, const doub
                           hipStream_t st);
 // ap with an fp16 part (hi F64 | F32, mid F32 or nullptr, hp F16): the shared tile-local-column plan when all parts carry it, else lane per row
 int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *d_x, void *d_y, hipStream_t stream);   // ap_kernels.hip
+// what launch_spmv_ap_hp runs: 3 the shared column-window sweep, 2 the shared tile-local-column plan, 0 lane per row
+int spmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, bool x_aligned16);                                   // ap_kernels.hip
+// ... on block vectors (X, Y in the type of the hi part): b = 1 forwards to launch_spmv_ap_hp; b in {2, 4, 8, 16} on 16-byte-aligned
+// vectors the staged kernel over the parts' shared tile-local-column plan where two vectors of its fullest tile fit LDS; else lane per
+// row with VB vectors per pass (handles without a plan or with the sweep plan, any other b, layout or alignment)
+int launch_spmmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *X, void *Y, int b, long ld, int layout,
+                       hipStream_t st);                                                                           // ap_hp_spmmv_kernels.hip
+int spmmv_ap_hp_plan_lines(int b, int x_dtype);   // most lines per tile of a shared plan the staged block kernel takes at width b (0: no such kernel)
+// what launch_spmmv_ap_hp runs for 16-byte-aligned X / Y: 0 lane per row, 2 staged over the shared line plan (b = 1: spmv_ap_hp_path);
+// vectors: per pass of the staged kernel, else 0
+void spmmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, int b, long ld, int layout, int *path, int *vectors);
+// lane per row over a list of chunks (for the rest chunks of a sweep plan's block form), any b
+int launch_spmmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
+                              const void *X, void *Y, int b, long ld, int layout, hipStream_t st);                 // ap_hp_spmmv_kernels.hip
 template <typename VT>
 int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st);                                    // sweep_kernels.hip (sweep tiles only)
 int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st);                       // sweep_kernels.hip
@@ -507,7 +521,7 @@ __device__ __forceinline__ void st_y(T *p, T v) {
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
-// Adaptive precision with an fp16 part (ap_kernels.hip, sweep_ap_hp_kernels.hip): one step of a part's chain.  With a double x every
+// Adaptive precision with an fp16 part (ap_kernels.hip, ap_hp_spmmv_kernels.hip, sweep_ap_hp_kernels.hip): one step of a part's chain.  With a double x every
 // product is an FMA in double on the exactly widened value (scs_ap_impl_cpu's convention, hp in the place of sp), with a float x the
 // product is rounded to float and then added to the part's double accumulator (the sp part of spmv_omp_scs_ap).  hp values arrive
 // as the binary16 bits; v_cvt_f32_f16 widens them exactly.
@@ -523,6 +537,24 @@ __device__ __forceinline__ HT ap_hp_y(double h, double m, double q) {
     if constexpr (sizeof(HT) == 4) return (float)(h + q);
     else if constexpr (MID) return (h + m) + q;
     else return h + q;
+}
+
+// the parts' arrays as the kernels take them (mid: nullptr unless ap[dp_sp_hp]); c16p / c16: the shared plan's per-part local indices
+struct ApHpParts {
+    const int *cp[3], *cl[3], *ci[3];
+    const void *va[3];
+    const unsigned *c16p[3];
+    const unsigned short *c16[3];
+};
+inline ApHpParts ap_hp_parts(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp) {
+    ApHpParts P{};
+    const uspmv_dmat *ms[3] = {hi, mid, hp};
+    for (int k = 0; k < 3; ++k) {
+        if (!ms[k]) continue;
+        P.cp[k] = ms[k]->chunk_ptrs; P.cl[k] = ms[k]->chunk_lengths; P.ci[k] = ms[k]->col_idxs; P.va[k] = ms[k]->values;
+        P.c16p[k] = ms[k]->tlc.c16_ptrs; P.c16[k] = ms[k]->tlc.col16;
+    }
+    return P;
 }
 
 // DPP quad broadcast: every lane of a quad gets lane U's value (the four-lanes-per-row SpMMV kernels)

@@ -305,6 +305,18 @@ int uspmv_dmat_tile_rows(const uspmv_dmat_t *m, int *tile_rows);
 /* Bits per tile-local column index the plan's kernel streams: 16, or 12 where the plan packed them (tiles of at most 256 lines; kept when
  * the mean row length is >= 8; tuning key "tlc_idx12" 0 switches it off, 2 keeps it wherever it can be built); 0 = no plan */
 int uspmv_dmat_index_bits(const uspmv_dmat_t *m, int *bits);
+/* Additive chunk records (uspmv_dmat_optimize on one struct that carries its permutation, n_rows == n_cols, line plan kept; tuning key
+ * "tlc_additive": 0 never, 1 kept when records + column map are at most half of the local-index stream they replace, 2 wherever they can
+ * be built): the tiles' x windows are laid out in LDS in the column order the sigma sort started from, where the entries of most chunks of a
+ * banded matrix sit at (one position per lane) + (one per slot); the kernel streams 64 + 2 * length bytes for such a chunk instead of 1.5 or
+ * 2 bytes per entry.  n_chunks: chunks of the tiles that carry records (0: the handle has none), n_additive: the additive ones among them.
+ * uspmv_dmat_index_bits keeps describing the local-index arrays, which stay as built. */
+int uspmv_dmat_additive_chunks(const uspmv_dmat_t *m, int64_t *n_additive, int64_t *n_chunks);
+/* The planner's encoder of those records on a host struct, no device needed (tests): the line plan uspmv_dmat_optimize would build at its
+ * default rows per tile (256, or tuning key "tlc_tile_rows"), the records over it under the current "tlc_additive", then every record read back to the column of its entry.
+ * stats = {kept, n_additive, n_chunks, tiles with records, tiles (of the records' own size where they have one), record bytes + map bytes, bytes of the stream replaced, LDS elements of the
+ * fullest tile}; cols[n_elements] (may be NULL): the decoded column of every entry, padding included (-1: the entry's tile has no records). */
+int uspmv_additive_plan_probe(const uspmv_scs_t *s, int64_t stats[8], int32_t *cols);
 /* uspmv_spmv over a subset of tiles (d_tile_ids[n_ids]) of a handle with a plan: the interior /
  * boundary split of the halo-overlap scheme at tile granularity.  Entries < 0 are skipped (a list another kernel switches on or off). */
 int uspmv_spmv_tiles(const uspmv_dmat_t *A, const int32_t *d_tile_ids, int64_t n_ids, const void *d_x, void *d_y,

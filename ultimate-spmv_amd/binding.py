@@ -94,6 +94,8 @@ _SIGS = {
     "uspmv_spmv_tiles": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "uspmv_dmat_tile_rows": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "uspmv_dmat_index_bits": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "uspmv_dmat_additive_chunks": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "uspmv_additive_plan_probe": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp]),
     "uspmv_dmat_optimize_device": (C.c_int, [_vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_dmat_optimize_device_ap": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_dmat_plan_download": (C.c_int, [_vp, C.POINTER(_i64), _vp, _vp, _vp, _vp]),
@@ -938,6 +940,12 @@ class DeviceMatrix:
         _ck(lib().uspmv_dmat_index_bits(self.h, C.byref(b)))
         return b.value
 
+    def additive_chunks(self):
+        """(additive chunks, chunks of the tiles that carry additive chunk records); (0, 0) without records: uspmv_dmat_additive_chunks."""
+        a, b = C.c_int64(), C.c_int64()
+        _ck(lib().uspmv_dmat_additive_chunks(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def plan_download(self):
         """Host copies of the tile-local-column plan (tests): dict or None when the handle has no plan."""
         meta = (_i64 * 4)()
@@ -1027,6 +1035,16 @@ class DeviceMatrix:
         if getattr(self, "h", None) and _LIB is not None:
             _LIB.uspmv_dmat_free(self.h)
             self.h = None
+
+
+def additive_plan_probe(scs, decode=True):
+    """The planner's additive chunk records of a host struct under the current "tlc_additive", read back (uspmv_additive_plan_probe; no device
+    needed): (stats, cols) with stats a dict and cols the decoded column of every entry (None when not asked for)."""
+    st = (C.c_int64 * 8)()
+    cols = np.full(scs.n_elements, -3, dtype=np.int32) if decode else None
+    _ck(lib().uspmv_additive_plan_probe(scs.h, st, _np_ptr(cols) if decode else None))
+    keys = ("kept", "n_additive", "n_chunks", "tiles_with_records", "tiles", "new_bytes", "replaced_bytes", "max_elems")
+    return dict(zip(keys, [int(v) for v in st])), cols
 
 
 def convert_to_scs_device(coo, C_, sigma, dtype=F64, fixed_permutation=None, permute_cols=True, device="cuda"):

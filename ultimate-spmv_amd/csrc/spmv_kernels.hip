@@ -204,13 +204,21 @@ __device__ __forceinline__ float ld_sys(const float *p) {
 // per non-zero.
 // ELEM: the tile's list holds single x ELEMENTS (uspmv_build_tlc_plan with line_shift 0): thread k gathers element k of the list into LDS -- one
 // 8-byte gather per DISTINCT column of the tile instead of one per entry; local indices = positions in the list.
-template <typename VT, int CT, bool NT, bool IDS, int SYNC = 0, bool I12 = false, bool ELEM = false>
+// ADD: the handle's additive chunk records (uspmv_additive_plan, host/tlc_plan.cpp; AddArgs).  A tile that carries intervals lays its x
+// window out in LDS in pre-sort column order -- it loads the lines of its list as ever and stores every element at the position of its
+// pre-sort column (gathering x[o2n[base + t]] interval by interval instead measured 0.90 against 0.72 ms on the 253^3 stencil: DESIGN 9.10)
+// -- and the local index of (lane i, slot j) of an additive chunk is R[i] + S[j]: one ushort per lane, then one 16-byte load of eight S per batch of eight slots, the
+// same address in all lanes of the chunk.  The other chunks of such a tile read one 16-bit position per entry into the same array, eight
+// per lane and batch, through the same loop; tiles without intervals run as without ADD.  Value loads, slot order and FMA chain are those of the other forms: bit-identical y.
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+template <typename VT, int CT, bool NT, bool IDS, int SYNC = 0, bool I12 = false, bool ELEM = false, bool ADD = false>
 __global__ void __launch_bounds__(1024) scs_spmv_tlc(const long n_chunks, const int C_rt, const int *__restrict__ chunk_ptrs,
         const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs, const VT *__restrict__ values,
         const VT *__restrict__ x_arg, VT *__restrict__ y, const int *__restrict__ tile_line_ptr,
         const int *__restrict__ tile_lines, const unsigned *__restrict__ c16_ptrs,
         const unsigned short *__restrict__ col16, const long x_len, const int *__restrict__ tile_ids,
-        const int xcd_remap, const long n_store, const StepArgs sa, const int *__restrict__ row_map) {
+        const int xcd_remap, const long n_store, const StepArgs sa, const int *__restrict__ row_map, const AddArgs aa) {
+    static_assert(!ADD || (SYNC == 0 && !ELEM && !IDS), "additive chunk records: the plain single-struct launch only");
     extern __shared__ __attribute__((aligned(16))) unsigned char tlc_smem[];
     VT *xs = (VT *)tlc_smem;
     constexpr int EPL = 16 / (int)sizeof(VT);   // elements per 16-byte load
@@ -268,7 +276,71 @@ __global__ void __launch_bounds__(1024) scs_spmv_tlc(const long n_chunks, const 
     unsigned q0 = 0;
     if (valid) { cs = chunk_ptrs[c]; L = chunk_lengths[c]; q0 = c16_ptrs[c]; }
     VT acc = VT(0);
-    if (nl > 0) {
+    bool add_tile = false;
+    if constexpr (ADD) {
+        const int iv0 = aa.iv_ptr[tile], niv = aa.iv_ptr[tile + 1] - iv0;
+        add_tile = niv > 0;
+        if (add_tile) {
+            // the tile's x lines as without ADD (coalesced 16-byte loads over its line list), each element then stored at the LDS position of
+            // its pre-sort column: aa.cmap[column] looked up in the tile's intervals (first column, length, first LDS element: wave-uniform
+            // loads; a copy of the table in LDS measured 10 % slower).  Line-mates no entry refers to may fall outside: skipped.
+            typedef int ivec_t __attribute__((ext_vector_type(EPL)));
+            const int sub = threadIdx.x % LPL, lk = threadIdx.x / LPL;
+            for (int k = lk; k < nl; k += blockDim.x / LPL) {
+                const long idx = (long)tile_lines[lp0 + k] * 16 + sub * EPL;
+                vec_t v;
+                ivec_t pc;
+                if (idx + EPL <= x_len) {
+                    v = *(const vec_t *)(x + idx);
+                    pc = *(const ivec_t *)(aa.cmap + idx);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < EPL; ++e) { const bool in = idx + e < x_len; v[e] = in ? x[idx + e] : VT(0); pc[e] = in ? aa.cmap[idx + e] : -1; }
+                }
+                int pos[EPL];
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) pos[e] = -1;
+                for (int q = 0; q < niv; ++q) {
+                    const int base = aa.iv[4 * (iv0 + q)], len = aa.iv[4 * (iv0 + q) + 1], off = aa.iv[4 * (iv0 + q) + 2];
+#pragma unroll
+                    for (int e = 0; e < EPL; ++e)
+                        if (pc[e] >= base && pc[e] - base < len) pos[e] = off + pc[e] - base;
+                }
+#pragma unroll
+                for (int e = 0; e < EPL; ++e)
+                    if (pos[e] >= 0) xs[pos[e]] = v[e];
+            }
+            __syncthreads();
+            if (L > 0) {
+                const unsigned ap = aa.ptrs[c];
+                const unsigned short *rec = aa.rec + (long)(ap >> 1) * 8;
+                const VT *vp = values + (long)cs + i;
+                // one loop for both kinds (the two chunks of a wave may differ): 16 bytes of positions per batch of eight slots, S (the same
+                // address in all lanes of the chunk) above the lane's R, or the lane's own eight positions above 0
+                const bool addv = ap & 1u;
+                const unsigned R = addv ? (unsigned)rec[i] : 0u;
+                const u32x4_t *sp = addv ? (const u32x4_t *)(rec + C) : (const u32x4_t *)rec + i;
+                const long ss = addv ? 1 : C;
+                int p = 0;
+                for (; 8 * p + 8 <= L; ++p) {
+                    VT v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = ld_stream<NT>(vp + (long)(8 * p + u) * C);
+                    const u32x4_t s4 = ld_stream<NT>(sp + p * ss);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) acc = fma_t(v[u], xs[R + ((s4[u >> 1] >> (16 * (u & 1))) & 0xFFFFu)], acc);
+                }
+                if (8 * p < L) {                                 // the last batch holds fewer than eight slots
+                    const u32x4_t s4 = ld_stream<NT>(sp + p * ss);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        if (8 * p + u < L) acc = fma_t(ld_stream<NT>(vp + (long)(8 * p + u) * C), xs[R + ((s4[u >> 1] >> (16 * (u & 1))) & 0xFFFFu)], acc);
+                }
+            }
+        }
+    }
+    if (add_tile) {                                          // (done above)
+    } else if (nl > 0) {
         const int sub = threadIdx.x % LPL, lk = threadIdx.x / LPL;
         if constexpr (ELEM) {
             for (int k = threadIdx.x; k < nl; k += blockDim.x) {
@@ -506,9 +578,17 @@ template <typename VT>
 int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, const VT *x, VT *y, hipStream_t st) {
     if (n_tiles == 0) return USPMV_OK;
     const int C = (int)A->C;
-    const unsigned grid = (unsigned)n_tiles;
+    unsigned grid = (unsigned)n_tiles;
     const bool elem = A->tlc.elem;
-    const size_t lds = (size_t)A->tlc.max_lines * (elem ? 1 : 16) * sizeof(VT);
+    // (additive chunk records: tlc_planner.hip tlc_additive_install; the launches over tile lists keep to the local indices)
+    const bool add = A->tlc.add_ptrs != nullptr && !elem && !tile_ids && !A->tlc.row_map;
+    const size_t lds = std::max((size_t)A->tlc.max_lines * (elem ? 1 : 16), add ? (size_t)A->tlc.add_max_elems : (size_t)0) * sizeof(VT);
+    const AddArgs aa = add ? AddArgs{A->tlc.add_iv_ptr, A->tlc.add_iv, A->tlc.add_cmap, A->tlc.add_ptrs, A->tlc.add_rec} : AddArgs{};
+    // (records on tiles of their own size: every tile carries intervals, and the launch walks their line lists instead of the plan's)
+    const bool own_tiles = add && A->tlc.add_line_ptr != nullptr;
+    const int block = own_tiles ? A->tlc.add_tile_rows : A->tlc.tile_rows;
+    const int *lptr = own_tiles ? A->tlc.add_line_ptr : A->tlc.line_ptr, *llist = own_tiles ? A->tlc.add_lines : A->tlc.lines;
+    if (own_tiles) grid = (unsigned)A->tlc.add_n_tiles;
     const bool i12 = A->tlc.col12 != nullptr;                 // (12-bit local indices: tlc_planner.hip tlc_pack12)
     const unsigned *iptrs = i12 ? A->tlc.c12_ptrs : A->tlc.c16_ptrs;
     const unsigned short *idata = i12 ? (const unsigned short *)A->tlc.col12 : A->tlc.col16;
@@ -516,10 +596,11 @@ int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, cons
     do {                                                                                                              \
         auto kfn = i12 ? scs_spmv_tlc<VT, CTV, NTV, IDSV, 0, true> : scs_spmv_tlc<VT, CTV, NTV, IDSV>;                \
         if (elem) kfn = i12 ? scs_spmv_tlc<VT, CTV, NTV, IDSV, 0, true, true> : scs_spmv_tlc<VT, CTV, NTV, IDSV, 0, false, true>; \
+        if constexpr (!IDSV) { if (add) kfn = i12 ? scs_spmv_tlc<VT, CTV, NTV, false, 0, true, false, true> : scs_spmv_tlc<VT, CTV, NTV, false, 0, false, false, true>; } \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(A->tlc.tile_rows), lds, st, (long)A->n_chunks, C, A->chunk_ptrs,        \
-                           A->chunk_lengths, A->tlc.cols ? A->tlc.cols : A->col_idxs, (const VT *)(A->tlc.values ? A->tlc.values : A->values), x, y, A->tlc.line_ptr, A->tlc.lines,   \
-                           iptrs, idata, (long)A->tlc.x_len, tile_ids, g_tune.xcd_remap, A->n_store, StepArgs{}, (const int *)A->tlc.row_map);  \
+        hipLaunchKernelGGL(kfn, dim3(grid), dim3(block), lds, st, (long)A->n_chunks, C, A->chunk_ptrs,        \
+                           A->chunk_lengths, A->tlc.cols ? A->tlc.cols : A->col_idxs, (const VT *)(A->tlc.values ? A->tlc.values : A->values), x, y, lptr, llist,   \
+                           iptrs, idata, (long)A->tlc.x_len, tile_ids, g_tune.xcd_remap, A->n_store, StepArgs{}, (const int *)A->tlc.row_map, aa);  \
     } while (0)
 #define TLC_LAUNCH_C(NTV, IDSV) do { if (C == 32) TLC_LAUNCH(32, NTV, IDSV); else TLC_LAUNCH(0, NTV, IDSV); } while (0)
     if (tile_ids) { if (g_tune.nontemporal) TLC_LAUNCH_C(true, true); else TLC_LAUNCH_C(false, true); }
@@ -546,7 +627,7 @@ int launch_spmv_tlc_step(const uspmv_dmat *A, const int *step_ids, const StepArg
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(kfn, dim3((unsigned)n), dim3(A->tlc.tile_rows), lds, st, (long)A->n_chunks, C, A->chunk_ptrs,  \
                            A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, A->tlc.line_ptr, A->tlc.lines,   \
-                           iptrs, idata, (long)A->tlc.x_len, step_ids, g_tune.xcd_remap, A->n_store, sa, (const int *)nullptr); \
+                           iptrs, idata, (long)A->tlc.x_len, step_ids, g_tune.xcd_remap, A->n_store, sa, (const int *)nullptr, AddArgs{}); \
     } while (0)
     if (sync == 1) { if (C == 32) TLC_STEP(32, 1); else TLC_STEP(0, 1); }
     else { if (C == 32) TLC_STEP(32, 2); else TLC_STEP(0, 2); }

@@ -127,8 +127,16 @@ int sweep_takes_over(uspmv_dmat *A, uspmv_dmat *B, const uspmv_scs *s, const usp
 // what scs_spmv_tlc then streams instead of the 16-bit array -- 1.5 instead of 2 bytes per non-zero.  The 16-bit array stays (the
 // adaptive-precision kernels, uspmv_dmat_plan_download and the plan digests read it).  cl: the chunk lengths when the caller has them on
 // the host, else they are copied back (4 bytes per chunk).
+// (the two rules of tlc_pack12, for the additive records' byte count as well: can the 12-bit array be built, is it kept)
+bool pack12_applies(bool elem, int max_lines, int64_t C, int64_t n_chunks) {
+    return g_tune.tlc_idx12 && !(elem ? max_lines > 4096 : max_lines > 256) && C >= 2 && C % 2 == 0 && n_chunks >= 1;
+}
+bool pack12_kept(int64_t n_elements, int64_t padded_rows) { return g_tune.tlc_idx12 == 2 || !((double)n_elements < 8.0 * (double)padded_rows); }
+// dwords of a chunk's 12-bit indices / ushorts of its 16-bit ones
+int64_t c12_dwords(int64_t L, int64_t C) { const int64_t ngt = (L + 3) / 4; return (ngt / 2) * 3 * C + (ngt & 1) * (C + C / 2); }
+
 int tlc_pack12(uspmv_dmat *A, const std::vector<int32_t> *cl, const char *who) {
-    if (!A->tlc.on || !g_tune.tlc_idx12 || (A->tlc.elem ? A->tlc.max_lines > 4096 : A->tlc.max_lines > 256) || A->C < 2 || A->C % 2 != 0 || A->n_chunks < 1) return USPMV_OK;
+    if (!A->tlc.on || !pack12_applies(A->tlc.elem, A->tlc.max_lines, A->C, A->n_chunks)) return USPMV_OK;
     std::vector<int32_t> own;
     if (!cl || (int64_t)cl->size() != A->n_chunks) {
         own.resize((size_t)A->n_chunks);
@@ -140,8 +148,7 @@ int tlc_pack12(uspmv_dmat *A, const std::vector<int32_t> *cl, const char *who) {
     int64_t tot = 0;                                             // dwords
     for (int64_t c = 0; c < nc; ++c) {
         p12[(size_t)c] = (uint32_t)tot;
-        const int64_t ngt = ((int64_t)(*cl)[(size_t)c] + 3) / 4;
-        tot += (ngt / 2) * 3 * C + (ngt & 1) * (C + C / 2);
+        tot += c12_dwords((*cl)[(size_t)c], C);
         if (tot > (int64_t)UINT32_MAX) return USPMV_OK;          // (too large for 32-bit offsets: the 16-bit array serves)
     }
     p12[(size_t)nc] = (uint32_t)tot;
@@ -158,7 +165,73 @@ int tlc_pack12(uspmv_dmat *A, const std::vector<int32_t> *cl, const char *who) {
     // 0.700 on a fast one; 304^3 between -15 % and +2 %).  The rule is a fixed one -- mean row length >= 8 -- and not a timing on the spot
     // (which was built first): a bench run, its counter passes and its profiler run must execute the same kernel, and a 1-2 % verdict
     // flips under a profiler's overhead.  "tlc_idx12" 2 keeps it regardless, 0 never builds it.
-    if (g_tune.tlc_idx12 != 2 && (double)A->n_elements < 8.0 * (double)(nc * C)) { A->tlc.c12_ptrs.reset(); A->tlc.col12.reset(); }
+    if (!pack12_kept(A->n_elements, nc * C)) { A->tlc.c12_ptrs.reset(); A->tlc.col12.reset(); }
+    return USPMV_OK;
+}
+
+// Additive chunk records (host/tlc_plan.cpp: uspmv_build_additive_plan) beside the local indices of a kept line plan: eligibility, the
+// keep rule and the install.  Eligible: one struct in dp or sp, the line plan on the caller's row order (not the element plan, not dealt
+// rows, not the sweep), n_rows == n_cols, the permutation at hand (the struct's own, or the caller's for the internal re-chunking) and not
+// a rank block of the distributed object (TlcPlanOpts::additive).
+bool additive_eligible(const uspmv_scs *s, const uspmv_tlc_plan &p, bool elem, const std::vector<int32_t> *n2o) {
+    if (!g_tune.tlc_additive || elem || !p.valid || p.line_shift != 4) return false;
+    if (s->dtype != USPMV_F64 && s->dtype != USPMV_F32) return false;
+    return s->n_rows == s->n_cols && s->n_rows > 0 && (int64_t)(n2o ? n2o->size() : s->new_to_old_idx.size()) >= s->n_rows;
+}
+// The keep rule, a fixed one in bytes like tlc_pack12's (a verdict timed on the spot flips under a profiler): the records of the
+// tiles that carry them plus 4 bytes per column of the map, counted once, against the local indices of those tiles as the kernel would stream
+// them otherwise (12 bits where that array is kept, else 16).  Kept at half or less; "tlc_additive" 2 keeps whatever could be built.
+struct AdditiveBytes { int64_t fresh = 0, replaced = 0; };
+AdditiveBytes additive_bytes(const uspmv_scs *s, const uspmv_additive_plan &a, bool idx12) {
+    AdditiveBytes b;
+    if (!a.valid) return b;
+    const int64_t C = s->C, T = a.tile_rows / C;
+    for (int64_t c = 0; c < s->n_chunks; ++c) {
+        if (a.iv_ptr[(size_t)(c / T) + 1] == a.iv_ptr[(size_t)(c / T)]) continue;
+        const int64_t L = s->chunk_lengths[(size_t)c];
+        b.replaced += idx12 ? 4 * c12_dwords(L, C) : 2 * ((L + 3) / 4) * 4 * C;
+    }
+    b.fresh = a.rec_bytes + 4 * (int64_t)a.cmap.size();
+    return b;
+}
+// Rows per tile of the records.  In pre-sort order all rows of a sigma window reach into the same intervals (the stencil: window + 2 lines per
+// plane), so a tile that is a whole window stages them once where two half-window tiles stage them twice: 0.695 against 0.804 ms on the 253^3
+// stencil, whose line plan is fastest at 256 rows.  Windows of 512 or 1024 rows that are larger than the line plan's tiles.
+int additive_tile_rows(const uspmv_scs *s, int line_plan_rows) {
+    return (s->sigma == 512 || s->sigma == 1024) && s->sigma > line_plan_rows && s->sigma % s->C == 0 ? (int)s->sigma : line_plan_rows;
+}
+// ... and at most five intervals per tile on average: every staged element is looked up in all of its tile's intervals.  The stencils
+// have 4.0 (three planes and the padding column) and gain 3-10 %; the KKT matrix has 7.1 and runs 16 % slower on its records although they
+// are a fifth of its local indices (tools/additive_probe.py).
+bool additive_kept(const uspmv_additive_plan &a, const AdditiveBytes &b) {
+    if (!a.valid || g_tune.tlc_additive == 2) return a.valid;
+    return 2 * b.fresh <= b.replaced && (int64_t)(a.iv.size() / 4) <= 5 * a.n_add_tiles;
+}
+
+int tlc_additive_install(uspmv_dmat *A, const uspmv_scs *s, const uspmv_tlc_plan &p, int max_lines, const std::vector<int32_t> *n2o, const char *who) {
+    if (!A->tlc.on || !additive_eligible(s, p, A->tlc.elem, n2o)) return USPMV_OK;
+    uspmv_additive_plan a;
+    if (int rc = uspmv_build_additive_plan(s, &p, max_lines * 16, &a, n2o, additive_tile_rows(s, p.tile_rows))) return rc;
+    const AdditiveBytes b = additive_bytes(s, a, A->tlc.col12 != nullptr);
+    if (verbose()) fprintf(stderr, "[uspmv] additive chunk records: valid=%d tiles=%lld of %lld chunks=%lld additive=%lld max_elems=%d tile_rows=%d records+map=%lld B against %lld B of local indices (columns %s) -> %s\n",
+                           (int)a.valid, (long long)a.n_add_tiles, (long long)a.n_tiles, (long long)a.n_chunks, (long long)a.n_additive, a.max_elems, a.tile_rows, (long long)b.fresh,
+                           (long long)b.replaced, a.cols_permuted ? "permuted" : "as they are", additive_kept(a, b) ? "kept" : "dropped");
+    if (!additive_kept(a, b)) return USPMV_OK;
+    auto &t = A->tlc;
+    hipError_t e = t.add_iv_ptr.upload(a.iv_ptr.data(), a.iv_ptr.size() * 4);
+    if (e == hipSuccess) e = t.add_iv.upload(a.iv.data(), a.iv.size() * 4);
+    if (e == hipSuccess) e = t.add_cmap.upload(a.cmap.data(), a.cmap.size() * 4);
+    if (e == hipSuccess) e = t.add_rec.upload(a.rec.data(), a.rec.size() * 2);
+    if (e == hipSuccess) e = t.add_ptrs.upload(a.rec_ptrs.data(), a.rec_ptrs.size() * 4);
+    if (e == hipSuccess && !a.line_ptr.empty()) e = t.add_line_ptr.upload(a.line_ptr.data(), a.line_ptr.size() * 4);
+    if (e == hipSuccess && !a.line_ptr.empty()) e = t.add_lines.upload(a.lines.data(), a.lines.size() * 4);
+    if (e != hipSuccess) {
+        t.add_line_ptr.reset(); t.add_lines.reset();
+        t.add_iv_ptr.reset(); t.add_iv.reset(); t.add_cmap.reset(); t.add_rec.reset(); t.add_ptrs.reset();
+        return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy of the additive chunk records failed: %s", who, hipGetErrorString(e));
+    }
+    t.add_max_elems = a.max_elems; t.add_chunks = a.n_chunks; t.add_additive = a.n_additive;
+    t.add_tile_rows = a.tile_rows; t.add_n_tiles = a.n_tiles;
     return USPMV_OK;
 }
 
@@ -528,7 +601,9 @@ int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPla
             uspmv_dmat_t *alt = nullptr;
             if (int rc2 = uspmv_dmat_upload(&r, &alt)) return rc2;
             alt->n_store = (long)(s->n_chunks * s->C);      // y of the caller has only the original padded rows
-            rc = dmat_optimize(alt, &r, max_lines, opts, n_tiles, n_staged);   // (C = 32: does not re-enter this branch)
+            TlcPlanOpts inner = opts;
+            inner.new_to_old = &s->new_to_old_idx;          // (same row order: the caller's permutation serves the re-chunked struct)
+            rc = dmat_optimize(alt, &r, max_lines, inner, n_tiles, n_staged);   // (C = 32: does not re-enter this branch)
             if (rc) { uspmv_dmat_free(alt); return rc; }
             A->alt = alt;
             return USPMV_OK;
@@ -614,12 +689,38 @@ int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPla
             return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
         }
     }
-    return tlc_pack12(A, &s->chunk_lengths, who);
+    if (int rc = tlc_pack12(A, &s->chunk_lengths, who)) return rc;
+    if (reordered || !opts.additive) return USPMV_OK;
+    return tlc_additive_install(A, s, p, max_lines, opts.new_to_old, who);
 }
 
 }  // namespace uspmv_dev
 
 extern "C" {
+
+int uspmv_additive_plan_probe(const uspmv_scs_t *s, int64_t stats[8], int32_t *cols) {
+    const char *who = "uspmv_additive_plan_probe";
+    if (!s || !stats) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct", who);
+    for (int k = 0; k < 8; ++k) stats[k] = 0;
+    if (cols) for (int64_t k = 0; k < s->n_elements; ++k) cols[k] = -1;
+    const int max_lines = line_budget(0, s->dtype, false);
+    uspmv_tlc_plan p;
+    if (int rc = uspmv_build_tlc_plan(s, nullptr, max_lines, plan_tile_rows(false), &p)) return rc;
+    stats[4] = p.n_tiles;
+    if (!additive_eligible(s, p, false, nullptr)) return USPMV_OK;
+    uspmv_additive_plan a;
+    if (int rc = uspmv_build_additive_plan(s, &p, max_lines * 16, &a, nullptr, additive_tile_rows(s, p.tile_rows))) return rc;
+    const bool idx12 = pack12_applies(false, p.max_lines_used, s->C, s->n_chunks) && pack12_kept(s->n_elements, s->n_chunks * s->C);
+    if (verbose()) fprintf(stderr, "[uspmv] additive probe: line plan tile_rows=%d max_lines=%d; records tile_rows=%d tiles=%lld with records=%lld intervals=%zu max_elems=%d\n", p.tile_rows, p.max_lines_used,
+                           a.tile_rows, (long long)a.n_tiles, (long long)a.n_add_tiles, a.iv.size() / 4, a.max_elems);
+    const AdditiveBytes b = additive_bytes(s, a, idx12);
+    stats[0] = additive_kept(a, b); stats[1] = a.n_additive; stats[2] = a.n_chunks; stats[3] = a.n_add_tiles;
+    stats[5] = b.fresh; stats[6] = b.replaced; stats[7] = a.max_elems;
+    if (a.valid) stats[4] = a.n_tiles;               // (the records' own tiles: whole sigma windows where additive_tile_rows says so)
+    if (cols && stats[0]) uspmv_additive_plan_decode(s, &a, cols);
+    return USPMV_OK;
+}
 
 int uspmv_dmat_optimize(uspmv_dmat_t *A, const uspmv_scs_t *s, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
     return dmat_optimize(A, s, max_lines, TlcPlanOpts{}, n_tiles, n_staged);

@@ -187,6 +187,7 @@ const TuneKey TUNE_KEYS[] = {
     {"tlc_auto_tile", &Tuning::tlc_auto_tile, flag},
     {"tlc_measure_tile", &Tuning::tlc_measure_tile, flag},
     {"tlc_idx12", &Tuning::tlc_idx12, clamped<0, 2>},
+    {"tlc_additive", &Tuning::tlc_additive, clamped<0, 2>},
     {"tlc_elem", &Tuning::tlc_elem, clamped<0, 2>},
     {"tlc_elem_rows", &Tuning::tlc_elem_rows, clamped<0>},
     {"tlc_elem_seg_rows", &Tuning::tlc_elem_seg_rows, clamped<65536>},
@@ -1330,6 +1331,15 @@ int uspmv_dmat_index_bits(const uspmv_dmat_t *A, int *bits) {
     if (!A || !bits) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_index_bits: NULL argument");
     const uspmv_dmat_t *M = (A->alt && g_tune.rechunk) ? A->alt : A;
     *bits = !M->tlc.on ? 0 : M->tlc.col12 ? 12 : 16;
+    return USPMV_OK;
+}
+
+int uspmv_dmat_additive_chunks(const uspmv_dmat_t *A, int64_t *n_additive, int64_t *n_chunks) {
+    if (!A || !n_additive || !n_chunks) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_additive_chunks: NULL argument");
+    const uspmv_dmat_t *M = (A->alt && g_tune.rechunk) ? A->alt : A;
+    const bool on = M->tlc.on && M->tlc.add_ptrs;
+    *n_additive = on ? M->tlc.add_additive : 0;
+    *n_chunks = on ? M->tlc.add_chunks : 0;
     return USPMV_OK;
 }
 

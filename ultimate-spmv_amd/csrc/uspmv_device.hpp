@@ -151,6 +151,15 @@ struct uspmv_dmat {
         // order and row_map[plan row] = row of y.  Null when the caller's row order is kept.
         DeviceBuf<void> values;
         DeviceBuf<int32_t> row_map, cols;     // (cols: the column indices in that order, for the few tiles that do not stage)
+        // additive chunk records (uspmv_additive_plan, host/tlc_plan.cpp; installed by tlc_planner.hip under "tlc_additive"): what the
+        // single-struct SpMV kernel streams instead of col12 / col16 in the tiles that carry intervals.  add_ptrs null: none.
+        DeviceBuf<int32_t> add_iv_ptr, add_iv, add_cmap;
+        DeviceBuf<uint32_t> add_ptrs;
+        DeviceBuf<uint16_t> add_rec;
+        DeviceBuf<int32_t> add_line_ptr, add_lines;   // the records' tiles where they are not the line plan's (add_tile_rows, add_n_tiles)
+        int add_max_elems = 0, add_tile_rows = 0;     // LDS elements of the fullest tile; rows per tile of the records
+        int64_t add_n_tiles = 0;
+        int64_t add_chunks = 0, add_additive = 0;   // chunks of the tiles with intervals / the additive ones among them
     } tlc;
     // block (SpMMV) plan: 64-row tiles, per tile the list of X rows it touches (uspmv_dmat_optimize_block)
     struct BlockPlan {
@@ -245,7 +254,9 @@ namespace uspmv_dev {
 // AND its tuning key say so: measure -- time 256 / 512 / 1024 rows per tile on large structs ("tlc_measure_tile"); elements -- fall to
 // the plan over single x elements ("tlc_elem"); deal_rows -- ... on rows dealt to the tiles by the matrix graph ("tlc_elem_rows"),
 // after which tile t no longer covers rows [t * tile_rows, (t + 1) * tile_rows) of the caller's order.
-struct TlcPlanOpts { bool measure = true, elements = true, deal_rows = true; };
+// additive -- the additive chunk records beside the local indices ("tlc_additive"; not for the rank blocks of the distributed object);
+// new_to_old: the permutation of the struct's rows where the struct does not carry it (the internal re-chunking of a narrow struct).
+struct TlcPlanOpts { bool measure = true, elements = true, deal_rows = true, additive = true; const std::vector<int32_t> *new_to_old = nullptr; };
 // uspmv_dmat_optimize with the options spelled out
 int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged);
 
@@ -268,6 +279,13 @@ struct StepArgs {
     int *defer = nullptr;          // [2][defer_cap] positions in the step list
     const void *stale = nullptr;   // value of x[pad_col] before the exchange
     int pad_col = -1;
+};
+
+// the additive chunk records as scs_spmv_tlc<..., ADD = true> takes them (uspmv_dmat::TlcPlan::add_*)
+struct AddArgs {
+    const int *iv_ptr = nullptr, *iv = nullptr, *cmap = nullptr;   // cmap[column of x] = pre-sort column
+    const unsigned *ptrs = nullptr;
+    const unsigned short *rec = nullptr;
 };
 
 constexpr int USPMV_SKIP_LEN = -4;     // (a multiple of four: no kernel sees a partial group or a tail in it)
@@ -340,6 +358,8 @@ struct Tuning {
     int tlc_elem_cap = 4096; // ... most elements a tile may list (4096: 32 KiB of doubles, local indices still fit 12 bits)
     int tlc_idx12 = 1;       // NEXT optimize: tile-local-column plans of <= 256 lines per tile also get their local indices packed to 12 bits: 0 = never,
                              // 1 = kept when the mean row length is >= 8, 2 = kept wherever it can be built
+    int tlc_additive = 1;    // NEXT uspmv_dmat_optimize (one struct with its permutation, square, line plan kept): additive chunk records beside the local
+                             // indices: 0 = never, 1 = kept when records + map are at most half of the index stream they replace, 2 = wherever they can be built
     int spmmv_reorder = 4;  // block plan's private copy of the entries (host planner): 1 = rows of equal-length chunks of a sigma window back in original order;
                             // 4 = on top of that, rows re-dealt to the tiles as FLAT patches of the matrix graph (grown along the slots of one phase
                             // around the diagonal: 7.9 instead of 11.9 staged X rows per row on config 3; kept only where a sample of tiles

@@ -899,7 +899,7 @@ int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_s
         //  -- 0.1785 / 0.1791 / 0.1822 ms -- and a 512-row tile = a whole sigma window always holds a padded chunk, i.e. no interior tile is left.
         //  Line tiles in the caller's row order: the tile classes below take tile t for rows [t * tile_rows, (t + 1) * tile_rows), and the
         //  step kernel has no element plan.)
-        const uspmv_dev::TlcPlanOpts as_is{/*measure=*/false, /*elements=*/false, /*deal_rows=*/false};
+        const uspmv_dev::TlcPlanOpts as_is{/*measure=*/false, /*elements=*/false, /*deal_rows=*/false, /*additive=*/false};
         rc = uspmv_dev::dmat_optimize(A, scs, 0, as_is, &n_tiles, &n_staged);
     }
     int tile_rows = 0;

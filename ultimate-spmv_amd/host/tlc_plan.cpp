@@ -148,6 +148,292 @@ int uspmv_build_tlc_plan(const uspmv_scs *s, const uspmv_scs *s2, int max_lines,
     return USPMV_OK;
 }
 
+// Additive chunk records.  The local indices of a line plan carry the scramble of the sigma sort (rows of equal length leave std::sort in
+// an arbitrary order, and the caller permutes the columns the same way): re-encoded in that numbering they do not shrink.  In the numbering
+// the sort STARTED from, a banded matrix has column - row equal over the 32 rows of almost every chunk.  So the tile's x window is laid out
+// in LDS in pre-sort order -- a few intervals of pre-sort columns; LDS element t of an interval holds x[o2n[base + t]], stored there by the
+// kernel as it loads the tile's x lines (position of cmap[column]) -- and an additive chunk stores one position per lane and one per slot
+// instead of one per entry.  Nothing is assumed about the caller: the candidate map (the struct's own
+// permutation, or the identity for columns that were left alone) is checked entry by entry, padding included, and every other chunk of the
+// tile keeps per-entry positions into the same LDS array.
+namespace {
+struct AddMaps {
+    const int32_t *n2o;      // row position -> pre-sort row (rows past n_rows: themselves)
+    const int32_t *cm;       // column -> pre-sort column, nullptr: the identity
+    int64_t n_rows;
+    int64_t row(int64_t r) const { return r < n_rows ? n2o[r] : r; }
+    int64_t col(int32_t c) const { return cm ? cm[c] : c; }
+};
+// the chunk's offsets d[j] = pre-sort column - pre-sort row when they are equal over all lanes in every slot (rr: pre-sort rows of the lanes)
+bool chunk_offsets(const uspmv_scs *s, const AddMaps &m, int64_t c, const int64_t *rr, int64_t *d) {
+    const int64_t C = s->C, cs = s->chunk_ptrs[(size_t)c], L = s->chunk_lengths[(size_t)c];
+    const int32_t *ci = s->col_idxs.data() + cs;
+    for (int64_t j = 0; j < L; ++j) {
+        const int64_t dj = m.col(ci[j * C]) - rr[0];
+        for (int64_t i = 1; i < C; ++i)
+            if (m.col(ci[j * C + i]) - rr[i] != dj) return false;
+        d[j] = dj;
+    }
+    return true;
+}
+// LDS position of a pre-sort column under the tile's intervals (iv: base, length pairs, ascending); -1: outside all of them
+int64_t add_pos(const int32_t *iv, int n_iv, int64_t p, int *which = nullptr) {
+    for (int k = 0; k < n_iv; ++k)
+        if (p >= iv[4 * k] && p < (int64_t)iv[4 * k] + iv[4 * k + 1]) { if (which) *which = k; return iv[4 * k + 2] + p - iv[4 * k]; }
+    return -1;
+}
+constexpr int ADD_MAX_IV = 16;      // intervals per tile
+constexpr int64_t ADD_HOLE = 32;    // unreferenced columns that are staged along rather than ending a run
+}  // namespace
+
+int uspmv_build_additive_plan(const uspmv_scs *s, const uspmv_tlc_plan *lp, int budget, uspmv_additive_plan *p, const std::vector<int32_t> *new_to_old, int tile_rows) {
+    *p = {};
+    const std::vector<int32_t> &n2o = new_to_old ? *new_to_old : s->new_to_old_idx;
+    const int64_t C = s->C, nc = s->n_chunks, n = s->n_rows;
+    if (!lp || !lp->valid || lp->line_shift != 4 || C < 8 || C % 8 != 0 || C > lp->tile_rows || nc < 1 || n < 1 || n != s->n_cols) return USPMV_OK;
+    if ((int64_t)n2o.size() < n || n > (int64_t)INT32_MAX || lp->x_len_min > n) return USPMV_OK;   // (x_len_min: no column beyond the map)
+    budget = std::min(budget, 65536);
+    // the struct's permutation, checked: o2n is built here as the inverse of new_to_old, not taken on trust
+    std::vector<int32_t> inv((size_t)n, -1);
+    for (int64_t r = 0; r < n; ++r) {
+        const int64_t o = n2o[(size_t)r];
+        if (o < 0 || o >= n || inv[(size_t)o] >= 0) return USPMV_OK;
+        inv[(size_t)o] = (int32_t)r;
+    }
+    // tiles of their own size (the caller's wish: the rows of a whole sigma window share their intervals) carry line lists of their own and
+    // only stand when every one of them gets intervals; else the records sit on the line plan's tiles and fall back to it tile by tile
+    const bool own_tiles = tile_rows > 0 && tile_rows != lp->tile_rows && tile_rows % C == 0 && tile_rows <= 1024 && lp->n_staged_tiles == lp->n_tiles;
+    if (!own_tiles) tile_rows = lp->tile_rows;
+    const int64_t T = tile_rows / C, nt = (nc + T - 1) / T;
+    p->tile_rows = tile_rows;
+    p->n_tiles = nt;
+    std::vector<std::vector<int32_t>> t_lines(own_tiles ? (size_t)nt : 0);
+    // which column map: the one under which more of a sample of the chunks is additive
+    AddMaps m{n2o.data(), n2o.data(), n};
+    {
+        const int64_t step = std::max<int64_t>(1, nc / 4096);
+        int64_t hits[2] = {0, 0};
+        for (int w = 0; w < 2; ++w) {
+            const AddMaps mw{m.n2o, w == 0 ? m.n2o : nullptr, n};
+            int64_t h = 0;
+#pragma omp parallel reduction(+ : h)
+            {
+                std::vector<int64_t> rr((size_t)C), d;
+#pragma omp for schedule(dynamic, 16)
+                for (int64_t c = 0; c < nc; c += step) {
+                    bool in_range = true;
+                    for (int64_t k = s->chunk_ptrs[(size_t)c]; k < s->chunk_ptrs[(size_t)c + 1]; ++k) in_range = in_range && s->col_idxs[(size_t)k] >= 0 && s->col_idxs[(size_t)k] < n;
+                    if (!in_range) continue;
+                    for (int64_t i = 0; i < C; ++i) rr[(size_t)i] = mw.row(c * C + i);
+                    d.resize((size_t)s->chunk_lengths[(size_t)c] + 1);
+                    h += chunk_offsets(s, mw, c, rr.data(), d.data());
+                }
+            }
+            hits[w] = h;
+        }
+        p->cols_permuted = hits[0] >= hits[1];
+        if (!p->cols_permuted) m.cm = nullptr;
+    }
+    // pass 1: per tile the intervals, per chunk the kind and the size of its record
+    std::vector<std::vector<int32_t>> t_iv((size_t)nt);
+    std::vector<uint32_t> units((size_t)nc, 0);          // record size in units of 16 bytes
+    std::vector<uint8_t> additive((size_t)nc, 0);
+    auto chunk_additive = [&](int64_t c, const int32_t *iv, int n_iv, int64_t *rr, int64_t *d, int64_t *rmin) -> bool {
+        const int64_t L = s->chunk_lengths[(size_t)c];
+        if (L < 1) return false;
+        int64_t lo = INT64_MAX, hi = INT64_MIN;
+        for (int64_t i = 0; i < C; ++i) { rr[i] = m.row(c * C + i); lo = std::min(lo, rr[i]); hi = std::max(hi, rr[i]); }
+        *rmin = lo;
+        if (hi - lo > 65535 || !chunk_offsets(s, m, c, rr, d)) return false;
+        for (int64_t j = 0; j < L; ++j) {                // the slot's entries of all lanes inside ONE interval (they are lo + d .. hi + d)
+            int ka = -1, kb = -2;
+            if (add_pos(iv, n_iv, lo + d[j], &ka) < 0 || add_pos(iv, n_iv, hi + d[j], &kb) < 0 || ka != kb) return false;
+        }
+        return true;
+    };
+#pragma omp parallel
+    {
+        std::vector<int64_t> cols, rr((size_t)C), d;
+        std::vector<std::pair<int64_t, int64_t>> gaps;   // (width, run in front of the gap)
+        std::vector<size_t> cb;                          // first column (index into cols) of every run, then cols.size()
+        std::vector<char> joined;
+#pragma omp for schedule(dynamic, 16)
+        for (int64_t t = 0; t < nt; ++t) {
+            if (!own_tiles && lp->tile_line_ptr[(size_t)t + 1] == lp->tile_line_ptr[(size_t)t]) continue;   // the line plan does not stage it either
+            const int64_t c0 = t * T, c1 = std::min<int64_t>(c0 + T, nc);
+            const int64_t e0 = s->chunk_ptrs[(size_t)c0], e1 = s->chunk_ptrs[(size_t)c1];
+            if (e1 <= e0) continue;
+            cols.clear();
+            bool in_range = true;
+            for (int64_t k = e0; k < e1; ++k) {
+                const int32_t col = s->col_idxs[(size_t)k];
+                if (col < 0 || col >= n) { in_range = false; break; }
+                cols.push_back(m.col(col));
+            }
+            if (!in_range) continue;
+            std::sort(cols.begin(), cols.end());
+            cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
+            // runs of referenced columns (holes of at most ADD_HOLE columns are staged along), joined wherever a slot of a chunk with equal
+            // offsets reaches across: its lanes' entries must share one interval.  Joined runs that overrun the budget fall apart again.
+            cb.clear();
+            cb.push_back(0);
+            for (size_t k = 1; k < cols.size(); ++k)
+                if (cols[k] - cols[k - 1] - 1 > ADD_HOLE) cb.push_back(k);
+            const size_t n_run = cb.size();
+            cb.push_back(cols.size());
+            joined.assign(n_run, 0);                         // run k joined to run k + 1
+            auto run_of = [&](int64_t pc) { return (size_t)(std::upper_bound(cb.begin(), cb.begin() + (long)n_run, (size_t)(std::lower_bound(cols.begin(), cols.end(), pc) - cols.begin())) - cb.begin()) - 1; };
+            for (int64_t c = c0; c < c1 && n_run > 1; ++c) {
+                const int64_t L = s->chunk_lengths[(size_t)c];
+                if (L < 1) continue;
+                int64_t lo = INT64_MAX, hi = INT64_MIN;
+                for (int64_t i = 0; i < C; ++i) { rr[(size_t)i] = m.row(c * C + i); lo = std::min(lo, rr[(size_t)i]); hi = std::max(hi, rr[(size_t)i]); }
+                d.resize((size_t)L + 1);
+                if (hi - lo > 65535 || !chunk_offsets(s, m, c, rr.data(), d.data())) continue;
+                for (int64_t j = 0; j < L; ++j)
+                    for (size_t k = run_of(lo + d[(size_t)j]), ke = run_of(hi + d[(size_t)j]); k < ke; ++k) joined[k] = 1;
+            }
+            std::vector<int32_t> iv;
+            int64_t total = 0;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                if (attempt == 1) joined.assign(n_run, 0);
+                size_t n_iv_now = 1;
+                gaps.clear();
+                for (size_t k = 0; k + 1 < n_run; ++k)
+                    if (!joined[k]) { ++n_iv_now; gaps.emplace_back(cols[cb[k + 1]] - cols[cb[k + 1] - 1] - 1, (int64_t)k); }
+                if (n_iv_now > (size_t)ADD_MAX_IV) {         // too many: the narrowest gaps close
+                    std::sort(gaps.begin(), gaps.end());
+                    for (size_t g = 0; g < n_iv_now - ADD_MAX_IV; ++g) joined[(size_t)gaps[g].second] = 1;
+                }
+                iv.clear();
+                total = 0;
+                for (size_t k = 0, first = 0; k < n_run; ++k) {
+                    if (k + 1 < n_run && joined[k]) continue;
+                    const int64_t len = cols[cb[k + 1] - 1] - cols[cb[first]] + 1;
+                    iv.push_back((int32_t)cols[cb[first]]); iv.push_back((int32_t)len); iv.push_back((int32_t)total); iv.push_back(0);
+                    total += len;
+                    first = k + 1;
+                }
+                if (total <= budget) break;
+            }
+            if (total > budget) continue;                // wider than the LDS budget: the tile keeps its line list
+            const int n_iv = (int)iv.size() / 4;
+            for (int64_t c = c0; c < c1; ++c) {
+                const int64_t L = s->chunk_lengths[(size_t)c];
+                d.resize((size_t)L + 1);
+                int64_t rmin = 0;
+                additive[(size_t)c] = chunk_additive(c, iv.data(), n_iv, rr.data(), d.data(), &rmin);
+                units[(size_t)c] = (uint32_t)(additive[(size_t)c] ? C / 8 + (L + 7) / 8 : ((L + 7) / 8) * C);
+            }
+            t_iv[(size_t)t] = std::move(iv);
+            if (own_tiles) {                             // the tile's x lines, as uspmv_build_tlc_plan lists them
+                auto &ln = t_lines[(size_t)t];
+                for (int64_t k = e0; k < e1; ++k) ln.push_back(s->col_idxs[(size_t)k] >> 4);
+                std::sort(ln.begin(), ln.end());
+                ln.erase(std::unique(ln.begin(), ln.end()), ln.end());
+            }
+        }
+    }
+    if (own_tiles) {
+        int64_t with = 0, n_lines = 0;
+        for (int64_t t = 0; t < nt; ++t) { with += !t_iv[(size_t)t].empty() || s->chunk_ptrs[(size_t)std::min<int64_t>(t * T + T, nc)] == s->chunk_ptrs[(size_t)(t * T)]; n_lines += (int64_t)t_lines[(size_t)t].size(); }
+        if (with != nt || n_lines > (int64_t)INT32_MAX) return uspmv_build_additive_plan(s, lp, budget, p, new_to_old, 0);
+        p->line_ptr.assign((size_t)nt + 1, 0);
+        p->lines.reserve((size_t)n_lines);
+        for (int64_t t = 0; t < nt; ++t) {
+            p->lines.insert(p->lines.end(), t_lines[(size_t)t].begin(), t_lines[(size_t)t].end());
+            p->line_ptr[(size_t)t + 1] = (int32_t)p->lines.size();
+        }
+    }
+    p->iv_ptr.assign((size_t)nt + 1, 0);
+    int64_t n_iv_all = 0;
+    for (int64_t t = 0; t < nt; ++t) {
+        p->iv_ptr[(size_t)t] = (int32_t)n_iv_all;
+        const int64_t k = (int64_t)t_iv[(size_t)t].size() / 4;
+        n_iv_all += k;
+        if (k == 0) continue;
+        ++p->n_add_tiles;
+        int64_t total = 0;
+        for (int64_t q = 0; q < k; ++q) total += t_iv[(size_t)t][(size_t)(4 * q + 1)];
+        p->max_elems = std::max<int>(p->max_elems, (int)total);
+        const int64_t c0 = t * T, c1 = std::min<int64_t>(c0 + T, nc);
+        p->n_chunks += c1 - c0;
+        for (int64_t c = c0; c < c1; ++c) p->n_additive += additive[(size_t)c];
+    }
+    p->iv_ptr[(size_t)nt] = (int32_t)n_iv_all;
+    if (p->n_add_tiles == 0 || n_iv_all > (int64_t)INT32_MAX / 4) return USPMV_OK;
+    p->iv.resize((size_t)(4 * n_iv_all));
+    for (int64_t t = 0; t < nt; ++t) std::copy(t_iv[(size_t)t].begin(), t_iv[(size_t)t].end(), p->iv.begin() + 4 * (int64_t)p->iv_ptr[(size_t)t]);
+    p->rec_ptrs.assign((size_t)nc, 0);
+    int64_t tot_units = 0;
+    for (int64_t c = 0; c < nc; ++c) {
+        p->rec_ptrs[(size_t)c] = (uint32_t)(tot_units << 1) | additive[(size_t)c];
+        tot_units += units[(size_t)c];
+        if (tot_units >= ((int64_t)1 << 31)) return USPMV_OK;   // too large for 31-bit offsets: no records
+    }
+    p->rec_bytes = tot_units * 16;
+    p->rec.assign((size_t)(tot_units * 8), 0);
+    // pass 2: the records
+#pragma omp parallel
+    {
+        std::vector<int64_t> rr((size_t)C), d;
+#pragma omp for schedule(dynamic, 16)
+        for (int64_t t = 0; t < nt; ++t) {
+            const int n_iv = p->iv_ptr[(size_t)t + 1] - p->iv_ptr[(size_t)t];
+            if (n_iv == 0) continue;
+            const int32_t *iv = p->iv.data() + 4 * (int64_t)p->iv_ptr[(size_t)t];
+            for (int64_t c = t * T; c < std::min<int64_t>(t * T + T, nc); ++c) {
+                const int64_t cs = s->chunk_ptrs[(size_t)c], L = s->chunk_lengths[(size_t)c];
+                uint16_t *q = p->rec.data() + (size_t)(p->rec_ptrs[(size_t)c] >> 1) * 8;
+                if (additive[(size_t)c]) {
+                    d.resize((size_t)L + 1);
+                    int64_t rmin = 0;
+                    chunk_additive(c, iv, n_iv, rr.data(), d.data(), &rmin);
+                    for (int64_t i = 0; i < C; ++i) q[i] = (uint16_t)(rr[(size_t)i] - rmin);
+                    for (int64_t j = 0; j < L; ++j) q[C + j] = (uint16_t)add_pos(iv, n_iv, rmin + d[(size_t)j]);
+                } else {
+                    for (int64_t j = 0; j < L; ++j)
+                        for (int64_t i = 0; i < C; ++i)
+                            q[((j / 8) * C + i) * 8 + (j % 8)] = (uint16_t)add_pos(iv, n_iv, m.col(s->col_idxs[(size_t)(cs + j * C + i)]));
+                }
+            }
+        }
+    }
+    if (p->cols_permuted) { p->o2n.swap(inv); p->cmap.assign(n2o.begin(), n2o.begin() + n); }
+    else { p->o2n.resize((size_t)n); for (int64_t k = 0; k < n; ++k) p->o2n[(size_t)k] = (int32_t)k; p->cmap = p->o2n; }
+    p->valid = true;
+    return USPMV_OK;
+}
+
+// What the kernel does with the records, on the host: interval list -> LDS position -> pre-sort column -> o2n.  Reads the plan's arrays
+// and the struct's chunk layout only, never its column indices.
+void uspmv_additive_plan_decode(const uspmv_scs *s, const uspmv_additive_plan *p, int32_t *out) {
+    const int64_t C = s->C, nc = s->n_chunks, T = p->tile_rows / C;
+    for (int64_t k = 0; k < s->n_elements; ++k) out[k] = -1;
+    if (!p->valid) return;
+    std::vector<int32_t> lds;                            // the tile's LDS image: which column of x every element holds
+    for (int64_t c = 0; c < nc; ++c) {
+        const int64_t t = c / T;
+        const int n_iv = p->iv_ptr[(size_t)t + 1] - p->iv_ptr[(size_t)t];
+        if (n_iv == 0) continue;
+        if (c % T == 0) {
+            const int32_t *iv = p->iv.data() + 4 * (int64_t)p->iv_ptr[(size_t)t];
+            lds.clear();
+            for (int k = 0; k < n_iv; ++k) {
+                lds.resize((size_t)iv[4 * k + 2], -2);           // (the interval's first LDS element as the table states it)
+                for (int32_t e = 0; e < iv[4 * k + 1]; ++e) lds.push_back(p->o2n[(size_t)(iv[4 * k] + e)]);
+            }
+        }
+        const int64_t cs = s->chunk_ptrs[(size_t)c], L = s->chunk_lengths[(size_t)c];
+        const uint16_t *q = p->rec.data() + (size_t)(p->rec_ptrs[(size_t)c] >> 1) * 8;
+        for (int64_t j = 0; j < L; ++j)
+            for (int64_t i = 0; i < C; ++i) {
+                const size_t l = (p->rec_ptrs[(size_t)c] & 1) ? (size_t)q[i] + q[C + j] : (size_t)q[((j / 8) * C + i) * 8 + (j % 8)];
+                out[cs + j * C + i] = l < lds.size() ? lds[l] : -2;
+            }
+    }
+}
+
 
 // Re-chunk a SELL-C-sigma struct with C in {1,2,4,8,16} into chunks of 32 rows WITHOUT touching the row
 // order: new chunk k = old chunks [k*32/C, (k+1)*32/C), its length the longest of theirs.  Row r keeps

@@ -106,6 +106,35 @@ struct uspmv_tlc_plan {
 int uspmv_build_tlc_plan(const uspmv_scs *s, const uspmv_scs *s2, int max_lines, int tile_rows, uspmv_tlc_plan *plan, int line_shift = 4,
                          const uspmv_scs *s3 = nullptr);
 
+// Additive chunk records (host copy), see host/tlc_plan.cpp: a third, derived index stream of a line plan.  The x window of a tile is laid
+// out in LDS in PRE-SORT column order (a few intervals of columns of the numbering the sigma sort started from), where
+// the entries of most chunks sit at (position of the lane's row) + (one offset per slot).
+struct uspmv_additive_plan {
+    bool valid = false;
+    bool cols_permuted = false;            // the column map that was taken: the struct's own permutation, or (false) the identity
+    int tile_rows = 256, max_elems = 0;    // max_elems: LDS elements of the fullest tile
+    int64_t n_tiles = 0, n_add_tiles = 0;  // tiles of the line plan / tiles that carry intervals
+    int64_t n_chunks = 0, n_additive = 0;  // chunks of the tiles with intervals / of these, the additive ones
+    int64_t rec_bytes = 0;                 // of `rec` (what the kernel streams instead of the local indices of those tiles)
+    std::vector<int32_t> line_ptr, lines;  // tile_rows other than the line plan's: the tiles' own x line lists (like uspmv_tlc_plan's), every tile with intervals
+    std::vector<int32_t> iv_ptr;           // n_tiles + 1: the tile's intervals (none: the tile keeps its line list)
+    std::vector<int32_t> iv;               // per interval four ints: first pre-sort column, length, first LDS element, 0
+    std::vector<uint32_t> rec_ptrs;        // per chunk: (offset into rec in units of 16 bytes) << 1 | additive
+    // additive chunk: R[C] (pre-sort position of the lane's row above the chunk's lowest), then S[slots rounded up to 8] (LDS position of the slot's
+    // entry in the lowest row): the entry of (lane i, slot j) reads LDS element R[i] + S[j].  Any other chunk: the LDS position of every entry,
+    // [batch of eight slots][row][slot % 8] -- a lane reads 16 bytes per batch in both kinds, so the two chunks of a wave share one loop.
+    std::vector<uint16_t> rec;
+    std::vector<int32_t> o2n;              // n_cols: pre-sort column -> column of x (the identity when !cols_permuted)
+    std::vector<int32_t> cmap;             // ... and its inverse, column of x -> pre-sort column: what the kernel stages through
+};
+// lp: the line plan of s (16-element lines); budget: most LDS elements a tile may take; new_to_old: the permutation of s's rows when s does not
+// carry it itself (the internal re-chunking of a narrow struct keeps the caller's row order); tile_rows: rows per tile the records are wanted
+// for (0: the line plan's), kept when every tile then gets intervals
+int uspmv_build_additive_plan(const uspmv_scs *s, const uspmv_tlc_plan *lp, int budget, uspmv_additive_plan *plan,
+                              const std::vector<int32_t> *new_to_old = nullptr, int tile_rows = 0);   // host/tlc_plan.cpp
+// the column of every entry (padding included) of the chunks whose tiles carry intervals, read back from the records alone; -1 elsewhere
+void uspmv_additive_plan_decode(const uspmv_scs *s, const uspmv_additive_plan *plan, int32_t *cols);                 // host/tlc_plan.cpp
+
 // Column-window sweep plan (host copy), see host/sweep_plan.cpp
 struct uspmv_sweep_plan {
     bool valid = false;

@@ -410,18 +410,27 @@ int uspmv_spmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspm
  * b >= 1, column v of Y is bit for bit what uspmv_spmv_ap_hp writes for column v of X: per (row, v) one chain per part in slot order with
  * the numerics above, then y = hi + hp, (hi + mid) + hp or (float)(sp + hp).  All n_rows_padded rows of every vector are written and
  * nothing else of Y; b = 1 is uspmv_spmv_ap_hp.  No workspace is used on any handle (uspmv_spmmv_x_prepared has nothing to skip here).
- * b in {2, 4, 8, 16} with 16-byte-aligned X and Y (and, column-major, ld * sizeof(element) a multiple of 16) on parts that carry one
- * shared tile-local-column plan (uspmv_dmat_optimize_ap_hp / _device_ap_hp) whose fullest tile fits the 160 KiB of LDS with two vectors
- * runs the staged kernel: per pass over the matrix entries the tile's X rows of BS vectors are staged in LDS straight from either layout
- * and every part streams sizeof(value) + 2 bytes per entry; BS is the largest of {8, 4, 2} that is at most b and fits the fullest tile,
- * b / BS passes inside one launch.  Everything else -- planless handles, handles with the column-window sweep plan, tuning "tlc" 0 or
- * "spmmv_variant" 1, other widths, unaligned vectors -- runs the generic lane-per-row kernel.  uspmv_spmmv_ap_hp_path reports which. */
+ * b in {2, 4, 8, 16} with 16-byte-aligned X and Y (and, column-major, ld * sizeof(element) a multiple of 16) takes one of two block
+ * kernels.  Parts that carry one shared column-window sweep plan (uspmv_dmat_optimize_ap_hp / _device_ap_hp on wide irregular rows,
+ * uspmv_dmat_optimize_sweep_ap_hp / _device_ap_hp) whose window leaves room for two vectors in the 160 KiB of LDS
+ * (uspmv_spmmv_ap_hp_sweep_vectors(b, wlog, x_dtype) >= 2: wlog <= 13 for double X, <= 14 for float X) run the block form of the sweep
+ * kernel under tuning "sweep" 1: every part's compacted stream is walked once per BS = uspmv_spmmv_ap_hp_sweep_vectors vectors, the
+ * windows of X staged in LDS straight from either layout, b / BS passes inside one launch, in one pass or several (every multi-pass
+ * combination of layout and number of passes measured ahead of the generic kernel);
+ * tiles that do not sweep run lane per row.  The planner's default window (2^14 doubles / 2^15 floats under "sweep_nbuf" 1) holds one
+ * vector: such handles keep the generic kernel until they are planned with a narrower window.  Parts that carry one shared
+ * tile-local-column plan (uspmv_dmat_optimize_ap_hp / _device_ap_hp) whose fullest tile fits the LDS with two vectors run the staged
+ * kernel: per pass over the matrix entries the tile's X rows of BS vectors are staged in LDS straight from either layout and every part
+ * streams sizeof(value) + 2 bytes per entry; BS is the largest of {8, 4, 2} that is at most b and fits the fullest tile, b / BS passes
+ * inside one launch.  Everything else -- planless handles, tuning "tlc" 0 / "sweep" 0 or "spmmv_variant" 1, other widths, unaligned
+ * vectors -- runs the generic lane-per-row kernel.  uspmv_spmmv_ap_hp_path reports which. */
 int uspmv_spmmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_X, void *d_Y, int b, int64_t ld,
                       int layout, void *stream);
 /* What uspmv_spmmv_ap_hp(hi, mid, hp, X, Y, b, ld, layout) would run for 16-byte-aligned X and Y, under the current tuning; the codes keep
  * the meaning they have in uspmv_spmmv_ap_path.  *path: 0 the generic lane-per-row kernel, 2 the staged kernel over the shared
- * tile-local-column plan (1 and 3 are not returned by this function yet).  *vectors_per_pass: the vectors per pass of the staged kernel,
- * else 0.  b = 1 reports uspmv_spmv_ap_hp's own choice with one vector per pass: 3 its sweep kernel, 2 its staged kernel, 0 lane per row.
+ * tile-local-column plan, 3 the column-window sweep kernel over the shared sweep plan (1 is not returned by this function).
+ * *vectors_per_pass: the vectors per pass of the staged or the sweep kernel, else 0.  b = 1 reports uspmv_spmv_ap_hp's own choice with
+ * one vector per pass: 3 its sweep kernel, 2 its staged kernel, 0 lane per row.
  * Same argument checks and error texts as uspmv_spmmv_ap_hp (under this function's name); nothing is launched. */
 int uspmv_spmmv_ap_hp_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout, int *path,
                            int *vectors_per_pass);
@@ -429,6 +438,18 @@ int uspmv_spmmv_ap_hp_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, cons
  * applies at width b whatever the matrix: two vectors of the fullest tile (16 X rows per line) in the 160 KiB of LDS -- 640 for
  * x_dtype USPMV_F64 and 1280 for USPMV_F32 at b in {2, 4, 8, 16}, 0 for every other b.  b < 1, another dtype or a NULL pointer is refused. */
 int uspmv_spmmv_ap_hp_plan_lines(int b, int x_dtype, int *max_lines);
+/* The vectors per pass the sweep kernel of uspmv_spmmv_ap_hp takes at width b on a plan whose windows hold 2^wlog elements of X
+ * (x_dtype USPMV_F64 for ap[dp_hp] and ap[dp_sp_hp], USPMV_F32 for ap[sp_hp]): the largest of {8, 4, 2} that is at most b, divides b
+ * and fits the 160 KiB of LDS with one window (2^wlog * sizeof(element) bytes per vector); 0 where the kernel does not apply (b not in
+ * {2, 4, 8, 16}, or not even two vectors fit):
+ *     wlog       <= 11   12   13   14   15
+ *     double X      8     4    2    0    0
+ *     float X       8     8    4    2    0
+ * A function of (b, wlog, x_dtype) alone, never of the matrix: callers use it to choose wlog for uspmv_dmat_optimize_sweep_ap_hp /
+ * _device_ap_hp (all b vectors in one pass: wlog 13 / 14 serves 2, 12 / 13 serves 4, 11 / 12 serves 8).  Several passes stay on the sweep kernel in
+ * both layouts, but a narrower window that takes more vectors per pass is faster from b = 4 on.
+ * b < 1, wlog outside 8..16, another x_dtype or a NULL pointer is refused (USPMV_ERR_INVALID). */
+int uspmv_spmmv_ap_hp_sweep_vectors(int b, int wlog, int x_dtype, int *vectors);
 
 /* Raw-array forms with the argument lists of the library kernels of code/interface.hpp
  * (uspmv_scs_gpu :1766-1793, uspmv_scs_c_gpu :1835-1867, uspmv_csr_gpu :1741-1760). */

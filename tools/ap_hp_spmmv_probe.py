@@ -17,6 +17,11 @@ the path uspmv_spmmv_ap_hp_path reports, and the bytes the staged kernel streams
 arrays, every tile's lines of X rows once per vector, Y) over the time over 8 TB/s.
 
     python tools/ap_hp_spmmv_probe.py [--kind dp_hp --kind dp_sp_hp --b 4 --b 8 --layout rowwise --reps 100 --rounds 3 --out probe.jsonl]
+
+--sweep: the block sweep kernel over the parts' shared column-window sweep plan (path 3) instead, on the banded-random matrix of DESIGN
+5.6 (500 000 x 140 over +-50 000 columns, 10 decades, SELL-32-512, t1 / t2 the 0.7 / 0.35 quantiles), see sweep_vs_generic.
+
+    python tools/ap_hp_spmmv_probe.py --sweep [--kind sp_hp --b 2 --layout rowwise --reps 200 --rounds 3 --out probe.jsonl]
 """
 import argparse
 import json
@@ -56,6 +61,80 @@ def _time(t, fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def sweep_vs_generic(pkg, t, a, out):
+    """(a) spmmv_ap_hp, (g) the same call under tuning "sweep" 0 -- the generic lane-per-row kernel, what ran before the block sweep
+    kernel existed --, (b) b x spmv_ap_hp on these handles, (b0) b x spmv_ap_hp on default-planned handles (the single-vector kernel at
+    its best), (a) once more for the A/A spread; alternated on the same handles in every round.  Plans: every window at which
+    uspmv_spmmv_ap_hp_sweep_vectors names more vectors of this b per pass than at the next wider one, from the widest that holds two,
+    built on the device (the arrays of the host planner, tests/test_gpu_sweep_ap_hp.py).  --tile-rows: the plan's rows per tile (0: the
+    planner's default)."""
+    m = pkg.gen_banded_random(500000, 140, 50000, magnitude_decades=10.0)
+    v = np.abs(np.asarray(m.arrays()[2]))
+    v = v[(v > 0) & np.isfinite(v)]
+    t1, t2 = float(np.quantile(v, 0.7)), float(np.quantile(v, 0.35))
+    del v
+    nnz = m.nnz
+    vs = {pkg.F64: 8, pkg.F32: 4, pkg.F16: 2}
+    for kind in a.kind or ["dp_hp", "sp_hp", "dp_sp_hp"]:
+        hi, mid, hp = pkg.partition_precisions_hp(m, kind, t1, t2)
+        xdt = pkg.F32 if kind == "sp_hp" else pkg.F64
+        st = _build(pkg, [hi, mid, hp], [xdt, pkg.F32, pkg.F16])
+        del hi, mid, hp
+        n = st[0].n_rows_padded
+        tdt = t.float32 if kind == "sp_hp" else t.float64
+        H0 = [pkg.DeviceMatrix(s) if s is not None else None for s in st]
+        pkg.optimize_device_ap_hp(H0[0], H0[1], H0[2])
+        for b in a.b or [2, 4, 8, 16]:
+            windows = [w for w in range(8, 16) if pkg.spmmv_ap_hp_sweep_vectors(b, w, xdt) > pkg.spmmv_ap_hp_sweep_vectors(b, w + 1, xdt)]
+            X = t.ones(b * n, dtype=tdt, device="cuda"); Y = t.zeros_like(X)
+            alg = sum(s.n_elements * (vs[s.dtype] + 4) + 8 * s.n_chunks for s in st if s is not None) + 2 * vs[xdt] * b * n
+            for wlog in sorted(windows, reverse=True):
+                H = [pkg.DeviceMatrix(s) if s is not None else None for s in st]
+                tiles, swept = pkg.optimize_sweep_device_ap_hp(H[0], H[1], H[2], wlog, a.tile_rows)
+                meta = H[0].sweep_plan_digest()[1]
+                for layout in a.layout or ["rowwise", "colwise"]:
+                    lay = pkg.ROWWISE if layout == "rowwise" else pkg.COLWISE
+                    path, vec = pkg.spmmv_ap_hp_path(H[0], H[1], H[2], b, n, lay)
+                    fa = lambda: pkg.spmmv_ap_hp(H[0], H[1], H[2], X, Y, b, n, lay)           # noqa: E731
+                    fb = lambda: [pkg.spmv_ap_hp(H[0], H[1], H[2], X, Y) for _ in range(b)]   # noqa: E731
+                    fb0 = lambda: [pkg.spmv_ap_hp(H0[0], H0[1], H0[2], X, Y) for _ in range(b)]   # noqa: E731
+                    ta, tg, tb, tb0, ta2 = [], [], [], [], []
+                    for _ in range(a.rounds):
+                        ta.append(_time(t, fa, a.reps))
+                        pkg.set_tuning(sweep=0)
+                        try:
+                            path_g = pkg.spmmv_ap_hp_path(H[0], H[1], H[2], b, n, lay)[0]
+                            tg.append(_time(t, fa, a.reps))
+                        finally:
+                            pkg.set_tuning(sweep=1)
+                        tb.append(_time(t, fb, max(1, a.reps // b)))
+                        tb0.append(_time(t, fb0, max(1, a.reps // b)))
+                        ta2.append(_time(t, fa, a.reps))
+                    ms_a, ms_g, ms_b, ms_b0 = (float(np.median(q)) for q in (ta, tg, tb, tb0))
+                    spread = max(ta + ta2) - min(ta + ta2)
+                    rec = dict(matrix="banded500k", config="sweep_vs_generic", kind=kind, b=b, layout=layout, nnz=nnz, n_rows_padded=n, t1=t1,
+                               t2=t2 if kind == "dp_sp_hp" else None, part_elements=[s.n_elements if s is not None else 0 for s in st],
+                               wlog=int(meta[2]), tile_rows=int(meta[1]), tiles=tiles, tiles_swept=swept, path=path, vectors_per_pass=vec,
+                               passes=b // vec if vec else 0, kernel=("generic", "gather", "staged", "sweep")[path], path_sweep_off=path_g,
+                               reps=a.reps, rounds=a.rounds, ms_a_spmmv_ap_hp=round(ms_a, 4), ms_g_sweep_off=round(ms_g, 4),
+                               ms_b_times_spmv_ap_hp=round(ms_b, 4), ms_b0_times_spmv_ap_hp_default_plan=round(ms_b0, 4),
+                               ms_a_again=round(float(np.median(ta2)), 4), aa_spread_ms=round(spread, 4), g_over_a=round(ms_g / ms_a, 3),
+                               b_over_a=round(ms_b / ms_a, 3), b0_over_a=round(ms_b0 / ms_a, 3),
+                               a_ahead_of_g_by_more_than_spread=bool(ms_g - ms_a > spread), a_ahead_of_b_by_more_than_spread=bool(ms_b - ms_a > spread),
+                               a_ahead_of_b0_by_more_than_spread=bool(ms_b0 - ms_a > spread), algorithmic_bytes=alg,
+                               algorithmic_bytes_over_time_over_8TBs=round(alg / (ms_a * 1e-3) / HBM, 3),
+                               ms_rounds=dict(a=[round(q, 4) for q in ta], g=[round(q, 4) for q in tg], b=[round(q, 4) for q in tb],
+                                              b0=[round(q, 4) for q in tb0], a_again=[round(q, 4) for q in ta2]))
+                    line = json.dumps(rec)
+                    print(line, flush=True)
+                    if out: out.write(line + "\n"); out.flush()
+                del H
+            del X, Y
+            t.cuda.synchronize()
+            t.cuda.empty_cache()
+        del st, H0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", action="append", default=[])
@@ -64,12 +143,19 @@ def main():
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--no-pair", action="store_true", help="skip (c), the ap[dp_sp] pair")
+    ap.add_argument("--sweep", action="store_true", help="only: the block sweep kernel over the shared sweep plan against the generic kernel and "
+                                                         "b x spmv_ap_hp on the same handles (sweep_vs_generic, banded-random 500 k x 140)")
+    ap.add_argument("--tile-rows", type=int, default=0, help="--sweep: rows per tile of the plans (0: the planner's default)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch as t
     pkg = ge.load_package()
     t.cuda.set_device(0)
     out = open(a.out, "a") if a.out else None
+    if a.sweep:
+        sweep_vs_generic(pkg, t, a, out)
+        if out: out.close()
+        return
     m = pkg.gen_stencil27(74, 74, 74, 5, magnitude_decades=8.0)
     v = np.abs(np.asarray(m.arrays()[2]))
     t1, t2 = float(np.quantile(v, 0.8)), float(np.quantile(v, 0.4))

@@ -79,6 +79,7 @@ _SIGS = {
     "uspmv_spmmv_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
     "uspmv_spmmv_ap_hp_path": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "uspmv_spmmv_ap_hp_plan_lines": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "uspmv_spmmv_ap_hp_sweep_vectors": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "uspmv_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "uspmv_set_device": (C.c_int, [C.c_int]),
     "uspmv_stream_synchronize": (C.c_int, [_vp]),
@@ -1249,8 +1250,8 @@ def spmmv_ap_hp(A_hi, A_mid, A_hp, X, Y, b, ld, layout=COLWISE, stream=None):
 
 def spmmv_ap_hp_path(A_hi, A_mid, A_hp, b, ld, layout=COLWISE):
     """(path, vectors) that spmmv_ap_hp would take for 16-byte-aligned X / Y under the current tuning (uspmv_spmmv_ap_hp_path): path 0
-    generic lane per row, 2 staged over the shared line plan (b = 1: spmv_ap_hp's own 3 sweep / 2 staged / 0); vectors per pass of the
-    staged kernel, else 0."""
+    generic lane per row, 2 staged over the shared line plan, 3 column-window sweep (b = 1: spmv_ap_hp's own 3 sweep / 2 staged / 0);
+    vectors per pass of the staged / sweep kernel, else 0."""
     path, vec = C.c_int(), C.c_int()
     _ck(lib().uspmv_spmmv_ap_hp_path(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, int(b), int(ld), int(layout), C.byref(path),
                                      C.byref(vec)))
@@ -1262,6 +1263,14 @@ def spmmv_ap_hp_plan_lines(b, dtype):
     `dtype` (640 for F64, 1280 for F32 at b in {2, 4, 8, 16}); 0: no staged kernel for that b."""
     n = C.c_int()
     _ck(lib().uspmv_spmmv_ap_hp_plan_lines(int(b), int(dtype), C.byref(n)))
+    return n.value
+
+
+def spmmv_ap_hp_sweep_vectors(b, wlog, x_dtype):
+    """Vectors per pass of spmmv_ap_hp's sweep kernel at width b on a plan with windows of 2^wlog elements of X of `x_dtype` (F64 | F32);
+    0: it does not apply there."""
+    n = C.c_int()
+    _ck(lib().uspmv_spmmv_ap_hp_sweep_vectors(int(b), int(wlog), int(x_dtype), C.byref(n)))
     return n.value
 
 

@@ -320,15 +320,26 @@ void launch_ap_hp_tlc(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT 
 }
 
 // What uspmv_spmmv_ap_hp runs for b >= 2: the ONE predicate behind the launch and behind uspmv_spmmv_ap_hp_path.  The codes are
-// uspmv_spmmv_ap_path's: 0 the generic lane-per-row kernel, 2 the staged kernel (bs: its vectors per pass, else 0); 1 and 3 have no hp
-// kernel yet.
-enum { AP_HP_PATH_GENERIC = 0, AP_HP_PATH_STAGED = 2 };
+// uspmv_spmmv_ap_path's: 0 the generic lane-per-row kernel, 2 the staged kernel, 3 the column-window sweep kernel (bs: the vectors per
+// pass of the staged / sweep kernel, else 0); 1 has no hp kernel.
+// The sweep kernel (ap_hp_spmmv_sweep.hip) takes parts that carry one shared sweep plan -- spmv_ap_hp_path's test -- under "sweep" 1
+// wherever the plan's window leaves room for two vectors in LDS (spmmv_ap_hp_sweep_vectors) and the threads / rows-per-lane shape is
+// one it serves, in one pass or several.
+enum { AP_HP_PATH_GENERIC = 0, AP_HP_PATH_STAGED = 2, AP_HP_PATH_SWEEP = 3 };
 struct ApHpBlockPath { int path, bs; };
 
 ApHpBlockPath ap_hp_block_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, int b, long ld, int layout, bool aligned16) {
     if (g_tune.spmmv_variant == 1 || !aligned16 || (b != 2 && b != 4 && b != 8 && b != 16)) return {AP_HP_PATH_GENERIC, 0};
     if (layout != USPMV_ROWWISE && ((size_t)ld * hp_x_bytes(hi)) % 16 != 0) return {AP_HP_PATH_GENERIC, 0};   // (16-byte pieces of the columns)
-    if (hi->sw.on) return {AP_HP_PATH_GENERIC, 0};           // the column-window sweep plan has no block form for hp parts
+    if (hi->sw.on) {
+        const uint64_t sid = hi->sw.plan_id;
+        const bool shared = hi->sw.tile_ids && hi->sw.n_parts == (mid ? 3 : 2) && hp->sw.on && hp->sw.plan_id == sid &&
+                            (!mid || (mid->sw.on && mid->sw.plan_id == sid));
+        if (!shared || !g_tune.sweep) return {AP_HP_PATH_GENERIC, 0};
+        const int bs = spmmv_ap_hp_sweep_bs(hi, b);
+        if (bs < 2) return {AP_HP_PATH_GENERIC, 0};          // not even two vectors of a window fit LDS (the planner's default window)
+        return {AP_HP_PATH_SWEEP, bs};
+    }
     const uint64_t id = hi->tlc.plan_id;
     const bool planned = hi->tlc.on && id != 0 && hp->tlc.on && hp->tlc.plan_id == id && (!mid || (mid->tlc.on && mid->tlc.plan_id == id));
     if (!planned || !g_tune.tlc || hi->tlc.max_lines < 1) return {AP_HP_PATH_GENERIC, 0};
@@ -342,6 +353,7 @@ int launch_ap_hp_block(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_
                        hipStream_t st) {
     const ApHpParts P = ap_hp_parts(hi, mid, hp);
     const ApHpBlockPath p = ap_hp_block_path(hi, mid, hp, b, ld, layout, ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0));
+    if (p.path == AP_HP_PATH_SWEEP) return launch_spmmv_ap_hp_sweep(hi, mid, hp, X, Y, b, ld, layout != USPMV_ROWWISE, p.bs, st);
     if (p.path == AP_HP_PATH_STAGED) {
         const bool col = layout != USPMV_ROWWISE;
         switch (b) {

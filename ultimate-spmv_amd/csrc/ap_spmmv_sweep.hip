@@ -26,38 +26,6 @@ constexpr size_t APSW_LDS = 160 * 1024;   // all the LDS a gfx950 workgroup can 
 // rounds per batch (profiles/ap_spmmv_sweep/resource_usage.txt).
 constexpr int apsw_group_rows(int bs) { return bs == 2 ? 4 : 2; }
 
-// One round of one chain for BS vectors: BS FMAs under the round's lane mask (EXEC), see masked_fma_batch.  All lanes of the wave are
-// active around the call.
-template <int BS>
-__device__ __forceinline__ void masked_fma_round(double (&a)[BS], const double v, const double (&x)[BS], const unsigned long long m) {
-    static_assert(BS == 2 || BS == 4 || BS == 8, "2, 4 or 8 vectors per pass");
-    unsigned long long save;
-    if constexpr (BS == 2)
-        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
-                     "v_fmac_f64 %[a0], %[v], %[x0]\n\tv_fmac_f64 %[a1], %[v], %[x1]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [sv] "=&s"(save)
-                     : [m] "s"(m), [v] "v"(v), [x0] "v"(x[0]), [x1] "v"(x[1]));
-    else if constexpr (BS == 4)
-        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
-                     "v_fmac_f64 %[a0], %[v], %[x0]\n\tv_fmac_f64 %[a1], %[v], %[x1]\n\t"
-                     "v_fmac_f64 %[a2], %[v], %[x2]\n\tv_fmac_f64 %[a3], %[v], %[x3]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [sv] "=&s"(save)
-                     : [m] "s"(m), [v] "v"(v), [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]));
-    else
-        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
-                     "v_fmac_f64 %[a0], %[v], %[x0]\n\tv_fmac_f64 %[a1], %[v], %[x1]\n\t"
-                     "v_fmac_f64 %[a2], %[v], %[x2]\n\tv_fmac_f64 %[a3], %[v], %[x3]\n\t"
-                     "v_fmac_f64 %[a4], %[v], %[x4]\n\tv_fmac_f64 %[a5], %[v], %[x5]\n\t"
-                     "v_fmac_f64 %[a6], %[v], %[x6]\n\tv_fmac_f64 %[a7], %[v], %[x7]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [a4] "+v"(a[4]), [a5] "+v"(a[5]),
-                       [a6] "+v"(a[6]), [a7] "+v"(a[7]), [sv] "=&s"(save)
-                     : [m] "s"(m), [v] "v"(v), [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]),
-                       [x5] "v"(x[5]), [x6] "v"(x[6]), [x7] "v"(x[7]));
-}
-
 // the BS operands of window element i: one X row of the row-major image, or one element of each plane
 template <int BS, bool XCOL>
 __device__ __forceinline__ void window_x(const double *win, const int wlog, const unsigned i, double (&x)[BS]) {

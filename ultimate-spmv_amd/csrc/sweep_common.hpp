@@ -110,4 +110,68 @@ __device__ __forceinline__ void masked_add_batch(double &acc, const double (&t)[
                      : [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]), [t0] "v"(t[0]), [t1] "v"(t[1]), [t2] "v"(t[2]), [t3] "v"(t[3]));
 }
 
+// The block kernels (ap_spmmv_sweep.hip, ap_hp_spmmv_sweep.hip): one round of one chain for BS vectors: BS FMAs under the round's lane mask (EXEC), see masked_fma_batch.  All lanes of the wave are
+// active around the call.
+template <int BS>
+__device__ __forceinline__ void masked_fma_round(double (&a)[BS], const double v, const double (&x)[BS], const unsigned long long m) {
+    static_assert(BS == 2 || BS == 4 || BS == 8, "2, 4 or 8 vectors per pass");
+    unsigned long long save;
+    if constexpr (BS == 2)
+        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
+                     "v_fmac_f64 %[a0], %[v], %[x0]\n\tv_fmac_f64 %[a1], %[v], %[x1]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [sv] "=&s"(save)
+                     : [m] "s"(m), [v] "v"(v), [x0] "v"(x[0]), [x1] "v"(x[1]));
+    else if constexpr (BS == 4)
+        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
+                     "v_fmac_f64 %[a0], %[v], %[x0]\n\tv_fmac_f64 %[a1], %[v], %[x1]\n\t"
+                     "v_fmac_f64 %[a2], %[v], %[x2]\n\tv_fmac_f64 %[a3], %[v], %[x3]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [sv] "=&s"(save)
+                     : [m] "s"(m), [v] "v"(v), [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]));
+    else
+        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
+                     "v_fmac_f64 %[a0], %[v], %[x0]\n\tv_fmac_f64 %[a1], %[v], %[x1]\n\t"
+                     "v_fmac_f64 %[a2], %[v], %[x2]\n\tv_fmac_f64 %[a3], %[v], %[x3]\n\t"
+                     "v_fmac_f64 %[a4], %[v], %[x4]\n\tv_fmac_f64 %[a5], %[v], %[x5]\n\t"
+                     "v_fmac_f64 %[a6], %[v], %[x6]\n\tv_fmac_f64 %[a7], %[v], %[x7]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [a4] "+v"(a[4]), [a5] "+v"(a[5]),
+                       [a6] "+v"(a[6]), [a7] "+v"(a[7]), [sv] "=&s"(save)
+                     : [m] "s"(m), [v] "v"(v), [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]),
+                       [x5] "v"(x[5]), [x6] "v"(x[6]), [x7] "v"(x[7]));
+}
+
+// ... and of one chain whose step is not an FMA (a float x: the products are rounded to float first): BS additions of the finished
+// terms under the round's lane mask, see masked_add_batch.
+template <int BS>
+__device__ __forceinline__ void masked_add_round(double (&a)[BS], const double (&t)[BS], const unsigned long long m) {
+    static_assert(BS == 2 || BS == 4 || BS == 8, "2, 4 or 8 vectors per pass");
+    unsigned long long save;
+    if constexpr (BS == 2)
+        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
+                     "v_add_f64 %[a0], %[a0], %[t0]\n\tv_add_f64 %[a1], %[a1], %[t1]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [sv] "=&s"(save)
+                     : [m] "s"(m), [t0] "v"(t[0]), [t1] "v"(t[1]));
+    else if constexpr (BS == 4)
+        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
+                     "v_add_f64 %[a0], %[a0], %[t0]\n\tv_add_f64 %[a1], %[a1], %[t1]\n\t"
+                     "v_add_f64 %[a2], %[a2], %[t2]\n\tv_add_f64 %[a3], %[a3], %[t3]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [sv] "=&s"(save)
+                     : [m] "s"(m), [t0] "v"(t[0]), [t1] "v"(t[1]), [t2] "v"(t[2]), [t3] "v"(t[3]));
+    else
+        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
+                     "v_add_f64 %[a0], %[a0], %[t0]\n\tv_add_f64 %[a1], %[a1], %[t1]\n\t"
+                     "v_add_f64 %[a2], %[a2], %[t2]\n\tv_add_f64 %[a3], %[a3], %[t3]\n\t"
+                     "v_add_f64 %[a4], %[a4], %[t4]\n\tv_add_f64 %[a5], %[a5], %[t5]\n\t"
+                     "v_add_f64 %[a6], %[a6], %[t6]\n\tv_add_f64 %[a7], %[a7], %[t7]\n\t"
+                     "s_mov_b64 exec, %[sv]"
+                     : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [a4] "+v"(a[4]), [a5] "+v"(a[5]),
+                       [a6] "+v"(a[6]), [a7] "+v"(a[7]), [sv] "=&s"(save)
+                     : [m] "s"(m), [t0] "v"(t[0]), [t1] "v"(t[1]), [t2] "v"(t[2]), [t3] "v"(t[3]), [t4] "v"(t[4]), [t5] "v"(t[5]),
+                       [t6] "v"(t[6]), [t7] "v"(t[7]));
+}
+
 }  // namespace

@@ -458,6 +458,13 @@ int uspmv_spmmv_ap_hp_plan_lines(int b, int x_dtype, int *max_lines) {
     return USPMV_OK;
 }
 
+int uspmv_spmmv_ap_hp_sweep_vectors(int b, int wlog, int x_dtype, int *vectors) {
+    if (b < 1 || wlog < 8 || wlog > 16 || (x_dtype != USPMV_F64 && x_dtype != USPMV_F32) || !vectors)
+        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv_ap_hp_sweep_vectors: bad argument");
+    *vectors = spmmv_ap_hp_sweep_vectors(b, wlog, x_dtype);
+    return USPMV_OK;
+}
+
 extern "C++" {
 namespace uspmv_dev {
 

@@ -444,17 +444,25 @@ int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_d
 // what launch_spmv_ap_hp runs: 3 the shared column-window sweep, 2 the shared tile-local-column plan, 0 lane per row
 int spmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, bool x_aligned16);                                   // ap_kernels.hip
 // ... on block vectors (X, Y in the type of the hi part): b = 1 forwards to launch_spmv_ap_hp; b in {2, 4, 8, 16} on 16-byte-aligned
-// vectors the staged kernel over the parts' shared tile-local-column plan where two vectors of its fullest tile fit LDS; else lane per
-// row with VB vectors per pass (handles without a plan or with the sweep plan, any other b, layout or alignment)
+// vectors the sweep kernel over the parts' shared column-window sweep plan where two vectors of a window fit LDS, the staged kernel over
+// their shared tile-local-column plan where two vectors of its fullest tile fit LDS; else lane per row with VB vectors per pass
+// (handles without a plan, any other b, layout or alignment)
 int launch_spmmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *X, void *Y, int b, long ld, int layout,
                        hipStream_t st);                                                                           // ap_hp_spmmv_kernels.hip
 int spmmv_ap_hp_plan_lines(int b, int x_dtype);   // most lines per tile of a shared plan the staged block kernel takes at width b (0: no such kernel)
 // what launch_spmmv_ap_hp runs for 16-byte-aligned X / Y: 0 lane per row, 2 staged over the shared line plan (b = 1: spmv_ap_hp_path);
-// vectors: per pass of the staged kernel, else 0
+// 3 the column-window sweep kernel over the shared sweep plan; vectors: per pass of the staged / sweep kernel, else 0
 void spmmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, int b, long ld, int layout, int *path, int *vectors);
 // lane per row over a list of chunks (for the rest chunks of a sweep plan's block form), any b
 int launch_spmmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
                               const void *X, void *Y, int b, long ld, int layout, hipStream_t st);                 // ap_hp_spmmv_kernels.hip
+// the block sweep kernel of the splits with an fp16 part (ap_hp_spmmv_sweep.hip): vectors per pass at width b on windows of 2^wlog
+// elements of x_dtype (USPMV_F64 | USPMV_F32; 0: does not apply) / on this handle's plan and threads per workgroup; the launch: sweep
+// tiles, then the rest chunks
+int spmmv_ap_hp_sweep_vectors(int b, int wlog, int x_dtype);
+int spmmv_ap_hp_sweep_bs(const uspmv_dmat *hi, int b);
+int launch_spmmv_ap_hp_sweep(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *X, void *Y, int b, long ld,
+                             bool colwise, int bs, hipStream_t st);
 template <typename VT>
 int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st);                                    // sweep_kernels.hip (sweep tiles only)
 int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st);                       // sweep_kernels.hip

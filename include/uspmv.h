@@ -242,8 +242,9 @@ int uspmv_dmat_optimize_sweep_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, 
  * handles without a host struct (uspmv_dmat_wrap, the launchers of include/uspmv_launchers.hpp) reach scs_spmv_sweep.  sp: the sp
  * part of an ap[dp_sp] pair or NULL.  The arrays equal those of uspmv_dmat_optimize_sweep[_ap] bit for bit. */
 int uspmv_dmat_optimize_sweep_device(uspmv_dmat_t *m, uspmv_dmat_t *sp, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep);
-/* FNV-1a digests of the sweep plan's device arrays and meta[8] = present, rows per tile, log2 window, sweep tiles, tiles, chunks
- * left to the gather kernel, elements of the dp / sp stream (tests) */
+/* FNV-1a digests of the sweep plan's device arrays -- digest[0..3] the tile arrays, [4..8] part 0 as uspmv_dmat_sweep_plan_digest_part
+ * gives it, [9] the chunks left to the gather kernel, [10..14] part 1 -- and meta[8] = present, rows per tile, log2 window, sweep
+ * tiles, tiles, chunks left to the gather kernel, elements of the stream of part 0 / of part 1 (tests) */
 int uspmv_dmat_sweep_plan_digest(const uspmv_dmat_t *m, uint64_t digest[16], int64_t meta[8]);
 /* ... and of the arrays of ONE part of a shared sweep plan (m: the first part's handle; part 0, 1 or 2 in the order of the split):
  * digest[5] = wave offsets, counts, values, indices, padding columns; *n_vals = elements of the part's stream (may be NULL).  Zeros

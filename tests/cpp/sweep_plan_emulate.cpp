@@ -46,8 +46,10 @@ static void run(int64_t n, int nnz_row, int64_t band, int C, int sigma, int wlog
     for (size_t i = 0; i < x.size(); ++i) x[i] = 1.0 + 1e-3 * (double)(i % 1000);
     if (special) { x[0] = -INFINITY; x[5] = -0.0; x[17] = NAN; }
     uspmv_sweep_plan p;
-    REQUIRE(uspmv_build_sweep_plan(s, s2, wlog, tile_rows, 1e9, &p) == 0);
+    const uspmv_scs *const ss[2] = {s, s2};
+    REQUIRE(uspmv_build_sweep_plan(ss, ap ? 2 : 1, wlog, tile_rows, 1e9, &p) == 0);
     REQUIRE(p.valid);
+    const auto &dp = p.part[0], &sp = p.part[1];
     const int64_t R = p.tile_rows, wpt = R / 64, n_pad = s->n_chunks * s->C;
     std::vector<double> y((size_t)n_pad, 12345.0);
     std::vector<char> covered((size_t)n_pad, 0);
@@ -56,18 +58,18 @@ static void run(int64_t n, int nnz_row, int64_t band, int C, int sigma, int wlog
         for (int64_t v = 0; v < wpt; ++v) {
             double acc[64], accb[64];
             for (int l = 0; l < 64; ++l) acc[l] = accb[l] = 0.0;
-            uint32_t base = p.wave_off[(size_t)(k * wpt + v)], base_b = ap ? p.wave_off_b[(size_t)(k * wpt + v)] : 0;
+            uint32_t base = dp.wave_off[(size_t)(k * wpt + v)], base_b = ap ? sp.wave_off[(size_t)(k * wpt + v)] : 0;
             for (int64_t sw = 0; sw < p.t_S[(size_t)k]; ++sw) {
                 const int64_t g0 = (int64_t)(p.t_smin[(size_t)k] + sw) << wlog;
                 for (int part = 0; part < (ap ? 2 : 1); ++part) {
-                    const uint8_t *cnt = (part ? p.cnt_b.data() : p.cnt.data()) + p.t_cnt_off[(size_t)k] + sw * R + v * 64;
+                    const uint8_t *cnt = p.part[part].cnt.data() + p.t_cnt_off[(size_t)k] + sw * R + v * 64;
                     for (int kk = 0;; ++kk) {
                         bool any = false;
                         for (int l = 0; l < 64; ++l) {
                             if (cnt[l] <= kk) continue;
                             any = true;
-                            if (part == 0) { acc[l] = std::fma(p.vals_f64[base], x[(size_t)(g0 + p.idx[base])], acc[l]); ++base; }
-                            else { accb[l] = std::fma((double)p.vals_b_f32[base_b], x[(size_t)(g0 + p.idx_b[base_b])], accb[l]); ++base_b; }
+                            if (part == 0) { acc[l] = std::fma(dp.vals_f64[base], x[(size_t)(g0 + dp.idx[base])], acc[l]); ++base; }
+                            else { accb[l] = std::fma((double)sp.vals_f32[base_b], x[(size_t)(g0 + sp.idx[base_b])], accb[l]); ++base_b; }
                         }
                         if (!any) break;
                     }
@@ -76,10 +78,10 @@ static void run(int64_t n, int nnz_row, int64_t band, int C, int sigma, int wlog
             for (int l = 0; l < 64; ++l) {
                 const int64_t row = t * R + v * 64 + l;
                 if (row >= n_pad) continue;
-                const int32_t pc = p.pad_col[(size_t)(k * R + v * 64 + l)];
+                const int32_t pc = dp.pad_col[(size_t)(k * R + v * 64 + l)];
                 if (pc >= 0) acc[l] = std::fma(0.0, x[(size_t)pc], acc[l]);
                 if (ap) {
-                    const int32_t pcb = p.pad_col_b[(size_t)(k * R + v * 64 + l)];
+                    const int32_t pcb = sp.pad_col[(size_t)(k * R + v * 64 + l)];
                     if (pcb >= 0) accb[l] = std::fma((double)0.0f, x[(size_t)pcb], accb[l]);
                     acc[l] += accb[l];
                 }

@@ -84,12 +84,9 @@ static std::vector<double> make_x(int64_t n, bool float_x, bool special) {
 
 struct PartView { const uint32_t *wave_off; const uint8_t *cnt; const uint16_t *idx; const int32_t *pad; const void *vals; int dtype; };
 static PartView part_view(const uspmv_sweep_plan &p, const Split &sp, int w) {
-    PartView v{};
-    v.dtype = sp.s[w]->dtype;
-    if (w == 0) { v = {p.wave_off.data(), p.cnt.data(), p.idx.data(), p.pad_col.data(), v.dtype == USPMV_F64 ? (const void *)p.vals_f64.data() : (const void *)p.vals_f32.data(), v.dtype}; }
-    else if (w == 1) { v = {p.wave_off_b.data(), p.cnt_b.data(), p.idx_b.data(), p.pad_col_b.data(), v.dtype == USPMV_F32 ? (const void *)p.vals_b_f32.data() : (const void *)p.vals_b_f16.data(), v.dtype}; }
-    else { v = {p.wave_off_c.data(), p.cnt_c.data(), p.idx_c.data(), p.pad_col_c.data(), (const void *)p.vals_c_f16.data(), v.dtype}; }
-    return v;
+    const auto &pt = p.part[w];
+    REQUIRE(pt.dtype == sp.s[w]->dtype);
+    return {pt.wave_off.data(), pt.cnt.data(), pt.idx.data(), pt.pad_col.data(), pt.vals(), sp.s[w]->dtype};
 }
 static double stream_val(const PartView &v, size_t k) {
     return v.dtype == USPMV_F64 ? ((const double *)v.vals)[k] : v.dtype == USPMV_F32 ? (double)((const float *)v.vals)[k] : uspmv_f16_to_f64(((const uint16_t *)v.vals)[k]);
@@ -102,7 +99,8 @@ static int64_t check_split(const char *what, const Split &sp, int wlog, int tile
     const int64_t C = s0->C, n_pad = s0->n_chunks * C;
     std::vector<double> x = make_x(std::max<int64_t>(s0->n_rows_padded, s0->n_cols), fx, special);
     uspmv_sweep_plan p;
-    REQUIRE(uspmv_build_sweep_plan(sp.s[0], sp.s[1], wlog, tile_rows, max_stage, &p, sp.np == 3 ? sp.s[2] : nullptr) == 0);
+    REQUIRE(uspmv_build_sweep_plan(sp.s, sp.np, wlog, tile_rows, max_stage, &p) == 0);
+    REQUIRE(p.n_parts == sp.np);
     REQUIRE(p.valid);
     if (!p.valid) return 0;
     const int64_t R = p.tile_rows, wpt = R / 64;
@@ -166,7 +164,7 @@ static int64_t check_split(const char *what, const Split &sp, int wlog, int tile
         }
     // the streams hold sizeof(value) + 2 bytes per stored entry and nothing else
     for (int w = 0; w < sp.np; ++w) {
-        const std::vector<uint16_t> &ix = w == 0 ? p.idx : w == 1 ? p.idx_b : p.idx_c;
+        const std::vector<uint16_t> &ix = p.part[w].idx;
         stream_total += (int64_t)ix.size() - 64;
         if (p.n_sweep_tiles == p.n_tiles) REQUIRE((int64_t)ix.size() - 64 <= sp.s[w]->n_elements);
     }
@@ -344,27 +342,33 @@ static void run_before(int64_t n, int nnz_row, int64_t band, int C, int sigma, i
         REQUIRE(uspmv_permute_scs_cols(s2, s->old_to_new_idx.data()) == 0);
     }
     uspmv_sweep_plan p;
-    REQUIRE(uspmv_build_sweep_plan(s, s2, wlog, tile_rows, max_stage, &p) == 0);
-    Before b;
     const uspmv_scs *ss[2] = {s, s2};
-    layout_before(ss, ap ? 2 : 1, wlog, tile_rows, max_stage, &b);
+    const int ns = ap ? 2 : 1;
+    REQUIRE(uspmv_build_sweep_plan(ss, ns, wlog, tile_rows, max_stage, &p) == 0);
+    Before b;
+    layout_before(ss, ns, wlog, tile_rows, max_stage, &b);
     REQUIRE(p.n_tiles == b.n_tiles && p.n_sweep_tiles == (int64_t)b.tile_ids.size());
     REQUIRE(same_vec(p.tile_ids, b.tile_ids) && same_vec(p.t_smin, b.t_smin) && same_vec(p.t_S, b.t_S) && same_vec(p.t_cnt_off, b.t_cnt_off));
     REQUIRE(same_vec(p.rest_chunks, b.rest));
     if (!b.tile_ids.empty()) {
         REQUIRE(p.valid);
-        REQUIRE(same_vec(p.wave_off, b.wave_off[0]) && same_vec(p.cnt, b.cnt[0]) && same_vec(p.idx, b.idx[0]) && same_vec(p.pad_col, b.pad[0]));
-        if (s->dtype == USPMV_F64) REQUIRE(same_vec(p.vals_f64, b.v64[0])); else REQUIRE(same_vec(p.vals_f32, b.v32[0]));
-        if (ap) {
-            REQUIRE(same_vec(p.wave_off_b, b.wave_off[1]) && same_vec(p.cnt_b, b.cnt[1]) && same_vec(p.idx_b, b.idx[1]) && same_vec(p.pad_col_b, b.pad[1]));
-            REQUIRE(same_vec(p.vals_b_f32, b.v32[1]));
+        REQUIRE(p.n_parts == ns);
+        for (int w = 0; w < ns; ++w) {
+            const auto &pt = p.part[w];
+            REQUIRE(pt.dtype == ss[w]->dtype);
+            REQUIRE(same_vec(pt.wave_off, b.wave_off[w]) && same_vec(pt.cnt, b.cnt[w]) && same_vec(pt.idx, b.idx[w]) && same_vec(pt.pad_col, b.pad[w]));
+            // the stream in the part's own type and in no other: nothing in binary16
+            REQUIRE(same_vec(pt.vals_f64, b.v64[w]) && same_vec(pt.vals_f32, b.v32[w]) && pt.vals_f16.empty());
         }
-        // nothing of a third part, nothing in binary16
-        REQUIRE(p.wave_off_c.empty() && p.cnt_c.empty() && p.idx_c.empty() && p.pad_col_c.empty() && p.vals_c_f16.empty() && p.vals_b_f16.empty());
-        if (!ap) REQUIRE(p.wave_off_b.empty() && p.cnt_b.empty() && p.idx_b.empty() && p.pad_col_b.empty());
+        // the parts the plan has not are empty
+        for (int w = ns; w < 3; ++w) {
+            const auto &pt = p.part[w];
+            REQUIRE(pt.wave_off.empty() && pt.cnt.empty() && pt.idx.empty() && pt.pad_col.empty());
+            REQUIRE(pt.vals_f64.empty() && pt.vals_f32.empty() && pt.vals_f16.empty());
+        }
     }
     printf("layout as before: n=%ld C=%d sigma=%d wlog=%d tile=%d ap=%d dtype=%d: sweep tiles %ld/%ld, %zu + %zu stream entries\n", (long)n, C, sigma, wlog,
-           tile_rows, (int)ap, s->dtype, (long)p.n_sweep_tiles, (long)p.n_tiles, p.idx.size(), p.idx_b.size());
+           tile_rows, (int)ap, s->dtype, (long)p.n_sweep_tiles, (long)p.n_tiles, p.part[0].idx.size(), p.part[1].idx.size());
     uspmv_scs_free(s); if (s2) uspmv_scs_free(s2);
     if (ap) { uspmv_coo_free(dpc); uspmv_coo_free(spc); }
     uspmv_coo_free(coo);
@@ -391,7 +395,7 @@ static void run_coverage() {
                 for (auto &sh : shapes) {
                     if (kind != SP_HP && sh[0] > 14) continue;          // 2^15 doubles do not fit the LDS
                     uspmv_sweep_plan p;
-                    REQUIRE(uspmv_build_sweep_plan(sp.s[0], sp.s[1], sh[0], sh[1], 24.0, &p, sp.np == 3 ? sp.s[2] : nullptr) == 0);
+                    REQUIRE(uspmv_build_sweep_plan(sp.s, sp.np, sh[0], sh[1], 24.0, &p) == 0);
                     REQUIRE(p.valid && p.n_sweep_tiles == p.n_tiles && p.rest_chunks.empty());
                     all += p.valid && p.n_sweep_tiles == p.n_tiles;
                 }

@@ -189,6 +189,9 @@ def test_device_sweep_plan_builder_equals_host_planner(pkg, orc, torch_cuda):
         dh, mh = Ahd.sweep_plan_digest()
         dd, md = Add.sweep_plan_digest()
         assert mh == md and dh == dd and mh[7] > 0, (wlog, rows, mh, md, [k for k in range(16) if dh[k] != dd[k]])
+        for A, d, m in ((Ahd, dh, mh), (Add, dd, md)):    # ... with the dp part at [4:9] / meta[6] and the sp part at [10:15] / meta[7]
+            p0, p1 = A.sweep_plan_digest_part(0), A.sweep_plan_digest_part(1)
+            assert d[4:9] == p0[0] and d[10:15] == p1[0] and m[6] == p0[1] and m[7] == p1[1], (wlog, rows, d, m, p0, p1)
         y = t.full((ds.n_rows_padded,), -7.0, dtype=t.float64, device="cuda")
         pkg.spmv_ap(Add, Ads, t.from_numpy(xp).cuda(), y)
         assert np.array_equal(y.cpu().numpy(), y_or)

@@ -121,7 +121,11 @@ def _digests(hand):
     """the shared arrays of the plan and every part's, as digests"""
     n_parts = sum(h is not None for h in hand)
     d, meta = hand[0].sweep_plan_digest()
-    return d[:5] + d[9:10], meta[:6], [hand[0].sweep_plan_digest_part(p) for p in range(3)], n_parts
+    parts = [hand[0].sweep_plan_digest_part(p) for p in range(3)]
+    # the whole-plan digest carries parts 0 and 1 at [4:9] and [10:15], their stream lengths in meta[6] and meta[7]
+    assert d[4:9] == parts[0][0] and d[10:15] == parts[1][0], (d, parts)
+    assert meta[6] == parts[0][1] and meta[7] == parts[1][1], (meta, parts)
+    return d[:5] + d[9:10], meta[:6], parts, n_parts
 
 
 def _same_sweep_plans(a, b):

@@ -26,8 +26,8 @@ int main(int argc, char **argv) {
                 if (cs.first < 32 && 32 % cs.first == 0) { uspmv_scs r; CK(uspmv_scs_rechunk32(s, &r)); }
                 if (256 % cs.first == 0) {                                   // column-window sweep plan (two window sizes, small tiles)
                     uspmv_sweep_plan sp;
-                    CK(uspmv_build_sweep_plan(s, nullptr, 6, 256, 1e9, &sp));
-                    CK(uspmv_build_sweep_plan(s, nullptr, 10, 1024, 24.0, &sp));
+                    CK(uspmv_build_sweep_plan(&s, 1, 6, 256, 1e9, &sp));
+                    CK(uspmv_build_sweep_plan(&s, 1, 10, 1024, 24.0, &sp));
                 }
                 if (cs.first == 32 || cs.first == 64 || cs.first == 16) {   // phased block plan over the tie-re-ordered copy, and the line form
                     uspmv_scs r; std::vector<int32_t> rm;

@@ -27,43 +27,7 @@ using namespace uspmv_dev;
 
 namespace {
 
-constexpr size_t APHSW_LDS = 160 * 1024;   // all the LDS a gfx950 workgroup can have
 constexpr int APHSW_U = 4;                 // rounds per batch
-
-// the plan's per-part arrays; [1] (mid) is unused unless ap[dp_sp_hp]
-struct SweepHpBlockParts {
-    const unsigned *wave_off[3];
-    const unsigned char *cnt[3];
-    const void *vals[3];
-    const unsigned short *idx[3];
-    const int *pad[3];
-};
-
-// the stored value widened to the type the product is formed in (double for a double X, float for a float X); exact
-__device__ __forceinline__ double hpb_widen(double v, double) { return v; }
-__device__ __forceinline__ double hpb_widen(float v, double) { return (double)v; }
-__device__ __forceinline__ double hpb_widen(unsigned short v, double) { return (double)hp_val(v); }
-__device__ __forceinline__ float hpb_widen(float v, float) { return v; }
-__device__ __forceinline__ float hpb_widen(unsigned short v, float) { return hp_val(v); }
-
-// the BS operands of window element i: one X row of the row-major image (16-byte reads; 8 bytes for two floats), or one element of each plane
-template <typename HT, int BS, bool XCOL>
-__device__ __forceinline__ void hpb_window_x(const HT *win, const int wlog, const unsigned i, HT (&x)[BS]) {
-    if constexpr (XCOL) {
-#pragma unroll
-        for (int w = 0; w < BS; ++w) x[w] = win[i + ((unsigned)w << wlog)];
-    } else {
-        constexpr int PE = (int)(16 / sizeof(HT)) < BS ? (int)(16 / sizeof(HT)) : BS;
-        typedef HT piece_t __attribute__((ext_vector_type(PE)));
-        const piece_t *xp = (const piece_t *)(win + i * BS);
-#pragma unroll
-        for (int k = 0; k < BS / PE; ++k) {
-            const piece_t t = xp[k];
-#pragma unroll
-            for (int e = 0; e < PE; ++e) x[k * PE + e] = t[e];
-        }
-    }
-}
 
 // One window, one part of one of the lane's rows: batches of U rounds over the wave's compacted stream, which starts at element o of
 // vals / idx; returns where the next window's starts.  c: the row's entries of this part in this window.  Entry registers of lanes that
@@ -95,12 +59,12 @@ __device__ __forceinline__ unsigned hpb_window(const HT *win, const int wlog, co
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             HT x[BS];
-            hpb_window_x<HT, BS, XCOL>(win, wlog, ix[u], x);
+            window_x<HT, BS, XCOL>(win, wlog, ix[u], x);
             if constexpr (sizeof(HT) == 8) {
-                masked_fma_round<BS>(acc, hpb_widen(v[u], HT(0)), x, m[u]);
+                masked_fma_round<BS>(acc, hp_widen(v[u], HT(0)), x, m[u]);
             } else {
                 double t[BS];
-                const float a = hpb_widen(v[u], HT(0));
+                const float a = hp_widen(v[u], HT(0));
 #pragma unroll
                 for (int w = 0; w < BS; ++w) t[w] = (double)__fmul_rn(a, x[w]);
                 masked_add_round<BS>(acc, t, m[u]);
@@ -117,7 +81,7 @@ __device__ __forceinline__ unsigned hpb_window(const HT *win, const int wlog, co
 template <typename HT, bool MID, int BS, bool XCOL, bool YCOL, bool NT, int RPL>
 __global__ void __launch_bounds__(1024) scs_spmmv_ap_hp_sweep(const int wlog, const int nbuf, const int *__restrict__ tile_ids,
         const int *__restrict__ t_smin, const int *__restrict__ t_S, const unsigned long long *__restrict__ t_cnt_off,
-        const SweepHpBlockParts P, const HT *__restrict__ X, HT *__restrict__ Y, const int b, const long ld, const long x_rows,
+        const SweepParts P, const HT *__restrict__ X, HT *__restrict__ Y, const int b, const long ld, const long x_rows,
         const long n_store, const int n_groups, const int xcd_remap) {
     static_assert(RPL * BS <= 8, "3 * RPL * BS accumulators per lane");
     extern __shared__ __attribute__((aligned(16))) unsigned char aphsw_smem[];
@@ -283,21 +247,14 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_hp_sweep(const int wlog, co
     }
 }
 
-// threads per workgroup as launch_sweep_hp (sweep_ap_hp_kernels.hip) chooses them: a lane owns tile_rows / threads rows, at most 4
-int aphsw_threads(const uspmv_dmat *hi) {
-    int threads = std::min<int>(hi->sw.tile_rows, g_tune.sweep_threads > 0 ? g_tune.sweep_threads : 1024);
-    if (hi->sw.tile_rows / threads > 4) threads = hi->sw.tile_rows / 4;
-    return threads;
-}
-
 template <typename HT, bool MID, int BS, bool COL, bool NT, int RPL>
-void aphsw_launch(const uspmv_dmat *hi, const SweepHpBlockParts &P, const HT *X, HT *Y, int b, long ld, int threads, int n_groups,
+void aphsw_launch(const uspmv_dmat *hi, const SweepParts &P, const HT *X, HT *Y, int b, long ld, int threads, int n_groups,
                   hipStream_t st) {
     const auto &w = hi->sw;
     auto kfn = scs_spmmv_ap_hp_sweep<HT, MID, BS, COL, COL, NT, RPL>;
     const size_t win = (sizeof(HT) << w.wlog) * BS;
     // (the second buffer only where two windows of BS vectors fit)
-    const int nbuf = (g_tune.sweep_nbuf == 2 && 2 * win <= APHSW_LDS) ? 2 : 1;
+    const int nbuf = (g_tune.sweep_nbuf == 2 && 2 * win <= WG_LDS_BYTES) ? 2 : 1;
     const size_t lds = nbuf * win;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     // X rows the staging may read: the columns the matrix references, and within one column of a column-major X at most ld
@@ -308,7 +265,7 @@ void aphsw_launch(const uspmv_dmat *hi, const SweepHpBlockParts &P, const HT *X,
 
 // rpl: rows of a lane (1, 2 or 4), held 8 / BS at a time at most
 template <typename HT, bool MID, int BS, bool COL, bool NT>
-void aphsw_launch_r(const uspmv_dmat *hi, const SweepHpBlockParts &P, const HT *X, HT *Y, int b, long ld, int threads, int rpl, hipStream_t st) {
+void aphsw_launch_r(const uspmv_dmat *hi, const SweepParts &P, const HT *X, HT *Y, int b, long ld, int threads, int rpl, hipStream_t st) {
     constexpr int G = 8 / BS;
     if constexpr (G >= 4) { if (rpl == 4) { aphsw_launch<HT, MID, BS, COL, NT, 4>(hi, P, X, Y, b, ld, threads, 1, st); return; } }
     if constexpr (G >= 2) { if (rpl >= 2) { aphsw_launch<HT, MID, BS, COL, NT, 2>(hi, P, X, Y, b, ld, threads, rpl / 2, st); return; } }
@@ -316,7 +273,7 @@ void aphsw_launch_r(const uspmv_dmat *hi, const SweepHpBlockParts &P, const HT *
 }
 
 template <typename HT, bool MID, int BS>
-void aphsw_launch_bs(const uspmv_dmat *hi, const SweepHpBlockParts &P, const HT *X, HT *Y, int b, long ld, bool col, int threads, int rpl,
+void aphsw_launch_bs(const uspmv_dmat *hi, const SweepParts &P, const HT *X, HT *Y, int b, long ld, bool col, int threads, int rpl,
                      hipStream_t st) {
     const bool nt = g_tune.nontemporal != 0;
     if (col) { if (nt) aphsw_launch_r<HT, MID, BS, true, true>(hi, P, X, Y, b, ld, threads, rpl, st);
@@ -328,16 +285,8 @@ void aphsw_launch_bs(const uspmv_dmat *hi, const SweepHpBlockParts &P, const HT 
 template <typename HT, bool MID>
 int aphsw_launch_kind(const uspmv_dmat *hi, const HT *X, HT *Y, int b, long ld, bool col, int bs, hipStream_t st) {
     const auto &w = hi->sw;
-    SweepHpBlockParts P{};
-    // the plan stores its parts in the order of the split: [hi, hp] or [hi, mid, hp]
-    P.wave_off[0] = w.wave_off; P.cnt[0] = w.cnt; P.vals[0] = w.vals; P.idx[0] = w.idx; P.pad[0] = w.pad;
-    if (MID) {
-        P.wave_off[1] = w.wave_off_b; P.cnt[1] = w.cnt_b; P.vals[1] = w.vals_b; P.idx[1] = w.idx_b; P.pad[1] = w.pad_b;
-        P.wave_off[2] = w.wave_off_c; P.cnt[2] = w.cnt_c; P.vals[2] = w.vals_c; P.idx[2] = w.idx_c; P.pad[2] = w.pad_c;
-    } else {
-        P.wave_off[2] = w.wave_off_b; P.cnt[2] = w.cnt_b; P.vals[2] = w.vals_b; P.idx[2] = w.idx_b; P.pad[2] = w.pad_b;
-    }
-    const int threads = aphsw_threads(hi);
+    const SweepParts P = sweep_parts(w);
+    const int threads = sweep_threads(w);
     const int rpl = w.tile_rows / threads;
     if (bs == 8) aphsw_launch_bs<HT, MID, 8>(hi, P, X, Y, b, ld, col, threads, rpl, st);
     else if (bs == 4) aphsw_launch_bs<HT, MID, 4>(hi, P, X, Y, b, ld, col, threads, rpl, st);
@@ -350,21 +299,8 @@ int aphsw_launch_kind(const uspmv_dmat *hi, const HT *X, HT *Y, int b, long ld, 
 
 namespace uspmv_dev {
 
-int spmmv_ap_hp_sweep_vectors(int b, int wlog, int x_dtype) {
-    if (b != 2 && b != 4 && b != 8 && b != 16) return 0;
-    const size_t xb = x_dtype == USPMV_F32 ? 4 : 8;
-    for (int bs = 8; bs >= 2; bs >>= 1)
-        if (bs <= b && b % bs == 0 && (xb << wlog) * bs <= APHSW_LDS) return bs;
-    return 0;
-}
-
-int spmmv_ap_hp_sweep_bs(const uspmv_dmat *hi, int b) {
-    const int threads = aphsw_threads(hi);
-    if (threads < 64 || threads % 64 || hi->sw.tile_rows % threads) return 0;
-    const int rpl = hi->sw.tile_rows / threads;
-    if (rpl != 1 && rpl != 2 && rpl != 4) return 0;
-    return spmmv_ap_hp_sweep_vectors(b, hi->sw.wlog, hi->dtype);
-}
+int spmmv_ap_hp_sweep_vectors(int b, int wlog, int x_dtype) { return sweep_vectors(b, wlog, x_dtype == USPMV_F32 ? 4 : 8); }
+int spmmv_ap_hp_sweep_bs(const uspmv_dmat *hi, int b) { return sweep_block_bs(hi->sw, b, hi->dtype == USPMV_F32 ? 4 : 8); }
 
 int launch_spmmv_ap_hp_sweep(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *X, void *Y, int b, long ld,
                              bool colwise, int bs, hipStream_t st) {

@@ -434,7 +434,7 @@ int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int 
 
 int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x, const float *d_x_sp, double *d_y,
                    hipStream_t stream) {
-    if (!d_x_sp && dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.idx_b && dp->sw.plan_id == sp->sw.plan_id && g_tune.sweep &&
+    if (!d_x_sp && dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.n_parts >= 2 && dp->sw.plan_id == sp->sw.plan_id && g_tune.sweep &&
         ((uintptr_t)d_x % 16 == 0)) {
         if (int rc = launch_spmv_sweep_ap(dp, d_x, d_y, stream)) return rc;
         return launch_spmv_ap_chunks(dp, sp, dp->sw.rest, (long)dp->sw.n_rest, d_x, d_y, stream);

@@ -419,8 +419,8 @@ ApBlockPath ap_block_path(const uspmv_dmat *dp, const uspmv_dmat *sp, int b, lon
     if (g_tune.spmmv_variant == 1 || !aligned16 || (b != 2 && b != 4 && b != 8 && b != 16)) return {AP_PATH_GENERIC, 0};
     // the pair's column-window sweep plan, under the conditions of launch_spmv_ap plus the block ones: the float second part, column-major
     // pieces of 16 bytes, no part of a distributed two-part step, and at least two vectors of a window in LDS
-    if (g_tune.sweep && dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.idx_b && dp->sw.plan_id == sp->sw.plan_id && dp->sw.n_parts == 2 &&
-        dp->sw.dtype_b == USPMV_F32 && !(col && (ld & 1)) && !dp->part && !sp->part && !W->part) {
+    if (g_tune.sweep && dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.n_parts == 2 && dp->sw.plan_id == sp->sw.plan_id &&
+        dp->sw.part[1].dtype == USPMV_F32 && !(col && (ld & 1)) && !dp->part && !sp->part && !W->part) {
         const int bs = spmmv_ap_sweep_bs(dp, b);
         // row-major X in more than two passes keeps the gather kernel: a pass stages bs * 8 bytes out of every b * 8-byte X row, so the rows'
         // sectors are read b / bs times (banded-random 500 k x 140 pair: 1.17 / 2.23 / 3.89 ms against 0.89 / 2.05 / 2.05 ms)

@@ -20,28 +20,10 @@ using namespace uspmv_dev;
 
 namespace {
 
-constexpr size_t APSW_LDS = 160 * 1024;   // all the LDS a gfx950 workgroup can have
 // Rows of a lane whose accumulators are held at a time (2 * rows * BS doubles) beside the batch registers: 1 024-thread workgroups leave
 // a lane 128 registers.  Four rows of four vectors spilled 8-14 registers even at two rounds per batch; two rows of eight fit at two
 // rounds per batch (profiles/ap_spmmv_sweep/resource_usage.txt).
 constexpr int apsw_group_rows(int bs) { return bs == 2 ? 4 : 2; }
-
-// the BS operands of window element i: one X row of the row-major image, or one element of each plane
-template <int BS, bool XCOL>
-__device__ __forceinline__ void window_x(const double *win, const int wlog, const unsigned i, double (&x)[BS]) {
-    if constexpr (XCOL) {
-#pragma unroll
-        for (int w = 0; w < BS; ++w) x[w] = win[i + ((unsigned)w << wlog)];
-    } else {
-        typedef double vec_t __attribute__((ext_vector_type(2)));
-        const vec_t *xp = (const vec_t *)(win + i * BS);
-#pragma unroll
-        for (int k = 0; k < BS / 2; ++k) {
-            const vec_t t = xp[k];
-            x[2 * k] = t[0]; x[2 * k + 1] = t[1];
-        }
-    }
-}
 
 // where a wave stands in the compacted dp / sp streams (a part's values and indices advance together): wave-uniform
 struct ApSweepPos { unsigned o0, o1; };
@@ -52,10 +34,10 @@ struct ApSweepPos { unsigned o0, o1; };
 template <int BS, bool XCOL, int U, bool NT>
 __device__ __forceinline__ ApSweepPos sweep_window_ap_block(const double *win, const int wlog, const int c0, const int c1, ApSweepPos pos,
                                                             const double *__restrict__ vals, const unsigned short *__restrict__ idx,
-                                                            const float *__restrict__ vals_b, const unsigned short *__restrict__ idx_b,
+                                                            const float *__restrict__ vals1, const unsigned short *__restrict__ idx1,
                                                             double (&a0)[BS], double (&a1)[BS]) {
     struct { const double *v0; const unsigned short *i0; const float *v1; const unsigned short *i1; } p{vals + pos.o0, idx + pos.o0,
-                                                                                                        vals_b + pos.o1, idx_b + pos.o1};
+                                                                                                        vals1 + pos.o1, idx1 + pos.o1};
     double v0[U];
     float v1[U];
     unsigned ix0[U], ix1[U];
@@ -87,9 +69,9 @@ __device__ __forceinline__ ApSweepPos sweep_window_ap_block(const double *win, c
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             double x[BS];
-            window_x<BS, XCOL>(win, wlog, ix0[u], x);
+            window_x<double, BS, XCOL>(win, wlog, ix0[u], x);
             masked_fma_round<BS>(a0, v0[u], x, m0[u]);
-            window_x<BS, XCOL>(win, wlog, ix1[u], x);
+            window_x<double, BS, XCOL>(win, wlog, ix1[u], x);
             masked_fma_round<BS>(a1, (double)v1[u], x, m1[u]);
         }
         p.v0 += f0[U]; p.i0 += f0[U];
@@ -238,25 +220,20 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_sweep(const int wlog, const
     }
 }
 
-// threads per workgroup as launch_sweep (sweep_kernels.hip) chooses them: a lane owns tile_rows / threads rows, at most 4
-int apsw_threads(const uspmv_dmat *dp) {
-    int threads = std::min<int>(dp->sw.tile_rows, g_tune.sweep_threads > 0 ? g_tune.sweep_threads : 1024);
-    if (dp->sw.tile_rows / threads > 4) threads = dp->sw.tile_rows / 4;
-    return threads;
-}
-
 template <int BS, bool COL, bool NT, int NBUF, int RPL>
 void apsw_launch(const uspmv_dmat *dp, const double *X, double *Y, int b, long ld, int threads, int n_groups, hipStream_t st) {
     // (rounds per batch: the batch registers of both chains stand beside 2 * RPL * BS accumulators -- four, and two where those are 32)
     constexpr int U = RPL * BS >= 16 ? 2 : 4;
     auto kfn = scs_spmmv_ap_sweep<BS, COL, COL, NT, NBUF, U, RPL>;
-    const size_t lds = (size_t)NBUF * ((size_t)8 << dp->sw.wlog) * BS;
+    const auto &w = dp->sw;
+    const auto &p0 = w.part[0], &p1 = w.part[1];          // the dp and the sp part
+    const size_t lds = (size_t)NBUF * ((size_t)8 << w.wlog) * BS;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     // X rows the staging may read: the columns the matrix references, and within one column of a column-major X at most ld
-    const long x_rows = COL ? std::min<long>((long)dp->sw.x_len, ld) : (long)dp->sw.x_len;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)dp->sw.n_tiles), dim3(threads), lds, st, dp->sw.wlog, dp->sw.tile_ids, dp->sw.smin, dp->sw.S,
-                       (const unsigned long long *)dp->sw.cnt_off, dp->sw.wave_off, dp->sw.cnt, (const double *)dp->sw.vals, dp->sw.idx,
-                       dp->sw.pad, dp->sw.wave_off_b, dp->sw.cnt_b, (const float *)dp->sw.vals_b, dp->sw.idx_b, dp->sw.pad_b, X, Y, b, ld,
+    const long x_rows = COL ? std::min<long>((long)w.x_len, ld) : (long)w.x_len;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)w.n_tiles), dim3(threads), lds, st, w.wlog, w.tile_ids.get(), w.smin.get(), w.S.get(),
+                       (const unsigned long long *)w.cnt_off, p0.wave_off.get(), p0.cnt.get(), (const double *)p0.vals, p0.idx.get(),
+                       p0.pad.get(), p1.wave_off.get(), p1.cnt.get(), (const float *)p1.vals, p1.idx.get(), p1.pad.get(), X, Y, b, ld,
                        x_rows, (long)dp->n_store, n_groups, g_tune.sweep_remap);
 }
 
@@ -272,7 +249,7 @@ void apsw_launch_r(const uspmv_dmat *dp, const double *X, double *Y, int b, long
 template <int BS>
 void apsw_launch_bs(const uspmv_dmat *dp, const double *X, double *Y, int b, long ld, bool col, int threads, int rpl, hipStream_t st) {
     // (the second buffer only where two windows of BS vectors fit)
-    const bool two = g_tune.sweep_nbuf == 2 && 2 * ((size_t)8 << dp->sw.wlog) * BS <= APSW_LDS;
+    const bool two = g_tune.sweep_nbuf == 2 && 2 * ((size_t)8 << dp->sw.wlog) * BS <= WG_LDS_BYTES;
     const bool nt = g_tune.nontemporal != 0;
 #define APSW_NB(COLV, NTV) do { if (two) apsw_launch_r<BS, COLV, NTV, 2>(dp, X, Y, b, ld, threads, rpl, st); \
                                 else apsw_launch_r<BS, COLV, NTV, 1>(dp, X, Y, b, ld, threads, rpl, st); } while (0)
@@ -285,25 +262,13 @@ void apsw_launch_bs(const uspmv_dmat *dp, const double *X, double *Y, int b, lon
 
 namespace uspmv_dev {
 
-int spmmv_ap_sweep_vectors(int b, int wlog) {
-    if (b != 2 && b != 4 && b != 8 && b != 16) return 0;
-    for (int bs = 8; bs >= 2; bs >>= 1)
-        if (bs <= b && b % bs == 0 && ((size_t)8 << wlog) * bs <= APSW_LDS) return bs;
-    return 0;
-}
-
-int spmmv_ap_sweep_bs(const uspmv_dmat *dp, int b) {
-    const int threads = apsw_threads(dp);
-    if (threads < 64 || threads % 64 || dp->sw.tile_rows % threads) return 0;
-    const int rpl = dp->sw.tile_rows / threads;
-    if (rpl != 1 && rpl != 2 && rpl != 4) return 0;
-    return spmmv_ap_sweep_vectors(b, dp->sw.wlog);
-}
+int spmmv_ap_sweep_vectors(int b, int wlog) { return sweep_vectors(b, wlog, sizeof(double)); }
+int spmmv_ap_sweep_bs(const uspmv_dmat *dp, int b) { return sweep_block_bs(dp->sw, b, sizeof(double)); }
 
 int launch_spmmv_ap_sweep(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, bool colwise, int bs,
                           hipStream_t st) {
     if (dp->sw.n_tiles > 0) {
-        const int threads = apsw_threads(dp);
+        const int threads = sweep_threads(dp->sw);
         const int rpl = dp->sw.tile_rows / threads;
         if (bs == 8) apsw_launch_bs<8>(dp, X, Y, b, ld, colwise, threads, rpl, st);
         else if (bs == 4) apsw_launch_bs<4>(dp, X, Y, b, ld, colwise, threads, rpl, st);

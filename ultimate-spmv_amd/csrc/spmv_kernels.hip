@@ -643,7 +643,7 @@ int launch_spmv_scs(const uspmv_dmat *A, const int *chunk_ids, long n_ids, const
     if (nwc == 0) return USPMV_OK;
     const int C = (int)A->C;
     const int block = g_tune.block;
-    if (!ids && A->sw.on && A->sw.tile_ids && !A->sw.idx_b && g_tune.sweep && !g_tune.ablate && g_tune.spmv_variant == 0 && ((uintptr_t)x % 16 == 0)) {
+    if (!ids && A->sw.on && A->sw.tile_ids && A->sw.n_parts == 1 && g_tune.sweep && !g_tune.ablate && g_tune.spmv_variant == 0 && ((uintptr_t)x % 16 == 0)) {
         // column-window sweep over the tiles that qualify, lane-per-row gather kernel over the chunks that are left
         if (int rc = launch_spmv_sweep<VT>(A, x, y, st)) return rc;
         return A->sw.n_rest ? launch_spmv_scs<VT>(A, A->sw.rest, (long)A->sw.n_rest, x, y, st) : USPMV_OK;

@@ -21,22 +21,6 @@ using namespace uspmv_dev;
 
 namespace {
 
-// the plan's per-part arrays; [1] (mid) is unused unless ap[dp_sp_hp]
-struct SweepHpParts {
-    const unsigned *wave_off[3];
-    const unsigned char *cnt[3];
-    const void *vals[3];
-    const unsigned short *idx[3];
-    const int *pad[3];
-};
-
-// the stored value widened to the type the product is formed in (double for a double x, float for a float x); exact
-__device__ __forceinline__ double hp_widen(double v, double) { return v; }
-__device__ __forceinline__ double hp_widen(float v, double) { return (double)v; }
-__device__ __forceinline__ double hp_widen(unsigned short v, double) { return (double)hp_val(v); }
-__device__ __forceinline__ float hp_widen(float v, float) { return v; }
-__device__ __forceinline__ float hp_widen(unsigned short v, float) { return hp_val(v); }
-
 // One window, one part of one row per lane: batches of U rounds over the wave's compacted stream, which starts at element o of vals /
 // idx; returns where the next window's starts.  In round u the active lanes are those with more than k0+u entries in this window -- one
 // ballot --, a lane's element sits `active lanes below it` behind the round's first one.  Loads run under the lane mask, the step's
@@ -150,7 +134,7 @@ __device__ __forceinline__ HpOffs hp_window2(const XT *__restrict__ xs, const in
 // RPL * blockDim.x rows, lane <-> rows tid, tid + blockDim.x, ...  nbuf: LDS buffers (2: window s+1 lands while window s is consumed).
 template <typename HT, bool MID, bool NT, int U, int RPL, int PAIRM>
 __global__ void __launch_bounds__(1024) scs_spmv_sweep_ap_hp(const int wlog, const int nbuf, const int *__restrict__ tile_ids,
-        const int *__restrict__ t_smin, const int *__restrict__ t_S, const unsigned long long *__restrict__ t_cnt_off, const SweepHpParts P,
+        const int *__restrict__ t_smin, const int *__restrict__ t_S, const unsigned long long *__restrict__ t_cnt_off, const SweepParts P,
         const HT *__restrict__ x, HT *__restrict__ y, const long x_len, const long n_store, const int xcd_remap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sweep_smem[];
     constexpr int EPL = 16 / (int)sizeof(HT);           // elements per 16-byte DMA lane
@@ -264,22 +248,12 @@ __global__ void __launch_bounds__(1024) scs_spmv_sweep_ap_hp(const int wlog, con
 template <typename HT, bool MID>
 int launch_sweep_hp(const uspmv_dmat *A, const HT *x, HT *y, hipStream_t st) {
     const auto &w = A->sw;
-    SweepHpParts P{};
-    // the plan stores its parts in the order of the split: [hi, hp] or [hi, mid, hp]
-    P.wave_off[0] = w.wave_off; P.cnt[0] = w.cnt; P.vals[0] = w.vals; P.idx[0] = w.idx; P.pad[0] = w.pad;
-    if (MID) {
-        P.wave_off[1] = w.wave_off_b; P.cnt[1] = w.cnt_b; P.vals[1] = w.vals_b; P.idx[1] = w.idx_b; P.pad[1] = w.pad_b;
-        P.wave_off[2] = w.wave_off_c; P.cnt[2] = w.cnt_c; P.vals[2] = w.vals_c; P.idx[2] = w.idx_c; P.pad[2] = w.pad_c;
-    } else {
-        P.wave_off[2] = w.wave_off_b; P.cnt[2] = w.cnt_b; P.vals[2] = w.vals_b; P.idx[2] = w.idx_b; P.pad[2] = w.pad_b;
-    }
+    const SweepParts P = sweep_parts(w);
     const long W = 1L << w.wlog;
     // (two buffers only where the plan's window leaves room for them)
-    const int nbuf = (g_tune.sweep_nbuf == 2 && 2 * (size_t)W * sizeof(HT) <= 160 * 1024) ? 2 : 1;
+    const int nbuf = (g_tune.sweep_nbuf == 2 && 2 * (size_t)W * sizeof(HT) <= WG_LDS_BYTES) ? 2 : 1;
     const size_t lds = (size_t)nbuf * (size_t)W * sizeof(HT);
-    // threads per workgroup as for the other sweep kernels: 1 024 (or the tile, if smaller) unless "sweep_threads" asks for fewer
-    int threads = std::min<int>(w.tile_rows, g_tune.sweep_threads > 0 ? g_tune.sweep_threads : 1024);
-    if (w.tile_rows / threads > 4) threads = w.tile_rows / 4;
+    const int threads = sweep_threads(w);
     const int rpl = w.tile_rows / threads;
 #define SWH_LAUNCH(NTV, UU, RP, PM)                                                                                              \
     do {                                                                                                                         \

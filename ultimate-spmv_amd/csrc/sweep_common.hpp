@@ -1,6 +1,7 @@
 // What the column-window sweep kernels share (sweep_kernels.hip: one struct and the ap[dp_sp] pair; sweep_ap_hp_kernels.hip: the
-// splits with an fp16 part): the address-space types of the LDS-DMA, the lane's place in a ballot, and the batches of accumulator
-// updates under the rounds' lane masks.
+// splits with an fp16 part; ap_spmmv_sweep.hip, ap_hp_spmmv_sweep.hip: their block twins): the address-space types of the LDS-DMA, the
+// lane's place in a ballot, the plan's per-part arrays as a kernel argument, the operands of a window element, and the batches of
+// accumulator updates under the rounds' lane masks.
 #pragma once
 #include "uspmv_device.hpp"
 
@@ -12,6 +13,53 @@ typedef __attribute__((address_space(1))) const void glb_cvoid_t;
 // active lanes strictly below this one
 __device__ __forceinline__ unsigned lanes_below(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// the plan's per-part arrays as the kernels of the splits with an fp16 part take them: slot 0 hi, 1 mid, 2 hp; [1] is unused unless
+// ap[dp_sp_hp]
+struct SweepParts {
+    const unsigned *wave_off[3];
+    const unsigned char *cnt[3];
+    const void *vals[3];
+    const unsigned short *idx[3];
+    const int *pad[3];
+};
+// the plan stores its parts in the order of the split: [hi, hp] goes to slots 0 and 2, [hi, mid, hp] to 0, 1, 2
+inline SweepParts sweep_parts(const uspmv_dmat::SweepPlan &w) {
+    SweepParts P{};
+    for (int k = 0; k < w.n_parts; ++k) {
+        const int slot = (w.n_parts == 2 && k == 1) ? 2 : k;
+        const auto &pt = w.part[k];
+        P.wave_off[slot] = pt.wave_off; P.cnt[slot] = pt.cnt; P.vals[slot] = pt.vals; P.idx[slot] = pt.idx; P.pad[slot] = pt.pad;
+    }
+    return P;
+}
+
+// the stored value widened to the type the product is formed in (double for a double x, float for a float x); exact
+__device__ __forceinline__ double hp_widen(double v, double) { return v; }
+__device__ __forceinline__ double hp_widen(float v, double) { return (double)v; }
+__device__ __forceinline__ double hp_widen(unsigned short v, double) { return (double)hp_val(v); }
+__device__ __forceinline__ float hp_widen(float v, float) { return v; }
+__device__ __forceinline__ float hp_widen(unsigned short v, float) { return hp_val(v); }
+
+// the BS operands of window element i of a block kernel's LDS image: one X row of the row-major image (16-byte reads; 8 bytes for two
+// floats), or one element of each plane
+template <typename HT, int BS, bool XCOL>
+__device__ __forceinline__ void window_x(const HT *win, const int wlog, const unsigned i, HT (&x)[BS]) {
+    if constexpr (XCOL) {
+#pragma unroll
+        for (int w = 0; w < BS; ++w) x[w] = win[i + ((unsigned)w << wlog)];
+    } else {
+        constexpr int PE = (int)(16 / sizeof(HT)) < BS ? (int)(16 / sizeof(HT)) : BS;
+        typedef HT piece_t __attribute__((ext_vector_type(PE)));
+        const piece_t *xp = (const piece_t *)(win + i * BS);
+#pragma unroll
+        for (int k = 0; k < BS / PE; ++k) {
+            const piece_t t = xp[k];
+#pragma unroll
+            for (int e = 0; e < PE; ++e) x[k * PE + e] = t[e];
+        }
+    }
 }
 
 // A batch of U fused multiply-adds, each under ITS round's lane mask: EXEC is set to the round's ballot, so that a lane that sits the

@@ -261,25 +261,25 @@ __global__ void __launch_bounds__(1024) scs_spmv_sweep(const int wlog, const int
 
 template <typename VT, bool AP>
 int launch_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st) {
-    const long W = 1L << A->sw.wlog;
+    const auto &w = A->sw;
+    const auto &p0 = w.part[0], &p1 = w.part[1];          // (the second part: the sp part of the pair; empty for one struct)
+    const long W = 1L << w.wlog;
     // (two buffers only where the plan's window leaves room for them)
-    const int nbuf = (g_tune.sweep_nbuf == 2 && 2 * (size_t)W * sizeof(VT) <= 160 * 1024) ? 2 : 1;
+    const int nbuf = (g_tune.sweep_nbuf == 2 && 2 * (size_t)W * sizeof(VT) <= WG_LDS_BYTES) ? 2 : 1;
     const size_t lds = (size_t)nbuf * (size_t)W * sizeof(VT);
     const int remap = g_tune.sweep_remap;
-    // threads per workgroup: 1 024 (or the tile, if smaller) unless "sweep_threads" asks for fewer -- a lane then owns more rows
-    int threads = std::min<int>(A->sw.tile_rows, g_tune.sweep_threads > 0 ? g_tune.sweep_threads : 1024);
-    if (A->sw.tile_rows / threads > 4) threads = A->sw.tile_rows / 4;
-    const int rpl = A->sw.tile_rows / threads;
+    const int threads = sweep_threads(w);
+    const int rpl = w.tile_rows / threads;
     const bool pair = g_tune.sweep_pair != 0 && (AP || rpl >= 2);
 #define SW_LAUNCH(NTV, NB, UU, RP)                                                                                          \
     do {                                                                                                                    \
         auto kfn = scs_spmv_sweep<VT, AP, NTV, NB, UU, RP>;                                                                 \
         if (pair) kfn = g_tune.sweep_pair == 2 ? scs_spmv_sweep<VT, AP, NTV, NB, UU, RP, 2> : scs_spmv_sweep<VT, AP, NTV, NB, UU, RP, 1>; \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)A->sw.n_tiles), dim3(threads), lds, st, A->sw.wlog, A->sw.tile_ids,           \
-                           A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off, A->sw.cnt,        \
-                           (const VT *)A->sw.vals, A->sw.idx, A->sw.pad, A->sw.wave_off_b, A->sw.cnt_b, (const float *)A->sw.vals_b,        \
-                           A->sw.idx_b, A->sw.pad_b, x, y, (long)A->sw.x_len, (long)A->n_store, remap);                      \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)w.n_tiles), dim3(threads), lds, st, w.wlog, w.tile_ids.get(), w.smin.get(),   \
+                           w.S.get(), (const unsigned long long *)w.cnt_off, p0.wave_off.get(), p0.cnt.get(),                \
+                           (const VT *)p0.vals, p0.idx.get(), p0.pad.get(), p1.wave_off.get(), p1.cnt.get(),                 \
+                           (const float *)p1.vals, p1.idx.get(), p1.pad.get(), x, y, (long)w.x_len, (long)A->n_store, remap); \
     } while (0)
 #define SW_LAUNCH_R(NTV, NB, UU) do { if (rpl == 4) SW_LAUNCH(NTV, NB, UU, 4); else if (rpl == 2) SW_LAUNCH(NTV, NB, UU, 2); else SW_LAUNCH(NTV, NB, UU, 1); } while (0)
 #define SW_LAUNCH_U(NTV, NB) do { if (g_tune.sweep_unroll >= 8) SW_LAUNCH_R(NTV, NB, 8); else SW_LAUNCH_R(NTV, NB, 4); } while (0)

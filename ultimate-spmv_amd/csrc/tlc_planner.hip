@@ -108,18 +108,16 @@ int install_host_plan(uspmv_dmat *const parts[3], const uspmv_tlc_plan &p, bool 
 }
 
 // Wide, irregular rows: most tiles touch too many x lines to stage them.  When the plan stages fewer than half of its tiles, try the
-// column-window sweep (from the host structs, or -- s == nullptr -- built on the device as well); *took: it covers at least half of its
-// tiles and stays on the handles.  One struct, the ap[dp_sp] pair (B) and the splits with an fp16 part (B, B3) alike.
-int sweep_takes_over(uspmv_dmat *A, uspmv_dmat *B, const uspmv_scs *s, const uspmv_scs *sB, const PlanStats &st, const char *who, bool *took,
-                     uspmv_dmat *B3 = nullptr, const uspmv_scs *sB3 = nullptr) {
+// column-window sweep (from the host structs, or -- ss == nullptr -- built on the device as well); *took: it covers at least half of its
+// tiles and stays on the handles.  One struct, the ap[dp_sp] pair and the splits with an fp16 part alike: ms / ss hold the n parts.
+int sweep_takes_over(uspmv_dmat *const ms[], const uspmv_scs *const ss[], int n, const PlanStats &st, const char *who, bool *took) {
     *took = false;
-    uspmv_dmat *const ms[3] = {A, B, B3};
-    for (uspmv_dmat *M : ms) if (M) M->sw = {};
+    for (int k = 0; k < n; ++k) ms[k]->sw = {};
     if (!g_tune.sweep || (st.valid && stages_half(st.n_tiles, st.n_staged))) return USPMV_OK;
     int64_t swt = 0, sws = 0;
-    if (int rc = s ? sweep_plan_install(A, B, s, sB, 0, 0, &swt, &sws, who, B3, sB3) : sweep_plan_install_device(A, B, 0, 0, &swt, &sws, who, B3)) return rc;
-    *took = A->sw.on && stages_half(swt, sws);
-    if (!*took) for (uspmv_dmat *M : ms) if (M) M->sw = {};
+    if (int rc = ss ? sweep_plan_install(ms, ss, n, 0, 0, &swt, &sws, who) : sweep_plan_install_device(ms, n, 0, 0, &swt, &sws, who)) return rc;
+    *took = ms[0]->sw.on && stages_half(swt, sws);
+    if (!*took) for (int k = 0; k < n; ++k) ms[k]->sw = {};
     return USPMV_OK;
 }
 
@@ -546,7 +544,8 @@ int device_plan_install(uspmv_dmat *A, uspmv_dmat *B, int max_lines, int64_t *n_
         B->tlc = std::move(kept[1]);
     }
     bool swept = false;
-    if (int rc2 = sweep_takes_over(A, B, nullptr, nullptr, st, who, &swept)) return rc2;
+    uspmv_dmat *const ms[2] = {A, B};
+    if (int rc2 = sweep_takes_over(ms, nullptr, B ? 2 : 1, st, who, &swept)) return rc2;
     if (swept) {             // (n_tiles / n_staged keep describing the tile-local-column attempt, as in uspmv_dmat_optimize;
         A->tlc = {};         //  uspmv_dmat_plan_info tells which plan the handle ended up with)
         if (B) B->tlc = {};
@@ -674,7 +673,7 @@ int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPla
     }
     if (!elem) {
         bool swept = false;
-        if (int rc = sweep_takes_over(A, nullptr, s, nullptr, stats_of(p), who, &swept)) return rc;
+        if (int rc = sweep_takes_over(&A, &s, 1, stats_of(p), who, &swept)) return rc;
         if (swept) return USPMV_OK;
     }
     if (!p.valid) return USPMV_OK;                              // nothing worth staging: plain kernel stays
@@ -795,9 +794,10 @@ int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t
     if (n_tiles) *n_tiles = p.n_tiles;
     if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
     bool swept = false;
-    if (int rc = sweep_takes_over(dp, sp, s_dp, s_sp, st, who, &swept)) return rc;
-    if (swept || !p.valid) return USPMV_OK;
     uspmv_dmat *const parts[3] = {dp, sp, nullptr};
+    const uspmv_scs *const ss[2] = {s_dp, s_sp};
+    if (int rc = sweep_takes_over(parts, ss, 2, st, who, &swept)) return rc;
+    if (swept || !p.valid) return USPMV_OK;
     return install_host_plan(parts, p, /*elem=*/false, who);
 }
 
@@ -834,7 +834,7 @@ int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t 
     if (n_tiles) *n_tiles = p.n_tiles;              // (the line plan's outcome also when the sweep takes over, as in uspmv_dmat_optimize_ap)
     if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
     bool swept = false;
-    if (int rc = sweep_takes_over(ms[0], ms[1], ss[0], ss[1], stats_of(p), who, &swept, ms[2], ss[2])) return rc;
+    if (int rc = sweep_takes_over(ms, ss, mid ? 3 : 2, stats_of(p), who, &swept)) return rc;
     if (swept || !p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
     return install_host_plan(ms, p, /*elem=*/false, who);
 }
@@ -850,7 +850,7 @@ int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_
     if (n_tiles) *n_tiles = st.n_tiles;
     if (n_staged) *n_staged = st.n_staged;
     bool swept = false;
-    if (int rc = sweep_takes_over(ms[0], ms[1], nullptr, nullptr, st, who, &swept, ms[2])) return rc;
+    if (int rc = sweep_takes_over(ms, nullptr, mid ? 3 : 2, st, who, &swept)) return rc;
     if (swept || !ap_hp_plan_worth(st.n_tiles, st.n_staged))
         for (uspmv_dmat_t *M : ms) if (M) M->tlc = {};
     return USPMV_OK;

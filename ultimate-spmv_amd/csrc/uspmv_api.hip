@@ -789,112 +789,97 @@ int uspmv_dmat_optimize_block_device(uspmv_dmat_t *A, int block_vec_size, int64_
 extern "C++" {
 namespace uspmv_dev {
 
-// builds and uploads a sweep plan for A (and, when B/sB [and B3/sB3] are given, for the parts A/B[/B3] of an ap split); returns the
-// number of sweep tiles.  A plan on the handles is replaced.
-int sweep_plan_install(uspmv_dmat_t *A, uspmv_dmat_t *B, const uspmv_scs_t *s, const uspmv_scs_t *sB, int wlog, int tile_rows,
-                              int64_t *n_tiles, int64_t *n_sweep, const char *who, uspmv_dmat_t *B3, const uspmv_scs_t *sB3) {
-    A->sw = {};
-    if (B) B->sw = {};
-    if (B3) B3->sw = {};
+// What the two builders of a sweep plan do before they look at the matrix: a plan on the handles is dropped, the results are zeroed,
+// wlog and tile_rows get their defaults (vsz: bytes of an x element, n_pad: padded rows), and a window that does not fit LDS is refused.
+static int sweep_plan_defaults(uspmv_dmat_t *const parts[], int n_parts, size_t vsz, int64_t n_pad, int *wlog, int *tile_rows,
+                               int64_t *n_tiles, int64_t *n_sweep, const char *who) {
+    for (int k = 0; k < n_parts; ++k) parts[k]->sw = {};
     if (n_tiles) *n_tiles = 0;
     if (n_sweep) *n_sweep = 0;
-    const size_t vsz = s->dtype == USPMV_F64 ? 8 : 4;
-    if (wlog <= 0) wlog = g_tune.sweep_wlog;
+    if (*wlog <= 0) *wlog = g_tune.sweep_wlog;
     const int nbuf = g_tune.sweep_nbuf == 2 ? 2 : 1;
     // window: as much of the LDS as one buffer per workgroup allows (128 KiB; 64 KiB each when double-buffered) -- on config 4b every
     // doubling from 8 KiB up paid (1.51 / 0.97 / 0.74 / 0.61 ms for the ap kernel at 2^10 .. 2^13 elements, 0.55 at 2^14 with 4 096-row
     // tiles; profiles/r02/config4b_sweep_variants.txt): fewer, longer rounds per wave and fewer barriers
-    if (wlog <= 0) wlog = (vsz == 8 ? 13 : 14) + (nbuf == 1 ? 1 : 0);
-    if (((size_t)1 << wlog) * vsz * (size_t)nbuf > 160 * 1024)
-        return uspmv::fail(USPMV_ERR_INVALID, "%s: %d window buffer(s) of 2^%d elements do not fit the 160 KB of LDS", who, nbuf, wlog);
-    if (tile_rows <= 0) tile_rows = g_tune.sweep_tile_rows;
+    if (*wlog <= 0) *wlog = (vsz == 8 ? 13 : 14) + (nbuf == 1 ? 1 : 0);
+    if (((size_t)1 << *wlog) * vsz * (size_t)nbuf > WG_LDS_BYTES)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: %d window buffer(s) of 2^%d elements do not fit the 160 KB of LDS", who, nbuf, *wlog);
+    if (*tile_rows <= 0) *tile_rows = g_tune.sweep_tile_rows;
     // rows per tile: the windows are staged once per tile, so more rows = fewer staged bytes per non-zero (a lane owns up to four rows);
     // but at least ~1.5 tiles per CU
-    if (tile_rows <= 0) {
-        const int64_t n_pad = s->n_chunks * s->C;
-        tile_rows = 4096;
-        while (tile_rows > 1024 && n_pad / tile_rows < 384) tile_rows /= 2;
+    if (*tile_rows <= 0) {
+        *tile_rows = 4096;
+        while (*tile_rows > 1024 && n_pad / *tile_rows < 384) *tile_rows /= 2;
     }
-    uspmv_sweep_plan p;
-    const double max_stage = g_tune.sweep_max_stage > 0 ? (double)g_tune.sweep_max_stage : 24.0;
-    if (int rc = uspmv_build_sweep_plan(s, sB, wlog, tile_rows, max_stage, &p, sB3)) return rc;
-    if (n_tiles) *n_tiles = p.n_tiles;
-    if (n_sweep) *n_sweep = p.valid ? p.n_sweep_tiles : 0;
-    if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] sweep plan: tile_rows=%d wlog=%d tiles=%lld sweep=%lld rest_chunks=%zu elements=%zu cnt_bytes=%zu\n",
-                                         p.tile_rows, p.wlog, (long long)p.n_tiles, (long long)p.n_sweep_tiles, p.rest_chunks.size(), p.idx.size(), p.cnt.size());
-    if (!p.valid) return USPMV_OK;
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = A->sw.tile_ids.upload(p.tile_ids.data(), p.tile_ids.size() * 4);
-    if (e == hipSuccess) e = A->sw.smin.upload(p.t_smin.data(), p.t_smin.size() * 4);
-    if (e == hipSuccess) e = A->sw.S.upload(p.t_S.data(), p.t_S.size() * 4);
-    if (e == hipSuccess) e = A->sw.cnt_off.upload(p.t_cnt_off.data(), p.t_cnt_off.size() * 8);
-    if (e == hipSuccess) e = A->sw.wave_off.upload(p.wave_off.data(), p.wave_off.size() * 4);
-    if (e == hipSuccess) e = A->sw.cnt.upload(p.cnt.data(), p.cnt.size());
-    if (e == hipSuccess) e = A->sw.vals.upload(vsz == 8 ? (const void *)p.vals_f64.data() : (const void *)p.vals_f32.data(), p.idx.size() * vsz);
-    if (e == hipSuccess) e = A->sw.idx.upload(p.idx.data(), p.idx.size() * 2);
-    if (e == hipSuccess) e = A->sw.pad.upload(p.pad_col.data(), p.pad_col.size() * 4);
-    if (e == hipSuccess) e = A->sw.rest.upload(p.rest_chunks.data(), p.rest_chunks.size() * 4);
-    if (B) {
-        if (e == hipSuccess) e = A->sw.wave_off_b.upload(p.wave_off_b.data(), p.wave_off_b.size() * 4);
-        if (e == hipSuccess) e = A->sw.cnt_b.upload(p.cnt_b.data(), p.cnt_b.size());
-        if (e == hipSuccess) e = sB->dtype == USPMV_F16 ? A->sw.vals_b.upload(p.vals_b_f16.data(), p.idx_b.size() * 2)
-                                                        : A->sw.vals_b.upload(p.vals_b_f32.data(), p.idx_b.size() * 4);
-        if (e == hipSuccess) e = A->sw.idx_b.upload(p.idx_b.data(), p.idx_b.size() * 2);
-        if (e == hipSuccess) e = A->sw.pad_b.upload(p.pad_col_b.data(), p.pad_col_b.size() * 4);
-    }
-    if (B3) {
-        if (e == hipSuccess) e = A->sw.wave_off_c.upload(p.wave_off_c.data(), p.wave_off_c.size() * 4);
-        if (e == hipSuccess) e = A->sw.cnt_c.upload(p.cnt_c.data(), p.cnt_c.size());
-        if (e == hipSuccess) e = A->sw.vals_c.upload(p.vals_c_f16.data(), p.idx_c.size() * 2);
-        if (e == hipSuccess) e = A->sw.idx_c.upload(p.idx_c.data(), p.idx_c.size() * 2);
-        if (e == hipSuccess) e = A->sw.pad_c.upload(p.pad_col_c.data(), p.pad_col_c.size() * 4);
-    }
-    if (e != hipSuccess) {
-        A->sw = {};
-        return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
-    }
-    static uint64_t next_sweep_id = 1;
-    const uint64_t id = next_sweep_id++;
-    A->sw.on = true; A->sw.tile_rows = p.tile_rows; A->sw.wlog = p.wlog; A->sw.n_tiles = p.n_sweep_tiles; A->sw.all_tiles = p.n_tiles;
-    A->sw.x_len = p.x_len_min; A->sw.n_rest = (int64_t)p.rest_chunks.size(); A->sw.plan_id = id;
-    A->sw.n_vals = (int64_t)p.idx.size() - 64; A->sw.n_vals_b = B ? (int64_t)p.idx_b.size() - 64 : 0; A->sw.cnt_bytes = (int64_t)p.cnt.size();
-    A->sw.n_vals_c = B3 ? (int64_t)p.idx_c.size() - 64 : 0;
-    A->sw.n_parts = B3 ? 3 : B ? 2 : 1;
-    if (B) A->sw.dtype_b = sB->dtype;
-    for (uspmv_dmat_t *M : {B, B3})
-        if (M) { M->sw.on = true; M->sw.plan_id = id; M->sw.n_tiles = p.n_sweep_tiles; M->sw.all_tiles = p.n_tiles; }
     return USPMV_OK;
 }
 
-// The same plan from the handle's DEVICE arrays (csrc/sweep_plan_kernels.hip): a scan kernel per struct, the tile decisions and the
-// offsets on the host (O(n_tiles); 16 bytes per 64-row group come back), a fill kernel per struct.  Same defaults, same criteria and
-// -- by construction of the fill kernel -- the same arrays as sweep_plan_install builds from a host struct.
-int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who,
-                              uspmv_dmat_t *B3) {
-    A->sw = {};
-    if (B) B->sw = {};
-    if (B3) B3->sw = {};
-    if (n_tiles) *n_tiles = 0;
-    if (n_sweep) *n_sweep = 0;
-    const int64_t C = A->C, nc = A->n_chunks;
-    const size_t vsz = A->dtype == USPMV_F64 ? 8 : 4;
-    if (wlog <= 0) wlog = g_tune.sweep_wlog;
-    const int nbuf = g_tune.sweep_nbuf == 2 ? 2 : 1;
-    if (wlog <= 0) wlog = (vsz == 8 ? 13 : 14) + (nbuf == 1 ? 1 : 0);
-    if (((size_t)1 << wlog) * vsz * (size_t)nbuf > 160 * 1024)
-        return uspmv::fail(USPMV_ERR_INVALID, "%s: %d window buffer(s) of 2^%d elements do not fit the 160 KB of LDS", who, nbuf, wlog);
-    if (tile_rows <= 0) tile_rows = g_tune.sweep_tile_rows;
-    const int64_t n_pad = nc * C;
-    if (tile_rows <= 0) {
-        tile_rows = 4096;
-        while (tile_rows > 1024 && n_pad / tile_rows < 384) tile_rows /= 2;
+// ... and after the arrays are on the first handle: the plan's metadata there; the other handles carry the plan id and the tile counts
+static void sweep_plan_stamp(uspmv_dmat_t *const parts[], int n_parts, uint64_t id, int tile_rows, int wlog, int64_t n_sweep,
+                             int64_t n_tiles, int64_t x_len, int64_t n_rest, int64_t cnt_bytes) {
+    auto &w = parts[0]->sw;
+    w.on = true; w.tile_rows = tile_rows; w.wlog = wlog; w.n_tiles = n_sweep; w.all_tiles = n_tiles;
+    w.x_len = x_len; w.n_rest = n_rest; w.plan_id = id; w.cnt_bytes = cnt_bytes; w.n_parts = n_parts;
+    for (int k = 1; k < n_parts; ++k) {
+        auto &o = parts[k]->sw;
+        o.on = true; o.plan_id = id; o.n_tiles = n_sweep; o.all_tiles = n_tiles;
     }
+}
+
+// builds and uploads a sweep plan for the one struct, or the n_parts parts of an ap split, behind parts / ss; returns the number of
+// sweep tiles.  A plan on the handles is replaced.
+int sweep_plan_install(uspmv_dmat_t *const parts[], const uspmv_scs_t *const ss[], int n_parts, int wlog, int tile_rows,
+                       int64_t *n_tiles, int64_t *n_sweep, const char *who) {
+    const uspmv_scs_t *s = ss[0];
+    if (int rc = sweep_plan_defaults(parts, n_parts, s->dtype == USPMV_F64 ? 8 : 4, s->n_chunks * s->C, &wlog, &tile_rows, n_tiles, n_sweep, who))
+        return rc;
+    uspmv_sweep_plan p;
+    const double max_stage = g_tune.sweep_max_stage > 0 ? (double)g_tune.sweep_max_stage : 24.0;
+    if (int rc = uspmv_build_sweep_plan(ss, n_parts, wlog, tile_rows, max_stage, &p)) return rc;
+    if (n_tiles) *n_tiles = p.n_tiles;
+    if (n_sweep) *n_sweep = p.valid ? p.n_sweep_tiles : 0;
+    if (getenv("USPMV_VERBOSE")) fprintf(stderr, "[uspmv] sweep plan: tile_rows=%d wlog=%d tiles=%lld sweep=%lld rest_chunks=%zu elements=%zu cnt_bytes=%zu\n",
+                                         p.tile_rows, p.wlog, (long long)p.n_tiles, (long long)p.n_sweep_tiles, p.rest_chunks.size(), p.part[0].idx.size(), p.part[0].cnt.size());
+    if (!p.valid) return USPMV_OK;
+    auto &w = parts[0]->sw;
+    hipError_t e = w.tile_ids.upload(p.tile_ids.data(), p.tile_ids.size() * 4);
+    if (e == hipSuccess) e = w.smin.upload(p.t_smin.data(), p.t_smin.size() * 4);
+    if (e == hipSuccess) e = w.S.upload(p.t_S.data(), p.t_S.size() * 4);
+    if (e == hipSuccess) e = w.cnt_off.upload(p.t_cnt_off.data(), p.t_cnt_off.size() * 8);
+    if (e == hipSuccess) e = w.rest.upload(p.rest_chunks.data(), p.rest_chunks.size() * 4);
+    for (int k = 0; k < n_parts; ++k) {
+        const auto &h = p.part[k];
+        auto &d = w.part[k];
+        d.dtype = h.dtype; d.n_vals = (int64_t)h.idx.size() - 64;
+        if (e == hipSuccess) e = d.wave_off.upload(h.wave_off.data(), h.wave_off.size() * 4);
+        if (e == hipSuccess) e = d.cnt.upload(h.cnt.data(), h.cnt.size());
+        if (e == hipSuccess) e = d.vals.upload(h.vals(), h.idx.size() * uspmv_dtype_bytes(h.dtype));
+        if (e == hipSuccess) e = d.idx.upload(h.idx.data(), h.idx.size() * 2);
+        if (e == hipSuccess) e = d.pad.upload(h.pad_col.data(), h.pad_col.size() * 4);
+    }
+    if (e != hipSuccess) {
+        w = {};
+        return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
+    }
+    static uint64_t next_sweep_id = 1;
+    sweep_plan_stamp(parts, n_parts, next_sweep_id++, p.tile_rows, p.wlog, p.n_sweep_tiles, p.n_tiles, p.x_len_min, (int64_t)p.rest_chunks.size(),
+                     (int64_t)p.part[0].cnt.size());
+    return USPMV_OK;
+}
+
+// The same plan from the handles' DEVICE arrays (csrc/sweep_plan_kernels.hip): a scan kernel per struct, the tile decisions and the
+// offsets on the host (O(n_tiles); 16 bytes per 64-row group come back), a fill kernel per struct.  Same defaults, same criteria and
+// -- by construction of the fill kernel -- the same arrays as sweep_plan_install builds from host structs.
+int sweep_plan_install_device(uspmv_dmat_t *const parts[], int ns, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep,
+                              const char *who) {
+    uspmv_dmat_t *const A = parts[0];
+    const int64_t C = A->C, nc = A->n_chunks, n_pad = nc * C;
+    const size_t vsz = A->dtype == USPMV_F64 ? 8 : 4;
+    if (int rc = sweep_plan_defaults(parts, ns, vsz, n_pad, &wlog, &tile_rows, n_tiles, n_sweep, who)) return rc;
     if (tile_rows != 256 && tile_rows != 512 && tile_rows != 1024 && tile_rows != 2048 && tile_rows != 4096) tile_rows = 1024;
     if (C < 1 || C > 64 || 64 % C != 0 || nc < 1 || wlog < 8 || wlog > 16) return USPMV_OK;
-    if (A->n_elements > (int64_t)UINT32_MAX || (B && B->n_elements > (int64_t)UINT32_MAX) || (B3 && B3->n_elements > (int64_t)UINT32_MAX)) return USPMV_OK;
+    for (int w = 0; w < ns; ++w) if (parts[w]->n_elements > (int64_t)UINT32_MAX) return USPMV_OK;
     const int64_t R = tile_rows, nt = (n_pad + R - 1) / R, wpt = R / 64, n_groups = (n_pad + 63) / 64;
-    const int ns = B3 ? 3 : B ? 2 : 1;
-    const uspmv_dmat_t *M[3] = {A, B, B3};
     const double max_stage = g_tune.sweep_max_stage > 0 ? (double)g_tune.sweep_max_stage : 24.0;
     // ---- scan
     DeviceBuf<int> d_le[3], d_pad[3], d_grp[3], d_max;
@@ -908,7 +893,7 @@ int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int ti
     std::vector<int32_t> grp[3];
     int max_col = 0;
     int rc = USPMV_OK;
-    for (int w = 0; w < ns && !rc; ++w) rc = launch_sweep_scan(M[w], wlog, d_le[w], d_pad[w], d_grp[w], d_max, nullptr);
+    for (int w = 0; w < ns && !rc; ++w) rc = launch_sweep_scan(parts[w], wlog, d_le[w], d_pad[w], d_grp[w], d_max, nullptr);
     for (int w = 0; w < ns && !rc; ++w) {
         grp[w].resize((size_t)n_groups * 4);
         e = hipMemcpy(grp[w].data(), d_grp[w], 16 * (size_t)n_groups, hipMemcpyDeviceToHost);
@@ -954,52 +939,35 @@ int sweep_plan_install_device(uspmv_dmat_t *A, uspmv_dmat_t *B, int wlog, int ti
     }
     // ---- device arrays of the plan
     constexpr size_t SPARE = 64;
-    if (e == hipSuccess) e = A->sw.tile_ids.upload(tile_ids.data(), tile_ids.size() * 4);
-    if (e == hipSuccess) e = A->sw.smin.upload(t_smin.data(), t_smin.size() * 4);
-    if (e == hipSuccess) e = A->sw.S.upload(t_S.data(), t_S.size() * 4);
-    if (e == hipSuccess) e = A->sw.cnt_off.upload(t_cnt_off.data(), t_cnt_off.size() * 8);
-    if (e == hipSuccess) e = A->sw.wave_off.upload(wave_off[0].data(), wave_off[0].size() * 4);
-    if (e == hipSuccess) e = A->sw.rest.upload(rest.data(), rest.size() * 4);
-    if (e == hipSuccess) e = A->sw.cnt.zeros((size_t)cnt_bytes);
-    if (e == hipSuccess) e = A->sw.vals.zeros(((size_t)tot[0] + SPARE) * vsz);
-    if (e == hipSuccess) e = A->sw.idx.zeros(((size_t)tot[0] + SPARE) * 2);
-    if (e == hipSuccess) e = A->sw.pad.zeros((size_t)(nsw * R) * 4);
-    if (B) {
-        if (e == hipSuccess) e = A->sw.wave_off_b.upload(wave_off[1].data(), wave_off[1].size() * 4);
-        if (e == hipSuccess) e = A->sw.cnt_b.zeros((size_t)cnt_bytes);
-        if (e == hipSuccess) e = A->sw.vals_b.zeros(((size_t)tot[1] + SPARE) * uspmv_dtype_bytes(B->dtype));
-        if (e == hipSuccess) e = A->sw.idx_b.zeros(((size_t)tot[1] + SPARE) * 2);
-        if (e == hipSuccess) e = A->sw.pad_b.zeros((size_t)(nsw * R) * 4);
+    auto &sw = A->sw;
+    if (e == hipSuccess) e = sw.tile_ids.upload(tile_ids.data(), tile_ids.size() * 4);
+    if (e == hipSuccess) e = sw.smin.upload(t_smin.data(), t_smin.size() * 4);
+    if (e == hipSuccess) e = sw.S.upload(t_S.data(), t_S.size() * 4);
+    if (e == hipSuccess) e = sw.cnt_off.upload(t_cnt_off.data(), t_cnt_off.size() * 8);
+    if (e == hipSuccess) e = sw.rest.upload(rest.data(), rest.size() * 4);
+    for (int w = 0; w < ns; ++w) {
+        auto &d = sw.part[w];
+        d.dtype = parts[w]->dtype; d.n_vals = tot[w];
+        if (e == hipSuccess) e = d.wave_off.upload(wave_off[w].data(), wave_off[w].size() * 4);
+        if (e == hipSuccess) e = d.cnt.zeros((size_t)cnt_bytes);
+        if (e == hipSuccess) e = d.vals.zeros(((size_t)tot[w] + SPARE) * uspmv_dtype_bytes(d.dtype));
+        if (e == hipSuccess) e = d.idx.zeros(((size_t)tot[w] + SPARE) * 2);
+        if (e == hipSuccess) e = d.pad.zeros((size_t)(nsw * R) * 4);
     }
-    if (B3) {
-        if (e == hipSuccess) e = A->sw.wave_off_c.upload(wave_off[2].data(), wave_off[2].size() * 4);
-        if (e == hipSuccess) e = A->sw.cnt_c.zeros((size_t)cnt_bytes);
-        if (e == hipSuccess) e = A->sw.vals_c.zeros(((size_t)tot[2] + SPARE) * uspmv_dtype_bytes(B3->dtype));
-        if (e == hipSuccess) e = A->sw.idx_c.zeros(((size_t)tot[2] + SPARE) * 2);
-        if (e == hipSuccess) e = A->sw.pad_c.zeros((size_t)(nsw * R) * 4);
+    for (int w = 0; w < ns; ++w) {
+        auto &d = sw.part[w];
+        if (e == hipSuccess && launch_sweep_fill(parts[w], wlog, (int)R, (long)nsw, sw.tile_ids, sw.smin, sw.S, (const unsigned long long *)sw.cnt_off,
+                                                 d.wave_off, d_le[w], d_pad[w], d.cnt, d.vals, d.idx, d.pad, nullptr) != USPMV_OK) e = hipErrorUnknown;
     }
-    if (e == hipSuccess && launch_sweep_fill(A, wlog, (int)R, (long)nsw, A->sw.tile_ids, A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off,
-                                             d_le[0], d_pad[0], A->sw.cnt, A->sw.vals, A->sw.idx, A->sw.pad, nullptr) != USPMV_OK) e = hipErrorUnknown;
-    if (e == hipSuccess && B && launch_sweep_fill(B, wlog, (int)R, (long)nsw, A->sw.tile_ids, A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off_b,
-                                                  d_le[1], d_pad[1], A->sw.cnt_b, A->sw.vals_b, A->sw.idx_b, A->sw.pad_b, nullptr) != USPMV_OK) e = hipErrorUnknown;
-    if (e == hipSuccess && B3 && launch_sweep_fill(B3, wlog, (int)R, (long)nsw, A->sw.tile_ids, A->sw.smin, A->sw.S, (const unsigned long long *)A->sw.cnt_off, A->sw.wave_off_c,
-                                                   d_le[2], d_pad[2], A->sw.cnt_c, A->sw.vals_c, A->sw.idx_c, A->sw.pad_c, nullptr) != USPMV_OK) e = hipErrorUnknown;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     for (int w = 0; w < 3; ++w) { d_le[w].reset(); d_pad[w].reset(); d_grp[w].reset(); }
     d_max.reset();
     if (e != hipSuccess) {
-        A->sw = {};
+        sw = {};
         return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     static uint64_t next_dev_sweep_id = (uint64_t)1 << 41;
-    const uint64_t id = next_dev_sweep_id++;
-    A->sw.on = true; A->sw.tile_rows = tile_rows; A->sw.wlog = wlog; A->sw.n_tiles = nsw; A->sw.all_tiles = nt;
-    A->sw.x_len = (int64_t)max_col + 1; A->sw.n_rest = (int64_t)rest.size(); A->sw.plan_id = id;
-    A->sw.n_vals = tot[0]; A->sw.n_vals_b = B ? tot[1] : 0; A->sw.n_vals_c = B3 ? tot[2] : 0; A->sw.cnt_bytes = cnt_bytes;
-    A->sw.n_parts = ns;
-    if (B) A->sw.dtype_b = B->dtype;
-    for (uspmv_dmat_t *Q : {B, B3})
-        if (Q) { Q->sw.on = true; Q->sw.plan_id = id; Q->sw.n_tiles = nsw; Q->sw.all_tiles = nt; }
+    sweep_plan_stamp(parts, ns, next_dev_sweep_id++, tile_rows, wlog, nsw, nt, (int64_t)max_col + 1, (int64_t)rest.size(), cnt_bytes);
     return USPMV_OK;
 }
 
@@ -1013,7 +981,7 @@ int uspmv_dmat_optimize_sweep(uspmv_dmat_t *A, const uspmv_scs_t *s, int wlog, i
     if (A->C != s->C || A->n_chunks != s->n_chunks || A->dtype != s->dtype)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_sweep: handle and host struct do not describe the same matrix");
     if (int rc = require_device()) return rc;
-    return sweep_plan_install(A, nullptr, s, nullptr, wlog, tile_rows, n_tiles, n_sweep, "uspmv_dmat_optimize_sweep");
+    return sweep_plan_install(&A, &s, 1, wlog, tile_rows, n_tiles, n_sweep, "uspmv_dmat_optimize_sweep");
 }
 
 int uspmv_dmat_optimize_sweep_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t *s_dp, const uspmv_scs_t *s_sp, int wlog, int tile_rows,
@@ -1026,7 +994,9 @@ int uspmv_dmat_optimize_sweep_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv
         dp->C != sp->C || dp->n_chunks != sp->n_chunks)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_sweep_ap: handles / host structs do not form a dp+sp pair");
     if (int rc = require_device()) return rc;
-    return sweep_plan_install(dp, sp, s_dp, s_sp, wlog, tile_rows, n_tiles, n_sweep, "uspmv_dmat_optimize_sweep_ap");
+    uspmv_dmat_t *const ms[2] = {dp, sp};
+    const uspmv_scs_t *const ss[2] = {s_dp, s_sp};
+    return sweep_plan_install(ms, ss, 2, wlog, tile_rows, n_tiles, n_sweep, "uspmv_dmat_optimize_sweep_ap");
 }
 
 int uspmv_dmat_optimize_sweep_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
@@ -1043,7 +1013,7 @@ int uspmv_dmat_optimize_sweep_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_d
             return uspmv::fail(USPMV_ERR_INVALID, "%s: handles and host structs do not describe the same parts", who);
     }
     if (int rc = require_device()) return rc;
-    return sweep_plan_install(ms[0], ms[1], ss[0], ss[1], wlog, tile_rows, n_tiles, n_sweep, who, ms[2], ss[2]);
+    return sweep_plan_install(ms, ss, mid ? 3 : 2, wlog, tile_rows, n_tiles, n_sweep, who);
 }
 
 int uspmv_dmat_optimize_sweep_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, int wlog, int tile_rows, int64_t *n_tiles,
@@ -1051,7 +1021,8 @@ int uspmv_dmat_optimize_sweep_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, 
     const char *who = "uspmv_dmat_optimize_sweep_device_ap_hp";
     if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
     if (int rc = require_device()) return rc;
-    return sweep_plan_install_device(hi, mid ? mid : hp, wlog, tile_rows, n_tiles, n_sweep, who, mid ? hp : nullptr);
+    uspmv_dmat_t *const ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
+    return sweep_plan_install_device(ms, mid ? 3 : 2, wlog, tile_rows, n_tiles, n_sweep, who);
 }
 
 // The block-vector column-window sweep plan (host/sweep_plan.cpp: uspmv_build_block_sweep_plan; kernel csrc/spmmv_sweep.hip) for 64-byte X
@@ -1073,7 +1044,7 @@ int uspmv_dmat_optimize_block_sweep(uspmv_dmat_t *A, const uspmv_scs_t *s, int b
     // defaults: the largest window (2^11 rows = 128 KiB, one buffer) and 4 096-row tiles measured best on the Queen_4147-class matrix
     // (0.998 / 1.016 ms row- / column-wise; 2^9-row windows with two buffers 1.26 / 1.29: profiles/r04/spmmv_sweep_probe.txt)
     if (wlog <= 0) wlog = 11;
-    if (((size_t)1 << wlog) * 64 > 160 * 1024) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block_sweep: a window of 2^%d rows does not fit the LDS", wlog);
+    if (((size_t)1 << wlog) * 64 > WG_LDS_BYTES) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_block_sweep: a window of 2^%d rows does not fit the LDS", wlog);
     if (tile_rows <= 0) {
         tile_rows = 4096;
         while (tile_rows > 1024 && s->n_chunks * s->C / tile_rows < 384) tile_rows /= 2;   // (at least ~1.5 tiles per CU)
@@ -1167,50 +1138,54 @@ int uspmv_dmat_optimize_sweep_device(uspmv_dmat_t *A, uspmv_dmat_t *sp, int wlog
             return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_optimize_sweep_device: handles do not form a dp+sp pair");
     }
     if (int rc = require_device()) return rc;
-    return sweep_plan_install_device(A, sp, wlog, tile_rows, n_tiles, n_sweep, "uspmv_dmat_optimize_sweep_device");
+    uspmv_dmat_t *const ms[2] = {A, sp};
+    return sweep_plan_install_device(ms, sp ? 2 : 1, wlog, tile_rows, n_tiles, n_sweep, "uspmv_dmat_optimize_sweep_device");
 }
 
-// FNV-1a digests of the sweep plan's device arrays (tests: a plan built on the device must equal the host planner's)
+// FNV-1a digest of a device array (tests: a plan built on the device must equal the host planner's)
+static int device_fnv(const void *d, size_t bytes, uint64_t *out) {
+    uint64_t h = 1469598103934665603ull;
+    if (d && bytes) {
+        std::vector<unsigned char> buf(bytes);
+        HIP_TRY(hipMemcpy(buf.data(), d, bytes, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < bytes; ++k) { h ^= buf[k]; h *= 1099511628211ull; }
+    }
+    *out = h;
+    return USPMV_OK;
+}
+
+// ... of one part's arrays of the sweep plan: wave offsets, counts, values, indices, padding columns
+static int sweep_part_digest(const uspmv_dmat::SweepPlan &w, int part, uint64_t digest[5]) {
+    const auto &pt = w.part[part];
+    const size_t nsw = (size_t)w.n_tiles, wpt = (size_t)w.tile_rows / 64, nv = (size_t)pt.n_vals;
+    int rc = device_fnv(pt.wave_off, nsw * wpt * 4, &digest[0]);
+    if (!rc) rc = device_fnv(pt.cnt, (size_t)w.cnt_bytes, &digest[1]);
+    if (!rc) rc = device_fnv(pt.vals, nv * uspmv_dtype_bytes(pt.dtype), &digest[2]);
+    if (!rc) rc = device_fnv(pt.idx, nv * 2, &digest[3]);
+    if (!rc) rc = device_fnv(pt.pad, nsw * (size_t)w.tile_rows * 4, &digest[4]);
+    return rc;
+}
+
+// ... of the whole plan: digest[0..3] the tile arrays, [4..8] part 0, [9] the rest chunks, [10..14] part 1
 int uspmv_dmat_sweep_plan_digest(const uspmv_dmat_t *A, uint64_t digest[16], int64_t meta[8]) {
     if (int rc = check_dmat(A, "uspmv_dmat_sweep_plan_digest")) return rc;
     if (!digest || !meta) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_sweep_plan_digest: NULL argument");
     for (int k = 0; k < 16; ++k) digest[k] = 0;
-    meta[0] = A->sw.on; meta[1] = A->sw.tile_rows; meta[2] = A->sw.wlog; meta[3] = A->sw.n_tiles; meta[4] = A->sw.all_tiles; meta[5] = A->sw.n_rest;
-    meta[6] = A->sw.n_vals; meta[7] = A->sw.n_vals_b;
-    if (!A->sw.on || !A->sw.tile_ids) return USPMV_OK;
-    std::vector<unsigned char> buf;
-    auto fnv = [&](const void *d, size_t bytes, uint64_t *out) -> int {
-        uint64_t h = 1469598103934665603ull;
-        if (d && bytes) {
-            buf.resize(bytes);
-            HIP_TRY(hipMemcpy(buf.data(), d, bytes, hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < bytes; ++k) { h ^= buf[k]; h *= 1099511628211ull; }
-        }
-        *out = h;
-        return USPMV_OK;
-    };
-    const size_t nsw = (size_t)A->sw.n_tiles, wpt = (size_t)A->sw.tile_rows / 64, vsz = A->dtype == USPMV_F64 ? 8 : 4;
-    int rc = fnv(A->sw.tile_ids, nsw * 4, &digest[0]);
-    if (!rc) rc = fnv(A->sw.smin, nsw * 4, &digest[1]);
-    if (!rc) rc = fnv(A->sw.S, nsw * 4, &digest[2]);
-    if (!rc) rc = fnv(A->sw.cnt_off, nsw * 8, &digest[3]);
-    if (!rc) rc = fnv(A->sw.wave_off, nsw * wpt * 4, &digest[4]);
-    if (!rc) rc = fnv(A->sw.cnt, (size_t)A->sw.cnt_bytes, &digest[5]);
-    if (!rc) rc = fnv(A->sw.vals, (size_t)A->sw.n_vals * vsz, &digest[6]);
-    if (!rc) rc = fnv(A->sw.idx, (size_t)A->sw.n_vals * 2, &digest[7]);
-    if (!rc) rc = fnv(A->sw.pad, nsw * (size_t)A->sw.tile_rows * 4, &digest[8]);
-    if (!rc) rc = fnv(A->sw.rest, (size_t)A->sw.n_rest * 4, &digest[9]);
-    if (!rc && A->sw.idx_b) {
-        rc = fnv(A->sw.wave_off_b, nsw * wpt * 4, &digest[10]);
-        if (!rc) rc = fnv(A->sw.cnt_b, (size_t)A->sw.cnt_bytes, &digest[11]);
-        if (!rc) rc = fnv(A->sw.vals_b, (size_t)A->sw.n_vals_b * uspmv_dtype_bytes(A->sw.dtype_b), &digest[12]);
-        if (!rc) rc = fnv(A->sw.idx_b, (size_t)A->sw.n_vals_b * 2, &digest[13]);
-        if (!rc) rc = fnv(A->sw.pad_b, nsw * (size_t)A->sw.tile_rows * 4, &digest[14]);
-    }
+    const auto &w = A->sw;
+    meta[0] = w.on; meta[1] = w.tile_rows; meta[2] = w.wlog; meta[3] = w.n_tiles; meta[4] = w.all_tiles; meta[5] = w.n_rest;
+    meta[6] = w.part[0].n_vals; meta[7] = w.part[1].n_vals;
+    if (!w.on || !w.tile_ids) return USPMV_OK;
+    const size_t nsw = (size_t)w.n_tiles;
+    int rc = device_fnv(w.tile_ids, nsw * 4, &digest[0]);
+    if (!rc) rc = device_fnv(w.smin, nsw * 4, &digest[1]);
+    if (!rc) rc = device_fnv(w.S, nsw * 4, &digest[2]);
+    if (!rc) rc = device_fnv(w.cnt_off, nsw * 8, &digest[3]);
+    if (!rc) rc = sweep_part_digest(w, 0, &digest[4]);
+    if (!rc) rc = device_fnv(w.rest, (size_t)w.n_rest * 4, &digest[9]);
+    if (!rc && w.n_parts >= 2) rc = sweep_part_digest(w, 1, &digest[10]);
     return rc;
 }
 
-// ... and of one part's arrays: wave offsets, counts, values, indices, padding columns
 int uspmv_dmat_sweep_plan_digest_part(const uspmv_dmat_t *A, int part, uint64_t digest[5], int64_t *n_vals) {
     if (int rc = check_dmat(A, "uspmv_dmat_sweep_plan_digest_part")) return rc;
     if (!digest || part < 0 || part > 2) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dmat_sweep_plan_digest_part: bad argument");
@@ -1218,32 +1193,8 @@ int uspmv_dmat_sweep_plan_digest_part(const uspmv_dmat_t *A, int part, uint64_t 
     if (n_vals) *n_vals = 0;
     const auto &w = A->sw;
     if (!w.on || !w.tile_ids || part >= w.n_parts) return USPMV_OK;
-    const void *wo = part == 0 ? (const void *)w.wave_off : part == 1 ? (const void *)w.wave_off_b : (const void *)w.wave_off_c;
-    const void *cn = part == 0 ? (const void *)w.cnt : part == 1 ? (const void *)w.cnt_b : (const void *)w.cnt_c;
-    const void *va = part == 0 ? (const void *)w.vals : part == 1 ? (const void *)w.vals_b : (const void *)w.vals_c;
-    const void *ix = part == 0 ? (const void *)w.idx : part == 1 ? (const void *)w.idx_b : (const void *)w.idx_c;
-    const void *pd = part == 0 ? (const void *)w.pad : part == 1 ? (const void *)w.pad_b : (const void *)w.pad_c;
-    const size_t nv = (size_t)(part == 0 ? w.n_vals : part == 1 ? w.n_vals_b : w.n_vals_c);
-    const size_t vsz = uspmv_dtype_bytes(part == 0 ? A->dtype : part == 1 ? w.dtype_b : w.dtype_c);
-    const size_t nsw = (size_t)w.n_tiles, wpt = (size_t)w.tile_rows / 64;
-    if (n_vals) *n_vals = (int64_t)nv;
-    std::vector<unsigned char> buf;
-    auto fnv = [&](const void *d, size_t bytes, uint64_t *out) -> int {
-        uint64_t h = 1469598103934665603ull;
-        if (d && bytes) {
-            buf.resize(bytes);
-            HIP_TRY(hipMemcpy(buf.data(), d, bytes, hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < bytes; ++k) { h ^= buf[k]; h *= 1099511628211ull; }
-        }
-        *out = h;
-        return USPMV_OK;
-    };
-    int rc = fnv(wo, nsw * wpt * 4, &digest[0]);
-    if (!rc) rc = fnv(cn, (size_t)w.cnt_bytes, &digest[1]);
-    if (!rc) rc = fnv(va, nv * vsz, &digest[2]);
-    if (!rc) rc = fnv(ix, nv * 2, &digest[3]);
-    if (!rc) rc = fnv(pd, nsw * (size_t)w.tile_rows * 4, &digest[4]);
-    return rc;
+    if (n_vals) *n_vals = w.part[part].n_vals;
+    return sweep_part_digest(w, part, digest);
 }
 
 int uspmv_dmat_plan_info(const uspmv_dmat_t *A, int *kind, int64_t *n_tiles, int64_t *n_planned) {
@@ -1265,30 +1216,19 @@ int uspmv_dmat_block_plan_digest(const uspmv_dmat_t *A0, uint64_t digest[8]) {
     const uspmv_dmat_t *A = (A0->alt && g_tune.rechunk) ? A0->alt : A0;
     for (int k = 0; k < 8; ++k) digest[k] = 0;
     if (!A->pb.on) return USPMV_OK;
-    std::vector<unsigned char> buf;
-    auto fnv = [&](const void *d, size_t bytes, uint64_t *out) -> int {
-        uint64_t h = 1469598103934665603ull;
-        if (d && bytes) {
-            buf.resize(bytes);
-            HIP_TRY(hipMemcpy(buf.data(), d, bytes, hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < bytes; ++k) { h ^= buf[k]; h *= 1099511628211ull; }
-        }
-        *out = h;
-        return USPMV_OK;
-    };
     const size_t nt = (size_t)A->pb.n_tiles, nph = (size_t)A->pb.n_phases, nc = (size_t)A->n_chunks, vsz = A->dtype == USPMV_F64 ? 8 : 4;
     int32_t n_list = 0;
     uint32_t tot16 = 0;
     HIP_TRY(hipMemcpy(&n_list, A->pb.list_ptr + nph, 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&tot16, A->pb.c16_ptrs + nc, 4, hipMemcpyDeviceToHost));
-    int rc = fnv(A->pb.ph_ptr, (nt + 1) * 4, &digest[0]);
-    if (!rc) rc = fnv(A->pb.g0, nph * 4, &digest[1]);
-    if (!rc) rc = fnv(A->pb.list_ptr, (nph + 1) * 4, &digest[2]);
-    if (!rc) rc = fnv(A->pb.xrows, (size_t)n_list * 4, &digest[3]);
-    if (!rc) rc = fnv(A->pb.c16_ptrs, (nc + 1) * 4, &digest[4]);
-    if (!rc) rc = fnv(A->pb.col16, (size_t)tot16 * (A->pb.idx8 ? 1 : 2), &digest[5]);
-    if (!rc) rc = fnv(A->pb.values, (size_t)tot16 * vsz, &digest[6]);
-    if (!rc) rc = fnv(A->bt.row_map, A->bt.row_map ? nc * (size_t)A->C * 4 : 0, &digest[7]);
+    int rc = device_fnv(A->pb.ph_ptr, (nt + 1) * 4, &digest[0]);
+    if (!rc) rc = device_fnv(A->pb.g0, nph * 4, &digest[1]);
+    if (!rc) rc = device_fnv(A->pb.list_ptr, (nph + 1) * 4, &digest[2]);
+    if (!rc) rc = device_fnv(A->pb.xrows, (size_t)n_list * 4, &digest[3]);
+    if (!rc) rc = device_fnv(A->pb.c16_ptrs, (nc + 1) * 4, &digest[4]);
+    if (!rc) rc = device_fnv(A->pb.col16, (size_t)tot16 * (A->pb.idx8 ? 1 : 2), &digest[5]);
+    if (!rc) rc = device_fnv(A->pb.values, (size_t)tot16 * vsz, &digest[6]);
+    if (!rc) rc = device_fnv(A->bt.row_map, A->bt.row_map ? nc * (size_t)A->C * 4 : 0, &digest[7]);
     return rc;
 }
 
@@ -1445,7 +1385,7 @@ int uspmv_spmmv_ap_path(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, int b, i
                            (long long)(dp->n_chunks * dp->C));
     *path = 0; *vectors_per_pass = 0;
     if (b == 1) {  // uspmv_spmv_ap: its sweep kernel, its staged kernel or lane per row, one vector each
-        if (dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.idx_b && dp->sw.plan_id == sp->sw.plan_id && g_tune.sweep) *path = 3;
+        if (dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.n_parts >= 2 && dp->sw.plan_id == sp->sw.plan_id && g_tune.sweep) *path = 3;
         else if (dp->tlc.on && sp->tlc.on && dp->tlc.plan_id != 0 && dp->tlc.plan_id == sp->tlc.plan_id && g_tune.tlc) *path = 2;
         *vectors_per_pass = *path ? 1 : 0;
         return USPMV_OK;

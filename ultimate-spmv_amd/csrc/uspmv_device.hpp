@@ -228,23 +228,26 @@ struct uspmv_dmat {
         DeviceBuf<void> vals;
         DeviceBuf<uint16_t> idx;
     } bw;
-    // column-window sweep plan (host/sweep_plan.cpp, uspmv_dmat_optimize_sweep[_ap | _ap_hp]); the _b arrays are the second part (the sp
-    // part of an ap[dp_sp] pair; the mid or the hp part of a split with an fp16 part), the _c arrays the third (the hp part of
-    // ap[dp_sp_hp]).  All live on the first part's handle; the other handles only carry the plan id and the tile counts.  n_parts and
-    // dtype_b / dtype_c say what the streams hold (vals_b: float, or binary16 bits; vals_c: binary16 bits)
+    // column-window sweep plan (host/sweep_plan.cpp, uspmv_dmat_optimize_sweep[_ap | _ap_hp]): part[k] holds the arrays of the plan's
+    // k-th struct, in the order of the split -- [one struct], [dp, sp] of an ap[dp_sp] pair, [hi, hp] or [hi, mid, hp] of a split with an
+    // fp16 part.  All live on the first part's handle; the other handles only carry the plan id and the tile counts.
     struct SweepPlan {
         bool on = false;
         int tile_rows = 1024, wlog = 13;
-        int64_t n_tiles = 0, all_tiles = 0, x_len = 0, n_rest = 0;
-        int64_t n_vals = 0, n_vals_b = 0, n_vals_c = 0, cnt_bytes = 0;   // elements of the compacted streams (without the spare tail), bytes of a count array
-        int n_parts = 1, dtype_b = USPMV_F32, dtype_c = USPMV_F16;
+        int64_t n_tiles = 0, all_tiles = 0, x_len = 0, n_rest = 0, cnt_bytes = 0;   // (cnt_bytes: bytes of a part's count array)
+        int n_parts = 1;
         uint64_t plan_id = 0;
-        DeviceBuf<int32_t> tile_ids, smin, S, pad, pad_b, pad_c, rest;
+        DeviceBuf<int32_t> tile_ids, smin, S, rest;
         DeviceBuf<uint64_t> cnt_off;
-        DeviceBuf<uint32_t> wave_off, wave_off_b, wave_off_c;
-        DeviceBuf<uint8_t> cnt, cnt_b, cnt_c;
-        DeviceBuf<void> vals, vals_b, vals_c;
-        DeviceBuf<uint16_t> idx, idx_b, idx_c;
+        struct Part {
+            int dtype = USPMV_F64;      // what vals holds: double, float or binary16 bits (part[0]: the handle's dtype)
+            int64_t n_vals = 0;         // elements of the compacted stream (without the spare tail)
+            DeviceBuf<uint32_t> wave_off;
+            DeviceBuf<uint8_t> cnt;
+            DeviceBuf<void> vals;
+            DeviceBuf<uint16_t> idx;
+            DeviceBuf<int32_t> pad;
+        } part[3];
     } sw;
 };
 
@@ -385,12 +388,35 @@ int check_dmat_one_prec(const uspmv_dmat *A, const char *who);   // uspmv_api.hi
 int check_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const char *who);   // tlc_planner.hip
 // 16-bit index offsets per chunk from the chunk lengths (O(n_chunks) on the host); false: too large for 32-bit offsets
 bool c16_offsets(const std::vector<int32_t> &cl, int64_t C, std::vector<uint32_t> *c16p, int64_t *tot16);   // tlc_planner.hip
-// the column-window sweep plan from a host struct / from the handle's device arrays (uspmv_api.hip); wlog, tile_rows 0: defaults
-// (B / B3: the further parts of an ap split sharing the plan, see uspmv_dmat::SweepPlan)
-int sweep_plan_install(uspmv_dmat *A, uspmv_dmat *B, const uspmv_scs *s, const uspmv_scs *sB, int wlog, int tile_rows, int64_t *n_tiles,
-                       int64_t *n_sweep, const char *who, uspmv_dmat *B3 = nullptr, const uspmv_scs *sB3 = nullptr);
-int sweep_plan_install_device(uspmv_dmat *A, uspmv_dmat *B, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep, const char *who,
-                              uspmv_dmat *B3 = nullptr);
+// the column-window sweep plan from host structs / from the handles' device arrays (uspmv_api.hip); wlog, tile_rows 0: defaults
+// (parts: the one struct, or the parts of an ap split sharing the plan, see uspmv_dmat::SweepPlan)
+int sweep_plan_install(uspmv_dmat *const parts[], const uspmv_scs *const ss[], int n_parts, int wlog, int tile_rows, int64_t *n_tiles,
+                       int64_t *n_sweep, const char *who);
+int sweep_plan_install_device(uspmv_dmat *const parts[], int n_parts, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep,
+                              const char *who);
+constexpr size_t WG_LDS_BYTES = 160 * 1024;   // all the LDS a gfx950 workgroup can have: what a sweep kernel's window buffer(s) must fit
+// threads per workgroup of every sweep kernel: 1 024 (or the tile, if smaller) unless "sweep_threads" asks for fewer -- a lane then owns
+// tile_rows / threads rows, at most 4
+inline int sweep_threads(const uspmv_dmat::SweepPlan &w) {
+    int threads = std::min<int>(w.tile_rows, g_tune.sweep_threads > 0 ? g_tune.sweep_threads : 1024);
+    if (w.tile_rows / threads > 4) threads = w.tile_rows / 4;
+    return threads;
+}
+// the block sweep kernels (ap_spmmv_sweep.hip, ap_hp_spmmv_sweep.hip): vectors per pass at width b on windows of 2^wlog elements of
+// x_bytes each (0: does not apply) / on this plan with its threads per workgroup
+inline int sweep_vectors(int b, int wlog, size_t x_bytes) {
+    if (b != 2 && b != 4 && b != 8 && b != 16) return 0;
+    for (int bs = 8; bs >= 2; bs >>= 1)
+        if (bs <= b && b % bs == 0 && (x_bytes << wlog) * bs <= WG_LDS_BYTES) return bs;
+    return 0;
+}
+inline int sweep_block_bs(const uspmv_dmat::SweepPlan &w, int b, size_t x_bytes) {
+    const int threads = sweep_threads(w);
+    if (threads < 64 || threads % 64 || w.tile_rows % threads) return 0;
+    const int rpl = w.tile_rows / threads;
+    if (rpl != 1 && rpl != 2 && rpl != 4) return 0;
+    return sweep_vectors(b, w.wlog, x_bytes);
+}
 inline unsigned grid_for(long work_items, int block) { return (unsigned)((work_items + block - 1) / block); }
 
 constexpr size_t BT_LDS_CAP = 80 * 1024;  // LDS per single-wave SpMMV tile (block plan): two tiles per CU at worst

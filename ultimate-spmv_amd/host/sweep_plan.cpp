@@ -65,22 +65,22 @@ inline int64_t effective_len(const uspmv_scs *m, int64_t cs, int64_t L, int64_t 
 
 }  // namespace
 
-int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, int tile_rows, double max_stage_bytes_per_nnz,
-                           uspmv_sweep_plan *p, const uspmv_scs *s3) {
+int uspmv_build_sweep_plan(const uspmv_scs *const ss[], int ns, int wlog, int tile_rows, double max_stage_bytes_per_nnz,
+                           uspmv_sweep_plan *p) {
     p->valid = false;
+    if (ns < 1 || ns > 3) return USPMV_OK;
+    const uspmv_scs *const s = ss[0];
     const int64_t C = s->C, nc = s->n_chunks;
     if (tile_rows != 256 && tile_rows != 512 && tile_rows != 1024 && tile_rows != 2048 && tile_rows != 4096) tile_rows = 1024;
     if (C < 1 || C > 64 || 64 % C != 0 || nc < 1) return USPMV_OK;          // a wave covers whole chunks
-    if (s3 && !s2) return USPMV_OK;
     if (s->dtype == USPMV_F16) return USPMV_OK;                              // (x has the first part's type)
-    const int ns = s3 ? 3 : s2 ? 2 : 1;
-    const uspmv_scs *ss[3] = {s, s2, s3};
     for (int w = 1; w < ns; ++w) if (ss[w]->C != C || ss[w]->n_chunks != nc) return USPMV_OK;
     if (wlog < 8 || wlog > 16) return USPMV_OK;                              // 16-bit local indices
     for (int w = 0; w < ns; ++w) if (ss[w]->n_elements > (int64_t)UINT32_MAX) return USPMV_OK;
     const int64_t R = tile_rows, n_pad = nc * C, n_tiles = (n_pad + R - 1) / R, wpt = R / 64;
     const size_t vsz = s->dtype == USPMV_F64 ? 8 : 4;                        // bytes of an x element
-    p->tile_rows = tile_rows; p->wlog = wlog; p->n_tiles = n_tiles;
+    p->tile_rows = tile_rows; p->wlog = wlog; p->n_tiles = n_tiles; p->n_parts = ns;
+    for (int w = 0; w < ns; ++w) p->part[w].dtype = ss[w]->dtype;
 
     // ---- pass 1: which tiles sweep, their window range, entries per wave
     std::vector<int32_t> smin((size_t)n_tiles, 0), S((size_t)n_tiles, 0);
@@ -148,12 +148,8 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
         if (!ok[(size_t)t])
             for (int64_t c = t * R / C; c < std::min((t + 1) * R / C, nc); ++c) p->rest_chunks.push_back((int32_t)c);
     if (nsw == 0) return USPMV_OK;
-    std::vector<uint32_t> *const wave_off[3] = {&p->wave_off, &p->wave_off_b, &p->wave_off_c};
-    std::vector<uint8_t> *const cnts[3] = {&p->cnt, &p->cnt_b, &p->cnt_c};
-    std::vector<uint16_t> *const idxs[3] = {&p->idx, &p->idx_b, &p->idx_c};
-    std::vector<int32_t> *const pads[3] = {&p->pad_col, &p->pad_col_b, &p->pad_col_c};
     for (int w = 0; w < ns; ++w) {
-        auto &wo = *wave_off[w];
+        auto &wo = p->part[w].wave_off;
         wo.assign((size_t)(nsw * wpt), 0);
         for (int64_t k = 0; k < nsw; ++k)
             for (int64_t v = 0; v < wpt; ++v) {
@@ -163,15 +159,15 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
         if (tot[w] > (int64_t)UINT32_MAX) return USPMV_OK;
     }
     constexpr size_t SPARE = 64;   // inactive lanes of the kernel load the batch's first element: keep that address valid at the very end
-    void *vals[3] = {nullptr, nullptr, nullptr};                              // the part's stream in its own type
     for (int w = 0; w < ns; ++w) {
-        cnts[w]->assign((size_t)cnt_bytes, 0);
-        idxs[w]->assign((size_t)tot[w] + SPARE, 0);
-        pads[w]->assign((size_t)(nsw * R), -1);
+        auto &pt = p->part[w];
         const size_t nv = (size_t)tot[w] + SPARE;
-        if (ss[w]->dtype == USPMV_F64) { auto &v = w == 0 ? p->vals_f64 : p->vals_b_f64; v.assign(nv, 0.0); vals[w] = v.data(); }
-        else if (ss[w]->dtype == USPMV_F32) { auto &v = w == 0 ? p->vals_f32 : p->vals_b_f32; v.assign(nv, 0.0f); vals[w] = v.data(); }
-        else { auto &v = w == 1 ? p->vals_b_f16 : p->vals_c_f16; v.assign(nv, 0); vals[w] = v.data(); }
+        pt.cnt.assign((size_t)cnt_bytes, 0);
+        pt.idx.assign(nv, 0);
+        pt.pad_col.assign((size_t)(nsw * R), -1);
+        if (pt.dtype == USPMV_F64) pt.vals_f64.assign(nv, 0.0);             // the part's stream in its own type
+        else if (pt.dtype == USPMV_F32) pt.vals_f32.assign(nv, 0.0f);
+        else pt.vals_f16.assign(nv, 0);
     }
     // ---- pass 2: counts and the compacted entry stream
 #pragma omp parallel
@@ -185,10 +181,11 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
             for (int w = 0; w < ns; ++w) {
                 const uspmv_scs *m = ss[w];
                 const int32_t *ci = m->col_idxs.data();
-                uint8_t *cnt = cnts[w]->data() + p->t_cnt_off[(size_t)k];
-                int32_t *padc = pads[w]->data() + k * R;
-                uint16_t *idx = idxs[w]->data();
-                const auto &wo = *wave_off[w];
+                auto &pt = p->part[w];
+                uint8_t *cnt = pt.cnt.data() + p->t_cnt_off[(size_t)k];
+                int32_t *padc = pt.pad_col.data() + k * R;
+                uint16_t *idx = pt.idx.data();
+                const auto &wo = pt.wave_off;
                 for (int64_t q = q0; q < q1; ++q) {
                     const int64_t c = q / C, i = q % C, cs = m->chunk_ptrs[(size_t)c], L = m->chunk_lengths[(size_t)c];
                     int32_t pc;
@@ -211,9 +208,9 @@ int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, in
                                 const int64_t j = pos[(size_t)r]++;
                                 const int64_t src = cs + j * C + i;
                                 idx[(size_t)out] = (uint16_t)(ci[src] - ((int32_t)(lo + sw) << wlog));
-                                if (m->dtype == USPMV_F64) ((double *)vals[w])[out] = m->values_f64[(size_t)src];
-                                else if (m->dtype == USPMV_F32) ((float *)vals[w])[out] = m->values_f32[(size_t)src];
-                                else ((uint16_t *)vals[w])[out] = m->values_f16[(size_t)src];
+                                if (m->dtype == USPMV_F64) pt.vals_f64[(size_t)out] = m->values_f64[(size_t)src];
+                                else if (m->dtype == USPMV_F32) pt.vals_f32[(size_t)out] = m->values_f32[(size_t)src];
+                                else pt.vals_f16[(size_t)out] = m->values_f16[(size_t)src];
                                 ++out;
                             }
                     }

@@ -142,20 +142,30 @@ struct uspmv_sweep_plan {
     int64_t n_tiles = 0, n_sweep_tiles = 0, x_len_min = 0;
     std::vector<int32_t> tile_ids, t_smin, t_S;   // per sweep tile: tile number, first window, number of windows
     std::vector<uint64_t> t_cnt_off;              // per sweep tile: offset of its S*tile_rows count bytes
-    // (the _b arrays: the second struct -- the sp part of ap[dp_sp], the mid or the hp part of a split with an fp16 part; _c: the third,
-    //  the hp part of ap[dp_sp_hp])
-    std::vector<uint32_t> wave_off, wave_off_b, wave_off_c;   // per (sweep tile, wave): first element of the wave's compacted stream
-    std::vector<uint8_t> cnt, cnt_b, cnt_c;       // [tile][window][row]: entries of the row in the window
-    std::vector<uint16_t> idx, idx_b, idx_c;      // column - window start
-    std::vector<double> vals_f64, vals_b_f64;
-    std::vector<float> vals_f32, vals_b_f32;
-    std::vector<uint16_t> vals_b_f16, vals_c_f16; // binary16 bits
-    std::vector<int32_t> pad_col, pad_col_b, pad_col_c;   // per (sweep tile, row): column of the stripped trailing padding, -1 = none
+    // one record per struct of the plan, in the order the builder was given them: [one struct], [dp, sp] of ap[dp_sp], or the parts of a
+    // split with an fp16 part, [hi, hp] or [hi, mid, hp].  Records from n_parts on stay empty.
+    struct part_t {
+        int dtype = USPMV_F64;
+        std::vector<uint32_t> wave_off;           // per (sweep tile, wave): first element of the wave's compacted stream
+        std::vector<uint8_t> cnt;                 // [tile][window][row]: entries of the row in the window
+        std::vector<uint16_t> idx;                // column - window start
+        std::vector<int32_t> pad_col;             // per (sweep tile, row): column of the stripped trailing padding, -1 = none
+        // the stream's values as uspmv_scs stores them: only the vector of `dtype` is filled
+        std::vector<double> vals_f64;
+        std::vector<float> vals_f32;
+        std::vector<uint16_t> vals_f16;           // binary16 bits
+        const void *vals() const {
+            return dtype == USPMV_F64 ? (const void *)vals_f64.data()
+                 : dtype == USPMV_F32 ? (const void *)vals_f32.data() : (const void *)vals_f16.data();
+        }
+    };
+    int n_parts = 1;
+    part_t part[3];
     std::vector<int32_t> rest_chunks;             // chunks of the tiles that do not sweep (gather kernel)
 };
-// s2 / s3: optional further structs with the row layout of s (ap[dp_sp]: F64, F32; with an fp16 part: F64 | F32, [F32,] F16)
-int uspmv_build_sweep_plan(const uspmv_scs *s, const uspmv_scs *s2, int wlog, int tile_rows, double max_stage_bytes_per_nnz,
-                           uspmv_sweep_plan *plan, const uspmv_scs *s3 = nullptr);   // host/sweep_plan.cpp
+// parts: one to three structs with one row layout (one struct; ap[dp_sp]: F64, F32; with an fp16 part: F64 | F32, [F32,] F16)
+int uspmv_build_sweep_plan(const uspmv_scs *const parts[], int n_parts, int wlog, int tile_rows, double max_stage_bytes_per_nnz,
+                           uspmv_sweep_plan *plan);   // host/sweep_plan.cpp
 
 // Block-vector column-window sweep plan (host copy; host/sweep_plan.cpp, csrc/spmmv_sweep.hip): like uspmv_sweep_plan, but the windows
 // are windows of X ROWS (2^wlog rows of block_vec_size values each) and a tile lists only the windows its rows TOUCH -- the rows of a

@@ -318,6 +318,9 @@ int uspmv_dmat_additive_chunks(const uspmv_dmat_t *m, int64_t *n_additive, int64
  * stats = {kept, n_additive, n_chunks, tiles with records, tiles (of the records' own size where they have one), record bytes + map bytes, bytes of the stream replaced, LDS elements of the
  * fullest tile}; cols[n_elements] (may be NULL): the decoded column of every entry, padding included (-1: the entry's tile has no records). */
 int uspmv_additive_plan_probe(const uspmv_scs_t *s, int64_t stats[8], int32_t *cols);
+/* The staging data of the same plan: stats = {W (the 2-byte column map stays inside aligned blocks of W columns), entries of the tagged
+ * line lists, x lines listed more than once (their elements go to more than one interval), bytes of the map}; all 0 without a plan. */
+int uspmv_additive_plan_probe2(const uspmv_scs_t *s, int64_t stats[4]);
 /* uspmv_spmv over a subset of tiles (d_tile_ids[n_ids]) of a handle with a plan: the interior /
  * boundary split of the halo-overlap scheme at tile granularity.  Entries < 0 are skipped (a list another kernel switches on or off). */
 int uspmv_spmv_tiles(const uspmv_dmat_t *A, const int32_t *d_tile_ids, int64_t n_ids, const void *d_x, void *d_y,

@@ -32,6 +32,9 @@ def main():
         a = s.arrays(); pkg.permute_scs_cols(s, a["old_to_new_idx"])
         x = t.rand(s.n_rows_padded, dtype=t.float64, device="cuda"); y = t.zeros_like(x)
         rule, _ = pkg.additive_plan_probe(s, decode=False)            # the byte rule's verdict (at 256 rows per tile)
+        pkg.set_tuning(tlc_additive=2)
+        stage = pkg.additive_plan_probe2(s)                           # W of the 2-byte map, the tagged line lists
+        pkg.set_tuning(tlc_additive=1)
         H = {}
         for v in (0, 1):
             pkg.set_tuning(tlc_additive=2 if v else 0)
@@ -51,7 +54,7 @@ def main():
             n_add, n_ch = H[v].additive_chunks()
             print(json.dumps(dict(matrix=name, n=s.n_rows, nnz=s.nnz, additive=v, tile_rows=H[v].tile_rows, kernel_ms_median=round(m, 5), kernel_ms_min=round(min(ms[v]), 5),
                                   rounds=[round(q, 5) for q in ms[v]], additive_chunks=n_add, chunks_with_records=n_ch, chunks=s.n_chunks, index_bits=H[v].index_bits(),
-                                  rule_keeps=bool(rule["kept"]), new_bytes=rule["new_bytes"], replaced_bytes=rule["replaced_bytes"], lds_elements=rule["max_elems"],
+                                  rule_keeps=bool(rule["kept"]), map_block=stage["W"], list_entries=stage["list_entries"], lines_listed_again=stage["lines_listed_again"], new_bytes=rule["new_bytes"], replaced_bytes=rule["replaced_bytes"], lds_elements=rule["max_elems"],
                                   same_as_local_indices=bool(t.equal(ys[v], ys[0])), same_as_gather=bool(t.equal(ys[v], yg)))), flush=True)
         del H, coo, s
 

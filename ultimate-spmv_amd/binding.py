@@ -97,6 +97,7 @@ _SIGS = {
     "uspmv_dmat_index_bits": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "uspmv_dmat_additive_chunks": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "uspmv_additive_plan_probe": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp]),
+    "uspmv_additive_plan_probe2": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "uspmv_dmat_optimize_device": (C.c_int, [_vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_dmat_optimize_device_ap": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_dmat_plan_download": (C.c_int, [_vp, C.POINTER(_i64), _vp, _vp, _vp, _vp]),
@@ -1046,6 +1047,14 @@ def additive_plan_probe(scs, decode=True):
     _ck(lib().uspmv_additive_plan_probe(scs.h, st, _np_ptr(cols) if decode else None))
     keys = ("kept", "n_additive", "n_chunks", "tiles_with_records", "tiles", "new_bytes", "replaced_bytes", "max_elems")
     return dict(zip(keys, [int(v) for v in st])), cols
+
+
+def additive_plan_probe2(scs):
+    """The staging data of the same plan (uspmv_additive_plan_probe2): the block size W of the 2-byte column map, the entries of the tagged
+    line lists, the x lines listed more than once (their elements go to more than one interval) and the map's bytes; all 0 without a plan."""
+    st = (C.c_int64 * 4)()
+    _ck(lib().uspmv_additive_plan_probe2(scs.h, st))
+    return dict(zip(("W", "list_entries", "lines_listed_again", "map_bytes"), [int(v) for v in st]))
 
 
 def convert_to_scs_device(coo, C_, sigma, dtype=F64, fixed_permutation=None, permute_cols=True, device="cuda"):

@@ -205,8 +205,8 @@ __device__ __forceinline__ float ld_sys(const float *p) {
 // ELEM: the tile's list holds single x ELEMENTS (uspmv_build_tlc_plan with line_shift 0): thread k gathers element k of the list into LDS -- one
 // 8-byte gather per DISTINCT column of the tile instead of one per entry; local indices = positions in the list.
 // ADD: the handle's additive chunk records (uspmv_additive_plan, host/tlc_plan.cpp; AddArgs).  A tile that carries intervals lays its x
-// window out in LDS in pre-sort column order -- it loads the lines of its list as ever and stores every element at the position of its
-// pre-sort column (gathering x[o2n[base + t]] interval by interval instead measured 0.90 against 0.72 ms on the 253^3 stencil: DESIGN 9.10)
+// window out in LDS in pre-sort column order -- it loads the lines of its tagged list as ever and stores every element at the position of its
+// pre-sort column (2-byte block-local map; the list entry names the interval; gathering x[o2n[base + t]] interval by interval instead measured 0.90 against 0.72 ms on the 253^3 stencil: DESIGN 9.10)
 // -- and the local index of (lane i, slot j) of an additive chunk is R[i] + S[j]: one ushort per lane, then one 16-byte load of eight S per batch of eight slots, the
 // same address in all lanes of the chunk.  The other chunks of such a tile read one 16-bit position per entry into the same array, eight
 // per lane and batch, through the same loop; tiles without intervals run as without ADD.  Value loads, slot order and FMA chain are those of the other forms: bit-identical y.
@@ -281,47 +281,73 @@ __global__ void __launch_bounds__(1024) scs_spmv_tlc(const long n_chunks, const 
         const int iv0 = aa.iv_ptr[tile], niv = aa.iv_ptr[tile + 1] - iv0;
         add_tile = niv > 0;
         if (add_tile) {
-            // the tile's x lines as without ADD (coalesced 16-byte loads over its line list), each element then stored at the LDS position of
-            // its pre-sort column: aa.cmap[column] looked up in the tile's intervals (first column, length, first LDS element: wave-uniform
-            // loads; a copy of the table in LDS measured 10 % slower).  Line-mates no entry refers to may fall outside: skipped.
-            typedef int ivec_t __attribute__((ext_vector_type(EPL)));
+            // the tile's tagged line list (AddArgs::lines: line | interval << 27): the line's x as without ADD (coalesced 16-byte loads) beside
+            // its 2-byte map, and the one row (first column, length, first LDS element) of the interval table the entry names (one 16-byte LDS read); every element
+            // whose pre-sort column lies in that interval is stored at its LDS position.  Line-mates no entry refers to may fall outside: skipped.
+            // The loop's prologue comes first -- the record pointer, the lane's R, the first 16 bytes of positions and the first batch of
+            // eight values: plain registers, nothing of it depends on LDS -- so that the matrix stream is in flight while the tile stages.
+            // one loop for both kinds (the two chunks of a wave may differ): 16 bytes of positions per batch of eight slots, S (the same
+            // address in all lanes of the chunk) above the lane's R, or the lane's own eight positions above 0
+            unsigned ap = 0, R = 0;
+            u32x4_t s40;
+            VT v0[8];
+            if (L > 0) {
+                ap = aa.ptrs[c];
+                const unsigned short *rec = aa.rec + (long)(ap >> 1) * 8;
+                R = (ap & 1u) ? (unsigned)rec[i] : 0u;
+                s40 = ld_stream<NT>((ap & 1u) ? (const u32x4_t *)(rec + C) : (const u32x4_t *)rec + i);
+                if (L >= 8) {
+                    const VT *vp = values + (long)cs + i;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v0[u] = ld_stream<NT>(vp + (long)u * C);
+                }
+            }
+            typedef unsigned short mvec_t __attribute__((ext_vector_type(EPL)));
+            typedef int i32x4_t __attribute__((ext_vector_type(4)));
+            // the tile's interval table (at most 16 rows), one copy per wave behind the x window: a wave reads only what it wrote itself, so
+            // this needs no workgroup barrier.  (The row by a 16-byte global load per lane and entry instead -- as many bytes through the
+            // vector memory path as the x line itself -- measured slower than the interval walk it replaced: DESIGN 9.11.)
+            i32x4_t *ivt = (i32x4_t *)(tlc_smem + aa.ivt_off) + (threadIdx.x / __builtin_amdgcn_wavefrontsize()) * 16;
+            {
+                const int lane = threadIdx.x % __builtin_amdgcn_wavefrontsize();
+                if (lane < niv) ivt[lane] = *((const i32x4_t *)aa.iv + iv0 + lane);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
             const int sub = threadIdx.x % LPL, lk = threadIdx.x / LPL;
-            for (int k = lk; k < nl; k += blockDim.x / LPL) {
-                const long idx = (long)tile_lines[lp0 + k] * 16 + sub * EPL;
+            const int al0 = aa.line_ptr[tile], anl = aa.line_ptr[tile + 1] - al0;
+            for (int k = lk; k < anl; k += blockDim.x / LPL) {
+                const unsigned ent = (unsigned)aa.lines[al0 + k];
+                const long idx = (long)(ent & 0x7FFFFFFu) * 16 + sub * EPL;
+                const i32x4_t ivr = ivt[ent >> 27];
+                const mvec_t m16 = *(const mvec_t *)(aa.map16 + idx);      // (the map is padded to whole lines)
                 vec_t v;
-                ivec_t pc;
                 if (idx + EPL <= x_len) {
                     v = *(const vec_t *)(x + idx);
-                    pc = *(const ivec_t *)(aa.cmap + idx);
                 } else {
 #pragma unroll
-                    for (int e = 0; e < EPL; ++e) { const bool in = idx + e < x_len; v[e] = in ? x[idx + e] : VT(0); pc[e] = in ? aa.cmap[idx + e] : -1; }
+                    for (int e = 0; e < EPL; ++e) v[e] = idx + e < x_len ? x[idx + e] : VT(0);
                 }
-                int pos[EPL];
+                const int blk = (int)idx & ~aa.w_mask;
 #pragma unroll
-                for (int e = 0; e < EPL; ++e) pos[e] = -1;
-                for (int q = 0; q < niv; ++q) {
-                    const int base = aa.iv[4 * (iv0 + q)], len = aa.iv[4 * (iv0 + q) + 1], off = aa.iv[4 * (iv0 + q) + 2];
-#pragma unroll
-                    for (int e = 0; e < EPL; ++e)
-                        if (pc[e] >= base && pc[e] - base < len) pos[e] = off + pc[e] - base;
+                for (int e = 0; e < EPL; ++e) {
+                    const unsigned r = (unsigned)(blk + (int)m16[e] - ivr[0]);
+                    if (r < (unsigned)ivr[1]) xs[ivr[2] + (int)r] = v[e];
                 }
-#pragma unroll
-                for (int e = 0; e < EPL; ++e)
-                    if (pos[e] >= 0) xs[pos[e]] = v[e];
             }
             __syncthreads();
             if (L > 0) {
-                const unsigned ap = aa.ptrs[c];
                 const unsigned short *rec = aa.rec + (long)(ap >> 1) * 8;
+                const u32x4_t *sp = (ap & 1u) ? (const u32x4_t *)(rec + C) : (const u32x4_t *)rec + i;
+                const long ss = (ap & 1u) ? 1 : C;
                 const VT *vp = values + (long)cs + i;
-                // one loop for both kinds (the two chunks of a wave may differ): 16 bytes of positions per batch of eight slots, S (the same
-                // address in all lanes of the chunk) above the lane's R, or the lane's own eight positions above 0
-                const bool addv = ap & 1u;
-                const unsigned R = addv ? (unsigned)rec[i] : 0u;
-                const u32x4_t *sp = addv ? (const u32x4_t *)(rec + C) : (const u32x4_t *)rec + i;
-                const long ss = addv ? 1 : C;
                 int p = 0;
+                if (L >= 8) {                                    // the batch that was loaded above
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) acc = fma_t(v0[u], xs[R + ((s40[u >> 1] >> (16 * (u & 1))) & 0xFFFFu)], acc);
+                    p = 1;
+                }
                 for (; 8 * p + 8 <= L; ++p) {
                     VT v[8];
 #pragma unroll
@@ -331,7 +357,7 @@ __global__ void __launch_bounds__(1024) scs_spmv_tlc(const long n_chunks, const 
                     for (int u = 0; u < 8; ++u) acc = fma_t(v[u], xs[R + ((s4[u >> 1] >> (16 * (u & 1))) & 0xFFFFu)], acc);
                 }
                 if (8 * p < L) {                                 // the last batch holds fewer than eight slots
-                    const u32x4_t s4 = ld_stream<NT>(sp + p * ss);
+                    const u32x4_t s4 = p == 0 ? s40 : ld_stream<NT>(sp + p * ss);
 #pragma unroll
                     for (int u = 0; u < 8; ++u)
                         if (8 * p + u < L) acc = fma_t(ld_stream<NT>(vp + (long)(8 * p + u) * C), xs[R + ((s4[u >> 1] >> (16 * (u & 1))) & 0xFFFFu)], acc);
@@ -582,11 +608,13 @@ int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, cons
     const bool elem = A->tlc.elem;
     // (additive chunk records: tlc_planner.hip tlc_additive_install; the launches over tile lists keep to the local indices)
     const bool add = A->tlc.add_ptrs != nullptr && !elem && !tile_ids && !A->tlc.row_map;
-    const size_t lds = std::max((size_t)A->tlc.max_lines * (elem ? 1 : 16), add ? (size_t)A->tlc.add_max_elems : (size_t)0) * sizeof(VT);
-    const AddArgs aa = add ? AddArgs{A->tlc.add_iv_ptr, A->tlc.add_iv, A->tlc.add_cmap, A->tlc.add_ptrs, A->tlc.add_rec} : AddArgs{};
-    // (records on tiles of their own size: every tile carries intervals, and the launch walks their line lists instead of the plan's)
-    const bool own_tiles = add && A->tlc.add_line_ptr != nullptr;
+    size_t lds = std::max((size_t)A->tlc.max_lines * (elem ? 1 : 16), add ? (size_t)A->tlc.add_max_elems : (size_t)0) * sizeof(VT);
+    // (records on tiles of their own size: every tile carries intervals and stages through its tagged line list alone)
+    const bool own_tiles = add && A->tlc.add_own_tiles;
     const int block = own_tiles ? A->tlc.add_tile_rows : A->tlc.tile_rows;
+    const int ivt_off = (int)((lds + 15) / 16 * 16);          // behind the x window: 16 rows of the interval table per wave (256 bytes)
+    if (add) lds = (size_t)ivt_off + (size_t)((block + 63) / 64) * 256;
+    const AddArgs aa = add ? AddArgs{A->tlc.add_iv_ptr, A->tlc.add_iv, A->tlc.add_map16, A->tlc.add_line_ptr, A->tlc.add_lines, (1 << A->tlc.add_w_log) - 1, ivt_off, A->tlc.add_ptrs, A->tlc.add_rec} : AddArgs{};
     const int *lptr = own_tiles ? A->tlc.add_line_ptr : A->tlc.line_ptr, *llist = own_tiles ? A->tlc.add_lines : A->tlc.lines;
     if (own_tiles) grid = (unsigned)A->tlc.add_n_tiles;
     const bool i12 = A->tlc.col12 != nullptr;                 // (12-bit local indices: tlc_planner.hip tlc_pack12)

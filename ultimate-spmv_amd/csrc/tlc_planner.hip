@@ -177,8 +177,10 @@ bool additive_eligible(const uspmv_scs *s, const uspmv_tlc_plan &p, bool elem, c
     return s->n_rows == s->n_cols && s->n_rows > 0 && (int64_t)(n2o ? n2o->size() : s->new_to_old_idx.size()) >= s->n_rows;
 }
 // The keep rule, a fixed one in bytes like tlc_pack12's (a verdict timed on the spot flips under a profiler): the records of the
-// tiles that carry them plus 4 bytes per column of the map, counted once, against the local indices of those tiles as the kernel would stream
-// them otherwise (12 bits where that array is kept, else 16).  Kept at half or less; "tlc_additive" 2 keeps whatever could be built.
+// tiles that carry them plus 2 bytes per column of the map, counted once, plus the tagged line lists where they are new (every entry on the
+// line plan's tiles, whose own list is no longer read there; on tiles of the records' own the entries that list a line again), against the
+// local indices of those tiles as the kernel would stream them otherwise (12 bits where that array is kept, else 16).  Kept at half or
+// less; "tlc_additive" 2 keeps whatever could be built.
 struct AdditiveBytes { int64_t fresh = 0, replaced = 0; };
 AdditiveBytes additive_bytes(const uspmv_scs *s, const uspmv_additive_plan &a, bool idx12) {
     AdditiveBytes b;
@@ -189,7 +191,7 @@ AdditiveBytes additive_bytes(const uspmv_scs *s, const uspmv_additive_plan &a, b
         const int64_t L = s->chunk_lengths[(size_t)c];
         b.replaced += idx12 ? 4 * c12_dwords(L, C) : 2 * ((L + 3) / 4) * 4 * C;
     }
-    b.fresh = a.rec_bytes + 4 * (int64_t)a.cmap.size();
+    b.fresh = a.rec_bytes + 2 * (int64_t)a.map16.size() + 4 * (a.own_tiles ? a.n_entries_again : (int64_t)a.lines.size());
     return b;
 }
 // Rows per tile of the records.  In pre-sort order all rows of a sigma window reach into the same intervals (the stencil: window + 2 lines per
@@ -198,9 +200,9 @@ AdditiveBytes additive_bytes(const uspmv_scs *s, const uspmv_additive_plan &a, b
 int additive_tile_rows(const uspmv_scs *s, int line_plan_rows) {
     return (s->sigma == 512 || s->sigma == 1024) && s->sigma > line_plan_rows && s->sigma % s->C == 0 ? (int)s->sigma : line_plan_rows;
 }
-// ... and at most five intervals per tile on average: every staged element is looked up in all of its tile's intervals.  The stencils
-// have 4.0 (three planes and the padding column) and gain 3-10 %; the KKT matrix has 7.1 and runs 16 % slower on its records although they
-// are a fifth of its local indices (tools/additive_probe.py).
+// ... and at most five intervals per tile on average.  The stencils have 4.0 (three planes and the padding column) and gain 3-10 %; the KKT
+// matrix has 7.1 and ran 16 % slower on its records although they are a fifth of its local indices, when every staged element was still
+// looked up in all of its tile's intervals (tools/additive_probe.py; with the tagged line lists: DESIGN 9.11).
 bool additive_kept(const uspmv_additive_plan &a, const AdditiveBytes &b) {
     if (!a.valid || g_tune.tlc_additive == 2) return a.valid;
     return 2 * b.fresh <= b.replaced && (int64_t)(a.iv.size() / 4) <= 5 * a.n_add_tiles;
@@ -218,18 +220,18 @@ int tlc_additive_install(uspmv_dmat *A, const uspmv_scs *s, const uspmv_tlc_plan
     auto &t = A->tlc;
     hipError_t e = t.add_iv_ptr.upload(a.iv_ptr.data(), a.iv_ptr.size() * 4);
     if (e == hipSuccess) e = t.add_iv.upload(a.iv.data(), a.iv.size() * 4);
-    if (e == hipSuccess) e = t.add_cmap.upload(a.cmap.data(), a.cmap.size() * 4);
+    if (e == hipSuccess) e = t.add_map16.upload(a.map16.data(), a.map16.size() * 2);
     if (e == hipSuccess) e = t.add_rec.upload(a.rec.data(), a.rec.size() * 2);
     if (e == hipSuccess) e = t.add_ptrs.upload(a.rec_ptrs.data(), a.rec_ptrs.size() * 4);
-    if (e == hipSuccess && !a.line_ptr.empty()) e = t.add_line_ptr.upload(a.line_ptr.data(), a.line_ptr.size() * 4);
-    if (e == hipSuccess && !a.line_ptr.empty()) e = t.add_lines.upload(a.lines.data(), a.lines.size() * 4);
+    if (e == hipSuccess) e = t.add_line_ptr.upload(a.line_ptr.data(), a.line_ptr.size() * 4);
+    if (e == hipSuccess) e = t.add_lines.upload(a.lines.data(), a.lines.size() * 4);
     if (e != hipSuccess) {
         t.add_line_ptr.reset(); t.add_lines.reset();
-        t.add_iv_ptr.reset(); t.add_iv.reset(); t.add_cmap.reset(); t.add_rec.reset(); t.add_ptrs.reset();
+        t.add_iv_ptr.reset(); t.add_iv.reset(); t.add_map16.reset(); t.add_rec.reset(); t.add_ptrs.reset();
         return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy of the additive chunk records failed: %s", who, hipGetErrorString(e));
     }
     t.add_max_elems = a.max_elems; t.add_chunks = a.n_chunks; t.add_additive = a.n_additive;
-    t.add_tile_rows = a.tile_rows; t.add_n_tiles = a.n_tiles;
+    t.add_tile_rows = a.tile_rows; t.add_n_tiles = a.n_tiles; t.add_own_tiles = a.own_tiles; t.add_w_log = a.w_log;
     return USPMV_OK;
 }
 
@@ -718,6 +720,22 @@ int uspmv_additive_plan_probe(const uspmv_scs_t *s, int64_t stats[8], int32_t *c
     stats[5] = b.fresh; stats[6] = b.replaced; stats[7] = a.max_elems;
     if (a.valid) stats[4] = a.n_tiles;               // (the records' own tiles: whole sigma windows where additive_tile_rows says so)
     if (cols && stats[0]) uspmv_additive_plan_decode(s, &a, cols);
+    return USPMV_OK;
+}
+
+int uspmv_additive_plan_probe2(const uspmv_scs_t *s, int64_t stats[4]) {
+    const char *who = "uspmv_additive_plan_probe2";
+    if (!s || !stats) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct", who);
+    for (int k = 0; k < 4; ++k) stats[k] = 0;
+    const int max_lines = line_budget(0, s->dtype, false);
+    uspmv_tlc_plan p;
+    if (int rc = uspmv_build_tlc_plan(s, nullptr, max_lines, plan_tile_rows(false), &p)) return rc;
+    if (!additive_eligible(s, p, false, nullptr)) return USPMV_OK;
+    uspmv_additive_plan a;
+    if (int rc = uspmv_build_additive_plan(s, &p, max_lines * 16, &a, nullptr, additive_tile_rows(s, p.tile_rows))) return rc;
+    if (!a.valid) return USPMV_OK;
+    stats[0] = (int64_t)1 << a.w_log; stats[1] = (int64_t)a.lines.size(); stats[2] = a.n_lines_again; stats[3] = 2 * (int64_t)a.map16.size();
     return USPMV_OK;
 }
 

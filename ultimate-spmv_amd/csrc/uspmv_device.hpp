@@ -153,11 +153,13 @@ struct uspmv_dmat {
         DeviceBuf<int32_t> row_map, cols;     // (cols: the column indices in that order, for the few tiles that do not stage)
         // additive chunk records (uspmv_additive_plan, host/tlc_plan.cpp; installed by tlc_planner.hip under "tlc_additive"): what the
         // single-struct SpMV kernel streams instead of col12 / col16 in the tiles that carry intervals.  add_ptrs null: none.
-        DeviceBuf<int32_t> add_iv_ptr, add_iv, add_cmap;
+        DeviceBuf<int32_t> add_iv_ptr, add_iv;
         DeviceBuf<uint32_t> add_ptrs;
-        DeviceBuf<uint16_t> add_rec;
-        DeviceBuf<int32_t> add_line_ptr, add_lines;   // the records' tiles where they are not the line plan's (add_tile_rows, add_n_tiles)
+        DeviceBuf<uint16_t> add_rec, add_map16;       // add_map16: 2-byte block-local column map (blocks of 1 << add_w_log columns)
+        DeviceBuf<int32_t> add_line_ptr, add_lines;   // the tagged line lists (line | interval << 27) of the records' tiles (add_tile_rows, add_n_tiles)
         int add_max_elems = 0, add_tile_rows = 0;     // LDS elements of the fullest tile; rows per tile of the records
+        int add_w_log = 4;
+        bool add_own_tiles = false;                   // the records' tiles are not the line plan's: every tile carries intervals
         int64_t add_n_tiles = 0;
         int64_t add_chunks = 0, add_additive = 0;   // chunks of the tiles with intervals / the additive ones among them
     } tlc;
@@ -286,7 +288,11 @@ struct StepArgs {
 
 // the additive chunk records as scs_spmv_tlc<..., ADD = true> takes them (uspmv_dmat::TlcPlan::add_*)
 struct AddArgs {
-    const int *iv_ptr = nullptr, *iv = nullptr, *cmap = nullptr;   // cmap[column of x] = pre-sort column
+    const int *iv_ptr = nullptr, *iv = nullptr;
+    const unsigned short *map16 = nullptr;         // pre-sort column of x[q] = (q & ~w_mask) + map16[q]
+    const int *line_ptr = nullptr, *lines = nullptr;   // per tile with intervals: line | interval << 27
+    int w_mask = 15;
+    int ivt_off = 0;                               // byte offset in LDS of the per-wave copies of the tile's interval table
     const unsigned *ptrs = nullptr;
     const unsigned short *rec = nullptr;
 };

@@ -152,8 +152,11 @@ int uspmv_build_tlc_plan(const uspmv_scs *s, const uspmv_scs *s2, int max_lines,
 // an arbitrary order, and the caller permutes the columns the same way): re-encoded in that numbering they do not shrink.  In the numbering
 // the sort STARTED from, a banded matrix has column - row equal over the 32 rows of almost every chunk.  So the tile's x window is laid out
 // in LDS in pre-sort order -- a few intervals of pre-sort columns; LDS element t of an interval holds x[o2n[base + t]], stored there by the
-// kernel as it loads the tile's x lines (position of cmap[column]) -- and an additive chunk stores one position per lane and one per slot
-// instead of one per entry.  Nothing is assumed about the caller: the candidate map (the struct's own
+// kernel as it loads the tile's x lines -- and an additive chunk stores one position per lane and one per slot instead of one per entry.
+// Staging data: the map moves a column only inside an aligned block of W columns (the sigma sort permutes inside its window), so the
+// pre-sort column of x[q] is (q & ~(W - 1)) + map16[q], two bytes per column; and every entry of a tile's line list names the interval
+// its elements go to (line | interval << 27; a line whose referenced elements fall into k intervals is listed k times), so the kernel reads
+// one row of the interval table per entry and searches nothing.  Nothing is assumed about the caller: the candidate map (the struct's own
 // permutation, or the identity for columns that were left alone) is checked entry by entry, padding included, and every other chunk of the
 // tile keeps per-entry positions into the same LDS array.
 namespace {
@@ -183,6 +186,7 @@ int64_t add_pos(const int32_t *iv, int n_iv, int64_t p, int *which = nullptr) {
     return -1;
 }
 constexpr int ADD_MAX_IV = 16;      // intervals per tile
+constexpr int ADD_LINE_BITS = 27;   // of a line-list entry: the x line; the interval above
 constexpr int64_t ADD_HOLE = 32;    // unreferenced columns that are staged along rather than ending a run
 }  // namespace
 
@@ -207,7 +211,7 @@ int uspmv_build_additive_plan(const uspmv_scs *s, const uspmv_tlc_plan *lp, int 
     const int64_t T = tile_rows / C, nt = (nc + T - 1) / T;
     p->tile_rows = tile_rows;
     p->n_tiles = nt;
-    std::vector<std::vector<int32_t>> t_lines(own_tiles ? (size_t)nt : 0);
+    std::vector<std::vector<int32_t>> t_lines((size_t)nt);
     // which column map: the one under which more of a sample of the chunks is additive
     AddMaps m{n2o.data(), n2o.data(), n};
     {
@@ -233,6 +237,16 @@ int uspmv_build_additive_plan(const uspmv_scs *s, const uspmv_tlc_plan *lp, int 
         }
         p->cols_permuted = hits[0] >= hits[1];
         if (!p->cols_permuted) m.cm = nullptr;
+    }
+    // the block the map stays inside: the smallest W = 16 ... 32768 with map(q) / W == q / W for every column; none: no plan
+    {
+        uint32_t moved = 0;
+        if (m.cm)
+            for (int64_t q = 0; q < n; ++q) moved |= (uint32_t)m.cm[q] ^ (uint32_t)q;
+        int w_log = 4;
+        while (w_log <= 15 && (moved >> w_log) != 0) ++w_log;
+        if (w_log > 15 || ((n - 1) >> 4) >= ((int64_t)1 << ADD_LINE_BITS)) return USPMV_OK;
+        p->w_log = w_log;
     }
     // pass 1: per tile the intervals, per chunk the kind and the size of its record
     std::vector<std::vector<int32_t>> t_iv((size_t)nt);
@@ -325,23 +339,38 @@ int uspmv_build_additive_plan(const uspmv_scs *s, const uspmv_tlc_plan *lp, int 
                 additive[(size_t)c] = chunk_additive(c, iv.data(), n_iv, rr.data(), d.data(), &rmin);
                 units[(size_t)c] = (uint32_t)(additive[(size_t)c] ? C / 8 + (L + 7) / 8 : ((L + 7) / 8) * C);
             }
-            t_iv[(size_t)t] = std::move(iv);
-            if (own_tiles) {                             // the tile's x lines, as uspmv_build_tlc_plan lists them
-                auto &ln = t_lines[(size_t)t];
-                for (int64_t k = e0; k < e1; ++k) ln.push_back(s->col_idxs[(size_t)k] >> 4);
-                std::sort(ln.begin(), ln.end());
-                ln.erase(std::unique(ln.begin(), ln.end()), ln.end());
+            // the tile's line list: the distinct (x line, interval) pairs of its entries, by line, then by interval
+            auto &ln = t_lines[(size_t)t];
+            for (int64_t k = e0; k < e1; ++k) {
+                const int32_t col = s->col_idxs[(size_t)k];
+                int which = 0;
+                add_pos(iv.data(), n_iv, m.col(col), &which);
+                const int32_t key = (col >> 4) << 4 | which;          // (ADD_MAX_IV = 16 intervals; a line number has 27 bits)
+                if (ln.empty() || ln.back() != key) ln.push_back(key);
             }
+            std::sort(ln.begin(), ln.end());
+            ln.erase(std::unique(ln.begin(), ln.end()), ln.end());
+            for (auto &e : ln) e = (int32_t)((uint32_t)e >> 4 | (uint32_t)(e & 15) << ADD_LINE_BITS);
+            t_iv[(size_t)t] = std::move(iv);
         }
     }
-    if (own_tiles) {
+    {
         int64_t with = 0, n_lines = 0;
         for (int64_t t = 0; t < nt; ++t) { with += !t_iv[(size_t)t].empty() || s->chunk_ptrs[(size_t)std::min<int64_t>(t * T + T, nc)] == s->chunk_ptrs[(size_t)(t * T)]; n_lines += (int64_t)t_lines[(size_t)t].size(); }
-        if (with != nt || n_lines > (int64_t)INT32_MAX) return uspmv_build_additive_plan(s, lp, budget, p, new_to_old, 0);
+        if (own_tiles && with != nt) return uspmv_build_additive_plan(s, lp, budget, p, new_to_old, 0);
+        if (n_lines > (int64_t)INT32_MAX) { const int w_log = p->w_log; *p = {}; p->w_log = w_log; return USPMV_OK; }
+        p->own_tiles = own_tiles;
         p->line_ptr.assign((size_t)nt + 1, 0);
         p->lines.reserve((size_t)n_lines);
+        const uint32_t line_mask = ((uint32_t)1 << ADD_LINE_BITS) - 1;
         for (int64_t t = 0; t < nt; ++t) {
-            p->lines.insert(p->lines.end(), t_lines[(size_t)t].begin(), t_lines[(size_t)t].end());
+            const auto &ln = t_lines[(size_t)t];
+            for (size_t k = 1; k < ln.size(); ++k)           // (a line listed k times counts once)
+                if (((uint32_t)ln[k] & line_mask) == ((uint32_t)ln[k - 1] & line_mask)) {
+                    ++p->n_entries_again;
+                    p->n_lines_again += k < 2 || ((uint32_t)ln[k - 2] & line_mask) != ((uint32_t)ln[k] & line_mask);
+                }
+            p->lines.insert(p->lines.end(), ln.begin(), ln.end());
             p->line_ptr[(size_t)t + 1] = (int32_t)p->lines.size();
         }
     }
@@ -399,29 +428,41 @@ int uspmv_build_additive_plan(const uspmv_scs *s, const uspmv_tlc_plan *lp, int 
             }
         }
     }
-    if (p->cols_permuted) { p->o2n.swap(inv); p->cmap.assign(n2o.begin(), n2o.begin() + n); }
-    else { p->o2n.resize((size_t)n); for (int64_t k = 0; k < n; ++k) p->o2n[(size_t)k] = (int32_t)k; p->cmap = p->o2n; }
+    if (p->cols_permuted) p->o2n.swap(inv);
+    else { p->o2n.resize((size_t)n); for (int64_t k = 0; k < n; ++k) p->o2n[(size_t)k] = (int32_t)k; }
+    // (padded to whole lines: the kernel loads the map of a line with vector loads; a pad column maps to itself, outside every interval)
+    const int64_t n16 = (n + 15) / 16 * 16, wm = ((int64_t)1 << p->w_log) - 1;
+    p->map16.resize((size_t)n16);
+    for (int64_t q = 0; q < n16; ++q) p->map16[(size_t)q] = (uint16_t)((q < n ? m.col((int32_t)q) : q) & wm);
     p->valid = true;
     return USPMV_OK;
 }
 
-// What the kernel does with the records, on the host: interval list -> LDS position -> pre-sort column -> o2n.  Reads the plan's arrays
-// and the struct's chunk layout only, never its column indices.
+// What the kernel does with the records, on the host: the tile's LDS image is built as the kernel stages it (tagged line list -> map16 and W
+// -> the entry's row of the interval table -> LDS position), then every record is read back through it.  Reads the plan's arrays and the
+// struct's chunk layout only, never its column indices.
 void uspmv_additive_plan_decode(const uspmv_scs *s, const uspmv_additive_plan *p, int32_t *out) {
     const int64_t C = s->C, nc = s->n_chunks, T = p->tile_rows / C;
     for (int64_t k = 0; k < s->n_elements; ++k) out[k] = -1;
     if (!p->valid) return;
-    std::vector<int32_t> lds;                            // the tile's LDS image: which column of x every element holds
+    const int64_t wm = ((int64_t)1 << p->w_log) - 1;
+    std::vector<int32_t> lds;                            // the tile's LDS image: which column of x every element holds (-2: nobody stored it)
     for (int64_t c = 0; c < nc; ++c) {
         const int64_t t = c / T;
         const int n_iv = p->iv_ptr[(size_t)t + 1] - p->iv_ptr[(size_t)t];
         if (n_iv == 0) continue;
         if (c % T == 0) {
             const int32_t *iv = p->iv.data() + 4 * (int64_t)p->iv_ptr[(size_t)t];
-            lds.clear();
-            for (int k = 0; k < n_iv; ++k) {
-                lds.resize((size_t)iv[4 * k + 2], -2);           // (the interval's first LDS element as the table states it)
-                for (int32_t e = 0; e < iv[4 * k + 1]; ++e) lds.push_back(p->o2n[(size_t)(iv[4 * k] + e)]);
+            lds.assign((size_t)p->max_elems, -2);
+            for (int32_t k = p->line_ptr[(size_t)t]; k < p->line_ptr[(size_t)t + 1]; ++k) {
+                const uint32_t ent = (uint32_t)p->lines[(size_t)k];
+                const int64_t line = ent & (((uint32_t)1 << ADD_LINE_BITS) - 1);
+                if ((int)(ent >> ADD_LINE_BITS) >= n_iv) continue;
+                const int32_t *row = iv + 4 * (ent >> ADD_LINE_BITS);
+                for (int64_t q = line * 16; q < line * 16 + 16 && q < s->n_cols; ++q) {
+                    const int64_t pc = (q & ~wm) + p->map16[(size_t)q], r = pc - row[0];
+                    if (r >= 0 && r < row[1] && row[2] + r < (int64_t)lds.size()) lds[(size_t)(row[2] + r)] = (int32_t)q;
+                }
             }
         }
         const int64_t cs = s->chunk_ptrs[(size_t)c], L = s->chunk_lengths[(size_t)c];

@@ -116,7 +116,12 @@ struct uspmv_additive_plan {
     int64_t n_tiles = 0, n_add_tiles = 0;  // tiles of the line plan / tiles that carry intervals
     int64_t n_chunks = 0, n_additive = 0;  // chunks of the tiles with intervals / of these, the additive ones
     int64_t rec_bytes = 0;                 // of `rec` (what the kernel streams instead of the local indices of those tiles)
-    std::vector<int32_t> line_ptr, lines;  // tile_rows other than the line plan's: the tiles' own x line lists (like uspmv_tlc_plan's), every tile with intervals
+    bool own_tiles = false;                // tile_rows other than the line plan's: every (non-empty) tile carries intervals
+    int w_log = 4;                         // W = 1 << w_log, 16 ... 32768: the column map stays inside aligned blocks of W columns
+    // per tile with intervals its x line list, every entry naming the interval its elements go to: line | interval << 27, by line, then by
+    // interval; a line whose referenced elements fall into k intervals is listed k times
+    std::vector<int32_t> line_ptr, lines;
+    int64_t n_lines_again = 0, n_entries_again = 0;   // lines listed more than once / entries that list a line again
     std::vector<int32_t> iv_ptr;           // n_tiles + 1: the tile's intervals (none: the tile keeps its line list)
     std::vector<int32_t> iv;               // per interval four ints: first pre-sort column, length, first LDS element, 0
     std::vector<uint32_t> rec_ptrs;        // per chunk: (offset into rec in units of 16 bytes) << 1 | additive
@@ -125,7 +130,7 @@ struct uspmv_additive_plan {
     // [batch of eight slots][row][slot % 8] -- a lane reads 16 bytes per batch in both kinds, so the two chunks of a wave share one loop.
     std::vector<uint16_t> rec;
     std::vector<int32_t> o2n;              // n_cols: pre-sort column -> column of x (the identity when !cols_permuted)
-    std::vector<int32_t> cmap;             // ... and its inverse, column of x -> pre-sort column: what the kernel stages through
+    std::vector<uint16_t> map16;           // what the kernel stages through: the pre-sort column of x[q] is (q & ~(W - 1)) + map16[q]; padded to whole lines
 };
 // lp: the line plan of s (16-element lines); budget: most LDS elements a tile may take; new_to_old: the permutation of s's rows when s does not
 // carry it itself (the internal re-chunking of a narrow struct keeps the caller's row order); tile_rows: rows per tile the records are wanted

@@ -222,6 +222,58 @@ def test_staged_kernel_over_the_shared_plan(pkg, orc, torch_cuda):
                     assert np.array_equal(dY.cpu().numpy(), want), (b, tile_rows, rowwise, ld, nt, kind, tiles, planned)
 
 
+# uspmv_spmmv_ap_path of the impcol_e pair planned with spmmv_ap_plan_lines(b), under ("tlc" 1, "tlc" 0, "spmmv_variant" 1): the staged, the
+# gather and the lane-per-row kernel.  The matrix yields the shared line plan (plan_info kind 1) at C = 8 as well as at C = 32, and the
+# commit before the pair moved to the shared kernels reports the same 2, 1, 0 at both (with 2 and 8 vectors per pass at b = 2 and 16).
+SHARED_KERNEL_PATHS = (2, 1, 0)
+
+
+@pytest.mark.parametrize("C", [8, 32])
+def test_pair_on_the_shared_block_kernels(pkg, torch_cuda, C):
+    """ap[dp_sp] runs the lane-per-row and the staged kernel that every ap kind shares (csrc/ap_hp_spmmv_kernels.hip, last part float):
+    impcol_e (225 rows) at C = 8 and C = 32, b = 2 and b = 16, both layouts, the pair planned with spmmv_ap_plan_lines(b).  Under "tlc" 1,
+    "tlc" 0 and "spmmv_variant" 1 every column of Y is bitwise uspmv_spmv_ap of that column of X, and uspmv_spmmv_ap_path reports
+    2, 1 and 0 (SHARED_KERNEL_PATHS)."""
+    t = torch_cuda
+    a = golden("ap.npz")
+    m = pkg.read_mtx(mtx_path("impcol_e"))
+    assert m.n_rows == 225
+    dp, sp = pkg.partition_precisions(m, float(a["impcol_e_th"]))
+    assert dp.nnz > 0 and sp.nnz > 0
+    ds = pkg.convert_to_scs(dp, C, int(a["impcol_e_sigma"]), pkg.F64)
+    perm = ds.arrays()["old_to_new_idx"].copy()
+    ss = pkg.convert_to_scs(sp, C, int(a["impcol_e_sigma"]), pkg.F32, fixed_permutation=perm)
+    pkg.permute_scs_cols(ds, perm); pkg.permute_scs_cols(ss, perm)
+    n = ds.n_rows_padded
+    xp = np.zeros(n); xp[:ds.n_rows] = pkg.apply_permutation(make_x(ds.n_rows), ds.arrays()["new_to_old_idx"])
+    tunings = (dict(tlc=1), dict(tlc=0), dict(spmmv_variant=1))
+    try:
+        for b in (2, 16):
+            Ad, As = pkg.DeviceMatrix(ds), pkg.DeviceMatrix(ss)
+            pkg.optimize_ap(Ad, As, ds, ss, pkg.spmmv_ap_plan_lines(b))
+            assert Ad.plan_info()[0] == 1                             # the shared line plan
+            for rowwise, ld in ((1, n), (0, n), (0, n + 32)):
+                lay = pkg.ROWWISE if rowwise else pkg.COLWISE
+                dX = _dev(t, block_x(xp, n, b, ld, rowwise))
+                want = t.full((b * ld + GUARD,), 9.0, dtype=t.float64, device="cuda")
+                for v in range(b):                                     # the single-vector product of every column, once
+                    xcol = (dX[v:n * b:b] if rowwise else dX[v * ld:v * ld + n]).contiguous()
+                    ycol = t.full((n,), -3.0, dtype=t.float64, device="cuda")
+                    pkg.spmv_ap(Ad, As, xcol, ycol)
+                    if rowwise: want[v:n * b:b] = ycol
+                    else: want[v * ld:v * ld + n] = ycol
+                for tune, path in zip(tunings, SHARED_KERNEL_PATHS):
+                    pkg.set_tuning(tlc=1, spmmv_variant=0)
+                    pkg.set_tuning(**tune)
+                    got_path = pkg.spmmv_ap_path(Ad, As, b, ld, lay)[0]
+                    assert got_path == path, (C, b, rowwise, ld, tune, got_path)
+                    dY = t.full((b * ld + GUARD,), 9.0, dtype=t.float64, device="cuda")
+                    pkg.spmmv_ap(Ad, As, dX, dY, b, ld, lay)
+                    assert t.equal(dY, want), (C, b, rowwise, ld, tune)
+    finally:
+        pkg.set_tuning(tlc=1, spmmv_variant=0)
+
+
 def test_prepared_x(pkg, torch_cuda, pairs):
     """uspmv_spmmv_x_prepared on the dp handle: the re-layout once, then calls that skip it; a new X needs a new call; release returns
     to the per-call pass"""

@@ -1,26 +1,31 @@
-// Adaptive precision with an fp16 part on block vectors: uspmv_spmmv_ap_hp for ap[dp_hp], ap[sp_hp] and ap[dp_sp_hp].  The reference has
-// no twin (its CLI stops at "SpMMV is not yet implemented for AP kernels", code/utilities.hpp:1389, and its GPU path has no hp kernels at
-// all, code/classes_structs.hpp:553-600); the numerics are those of uspmv_spmv_ap_hp applied to every column of X: per (row, v) one chain
-// per part in slot order (ap_step), then ap_hp_y.  One lane per row everywhere and no chain is ever re-associated, so column v of Y is
-// bitwise uspmv_spmv_ap_hp of column v of X.  See DESIGN.md 5.8.
+// Adaptive precision on block vectors: the lane-per-row kernel and the staged (tile-local-column) kernel of all four kinds -- ap[dp_hp],
+// ap[sp_hp], ap[dp_sp_hp] (uspmv_spmmv_ap_hp, dispatched here) and ap[dp_sp] (uspmv_spmmv_ap, dispatched in ap_spmmv_kernels.hip).  A kind
+// is <HT, MID, LT>: HT the type of X, Y and the first part, MID whether a float part sits in the middle, LT the value type of the last
+// part -- unsigned short (binary16 bits) for the three kinds with an fp16 part, float for ap[dp_sp], which is <double, false, float>.
+// The reference has no twin (its CLI stops at "SpMMV is not yet implemented for AP kernels", code/utilities.hpp:1389, and its GPU path
+// has no hp kernels at all, code/classes_structs.hpp:553-600); the numerics are those of uspmv_spmv_ap_hp / uspmv_spmv_ap applied to
+// every column of X: per (row, v) one chain per part in slot order (ap_step), then ap_hp_y.  One lane per row everywhere and no chain is
+// ever re-associated, so column v of Y is bitwise the single-vector product of column v of X.  See DESIGN.md 5.7, 5.8.
+#include <type_traits>
+
 #include "uspmv_device.hpp"
 
 using namespace uspmv_dev;
 
 namespace {
 
-// y from the folded sum of the leading parts and the hp chain: hi + hp, (hi + mid) + hp, or (float)(sp + hp) -- ap_hp_y with the
-// (hi + mid) already taken
+// y from the folded sum of the leading parts and the last part's chain: hi + last, (hi + mid) + hp, or (float)(sp + hp) -- ap_hp_y with
+// the (hi + mid) already taken
 template <typename HT>
 __device__ __forceinline__ HT ap_hp_fold_y(double s, double q) { return ap_hp_y<HT, false>(s, 0.0, q); }
 
-// Any b, either layout, any C, no alignment demands: the hp twin of scs_spmmv_ap_rows.  VB vectors per pass held in registers; per
-// vector the parts' chains run one after the other with global gathers of X, (hi + mid) folded before the hp chain starts.
+// Any b, either layout, any C, no alignment demands: the block form of scs_spmmv_rows for a split.  VB vectors per pass held in
+// registers; per vector the parts' chains run one after the other with global gathers of X, (hi + mid) folded before the last chain starts.
 // colwise: X[col + v*ld], Y[row + v*ld];  rowwise: X[col*b + v], Y[row*b + v].
 // IDS: the chunks chunk_ids[0 .. n_chunks) instead of all (the rest chunks of a column-window sweep plan).
-template <int VB, bool ROWWISE, bool NT, typename HT, bool MID, bool IDS = false>
-__global__ void scs_spmmv_ap_hp_rows(const long n_chunks, const int C, const ApHpParts P, const HT *__restrict__ X, HT *__restrict__ Y,
-                                     const int b, const long ld, const int xcd_remap, const int *__restrict__ chunk_ids) {
+template <int VB, bool ROWWISE, bool NT, typename HT, bool MID, typename LT, bool IDS = false>
+__global__ void scs_spmmv_ap_rows(const long n_chunks, const int C, const ApHpParts P, const HT *__restrict__ X, HT *__restrict__ Y,
+                                  const int b, const long ld, const int xcd_remap, const int *__restrict__ chunk_ids) {
     const unsigned lb = remap_block(blockIdx.x, gridDim.x, xcd_remap);
     long row = (long)lb * blockDim.x + threadIdx.x;
     long c = row / C;
@@ -51,7 +56,7 @@ __global__ void scs_spmmv_ap_hp_rows(const long n_chunks, const int C, const ApH
 #pragma unroll
             for (int v = 0; v < VB; ++v) { s[v] = s[v] + q[v]; q[v] = 0.0; }
         }
-        chain((unsigned short)0, 2, v0, q);
+        chain(LT(), 2, v0, q);
 #pragma unroll
         for (int v = 0; v < VB; ++v) {
             if (v0 + v < b) {
@@ -71,10 +76,11 @@ struct XRow {
 };
 
 // One part's chain of the staged kernel: values one per lane and slot, the 16-bit local indices four slots per 8-byte load (the streams of
-// scs_spmv_ap_hp_tlc: sizeof(VT) + 2 bytes per entry), the X row of a slot BS elements from LDS.  W: slots per batch, 8 or 4.
+// scs_spmv_ap_tlc / scs_spmv_ap_hp_tlc: sizeof(VT) + 2 bytes per entry), the X row of a slot BS elements from LDS.  W: slots per batch,
+// 8 or 4.
 template <int BS, bool NT, int W, typename VT, typename HT>
-__device__ __forceinline__ void tlc_hp_block_chain(const VT *__restrict__ vp, const unsigned long long *__restrict__ cq, const int L,
-                                                   const int C, const HT *xs, double (&acc)[BS]) {
+__device__ __forceinline__ void tlc_block_chain(const VT *__restrict__ vp, const unsigned long long *__restrict__ cq, const int L,
+                                                const int C, const HT *xs, double (&acc)[BS]) {
     typedef XRow<HT, BS> R;
     auto step = [&](const VT a, const unsigned li) {
         const typename R::piece_t *xp = (const typename R::piece_t *)(xs + li * BS);
@@ -117,8 +123,8 @@ __device__ __forceinline__ void tlc_hp_block_chain(const VT *__restrict__ vp, co
 // ... and with 32-bit columns and X gathered from global memory in the caller's layout (tiles without a line list).
 // X points at vector v0 of the pass: row-major X[col * xstride + v], column-major X[col + v * xstride].
 template <int BS, bool NT, bool XCOL, typename VT, typename HT>
-__device__ __forceinline__ void gather_hp_block_chain(const VT *__restrict__ vp, const int *__restrict__ cp, const int L, const int C,
-                                                      const HT *__restrict__ X, const long xstride, double (&acc)[BS]) {
+__device__ __forceinline__ void gather_block_chain(const VT *__restrict__ vp, const int *__restrict__ cp, const int L, const int C,
+                                                   const HT *__restrict__ X, const long xstride, double (&acc)[BS]) {
     typedef XRow<HT, BS> R;
     for (int j = 0; j < L; ++j) {
         const VT a = ld_stream<NT>(vp + (long)j * C);
@@ -138,26 +144,33 @@ __device__ __forceinline__ void gather_hp_block_chain(const VT *__restrict__ vp,
     }
 }
 
-// The parts' shared tile-local-column plan on block vectors of width B: the block twin of scs_spmv_ap_hp_tlc and the three-part sibling
-// of scs_spmmv_ap_tlc.  A line of the plan (16 consecutive x elements there) is 16 consecutive X rows here.  Per pass BS of the B vectors:
+// Slots per batch of the staged kernel's chains: four where the kernel makes several passes (the pass loop costs registers, and 128 is
+// all a 1024-thread workgroup leaves a lane); the kinds with an fp16 part also at eight vectors per pass (<8, 8> spilled 2-3 VGPRs
+// there), where ap[dp_sp] keeps the eight it was measured with.
+constexpr int tlc_chain_slots(int B, int BS, bool pair) { return ((BS >= 8 && !pair) || (BS < B && BS >= 4)) ? 4 : 8; }
+
+// The parts' shared tile-local-column plan on block vectors of width B: the block form of scs_spmv_ap_tlc / scs_spmv_ap_hp_tlc.  A line
+// of the plan (16 consecutive x elements there) is 16 consecutive X rows here.  Per pass BS of the B vectors:
 // the tile's lines are staged once in LDS as [X row][BS] in the type of X, then every part runs its chain from its own streams
 // (sizeof(value) + 2 bytes per entry and pass) with BS accumulators and the X operands from LDS.  (hi + mid) is folded per vector before
-// the hp chain starts -- exactly the (dp + sp) + hp of ap_hp_y -- so at most two sets of BS double accumulators are live.
+// the hp chain starts -- exactly the (dp + sp) + hp of ap_hp_y -- so at most two sets of BS double accumulators are live.  B / BS
+// passes: a tile whose lines do not fit LDS at the full width still keeps its gathers out of the L2 -> L1 path, at the price of
+// streaming its entries again (from the caches: the same workgroup has just read them).
 // XCOL: X column-major (X[col + v*ld]), staged straight from the caller's columns: per line and vector 16 consecutive elements (128 or
 // 64 contiguous bytes), read in 16-byte pieces and stored element by element into the rows of LDS; else row-major (X[col*B + v]), read
 // and stored in 16-byte pieces (8 bytes for float X at BS = 2).  Rows at or beyond x_rows are staged as zeros.  Tiles without a line
 // list gather from global X.  YCOL: Y[row + v*ld], else Y[row*B + v].
-template <int B, int BS, int CT, bool NT, typename HT, bool MID, bool XCOL, bool YCOL>
-__global__ void __launch_bounds__(1024) scs_spmmv_ap_hp_tlc(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ X,
-                                                            HT *__restrict__ Y, const long ld, const int *__restrict__ tile_line_ptr,
-                                                            const int *__restrict__ tile_lines, const long x_rows, const int xcd_remap) {
+template <int B, int BS, int CT, bool NT, typename HT, bool MID, typename LT, bool XCOL, bool YCOL>
+__global__ void __launch_bounds__(1024) scs_spmmv_ap_tlc(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ X,
+                                                         HT *__restrict__ Y, const long ld, const int *__restrict__ tile_line_ptr,
+                                                         const int *__restrict__ tile_lines, const long x_rows, const int xcd_remap) {
     static_assert(BS >= 2 && BS <= B && B % BS == 0, "whole passes");
     extern __shared__ __attribute__((aligned(16))) unsigned char tlc_smem[];
     HT *xs = (HT *)tlc_smem;
     typedef XRow<HT, BS> R;
     typedef typename R::piece_t piece_t;
-    // slots per batch of the chains: four where the pass loop or eight vectors' accumulators leave no room for eight (<8, 8> spilled 2-3 VGPRs)
-    constexpr int W = (BS >= 8 || (BS < B && BS >= 4)) ? 4 : 8;
+    constexpr bool PAIR = std::is_same<LT, float>::value;    // ap[dp_sp]
+    constexpr int W = tlc_chain_slots(B, BS, PAIR);
     const int C = CT > 0 ? CT : C_rt;
     const unsigned tile = remap_block(blockIdx.x, gridDim.x, xcd_remap);
     const int lp0 = tile_line_ptr[tile];
@@ -211,27 +224,26 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_hp_tlc(const long n_chunks,
             }
             __syncthreads();
             if (L[0] > 0)
-                tlc_hp_block_chain<BS, NT, W>((const HT *)P.va[0] + (long)cs[0] + i, (const unsigned long long *)(P.c16[0] + q0[0]) + i, L[0], C, xs, s);
+                tlc_block_chain<BS, NT, W>((const HT *)P.va[0] + (long)cs[0] + i, (const unsigned long long *)(P.c16[0] + q0[0]) + i, L[0], C, xs, s);
             if constexpr (MID) {
                 if (L[1] > 0)
-                    tlc_hp_block_chain<BS, NT, W>((const float *)P.va[1] + (long)cs[1] + i, (const unsigned long long *)(P.c16[1] + q0[1]) + i, L[1], C,
+                    tlc_block_chain<BS, NT, W>((const float *)P.va[1] + (long)cs[1] + i, (const unsigned long long *)(P.c16[1] + q0[1]) + i, L[1], C,
                                                   xs, q);
 #pragma unroll
                 for (int v = 0; v < BS; ++v) { s[v] = s[v] + q[v]; q[v] = 0.0; }
             }
             if (L[2] > 0)
-                tlc_hp_block_chain<BS, NT, W>((const unsigned short *)P.va[2] + (long)cs[2] + i, (const unsigned long long *)(P.c16[2] + q0[2]) + i,
-                                              L[2], C, xs, q);
+                tlc_block_chain<BS, NT, W>((const LT *)P.va[2] + (long)cs[2] + i, (const unsigned long long *)(P.c16[2] + q0[2]) + i, L[2], C, xs, q);
         } else {  // wide-footprint tile: 32-bit columns, global gathers
             const HT *Xv = XCOL ? X + (long)v0 * ld : X + v0;
             const long xstride = XCOL ? ld : (long)B;
-            gather_hp_block_chain<BS, NT, XCOL>((const HT *)P.va[0] + (long)cs[0] + i, P.ci[0] + (long)cs[0] + i, L[0], C, Xv, xstride, s);
+            gather_block_chain<BS, NT, XCOL>((const HT *)P.va[0] + (long)cs[0] + i, P.ci[0] + (long)cs[0] + i, L[0], C, Xv, xstride, s);
             if constexpr (MID) {
-                gather_hp_block_chain<BS, NT, XCOL>((const float *)P.va[1] + (long)cs[1] + i, P.ci[1] + (long)cs[1] + i, L[1], C, Xv, xstride, q);
+                gather_block_chain<BS, NT, XCOL>((const float *)P.va[1] + (long)cs[1] + i, P.ci[1] + (long)cs[1] + i, L[1], C, Xv, xstride, q);
 #pragma unroll
                 for (int v = 0; v < BS; ++v) { s[v] = s[v] + q[v]; q[v] = 0.0; }
             }
-            gather_hp_block_chain<BS, NT, XCOL>((const unsigned short *)P.va[2] + (long)cs[2] + i, P.ci[2] + (long)cs[2] + i, L[2], C, Xv, xstride, q);
+            gather_block_chain<BS, NT, XCOL>((const LT *)P.va[2] + (long)cs[2] + i, P.ci[2] + (long)cs[2] + i, L[2], C, Xv, xstride, q);
         }
         if (valid) {
             if constexpr (YCOL) {
@@ -244,7 +256,7 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_hp_tlc(const long n_chunks,
                     piece_t t;
 #pragma unroll
                     for (int e = 0; e < R::PE; ++e) t[e] = ap_hp_fold_y<HT>(s[k * R::PE + e], q[k * R::PE + e]);
-                    st_y<NT>(yp + k, t);
+                    st_y<NT && !PAIR>(yp + k, t);     // (ap[dp_sp] keeps the plain row-major store it was measured with)
                 }
             }
         }
@@ -252,71 +264,67 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_hp_tlc(const long n_chunks,
 }
 
 // ids: the chunks to run (n_ids of them), or nullptr for all
-template <int VB, typename HT, bool MID>
-void launch_ap_hp_vb(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, int b, long ld, int layout, hipStream_t st, const int *ids,
-                     long n_ids) {
+template <int VB, typename HT, bool MID, typename LT>
+void launch_ap_vb(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, int b, long ld, int layout, hipStream_t st, const int *ids,
+                  long n_ids) {
     const int block = g_tune.block;
     const long n_chunks = ids ? n_ids : (long)hi->n_chunks;
     const unsigned grid = grid_for(n_chunks * hi->C, block);
     const bool nt = g_tune.nontemporal != 0;
-#define APHV_LAUNCH(RW, NTV)                                                                                                              \
+#define APV_LAUNCH(RW, NTV)                                                                                                               \
     do {                                                                                                                                  \
         if (ids)                                                                                                                          \
-            hipLaunchKernelGGL((scs_spmmv_ap_hp_rows<VB, RW, NTV, HT, MID, true>), dim3(grid), dim3(block), 0, st, n_chunks, (int)hi->C, P, X, Y, \
+            hipLaunchKernelGGL((scs_spmmv_ap_rows<VB, RW, NTV, HT, MID, LT, true>), dim3(grid), dim3(block), 0, st, n_chunks, (int)hi->C, P, X, Y, \
                                b, ld, g_tune.xcd_remap, ids);                                                                            \
         else                                                                                                                              \
-            hipLaunchKernelGGL((scs_spmmv_ap_hp_rows<VB, RW, NTV, HT, MID, false>), dim3(grid), dim3(block), 0, st, n_chunks, (int)hi->C, P, X, Y, \
+            hipLaunchKernelGGL((scs_spmmv_ap_rows<VB, RW, NTV, HT, MID, LT, false>), dim3(grid), dim3(block), 0, st, n_chunks, (int)hi->C, P, X, Y, \
                                b, ld, g_tune.xcd_remap, (const int *)nullptr);                                                           \
     } while (0)
-    if (layout == USPMV_ROWWISE) { if (nt) APHV_LAUNCH(true, true); else APHV_LAUNCH(true, false); }
-    else { if (nt) APHV_LAUNCH(false, true); else APHV_LAUNCH(false, false); }
-#undef APHV_LAUNCH
+    if (layout == USPMV_ROWWISE) { if (nt) APV_LAUNCH(true, true); else APV_LAUNCH(true, false); }
+    else { if (nt) APV_LAUNCH(false, true); else APV_LAUNCH(false, false); }
+#undef APV_LAUNCH
 }
 
-// any b through the lane-per-row kernel, VB vectors per pass
-template <typename HT, bool MID>
-void launch_ap_hp_generic(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, int b, long ld, int layout, hipStream_t st,
-                          const int *ids = nullptr, long n_ids = 0) {
-    if (b <= 2) launch_ap_hp_vb<2, HT, MID>(hi, P, X, Y, b, ld, layout, st, ids, n_ids);
-    else if (b <= 4) launch_ap_hp_vb<4, HT, MID>(hi, P, X, Y, b, ld, layout, st, ids, n_ids);
-    else launch_ap_hp_vb<8, HT, MID>(hi, P, X, Y, b, ld, layout, st, ids, n_ids);
-}
-
-constexpr size_t AP_HP_TLC_LDS = 160 * 1024;   // LDS budget of the staged kernel: all a gfx950 workgroup can have
-
-size_t hp_x_bytes(const uspmv_dmat *hi) { return hi->dtype == USPMV_F32 ? 4 : 8; }
-
-// as many of the b vectors per pass as the plan's fullest tile leaves room for in LDS (at most 8: 2 * 8 accumulators per lane); 0: not two
-int ap_hp_tlc_bs(const uspmv_dmat *hi, int b) {
-    const size_t line_bytes = (size_t)hi->tlc.max_lines * 16 * hp_x_bytes(hi);
-    for (int bs = 8; bs >= 2; bs >>= 1)
-        if (bs <= b && b % bs == 0 && line_bytes * bs <= AP_HP_TLC_LDS) return bs;
-    return 0;
-}
-
-template <int B, int BS, typename HT, bool MID>
-void launch_ap_hp_tlc_bs(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool col, hipStream_t st) {
+// <XCOL, YCOL>: the kinds with an fp16 part stage X and store Y in the caller's layout; ap[dp_sp] always reads row-major X (column-major
+// callers arrive through the re-layout workspace) and stores Y either way
+template <int B, int BS, typename HT, bool MID, typename LT>
+void launch_ap_tlc_bs(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool ycol, hipStream_t st) {
+    constexpr bool PAIR = std::is_same<LT, float>::value;
     const size_t lds = (size_t)hi->tlc.max_lines * 16 * sizeof(HT) * BS;     // (what the fullest tile lists, not the budget)
     const int C = (int)hi->C;
-#define APHT_LAUNCH(CTV, NTV, COLV)                                                                                                  \
+#define APT_LAUNCH(CTV, NTV, XC, YC)                                                                                                 \
     do {                                                                                                                             \
-        auto kfn = scs_spmmv_ap_hp_tlc<B, BS, CTV, NTV, HT, MID, COLV, COLV>;                                                        \
+        auto kfn = scs_spmmv_ap_tlc<B, BS, CTV, NTV, HT, MID, LT, XC, YC>;                                                           \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
         hipLaunchKernelGGL(kfn, dim3((unsigned)hi->tlc.n_tiles), dim3(hi->tlc.tile_rows), lds, st, (long)hi->n_chunks, C, P, X, Y, ld, \
                            hi->tlc.line_ptr.get(), hi->tlc.lines.get(), (long)hi->tlc.x_len, g_tune.xcd_remap);                      \
     } while (0)
-#define APHT_NT(CTV, NTV) do { if (col) APHT_LAUNCH(CTV, NTV, true); else APHT_LAUNCH(CTV, NTV, false); } while (0)
-    if (g_tune.nontemporal) { if (C == 32) APHT_NT(32, true); else APHT_NT(0, true); }
-    else { if (C == 32) APHT_NT(32, false); else APHT_NT(0, false); }
-#undef APHT_NT
-#undef APHT_LAUNCH
+#define APT_NT(CTV, NTV)                                                                                                             \
+    do {                                                                                                                             \
+        if (!ycol) APT_LAUNCH(CTV, NTV, false, false);                                                                               \
+        else if constexpr (PAIR) APT_LAUNCH(CTV, NTV, false, true);                                                                  \
+        else APT_LAUNCH(CTV, NTV, true, true);                                                                                       \
+    } while (0)
+    if (g_tune.nontemporal) { if (C == 32) APT_NT(32, true); else APT_NT(0, true); }
+    else { if (C == 32) APT_NT(32, false); else APT_NT(0, false); }
+#undef APT_NT
+#undef APT_LAUNCH
 }
 
-template <int B, typename HT, bool MID>
-void launch_ap_hp_tlc(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool col, int bs, hipStream_t st) {
-    if constexpr (B >= 8) { if (bs == 8) { launch_ap_hp_tlc_bs<B, 8, HT, MID>(hi, P, X, Y, ld, col, st); return; } }
-    if constexpr (B >= 4) { if (bs == 4) { launch_ap_hp_tlc_bs<B, 4, HT, MID>(hi, P, X, Y, ld, col, st); return; } }
-    launch_ap_hp_tlc_bs<B, 2, HT, MID>(hi, P, X, Y, ld, col, st);
+template <int B, typename HT, bool MID, typename LT>
+void launch_ap_tlc(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool ycol, int bs, hipStream_t st) {
+    if constexpr (B >= 8) { if (bs == 8) { launch_ap_tlc_bs<B, 8, HT, MID, LT>(hi, P, X, Y, ld, ycol, st); return; } }
+    if constexpr (B >= 4) { if (bs == 4) { launch_ap_tlc_bs<B, 4, HT, MID, LT>(hi, P, X, Y, ld, ycol, st); return; } }
+    launch_ap_tlc_bs<B, 2, HT, MID, LT>(hi, P, X, Y, ld, ycol, st);
+}
+
+// The kind of a split from its handles, handed to f as tags: HT(), whether there is a mid part, LT().
+template <typename F>
+void ap_kind(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, F &&f) {
+    if (last->dtype == USPMV_F32) f(double(), std::false_type(), float());                     // ap[dp_sp]
+    else if (hi->dtype == USPMV_F32) f(float(), std::false_type(), (unsigned short)0);         // ap[sp_hp]
+    else if (mid) f(double(), std::true_type(), (unsigned short)0);                            // ap[dp_sp_hp]
+    else f(double(), std::false_type(), (unsigned short)0);                                    // ap[dp_hp]
 }
 
 // What uspmv_spmmv_ap_hp runs for b >= 2: the ONE predicate behind the launch and behind uspmv_spmmv_ap_hp_path.  The codes are
@@ -329,8 +337,9 @@ enum { AP_HP_PATH_GENERIC = 0, AP_HP_PATH_STAGED = 2, AP_HP_PATH_SWEEP = 3 };
 struct ApHpBlockPath { int path, bs; };
 
 ApHpBlockPath ap_hp_block_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, int b, long ld, int layout, bool aligned16) {
+    const size_t x_bytes = hi->dtype == USPMV_F32 ? 4 : 8;
     if (g_tune.spmmv_variant == 1 || !aligned16 || (b != 2 && b != 4 && b != 8 && b != 16)) return {AP_HP_PATH_GENERIC, 0};
-    if (layout != USPMV_ROWWISE && ((size_t)ld * hp_x_bytes(hi)) % 16 != 0) return {AP_HP_PATH_GENERIC, 0};   // (16-byte pieces of the columns)
+    if (layout != USPMV_ROWWISE && ((size_t)ld * x_bytes) % 16 != 0) return {AP_HP_PATH_GENERIC, 0};   // (16-byte pieces of the columns)
     if (hi->sw.on) {
         const uint64_t sid = hi->sw.plan_id;
         const bool shared = hi->sw.tile_ids && hi->sw.n_parts == (mid ? 3 : 2) && hp->sw.on && hp->sw.plan_id == sid &&
@@ -343,30 +352,9 @@ ApHpBlockPath ap_hp_block_path(const uspmv_dmat *hi, const uspmv_dmat *mid, cons
     const uint64_t id = hi->tlc.plan_id;
     const bool planned = hi->tlc.on && id != 0 && hp->tlc.on && hp->tlc.plan_id == id && (!mid || (mid->tlc.on && mid->tlc.plan_id == id));
     if (!planned || !g_tune.tlc || hi->tlc.max_lines < 1) return {AP_HP_PATH_GENERIC, 0};
-    const int bs = ap_hp_tlc_bs(hi, b);
+    const int bs = tlc_block_bs(hi->tlc, b, x_bytes);
     if (bs < 2) return {AP_HP_PATH_GENERIC, 0};              // not even two vectors of the fullest tile fit LDS
     return {AP_HP_PATH_STAGED, bs};
-}
-
-template <typename HT, bool MID>
-int launch_ap_hp_block(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const HT *X, HT *Y, int b, long ld, int layout,
-                       hipStream_t st) {
-    const ApHpParts P = ap_hp_parts(hi, mid, hp);
-    const ApHpBlockPath p = ap_hp_block_path(hi, mid, hp, b, ld, layout, ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0));
-    if (p.path == AP_HP_PATH_SWEEP) return launch_spmmv_ap_hp_sweep(hi, mid, hp, X, Y, b, ld, layout != USPMV_ROWWISE, p.bs, st);
-    if (p.path == AP_HP_PATH_STAGED) {
-        const bool col = layout != USPMV_ROWWISE;
-        switch (b) {
-            case 2: launch_ap_hp_tlc<2, HT, MID>(hi, P, X, Y, ld, col, p.bs, st); break;
-            case 4: launch_ap_hp_tlc<4, HT, MID>(hi, P, X, Y, ld, col, p.bs, st); break;
-            case 8: launch_ap_hp_tlc<8, HT, MID>(hi, P, X, Y, ld, col, p.bs, st); break;
-            default: launch_ap_hp_tlc<16, HT, MID>(hi, P, X, Y, ld, col, p.bs, st); break;
-        }
-    } else {
-        launch_ap_hp_generic<HT, MID>(hi, P, X, Y, b, ld, layout, st);
-    }
-    HIP_TRY(hipGetLastError());
-    return USPMV_OK;
 }
 
 }  // namespace
@@ -376,7 +364,7 @@ namespace uspmv_dev {
 // two vectors of the fullest tile's X rows (16 per line) in LDS: the staged kernel then takes a shared plan at every specialised width
 int spmmv_ap_hp_plan_lines(int b, int x_dtype) {
     const size_t xb = x_dtype == USPMV_F32 ? 4 : 8;
-    return (b == 2 || b == 4 || b == 8 || b == 16) ? (int)(AP_HP_TLC_LDS / (16 * 2 * xb)) : 0;
+    return (b == 2 || b == 4 || b == 8 || b == 16) ? (int)(WG_LDS_BYTES / (16 * 2 * xb)) : 0;
 }
 
 void spmmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, int b, long ld, int layout, int *path, int *vectors) {
@@ -389,24 +377,52 @@ void spmmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_d
     *path = p.path; *vectors = p.bs;
 }
 
+int launch_spmmv_ap_rows(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const int *chunk_ids, long n_ids, const void *X,
+                         void *Y, int b, long ld, int layout, hipStream_t st) {
+    const ApHpParts P = ap_hp_parts(hi, mid, last);
+    ap_kind(hi, mid, last, [&](auto ht, auto m, auto lt) {      // VB vectors per pass
+        typedef decltype(ht) HT; typedef decltype(lt) LT;
+        constexpr bool MID = decltype(m)::value;
+        if (b <= 2) launch_ap_vb<2, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, b, ld, layout, st, chunk_ids, n_ids);
+        else if (b <= 4) launch_ap_vb<4, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, b, ld, layout, st, chunk_ids, n_ids);
+        else launch_ap_vb<8, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, b, ld, layout, st, chunk_ids, n_ids);
+    });
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
+int launch_spmmv_ap_staged(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const void *X, void *Y, int b, long ld, bool ycol,
+                           int bs, hipStream_t st) {
+    const ApHpParts P = ap_hp_parts(hi, mid, last);
+    ap_kind(hi, mid, last, [&](auto ht, auto m, auto lt) {
+        typedef decltype(ht) HT; typedef decltype(lt) LT;
+        constexpr bool MID = decltype(m)::value;
+        switch (b) {
+            case 2: launch_ap_tlc<2, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st); break;
+            case 4: launch_ap_tlc<4, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st); break;
+            case 8: launch_ap_tlc<8, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st); break;
+            default: launch_ap_tlc<16, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st); break;
+        }
+    });
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
 int launch_spmmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
                               const void *X, void *Y, int b, long ld, int layout, hipStream_t st) {
     if (n_ids == 0) return USPMV_OK;
-    const ApHpParts P = ap_hp_parts(hi, mid, hp);
-    if (hi->dtype == USPMV_F32) launch_ap_hp_generic<float, false>(hi, P, (const float *)X, (float *)Y, b, ld, layout, st, chunk_ids, n_ids);
-    else if (mid) launch_ap_hp_generic<double, true>(hi, P, (const double *)X, (double *)Y, b, ld, layout, st, chunk_ids, n_ids);
-    else launch_ap_hp_generic<double, false>(hi, P, (const double *)X, (double *)Y, b, ld, layout, st, chunk_ids, n_ids);
-    HIP_TRY(hipGetLastError());
-    return USPMV_OK;
+    return launch_spmmv_ap_rows(hi, mid, hp, chunk_ids, n_ids, X, Y, b, ld, layout, st);
 }
 
 int launch_spmmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *X, void *Y, int b, long ld, int layout,
                        hipStream_t st) {
     if (hi->n_chunks == 0) return USPMV_OK;
     if (b == 1) return launch_spmv_ap_hp(hi, mid, hp, X, Y, st);
-    if (hi->dtype == USPMV_F32) return launch_ap_hp_block<float, false>(hi, nullptr, hp, (const float *)X, (float *)Y, b, ld, layout, st);
-    if (mid) return launch_ap_hp_block<double, true>(hi, mid, hp, (const double *)X, (double *)Y, b, ld, layout, st);
-    return launch_ap_hp_block<double, false>(hi, nullptr, hp, (const double *)X, (double *)Y, b, ld, layout, st);
+    const bool col = layout != USPMV_ROWWISE;
+    const ApHpBlockPath p = ap_hp_block_path(hi, mid, hp, b, ld, layout, ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0));
+    if (p.path == AP_HP_PATH_SWEEP) return launch_spmmv_ap_hp_sweep(hi, mid, hp, X, Y, b, ld, col, p.bs, st);
+    if (p.path == AP_HP_PATH_STAGED) return launch_spmmv_ap_staged(hi, mid, hp, X, Y, b, ld, col, p.bs, st);
+    return launch_spmmv_ap_rows(hi, mid, hp, nullptr, 0, X, Y, b, ld, layout, st);
 }
 
 }  // namespace uspmv_dev

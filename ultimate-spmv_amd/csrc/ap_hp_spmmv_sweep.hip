@@ -1,5 +1,5 @@
-// Adaptive precision with an fp16 part on block vectors over the parts' shared column-window sweep plan: the block twin of
-// scs_spmv_sweep_ap_hp (sweep_ap_hp_kernels.hip) and the three-part sibling of scs_spmmv_ap_sweep (ap_spmmv_sweep.hip).  It reads the
+// Adaptive precision with an fp16 part on block vectors over the parts' shared column-window sweep plan: the block form of
+// scs_spmv_sweep_ap_hp (sweep_ap_hp_kernels.hip); scs_spmmv_ap_sweep (ap_spmmv_sweep.hip) is the same for the ap[dp_sp] pair.  It reads the
 // same plan arrays (uspmv_dmat::SweepPlan on the hi handle, parts [hi, hp] or [hi, mid, hp]) and walks every part's compacted stream of
 // a tile once for BS of the b vectors: one workgroup per sweep tile, per window the 2^wlog X rows of the pass's BS vectors staged in LDS
 // in the type of X, and every wave runs its compacted rounds as the single-vector kernel does -- one ballot per round and chain gives a

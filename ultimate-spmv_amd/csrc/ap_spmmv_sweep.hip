@@ -1,4 +1,4 @@
-// ap[dp_sp] SpMMV on the pair's column-window sweep plan: the block twin of scs_spmv_sweep<double, AP> (sweep_kernels.hip).  It reads the
+// ap[dp_sp] SpMMV on the pair's column-window sweep plan: the block form of scs_spmv_sweep<double, AP> (sweep_kernels.hip).  It reads the
 // same plan arrays (uspmv_dmat::SweepPlan on the dp handle) and walks the compacted dp and sp entry streams of a tile once for BS of
 // the b vectors: one workgroup per sweep tile, RPL rows of a lane at a time, per row BS dp and BS sp accumulators in double.  Per window the
 // 2^wlog X rows are staged in LDS by LDS-DMA for the BS vectors of the pass, and every wave runs its compacted rounds as the

@@ -1,5 +1,5 @@
 // What the column-window sweep kernels share (sweep_kernels.hip: one struct and the ap[dp_sp] pair; sweep_ap_hp_kernels.hip: the
-// splits with an fp16 part; ap_spmmv_sweep.hip, ap_hp_spmmv_sweep.hip: their block twins): the address-space types of the LDS-DMA, the
+// splits with an fp16 part; ap_spmmv_sweep.hip, ap_hp_spmmv_sweep.hip: their block forms): the address-space types of the LDS-DMA, the
 // lane's place in a ballot, the plan's per-part arrays as a kernel argument, the operands of a window element, and the batches of
 // accumulator updates under the rounds' lane masks.
 #pragma once

@@ -1,6 +1,7 @@
 // Shared declarations of the device half of libuspmv: the matrix handle, the tuning knobs, the
 // device helpers every kernel file uses and the launch entry points the C ABI (uspmv_api.hip) calls.
-// Kernels live in spmv_kernels.hip, spmmv_kernels.hip, ap_kernels.hip and ap_spmmv_kernels.hip.
+// Kernels live in spmv_kernels.hip, spmmv_kernels.hip, ap_kernels.hip, ap_spmmv_kernels.hip (ap[dp_sp] on block vectors: dispatch and
+// the row-major gather kernel) and ap_hp_spmmv_kernels.hip (the lane-per-row and staged block kernels of every ap kind).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -400,7 +401,7 @@ int sweep_plan_install(uspmv_dmat *const parts[], const uspmv_scs *const ss[], i
                        int64_t *n_sweep, const char *who);
 int sweep_plan_install_device(uspmv_dmat *const parts[], int n_parts, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep,
                               const char *who);
-constexpr size_t WG_LDS_BYTES = 160 * 1024;   // all the LDS a gfx950 workgroup can have: what a sweep kernel's window buffer(s) must fit
+constexpr size_t WG_LDS_BYTES = 160 * 1024;   // all the LDS a gfx950 workgroup can have: what a sweep kernel's window buffer(s) and the staged block kernel's tile must fit
 // threads per workgroup of every sweep kernel: 1 024 (or the tile, if smaller) unless "sweep_threads" asks for fewer -- a lane then owns
 // tile_rows / threads rows, at most 4
 inline int sweep_threads(const uspmv_dmat::SweepPlan &w) {
@@ -422,6 +423,14 @@ inline int sweep_block_bs(const uspmv_dmat::SweepPlan &w, int b, size_t x_bytes)
     const int rpl = w.tile_rows / threads;
     if (rpl != 1 && rpl != 2 && rpl != 4) return 0;
     return sweep_vectors(b, w.wlog, x_bytes);
+}
+// the staged block kernel of the ap kinds (ap_hp_spmmv_kernels.hip): as many of the b vectors per pass as the plan's fullest tile leaves
+// room for in LDS (at most 8: 2 * 8 accumulators per lane); 0: not two
+inline int tlc_block_bs(const uspmv_dmat::TlcPlan &t, int b, size_t x_bytes) {
+    const size_t line_bytes = (size_t)t.max_lines * 16 * x_bytes;
+    for (int bs = 8; bs >= 2; bs >>= 1)
+        if (bs <= b && b % bs == 0 && line_bytes * bs <= WG_LDS_BYTES) return bs;
+    return 0;
 }
 inline unsigned grid_for(long work_items, int block) { return (unsigned)((work_items + block - 1) / block); }
 
@@ -485,6 +494,15 @@ int spmmv_ap_hp_plan_lines(int b, int x_dtype);   // most lines per tile of a sh
 // what launch_spmmv_ap_hp runs for 16-byte-aligned X / Y: 0 lane per row, 2 staged over the shared line plan (b = 1: spmv_ap_hp_path);
 // 3 the column-window sweep kernel over the shared sweep plan; vectors: per pass of the staged / sweep kernel, else 0
 void spmmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, int b, long ld, int layout, int *path, int *vectors);
+// the block kernels every ap kind shares (ap_hp_spmmv_kernels.hip); the kind follows from the handles: hi F64 | F32, mid F32 or nullptr,
+// last F16 -- or F32 for the ap[dp_sp] pair (dp, nullptr, sp).  X, Y in the type of hi.
+// lane per row, any b, layout and alignment: over the chunks chunk_ids[0 .. n_ids), or over all where chunk_ids is nullptr
+int launch_spmmv_ap_rows(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const int *chunk_ids, long n_ids, const void *X,
+                         void *Y, int b, long ld, int layout, hipStream_t st);
+// staged over the parts' shared tile-local-column plan, b in {2, 4, 8, 16}, bs vectors per pass (tlc_block_bs), 16-byte-aligned X / Y.
+// ycol: column-major Y.  The kinds with an fp16 part read X in the layout of Y; the pair always reads row-major X
+int launch_spmmv_ap_staged(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const void *X, void *Y, int b, long ld, bool ycol,
+                           int bs, hipStream_t st);
 // lane per row over a list of chunks (for the rest chunks of a sweep plan's block form), any b
 int launch_spmmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
                               const void *X, void *Y, int b, long ld, int layout, hipStream_t st);                 // ap_hp_spmmv_kernels.hip
@@ -581,7 +599,7 @@ __device__ __forceinline__ void st_y(T *p, T v) {
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
-// Adaptive precision with an fp16 part (ap_kernels.hip, ap_hp_spmmv_kernels.hip, sweep_ap_hp_kernels.hip): one step of a part's chain.  With a double x every
+// Adaptive precision (ap_kernels.hip, ap_hp_spmmv_kernels.hip, sweep_ap_hp_kernels.hip): one step of a part's chain.  With a double x every
 // product is an FMA in double on the exactly widened value (scs_ap_impl_cpu's convention, hp in the place of sp), with a float x the
 // product is rounded to float and then added to the part's double accumulator (the sp part of spmv_omp_scs_ap).  hp values arrive
 // as the binary16 bits; v_cvt_f32_f16 widens them exactly.

@@ -343,6 +343,16 @@ int uspmv_spmv_chunks(const uspmv_dmat_t *A, const int32_t *d_chunk_ids, int64_t
  * semantics = block_spmv_omp_scs_general (code/kernels.hpp:306-398).  ld = vec_length of the
  * colwise layout (ignored for rowwise). */
 int uspmv_spmmv(const uspmv_dmat_t *A, const void *d_X, void *d_Y, int b, int64_t ld, int layout, void *stream);
+/* Which kernel the last uspmv_spmmv on this handle launched, as recorded on the host at the launch itself (tests: "the kernel under test
+ * is the one that answered"; every rung of uspmv_spmmv's launch ladder that declines a call falls through to the next one, with the
+ * same bits).  *kernel, the "spmmv_variant" number where there is one: 0 nothing launched yet, 1 the generic lane-per-row kernel
+ * (scs_spmmv_rows), 2 scs_spmmv_xpose, 3 the gather kernel scs_spmmv_rowmajor on the original arrays, 4 scs_spmmv_tlc, 5
+ * scs_spmmv_rowmajor on the block plan's re-ordered copy, 6 scs_spmmv_quad, 8 the phased kernel, 9 the block-vector window sweep
+ * (scs_spmmv_sweep), 10 the phased plan streamed by persistent workgroups ("spmmv_stream").  *x_pass, what happened to X in that call:
+ * 0 used as passed, 1 re-laid out into the workspace in this call, 2 the workspace prepared by uspmv_spmmv_x_prepared reused, 3 a
+ * re-layout that also undid the sigma permutation ("spmmv_unscramble").  A handle that carries an internal re-chunking answers for it,
+ * as uspmv_spmmv runs on it.  Nothing is launched. */
+int uspmv_spmmv_last_path(const uspmv_dmat_t *m, int *kernel, int *x_pass);
 /* Column-major block vectors whose X does NOT change between calls -- the reference's bench loop multiplies the same X in every
  * iteration (code/main.cpp:458-519): re-lay X out into the handle's row-major workspace once, now.  Until uspmv_spmmv_x_release, every
  * uspmv_spmmv(m, d_X, ..., b, ld, USPMV_COLWISE) with THIS pointer, b and ld skips its re-layout pass (another X, b or ld takes the

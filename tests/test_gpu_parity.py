@@ -1095,8 +1095,11 @@ def test_spmmv_column_major_x_prepared_once(pkg, orc, torch_cuda):
         d1, d2 = _dev(t, X1), _dev(t, X2)
         Y = t.zeros(b * ld, dtype=t.float64, device="cuda")
         ref = {}
+        # x_pass of uspmv_spmmv_last_path: 0 X as passed (b = 3 has no re-layout pass), 1 re-laid out in the call, 2 the prepared workspace reused
+        fresh, reused = (0, 0) if b == 3 else (1, 2)
         for nm, d in (("1", d1), ("2", d2)):
             pkg.spmmv(A, d, Y, b, ld, pkg.COLWISE); t.cuda.synchronize()
+            assert A.spmmv_last_path()[1] == fresh, b
             ref[nm] = Y.clone()
             Yo = orc.spmmv_scs(32, s.n_chunks, a["chunk_ptrs"], a["chunk_lengths"], a["col_idxs"], a["values"], d.cpu().numpy(), b, ld, False)
             assert np.array_equal(ref[nm].cpu().numpy(), Yo)
@@ -1104,14 +1107,19 @@ def test_spmmv_column_major_x_prepared_once(pkg, orc, torch_cuda):
         for _ in range(3):
             Y.zero_(); pkg.spmmv(A, d1, Y, b, ld, pkg.COLWISE); t.cuda.synchronize()
             assert t.equal(Y, ref["1"]), b
+            assert A.spmmv_last_path()[1] == reused, b
         Y.zero_(); pkg.spmmv(A, d2, Y, b, ld, pkg.COLWISE); t.cuda.synchronize()
         assert t.equal(Y, ref["2"]), b
+        assert A.spmmv_last_path()[1] == fresh, b             # (the other X: the per-call pass)
         Y.zero_(); pkg.spmmv(A, d1, Y, b, ld, pkg.COLWISE); t.cuda.synchronize()
         assert t.equal(Y, ref["1"]), b
+        assert A.spmmv_last_path()[1] == fresh, b             # (the workspace held the other X)
         pkg.spmmv_x_prepared(A, d2, b, ld)
         d2.mul_(1.0)                                          # (contents unchanged)
         Y.zero_(); pkg.spmmv(A, d2, Y, b, ld, pkg.COLWISE); t.cuda.synchronize()
         assert t.equal(Y, ref["2"]), b
+        assert A.spmmv_last_path()[1] == reused, b
         pkg.spmmv_x_release(A)
         Y.zero_(); pkg.spmmv(A, d2, Y, b, ld, pkg.ROWWISE if False else pkg.COLWISE); t.cuda.synchronize()
         assert t.equal(Y, ref["2"]), b
+        assert A.spmmv_last_path()[1] == fresh, b

@@ -66,6 +66,7 @@ def test_stream_kernel_bitexact_both_layouts(pkg, orc, t, name, C, sigma, wgs, b
     try:
         A = pkg.DeviceMatrix(s, block_tlc=b)
         info = A.block_plan_info()
+        assert A.spmmv_last_path() == (0, 0)                                                     # (nothing launched yet)
         if C == 32 and info["phased_plan"] and info["idx8"]:
             assert info["stream_grid"] > 0 and info["stream_descriptors"] >= info["phases"]      # (the kernel under test is the one that answers)
         else:
@@ -79,6 +80,10 @@ def test_stream_kernel_bitexact_both_layouts(pkg, orc, t, name, C, sigma, wgs, b
                 dX = t.from_numpy(X).cuda(); dY = t.full((b * ld,), -7.0, dtype=dX.dtype, device="cuda")
                 pkg.spmmv(A, dX, dY, b, ld, pkg.ROWWISE if rowwise else pkg.COLWISE)
                 t.cuda.synchronize()
+                # 10 = the streamed phased kernel (uspmv_spmmv_last_path); column-major X reaches it through the re-layout pass
+                kernel, x_pass = A.spmmv_last_path()
+                assert (kernel == 10) if info["stream_grid"] > 0 else (kernel != 10), (kernel, x_pass, rowwise, ld)
+                assert x_pass == (0 if rowwise else 1), (kernel, x_pass, rowwise, ld)
                 got = dY.cpu().numpy()
                 n = s.n_rows_padded
                 if rowwise:
@@ -112,6 +117,7 @@ def test_stream_kernel_on_the_device_built_plan_and_special_values(pkg, orc, t):
         dX = t.from_numpy(X).cuda(); dY = t.zeros(b * ld, dtype=t.float64, device="cuda")
         pkg.spmmv(A, dX, dY, b, ld, pkg.ROWWISE)
         t.cuda.synchronize()
+        assert A.spmmv_last_path() == (10, 0)
         got = dY.cpu().numpy()
     finally:
         pkg.set_tuning(spmmv_stream=0, spmmv_stream_depth=1)

@@ -58,9 +58,11 @@ def test_block_sweep_bitexact_both_layouts(pkg, orc, t, name, C, sigma, wlog, ti
     A = pkg.DeviceMatrix(s)
     nt, ns = A.optimize_block_sweep(s, b, wlog=wlog, tile_rows=tile_rows)
     assert nt > 0
-    if ns != nt:
-        pytest.skip(f"plan not installed for this shape ({ns} of {nt} tiles sweep)")
-    pkg.set_tuning(spmmv_variant=9)                      # nothing but the sweep may answer
+    # the planner declines sigma 512 / wlog 8 / 2048-row tiles (no tile sweeps, nothing is installed: the gather kernel must answer);
+    # every other case is installed and the sweep kernel must be the one that answers
+    declined = (name, C, sigma, wlog, tile_rows) == ("stencil3", 32, 512, 8, 2048)
+    assert ns == (0 if declined else nt), (nt, ns)
+    pkg.set_tuning(spmmv_variant=9)                      # with the plan, nothing but the sweep may answer (checked below)
     try:
         for ld in (s.n_rows_padded, s.n_rows_padded + 24):
             for rowwise in (True, False):
@@ -71,6 +73,11 @@ def test_block_sweep_bitexact_both_layouts(pkg, orc, t, name, C, sigma, wlog, ti
                 dX = t.from_numpy(X).cuda(); dY = t.full((b * ld,), -7.0, dtype=dX.dtype, device="cuda")
                 pkg.spmmv(A, dX, dY, b, ld, pkg.ROWWISE if rowwise else pkg.COLWISE)
                 t.cuda.synchronize()
+                kernel = A.spmmv_last_path()[0]
+                # (column-major X is staged by wave instructions of 64 pieces of 16 bytes per column: the launcher turns down windows
+                # narrower than that -- float at wlog 7, the band case -- and the call takes the re-layout pass and the gather kernel)
+                narrow = not rowwise and (1 << wlog) < 64 * (16 // X.itemsize)
+                assert (kernel != 9) if (declined or narrow) else (kernel == 9), (kernel, rowwise, ld)
                 got = dY.cpu().numpy()
                 n = s.n_rows_padded
                 if rowwise:
@@ -104,6 +111,7 @@ def test_block_sweep_special_values_and_padding(pkg, orc, t):
     try:
         pkg.spmmv(A, dX, dY, b, ld, pkg.ROWWISE)
         t.cuda.synchronize()
+        assert A.spmmv_last_path()[0] == 9
     finally:
         pkg.set_tuning(spmmv_variant=0)
     got = dY.cpu().numpy()

@@ -162,6 +162,7 @@ _SIGS = {
     "uspmv_dmat_optimize_block_sweep": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_spmmv_x_prepared": (C.c_int, [_vp, _vp, C.c_int, _i64, _vp]),
     "uspmv_spmmv_x_release": (C.c_int, [_vp]),
+    "uspmv_spmmv_last_path": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "uspmv_dmat_meta": (C.c_int, [_vp, C.POINTER(_i64)]),
     "uspmv_dist_comm_count": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "uspmv_dist_exchange": (C.c_int, [_vp, C.POINTER(C.c_int)]),
@@ -910,6 +911,14 @@ class DeviceMatrix:
         a, n = _i64(), _i64()
         _ck(lib().uspmv_dmat_optimize_block_sweep(self.h, scs.h, int(b), int(wlog), int(tile_rows), C.byref(a), C.byref(n)))
         return a.value, n.value
+
+    def spmmv_last_path(self):
+        """(kernel, x_pass) of the last spmmv on this handle (uspmv_spmmv_last_path).  kernel: 0 none yet, 1 generic, 2 xpose, 3 gather,
+        4 tlc, 5 gather on the re-ordered copy, 6 quad, 8 phased, 9 block-vector window sweep, 10 streamed phased; x_pass: 0 X as passed,
+        1 re-laid out in the call, 2 prepared workspace reused, 3 re-layout that undid the sigma permutation."""
+        k, x = C.c_int(), C.c_int()
+        _ck(lib().uspmv_spmmv_last_path(self.h, C.byref(k), C.byref(x)))
+        return k.value, x.value
 
     def optimize_device(self, max_lines=0):
         """Build the tile-local-column plan on the device from the handle's own arrays (uspmv_dmat_optimize_device); returns (n_tiles,

@@ -628,6 +628,7 @@ void launch_spmmv_vb(const uspmv_dmat *A, const VT *X, VT *Y, int b, long ld, in
     const int block = g_tune.block;
     const unsigned grid = grid_for(A->n_chunks * A->C, block);
     const bool nt = g_tune.nontemporal != 0;
+    A->last_kernel = 1;
 #define SPMMV_LAUNCH(RW, NTV)                                                                                     \
     hipLaunchKernelGGL((scs_spmmv_rows<VT, VB, RW, NTV>), dim3(grid), dim3(block), 0, st, (long)A->n_chunks,      \
                        (int)A->C, A->chunk_ptrs, part_lengths(A, 0), A->col_idxs, (const VT *)A->values, X, Y, b, ld, \
@@ -647,6 +648,7 @@ void launch_spmmv_rowmajor_u(const uspmv_dmat *A, const VT *X, VT *Y, long ld, b
     const int *cols = ro ? A->bt.cols : A->col_idxs;
     const VT *vals = (const VT *)(ro ? A->bt.values : A->values);
     const int *rmap = ro ? A->bt.row_map : nullptr;
+    A->last_kernel = ro ? 5 : 3;
 #define RM_LAUNCH(NTV, YC)                                                                                          \
     do {                                                                                                            \
         if (g_tune.spmmv_prefetch)                                                                                  \
@@ -667,6 +669,7 @@ template <typename VT, int B, int U>
 void launch_spmmv_xpose_u(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, hipStream_t st) {
     const int block = g_tune.block;
     const unsigned grid = grid_for(A->n_chunks * A->C, block);
+    A->last_kernel = 2;
 #define XP_LAUNCH(NTV, YC)                                                                                          \
     do {                                                                                                            \
         if (g_tune.spmmv_prefetch)                                                                                  \
@@ -687,6 +690,7 @@ template <typename VT, int B, int G, int CT, int HS, bool SWZ>
 void launch_spmmv_tlc_g(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, hipStream_t st) {
     const size_t x_bytes = (size_t)A->bt.max_rows * B * sizeof(VT);
     const size_t lds = x_bytes + (((size_t)A->bt.max_rows * 4 + 15) & ~(size_t)15);   // X rows + the tile's row list
+    A->last_kernel = 4;
 #define BT_LAUNCH(NTV, YC)                                                                                              \
     do {                                                                                                                \
         auto kfn = scs_spmmv_tlc<VT, B, NTV, YC, G, CT, HS, SWZ>;                                                                \
@@ -707,6 +711,7 @@ template <typename VT, int B, int CT, bool SWZ, int PD, int MAXP>
 void launch_spmmv_quad_m(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, hipStream_t st) {
     const size_t x_bytes = (size_t)MAXP * 4 * 1024;          // whole DMA pieces: MAXP per wave, four waves
     const size_t lds = x_bytes;
+    A->last_kernel = 6;
 #define QD_LAUNCH(NTV, YC)                                                                                              \
     do {                                                                                                                \
         auto kfn = scs_spmmv_quad<VT, B, NTV, YC, CT, SWZ, PD, MAXP>;                                                   \
@@ -863,11 +868,13 @@ int spmmv_fast(const uspmv_dmat *A, const VT *X, VT *Y, long ld, int layout, hip
         A->xprep_ptr = nullptr;                               // (the workspace is about to hold another X)
         if (int rc = relayout_x<VT, B>(A, X, ld, st, &form)) return rc;
     }
+    A->last_xpass = prepared ? 2 : form == 2 ? 3 : 1;
     VT *Xr = (VT *)A->ws;
     if constexpr (B * (int)sizeof(VT) == 64) {
         if (form == 2 && launch_spmmv_quadph<VT, B>(A, Xr, Y, ld, true, 3, st)) return USPMV_OK;
         if (form == 2) {      // (the plan over original X-row numbering turned the launch down: plain re-layout, plain plan)
             if (int rc = relayout_x<VT, B>(A, X, ld, st, &form, true)) return rc;
+            A->last_xpass = 1;
         }
     }
     launch_spmmv_rowmajor<VT, B>(A, Xr, Y, ld, true, st);
@@ -881,6 +888,7 @@ namespace uspmv_dev {
 template <typename VT>
 int launch_spmmv(const uspmv_dmat *A, const VT *X, VT *Y, int b, long ld, int layout, hipStream_t st) {
     if (A->n_chunks == 0) return USPMV_OK;
+    A->last_xpass = 0;                                        // (spmmv_fast overwrites it where a column-major X goes through the workspace)
     int rc = -1;
     if (g_tune.spmmv_variant != 1 && ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0)) {
         constexpr int VW = 16 / (int)sizeof(VT);

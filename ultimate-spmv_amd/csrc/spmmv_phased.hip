@@ -249,6 +249,7 @@ __global__ void __launch_bounds__(256) scs_spmmv_quadph(const long n_chunks, con
 template <typename VT, typename IT, int B, int CT, int MAXP>
 void launch_spmmv_quadph_m(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, int xmode, hipStream_t st) {
     const bool xcol = xmode == 1;
+    A->last_kernel = 8;
     const size_t lds = xcol ? (size_t)MAXP * 64 * 80 : (size_t)MAXP * 4 * 1024;   // MAXP*64 rows of 64 (row-major X / lines, DMA pieces) or 80 bytes
 #define QH_ARGS(PH, G0, LP, XR, C16) (long)A->n_chunks, A->chunk_ptrs, part_lengths(A, 1), (const VT *)A->pb.values, X, Y, ld, PH, G0, LP, XR, A->pb.c16_ptrs, \
                            (const IT *)C16, g_tune.xcd_remap, (long)A->n_store, (const int *)A->bt.row_map

@@ -298,6 +298,7 @@ template <typename VT, int B>
 bool launch_pstream(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, hipStream_t st) {
     if (!A->ps.desc || !A->ps.wg_ptr || A->ps.grid <= 0 || A->part || A->C != 32 || !A->pb.idx8 || A->pb.max_rows > 256 || A->pb.ngp > 8) return false;
     const size_t lds = 2 * 16384;
+    A->last_kernel = 10;
     const bool per_tile = (int64_t)A->ps.grid == A->pb.n_tiles && A->ps.per_tile;
     // measurement aid: USPMV_STREAM_CLOCK=<file> -- every workgroup's start and end time (100 MHz counter) of THIS launch, written as text
     static const char *clock_file = getenv("USPMV_STREAM_CLOCK");

@@ -215,6 +215,7 @@ int launch_bsw(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool xcol, bool
     if (xcol && (ld % VW != 0 || ((uintptr_t)X % 16) != 0 || W < 64 * VW)) return 1;
     if (((uintptr_t)X % 16) != 0 || ((uintptr_t)Y % 16) != 0) return 1;
     const long x_rows = xcol ? ld : std::max<long>(A->bw.x_rows, ld);      // rows of X that exist (row-major: the caller's padded_vec_size)
+    A->last_kernel = 9;
 #define BSW_LAUNCH(XC, YC, NB, RP)                                                                                                    \
     do {                                                                                                                              \
         auto kfn = g_tune.nontemporal ? scs_spmmv_sweep<VT, B, true, XC, YC, NB, 4, RP> : scs_spmmv_sweep<VT, B, false, XC, YC, NB, 4, RP>; \

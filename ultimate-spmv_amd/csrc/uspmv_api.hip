@@ -1305,6 +1305,14 @@ int uspmv_spmmv(const uspmv_dmat_t *A, const void *d_X, void *d_Y, int b, int64_
     return launch_spmmv<float>(A, (const float *)d_X, (float *)d_Y, b, (long)ld, layout, (hipStream_t)stream);
 }
 
+int uspmv_spmmv_last_path(const uspmv_dmat_t *A, int *kernel, int *x_pass) {
+    if (int rc = check_dmat(A, "uspmv_spmmv_last_path")) return rc;
+    if (!kernel || !x_pass) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv_last_path: NULL result pointer");
+    if (A->alt && g_tune.rechunk) A = A->alt;                 // (the handle uspmv_spmmv launches on)
+    *kernel = A->last_kernel; *x_pass = A->last_xpass;
+    return USPMV_OK;
+}
+
 int uspmv_spmmv_x_prepared(const uspmv_dmat_t *A, const void *d_X, int b, int64_t ld, void *stream) {
     if (int rc = check_dmat_one_prec(A, "uspmv_spmmv_x_prepared")) return rc;
     if (!d_X || b < 1 || ld < A->n_chunks * A->C) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv_x_prepared: bad argument");

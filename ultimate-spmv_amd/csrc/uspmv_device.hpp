@@ -124,6 +124,11 @@ struct uspmv_dmat {
     mutable const void *xprep_ptr = nullptr;
     mutable int xprep_b = 0, xprep_form = 0;
     mutable long xprep_ld = 0;
+    // uspmv_spmmv_last_path: what the last uspmv_spmmv on this handle launched, written on the host at the launch sites themselves.
+    // last_kernel: 0 nothing yet, 1 scs_spmmv_rows, 2 _xpose, 3 _rowmajor, 4 _tlc, 5 _rowmajor on the block plan's re-ordered copy, 6 _quad,
+    // 8 the phased kernel, 9 scs_spmmv_sweep, 10 the streamed phased kernel (the "spmmv_variant" numbers where there is one).
+    // last_xpass: 0 X as passed, 1 re-laid out in this call, 2 the prepared workspace reused, 3 a re-layout that undid the sigma permutation.
+    mutable int last_kernel = 0, last_xpass = 0;
     // SpMMV in two parts (the halo overlap of uspmv_dist_spmmv, csrc/uspmv_dist_api.hip): chunk-length arrays in which the chunks of the
     // OTHER part carry USPMV_SKIP_LEN -- a kernel that meets it leaves those rows of Y alone.  [order][part - 1]: order 0 = the caller's
     // row order (gather kernels), order 1 = the phased plan's tie-re-ordered rows (scs_spmmv_quadph), classified per 64-row plan tile.

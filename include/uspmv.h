@@ -43,7 +43,7 @@ typedef enum {
 
 typedef enum { USPMV_F64 = 0, USPMV_F32 = 1, USPMV_F16 = 2 } uspmv_dtype;   /* -dp / -sp / hp part      */
 /* USPMV_F16: IEEE binary16 values (uint16_t bits), the hp part of an adaptive-precision split (uspmv_partition_precisions_hp).
- * Accepted by uspmv_convert_to_scs, uspmv_dmat_upload and uspmv_dmat_wrap; a one-precision SpMV / SpMMV or plan of an F16 handle
+ * Accepted by uspmv_convert_to_scs, uspmv_convert_to_scs_device_from_arrays, uspmv_dmat_upload and uspmv_dmat_wrap; a one-precision SpMV / SpMMV or plan of an F16 handle
  * returns USPMV_ERR_UNSUPPORTED (the reference's -hp accumulates in _Float16); such a handle only runs inside uspmv_spmv_ap_hp. */
 typedef enum { USPMV_COLWISE = 0, USPMV_ROWWISE = 1 } uspmv_layout;   /* Makefile:26-31         */
 typedef enum { USPMV_SEG_ROWS = 0, USPMV_SEG_NNZ = 1 } uspmv_seg;     /* -seg_rows / -seg_nnz   */
@@ -138,7 +138,7 @@ int uspmv_partition_precisions(const uspmv_coo_t *m, double threshold_1, uspmv_c
  *   USPMV_AP_DP_SP_HP  |v| >= t1 -> hi (double), else t2 <= |v| <= t1 -> mid ((float)v), else -> hp (NaN included)
  * hp values are rounded once to binary16, to nearest even (subnormals kept, overflow to +-inf, bit-equal to numpy's float64 -> float16).
  * *mid is set to NULL for the two-part kinds (mid may then be NULL). */
-enum { USPMV_AP_DP_HP = 0, USPMV_AP_SP_HP = 1, USPMV_AP_DP_SP_HP = 2 };
+enum { USPMV_AP_DP_HP = 0, USPMV_AP_SP_HP = 1, USPMV_AP_DP_SP_HP = 2, USPMV_AP_DP_SP = 3 };   /* (DP_SP: the device-side set-up below only) */
 int uspmv_partition_precisions_hp(const uspmv_coo_t *m, int kind, double threshold_1, double threshold_2, uspmv_coo_t **hi,
                                   uspmv_coo_t **mid, uspmv_coo_t **hp);
 
@@ -170,7 +170,8 @@ int uspmv_convert_to_scs_device(const uspmv_coo_t *m, int64_t C, int64_t sigma, 
  *                            equal-length rows inside a window, hence old_to_new_idx and the row order of y_permuted, differs.
  * d_fixed_permutation (device, n_rows entries, may be NULL) as fixed_permutation above.  d_old_to_new / d_new_to_old (device, n_rows
  * int32 each, may be NULL) receive the struct's permutations for uspmv_apply_permutation_dev; *layout (may be NULL) a host struct
- * without entries as above.  Works on `stream`; returns when the handle is complete. */
+ * without entries as above.  Works on `stream`; returns when the handle is complete.  dtype USPMV_F16: the values are rounded once from
+ * the double to binary16, as uspmv_convert_to_scs stores them. */
 /* diagnosis: device addresses of {tile-local-column indices, x-line lists, line pointers, index offsets, values, col_idxs, chunk_ptrs,
  * chunk_lengths} of the struct the SpMV kernels read (tools/placement_probe.py) */
 int uspmv_dmat_plan_addresses(const uspmv_dmat_t *m, uint64_t addr[8]);
@@ -181,6 +182,37 @@ int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const int32_t *d
                                             int64_t C, int64_t sigma, int dtype, const int32_t *d_fixed_permutation, int permute_cols,
                                             int sort_mode, void *stream, uspmv_scs_t **layout, int32_t *d_old_to_new, int32_t *d_new_to_old,
                                             uspmv_dmat_t **out);
+/* Adaptive-precision set-up from DEVICE-resident COO arrays: uspmv_partition_precisions[_hp] on the device.  d_I, d_J
+ * (int32) and d_V (double) as above: sorted by row, order inside a row = summation order, which every part keeps.  kind: USPMV_AP_DP_SP
+ * (|v| >= t1 -> dp, |v| < t1 -> sp stored as (double)(float)v, NaN refused) or one of the kinds of uspmv_partition_precisions_hp, classified
+ * in the host functions' branch order; hp values are rounded once from the double (host/uspmv_f16_round.hpp).  Every part equals the host
+ * function's bit for bit.  parts[0] = hi, parts[1] = mid (NULL for the two-part kinds), parts[2] = lo; a part may be empty.
+ * Three passes, none waiting on another workgroup: classify and count per workgroup of 1024 entries, scan the counts, classify again and
+ * scatter.  The first pass also checks 0 <= I < n_rows, 0 <= J < n_cols and the row order: USPMV_ERR_INVALID / _UNSUPPORTED, and a NaN in
+ * a two-part kind "element %lld fits neither struct" (the first such element), all before anything is written.
+ * Device memory beyond the returned parts (16 bytes per entry in all): 3 * (nnz / 1024) * 20 bytes of counts and bases. */
+typedef struct uspmv_dcoo uspmv_dcoo_t;   /* one compacted part in HBM */
+int uspmv_partition_precisions_device(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                                      int kind, double threshold_1, double threshold_2, void *stream, uspmv_dcoo_t *parts[3]);
+/* borrowed device pointers, valid until uspmv_dcoo_free (any argument may be NULL) */
+int uspmv_dcoo_arrays(const uspmv_dcoo_t *p, const int32_t **d_I, const int32_t **d_J, const double **d_V, int64_t *nnz);
+/* the part copied into the caller's device arrays of nnz elements each (a framework's own allocations; any of them may be NULL) */
+int uspmv_dcoo_copy(const uspmv_dcoo_t *p, int32_t *d_I, int32_t *d_J, double *d_V, void *stream);
+void uspmv_dcoo_free(uspmv_dcoo_t *p);
+/* The whole set-up in one call: the partition above, the first part (hi: F64, F32 for ap[sp_hp]) converted with its own sigma ordering
+ * (sort_mode as in uspmv_convert_to_scs_device_from_arrays), the other parts (mid: F32; lo: F32 for ap[dp_sp], else F16) with the first
+ * part's permutation as their fixed permutation, and the columns of ALL parts permuted by the first part's old_to_new -- the handles the
+ * host route (partition, uspmv_convert_to_scs with fixed_permutation, uspmv_permute_scs_cols, upload) gives, array for array.  They go
+ * straight into uspmv_dmat_optimize_device_ap / _device_ap_hp / _sweep_device* and uspmv_spmv_ap[_hp] / uspmv_spmmv_ap[_hp].
+ * layout, d_old_to_new, d_new_to_old (any may be NULL) describe the first part; part_nnz[3] (may be NULL) = entries of hi, mid, lo;
+ * mid may be NULL for the two-part kinds (*mid is set to NULL otherwise).  A row without an entry in the first part that its ordering
+ * sends behind n_rows while another part has entries in it is refused as uspmv_convert_to_scs refuses it.  On failure nothing is returned.
+ * Device memory beyond the returned handles: the compacted copy of the parts (16 bytes per entry, each part released as soon as it is
+ * converted) + 60 bytes per 1024 entries + about 24 bytes per padded row of conversion scratch. */
+int uspmv_convert_to_scs_device_ap_from_arrays(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                                               int64_t nnz, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2,
+                                               int sort_mode, void *stream, uspmv_scs_t **layout, int32_t *d_old_to_new, int32_t *d_new_to_old,
+                                               int64_t part_nnz[3], uspmv_dmat_t **hi, uspmv_dmat_t **mid, uspmv_dmat_t **lo);
 /* copies of the device arrays of a handle (any pointer may be NULL): n_chunks+1, n_chunks, n_elements, n_elements */
 int uspmv_dmat_download(const uspmv_dmat_t *m, int32_t *chunk_ptrs, int32_t *chunk_lengths, int32_t *col_idxs, void *values);
 /* Wrap arrays that already live in HBM (owned by the caller, e.g. a framework allocator). */

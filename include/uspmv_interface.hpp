@@ -233,6 +233,55 @@ private:
     ST n_rows_padded_ = 0;
 };
 
+// The two or three device-resident parts of an adaptive-precision split, built from COO arrays that already live in HBM
+// (uspmv_convert_to_scs_device_ap_from_arrays: partition, conversion and column permutation on the device).  Same ownership rules as
+// DeviceScs: RAII over the handles, move-only.  kind: USPMV_AP_DP_SP | _DP_HP | _SP_HP | _DP_SP_HP; x and y are double, float for
+// USPMV_AP_SP_HP.  d_perm / d_inv_perm (device, n_rows ints each, may be null) receive the first part's old_to_new_idx / new_to_old_idx.
+class DeviceApScs {
+public:
+    DeviceApScs() = default;
+    DeviceApScs(const DeviceApScs &) = delete;
+    DeviceApScs &operator=(const DeviceApScs &) = delete;
+    DeviceApScs(DeviceApScs &&o) noexcept : kind_(o.kind_), n_rows_padded_(o.n_rows_padded_) {
+        for (int k = 0; k < 3; ++k) { h_[k] = o.h_[k]; o.h_[k] = nullptr; part_nnz_[k] = o.part_nnz_[k]; }
+    }
+    ~DeviceApScs() { for (uspmv_dmat_t *h : h_) if (h) uspmv_dmat_free(h); }
+    static DeviceApScs from_device_coo(const int *d_I, const int *d_J, const double *d_V, ST n_rows, ST n_cols, ST nnz, ST C, ST sigma, int kind,
+                                       double threshold_1, double threshold_2, int *d_perm, int *d_inv_perm, bool stable_ties = false,
+                                       bool optimise = true, void *stream = nullptr) {
+        DeviceApScs d;
+        d.kind_ = kind;
+        uspmv_detail::check(uspmv_convert_to_scs_device_ap_from_arrays(d_I, d_J, d_V, n_rows, n_cols, nnz, C, sigma, kind, threshold_1, threshold_2,
+                                                                       stable_ties ? USPMV_SORT_DEVICE_STABLE : USPMV_SORT_HOST, stream, nullptr, d_perm,
+                                                                       d_inv_perm, d.part_nnz_, &d.h_[0], &d.h_[1], &d.h_[2]),
+                            "uspmv_convert_to_scs_device_ap_from_arrays");
+        d.n_rows_padded_ = ((n_rows + C - 1) / C) * C;
+        if (optimise) {
+            if (kind == USPMV_AP_DP_SP) uspmv_detail::check(uspmv_dmat_optimize_device_ap(d.h_[0], d.h_[2], 0, nullptr, nullptr), "uspmv_dmat_optimize_device_ap");
+            else uspmv_detail::check(uspmv_dmat_optimize_device_ap_hp(d.h_[0], d.h_[1], d.h_[2], 0, nullptr, nullptr), "uspmv_dmat_optimize_device_ap_hp");
+        }
+        return d;
+    }
+    void spmv(const void *d_x, void *d_y, void *stream = nullptr) const {
+        if (kind_ == USPMV_AP_DP_SP) uspmv_detail::check(uspmv_spmv_ap(h_[0], h_[2], (const double *)d_x, (double *)d_y, stream), "uspmv_spmv_ap");
+        else uspmv_detail::check(uspmv_spmv_ap_hp(h_[0], h_[1], h_[2], d_x, d_y, stream), "uspmv_spmv_ap_hp");
+    }
+    void spmmv(const void *d_X, void *d_Y, int b, ST ld, bool rowwise, void *stream = nullptr) const {
+        const int lay = rowwise ? USPMV_ROWWISE : USPMV_COLWISE;
+        if (kind_ == USPMV_AP_DP_SP) uspmv_detail::check(uspmv_spmmv_ap(h_[0], h_[2], d_X, d_Y, b, ld, lay, stream), "uspmv_spmmv_ap");
+        else uspmv_detail::check(uspmv_spmmv_ap_hp(h_[0], h_[1], h_[2], d_X, d_Y, b, ld, lay, stream), "uspmv_spmmv_ap_hp");
+    }
+    ST n_rows_padded() const { return n_rows_padded_; }
+    ST part_nnz(int part) const { return part_nnz_[part]; }              // 0 hi, 1 mid, 2 lo
+    uspmv_dmat_t *handle(int part) const { return h_[part]; }
+
+private:
+    uspmv_dmat_t *h_[3] = {nullptr, nullptr, nullptr};
+    int64_t part_nnz_[3] = {0, 0, 0};
+    int kind_ = USPMV_AP_DP_SP;
+    ST n_rows_padded_ = 0;
+};
+
 // adaptive precision dp+sp on a block of b vectors (uspmv_spmmv_ap): dp holds the double part, sp the float part of one split, both in
 // one row layout; X and Y double.  dp.x_prepared / dp.x_released serve a column-major X that does not change between calls.
 inline void spmmv_ap(const DeviceScs &dp, const DeviceScs &sp, const void *d_X, void *d_Y, int b, ST ld, bool rowwise, void *stream = nullptr) {

@@ -16,6 +16,7 @@ _LIB = None
 
 F64, F32, F16 = 0, 1, 2
 AP_DP_HP, AP_SP_HP, AP_DP_SP_HP = 0, 1, 2     # kinds of uspmv_partition_precisions_hp
+AP_DP_SP = 3                                  # ... and the fourth kind of the device-side set-up (partition_precisions_device)
 COLWISE, ROWWISE = 0, 1
 SEG_ROWS, SEG_NNZ = 0, 1
 
@@ -73,6 +74,12 @@ _SIGS = {
     "uspmv_apply_permutation": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int]),
     "uspmv_partition_precisions": (C.c_int, [_vp, C.c_double, C.POINTER(_vp), C.POINTER(_vp)]),
     "uspmv_partition_precisions_hp": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "uspmv_partition_precisions_device": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, C.c_double, C.c_double, _vp, C.POINTER(_vp)]),
+    "uspmv_dcoo_arrays": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64)]),
+    "uspmv_dcoo_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "uspmv_dcoo_free": (None, [_vp]),
+    "uspmv_convert_to_scs_device_ap_from_arrays": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int, C.c_double, C.c_double, C.c_int, _vp,
+                                                             C.POINTER(_vp), _vp, _vp, C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "uspmv_dmat_optimize_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_dmat_optimize_device_ap_hp": (C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_spmv_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -444,7 +451,7 @@ def partition_precisions(coo, threshold_1):
     return Coo(dp), Coo(sp)
 
 
-_AP_KINDS = {"dp_hp": AP_DP_HP, "sp_hp": AP_SP_HP, "dp_sp_hp": AP_DP_SP_HP}
+_AP_KINDS = {"dp_hp": AP_DP_HP, "sp_hp": AP_SP_HP, "dp_sp_hp": AP_DP_SP_HP, "dp_sp": AP_DP_SP}
 
 
 def partition_precisions_hp(coo, kind, threshold_1, threshold_2=0.0):
@@ -1099,14 +1106,69 @@ def convert_to_scs_device_from_arrays(d_I, d_J, d_V, n_rows, n_cols, C_, sigma, 
         s = Scs(hs)
         return s, DeviceMatrix(s, d_I.device, _handle=hA), o2n, n2o
 
-    class _Meta:      # what DeviceMatrix needs to know about a handle that has no host struct
+    return None, DeviceMatrix(_handle_meta(hA, n_rows, nnz), d_I.device, _handle=hA), o2n, n2o
+
+
+def _handle_meta(hA, n_rows, nnz):
+    """what DeviceMatrix needs to know about a handle that has no host struct"""
+    class _Meta:
         pass
     m = (_i64 * 4)()
     _ck(lib().uspmv_dmat_meta(hA, m))
     s = _Meta()
     s.C, s.n_chunks, s.n_elements, s.dtype = int(m[0]), int(m[1]), int(m[2]), int(m[3])
     s.n_rows, s.n_rows_padded, s.nnz = n_rows, s.n_chunks * s.C, nnz
-    return None, DeviceMatrix(s, d_I.device, _handle=hA), o2n, n2o
+    return s
+
+
+def partition_precisions_device(d_I, d_J, d_V, n_rows, n_cols, kind, threshold_1, threshold_2=0.0, stream=None):
+    """partition_precisions[_hp] of DEVICE-resident COO arrays (torch int32 / int32 / float64 tensors, entries sorted by row; kind: AP_* or
+    "dp_sp" | "dp_hp" | "sp_hp" | "dp_sp_hp"): [hi, mid, lo], each an (I, J, V) triple of device tensors -- copies owned by torch, V float64
+    holding the part's rounded value -- and mid None for the two-part kinds."""
+    import torch
+    assert d_I.dtype == torch.int32 and d_J.dtype == torch.int32 and d_V.dtype == torch.float64 and d_I.is_cuda
+    parts = (_vp * 3)()
+    st = _stream_ptr(stream)
+    _ck(lib().uspmv_partition_precisions_device(_dp(d_I), _dp(d_J), _dp(d_V), n_rows, n_cols, int(d_I.numel()), _AP_KINDS.get(kind, kind),
+                                                threshold_1, threshold_2, st, parts))
+    out = []
+    try:
+        for h in parts:
+            if not h:
+                out.append(None)
+                continue
+            n = _i64()
+            _ck(lib().uspmv_dcoo_arrays(h, None, None, None, C.byref(n)))
+            I = torch.empty(n.value, dtype=torch.int32, device=d_I.device); J = torch.empty_like(I)
+            V = torch.empty(n.value, dtype=torch.float64, device=d_I.device)
+            _ck(lib().uspmv_dcoo_copy(h, _dp(I), _dp(J), _dp(V), st))
+            out.append((I, J, V))
+    finally:
+        for h in parts:
+            if h:
+                lib().uspmv_dcoo_free(h)
+    return out
+
+
+def convert_ap_device_from_arrays(d_I, d_J, d_V, n_rows, n_cols, C_, sigma, kind, threshold_1, threshold_2=0.0, sort=SORT_HOST, want_layout=True,
+                                  stream=None):
+    """The adaptive-precision set-up in one call from DEVICE-resident COO arrays (uspmv_convert_to_scs_device_ap_from_arrays): returns
+    (layout-only Scs of the first part or None, [A_hi, A_mid | None, A_lo], old_to_new, new_to_old, part_nnz) -- the handles of the host
+    route (partition, convert_to_scs with the first part's permutation, permute_scs_cols with it, upload), ready for optimize_device_ap[_hp]
+    and spmv_ap[_hp] / spmmv_ap[_hp]; the permutations, of the first part, as int32 device tensors."""
+    import torch
+    assert d_I.dtype == torch.int32 and d_J.dtype == torch.int32 and d_V.dtype == torch.float64 and d_I.is_cuda
+    nnz = int(d_I.numel())
+    o2n = torch.empty(max(n_rows, 0), dtype=torch.int32, device=d_I.device)
+    n2o = torch.empty(max(n_rows, 0), dtype=torch.int32, device=d_I.device)
+    hs, hh, hm, hl = _vp(), _vp(), _vp(), _vp()
+    cnt = (_i64 * 3)()
+    _ck(lib().uspmv_convert_to_scs_device_ap_from_arrays(_dp(d_I), _dp(d_J), _dp(d_V), n_rows, n_cols, nnz, C_, sigma, _AP_KINDS.get(kind, kind),
+                                                         threshold_1, threshold_2, int(sort), _stream_ptr(stream), C.byref(hs) if want_layout else None,
+                                                         _dp(o2n), _dp(n2o), cnt, C.byref(hh), C.byref(hm), C.byref(hl)))
+    lay = Scs(hs) if want_layout else None
+    hand = [DeviceMatrix(_handle_meta(h, n_rows, int(c)), d_I.device, _handle=h) if h else None for h, c in zip((hh, hm, hl), cnt)]
+    return lay, hand, o2n, n2o, [int(c) for c in cnt]
 
 
 def spmmv_x_prepared(A, X, b, ld, stream=None):

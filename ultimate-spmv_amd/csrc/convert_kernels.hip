@@ -148,14 +148,27 @@ __global__ void perm_kernel(const int *__restrict__ new_pos, const int n_rows, c
 
 }  // namespace
 
-extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
-                                                       int64_t nnz, int64_t C, int64_t sigma, int dtype, const int32_t *d_fixed_permutation,
-                                                       int permute_cols, int sort_mode, void *stream, uspmv_scs_t **layout, int32_t *d_old_to_new,
-                                                       int32_t *d_new_to_old, uspmv_dmat_t **out) {
-    const char *who = "uspmv_convert_to_scs_device_from_arrays";
+namespace uspmv_dev {
+int launch_exclusive_scan(const long *d_in, long n, long *d_part, long *d_sums, long *d_total, int *d_ptrs, hipStream_t st) {
+    const long nb = (n + 1023) / 1024;
+    hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(256), 0, st, d_in, n, d_part, d_sums);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, st, d_sums, nb, d_total);
+    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, d_part, d_sums, d_total, n, d_ptrs);
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+}  // namespace uspmv_dev
+
+// uspmv_convert_to_scs_device_from_arrays, with the column permutation given explicitly: d_col_perm != NULL is what permute_scs_cols is
+// folded in with (the parts of an adaptive-precision split all take the FIRST part's old_to_new, while a fixed-permutation struct's own
+// is the identity); NULL: the struct's own old_to_new when permute_cols, none otherwise.
+static int convert_from_arrays(const char *who, const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                               int64_t nnz, int64_t C, int64_t sigma, int dtype, const int32_t *d_fixed_permutation, int permute_cols,
+                               const int32_t *d_col_perm, int sort_mode, void *stream, uspmv_scs_t **layout, int32_t *d_old_to_new,
+                               int32_t *d_new_to_old, uspmv_dmat_t **out) {
     if (!out || n_rows < 1 || nnz < 0 || (nnz > 0 && (!d_I || !d_J || !d_V))) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
     if (C < 1 || sigma < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: C and sigma must be >= 1", who);
-    if (dtype != USPMV_F64 && dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+    if (dtype != USPMV_F64 && dtype != USPMV_F32 && dtype != USPMV_F16) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
     if (sort_mode != USPMV_SORT_HOST && sort_mode != USPMV_SORT_DEVICE_STABLE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown sort mode %d", who, sort_mode);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); return uspmv::fail(USPMV_ERR_NO_DEVICE, "%s: no HIP device", who); }
@@ -228,9 +241,7 @@ extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const
     A->chunk_lengths = cl; A->chunk_ptrs = cp;
     if (e != hipSuccess) { return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e)); }
     hipLaunchKernelGGL(chunk_max_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, st, len_new, (long)n_chunks, (int)C, cl, elems);
-    hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(256), 0, st, elems, (long)n_chunks, part, sums);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, nb, total);
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((n_chunks + 1 + 255) / 256)), dim3(256), 0, st, part, sums, total, (long)n_chunks, cp);
+    if (int rc = launch_exclusive_scan(elems, (long)n_chunks, part, sums, total, cp, st)) return rc;
     if (d_fixed_permutation)
         hipLaunchKernelGGL(check_fixed_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, start, d_fixed_permutation, cl, (int)n_rows, (int)C, flag);
     long h_total = 0;
@@ -253,19 +264,20 @@ extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const
     if (!n2o) { HIP_TRY(n2o_own.alloc(4 * (size_t)n_rows)); n2o = n2o_own; }
     HIP_TRY(hipMemsetAsync(n2o, 0, 4 * (size_t)n_rows, st));
     hipLaunchKernelGGL(perm_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, new_pos, (int)n_rows, d_fixed_permutation != nullptr, o2n, n2o);
-    const size_t vsz = dtype == USPMV_F64 ? 8 : 4, ne = (size_t)std::max<int64_t>(h_total, 1);
+    const size_t vsz = uspmv_dtype_bytes(dtype), ne = (size_t)std::max<int64_t>(h_total, 1);
     e = A->own.col_idxs.alloc(4 * ne);
     if (e == hipSuccess) e = A->own.values.alloc(vsz * ne);
     void *ci = A->own.col_idxs, *va = A->own.values;
     A->col_idxs = (const int32_t *)ci; A->values = va;
+    const int *col_perm = d_col_perm ? d_col_perm : permute_cols ? o2n : nullptr;
     int pad_col = 0;
-    if (e == hipSuccess && permute_cols) e = hipMemcpyAsync(&pad_col, o2n, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && permute_cols) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && col_perm) e = hipMemcpyAsync(&pad_col, col_perm, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && col_perm) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)ci, pad_col, ne, st);
     if (e == hipSuccess) e = hipMemsetAsync(va, 0, vsz * ne, st);
     if (e != hipSuccess) { return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e)); }
     if (nnz > 0)
-        if (int rc = launch_scs_fill(dtype, (long)nnz, (int)C, (int)n_rows, d_I, d_J, d_V, start, row_map, permute_cols ? o2n : nullptr, cp, (int *)ci, va, st)) { return rc; }
+        if (int rc = launch_scs_fill(dtype, (long)nnz, (int)C, (int)n_rows, d_I, d_J, d_V, start, row_map, col_perm, cp, (int *)ci, va, st)) { return rc; }
 
     // ---- optional host struct without entries (meta data, chunk arrays, permutations), as uspmv_convert_to_scs_device returns it
     if (layout) {
@@ -285,5 +297,172 @@ extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const
     e = hipStreamSynchronize(st);                            // (the scratch of this call is released on return)
     if (e != hipSuccess) { if (layout) { delete *layout; *layout = nullptr; } return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
     *out = A.release();
+    return USPMV_OK;
+}
+
+extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                                                       int64_t nnz, int64_t C, int64_t sigma, int dtype, const int32_t *d_fixed_permutation,
+                                                       int permute_cols, int sort_mode, void *stream, uspmv_scs_t **layout, int32_t *d_old_to_new,
+                                                       int32_t *d_new_to_old, uspmv_dmat_t **out) {
+    return convert_from_arrays("uspmv_convert_to_scs_device_from_arrays", d_I, d_J, d_V, n_rows, n_cols, nnz, C, sigma, dtype, d_fixed_permutation,
+                               permute_cols, nullptr, sort_mode, stream, layout, d_old_to_new, d_new_to_old, out);
+}
+
+// ============================================================================ adaptive-precision set-up from device-resident COO arrays
+// One part of uspmv_partition_precisions_device: compacted COO arrays in HBM, owned by the object.
+struct uspmv_dcoo {
+    DeviceBuf<int32_t> I, J;
+    DeviceBuf<double> V;
+    int64_t nnz = 0;
+};
+
+namespace {
+
+bool ap_kind_known(int kind) { return kind == USPMV_AP_DP_HP || kind == USPMV_AP_SP_HP || kind == USPMV_AP_DP_SP_HP || kind == USPMV_AP_DP_SP; }
+
+// the three passes (csrc/ap_partition_kernels.hip); the caller has checked the arguments and the device.  Nothing is written to a part
+// before the index checks and the NaN check of pass (a) have come back clean.
+int partition_device(const char *who, const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                     int kind, double t1, double t2, hipStream_t st, std::unique_ptr<uspmv_dcoo> parts[3]) {
+    const bool three = kind == USPMV_AP_DP_SP_HP;
+    const long n_wg = ap_partition_workgroups((long)nnz), n_cnt = 3 * n_wg;
+    int32_t h_base[4] = {0, 0, 0, 0};                     // where the parts start in the scan, and the total
+    if (n_wg > 0) {
+        DeviceBuf<long> counts, part, sums, total;
+        DeviceBuf<int> base, flag;
+        DeviceBuf<unsigned long long> first_nan;
+        HIP_TRY(counts.alloc(8 * (size_t)n_cnt));
+        HIP_TRY(part.alloc(8 * (size_t)n_cnt));
+        HIP_TRY(sums.alloc(8 * (size_t)((n_cnt + 1023) / 1024)));
+        HIP_TRY(total.alloc(8));
+        HIP_TRY(base.alloc(4 * ((size_t)n_cnt + 1)));
+        HIP_TRY(flag.alloc(4));
+        HIP_TRY(first_nan.alloc(8));
+        HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
+        HIP_TRY(hipMemsetAsync(first_nan, 0xFF, 8, st));
+        if (int rc = launch_ap_partition_count(d_I, d_J, d_V, (long)nnz, (int)n_rows, (int)n_cols, kind, t1, t2, counts, flag, first_nan, st)) return rc;
+        if (int rc = launch_exclusive_scan(counts, n_cnt, part, sums, total, base, st)) return rc;
+        int h_flag = 0;
+        unsigned long long h_nan = 0;
+        HIP_TRY(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&h_nan, first_nan, 8, hipMemcpyDeviceToHost, st));
+        for (int p = 0; p < 4; ++p) HIP_TRY(hipMemcpyAsync(&h_base[p], (int *)base + (size_t)p * n_wg, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (h_flag & 2) return uspmv::fail(USPMV_ERR_INVALID, "%s: a row index lies outside [0, n_rows)", who);
+        if (h_flag & 4) return uspmv::fail(USPMV_ERR_INVALID, "%s: a column index lies outside [0, n_cols)", who);
+        if (h_flag & 1) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: COO entries must be sorted by row (uspmv_read_mtx and the generators produce that order)", who);
+        if (h_nan != ~0ull) return uspmv::fail(USPMV_ERR_INVALID, "%s: element %lld fits neither struct", who, (long long)h_nan);
+        ApPartOut o{};
+        for (int p = 0; p < 3; ++p) {
+            if (p == 1 && !three) continue;
+            parts[p].reset(new uspmv_dcoo);
+            const size_t n = (size_t)(h_base[p + 1] - h_base[p]);
+            parts[p]->nnz = (int64_t)n;
+            HIP_TRY(parts[p]->I.alloc(4 * n));
+            HIP_TRY(parts[p]->J.alloc(4 * n));
+            HIP_TRY(parts[p]->V.alloc(8 * n));
+            o.I[p] = parts[p]->I; o.J[p] = parts[p]->J; o.V[p] = parts[p]->V; o.n[p] = (long)n;
+        }
+        if (int rc = launch_ap_partition_scatter(d_I, d_J, d_V, (long)nnz, kind, t1, t2, base, o, st)) return rc;
+        HIP_TRY(hipStreamSynchronize(st));               // (the scratch of this call is released on return)
+    } else {
+        for (int p = 0; p < 3; ++p)
+            if (p != 1 || three) parts[p].reset(new uspmv_dcoo);
+    }
+    return USPMV_OK;
+}
+
+int ap_common_args(const char *who, const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols, int64_t nnz, int kind) {
+    if (nnz < 0 || (nnz > 0 && (!d_I || !d_J || !d_V))) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    if (!ap_kind_known(kind)) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown kind %d", who, kind);
+    if (n_rows < 1 || n_cols < 0) return uspmv::fail(USPMV_ERR_INVALID, "%s: matrix has no rows", who);
+    return USPMV_OK;
+}
+
+}  // namespace
+
+extern "C" int uspmv_partition_precisions_device(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                                                 int kind, double threshold_1, double threshold_2, void *stream, uspmv_dcoo_t *parts[3]) {
+    const char *who = "uspmv_partition_precisions_device";
+    if (!parts) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (int rc = ap_common_args(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind)) return rc;
+    if (int rc = require_device()) return rc;
+    if (n_rows > INT32_MAX || n_cols > INT32_MAX || nnz > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: rows / columns / entries exceed int32", who);
+    std::unique_ptr<uspmv_dcoo> p[3];
+    if (int rc = partition_device(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind, threshold_1, threshold_2, (hipStream_t)stream, p)) return rc;
+    for (int k = 0; k < 3; ++k) parts[k] = p[k].release();
+    return USPMV_OK;
+}
+
+extern "C" int uspmv_dcoo_arrays(const uspmv_dcoo_t *p, const int32_t **d_I, const int32_t **d_J, const double **d_V, int64_t *nnz) {
+    if (!p) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dcoo_arrays: NULL part");
+    if (d_I) *d_I = p->I;
+    if (d_J) *d_J = p->J;
+    if (d_V) *d_V = p->V;
+    if (nnz) *nnz = p->nnz;
+    return USPMV_OK;
+}
+
+extern "C" int uspmv_dcoo_copy(const uspmv_dcoo_t *p, int32_t *d_I, int32_t *d_J, double *d_V, void *stream) {
+    if (!p) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dcoo_copy: NULL part");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)p->nnz;
+    if (n && d_I) HIP_TRY(hipMemcpyAsync(d_I, p->I, 4 * n, hipMemcpyDeviceToDevice, st));
+    if (n && d_J) HIP_TRY(hipMemcpyAsync(d_J, p->J, 4 * n, hipMemcpyDeviceToDevice, st));
+    if (n && d_V) HIP_TRY(hipMemcpyAsync(d_V, p->V, 8 * n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return USPMV_OK;
+}
+
+extern "C" void uspmv_dcoo_free(uspmv_dcoo_t *p) { delete p; }
+
+extern "C" int uspmv_convert_to_scs_device_ap_from_arrays(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                                                          int64_t nnz, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2,
+                                                          int sort_mode, void *stream, uspmv_scs_t **layout, int32_t *d_old_to_new,
+                                                          int32_t *d_new_to_old, int64_t part_nnz[3], uspmv_dmat_t **hi, uspmv_dmat_t **mid,
+                                                          uspmv_dmat_t **lo) {
+    const char *who = "uspmv_convert_to_scs_device_ap_from_arrays";
+    if (int rc = ap_common_args(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind)) return rc;
+    const bool three = kind == USPMV_AP_DP_SP_HP;
+    if (!hi || !lo || (three && !mid)) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL output for a part the kind has", who);
+    if (C < 1 || sigma < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: C and sigma must be >= 1", who);
+    if (sort_mode != USPMV_SORT_HOST && sort_mode != USPMV_SORT_DEVICE_STABLE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown sort mode %d", who, sort_mode);
+    if (int rc = require_device()) return rc;
+    const int64_t n_pad = (n_rows + C - 1) / C * C;
+    if (n_pad > INT32_MAX || n_cols > INT32_MAX || nnz > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: padded rows / columns / entries exceed int32", who);
+    if (sort_mode == USPMV_SORT_DEVICE_STABLE && std::min<int64_t>(sigma, n_pad) > 8192)
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: the device-side stable ordering takes sorting scopes of up to 8192 rows (sigma = %lld): use USPMV_SORT_HOST", who, (long long)sigma);
+    hipStream_t st = (hipStream_t)stream;
+    std::unique_ptr<uspmv_dcoo> p[3];
+    if (int rc = partition_device(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind, threshold_1, threshold_2, st, p)) return rc;
+
+    // the first part orders the rows; the others take its permutation for their rows AND for their columns (what uspmv_main.cpp and the
+    // host tests do with uspmv_convert_to_scs(fixed_permutation) + uspmv_permute_scs_cols(first part's old_to_new))
+    struct Free { void operator()(uspmv_dmat_t *m) const { uspmv_dmat_free(m); } };
+    std::unique_ptr<uspmv_dmat_t, Free> A[3];
+    std::unique_ptr<uspmv_scs> lay;
+    DeviceBuf<int32_t> o2n_own;
+    int32_t *o2n = d_old_to_new;
+    if (!o2n) { HIP_TRY(o2n_own.alloc(4 * (size_t)n_rows)); o2n = o2n_own; }
+    const int dtypes[3] = {kind == USPMV_AP_SP_HP ? USPMV_F32 : USPMV_F64, USPMV_F32, kind == USPMV_AP_DP_SP ? USPMV_F32 : USPMV_F16};
+    int64_t cnt[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) {
+        if (!p[k]) continue;
+        cnt[k] = p[k]->nnz;
+        uspmv_dmat_t *h = nullptr;
+        uspmv_scs_t *l = nullptr;
+        const int rc = convert_from_arrays(who, p[k]->I, p[k]->J, p[k]->V, n_rows, n_cols, p[k]->nnz, C, sigma, dtypes[k], k == 0 ? nullptr : o2n, 1,
+                                           k == 0 ? nullptr : o2n, sort_mode, stream, k == 0 && layout ? &l : nullptr, k == 0 ? o2n : nullptr,
+                                           k == 0 ? d_new_to_old : nullptr, &h);
+        if (rc) return rc;                                // (what was built so far is released by its owner)
+        A[k].reset(h);
+        if (k == 0) lay.reset(l);
+        p[k].reset();                                     // the part's COO copy is not needed any longer
+    }
+    if (layout) *layout = lay.release();
+    if (part_nnz) { part_nnz[0] = cnt[0]; part_nnz[1] = cnt[1]; part_nnz[2] = cnt[2]; }
+    *hi = A[0].release();
+    if (mid) *mid = A[1].release();
+    *lo = A[2].release();
     return USPMV_OK;
 }

@@ -3,6 +3,8 @@
 // (uspmv_dmat_optimize and its variants) is csrc/tlc_planner.hip.
 #include "uspmv_device.hpp"
 
+#include "../host/uspmv_f16_round.hpp"
+
 #include <mutex>
 
 using namespace uspmv_dev;
@@ -46,6 +48,12 @@ namespace {
 // COO -> SELL-C-sigma scatter of uspmv_convert_to_scs_device: one thread per COO entry k (entries sorted by
 // row, order inside a row preserved): slot = k - row_start[row], destination as convert_to_scs
 // (code/utilities.hpp:2013-2036).  perm != nullptr folds permute_scs_cols (:1802-1831) into the same pass.
+// VT = unsigned short: binary16 bits, rounded once from the double (uspmv_f16_round.hpp), as uspmv_convert_to_scs stores USPMV_F16.
+template <typename VT>
+__device__ __forceinline__ VT scs_fill_value(double v) {
+    if constexpr (sizeof(VT) == 2) return uspmv_f64_bits_to_f16((uint64_t)__double_as_longlong(v));
+    else return (VT)v;
+}
 template <typename VT>
 __global__ void scs_fill_kernel(const long nnz, const int C, const int n_rows, const int *__restrict__ I,
                                 const int *__restrict__ J, const double *__restrict__ V,
@@ -62,7 +70,7 @@ __global__ void scs_fill_kernel(const long nnz, const int C, const int n_rows, c
     int col = J[k];
     if (perm && col < n_rows) col = perm[col];
     col_idxs[dst] = col;
-    values[dst] = (VT)V[k];
+    values[dst] = scs_fill_value<VT>(V[k]);
 }
 
 // out[i] = in[perm[idx ? idx[i] : i] + offset]   (pack_send_buf with idx, apply_permutation without)
@@ -242,8 +250,10 @@ int launch_scs_fill(int dtype, long nnz, int C, int n_rows, const int *I, const 
     const unsigned grid = (unsigned)((nnz + 255) / 256);
     if (dtype == USPMV_F64)
         hipLaunchKernelGGL(scs_fill_kernel<double>, dim3(grid), dim3(256), 0, st, nnz, C, n_rows, I, J, V, row_start, row_map, perm, chunk_ptrs, col_idxs, (double *)values);
-    else
+    else if (dtype == USPMV_F32)
         hipLaunchKernelGGL(scs_fill_kernel<float>, dim3(grid), dim3(256), 0, st, nnz, C, n_rows, I, J, V, row_start, row_map, perm, chunk_ptrs, col_idxs, (float *)values);
+    else
+        hipLaunchKernelGGL(scs_fill_kernel<unsigned short>, dim3(grid), dim3(256), 0, st, nnz, C, n_rows, I, J, V, row_start, row_map, perm, chunk_ptrs, col_idxs, (unsigned short *)values);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }

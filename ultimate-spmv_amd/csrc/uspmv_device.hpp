@@ -566,9 +566,26 @@ int launch_sweep_fill(const uspmv_dmat *A, int wlog, int R, long n_sweep_tiles, 
                       const unsigned long long *d_cnt_off, const unsigned *d_wave_off, const int *d_row_le, const int *d_row_pad,
                       unsigned char *d_cnt, void *d_vals, unsigned short *d_idx, int *d_pad_col, hipStream_t st);
 
+// exclusive scan of n longs on the device, narrowed to 32 bits: d_ptrs[0 .. n] (d_ptrs[n] = *d_total = the sum); d_part: n longs,
+// d_sums: (n + 1023) / 1024 longs of scratch (convert_kernels.hip: the chunk pointers, the bases of the partition)
+int launch_exclusive_scan(const long *d_in, long n, long *d_part, long *d_sums, long *d_total, int *d_ptrs, hipStream_t st);
+// partition_precisions on the device (ap_partition_kernels.hip): the compacted parts' arrays (n: their sizes) ...
+struct ApPartOut {
+    int *I[3], *J[3];
+    double *V[3];
+    long n[3];
+};
+// ... workgroups of the two passes = counts per part, d_counts[part * n_wg + wg]; d_flag: 1 rows unsorted, 2 row index / 4 column index
+// outside the matrix; *d_first_nan: the first element that fits no part (min over the workgroups); d_base: the scan of d_counts
+long ap_partition_workgroups(long nnz);
+int launch_ap_partition_count(const int *I, const int *J, const double *V, long nnz, int n_rows, int n_cols, int kind, double t1, double t2,
+                              long *d_counts, int *d_flag, unsigned long long *d_first_nan, hipStream_t st);
+int launch_ap_partition_scatter(const int *I, const int *J, const double *V, long nnz, int kind, double t1, double t2, const int *d_base,
+                                const ApPartOut &out, hipStream_t st);
+
 }  // namespace uspmv_dev
 
-#define HIP_TRY(call)                                                                              \
+#define HIP_TRY(call)                                                                             \
     do {                                                                                           \
         hipError_t e_ = (call);                                                                    \
         if (e_ != hipSuccess)                                                                      \

@@ -21,49 +21,18 @@
 #include <utility>
 
 #include "uspmv_internal.hpp"
+#include "uspmv_f16_round.hpp"
 
-// binary16 from a double in ONE rounding step (to nearest, ties to even), with integer operations on the bits (the host compiler has no
-// _Float16 here): subnormal results kept, overflow to +-inf, -0.0 kept, NaN -> quiet NaN with the top mantissa bits (numpy's
-// npy_doublebits_to_halfbits, so that the result equals numpy's float64 -> float16 bit for bit).
+// binary16 from a double in ONE rounding step (to nearest, ties to even) and back, with integer operations on the bits (the host
+// compiler has no _Float16 here): uspmv_f16_round.hpp, the text the device-side partition compiles as well.
 uint16_t uspmv_f64_to_f16(double v) {
     uint64_t b;
     std::memcpy(&b, &v, 8);
-    const uint16_t sign = (uint16_t)((b >> 48) & 0x8000u);
-    const int e = (int)((b >> 52) & 0x7FF);
-    const uint64_t m = b & 0xFFFFFFFFFFFFFull;
-    if (e == 0x7FF) {
-        if (m == 0) return (uint16_t)(sign | 0x7C00u);
-        const uint16_t q = (uint16_t)(m >> 42);
-        return (uint16_t)(sign | 0x7C00u | (q ? q : 1u));
-    }
-    const int E = e - 1023;
-    if (E >= 16) return (uint16_t)(sign | 0x7C00u);                   // |v| >= 65536: beyond every rounding to 65504
-    if (e == 0 || E < -26) return sign;                                // below half the smallest subnormal (2^-25): +-0
-    uint64_t q, rem, half;
-    if (E >= -14) {                                                    // normal: 10 mantissa bits kept, 42 rounded away
-        q = ((uint64_t)(E + 15) << 10) | (m >> 42);
-        rem = m & ((1ull << 42) - 1); half = 1ull << 41;
-    } else {                                                           // subnormal: units of 2^-24
-        const uint64_t M = m | (1ull << 52);
-        const int sh = 28 - E;                                         // 43 .. 54
-        q = M >> sh;
-        rem = M & ((1ull << sh) - 1); half = 1ull << (sh - 1);
-    }
-    if (rem > half || (rem == half && (q & 1))) ++q;                   // a carry moves into the exponent (0x7BFF + 1 = inf)
-    return (uint16_t)(sign | q);
+    return uspmv_f64_bits_to_f16(b);
 }
 
 double uspmv_f16_to_f64(uint16_t h) {
-    const uint64_t sign = (uint64_t)(h & 0x8000u) << 48;
-    const int e = (h >> 10) & 0x1F;
-    const uint64_t m = h & 0x3FFu;
-    uint64_t b;
-    if (e == 0x1F) b = sign | (0x7FFull << 52) | (m << 42);
-    else if (e == 0) {
-        const double v = std::ldexp((double)m, -24);
-        std::memcpy(&b, &v, 8);
-        b |= sign;
-    } else b = sign | ((uint64_t)(e - 15 + 1023) << 52) | (m << 42);
+    const uint64_t b = uspmv_f16_to_f64_bits(h);
     double v;
     std::memcpy(&v, &b, 8);
     return v;

@@ -398,6 +398,15 @@ int uspmv_spmmv_x_release(const uspmv_dmat_t *m);
  * kernel scs_ap_impl_cpu (code/ap_kernels.hpp:24-82): both parts accumulated in double from the
  * double x, y = dp_sum + sp_sum.  dp and sp must share C and n_chunks. */
 int uspmv_spmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const double *d_x, double *d_y, void *stream);
+/* uspmv_spmv_ap restricted to a subset of the rows, for the distributed ap step (no twin in the reference, which refuses ap under MPI:
+ * "not supported at this time", code/utilities.hpp:1445-1451).  Extends uspmv_spmv_tiles / uspmv_spmv_chunks to the ap[dp_sp] pair; every
+ * row written carries the bits uspmv_spmv_ap gives it, rows outside the list are not touched.
+ * _tiles: the tiles of the pair's shared tile-local-column plan (uspmv_dmat_optimize_ap; tile t = rows [t * tile_rows, (t + 1) * tile_rows)),
+ *   x must be 16-byte aligned.  _chunks: chunk ids, lane per row, any pair.  Entries < 0 are skipped (a conditional list). */
+int uspmv_spmv_ap_tiles(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const int32_t *d_tile_ids, int64_t n_ids, const double *d_x,
+                        double *d_y, void *stream);
+int uspmv_spmv_ap_chunks(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const int32_t *d_chunk_ids, int64_t n_ids, const double *d_x,
+                         double *d_y, void *stream);
 /* Adaptive precision dp+sp on block vectors: Y = (A_dp + A_sp) X, b right-hand sides, X and Y double.  The reference has no such path
  * (its CLI stops at "SpMMV is not yet implemented for AP kernels", code/utilities.hpp:1389).  For every C, column v of Y is bitwise what
  * uspmv_spmv_ap gives for column v of X: per (row, v) the dp FMA chain and the sp FMA chain of scs_ap_impl_cpu, each in slot order,
@@ -579,6 +588,10 @@ int uspmv_seg_local_coo(const uspmv_coo_t *total, const int32_t *wsa, int rank, 
  * SCS struct (scanned in storage order, padding entries included), rewrites col_idxs to
  * local + halo numbering, and records per owner which of ITS local rows this rank needs. */
 int uspmv_halo_discover(uspmv_scs_t *local_scs, const int32_t *wsa, int rank, int P, uspmv_halo_t **out);
+/* uspmv_halo_discover for the two structs of an ap[dp_sp] pair: ONE halo, as if collect_local_needed_heri ran over the dp struct's
+ * col_idxs followed by the sp struct's (first-seen scan in that order), both structs' columns rewritten against that one numbering.
+ * The structs must share C, n_chunks and the row layout (sp converted with dp's permutation). */
+int uspmv_halo_discover_ap(uspmv_scs_t *dp, uspmv_scs_t *sp, const int32_t *wsa, int rank, int P, uspmv_halo_t **out);
 /* n_halo = recv_counts_cumsum.back(); recv_counts_cumsum[P+1]; recv_idxs grouped by owner rank
  * ascending with recv_counts[P] entries each (borrowed pointers). */
 int uspmv_halo_meta(const uspmv_halo_t *h, int64_t *n_halo, const int32_t **recv_counts_cumsum,
@@ -697,6 +710,17 @@ int uspmv_dist_create_ex(const void *comm_id, int comm_rank, int comm_size, int 
 int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
                                   const int32_t *wsa, int64_t C, int64_t sigma, int dtype, int tlc, const uspmv_dist_options_t *opt,
                                   uspmv_dist_t **out);
+/* uspmv_dist_create_from_coo[_ex] for adaptive precision ap[dp_sp] (the reference refuses ap under MPI, code/utilities.hpp:1445-1451):
+ * uspmv_partition_precisions of the block at threshold_1 -> convert the dp part -> the sp part with the dp part's permutation ->
+ * uspmv_halo_discover_ap -> column permutation of both -> upload -> with tlc the pair's shared line plan at 256-row tiles -> tile classes
+ * from both parts -> the object.  Vectors are double.  Its step is uspmv_spmv_ap split into interior and boundary tiles (chunks);
+ * "pad_split" defaults to 1 here (an ap pair pads nearly every chunk of both parts, and the padding column is a halo column on every
+ * rank but the first).  "fused_step", "block_plan", "autotune_all" and uspmv_dist_spmmv answer USPMV_ERR_UNSUPPORTED on such an object. */
+int uspmv_dist_create_ap_from_coo(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                  const int32_t *wsa, int64_t C, int64_t sigma, double threshold_1, int tlc, uspmv_dist_t **out);
+int uspmv_dist_create_ap_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                     const int32_t *wsa, int64_t C, int64_t sigma, double threshold_1, int tlc,
+                                     const uspmv_dist_options_t *opt, uspmv_dist_t **out);
 /* the exchange plan of the object (borrowed): n_send, send_off[P+1], send_idxs[n_send], recv_off[P+1] as in uspmv_comm_plan_meta */
 int uspmv_dist_comm_plan(const uspmv_dist_t *d, int64_t *n_send, const int64_t **send_off, const int32_t **send_idxs,
                          const int64_t **recv_off);
@@ -709,10 +733,13 @@ int uspmv_dist_comm_plan(const uspmv_dist_t *d, int64_t *n_send, const int64_t *
  * "fused_step" 0|1 (default 0; tile lists: the step's tiles in ONE launch -- interior and padding tiles first, the boundary tiles at the end of
  *   the grid, each of which looks once whether the exchange has completed and otherwise defers itself to a small second launch behind
  *   the exchange; nothing spins.  0: interior launch, exchange, boundary launch),
- * "pad_split" 0|1 (default 0; 1: padding tiles run with the interior ones, see uspmv_dist_pad_info; 0: with the boundary tiles),
+ * "pad_split" 0|1 (default 0, on an ap[dp_sp] object 1; 1: padding tiles run with the interior ones, see uspmv_dist_pad_info; 0: with the
+ *   boundary tiles),
  * "autotune_all" 0|1 (default 0: uspmv_dist_autotune times overlap | plain; 1: the pad / fused arrangements as well),
  * "diag_spmmv_part" 0|1|2 (diagnosis only: the two-part block-vector step runs both parts, its interior part, its boundary part),
- * "block_plan" b (block vectors: build the phased block plan for b columns on the rank's matrix, 0 drops it; see uspmv_dist_spmmv). */
+ * "block_plan" b (block vectors: build the phased block plan for b columns on the rank's matrix, 0 drops it; see uspmv_dist_spmmv).
+ * On an ap[dp_sp] object (uspmv_dist_create_ap_from_coo) "fused_step" 1, "autotune_all" 1 and "block_plan" b > 0 answer
+ * USPMV_ERR_UNSUPPORTED; uspmv_dist_autotune times overlap | plain there and leaves "pad_split" as it is. */
 int uspmv_dist_set_option(uspmv_dist_t *d, const char *key, int value);
 /* How the single-vector step is arranged around the exchange: interior tiles during the exchange and boundary tiles after it | the
  * exchange, then the whole matrix (the reference's order) | overlap with the padding-only tiles in front of the exchange ("pad_split") |
@@ -735,6 +762,10 @@ int uspmv_dist_check(uspmv_dist_t *d, const uspmv_coo_t *local, const int32_t *w
 /* The host half of that check alone (no GPU): y_ref[i] (n_rows of `local`, dtype) = the entry-ordered FMA chain of local row i over
  * x_global[j] = 1 + 1e-3 * (j mod 1000), for steps that do not run on a uspmv_dist object (bench.py's torch.distributed twin). */
 int uspmv_dist_check_reference(const uspmv_coo_t *local, const int32_t *wsa, int rank, int P, int dtype, void *y_ref);
+/* uspmv_dist_check_reference for an ap[dp_sp] object (uspmv_dist_check applies it there): per local row the dp chain over the entries
+ * with |v| >= threshold_1 and the sp chain over the others with the value (double)(float)v, each an FMA chain in entry order from +0.0
+ * (scs_ap_impl_cpu, code/ap_kernels.hpp:24-82), y_ref[i] = dp + sp (double). */
+int uspmv_dist_check_reference_ap(const uspmv_coo_t *local, const int32_t *wsa, int rank, int P, double threshold_1, double *y_ref);
 /* HIP / RCCL versions this library was COMPILED against and the ones it RUNS on in this process:
  * v[0] HIP_VERSION (build), v[1] hipRuntimeGetVersion, v[2] NCCL_VERSION_CODE (build), v[3] ncclGetVersion. */
 int uspmv_runtime_versions(int v[4]);
@@ -748,6 +779,10 @@ int uspmv_dist_exchange(const uspmv_dist_t *d, int *exchange);
 int uspmv_dist_info(const uspmv_dist_t *d, int64_t meta[12]);
 /* borrowed handles of an object made by uspmv_dist_create_from_coo (NULL scs / halo otherwise) */
 int uspmv_dist_parts(const uspmv_dist_t *d, const uspmv_scs_t **scs, const uspmv_dmat_t **A, const uspmv_halo_t **halo);
+/* uspmv_dist_parts of an ap[dp_sp] object: both structs, both handles, the one halo (uspmv_dist_parts answers with the dp ones);
+ * the sp ones are NULL on a one-precision object */
+int uspmv_dist_parts_ap(const uspmv_dist_t *d, const uspmv_scs_t **scs_dp, const uspmv_scs_t **scs_sp, const uspmv_dmat_t **A_dp,
+                        const uspmv_dmat_t **A_sp, const uspmv_halo_t **halo);
 int uspmv_dist_set_overlap(uspmv_dist_t *d, int overlap);
 /* -no_pack 1 of the reference (code/classes_structs.hpp:941): no element is packed (pushed), every exchange of the object ships a
  * stale buffer (timing only) */

@@ -148,6 +148,9 @@ _SIGS = {
     "uspmv_read_partition": (C.c_int, [C.c_char_p, _i64, C.c_int, _vp]),
     "uspmv_coo_apply_partition": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp), _vp, _vp]),
     "uspmv_halo_discover": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "uspmv_halo_discover_ap": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "uspmv_spmv_ap_tiles": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "uspmv_spmv_ap_chunks": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "uspmv_halo_meta": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i32p), C.POINTER(_i32p), C.POINTER(_i32p)]),
     "uspmv_halo_free": (None, [_vp]),
     "uspmv_scs_chunk_classes": (C.c_int, [_vp, _i64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
@@ -176,6 +179,11 @@ _SIGS = {
     "uspmv_dist_autotune": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _i32p, _vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "uspmv_dist_check_reference": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_int, _vp]),
     "uspmv_dist_parts": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "uspmv_dist_parts_ap": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "uspmv_dist_check_reference_ap": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_double, _vp]),
+    "uspmv_dist_create_ap_from_coo": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _i64, C.c_double, C.c_int, C.POINTER(_vp)]),
+    "uspmv_dist_create_ap_from_coo_ex": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _i64, C.c_double, C.c_int, _vp,
+                                                  C.POINTER(_vp)]),
     "uspmv_dist_set_overlap": (C.c_int, [_vp, C.c_int]),
     "uspmv_dist_set_no_pack": (C.c_int, [_vp, C.c_int]),
     "uspmv_dist_spmv": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
@@ -621,6 +629,15 @@ def dist_check_reference(local, wsa, rank, P, dtype=F64):
     return y
 
 
+def dist_check_reference_ap(local, wsa, rank, P, threshold_1):
+    """the same for an ap[dp_sp] object: per row the dp chain over |v| >= threshold_1 plus the sp chain over the others with the value
+    rounded to float (uspmv_dist_check_reference_ap)"""
+    w = np.ascontiguousarray(wsa, np.int32)
+    y = np.zeros(local.n_rows, np.float64)
+    _ck(lib().uspmv_dist_check_reference_ap(local.h, w.ctypes.data_as(_i32p), int(rank), int(P), float(threshold_1), y.ctypes.data_as(_vp)))
+    return y
+
+
 def runtime_versions():
     """(HIP build, HIP runtime, RCCL build, RCCL runtime) version codes of libuspmv.so in this process"""
     v = (C.c_int * 4)()
@@ -635,15 +652,21 @@ class DistNative:
     the capture of an RCCL group crashes in hipStreamEndCapture, so it is off by default here."""
 
     def __init__(self, local_coo, wsa, C_, sigma, rank, P, comm_id=None, comm_rank=None, comm_size=None, dtype=F64, tlc=True,
-                 hostcomm=None, host_exchange=False, exchange=None):
+                 hostcomm=None, host_exchange=False, exchange=None, ap_threshold=None):
         """hostcomm: a HostComm that carries the set-up exchanges (default: the RCCL communicator made from comm_id);
         host_exchange=True additionally stages the per-step halo exchange through it (USPMV_EXCHANGE_HOST: no RCCL communicator,
         P processes may share one GPU).  exchange="rccl" | "host" | "peer" names the per-step exchange instead (host_exchange=True is
         exchange="host"); "peer" (USPMV_EXCHANGE_PEER) stores the halos into the neighbours' IPC windows, over the HostComm between real
         ranks, with no transport at all in loopback (comm_size=1).  Peer ranks in separate processes need HSA_ENABLE_IPC_MODE_LEGACY=0
-        in their environment before the HIP runtime starts."""
+        in their environment before the HIP runtime starts.
+        ap_threshold: a float makes the adaptive-precision ap[dp_sp] object (uspmv_dist_create_ap_from_coo_ex: entries with
+        |v| >= ap_threshold in double, the others in float, vectors double); dtype must then be F64.  scs / A_sp_handle: self.scs is the
+        dp struct, self.scs_sp the sp struct."""
         import torch
         self.rank, self.P = rank, P
+        self.ap_threshold = None if ap_threshold is None else float(ap_threshold)
+        if self.ap_threshold is not None and dtype != F64:
+            raise ValueError("ap_threshold selects the ap[dp_sp] object, whose vectors are double: dtype must be F64")
         wsa = np.ascontiguousarray(wsa, np.int32)
         self._wsa = wsa
         h = _vp()
@@ -663,8 +686,12 @@ class DistNative:
         elif ex == EXCHANGE_PEER:
             self._opt = DistOptions(None, ex)      # no transport: loopback (the library refuses real ranks without one)
             opt = C.byref(self._opt)
-        _ck(lib().uspmv_dist_create_from_coo_ex(idbuf, rank if comm_rank is None else comm_rank, P if comm_size is None else comm_size,
-                                                rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, dtype, int(bool(tlc)), opt, C.byref(h)))
+        cr, cs = rank if comm_rank is None else comm_rank, P if comm_size is None else comm_size
+        if self.ap_threshold is not None:
+            _ck(lib().uspmv_dist_create_ap_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, self.ap_threshold,
+                                                       int(bool(tlc)), opt, C.byref(h)))
+        else:
+            _ck(lib().uspmv_dist_create_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, dtype, int(bool(tlc)), opt, C.byref(h)))
         self.h = h
         e = C.c_int(0)
         _ck(lib().uspmv_dist_exchange(h, C.byref(e)))
@@ -673,6 +700,11 @@ class DistNative:
         _ck(lib().uspmv_dist_parts(h, C.byref(s), C.byref(a), C.byref(hl)))
         self.scs = _BorrowedScs(s, self)
         self._A = a
+        self.scs_sp, self._A_sp = None, None
+        if self.ap_threshold is not None:
+            s2, a2 = _vp(), _vp()
+            _ck(lib().uspmv_dist_parts_ap(h, None, C.byref(s2), None, C.byref(a2), None))
+            self.scs_sp, self._A_sp = _BorrowedScs(s2, self), a2
         self.tdtype = torch.float64 if dtype == F64 else torch.float32
         self.stream = torch.cuda.Stream()
         self._refresh()
@@ -808,7 +840,7 @@ class DistNative:
 
     def close(self):
         if getattr(self, "h", None) and _LIB is not None:
-            self.scs = None
+            self.scs = self.scs_sp = None
             _LIB.uspmv_dist_free(self.h)
             self.h = None
 
@@ -819,10 +851,14 @@ class DistNative:
 class HaloPlan:
     """Result of collect_local_needed_heri on one rank (code/mpi_funcs.hpp:242-415)."""
 
-    def __init__(self, scs, wsa, rank, P):
+    def __init__(self, scs, wsa, rank, P, scs_sp=None):
+        """scs_sp: the sp struct of an ap[dp_sp] pair -- one halo for both (uspmv_halo_discover_ap), both structs' columns rewritten"""
         wsa = np.ascontiguousarray(wsa, np.int32)
         h = _vp()
-        _ck(lib().uspmv_halo_discover(scs.h, _np_ptr(wsa), rank, P, C.byref(h)))
+        if scs_sp is not None:
+            _ck(lib().uspmv_halo_discover_ap(scs.h, scs_sp.h, _np_ptr(wsa), rank, P, C.byref(h)))
+        else:
+            _ck(lib().uspmv_halo_discover(scs.h, _np_ptr(wsa), rank, P, C.byref(h)))
         self.h, self.P, self.rank = h, P, rank
         n = _i64()
         cum, idx, cnt = _i32p(), _i32p(), _i32p()
@@ -841,6 +877,11 @@ class HaloPlan:
         if getattr(self, "h", None) and _LIB is not None:
             _LIB.uspmv_halo_free(self.h)
             self.h = None
+
+
+def halo_discover_ap(scs_dp, scs_sp, wsa, rank, P):
+    """HaloPlan of an ap[dp_sp] pair: the first-seen scan over the dp struct's columns, then the sp struct's (uspmv_halo_discover_ap)"""
+    return HaloPlan(scs_dp, wsa, rank, P, scs_sp=scs_sp)
 
 
 # ---------------------------------------------------------------------------------------- device
@@ -1263,6 +1304,18 @@ def spmv_chunks(A, chunk_ids, x, y, stream=None):
 
 def spmv_tiles(A, tile_ids, x, y, stream=None):
     _ck(lib().uspmv_spmv_tiles(A.h, _dp(tile_ids), tile_ids.numel(), _dp(x), _dp(y), _stream_ptr(stream)))
+    return y
+
+
+def spmv_ap_tiles(A_dp, A_sp, tile_ids, x, y, stream=None):
+    """the tiles in tile_ids (int32 tensor; entries < 0 skipped) of the pair's shared plan (uspmv_spmv_ap_tiles)"""
+    _ck(lib().uspmv_spmv_ap_tiles(A_dp.h, A_sp.h, _dp(tile_ids), tile_ids.numel(), _dp(x), _dp(y), _stream_ptr(stream)))
+    return y
+
+
+def spmv_ap_chunks(A_dp, A_sp, chunk_ids, x, y, stream=None):
+    """the chunks in chunk_ids (int32 tensor; entries < 0 skipped), lane per row (uspmv_spmv_ap_chunks)"""
+    _ck(lib().uspmv_spmv_ap_chunks(A_dp.h, A_sp.h, _dp(chunk_ids), chunk_ids.numel(), _dp(x), _dp(y), _stream_ptr(stream)))
     return y
 
 

@@ -10,18 +10,23 @@ namespace {
 // per tile covering the columns of both): x lines staged once, then the dp chain (8-byte values +
 // 2-byte local indices) and the sp chain (4-byte values + 2-byte local indices), y = dp + sp.
 // 10 and 6 bytes per non-zero instead of 12 and 8; numerics of scs_ap_impl_cpu, bit-exact.
-template <int CT, bool NT>
+// IDS: workgroup b runs tile tile_ids[b] (the interior / boundary lists of the distributed step); an entry < 0 is a conditional entry
+// that was switched off (uspmv_dist's padding re-run) and returns before the barrier, uniformly for the workgroup.
+template <int CT, bool NT, bool IDS = false>
 __global__ void __launch_bounds__(1024) scs_spmv_ap_tlc(const long n_chunks, const int C_rt,
         const int *__restrict__ dp_cp, const int *__restrict__ dp_cl, const int *__restrict__ dp_ci, const double *__restrict__ dp_va,
         const int *__restrict__ sp_cp, const int *__restrict__ sp_cl, const int *__restrict__ sp_ci, const float *__restrict__ sp_va,
         const double *__restrict__ x, double *__restrict__ y, const int *__restrict__ tile_line_ptr,
         const int *__restrict__ tile_lines, const unsigned *__restrict__ dp_c16p, const unsigned short *__restrict__ dp_c16,
-        const unsigned *__restrict__ sp_c16p, const unsigned short *__restrict__ sp_c16, const long x_len, const int xcd_remap) {
+        const unsigned *__restrict__ sp_c16p, const unsigned short *__restrict__ sp_c16, const long x_len, const int xcd_remap,
+        const int *__restrict__ tile_ids = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tlc_smem[];
     double *xs = (double *)tlc_smem;
     typedef double vec_t __attribute__((ext_vector_type(2)));
     const int C = CT > 0 ? CT : C_rt;
-    const unsigned tile = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    const unsigned lbt = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    const unsigned tile = IDS ? (unsigned)tile_ids[lbt] : lbt;
+    if (IDS && (int)tile < 0) return;
     const int lp0 = tile_line_ptr[tile];
     const int nl = tile_line_ptr[tile + 1] - lp0;
     const long row = (long)tile * blockDim.x + threadIdx.x;
@@ -130,6 +135,7 @@ __global__ void scs_spmv_ap_rows(const long n_chunks, const int C_rt, const int 
     const int i = (int)(vrow - vc * C);
     if (vc >= n_chunks) return;
     const long c = IDS ? (long)chunk_ids[vc] : vc;
+    if (IDS && c < 0) return;                // (an entry that was switched off, as in the tile lists)
     const long row = c * C + i;
     double dt = 0.0, st = 0.0;
     const long dcs = dp_cp[c], scs_ = sp_cp[c];
@@ -432,6 +438,28 @@ int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int 
     return USPMV_OK;
 }
 
+int launch_spmv_ap_tiles(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *tile_ids, long n_ids, const double *d_x, double *d_y,
+                         hipStream_t stream) {
+    if (n_ids == 0) return USPMV_OK;
+    const size_t lds = (size_t)dp->tlc.max_lines * 16 * sizeof(double);
+    const int C = (int)dp->C;
+#define APT_IDS_LAUNCH(CTV, NTV)                                                                                      \
+    do {                                                                                                              \
+        auto kfn = scs_spmv_ap_tlc<CTV, NTV, true>;                                                                  \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)n_ids), dim3(dp->tlc.tile_rows), lds, stream, (long)dp->n_chunks, C,   \
+                           dp->chunk_ptrs, dp->chunk_lengths, dp->col_idxs, (const double *)dp->values, sp->chunk_ptrs, \
+                           sp->chunk_lengths, sp->col_idxs, (const float *)sp->values, d_x, d_y, dp->tlc.line_ptr,     \
+                           dp->tlc.lines, dp->tlc.c16_ptrs, dp->tlc.col16, sp->tlc.c16_ptrs, sp->tlc.col16,            \
+                           (long)dp->tlc.x_len, g_tune.xcd_remap, tile_ids);                                          \
+    } while (0)
+    if (g_tune.nontemporal) { if (C == 32) APT_IDS_LAUNCH(32, true); else APT_IDS_LAUNCH(0, true); }
+    else { if (C == 32) APT_IDS_LAUNCH(32, false); else APT_IDS_LAUNCH(0, false); }
+#undef APT_IDS_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
 int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x, const float *d_x_sp, double *d_y,
                    hipStream_t stream) {
     if (!d_x_sp && dp->sw.on && sp->sw.on && dp->sw.tile_ids && dp->sw.n_parts >= 2 && dp->sw.plan_id == sp->sw.plan_id && g_tune.sweep &&
@@ -451,7 +479,7 @@ int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x
                            (long)dp->n_chunks, C, dp->chunk_ptrs, dp->chunk_lengths, dp->col_idxs, (const double *)dp->values, \
                            sp->chunk_ptrs, sp->chunk_lengths, sp->col_idxs, (const float *)sp->values, d_x, d_y,         \
                            dp->tlc.line_ptr, dp->tlc.lines, dp->tlc.c16_ptrs, dp->tlc.col16, sp->tlc.c16_ptrs,           \
-                           sp->tlc.col16, (long)dp->tlc.x_len, g_tune.xcd_remap);                                        \
+                           sp->tlc.col16, (long)dp->tlc.x_len, g_tune.xcd_remap, (const int *)nullptr);                  \
     } while (0)
         if (g_tune.nontemporal) { if (C == 32) APT_LAUNCH(32, true); else APT_LAUNCH(0, true); }
         else { if (C == 32) APT_LAUNCH(32, false); else APT_LAUNCH(0, false); }

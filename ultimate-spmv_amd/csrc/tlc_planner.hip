@@ -584,6 +584,45 @@ bool c16_offsets(const std::vector<int32_t> &cl, int64_t C, std::vector<uint32_t
     return true;
 }
 
+int dmat_optimize_ap(uspmv_dmat *dp, uspmv_dmat *sp, const uspmv_scs *s_dp, const uspmv_scs *s_sp, int max_lines, const TlcPlanOpts &opts,
+                     int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_ap";
+    if (!dp || !sp || !s_dp || !s_sp) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (!uspmv::scs_has_entries(s_dp) || !uspmv::scs_has_entries(s_sp))
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host column indices", who);
+    if (dp->C != s_dp->C || dp->n_chunks != s_dp->n_chunks || dp->dtype != USPMV_F64 || s_dp->dtype != USPMV_F64 ||
+        sp->C != s_sp->C || sp->n_chunks != s_sp->n_chunks || sp->dtype != USPMV_F32 || s_sp->dtype != USPMV_F32 ||
+        dp->C != sp->C || dp->n_chunks != sp->n_chunks)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: handles / host structs do not form a dp+sp pair", who);
+    if (int rc = require_device()) return rc;
+    dp->tlc = {};
+    sp->tlc = {};
+    max_lines = line_budget(max_lines, USPMV_F64, true);
+    uspmv_tlc_plan p;
+    PlanStats st;
+    auto build = [&](int R, PlanStats *o) {
+        const int rc = uspmv_build_tlc_plan(s_dp, s_sp, max_lines, R, &p);
+        *o = stats_of(p);
+        return rc;
+    };
+    // (measure off: one candidate, at the rows per tile of one struct)
+    if (int rc = opts.measure ? plan_at_chosen_rows(measured_tile_rows(dp, sp, max_lines, who), true, build, []() {}, &st)
+                              : build(plan_tile_rows(false), &st))
+        return rc;
+    if (n_tiles) *n_tiles = p.n_tiles;
+    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
+    uspmv_dmat *const parts[3] = {dp, sp, nullptr};
+    if (!opts.measure) {
+        dp->sw = {}; sp->sw = {};
+        return p.valid ? install_host_plan(parts, p, /*elem=*/false, who) : USPMV_OK;
+    }
+    bool swept = false;
+    const uspmv_scs *const ss[2] = {s_dp, s_sp};
+    if (int rc = sweep_takes_over(parts, ss, 2, st, who, &swept)) return rc;
+    if (swept || !p.valid) return USPMV_OK;
+    return install_host_plan(parts, p, /*elem=*/false, who);
+}
+
 int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged) {
     const char *who = "uspmv_dmat_optimize";
     if (!A || !s) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
@@ -789,34 +828,7 @@ int uspmv_dmat_optimize_device(uspmv_dmat_t *A, int max_lines, int64_t *n_tiles,
 
 int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t *s_dp, const uspmv_scs_t *s_sp,
                            int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    const char *who = "uspmv_dmat_optimize_ap";
-    if (!dp || !sp || !s_dp || !s_sp) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
-    if (!uspmv::scs_has_entries(s_dp) || !uspmv::scs_has_entries(s_sp))
-        return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host column indices", who);
-    if (dp->C != s_dp->C || dp->n_chunks != s_dp->n_chunks || dp->dtype != USPMV_F64 || s_dp->dtype != USPMV_F64 ||
-        sp->C != s_sp->C || sp->n_chunks != s_sp->n_chunks || sp->dtype != USPMV_F32 || s_sp->dtype != USPMV_F32 ||
-        dp->C != sp->C || dp->n_chunks != sp->n_chunks)
-        return uspmv::fail(USPMV_ERR_INVALID, "%s: handles / host structs do not form a dp+sp pair", who);
-    if (int rc = require_device()) return rc;
-    dp->tlc = {};
-    sp->tlc = {};
-    max_lines = line_budget(max_lines, USPMV_F64, true);
-    uspmv_tlc_plan p;
-    PlanStats st;
-    auto build = [&](int R, PlanStats *o) {
-        const int rc = uspmv_build_tlc_plan(s_dp, s_sp, max_lines, R, &p);
-        *o = stats_of(p);
-        return rc;
-    };
-    if (int rc = plan_at_chosen_rows(measured_tile_rows(dp, sp, max_lines, who), true, build, []() {}, &st)) return rc;
-    if (n_tiles) *n_tiles = p.n_tiles;
-    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
-    bool swept = false;
-    uspmv_dmat *const parts[3] = {dp, sp, nullptr};
-    const uspmv_scs *const ss[2] = {s_dp, s_sp};
-    if (int rc = sweep_takes_over(parts, ss, 2, st, who, &swept)) return rc;
-    if (swept || !p.valid) return USPMV_OK;
-    return install_host_plan(parts, p, /*elem=*/false, who);
+    return dmat_optimize_ap(dp, sp, s_dp, s_sp, max_lines, TlcPlanOpts{}, n_tiles, n_staged);
 }
 
 int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {

@@ -1362,6 +1362,36 @@ int uspmv_spmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const double *
     return spmv_ap_impl(dp, sp, d_x, nullptr, d_y, stream, "uspmv_spmv_ap");
 }
 
+// the pair checks of spmv_ap_impl for the list forms
+static int check_ap_pair(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const char *who) {
+    if (int rc = check_dmat(dp, who)) return rc;
+    if (int rc = check_dmat(sp, who)) return rc;
+    if (dp->dtype != USPMV_F64 || sp->dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_INVALID, "%s: expects a double and a float struct", who);
+    if (dp->C != sp->C || dp->n_chunks != sp->n_chunks) return uspmv::fail(USPMV_ERR_INVALID, "%s: dp and sp structs must share C and n_chunks", who);
+    return USPMV_OK;
+}
+
+int uspmv_spmv_ap_tiles(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const int32_t *d_tile_ids, int64_t n_ids, const double *d_x,
+                        double *d_y, void *stream) {
+    if (int rc = check_ap_pair(dp, sp, "uspmv_spmv_ap_tiles")) return rc;
+    if (!dp->tlc.on || !sp->tlc.on || dp->tlc.plan_id == 0 || dp->tlc.plan_id != sp->tlc.plan_id)
+        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_ap_tiles: the pair has no shared tile-local-column plan (uspmv_dmat_optimize_ap)");
+    if (n_ids < 0 || n_ids > dp->tlc.n_tiles || (n_ids > 0 && !d_tile_ids) || !d_x || !d_y)
+        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_ap_tiles: bad argument");
+    if ((uintptr_t)d_x % 16) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_ap_tiles: x must be 16-byte aligned");
+    if (int rc = require_device()) return rc;
+    return launch_spmv_ap_tiles(dp, sp, d_tile_ids, (long)n_ids, d_x, d_y, (hipStream_t)stream);
+}
+
+int uspmv_spmv_ap_chunks(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const int32_t *d_chunk_ids, int64_t n_ids, const double *d_x,
+                         double *d_y, void *stream) {
+    if (int rc = check_ap_pair(dp, sp, "uspmv_spmv_ap_chunks")) return rc;
+    if (n_ids < 0 || n_ids > dp->n_chunks || (n_ids > 0 && !d_chunk_ids) || !d_x || !d_y)
+        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_ap_chunks: bad argument");
+    if (int rc = require_device()) return rc;
+    return launch_spmv_ap_chunks(dp, sp, d_chunk_ids, (long)n_ids, d_x, d_y, (hipStream_t)stream);
+}
+
 int uspmv_spmv_ap_generic(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const double *d_x, const float *d_x_sp,
                           double *d_y, void *stream) {
     if (!d_x_sp) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_ap_generic: NULL float x");

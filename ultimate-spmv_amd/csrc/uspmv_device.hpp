@@ -270,6 +270,10 @@ namespace uspmv_dev {
 struct TlcPlanOpts { bool measure = true, elements = true, deal_rows = true, additive = true; const std::vector<int32_t> *new_to_old = nullptr; };
 // uspmv_dmat_optimize with the options spelled out
 int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged);
+// uspmv_dmat_optimize_ap likewise.  measure off: the shared line plan at the rows per tile of ONE struct (256, not the pair's 512) in the
+// caller's row order, and no fall-through to the column-window sweep -- what the distributed object needs of an ap[dp_sp] pair
+int dmat_optimize_ap(uspmv_dmat *dp, uspmv_dmat *sp, const uspmv_scs *s_dp, const uspmv_scs *s_sp, int max_lines, const TlcPlanOpts &opts,
+                     int64_t *n_tiles, int64_t *n_staged);
 
 // One-launch distributed step (csrc/uspmv_dist_api.hip): the tile list of a step is [early | late | conditional | early].  Early entries
 // (interior + padding tiles) run at once.  A late entry (a tile with real halo references) looks ONCE at the exchange counter: if the
@@ -523,6 +527,9 @@ int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st); 
 int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st);                       // sweep_kernels.hip
 int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *d_x,
                           double *d_y, hipStream_t stream);                                                        // ap_kernels.hip
+// the tiles in tile_ids of the pair's shared tile-local-column plan (entries < 0 skipped): scs_spmv_ap_tlc over a tile list
+int launch_spmv_ap_tiles(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *tile_ids, long n_ids, const double *d_x, double *d_y,
+                         hipStream_t stream);                                                                      // ap_kernels.hip
 // the sweep tiles of a plan shared by the parts of a split with an fp16 part (sweep_ap_hp_kernels.hip) and the chunks it leaves over
 int launch_spmv_sweep_ap_hp(const uspmv_dmat *hi, bool mid, const void *x, void *y, hipStream_t st);
 int launch_spmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,

@@ -31,6 +31,10 @@
 // tiles look once at an exchange counter and defer themselves otherwise), uspmv_dist_autotune (times the arrangements collectively and
 // keeps the fastest, self-checked), the block-vector step in two parts over marked chunk-length arrays (uspmv_dist_spmmv, also with
 // the phased block plan built on the rank's matrix), the block exchange staged through the host for real ranks on one GPU.
+//
+// Adaptive precision ap[dp_sp] (uspmv_dist_create_ap_from_coo; the reference refuses ap with MPI, code/utilities.hpp:1445-1451): the object
+// carries the sp part as a second handle.  One halo for the pair, tile classes from both parts, "pad_split" on by default; the single-vector
+// step only.
 #include <rccl/rccl.h>
 
 #include <chrono>
@@ -52,6 +56,11 @@ struct uspmv_dist {
     hipEvent_t ev_main = nullptr, ev_comm = nullptr;
     uspmv_dmat_t *A = nullptr;
     uspmv_scs_t *scs = nullptr;       // owned when built by uspmv_dist_create_from_coo
+    // adaptive precision ap[dp_sp] (uspmv_dist_create_ap_from_coo): A / scs are the dp part, these the sp part; vectors are double, so pack,
+    // exchange, guard, barrier and capture are the one-precision object's -- only part() and the whole-matrix launch differ
+    uspmv_dmat_t *A_sp = nullptr;
+    uspmv_scs_t *scs_sp = nullptr;
+    double ap_threshold = 0.0;
     uspmv_halo_t *halo = nullptr;
     uspmv_comm_plan_t *plan = nullptr;
     int dtype = USPMV_F64;
@@ -217,7 +226,7 @@ int sync_reset(uspmv_dist *D) {
     return USPMV_OK;
 }
 
-inline bool fused_on(const uspmv_dist *D) { return D->fused && D->overlap && D->tiles && D->d_step && D->sa.n_real + D->sa.n_cond > 0; }
+inline bool fused_on(const uspmv_dist *D) { return !D->A_sp && D->fused && D->overlap && D->tiles && D->d_step && D->sa.n_real + D->sa.n_cond > 0; }
 
 inline bool pads_on(const uspmv_dist *D) { return D->pad_split && D->overlap && D->tiles && D->n_pad > 0 && D->pad_col >= 0; }
 
@@ -608,7 +617,15 @@ inline bool eager_only(const uspmv_dist *D) { return D->exchange != USPMV_EXCHAN
 
 int part(uspmv_dist *D, const int32_t *ids, int64_t n, const void *x, void *y, hipStream_t st) {
     if (n == 0) return USPMV_OK;
+    if (D->A_sp)
+        return D->tiles ? uspmv_spmv_ap_tiles(D->A, D->A_sp, ids, n, (const double *)x, (double *)y, st)
+                        : uspmv_spmv_ap_chunks(D->A, D->A_sp, ids, n, (const double *)x, (double *)y, st);
     return D->tiles ? uspmv_spmv_tiles(D->A, ids, n, x, y, st) : uspmv_spmv_chunks(D->A, ids, n, x, y, st);
+}
+
+// the whole matrix in one launch
+int whole(uspmv_dist *D, const void *x, void *y, hipStream_t st) {
+    return D->A_sp ? uspmv_spmv_ap(D->A, D->A_sp, (const double *)x, (double *)y, st) : uspmv_spmv(D->A, x, y, st);
 }
 
 // -ba_synch 1: the barrier the reference issues after every iteration (code/main.cpp:467, :417; default on,
@@ -653,10 +670,10 @@ int step_fused(uspmv_dist *D, void *d_x, void *d_y, hipStream_t main) {
 // JOINED the capture through an event, while the same group on the origin stream, and kernels on joined streams, capture fine
 // (profiles/r03/graph_capture_diag_before_fix.txt / _after_fix.txt; the system's HIP 7.2 / RCCL 2.27 takes either form).  Same DAG, same overlap.
 int step(uspmv_dist *D, void *d_x, void *d_y, hipStream_t main, bool comm_halos) {
-    if (D->P == 1 || !comm_halos) return uspmv_spmv(D->A, d_x, d_y, main);
+    if (D->P == 1 || !comm_halos) return whole(D, d_x, d_y, main);
     if (!D->overlap) {
         if (int rc = exchange_x(D, d_x, main)) return rc;
-        if (int rc = uspmv_spmv(D->A, d_x, d_y, main)) return rc;
+        if (int rc = whole(D, d_x, d_y, main)) return rc;
         return step_barrier(D, main);
     }
     // (not under capture: replayed from a hipGraph the one-launch form measured 0.54 ms against 0.21 ms, profiles/r03/dist_step_ab.txt)
@@ -738,14 +755,15 @@ void uspmv_dist_free(uspmv_dist_t *D) {
     if (D->side_stream) (void)hipStreamDestroy(D->side_stream);
     if (D->comm) (void)ncclCommDestroy(D->comm);
     uspmv_comm_plan_free(D->plan);
-    if (D->owns_setup) { uspmv_dmat_free(D->A); uspmv_halo_free(D->halo); uspmv_scs_free(D->scs); }
+    if (D->owns_setup) { uspmv_dmat_free(D->A); uspmv_dmat_free(D->A_sp); uspmv_halo_free(D->halo); uspmv_scs_free(D->scs); uspmv_scs_free(D->scs_sp); }
     delete D;
 }
 
 // uspmv_dist_create_ex; windows = false leaves the collective window set-up of USPMV_EXCHANGE_PEER to the caller
 static int create_dist(const void *comm_id, int comm_rank, int comm_size, int rank, int P, uspmv_dmat_t *A, const uspmv_halo_t *halo,
                        const int32_t *old_to_new_idx, const int32_t *interior_ids, int64_t n_interior, const int32_t *boundary_ids,
-                       int64_t n_boundary, int ids_are_tiles, const uspmv_dist_options_t *opt, uspmv_dist_t **out, bool windows) {
+                       int64_t n_boundary, int ids_are_tiles, const uspmv_dist_options_t *opt, uspmv_dist_t **out, bool windows,
+                       uspmv_dmat_t *A_sp = nullptr) {
     const int ex = opt ? opt->exchange : USPMV_EXCHANGE_RCCL;
     if (ex != USPMV_EXCHANGE_RCCL && ex != USPMV_EXCHANGE_HOST && ex != USPMV_EXCHANGE_PEER)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: unknown exchange %d", ex);
@@ -784,6 +802,7 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     D->rank = rank; D->P = P; D->comm_rank = comm_rank; D->comm_size = comm_size; D->loopback = comm_size == 1 && P > 1;   // (host: comm_size == P)
     D->exchange = ex;
     D->A = A; D->dtype = A->dtype; D->tiles = ids_are_tiles != 0;
+    D->pad_split = A_sp != nullptr;   // (the sp handle itself is attached by the caller once it owns the set-up: a failure in here frees the caller's)
     D->n_local = halo->n_local; D->n_halo = halo->n_halo; D->n_int = n_interior; D->n_bnd = n_boundary;
     D->recv_counts = halo->recv_counts;
     auto bail = [&](int code) { uspmv_dist_free(D); return code; };
@@ -830,7 +849,7 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     D->vec_len = D->n_local + std::max(D->n_rows_padded - D->n_local, D->n_halo);       // padded_vec_size (code/main.cpp:1406-1412)
     // the single-vector step's exchange plan, here so that no step allocates (a captured one must not); peer stores need none
     if (ex != USPMV_EXCHANGE_PEER) D_HIP(add_block_plan(D, 1, USPMV_ROWWISE, USPMV_BULKVEC));
-    if (P > 1 && !A->alt && A->n_chunks > 0) {
+    if (P > 1 && !A->alt && A->n_chunks > 0 && !A_sp) {
         // the same split for block vectors: per chunk, does it (or its tile) touch a halo column
         std::vector<unsigned char> flag((size_t)A->n_chunks, 0);
         const int64_t cpt = ids_are_tiles ? std::max<int64_t>(A->tlc.tile_rows / A->C, 1) : 1;
@@ -975,6 +994,106 @@ int uspmv_dist_create_from_coo(const void *comm_id, int comm_rank, int comm_size
     return uspmv_dist_create_from_coo_ex(comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, dtype, tlc, nullptr, out);
 }
 
+// uspmv_dist_create_from_coo_ex for an ap[dp_sp] pair.  The tile of a pair is a tile of BOTH parts (same rows), its class the larger of the
+// two parts' classes; the lists, the padding column and the guard are then the one-precision object's.  No one-launch step: no d_step.
+int uspmv_dist_create_ap_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                     const int32_t *wsa, int64_t C, int64_t sigma, double threshold_1, int tlc,
+                                     const uspmv_dist_options_t *opt, uspmv_dist_t **out) {
+    const char *who = "uspmv_dist_create_ap_from_coo";
+    if (!local || !wsa || !out) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad rank / P", who);
+    // (refused HERE, by all ranks alike, before the first collective: see uspmv_dist_create_from_coo_ex)
+    for (int p = 0; p < P; ++p)
+        if (wsa[p + 1] <= wsa[p])
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: block %d of %d owns no rows (work_sharing_arr %d .. %d) -- fewer ranks or another partition", who, p, P,
+                               (int)wsa[p], (int)wsa[p + 1]);
+    if (int rc = uspmv_dev::require_device()) return rc;
+    uspmv_coo_t *coo_dp = nullptr, *coo_sp = nullptr;
+    uspmv_scs_t *s_dp = nullptr, *s_sp = nullptr;
+    uspmv_halo_t *halo = nullptr;
+    uspmv_dmat_t *A_dp = nullptr, *A_sp = nullptr;
+    auto cleanup = [&]() {
+        uspmv_coo_free(coo_dp); uspmv_coo_free(coo_sp); coo_dp = coo_sp = nullptr;
+        uspmv_dmat_free(A_dp); uspmv_dmat_free(A_sp); uspmv_halo_free(halo); uspmv_scs_free(s_dp); uspmv_scs_free(s_sp);
+    };
+    // the single-GPU order (host/uspmv_main.cpp) with the halo discovery between conversion and column permutation, as for one struct
+    int rc = uspmv_partition_precisions(local, threshold_1, &coo_dp, &coo_sp);
+    if (!rc) rc = uspmv_convert_to_scs(coo_dp, C, sigma, USPMV_F64, nullptr, &s_dp);
+    const int32_t *o2n = nullptr;
+    if (!rc) rc = uspmv_scs_arrays(s_dp, nullptr, nullptr, nullptr, nullptr, &o2n, nullptr);
+    if (!rc) rc = uspmv_convert_to_scs(coo_sp, C, sigma, USPMV_F32, o2n, &s_sp);
+    uspmv_coo_free(coo_dp); uspmv_coo_free(coo_sp); coo_dp = coo_sp = nullptr;
+    if (!rc) rc = uspmv_halo_discover_ap(s_dp, s_sp, wsa, rank, P, &halo);
+    if (!rc) rc = uspmv_permute_scs_cols(s_dp, o2n);
+    if (!rc) rc = uspmv_permute_scs_cols(s_sp, o2n);
+    if (!rc) rc = uspmv_dmat_upload(s_dp, &A_dp);
+    if (!rc) rc = uspmv_dmat_upload(s_sp, &A_sp);
+    int64_t n_tiles = 0, n_staged = 0;
+    if (!rc && tlc) {
+        // (256-row tiles, not the pair's single-GPU 512: a whole sigma window per tile leaves no interior tile -- see uspmv_dist_create_from_coo_ex)
+        const uspmv_dev::TlcPlanOpts as_is{/*measure=*/false, /*elements=*/false, /*deal_rows=*/false, /*additive=*/false};
+        rc = uspmv_dev::dmat_optimize_ap(A_dp, A_sp, s_dp, s_sp, 0, as_is, &n_tiles, &n_staged);
+    }
+    const int64_t n_local = wsa[rank + 1] - wsa[rank];
+    std::vector<uint8_t> cls, cls_sp;
+    int32_t pad_col = -1, pad_sp = -1;
+    if (!rc) rc = uspmv_scs_classify_chunks(s_dp, n_local, &cls, &pad_col);
+    if (!rc) rc = uspmv_scs_classify_chunks(s_sp, n_local, &cls_sp, &pad_sp);
+    if (rc) { cleanup(); return rc; }
+    // one padding column for both parts (both pad with global column 0, one halo numbering); if they ever disagree, no chunk is padding-only
+    const bool pad_clash = pad_col >= 0 && pad_sp >= 0 && pad_col != pad_sp;
+    if (pad_col < 0) pad_col = pad_sp;
+    for (size_t c = 0; c < cls.size(); ++c) {
+        cls[c] = std::max(cls[c], cls_sp[c]);
+        if (pad_clash && cls[c] == 1) cls[c] = 2;
+    }
+    if (pad_clash) pad_col = -1;
+    const int tile_rows = A_dp->tlc.on && A_dp->tlc.plan_id != 0 ? A_dp->tlc.tile_rows : 0;
+    const bool use_tiles = tile_rows > 0 && n_staged > 0;
+    std::vector<int32_t> ids_int, ids_bnd, ids_pad, ids_real;
+    if (use_tiles) {
+        const int64_t cpt = std::max<int64_t>(tile_rows / C, 1);
+        std::vector<uint8_t> tc((size_t)n_tiles, 0);
+        for (int64_t c = 0; c < (int64_t)cls.size(); ++c) tc[(size_t)(c / cpt)] = std::max(tc[(size_t)(c / cpt)], cls[(size_t)c]);
+        for (int64_t t = 0; t < n_tiles; ++t) {
+            if (tc[(size_t)t] == 0) ids_int.push_back((int32_t)t);
+            else { ids_bnd.push_back((int32_t)t); (tc[(size_t)t] == 1 ? ids_pad : ids_real).push_back((int32_t)t); }
+        }
+    } else {   // chunk lists: a chunk is boundary when it is in either part
+        if (A_dp->tlc.on) { A_dp->tlc = {}; A_sp->tlc = {}; }   // (a plan that stages nothing: the whole-matrix launch takes the lane-per-row kernel too)
+        for (int64_t c = 0; c < (int64_t)cls.size(); ++c) (cls[(size_t)c] ? ids_bnd : ids_int).push_back((int32_t)c);
+    }
+    uspmv_dist_t *D = nullptr;
+    rc = create_dist(comm_id, comm_rank, comm_size, rank, P, A_dp, halo, o2n, ids_int.data(), (int64_t)ids_int.size(), ids_bnd.data(),
+                     (int64_t)ids_bnd.size(), use_tiles ? 1 : 0, opt, &D, false, A_sp);
+    if (rc) { cleanup(); return rc; }
+    const bool pads = use_tiles && P > 1 && pad_col >= 0 && !ids_pad.empty();
+    if (pads) {
+        std::vector<int32_t> early(ids_int.size() + ids_pad.size()), late(ids_real.size() + ids_pad.size(), -1);
+        std::merge(ids_int.begin(), ids_int.end(), ids_pad.begin(), ids_pad.end(), early.begin());
+        std::copy(ids_real.begin(), ids_real.end(), late.begin());
+        hipError_t e = D->d_pad.upload(ids_pad.data(), 4 * ids_pad.size());
+        if (e == hipSuccess) e = D->d_early.upload(early.data(), 4 * early.size());
+        if (e == hipSuccess) e = D->d_late.upload(late.data(), 4 * late.size());
+        if (e != hipSuccess) {
+            uspmv_dist_free(D); cleanup();
+            return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
+        }
+        D->n_pad = (int64_t)ids_pad.size(); D->n_bnd_real = (int64_t)ids_real.size(); D->pad_col = pad_col;
+    }
+    // (the collective window set-up after every step above that could fail on this rank alone)
+    if (D->exchange == USPMV_EXCHANGE_PEER && P > 1)
+        if ((rc = peer_setup(D, 1))) { uspmv_dist_free(D); cleanup(); return rc; }
+    D->owns_setup = true; D->scs = s_dp; D->scs_sp = s_sp; D->halo = halo; D->A_sp = A_sp; D->ap_threshold = threshold_1;
+    *out = D;
+    return USPMV_OK;
+}
+
+int uspmv_dist_create_ap_from_coo(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                  const int32_t *wsa, int64_t C, int64_t sigma, double threshold_1, int tlc, uspmv_dist_t **out) {
+    return uspmv_dist_create_ap_from_coo_ex(comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, threshold_1, tlc, nullptr, out);
+}
+
 int uspmv_dist_comm_plan(const uspmv_dist_t *D, int64_t *n_send, const int64_t **send_off, const int32_t **send_idxs, const int64_t **recv_off) {
     if (!D || !D->plan) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_comm_plan: NULL argument");
     return uspmv_comm_plan_meta(D->plan, n_send, send_off, send_idxs, recv_off);
@@ -983,6 +1102,9 @@ int uspmv_dist_comm_plan(const uspmv_dist_t *D, int64_t *n_send, const int64_t *
 int uspmv_dist_set_option(uspmv_dist_t *D, const char *key, int value) {
     if (!D || !key) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_set_option: NULL argument");
     const std::string k(key);
+    if (D->A_sp && (((k == "fused_step" || k == "autotune_all") && value != 0) || (k == "block_plan" && value > 0)))
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_set_option: '%s' is not available on an adaptive-precision (ap[dp_sp]) object: its step has "
+                           "the overlap, plain and pad_split forms, and no block vectors", key);
     if (k == "overlap") { if ((value != 0) != D->overlap) drop_graph(D); D->overlap = value != 0; }
     else if (k == "no_pack") { if ((value != 0) != D->no_pack) drop_graph(D); D->no_pack = value != 0; }
     else if (k == "ba_synch") { if ((value != 0) != D->ba_synch) drop_graph(D); D->ba_synch = value != 0; }
@@ -1064,6 +1186,17 @@ int uspmv_dist_parts(const uspmv_dist_t *D, const uspmv_scs_t **scs, const uspmv
     return USPMV_OK;
 }
 
+int uspmv_dist_parts_ap(const uspmv_dist_t *D, const uspmv_scs_t **scs_dp, const uspmv_scs_t **scs_sp, const uspmv_dmat_t **A_dp,
+                        const uspmv_dmat_t **A_sp, const uspmv_halo_t **halo) {
+    if (!D) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap: NULL argument");
+    if (scs_dp) *scs_dp = D->scs;
+    if (scs_sp) *scs_sp = D->scs_sp;
+    if (A_dp) *A_dp = D->A;
+    if (A_sp) *A_sp = D->A_sp;
+    if (halo) *halo = D->halo;
+    return USPMV_OK;
+}
+
 int uspmv_dist_set_overlap(uspmv_dist_t *D, int overlap) {
     if (!D) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_set_overlap: NULL argument");
     if ((overlap != 0) != D->overlap) drop_graph(D);
@@ -1124,6 +1257,8 @@ int uspmv_dist_autotune(uspmv_dist_t *D, void *d_x, void *d_y, int use_graph, co
     hipStream_t st = (hipStream_t)stream;
     auto apply = [&](int f) -> int {
         if (int rc = uspmv_dist_set_option(D, "overlap", f == USPMV_STEP_PLAIN ? 0 : 1)) return rc;
+        // (an ap object times overlap | plain only, and its overlap form keeps the "pad_split" it has -- 1 unless the caller changed it)
+        if (D->A_sp) return USPMV_OK;
         if (int rc = uspmv_dist_set_option(D, "pad_split", f == USPMV_STEP_PAD || f == USPMV_STEP_FUSED ? 1 : 0)) return rc;
         return uspmv_dist_set_option(D, "fused_step", f == USPMV_STEP_FUSED ? 1 : 0);
     };
@@ -1251,7 +1386,9 @@ int uspmv_dist_check(uspmv_dist_t *D, const uspmv_coo_t *local, const int32_t *w
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(hy.data(), d_y, (size_t)D->n_rows_padded * vsz, hipMemcpyDeviceToHost));
     std::vector<char> ref((size_t)std::max<int64_t>(nl, 1) * vsz);
-    if (int rc = uspmv::dist_reference_rows(local, wsa, D->P, D->rank, D->loopback, D->dtype, ref.data())) return rc;
+    if (int rc = D->A_sp ? uspmv::dist_reference_rows_ap(local, wsa, D->P, D->rank, D->loopback, D->ap_threshold, (double *)ref.data())
+                         : uspmv::dist_reference_rows(local, wsa, D->P, D->rank, D->loopback, D->dtype, ref.data()))
+        return rc;
     int64_t bad = 0;
     double sum = 0.0;
     for (int64_t i = 0; i < nl; ++i) {   // copy_back_result: y_orig[i] = y[old_to_new[i]] (code/utilities.hpp:3862)
@@ -1266,6 +1403,7 @@ int uspmv_dist_check(uspmv_dist_t *D, const uspmv_coo_t *local, const int32_t *w
 
 int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
     if (!D || !d_X || !d_Y || b < 1) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: bad argument");
+    if (D->A_sp) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: not available on an adaptive-precision (ap[dp_sp]) object (single vectors only)");
     if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown layout %d", layout);
     if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown mode %d", mode);
     if (layout == USPMV_ROWWISE && mode != USPMV_BULKVEC)

@@ -54,6 +54,21 @@ int dist_reference_rows(const uspmv_coo *local, const int32_t *wsa, int P, int r
     return USPMV_OK;
 }
 
+// ap[dp_sp]: the block split as the object's set-up splits it (the sp part holds (double)(float)v), one chain per part, y = dp + sp
+int dist_reference_rows_ap(const uspmv_coo *local, const int32_t *wsa, int P, int rank, bool loopback, double threshold_1, double *y_ref) {
+    if (!local || !wsa || !y_ref) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: NULL argument");
+    for (int64_t k = 0; k < local->nnz; ++k)
+        if (local->I[(size_t)k] < 0 || local->I[(size_t)k] >= local->n_rows) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: row id outside the block");
+    uspmv_coo *dp = nullptr, *sp = nullptr;
+    if (int rc = uspmv_partition_precisions(local, threshold_1, &dp, &sp)) return rc;
+    std::vector<double> ys((size_t)std::max<int64_t>(local->n_rows, 1));
+    rows<double>(dp, wsa, P, rank, loopback, y_ref);
+    rows<double>(sp, wsa, P, rank, loopback, ys.data());
+    for (int64_t i = 0; i < local->n_rows; ++i) y_ref[i] += ys[(size_t)i];
+    uspmv_coo_free(dp); uspmv_coo_free(sp);
+    return USPMV_OK;
+}
+
 }  // namespace uspmv
 
 // The rows of the check on the host alone (no GPU): y_ref[i] = the entry-ordered FMA chain of local row i over
@@ -63,4 +78,10 @@ extern "C" int uspmv_dist_check_reference(const uspmv_coo_t *local, const int32_
     if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_check_reference: bad rank / P");
     if (dtype != USPMV_F64 && dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_check_reference: unknown dtype %d", dtype);
     return uspmv::dist_reference_rows(local, wsa, P, rank, /*loopback=*/false, dtype, y_ref);
+}
+
+// ... and for an ap[dp_sp] object: the dp chain over |v| >= threshold_1, the sp chain over the others with (double)(float)v, y = dp + sp
+extern "C" int uspmv_dist_check_reference_ap(const uspmv_coo_t *local, const int32_t *wsa, int rank, int P, double threshold_1, double *y_ref) {
+    if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_check_reference_ap: bad rank / P");
+    return uspmv::dist_reference_rows_ap(local, wsa, P, rank, /*loopback=*/false, threshold_1, y_ref);
 }

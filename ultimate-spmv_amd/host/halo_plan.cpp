@@ -20,6 +20,74 @@
 
 #include "uspmv_internal.hpp"
 
+// collect_local_needed_heri over the col_idxs of n structs taken as ONE array, struct after struct in storage order: one first-seen scan,
+// one numbering, every struct's columns rewritten against it (n = 1: uspmv_halo_discover; n = 2: the dp and sp parts of an ap[dp_sp] pair)
+static int discover_halo(uspmv_scs_t *const parts[], int n, const int32_t *wsa, int rank, int P, uspmv_halo_t **out, const char *who) {
+    const int32_t lo = wsa[rank], hi = wsa[rank + 1];
+    int64_t n_cols = wsa[P];
+    for (int q = 0; q < n; ++q) n_cols = std::max<int64_t>(n_cols, parts[q]->n_cols);
+
+    std::vector<int32_t> slot((size_t)n_cols, -1);  // first-seen position inside the owner's list
+    std::vector<std::vector<int32_t>> lists((size_t)P);
+    auto owner_of = [&](int32_t col) {
+        return (int)(std::upper_bound(wsa, wsa + P + 1, col) - wsa) - 1;
+    };
+    for (int q = 0; q < n; ++q) {
+        const int64_t n_el = parts[q]->n_elements;
+        const int32_t *ci = parts[q]->col_idxs.data();
+        for (int64_t k = 0; k < n_el; ++k) {
+            int32_t col = ci[k];
+            if (col < 0 || col >= n_cols) return uspmv::fail(USPMV_ERR_INVALID, "%s: column %d outside the global matrix", who, col);
+            if (col >= lo && col < hi) continue;
+            if (slot[(size_t)col] >= 0) continue;
+            int p = owner_of(col);
+            if (p < 0 || p >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: column %d has no owner", who, col);
+            slot[(size_t)col] = (int32_t)lists[(size_t)p].size();
+            lists[(size_t)p].push_back(col - wsa[p]);
+        }
+    }
+    auto *h = new uspmv_halo;
+    h->P = P; h->rank = rank; h->n_local = hi - lo;
+    std::vector<int64_t> base((size_t)P + 1, 0);
+    for (int p = 0; p < P; ++p) base[(size_t)p + 1] = base[(size_t)p] + (int64_t)lists[(size_t)p].size();
+    h->n_halo = base[(size_t)P];
+    if (h->n_local + h->n_halo > INT32_MAX) {
+        delete h;
+        return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: local + halo columns exceed int32", who);
+    }
+    const int64_t n_local = h->n_local;
+    for (int q = 0; q < n; ++q) {
+        const int64_t n_el = parts[q]->n_elements;
+        int32_t *ci = parts[q]->col_idxs.data();
+#pragma omp parallel for schedule(static)
+        for (int64_t k = 0; k < n_el; ++k) {
+            int32_t col = ci[k];
+            if (col >= lo && col < hi) { ci[k] = col - lo; continue; }
+            int p = owner_of(col);
+            ci[k] = (int32_t)(n_local + base[(size_t)p] + slot[(size_t)col]);
+        }
+    }
+    h->recv_counts.resize((size_t)P);
+    for (int p = 0; p < P; ++p) {
+        h->recv_counts[(size_t)p] = (int32_t)lists[(size_t)p].size();
+        h->recv_idxs.insert(h->recv_idxs.end(), lists[(size_t)p].begin(), lists[(size_t)p].end());
+    }
+    // recv_counts_cumsum assembled exactly as code/mpi_funcs.hpp:403-414 does (entries below
+    // `rank` from the lower-owner cumsum, entries rank..P from lower total + higher-owner cumsum)
+    h->recv_counts_cumsum.assign((size_t)P + 1, 0);
+    std::vector<int64_t> lhs((size_t)P + 1, 0), rhs((size_t)P + 1, 0);
+    for (int p = 1; p <= P; ++p) {
+        lhs[(size_t)p] = lhs[(size_t)p - 1] + ((p - 1) < rank ? h->recv_counts[(size_t)p - 1] : 0);
+        rhs[(size_t)p] = rhs[(size_t)p - 1] + ((p - 1) > rank ? h->recv_counts[(size_t)p - 1] : 0);
+    }
+    for (int p = 0; p < rank; ++p) h->recv_counts_cumsum[(size_t)p] = (int32_t)lhs[(size_t)p];
+    int limit = (P == 1) ? P - (rank + 1) : P - rank + 1;
+    for (int i = 0; i < limit; ++i)
+        h->recv_counts_cumsum[(size_t)(rank + i)] = (int32_t)(lhs[(size_t)rank] + rhs[(size_t)(rank + i)]);
+    *out = h;
+    return USPMV_OK;
+}
+
 extern "C" {
 
 int uspmv_seg_work_sharing_arr(const uspmv_coo_t *t, int seg_method, int P, int32_t *wsa) {
@@ -114,63 +182,21 @@ int uspmv_halo_discover(uspmv_scs_t *s, const int32_t *wsa, int rank, int P, usp
     if (!s || !wsa || !out || P < 1 || rank < 0 || rank >= P)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_halo_discover: bad argument");
     if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_halo_discover: layout-only struct (uspmv_convert_to_scs_device)");
-    const int32_t lo = wsa[rank], hi = wsa[rank + 1];
-    const int64_t n_cols = std::max<int64_t>(s->n_cols, wsa[P]);
-    const int64_t n_el = s->n_elements;
-    int32_t *ci = s->col_idxs.data();
+    uspmv_scs_t *const parts[1] = {s};
+    return discover_halo(parts, 1, wsa, rank, P, out, "uspmv_halo_discover");
+}
 
-    std::vector<int32_t> slot((size_t)n_cols, -1);  // first-seen position inside the owner's list
-    std::vector<std::vector<int32_t>> lists((size_t)P);
-    auto owner_of = [&](int32_t col) {
-        return (int)(std::upper_bound(wsa, wsa + P + 1, col) - wsa) - 1;
-    };
-    for (int64_t k = 0; k < n_el; ++k) {
-        int32_t col = ci[k];
-        if (col < 0 || col >= n_cols)
-            return uspmv::fail(USPMV_ERR_INVALID, "uspmv_halo_discover: column %d outside the global matrix", col);
-        if (col >= lo && col < hi) continue;
-        if (slot[(size_t)col] >= 0) continue;
-        int p = owner_of(col);
-        if (p < 0 || p >= P) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_halo_discover: column %d has no owner", col);
-        slot[(size_t)col] = (int32_t)lists[(size_t)p].size();
-        lists[(size_t)p].push_back(col - wsa[p]);
-    }
-    auto *h = new uspmv_halo;
-    h->P = P; h->rank = rank; h->n_local = hi - lo;
-    std::vector<int64_t> base((size_t)P + 1, 0);
-    for (int p = 0; p < P; ++p) base[(size_t)p + 1] = base[(size_t)p] + (int64_t)lists[(size_t)p].size();
-    h->n_halo = base[(size_t)P];
-    if (h->n_local + h->n_halo > INT32_MAX) {
-        delete h;
-        return uspmv::fail(USPMV_ERR_OVERFLOW, "uspmv_halo_discover: local + halo columns exceed int32");
-    }
-    const int64_t n_local = h->n_local;
-#pragma omp parallel for schedule(static)
-    for (int64_t k = 0; k < n_el; ++k) {
-        int32_t col = ci[k];
-        if (col >= lo && col < hi) { ci[k] = col - lo; continue; }
-        int p = owner_of(col);
-        ci[k] = (int32_t)(n_local + base[(size_t)p] + slot[(size_t)col]);
-    }
-    h->recv_counts.resize((size_t)P);
-    for (int p = 0; p < P; ++p) {
-        h->recv_counts[(size_t)p] = (int32_t)lists[(size_t)p].size();
-        h->recv_idxs.insert(h->recv_idxs.end(), lists[(size_t)p].begin(), lists[(size_t)p].end());
-    }
-    // recv_counts_cumsum assembled exactly as code/mpi_funcs.hpp:403-414 does (entries below
-    // `rank` from the lower-owner cumsum, entries rank..P from lower total + higher-owner cumsum)
-    h->recv_counts_cumsum.assign((size_t)P + 1, 0);
-    std::vector<int64_t> lhs((size_t)P + 1, 0), rhs((size_t)P + 1, 0);
-    for (int p = 1; p <= P; ++p) {
-        lhs[(size_t)p] = lhs[(size_t)p - 1] + ((p - 1) < rank ? h->recv_counts[(size_t)p - 1] : 0);
-        rhs[(size_t)p] = rhs[(size_t)p - 1] + ((p - 1) > rank ? h->recv_counts[(size_t)p - 1] : 0);
-    }
-    for (int p = 0; p < rank; ++p) h->recv_counts_cumsum[(size_t)p] = (int32_t)lhs[(size_t)p];
-    int limit = (P == 1) ? P - (rank + 1) : P - rank + 1;
-    for (int i = 0; i < limit; ++i)
-        h->recv_counts_cumsum[(size_t)(rank + i)] = (int32_t)(lhs[(size_t)rank] + rhs[(size_t)(rank + i)]);
-    *out = h;
-    return USPMV_OK;
+int uspmv_halo_discover_ap(uspmv_scs_t *dp, uspmv_scs_t *sp, const int32_t *wsa, int rank, int P, uspmv_halo_t **out) {
+    const char *who = "uspmv_halo_discover_ap";
+    if (!dp || !sp || !wsa || !out || P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    if (!uspmv::scs_has_entries(dp) || !uspmv::scs_has_entries(sp))
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct (uspmv_convert_to_scs_device)", who);
+    if (dp == sp) return uspmv::fail(USPMV_ERR_INVALID, "%s: the two parts are one struct", who);
+    // (the permutations cannot be compared: a struct converted with a fixed permutation records the identity, code/utilities.hpp:1911-1928)
+    if (dp->C != sp->C || dp->n_chunks != sp->n_chunks || dp->n_rows != sp->n_rows)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts must share C, n_chunks and the row layout (convert the sp part with the dp part's permutation)", who);
+    uspmv_scs_t *const parts[2] = {dp, sp};
+    return discover_halo(parts, 2, wsa, rank, P, out, who);
 }
 
 int uspmv_halo_meta(const uspmv_halo_t *h, int64_t *n_halo, const int32_t **recv_counts_cumsum,

@@ -1,6 +1,6 @@
 // Multi-rank path of the `uspmv` harness: one process per GPU, halo exchange on RCCL (xGMI).
 //
-// Replaces, for the SINGLEVEC colwise one-precision path, the reference's MPI flow:
+// Replaces, for the SINGLEVEC colwise one-precision path (and, beyond the reference, for -ap[dp_sp] on a single vector), the reference's MPI flow:
 //   init_local_structs            code/main.cpp:1075-1334   (partition, convert, halo discovery)
 //   collect_comm_info             code/mpi_funcs.hpp:1061-1124 (who sends what to whom)
 //   init/finalize_halo_exchange   code/classes_structs.hpp:857-995 (per-iteration exchange)
@@ -214,7 +214,8 @@ int uspmv_run_distributed(const DistConfig &c) {
     // -equilibrate 1: every rank scales ITS block (rows, then columns of the row-scaled block), as the reference does after the
     // segmentation (code/main.cpp:1117-1125 on local_mtx)
     if (c.equilibrate) CK(uspmv_coo_equilibrate(local));
-    CK(uspmv_dist_create_from_coo_ex(host_exchange || peer_exchange ? nullptr : id, comm_rank, comm_size, rank, P, local, wsa.data(), c.C, c.sigma, c.sp ? USPMV_F32 : USPMV_F64, c.tlc ? 1 : 0, &opt, &D));
+    if (c.ap) CK(uspmv_dist_create_ap_from_coo_ex(host_exchange || peer_exchange ? nullptr : id, comm_rank, comm_size, rank, P, local, wsa.data(), c.C, c.sigma, c.ap_threshold_1, c.tlc ? 1 : 0, &opt, &D));
+    else CK(uspmv_dist_create_from_coo_ex(host_exchange || peer_exchange ? nullptr : id, comm_rank, comm_size, rank, P, local, wsa.data(), c.C, c.sigma, c.sp ? USPMV_F32 : USPMV_F64, c.tlc ? 1 : 0, &opt, &D));
     // (the block's COO stays until the end: -rand_x reads its values, -step_form auto and -check_y run the self-check against it)
     stage("step object created (communicator up)");
     hipStream_t st = nullptr;
@@ -230,10 +231,11 @@ int uspmv_run_distributed(const DistConfig &c) {
     int64_t meta[12];
     CK(uspmv_dist_info(D, meta));
     const int64_t n_local = meta[0], n_halo = meta[1], vec_len = meta[2], n_send = meta[3];
-    const uspmv_scs_t *scs = nullptr;
-    CK(uspmv_dist_parts(D, &scs, nullptr, nullptr));
-    int64_t sm[8];
+    const uspmv_scs_t *scs = nullptr, *scs_sp = nullptr;   // (ap[dp_sp]: scs is the dp struct, which carries the row permutation)
+    CK(uspmv_dist_parts_ap(D, &scs, &scs_sp, nullptr, nullptr, nullptr));
+    int64_t sm[8], sm_sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     CK(uspmv_scs_meta(scs, sm));
+    if (scs_sp) CK(uspmv_scs_meta(scs_sp, sm_sp));
     const int64_t n_pad = sm[4], n_chunks = sm[5], n_el = sm[6];
     const int32_t *o2n, *n2o;
     CK(uspmv_scs_arrays(scs, nullptr, nullptr, nullptr, nullptr, &o2n, &n2o));
@@ -346,6 +348,9 @@ int uspmv_run_distributed(const DistConfig &c) {
     if (!(P > 1 && comm_halos && b == 1) || legacy_knobs) form = c.no_overlap ? "plain" : "overlap";
     auto apply_form = [&](const std::string &f) -> int {
         if (int rc = uspmv_dist_set_option(D, "overlap", f == "plain" ? 0 : 1)) return rc;
+        // (an ap[dp_sp] object has no one-launch step, and its "overlap" is the object's default: with the padding tiles in front of the
+        //  exchange; -step_form pad asks for that by name, USPMV_PAD_SPLIT=0 switches it off)
+        if (c.ap) return f == "pad" ? uspmv_dist_set_option(D, "pad_split", 1) : USPMV_OK;
         if (int rc = uspmv_dist_set_option(D, "pad_split", f == "pad" || f == "fused" ? 1 : 0)) return rc;
         return uspmv_dist_set_option(D, "fused_step", f == "fused" ? 1 : 0);
     };
@@ -452,7 +457,7 @@ int uspmv_run_distributed(const DistConfig &c) {
     CK(uspmv_dist_allgather_i64(D, n_send, sends.data(), st));
     CK(uspmv_dist_info(D, meta));
     // every rank's row of the report (the reference gathers its per-rank numbers on rank 0 too, code/main.cpp:809-1062)
-    const double my_bytes = n_el * (vsz + 4.0) + 8.0 * n_chunks + (double)vsz * b * (n_local + n_halo) + (double)vsz * b * n_pad;
+    const double my_bytes = n_el * (vsz + 4.0) + (double)sm_sp[6] * (4.0 + 4.0) + 8.0 * n_chunks * (c.ap ? 2 : 1) + (double)vsz * b * (n_local + n_halo) + (double)vsz * b * n_pad;
     const int n_rep = meta[8] ? 1 : comm_size;
     const char *rank_keys[9] = {"n_local", "n_halo", "n_send", "interior", "boundary", "n_elements", "nnz", "algorithmic_bytes", "local_kernel_ns"};
     const int64_t rank_vals[9] = {n_local, n_halo, n_send, meta[4], meta[5], n_el, sm[7], (int64_t)my_bytes, (int64_t)(kernel_ms * 1e6)};
@@ -464,10 +469,12 @@ int uspmv_run_distributed(const DistConfig &c) {
     CK(uspmv_runtime_versions(ver));
     const char *protocol = c.bench_steps > 0 ? "fixed steps between barriers" : "reference bench loop (doubling batches)";
     if (comm_rank == 0) {
-        const double bytes = n_el * (vsz + 4.0) + 8.0 * n_chunks + (double)vsz * b * (n_local + n_halo) + (double)vsz * b * n_pad;  // this rank's share
+        const double bytes = my_bytes;  // this rank's share
         std::ofstream f("spmv_bench.txt", std::ios::app);
+        char ap_note[64] = "";                                 // (as the single-rank report: the threshold next to the data type)
+        if (c.ap) snprintf(ap_note, sizeof ap_note, ", threshold: %.2f", c.ap_threshold_1);
         f << c.matrix_name << " with " << P << " RCCL ranks (one per GPU), halo exchange " << (c.comm_halos ? "on" : "off") << std::endl;
-        f << "kernel: scs, block_vec_size: " << b << ", C: " << c.C << " sigma: " << c.sigma << ", data_type: " << (c.sp ? "float" : "double") << ", revisions: " << n_iter
+        f << "kernel: scs, block_vec_size: " << b << ", C: " << c.C << " sigma: " << c.sigma << ", data_type: " << (c.ap ? "ap[dp_sp]" : c.sp ? "float" : "double") << ap_note << ", revisions: " << n_iter
           << ", seg_method: " << (c.seg_metis ? "seg-metis" : c.seg_nnz ? "seg-nnz" : "seg-rows") << ", MPI_mode: " << (b == 1 || c.vec_mode == USPMV_SINGLEVEC ? "singlevec" : c.vec_mode == USPMV_MULTIVEC ? "multivec" : "bulkvec")
           << ", ba_synch: " << (c.ba_synch && c.comm_halos ? 1 : 0) << std::endl << std::endl;
         char buf[256];
@@ -510,13 +517,13 @@ int uspmv_run_distributed(const DistConfig &c) {
             char js[3072];
             snprintf(js, sizeof js,
                      "{\"gflops\": %.4f, \"ms_per_step\": %.6f, \"steps\": %d, \"warmup\": %d, \"runtime_s\": %.6f, \"ranks\": %d, \"loopback\": %s, "
-                     "\"exchange\": \"%s\", \"n_rows\": %ld, \"nnz\": %ld, \"protocol\": \"%s\", \"ba_synch\": %d, \"graph_replay\": %s, \"graph_launches\": %ld, "
+                     "\"exchange\": \"%s\", \"data_type\": \"%s\", \"ap_threshold_1\": %.17g, \"n_rows\": %ld, \"nnz\": %ld, \"protocol\": \"%s\", \"ba_synch\": %d, \"graph_replay\": %s, \"graph_launches\": %ld, "
                      "\"eager_steps\": %ld, \"overlap\": %s, \"step_form\": \"%s\", \"step_form_candidates_ms\": {%s}, \"other_ba_synch_ms_per_step\": %.6f, \"y_checked\": %s, \"y_mismatches\": %ld, \"y_checksum_rank0\": %.17g, "
                      "\"rank0\": {\"n_local\": %ld, \"n_halo\": %ld, \"n_send\": %ld, \"interior\": %ld, \"boundary\": %ld, \"tiles\": %s, \"n_elements\": %ld, "
                      "\"n_chunks\": %ld, \"n_rows_padded\": %ld, \"algorithmic_bytes\": %.0f, \"local_kernel_ms\": %.6f}, "
                      "\"rccl_nranks\": %d, \"versions\": {\"hip_build\": %d, \"hip_runtime\": %d, \"rccl_build\": %d, \"rccl_runtime\": %d}",
-                     perf, runtime / n_iter * 1e3, n_iter, warm, runtime, P, meta[8] ? "true" : "false", host_exchange ? "host" : peer_exchange ? "peer" : "rccl", (long)n_rows_g, (long)nnz_g,
-                     protocol, c.ba_synch && c.comm_halos ? 1 : 0, meta[9] ? "true" : "false", (long)meta[10], (long)meta[11], form == "plain" ? "false" : "true", form.c_str(), form_report.c_str(), runtime_other / n_iter * 1e3,
+                     perf, runtime / n_iter * 1e3, n_iter, warm, runtime, P, meta[8] ? "true" : "false", host_exchange ? "host" : peer_exchange ? "peer" : "rccl", c.ap ? "ap[dp_sp]" : c.sp ? "float" : "double", c.ap ? c.ap_threshold_1 : 0.0,
+                     (long)n_rows_g, (long)nnz_g, protocol, c.ba_synch && c.comm_halos ? 1 : 0, meta[9] ? "true" : "false", (long)meta[10], (long)meta[11], form == "plain" ? "false" : "true", form.c_str(), form_report.c_str(), runtime_other / n_iter * 1e3,
                      mism_total < 0 ? "null" : mism_total == 0 ? "true" : "false", (long)mism_total, checksum, (long)n_local, (long)n_halo, (long)n_send,
                      (long)meta[4], (long)meta[5], meta[6] ? "true" : "false", (long)n_el, (long)n_chunks, (long)n_pad, bytes, kernel_ms,
                      rccl_nranks, ver[0], ver[1], ver[2], ver[3]);

@@ -23,6 +23,8 @@ struct DistConfig {
                                                // (rank 0 extracts, MPI_Bcast: code/utilities.hpp:2502-2540; the same sequence on every rank, :880-912) | their midpoint
     bool equilibrate = false;                  // -equilibrate 1: per-rank scaling of the block (code/main.cpp:1117-1125)
     bool sp = false;                           // -sp: single precision matrix, vectors and exchange
+    bool ap = false;                           // -ap[dp_sp]: the adaptive-precision object (uspmv_dist_create_ap_from_coo), double vectors, single vector, scs
+    double ap_threshold_1 = 0.0;               // ... -ap_threshold_1: entries with |v| >= it stay double
     char mode = 'b';                           // -mode s: the reference's COMM-spmv-SWAP loop (code/main.cpp:528-607), -rev iterations, no timing
     unsigned long n_repetitions = 1;
     std::string dump_y;                        // -dump_y <file>: every rank writes y of its rows (original order, raw doubles) to <file>.<rank>

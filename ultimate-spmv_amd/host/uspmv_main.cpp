@@ -83,7 +83,7 @@ void usage() {
             "  -bench_steps <int> -bench_warmup <int> -json <file|-> (fixed-count protocol, JSON report)  -x_prepared <0|1> (bench mode, column-major block vectors: X re-laid out once)\n"
             "  -convert <host|device|device_stable> (where convert_to_scs runs; device_stable: ties of the sigma sort in original order)\n"
             "  -tune <key>=<int> (a tuning key of the library, e.g. tlc_idx12=0, spmmv_reorder=1; repeatable)\n"
-            "  multi-rank runs: -check_y <0|1> -step_form <auto|auto_all|overlap|plain|pad|fused>\n"
+            "  multi-rank runs: -check_y <0|1> -step_form <auto|auto_all|overlap|plain|pad|fused>  (-ap[dp_sp]: scs, single vector, no auto_all / fused)\n"
             "  -seg_metis [-part_file <file>]: graph partition (built-in level-set partitioner, or part ids from a gpmetis-style file)\n");
 }
 
@@ -478,9 +478,14 @@ int run(const Config &c, uspmv_coo_t *coo) {
 int main(int argc, char **argv) {
     Config c = parse(argc, argv);
     if (uspmv_dist_requested()) {  // one process per GPU, halo exchange on RCCL (uspmv_dist.cpp)
-        if (c.value_type != "dp" && c.value_type != "sp")
-            die("multi-rank runs are -dp or -sp (single vector or -block_vec_size b, crs or scs, -mode b or s) "
-                "(the reference also refuses ap with MPI, code/utilities.hpp:1443-1450)");
+        const bool dist_ap = c.value_type == "ap[dp_sp]";
+        if (c.value_type != "dp" && c.value_type != "sp" && !dist_ap)
+            die("multi-rank runs are -dp, -sp or -ap[dp_sp] (single vector or, one precision only, -block_vec_size b; crs or scs, -mode b or s) "
+                "(the reference refuses ap with MPI altogether, code/utilities.hpp:1443-1450)");
+        // ap[dp_sp] across ranks (uspmv_dist_create_ap_from_coo): scs, single vector (-block_vec_size > 1 and -equilibrate 1 died in parse)
+        if (dist_ap && c.kernel_format != "scs") die("multi-rank ap[dp_sp] runs take the scs format only.");
+        if (dist_ap && c.step_form == "fused") die("-step_form fused is not available for multi-rank ap[dp_sp] runs (auto, overlap, plain or pad).");
+        if (dist_ap && c.step_form == "auto_all") die("-step_form auto_all is not available for multi-rank ap[dp_sp] runs (auto, overlap, plain or pad).");
         if (c.mode == 's' && c.block_vec_size > 1) die("multi-rank solve mode takes a single vector.");
         // crs across ranks: the reference's C = 1, sigma = 1 struct (code/utilities.hpp:1420-1424) on the SELL kernels -- every row still the
         // entry-ordered FMA chain (the single-rank crs kernel reassociates like the reference's omp simd loop)
@@ -501,6 +506,7 @@ int main(int argc, char **argv) {
         // here the bitwise self-check of one step plays that role, as -check_y 1 does in bench mode
         d.check_y = c.check_y != 0 || (c.mode == 's' && c.validate_result != 0 && c.comm_halos != 0);
         d.equilibrate = c.equilibrate != 0;
+        d.ap = dist_ap; d.ap_threshold_1 = c.ap_threshold_1;
         // (-par_pack: on the device the send buffer is packed by one kernel either way, as in the reference's device branch, code/classes_structs.hpp:787-806)
         return uspmv_run_distributed(d);   // every rank generates / receives only its row block
     }

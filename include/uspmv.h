@@ -434,6 +434,25 @@ int uspmv_spmmv_ap_plan_lines(int b, int *max_lines);
  * the matrix entries, else 0.  b = 1 reports uspmv_spmv_ap's choice: 3 its sweep kernel, 2 its staged kernel (one vector per pass), 0
  * lane per row.  Same argument checks and error texts as uspmv_spmmv_ap (under this function's name); nothing is launched. */
 int uspmv_spmmv_ap_path(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, int b, int64_t ld, int layout, int *path, int *vectors_per_pass);
+/* uspmv_spmmv_ap restricted to a subset of the rows, for the distributed ap block step (uspmv_dist_spmmv_ap): the block twins of
+ * uspmv_spmv_ap_tiles / _chunks.  X and Y double, layouts and ld as uspmv_spmmv_ap.  Every row written carries, in every column, the bits
+ * uspmv_spmmv_ap gives it (one lane per row, every chain in slot order); rows outside the list are not touched.  Entries < 0 are skipped
+ * (a conditional list); n_ids == 0 is USPMV_OK and launches nothing.
+ * _tiles: the tiles of the pair's shared tile-local-column plan (tile t = rows [t * tile_rows, (t + 1) * tile_rows)); a pair without one
+ *   is refused.  b in {2, 4, 8, 16}, X and Y 16-byte aligned, an even ld for column-major vectors, "tlc" 1, "spmmv_variant" not 1 and room
+ *   for two vectors of the fullest tile in LDS: workgroup g runs tile d_tile_ids[g] with the staged kernel of uspmv_spmmv_ap, which here
+ *   stages X straight from EITHER layout (no re-layout workspace: a part of a step has no whole X to re-lay out).  Otherwise lane per
+ *   row over the tiles' rows.
+ * _chunks: chunk ids, lane per row, any pair, any b, layout and alignment.
+ * _tiles_path: what _tiles would run for 16-byte-aligned X and Y under the current tuning -- *path 2 the staged kernel
+ *   (*vectors_per_pass of the b vectors per pass over the entries), 0 lane per row (*vectors_per_pass 0).  The checks and error texts of
+ *   _tiles under this function's name; nothing is launched. */
+int uspmv_spmmv_ap_tiles(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const int32_t *d_tile_ids, int64_t n_ids, const void *d_X, void *d_Y,
+                         int b, int64_t ld, int layout, void *stream);
+int uspmv_spmmv_ap_chunks(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const int32_t *d_chunk_ids, int64_t n_ids, const void *d_X,
+                          void *d_Y, int b, int64_t ld, int layout, void *stream);
+int uspmv_spmmv_ap_tiles_path(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, int b, int64_t ld, int layout, int *path,
+                              int *vectors_per_pass);
 /* The vectors per pass the sweep kernel of uspmv_spmmv_ap takes at width b on a plan whose windows hold 2^wlog doubles: the largest of
  * {8, 4, 2} that is at most b, divides b and fits 160 KiB of LDS with one window (2^wlog * 8 bytes per vector); 0 where the kernel does not
  * apply (b not in {2, 4, 8, 16}, or wlog >= 14: two vectors of a window do not fit).  A pure function: callers use it to choose wlog for
@@ -715,7 +734,8 @@ int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_s
  * uspmv_halo_discover_ap -> column permutation of both -> upload -> with tlc the pair's shared line plan at 256-row tiles -> tile classes
  * from both parts -> the object.  Vectors are double.  Its step is uspmv_spmv_ap split into interior and boundary tiles (chunks);
  * "pad_split" defaults to 1 here (an ap pair pads nearly every chunk of both parts, and the padding column is a halo column on every
- * rank but the first).  "fused_step", "block_plan", "autotune_all" and uspmv_dist_spmmv answer USPMV_ERR_UNSUPPORTED on such an object. */
+ * rank but the first).  "fused_step", "block_plan", "autotune_all" and uspmv_dist_spmmv answer USPMV_ERR_UNSUPPORTED on such an object; its
+ * block-vector step is uspmv_dist_spmmv_ap. */
 int uspmv_dist_create_ap_from_coo(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
                                   const int32_t *wsa, int64_t C, int64_t sigma, double threshold_1, int tlc, uspmv_dist_t **out);
 int uspmv_dist_create_ap_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
@@ -808,6 +828,17 @@ int uspmv_dist_run(uspmv_dist_t *d, void *d_x, void *d_y, int n_steps, int use_g
  * collectively when a wider block first appears; the three patterns share that one wire format. */
 typedef enum { USPMV_BULKVEC = 0, USPMV_MULTIVEC = 1, USPMV_SINGLEVEC = 2 } uspmv_vecmode;
 int uspmv_dist_spmmv(uspmv_dist_t *d, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream);
+/* uspmv_dist_spmmv for an ap[dp_sp] object (uspmv_dist_create_ap_from_coo; one entry point per kind, as uspmv_spmmv / uspmv_spmmv_ap):
+ * same arguments, X and Y double, ld = padded_vec_size, row-wise X bulkvec only; a one-precision object is refused.  b = 1 is the eager
+ * single-vector step (uspmv_dist_spmv).  P == 1 or comm_halos 0: uspmv_spmmv_ap on the block.  "overlap" 0: the exchange, then
+ * uspmv_spmmv_ap.  "overlap" 1 (default): the single-vector step's interior list through uspmv_spmmv_ap_tiles (_chunks on an object
+ * without tile lists) on a side stream while the exchange runs, the boundary list after both.  "pad_split" 1 (the object's default) is
+ * honoured: the b values of the padding column's slot are kept before the exchange, and the padding tiles run again after the boundary
+ * tiles iff for ANY column the kept or the delivered value is not finite or their signs differ (one re-run per step in
+ * uspmv_dist_pad_info).  Every arrangement gives the same bits: column v of Y is what uspmv_dist_spmv gives for column v of X.
+ * uspmv_dist_spmmv_info counts these steps.  uspmv_dist_spmmv itself, "block_plan", "fused_step" and "autotune_all" stay refused on
+ * an ap object. */
+int uspmv_dist_spmmv_ap(uspmv_dist_t *d, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream);
 /* Padding tiles of the single-vector step (tile lists, "pad_split" 1; an option, off by default -- see DESIGN 6.4 for the A/B).  The reference pads chunks with (value +0, column 0);
  * on every rank but the first, column 0 is a halo column (code/mpi_funcs.hpp:279-306), so most tiles of a rank touch the halo only
  * through fma(+0, x[pad_col], acc).  They run with the interior tiles, before the exchange has delivered x[pad_col]: for finite

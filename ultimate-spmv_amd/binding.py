@@ -151,6 +151,9 @@ _SIGS = {
     "uspmv_halo_discover_ap": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "uspmv_spmv_ap_tiles": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "uspmv_spmv_ap_chunks": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "uspmv_spmmv_ap_tiles": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
+    "uspmv_spmmv_ap_chunks": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
+    "uspmv_spmmv_ap_tiles_path": (C.c_int, [_vp, _vp, C.c_int, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "uspmv_halo_meta": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i32p), C.POINTER(_i32p), C.POINTER(_i32p)]),
     "uspmv_halo_free": (None, [_vp]),
     "uspmv_scs_chunk_classes": (C.c_int, [_vp, _i64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
@@ -189,6 +192,7 @@ _SIGS = {
     "uspmv_dist_spmv": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "uspmv_dist_run": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "uspmv_dist_spmmv": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "uspmv_dist_spmmv_ap": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "uspmv_dist_barrier": (C.c_int, [_vp, _vp]),
     "uspmv_dist_allreduce_max": (C.c_int, [_vp, C.POINTER(C.c_double), _vp]),
     "uspmv_dist_allgather_i64": (C.c_int, [_vp, _i64, C.POINTER(_i64), _vp]),
@@ -777,6 +781,12 @@ class DistNative:
         _ck(lib().uspmv_dist_spmmv(self.h, _dp(X), _dp(Y), int(b), int(layout), int(mode), int(bool(comm_halos)), self.stream.cuda_stream))
         return Y
 
+    def spmmv_ap(self, X, Y, b, layout=COLWISE, mode=0, comm_halos=True):
+        """spmmv on an ap[dp_sp] object (uspmv_dist_spmmv_ap): X, Y float64, column v of Y bitwise what spmv gives for column v of X."""
+        self._order(X, Y)
+        _ck(lib().uspmv_dist_spmmv_ap(self.h, _dp(X), _dp(Y), int(b), int(layout), int(mode), int(bool(comm_halos)), self.stream.cuda_stream))
+        return Y
+
     STEP_FORMS = ("overlap", "plain", "pad", "fused")
 
     def comm_count(self):
@@ -1355,6 +1365,26 @@ def spmmv_ap_path(A_dp, A_sp, b, ld, layout=COLWISE):
     lane per row, 1 gather, 2 staged over the shared line plan, 3 column-window sweep; vectors per pass of the sweep / staged kernel, else 0."""
     path, vec = C.c_int(), C.c_int()
     _ck(lib().uspmv_spmmv_ap_path(A_dp.h, A_sp.h, int(b), int(ld), int(layout), C.byref(path), C.byref(vec)))
+    return path.value, vec.value
+
+
+def spmmv_ap_tiles(A_dp, A_sp, tile_ids, X, Y, b, ld, layout=COLWISE, stream=None):
+    """spmmv_ap over the tiles in tile_ids (int32 tensor; entries < 0 skipped) of the pair's shared plan (uspmv_spmmv_ap_tiles)"""
+    _ck(lib().uspmv_spmmv_ap_tiles(A_dp.h, A_sp.h, _dp(tile_ids), tile_ids.numel(), _dp(X), _dp(Y), int(b), int(ld), int(layout), _stream_ptr(stream)))
+    return Y
+
+
+def spmmv_ap_chunks(A_dp, A_sp, chunk_ids, X, Y, b, ld, layout=COLWISE, stream=None):
+    """spmmv_ap over the chunks in chunk_ids (int32 tensor; entries < 0 skipped), lane per row (uspmv_spmmv_ap_chunks)"""
+    _ck(lib().uspmv_spmmv_ap_chunks(A_dp.h, A_sp.h, _dp(chunk_ids), chunk_ids.numel(), _dp(X), _dp(Y), int(b), int(ld), int(layout), _stream_ptr(stream)))
+    return Y
+
+
+def spmmv_ap_tiles_path(A_dp, A_sp, b, ld, layout=COLWISE):
+    """(path, vectors) that spmmv_ap_tiles would take for 16-byte-aligned X / Y under the current tuning (uspmv_spmmv_ap_tiles_path):
+    path 2 the staged kernel with `vectors` per pass, 0 lane per row over the tiles' rows."""
+    path, vec = C.c_int(), C.c_int()
+    _ck(lib().uspmv_spmmv_ap_tiles_path(A_dp.h, A_sp.h, int(b), int(ld), int(layout), C.byref(path), C.byref(vec)))
     return path.value, vec.value
 
 

@@ -22,16 +22,37 @@ __device__ __forceinline__ HT ap_hp_fold_y(double s, double q) { return ap_hp_y<
 // Any b, either layout, any C, no alignment demands: the block form of scs_spmmv_rows for a split.  VB vectors per pass held in
 // registers; per vector the parts' chains run one after the other with global gathers of X, (hi + mid) folded before the last chain starts.
 // colwise: X[col + v*ld], Y[row + v*ld];  rowwise: X[col*b + v], Y[row*b + v].
-// IDS: the chunks chunk_ids[0 .. n_chunks) instead of all (the rest chunks of a column-window sweep plan).
-template <int VB, bool ROWWISE, bool NT, typename HT, bool MID, typename LT, bool IDS = false>
+// IDS 1: the chunks ids[0 .. n_chunks) instead of all (the rest chunks of a column-window sweep plan, the chunk lists of the distributed
+// step); IDS 2: the tiles ids[0 .. n_chunks), tile t = the rows [t * unit_rows, (t + 1) * unit_rows) as far as the matrix has them
+// (n_total chunks) -- tile lists at widths, alignments and leading dimensions the staged kernel does not take.  An entry < 0 is a
+// conditional entry that was switched off: its lanes return, no row of it is touched.
+template <int VB, bool ROWWISE, bool NT, typename HT, bool MID, typename LT, int IDS = 0>
 __global__ void scs_spmmv_ap_rows(const long n_chunks, const int C, const ApHpParts P, const HT *__restrict__ X, HT *__restrict__ Y,
-                                  const int b, const long ld, const int xcd_remap, const int *__restrict__ chunk_ids) {
+                                  const int b, const long ld, const int xcd_remap, const int *__restrict__ ids, const int unit_rows,
+                                  const long n_total) {
     const unsigned lb = remap_block(blockIdx.x, gridDim.x, xcd_remap);
     long row = (long)lb * blockDim.x + threadIdx.x;
-    long c = row / C;
-    const int i = (int)(row - c * C);
-    if (c >= n_chunks) return;
-    if constexpr (IDS) { c = chunk_ids[c]; row = c * C + i; }
+    long c;
+    int i;
+    if constexpr (IDS == 2) {
+        const long u = row / unit_rows;
+        if (u >= n_chunks) return;
+        const long t = ids[u];
+        if (t < 0) return;
+        row = t * unit_rows + (row - u * unit_rows);
+        c = row / C;
+        i = (int)(row - c * C);
+        if (c >= n_total) return;
+    } else {
+        c = row / C;
+        i = (int)(row - c * C);
+        if (c >= n_chunks) return;
+        if constexpr (IDS == 1) {
+            c = ids[c];
+            if (c < 0) return;
+            row = c * C + i;
+        }
+    }
     auto chain = [&](auto vtag, const int k, const int v0, double (&acc)[VB]) {
         typedef decltype(vtag) VT;
         const long cs = P.cp[k][c];
@@ -160,10 +181,13 @@ constexpr int tlc_chain_slots(int B, int BS, bool pair) { return ((BS >= 8 && !p
 // 64 contiguous bytes), read in 16-byte pieces and stored element by element into the rows of LDS; else row-major (X[col*B + v]), read
 // and stored in 16-byte pieces (8 bytes for float X at BS = 2).  Rows at or beyond x_rows are staged as zeros.  Tiles without a line
 // list gather from global X.  YCOL: Y[row + v*ld], else Y[row*B + v].
-template <int B, int BS, int CT, bool NT, typename HT, bool MID, typename LT, bool XCOL, bool YCOL>
+// IDS: workgroup g runs tile tile_ids[g] (the interior / boundary lists of the distributed block step, uspmv_spmmv_ap_tiles); an entry < 0
+// is a conditional entry that was switched off and returns before the first barrier, uniformly for the workgroup.
+template <int B, int BS, int CT, bool NT, typename HT, bool MID, typename LT, bool XCOL, bool YCOL, bool IDS = false>
 __global__ void __launch_bounds__(1024) scs_spmmv_ap_tlc(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ X,
                                                          HT *__restrict__ Y, const long ld, const int *__restrict__ tile_line_ptr,
-                                                         const int *__restrict__ tile_lines, const long x_rows, const int xcd_remap) {
+                                                         const int *__restrict__ tile_lines, const long x_rows, const int xcd_remap,
+                                                         const int *__restrict__ tile_ids = nullptr) {
     static_assert(BS >= 2 && BS <= B && B % BS == 0, "whole passes");
     extern __shared__ __attribute__((aligned(16))) unsigned char tlc_smem[];
     HT *xs = (HT *)tlc_smem;
@@ -172,7 +196,9 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_tlc(const long n_chunks, co
     constexpr bool PAIR = std::is_same<LT, float>::value;    // ap[dp_sp]
     constexpr int W = tlc_chain_slots(B, BS, PAIR);
     const int C = CT > 0 ? CT : C_rt;
-    const unsigned tile = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    const unsigned lbt = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    const unsigned tile = IDS ? (unsigned)tile_ids[lbt] : lbt;
+    if (IDS && (int)tile < 0) return;
     const int lp0 = tile_line_ptr[tile];
     const int nl = tile_line_ptr[tile + 1] - lp0;
     const long row = (long)tile * blockDim.x + threadIdx.x;
@@ -263,47 +289,55 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_tlc(const long n_chunks, co
     }
 }
 
-// ids: the chunks to run (n_ids of them), or nullptr for all
+// ids: the chunks to run (n_ids of them), or nullptr for all; tile_rows > 0: ids are tiles of that many rows (the pair only)
 template <int VB, typename HT, bool MID, typename LT>
 void launch_ap_vb(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, int b, long ld, int layout, hipStream_t st, const int *ids,
-                  long n_ids) {
+                  long n_ids, int tile_rows) {
+    constexpr bool PAIR = std::is_same<LT, float>::value;
     const int block = g_tune.block;
     const long n_chunks = ids ? n_ids : (long)hi->n_chunks;
-    const unsigned grid = grid_for(n_chunks * hi->C, block);
+    const unsigned grid = grid_for(n_chunks * (ids && tile_rows > 0 ? (long)tile_rows : (long)hi->C), block);
     const bool nt = g_tune.nontemporal != 0;
+#define APV_LAUNCH_I(RW, NTV, IDSV)                                                                                                       \
+    hipLaunchKernelGGL((scs_spmmv_ap_rows<VB, RW, NTV, HT, MID, LT, IDSV>), dim3(grid), dim3(block), 0, st, n_chunks, (int)hi->C, P, X, Y, b, \
+                       ld, g_tune.xcd_remap, ids, tile_rows, (long)hi->n_chunks)
 #define APV_LAUNCH(RW, NTV)                                                                                                               \
     do {                                                                                                                                  \
-        if (ids)                                                                                                                          \
-            hipLaunchKernelGGL((scs_spmmv_ap_rows<VB, RW, NTV, HT, MID, LT, true>), dim3(grid), dim3(block), 0, st, n_chunks, (int)hi->C, P, X, Y, \
-                               b, ld, g_tune.xcd_remap, ids);                                                                            \
-        else                                                                                                                              \
-            hipLaunchKernelGGL((scs_spmmv_ap_rows<VB, RW, NTV, HT, MID, LT, false>), dim3(grid), dim3(block), 0, st, n_chunks, (int)hi->C, P, X, Y, \
-                               b, ld, g_tune.xcd_remap, (const int *)nullptr);                                                           \
+        if (!ids) APV_LAUNCH_I(RW, NTV, 0);                                                                                               \
+        else if (tile_rows <= 0) APV_LAUNCH_I(RW, NTV, 1);                                                                                \
+        else if constexpr (PAIR) APV_LAUNCH_I(RW, NTV, 2);                                                                                \
     } while (0)
     if (layout == USPMV_ROWWISE) { if (nt) APV_LAUNCH(true, true); else APV_LAUNCH(true, false); }
     else { if (nt) APV_LAUNCH(false, true); else APV_LAUNCH(false, false); }
 #undef APV_LAUNCH
+#undef APV_LAUNCH_I
 }
 
 // <XCOL, YCOL>: the kinds with an fp16 part stage X and store Y in the caller's layout; ap[dp_sp] always reads row-major X (column-major
-// callers arrive through the re-layout workspace) and stores Y either way
+// callers arrive through the re-layout workspace) and stores Y either way -- except over a tile list (ids, the pair only), where it too
+// stages X straight from the caller's columns: a part of a distributed step has no whole X to re-lay out
 template <int B, int BS, typename HT, bool MID, typename LT>
-void launch_ap_tlc_bs(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool ycol, hipStream_t st) {
+void launch_ap_tlc_bs(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool ycol, hipStream_t st, const int *ids, long n_ids) {
     constexpr bool PAIR = std::is_same<LT, float>::value;
     const size_t lds = (size_t)hi->tlc.max_lines * 16 * sizeof(HT) * BS;     // (what the fullest tile lists, not the budget)
     const int C = (int)hi->C;
-#define APT_LAUNCH(CTV, NTV, XC, YC)                                                                                                 \
+    const unsigned grid = ids ? (unsigned)n_ids : (unsigned)hi->tlc.n_tiles;
+    const long x_rows = ids && ycol ? std::min<long>((long)hi->tlc.x_len, ld) : (long)hi->tlc.x_len;
+#define APT_LAUNCH(CTV, NTV, XC, YC, IDSV)                                                                                           \
     do {                                                                                                                             \
-        auto kfn = scs_spmmv_ap_tlc<B, BS, CTV, NTV, HT, MID, LT, XC, YC>;                                                           \
+        auto kfn = scs_spmmv_ap_tlc<B, BS, CTV, NTV, HT, MID, LT, XC, YC, IDSV>;                                                     \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)hi->tlc.n_tiles), dim3(hi->tlc.tile_rows), lds, st, (long)hi->n_chunks, C, P, X, Y, ld, \
-                           hi->tlc.line_ptr.get(), hi->tlc.lines.get(), (long)hi->tlc.x_len, g_tune.xcd_remap);                      \
+        hipLaunchKernelGGL(kfn, dim3(grid), dim3(hi->tlc.tile_rows), lds, st, (long)hi->n_chunks, C, P, X, Y, ld,                    \
+                           hi->tlc.line_ptr.get(), hi->tlc.lines.get(), x_rows, g_tune.xcd_remap, ids);                              \
     } while (0)
 #define APT_NT(CTV, NTV)                                                                                                             \
     do {                                                                                                                             \
-        if (!ycol) APT_LAUNCH(CTV, NTV, false, false);                                                                               \
-        else if constexpr (PAIR) APT_LAUNCH(CTV, NTV, false, true);                                                                  \
-        else APT_LAUNCH(CTV, NTV, true, true);                                                                                       \
+        if (ids) {                                                                                                                   \
+            if constexpr (PAIR) { if (ycol) APT_LAUNCH(CTV, NTV, true, true, true); else APT_LAUNCH(CTV, NTV, false, false, true); } \
+        }                                                                                                                            \
+        else if (!ycol) APT_LAUNCH(CTV, NTV, false, false, false);                                                                   \
+        else if constexpr (PAIR) APT_LAUNCH(CTV, NTV, false, true, false);                                                           \
+        else APT_LAUNCH(CTV, NTV, true, true, false);                                                                                \
     } while (0)
     if (g_tune.nontemporal) { if (C == 32) APT_NT(32, true); else APT_NT(0, true); }
     else { if (C == 32) APT_NT(32, false); else APT_NT(0, false); }
@@ -312,10 +346,11 @@ void launch_ap_tlc_bs(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT 
 }
 
 template <int B, typename HT, bool MID, typename LT>
-void launch_ap_tlc(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool ycol, int bs, hipStream_t st) {
-    if constexpr (B >= 8) { if (bs == 8) { launch_ap_tlc_bs<B, 8, HT, MID, LT>(hi, P, X, Y, ld, ycol, st); return; } }
-    if constexpr (B >= 4) { if (bs == 4) { launch_ap_tlc_bs<B, 4, HT, MID, LT>(hi, P, X, Y, ld, ycol, st); return; } }
-    launch_ap_tlc_bs<B, 2, HT, MID, LT>(hi, P, X, Y, ld, ycol, st);
+void launch_ap_tlc(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool ycol, int bs, hipStream_t st, const int *ids,
+                   long n_ids) {
+    if constexpr (B >= 8) { if (bs == 8) { launch_ap_tlc_bs<B, 8, HT, MID, LT>(hi, P, X, Y, ld, ycol, st, ids, n_ids); return; } }
+    if constexpr (B >= 4) { if (bs == 4) { launch_ap_tlc_bs<B, 4, HT, MID, LT>(hi, P, X, Y, ld, ycol, st, ids, n_ids); return; } }
+    launch_ap_tlc_bs<B, 2, HT, MID, LT>(hi, P, X, Y, ld, ycol, st, ids, n_ids);
 }
 
 // The kind of a split from its handles, handed to f as tags: HT(), whether there is a mid part, LT().
@@ -378,30 +413,32 @@ void spmmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_d
 }
 
 int launch_spmmv_ap_rows(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const int *chunk_ids, long n_ids, const void *X,
-                         void *Y, int b, long ld, int layout, hipStream_t st) {
+                         void *Y, int b, long ld, int layout, hipStream_t st, int tile_rows) {
+    if (tile_rows > 0 && last->dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_spmmv_ap_rows: tile lists are the ap[dp_sp] pair's");
     const ApHpParts P = ap_hp_parts(hi, mid, last);
     ap_kind(hi, mid, last, [&](auto ht, auto m, auto lt) {      // VB vectors per pass
         typedef decltype(ht) HT; typedef decltype(lt) LT;
         constexpr bool MID = decltype(m)::value;
-        if (b <= 2) launch_ap_vb<2, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, b, ld, layout, st, chunk_ids, n_ids);
-        else if (b <= 4) launch_ap_vb<4, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, b, ld, layout, st, chunk_ids, n_ids);
-        else launch_ap_vb<8, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, b, ld, layout, st, chunk_ids, n_ids);
+        if (b <= 2) launch_ap_vb<2, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, b, ld, layout, st, chunk_ids, n_ids, tile_rows);
+        else if (b <= 4) launch_ap_vb<4, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, b, ld, layout, st, chunk_ids, n_ids, tile_rows);
+        else launch_ap_vb<8, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, b, ld, layout, st, chunk_ids, n_ids, tile_rows);
     });
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }
 
 int launch_spmmv_ap_staged(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const void *X, void *Y, int b, long ld, bool ycol,
-                           int bs, hipStream_t st) {
+                           int bs, hipStream_t st, const int *tile_ids, long n_ids) {
+    if (tile_ids && last->dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_spmmv_ap_staged: tile lists are the ap[dp_sp] pair's");
     const ApHpParts P = ap_hp_parts(hi, mid, last);
     ap_kind(hi, mid, last, [&](auto ht, auto m, auto lt) {
         typedef decltype(ht) HT; typedef decltype(lt) LT;
         constexpr bool MID = decltype(m)::value;
         switch (b) {
-            case 2: launch_ap_tlc<2, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st); break;
-            case 4: launch_ap_tlc<4, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st); break;
-            case 8: launch_ap_tlc<8, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st); break;
-            default: launch_ap_tlc<16, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st); break;
+            case 2: launch_ap_tlc<2, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st, tile_ids, n_ids); break;
+            case 4: launch_ap_tlc<4, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st, tile_ids, n_ids); break;
+            case 8: launch_ap_tlc<8, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st, tile_ids, n_ids); break;
+            default: launch_ap_tlc<16, HT, MID, LT>(hi, P, (const HT *)X, (HT *)Y, ld, ycol, bs, st, tile_ids, n_ids); break;
         }
     });
     HIP_TRY(hipGetLastError());

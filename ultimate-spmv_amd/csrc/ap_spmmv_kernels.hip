@@ -4,7 +4,8 @@
 // Y(r, v) = dp + sp.  One lane per row everywhere, so column v of Y is bitwise uspmv_spmv_ap of column v of X.  See DESIGN.md 5.7.
 // The pair is the kind <double, no mid, float last part> of the lane-per-row and staged block kernels in ap_hp_spmmv_kernels.hip
 // (launch_spmmv_ap_rows, launch_spmmv_ap_staged); what lives here is its own: the path predicate, the row-major gather kernel, and the
-// column-major re-layout through the dp handle's workspace.
+// column-major re-layout through the dp handle's workspace, and the dispatch of the list forms (uspmv_spmmv_ap_tiles / _chunks: the parts
+// of the distributed block step).
 #include "uspmv_device.hpp"
 
 using namespace uspmv_dev;
@@ -182,6 +183,19 @@ ApBlockPath ap_block_path(const uspmv_dmat *dp, const uspmv_dmat *sp, int b, lon
     return {AP_PATH_GATHER, 0};
 }
 
+// What uspmv_spmmv_ap_tiles runs: the ONE predicate behind the launch and behind uspmv_spmmv_ap_tiles_path.  The staged kernel over the
+// listed tiles -- X staged straight from the caller's layout, so column-major X wants whole 16-byte pieces of its columns (ld even) --
+// or lane per row over the tiles' rows: any other width, alignment or leading dimension, "tlc" 0, "spmmv_variant" 1, or a plan whose
+// fullest tile leaves no room for two vectors in LDS.
+ApBlockPath ap_tiles_path(const uspmv_dmat *dp, const uspmv_dmat *sp, int b, long ld, int layout, bool aligned16) {
+    if (g_tune.spmmv_variant == 1 || !aligned16 || (b != 2 && b != 4 && b != 8 && b != 16)) return {AP_PATH_GENERIC, 0};
+    if (layout != USPMV_ROWWISE && (ld & 1)) return {AP_PATH_GENERIC, 0};
+    if (!ap_tlc_applies(dp, sp)) return {AP_PATH_GENERIC, 0};
+    const int bs = tlc_block_bs(dp->tlc, b, sizeof(double));
+    if (bs < 2) return {AP_PATH_GENERIC, 0};
+    return {AP_PATH_STAGED, bs};
+}
+
 // the staged kernel over the shared plan (bs vectors per pass) or the gather kernel on the original arrays (bs 0), as ap_block_path
 // chose; X row-major
 template <int B>
@@ -221,6 +235,19 @@ int launch_spmmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int
                            long ld, int layout, hipStream_t st) {
     if (n_ids == 0) return USPMV_OK;
     return launch_spmmv_ap_rows(dp, nullptr, sp, chunk_ids, n_ids, X, Y, b, ld, layout, st);
+}
+
+void spmmv_ap_tiles_path(const uspmv_dmat *dp, const uspmv_dmat *sp, int b, long ld, int layout, int *path, int *vectors) {
+    const ApBlockPath p = ap_tiles_path(dp, sp, b, ld, layout, true);
+    *path = p.path; *vectors = p.bs;
+}
+
+int launch_spmmv_ap_tiles(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *tile_ids, long n_ids, const double *X, double *Y, int b,
+                          long ld, int layout, hipStream_t st) {
+    if (n_ids == 0) return USPMV_OK;
+    const ApBlockPath p = ap_tiles_path(dp, sp, b, ld, layout, ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0));
+    if (p.path == AP_PATH_STAGED) return launch_spmmv_ap_staged(dp, nullptr, sp, X, Y, b, ld, layout != USPMV_ROWWISE, p.bs, st, tile_ids, n_ids);
+    return launch_spmmv_ap_rows(dp, nullptr, sp, tile_ids, n_ids, X, Y, b, ld, layout, st, dp->tlc.tile_rows);
 }
 
 int launch_spmmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, int layout, hipStream_t st) {

@@ -1442,6 +1442,47 @@ int uspmv_spmmv_ap_path(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, int b, i
     return USPMV_OK;
 }
 
+// the checks the list forms of uspmv_spmmv_ap share: those of uspmv_spmv_ap_tiles / _chunks and of uspmv_spmmv_ap.  Nothing here
+// touches a device.
+static int check_ap_block_list(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, int b, int64_t ld, int layout, bool tiles, const char *who) {
+    if (b < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: b=%d", who, b);
+    if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown layout %d", who, layout);
+    if (int rc = check_ap_pair(dp, sp, who)) return rc;
+    if (layout == USPMV_COLWISE && ld < dp->n_chunks * dp->C)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: ld=%lld smaller than n_rows_padded=%lld", who, (long long)ld, (long long)(dp->n_chunks * dp->C));
+    if (tiles && (!dp->tlc.on || !sp->tlc.on || dp->tlc.plan_id == 0 || dp->tlc.plan_id != sp->tlc.plan_id))
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: the pair has no shared tile-local-column plan (uspmv_dmat_optimize_ap)", who);
+    return USPMV_OK;
+}
+
+int uspmv_spmmv_ap_tiles(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const int32_t *d_tile_ids, int64_t n_ids, const void *d_X, void *d_Y,
+                         int b, int64_t ld, int layout, void *stream) {
+    const char *who = "uspmv_spmmv_ap_tiles";
+    if (int rc = check_ap_block_list(dp, sp, b, ld, layout, true, who)) return rc;
+    if (n_ids < 0 || n_ids > dp->tlc.n_tiles || (n_ids > 0 && !d_tile_ids) || !d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    if (n_ids == 0) return USPMV_OK;
+    if (int rc = require_device()) return rc;
+    return launch_spmmv_ap_tiles(dp, sp, d_tile_ids, (long)n_ids, (const double *)d_X, (double *)d_Y, b, (long)ld, layout, (hipStream_t)stream);
+}
+
+int uspmv_spmmv_ap_chunks(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const int32_t *d_chunk_ids, int64_t n_ids, const void *d_X, void *d_Y,
+                          int b, int64_t ld, int layout, void *stream) {
+    const char *who = "uspmv_spmmv_ap_chunks";
+    if (int rc = check_ap_block_list(dp, sp, b, ld, layout, false, who)) return rc;
+    if (n_ids < 0 || n_ids > dp->n_chunks || (n_ids > 0 && !d_chunk_ids) || !d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    if (n_ids == 0) return USPMV_OK;
+    if (int rc = require_device()) return rc;
+    return launch_spmmv_ap_chunks(dp, sp, d_chunk_ids, (long)n_ids, (const double *)d_X, (double *)d_Y, b, (long)ld, layout, (hipStream_t)stream);
+}
+
+int uspmv_spmmv_ap_tiles_path(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, int b, int64_t ld, int layout, int *path, int *vectors_per_pass) {
+    const char *who = "uspmv_spmmv_ap_tiles_path";
+    if (int rc = check_ap_block_list(dp, sp, b, ld, layout, true, who)) return rc;
+    if (!path || !vectors_per_pass) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL result pointer", who);
+    spmmv_ap_tiles_path(dp, sp, b, (long)ld, layout, path, vectors_per_pass);
+    return USPMV_OK;
+}
+
 int uspmv_spmmv_ap_sweep_vectors(int b, int wlog, int *vectors) {
     if (b < 1 || wlog < 8 || wlog > 16 || !vectors) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmmv_ap_sweep_vectors: bad argument");
     *vectors = spmmv_ap_sweep_vectors(b, wlog);

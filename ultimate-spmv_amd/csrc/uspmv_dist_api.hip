@@ -34,7 +34,8 @@
 //
 // Adaptive precision ap[dp_sp] (uspmv_dist_create_ap_from_coo; the reference refuses ap with MPI, code/utilities.hpp:1445-1451): the object
 // carries the sp part as a second handle.  One halo for the pair, tile classes from both parts, "pad_split" on by default; the single-vector
-// step only.
+// step and, for block vectors, uspmv_dist_spmmv_ap: the same lists run by the list forms of the pair's block kernels
+// (uspmv_spmmv_ap_tiles / _chunks), the padding guard over the b values of the slot.
 #include <rccl/rccl.h>
 
 #include <chrono>
@@ -89,6 +90,8 @@ struct uspmv_dist {
     int32_t pad_col = -1;
     bool pad_split = false;           // (off by default: on one GPU it measures 0.221 against 0.209 ms per step, profiles/r03/dist_step_ab.txt)
     DeviceBuf<void> d_stale;
+    DeviceBuf<double> d_stale_b;      // the block step of an ap object (uspmv_dist_spmmv_ap): the slot's b values, grown to b at first use
+    int stale_b = 0;
     // peer-store exchange: this rank's receive window = two halves (step parity) of win_half elements, sized for block vectors of up to
     // win_b columns; the windows of the ranks it sends to, opened through IPC (nullptr: not opened; loopback opens nothing); the push
     // table (per neighbour q: q's window, its half size, where this rank's block starts in it) and the send offsets it is indexed by
@@ -210,6 +213,27 @@ __global__ void pad_guard_kernel(const VT *__restrict__ x, const int pad_col, co
     const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const VT s = *stale, c = x[pad_col];
     const bool need = !(isfinite(s) && isfinite(c) && (signbit(s) == signbit(c)));
+    if (k < n_pad) rerun[k] = need ? pad_ids[k] : -1;
+    if (k == 0 && need) atomicAdd(counter, 1);
+}
+
+// The block form of that pair for uspmv_dist_spmmv_ap: the padding column's slot holds one value per vector -- X[pad_col + v*ld]
+// column-wise, X[pad_col*b + v] row-wise.  Kept before the exchange; after it the padding tiles run again iff for ANY vector the kept
+// or the delivered value is not finite or their signs differ (a tile computes all b columns, so one such column re-runs it).
+__global__ void pad_keep_block_kernel(const double *__restrict__ X, const int pad_col, const int b, const long ld, const int rowwise,
+                                      double *__restrict__ stale) {
+    const int v = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (v < b) stale[v] = rowwise ? X[(long)pad_col * b + v] : X[pad_col + (long)v * ld];
+}
+__global__ void pad_guard_block_kernel(const double *__restrict__ X, const int pad_col, const int b, const long ld, const int rowwise,
+                                       const double *__restrict__ stale, const int *__restrict__ pad_ids, int *__restrict__ rerun,
+                                       const long n_pad, int *__restrict__ counter) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool need = false;
+    for (int v = 0; v < b; ++v) {
+        const double s = stale[v], c = rowwise ? X[(long)pad_col * b + v] : X[pad_col + (long)v * ld];
+        need = need || !(isfinite(s) && isfinite(c) && (signbit(s) == signbit(c)));
+    }
     if (k < n_pad) rerun[k] = need ? pad_ids[k] : -1;
     if (k == 0 && need) atomicAdd(counter, 1);
 }
@@ -606,6 +630,16 @@ int exchange(uspmv_dist *D, void *d_X, int b, int layout, int mode, int pad_col,
         for (int v = 0; v < b; ++v)
             if (int rc = uspmv_apply_permutation_dev(X + (size_t)(v * ld + D->n_local) * vsz, bp->d_recv, bp->d_unpack[(size_t)v], nh, D->dtype, st)) return rc;
     return USPMV_OK;
+}
+
+// The exchange of a block of b > 1 vectors: their gather lists index b * padded_vec_size elements in int32; the peer-store windows grow
+// (collectively, as the call is) the first time a wider block appears -- never in the single-vector step, which refuses once a failed
+// growth lost them
+int block_exchange(uspmv_dist *D, void *d_X, int b, int layout, int mode, hipStream_t st, const char *who) {
+    if ((int64_t)b * std::max(D->vec_len, (int64_t)1) > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: b * padded_vec_size exceeds int32", who);
+    if (D->exchange == USPMV_EXCHANGE_PEER && b > D->win_b)
+        if (int rc = peer_setup(D, b)) return rc;
+    return exchange(D, d_X, b, layout, mode, -1, st);
 }
 
 // the single-vector step's exchange
@@ -1104,7 +1138,7 @@ int uspmv_dist_set_option(uspmv_dist_t *D, const char *key, int value) {
     const std::string k(key);
     if (D->A_sp && (((k == "fused_step" || k == "autotune_all") && value != 0) || (k == "block_plan" && value > 0)))
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_set_option: '%s' is not available on an adaptive-precision (ap[dp_sp]) object: its step has "
-                           "the overlap, plain and pad_split forms, and no block vectors", key);
+                           "the overlap, plain and pad_split forms; block vectors run through uspmv_dist_spmmv_ap", key);
     if (k == "overlap") { if ((value != 0) != D->overlap) drop_graph(D); D->overlap = value != 0; }
     else if (k == "no_pack") { if ((value != 0) != D->no_pack) drop_graph(D); D->no_pack = value != 0; }
     else if (k == "ba_synch") { if ((value != 0) != D->ba_synch) drop_graph(D); D->ba_synch = value != 0; }
@@ -1403,21 +1437,14 @@ int uspmv_dist_check(uspmv_dist_t *D, const uspmv_coo_t *local, const int32_t *w
 
 int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
     if (!D || !d_X || !d_Y || b < 1) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: bad argument");
-    if (D->A_sp) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: not available on an adaptive-precision (ap[dp_sp]) object (single vectors only)");
+    if (D->A_sp) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: not available on an adaptive-precision (ap[dp_sp]) object (its block step is uspmv_dist_spmmv_ap)");
     if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown layout %d", layout);
     if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown mode %d", mode);
     if (layout == USPMV_ROWWISE && mode != USPMV_BULKVEC)
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: row-wise block vectors travel in one message per neighbour (bulkvec) only");
     hipStream_t main = (hipStream_t)stream;
     if (!(D->P > 1 && comm_halos)) return uspmv_spmmv(D->A, d_X, d_Y, b, D->vec_len, layout, stream);
-    // the exchange of block vectors: their gather lists index b * padded_vec_size elements in int32; the peer-store windows grow (collectively,
-    // as the call is) the first time a wider block appears -- never in the single-vector step, which refuses once a failed growth lost them
-    auto grow_and_exchange = [&]() -> int {
-        if ((int64_t)b * std::max(D->vec_len, (int64_t)1) > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "uspmv_dist_spmmv: b * padded_vec_size exceeds int32");
-        if (D->exchange == USPMV_EXCHANGE_PEER && b > D->win_b)
-            if (int rc = peer_setup(D, b)) return rc;
-        return exchange(D, d_X, b, layout, mode, -1, main);
-    };
+    auto grow_and_exchange = [&]() -> int { return block_exchange(D, d_X, b, layout, mode, main, "uspmv_dist_spmmv"); };
     // (a handle whose only block plan is the one-list-per-tile one runs that plan's kernels on the whole matrix: they are ahead of the
     //  gather kernels by more than the exchange costs)
     if (!(D->overlap && D->parts && !D->A->alt) || (D->A->bt.on && !(D->A->pb.on && D->A->part_len[1][0]))) {
@@ -1446,6 +1473,62 @@ int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, i
     A->part = 2;
     if (D->diag_spmmv_part != 1)
         if (int rc = uspmv_spmmv(A, d_X, d_Y, b, D->vec_len, layout, main)) return rc;
+    ++D->spmmv_two_part;
+    return step_barrier(D, main);
+}
+
+// The block step of an ap[dp_sp] object.  Unlike the dp object's two-part step (marked chunk-length arrays, uspmv_dmat::part_len) the
+// parts here are the single-vector step's own tile (chunk) lists run by the list forms of the pair's block kernels, so "pad_split"
+// carries over: see pad_keep_block_kernel.
+int uspmv_dist_spmmv_ap(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
+    const char *who = "uspmv_dist_spmmv_ap";
+    if (b < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: b=%d", who, b);
+    if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown layout %d", who, layout);
+    if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown mode %d", who, mode);
+    if (!D || !d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (!D->A_sp)
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: a one-precision object (uspmv_dist_create_from_coo); its block step is uspmv_dist_spmmv", who);
+    if (layout == USPMV_ROWWISE && mode != USPMV_BULKVEC)
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: row-wise block vectors travel in one message per neighbour (bulkvec) only", who);
+    hipStream_t main = (hipStream_t)stream;
+    if (b == 1) { ++D->eager_steps; return step(D, d_X, d_Y, main, comm_halos != 0); }
+    const int64_t ld = D->vec_len;
+    if (!(D->P > 1 && comm_halos)) return uspmv_spmmv_ap(D->A, D->A_sp, d_X, d_Y, b, ld, layout, stream);
+    if ((int64_t)b * std::max(ld, (int64_t)1) > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: b * padded_vec_size exceeds int32", who);
+    if (!D->overlap) {
+        if (int rc = block_exchange(D, d_X, b, layout, mode, main, who)) return rc;
+        if (int rc = uspmv_spmmv_ap(D->A, D->A_sp, d_X, d_Y, b, ld, layout, stream)) return rc;
+        ++D->spmmv_one_part;
+        return step_barrier(D, main);
+    }
+    const bool pads = pads_on(D);
+    const int rowwise = layout == USPMV_ROWWISE;
+    if (pads && b > D->stale_b) {
+        HIP_TRY(D->d_stale_b.zeros(sizeof(double) * (size_t)b));
+        D->stale_b = b;
+    }
+    auto part_b = [&](const int32_t *ids, int64_t n, hipStream_t st) -> int {
+        if (n == 0) return USPMV_OK;
+        return D->tiles ? uspmv_spmmv_ap_tiles(D->A, D->A_sp, ids, n, d_X, d_Y, b, ld, layout, st)
+                        : uspmv_spmmv_ap_chunks(D->A, D->A_sp, ids, n, d_X, d_Y, b, ld, layout, st);
+    };
+    HIP_TRY(hipEventRecord(D->ev_main, main));                       // fork, join and the lists: those of step()
+    HIP_TRY(hipStreamWaitEvent(D->side_stream, D->ev_main, 0));
+    if (int rc = pads ? part_b(D->d_early, D->n_int + D->n_pad, D->side_stream) : part_b(D->d_int, D->n_int, D->side_stream)) return rc;
+    HIP_TRY(hipEventRecord(D->ev_comm, D->side_stream));
+    if (pads) {
+        hipLaunchKernelGGL(pad_keep_block_kernel, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, main, (const double *)d_X, D->pad_col, b, (long)ld, rowwise,
+                           D->d_stale_b.get());
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = block_exchange(D, d_X, b, layout, mode, main, who)) return rc;
+    if (pads) {
+        hipLaunchKernelGGL(pad_guard_block_kernel, dim3((unsigned)((D->n_pad + 255) / 256)), dim3(256), 0, main, (const double *)d_X, D->pad_col, b, (long)ld,
+                           rowwise, (const double *)D->d_stale_b.get(), D->d_pad.get(), D->d_late + D->n_bnd_real, (long)D->n_pad, D->d_scratch + 2);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamWaitEvent(main, D->ev_comm, 0));                // join
+    if (int rc = pads ? part_b(D->d_late, D->n_bnd_real + D->n_pad, main) : part_b(D->d_bnd, D->n_bnd, main)) return rc;
     ++D->spmmv_two_part;
     return step_barrier(D, main);
 }

@@ -177,7 +177,7 @@ enum Expect { SWEEPS, DECLINED };
 
 template <typename VT>
 static void run_t(const char *name, const uspmv_coo_t *coo, int C, int sigma, int wlog, int tile_rows, double max_stage, Expect expect, int want_max_cnt,
-                  bool want_empty_tile, bool corrupt_it) {
+                  bool want_empty_tile, bool corrupt_it, bool exact_x) {
     constexpr int B = 64 / (int)sizeof(VT);
     uspmv_scs_t *s = nullptr;
     REQUIRE(uspmv_convert_to_scs(coo, C, sigma, sizeof(VT) == 8 ? USPMV_F64 : USPMV_F32, nullptr, &s) == 0);
@@ -197,7 +197,9 @@ static void run_t(const char *name, const uspmv_coo_t *coo, int C, int sigma, in
     int32_t max_col = 0;
     for (int32_t c : s->col_idxs) max_col = std::max(max_col, c);
     REQUIRE(p.x_rows_min == (int64_t)max_col + 1);
-    const int64_t x_rows = std::max<int64_t>(std::max<int64_t>(s->n_rows_padded, s->n_cols), p.x_rows_min);
+    // exact_x: X of x_rows_min rows and no more (the kernel's contract), which a row block needs beyond its padded rows
+    if (exact_x) REQUIRE(s->n_rows != s->n_cols && p.x_rows_min > s->n_rows_padded);
+    const int64_t x_rows = exact_x ? p.x_rows_min : std::max<int64_t>(std::max<int64_t>(s->n_rows_padded, s->n_cols), p.x_rows_min);
     for (int special = 0; special < 2; ++special) {
         const std::vector<VT> X = make_X<VT>(s, x_rows, B, special != 0);
         const std::vector<VT> ref = chain<VT>(s, X, B);
@@ -225,9 +227,9 @@ static void run_t(const char *name, const uspmv_coo_t *coo, int C, int sigma, in
 }
 
 static void run(const char *name, const uspmv_coo_t *coo, int C, int sigma, int wlog_f64, int wlog_f32, int tile_rows, double max_stage = 24.0,
-                Expect expect = SWEEPS, int want_max_cnt = 0, bool want_empty_tile = false, bool corrupt_it = false) {
-    run_t<double>(name, coo, C, sigma, wlog_f64, tile_rows, max_stage, expect, want_max_cnt, want_empty_tile, corrupt_it);
-    run_t<float>(name, coo, C, sigma, wlog_f32, tile_rows, max_stage, expect, want_max_cnt, want_empty_tile, corrupt_it);
+                Expect expect = SWEEPS, int want_max_cnt = 0, bool want_empty_tile = false, bool corrupt_it = false, bool exact_x = false) {
+    run_t<double>(name, coo, C, sigma, wlog_f64, tile_rows, max_stage, expect, want_max_cnt, want_empty_tile, corrupt_it, exact_x);
+    run_t<float>(name, coo, C, sigma, wlog_f32, tile_rows, max_stage, expect, want_max_cnt, want_empty_tile, corrupt_it, exact_x);
 }
 
 static uspmv_coo_t *from_rows(int64_t n, const std::vector<std::vector<int32_t>> &rows) {
@@ -281,7 +283,14 @@ int main() {
     run("stencil3", st3, 32, 512, 9, 9, 1024);
     run("stencil3", st3, 32, 512, 8, 8, 2048, 24.0, DECLINED);
     run("stencil3", st3, 32, 512, 11, 11, 1024);                           // 128-KiB windows: one LDS buffer whatever "sweep_nbuf" asks
-    for (uspmv_coo_t *m : {a, band, st3, h, d255, d256}) uspmv_coo_free(m);
+    // a row block, rows 4001..7001 of the 9999-row banded matrix (tests/test_gpu_nonsquare.py): 3001 x 9999, X of x_rows_min rows
+    uspmv_coo_t *rb = nullptr;
+    const int64_t row_begin = 4001, row_end = 7002;
+    REQUIRE(uspmv_gen_banded_random(9999, 23, 700, 7, 10.0, row_begin, row_end, &rb) == 0);
+    REQUIRE(rb->n_rows == row_end - row_begin && rb->n_cols == 9999);
+    run("row block", rb, 32, 512, 9, 9, 1024, 24.0, SWEEPS, 0, false, false, true);
+    run("row block", rb, 64, 1, 11, 11, 1024, 24.0, SWEEPS, 0, false, false, true);
+    for (uspmv_coo_t *m : {a, band, st3, h, d255, d256, rb}) uspmv_coo_free(m);
     printf(fails ? "FAILED\n" : "OK\n");
     return fails ? 1 : 0;
 }

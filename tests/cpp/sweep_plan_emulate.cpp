@@ -2,6 +2,7 @@
 // scs_spmv_sweep consumes it (windows ascending, rounds, active lanes ascending, compacted stream, trailing padding once)
 // and compares y bit for bit with the plain slot-ordered FMA chain over the SCS arrays (the reference's summation,
 // code/kernels.hpp:237-252 / code/ap_kernels.hpp:59-75).  Test infrastructure only; built by tests/test_sweep_plan.py.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -30,11 +31,16 @@ static std::vector<VT> chain(const uspmv_scs *s, const std::vector<VT> &x, const
 
 static bool same_bits(double a, double b) { return std::memcmp(&a, &b, 8) == 0 || (std::isnan(a) && std::isnan(b)); }
 
-static void run(int64_t n, int nnz_row, int64_t band, int C, int sigma, int wlog, int tile_rows, bool ap, bool special) {
+// row_begin / row_end: the rows of the generator's matrix that are kept (renumbered from 0: a row block of n columns).  A row block gets
+// the split threshold th and an x of exactly x_len_min elements, the kernels' contract.
+static void run(int64_t n, int nnz_row, int64_t band, int C, int sigma, int wlog, int tile_rows, bool ap, bool special, int64_t row_begin = 0,
+                int64_t row_end = -1, double th = 1e-3) {
+    if (row_end < 0) row_end = n;
+    const bool block = row_begin != 0 || row_end != n;
     uspmv_coo_t *coo = nullptr;
-    REQUIRE(uspmv_gen_banded_random(n, nnz_row, band, 7, ap ? 10.0 : 0.0, 0, n, &coo) == 0);
+    REQUIRE(uspmv_gen_banded_random(n, nnz_row, band, 7, ap ? 10.0 : 0.0, row_begin, row_end, &coo) == 0);
     uspmv_coo_t *dpc = coo, *spc = nullptr;
-    if (ap) REQUIRE(uspmv_partition_precisions(coo, 1e-3, &dpc, &spc) == 0);
+    if (ap) REQUIRE(uspmv_partition_precisions(coo, th, &dpc, &spc) == 0);
     uspmv_scs_t *s = nullptr, *s2 = nullptr;
     REQUIRE(uspmv_convert_to_scs(dpc, C, sigma, USPMV_F64, nullptr, &s) == 0);
     REQUIRE(uspmv_permute_scs_cols(s, s->old_to_new_idx.data()) == 0);
@@ -42,13 +48,20 @@ static void run(int64_t n, int nnz_row, int64_t band, int C, int sigma, int wlog
         REQUIRE(uspmv_convert_to_scs(spc, C, sigma, USPMV_F32, s->old_to_new_idx.data(), &s2) == 0);
         REQUIRE(uspmv_permute_scs_cols(s2, s->old_to_new_idx.data()) == 0);
     }
-    std::vector<double> x((size_t)std::max<int64_t>(s->n_rows_padded, n));
-    for (size_t i = 0; i < x.size(); ++i) x[i] = 1.0 + 1e-3 * (double)(i % 1000);
-    if (special) { x[0] = -INFINITY; x[5] = -0.0; x[17] = NAN; }
     uspmv_sweep_plan p;
     const uspmv_scs *const ss[2] = {s, s2};
     REQUIRE(uspmv_build_sweep_plan(ss, ap ? 2 : 1, wlog, tile_rows, 1e9, &p) == 0);
     REQUIRE(p.valid);
+    int64_t max_col = -1;
+    for (const uspmv_scs *q : ss) if (q) for (int32_t c : q->col_idxs) max_col = std::max<int64_t>(max_col, c);
+    REQUIRE(p.x_len_min == max_col + 1);
+    if (block) {
+        REQUIRE(s->n_rows == row_end - row_begin && s->n_rows != s->n_cols && p.x_len_min > s->n_rows_padded);
+        REQUIRE(p.n_sweep_tiles == p.n_tiles && p.rest_chunks.empty());
+    }
+    std::vector<double> x((size_t)(block ? p.x_len_min : std::max<int64_t>(s->n_rows_padded, n)));
+    for (size_t i = 0; i < x.size(); ++i) x[i] = 1.0 + 1e-3 * (double)(i % 1000);
+    if (special) { x[0] = -INFINITY; x[5] = -0.0; x[17] = NAN; }
     const auto &dp = p.part[0], &sp = p.part[1];
     const int64_t R = p.tile_rows, wpt = R / 64, n_pad = s->n_chunks * s->C;
     std::vector<double> y((size_t)n_pad, 12345.0);
@@ -110,6 +123,7 @@ static void run(int64_t n, int nnz_row, int64_t band, int C, int sigma, int wlog
         REQUIRE(covered[(size_t)r] != 0);
         if (covered[(size_t)r] == 1) { ++nsw; if (!same_bits(y[(size_t)r], ref[(size_t)r])) ++bad; }
     }
+    if (block) printf("rows %ld..%ld of ", (long)row_begin, (long)row_end - 1);
     printf("n=%ld C=%d sigma=%d wlog=%d tile=%d ap=%d special=%d: sweep tiles %ld/%ld, rows checked %ld, mismatches %ld\n", (long)n, C, sigma, wlog,
            tile_rows, (int)ap, (int)special, (long)p.n_sweep_tiles, (long)p.n_tiles, (long)nsw, (long)bad);
     REQUIRE(bad == 0);
@@ -128,6 +142,9 @@ int main() {
     run(20000, 40, 3000, 32, 512, 10, 2048, true, false);   // several rows per lane in the kernel: tiles above 1 024 rows
     run(9999, 23, 700, 16, 64, 9, 4096, false, true);
     run(7777, 31, 900, 64, 128, 8, 256, true, true);
+    // a row block, 3001 x 9999 (tests/test_gpu_nonsquare.py): x windows beyond the padded rows, x of x_len_min = 7695 elements and no more
+    run(9999, 23, 700, 32, 512, 10, 1024, false, true, 4001, 7002);
+    run(9999, 23, 700, 8, 64, 8, 256, true, false, 4001, 7002, 1e-1);
     printf(fails ? "FAILED\n" : "OK\n");
     return fails ? 1 : 0;
 }

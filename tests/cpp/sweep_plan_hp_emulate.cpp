@@ -93,16 +93,21 @@ static double stream_val(const PartView &v, size_t k) {
 }
 
 // replay + compare; returns sweep tiles.  expect: 0 = any coverage > 0, 1 = every tile sweeps, 2 = some tiles sweep and some do not
-static int64_t check_split(const char *what, const Split &sp, int wlog, int tile_rows, double max_stage, bool special, int expect) {
+static int64_t check_split(const char *what, const Split &sp, int wlog, int tile_rows, double max_stage, bool special, int expect, bool exact_x = false) {
     const bool fx = sp.kind == SP_HP;
     const uspmv_scs *s0 = sp.s[0];
     const int64_t C = s0->C, n_pad = s0->n_chunks * C;
-    std::vector<double> x = make_x(std::max<int64_t>(s0->n_rows_padded, s0->n_cols), fx, special);
     uspmv_sweep_plan p;
     REQUIRE(uspmv_build_sweep_plan(sp.s, sp.np, wlog, tile_rows, max_stage, &p) == 0);
     REQUIRE(p.n_parts == sp.np);
     REQUIRE(p.valid);
     if (!p.valid) return 0;
+    int64_t max_col = -1;
+    for (int w = 0; w < sp.np; ++w) for (int32_t c : sp.s[w]->col_idxs) max_col = std::max<int64_t>(max_col, c);
+    REQUIRE(p.x_len_min == max_col + 1);
+    // exact_x: x of x_len_min elements and no more (the kernels' contract), which a row block needs beyond its padded rows
+    if (exact_x) REQUIRE(s0->n_rows != s0->n_cols && p.x_len_min > s0->n_rows_padded);
+    std::vector<double> x = make_x(exact_x ? p.x_len_min : std::max<int64_t>(s0->n_rows_padded, s0->n_cols), fx, special);
     const int64_t R = p.tile_rows, wpt = R / 64;
     std::vector<double> y((size_t)n_pad, 12345.0);
     std::vector<char> covered((size_t)n_pad, 0);
@@ -179,9 +184,11 @@ static int64_t check_split(const char *what, const Split &sp, int wlog, int tile
 }
 
 static void run(int64_t n, int nnz_row, int64_t band, int C, int sigma, int wlog, int tile_rows, int kind, bool special, int expect,
-                double q1 = 0.7, double q2 = 0.35) {
+                double q1 = 0.7, double q2 = 0.35, int64_t row_begin = 0, int64_t row_end = -1) {
+    if (row_end < 0) row_end = n;
+    const bool block = row_begin != 0 || row_end != n;      // a row block of n columns, rows renumbered from 0
     uspmv_coo_t *coo = nullptr;
-    REQUIRE(uspmv_gen_banded_random(n, nnz_row, band, 7, 10.0, 0, n, &coo) == 0);
+    REQUIRE(uspmv_gen_banded_random(n, nnz_row, band, 7, 10.0, row_begin, row_end, &coo) == 0);
     double t1 = q1 < 0 ? 0.0 : q1 > 1 ? INFINITY : quantile(coo, q1), t2 = q2 < 0 ? 0.0 : q2 > 1 ? INFINITY : quantile(coo, q2);
     if (special) {
         t1 = std::max(t1, 1e6); t2 = std::max(t2, 1e5);       // 7e4 lands in the hp part of every kind and overflows binary16 there
@@ -204,7 +211,8 @@ static void run(int64_t n, int nnz_row, int64_t band, int C, int sigma, int wlog
     }
     Split sp;
     if (make_split(coo, kind, t1, t2, C, sigma, &sp)) {
-        check_split("split", sp, wlog, tile_rows, 1e9, special, expect);
+        if (block) REQUIRE(sp.s[0]->n_rows == row_end - row_begin);
+        check_split(block ? "row block" : "split", sp, wlog, tile_rows, 1e9, special, expect, block);
         sp.free();
     } else REQUIRE(!"conversion of a part refused");
     uspmv_coo_free(coo);
@@ -427,6 +435,8 @@ int main() {
         run(6016, 30, 800, 64, 1, 10, 256, kind, false, 1, 2.0, -1.0);     // dp_sp_hp: everything in mid
         run(6016, 30, 800, 32, 64, 9, 512, kind, false, 1, 0.98, 0.02);    // thin hi and hp parts: rows empty in some parts only
         run_unsorted(kind);
+        // a row block, 3001 x 9999 (tests/test_gpu_nonsquare.py): x windows beyond the padded rows, x of x_len_min elements and no more
+        run(9999, 23, 700, 32, 512, 10, 1024, kind, false, 1, 0.7, 0.35, 4001, 7002);
     }
     run_coverage();
     printf(fails ? "FAILED\n" : "OK\n");

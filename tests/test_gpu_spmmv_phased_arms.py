@@ -1,5 +1,6 @@
 """The phased SpMMV kernel scs_spmmv_quadph (csrc/spmmv_phased.hip; 64-byte X rows: dp b = 8, sp b = 16) on the arms and tuning keys that no
-other file runs: the plan over original X-row numbering behind the permuting re-layout ("spmmv_unscramble", xmode 3), non-temporal
+other file runs: the plan over original X-row numbering behind the permuting re-layout ("spmmv_unscramble", xmode 3), a handle planned
+again without its optional (unscrambled / line) plan, non-temporal
 column-major stores ("spmmv_ycol_nt") in every X mode and in the streamed kernels, 512-row phases ("spmmv_phase_rows": two-byte indices, the
 MAXP = 8 instantiation with 32 KB of LDS), no phased plan at all ("spmmv_phased" 0: kernel 6 answers), the brick row order ("spmmv_reorder" 3),
 the line-staged form (XM = 2) where the last line of a column crosses the leading dimension, and the block remap of remap_block
@@ -253,6 +254,27 @@ def test_unscrambled_plan_special_values(pkg, t, cases, dt):
             got, path = product(t, K, A, t.from_numpy(X).cuda(), ld, False)
             assert path == (8, 3), (what, dt, path)
             same_bits(K, got, Yo, ld, False, (what, dt), nan_ok=True)
+
+
+@pytest.mark.parametrize("name,dt,key,col_path", [("mesh3", "f64", "spmmv_unscramble", (8, 3)), ("mesh3", "f32", "spmmv_unscramble", (8, 3)),
+                                                  ("mesh3-s1", "f64", "spmmv_xline", (8, 0))])
+def test_replanning_a_handle_drops_the_optional_plans(pkg, t, cases, name, dt, key, col_path):
+    """a handle that carries the unscrambled or the line plan is planned again without the key: the second uspmv_dmat_optimize_block must
+    release the optional plan with everything else (block_plan_reset, the one release path of the plans' phase lists), so that the key set
+    again at LAUNCH time finds no such plan and the plain re-layout over the new phased plan answers"""
+    K = cases(name, dt)
+    A = pkg.DeviceMatrix(K.s)
+    with tuning(pkg, **{key: 1}):
+        A.optimize_block(K.s, K.b)
+        info = A.block_plan_info()
+        assert info["phased_plan"] == 1 and info["line_plan"] == int(key == "spmmv_xline"), info
+        run_all(t, K, A, (8, 0), col_path, (name, dt, key, "first plan"))
+    with tuning(pkg):
+        A.optimize_block(K.s, K.b)
+    with tuning(pkg, **{key: 1}):
+        info = A.block_plan_info()
+        assert info["phased_plan"] == 1 and info["line_plan"] == 0 and info["line_phases"] == 0, info
+        run_all(t, K, A, (8, 0), (8, 1), (name, dt, key, "planned again"))
 
 
 # ------------------------------------------------------------------------------------------------ 3. spmmv_ycol_nt

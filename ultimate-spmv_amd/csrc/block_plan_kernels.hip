@@ -210,8 +210,8 @@ namespace uspmv_dev {
 
 int launch_block_tile_class(const uspmv_dmat *A, long n_local, unsigned char *d_flags, hipStream_t st) {
     if (A->pb.n_tiles == 0) return USPMV_OK;
-    hipLaunchKernelGGL(block_tile_class, dim3((unsigned)((A->pb.n_tiles + 255) / 256)), dim3(256), 0, st, (long)A->pb.n_tiles, A->pb.ph_ptr, A->pb.list_ptr,
-                       A->pb.xrows, (int)std::min<long>(n_local, INT32_MAX), d_flags);
+    hipLaunchKernelGGL(block_tile_class, dim3((unsigned)((A->pb.n_tiles + 255) / 256)), dim3(256), 0, st, (long)A->pb.n_tiles, A->pb.lists.ph_ptr, A->pb.lists.list_ptr,
+                       A->pb.lists.list, (int)std::min<long>(n_local, INT32_MAX), d_flags);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }

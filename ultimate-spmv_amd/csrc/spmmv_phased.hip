@@ -246,86 +246,84 @@ __global__ void __launch_bounds__(256) scs_spmmv_quadph(const long n_chunks, con
     }
 }
 
+#define QH_ARGS(L) (long)A->n_chunks, A->chunk_ptrs, part_lengths(A, 1), (const VT *)A->pb.values, X, Y, ld, (L).ph_ptr, (L).g0, (L).list_ptr, (L).list, \
+                   A->pb.c16_ptrs, (const IT *)(L).idx, g_tune.xcd_remap, (long)A->n_store, (const int *)A->bt.row_map
+
+// One launch over the phase lists L of the handle's plan.  NTV: nontemporal matrix stream; YC: column-major Y, which behind a nontemporal
+// stream is written with plain stores that the L2 merges into whole lines unless "spmmv_ycol_nt" (no such form for XM 1).
+template <typename VT, typename IT, int B, int CT, int MAXP, int XM, bool NTV, bool YC>
+void launch_quadph_form(const uspmv_dmat *A, const PhaseLists &L, const VT *X, VT *Y, long ld, size_t lds, hipStream_t st) {
+    auto kfn = scs_spmmv_quadph<VT, IT, B, NTV, YC, CT, PHASE_GROUPS, MAXP, XM>;
+    if constexpr (NTV && XM != 1)
+        if (YC && !g_tune.spmmv_ycol_nt) kfn = scs_spmmv_quadph<VT, IT, B, NTV, YC, CT, PHASE_GROUPS, MAXP, XM, 0, false>;
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st, QH_ARGS(L));
+}
+// ... the form by "nontemporal" and the layout of Y.  The line lists (XM 2) are compiled for column-major Y only.
+template <typename VT, typename IT, int B, int CT, int MAXP, int XM>
+void launch_quadph_lists(const uspmv_dmat *A, const PhaseLists &L, const VT *X, VT *Y, long ld, bool ycol, size_t lds, hipStream_t st) {
+    if constexpr (XM != 2) {
+        if (!ycol) {
+            if (g_tune.nontemporal) launch_quadph_form<VT, IT, B, CT, MAXP, XM, true, false>(A, L, X, Y, ld, lds, st);
+            else launch_quadph_form<VT, IT, B, CT, MAXP, XM, false, false>(A, L, X, Y, ld, lds, st);
+            return;
+        }
+    }
+    if (g_tune.nontemporal) launch_quadph_form<VT, IT, B, CT, MAXP, XM, true, true>(A, L, X, Y, ld, lds, st);
+    else launch_quadph_form<VT, IT, B, CT, MAXP, XM, false, true>(A, L, X, Y, ld, lds, st);
+}
+
+// xmode 0 / 1: the phased plan's X-row lists (1: rows assembled from column-major X); 2: the line plan's lists; 3: the unscrambled plan's
+// lists over the row-major workspace in ORIGINAL row numbering (the re-layout pass undid the sigma permutation).  2 and 3: Y column-major.
 template <typename VT, typename IT, int B, int CT, int MAXP>
 void launch_spmmv_quadph_m(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, int xmode, hipStream_t st) {
     const bool xcol = xmode == 1;
     A->last_kernel = 8;
     const size_t lds = xcol ? (size_t)MAXP * 64 * 80 : (size_t)MAXP * 4 * 1024;   // MAXP*64 rows of 64 (row-major X / lines, DMA pieces) or 80 bytes
-#define QH_ARGS(PH, G0, LP, XR, C16) (long)A->n_chunks, A->chunk_ptrs, part_lengths(A, 1), (const VT *)A->pb.values, X, Y, ld, PH, G0, LP, XR, A->pb.c16_ptrs, \
-                           (const IT *)C16, g_tune.xcd_remap, (long)A->n_store, (const int *)A->bt.row_map
-#define QH_LAUNCH(NTV, YC)                                                                                              \
-    do {                                                                                                                \
-        auto kfn = xcol ? scs_spmmv_quadph<VT, IT, B, NTV, YC, CT, 8, MAXP, 1> : scs_spmmv_quadph<VT, IT, B, NTV, YC, CT, 8, MAXP, 0>; \
-        if (YC && NTV && !xcol && !g_tune.spmmv_ycol_nt) kfn = scs_spmmv_quadph<VT, IT, B, NTV, YC, CT, 8, MAXP, 0, 0, false>;            \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st, QH_ARGS(A->pb.ph_ptr, A->pb.g0, A->pb.list_ptr, A->pb.xrows, A->pb.col16)); \
-    } while (0)
-    if constexpr (MAXP == 4 && sizeof(IT) == 1) {
-        if (xmode == 3) {   // row-major workspace in ORIGINAL row numbering (the re-layout pass undid the sigma permutation): the handle's third plan
-            if (g_tune.nontemporal && g_tune.spmmv_ycol_nt)
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 0>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pu.ph_ptr, A->pu.g0, A->pu.list_ptr, A->pu.xrows, A->pu.col8));
-            else if (g_tune.nontemporal)
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 0, 0, false>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pu.ph_ptr, A->pu.g0, A->pu.list_ptr, A->pu.xrows, A->pu.col8));
-            else
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, false, true, CT, 8, MAXP, 0>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pu.ph_ptr, A->pu.g0, A->pu.list_ptr, A->pu.xrows, A->pu.col8));
-            return;
-        }
-        if (xmode == 2) {   // column-major X staged by lines (the handle's second phased plan); Y column-major as well
-            if (g_tune.nontemporal && g_tune.spmmv_ycol_nt)
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 2>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pl.ph_ptr, A->pl.g0, A->pl.list_ptr, A->pl.lines, A->pl.col8));
-            else if (g_tune.nontemporal)
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, true, CT, 8, MAXP, 2, 0, false>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pl.ph_ptr, A->pl.g0, A->pl.list_ptr, A->pl.lines, A->pl.col8));
-            else
-                hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, false, true, CT, 8, MAXP, 2>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st,
-                                   QH_ARGS(A->pl.ph_ptr, A->pl.g0, A->pl.list_ptr, A->pl.lines, A->pl.col8));
-            return;
-        }
+    if constexpr (MAXP == PHASE_PIECES_SMALL && sizeof(IT) == 1) {
+        if (xmode == 3) return launch_quadph_lists<VT, IT, B, CT, MAXP, 0>(A, A->pu.lists, X, Y, ld, true, lds, st);
+        if (xmode == 2) return launch_quadph_lists<VT, IT, B, CT, MAXP, 2>(A, A->pl.lists, X, Y, ld, true, lds, st);
     }
-    if constexpr (sizeof(VT) == 8 && CT == 32 && MAXP == 4 && sizeof(IT) == 1) {
+    if constexpr (sizeof(VT) == 8 && CT == 32 && MAXP == PHASE_PIECES_SMALL && sizeof(IT) == 1) {
         if (g_tune.ablate >= 1 && !xcol && !ycol) {   // measurement only
-#define QH_ABL(N) case N: hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, false, CT, 8, MAXP, 0, N>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st, \
-                           QH_ARGS(A->pb.ph_ptr, A->pb.g0, A->pb.list_ptr, A->pb.xrows, A->pb.col16)); break;
+#define QH_ABL(N) case N: hipLaunchKernelGGL((scs_spmmv_quadph<VT, IT, B, true, false, CT, PHASE_GROUPS, MAXP, 0, N>), dim3((unsigned)A->pb.n_tiles), dim3(256), lds, st, \
+                           QH_ARGS(A->pb.lists)); break;
             switch (g_tune.ablate) { QH_ABL(1) QH_ABL(2) QH_ABL(4) QH_ABL(8) QH_ABL(17) QH_ABL(14) QH_ABL(3) QH_ABL(19) QH_ABL(32) QH_ABL(64) QH_ABL(78) default: break; }
 #undef QH_ABL
             return;
         }
     }
-    if (g_tune.nontemporal) { if (ycol) QH_LAUNCH(true, true); else QH_LAUNCH(true, false); }
-    else { if (ycol) QH_LAUNCH(false, true); else QH_LAUNCH(false, false); }
-#undef QH_LAUNCH
-#undef QH_ARGS
+    if (xcol) launch_quadph_lists<VT, IT, B, CT, MAXP, 1>(A, A->pb.lists, X, Y, ld, ycol, lds, st);
+    else launch_quadph_lists<VT, IT, B, CT, MAXP, 0>(A, A->pb.lists, X, Y, ld, ycol, lds, st);
 }
+#undef QH_ARGS
 
 // false: the handle's phased plan does not fit the compiled shapes.  xmode: 0 = X row-major, 1 = column-major X assembled through
 // registers (measured slower, kept as "spmmv_xcol" 1), 2 = column-major X staged by 128-byte lines (needs the handle's line plan)
 template <typename VT, int B>
 bool launch_spmmv_quadph(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, int xmode, hipStream_t st) {
-    if (!A->pb.on || !A->pb.values || A->pb.ngp > 8 || !part_ok(A, 1)) return false;
+    if (!A->pb.on || !A->pb.values || A->pb.ngp > PHASE_GROUPS || !part_ok(A, 1)) return false;
     if (A->part && xmode != 0) return false;                   // (the two-part form runs on the row-major plan only)
     if (xmode == 3) {
-        if (!A->pu.on || !ycol || !A->pu.col8 || A->pu.max_rows > 256) return false;
-#define QU_C(CTV) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, 4>(A, X, Y, ld, ycol, 3, st)
+        if (!A->pu.on || !ycol || !A->pu.lists.idx || A->pu.lists.max_rows > PHASE_ROWS_IDX8) return false;
+#define QU_C(CTV) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, PHASE_PIECES_SMALL>(A, X, Y, ld, ycol, 3, st)
         if (A->C == 32) QU_C(32); else if (A->C == 64) QU_C(64); else if (A->C == 16) QU_C(16); else return false;
 #undef QU_C
         return true;
     }
     if (xmode == 2) {
         constexpr int VW = 16 / (int)sizeof(VT);
-        if (!A->pl.on || !ycol || !A->pl.col8 || A->pl.max_rows > 256 || ld % VW != 0 || ((uintptr_t)X % 16) != 0) return false;
-#define QL_C(CTV) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, 4>(A, X, Y, ld, ycol, 2, st)
+        if (!A->pl.on || !ycol || !A->pl.lists.idx || A->pl.lists.max_rows > PHASE_ROWS_IDX8 || ld % VW != 0 || ((uintptr_t)X % 16) != 0) return false;
+#define QL_C(CTV) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, PHASE_PIECES_SMALL>(A, X, Y, ld, ycol, 2, st)
         if (A->C == 32) QL_C(32); else if (A->C == 64) QL_C(64); else if (A->C == 16) QL_C(16); else return false;
 #undef QL_C
         return true;
     }
-    const int pieces = (A->pb.max_rows * 4 + 255) / 256;
-#define QH_C(CTV) do { if (pieces <= 4 && A->pb.idx8) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, 4>(A, X, Y, ld, ycol, xmode, st); \
-        else if (pieces <= 4) launch_spmmv_quadph_m<VT, unsigned short, B, CTV, 4>(A, X, Y, ld, ycol, xmode, st); \
-        else if (pieces <= 8) launch_spmmv_quadph_m<VT, unsigned short, B, CTV, 8>(A, X, Y, ld, ycol, xmode, st); else return false; } while (0)
+    const int pieces = phase_pieces(A->pb.lists.max_rows);
+    const bool idx8 = A->pb.lists.idx8();
+#define QH_C(CTV) do { if (pieces <= PHASE_PIECES_SMALL && idx8) launch_spmmv_quadph_m<VT, unsigned char, B, CTV, PHASE_PIECES_SMALL>(A, X, Y, ld, ycol, xmode, st); \
+        else if (pieces <= PHASE_PIECES_SMALL) launch_spmmv_quadph_m<VT, unsigned short, B, CTV, PHASE_PIECES_SMALL>(A, X, Y, ld, ycol, xmode, st); \
+        else if (pieces <= PHASE_PIECES_MAX) launch_spmmv_quadph_m<VT, unsigned short, B, CTV, PHASE_PIECES_MAX>(A, X, Y, ld, ycol, xmode, st); else return false; } while (0)
     if (A->C == 32) QH_C(32); else if (A->C == 64) QH_C(64); else if (A->C == 16) QH_C(16); else return false;
 #undef QH_C
     return true;

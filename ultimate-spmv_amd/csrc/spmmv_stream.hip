@@ -296,7 +296,7 @@ __global__ void __launch_bounds__(256, 3) scs_spmmv_pstream2(const PhDesc *__res
 
 template <typename VT, int B>
 bool launch_pstream(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol, hipStream_t st) {
-    if (!A->ps.desc || !A->ps.wg_ptr || A->ps.grid <= 0 || A->part || A->C != 32 || !A->pb.idx8 || A->pb.max_rows > 256 || A->pb.ngp > 8) return false;
+    if (!A->ps.desc || !A->ps.wg_ptr || A->ps.grid <= 0 || A->part || A->C != 32 || !A->pb.lists.idx8() || A->pb.lists.max_rows > PHASE_ROWS_IDX8 || A->pb.ngp > PHASE_GROUPS) return false;
     const size_t lds = 2 * 16384;
     A->last_kernel = 10;
     const bool per_tile = (int64_t)A->ps.grid == A->pb.n_tiles && A->ps.per_tile;
@@ -320,7 +320,7 @@ bool launch_pstream(const uspmv_dmat *A, const VT *X, VT *Y, long ld, bool ycol,
             (void)hipFree(d);
         }
     } clock_out{d_clock, A->ps.grid, st, clock_file};
-#define PS_ARGS (const PhDesc *)A->ps.desc, (const int *)A->ps.wg_ptr, (const VT *)A->pb.values, (const unsigned char *)A->pb.col16, (const int *)A->pb.xrows, X, Y, ld, \
+#define PS_ARGS (const PhDesc *)A->ps.desc, (const int *)A->ps.wg_ptr, (const VT *)A->pb.values, (const unsigned char *)A->pb.lists.idx, (const int *)A->pb.lists.list, X, Y, ld, \
                 (long)(A->n_chunks * A->C), (long)A->n_store, (const int *)A->bt.row_map, d_clock, per_tile ? g_tune.xcd_remap : 0
 #define PS_LAUNCH(NTV, YC, YN, AB) hipLaunchKernelGGL((scs_spmmv_pstream<VT, B, NTV, YC, YN, AB>), dim3((unsigned)A->ps.grid), dim3(256), lds, st, PS_ARGS)
     if constexpr (sizeof(VT) == 8) {
@@ -374,7 +374,7 @@ namespace uspmv_dev {
 // (the whole grid moves through the matrix as one front, like the one-tile-per-workgroup launch), its descriptors contiguous.
 int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu) {
     A->ps = {};
-    if (!A->pb.on || A->C != 32 || !A->pb.idx8 || A->pb.n_tiles <= 0 || wgs_per_cu <= 0) return USPMV_OK;
+    if (!A->pb.on || A->C != 32 || !A->pb.lists.idx8() || A->pb.n_tiles <= 0 || wgs_per_cu <= 0) return USPMV_OK;
     int dev = 0, cus = 0;
     HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -382,7 +382,7 @@ int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu) {
     const bool per_tile = wgs_per_cu >= 99 && nt <= INT32_MAX;          // one tile per workgroup: only the phases of a tile are pipelined
     const int G = per_tile ? (int)nt : (int)std::min<int64_t>((int64_t)std::max(cus, 1) * std::min(wgs_per_cu, 5), nt);
     std::vector<int32_t> php((size_t)nt + 1), slot((size_t)nt), wgp((size_t)G + 1, 0);
-    HIP_TRY(hipMemcpy(php.data(), A->pb.ph_ptr, 4 * ((size_t)nt + 1), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(php.data(), A->pb.lists.ph_ptr, 4 * ((size_t)nt + 1), hipMemcpyDeviceToHost));
     // workgroup w runs on XCD w % 8 (round-robin dispatch): with "spmmv_stream_xcd" the G / 8 workgroups of an XCD take CONSECUTIVE tiles of
     // every super-block of G tiles -- neighbouring tiles share most of their X rows, which then meet in one L2 -- otherwise tile t goes to
     // workgroup t % G
@@ -405,7 +405,7 @@ int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu) {
     if (e == hipSuccess) e = A->ps.desc.alloc(sizeof(PhDesc) * (size_t)pos);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(stream_desc_fill, dim3(grid_for(nt, 256)), dim3(256), 0, nullptr, (long)nt, (long)A->n_chunks, A->chunk_lengths,
-                           (const unsigned *)A->pb.c16_ptrs, (const int *)A->pb.ph_ptr, (const int *)A->pb.g0, (const int *)A->pb.list_ptr, (const int *)d_slot, (PhDesc *)A->ps.desc);
+                           (const unsigned *)A->pb.c16_ptrs, (const int *)A->pb.lists.ph_ptr, (const int *)A->pb.lists.g0, (const int *)A->pb.lists.list_ptr, (const int *)d_slot, (PhDesc *)A->ps.desc);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }

@@ -1,5 +1,6 @@
 // Shared declarations of the device half of libuspmv: the matrix handle, the tuning knobs, the
-// device helpers every kernel file uses and the launch entry points the C ABI (uspmv_api.hip) calls.
+// device helpers every kernel file uses and the launch entry points the C ABI calls (uspmv_api.hip: handles, tuning, SpMV / SpMMV / ap
+// entry points; tlc_planner.hip, block_planner.hip, sweep_planner.hip: the plans; stream_kernels.hip: the STREAM calibrators).
 // Kernels live in spmv_kernels.hip, spmmv_kernels.hip, ap_kernels.hip, ap_spmmv_kernels.hip (ap[dp_sp] on block vectors: dispatch and
 // the row-major gather kernel) and ap_hp_spmmv_kernels.hip (the lane-per-row and staged block kernels of every ap kind).
 #pragma once
@@ -87,9 +88,31 @@ class PinnedBuf {
     void *p_ = nullptr;
 };
 
+namespace uspmv_dev {
+// The shapes of a phased block plan the SpMMV kernels are compiled for: what block_planner.hip plans within, what the device builder
+// (block_plan_kernels.hip) is asked for and what spmmv_phased.hip / spmmv_stream.hip dispatch on.
+constexpr int PHASE_ROWS_IDX8 = 256;       // most list entries of a phase that one-byte phase-local indices address
+constexpr int PHASE_GROUPS = 8;            // most groups of four slots per phase
+constexpr int PHASE_PIECES_SMALL = 4, PHASE_PIECES_MAX = 8;   // LDS pieces of 64 X rows the phased kernel exists for
+inline int phase_pieces(int max_rows) { return (max_rows * 4 + 255) / 256; }
+
+// The phase lists of a phased block plan -- what uspmv_dmat's phased, line and unscrambled plans each carry one of.  Tile t runs the
+// phases ph_ptr[t] .. ph_ptr[t + 1]; phase p starts at group g0[p] of its chunks and lists list[list_ptr[p] .. list_ptr[p + 1]): X rows,
+// or lines of X rows.  idx: per entry of the matrix the position in its phase's list, laid out like the plan's values.
+struct PhaseLists {
+    DeviceBuf<int32_t> ph_ptr, g0, list_ptr, list;
+    DeviceBuf<void> idx;
+    int idx_bytes = 2;                     // of an element of idx: 1 (no phase lists more than PHASE_ROWS_IDX8 entries) or 2
+    int max_rows = 0;                      // X rows of the fullest phase
+    int64_t n_phases = 0, rows_staged = 0;
+    bool idx8() const { return idx_bytes == 1; }
+};
+}  // namespace uspmv_dev
+
 // The device matrix.  Every plan family is one member struct holding its device arrays and metadata; `on` says the plan is installed,
 // and assigning {} to the member releases the plan and resets every field of it.
 struct uspmv_dmat {
+    using PhaseLists = uspmv_dev::PhaseLists;
     uspmv_dmat() = default;
     uspmv_dmat(const uspmv_dmat &) = delete;
     uspmv_dmat &operator=(const uspmv_dmat &) = delete;
@@ -186,13 +209,11 @@ struct uspmv_dmat {
     // phased block plan (uspmv_build_phased_plan; 64-byte X rows): per tile a run of phases, each with its own X-row list
     struct PhasedPlan {
         bool on = false;
-        int cap_rows = 0, ngp = 0, max_rows = 0;
-        int64_t n_tiles = 0, n_phases = 0, rows_staged = 0;
-        DeviceBuf<int32_t> ph_ptr, g0, list_ptr, xrows;
-        DeviceBuf<void> values;             // the entries again, GROUP-major like col16 ([chunk][group of four slots][row][slot % 4])
+        int cap_rows = 0, ngp = 0;
+        int64_t n_tiles = 0;
+        PhaseLists lists;                   // X rows
+        DeviceBuf<void> values;             // the entries again, GROUP-major like the indices ([chunk][group of four slots][row][slot % 4])
         DeviceBuf<uint32_t> c16_ptrs;
-        DeviceBuf<uint16_t> col16;          // phase-local indices; ONE BYTE each when idx8 (no phase lists more than 256 rows)
-        bool idx8 = false;
         bool device_built = false;          // the plan's index part was built by csrc/block_plan_kernels.hip
     } pb;
     // the phased plan once more as a flat schedule of 32-byte phase descriptors for persistent workgroups (spmmv_stream.hip; "spmmv_stream")
@@ -207,10 +228,8 @@ struct uspmv_dmat {
     // shares pb.values / pb.c16_ptrs / the row map; one-byte local indices (line << shift | row in line)
     struct LinePlan {
         bool on = false;
-        int shift = 0, max_rows = 0;
-        int64_t n_phases = 0, rows_staged = 0;
-        DeviceBuf<int32_t> ph_ptr, g0, list_ptr, lines;
-        DeviceBuf<uint8_t> col8;
+        int shift = 0;
+        PhaseLists lists;                   // X lines
     } pl;
     // ... and once more for column-major block vectors behind the re-layout pass, with the X rows numbered in the ORIGINAL row order:
     // the pass that turns the caller's column-major X into the row-major workspace also undoes the sigma permutation
@@ -218,10 +237,9 @@ struct uspmv_dmat {
     // workspace holds two rows the tile needs instead of 1.1 (shares pb.values / pb.c16_ptrs / the row map)
     struct UnscrambledPlan {
         bool on = false;
-        int max_rows = 0;
-        int64_t n_phases = 0, n_perm = 0;
-        DeviceBuf<int32_t> ph_ptr, g0, list_ptr, xrows, perm;
-        DeviceBuf<uint8_t> col8;
+        int64_t n_perm = 0;
+        PhaseLists lists;                   // X rows in original numbering; one-byte local indices
+        DeviceBuf<int32_t> perm;
     } pu;
     // block-vector column-window sweep plan (uspmv_build_block_sweep_plan, csrc/spmmv_sweep.hip): 64-byte X rows, windows of 2^wlog X rows,
     // per tile the list of windows its rows touch
@@ -404,12 +422,18 @@ int check_dmat_one_prec(const uspmv_dmat *A, const char *who);   // uspmv_api.hi
 int check_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const char *who);   // tlc_planner.hip
 // 16-bit index offsets per chunk from the chunk lengths (O(n_chunks) on the host); false: too large for 32-bit offsets
 bool c16_offsets(const std::vector<int32_t> &cl, int64_t C, std::vector<uint32_t> *c16p, int64_t *tot16);   // tlc_planner.hip
-// the column-window sweep plan from host structs / from the handles' device arrays (uspmv_api.hip); wlog, tile_rows 0: defaults
+// the column-window sweep plan from host structs / from the handles' device arrays (sweep_planner.hip); wlog, tile_rows 0: defaults
 // (parts: the one struct, or the parts of an ap split sharing the plan, see uspmv_dmat::SweepPlan)
 int sweep_plan_install(uspmv_dmat *const parts[], const uspmv_scs *const ss[], int n_parts, int wlog, int tile_rows, int64_t *n_tiles,
                        int64_t *n_sweep, const char *who);
 int sweep_plan_install_device(uspmv_dmat *const parts[], int n_parts, int wlog, int tile_rows, int64_t *n_tiles, int64_t *n_sweep,
                               const char *who);
+// what a sweep plan -- of vectors or of block vectors -- is built with when the caller and the tuning table leave it open (sweep_planner.hip):
+// rows per tile for n_pad padded rows, and the most staged bytes per non-zero at which a tile still sweeps
+int sweep_default_tile_rows(int64_t n_pad);
+double sweep_max_stage();
+// FNV-1a digest of a device array (sweep_planner.hip; the plan digests the tests compare host and device builders by)
+int device_fnv(const void *d, size_t bytes, uint64_t *out);
 constexpr size_t WG_LDS_BYTES = 160 * 1024;   // all the LDS a gfx950 workgroup can have: what a sweep kernel's window buffer(s) and the staged block kernel's tile must fit
 // threads per workgroup of every sweep kernel: 1 024 (or the tile, if smaller) unless "sweep_threads" asks for fewer -- a lane then owns
 // tile_rows / threads rows, at most 4
@@ -570,8 +594,8 @@ inline void block_plan_reset(uspmv_dmat *A) {
     A->bt = {}; A->pb = {}; A->ps = {}; A->pl = {}; A->pu = {};
     A->part_len[1][0].reset(); A->part_len[1][1].reset();
 }
-// two-part SpMMV (uspmv_dmat::part_len): order 0 from per-chunk flags (1 = the chunk touches a halo column), order 1 from the lists of the
-// handle's phased plan (no-op without one); the arrays belong to the handle (order 1 goes with the plan)
+// two-part SpMMV (uspmv_dmat::part_len; block_planner.hip): order 0 from per-chunk flags (1 = the chunk touches a halo column), order 1 from
+// the lists of the handle's phased plan (no-op without one); the arrays belong to the handle (order 1 goes with the plan)
 int dmat_part_set_chunks(uspmv_dmat *A, const unsigned char *h_chunk_flags);
 int dmat_part_set_plan(uspmv_dmat *A, long n_local, int64_t *n_boundary_tiles);
 int launch_block_phase_plan(const uspmv_dmat *A, bool write, int cap, int ngp, const int *d_row_map, const unsigned *d_c16_ptrs, int *d_t_phases,

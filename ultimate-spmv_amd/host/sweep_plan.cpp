@@ -71,7 +71,7 @@ int uspmv_build_sweep_plan(const uspmv_scs *const ss[], int ns, int wlog, int ti
     if (ns < 1 || ns > 3) return USPMV_OK;
     const uspmv_scs *const s = ss[0];
     const int64_t C = s->C, nc = s->n_chunks;
-    if (tile_rows != 256 && tile_rows != 512 && tile_rows != 1024 && tile_rows != 2048 && tile_rows != 4096) tile_rows = 1024;
+    tile_rows = uspmv_sweep_tile_rows(tile_rows, /*blocks=*/false);
     if (C < 1 || C > 64 || 64 % C != 0 || nc < 1) return USPMV_OK;          // a wave covers whole chunks
     if (s->dtype == USPMV_F16) return USPMV_OK;                              // (x has the first part's type)
     for (int w = 1; w < ns; ++w) if (ss[w]->C != C || ss[w]->n_chunks != nc) return USPMV_OK;
@@ -122,9 +122,7 @@ int uspmv_build_sweep_plan(const uspmv_scs *const ss[], int ns, int wlog, int ti
             }
             if (!good || hi < 0) continue;
             const int64_t nS = (int64_t)hi - lo + 1;
-            // staging cost: every window is copied once per tile
-            if ((double)nS * (double)((int64_t)1 << wlog) * (double)vsz > max_stage_bytes_per_nnz * (double)std::max<int64_t>(nnz_t, 1)) continue;
-            if (nS > 4096) continue;
+            if (!uspmv_sweep_tile_ok(nS, wlog, vsz, nnz_t, max_stage_bytes_per_nnz)) continue;
             ok[(size_t)t] = 1; smin[(size_t)t] = lo; S[(size_t)t] = (int32_t)nS;
         }
 #pragma omp critical
@@ -235,7 +233,7 @@ int uspmv_build_block_sweep_plan(const uspmv_scs *s, int wlog, int tile_rows, in
                                  uspmv_block_sweep_plan *p) {
     p->valid = false;
     const int64_t C = s->C, nc = s->n_chunks;
-    if (tile_rows != 1024 && tile_rows != 2048 && tile_rows != 4096) tile_rows = 2048;
+    tile_rows = uspmv_sweep_tile_rows(tile_rows, /*blocks=*/true);
     if (C < 1 || C > 64 || 64 % C != 0 || nc < 1) return USPMV_OK;          // a wave covers whole chunks
     if (wlog < 6 || wlog > 12) return USPMV_OK;
     if (s->n_elements > (int64_t)UINT32_MAX) return USPMV_OK;
@@ -284,9 +282,7 @@ int uspmv_build_block_sweep_plan(const uspmv_scs *s, int wlog, int tile_rows, in
             if (!good) continue;
             std::sort(seen.begin(), seen.end());
             seen.erase(std::unique(seen.begin(), seen.end()), seen.end());
-            // staging cost: every touched window is copied once per tile
-            if ((double)seen.size() * (double)((int64_t)1 << wlog) * (double)row_bytes > max_stage_bytes_per_nnz * (double)std::max<int64_t>(nnz_t, 1)) continue;
-            if (seen.size() > 4096) continue;
+            if (!uspmv_sweep_tile_ok((int64_t)seen.size(), wlog, (size_t)row_bytes, nnz_t, max_stage_bytes_per_nnz)) continue;   // (the windows it touches)
             ok[(size_t)t] = 1;
             twins[(size_t)t] = seen;
         }

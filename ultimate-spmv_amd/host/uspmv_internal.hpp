@@ -1,6 +1,7 @@
 // Internal definitions shared by the host data layer and the HIP C-ABI layer of libuspmv.so.
 #pragma once
 #include <sys/mman.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdarg>
 #include <cstdint>
@@ -168,6 +169,20 @@ struct uspmv_sweep_plan {
     part_t part[3];
     std::vector<int32_t> rest_chunks;             // chunks of the tiles that do not sweep (gather kernel)
 };
+// Two rules that the host builders below and the device builder (csrc/sweep_planner.hip: sweep_plan_install_device) share; the tests
+// hold host- and device-built plans to the same bits.
+// Rows per tile: a value outside the builder's set becomes its default -- 256 | 512 | 1024 | 2048 | 4096, else 1024, for the plan over
+// vectors; 1024 | 2048 | 4096, else 2048, for the plan over block vectors (blocks).
+inline int uspmv_sweep_tile_rows(int tile_rows, bool blocks) {
+    const bool in_set = tile_rows == 1024 || tile_rows == 2048 || tile_rows == 4096 || (!blocks && (tile_rows == 256 || tile_rows == 512));
+    return in_set ? tile_rows : blocks ? 2048 : 1024;
+}
+// Does this tile sweep: each of its n_windows windows of 2^wlog units (x elements, or X rows) of unit_bytes is copied once per tile, which
+// may cost at most max_stage_bytes_per_nnz for each of the tile's nnz entries; and a tile has at most 4 096 windows.
+inline bool uspmv_sweep_tile_ok(int64_t n_windows, int wlog, size_t unit_bytes, int64_t nnz, double max_stage_bytes_per_nnz) {
+    return (double)n_windows * (double)((int64_t)1 << wlog) * (double)unit_bytes <= max_stage_bytes_per_nnz * (double)std::max<int64_t>(nnz, 1) &&
+           n_windows <= 4096;
+}
 // parts: one to three structs with one row layout (one struct; ap[dp_sp]: F64, F32; with an fp16 part: F64 | F32, [F32,] F16)
 int uspmv_build_sweep_plan(const uspmv_scs *const parts[], int n_parts, int wlog, int tile_rows, double max_stage_bytes_per_nnz,
                            uspmv_sweep_plan *plan);   // host/sweep_plan.cpp

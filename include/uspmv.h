@@ -478,6 +478,17 @@ int uspmv_spmv_ap_generic(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const 
  *   ap[sp_hp]     (hi F32, no mid): x, y float; every product sp_v * x and (float)hp_v * x rounded to float, then added to a double
  *                 accumulator per part; y = (float)(sp + hp) */
 int uspmv_spmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, void *d_y, void *stream);
+/* uspmv_spmv_ap_hp restricted to a subset of the rows, for the distributed step of the kinds with an fp16 part (uspmv_dist_create_ap_hp_from_coo):
+ * the twins of uspmv_spmv_ap_tiles / _chunks.  Handles as for uspmv_spmv_ap_hp (mid NULL for the two-part kinds), x and y in the type of the hi
+ * part.  Every row written carries the bits uspmv_spmv_ap_hp gives it, rows outside the list are not touched.  Entries < 0 are skipped (a
+ * conditional list); n_ids == 0 is USPMV_OK and launches nothing.
+ * _tiles: the tiles of the parts' shared tile-local-column plan (tile t = rows [t * tile_rows, (t + 1) * tile_rows)); parts without one are
+ *   refused ("no shared tile-local-column plan").  x must be 16-byte aligned, n_ids at most the number of tiles.
+ * _chunks: chunk ids, lane per row, any such handles. */
+int uspmv_spmv_ap_hp_tiles(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const int32_t *d_tile_ids, int64_t n_ids,
+                           const void *d_x, void *d_y, void *stream);
+int uspmv_spmv_ap_hp_chunks(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const int32_t *d_chunk_ids, int64_t n_ids,
+                            const void *d_x, void *d_y, void *stream);
 /* Adaptive precision with an fp16 part on block vectors: b right-hand sides, X and Y in the type of the hi part (double for ap[dp_hp] and
  * ap[dp_sp_hp], float for ap[sp_hp]), handles as for uspmv_spmv_ap_hp, layouts and ld as uspmv_spmmv / uspmv_spmmv_ap (column-major
  * X[col + v*ld] with ld >= n_rows_padded, row-major X[col*b + v]).  The reference has no such path.  For every C, both layouts and every
@@ -611,6 +622,10 @@ int uspmv_halo_discover(uspmv_scs_t *local_scs, const int32_t *wsa, int rank, in
  * col_idxs followed by the sp struct's (first-seen scan in that order), both structs' columns rewritten against that one numbering.
  * The structs must share C, n_chunks and the row layout (sp converted with dp's permutation). */
 int uspmv_halo_discover_ap(uspmv_scs_t *dp, uspmv_scs_t *sp, const int32_t *wsa, int rank, int P, uspmv_halo_t **out);
+/* ... and for the two or three structs of a split with an fp16 part (mid NULL for ap[dp_hp] and ap[sp_hp]): ONE halo, the first-seen scan over
+ * hi's col_idxs, then mid's, then hp's; all structs' columns rewritten against that one numbering.  Refusals as above: the structs must share
+ * C, n_chunks and the row layout, no struct may appear twice, and nothing is rewritten when the call is refused. */
+int uspmv_halo_discover_ap_hp(uspmv_scs_t *hi, uspmv_scs_t *mid, uspmv_scs_t *hp, const int32_t *wsa, int rank, int P, uspmv_halo_t **out);
 /* n_halo = recv_counts_cumsum.back(); recv_counts_cumsum[P+1]; recv_idxs grouped by owner rank
  * ascending with recv_counts[P] entries each (borrowed pointers). */
 int uspmv_halo_meta(const uspmv_halo_t *h, int64_t *n_halo, const int32_t **recv_counts_cumsum,
@@ -741,6 +756,22 @@ int uspmv_dist_create_ap_from_coo(const void *comm_id, int comm_rank, int comm_s
 int uspmv_dist_create_ap_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
                                      const int32_t *wsa, int64_t C, int64_t sigma, double threshold_1, int tlc,
                                      const uspmv_dist_options_t *opt, uspmv_dist_t **out);
+/* ... for the kinds with an fp16 part: kind USPMV_AP_DP_HP, USPMV_AP_SP_HP or USPMV_AP_DP_SP_HP (USPMV_AP_DP_SP is refused: that object is
+ * made by uspmv_dist_create_ap_from_coo).  uspmv_partition_precisions_hp of the block -> convert the hi part (F32 for ap[sp_hp], else F64) ->
+ * the mid and hp parts with hi's permutation -> uspmv_halo_discover_ap_hp -> column permutation of all parts -> upload -> with tlc the
+ * parts' shared line plan at 256-row tiles, as built (no timing, no sweep plan; dropped for chunk lists when it stages nothing) -> tile
+ * classes from all parts -> the object.  A block whose conversion the host route refuses ("fixed_permutation maps a non-empty row onto a
+ * padded slot") fails the call with that text.  Vectors are in the type of the hi part: float for ap[sp_hp] (pack, exchange, padding
+ * guard and self-check then work on floats), double otherwise.  The step is uspmv_spmv_ap_hp split into interior and boundary tiles
+ * (uspmv_spmv_ap_hp_tiles / _chunks) in the overlap, plain and "pad_split" forms ("pad_split" defaults to 1), eager or captured, over every
+ * exchange.  "fused_step" 1, "autotune_all" 1, "block_plan" b > 0, uspmv_dist_spmmv and uspmv_dist_spmmv_ap answer USPMV_ERR_UNSUPPORTED
+ * with the kind's name: block vectors for these kinds do not run across ranks yet. */
+int uspmv_dist_create_ap_hp_from_coo(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                     const int32_t *wsa, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2, int tlc,
+                                     uspmv_dist_t **out);
+int uspmv_dist_create_ap_hp_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                        const int32_t *wsa, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2, int tlc,
+                                        const uspmv_dist_options_t *opt, uspmv_dist_t **out);
 /* the exchange plan of the object (borrowed): n_send, send_off[P+1], send_idxs[n_send], recv_off[P+1] as in uspmv_comm_plan_meta */
 int uspmv_dist_comm_plan(const uspmv_dist_t *d, int64_t *n_send, const int64_t **send_off, const int32_t **send_idxs,
                          const int64_t **recv_off);
@@ -759,7 +790,8 @@ int uspmv_dist_comm_plan(const uspmv_dist_t *d, int64_t *n_send, const int64_t *
  * "diag_spmmv_part" 0|1|2 (diagnosis only: the two-part block-vector step runs both parts, its interior part, its boundary part),
  * "block_plan" b (block vectors: build the phased block plan for b columns on the rank's matrix, 0 drops it; see uspmv_dist_spmmv).
  * On an ap[dp_sp] object (uspmv_dist_create_ap_from_coo) "fused_step" 1, "autotune_all" 1 and "block_plan" b > 0 answer
- * USPMV_ERR_UNSUPPORTED; uspmv_dist_autotune times overlap | plain there and leaves "pad_split" as it is. */
+ * USPMV_ERR_UNSUPPORTED; uspmv_dist_autotune times overlap | plain there and leaves "pad_split" as it is.  The same holds for an object
+ * of a kind with an fp16 part (uspmv_dist_create_ap_hp_from_coo), whose "pad_split" defaults to 1 as well. */
 int uspmv_dist_set_option(uspmv_dist_t *d, const char *key, int value);
 /* How the single-vector step is arranged around the exchange: interior tiles during the exchange and boundary tiles after it | the
  * exchange, then the whole matrix (the reference's order) | overlap with the padding-only tiles in front of the exchange ("pad_split") |
@@ -786,6 +818,13 @@ int uspmv_dist_check_reference(const uspmv_coo_t *local, const int32_t *wsa, int
  * with |v| >= threshold_1 and the sp chain over the others with the value (double)(float)v, each an FMA chain in entry order from +0.0
  * (scs_ap_impl_cpu, code/ap_kernels.hpp:24-82), y_ref[i] = dp + sp (double). */
 int uspmv_dist_check_reference_ap(const uspmv_coo_t *local, const int32_t *wsa, int rank, int P, double threshold_1, double *y_ref);
+/* ... for an object of a kind with an fp16 part (uspmv_dist_check applies it there).  The entries are classified exactly as
+ * uspmv_partition_precisions_hp classifies them (hp values rounded once to binary16), and the numerics are those of uspmv_spmv_ap_hp.
+ * USPMV_AP_DP_HP / USPMV_AP_DP_SP_HP: one FMA chain per part in entry order from +0.0, y_ref[i] = hi + hp resp. (hi + mid) + hp (double).
+ * USPMV_AP_SP_HP: x converted to float, every product rounded to float and then added to the part's double accumulator,
+ * y_ref[i] = (float)(sp + hp) (float). */
+int uspmv_dist_check_reference_ap_hp(const uspmv_coo_t *local, const int32_t *wsa, int rank, int P, int kind, double threshold_1,
+                                     double threshold_2, void *y_ref);
 /* HIP / RCCL versions this library was COMPILED against and the ones it RUNS on in this process:
  * v[0] HIP_VERSION (build), v[1] hipRuntimeGetVersion, v[2] NCCL_VERSION_CODE (build), v[3] ncclGetVersion. */
 int uspmv_runtime_versions(int v[4]);
@@ -803,6 +842,11 @@ int uspmv_dist_parts(const uspmv_dist_t *d, const uspmv_scs_t **scs, const uspmv
  * the sp ones are NULL on a one-precision object */
 int uspmv_dist_parts_ap(const uspmv_dist_t *d, const uspmv_scs_t **scs_dp, const uspmv_scs_t **scs_sp, const uspmv_dmat_t **A_dp,
                         const uspmv_dmat_t **A_sp, const uspmv_halo_t **halo);
+/* uspmv_dist_parts of an object of a kind with an fp16 part: its kind, the structs, the handles (mid NULL for the two-part kinds) and
+ * the one halo.  uspmv_dist_parts answers such an object with the hi ones, uspmv_dist_parts_ap with USPMV_ERR_INVALID; any other object
+ * is refused here. */
+int uspmv_dist_parts_ap_hp(const uspmv_dist_t *d, int *kind, const uspmv_scs_t **scs_hi, const uspmv_scs_t **scs_mid, const uspmv_scs_t **scs_hp,
+                           const uspmv_dmat_t **A_hi, const uspmv_dmat_t **A_mid, const uspmv_dmat_t **A_hp, const uspmv_halo_t **halo);
 int uspmv_dist_set_overlap(uspmv_dist_t *d, int overlap);
 /* -no_pack 1 of the reference (code/classes_structs.hpp:941): no element is packed (pushed), every exchange of the object ships a
  * stale buffer (timing only) */

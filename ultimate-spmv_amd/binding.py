@@ -187,6 +187,16 @@ _SIGS = {
     "uspmv_dist_create_ap_from_coo": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _i64, C.c_double, C.c_int, C.POINTER(_vp)]),
     "uspmv_dist_create_ap_from_coo_ex": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _i64, C.c_double, C.c_int, _vp,
                                                   C.POINTER(_vp)]),
+    "uspmv_spmv_ap_hp_tiles": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "uspmv_spmv_ap_hp_chunks": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "uspmv_halo_discover_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "uspmv_dist_check_reference_ap_hp": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),
+    "uspmv_dist_create_ap_hp_from_coo": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _i64, C.c_int, C.c_double, C.c_double,
+                                                  C.c_int, C.POINTER(_vp)]),
+    "uspmv_dist_create_ap_hp_from_coo_ex": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _i64, C.c_int, C.c_double, C.c_double,
+                                                     C.c_int, _vp, C.POINTER(_vp)]),
+    "uspmv_dist_parts_ap_hp": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                        C.POINTER(_vp), C.POINTER(_vp)]),
     "uspmv_dist_set_overlap": (C.c_int, [_vp, C.c_int]),
     "uspmv_dist_set_no_pack": (C.c_int, [_vp, C.c_int]),
     "uspmv_dist_spmv": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
@@ -642,6 +652,17 @@ def dist_check_reference_ap(local, wsa, rank, P, threshold_1):
     return y
 
 
+def dist_check_reference_ap_hp(local, wsa, rank, P, kind, threshold_1, threshold_2=0.0):
+    """the same for an object of a kind with an fp16 part (kind: AP_* or "dp_hp" | "sp_hp" | "dp_sp_hp"): the parts of partition_precisions_hp, the
+    numerics of spmv_ap_hp; float32 for sp_hp, else float64 (uspmv_dist_check_reference_ap_hp)"""
+    k = _AP_KINDS.get(kind, kind)
+    w = np.ascontiguousarray(wsa, np.int32)
+    y = np.zeros(local.n_rows, np.float32 if k == AP_SP_HP else np.float64)
+    _ck(lib().uspmv_dist_check_reference_ap_hp(local.h, w.ctypes.data_as(_i32p), int(rank), int(P), int(k), float(threshold_1), float(threshold_2),
+                                               y.ctypes.data_as(_vp)))
+    return y
+
+
 def runtime_versions():
     """(HIP build, HIP runtime, RCCL build, RCCL runtime) version codes of libuspmv.so in this process"""
     v = (C.c_int * 4)()
@@ -655,8 +676,8 @@ class DistNative:
     hipGraphLaunch per step) works in processes bound to the system's RCCL (the uspmv CLI); under torch's bundled RCCL / HIP runtime
     the capture of an RCCL group crashes in hipStreamEndCapture, so it is off by default here."""
 
-    def __init__(self, local_coo, wsa, C_, sigma, rank, P, comm_id=None, comm_rank=None, comm_size=None, dtype=F64, tlc=True,
-                 hostcomm=None, host_exchange=False, exchange=None, ap_threshold=None):
+    def __init__(self, local_coo, wsa, C_, sigma, rank, P, comm_id=None, comm_rank=None, comm_size=None, dtype=None, tlc=True,
+                 hostcomm=None, host_exchange=False, exchange=None, ap_threshold=None, ap_kind=None, ap_threshold_2=0.0):
         """hostcomm: a HostComm that carries the set-up exchanges (default: the RCCL communicator made from comm_id);
         host_exchange=True additionally stages the per-step halo exchange through it (USPMV_EXCHANGE_HOST: no RCCL communicator,
         P processes may share one GPU).  exchange="rccl" | "host" | "peer" names the per-step exchange instead (host_exchange=True is
@@ -665,12 +686,29 @@ class DistNative:
         in their environment before the HIP runtime starts.
         ap_threshold: a float makes the adaptive-precision ap[dp_sp] object (uspmv_dist_create_ap_from_coo_ex: entries with
         |v| >= ap_threshold in double, the others in float, vectors double); dtype must then be F64.  scs / A_sp_handle: self.scs is the
-        dp struct, self.scs_sp the sp struct."""
+        dp struct, self.scs_sp the sp struct.
+        ap_kind: "dp_hp" | "sp_hp" | "dp_sp_hp" with ap_threshold (and ap_threshold_2 for dp_sp_hp) makes the object of a kind with an fp16
+        part (uspmv_dist_create_ap_hp_from_coo_ex); dtype is derived from the kind (F32 for sp_hp, else F64), a dtype that contradicts it is
+        a ValueError.  self.scs is then the hi struct, self.scs_mid (None for the two-part kinds) and self.scs_hp the others; ap_threshold
+        alone keeps meaning ap[dp_sp]."""
         import torch
         self.rank, self.P = rank, P
         self.ap_threshold = None if ap_threshold is None else float(ap_threshold)
-        if self.ap_threshold is not None and dtype != F64:
+        self.ap_kind = None if ap_kind in (None, "dp_sp") else ap_kind
+        self.ap_threshold_2 = float(ap_threshold_2)
+        if self.ap_kind is not None:
+            if self.ap_kind not in ("dp_hp", "sp_hp", "dp_sp_hp"):
+                raise ValueError(f"ap_kind={ap_kind!r}: one of 'dp_sp', 'dp_hp', 'sp_hp', 'dp_sp_hp'")
+            if self.ap_threshold is None:
+                raise ValueError("ap_kind needs ap_threshold")
+            want = F32 if self.ap_kind == "sp_hp" else F64
+            if dtype is not None and dtype != want:
+                raise ValueError(f"ap[{self.ap_kind}] runs on {'float' if want == F32 else 'double'} vectors: dtype contradicts the kind")
+            dtype = want
+        elif self.ap_threshold is not None and dtype not in (None, F64):
             raise ValueError("ap_threshold selects the ap[dp_sp] object, whose vectors are double: dtype must be F64")
+        if dtype is None:
+            dtype = F64
         wsa = np.ascontiguousarray(wsa, np.int32)
         self._wsa = wsa
         h = _vp()
@@ -691,7 +729,10 @@ class DistNative:
             self._opt = DistOptions(None, ex)      # no transport: loopback (the library refuses real ranks without one)
             opt = C.byref(self._opt)
         cr, cs = rank if comm_rank is None else comm_rank, P if comm_size is None else comm_size
-        if self.ap_threshold is not None:
+        if self.ap_kind is not None:
+            _ck(lib().uspmv_dist_create_ap_hp_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, _AP_KINDS[self.ap_kind],
+                                                          self.ap_threshold, self.ap_threshold_2, int(bool(tlc)), opt, C.byref(h)))
+        elif self.ap_threshold is not None:
             _ck(lib().uspmv_dist_create_ap_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, self.ap_threshold,
                                                        int(bool(tlc)), opt, C.byref(h)))
         else:
@@ -705,7 +746,14 @@ class DistNative:
         self.scs = _BorrowedScs(s, self)
         self._A = a
         self.scs_sp, self._A_sp = None, None
-        if self.ap_threshold is not None:
+        self.scs_mid, self.scs_hp, self._A_mid, self._A_hp = None, None, None, None
+        if self.ap_kind is not None:
+            k, sm, sq, am, aq = C.c_int(-1), _vp(), _vp(), _vp(), _vp()
+            _ck(lib().uspmv_dist_parts_ap_hp(h, C.byref(k), None, C.byref(sm), C.byref(sq), None, C.byref(am), C.byref(aq), None))
+            assert k.value == _AP_KINDS[self.ap_kind]
+            self.scs_mid, self._A_mid = (_BorrowedScs(sm, self), am) if sm.value else (None, None)
+            self.scs_hp, self._A_hp = _BorrowedScs(sq, self), aq
+        elif self.ap_threshold is not None:
             s2, a2 = _vp(), _vp()
             _ck(lib().uspmv_dist_parts_ap(h, None, C.byref(s2), None, C.byref(a2), None))
             self.scs_sp, self._A_sp = _BorrowedScs(s2, self), a2
@@ -850,7 +898,7 @@ class DistNative:
 
     def close(self):
         if getattr(self, "h", None) and _LIB is not None:
-            self.scs = self.scs_sp = None
+            self.scs = self.scs_sp = self.scs_mid = self.scs_hp = None
             _LIB.uspmv_dist_free(self.h)
             self.h = None
 
@@ -861,11 +909,14 @@ class DistNative:
 class HaloPlan:
     """Result of collect_local_needed_heri on one rank (code/mpi_funcs.hpp:242-415)."""
 
-    def __init__(self, scs, wsa, rank, P, scs_sp=None):
-        """scs_sp: the sp struct of an ap[dp_sp] pair -- one halo for both (uspmv_halo_discover_ap), both structs' columns rewritten"""
+    def __init__(self, scs, wsa, rank, P, scs_sp=None, scs_hp=None):
+        """scs_sp: the sp struct of an ap[dp_sp] pair -- one halo for both (uspmv_halo_discover_ap), both structs' columns rewritten.
+        scs_hp: the hp struct of a split with an fp16 part -- scs the hi struct, scs_sp the mid struct or None (uspmv_halo_discover_ap_hp)"""
         wsa = np.ascontiguousarray(wsa, np.int32)
         h = _vp()
-        if scs_sp is not None:
+        if scs_hp is not None:
+            _ck(lib().uspmv_halo_discover_ap_hp(scs.h, scs_sp.h if scs_sp is not None else None, scs_hp.h, _np_ptr(wsa), rank, P, C.byref(h)))
+        elif scs_sp is not None:
             _ck(lib().uspmv_halo_discover_ap(scs.h, scs_sp.h, _np_ptr(wsa), rank, P, C.byref(h)))
         else:
             _ck(lib().uspmv_halo_discover(scs.h, _np_ptr(wsa), rank, P, C.byref(h)))
@@ -892,6 +943,12 @@ class HaloPlan:
 def halo_discover_ap(scs_dp, scs_sp, wsa, rank, P):
     """HaloPlan of an ap[dp_sp] pair: the first-seen scan over the dp struct's columns, then the sp struct's (uspmv_halo_discover_ap)"""
     return HaloPlan(scs_dp, wsa, rank, P, scs_sp=scs_sp)
+
+
+def halo_discover_ap_hp(scs_hi, scs_mid, scs_hp, wsa, rank, P):
+    """HaloPlan of a split with an fp16 part: the first-seen scan over the hi struct's columns, then the mid struct's (None for the two-part
+    kinds), then the hp struct's (uspmv_halo_discover_ap_hp)"""
+    return HaloPlan(scs_hi, wsa, rank, P, scs_sp=scs_mid, scs_hp=scs_hp)
 
 
 # ---------------------------------------------------------------------------------------- device
@@ -1400,6 +1457,20 @@ def spmv_ap_hp(A_hi, A_mid, A_hp, x, y, stream=None):
     the two-part kinds."""
     assert x.dtype == A_hi.torch_dtype and y.dtype == A_hi.torch_dtype and y.numel() >= A_hi.n_rows_padded
     _ck(lib().uspmv_spmv_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(x), _dp(y), _stream_ptr(stream)))
+    return y
+
+
+def spmv_ap_hp_tiles(A_hi, A_mid, A_hp, tile_ids, x, y, stream=None):
+    """the tiles in tile_ids (int32 tensor; entries < 0 skipped) of the parts' shared plan (uspmv_spmv_ap_hp_tiles)"""
+    _ck(lib().uspmv_spmv_ap_hp_tiles(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(tile_ids), tile_ids.numel(), _dp(x), _dp(y),
+                                     _stream_ptr(stream)))
+    return y
+
+
+def spmv_ap_hp_chunks(A_hi, A_mid, A_hp, chunk_ids, x, y, stream=None):
+    """the chunks in chunk_ids (int32 tensor; entries < 0 skipped), lane per row (uspmv_spmv_ap_hp_chunks)"""
+    _ck(lib().uspmv_spmv_ap_hp_chunks(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(chunk_ids), chunk_ids.numel(), _dp(x), _dp(y),
+                                      _stream_ptr(stream)))
     return y
 
 

@@ -268,15 +268,20 @@ __device__ __forceinline__ double gather_chain(const VT *__restrict__ vp, const 
 
 // Tile-local-column form: the tile's x lines (the union over all parts) staged once in LDS, then the parts' chains one after the other,
 // each streaming sizeof(VT) + 2 bytes per non-zero.  Tiles without a line list (footprint over the plan's line budget) gather from x.
-template <int CT, bool NT, typename HT, bool MID>
+// IDS: workgroup b runs tile tile_ids[b] (the interior / boundary lists of the distributed step), an entry < 0 returns before the barrier,
+// uniformly for the workgroup -- as in scs_spmv_ap_tlc.
+template <int CT, bool NT, typename HT, bool MID, bool IDS = false>
 __global__ void __launch_bounds__(1024) scs_spmv_ap_hp_tlc(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ x,
                                                            HT *__restrict__ y, const int *__restrict__ tile_line_ptr,
-                                                           const int *__restrict__ tile_lines, const long x_len, const int xcd_remap) {
+                                                           const int *__restrict__ tile_lines, const long x_len, const int xcd_remap,
+                                                           const int *__restrict__ tile_ids = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tlc_smem[];
     HT *xs = (HT *)tlc_smem;
     typedef HT vec_t __attribute__((ext_vector_type(2)));
     const int C = CT > 0 ? CT : C_rt;
-    const unsigned tile = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    const unsigned lbt = remap_block(blockIdx.x, gridDim.x, xcd_remap);
+    const unsigned tile = IDS ? (unsigned)tile_ids[lbt] : lbt;
+    if (IDS && (int)tile < 0) return;
     const int lp0 = tile_line_ptr[tile];
     const int nl = tile_line_ptr[tile + 1] - lp0;
     const long row = (long)tile * blockDim.x + threadIdx.x;
@@ -317,7 +322,7 @@ __global__ void __launch_bounds__(1024) scs_spmv_ap_hp_tlc(const long n_chunks, 
 }
 
 // Lane per row, any C and handles without a plan: the parts' chains one after the other with global gathers.  IDS: virtual chunk vc ->
-// chunk_ids[vc] (the chunks a sweep plan leaves over)
+// chunk_ids[vc] (the chunks a sweep plan leaves over; the chunk lists of the distributed step, where an entry < 0 is switched off)
 template <int U, bool NT, int CT, typename HT, bool MID, bool IDS = false>
 __global__ void scs_spmv_ap_hp_rows(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ x, HT *__restrict__ y,
                                     const int xcd_remap, const int *__restrict__ chunk_ids = nullptr) {
@@ -328,6 +333,7 @@ __global__ void scs_spmv_ap_hp_rows(const long n_chunks, const int C_rt, const A
     const int i = (int)(vrow - vc * C);
     if (vc >= n_chunks) return;
     const long c = IDS ? (long)chunk_ids[vc] : vc;
+    if (IDS && c < 0) return;
     const long row = c * C + i;
     double acc[3] = {0.0, 0.0, 0.0};
     long cs = P.cp[0][c];
@@ -357,6 +363,27 @@ int launch_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv
     return USPMV_OK;
 }
 
+// the tiles in tile_ids through the tile-local-column kernel of the shared line plan
+template <typename HT, bool MID>
+int launch_ap_hp_tiles(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *tile_ids, long n_ids, const HT *d_x,
+                       HT *d_y, hipStream_t stream) {
+    const ApHpParts P = ap_hp_parts(hi, mid, hp);
+    const size_t lds = (size_t)hi->tlc.max_lines * 16 * sizeof(HT);
+    const int C = (int)hi->C;
+#define APHP_IDS(CTV, NTV)                                                                                                        \
+    do {                                                                                                                         \
+        auto kfn = scs_spmv_ap_hp_tlc<CTV, NTV, HT, MID, true>;                                                                  \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)n_ids), dim3(hi->tlc.tile_rows), lds, stream, (long)hi->n_chunks, C, P, d_x, d_y,  \
+                           hi->tlc.line_ptr.get(), hi->tlc.lines.get(), (long)hi->tlc.x_len, g_tune.xcd_remap, tile_ids);        \
+    } while (0)
+    if (g_tune.nontemporal) { if (C == 32) APHP_IDS(32, true); else APHP_IDS(0, true); }
+    else { if (C == 32) APHP_IDS(32, false); else APHP_IDS(0, false); }
+#undef APHP_IDS
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
 template <typename HT, bool MID>
 int launch_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const HT *d_x, HT *d_y, hipStream_t stream) {
     const int path = spmv_ap_hp_path(hi, mid, hp, (uintptr_t)d_x % 16 == 0);
@@ -375,7 +402,8 @@ int launch_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *
         auto kfn = scs_spmv_ap_hp_tlc<CTV, NTV, HT, MID>;                                                                        \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
         hipLaunchKernelGGL(kfn, dim3((unsigned)hi->tlc.n_tiles), dim3(hi->tlc.tile_rows), lds, stream, (long)hi->n_chunks, C, P,  \
-                           d_x, d_y, hi->tlc.line_ptr.get(), hi->tlc.lines.get(), (long)hi->tlc.x_len, g_tune.xcd_remap);        \
+                           d_x, d_y, hi->tlc.line_ptr.get(), hi->tlc.lines.get(), (long)hi->tlc.x_len, g_tune.xcd_remap,         \
+                           (const int *)nullptr);                                                                                \
     } while (0)
         if (nt) { if (C == 32) APHP_TLC(32, true); else APHP_TLC(0, true); }
         else { if (C == 32) APHP_TLC(32, false); else APHP_TLC(0, false); }
@@ -420,6 +448,14 @@ int launch_spmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const 
     if (hi->dtype == USPMV_F32) return launch_ap_hp_chunks<float, false>(hi, nullptr, hp, chunk_ids, n_ids, (const float *)d_x, (float *)d_y, stream);
     if (mid) return launch_ap_hp_chunks<double, true>(hi, mid, hp, chunk_ids, n_ids, (const double *)d_x, (double *)d_y, stream);
     return launch_ap_hp_chunks<double, false>(hi, nullptr, hp, chunk_ids, n_ids, (const double *)d_x, (double *)d_y, stream);
+}
+
+int launch_spmv_ap_hp_tiles(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *tile_ids, long n_ids,
+                            const void *d_x, void *d_y, hipStream_t stream) {
+    if (n_ids == 0) return USPMV_OK;
+    if (hi->dtype == USPMV_F32) return launch_ap_hp_tiles<float, false>(hi, nullptr, hp, tile_ids, n_ids, (const float *)d_x, (float *)d_y, stream);
+    if (mid) return launch_ap_hp_tiles<double, true>(hi, mid, hp, tile_ids, n_ids, (const double *)d_x, (double *)d_y, stream);
+    return launch_ap_hp_tiles<double, false>(hi, nullptr, hp, tile_ids, n_ids, (const double *)d_x, (double *)d_y, stream);
 }
 
 int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *d_x,

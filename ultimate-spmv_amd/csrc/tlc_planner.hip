@@ -734,6 +734,36 @@ int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPla
     return tlc_additive_install(A, s, p, max_lines, opts.new_to_old, who);
 }
 
+int dmat_optimize_ap_hp(uspmv_dmat *hi, uspmv_dmat *mid, uspmv_dmat *hp, const uspmv_scs *s_hi, const uspmv_scs *s_mid, const uspmv_scs *s_hp,
+                        int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_ap_hp";
+    if (!s_hi || !s_hp || (mid && !s_mid)) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    const uspmv_scs_t *ss[3] = {s_hi, mid ? s_mid : s_hp, mid ? s_hp : nullptr};
+    uspmv_dmat_t *const ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
+    for (int k = 0; k < 3; ++k) {
+        if (!ms[k]) continue;
+        if (!uspmv::scs_has_entries(ss[k]))
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host column indices", who);
+        if (ms[k]->C != ss[k]->C || ms[k]->n_chunks != ss[k]->n_chunks || ms[k]->dtype != ss[k]->dtype)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: handles and host structs do not describe the same parts", who);
+    }
+    if (int rc = require_device()) return rc;
+    for (uspmv_dmat_t *M : ms) if (M) { M->tlc = {}; M->sw = {}; }
+    if (n_tiles) *n_tiles = 0;
+    if (n_staged) *n_staged = 0;
+    uspmv_tlc_plan p;
+    // (measure off: at the rows per tile of one struct, as in dmat_optimize_ap)
+    if (int rc = uspmv_build_tlc_plan(ss[0], ss[1], line_budget(max_lines, hi->dtype, true), plan_tile_rows(opts.measure), &p, 4, ss[2])) return rc;
+    if (n_tiles) *n_tiles = p.n_tiles;              // (the line plan's outcome also when the sweep takes over, as in uspmv_dmat_optimize_ap)
+    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
+    if (!opts.measure) return p.valid ? install_host_plan(ms, p, /*elem=*/false, who) : USPMV_OK;
+    bool swept = false;
+    if (int rc = sweep_takes_over(ms, ss, mid ? 3 : 2, stats_of(p), who, &swept)) return rc;
+    if (swept || !p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
+    return install_host_plan(ms, p, /*elem=*/false, who);
+}
+
 }  // namespace uspmv_dev
 
 extern "C" {
@@ -843,30 +873,7 @@ int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_li
 
 int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
                               const uspmv_scs_t *s_hp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    const char *who = "uspmv_dmat_optimize_ap_hp";
-    if (!s_hi || !s_hp || (mid && !s_mid)) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
-    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
-    const uspmv_scs_t *ss[3] = {s_hi, mid ? s_mid : s_hp, mid ? s_hp : nullptr};
-    uspmv_dmat_t *const ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
-    for (int k = 0; k < 3; ++k) {
-        if (!ms[k]) continue;
-        if (!uspmv::scs_has_entries(ss[k]))
-            return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct; the plan builder needs the host column indices", who);
-        if (ms[k]->C != ss[k]->C || ms[k]->n_chunks != ss[k]->n_chunks || ms[k]->dtype != ss[k]->dtype)
-            return uspmv::fail(USPMV_ERR_INVALID, "%s: handles and host structs do not describe the same parts", who);
-    }
-    if (int rc = require_device()) return rc;
-    for (uspmv_dmat_t *M : ms) if (M) { M->tlc = {}; M->sw = {}; }
-    if (n_tiles) *n_tiles = 0;
-    if (n_staged) *n_staged = 0;
-    uspmv_tlc_plan p;
-    if (int rc = uspmv_build_tlc_plan(ss[0], ss[1], line_budget(max_lines, hi->dtype, true), plan_tile_rows(true), &p, 4, ss[2])) return rc;
-    if (n_tiles) *n_tiles = p.n_tiles;              // (the line plan's outcome also when the sweep takes over, as in uspmv_dmat_optimize_ap)
-    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
-    bool swept = false;
-    if (int rc = sweep_takes_over(ms, ss, mid ? 3 : 2, stats_of(p), who, &swept)) return rc;
-    if (swept || !p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
-    return install_host_plan(ms, p, /*elem=*/false, who);
+    return dmat_optimize_ap_hp(hi, mid, hp, s_hi, s_mid, s_hp, max_lines, TlcPlanOpts{}, n_tiles, n_staged);
 }
 
 int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {

@@ -358,6 +358,28 @@ int uspmv_spmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspm
     return launch_spmv_ap_hp(hi, mid, hp, d_x, d_y, (hipStream_t)stream);
 }
 
+int uspmv_spmv_ap_hp_tiles(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const int32_t *d_tile_ids, int64_t n_ids,
+                           const void *d_x, void *d_y, void *stream) {
+    const char *who = "uspmv_spmv_ap_hp_tiles";
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    const uint64_t id = hi->tlc.plan_id;
+    if (!hi->tlc.on || id == 0 || !hp->tlc.on || hp->tlc.plan_id != id || (mid && (!mid->tlc.on || mid->tlc.plan_id != id)))
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts have no shared tile-local-column plan (uspmv_dmat_optimize_ap_hp)", who);
+    if (n_ids < 0 || n_ids > hi->tlc.n_tiles || (n_ids > 0 && !d_tile_ids) || !d_x || !d_y) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    if ((uintptr_t)d_x % 16) return uspmv::fail(USPMV_ERR_INVALID, "%s: x must be 16-byte aligned", who);
+    if (int rc = require_device()) return rc;
+    return launch_spmv_ap_hp_tiles(hi, mid, hp, d_tile_ids, (long)n_ids, d_x, d_y, (hipStream_t)stream);
+}
+
+int uspmv_spmv_ap_hp_chunks(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const int32_t *d_chunk_ids, int64_t n_ids,
+                            const void *d_x, void *d_y, void *stream) {
+    const char *who = "uspmv_spmv_ap_hp_chunks";
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    if (n_ids < 0 || n_ids > hi->n_chunks || (n_ids > 0 && !d_chunk_ids) || !d_x || !d_y) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    if (int rc = require_device()) return rc;
+    return launch_spmv_ap_hp_chunks(hi, mid, hp, d_chunk_ids, (long)n_ids, d_x, d_y, (hipStream_t)stream);
+}
+
 // the argument checks uspmv_spmmv_ap_hp and uspmv_spmmv_ap_hp_path share
 static int check_spmmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout, const char *who) {
     if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;

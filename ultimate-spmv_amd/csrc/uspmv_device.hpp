@@ -292,6 +292,10 @@ int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPla
 // caller's row order, and no fall-through to the column-window sweep -- what the distributed object needs of an ap[dp_sp] pair
 int dmat_optimize_ap(uspmv_dmat *dp, uspmv_dmat *sp, const uspmv_scs *s_dp, const uspmv_scs *s_sp, int max_lines, const TlcPlanOpts &opts,
                      int64_t *n_tiles, int64_t *n_staged);
+// uspmv_dmat_optimize_ap_hp likewise (mid / s_mid NULL for the two-part kinds).  measure off: the shared line plan at 256 rows per tile in
+// the caller's row order, installed whenever it stages a tile, no column-window sweep -- what the distributed object needs of the parts
+int dmat_optimize_ap_hp(uspmv_dmat *hi, uspmv_dmat *mid, uspmv_dmat *hp, const uspmv_scs *s_hi, const uspmv_scs *s_mid, const uspmv_scs *s_hp,
+                        int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged);
 
 // One-launch distributed step (csrc/uspmv_dist_api.hip): the tile list of a step is [early | late | conditional | early].  Early entries
 // (interior + padding tiles) run at once.  A late entry (a tile with real halo references) looks ONCE at the exchange counter: if the
@@ -567,6 +571,9 @@ int launch_spmv_ap_tiles(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *
 int launch_spmv_sweep_ap_hp(const uspmv_dmat *hi, bool mid, const void *x, void *y, hipStream_t st);
 int launch_spmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
                              const void *d_x, void *d_y, hipStream_t stream);                                      // ap_kernels.hip
+// the tiles in tile_ids of the parts' shared tile-local-column plan (entries < 0 skipped): scs_spmv_ap_hp_tlc over a tile list
+int launch_spmv_ap_hp_tiles(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *tile_ids, long n_ids,
+                            const void *d_x, void *d_y, hipStream_t stream);                                       // ap_kernels.hip
 
 // (A2 / the *_2 arrays: optional second struct sharing the plan -- the sp part of an ap[dp_sp] pair; A3 / *_3 a third -- the hp part of
 //  ap[dp_sp_hp])

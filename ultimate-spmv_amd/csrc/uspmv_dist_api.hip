@@ -36,6 +36,10 @@
 // carries the sp part as a second handle.  One halo for the pair, tile classes from both parts, "pad_split" on by default; the single-vector
 // step and, for block vectors, uspmv_dist_spmmv_ap: the same lists run by the list forms of the pair's block kernels
 // (uspmv_spmmv_ap_tiles / _chunks), the padding guard over the b values of the slot.
+//
+// The kinds with an fp16 part, ap[dp_hp], ap[sp_hp], ap[dp_sp_hp] (uspmv_dist_create_ap_hp_from_coo): A / scs are the hi part, the
+// object carries the hp part and, for ap[dp_sp_hp], the mid part beside it.  One halo for all parts, tile classes from all of them, the
+// single-vector step in the vector type of the hi part (float for ap[sp_hp]); no block-vector step yet.
 #include <rccl/rccl.h>
 
 #include <chrono>
@@ -62,6 +66,12 @@ struct uspmv_dist {
     uspmv_dmat_t *A_sp = nullptr;
     uspmv_scs_t *scs_sp = nullptr;
     double ap_threshold = 0.0;
+    // the kinds with an fp16 part (uspmv_dist_create_ap_hp_from_coo): A / scs are the hi part (F32 for ap[sp_hp], whose vectors are float: dtype
+    // follows it), A_mid / scs_mid the float part of ap[dp_sp_hp] (else NULL), A_hp / scs_hp the fp16 part; A_sp stays NULL
+    uspmv_dmat_t *A_mid = nullptr, *A_hp = nullptr;
+    uspmv_scs_t *scs_mid = nullptr, *scs_hp = nullptr;
+    int ap_kind = -1;                 // uspmv_partition_precisions_hp's kind
+    double ap_threshold_2 = 0.0;
     uspmv_halo_t *halo = nullptr;
     uspmv_comm_plan_t *plan = nullptr;
     int dtype = USPMV_F64;
@@ -250,7 +260,13 @@ int sync_reset(uspmv_dist *D) {
     return USPMV_OK;
 }
 
-inline bool fused_on(const uspmv_dist *D) { return !D->A_sp && D->fused && D->overlap && D->tiles && D->d_step && D->sa.n_real + D->sa.n_cond > 0; }
+// an adaptive-precision object of either family
+inline bool is_ap(const uspmv_dist *D) { return D->A_sp || D->A_hp; }
+inline const char *ap_name(const uspmv_dist *D) {
+    return !D->A_hp ? "ap[dp_sp]" : D->ap_kind == USPMV_AP_DP_HP ? "ap[dp_hp]" : D->ap_kind == USPMV_AP_SP_HP ? "ap[sp_hp]" : "ap[dp_sp_hp]";
+}
+
+inline bool fused_on(const uspmv_dist *D) { return !is_ap(D) && D->fused && D->overlap && D->tiles && D->d_step && D->sa.n_real + D->sa.n_cond > 0; }
 
 inline bool pads_on(const uspmv_dist *D) { return D->pad_split && D->overlap && D->tiles && D->n_pad > 0 && D->pad_col >= 0; }
 
@@ -651,6 +667,8 @@ inline bool eager_only(const uspmv_dist *D) { return D->exchange != USPMV_EXCHAN
 
 int part(uspmv_dist *D, const int32_t *ids, int64_t n, const void *x, void *y, hipStream_t st) {
     if (n == 0) return USPMV_OK;
+    if (D->A_hp)
+        return D->tiles ? uspmv_spmv_ap_hp_tiles(D->A, D->A_mid, D->A_hp, ids, n, x, y, st) : uspmv_spmv_ap_hp_chunks(D->A, D->A_mid, D->A_hp, ids, n, x, y, st);
     if (D->A_sp)
         return D->tiles ? uspmv_spmv_ap_tiles(D->A, D->A_sp, ids, n, (const double *)x, (double *)y, st)
                         : uspmv_spmv_ap_chunks(D->A, D->A_sp, ids, n, (const double *)x, (double *)y, st);
@@ -659,6 +677,7 @@ int part(uspmv_dist *D, const int32_t *ids, int64_t n, const void *x, void *y, h
 
 // the whole matrix in one launch
 int whole(uspmv_dist *D, const void *x, void *y, hipStream_t st) {
+    if (D->A_hp) return uspmv_spmv_ap_hp(D->A, D->A_mid, D->A_hp, x, y, st);
     return D->A_sp ? uspmv_spmv_ap(D->A, D->A_sp, (const double *)x, (double *)y, st) : uspmv_spmv(D->A, x, y, st);
 }
 
@@ -789,7 +808,8 @@ void uspmv_dist_free(uspmv_dist_t *D) {
     if (D->side_stream) (void)hipStreamDestroy(D->side_stream);
     if (D->comm) (void)ncclCommDestroy(D->comm);
     uspmv_comm_plan_free(D->plan);
-    if (D->owns_setup) { uspmv_dmat_free(D->A); uspmv_dmat_free(D->A_sp); uspmv_halo_free(D->halo); uspmv_scs_free(D->scs); uspmv_scs_free(D->scs_sp); }
+    if (D->owns_setup) { uspmv_dmat_free(D->A); uspmv_dmat_free(D->A_sp); uspmv_halo_free(D->halo); uspmv_scs_free(D->scs); uspmv_scs_free(D->scs_sp);
+                         uspmv_dmat_free(D->A_mid); uspmv_dmat_free(D->A_hp); uspmv_scs_free(D->scs_mid); uspmv_scs_free(D->scs_hp); }
     delete D;
 }
 
@@ -797,7 +817,7 @@ void uspmv_dist_free(uspmv_dist_t *D) {
 static int create_dist(const void *comm_id, int comm_rank, int comm_size, int rank, int P, uspmv_dmat_t *A, const uspmv_halo_t *halo,
                        const int32_t *old_to_new_idx, const int32_t *interior_ids, int64_t n_interior, const int32_t *boundary_ids,
                        int64_t n_boundary, int ids_are_tiles, const uspmv_dist_options_t *opt, uspmv_dist_t **out, bool windows,
-                       uspmv_dmat_t *A_sp = nullptr) {
+                       bool ap = false) {
     const int ex = opt ? opt->exchange : USPMV_EXCHANGE_RCCL;
     if (ex != USPMV_EXCHANGE_RCCL && ex != USPMV_EXCHANGE_HOST && ex != USPMV_EXCHANGE_PEER)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create: unknown exchange %d", ex);
@@ -836,7 +856,7 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     D->rank = rank; D->P = P; D->comm_rank = comm_rank; D->comm_size = comm_size; D->loopback = comm_size == 1 && P > 1;   // (host: comm_size == P)
     D->exchange = ex;
     D->A = A; D->dtype = A->dtype; D->tiles = ids_are_tiles != 0;
-    D->pad_split = A_sp != nullptr;   // (the sp handle itself is attached by the caller once it owns the set-up: a failure in here frees the caller's)
+    D->pad_split = ap;                // (adaptive precision; the other handles are attached by the caller once it owns the set-up: a failure in here frees the caller's)
     D->n_local = halo->n_local; D->n_halo = halo->n_halo; D->n_int = n_interior; D->n_bnd = n_boundary;
     D->recv_counts = halo->recv_counts;
     auto bail = [&](int code) { uspmv_dist_free(D); return code; };
@@ -883,7 +903,7 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     D->vec_len = D->n_local + std::max(D->n_rows_padded - D->n_local, D->n_halo);       // padded_vec_size (code/main.cpp:1406-1412)
     // the single-vector step's exchange plan, here so that no step allocates (a captured one must not); peer stores need none
     if (ex != USPMV_EXCHANGE_PEER) D_HIP(add_block_plan(D, 1, USPMV_ROWWISE, USPMV_BULKVEC));
-    if (P > 1 && !A->alt && A->n_chunks > 0 && !A_sp) {
+    if (P > 1 && !A->alt && A->n_chunks > 0 && !ap) {
         // the same split for block vectors: per chunk, does it (or its tile) touch a halo column
         std::vector<unsigned char> flag((size_t)A->n_chunks, 0);
         const int64_t cpt = ids_are_tiles ? std::max<int64_t>(A->tlc.tile_rows / A->C, 1) : 1;
@@ -1099,7 +1119,7 @@ int uspmv_dist_create_ap_from_coo_ex(const void *comm_id, int comm_rank, int com
     }
     uspmv_dist_t *D = nullptr;
     rc = create_dist(comm_id, comm_rank, comm_size, rank, P, A_dp, halo, o2n, ids_int.data(), (int64_t)ids_int.size(), ids_bnd.data(),
-                     (int64_t)ids_bnd.size(), use_tiles ? 1 : 0, opt, &D, false, A_sp);
+                     (int64_t)ids_bnd.size(), use_tiles ? 1 : 0, opt, &D, false, /*ap=*/true);
     if (rc) { cleanup(); return rc; }
     const bool pads = use_tiles && P > 1 && pad_col >= 0 && !ids_pad.empty();
     if (pads) {
@@ -1128,6 +1148,127 @@ int uspmv_dist_create_ap_from_coo(const void *comm_id, int comm_rank, int comm_s
     return uspmv_dist_create_ap_from_coo_ex(comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, threshold_1, tlc, nullptr, out);
 }
 
+// uspmv_dist_create_ap_from_coo_ex for the kinds with an fp16 part.  A tile is a tile of ALL parts (same rows), its class the largest of the
+// parts' classes; lists, padding column and guard are then the one-precision object's, in the vector type of the hi part.
+// Why the padding guard stays sufficient: every part pads with (value +0 of its type, global column 0), one slot of one halo numbering.  On
+// the double kinds a padding slot contributes fma(+0.0, x, acc) to its part's chain (the float and fp16 zeros widen to +0.0 exactly); on
+// ap[sp_hp] it contributes acc + (double)(0.0f * x) with a float x.  In both, a finite x of unchanged sign gives the same signed zero product,
+// so every chain -- and y, a fixed expression of the chains -- comes out bit for bit as with the delivered value; the guard
+// (pad_guard_kernel<double | float>, by D->dtype) re-runs the padding tiles whenever the kept or the delivered value is not finite or
+// their signs differ.
+int uspmv_dist_create_ap_hp_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                        const int32_t *wsa, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2, int tlc,
+                                        const uspmv_dist_options_t *opt, uspmv_dist_t **out) {
+    const char *who = "uspmv_dist_create_ap_hp_from_coo";
+    if (!local || !wsa || !out) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad rank / P", who);
+    if (kind == USPMV_AP_DP_SP) return uspmv::fail(USPMV_ERR_INVALID, "%s: ap[dp_sp] has no fp16 part; its object is made by uspmv_dist_create_ap_from_coo", who);
+    if (kind != USPMV_AP_DP_HP && kind != USPMV_AP_SP_HP && kind != USPMV_AP_DP_SP_HP) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown kind %d", who, kind);
+    // (refused HERE, by all ranks alike, before the first collective: see uspmv_dist_create_from_coo_ex)
+    for (int p = 0; p < P; ++p)
+        if (wsa[p + 1] <= wsa[p])
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: block %d of %d owns no rows (work_sharing_arr %d .. %d) -- fewer ranks or another partition", who, p, P,
+                               (int)wsa[p], (int)wsa[p + 1]);
+    if (int rc = uspmv_dev::require_device()) return rc;
+    const bool three = kind == USPMV_AP_DP_SP_HP;
+    uspmv_coo_t *coo[3] = {nullptr, nullptr, nullptr};           // hi, mid, hp
+    uspmv_scs_t *s[3] = {nullptr, nullptr, nullptr};
+    uspmv_dmat_t *A[3] = {nullptr, nullptr, nullptr};
+    uspmv_halo_t *halo = nullptr;
+    auto free_coo = [&]() { for (auto *&c : coo) { uspmv_coo_free(c); c = nullptr; } };
+    auto cleanup = [&]() {
+        free_coo();
+        for (int q = 0; q < 3; ++q) { uspmv_dmat_free(A[q]); uspmv_scs_free(s[q]); }
+        uspmv_halo_free(halo);
+    };
+    // the single-GPU order of the host route (partition, hi, the other parts with hi's permutation) with the halo discovery between
+    // conversion and column permutation, as for one struct
+    int rc = uspmv_partition_precisions_hp(local, kind, threshold_1, threshold_2, &coo[0], three ? &coo[1] : nullptr, &coo[2]);
+    if (!rc) rc = uspmv_convert_to_scs(coo[0], C, sigma, kind == USPMV_AP_SP_HP ? USPMV_F32 : USPMV_F64, nullptr, &s[0]);
+    const int32_t *o2n = nullptr;
+    if (!rc) rc = uspmv_scs_arrays(s[0], nullptr, nullptr, nullptr, nullptr, &o2n, nullptr);
+    if (!rc && three) rc = uspmv_convert_to_scs(coo[1], C, sigma, USPMV_F32, o2n, &s[1]);
+    if (!rc) rc = uspmv_convert_to_scs(coo[2], C, sigma, USPMV_F16, o2n, &s[2]);
+    free_coo();
+    if (!rc) rc = uspmv_halo_discover_ap_hp(s[0], s[1], s[2], wsa, rank, P, &halo);
+    for (int q = 0; q < 3 && !rc; ++q)
+        if (s[q]) rc = uspmv_permute_scs_cols(s[q], o2n);
+    for (int q = 0; q < 3 && !rc; ++q)
+        if (s[q]) rc = uspmv_dmat_upload(s[q], &A[q]);
+    int64_t n_tiles = 0, n_staged = 0;
+    if (!rc && tlc) {
+        // (the shared line plan as built, at 256-row tiles in the caller's row order: a sweep plan's tiles are no row ranges -- see uspmv_dist_create_from_coo_ex)
+        const uspmv_dev::TlcPlanOpts as_is{/*measure=*/false, /*elements=*/false, /*deal_rows=*/false, /*additive=*/false};
+        rc = uspmv_dev::dmat_optimize_ap_hp(A[0], A[1], A[2], s[0], s[1], s[2], 0, as_is, &n_tiles, &n_staged);
+    }
+    const int64_t n_local = wsa[rank + 1] - wsa[rank];
+    // one padding column for all parts (all pad with global column 0, one halo numbering); if they ever disagree, no chunk is padding-only
+    std::vector<uint8_t> cls;
+    int32_t pad_col = -1;
+    bool pad_clash = false;
+    for (int q = 0; q < 3 && !rc; ++q) {
+        if (!s[q]) continue;
+        std::vector<uint8_t> cq;
+        int32_t pq = -1;
+        rc = uspmv_scs_classify_chunks(s[q], n_local, &cq, &pq);
+        if (rc) break;
+        if (cls.empty()) cls.assign(cq.size(), 0);
+        for (size_t c = 0; c < cls.size(); ++c) cls[c] = std::max(cls[c], cq[c]);
+        if (pq >= 0) { pad_clash = pad_clash || (pad_col >= 0 && pad_col != pq); pad_col = pq; }
+    }
+    if (rc) { cleanup(); return rc; }
+    if (pad_clash) {
+        for (auto &c : cls) if (c == 1) c = 2;
+        pad_col = -1;
+    }
+    const int tile_rows = A[0]->tlc.on && A[0]->tlc.plan_id != 0 ? A[0]->tlc.tile_rows : 0;
+    const bool use_tiles = tile_rows > 0 && n_staged > 0;
+    std::vector<int32_t> ids_int, ids_bnd, ids_pad, ids_real;
+    if (use_tiles) {
+        const int64_t cpt = std::max<int64_t>(tile_rows / C, 1);
+        std::vector<uint8_t> tc((size_t)n_tiles, 0);
+        for (int64_t c = 0; c < (int64_t)cls.size(); ++c) tc[(size_t)(c / cpt)] = std::max(tc[(size_t)(c / cpt)], cls[(size_t)c]);
+        for (int64_t t = 0; t < n_tiles; ++t) {
+            if (tc[(size_t)t] == 0) ids_int.push_back((int32_t)t);
+            else { ids_bnd.push_back((int32_t)t); (tc[(size_t)t] == 1 ? ids_pad : ids_real).push_back((int32_t)t); }
+        }
+    } else {   // chunk lists: a chunk is boundary when it is in any part
+        for (auto *M : A) if (M && M->tlc.on) M->tlc = {};   // (a plan that stages nothing: the whole-matrix launch takes the lane-per-row kernel too)
+        for (int64_t c = 0; c < (int64_t)cls.size(); ++c) (cls[(size_t)c] ? ids_bnd : ids_int).push_back((int32_t)c);
+    }
+    uspmv_dist_t *D = nullptr;
+    rc = create_dist(comm_id, comm_rank, comm_size, rank, P, A[0], halo, o2n, ids_int.data(), (int64_t)ids_int.size(), ids_bnd.data(),
+                     (int64_t)ids_bnd.size(), use_tiles ? 1 : 0, opt, &D, false, /*ap=*/true);
+    if (rc) { cleanup(); return rc; }
+    const bool pads = use_tiles && P > 1 && pad_col >= 0 && !ids_pad.empty();
+    if (pads) {
+        std::vector<int32_t> early(ids_int.size() + ids_pad.size()), late(ids_real.size() + ids_pad.size(), -1);
+        std::merge(ids_int.begin(), ids_int.end(), ids_pad.begin(), ids_pad.end(), early.begin());
+        std::copy(ids_real.begin(), ids_real.end(), late.begin());
+        hipError_t e = D->d_pad.upload(ids_pad.data(), 4 * ids_pad.size());
+        if (e == hipSuccess) e = D->d_early.upload(early.data(), 4 * early.size());
+        if (e == hipSuccess) e = D->d_late.upload(late.data(), 4 * late.size());
+        if (e != hipSuccess) {
+            uspmv_dist_free(D); cleanup();
+            return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
+        }
+        D->n_pad = (int64_t)ids_pad.size(); D->n_bnd_real = (int64_t)ids_real.size(); D->pad_col = pad_col;
+    }
+    // (the collective window set-up after every step above that could fail on this rank alone)
+    if (D->exchange == USPMV_EXCHANGE_PEER && P > 1)
+        if ((rc = peer_setup(D, 1))) { uspmv_dist_free(D); cleanup(); return rc; }
+    D->owns_setup = true; D->scs = s[0]; D->scs_mid = s[1]; D->scs_hp = s[2]; D->halo = halo; D->A_mid = A[1]; D->A_hp = A[2];
+    D->ap_kind = kind; D->ap_threshold = threshold_1; D->ap_threshold_2 = threshold_2;
+    *out = D;
+    return USPMV_OK;
+}
+
+int uspmv_dist_create_ap_hp_from_coo(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                     const int32_t *wsa, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2, int tlc,
+                                     uspmv_dist_t **out) {
+    return uspmv_dist_create_ap_hp_from_coo_ex(comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, kind, threshold_1, threshold_2, tlc, nullptr, out);
+}
+
 int uspmv_dist_comm_plan(const uspmv_dist_t *D, int64_t *n_send, const int64_t **send_off, const int32_t **send_idxs, const int64_t **recv_off) {
     if (!D || !D->plan) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_comm_plan: NULL argument");
     return uspmv_comm_plan_meta(D->plan, n_send, send_off, send_idxs, recv_off);
@@ -1136,6 +1277,9 @@ int uspmv_dist_comm_plan(const uspmv_dist_t *D, int64_t *n_send, const int64_t *
 int uspmv_dist_set_option(uspmv_dist_t *D, const char *key, int value) {
     if (!D || !key) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_set_option: NULL argument");
     const std::string k(key);
+    if (D->A_hp && (((k == "fused_step" || k == "autotune_all") && value != 0) || (k == "block_plan" && value > 0)))
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_set_option: '%s' is not available on an adaptive-precision (%s) object: its step has "
+                           "the overlap, plain and pad_split forms, and it has no block-vector step", key, ap_name(D));
     if (D->A_sp && (((k == "fused_step" || k == "autotune_all") && value != 0) || (k == "block_plan" && value > 0)))
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_set_option: '%s' is not available on an adaptive-precision (ap[dp_sp]) object: its step has "
                            "the overlap, plain and pad_split forms; block vectors run through uspmv_dist_spmmv_ap", key);
@@ -1223,10 +1367,26 @@ int uspmv_dist_parts(const uspmv_dist_t *D, const uspmv_scs_t **scs, const uspmv
 int uspmv_dist_parts_ap(const uspmv_dist_t *D, const uspmv_scs_t **scs_dp, const uspmv_scs_t **scs_sp, const uspmv_dmat_t **A_dp,
                         const uspmv_dmat_t **A_sp, const uspmv_halo_t **halo) {
     if (!D) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap: NULL argument");
+    if (D->A_hp) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap: an %s object (its parts: uspmv_dist_parts_ap_hp)", ap_name(D));
     if (scs_dp) *scs_dp = D->scs;
     if (scs_sp) *scs_sp = D->scs_sp;
     if (A_dp) *A_dp = D->A;
     if (A_sp) *A_sp = D->A_sp;
+    if (halo) *halo = D->halo;
+    return USPMV_OK;
+}
+
+int uspmv_dist_parts_ap_hp(const uspmv_dist_t *D, int *kind, const uspmv_scs_t **scs_hi, const uspmv_scs_t **scs_mid, const uspmv_scs_t **scs_hp,
+                           const uspmv_dmat_t **A_hi, const uspmv_dmat_t **A_mid, const uspmv_dmat_t **A_hp, const uspmv_halo_t **halo) {
+    if (!D) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap_hp: NULL argument");
+    if (!D->A_hp) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap_hp: not an object made by uspmv_dist_create_ap_hp_from_coo");
+    if (kind) *kind = D->ap_kind;
+    if (scs_hi) *scs_hi = D->scs;
+    if (scs_mid) *scs_mid = D->scs_mid;
+    if (scs_hp) *scs_hp = D->scs_hp;
+    if (A_hi) *A_hi = D->A;
+    if (A_mid) *A_mid = D->A_mid;
+    if (A_hp) *A_hp = D->A_hp;
     if (halo) *halo = D->halo;
     return USPMV_OK;
 }
@@ -1292,7 +1452,7 @@ int uspmv_dist_autotune(uspmv_dist_t *D, void *d_x, void *d_y, int use_graph, co
     auto apply = [&](int f) -> int {
         if (int rc = uspmv_dist_set_option(D, "overlap", f == USPMV_STEP_PLAIN ? 0 : 1)) return rc;
         // (an ap object times overlap | plain only, and its overlap form keeps the "pad_split" it has -- 1 unless the caller changed it)
-        if (D->A_sp) return USPMV_OK;
+        if (is_ap(D)) return USPMV_OK;
         if (int rc = uspmv_dist_set_option(D, "pad_split", f == USPMV_STEP_PAD || f == USPMV_STEP_FUSED ? 1 : 0)) return rc;
         return uspmv_dist_set_option(D, "fused_step", f == USPMV_STEP_FUSED ? 1 : 0);
     };
@@ -1420,7 +1580,8 @@ int uspmv_dist_check(uspmv_dist_t *D, const uspmv_coo_t *local, const int32_t *w
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(hy.data(), d_y, (size_t)D->n_rows_padded * vsz, hipMemcpyDeviceToHost));
     std::vector<char> ref((size_t)std::max<int64_t>(nl, 1) * vsz);
-    if (int rc = D->A_sp ? uspmv::dist_reference_rows_ap(local, wsa, D->P, D->rank, D->loopback, D->ap_threshold, (double *)ref.data())
+    if (int rc = D->A_hp ? uspmv::dist_reference_rows_ap_hp(local, wsa, D->P, D->rank, D->loopback, D->ap_kind, D->ap_threshold, D->ap_threshold_2, ref.data())
+                 : D->A_sp ? uspmv::dist_reference_rows_ap(local, wsa, D->P, D->rank, D->loopback, D->ap_threshold, (double *)ref.data())
                          : uspmv::dist_reference_rows(local, wsa, D->P, D->rank, D->loopback, D->dtype, ref.data()))
         return rc;
     int64_t bad = 0;
@@ -1437,6 +1598,7 @@ int uspmv_dist_check(uspmv_dist_t *D, const uspmv_coo_t *local, const int32_t *w
 
 int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
     if (!D || !d_X || !d_Y || b < 1) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: bad argument");
+    if (D->A_hp) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: not available on an adaptive-precision (%s) object (no block-vector step across ranks yet)", ap_name(D));
     if (D->A_sp) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: not available on an adaptive-precision (ap[dp_sp]) object (its block step is uspmv_dist_spmmv_ap)");
     if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown layout %d", layout);
     if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown mode %d", mode);
@@ -1486,6 +1648,7 @@ int uspmv_dist_spmmv_ap(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout
     if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown layout %d", who, layout);
     if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown mode %d", who, mode);
     if (!D || !d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (D->A_hp) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: an adaptive-precision %s object (no block-vector step across ranks yet)", who, ap_name(D));
     if (!D->A_sp)
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: a one-precision object (uspmv_dist_create_from_coo); its block step is uspmv_dist_spmmv", who);
     if (layout == USPMV_ROWWISE && mode != USPMV_BULKVEC)

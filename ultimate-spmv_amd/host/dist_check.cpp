@@ -69,6 +69,42 @@ int dist_reference_rows_ap(const uspmv_coo *local, const int32_t *wsa, int P, in
     return USPMV_OK;
 }
 
+// one part of ap[sp_hp]: x float, every product rounded to float and then added to the row's double accumulator (ap_step(float, float, double)
+// of the kernels; the part's values are floats, resp. binary16 values, held in doubles)
+static void rows_float_products(const uspmv_coo *m, const int32_t *wsa, int P, int rank, bool loopback, double *acc) {
+    for (int64_t i = 0; i < m->n_rows; ++i) acc[i] = 0.0;
+    for (int64_t k = 0; k < m->nnz; ++k) {
+        const float v = (float)m->values[(size_t)k], x = (float)check_x(check_col(m->J[(size_t)k], wsa, P, rank, loopback));
+        const float prod = v * x;
+        acc[m->I[(size_t)k]] += (double)prod;
+    }
+}
+
+// the kinds with an fp16 part: the block split as the object's set-up splits it (uspmv_partition_precisions_hp: sp values (double)(float)v, hp
+// values rounded once to binary16), the numerics of uspmv_spmv_ap_hp
+int dist_reference_rows_ap_hp(const uspmv_coo *local, const int32_t *wsa, int P, int rank, bool loopback, int kind, double threshold_1,
+                              double threshold_2, void *y_ref) {
+    if (!local || !wsa || !y_ref) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: NULL argument");
+    for (int64_t k = 0; k < local->nnz; ++k)
+        if (local->I[(size_t)k] < 0 || local->I[(size_t)k] >= local->n_rows) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: row id outside the block");
+    uspmv_coo *hi = nullptr, *mid = nullptr, *hp = nullptr;
+    if (int rc = uspmv_partition_precisions_hp(local, kind, threshold_1, threshold_2, &hi, kind == USPMV_AP_DP_SP_HP ? &mid : nullptr, &hp)) return rc;
+    const int64_t n = local->n_rows;
+    std::vector<double> a((size_t)std::max<int64_t>(n, 1)), b(a.size()), c(a.size());
+    if (kind == USPMV_AP_SP_HP) {
+        rows_float_products(hi, wsa, P, rank, loopback, a.data());
+        rows_float_products(hp, wsa, P, rank, loopback, c.data());
+        for (int64_t i = 0; i < n; ++i) ((float *)y_ref)[i] = (float)(a[(size_t)i] + c[(size_t)i]);
+    } else {
+        rows<double>(hi, wsa, P, rank, loopback, a.data());
+        if (mid) rows<double>(mid, wsa, P, rank, loopback, b.data());
+        rows<double>(hp, wsa, P, rank, loopback, c.data());
+        for (int64_t i = 0; i < n; ++i) ((double *)y_ref)[i] = mid ? (a[(size_t)i] + b[(size_t)i]) + c[(size_t)i] : a[(size_t)i] + c[(size_t)i];
+    }
+    uspmv_coo_free(hi); uspmv_coo_free(mid); uspmv_coo_free(hp);
+    return USPMV_OK;
+}
+
 }  // namespace uspmv
 
 // The rows of the check on the host alone (no GPU): y_ref[i] = the entry-ordered FMA chain of local row i over
@@ -84,4 +120,14 @@ extern "C" int uspmv_dist_check_reference(const uspmv_coo_t *local, const int32_
 extern "C" int uspmv_dist_check_reference_ap(const uspmv_coo_t *local, const int32_t *wsa, int rank, int P, double threshold_1, double *y_ref) {
     if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_check_reference_ap: bad rank / P");
     return uspmv::dist_reference_rows_ap(local, wsa, P, rank, /*loopback=*/false, threshold_1, y_ref);
+}
+
+// ... and for an object of a kind with an fp16 part (uspmv_dist_create_ap_hp_from_coo): parts as uspmv_partition_precisions_hp makes them, one
+// chain per part in entry order, y_ref in the type of the hi part (float for USPMV_AP_SP_HP, else double)
+extern "C" int uspmv_dist_check_reference_ap_hp(const uspmv_coo_t *local, const int32_t *wsa, int rank, int P, int kind, double threshold_1,
+                                                double threshold_2, void *y_ref) {
+    if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_check_reference_ap_hp: bad rank / P");
+    if (kind != USPMV_AP_DP_HP && kind != USPMV_AP_SP_HP && kind != USPMV_AP_DP_SP_HP)
+        return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_check_reference_ap_hp: unknown kind %d", kind);
+    return uspmv::dist_reference_rows_ap_hp(local, wsa, P, rank, /*loopback=*/false, kind, threshold_1, threshold_2, y_ref);
 }

@@ -186,17 +186,32 @@ int uspmv_halo_discover(uspmv_scs_t *s, const int32_t *wsa, int rank, int P, usp
     return discover_halo(parts, 1, wsa, rank, P, out, "uspmv_halo_discover");
 }
 
-int uspmv_halo_discover_ap(uspmv_scs_t *dp, uspmv_scs_t *sp, const int32_t *wsa, int rank, int P, uspmv_halo_t **out) {
-    const char *who = "uspmv_halo_discover_ap";
-    if (!dp || !sp || !wsa || !out || P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
-    if (!uspmv::scs_has_entries(dp) || !uspmv::scs_has_entries(sp))
-        return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct (uspmv_convert_to_scs_device)", who);
-    if (dp == sp) return uspmv::fail(USPMV_ERR_INVALID, "%s: the two parts are one struct", who);
+// the checks of a split's n >= 2 structs, then the one scan; nothing is rewritten when a check refuses
+static int discover_halo_parts(uspmv_scs_t *const parts[], int n, const int32_t *wsa, int rank, int P, uspmv_halo_t **out, const char *who,
+                               const char *first) {
+    if (!wsa || !out || P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    for (int q = 0; q < n; ++q)
+        if (!parts[q]) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    for (int q = 0; q < n; ++q)
+        if (!uspmv::scs_has_entries(parts[q])) return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct (uspmv_convert_to_scs_device)", who);
+    for (int q = 1; q < n; ++q)
+        for (int r = 0; r < q; ++r)
+            if (parts[q] == parts[r]) return uspmv::fail(USPMV_ERR_INVALID, "%s: %s parts are one struct", who, n == 2 ? "the two" : "two of the");
     // (the permutations cannot be compared: a struct converted with a fixed permutation records the identity, code/utilities.hpp:1911-1928)
-    if (dp->C != sp->C || dp->n_chunks != sp->n_chunks || dp->n_rows != sp->n_rows)
-        return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts must share C, n_chunks and the row layout (convert the sp part with the dp part's permutation)", who);
+    for (int q = 1; q < n; ++q)
+        if (parts[0]->C != parts[q]->C || parts[0]->n_chunks != parts[q]->n_chunks || parts[0]->n_rows != parts[q]->n_rows)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts must share C, n_chunks and the row layout (convert the %s part's permutation)", who, first);
+    return discover_halo(parts, n, wsa, rank, P, out, who);
+}
+
+int uspmv_halo_discover_ap(uspmv_scs_t *dp, uspmv_scs_t *sp, const int32_t *wsa, int rank, int P, uspmv_halo_t **out) {
     uspmv_scs_t *const parts[2] = {dp, sp};
-    return discover_halo(parts, 2, wsa, rank, P, out, who);
+    return discover_halo_parts(parts, 2, wsa, rank, P, out, "uspmv_halo_discover_ap", "sp part with the dp");
+}
+
+int uspmv_halo_discover_ap_hp(uspmv_scs_t *hi, uspmv_scs_t *mid, uspmv_scs_t *hp, const int32_t *wsa, int rank, int P, uspmv_halo_t **out) {
+    uspmv_scs_t *const parts[3] = {hi, mid ? mid : hp, hp};
+    return discover_halo_parts(parts, mid ? 3 : 2, wsa, rank, P, out, "uspmv_halo_discover_ap_hp", "other parts with the hi");
 }
 
 int uspmv_halo_meta(const uspmv_halo_t *h, int64_t *n_halo, const int32_t **recv_counts_cumsum,

@@ -246,4 +246,6 @@ double check_x(int64_t global_col);
 int64_t check_col(int64_t j, const int32_t *wsa, int P, int rank, bool loopback);
 int dist_reference_rows(const uspmv_coo *local, const int32_t *wsa, int P, int rank, bool loopback, int dtype, void *y_ref);
 int dist_reference_rows_ap(const uspmv_coo *local, const int32_t *wsa, int P, int rank, bool loopback, double threshold_1, double *y_ref);
+int dist_reference_rows_ap_hp(const uspmv_coo *local, const int32_t *wsa, int P, int rank, bool loopback, int kind, double threshold_1,
+                              double threshold_2, void *y_ref);
 }

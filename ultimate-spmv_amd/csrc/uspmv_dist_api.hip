@@ -59,19 +59,19 @@ struct uspmv_dist {
     uspmv_transport_t tr{};           // set-up transport (and the per-step one of USPMV_EXCHANGE_HOST)
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_main = nullptr, ev_comm = nullptr;
-    uspmv_dmat_t *A = nullptr;
-    uspmv_scs_t *scs = nullptr;       // owned when built by uspmv_dist_create_from_coo
-    // adaptive precision ap[dp_sp] (uspmv_dist_create_ap_from_coo): A / scs are the dp part, these the sp part; vectors are double, so pack,
-    // exchange, guard, barrier and capture are the one-precision object's -- only part() and the whole-matrix launch differ
-    uspmv_dmat_t *A_sp = nullptr;
-    uspmv_scs_t *scs_sp = nullptr;
-    double ap_threshold = 0.0;
-    // the kinds with an fp16 part (uspmv_dist_create_ap_hp_from_coo): A / scs are the hi part (F32 for ap[sp_hp], whose vectors are float: dtype
-    // follows it), A_mid / scs_mid the float part of ap[dp_sp_hp] (else NULL), A_hp / scs_hp the fp16 part; A_sp stays NULL
-    uspmv_dmat_t *A_mid = nullptr, *A_hp = nullptr;
-    uspmv_scs_t *scs_mid = nullptr, *scs_hp = nullptr;
-    int ap_kind = -1;                 // uspmv_partition_precisions_hp's kind
-    double ap_threshold_2 = 0.0;
+    // The rank's matrix: one precision, or an adaptive-precision split of kind USPMV_AP_DP_SP | _DP_HP | _SP_HP | _DP_SP_HP (uspmv.h).  Its parts
+    // by slot: pt[0] the hi part (the vectors have its type -- F32 for ap[sp_hp], else F64 -- so pack, exchange, guard, barrier and capture are
+    // the one-precision object's; only part() and the whole-matrix launch differ), pt[1] the float part below it (sp of ap[dp_sp], mid of
+    // ap[dp_sp_hp]), pt[2] the fp16 part.  A slot the kind does not have is NULL; n_pt counts the others.  The handles and structs (and the
+    // halo) are owned when a _from_coo creator built them (owns_setup); uspmv_dist_create lends A and leaves scs NULL.
+    enum { ONE_PRECISION = -1 };
+    struct Part { uspmv_dmat_t *A = nullptr; uspmv_scs_t *scs = nullptr; };
+    int kind = ONE_PRECISION;
+    Part pt[3];
+    int n_pt = 1;
+    uspmv_dmat_t *&A = pt[0].A;       // (the names most of the step knows the hi part by)
+    uspmv_scs_t *&scs = pt[0].scs;
+    double ap_threshold = 0.0, ap_threshold_2 = 0.0;   // the split's thresholds (uspmv_partition_precisions / _hp), for the self-check's reference
     uspmv_halo_t *halo = nullptr;
     uspmv_comm_plan_t *plan = nullptr;
     int dtype = USPMV_F64;
@@ -260,10 +260,11 @@ int sync_reset(uspmv_dist *D) {
     return USPMV_OK;
 }
 
-// an adaptive-precision object of either family
-inline bool is_ap(const uspmv_dist *D) { return D->A_sp || D->A_hp; }
+// an adaptive-precision object; one of a kind with an fp16 part
+inline bool is_ap(const uspmv_dist *D) { return D->kind != uspmv_dist::ONE_PRECISION; }
+inline bool has_hp(const uspmv_dist *D) { return is_ap(D) && D->kind != USPMV_AP_DP_SP; }
 inline const char *ap_name(const uspmv_dist *D) {
-    return !D->A_hp ? "ap[dp_sp]" : D->ap_kind == USPMV_AP_DP_HP ? "ap[dp_hp]" : D->ap_kind == USPMV_AP_SP_HP ? "ap[sp_hp]" : "ap[dp_sp_hp]";
+    return D->kind == USPMV_AP_DP_SP ? "ap[dp_sp]" : D->kind == USPMV_AP_DP_HP ? "ap[dp_hp]" : D->kind == USPMV_AP_SP_HP ? "ap[sp_hp]" : "ap[dp_sp_hp]";
 }
 
 inline bool fused_on(const uspmv_dist *D) { return !is_ap(D) && D->fused && D->overlap && D->tiles && D->d_step && D->sa.n_real + D->sa.n_cond > 0; }
@@ -667,18 +668,20 @@ inline bool eager_only(const uspmv_dist *D) { return D->exchange != USPMV_EXCHAN
 
 int part(uspmv_dist *D, const int32_t *ids, int64_t n, const void *x, void *y, hipStream_t st) {
     if (n == 0) return USPMV_OK;
-    if (D->A_hp)
-        return D->tiles ? uspmv_spmv_ap_hp_tiles(D->A, D->A_mid, D->A_hp, ids, n, x, y, st) : uspmv_spmv_ap_hp_chunks(D->A, D->A_mid, D->A_hp, ids, n, x, y, st);
-    if (D->A_sp)
-        return D->tiles ? uspmv_spmv_ap_tiles(D->A, D->A_sp, ids, n, (const double *)x, (double *)y, st)
-                        : uspmv_spmv_ap_chunks(D->A, D->A_sp, ids, n, (const double *)x, (double *)y, st);
+    const uspmv_dist::Part *p = D->pt;
+    if (has_hp(D))
+        return D->tiles ? uspmv_spmv_ap_hp_tiles(p[0].A, p[1].A, p[2].A, ids, n, x, y, st) : uspmv_spmv_ap_hp_chunks(p[0].A, p[1].A, p[2].A, ids, n, x, y, st);
+    if (is_ap(D))
+        return D->tiles ? uspmv_spmv_ap_tiles(p[0].A, p[1].A, ids, n, (const double *)x, (double *)y, st)
+                        : uspmv_spmv_ap_chunks(p[0].A, p[1].A, ids, n, (const double *)x, (double *)y, st);
     return D->tiles ? uspmv_spmv_tiles(D->A, ids, n, x, y, st) : uspmv_spmv_chunks(D->A, ids, n, x, y, st);
 }
 
 // the whole matrix in one launch
 int whole(uspmv_dist *D, const void *x, void *y, hipStream_t st) {
-    if (D->A_hp) return uspmv_spmv_ap_hp(D->A, D->A_mid, D->A_hp, x, y, st);
-    return D->A_sp ? uspmv_spmv_ap(D->A, D->A_sp, (const double *)x, (double *)y, st) : uspmv_spmv(D->A, x, y, st);
+    const uspmv_dist::Part *p = D->pt;
+    if (has_hp(D)) return uspmv_spmv_ap_hp(p[0].A, p[1].A, p[2].A, x, y, st);
+    return is_ap(D) ? uspmv_spmv_ap(p[0].A, p[1].A, (const double *)x, (double *)y, st) : uspmv_spmv(D->A, x, y, st);
 }
 
 // -ba_synch 1: the barrier the reference issues after every iteration (code/main.cpp:467, :417; default on,
@@ -808,8 +811,10 @@ void uspmv_dist_free(uspmv_dist_t *D) {
     if (D->side_stream) (void)hipStreamDestroy(D->side_stream);
     if (D->comm) (void)ncclCommDestroy(D->comm);
     uspmv_comm_plan_free(D->plan);
-    if (D->owns_setup) { uspmv_dmat_free(D->A); uspmv_dmat_free(D->A_sp); uspmv_halo_free(D->halo); uspmv_scs_free(D->scs); uspmv_scs_free(D->scs_sp);
-                         uspmv_dmat_free(D->A_mid); uspmv_dmat_free(D->A_hp); uspmv_scs_free(D->scs_mid); uspmv_scs_free(D->scs_hp); }
+    if (D->owns_setup) {
+        for (auto &p : D->pt) { uspmv_dmat_free(p.A); uspmv_scs_free(p.scs); }
+        uspmv_halo_free(D->halo);
+    }
     delete D;
 }
 
@@ -856,7 +861,7 @@ static int create_dist(const void *comm_id, int comm_rank, int comm_size, int ra
     D->rank = rank; D->P = P; D->comm_rank = comm_rank; D->comm_size = comm_size; D->loopback = comm_size == 1 && P > 1;   // (host: comm_size == P)
     D->exchange = ex;
     D->A = A; D->dtype = A->dtype; D->tiles = ids_are_tiles != 0;
-    D->pad_split = ap;                // (adaptive precision; the other handles are attached by the caller once it owns the set-up: a failure in here frees the caller's)
+    D->pad_split = ap;                // (adaptive precision: on by default; kind and the other parts are attached by setup_from_coo at its hand-over)
     D->n_local = halo->n_local; D->n_halo = halo->n_halo; D->n_int = n_interior; D->n_bnd = n_boundary;
     D->recv_counts = halo->recv_counts;
     auto bail = [&](int code) { uspmv_dist_free(D); return code; };
@@ -941,106 +946,228 @@ int uspmv_dist_create(const void *comm_id, int comm_rank, int comm_size, int ran
                                 ids_are_tiles, nullptr, out);
 }
 
-int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
-                                  const int32_t *wsa, int64_t C, int64_t sigma, int dtype, int tlc, const uspmv_dist_options_t *opt,
-                                  uspmv_dist_t **out) {
-    if (!local || !wsa || !out) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create_from_coo: NULL argument");
-    if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create_from_coo: bad rank / P");
-    if (dtype != USPMV_F64 && dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create_from_coo: unknown dtype %d", dtype);
+}  // extern "C"
+
+namespace {
+
+// ---- set-up from a rank's COO block (setup_from_coo), for every kind of object
+
+// What the set-up is told about the kind of object it makes; filled in by the public creators below.  What else differs between one
+// precision and the adaptive-precision kinds is marked "one precision:" / "ap kinds:" inside setup_from_coo.
+struct CooSetup {
+    const char *who;                   // the creator's public name: the prefix of every message
+    int kind;                          // uspmv_dist::kind
+    int dtype[3];                      // value type of the part in slot q of uspmv_dist::pt; -1: the kind has no such part
+    double threshold_1, threshold_2;   // of the split (uspmv_partition_precisions / _hp); kept for the self-check's reference
+    const char *refusal;               // what the creator's own check (dtype, kind) objects to, "" if nothing: reported after the NULL and rank checks
+    const char *empty_tail;            // how the "owns no rows" refusal ends
+};
+
+// The units of the step (tiles; chunks without tile lists), ascending, by class: no halo column at all / halo only through the +0.0 padding
+// on one column / real halo references; boundary = the latter two together
+struct StepLists { std::vector<int32_t> interior, boundary, pad, real; };
+
+// A unit is cpt consecutive chunks (1: chunk lists), its class the largest of its chunks' classes (uspmv_scs_classify_chunks)
+StepLists fold_classes(const std::vector<uint8_t> &cls, int64_t cpt, int64_t n_units) {
+    std::vector<uint8_t> uc((size_t)n_units, 0);
+    for (int64_t c = 0; c < (int64_t)cls.size(); ++c) uc[(size_t)(c / cpt)] = std::max(uc[(size_t)(c / cpt)], cls[(size_t)c]);
+    StepLists L;
+    for (int64_t u = 0; u < n_units; ++u) {
+        if (uc[(size_t)u] == 0) L.interior.push_back((int32_t)u);
+        else { L.boundary.push_back((int32_t)u); (uc[(size_t)u] == 1 ? L.pad : L.real).push_back((int32_t)u); }
+    }
+    return L;
+}
+
+// The lists of the padding-tile step (uspmv_dist::d_early): d_pad, d_early = *early, d_late = the real boundary tiles and one conditional
+// entry per padding tile
+hipError_t upload_pad_lists(uspmv_dist *D, const StepLists &L, int32_t pad_col, std::vector<int32_t> *early) {
+    early->resize(L.interior.size() + L.pad.size());
+    std::merge(L.interior.begin(), L.interior.end(), L.pad.begin(), L.pad.end(), early->begin());
+    std::vector<int32_t> late(L.real.size() + L.pad.size(), -1);
+    std::copy(L.real.begin(), L.real.end(), late.begin());
+    hipError_t e = D->d_pad.upload(L.pad.data(), 4 * L.pad.size());
+    if (e == hipSuccess) e = D->d_early.upload(early->data(), 4 * early->size());
+    if (e == hipSuccess) e = D->d_late.upload(late.data(), 4 * late.size());
+    if (e != hipSuccess) return e;
+    D->n_pad = (int64_t)L.pad.size(); D->n_bnd_real = (int64_t)L.real.size(); D->pad_col = pad_col;
+    return hipSuccess;
+}
+
+// The list and the state of the one-launch step (uspmv_dist::d_step): `early` with the late entries -- `real`, then the conditional `cond`
+// -- spliced in
+hipError_t upload_one_launch_lists(uspmv_dist *D, const std::vector<int32_t> &early, const std::vector<int32_t> &real, const std::vector<int32_t> &cond,
+                                   int32_t pad_col) {
+    // the late entries three quarters into the grid: late enough for the exchange to have completed in the common case, early enough
+    // for their slower (system-scope) loads not to be the tail of the launch
+    const size_t late0 = early.size() - early.size() / 4, n_late = real.size() + cond.size();
+    std::vector<int32_t> stepl(early.begin(), early.begin() + (long)late0);
+    stepl.insert(stepl.end(), real.begin(), real.end());
+    stepl.insert(stepl.end(), cond.begin(), cond.end());
+    stepl.insert(stepl.end(), early.begin() + (long)late0, early.end());
+    hipError_t e = D->d_step.upload(stepl.data(), 4 * stepl.size());
+    if (e == hipSuccess) e = D->d_defer.alloc(4 * 2 * std::max<size_t>(n_late, 1));
+    if (e == hipSuccess) e = D->d_ss.alloc(sizeof(uspmv_dev::StepSync));
+    if (e != hipSuccess) return e;
+    D->sa.n_early = (long)early.size(); D->sa.n_real = (long)real.size(); D->sa.n_cond = (long)cond.size(); D->sa.defer_cap = (long)std::max<size_t>(n_late, 1);
+    D->sa.late0 = (long)late0;
+    D->sa.ss = D->d_ss; D->sa.defer = D->d_defer; D->sa.stale = D->d_stale; D->sa.pad_col = pad_col;
+    return hipSuccess;
+}
+
+// uspmv_dist_create_ex on a block given as COO: converts it (one struct, or the two or three of a split), discovers the one halo of all
+// parts, plans, and sorts the tiles (chunks) into the step's lists.  A tile of a split is a tile of ALL parts (same rows), its class the
+// largest of the parts' classes; the lists, the padding column and the guard are then the one-precision object's, in the vector type of the
+// hi part.
+// Why the padding guard stays sufficient for a split: every part pads with (value +0 of its type, global column 0), one slot of one halo
+// numbering.  On the double kinds a padding slot contributes fma(+0.0, x, acc) to its part's chain (the float and fp16 zeros widen to +0.0
+// exactly); on ap[sp_hp] it contributes acc + (double)(0.0f * x) with a float x.  In both, a finite x of unchanged sign gives the same signed
+// zero product, so every chain -- and y, a fixed expression of the chains -- comes out bit for bit as with the delivered value; the guard
+// (pad_guard_kernel<double | float>, by D->dtype) re-runs the padding tiles whenever the kept or the delivered value is not finite or
+// their signs differ.
+int setup_from_coo(const CooSetup &k, const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local, const int32_t *wsa,
+                   int64_t C, int64_t sigma, int tlc, const uspmv_dist_options_t *opt, uspmv_dist_t **out) {
+    const char *who = k.who;
+    const bool ap = k.kind != uspmv_dist::ONE_PRECISION;
+    if (!local || !wsa || !out) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad rank / P", who);
+    if (k.refusal[0]) return uspmv::fail(USPMV_ERR_INVALID, "%s: %s", who, k.refusal);
     // every rank sees the whole work_sharing_arr: a block without rows is refused HERE, by all ranks alike, before the first collective
     // (the conversion of that block would fail on its rank alone and leave the others waiting in the set-up exchange)
     for (int p = 0; p < P; ++p)
         if (wsa[p + 1] <= wsa[p])
-            return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_create_from_coo: block %d of %d owns no rows (work_sharing_arr %d .. %d) -- fewer ranks or another "
-                               "partition (the reference's seg methods only repair an empty LAST block, code/mpi_funcs.hpp:602-606)", p, P, (int)wsa[p], (int)wsa[p + 1]);
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: block %d of %d owns no rows (work_sharing_arr %d .. %d) -- fewer ranks or another partition%s", who, p, P,
+                               (int)wsa[p], (int)wsa[p + 1], k.empty_tail);
     if (int rc = uspmv_dev::require_device()) return rc;
-    uspmv_scs_t *scs = nullptr;
+    uspmv_coo_t *coo[3] = {nullptr, nullptr, nullptr};   // the parts of a split, by slot (one precision converts `local` itself)
+    uspmv_dist::Part pt[3];
     uspmv_halo_t *halo = nullptr;
-    uspmv_dmat_t *A = nullptr;
-    int32_t *interior = nullptr, *boundary = nullptr;
-    auto cleanup = [&]() { uspmv_dmat_free(A); uspmv_halo_free(halo); uspmv_scs_free(scs); uspmv_free(interior); uspmv_free(boundary); };
-    // order of the reference: convert -> halo discovery (rewrites columns) -> column permutation (code/main.cpp:1128, :1271-1308)
-    int rc = uspmv_convert_to_scs(local, C, sigma, dtype, nullptr, &scs);
-    if (!rc) rc = uspmv_halo_discover(scs, wsa, rank, P, &halo);
+    uspmv_dist_t *D = nullptr;
+    auto free_coo = [&]() { for (auto *&c : coo) { uspmv_coo_free(c); c = nullptr; } };
+    // every exit: a failure frees whatever exists by then (D lends A, scs and halo until the hand-over at the very end)
+    auto done = [&](int rc) {
+        free_coo();
+        if (rc == USPMV_OK) return rc;
+        uspmv_dist_free(D);
+        for (auto &p : pt) { uspmv_dmat_free(p.A); uspmv_scs_free(p.scs); }
+        uspmv_halo_free(halo);
+        return rc;
+    };
+    // order of the reference: convert -> halo discovery (rewrites columns) -> column permutation (code/main.cpp:1128, :1271-1308); a split in
+    // the single-GPU order of the host route (host/uspmv_main.cpp): partition, hi, the other parts with hi's permutation
+    int rc = USPMV_OK;
+    if (k.kind == USPMV_AP_DP_SP) rc = uspmv_partition_precisions(local, k.threshold_1, &coo[0], &coo[1]);
+    else if (ap) rc = uspmv_partition_precisions_hp(local, k.kind, k.threshold_1, k.threshold_2, &coo[0], k.dtype[1] >= 0 ? &coo[1] : nullptr, &coo[2]);
     const int32_t *o2n = nullptr;
-    if (!rc) rc = uspmv_scs_arrays(scs, nullptr, nullptr, nullptr, nullptr, &o2n, nullptr);
-    if (!rc) rc = uspmv_permute_scs_cols(scs, o2n);
-    if (!rc) rc = uspmv_dmat_upload(scs, &A);
+    for (int q = 0; q < 3 && !rc; ++q) {
+        if (k.dtype[q] < 0) continue;
+        rc = uspmv_convert_to_scs(ap ? coo[q] : local, C, sigma, k.dtype[q], o2n, &pt[q].scs);
+        if (!rc && q == 0) rc = uspmv_scs_arrays(pt[0].scs, nullptr, nullptr, nullptr, nullptr, &o2n, nullptr);
+    }
+    free_coo();
+    if (!rc) rc = !ap                        ? uspmv_halo_discover(pt[0].scs, wsa, rank, P, &halo)
+                  : k.kind == USPMV_AP_DP_SP ? uspmv_halo_discover_ap(pt[0].scs, pt[1].scs, wsa, rank, P, &halo)
+                                             : uspmv_halo_discover_ap_hp(pt[0].scs, pt[1].scs, pt[2].scs, wsa, rank, P, &halo);
+    for (int q = 0; q < 3 && !rc; ++q)
+        if (pt[q].scs) rc = uspmv_permute_scs_cols(pt[q].scs, o2n);
+    for (int q = 0; q < 3 && !rc; ++q)
+        if (pt[q].scs) rc = uspmv_dmat_upload(pt[q].scs, &pt[q].A);
     int64_t n_tiles = 0, n_staged = 0;
     if (!rc && tlc) {
-        // (a rank's block keeps the 256-row tiles unless its lines ask for more: larger tiles measured level on a block of the 304^3 stencil
-        //  -- 0.1785 / 0.1791 / 0.1822 ms -- and a 512-row tile = a whole sigma window always holds a padded chunk, i.e. no interior tile is left.
-        //  Line tiles in the caller's row order: the tile classes below take tile t for rows [t * tile_rows, (t + 1) * tile_rows), and the
-        //  step kernel has no element plan.)
+        // The (shared) line plan as built, at 256-row tiles in the caller's row order.  A rank's block keeps the 256-row tiles unless its lines
+        // ask for more: larger tiles measured level on a block of the 304^3 stencil -- 0.1785 / 0.1791 / 0.1822 ms -- and a 512-row tile (the
+        // pair's single-GPU size) = a whole sigma window always holds a padded chunk, i.e. no interior tile is left.  The caller's row order:
+        // the tile classes below take tile t for rows [t * tile_rows, (t + 1) * tile_rows) -- a sweep plan's tiles are no row ranges -- and the
+        // step kernel has no element plan.
         const uspmv_dev::TlcPlanOpts as_is{/*measure=*/false, /*elements=*/false, /*deal_rows=*/false, /*additive=*/false};
-        rc = uspmv_dev::dmat_optimize(A, scs, 0, as_is, &n_tiles, &n_staged);
+        rc = !ap                        ? uspmv_dev::dmat_optimize(pt[0].A, pt[0].scs, 0, as_is, &n_tiles, &n_staged)
+             : k.kind == USPMV_AP_DP_SP ? uspmv_dev::dmat_optimize_ap(pt[0].A, pt[1].A, pt[0].scs, pt[1].scs, 0, as_is, &n_tiles, &n_staged)
+                                        : uspmv_dev::dmat_optimize_ap_hp(pt[0].A, pt[1].A, pt[2].A, pt[0].scs, pt[1].scs, pt[2].scs, 0, as_is, &n_tiles, &n_staged);
     }
-    int tile_rows = 0;
-    if (!rc) rc = uspmv_dmat_tile_rows(A, &tile_rows);
+    // chunk classes over all parts.  One padding column for all of them (all pad with global column 0, one halo numbering); if they ever
+    // disagree, no chunk is padding-only
     const int64_t n_local = wsa[rank + 1] - wsa[rank];
-    int64_t n_int = 0, n_bnd = 0;
-    if (!rc) rc = uspmv_scs_split_chunks(scs, n_local, &interior, &n_int, &boundary, &n_bnd);
-    if (rc) { cleanup(); return rc; }
-    std::vector<int32_t> ids_int, ids_bnd, ids_pad, ids_real;
+    std::vector<uint8_t> cls;
     int32_t pad_col = -1;
-    const bool use_tiles = tile_rows > 0 && n_staged > 0 && !A->alt;
-    if (use_tiles) {   // interior / boundary at tile granularity (a tile = tile_rows/C chunks)
-        // three classes per tile: no halo column at all / halo only through the +0.0 padding on one column / real halo references
-        std::vector<uint8_t> cls;
-        rc = uspmv_scs_classify_chunks(scs, n_local, &cls, &pad_col);
-        if (rc) { cleanup(); return rc; }
-        const int64_t cpt = tile_rows / C;
-        std::vector<uint8_t> tc((size_t)n_tiles, 0);
-        for (int64_t c = 0; c < (int64_t)cls.size(); ++c) tc[(size_t)(c / cpt)] = std::max(tc[(size_t)(c / cpt)], cls[(size_t)c]);
-        for (int64_t t = 0; t < n_tiles; ++t) {
-            if (tc[(size_t)t] == 0) ids_int.push_back((int32_t)t);
-            else { ids_bnd.push_back((int32_t)t); (tc[(size_t)t] == 1 ? ids_pad : ids_real).push_back((int32_t)t); }
-        }
-    } else {
-        ids_int.assign(interior, interior + n_int);
-        ids_bnd.assign(boundary, boundary + n_bnd);
+    bool pad_clash = false;
+    for (int q = 0; q < 3 && !rc; ++q) {
+        if (!pt[q].scs) continue;
+        std::vector<uint8_t> cq;
+        int32_t pq = -1;
+        if ((rc = uspmv_scs_classify_chunks(pt[q].scs, n_local, &cq, &pq))) break;
+        if (cls.empty()) cls.assign(cq.size(), 0);
+        for (size_t c = 0; c < cls.size(); ++c) cls[c] = std::max(cls[c], cq[c]);
+        if (pq >= 0) { pad_clash = pad_clash || (pad_col >= 0 && pad_col != pq); pad_col = pq; }
     }
-    uspmv_free(interior); uspmv_free(boundary); interior = boundary = nullptr;
-    uspmv_dist_t *D = nullptr;
-    rc = create_dist(comm_id, comm_rank, comm_size, rank, P, A, halo, o2n, ids_int.data(), (int64_t)ids_int.size(), ids_bnd.data(),
-                     (int64_t)ids_bnd.size(), use_tiles ? 1 : 0, opt, &D, false);
-    if (rc) { cleanup(); return rc; }
-    if (use_tiles && P > 1) {
-        const bool pads = pad_col >= 0 && !ids_pad.empty();
-        if (!pads) { ids_real = ids_bnd; ids_pad.clear(); }
-        std::vector<int32_t> early(ids_int.size() + ids_pad.size()), late(ids_real.size() + ids_pad.size(), -1), stepl;
-        std::merge(ids_int.begin(), ids_int.end(), ids_pad.begin(), ids_pad.end(), early.begin());
-        std::copy(ids_real.begin(), ids_real.end(), late.begin());
-        // the late entries three quarters into the grid: late enough for the exchange to have completed in the common case, early enough
-        // for their slower (system-scope) loads not to be the tail of the launch
-        const size_t late0 = early.size() - early.size() / 4;
-        stepl.assign(early.begin(), early.begin() + (long)late0);
-        stepl.insert(stepl.end(), ids_real.begin(), ids_real.end());
-        stepl.insert(stepl.end(), ids_pad.begin(), ids_pad.end());
-        stepl.insert(stepl.end(), early.begin() + (long)late0, early.end());
-        const size_t n_late = late.size();
-        hipError_t e = D->d_step.upload(stepl.data(), 4 * stepl.size());
-        if (e == hipSuccess && pads) e = D->d_pad.upload(ids_pad.data(), 4 * ids_pad.size());
-        if (e == hipSuccess && pads) e = D->d_early.upload(early.data(), 4 * early.size());
-        if (e == hipSuccess && pads) e = D->d_late.upload(late.data(), 4 * late.size());
-        if (e == hipSuccess) e = D->d_defer.alloc(4 * 2 * std::max<size_t>(n_late, 1));
-        if (e == hipSuccess) e = D->d_ss.alloc(sizeof(uspmv_dev::StepSync));
-        if (e != hipSuccess) {
-            uspmv_dist_free(D); cleanup();
-            return uspmv::fail(USPMV_ERR_ALLOC, "uspmv_dist_create_from_coo: %s", hipGetErrorString(e));
-        }
-        if (pads) { D->n_pad = (int64_t)ids_pad.size(); D->n_bnd_real = (int64_t)ids_real.size(); D->pad_col = pad_col; }
-        D->sa.n_early = (long)early.size(); D->sa.n_real = (long)ids_real.size(); D->sa.n_cond = (long)ids_pad.size(); D->sa.defer_cap = (long)std::max<size_t>(n_late, 1);
-        D->sa.late0 = (long)late0;
-        D->sa.ss = D->d_ss; D->sa.defer = D->d_defer; D->sa.stale = D->d_stale; D->sa.pad_col = pads ? pad_col : -1;
-        if ((rc = sync_reset(D))) { uspmv_dist_free(D); cleanup(); return rc; }
+    if (rc) return done(rc);
+    if (pad_clash) {
+        for (auto &c : cls) if (c == 1) c = 2;
+        pad_col = -1;
     }
-    // (the collective window set-up after every step above that could fail on this rank alone)
+    // tile lists when the plan stages something.  one precision: whatever line plan the handle carries, unless it runs on a re-chunked copy;
+    // ap kinds: only the shared line plan (plan_id != 0)
+    const auto &plan = pt[0].A->tlc;
+    const int tile_rows = plan.on && (!ap || plan.plan_id != 0) ? plan.tile_rows : 0;
+    const bool use_tiles = tile_rows > 0 && n_staged > 0 && (ap || !pt[0].A->alt);
+    // ap kinds: a plan that stages nothing is dropped, so that the whole-matrix launch takes the lane-per-row kernel too
+    if (ap && !use_tiles)
+        for (auto &p : pt) if (p.A && p.A->tlc.on) p.A->tlc = {};
+    const StepLists L = use_tiles ? fold_classes(cls, std::max<int64_t>(tile_rows / C, 1), n_tiles) : fold_classes(cls, 1, (int64_t)cls.size());
+    // (ap kinds: create_dist switches "pad_split" on, and leaves the block-vector split of the hi handle's chunks alone)
+    rc = create_dist(comm_id, comm_rank, comm_size, rank, P, pt[0].A, halo, o2n, L.interior.data(), (int64_t)L.interior.size(), L.boundary.data(),
+                     (int64_t)L.boundary.size(), use_tiles ? 1 : 0, opt, &D, false, ap);
+    if (rc) return done(rc);
+    const bool pads = use_tiles && P > 1 && pad_col >= 0 && !L.pad.empty();
+    std::vector<int32_t> early = L.interior;
+    hipError_t e = pads ? upload_pad_lists(D, L, pad_col, &early) : hipSuccess;
+    // one precision: the one-launch step.  Without padding tiles every boundary tile is a late entry and none is conditional
+    if (!ap && use_tiles && P > 1 && e == hipSuccess)
+        e = upload_one_launch_lists(D, early, pads ? L.real : L.boundary, pads ? L.pad : std::vector<int32_t>(), pads ? pad_col : -1);
+    if (e != hipSuccess) return done(uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e)));
+    if (!ap && (rc = sync_reset(D))) return done(rc);               // (the one-launch step's counters)
+    // the collective window set-up after every step above that could fail on this rank alone
     if (D->exchange == USPMV_EXCHANGE_PEER && P > 1)
-        if ((rc = peer_setup(D, 1))) { uspmv_dist_free(D); cleanup(); return rc; }
-    D->owns_setup = true; D->scs = scs; D->halo = halo;
+        if ((rc = peer_setup(D, 1))) return done(rc);
+    D->owns_setup = true; D->halo = halo;
+    D->kind = k.kind; D->ap_threshold = k.threshold_1; D->ap_threshold_2 = k.threshold_2;
+    D->n_pt = 0;
+    for (int q = 0; q < 3; ++q) { D->pt[q] = pt[q]; D->n_pt += pt[q].A != nullptr; }
     *out = D;
-    return USPMV_OK;
+    return done(USPMV_OK);
+}
+
+}  // namespace
+
+extern "C" {
+
+int uspmv_dist_create_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                  const int32_t *wsa, int64_t C, int64_t sigma, int dtype, int tlc, const uspmv_dist_options_t *opt,
+                                  uspmv_dist_t **out) {
+    char bad[32] = "";
+    if (dtype != USPMV_F64 && dtype != USPMV_F32) snprintf(bad, sizeof bad, "unknown dtype %d", dtype);
+    const CooSetup k{"uspmv_dist_create_from_coo", uspmv_dist::ONE_PRECISION, {dtype, -1, -1}, 0.0, 0.0, bad,
+                     " (the reference's seg methods only repair an empty LAST block, code/mpi_funcs.hpp:602-606)"};
+    return setup_from_coo(k, comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, tlc, opt, out);
+}
+
+// ... for an ap[dp_sp] pair: the dp part, the sp part
+int uspmv_dist_create_ap_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                     const int32_t *wsa, int64_t C, int64_t sigma, double threshold_1, int tlc,
+                                     const uspmv_dist_options_t *opt, uspmv_dist_t **out) {
+    const CooSetup k{"uspmv_dist_create_ap_from_coo", USPMV_AP_DP_SP, {USPMV_F64, USPMV_F32, -1}, threshold_1, 0.0, "", ""};
+    return setup_from_coo(k, comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, tlc, opt, out);
+}
+
+// ... for the kinds with an fp16 part: the hi part (float for ap[sp_hp]), the float part of ap[dp_sp_hp], the fp16 part
+int uspmv_dist_create_ap_hp_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
+                                        const int32_t *wsa, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2, int tlc,
+                                        const uspmv_dist_options_t *opt, uspmv_dist_t **out) {
+    char bad[96] = "";
+    if (kind == USPMV_AP_DP_SP) snprintf(bad, sizeof bad, "ap[dp_sp] has no fp16 part; its object is made by uspmv_dist_create_ap_from_coo");
+    else if (kind != USPMV_AP_DP_HP && kind != USPMV_AP_SP_HP && kind != USPMV_AP_DP_SP_HP) snprintf(bad, sizeof bad, "unknown kind %d", kind);
+    const CooSetup k{"uspmv_dist_create_ap_hp_from_coo", kind, {kind == USPMV_AP_SP_HP ? USPMV_F32 : USPMV_F64, kind == USPMV_AP_DP_SP_HP ? USPMV_F32 : -1, USPMV_F16},
+                     threshold_1, threshold_2, bad, ""};
+    return setup_from_coo(k, comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, tlc, opt, out);
 }
 
 int uspmv_dist_create_from_coo(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
@@ -1048,219 +1175,9 @@ int uspmv_dist_create_from_coo(const void *comm_id, int comm_rank, int comm_size
     return uspmv_dist_create_from_coo_ex(comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, dtype, tlc, nullptr, out);
 }
 
-// uspmv_dist_create_from_coo_ex for an ap[dp_sp] pair.  The tile of a pair is a tile of BOTH parts (same rows), its class the larger of the
-// two parts' classes; the lists, the padding column and the guard are then the one-precision object's.  No one-launch step: no d_step.
-int uspmv_dist_create_ap_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
-                                     const int32_t *wsa, int64_t C, int64_t sigma, double threshold_1, int tlc,
-                                     const uspmv_dist_options_t *opt, uspmv_dist_t **out) {
-    const char *who = "uspmv_dist_create_ap_from_coo";
-    if (!local || !wsa || !out) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
-    if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad rank / P", who);
-    // (refused HERE, by all ranks alike, before the first collective: see uspmv_dist_create_from_coo_ex)
-    for (int p = 0; p < P; ++p)
-        if (wsa[p + 1] <= wsa[p])
-            return uspmv::fail(USPMV_ERR_INVALID, "%s: block %d of %d owns no rows (work_sharing_arr %d .. %d) -- fewer ranks or another partition", who, p, P,
-                               (int)wsa[p], (int)wsa[p + 1]);
-    if (int rc = uspmv_dev::require_device()) return rc;
-    uspmv_coo_t *coo_dp = nullptr, *coo_sp = nullptr;
-    uspmv_scs_t *s_dp = nullptr, *s_sp = nullptr;
-    uspmv_halo_t *halo = nullptr;
-    uspmv_dmat_t *A_dp = nullptr, *A_sp = nullptr;
-    auto cleanup = [&]() {
-        uspmv_coo_free(coo_dp); uspmv_coo_free(coo_sp); coo_dp = coo_sp = nullptr;
-        uspmv_dmat_free(A_dp); uspmv_dmat_free(A_sp); uspmv_halo_free(halo); uspmv_scs_free(s_dp); uspmv_scs_free(s_sp);
-    };
-    // the single-GPU order (host/uspmv_main.cpp) with the halo discovery between conversion and column permutation, as for one struct
-    int rc = uspmv_partition_precisions(local, threshold_1, &coo_dp, &coo_sp);
-    if (!rc) rc = uspmv_convert_to_scs(coo_dp, C, sigma, USPMV_F64, nullptr, &s_dp);
-    const int32_t *o2n = nullptr;
-    if (!rc) rc = uspmv_scs_arrays(s_dp, nullptr, nullptr, nullptr, nullptr, &o2n, nullptr);
-    if (!rc) rc = uspmv_convert_to_scs(coo_sp, C, sigma, USPMV_F32, o2n, &s_sp);
-    uspmv_coo_free(coo_dp); uspmv_coo_free(coo_sp); coo_dp = coo_sp = nullptr;
-    if (!rc) rc = uspmv_halo_discover_ap(s_dp, s_sp, wsa, rank, P, &halo);
-    if (!rc) rc = uspmv_permute_scs_cols(s_dp, o2n);
-    if (!rc) rc = uspmv_permute_scs_cols(s_sp, o2n);
-    if (!rc) rc = uspmv_dmat_upload(s_dp, &A_dp);
-    if (!rc) rc = uspmv_dmat_upload(s_sp, &A_sp);
-    int64_t n_tiles = 0, n_staged = 0;
-    if (!rc && tlc) {
-        // (256-row tiles, not the pair's single-GPU 512: a whole sigma window per tile leaves no interior tile -- see uspmv_dist_create_from_coo_ex)
-        const uspmv_dev::TlcPlanOpts as_is{/*measure=*/false, /*elements=*/false, /*deal_rows=*/false, /*additive=*/false};
-        rc = uspmv_dev::dmat_optimize_ap(A_dp, A_sp, s_dp, s_sp, 0, as_is, &n_tiles, &n_staged);
-    }
-    const int64_t n_local = wsa[rank + 1] - wsa[rank];
-    std::vector<uint8_t> cls, cls_sp;
-    int32_t pad_col = -1, pad_sp = -1;
-    if (!rc) rc = uspmv_scs_classify_chunks(s_dp, n_local, &cls, &pad_col);
-    if (!rc) rc = uspmv_scs_classify_chunks(s_sp, n_local, &cls_sp, &pad_sp);
-    if (rc) { cleanup(); return rc; }
-    // one padding column for both parts (both pad with global column 0, one halo numbering); if they ever disagree, no chunk is padding-only
-    const bool pad_clash = pad_col >= 0 && pad_sp >= 0 && pad_col != pad_sp;
-    if (pad_col < 0) pad_col = pad_sp;
-    for (size_t c = 0; c < cls.size(); ++c) {
-        cls[c] = std::max(cls[c], cls_sp[c]);
-        if (pad_clash && cls[c] == 1) cls[c] = 2;
-    }
-    if (pad_clash) pad_col = -1;
-    const int tile_rows = A_dp->tlc.on && A_dp->tlc.plan_id != 0 ? A_dp->tlc.tile_rows : 0;
-    const bool use_tiles = tile_rows > 0 && n_staged > 0;
-    std::vector<int32_t> ids_int, ids_bnd, ids_pad, ids_real;
-    if (use_tiles) {
-        const int64_t cpt = std::max<int64_t>(tile_rows / C, 1);
-        std::vector<uint8_t> tc((size_t)n_tiles, 0);
-        for (int64_t c = 0; c < (int64_t)cls.size(); ++c) tc[(size_t)(c / cpt)] = std::max(tc[(size_t)(c / cpt)], cls[(size_t)c]);
-        for (int64_t t = 0; t < n_tiles; ++t) {
-            if (tc[(size_t)t] == 0) ids_int.push_back((int32_t)t);
-            else { ids_bnd.push_back((int32_t)t); (tc[(size_t)t] == 1 ? ids_pad : ids_real).push_back((int32_t)t); }
-        }
-    } else {   // chunk lists: a chunk is boundary when it is in either part
-        if (A_dp->tlc.on) { A_dp->tlc = {}; A_sp->tlc = {}; }   // (a plan that stages nothing: the whole-matrix launch takes the lane-per-row kernel too)
-        for (int64_t c = 0; c < (int64_t)cls.size(); ++c) (cls[(size_t)c] ? ids_bnd : ids_int).push_back((int32_t)c);
-    }
-    uspmv_dist_t *D = nullptr;
-    rc = create_dist(comm_id, comm_rank, comm_size, rank, P, A_dp, halo, o2n, ids_int.data(), (int64_t)ids_int.size(), ids_bnd.data(),
-                     (int64_t)ids_bnd.size(), use_tiles ? 1 : 0, opt, &D, false, /*ap=*/true);
-    if (rc) { cleanup(); return rc; }
-    const bool pads = use_tiles && P > 1 && pad_col >= 0 && !ids_pad.empty();
-    if (pads) {
-        std::vector<int32_t> early(ids_int.size() + ids_pad.size()), late(ids_real.size() + ids_pad.size(), -1);
-        std::merge(ids_int.begin(), ids_int.end(), ids_pad.begin(), ids_pad.end(), early.begin());
-        std::copy(ids_real.begin(), ids_real.end(), late.begin());
-        hipError_t e = D->d_pad.upload(ids_pad.data(), 4 * ids_pad.size());
-        if (e == hipSuccess) e = D->d_early.upload(early.data(), 4 * early.size());
-        if (e == hipSuccess) e = D->d_late.upload(late.data(), 4 * late.size());
-        if (e != hipSuccess) {
-            uspmv_dist_free(D); cleanup();
-            return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-        }
-        D->n_pad = (int64_t)ids_pad.size(); D->n_bnd_real = (int64_t)ids_real.size(); D->pad_col = pad_col;
-    }
-    // (the collective window set-up after every step above that could fail on this rank alone)
-    if (D->exchange == USPMV_EXCHANGE_PEER && P > 1)
-        if ((rc = peer_setup(D, 1))) { uspmv_dist_free(D); cleanup(); return rc; }
-    D->owns_setup = true; D->scs = s_dp; D->scs_sp = s_sp; D->halo = halo; D->A_sp = A_sp; D->ap_threshold = threshold_1;
-    *out = D;
-    return USPMV_OK;
-}
-
 int uspmv_dist_create_ap_from_coo(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
                                   const int32_t *wsa, int64_t C, int64_t sigma, double threshold_1, int tlc, uspmv_dist_t **out) {
     return uspmv_dist_create_ap_from_coo_ex(comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, threshold_1, tlc, nullptr, out);
-}
-
-// uspmv_dist_create_ap_from_coo_ex for the kinds with an fp16 part.  A tile is a tile of ALL parts (same rows), its class the largest of the
-// parts' classes; lists, padding column and guard are then the one-precision object's, in the vector type of the hi part.
-// Why the padding guard stays sufficient: every part pads with (value +0 of its type, global column 0), one slot of one halo numbering.  On
-// the double kinds a padding slot contributes fma(+0.0, x, acc) to its part's chain (the float and fp16 zeros widen to +0.0 exactly); on
-// ap[sp_hp] it contributes acc + (double)(0.0f * x) with a float x.  In both, a finite x of unchanged sign gives the same signed zero product,
-// so every chain -- and y, a fixed expression of the chains -- comes out bit for bit as with the delivered value; the guard
-// (pad_guard_kernel<double | float>, by D->dtype) re-runs the padding tiles whenever the kept or the delivered value is not finite or
-// their signs differ.
-int uspmv_dist_create_ap_hp_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
-                                        const int32_t *wsa, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2, int tlc,
-                                        const uspmv_dist_options_t *opt, uspmv_dist_t **out) {
-    const char *who = "uspmv_dist_create_ap_hp_from_coo";
-    if (!local || !wsa || !out) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
-    if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad rank / P", who);
-    if (kind == USPMV_AP_DP_SP) return uspmv::fail(USPMV_ERR_INVALID, "%s: ap[dp_sp] has no fp16 part; its object is made by uspmv_dist_create_ap_from_coo", who);
-    if (kind != USPMV_AP_DP_HP && kind != USPMV_AP_SP_HP && kind != USPMV_AP_DP_SP_HP) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown kind %d", who, kind);
-    // (refused HERE, by all ranks alike, before the first collective: see uspmv_dist_create_from_coo_ex)
-    for (int p = 0; p < P; ++p)
-        if (wsa[p + 1] <= wsa[p])
-            return uspmv::fail(USPMV_ERR_INVALID, "%s: block %d of %d owns no rows (work_sharing_arr %d .. %d) -- fewer ranks or another partition", who, p, P,
-                               (int)wsa[p], (int)wsa[p + 1]);
-    if (int rc = uspmv_dev::require_device()) return rc;
-    const bool three = kind == USPMV_AP_DP_SP_HP;
-    uspmv_coo_t *coo[3] = {nullptr, nullptr, nullptr};           // hi, mid, hp
-    uspmv_scs_t *s[3] = {nullptr, nullptr, nullptr};
-    uspmv_dmat_t *A[3] = {nullptr, nullptr, nullptr};
-    uspmv_halo_t *halo = nullptr;
-    auto free_coo = [&]() { for (auto *&c : coo) { uspmv_coo_free(c); c = nullptr; } };
-    auto cleanup = [&]() {
-        free_coo();
-        for (int q = 0; q < 3; ++q) { uspmv_dmat_free(A[q]); uspmv_scs_free(s[q]); }
-        uspmv_halo_free(halo);
-    };
-    // the single-GPU order of the host route (partition, hi, the other parts with hi's permutation) with the halo discovery between
-    // conversion and column permutation, as for one struct
-    int rc = uspmv_partition_precisions_hp(local, kind, threshold_1, threshold_2, &coo[0], three ? &coo[1] : nullptr, &coo[2]);
-    if (!rc) rc = uspmv_convert_to_scs(coo[0], C, sigma, kind == USPMV_AP_SP_HP ? USPMV_F32 : USPMV_F64, nullptr, &s[0]);
-    const int32_t *o2n = nullptr;
-    if (!rc) rc = uspmv_scs_arrays(s[0], nullptr, nullptr, nullptr, nullptr, &o2n, nullptr);
-    if (!rc && three) rc = uspmv_convert_to_scs(coo[1], C, sigma, USPMV_F32, o2n, &s[1]);
-    if (!rc) rc = uspmv_convert_to_scs(coo[2], C, sigma, USPMV_F16, o2n, &s[2]);
-    free_coo();
-    if (!rc) rc = uspmv_halo_discover_ap_hp(s[0], s[1], s[2], wsa, rank, P, &halo);
-    for (int q = 0; q < 3 && !rc; ++q)
-        if (s[q]) rc = uspmv_permute_scs_cols(s[q], o2n);
-    for (int q = 0; q < 3 && !rc; ++q)
-        if (s[q]) rc = uspmv_dmat_upload(s[q], &A[q]);
-    int64_t n_tiles = 0, n_staged = 0;
-    if (!rc && tlc) {
-        // (the shared line plan as built, at 256-row tiles in the caller's row order: a sweep plan's tiles are no row ranges -- see uspmv_dist_create_from_coo_ex)
-        const uspmv_dev::TlcPlanOpts as_is{/*measure=*/false, /*elements=*/false, /*deal_rows=*/false, /*additive=*/false};
-        rc = uspmv_dev::dmat_optimize_ap_hp(A[0], A[1], A[2], s[0], s[1], s[2], 0, as_is, &n_tiles, &n_staged);
-    }
-    const int64_t n_local = wsa[rank + 1] - wsa[rank];
-    // one padding column for all parts (all pad with global column 0, one halo numbering); if they ever disagree, no chunk is padding-only
-    std::vector<uint8_t> cls;
-    int32_t pad_col = -1;
-    bool pad_clash = false;
-    for (int q = 0; q < 3 && !rc; ++q) {
-        if (!s[q]) continue;
-        std::vector<uint8_t> cq;
-        int32_t pq = -1;
-        rc = uspmv_scs_classify_chunks(s[q], n_local, &cq, &pq);
-        if (rc) break;
-        if (cls.empty()) cls.assign(cq.size(), 0);
-        for (size_t c = 0; c < cls.size(); ++c) cls[c] = std::max(cls[c], cq[c]);
-        if (pq >= 0) { pad_clash = pad_clash || (pad_col >= 0 && pad_col != pq); pad_col = pq; }
-    }
-    if (rc) { cleanup(); return rc; }
-    if (pad_clash) {
-        for (auto &c : cls) if (c == 1) c = 2;
-        pad_col = -1;
-    }
-    const int tile_rows = A[0]->tlc.on && A[0]->tlc.plan_id != 0 ? A[0]->tlc.tile_rows : 0;
-    const bool use_tiles = tile_rows > 0 && n_staged > 0;
-    std::vector<int32_t> ids_int, ids_bnd, ids_pad, ids_real;
-    if (use_tiles) {
-        const int64_t cpt = std::max<int64_t>(tile_rows / C, 1);
-        std::vector<uint8_t> tc((size_t)n_tiles, 0);
-        for (int64_t c = 0; c < (int64_t)cls.size(); ++c) tc[(size_t)(c / cpt)] = std::max(tc[(size_t)(c / cpt)], cls[(size_t)c]);
-        for (int64_t t = 0; t < n_tiles; ++t) {
-            if (tc[(size_t)t] == 0) ids_int.push_back((int32_t)t);
-            else { ids_bnd.push_back((int32_t)t); (tc[(size_t)t] == 1 ? ids_pad : ids_real).push_back((int32_t)t); }
-        }
-    } else {   // chunk lists: a chunk is boundary when it is in any part
-        for (auto *M : A) if (M && M->tlc.on) M->tlc = {};   // (a plan that stages nothing: the whole-matrix launch takes the lane-per-row kernel too)
-        for (int64_t c = 0; c < (int64_t)cls.size(); ++c) (cls[(size_t)c] ? ids_bnd : ids_int).push_back((int32_t)c);
-    }
-    uspmv_dist_t *D = nullptr;
-    rc = create_dist(comm_id, comm_rank, comm_size, rank, P, A[0], halo, o2n, ids_int.data(), (int64_t)ids_int.size(), ids_bnd.data(),
-                     (int64_t)ids_bnd.size(), use_tiles ? 1 : 0, opt, &D, false, /*ap=*/true);
-    if (rc) { cleanup(); return rc; }
-    const bool pads = use_tiles && P > 1 && pad_col >= 0 && !ids_pad.empty();
-    if (pads) {
-        std::vector<int32_t> early(ids_int.size() + ids_pad.size()), late(ids_real.size() + ids_pad.size(), -1);
-        std::merge(ids_int.begin(), ids_int.end(), ids_pad.begin(), ids_pad.end(), early.begin());
-        std::copy(ids_real.begin(), ids_real.end(), late.begin());
-        hipError_t e = D->d_pad.upload(ids_pad.data(), 4 * ids_pad.size());
-        if (e == hipSuccess) e = D->d_early.upload(early.data(), 4 * early.size());
-        if (e == hipSuccess) e = D->d_late.upload(late.data(), 4 * late.size());
-        if (e != hipSuccess) {
-            uspmv_dist_free(D); cleanup();
-            return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-        }
-        D->n_pad = (int64_t)ids_pad.size(); D->n_bnd_real = (int64_t)ids_real.size(); D->pad_col = pad_col;
-    }
-    // (the collective window set-up after every step above that could fail on this rank alone)
-    if (D->exchange == USPMV_EXCHANGE_PEER && P > 1)
-        if ((rc = peer_setup(D, 1))) { uspmv_dist_free(D); cleanup(); return rc; }
-    D->owns_setup = true; D->scs = s[0]; D->scs_mid = s[1]; D->scs_hp = s[2]; D->halo = halo; D->A_mid = A[1]; D->A_hp = A[2];
-    D->ap_kind = kind; D->ap_threshold = threshold_1; D->ap_threshold_2 = threshold_2;
-    *out = D;
-    return USPMV_OK;
 }
 
 int uspmv_dist_create_ap_hp_from_coo(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
@@ -1277,12 +1194,10 @@ int uspmv_dist_comm_plan(const uspmv_dist_t *D, int64_t *n_send, const int64_t *
 int uspmv_dist_set_option(uspmv_dist_t *D, const char *key, int value) {
     if (!D || !key) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_set_option: NULL argument");
     const std::string k(key);
-    if (D->A_hp && (((k == "fused_step" || k == "autotune_all") && value != 0) || (k == "block_plan" && value > 0)))
+    if (is_ap(D) && (((k == "fused_step" || k == "autotune_all") && value != 0) || (k == "block_plan" && value > 0)))
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_set_option: '%s' is not available on an adaptive-precision (%s) object: its step has "
-                           "the overlap, plain and pad_split forms, and it has no block-vector step", key, ap_name(D));
-    if (D->A_sp && (((k == "fused_step" || k == "autotune_all") && value != 0) || (k == "block_plan" && value > 0)))
-        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_set_option: '%s' is not available on an adaptive-precision (ap[dp_sp]) object: its step has "
-                           "the overlap, plain and pad_split forms; block vectors run through uspmv_dist_spmmv_ap", key);
+                           "the overlap, plain and pad_split forms%s", key, ap_name(D),
+                           has_hp(D) ? ", and it has no block-vector step" : "; block vectors run through uspmv_dist_spmmv_ap");
     if (k == "overlap") { if ((value != 0) != D->overlap) drop_graph(D); D->overlap = value != 0; }
     else if (k == "no_pack") { if ((value != 0) != D->no_pack) drop_graph(D); D->no_pack = value != 0; }
     else if (k == "ba_synch") { if ((value != 0) != D->ba_synch) drop_graph(D); D->ba_synch = value != 0; }
@@ -1367,11 +1282,11 @@ int uspmv_dist_parts(const uspmv_dist_t *D, const uspmv_scs_t **scs, const uspmv
 int uspmv_dist_parts_ap(const uspmv_dist_t *D, const uspmv_scs_t **scs_dp, const uspmv_scs_t **scs_sp, const uspmv_dmat_t **A_dp,
                         const uspmv_dmat_t **A_sp, const uspmv_halo_t **halo) {
     if (!D) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap: NULL argument");
-    if (D->A_hp) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap: an %s object (its parts: uspmv_dist_parts_ap_hp)", ap_name(D));
-    if (scs_dp) *scs_dp = D->scs;
-    if (scs_sp) *scs_sp = D->scs_sp;
-    if (A_dp) *A_dp = D->A;
-    if (A_sp) *A_sp = D->A_sp;
+    if (has_hp(D)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap: an %s object (its parts: uspmv_dist_parts_ap_hp)", ap_name(D));
+    if (scs_dp) *scs_dp = D->pt[0].scs;
+    if (scs_sp) *scs_sp = D->pt[1].scs;
+    if (A_dp) *A_dp = D->pt[0].A;
+    if (A_sp) *A_sp = D->pt[1].A;
     if (halo) *halo = D->halo;
     return USPMV_OK;
 }
@@ -1379,14 +1294,14 @@ int uspmv_dist_parts_ap(const uspmv_dist_t *D, const uspmv_scs_t **scs_dp, const
 int uspmv_dist_parts_ap_hp(const uspmv_dist_t *D, int *kind, const uspmv_scs_t **scs_hi, const uspmv_scs_t **scs_mid, const uspmv_scs_t **scs_hp,
                            const uspmv_dmat_t **A_hi, const uspmv_dmat_t **A_mid, const uspmv_dmat_t **A_hp, const uspmv_halo_t **halo) {
     if (!D) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap_hp: NULL argument");
-    if (!D->A_hp) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap_hp: not an object made by uspmv_dist_create_ap_hp_from_coo");
-    if (kind) *kind = D->ap_kind;
-    if (scs_hi) *scs_hi = D->scs;
-    if (scs_mid) *scs_mid = D->scs_mid;
-    if (scs_hp) *scs_hp = D->scs_hp;
-    if (A_hi) *A_hi = D->A;
-    if (A_mid) *A_mid = D->A_mid;
-    if (A_hp) *A_hp = D->A_hp;
+    if (!has_hp(D)) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_parts_ap_hp: not an object made by uspmv_dist_create_ap_hp_from_coo");
+    if (kind) *kind = D->kind;
+    if (scs_hi) *scs_hi = D->pt[0].scs;
+    if (scs_mid) *scs_mid = D->pt[1].scs;
+    if (scs_hp) *scs_hp = D->pt[2].scs;
+    if (A_hi) *A_hi = D->pt[0].A;
+    if (A_mid) *A_mid = D->pt[1].A;
+    if (A_hp) *A_hp = D->pt[2].A;
     if (halo) *halo = D->halo;
     return USPMV_OK;
 }
@@ -1580,9 +1495,9 @@ int uspmv_dist_check(uspmv_dist_t *D, const uspmv_coo_t *local, const int32_t *w
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(hy.data(), d_y, (size_t)D->n_rows_padded * vsz, hipMemcpyDeviceToHost));
     std::vector<char> ref((size_t)std::max<int64_t>(nl, 1) * vsz);
-    if (int rc = D->A_hp ? uspmv::dist_reference_rows_ap_hp(local, wsa, D->P, D->rank, D->loopback, D->ap_kind, D->ap_threshold, D->ap_threshold_2, ref.data())
-                 : D->A_sp ? uspmv::dist_reference_rows_ap(local, wsa, D->P, D->rank, D->loopback, D->ap_threshold, (double *)ref.data())
-                         : uspmv::dist_reference_rows(local, wsa, D->P, D->rank, D->loopback, D->dtype, ref.data()))
+    if (int rc = has_hp(D) ? uspmv::dist_reference_rows_ap_hp(local, wsa, D->P, D->rank, D->loopback, D->kind, D->ap_threshold, D->ap_threshold_2, ref.data())
+                 : is_ap(D) ? uspmv::dist_reference_rows_ap(local, wsa, D->P, D->rank, D->loopback, D->ap_threshold, (double *)ref.data())
+                            : uspmv::dist_reference_rows(local, wsa, D->P, D->rank, D->loopback, D->dtype, ref.data()))
         return rc;
     int64_t bad = 0;
     double sum = 0.0;
@@ -1598,8 +1513,9 @@ int uspmv_dist_check(uspmv_dist_t *D, const uspmv_coo_t *local, const int32_t *w
 
 int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
     if (!D || !d_X || !d_Y || b < 1) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: bad argument");
-    if (D->A_hp) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: not available on an adaptive-precision (%s) object (no block-vector step across ranks yet)", ap_name(D));
-    if (D->A_sp) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: not available on an adaptive-precision (ap[dp_sp]) object (its block step is uspmv_dist_spmmv_ap)");
+    if (is_ap(D))
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: not available on an adaptive-precision (%s) object (%s)", ap_name(D),
+                           has_hp(D) ? "no block-vector step across ranks yet" : "its block step is uspmv_dist_spmmv_ap");
     if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown layout %d", layout);
     if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown mode %d", mode);
     if (layout == USPMV_ROWWISE && mode != USPMV_BULKVEC)
@@ -1648,19 +1564,19 @@ int uspmv_dist_spmmv_ap(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout
     if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown layout %d", who, layout);
     if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown mode %d", who, mode);
     if (!D || !d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
-    if (D->A_hp) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: an adaptive-precision %s object (no block-vector step across ranks yet)", who, ap_name(D));
-    if (!D->A_sp)
+    if (has_hp(D)) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: an adaptive-precision %s object (no block-vector step across ranks yet)", who, ap_name(D));
+    if (!is_ap(D))
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: a one-precision object (uspmv_dist_create_from_coo); its block step is uspmv_dist_spmmv", who);
     if (layout == USPMV_ROWWISE && mode != USPMV_BULKVEC)
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: row-wise block vectors travel in one message per neighbour (bulkvec) only", who);
     hipStream_t main = (hipStream_t)stream;
     if (b == 1) { ++D->eager_steps; return step(D, d_X, d_Y, main, comm_halos != 0); }
     const int64_t ld = D->vec_len;
-    if (!(D->P > 1 && comm_halos)) return uspmv_spmmv_ap(D->A, D->A_sp, d_X, d_Y, b, ld, layout, stream);
+    if (!(D->P > 1 && comm_halos)) return uspmv_spmmv_ap(D->pt[0].A, D->pt[1].A, d_X, d_Y, b, ld, layout, stream);
     if ((int64_t)b * std::max(ld, (int64_t)1) > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: b * padded_vec_size exceeds int32", who);
     if (!D->overlap) {
         if (int rc = block_exchange(D, d_X, b, layout, mode, main, who)) return rc;
-        if (int rc = uspmv_spmmv_ap(D->A, D->A_sp, d_X, d_Y, b, ld, layout, stream)) return rc;
+        if (int rc = uspmv_spmmv_ap(D->pt[0].A, D->pt[1].A, d_X, d_Y, b, ld, layout, stream)) return rc;
         ++D->spmmv_one_part;
         return step_barrier(D, main);
     }
@@ -1672,8 +1588,8 @@ int uspmv_dist_spmmv_ap(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout
     }
     auto part_b = [&](const int32_t *ids, int64_t n, hipStream_t st) -> int {
         if (n == 0) return USPMV_OK;
-        return D->tiles ? uspmv_spmmv_ap_tiles(D->A, D->A_sp, ids, n, d_X, d_Y, b, ld, layout, st)
-                        : uspmv_spmmv_ap_chunks(D->A, D->A_sp, ids, n, d_X, d_Y, b, ld, layout, st);
+        return D->tiles ? uspmv_spmmv_ap_tiles(D->pt[0].A, D->pt[1].A, ids, n, d_X, d_Y, b, ld, layout, st)
+                        : uspmv_spmmv_ap_chunks(D->pt[0].A, D->pt[1].A, ids, n, d_X, d_Y, b, ld, layout, st);
     };
     HIP_TRY(hipEventRecord(D->ev_main, main));                       // fork, join and the lists: those of step()
     HIP_TRY(hipStreamWaitEvent(D->side_stream, D->ev_main, 0));

@@ -45,10 +45,16 @@ static void rows(const uspmv_coo *m, const int32_t *wsa, int P, int rank, bool l
     }
 }
 
-int dist_reference_rows(const uspmv_coo *local, const int32_t *wsa, int P, int rank, bool loopback, int dtype, void *y_ref) {
+// what every reference below asks of its block: the arguments, and row ids inside the block (rows() indexes y by them)
+static int check_block(const uspmv_coo *local, const int32_t *wsa, const void *y_ref) {
     if (!local || !wsa || !y_ref) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: NULL argument");
     for (int64_t k = 0; k < local->nnz; ++k)
         if (local->I[(size_t)k] < 0 || local->I[(size_t)k] >= local->n_rows) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: row id outside the block");
+    return USPMV_OK;
+}
+
+int dist_reference_rows(const uspmv_coo *local, const int32_t *wsa, int P, int rank, bool loopback, int dtype, void *y_ref) {
+    if (int rc = check_block(local, wsa, y_ref)) return rc;
     if (dtype == USPMV_F64) rows<double>(local, wsa, P, rank, loopback, (double *)y_ref);
     else rows<float>(local, wsa, P, rank, loopback, (float *)y_ref);
     return USPMV_OK;
@@ -56,9 +62,7 @@ int dist_reference_rows(const uspmv_coo *local, const int32_t *wsa, int P, int r
 
 // ap[dp_sp]: the block split as the object's set-up splits it (the sp part holds (double)(float)v), one chain per part, y = dp + sp
 int dist_reference_rows_ap(const uspmv_coo *local, const int32_t *wsa, int P, int rank, bool loopback, double threshold_1, double *y_ref) {
-    if (!local || !wsa || !y_ref) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: NULL argument");
-    for (int64_t k = 0; k < local->nnz; ++k)
-        if (local->I[(size_t)k] < 0 || local->I[(size_t)k] >= local->n_rows) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: row id outside the block");
+    if (int rc = check_block(local, wsa, y_ref)) return rc;
     uspmv_coo *dp = nullptr, *sp = nullptr;
     if (int rc = uspmv_partition_precisions(local, threshold_1, &dp, &sp)) return rc;
     std::vector<double> ys((size_t)std::max<int64_t>(local->n_rows, 1));
@@ -84,9 +88,7 @@ static void rows_float_products(const uspmv_coo *m, const int32_t *wsa, int P, i
 // values rounded once to binary16), the numerics of uspmv_spmv_ap_hp
 int dist_reference_rows_ap_hp(const uspmv_coo *local, const int32_t *wsa, int P, int rank, bool loopback, int kind, double threshold_1,
                               double threshold_2, void *y_ref) {
-    if (!local || !wsa || !y_ref) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: NULL argument");
-    for (int64_t k = 0; k < local->nnz; ++k)
-        if (local->I[(size_t)k] < 0 || local->I[(size_t)k] >= local->n_rows) return fail(USPMV_ERR_INVALID, "uspmv_dist_check: row id outside the block");
+    if (int rc = check_block(local, wsa, y_ref)) return rc;
     uspmv_coo *hi = nullptr, *mid = nullptr, *hp = nullptr;
     if (int rc = uspmv_partition_precisions_hp(local, kind, threshold_1, threshold_2, &hi, kind == USPMV_AP_DP_SP_HP ? &mid : nullptr, &hp)) return rc;
     const int64_t n = local->n_rows;

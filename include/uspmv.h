@@ -519,6 +519,30 @@ int uspmv_spmmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const usp
  * Same argument checks and error texts as uspmv_spmmv_ap_hp (under this function's name); nothing is launched. */
 int uspmv_spmmv_ap_hp_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout, int *path,
                            int *vectors_per_pass);
+/* uspmv_spmmv_ap_hp restricted to a subset of the rows, for the distributed block step of the kinds with an fp16 part
+ * (uspmv_dist_spmmv_ap_hp): the block twins of uspmv_spmv_ap_hp_tiles / _chunks and the twins of uspmv_spmmv_ap_tiles / _chunks / _tiles_path
+ * for these kinds.  Handles as for uspmv_spmmv_ap_hp (mid NULL for the two-part kinds), X and Y in the type of the hi part, layouts and ld
+ * as there.  Every row written carries, in every column, the bits uspmv_spmmv_ap_hp gives it (one lane per row, every chain in slot order,
+ * (hi + mid) folded before the hp chain); rows outside the list are not touched.  Entries < 0 are skipped (a conditional list);
+ * n_ids == 0 is USPMV_OK and launches nothing.
+ * _tiles: the tiles of the parts' shared tile-local-column plan (tile t = rows [t * tile_rows, (t + 1) * tile_rows)); parts without one --
+ *   planless ones, and those that carry a column-window sweep plan instead -- are refused ("no shared tile-local-column plan").
+ *   b in {2, 4, 8, 16}, X and Y 16-byte aligned, "tlc" 1, "spmmv_variant" not 1 and room for two vectors of the fullest tile in LDS:
+ *   workgroup g runs tile d_tile_ids[g] with the staged kernel of uspmv_spmmv_ap_hp, X staged straight from either layout.  Column-major
+ *   X is taken at EVERY ld: where ld * sizeof(element) is no multiple of 16 -- a rank's padded_vec_size is whatever its halo makes it -- the
+ *   columns are staged in the widest pieces all of them start aligned to (8 bytes for double X and for float X with ld % 4 == 2, 4 bytes
+ *   for float X with an odd ld), a wave's loads of one column's line running over consecutive addresses.  Otherwise lane per row over
+ *   the tiles' rows.
+ * _chunks: chunk ids, lane per row, any such handles, any b, layout and alignment.
+ * _tiles_path: what _tiles would run for 16-byte-aligned X and Y under the current tuning -- *path 2 the staged kernel
+ *   (*vectors_per_pass of the b vectors per pass over the entries), 0 lane per row (*vectors_per_pass 0).  The checks and error texts of
+ *   _tiles under this function's name; nothing is launched. */
+int uspmv_spmmv_ap_hp_tiles(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const int32_t *d_tile_ids, int64_t n_ids,
+                            const void *d_X, void *d_Y, int b, int64_t ld, int layout, void *stream);
+int uspmv_spmmv_ap_hp_chunks(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const int32_t *d_chunk_ids, int64_t n_ids,
+                             const void *d_X, void *d_Y, int b, int64_t ld, int layout, void *stream);
+int uspmv_spmmv_ap_hp_tiles_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout,
+                                 int *path, int *vectors_per_pass);
 /* The largest max_lines a caller can pass to uspmv_dmat_optimize_ap_hp / _device_ap_hp for which the staged kernel of uspmv_spmmv_ap_hp
  * applies at width b whatever the matrix: two vectors of the fullest tile (16 X rows per line) in the 160 KiB of LDS -- 640 for
  * x_dtype USPMV_F64 and 1280 for USPMV_F32 at b in {2, 4, 8, 16}, 0 for every other b.  b < 1, another dtype or a NULL pointer is refused. */
@@ -765,7 +789,7 @@ int uspmv_dist_create_ap_from_coo_ex(const void *comm_id, int comm_rank, int com
  * guard and self-check then work on floats), double otherwise.  The step is uspmv_spmv_ap_hp split into interior and boundary tiles
  * (uspmv_spmv_ap_hp_tiles / _chunks) in the overlap, plain and "pad_split" forms ("pad_split" defaults to 1), eager or captured, over every
  * exchange.  "fused_step" 1, "autotune_all" 1, "block_plan" b > 0, uspmv_dist_spmmv and uspmv_dist_spmmv_ap answer USPMV_ERR_UNSUPPORTED
- * with the kind's name: block vectors for these kinds do not run across ranks yet. */
+ * with the kind's name: block vectors for these kinds run through uspmv_dist_spmmv_ap_hp. */
 int uspmv_dist_create_ap_hp_from_coo(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
                                      const int32_t *wsa, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2, int tlc,
                                      uspmv_dist_t **out);
@@ -883,6 +907,13 @@ int uspmv_dist_spmmv(uspmv_dist_t *d, void *d_X, void *d_Y, int b, int layout, i
  * uspmv_dist_spmmv_info counts these steps.  uspmv_dist_spmmv itself, "block_plan", "fused_step" and "autotune_all" stay refused on
  * an ap object. */
 int uspmv_dist_spmmv_ap(uspmv_dist_t *d, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream);
+/* ... and for an object of a kind with an fp16 part (uspmv_dist_create_ap_hp_from_coo): the same step with the same arguments and forms,
+ * X and Y in the object's vector type (float for ap[sp_hp], else double), over uspmv_spmmv_ap_hp and its list forms
+ * (uspmv_spmmv_ap_hp_tiles / _chunks).  Column-wise X is staged at every padded_vec_size (see uspmv_spmmv_ap_hp_tiles).  The padding
+ * guard keeps and compares values of the vector type, under the same rule.  Column v of Y is what uspmv_dist_spmv gives for column v
+ * of X, in every arrangement.  A one-precision object and an ap[dp_sp] object are refused with USPMV_ERR_UNSUPPORTED and the name of
+ * their own entry point; "block_plan", "fused_step" and "autotune_all" stay refused on these objects. */
+int uspmv_dist_spmmv_ap_hp(uspmv_dist_t *d, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream);
 /* Padding tiles of the single-vector step (tile lists, "pad_split" 1; an option, off by default -- see DESIGN 6.4 for the A/B).  The reference pads chunks with (value +0, column 0);
  * on every rank but the first, column 0 is a halo column (code/mpi_funcs.hpp:279-306), so most tiles of a rank touch the halo only
  * through fma(+0, x[pad_col], acc).  They run with the interior tiles, before the exchange has delivered x[pad_col]: for finite

@@ -189,6 +189,9 @@ _SIGS = {
                                                   C.POINTER(_vp)]),
     "uspmv_spmv_ap_hp_tiles": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "uspmv_spmv_ap_hp_chunks": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "uspmv_spmmv_ap_hp_tiles": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
+    "uspmv_spmmv_ap_hp_chunks": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
+    "uspmv_spmmv_ap_hp_tiles_path": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "uspmv_halo_discover_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "uspmv_dist_check_reference_ap_hp": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),
     "uspmv_dist_create_ap_hp_from_coo": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _i64, C.c_int, C.c_double, C.c_double,
@@ -203,6 +206,7 @@ _SIGS = {
     "uspmv_dist_run": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "uspmv_dist_spmmv": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "uspmv_dist_spmmv_ap": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "uspmv_dist_spmmv_ap_hp": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "uspmv_dist_barrier": (C.c_int, [_vp, _vp]),
     "uspmv_dist_allreduce_max": (C.c_int, [_vp, C.POINTER(C.c_double), _vp]),
     "uspmv_dist_allgather_i64": (C.c_int, [_vp, _i64, C.POINTER(_i64), _vp]),
@@ -834,6 +838,19 @@ class DistNative:
         self._order(X, Y)
         _ck(lib().uspmv_dist_spmmv_ap(self.h, _dp(X), _dp(Y), int(b), int(layout), int(mode), int(bool(comm_halos)), self.stream.cuda_stream))
         return Y
+
+    def spmmv_ap_hp(self, X, Y, b, layout=COLWISE, mode=0, comm_halos=True):
+        """spmmv on an object of a kind with an fp16 part (uspmv_dist_spmmv_ap_hp): X, Y in self.tdtype (new_X builds such an X), column v
+        of Y bitwise what spmv gives for column v of X."""
+        self._order(X, Y)
+        _ck(lib().uspmv_dist_spmmv_ap_hp(self.h, _dp(X), _dp(Y), int(b), int(layout), int(mode), int(bool(comm_halos)), self.stream.cuda_stream))
+        return Y
+
+    def spmmv_ap_hp_tiles_path(self, b, layout=COLWISE):
+        """(path, vectors) of the tile lists of spmmv_ap_hp at width b on this object's parts and padded_vec_size (uspmv_spmmv_ap_hp_tiles_path)"""
+        path, vec = C.c_int(), C.c_int()
+        _ck(lib().uspmv_spmmv_ap_hp_tiles_path(self._A, self._A_mid, self._A_hp, int(b), self.padded_vec_size, int(layout), C.byref(path), C.byref(vec)))
+        return path.value, vec.value
 
     STEP_FORMS = ("overlap", "plain", "pad", "fused")
 
@@ -1489,6 +1506,29 @@ def spmmv_ap_hp_path(A_hi, A_mid, A_hp, b, ld, layout=COLWISE):
     path, vec = C.c_int(), C.c_int()
     _ck(lib().uspmv_spmmv_ap_hp_path(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, int(b), int(ld), int(layout), C.byref(path),
                                      C.byref(vec)))
+    return path.value, vec.value
+
+
+def spmmv_ap_hp_tiles(A_hi, A_mid, A_hp, tile_ids, X, Y, b, ld, layout=COLWISE, stream=None):
+    """spmmv_ap_hp over the tiles in tile_ids (int32 tensor; entries < 0 skipped) of the parts' shared plan (uspmv_spmmv_ap_hp_tiles)"""
+    _ck(lib().uspmv_spmmv_ap_hp_tiles(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(tile_ids), tile_ids.numel(), _dp(X), _dp(Y), int(b),
+                                      int(ld), int(layout), _stream_ptr(stream)))
+    return Y
+
+
+def spmmv_ap_hp_chunks(A_hi, A_mid, A_hp, chunk_ids, X, Y, b, ld, layout=COLWISE, stream=None):
+    """spmmv_ap_hp over the chunks in chunk_ids (int32 tensor; entries < 0 skipped), lane per row (uspmv_spmmv_ap_hp_chunks)"""
+    _ck(lib().uspmv_spmmv_ap_hp_chunks(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(chunk_ids), chunk_ids.numel(), _dp(X), _dp(Y), int(b),
+                                       int(ld), int(layout), _stream_ptr(stream)))
+    return Y
+
+
+def spmmv_ap_hp_tiles_path(A_hi, A_mid, A_hp, b, ld, layout=COLWISE):
+    """(path, vectors) that spmmv_ap_hp_tiles would take for 16-byte-aligned X / Y under the current tuning (uspmv_spmmv_ap_hp_tiles_path):
+    path 2 the staged kernel -- column-major X at every ld -- with `vectors` of the b vectors per pass, 0 lane per row (vectors 0)"""
+    path, vec = C.c_int(), C.c_int()
+    _ck(lib().uspmv_spmmv_ap_hp_tiles_path(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, int(b), int(ld), int(layout), C.byref(path),
+                                           C.byref(vec)))
     return path.value, vec.value
 
 

@@ -170,6 +170,33 @@ __device__ __forceinline__ void gather_block_chain(const VT *__restrict__ vp, co
 // there), where ap[dp_sp] keeps the eight it was measured with.
 constexpr int tlc_chain_slots(int B, int BS, bool pair) { return ((BS >= 8 && !pair) || (BS < B && BS >= 4)) ? 4 : 8; }
 
+// Column-major X whose columns start on multiples of NE elements only (NE * sizeof(HT) = 8 or 4 bytes): the nl lines of a tile into
+// LDS as [X row][BS], in pieces of NE elements.  Piece p: the piece of the line's 16 rows fastest, then the vector, then the line, so
+// the 16 / NE lanes of one (line, vector) read consecutive addresses.  X points at the first vector of the pass; rows at or beyond
+// x_rows are staged as +0 and never read.
+template <int BS, int NE, typename HT>
+__device__ __forceinline__ void stage_x_narrow(HT *xs, const HT *__restrict__ X, const long ld, const int *__restrict__ lines, const int nl,
+                                               const long x_rows) {
+    constexpr int NPL = 16 / NE;              // pieces per (line, vector)
+    constexpr int PPL = BS * NPL;
+    typedef HT npiece_t __attribute__((ext_vector_type(NE)));
+    for (int p = threadIdx.x; p < nl * PPL; p += blockDim.x) {
+        const int k = p / PPL, w = p - k * PPL;
+        const int v = w / NPL, r0 = (w % NPL) * NE;
+        const long xrow = (long)lines[k] * 16 + r0;
+        const HT *xp = X + xrow + (long)v * ld;
+        npiece_t t;
+        if (xrow + NE <= x_rows) t = *(const npiece_t *)xp;
+        else {
+#pragma unroll
+            for (int e = 0; e < NE; ++e) t[e] = xrow + e < x_rows ? xp[e] : (HT)0;
+        }
+        HT *dst = xs + ((long)k * 16 + r0) * BS + v;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) dst[e * BS] = t[e];
+    }
+}
+
 // The parts' shared tile-local-column plan on block vectors of width B: the block form of scs_spmv_ap_tlc / scs_spmv_ap_hp_tlc.  A line
 // of the plan (16 consecutive x elements there) is 16 consecutive X rows here.  Per pass BS of the B vectors:
 // the tile's lines are staged once in LDS as [X row][BS] in the type of X, then every part runs its chain from its own streams
@@ -183,17 +210,22 @@ constexpr int tlc_chain_slots(int B, int BS, bool pair) { return ((BS >= 8 && !p
 // list gather from global X.  YCOL: Y[row + v*ld], else Y[row*B + v].
 // IDS: workgroup g runs tile tile_ids[g] (the interior / boundary lists of the distributed block step, uspmv_spmmv_ap_tiles); an entry < 0
 // is a conditional entry that was switched off and returns before the first barrier, uniformly for the workgroup.
+// xpiece (the list form of the kinds with an fp16 part on column-major X only; 16 everywhere else): the bytes of the widest power-of-two
+// piece every column of X starts aligned to -- 16, or 8 / 4 where ld * sizeof(HT) is no multiple of 16 (a rank's padded_vec_size is
+// whatever its halo makes it).  Below 16 the columns are staged in pieces of that size, the pieces of one (line, vector) on consecutive
+// lanes: a wave's loads of a line run over its 128 (64) contiguous bytes, column after column.
 template <int B, int BS, int CT, bool NT, typename HT, bool MID, typename LT, bool XCOL, bool YCOL, bool IDS = false>
 __global__ void __launch_bounds__(1024) scs_spmmv_ap_tlc(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ X,
                                                          HT *__restrict__ Y, const long ld, const int *__restrict__ tile_line_ptr,
                                                          const int *__restrict__ tile_lines, const long x_rows, const int xcd_remap,
-                                                         const int *__restrict__ tile_ids = nullptr) {
+                                                         const int *__restrict__ tile_ids = nullptr, const int xpiece = 16) {
     static_assert(BS >= 2 && BS <= B && B % BS == 0, "whole passes");
     extern __shared__ __attribute__((aligned(16))) unsigned char tlc_smem[];
     HT *xs = (HT *)tlc_smem;
     typedef XRow<HT, BS> R;
     typedef typename R::piece_t piece_t;
     constexpr bool PAIR = std::is_same<LT, float>::value;    // ap[dp_sp]
+    constexpr bool NARROW = IDS && XCOL && !PAIR;            // the forms that read xpiece
     constexpr int W = tlc_chain_slots(B, BS, PAIR);
     const int C = CT > 0 ? CT : C_rt;
     const unsigned lbt = remap_block(blockIdx.x, gridDim.x, xcd_remap);
@@ -218,7 +250,10 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_tlc(const long n_chunks, co
         for (int v = 0; v < BS; ++v) { s[v] = 0.0; q[v] = 0.0; }
         if (nl > 0) {
             if (v0) __syncthreads();              // (the previous pass has read its X rows)
-            if constexpr (XCOL) {
+            if (NARROW && xpiece < 16) {          // (uniform for the workgroup)
+                if (sizeof(HT) == 4 && xpiece == 8) stage_x_narrow<BS, 2>(xs, X + (long)v0 * ld, ld, tile_lines + lp0, nl, x_rows);
+                else stage_x_narrow<BS, 1>(xs, X + (long)v0 * ld, ld, tile_lines + lp0, nl, x_rows);
+            } else if constexpr (XCOL) {
                 // piece p of the tile: vector v fastest, then the piece of the line's 16 rows, then the line
                 constexpr int XE = (int)(16 / sizeof(HT));    // consecutive X rows of one vector per 16-byte piece
                 constexpr int PPL = BS * (16 / XE);
@@ -289,11 +324,10 @@ __global__ void __launch_bounds__(1024) scs_spmmv_ap_tlc(const long n_chunks, co
     }
 }
 
-// ids: the chunks to run (n_ids of them), or nullptr for all; tile_rows > 0: ids are tiles of that many rows (the pair only)
+// ids: the chunks to run (n_ids of them), or nullptr for all; tile_rows > 0: ids are tiles of that many rows
 template <int VB, typename HT, bool MID, typename LT>
 void launch_ap_vb(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, int b, long ld, int layout, hipStream_t st, const int *ids,
                   long n_ids, int tile_rows) {
-    constexpr bool PAIR = std::is_same<LT, float>::value;
     const int block = g_tune.block;
     const long n_chunks = ids ? n_ids : (long)hi->n_chunks;
     const unsigned grid = grid_for(n_chunks * (ids && tile_rows > 0 ? (long)tile_rows : (long)hi->C), block);
@@ -305,7 +339,7 @@ void launch_ap_vb(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, 
     do {                                                                                                                                  \
         if (!ids) APV_LAUNCH_I(RW, NTV, 0);                                                                                               \
         else if (tile_rows <= 0) APV_LAUNCH_I(RW, NTV, 1);                                                                                \
-        else if constexpr (PAIR) APV_LAUNCH_I(RW, NTV, 2);                                                                                \
+        else APV_LAUNCH_I(RW, NTV, 2);                                                                                                    \
     } while (0)
     if (layout == USPMV_ROWWISE) { if (nt) APV_LAUNCH(true, true); else APV_LAUNCH(true, false); }
     else { if (nt) APV_LAUNCH(false, true); else APV_LAUNCH(false, false); }
@@ -314,8 +348,9 @@ void launch_ap_vb(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, 
 }
 
 // <XCOL, YCOL>: the kinds with an fp16 part stage X and store Y in the caller's layout; ap[dp_sp] always reads row-major X (column-major
-// callers arrive through the re-layout workspace) and stores Y either way -- except over a tile list (ids, the pair only), where it too
-// stages X straight from the caller's columns: a part of a distributed step has no whole X to re-lay out
+// callers arrive through the re-layout workspace) and stores Y either way -- except over a tile list (ids), where it too stages X straight
+// from the caller's columns: a part of a distributed step has no whole X to re-lay out.  Over a list the fp16 kinds take every ld: columns
+// that do not start on 16-byte boundaries are staged in 8- or 4-byte pieces (xpiece)
 template <int B, int BS, typename HT, bool MID, typename LT>
 void launch_ap_tlc_bs(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT *Y, long ld, bool ycol, hipStream_t st, const int *ids, long n_ids) {
     constexpr bool PAIR = std::is_same<LT, float>::value;
@@ -323,18 +358,18 @@ void launch_ap_tlc_bs(const uspmv_dmat *hi, const ApHpParts &P, const HT *X, HT 
     const int C = (int)hi->C;
     const unsigned grid = ids ? (unsigned)n_ids : (unsigned)hi->tlc.n_tiles;
     const long x_rows = ids && ycol ? std::min<long>((long)hi->tlc.x_len, ld) : (long)hi->tlc.x_len;
+    const size_t col_bytes = (size_t)ld * sizeof(HT);
+    const int xpiece = !(ids && ycol) || PAIR || col_bytes % 16 == 0 ? 16 : col_bytes % 8 == 0 ? 8 : 4;
 #define APT_LAUNCH(CTV, NTV, XC, YC, IDSV)                                                                                           \
     do {                                                                                                                             \
         auto kfn = scs_spmmv_ap_tlc<B, BS, CTV, NTV, HT, MID, LT, XC, YC, IDSV>;                                                     \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(hi->tlc.tile_rows), lds, st, (long)hi->n_chunks, C, P, X, Y, ld,                    \
-                           hi->tlc.line_ptr.get(), hi->tlc.lines.get(), x_rows, g_tune.xcd_remap, ids);                              \
+                           hi->tlc.line_ptr.get(), hi->tlc.lines.get(), x_rows, g_tune.xcd_remap, ids, xpiece);                      \
     } while (0)
 #define APT_NT(CTV, NTV)                                                                                                             \
     do {                                                                                                                             \
-        if (ids) {                                                                                                                   \
-            if constexpr (PAIR) { if (ycol) APT_LAUNCH(CTV, NTV, true, true, true); else APT_LAUNCH(CTV, NTV, false, false, true); } \
-        }                                                                                                                            \
+        if (ids) { if (ycol) APT_LAUNCH(CTV, NTV, true, true, true); else APT_LAUNCH(CTV, NTV, false, false, true); }                \
         else if (!ycol) APT_LAUNCH(CTV, NTV, false, false, false);                                                                   \
         else if constexpr (PAIR) APT_LAUNCH(CTV, NTV, false, true, false);                                                           \
         else APT_LAUNCH(CTV, NTV, true, true, false);                                                                                \
@@ -392,6 +427,18 @@ ApHpBlockPath ap_hp_block_path(const uspmv_dmat *hi, const uspmv_dmat *mid, cons
     return {AP_HP_PATH_STAGED, bs};
 }
 
+// What uspmv_spmmv_ap_hp_tiles runs: the ONE predicate behind the launch and behind uspmv_spmmv_ap_hp_tiles_path.  The staged kernel over
+// the listed tiles -- X staged straight from the caller's layout; column-major X at every ld, in pieces of 16, 8 or 4 bytes -- or lane
+// per row over the tiles' rows: any other width or alignment of X / Y, "tlc" 0, "spmmv_variant" 1, or a plan whose fullest tile leaves no
+// room for two vectors in LDS.  (The caller has checked that the parts share a line plan.)
+ApHpBlockPath ap_hp_tiles_path(const uspmv_dmat *hi, int b, bool aligned16) {
+    if (g_tune.spmmv_variant == 1 || !aligned16 || (b != 2 && b != 4 && b != 8 && b != 16)) return {AP_HP_PATH_GENERIC, 0};
+    if (!g_tune.tlc || hi->tlc.max_lines < 1) return {AP_HP_PATH_GENERIC, 0};
+    const int bs = tlc_block_bs(hi->tlc, b, hi->dtype == USPMV_F32 ? 4 : 8);
+    if (bs < 2) return {AP_HP_PATH_GENERIC, 0};
+    return {AP_HP_PATH_STAGED, bs};
+}
+
 }  // namespace
 
 namespace uspmv_dev {
@@ -414,7 +461,6 @@ void spmmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_d
 
 int launch_spmmv_ap_rows(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const int *chunk_ids, long n_ids, const void *X,
                          void *Y, int b, long ld, int layout, hipStream_t st, int tile_rows) {
-    if (tile_rows > 0 && last->dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_spmmv_ap_rows: tile lists are the ap[dp_sp] pair's");
     const ApHpParts P = ap_hp_parts(hi, mid, last);
     ap_kind(hi, mid, last, [&](auto ht, auto m, auto lt) {      // VB vectors per pass
         typedef decltype(ht) HT; typedef decltype(lt) LT;
@@ -429,7 +475,6 @@ int launch_spmmv_ap_rows(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspm
 
 int launch_spmmv_ap_staged(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const void *X, void *Y, int b, long ld, bool ycol,
                            int bs, hipStream_t st, const int *tile_ids, long n_ids) {
-    if (tile_ids && last->dtype != USPMV_F32) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_spmmv_ap_staged: tile lists are the ap[dp_sp] pair's");
     const ApHpParts P = ap_hp_parts(hi, mid, last);
     ap_kind(hi, mid, last, [&](auto ht, auto m, auto lt) {
         typedef decltype(ht) HT; typedef decltype(lt) LT;
@@ -449,6 +494,19 @@ int launch_spmmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const
                               const void *X, void *Y, int b, long ld, int layout, hipStream_t st) {
     if (n_ids == 0) return USPMV_OK;
     return launch_spmmv_ap_rows(hi, mid, hp, chunk_ids, n_ids, X, Y, b, ld, layout, st);
+}
+
+void spmmv_ap_hp_tiles_path(const uspmv_dmat *hi, int b, int *path, int *vectors) {
+    const ApHpBlockPath p = ap_hp_tiles_path(hi, b, true);
+    *path = p.path; *vectors = p.bs;
+}
+
+int launch_spmmv_ap_hp_tiles(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *tile_ids, long n_ids, const void *X,
+                             void *Y, int b, long ld, int layout, hipStream_t st) {
+    if (n_ids == 0) return USPMV_OK;
+    const ApHpBlockPath p = ap_hp_tiles_path(hi, b, ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0));
+    if (p.path == AP_HP_PATH_STAGED) return launch_spmmv_ap_staged(hi, mid, hp, X, Y, b, ld, layout != USPMV_ROWWISE, p.bs, st, tile_ids, n_ids);
+    return launch_spmmv_ap_rows(hi, mid, hp, tile_ids, n_ids, X, Y, b, ld, layout, st, hi->tlc.tile_rows);
 }
 
 int launch_spmmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *X, void *Y, int b, long ld, int layout,

@@ -380,7 +380,7 @@ int uspmv_spmv_ap_hp_chunks(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, con
     return launch_spmv_ap_hp_chunks(hi, mid, hp, d_chunk_ids, (long)n_ids, d_x, d_y, (hipStream_t)stream);
 }
 
-// the argument checks uspmv_spmmv_ap_hp and uspmv_spmmv_ap_hp_path share
+// the argument checks uspmv_spmmv_ap_hp, uspmv_spmmv_ap_hp_path and the list forms share
 static int check_spmmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout, const char *who) {
     if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
     if (b < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: b=%d", who, b);
@@ -407,6 +407,46 @@ int uspmv_spmmv_ap_hp_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, cons
     if (int rc = check_spmmv_ap_hp(hi, mid, hp, b, ld, layout, who)) return rc;
     if (!path || !vectors_per_pass) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL result pointer", who);
     spmmv_ap_hp_path(hi, mid, hp, b, (long)ld, layout, path, vectors_per_pass);
+    return USPMV_OK;
+}
+
+// the checks of the list forms of uspmv_spmmv_ap_hp: those of uspmv_spmmv_ap_hp and of uspmv_spmv_ap_hp_tiles.  Nothing here touches a
+// device.
+static int check_ap_hp_block_list(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout, bool tiles,
+                                  const char *who) {
+    if (int rc = check_spmmv_ap_hp(hi, mid, hp, b, ld, layout, who)) return rc;
+    const uint64_t id = hi->tlc.plan_id;
+    if (tiles && (!hi->tlc.on || id == 0 || !hp->tlc.on || hp->tlc.plan_id != id || (mid && (!mid->tlc.on || mid->tlc.plan_id != id))))
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: the parts have no shared tile-local-column plan (uspmv_dmat_optimize_ap_hp)", who);
+    return USPMV_OK;
+}
+
+int uspmv_spmmv_ap_hp_tiles(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const int32_t *d_tile_ids, int64_t n_ids,
+                            const void *d_X, void *d_Y, int b, int64_t ld, int layout, void *stream) {
+    const char *who = "uspmv_spmmv_ap_hp_tiles";
+    if (int rc = check_ap_hp_block_list(hi, mid, hp, b, ld, layout, true, who)) return rc;
+    if (n_ids < 0 || n_ids > hi->tlc.n_tiles || (n_ids > 0 && !d_tile_ids) || !d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    if (n_ids == 0) return USPMV_OK;
+    if (int rc = require_device()) return rc;
+    return launch_spmmv_ap_hp_tiles(hi, mid, hp, d_tile_ids, (long)n_ids, d_X, d_Y, b, (long)ld, layout, (hipStream_t)stream);
+}
+
+int uspmv_spmmv_ap_hp_chunks(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const int32_t *d_chunk_ids, int64_t n_ids,
+                             const void *d_X, void *d_Y, int b, int64_t ld, int layout, void *stream) {
+    const char *who = "uspmv_spmmv_ap_hp_chunks";
+    if (int rc = check_ap_hp_block_list(hi, mid, hp, b, ld, layout, false, who)) return rc;
+    if (n_ids < 0 || n_ids > hi->n_chunks || (n_ids > 0 && !d_chunk_ids) || !d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad argument", who);
+    if (n_ids == 0) return USPMV_OK;
+    if (int rc = require_device()) return rc;
+    return launch_spmmv_ap_hp_chunks(hi, mid, hp, d_chunk_ids, (long)n_ids, d_X, d_Y, b, (long)ld, layout, (hipStream_t)stream);
+}
+
+int uspmv_spmmv_ap_hp_tiles_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, int b, int64_t ld, int layout, int *path,
+                                 int *vectors_per_pass) {
+    const char *who = "uspmv_spmmv_ap_hp_tiles_path";
+    if (int rc = check_ap_hp_block_list(hi, mid, hp, b, ld, layout, true, who)) return rc;
+    if (!path || !vectors_per_pass) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL result pointer", who);
+    spmmv_ap_hp_tiles_path(hi, b, path, vectors_per_pass);
     return USPMV_OK;
 }
 

@@ -541,17 +541,25 @@ void spmmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_d
 // the block kernels every ap kind shares (ap_hp_spmmv_kernels.hip); the kind follows from the handles: hi F64 | F32, mid F32 or nullptr,
 // last F16 -- or F32 for the ap[dp_sp] pair (dp, nullptr, sp).  X, Y in the type of hi.
 // lane per row, any b, layout and alignment: over the chunks chunk_ids[0 .. n_ids) (entries < 0 skipped), or over all where chunk_ids is
-// nullptr.  tile_rows > 0 (the pair only): the ids are tiles, tile t = the rows [t * tile_rows, (t + 1) * tile_rows)
+// nullptr.  tile_rows > 0: the ids are tiles, tile t = the rows [t * tile_rows, (t + 1) * tile_rows)
 int launch_spmmv_ap_rows(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const int *chunk_ids, long n_ids, const void *X,
                          void *Y, int b, long ld, int layout, hipStream_t st, int tile_rows = 0);
 // staged over the parts' shared tile-local-column plan, b in {2, 4, 8, 16}, bs vectors per pass (tlc_block_bs), 16-byte-aligned X / Y.
 // ycol: column-major Y.  The kinds with an fp16 part read X in the layout of Y; the pair always reads row-major X -- except over
-// tile_ids (the pair only: workgroup g runs tile tile_ids[g] of the n_ids listed, entries < 0 skipped), where X is in the layout of Y
+// tile_ids (workgroup g runs tile tile_ids[g] of the n_ids listed, entries < 0 skipped), where X is in the layout of Y.  Over tile_ids the
+// kinds with an fp16 part take column-major X at every ld (columns off the 16-byte grid are staged in 8- or 4-byte pieces)
 int launch_spmmv_ap_staged(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *last, const void *X, void *Y, int b, long ld, bool ycol,
                            int bs, hipStream_t st, const int *tile_ids = nullptr, long n_ids = 0);
-// lane per row over a list of chunks (for the rest chunks of a sweep plan's block form), any b
+// lane per row over a list of chunks (the rest chunks of a sweep plan's block form, the chunk lists of a distributed step; entries < 0
+// skipped), any b
 int launch_spmmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
                               const void *X, void *Y, int b, long ld, int layout, hipStream_t st);                 // ap_hp_spmmv_kernels.hip
+// the tiles in tile_ids of the parts' shared tile-local-column plan (entries < 0 skipped; the caller has checked that they share one),
+// X and Y in `layout`: the staged kernel where spmmv_ap_hp_tiles_path says 2, else lane per row over the tiles' rows
+int launch_spmmv_ap_hp_tiles(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *tile_ids, long n_ids, const void *X,
+                             void *Y, int b, long ld, int layout, hipStream_t st);                                  // ap_hp_spmmv_kernels.hip
+// what launch_spmmv_ap_hp_tiles runs for 16-byte-aligned X / Y: 2 the staged kernel (vectors per pass), 0 lane per row (vectors 0)
+void spmmv_ap_hp_tiles_path(const uspmv_dmat *hi, int b, int *path, int *vectors);                                 // ap_hp_spmmv_kernels.hip
 // the block sweep kernel of the splits with an fp16 part (ap_hp_spmmv_sweep.hip): vectors per pass at width b on windows of 2^wlog
 // elements of x_dtype (USPMV_F64 | USPMV_F32; 0: does not apply) / on this handle's plan and threads per workgroup; the launch: sweep
 // tiles, then the rest chunks

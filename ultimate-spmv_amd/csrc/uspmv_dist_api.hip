@@ -39,7 +39,8 @@
 //
 // The kinds with an fp16 part, ap[dp_hp], ap[sp_hp], ap[dp_sp_hp] (uspmv_dist_create_ap_hp_from_coo): A / scs are the hi part, the
 // object carries the hp part and, for ap[dp_sp_hp], the mid part beside it.  One halo for all parts, tile classes from all of them, the
-// single-vector step in the vector type of the hi part (float for ap[sp_hp]); no block-vector step yet.
+// single-vector step in the vector type of the hi part (float for ap[sp_hp]); block vectors through uspmv_dist_spmmv_ap_hp: the step of
+// uspmv_dist_spmmv_ap over the list forms of these kinds' block kernels (uspmv_spmmv_ap_hp_tiles / _chunks), guard in that type.
 #include <rccl/rccl.h>
 
 #include <chrono>
@@ -100,7 +101,8 @@ struct uspmv_dist {
     int32_t pad_col = -1;
     bool pad_split = false;           // (off by default: on one GPU it measures 0.221 against 0.209 ms per step, profiles/r03/dist_step_ab.txt)
     DeviceBuf<void> d_stale;
-    DeviceBuf<double> d_stale_b;      // the block step of an ap object (uspmv_dist_spmmv_ap): the slot's b values, grown to b at first use
+    DeviceBuf<double> d_stale_b;      // the block step of an ap object (uspmv_dist_spmmv_ap / _ap_hp): the slot's b values in the vector type,
+                                      // 8 bytes each whatever that type is, grown to b at first use
     int stale_b = 0;
     // peer-store exchange: this rank's receive window = two halves (step parity) of win_half elements, sized for block vectors of up to
     // win_b columns; the windows of the ranks it sends to, opened through IPC (nullptr: not opened; loopback opens nothing); the push
@@ -227,21 +229,23 @@ __global__ void pad_guard_kernel(const VT *__restrict__ x, const int pad_col, co
     if (k == 0 && need) atomicAdd(counter, 1);
 }
 
-// The block form of that pair for uspmv_dist_spmmv_ap: the padding column's slot holds one value per vector -- X[pad_col + v*ld]
+// The block form of that pair for uspmv_dist_spmmv_ap / _ap_hp: the padding column's slot holds one value per vector -- X[pad_col + v*ld]
 // column-wise, X[pad_col*b + v] row-wise.  Kept before the exchange; after it the padding tiles run again iff for ANY vector the kept
 // or the delivered value is not finite or their signs differ (a tile computes all b columns, so one such column re-runs it).
-__global__ void pad_keep_block_kernel(const double *__restrict__ X, const int pad_col, const int b, const long ld, const int rowwise,
-                                      double *__restrict__ stale) {
+template <typename VT>
+__global__ void pad_keep_block_kernel(const VT *__restrict__ X, const int pad_col, const int b, const long ld, const int rowwise,
+                                      VT *__restrict__ stale) {
     const int v = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (v < b) stale[v] = rowwise ? X[(long)pad_col * b + v] : X[pad_col + (long)v * ld];
 }
-__global__ void pad_guard_block_kernel(const double *__restrict__ X, const int pad_col, const int b, const long ld, const int rowwise,
-                                       const double *__restrict__ stale, const int *__restrict__ pad_ids, int *__restrict__ rerun,
+template <typename VT>
+__global__ void pad_guard_block_kernel(const VT *__restrict__ X, const int pad_col, const int b, const long ld, const int rowwise,
+                                       const VT *__restrict__ stale, const int *__restrict__ pad_ids, int *__restrict__ rerun,
                                        const long n_pad, int *__restrict__ counter) {
     const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
     bool need = false;
     for (int v = 0; v < b; ++v) {
-        const double s = stale[v], c = rowwise ? X[(long)pad_col * b + v] : X[pad_col + (long)v * ld];
+        const VT s = stale[v], c = rowwise ? X[(long)pad_col * b + v] : X[pad_col + (long)v * ld];
         need = need || !(isfinite(s) && isfinite(c) && (signbit(s) == signbit(c)));
     }
     if (k < n_pad) rerun[k] = need ? pad_ids[k] : -1;
@@ -291,6 +295,28 @@ int pad_guard(uspmv_dist *D, const void *d_x, hipStream_t st) {
     else
         hipLaunchKernelGGL(pad_guard_kernel<float>, dim3(grid), dim3(256), 0, st, (const float *)d_x, D->pad_col, (const float *)D->d_stale, D->d_pad, D->d_late + D->n_bnd_real,
                            (long)D->n_pad, D->d_scratch + 2);
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
+// the block forms of the guard's two halves, in the object's vector type (D->d_stale_b holds b values of it)
+int pad_keep_block(uspmv_dist *D, const void *d_X, int b, long ld, int rowwise, hipStream_t st) {
+    const dim3 grid((unsigned)((b + 63) / 64));
+    if (D->dtype == USPMV_F64)
+        hipLaunchKernelGGL(pad_keep_block_kernel<double>, grid, dim3(64), 0, st, (const double *)d_X, D->pad_col, b, ld, rowwise, D->d_stale_b.get());
+    else
+        hipLaunchKernelGGL(pad_keep_block_kernel<float>, grid, dim3(64), 0, st, (const float *)d_X, D->pad_col, b, ld, rowwise, (float *)D->d_stale_b.get());
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+int pad_guard_block(uspmv_dist *D, const void *d_X, int b, long ld, int rowwise, hipStream_t st) {
+    const dim3 grid((unsigned)((D->n_pad + 255) / 256));
+    if (D->dtype == USPMV_F64)
+        hipLaunchKernelGGL(pad_guard_block_kernel<double>, grid, dim3(256), 0, st, (const double *)d_X, D->pad_col, b, ld, rowwise,
+                           (const double *)D->d_stale_b.get(), D->d_pad.get(), D->d_late + D->n_bnd_real, (long)D->n_pad, D->d_scratch + 2);
+    else
+        hipLaunchKernelGGL(pad_guard_block_kernel<float>, grid, dim3(256), 0, st, (const float *)d_X, D->pad_col, b, ld, rowwise,
+                           (const float *)D->d_stale_b.get(), D->d_pad.get(), D->d_late + D->n_bnd_real, (long)D->n_pad, D->d_scratch + 2);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }
@@ -1197,7 +1223,7 @@ int uspmv_dist_set_option(uspmv_dist_t *D, const char *key, int value) {
     if (is_ap(D) && (((k == "fused_step" || k == "autotune_all") && value != 0) || (k == "block_plan" && value > 0)))
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_set_option: '%s' is not available on an adaptive-precision (%s) object: its step has "
                            "the overlap, plain and pad_split forms%s", key, ap_name(D),
-                           has_hp(D) ? ", and it has no block-vector step" : "; block vectors run through uspmv_dist_spmmv_ap");
+                           has_hp(D) ? "; block vectors run through uspmv_dist_spmmv_ap_hp" : "; block vectors run through uspmv_dist_spmmv_ap");
     if (k == "overlap") { if ((value != 0) != D->overlap) drop_graph(D); D->overlap = value != 0; }
     else if (k == "no_pack") { if ((value != 0) != D->no_pack) drop_graph(D); D->no_pack = value != 0; }
     else if (k == "ba_synch") { if ((value != 0) != D->ba_synch) drop_graph(D); D->ba_synch = value != 0; }
@@ -1515,7 +1541,7 @@ int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, i
     if (!D || !d_X || !d_Y || b < 1) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: bad argument");
     if (is_ap(D))
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "uspmv_dist_spmmv: not available on an adaptive-precision (%s) object (%s)", ap_name(D),
-                           has_hp(D) ? "no block-vector step across ranks yet" : "its block step is uspmv_dist_spmmv_ap");
+                           has_hp(D) ? "its block step is uspmv_dist_spmmv_ap_hp" : "its block step is uspmv_dist_spmmv_ap");
     if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown layout %d", layout);
     if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_spmmv: unknown mode %d", mode);
     if (layout == USPMV_ROWWISE && mode != USPMV_BULKVEC)
@@ -1555,28 +1581,26 @@ int uspmv_dist_spmmv(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, i
     return step_barrier(D, main);
 }
 
-// The block step of an ap[dp_sp] object.  Unlike the dp object's two-part step (marked chunk-length arrays, uspmv_dmat::part_len) the
-// parts here are the single-vector step's own tile (chunk) lists run by the list forms of the pair's block kernels, so "pad_split"
-// carries over: see pad_keep_block_kernel.
-int uspmv_dist_spmmv_ap(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
-    const char *who = "uspmv_dist_spmmv_ap";
-    if (b < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: b=%d", who, b);
-    if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown layout %d", who, layout);
-    if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown mode %d", who, mode);
-    if (!D || !d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
-    if (has_hp(D)) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: an adaptive-precision %s object (no block-vector step across ranks yet)", who, ap_name(D));
-    if (!is_ap(D))
-        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: a one-precision object (uspmv_dist_create_from_coo); its block step is uspmv_dist_spmmv", who);
+// The block step of an adaptive-precision object, behind uspmv_dist_spmmv_ap (ap[dp_sp]) and uspmv_dist_spmmv_ap_hp (the kinds with an fp16
+// part).  Unlike the dp object's two-part step (marked chunk-length arrays, uspmv_dmat::part_len) the parts here are the single-vector
+// step's own tile (chunk) lists run by the list forms of the kind's block kernels, so "pad_split" carries over: see pad_keep_block_kernel.
+// X and Y are in the object's vector type (float for ap[sp_hp]).
+static int ap_block_step(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream, const char *who) {
     if (layout == USPMV_ROWWISE && mode != USPMV_BULKVEC)
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: row-wise block vectors travel in one message per neighbour (bulkvec) only", who);
     hipStream_t main = (hipStream_t)stream;
     if (b == 1) { ++D->eager_steps; return step(D, d_X, d_Y, main, comm_halos != 0); }
     const int64_t ld = D->vec_len;
-    if (!(D->P > 1 && comm_halos)) return uspmv_spmmv_ap(D->pt[0].A, D->pt[1].A, d_X, d_Y, b, ld, layout, stream);
+    const uspmv_dist::Part *p = D->pt;
+    const bool hp = has_hp(D);
+    auto whole_b = [&]() -> int {
+        return hp ? uspmv_spmmv_ap_hp(p[0].A, p[1].A, p[2].A, d_X, d_Y, b, ld, layout, stream) : uspmv_spmmv_ap(p[0].A, p[1].A, d_X, d_Y, b, ld, layout, stream);
+    };
+    if (!(D->P > 1 && comm_halos)) return whole_b();
     if ((int64_t)b * std::max(ld, (int64_t)1) > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: b * padded_vec_size exceeds int32", who);
     if (!D->overlap) {
         if (int rc = block_exchange(D, d_X, b, layout, mode, main, who)) return rc;
-        if (int rc = uspmv_spmmv_ap(D->pt[0].A, D->pt[1].A, d_X, d_Y, b, ld, layout, stream)) return rc;
+        if (int rc = whole_b()) return rc;
         ++D->spmmv_one_part;
         return step_barrier(D, main);
     }
@@ -1588,28 +1612,52 @@ int uspmv_dist_spmmv_ap(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout
     }
     auto part_b = [&](const int32_t *ids, int64_t n, hipStream_t st) -> int {
         if (n == 0) return USPMV_OK;
-        return D->tiles ? uspmv_spmmv_ap_tiles(D->pt[0].A, D->pt[1].A, ids, n, d_X, d_Y, b, ld, layout, st)
-                        : uspmv_spmmv_ap_chunks(D->pt[0].A, D->pt[1].A, ids, n, d_X, d_Y, b, ld, layout, st);
+        if (hp)
+            return D->tiles ? uspmv_spmmv_ap_hp_tiles(p[0].A, p[1].A, p[2].A, ids, n, d_X, d_Y, b, ld, layout, st)
+                            : uspmv_spmmv_ap_hp_chunks(p[0].A, p[1].A, p[2].A, ids, n, d_X, d_Y, b, ld, layout, st);
+        return D->tiles ? uspmv_spmmv_ap_tiles(p[0].A, p[1].A, ids, n, d_X, d_Y, b, ld, layout, st)
+                        : uspmv_spmmv_ap_chunks(p[0].A, p[1].A, ids, n, d_X, d_Y, b, ld, layout, st);
     };
     HIP_TRY(hipEventRecord(D->ev_main, main));                       // fork, join and the lists: those of step()
     HIP_TRY(hipStreamWaitEvent(D->side_stream, D->ev_main, 0));
     if (int rc = pads ? part_b(D->d_early, D->n_int + D->n_pad, D->side_stream) : part_b(D->d_int, D->n_int, D->side_stream)) return rc;
     HIP_TRY(hipEventRecord(D->ev_comm, D->side_stream));
-    if (pads) {
-        hipLaunchKernelGGL(pad_keep_block_kernel, dim3((unsigned)((b + 63) / 64)), dim3(64), 0, main, (const double *)d_X, D->pad_col, b, (long)ld, rowwise,
-                           D->d_stale_b.get());
-        HIP_TRY(hipGetLastError());
-    }
+    if (pads)
+        if (int rc = pad_keep_block(D, d_X, b, (long)ld, rowwise, main)) return rc;
     if (int rc = block_exchange(D, d_X, b, layout, mode, main, who)) return rc;
-    if (pads) {
-        hipLaunchKernelGGL(pad_guard_block_kernel, dim3((unsigned)((D->n_pad + 255) / 256)), dim3(256), 0, main, (const double *)d_X, D->pad_col, b, (long)ld,
-                           rowwise, (const double *)D->d_stale_b.get(), D->d_pad.get(), D->d_late + D->n_bnd_real, (long)D->n_pad, D->d_scratch + 2);
-        HIP_TRY(hipGetLastError());
-    }
+    if (pads)
+        if (int rc = pad_guard_block(D, d_X, b, (long)ld, rowwise, main)) return rc;
     HIP_TRY(hipStreamWaitEvent(main, D->ev_comm, 0));                // join
     if (int rc = pads ? part_b(D->d_late, D->n_bnd_real + D->n_pad, main) : part_b(D->d_bnd, D->n_bnd, main)) return rc;
     ++D->spmmv_two_part;
     return step_barrier(D, main);
+}
+
+// the argument checks the two block steps of an ap object share, before the kind is looked at
+static int check_ap_block_step(const uspmv_dist_t *D, const void *d_X, const void *d_Y, int b, int layout, int mode, const char *who) {
+    if (b < 1) return uspmv::fail(USPMV_ERR_INVALID, "%s: b=%d", who, b);
+    if (layout != USPMV_COLWISE && layout != USPMV_ROWWISE) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown layout %d", who, layout);
+    if (mode != USPMV_BULKVEC && mode != USPMV_MULTIVEC && mode != USPMV_SINGLEVEC) return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown mode %d", who, mode);
+    if (!D || !d_X || !d_Y) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    return USPMV_OK;
+}
+
+int uspmv_dist_spmmv_ap(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
+    const char *who = "uspmv_dist_spmmv_ap";
+    if (int rc = check_ap_block_step(D, d_X, d_Y, b, layout, mode, who)) return rc;
+    if (has_hp(D)) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: an adaptive-precision %s object; its block step is uspmv_dist_spmmv_ap_hp", who, ap_name(D));
+    if (!is_ap(D))
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: a one-precision object (uspmv_dist_create_from_coo); its block step is uspmv_dist_spmmv", who);
+    return ap_block_step(D, d_X, d_Y, b, layout, mode, comm_halos, stream, who);
+}
+
+int uspmv_dist_spmmv_ap_hp(uspmv_dist_t *D, void *d_X, void *d_Y, int b, int layout, int mode, int comm_halos, void *stream) {
+    const char *who = "uspmv_dist_spmmv_ap_hp";
+    if (int rc = check_ap_block_step(D, d_X, d_Y, b, layout, mode, who)) return rc;
+    if (!is_ap(D))
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: a one-precision object (uspmv_dist_create_from_coo); its block step is uspmv_dist_spmmv", who);
+    if (!has_hp(D)) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: an adaptive-precision %s object; its block step is uspmv_dist_spmmv_ap", who, ap_name(D));
+    return ap_block_step(D, d_X, d_Y, b, layout, mode, comm_halos, stream, who);
 }
 
 }  // extern "C"

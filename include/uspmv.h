@@ -664,6 +664,24 @@ int uspmv_scs_split_chunks(const uspmv_scs_t *s, int64_t n_local, int32_t **inte
  * code/mpi_funcs.hpp:279-306); 2 = other halo references.  *pad_col = -1 when no chunk is of class 1.  (What "pad_split" of
  * uspmv_dist_set_option is built on.) */
 int uspmv_scs_chunk_classes(const uspmv_scs_t *s, int64_t n_local, uint8_t *classes, int32_t *pad_col);
+/* collect_local_needed_heri (code/mpi_funcs.hpp:242-415) + permute_scs_cols (code/utilities.hpp:1802-1831) ON THE DEVICE, for handles whose
+ * entries never visit the host (csrc/halo_kernels.hip): parts[0 .. n_parts) (1 .. 3: one struct, or the parts of an
+ * adaptive-precision split in the order hi, mid, lo) hold GLOBAL column ids (converted with permute_cols = 0), own their arrays (a
+ * uspmv_dmat_wrap handle is refused), carry no plan, and share C and n_chunks.  ONE first-seen numbering over the parts' col_idxs taken as
+ * one array in storage order, part after part, padding entries (column 0) included -- a column's first-seen position is the least
+ * (part << 32 | storage index) among the entries that name it, found by a 64-bit atomic minimum per column; its slot within its owner is
+ * its rank under that key (the n_halo claimed columns are ordered on the host, O(n_halo) records cross).  Then every part's col_idxs is
+ * rewritten in place: a local column to d_old_to_new[col - wsa[rank]] (device array of n_local entries; NULL: col - wsa[rank]), a remote
+ * one to n_local + base[owner] + slot.  *out equals the plan of uspmv_halo_discover[_ap | _ap_hp] on the same structs integer for
+ * integer.  n_cols: columns of the global matrix (the table has max(wsa[P], n_cols) entries of 8 bytes -- the device memory this call takes
+ * beyond the handles, plus 16 bytes per halo column).  Refused before anything is written: a column outside [0, max(wsa[P], n_cols))
+ * ("column %d outside the global matrix", the first in scan order, as on the host), a column no block owns, n_local + n_halo beyond
+ * int32 (USPMV_ERR_OVERFLOW).  Works on `stream`; returns when the handles are rewritten. */
+int uspmv_halo_discover_device(uspmv_dmat_t *const parts[], int n_parts, int64_t n_cols, const int32_t *wsa, int rank, int P,
+                               const int32_t *d_old_to_new, void *stream, uspmv_halo_t **out);
+/* uspmv_scs_chunk_classes of a device handle (F64, F32 or F16; the +0.0 test is on the value's bits), bit for bit: one wave per chunk,
+ * O(n_chunks) bytes come back.  classes: host array of n_chunks. */
+int uspmv_dmat_chunk_classes_device(const uspmv_dmat_t *m, int64_t n_local, uint8_t *classes, int32_t *pad_col, void *stream);
 void uspmv_free(void *p);
 /* Send-buffer gather for ALL neighbours in one launch over the concatenated index list:
  * d_send[i] = d_x[d_perm[d_send_idxs[i]] + block_offset].  Replaces pack_send_buf /
@@ -796,6 +814,25 @@ int uspmv_dist_create_ap_hp_from_coo(const void *comm_id, int comm_rank, int com
 int uspmv_dist_create_ap_hp_from_coo_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const uspmv_coo_t *local,
                                         const int32_t *wsa, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2, int tlc,
                                         const uspmv_dist_options_t *opt, uspmv_dist_t **out);
+/* uspmv_dist_create_from_coo / _ap_from_coo / _ap_hp_from_coo for a block that lives in HBM: d_I local row ids, d_J GLOBAL
+ * column ids, d_V (device arrays of nnz entries, sorted by row -- what uspmv_seg_local_coo gives), n_cols the columns of the global matrix.
+ * kind: USPMV_ONE_PRECISION (dtype F64 | F32), USPMV_AP_DP_SP, or a kind with an fp16 part (dtype is then ignored; threshold_2 only for
+ * USPMV_AP_DP_SP_HP).  The host route's steps in the host route's order (init_local_structs, code/main.cpp:1075-1334), each on the device:
+ * uspmv_partition_precisions_device -> uspmv_convert_to_scs_device_from_arrays (first part with its own sigma ordering under sort_mode,
+ * the others with its permutation; permute_cols 0) -> uspmv_halo_discover_device -> with tlc the (shared) line plan at 256-row tiles
+ * from the handles' own arrays -> uspmv_dmat_chunk_classes_device -> the object; nothing of O(nnz) crosses to the host.  Refusals as on
+ * the host route, an empty block of wsa first and on all ranks alike.  USPMV_SORT_HOST: every array of the object equals the host
+ * route's; USPMV_SORT_DEVICE_STABLE: y in original row order does, the permutations may differ in the order of equal-length rows.
+ * The object owns handles and halo; uspmv_dist_parts[_ap | _ap_hp] hand out the first part's struct WITHOUT entries (meta data, chunk
+ * arrays, permutations -- what uspmv_dist_check needs) and NULL for the other parts' structs.  "block_plan" plans from the handle. */
+enum { USPMV_ONE_PRECISION = -1 };
+int uspmv_dist_create_from_arrays(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const int32_t *d_I, const int32_t *d_J,
+                                  const double *d_V, int64_t nnz, int64_t n_cols, const int32_t *wsa, int64_t C, int64_t sigma, int kind, int dtype,
+                                  double threshold_1, double threshold_2, int tlc, int sort_mode, void *stream, uspmv_dist_t **out);
+int uspmv_dist_create_from_arrays_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const int32_t *d_I, const int32_t *d_J,
+                                     const double *d_V, int64_t nnz, int64_t n_cols, const int32_t *wsa, int64_t C, int64_t sigma, int kind, int dtype,
+                                     double threshold_1, double threshold_2, int tlc, int sort_mode, const uspmv_dist_options_t *opt, void *stream,
+                                     uspmv_dist_t **out);
 /* the exchange plan of the object (borrowed): n_send, send_off[P+1], send_idxs[n_send], recv_off[P+1] as in uspmv_comm_plan_meta */
 int uspmv_dist_comm_plan(const uspmv_dist_t *d, int64_t *n_send, const int64_t **send_off, const int32_t **send_idxs,
                          const int64_t **recv_off);
@@ -860,7 +897,8 @@ int uspmv_dist_exchange(const uspmv_dist_t *d, int *exchange);
 /* meta[12] = n_local, n_halo, padded_vec_size, n_send, n_interior, n_boundary, ids_are_tiles, n_rows_padded, loopback,
  *            graph captured, graph launches so far, eager steps so far */
 int uspmv_dist_info(const uspmv_dist_t *d, int64_t meta[12]);
-/* borrowed handles of an object made by uspmv_dist_create_from_coo (NULL scs / halo otherwise) */
+/* borrowed handles of an object made by uspmv_dist_create_from_coo (NULL scs / halo otherwise).  An object made by
+ * uspmv_dist_create_from_arrays answers with a struct that has no entries (uspmv_scs_arrays: NULL col_idxs / values), here and below. */
 int uspmv_dist_parts(const uspmv_dist_t *d, const uspmv_scs_t **scs, const uspmv_dmat_t **A, const uspmv_halo_t **halo);
 /* uspmv_dist_parts of an ap[dp_sp] object: both structs, both handles, the one halo (uspmv_dist_parts answers with the dp ones);
  * the sp ones are NULL on a one-precision object */

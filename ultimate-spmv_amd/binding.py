@@ -17,6 +17,8 @@ _LIB = None
 F64, F32, F16 = 0, 1, 2
 AP_DP_HP, AP_SP_HP, AP_DP_SP_HP = 0, 1, 2     # kinds of uspmv_partition_precisions_hp
 AP_DP_SP = 3                                  # ... and the fourth kind of the device-side set-up (partition_precisions_device)
+ONE_PRECISION = -1                            # kind of a one-precision object (DistNative.from_device_arrays)
+SORT_HOST, SORT_DEVICE_STABLE = 0, 1          # sigma-window ordering of the device-side conversions
 COLWISE, ROWWISE = 0, 1
 SEG_ROWS, SEG_NNZ = 0, 1
 
@@ -154,6 +156,12 @@ _SIGS = {
     "uspmv_spmmv_ap_tiles": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
     "uspmv_spmmv_ap_chunks": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
     "uspmv_spmmv_ap_tiles_path": (C.c_int, [_vp, _vp, C.c_int, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "uspmv_halo_discover_device": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(_vp)]),
+    "uspmv_dmat_chunk_classes_device": (C.c_int, [_vp, _i64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), _vp]),
+    "uspmv_dist_create_from_arrays": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, C.c_int, C.c_int,
+                                               C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
+    "uspmv_dist_create_from_arrays_ex": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, C.c_int, C.c_int,
+                                                  C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, C.POINTER(_vp)]),
     "uspmv_halo_meta": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i32p), C.POINTER(_i32p), C.POINTER(_i32p)]),
     "uspmv_halo_free": (None, [_vp]),
     "uspmv_scs_chunk_classes": (C.c_int, [_vp, _i64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
@@ -695,7 +703,44 @@ class DistNative:
         part (uspmv_dist_create_ap_hp_from_coo_ex); dtype is derived from the kind (F32 for sp_hp, else F64), a dtype that contradicts it is
         a ValueError.  self.scs is then the hi struct, self.scs_mid (None for the two-part kinds) and self.scs_hp the others; ap_threshold
         alone keeps meaning ap[dp_sp]."""
+        wsa, dtype, idbuf, opt, cr, cs = self._options(wsa, rank, P, comm_id, comm_rank, comm_size, dtype, hostcomm, host_exchange, exchange,
+                                                       ap_threshold, ap_kind, ap_threshold_2)
+        h = _vp()
+        if self.ap_kind is not None:
+            _ck(lib().uspmv_dist_create_ap_hp_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, _AP_KINDS[self.ap_kind],
+                                                          self.ap_threshold, self.ap_threshold_2, int(bool(tlc)), opt, C.byref(h)))
+        elif self.ap_threshold is not None:
+            _ck(lib().uspmv_dist_create_ap_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, self.ap_threshold,
+                                                       int(bool(tlc)), opt, C.byref(h)))
+        else:
+            _ck(lib().uspmv_dist_create_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, dtype, int(bool(tlc)), opt, C.byref(h)))
+        self._attach(h, dtype)
+
+    @classmethod
+    def from_device_arrays(cls, d_I, d_J, d_V, n_cols, wsa, C_, sigma, rank, P, comm_id=None, comm_rank=None, comm_size=None, dtype=None, tlc=True,
+                           hostcomm=None, host_exchange=False, exchange=None, ap_threshold=None, ap_kind=None, ap_threshold_2=0.0,
+                           sort_mode=SORT_HOST, stream=None):
+        """The same object from a block that lives in HBM (uspmv_dist_create_from_arrays_ex): d_I local row ids, d_J GLOBAL column ids, d_V
+        (torch int32 / int32 / float64 device tensors, entries sorted by row -- seg_local_coo's arrays), n_cols the columns of the global
+        matrix.  Keyword options as for __init__; sort_mode SORT_HOST (every array as on the host route) | SORT_DEVICE_STABLE.  Every
+        O(nnz) step of the set-up runs on the device.  self.scs is the first part's struct WITHOUT entries (its permutations and chunk
+        arrays); scs_sp / scs_mid / scs_hp are None."""
         import torch
+        assert d_I.dtype == torch.int32 and d_J.dtype == torch.int32 and d_V.dtype == torch.float64 and d_I.is_cuda
+        self = cls.__new__(cls)
+        wsa, dtype, idbuf, opt, cr, cs = self._options(wsa, rank, P, comm_id, comm_rank, comm_size, dtype, hostcomm, host_exchange, exchange,
+                                                       ap_threshold, ap_kind, ap_threshold_2)
+        kind = _AP_KINDS[self.ap_kind] if self.ap_kind is not None else AP_DP_SP if self.ap_threshold is not None else ONE_PRECISION
+        h = _vp()
+        _ck(lib().uspmv_dist_create_from_arrays_ex(idbuf, cr, cs, rank, P, _dp(d_I), _dp(d_J), _dp(d_V), int(d_I.numel()), int(n_cols), _np_ptr(wsa),
+                                                   C_, sigma, kind, dtype, self.ap_threshold or 0.0, self.ap_threshold_2, int(bool(tlc)), int(sort_mode),
+                                                   opt, _stream_ptr(stream), C.byref(h)))
+        self._attach(h, dtype)
+        return self
+
+    def _options(self, wsa, rank, P, comm_id, comm_rank, comm_size, dtype, hostcomm, host_exchange, exchange, ap_threshold, ap_kind, ap_threshold_2):
+        """the keyword options of the creators: sets the kind's attributes, returns (wsa, dtype, comm id buffer, options pointer or None,
+        comm_rank, comm_size) for the library call"""
         self.rank, self.P = rank, P
         self.ap_threshold = None if ap_threshold is None else float(ap_threshold)
         self.ap_kind = None if ap_kind in (None, "dp_sp") else ap_kind
@@ -715,7 +760,6 @@ class DistNative:
             dtype = F64
         wsa = np.ascontiguousarray(wsa, np.int32)
         self._wsa = wsa
-        h = _vp()
         idbuf = (C.c_ubyte * 128).from_buffer_copy(comm_id) if comm_id is not None else None
         self._hostcomm = hostcomm
         if exchange is None:
@@ -733,14 +777,11 @@ class DistNative:
             self._opt = DistOptions(None, ex)      # no transport: loopback (the library refuses real ranks without one)
             opt = C.byref(self._opt)
         cr, cs = rank if comm_rank is None else comm_rank, P if comm_size is None else comm_size
-        if self.ap_kind is not None:
-            _ck(lib().uspmv_dist_create_ap_hp_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, _AP_KINDS[self.ap_kind],
-                                                          self.ap_threshold, self.ap_threshold_2, int(bool(tlc)), opt, C.byref(h)))
-        elif self.ap_threshold is not None:
-            _ck(lib().uspmv_dist_create_ap_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, self.ap_threshold,
-                                                       int(bool(tlc)), opt, C.byref(h)))
-        else:
-            _ck(lib().uspmv_dist_create_from_coo_ex(idbuf, cr, cs, rank, P, local_coo.h, _np_ptr(wsa), C_, sigma, dtype, int(bool(tlc)), opt, C.byref(h)))
+        return wsa, dtype, idbuf, opt, cr, cs
+
+    def _attach(self, h, dtype):
+        """what every creator does with the library's object: borrowed structs and handles, the stream, the permutations"""
+        import torch
         self.h = h
         e = C.c_int(0)
         _ck(lib().uspmv_dist_exchange(h, C.byref(e)))
@@ -755,12 +796,12 @@ class DistNative:
             k, sm, sq, am, aq = C.c_int(-1), _vp(), _vp(), _vp(), _vp()
             _ck(lib().uspmv_dist_parts_ap_hp(h, C.byref(k), None, C.byref(sm), C.byref(sq), None, C.byref(am), C.byref(aq), None))
             assert k.value == _AP_KINDS[self.ap_kind]
-            self.scs_mid, self._A_mid = (_BorrowedScs(sm, self), am) if sm.value else (None, None)
-            self.scs_hp, self._A_hp = _BorrowedScs(sq, self), aq
+            self.scs_mid, self._A_mid = (_BorrowedScs(sm, self) if sm.value else None), (am if am.value else None)
+            self.scs_hp, self._A_hp = (_BorrowedScs(sq, self) if sq.value else None), aq
         elif self.ap_threshold is not None:
             s2, a2 = _vp(), _vp()
             _ck(lib().uspmv_dist_parts_ap(h, None, C.byref(s2), None, C.byref(a2), None))
-            self.scs_sp, self._A_sp = _BorrowedScs(s2, self), a2
+            self.scs_sp, self._A_sp = (_BorrowedScs(s2, self) if s2.value else None), a2
         self.tdtype = torch.float64 if dtype == F64 else torch.float32
         self.stream = torch.cuda.Stream()
         self._refresh()
@@ -937,6 +978,9 @@ class HaloPlan:
             _ck(lib().uspmv_halo_discover_ap(scs.h, scs_sp.h, _np_ptr(wsa), rank, P, C.byref(h)))
         else:
             _ck(lib().uspmv_halo_discover(scs.h, _np_ptr(wsa), rank, P, C.byref(h)))
+        self._read(h, wsa, rank, P)
+
+    def _read(self, h, wsa, rank, P):
         self.h, self.P, self.rank = h, P, rank
         n = _i64()
         cum, idx, cnt = _i32p(), _i32p(), _i32p()
@@ -955,6 +999,21 @@ class HaloPlan:
         if getattr(self, "h", None) and _LIB is not None:
             _LIB.uspmv_halo_free(self.h)
             self.h = None
+
+
+def halo_discover_device(parts, n_cols, wsa, rank, P, old_to_new=None, stream=None):
+    """HaloPlan of one DeviceMatrix or of the parts of a split (a list of 1 .. 3, in the order hi, mid, lo) whose entries live on the device
+    only (uspmv_halo_discover_device): handles converted with permute_cols=False, whose col_idxs this call rewrites in place -- local
+    columns through old_to_new (int32 device tensor of n_local entries, or None), remote ones to the halo numbering.  n_cols: columns of
+    the global matrix."""
+    parts = list(parts) if isinstance(parts, (list, tuple)) else [parts]
+    wsa = np.ascontiguousarray(wsa, np.int32)
+    hs = (_vp * len(parts))(*[A.h for A in parts])
+    h = _vp()
+    _ck(lib().uspmv_halo_discover_device(hs, len(parts), int(n_cols), _np_ptr(wsa), rank, P, _dp(old_to_new), _stream_ptr(stream), C.byref(h)))
+    plan = HaloPlan.__new__(HaloPlan)
+    plan._read(h, wsa, rank, P)
+    return plan
 
 
 def halo_discover_ap(scs_dp, scs_sp, wsa, rank, P):
@@ -1036,6 +1095,14 @@ class DeviceMatrix:
         self.block_tiles = self.block_staged = 0
         if block_tlc:
             self.optimize_block(scs, block_tlc)
+
+    def chunk_classes_device(self, n_local, stream=None):
+        """Scs.chunk_classes computed on the device from this handle's own arrays (uspmv_dmat_chunk_classes_device):
+        (classes uint8[n_chunks], pad_col)"""
+        cls = np.zeros(self.n_chunks, np.uint8)
+        pad = C.c_int32(-1)
+        _ck(lib().uspmv_dmat_chunk_classes_device(self.h, int(n_local), cls.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(pad), _stream_ptr(stream)))
+        return cls, pad.value
 
     def optimize_block_sweep(self, scs, b, wlog=0, tile_rows=0):
         """Block-vector column-window sweep plan for 64-byte X rows (uspmv_dmat_optimize_block_sweep); returns (n_tiles, n_sweep_tiles):
@@ -1209,9 +1276,6 @@ def convert_to_scs_device(coo, C_, sigma, dtype=F64, fixed_permutation=None, per
     _ck(lib().uspmv_convert_to_scs_device(coo.h, C_, sigma, dtype, _np_ptr(fp), int(bool(permute_cols)), C.byref(hs), C.byref(hA)))
     s = Scs(hs)
     return s, DeviceMatrix(s, device, _handle=hA)
-
-
-SORT_HOST, SORT_DEVICE_STABLE = 0, 1
 
 
 def convert_to_scs_device_from_arrays(d_I, d_J, d_V, n_rows, n_cols, C_, sigma, dtype=F64, fixed_permutation=None, permute_cols=True,

@@ -516,9 +516,9 @@ int device_elem_install(uspmv_dmat *A, const ElemCounts &cnt, ElemStats *st, con
 
 // the device planner of one struct or an ap[dp_sp] pair: the plan at the rows per tile uspmv_dmat_optimize[_ap] chooses, then -- one
 // struct only -- its fallback to the plan over single x elements, then its sweep rule
-int device_plan_install(uspmv_dmat *A, uspmv_dmat *B, int max_lines, int64_t *n_tiles, int64_t *n_staged, const char *who) {
+int device_plan_install(uspmv_dmat *A, uspmv_dmat *B, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged, const char *who) {
     uspmv_dmat *const parts[3] = {A, B, nullptr};
-    const int R_meas = measured_tile_rows(A, B, line_budget(max_lines, A->dtype, B != nullptr), who);
+    const int R_meas = opts.measure ? measured_tile_rows(A, B, line_budget(max_lines, A->dtype, B != nullptr), who) : 0;
     uspmv_dmat::TlcPlan kept[2];
     PlanStats st;
     const int rc = plan_at_chosen_rows(R_meas, B != nullptr, [&](int R, PlanStats *o) { return device_plan_install_rows(parts, max_lines, R, o, who); },
@@ -530,7 +530,7 @@ int device_plan_install(uspmv_dmat *A, uspmv_dmat *B, int max_lines, int64_t *n_
         // (the line plan waits in kept[0]: the handle gets it back unless the element plan is taken, also when the attempt fails)
         ElemCounts cnt;
         bool elem = false;
-        int rc2 = elements_take_over(max_lines > 0, st, true, A->dtype, A->n_elements,
+        int rc2 = elements_take_over(max_lines > 0, st, opts.elements, A->dtype, A->n_elements,
                                      [&](int cap, double *over) {
                                          const int r = device_elem_count(A, cap, &cnt, who);
                                          *over = sampled_over_cap_frac((int64_t)cnt.n.size(), [&](int64_t t) { return cnt.n[(size_t)t] > cap; });
@@ -813,6 +813,23 @@ int uspmv_dmat_optimize(uspmv_dmat_t *A, const uspmv_scs_t *s, int max_lines, in
 }
 
 int uspmv_dmat_optimize_device(uspmv_dmat_t *A, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    return dmat_optimize_device(A, max_lines, TlcPlanOpts{}, n_tiles, n_staged);
+}
+
+int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = "uspmv_dmat_optimize_device_ap";
+    if (int rc = check_dmat(dp, who)) return rc;
+    if (int rc = check_dmat(sp, who)) return rc;
+    if (dp->dtype != USPMV_F64 || sp->dtype != USPMV_F32 || dp->C != sp->C || dp->n_chunks != sp->n_chunks)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: handles do not form a dp+sp pair", who);
+    if (int rc = require_device()) return rc;
+    return device_plan_install(dp, sp, max_lines, TlcPlanOpts{}, n_tiles, n_staged, who);
+}
+
+}  // extern "C"
+
+// uspmv_dmat_optimize_device with the options spelled out, as dmat_optimize above takes them (deal_rows and additive: host planner only)
+int uspmv_dev::dmat_optimize_device(uspmv_dmat *A, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged) {
     const char *who = "uspmv_dmat_optimize_device";
     if (int rc = check_dmat_one_prec(A, who)) return rc;
     if (int rc = require_device()) return rc;
@@ -846,29 +863,32 @@ int uspmv_dmat_optimize_device(uspmv_dmat_t *A, int max_lines, int64_t *n_tiles,
             if (e == hipSuccess) e = hipMemsetAsync(alt->own.col_idxs, 0, 4 * ne, nullptr);
             if (e == hipSuccess) e = hipMemsetAsync(alt->own.values, 0, vsz * ne, nullptr);
             int rc = e == hipSuccess ? launch_rechunk32(A, alt->chunk_ptrs, alt->own.col_idxs, alt->own.values, nullptr) : uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-            if (!rc) rc = device_plan_install(alt, nullptr, max_lines, n_tiles, n_staged, who);
+            if (!rc) rc = device_plan_install(alt, nullptr, max_lines, opts, n_tiles, n_staged, who);
             if (rc) { uspmv_dmat_free(alt); return rc; }
             A->tlc = {};
             A->alt = alt;
             return USPMV_OK;
         }
     }
-    return device_plan_install(A, nullptr, max_lines, n_tiles, n_staged, who);
+    return device_plan_install(A, nullptr, max_lines, opts, n_tiles, n_staged, who);
 }
+
+// The line plan shared by the two or three parts of a split (parts[2] NULL: two), as dmat_optimize_ap / _ap_hp install it with `measure`
+// off: at the rows per tile of ONE struct in the caller's row order, kept whenever it stages a tile, no column-window sweep
+int uspmv_dev::dmat_optimize_device_shared(uspmv_dmat *const parts[3], int64_t *n_tiles, int64_t *n_staged, const char *who) {
+    for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->sw = {};
+    PlanStats st;
+    if (int rc = device_plan_install_rows(parts, 0, plan_tile_rows(false), &st, who)) return rc;
+    if (n_tiles) *n_tiles = st.n_tiles;
+    if (n_staged) *n_staged = st.n_staged;
+    return USPMV_OK;
+}
+
+extern "C" {
 
 int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t *s_dp, const uspmv_scs_t *s_sp,
                            int max_lines, int64_t *n_tiles, int64_t *n_staged) {
     return dmat_optimize_ap(dp, sp, s_dp, s_sp, max_lines, TlcPlanOpts{}, n_tiles, n_staged);
-}
-
-int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_lines, int64_t *n_tiles, int64_t *n_staged) {
-    const char *who = "uspmv_dmat_optimize_device_ap";
-    if (int rc = check_dmat(dp, who)) return rc;
-    if (int rc = check_dmat(sp, who)) return rc;
-    if (dp->dtype != USPMV_F64 || sp->dtype != USPMV_F32 || dp->C != sp->C || dp->n_chunks != sp->n_chunks)
-        return uspmv::fail(USPMV_ERR_INVALID, "%s: handles do not form a dp+sp pair", who);
-    if (int rc = require_device()) return rc;
-    return device_plan_install(dp, sp, max_lines, n_tiles, n_staged, who);
 }
 
 int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,

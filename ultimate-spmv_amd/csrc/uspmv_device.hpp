@@ -296,6 +296,10 @@ int dmat_optimize_ap(uspmv_dmat *dp, uspmv_dmat *sp, const uspmv_scs *s_dp, cons
 // the caller's row order, installed whenever it stages a tile, no column-window sweep -- what the distributed object needs of the parts
 int dmat_optimize_ap_hp(uspmv_dmat *hi, uspmv_dmat *mid, uspmv_dmat *hp, const uspmv_scs *s_hi, const uspmv_scs *s_mid, const uspmv_scs *s_hp,
                         int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged);
+// The same plans built on the device from the handles' own arrays (no host struct): uspmv_dmat_optimize_device with measure / elements
+// spelled out, and the line plan shared by the two or three parts of a split (parts[2] NULL: two) as `measure` off gives it above
+int dmat_optimize_device(uspmv_dmat *A, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged);
+int dmat_optimize_device_shared(uspmv_dmat *const parts[3], int64_t *n_tiles, int64_t *n_staged, const char *who);
 
 // One-launch distributed step (csrc/uspmv_dist_api.hip): the tile list of a step is [early | late | conditional | early].  Early entries
 // (interior + padding tiles) run at once.  A late entry (a tile with real halo references) looks ONCE at the exchange counter: if the

@@ -1041,6 +1041,69 @@ hipError_t upload_one_launch_lists(uspmv_dist *D, const std::vector<int32_t> &ea
     return hipSuccess;
 }
 
+// Chunk classes over all parts of a split: per chunk the largest of the parts' classes.  One padding column for all of them (all pad with
+// global column 0, one halo numbering); if they ever disagree, no chunk is padding-only
+struct PartClasses {
+    std::vector<uint8_t> cls;
+    int32_t pad_col = -1;
+    bool pad_clash = false;
+    void merge(const std::vector<uint8_t> &cq, int32_t pq) {
+        if (cls.empty()) cls.assign(cq.size(), 0);
+        for (size_t c = 0; c < cls.size(); ++c) cls[c] = std::max(cls[c], cq[c]);
+        if (pq >= 0) { pad_clash = pad_clash || (pad_col >= 0 && pad_col != pq); pad_col = pq; }
+    }
+    void settle() {
+        if (!pad_clash) return;
+        for (auto &c : cls) if (c == 1) c = 2;
+        pad_col = -1;
+    }
+};
+
+// Where the set-up routes meet (setup_from_coo: host structs; setup_from_arrays: device arrays only): the handles pt[] exist, columns in
+// the rank's numbering of `halo`, the (shared) line plan installed where the route builds one, the chunks classified.  From here: the
+// step's lists, the object, the pad and one-launch lists, the collective window set-up, the hand-over of pt[] and halo to the object.
+// *D is set as soon as the object exists, so that the caller's exit can free it when a later step fails.
+int finish_setup(const CooSetup &k, const void *comm_id, int comm_rank, int comm_size, int rank, int P, int64_t C, uspmv_dist::Part (&pt)[3],
+                 uspmv_halo_t *halo, const int32_t *o2n, PartClasses &pc, int64_t n_tiles, int64_t n_staged, const uspmv_dist_options_t *opt,
+                 uspmv_dist_t **Dp, uspmv_dist_t **out) {
+    const char *who = k.who;
+    const bool ap = k.kind != uspmv_dist::ONE_PRECISION;
+    pc.settle();
+    const std::vector<uint8_t> &cls = pc.cls;
+    const int32_t pad_col = pc.pad_col;
+    // tile lists when the plan stages something.  one precision: whatever line plan the handle carries, unless it runs on a re-chunked copy;
+    // ap kinds: only the shared line plan (plan_id != 0)
+    const auto &plan = pt[0].A->tlc;
+    const int tile_rows = plan.on && (!ap || plan.plan_id != 0) ? plan.tile_rows : 0;
+    const bool use_tiles = tile_rows > 0 && n_staged > 0 && (ap || !pt[0].A->alt);
+    // ap kinds: a plan that stages nothing is dropped, so that the whole-matrix launch takes the lane-per-row kernel too
+    if (ap && !use_tiles)
+        for (auto &p : pt) if (p.A && p.A->tlc.on) p.A->tlc = {};
+    const StepLists L = use_tiles ? fold_classes(cls, std::max<int64_t>(tile_rows / C, 1), n_tiles) : fold_classes(cls, 1, (int64_t)cls.size());
+    // (ap kinds: create_dist switches "pad_split" on, and leaves the block-vector split of the hi handle's chunks alone)
+    int rc = create_dist(comm_id, comm_rank, comm_size, rank, P, pt[0].A, halo, o2n, L.interior.data(), (int64_t)L.interior.size(), L.boundary.data(),
+                         (int64_t)L.boundary.size(), use_tiles ? 1 : 0, opt, Dp, false, ap);
+    if (rc) return rc;
+    uspmv_dist_t *D = *Dp;
+    const bool pads = use_tiles && P > 1 && pad_col >= 0 && !L.pad.empty();
+    std::vector<int32_t> early = L.interior;
+    hipError_t e = pads ? upload_pad_lists(D, L, pad_col, &early) : hipSuccess;
+    // one precision: the one-launch step.  Without padding tiles every boundary tile is a late entry and none is conditional
+    if (!ap && use_tiles && P > 1 && e == hipSuccess)
+        e = upload_one_launch_lists(D, early, pads ? L.real : L.boundary, pads ? L.pad : std::vector<int32_t>(), pads ? pad_col : -1);
+    if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
+    if (!ap && (rc = sync_reset(D))) return rc;                     // (the one-launch step's counters)
+    // the collective window set-up after every step above that could fail on this rank alone
+    if (D->exchange == USPMV_EXCHANGE_PEER && P > 1)
+        if ((rc = peer_setup(D, 1))) return rc;
+    D->owns_setup = true; D->halo = halo;
+    D->kind = k.kind; D->ap_threshold = k.threshold_1; D->ap_threshold_2 = k.threshold_2;
+    D->n_pt = 0;
+    for (int q = 0; q < 3; ++q) { D->pt[q] = pt[q]; D->n_pt += pt[q].A != nullptr; }
+    *out = D;
+    return USPMV_OK;
+}
+
 // uspmv_dist_create_ex on a block given as COO: converts it (one struct, or the two or three of a split), discovers the one halo of all
 // parts, plans, and sorts the tiles (chunks) into the step's lists.  A tile of a split is a tile of ALL parts (same rows), its class the
 // largest of the parts' classes; the lists, the padding column and the guard are then the one-precision object's, in the vector type of the
@@ -1110,56 +1173,89 @@ int setup_from_coo(const CooSetup &k, const void *comm_id, int comm_rank, int co
              : k.kind == USPMV_AP_DP_SP ? uspmv_dev::dmat_optimize_ap(pt[0].A, pt[1].A, pt[0].scs, pt[1].scs, 0, as_is, &n_tiles, &n_staged)
                                         : uspmv_dev::dmat_optimize_ap_hp(pt[0].A, pt[1].A, pt[2].A, pt[0].scs, pt[1].scs, pt[2].scs, 0, as_is, &n_tiles, &n_staged);
     }
-    // chunk classes over all parts.  One padding column for all of them (all pad with global column 0, one halo numbering); if they ever
-    // disagree, no chunk is padding-only
+    // chunk classes over all parts
     const int64_t n_local = wsa[rank + 1] - wsa[rank];
-    std::vector<uint8_t> cls;
-    int32_t pad_col = -1;
-    bool pad_clash = false;
+    PartClasses pc;
     for (int q = 0; q < 3 && !rc; ++q) {
         if (!pt[q].scs) continue;
         std::vector<uint8_t> cq;
         int32_t pq = -1;
         if ((rc = uspmv_scs_classify_chunks(pt[q].scs, n_local, &cq, &pq))) break;
-        if (cls.empty()) cls.assign(cq.size(), 0);
-        for (size_t c = 0; c < cls.size(); ++c) cls[c] = std::max(cls[c], cq[c]);
-        if (pq >= 0) { pad_clash = pad_clash || (pad_col >= 0 && pad_col != pq); pad_col = pq; }
+        pc.merge(cq, pq);
     }
     if (rc) return done(rc);
-    if (pad_clash) {
-        for (auto &c : cls) if (c == 1) c = 2;
-        pad_col = -1;
+    return done(finish_setup(k, comm_id, comm_rank, comm_size, rank, P, C, pt, halo, o2n, pc, n_tiles, n_staged, opt, &D, out));
+}
+
+// setup_from_coo for a block that lives in HBM (d_I local row ids, d_J GLOBAL column ids, d_V; sorted by row): the same steps in the same
+// order, each on the device -- uspmv_partition_precisions_device, uspmv_convert_to_scs_device_from_arrays with permute_cols = 0 (the first
+// part with its own sigma ordering, the others with its old_to_new as fixed permutation; a part's COO copy is released once it is
+// converted), uspmv_halo_discover_device with that permutation, the (shared) line plan from the handles' own arrays, and
+// uspmv_dmat_chunk_classes_device per part.  Nothing of O(nnz) crosses to the host.  The object keeps the first part's layout-only struct
+// (the permutations) as pt[0].scs; the other slots have none.
+int setup_from_arrays(const CooSetup &k, const void *comm_id, int comm_rank, int comm_size, int rank, int P, const int32_t *d_I, const int32_t *d_J,
+                      const double *d_V, int64_t nnz, int64_t n_cols, const int32_t *wsa, int64_t C, int64_t sigma, int tlc, int sort_mode,
+                      const uspmv_dist_options_t *opt, void *stream, uspmv_dist_t **out) {
+    const char *who = k.who;
+    const bool ap = k.kind != uspmv_dist::ONE_PRECISION;
+    if (!wsa || !out || nnz < 0 || (nnz > 0 && (!d_I || !d_J || !d_V))) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (P < 1 || rank < 0 || rank >= P) return uspmv::fail(USPMV_ERR_INVALID, "%s: bad rank / P", who);
+    if (k.refusal[0]) return uspmv::fail(USPMV_ERR_INVALID, "%s: %s", who, k.refusal);
+    // (as in setup_from_coo: by all ranks alike, before the first collective)
+    for (int p = 0; p < P; ++p)
+        if (wsa[p + 1] <= wsa[p])
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: block %d of %d owns no rows (work_sharing_arr %d .. %d) -- fewer ranks or another partition%s", who, p, P,
+                               (int)wsa[p], (int)wsa[p + 1], k.empty_tail);
+    if (int rc = uspmv_dev::require_device()) return rc;
+    const int64_t n_local = wsa[rank + 1] - wsa[rank];
+    uspmv_dcoo_t *coo[3] = {nullptr, nullptr, nullptr};
+    uspmv_dist::Part pt[3];
+    uspmv_halo_t *halo = nullptr;
+    uspmv_dist_t *D = nullptr;
+    DeviceBuf<int32_t> d_o2n;
+    auto free_coo = [&]() { for (auto *&c : coo) { uspmv_dcoo_free(c); c = nullptr; } };
+    auto done = [&](int rc) {
+        free_coo();
+        if (rc == USPMV_OK) return rc;
+        uspmv_dist_free(D);
+        for (auto &p : pt) { uspmv_dmat_free(p.A); uspmv_scs_free(p.scs); }
+        uspmv_halo_free(halo);
+        return rc;
+    };
+    if (hipError_t e = d_o2n.alloc(4 * (size_t)n_local); e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
+    int rc = ap ? uspmv_partition_precisions_device(d_I, d_J, d_V, n_local, n_cols, nnz, k.kind, k.threshold_1, k.threshold_2, stream, coo) : USPMV_OK;
+    for (int q = 0; q < 3 && !rc; ++q) {
+        if (k.dtype[q] < 0) continue;
+        const int32_t *I = d_I, *J = d_J;
+        const double *V = d_V;
+        int64_t n = nnz;
+        uspmv_dcoo_t *&part = coo[k.kind == USPMV_AP_DP_SP && q == 1 ? 2 : q];   // (the partition hands the sp part of ap[dp_sp] out as its last)
+        if (ap) rc = uspmv_dcoo_arrays(part, &I, &J, &V, &n);
+        if (!rc) rc = uspmv_convert_to_scs_device_from_arrays(I, J, V, n_local, n_cols, n, C, sigma, k.dtype[q], q == 0 ? nullptr : d_o2n.get(), /*permute_cols=*/0,
+                                                              sort_mode, stream, q == 0 ? &pt[0].scs : nullptr, q == 0 ? d_o2n.get() : nullptr, nullptr, &pt[q].A);
+        uspmv_dcoo_free(part); part = nullptr;
     }
-    // tile lists when the plan stages something.  one precision: whatever line plan the handle carries, unless it runs on a re-chunked copy;
-    // ap kinds: only the shared line plan (plan_id != 0)
-    const auto &plan = pt[0].A->tlc;
-    const int tile_rows = plan.on && (!ap || plan.plan_id != 0) ? plan.tile_rows : 0;
-    const bool use_tiles = tile_rows > 0 && n_staged > 0 && (ap || !pt[0].A->alt);
-    // ap kinds: a plan that stages nothing is dropped, so that the whole-matrix launch takes the lane-per-row kernel too
-    if (ap && !use_tiles)
-        for (auto &p : pt) if (p.A && p.A->tlc.on) p.A->tlc = {};
-    const StepLists L = use_tiles ? fold_classes(cls, std::max<int64_t>(tile_rows / C, 1), n_tiles) : fold_classes(cls, 1, (int64_t)cls.size());
-    // (ap kinds: create_dist switches "pad_split" on, and leaves the block-vector split of the hi handle's chunks alone)
-    rc = create_dist(comm_id, comm_rank, comm_size, rank, P, pt[0].A, halo, o2n, L.interior.data(), (int64_t)L.interior.size(), L.boundary.data(),
-                     (int64_t)L.boundary.size(), use_tiles ? 1 : 0, opt, &D, false, ap);
+    uspmv_dmat_t *hs[3];
+    int n_hs = 0;
+    for (auto &p : pt) if (p.A) hs[n_hs++] = p.A;
+    if (!rc) rc = uspmv_halo_discover_device(hs, n_hs, n_cols, wsa, rank, P, d_o2n, stream, &halo);
+    int64_t n_tiles = 0, n_staged = 0;
+    if (!rc && tlc) {
+        // (the options of setup_from_coo, which says why)
+        const uspmv_dev::TlcPlanOpts as_is{/*measure=*/false, /*elements=*/false, /*deal_rows=*/false, /*additive=*/false};
+        uspmv_dmat_t *const shared[3] = {hs[0], n_hs > 1 ? hs[1] : nullptr, n_hs > 2 ? hs[2] : nullptr};
+        rc = !ap ? uspmv_dev::dmat_optimize_device(pt[0].A, 0, as_is, &n_tiles, &n_staged) : uspmv_dev::dmat_optimize_device_shared(shared, &n_tiles, &n_staged, who);
+    }
+    PartClasses pc;
+    for (int q = 0; q < 3 && !rc; ++q) {
+        if (!pt[q].A) continue;
+        std::vector<uint8_t> cq((size_t)pt[q].A->n_chunks);
+        int32_t pq = -1;
+        if ((rc = uspmv_dmat_chunk_classes_device(pt[q].A, n_local, cq.data(), &pq, stream))) break;
+        pc.merge(cq, pq);
+    }
     if (rc) return done(rc);
-    const bool pads = use_tiles && P > 1 && pad_col >= 0 && !L.pad.empty();
-    std::vector<int32_t> early = L.interior;
-    hipError_t e = pads ? upload_pad_lists(D, L, pad_col, &early) : hipSuccess;
-    // one precision: the one-launch step.  Without padding tiles every boundary tile is a late entry and none is conditional
-    if (!ap && use_tiles && P > 1 && e == hipSuccess)
-        e = upload_one_launch_lists(D, early, pads ? L.real : L.boundary, pads ? L.pad : std::vector<int32_t>(), pads ? pad_col : -1);
-    if (e != hipSuccess) return done(uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e)));
-    if (!ap && (rc = sync_reset(D))) return done(rc);               // (the one-launch step's counters)
-    // the collective window set-up after every step above that could fail on this rank alone
-    if (D->exchange == USPMV_EXCHANGE_PEER && P > 1)
-        if ((rc = peer_setup(D, 1))) return done(rc);
-    D->owns_setup = true; D->halo = halo;
-    D->kind = k.kind; D->ap_threshold = k.threshold_1; D->ap_threshold_2 = k.threshold_2;
-    D->n_pt = 0;
-    for (int q = 0; q < 3; ++q) { D->pt[q] = pt[q]; D->n_pt += pt[q].A != nullptr; }
-    *out = D;
-    return done(USPMV_OK);
+    return done(finish_setup(k, comm_id, comm_rank, comm_size, rank, P, C, pt, halo, pt[0].scs->old_to_new_idx.data(), pc, n_tiles, n_staged, opt, &D, out));
 }
 
 }  // namespace
@@ -1212,6 +1308,33 @@ int uspmv_dist_create_ap_hp_from_coo(const void *comm_id, int comm_rank, int com
     return uspmv_dist_create_ap_hp_from_coo_ex(comm_id, comm_rank, comm_size, rank, P, local, wsa, C, sigma, kind, threshold_1, threshold_2, tlc, nullptr, out);
 }
 
+// ... from a block in HBM, for every kind of object
+int uspmv_dist_create_from_arrays_ex(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const int32_t *d_I, const int32_t *d_J,
+                                     const double *d_V, int64_t nnz, int64_t n_cols, const int32_t *wsa, int64_t C, int64_t sigma, int kind, int dtype,
+                                     double threshold_1, double threshold_2, int tlc, int sort_mode, const uspmv_dist_options_t *opt, void *stream,
+                                     uspmv_dist_t **out) {
+    const char *who = "uspmv_dist_create_from_arrays";
+    char bad[48] = "";
+    if (kind == USPMV_ONE_PRECISION) {
+        if (dtype != USPMV_F64 && dtype != USPMV_F32) snprintf(bad, sizeof bad, "unknown dtype %d", dtype);
+        const CooSetup k{who, uspmv_dist::ONE_PRECISION, {dtype, -1, -1}, 0.0, 0.0, bad,
+                         " (the reference's seg methods only repair an empty LAST block, code/mpi_funcs.hpp:602-606)"};
+        return setup_from_arrays(k, comm_id, comm_rank, comm_size, rank, P, d_I, d_J, d_V, nnz, n_cols, wsa, C, sigma, tlc, sort_mode, opt, stream, out);
+    }
+    if (kind != USPMV_AP_DP_SP && kind != USPMV_AP_DP_HP && kind != USPMV_AP_SP_HP && kind != USPMV_AP_DP_SP_HP) snprintf(bad, sizeof bad, "unknown kind %d", kind);
+    const bool hp = kind != USPMV_AP_DP_SP;
+    const CooSetup k{who, kind, {kind == USPMV_AP_SP_HP ? USPMV_F32 : USPMV_F64, kind == USPMV_AP_DP_SP_HP || !hp ? USPMV_F32 : -1, hp ? USPMV_F16 : -1},
+                     threshold_1, hp ? threshold_2 : 0.0, bad, ""};
+    return setup_from_arrays(k, comm_id, comm_rank, comm_size, rank, P, d_I, d_J, d_V, nnz, n_cols, wsa, C, sigma, tlc, sort_mode, opt, stream, out);
+}
+
+int uspmv_dist_create_from_arrays(const void *comm_id, int comm_rank, int comm_size, int rank, int P, const int32_t *d_I, const int32_t *d_J,
+                                  const double *d_V, int64_t nnz, int64_t n_cols, const int32_t *wsa, int64_t C, int64_t sigma, int kind, int dtype,
+                                  double threshold_1, double threshold_2, int tlc, int sort_mode, void *stream, uspmv_dist_t **out) {
+    return uspmv_dist_create_from_arrays_ex(comm_id, comm_rank, comm_size, rank, P, d_I, d_J, d_V, nnz, n_cols, wsa, C, sigma, kind, dtype, threshold_1,
+                                            threshold_2, tlc, sort_mode, nullptr, stream, out);
+}
+
 int uspmv_dist_comm_plan(const uspmv_dist_t *D, int64_t *n_send, const int64_t **send_off, const int32_t **send_idxs, const int64_t **recv_off) {
     if (!D || !D->plan) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_comm_plan: NULL argument");
     return uspmv_comm_plan_meta(D->plan, n_send, send_off, send_idxs, recv_off);
@@ -1241,7 +1364,9 @@ int uspmv_dist_set_option(uspmv_dist_t *D, const char *key, int value) {
         D->plan_b = 0; D->plan_bnd_tiles = 0;
         int64_t nt = 0, ns = 0;
         if (value == 0) { uspmv_dev::block_plan_reset(D->A); return USPMV_OK; }
-        int rc = D->scs ? uspmv_dmat_optimize_block(D->A, D->scs, value, &nt, &ns) : uspmv_dmat_optimize_block_device(D->A, value, &nt, &ns);
+        // (a layout-only struct -- an object made from device arrays -- has no entries for the host planner)
+        int rc = D->scs && uspmv::scs_has_entries(D->scs) ? uspmv_dmat_optimize_block(D->A, D->scs, value, &nt, &ns)
+                                                          : uspmv_dmat_optimize_block_device(D->A, value, &nt, &ns);
         if (rc) return rc;
         if (D->A->pb.on) {
             D->plan_b = value;

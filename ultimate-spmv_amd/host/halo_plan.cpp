@@ -46,16 +46,10 @@ static int discover_halo(uspmv_scs_t *const parts[], int n, const int32_t *wsa, 
             lists[(size_t)p].push_back(col - wsa[p]);
         }
     }
-    auto *h = new uspmv_halo;
-    h->P = P; h->rank = rank; h->n_local = hi - lo;
     std::vector<int64_t> base((size_t)P + 1, 0);
     for (int p = 0; p < P; ++p) base[(size_t)p + 1] = base[(size_t)p] + (int64_t)lists[(size_t)p].size();
-    h->n_halo = base[(size_t)P];
-    if (h->n_local + h->n_halo > INT32_MAX) {
-        delete h;
-        return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: local + halo columns exceed int32", who);
-    }
-    const int64_t n_local = h->n_local;
+    const int64_t n_local = hi - lo;
+    if (n_local + base[(size_t)P] > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: local + halo columns exceed int32", who);
     for (int q = 0; q < n; ++q) {
         const int64_t n_el = parts[q]->n_elements;
         int32_t *ci = parts[q]->col_idxs.data();
@@ -67,11 +61,21 @@ static int discover_halo(uspmv_scs_t *const parts[], int n, const int32_t *wsa, 
             ci[k] = (int32_t)(n_local + base[(size_t)p] + slot[(size_t)col]);
         }
     }
+    *out = uspmv::halo_from_lists(P, rank, n_local, lists);
+    return USPMV_OK;
+}
+
+// The halo description from the per-owner lists of owner-local row ids, each in first-seen order (what discover_halo above and the device
+// discovery, csrc/halo_kernels.hip, both end on)
+uspmv_halo *uspmv::halo_from_lists(int P, int rank, int64_t n_local, const std::vector<std::vector<int32_t>> &lists) {
+    auto *h = new uspmv_halo;
+    h->P = P; h->rank = rank; h->n_local = n_local;
     h->recv_counts.resize((size_t)P);
     for (int p = 0; p < P; ++p) {
         h->recv_counts[(size_t)p] = (int32_t)lists[(size_t)p].size();
         h->recv_idxs.insert(h->recv_idxs.end(), lists[(size_t)p].begin(), lists[(size_t)p].end());
     }
+    h->n_halo = (int64_t)h->recv_idxs.size();
     // recv_counts_cumsum assembled exactly as code/mpi_funcs.hpp:403-414 does (entries below
     // `rank` from the lower-owner cumsum, entries rank..P from lower total + higher-owner cumsum)
     h->recv_counts_cumsum.assign((size_t)P + 1, 0);
@@ -84,8 +88,7 @@ static int discover_halo(uspmv_scs_t *const parts[], int n, const int32_t *wsa, 
     int limit = (P == 1) ? P - (rank + 1) : P - rank + 1;
     for (int i = 0; i < limit; ++i)
         h->recv_counts_cumsum[(size_t)(rank + i)] = (int32_t)(lhs[(size_t)rank] + rhs[(size_t)(rank + i)]);
-    *out = h;
-    return USPMV_OK;
+    return h;
 }
 
 extern "C" {

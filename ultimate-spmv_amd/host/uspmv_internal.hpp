@@ -241,6 +241,8 @@ namespace uspmv {
 int fail(int status, const char *fmt, ...);  // records the thread-local error text, returns status
 // false for the layout-only structs uspmv_convert_to_scs_device hands back (entries live on the device only)
 inline bool scs_has_entries(const uspmv_scs *s) { return (int64_t)s->col_idxs.size() == s->n_elements; }
+// the halo description of a rank from its per-owner lists of owner-local row ids in first-seen order (host/halo_plan.cpp)
+uspmv_halo *halo_from_lists(int P, int rank, int64_t n_local, const std::vector<std::vector<int32_t>> &lists);
 // host side of uspmv_dist_check (host/dist_check.cpp)
 double check_x(int64_t global_col);
 int64_t check_col(int64_t j, const int32_t *wsa, int P, int rank, bool loopback);

@@ -199,6 +199,15 @@ int uspmv_dcoo_arrays(const uspmv_dcoo_t *p, const int32_t **d_I, const int32_t 
 /* the part copied into the caller's device arrays of nnz elements each (a framework's own allocations; any of them may be NULL) */
 int uspmv_dcoo_copy(const uspmv_dcoo_t *p, int32_t *d_I, int32_t *d_J, double *d_V, void *stream);
 void uspmv_dcoo_free(uspmv_dcoo_t *p);
+/* uspmv_gen_stencil27 on the device (csrc/gen_kernels.hip): rows [row_begin,row_end) as COO arrays in HBM -- row ids local,
+ * column ids global, sorted by row, columns ascending inside a row: what uspmv_dist_create_from_arrays takes (uspmv_dcoo_arrays / _copy /
+ * _free handle the result).  I, J and V equal uspmv_gen_stencil27's in every bit.  magnitude_decades > 0 is refused with
+ * USPMV_ERR_UNSUPPORTED (the host's pow is not the device's; a generated matrix must not depend on where it was generated).  The host
+ * function's other refusals, before any HIP call: bad argument, bad row range (USPMV_ERR_INVALID), more than INT32_MAX rows
+ * (USPMV_ERR_OVERFLOW); more than INT32_MAX local entries: USPMV_ERR_OVERFLOW once they are counted, nothing returned.  Works on `stream`,
+ * returns when the arrays are written. */
+int uspmv_gen_stencil27_device(int64_t nx, int64_t ny, int64_t nz, int dof, uint64_t seed, double magnitude_decades, int64_t row_begin,
+                               int64_t row_end, void *stream, uspmv_dcoo_t **out);
 /* The whole set-up in one call: the partition above, the first part (hi: F64, F32 for ap[sp_hp]) converted with its own sigma ordering
  * (sort_mode as in uspmv_convert_to_scs_device_from_arrays), the other parts (mid: F32; lo: F32 for ap[dp_sp], else F16) with the first
  * part's permutation as their fixed permutation, and the columns of ALL parts permuted by the first part's old_to_new -- the handles the
@@ -872,6 +881,16 @@ int uspmv_dist_autotune(uspmv_dist_t *d, void *d_x, void *d_y, int use_graph, co
  * mismatches = rows that differ on this rank, checksum = sum of the local y in original order (both optional). */
 int uspmv_dist_check(uspmv_dist_t *d, const uspmv_coo_t *local, const int32_t *wsa, void *d_x, void *d_y, int use_graph,
                      void *stream, int64_t *mismatches, double *checksum);
+/* uspmv_dist_check against a block that lives in HBM (d_I local row ids, d_J GLOBAL column ids, d_V; nnz entries sorted by row -- the
+ * arrays the object was made from by uspmv_dist_create_from_arrays, or uspmv_gen_stencil27_device's): the same x, the same single step,
+ * the same meaning of mismatches and checksum.  The rows' entry-ordered FMA chains are evaluated by a kernel from the device arrays (row
+ * bounds from the sorted row ids; F64 object: double chain; F32 object: (float) value and float x, float chain; ap[dp_sp]: the dp chain
+ * over |v| >= threshold_1 and the sp chain over the rest with (double)(float)v, y = dp + sp); x_global is evaluated on the host and
+ * uploaded (O(columns)), the comparison and the checksum run on the host on the downloaded y of the local rows (O(local rows), the
+ * summation order of uspmv_dist_check).  Nothing of O(nnz) exists on the host.  An object of a kind with an fp16 part:
+ * USPMV_ERR_UNSUPPORTED; a column id outside the global matrix (wsa[P] columns): USPMV_ERR_INVALID. */
+int uspmv_dist_check_arrays(uspmv_dist_t *d, const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t nnz, const int32_t *wsa,
+                            void *d_x, void *d_y, int use_graph, void *stream, int64_t *mismatches, double *checksum);
 /* The host half of that check alone (no GPU): y_ref[i] (n_rows of `local`, dtype) = the entry-ordered FMA chain of local row i over
  * x_global[j] = 1 + 1e-3 * (j mod 1000), for steps that do not run on a uspmv_dist object (bench.py's torch.distributed twin). */
 int uspmv_dist_check_reference(const uspmv_coo_t *local, const int32_t *wsa, int rank, int P, int dtype, void *y_ref);

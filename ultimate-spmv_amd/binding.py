@@ -80,6 +80,7 @@ _SIGS = {
     "uspmv_dcoo_arrays": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64)]),
     "uspmv_dcoo_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "uspmv_dcoo_free": (None, [_vp]),
+    "uspmv_gen_stencil27_device": (C.c_int, [_i64, _i64, _i64, C.c_int, C.c_uint64, C.c_double, _i64, _i64, _vp, C.POINTER(_vp)]),
     "uspmv_convert_to_scs_device_ap_from_arrays": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int, C.c_double, C.c_double, C.c_int, _vp,
                                                              C.POINTER(_vp), _vp, _vp, C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "uspmv_dmat_optimize_ap_hp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
@@ -224,6 +225,7 @@ _SIGS = {
     "uspmv_dist_comm_plan": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.POINTER(_i64)), C.POINTER(_i32p), C.POINTER(C.POINTER(_i64))]),
     "uspmv_dist_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "uspmv_dist_check": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
+    "uspmv_dist_check_arrays": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "uspmv_runtime_versions": (C.c_int, [C.POINTER(C.c_int)]),
     "uspmv_debug_backtrace_on_crash": (C.c_int, [C.c_int]),
     "uspmv_hostcomm_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_double, C.POINTER(_vp)]),
@@ -854,6 +856,18 @@ class DistNative:
                                    C.byref(bad), C.byref(cs)))
         return bad.value, cs.value
 
+    def check_arrays(self, d_I, d_J, d_V, x, y, use_graph=False):
+        """uspmv_dist_check_arrays: check() against the block in HBM (d_I local row ids, d_J GLOBAL column ids, d_V: torch int32 / int32 /
+        float64 device tensors, entries sorted by row -- what from_device_arrays took); the reference rows are evaluated on the device.
+        Overwrites x and y.  Returns (mismatching rows, checksum of the local y)."""
+        import torch
+        assert d_I.dtype == torch.int32 and d_J.dtype == torch.int32 and d_V.dtype == torch.float64 and d_I.is_cuda
+        bad, cs = _i64(), C.c_double()
+        self._order(x, y, d_I, d_J, d_V)
+        _ck(lib().uspmv_dist_check_arrays(self.h, _dp(d_I), _dp(d_J), _dp(d_V), int(d_I.numel()), _np_ptr(self._wsa), _dp(x), _dp(y),
+                                          int(bool(use_graph)), self.stream.cuda_stream, C.byref(bad), C.byref(cs)))
+        return bad.value, cs.value
+
     def _order(self, *tensors):
         """the object's stream is non-blocking: make it wait for whatever torch's current stream still does to the tensors
         (zero fills, copies of new_x / new_y), and tell the caching allocator the tensors are used on it"""
@@ -1337,6 +1351,27 @@ def partition_precisions_device(d_I, d_J, d_V, n_rows, n_cols, kind, threshold_1
             if h:
                 lib().uspmv_dcoo_free(h)
     return out
+
+
+def gen_stencil27_device(nx, ny, nz, dof=1, seed=0x5EED, magnitude_decades=0.0, row_begin=0, row_end=None, stream=None, device="cuda"):
+    """gen_stencil27 ON THE DEVICE (uspmv_gen_stencil27_device): rows [row_begin, row_end) as (I, J, V) device tensors -- local row ids,
+    GLOBAL column ids, float64 values, sorted by row: what DistNative.from_device_arrays takes.  Bit for bit the host generator's arrays;
+    magnitude_decades > 0 is refused (UspmvError, status 3).  The tensors are copies owned by torch."""
+    if row_end is None:
+        row_end = nx * ny * nz * dof
+    h = _vp()
+    st = _stream_ptr(stream)
+    _ck(lib().uspmv_gen_stencil27_device(nx, ny, nz, dof, seed, magnitude_decades, row_begin, row_end, st, C.byref(h)))
+    import torch
+    try:
+        n = _i64()
+        _ck(lib().uspmv_dcoo_arrays(h, None, None, None, C.byref(n)))
+        I = torch.empty(n.value, dtype=torch.int32, device=device); J = torch.empty_like(I)
+        V = torch.empty(n.value, dtype=torch.float64, device=device)
+        _ck(lib().uspmv_dcoo_copy(h, _dp(I), _dp(J), _dp(V), st))
+    finally:
+        lib().uspmv_dcoo_free(h)
+    return I, J, V
 
 
 def convert_ap_device_from_arrays(d_I, d_J, d_V, n_rows, n_cols, C_, sigma, kind, threshold_1, threshold_2=0.0, sort=SORT_HOST, want_layout=True,

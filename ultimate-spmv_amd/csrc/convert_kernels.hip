@@ -309,13 +309,7 @@ extern "C" int uspmv_convert_to_scs_device_from_arrays(const int32_t *d_I, const
 }
 
 // ============================================================================ adaptive-precision set-up from device-resident COO arrays
-// One part of uspmv_partition_precisions_device: compacted COO arrays in HBM, owned by the object.
-struct uspmv_dcoo {
-    DeviceBuf<int32_t> I, J;
-    DeviceBuf<double> V;
-    int64_t nnz = 0;
-};
-
+// (struct uspmv_dcoo, one part of uspmv_partition_precisions_device: uspmv_device.hpp)
 namespace {
 
 bool ap_kind_known(int kind) { return kind == USPMV_AP_DP_HP || kind == USPMV_AP_SP_HP || kind == USPMV_AP_DP_SP_HP || kind == USPMV_AP_DP_SP; }

@@ -88,6 +88,14 @@ class PinnedBuf {
     void *p_ = nullptr;
 };
 
+// COO arrays in HBM, owned by the object (uspmv_dcoo_t of the C ABI): one compacted part of uspmv_partition_precisions_device
+// (convert_kernels.hip), or a block of uspmv_gen_stencil27_device (gen_kernels.hip).
+struct uspmv_dcoo {
+    DeviceBuf<int32_t> I, J;
+    DeviceBuf<double> V;
+    int64_t nnz = 0;
+};
+
 namespace uspmv_dev {
 // The shapes of a phased block plan the SpMMV kernels are compiled for: what block_planner.hip plans within, what the device builder
 // (block_plan_kernels.hip) is asked for and what spmmv_phased.hip / spmmv_stream.hip dispatch on.

@@ -1258,6 +1258,85 @@ int setup_from_arrays(const CooSetup &k, const void *comm_id, int comm_rank, int
     return done(finish_setup(k, comm_id, comm_rank, comm_size, rank, P, C, pt, halo, pt[0].scs->old_to_new_idx.data(), pc, n_tiles, n_staged, opt, &D, out));
 }
 
+// ---- the self-check (uspmv_dist_check, uspmv_dist_check_arrays)
+
+// The step of the check: x_perm[k] = x_global[wsa[rank] + new_to_old[k]] in the kernel's (permuted) order, halo tail and padding zero; y
+// preset to a NaN pattern (a row nobody writes cannot pass); one step; hy = the padded y
+int check_step(uspmv_dist *D, const int32_t *wsa, void *d_x, void *d_y, int use_graph, void *stream, std::vector<char> *hy) {
+    const size_t vsz = vsize(D);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<char> hx((size_t)D->vec_len * vsz, 0);
+    hy->resize((size_t)D->vec_len * vsz);
+    const int32_t *n2o = D->scs->new_to_old_idx.data();
+    for (int64_t k = 0; k < D->n_local; ++k) {
+        const double v = uspmv::check_x((int64_t)wsa[D->rank] + n2o[k]);
+        if (D->dtype == USPMV_F64) ((double *)hx.data())[k] = v; else ((float *)hx.data())[k] = (float)v;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(d_x, hx.data(), hx.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_y, 0xff, (size_t)D->n_rows_padded * vsz));
+    if (int rc = uspmv_dist_run(D, d_x, d_y, 1, use_graph, stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(hy->data(), d_y, (size_t)D->n_rows_padded * vsz, hipMemcpyDeviceToHost));
+    return USPMV_OK;
+}
+
+// ... and its verdict: y of the local rows in original order against ref (n_local values of the object's vector type), bitwise
+void check_compare(const uspmv_dist *D, const std::vector<char> &hy, const char *ref, int64_t *mismatches, double *checksum) {
+    const size_t vsz = vsize(D);
+    const int32_t *o2n = D->scs->old_to_new_idx.data();
+    int64_t bad = 0;
+    double sum = 0.0;
+    for (int64_t i = 0; i < D->n_local; ++i) {   // copy_back_result: y_orig[i] = y[old_to_new[i]] (code/utilities.hpp:3862)
+        const char *got = hy.data() + (size_t)o2n[i] * vsz, *want = ref + (size_t)i * vsz;
+        if (memcmp(got, want, vsz) != 0) ++bad;
+        sum += D->dtype == USPMV_F64 ? *(const double *)got : (double)*(const float *)got;
+    }
+    if (mismatches) *mismatches = bad;
+    if (checksum) *checksum = sum;
+}
+
+// The reference rows of uspmv_dist_check_arrays: one lane per local row; its entries are the run of row id `row` in the sorted I (two
+// bisections), taken in entry order as ONE FMA chain from +0 (std::fma of host/dist_check.cpp = the fma instruction here: the calls
+// below are the builtins, nothing is left to contraction).  VT double | float: value and x in VT.  AP (VT double): two chains, the dp one
+// over |v| >= t1, the sp one over |v| < t1 with (double)(float)v, y = dp + sp (uspmv_partition_precisions's branch order; a NaN fits
+// neither and raises flag 4).  xg: x_global by GLOBAL column, in VT.  flag 2: a column outside [0, n_glob).
+template <typename VT, bool AP>
+__global__ void __launch_bounds__(256) check_rows_kernel(const int *__restrict__ I, const int *__restrict__ J, const double *__restrict__ V, const long nnz,
+                                                         const int n_local, const int n_glob, const VT *__restrict__ xg, const double t1,
+                                                         VT *__restrict__ y_ref, int *__restrict__ flag) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n_local) return;
+    auto lower = [&](const int key) {                     // first k with I[k] >= key
+        long lo = 0, hi = nnz;
+        while (lo < hi) {
+            const long mid = (lo + hi) >> 1;
+            if (I[mid] < key) lo = mid + 1; else hi = mid;
+        }
+        return lo;
+    };
+    const long k0 = lower(row), k1 = lower(row + 1);
+    VT a = VT(0), b = VT(0);
+    int err = 0;
+    for (long k = k0; k < k1; ++k) {
+        const int j = J[k];
+        if (j < 0 || j >= n_glob) { err |= 2; continue; }
+        const double v = V[k];
+        if constexpr (AP) {
+            const double av = __builtin_fabs(v);
+            if (av >= t1) a = __builtin_fma(v, xg[j], a);
+            else if (av < t1) b = __builtin_fma((double)(float)v, xg[j], b);
+            else err |= 4;
+        } else if constexpr (sizeof(VT) == 8) {
+            a = __builtin_fma(v, xg[j], a);
+        } else {
+            a = __builtin_fmaf((float)v, xg[j], a);
+        }
+    }
+    y_ref[row] = AP ? a + b : a;
+    if (err) atomicOr(flag, err);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1629,36 +1708,59 @@ int uspmv_dist_check(uspmv_dist_t *D, const uspmv_coo_t *local, const int32_t *w
     if (!D->scs) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_check: needs an object made by uspmv_dist_create_from_coo (it owns the row permutation)");
     if (local->n_rows != D->n_local || wsa[D->rank + 1] - wsa[D->rank] != D->n_local)
         return uspmv::fail(USPMV_ERR_INVALID, "uspmv_dist_check: the COO block has %ld rows, the object %ld", (long)local->n_rows, (long)D->n_local);
-    const size_t vsz = vsize(D);
-    const int64_t nl = D->n_local;
-    hipStream_t st = (hipStream_t)stream;
-    // x in the kernel's (permuted) order: x_perm[k] = x_global[wsa[rank] + new_to_old[k]]; halo tail and padding zero
-    std::vector<char> hx((size_t)D->vec_len * vsz, 0), hy((size_t)D->vec_len * vsz);
-    const int32_t *n2o = D->scs->new_to_old_idx.data(), *o2n = D->scs->old_to_new_idx.data();
-    for (int64_t k = 0; k < nl; ++k) {
-        const double v = uspmv::check_x((int64_t)wsa[D->rank] + n2o[k]);
-        if (D->dtype == USPMV_F64) ((double *)hx.data())[k] = v; else ((float *)hx.data())[k] = (float)v;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(d_x, hx.data(), hx.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_y, 0xff, (size_t)D->n_rows_padded * vsz));            // NaN pattern: a row nobody writes cannot pass
-    if (int rc = uspmv_dist_run(D, d_x, d_y, 1, use_graph, stream)) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(hy.data(), d_y, (size_t)D->n_rows_padded * vsz, hipMemcpyDeviceToHost));
-    std::vector<char> ref((size_t)std::max<int64_t>(nl, 1) * vsz);
+    std::vector<char> hy;
+    if (int rc = check_step(D, wsa, d_x, d_y, use_graph, stream, &hy)) return rc;
+    std::vector<char> ref((size_t)std::max<int64_t>(D->n_local, 1) * vsize(D));
     if (int rc = has_hp(D) ? uspmv::dist_reference_rows_ap_hp(local, wsa, D->P, D->rank, D->loopback, D->kind, D->ap_threshold, D->ap_threshold_2, ref.data())
                  : is_ap(D) ? uspmv::dist_reference_rows_ap(local, wsa, D->P, D->rank, D->loopback, D->ap_threshold, (double *)ref.data())
                             : uspmv::dist_reference_rows(local, wsa, D->P, D->rank, D->loopback, D->dtype, ref.data()))
         return rc;
-    int64_t bad = 0;
-    double sum = 0.0;
-    for (int64_t i = 0; i < nl; ++i) {   // copy_back_result: y_orig[i] = y[old_to_new[i]] (code/utilities.hpp:3862)
-        const char *got = hy.data() + (size_t)o2n[i] * vsz, *want = ref.data() + (size_t)i * vsz;
-        if (memcmp(got, want, vsz) != 0) ++bad;
-        sum += D->dtype == USPMV_F64 ? *(const double *)got : (double)*(const float *)got;
+    check_compare(D, hy, ref.data(), mismatches, checksum);
+    return USPMV_OK;
+}
+
+// ... against a block that lives in HBM: the reference rows by check_rows_kernel from the device arrays, over an x_global evaluated on the
+// host exactly as dist_reference_rows evaluates it (check_x of check_col: in loopback a halo column reads this block's own row) and
+// uploaded in the vector type -- O(columns), and the device never re-derives that expression
+int uspmv_dist_check_arrays(uspmv_dist_t *D, const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t nnz, const int32_t *wsa, void *d_x,
+                            void *d_y, int use_graph, void *stream, int64_t *mismatches, double *checksum) {
+    const char *who = "uspmv_dist_check_arrays";
+    if (!D || !wsa || !d_x || !d_y || nnz < 0 || (nnz > 0 && (!d_I || !d_J || !d_V))) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (has_hp(D)) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: not available on an %s object (its check is uspmv_dist_check, on the host block)", who, ap_name(D));
+    if (!D->scs) return uspmv::fail(USPMV_ERR_INVALID, "%s: needs an object made by uspmv_dist_create_from_coo / _from_arrays (it owns the row permutation)", who);
+    if (wsa[D->rank + 1] - wsa[D->rank] != D->n_local)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: work_sharing_arr gives this rank %ld rows, the object has %ld", who, (long)(wsa[D->rank + 1] - wsa[D->rank]), (long)D->n_local);
+    const size_t vsz = vsize(D);
+    const int64_t nl = D->n_local, n_glob = wsa[D->P];
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<char> hy;
+    if (int rc = check_step(D, wsa, d_x, d_y, use_graph, stream, &hy)) return rc;
+    std::vector<char> xg((size_t)std::max<int64_t>(n_glob, 1) * vsz);
+    for (int64_t j = 0; j < n_glob; ++j) {
+        const double v = uspmv::check_x(uspmv::check_col(j, wsa, D->P, D->rank, D->loopback));
+        if (D->dtype == USPMV_F64) ((double *)xg.data())[j] = v; else ((float *)xg.data())[j] = (float)v;
     }
-    if (mismatches) *mismatches = bad;
-    if (checksum) *checksum = sum;
+    DeviceBuf<void> d_xg, d_ref;
+    DeviceBuf<int> d_flag;
+    HIP_TRY(d_xg.upload(xg.data(), xg.size()));
+    HIP_TRY(d_ref.alloc((size_t)nl * vsz));
+    HIP_TRY(d_flag.zeros(4));
+    const dim3 grid((unsigned)((nl + 255) / 256)), block(256);
+    if (is_ap(D))
+        hipLaunchKernelGGL((check_rows_kernel<double, true>), grid, block, 0, st, d_I, d_J, d_V, (long)nnz, (int)nl, (int)n_glob, (const double *)d_xg.get(), D->ap_threshold, (double *)d_ref.get(), d_flag.get());
+    else if (D->dtype == USPMV_F64)
+        hipLaunchKernelGGL((check_rows_kernel<double, false>), grid, block, 0, st, d_I, d_J, d_V, (long)nnz, (int)nl, (int)n_glob, (const double *)d_xg.get(), 0.0, (double *)d_ref.get(), d_flag.get());
+    else
+        hipLaunchKernelGGL((check_rows_kernel<float, false>), grid, block, 0, st, d_I, d_J, d_V, (long)nnz, (int)nl, (int)n_glob, (const float *)d_xg.get(), 0.0, (float *)d_ref.get(), d_flag.get());
+    HIP_TRY(hipGetLastError());
+    std::vector<char> ref((size_t)std::max<int64_t>(nl, 1) * vsz);
+    int h_flag = 0;
+    HIP_TRY(hipMemcpyAsync(ref.data(), d_ref, (size_t)nl * vsz, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_flag & 2) return uspmv::fail(USPMV_ERR_INVALID, "%s: a column index lies outside the global matrix (work_sharing_arr ends at %ld)", who, (long)n_glob);
+    if (h_flag & 4) return uspmv::fail(USPMV_ERR_INVALID, "%s: an element fits neither part", who);
+    check_compare(D, hy, ref.data(), mismatches, checksum);
     return USPMV_OK;
 }
 

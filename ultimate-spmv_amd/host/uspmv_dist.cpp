@@ -17,6 +17,9 @@
 // Every rank holds ONLY its row block: generated matrices (gen:...) are generated per block (the partition comes from the
 // analytic row counts); a .mtx file is read by rank 0 alone, which writes one binary block per rank (file names carry the
 // segment's nonce) -- the reference's root-reads-and-scatters (code/mpi_funcs.hpp:739-860) without MPI.
+// -convert device | device_stable: the rank's set-up runs on the device from the block in HBM (uspmv_dist_create_from_arrays_ex); a gen:
+// block is then generated there (uspmv_gen_stencil27_device) and self-checked there (uspmv_dist_check_arrays), any other block is the
+// host block uploaded -- see "this rank's row block" below and DESIGN.md 6.12.
 //
 // Protocols: the reference's (100 warm-ups, doubling batches until -bench_time, code/main.cpp:408-474) by default;
 // `-bench_steps K [-bench_warmup W]` times EXACTLY K steps between barriers (what bench.py --gpus N asks for).  -ba_synch 1
@@ -133,21 +136,44 @@ int uspmv_run_distributed(const DistConfig &c) {
     }
 
     // ---- this rank's row block (and nothing else)
+    //      -convert device | device_stable: the set-up reads the block from HBM.  A gen: block with decades 0 is GENERATED there
+    //      (uspmv_gen_stencil27_device) and the host block never exists, unless something below reads the host block: -equilibrate 1 scales
+    //      it, -rand_x 1 | m takes the min / max of its values, -step_form auto_all self-checks a pad / fused winner against it.  Those runs,
+    //      gen: with decades > 0 (the host's pow) and every .mtx block build the host block as before and UPLOAD it.
+    //      USPMV_DEVICE_BLOCK=upload forces the uploaded source (A/B of the two sources on one command).
     std::vector<int32_t> wsa((size_t)P + 1, 0), metis_perm;
     uspmv_coo_t *local = nullptr;
-    int64_t n_rows_g = 0, nnz_g = 0;
+    uspmv_dcoo_t *dblock = nullptr;            // the generated block in HBM (device_generated)
+    int32_t *up_I = nullptr, *up_J = nullptr;  // the uploaded block (device_uploaded), released once the object exists
+    double *up_V = nullptr;
+    const int32_t *d_I = nullptr, *d_J = nullptr;
+    const double *d_V = nullptr;
+    int64_t d_nnz = 0;
+    int64_t n_rows_g = 0, n_cols_g = 0, nnz_g = 0;
     const int seg = c.seg_nnz ? USPMV_SEG_NNZ : USPMV_SEG_ROWS;
+    const bool dev_route = c.convert != "host";
+    bool dev_gen = false;
+    const char *force_src = getenv("USPMV_DEVICE_BLOCK");
+    double block_s = 0, object_s = 0;
+    auto t_block = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
     if (c.matrix_name.rfind("gen:", 0) == 0) {
         long nx = 0, ny = 0, nz = 0; int dof = 1; double dec = 0.0;
         if (sscanf(c.matrix_name.c_str() + 4, "%ldx%ldx%ld:%d:%lf", &nx, &ny, &nz, &dof, &dec) < 3) die("generator syntax: gen:NXxNYxNZ[:dof[:decades]]");
-        n_rows_g = (int64_t)nx * ny * nz * dof;
+        n_rows_g = n_cols_g = (int64_t)nx * ny * nz * dof;
         {
             std::vector<int32_t> counts((size_t)n_rows_g);
             CK(uspmv_gen_stencil27_row_counts(nx, ny, nz, dof, 0, n_rows_g, counts.data()));
             for (int32_t v : counts) nnz_g += v;
             CK(uspmv_seg_from_row_counts(counts.data(), n_rows_g, seg, P, wsa.data()));
         }
-        CK(uspmv_gen_stencil27(nx, ny, nz, dof, 0x5EED, dec, wsa[(size_t)rank], wsa[(size_t)rank + 1], &local));
+        dev_gen = dev_route && !(dec > 0.0) && !c.equilibrate && c.random_init_x == '0' && c.step_form != "auto_all" &&
+                  !(force_src && !strcmp(force_src, "upload"));
+        t_block = std::chrono::steady_clock::now();       // (the partition above is every route's; the block is what the routes build differently)
+        if (dev_gen) {
+            CK(uspmv_gen_stencil27_device(nx, ny, nz, dof, 0x5EED, dec, wsa[(size_t)rank], wsa[(size_t)rank + 1], nullptr, &dblock));
+            CK(uspmv_dcoo_arrays(dblock, &d_I, &d_J, &d_V, &d_nnz));
+        } else CK(uspmv_gen_stencil27(nx, ny, nz, dof, 0x5EED, dec, wsa[(size_t)rank], wsa[(size_t)rank + 1], &local));
     } else {
         std::vector<int64_t> meta((size_t)P + 3, 0);
         if (comm_rank == 0) {
@@ -187,6 +213,8 @@ int uspmv_run_distributed(const DistConfig &c) {
             unlink(block_path(nonce, rank).c_str());
         }
     }
+    block_s = since(t_block);
+    if (local) { int64_t nr_ = 0, nz_ = 0; CK(uspmv_coo_dims(local, &nr_, &n_cols_g, &nz_)); }
 
     stage("matrix block built");
     // ---- the distributed object: convert, halo discovery, upload, plan, exchange plan, communicator (init_local_structs + collect_comm_info)
@@ -213,10 +241,47 @@ int uspmv_run_distributed(const DistConfig &c) {
     }
     // -equilibrate 1: every rank scales ITS block (rows, then columns of the row-scaled block), as the reference does after the
     // segmentation (code/main.cpp:1117-1125 on local_mtx)
+    t_block = std::chrono::steady_clock::now();
     if (c.equilibrate) CK(uspmv_coo_equilibrate(local));
-    if (c.ap) CK(uspmv_dist_create_ap_from_coo_ex(host_exchange || peer_exchange ? nullptr : id, comm_rank, comm_size, rank, P, local, wsa.data(), c.C, c.sigma, c.ap_threshold_1, c.tlc ? 1 : 0, &opt, &D));
-    else CK(uspmv_dist_create_from_coo_ex(host_exchange || peer_exchange ? nullptr : id, comm_rank, comm_size, rank, P, local, wsa.data(), c.C, c.sigma, c.sp ? USPMV_F32 : USPMV_F64, c.tlc ? 1 : 0, &opt, &D));
-    // (the block's COO stays until the end: -rand_x reads its values, -step_form auto and -check_y run the self-check against it)
+    if (dev_route && !dev_gen) {   // the host block, built and scaled as on the host route, into three device arrays
+        const int32_t *ci = nullptr, *cj = nullptr;
+        const double *cv = nullptr;
+        int64_t nr_ = 0, nc_ = 0;
+        CK(uspmv_coo_dims(local, &nr_, &nc_, &d_nnz));
+        CK(uspmv_coo_arrays(local, &ci, &cj, &cv));
+        const size_t ne = (size_t)std::max<int64_t>(d_nnz, 1);
+        HK(hipMalloc((void **)&up_I, 4 * ne)); HK(hipMalloc((void **)&up_J, 4 * ne)); HK(hipMalloc((void **)&up_V, 8 * ne));
+        HK(hipMemcpy(up_I, ci, 4 * (size_t)d_nnz, hipMemcpyHostToDevice));
+        HK(hipMemcpy(up_J, cj, 4 * (size_t)d_nnz, hipMemcpyHostToDevice));
+        HK(hipMemcpy(up_V, cv, 8 * (size_t)d_nnz, hipMemcpyHostToDevice));
+        d_I = up_I; d_J = up_J; d_V = up_V;
+    }
+    block_s += since(t_block);
+    const void *comm_id = host_exchange || peer_exchange ? nullptr : id;
+    const auto t_object = std::chrono::steady_clock::now();
+    if (dev_route)
+        CK(uspmv_dist_create_from_arrays_ex(comm_id, comm_rank, comm_size, rank, P, d_I, d_J, d_V, d_nnz, n_cols_g, wsa.data(), c.C, c.sigma,
+                                            c.ap ? USPMV_AP_DP_SP : USPMV_ONE_PRECISION, c.sp ? USPMV_F32 : USPMV_F64, c.ap ? c.ap_threshold_1 : 0.0, 0.0,
+                                            c.tlc ? 1 : 0, c.convert == "device_stable" ? USPMV_SORT_DEVICE_STABLE : USPMV_SORT_HOST, &opt, nullptr, &D));
+    else if (c.ap) CK(uspmv_dist_create_ap_from_coo_ex(comm_id, comm_rank, comm_size, rank, P, local, wsa.data(), c.C, c.sigma, c.ap_threshold_1, c.tlc ? 1 : 0, &opt, &D));
+    else CK(uspmv_dist_create_from_coo_ex(comm_id, comm_rank, comm_size, rank, P, local, wsa.data(), c.C, c.sigma, c.sp ? USPMV_F32 : USPMV_F64, c.tlc ? 1 : 0, &opt, &D));
+    object_s = since(t_object);
+    const char *route = !dev_route ? "host" : dev_gen ? "device_generated" : "device_uploaded";
+    if (dev_route && comm_rank == 0)
+        printf("distributed set-up on the device from the block in HBM (%s; %s)\n", dev_gen ? "block generated on the device" : "host block uploaded",
+               c.convert == "device_stable" ? "stable tie order" : "the reference's tie order");
+    // the device arrays go as soon as nothing needs them: the uploaded copy now (everything that reads the block reads the host block, which
+    // stays until the end: -rand_x reads its values, -step_form auto and -check_y run the self-check against it); the generated block now
+    // too, unless -check_y will run uspmv_dist_check_arrays against it
+    if (up_I) { (void)hipFree(up_I); (void)hipFree(up_J); (void)hipFree(up_V); up_I = up_J = nullptr; up_V = nullptr; d_I = d_J = nullptr; d_V = nullptr; }
+    const bool check_wanted = c.check_y && c.comm_halos && (c.mode == 's' || c.block_vec_size == 1);
+    auto free_dblock = [&]() { uspmv_dcoo_free(dblock); dblock = nullptr; d_I = d_J = nullptr; d_V = nullptr; };
+    if (dblock && !check_wanted) free_dblock();
+    // the self-check of this run's source: against the host block, or against the generated block in HBM
+    auto self_check = [&](void *x, void *y, int graph, hipStream_t s, int64_t *mm, double *cs) {
+        if (dev_gen) CK(uspmv_dist_check_arrays(D, d_I, d_J, d_V, d_nnz, wsa.data(), x, y, graph, s, mm, cs));
+        else CK(uspmv_dist_check(D, local, wsa.data(), x, y, graph, s, mm, cs));
+    };
     stage("step object created (communicator up)");
     hipStream_t st = nullptr;
     HK(hipStreamCreate(&st));
@@ -232,10 +297,16 @@ int uspmv_run_distributed(const DistConfig &c) {
     CK(uspmv_dist_info(D, meta));
     const int64_t n_local = meta[0], n_halo = meta[1], vec_len = meta[2], n_send = meta[3];
     const uspmv_scs_t *scs = nullptr, *scs_sp = nullptr;   // (ap[dp_sp]: scs is the dp struct, which carries the row permutation)
-    CK(uspmv_dist_parts_ap(D, &scs, &scs_sp, nullptr, nullptr, nullptr));
+    const uspmv_dmat_t *A_sp = nullptr;
+    CK(uspmv_dist_parts_ap(D, &scs, &scs_sp, nullptr, &A_sp, nullptr));
     int64_t sm[8], sm_sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     CK(uspmv_scs_meta(scs, sm));
     if (scs_sp) CK(uspmv_scs_meta(scs_sp, sm_sp));
+    else if (c.ap && A_sp) {   // (an object made from arrays hands out no struct for the sp part: its element count from the handle)
+        int64_t hm[4];
+        CK(uspmv_dmat_meta(A_sp, hm));
+        sm_sp[6] = hm[2];
+    }
     const int64_t n_pad = sm[4], n_chunks = sm[5], n_el = sm[6];
     const int32_t *o2n, *n2o;
     CK(uspmv_scs_arrays(scs, nullptr, nullptr, nullptr, nullptr, &o2n, &n2o));
@@ -314,13 +385,14 @@ int uspmv_run_distributed(const DistConfig &c) {
         }
         int64_t mm = -1, tot = -1;
         if (c.check_y && comm_halos) {
-            CK(uspmv_dist_check(D, local, wsa.data(), d_x, d_y, 0, st, &mm, nullptr));
+            self_check(d_x, d_y, 0, st, &mm, nullptr);
             std::vector<int64_t> all((size_t)std::max(P, comm_size), 0);
             CK(uspmv_dist_allgather_i64(D, mm, all.data(), st));
             tot = 0;
             for (int p = 0; p < (meta[8] ? 1 : comm_size); ++p) tot += all[(size_t)p];
         }
         uspmv_coo_free(local);
+        free_dblock();
         if (rank == 0)
             printf("solve mode: %lu revision(s) done on %d ranks%s%s\n", c.n_repetitions, P, meta[8] ? " (loopback)" : "",
                    tot < 0 ? "" : tot == 0 ? ", y checked bitwise on every rank: ok" : ", y CHECK FAILED");
@@ -361,6 +433,8 @@ int uspmv_run_distributed(const DistConfig &c) {
             int best = USPMV_STEP_OVERLAP;
             double tms[4];
             CK(uspmv_dist_set_option(D, "autotune_all", form == "auto_all"));   // (pad / fused: timed on request only, see uspmv_dist_autotune)
+            // (local is NULL when the block was generated on the device: only auto_all's pad / fused winners are self-checked, and auto_all
+            //  takes the uploaded source)
             CK(uspmv_dist_autotune(D, d_x, d_y, c.use_graph ? 1 : 0, local, wsa.data(), st, &best, tms));
             for (int k = 0; k < 4; ++k) {
                 if (tms[k] == 0) continue;
@@ -441,7 +515,7 @@ int uspmv_run_distributed(const DistConfig &c) {
     int64_t mism = -1, mism_total = -1;
     double checksum = 0;
     if (c.check_y && b == 1 && comm_halos) {
-        CK(uspmv_dist_check(D, local, wsa.data(), d_x, d_y, c.use_graph ? 1 : 0, st, &mism, &checksum));
+        self_check(d_x, d_y, c.use_graph ? 1 : 0, st, &mism, &checksum);
         std::vector<int64_t> all((size_t)std::max(P, comm_size), 0);
         CK(uspmv_dist_allgather_i64(D, mism, all.data(), st));
         mism_total = 0;
@@ -450,6 +524,7 @@ int uspmv_run_distributed(const DistConfig &c) {
         if (mism) fprintf(stderr, "[rank %d] CHECK FAILED: %ld of %ld local rows differ from the entry-ordered FMA chains\n", rank, (long)mism, (long)n_local);
     }
     uspmv_coo_free(local);
+    free_dblock();
 
     // ---- report
     std::vector<int64_t> halos((size_t)std::max(P, comm_size), 0), sends((size_t)std::max(P, comm_size), 0);
@@ -527,7 +602,9 @@ int uspmv_run_distributed(const DistConfig &c) {
                      mism_total < 0 ? "null" : mism_total == 0 ? "true" : "false", (long)mism_total, checksum, (long)n_local, (long)n_halo, (long)n_send,
                      (long)meta[4], (long)meta[5], meta[6] ? "true" : "false", (long)n_el, (long)n_chunks, (long)n_pad, bytes, kernel_ms,
                      rccl_nranks, ver[0], ver[1], ver[2], ver[3]);
-            const std::string full = std::string(js) + ", \"per_rank\": " + per_rank + "}";
+            char setup[160];                                   // which set-up ran (-convert) and what it cost this rank
+            snprintf(setup, sizeof setup, ", \"setup\": {\"route\": \"%s\", \"block_s\": %.6f, \"object_s\": %.6f}", route, block_s, object_s);
+            const std::string full = std::string(js) + setup + ", \"per_rank\": " + per_rank + "}";
             if (c.json == "-") printf("%s\n", full.c_str());
             else { std::ofstream jf(c.json); jf << full << std::endl; }
         }

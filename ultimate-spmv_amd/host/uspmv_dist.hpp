@@ -25,6 +25,10 @@ struct DistConfig {
     bool sp = false;                           // -sp: single precision matrix, vectors and exchange
     bool ap = false;                           // -ap[dp_sp]: the adaptive-precision object (uspmv_dist_create_ap_from_coo), double vectors, single vector, scs
     double ap_threshold_1 = 0.0;               // ... -ap_threshold_1: entries with |v| >= it stay double
+    // -convert host | device | device_stable: where the rank's set-up runs.  host: uspmv_dist_create[_ap]_from_coo_ex on the host block.
+    // device (the reference's tie order of the sigma sort) | device_stable (ties in original order): uspmv_dist_create_from_arrays_ex on
+    // the block in HBM -- generated there when nothing needs the host block, else the host block uploaded (uspmv_dist.cpp)
+    std::string convert = "host";
     char mode = 'b';                           // -mode s: the reference's COMM-spmv-SWAP loop (code/main.cpp:528-607), -rev iterations, no timing
     unsigned long n_repetitions = 1;
     std::string dump_y;                        // -dump_y <file>: every rank writes y of its rows (original order, raw doubles) to <file>.<rank>

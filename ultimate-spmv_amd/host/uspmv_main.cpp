@@ -81,7 +81,9 @@ void usage() {
             "  -dropout_threshold <float> -block_vec_layout <colwise|rowwise> -tlc <0|1> -graph <0|1> -dump_y <file>\n"
             "  -mpi_mode <singlevec|multivec|bulkvec>\n"
             "  -bench_steps <int> -bench_warmup <int> -json <file|-> (fixed-count protocol, JSON report)  -x_prepared <0|1> (bench mode, column-major block vectors: X re-laid out once)\n"
-            "  -convert <host|device|device_stable> (where convert_to_scs runs; device_stable: ties of the sigma sort in original order)\n"
+            "  -convert <host|device|device_stable> (where convert_to_scs runs; device_stable: ties of the sigma sort in original order;\n"
+            "    multi-rank runs: the whole per-rank set-up on the device, any of -dp|-sp|-ap[dp_sp] -- a gen: block with decades 0 is generated\n"
+            "    in HBM unless -equilibrate 1, -rand_x 1|m or -step_form auto_all need the host block, which is then uploaded, as a .mtx block is)\n"
             "  -tune <key>=<int> (a tuning key of the library, e.g. tlc_idx12=0, spmmv_reorder=1; repeatable)\n"
             "  multi-rank runs: -check_y <0|1> -step_form <auto|auto_all|overlap|plain|pad|fused>  (-ap[dp_sp]: scs, single vector, no auto_all / fused)\n"
             "  -seg_metis [-part_file <file>]: graph partition (built-in level-set partitioner, or part ids from a gpmetis-style file)\n");
@@ -147,8 +149,8 @@ Config parse(int argc, char **argv) {
         die("Row-wise block vector layout selected, but block vector width is 1.\n Please choose colwise block vector layout if using SpMV.");
     bool ap = c.value_type.rfind("ap[", 0) == 0;
     if (c.block_vec_size > 1 && ap) die("SpMMV is not yet implemented for AP kernels.");
-    if (c.convert != "host" && ap) die("-convert device needs a one-precision run (-dp or -sp).");
-    if (c.convert != "host" && uspmv_dist_requested()) die("-convert device is a single-rank option (every rank of a multi-rank run converts its block on the host).");
+    // (a multi-rank run takes -convert device with -ap[dp_sp] too: uspmv_dist_create_from_arrays_ex splits on the device)
+    if (c.convert != "host" && ap && !uspmv_dist_requested()) die("-convert device needs a one-precision run (-dp or -sp).");
     if (c.seg_method == "seg-metis" && !uspmv_dist_requested()) die("seg-metis selected, but this is a single-rank run (the partition only matters across ranks).");
     if (c.seg_method == "seg-metis" && c.matrix_file_name.rfind("gen:", 0) == 0) die("seg-metis needs the whole matrix on rank 0: use a .mtx file (generated matrices are built per rank).");
     if (c.value_type == "hp" || c.value_type == "ap[sp_hp]" || c.value_type == "ap[dp_hp]" || c.value_type == "ap[dp_sp_hp]")
@@ -507,6 +509,7 @@ int main(int argc, char **argv) {
         d.check_y = c.check_y != 0 || (c.mode == 's' && c.validate_result != 0 && c.comm_halos != 0);
         d.equilibrate = c.equilibrate != 0;
         d.ap = dist_ap; d.ap_threshold_1 = c.ap_threshold_1;
+        d.convert = c.convert;
         // (-par_pack: on the device the send buffer is packed by one kernel either way, as in the reference's device branch, code/classes_structs.hpp:787-806)
         return uspmv_run_distributed(d);   // every rank generates / receives only its row block
     }

@@ -76,6 +76,14 @@ int uspmv_coo_write_mtx(const uspmv_coo_t *m, const char *path, int symmetric);
 /* -equilibrate 1 of a one-precision run: equilibrate_matrix (code/utilities.hpp:2667-2685), in place.  (With
  * ap[dp_sp] the reference indexes two empty vectors here, code/main.cpp:1143-1153 -- undefined behaviour, not offered.) */
 int uspmv_coo_equilibrate(uspmv_coo_t *m);
+/* The same, in place and bit for bit, handing out the two divisor vectors that the equilibrated branch of partition_precisions takes
+ * (largest_row_elems, largest_col_elems; code/main.cpp:1147-1153 calls extract_largest_row_elems, scale_matrix_rows,
+ * extract_largest_col_elems, scale_matrix_cols of code/utilities.hpp:2605-2665 in this order): row_max[n_rows] = largest magnitude of
+ * every row, col_max[n_cols] = largest magnitude of every column of the ROW-SCALED matrix; 0 for an empty row or column.  (The
+ * reference's CLI indexes two empty vectors there; its library function is sound for vectors sized like these.)
+ * USPMV_ERR_INVALID, before any value is written: a non-finite value, or an entry whose row or column divisor is 0 (a row or column of
+ * explicit zeros only, or scaled values that underflowed to 0) -- 0 / 0 is a NaN whose sign differs between x86 and the GPU. */
+int uspmv_coo_equilibrate_scales(uspmv_coo_t *m, double *row_max, double *col_max);
 /* MtxData filled by a host application (API_doc.md:7-9).  Arrays are copied. */
 int uspmv_coo_create(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t *I, const int32_t *J,
                      const double *values, uspmv_coo_t **out);
@@ -141,6 +149,16 @@ int uspmv_partition_precisions(const uspmv_coo_t *m, double threshold_1, uspmv_c
 enum { USPMV_AP_DP_HP = 0, USPMV_AP_SP_HP = 1, USPMV_AP_DP_SP_HP = 2, USPMV_AP_DP_SP = 3 };   /* (DP_SP: the device-side set-up below only) */
 int uspmv_partition_precisions_hp(const uspmv_coo_t *m, int kind, double threshold_1, double threshold_2, uspmv_coo_t **hi,
                                   uspmv_coo_t **mid, uspmv_coo_t **hp);
+/* partition_precisions, the EQUILIBRATED branch of all four kinds (config->equilibrate: code/utilities.hpp:2883-2896 ap[dp_sp],
+ * :2934-2950 ap[dp_hp], :2989-3007 ap[sp_hp], :3046-3078 ap[dp_sp_hp]; library twin code/interface.hpp:691-987).  m is the matrix
+ * uspmv_coo_equilibrate_scales scaled, row_max / col_max its vectors.  Entry k = (I, J, v) has its own thresholds
+ * T1 = threshold_1 / (col_max[J] * row_max[I]) and T2 likewise (one multiplication, one division):
+ *   two-part kinds     |v| >= T1 -> hi, else -> lo (a plain else: a NaN goes to lo, where the non-equilibrated branch refuses it)
+ *   USPMV_AP_DP_SP_HP  |v| >= T1 -> hi, else T2 <= |v| <= T1 -> mid, else -> lo
+ * Stored values as in uspmv_partition_precisions[_hp]: (double)(float)v for an sp part, one rounding to binary16 for an hp part.
+ * parts[0] = hi, parts[1] = mid (NULL for the two-part kinds), parts[2] = lo, as uspmv_partition_precisions_device; COO order kept. */
+int uspmv_partition_precisions_eq(const uspmv_coo_t *m, int kind, double threshold_1, double threshold_2, const double *row_max,
+                                  const double *col_max, uspmv_coo_t *parts[3]);
 
 /* ------------------------------------------------------------------ L3: device kernels    */
 int uspmv_device_count(int *count);
@@ -222,6 +240,34 @@ int uspmv_convert_to_scs_device_ap_from_arrays(const int32_t *d_I, const int32_t
                                                int64_t nnz, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2,
                                                int sort_mode, void *stream, uspmv_scs_t **layout, int32_t *d_old_to_new, int32_t *d_new_to_old,
                                                int64_t part_nnz[3], uspmv_dmat_t **hi, uspmv_dmat_t **mid, uspmv_dmat_t **lo);
+/* uspmv_coo_equilibrate_scales on the device (csrc/equilibrate_kernels.hip): device COO sorted by row as above; the
+ * scaled values go to d_V_out (nnz doubles; may be d_V), the divisors to d_row_max[n_rows] and d_col_max[n_cols].  Values and vectors
+ * equal the host function's bit for bit (max is order-independent, IEEE division exact).  Three passes: row maxima by a segmented
+ * maximum per wave (an atomic only for a row's run that crosses a wave), column maxima of the row-scaled values by a 64-bit integer
+ * atomic maximum on the bit pattern, issued only where a plain load shows a smaller value, then the scaling.  The host function's
+ * refusals (USPMV_ERR_INVALID: non-finite value, zero divisor) and the index / row-order checks of uspmv_partition_precisions_device
+ * are raised through a flag BEFORE d_V_out is written; the two vectors are overwritten either way.  Works on `stream`, returns when
+ * d_V_out is written.  No device memory beyond a flag word. */
+int uspmv_equilibrate_device(const int32_t *d_I, const int32_t *d_J, const double *d_V, double *d_V_out, int64_t n_rows, int64_t n_cols,
+                             int64_t nnz, double *d_row_max, double *d_col_max, void *stream);
+/* diagnosis (tools/ap_equilibrate_probe.py): the column pass alone, with the vectors as uspmv_equilibrate_device left d_row_max and a
+ * zeroed d_col_max, counting the atomics it issues after the skip */
+int uspmv_equilibrate_device_count_atomics(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                                           int64_t nnz, const double *d_row_max, double *d_col_max, void *stream, int64_t *n_atomics);
+/* uspmv_partition_precisions_eq on the device: uspmv_partition_precisions_device with the per-entry thresholds
+ * t / (d_col_max[J] * d_row_max[I]) (device vectors of n_rows / n_cols doubles, as uspmv_equilibrate_device wrote them; d_V the scaled
+ * values).  Every part equals the host function's bit for bit; no element is refused as fitting no part. */
+int uspmv_partition_precisions_device_eq(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                                         int kind, double threshold_1, double threshold_2, const double *d_row_max, const double *d_col_max,
+                                         void *stream, uspmv_dcoo_t *parts[3]);
+/* uspmv_convert_to_scs_device_ap_from_arrays of an equilibrated matrix: the same set-up with the partition above (both vectors NULL:
+ * the unscaled function).  The handles, the layout and the permutations are those of the host route uspmv_coo_equilibrate_scales ->
+ * uspmv_partition_precisions_eq -> uspmv_convert_to_scs with the first part's permutation -> uspmv_permute_scs_cols -> upload. */
+int uspmv_convert_to_scs_device_ap_from_arrays_eq(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                                                  int64_t nnz, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2,
+                                                  const double *d_row_max, const double *d_col_max, int sort_mode, void *stream,
+                                                  uspmv_scs_t **layout, int32_t *d_old_to_new, int32_t *d_new_to_old, int64_t part_nnz[3],
+                                                  uspmv_dmat_t **hi, uspmv_dmat_t **mid, uspmv_dmat_t **lo);
 /* copies of the device arrays of a handle (any pointer may be NULL): n_chunks+1, n_chunks, n_elements, n_elements */
 int uspmv_dmat_download(const uspmv_dmat_t *m, int32_t *chunk_ptrs, int32_t *chunk_lengths, int32_t *col_idxs, void *values);
 /* Wrap arrays that already live in HBM (owned by the caller, e.g. a framework allocator). */

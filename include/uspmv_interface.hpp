@@ -129,6 +129,33 @@ inline void partition_precisions(double ap_threshold_1, MtxData<double, int> *lo
     fill(sp, sp_local_mtx);
 }
 
+// ap[dp_sp] split with the reference's scaling arguments (code/interface.hpp:691-987): is_equilibrated takes the branch of
+// code/utilities.hpp:2883-2896 -- local_mtx scaled, largest_row_elems of n_rows and largest_col_elems of n_cols elements, as
+// uspmv_coo_equilibrate_scales hands them out -- and the overload above otherwise
+inline void partition_precisions(double ap_threshold_1, MtxData<double, int> *local_mtx, MtxData<double, int> *dp_local_mtx,
+                                 MtxData<float, int> *sp_local_mtx, std::vector<double> *largest_row_elems,
+                                 std::vector<double> *largest_col_elems, bool is_equilibrated) {
+    if (!is_equilibrated) return partition_precisions(ap_threshold_1, local_mtx, dp_local_mtx, sp_local_mtx);
+    if (!largest_row_elems || !largest_col_elems || (ST)largest_row_elems->size() < local_mtx->n_rows ||
+        (ST)largest_col_elems->size() < local_mtx->n_cols)
+        throw std::runtime_error("partition_precisions: largest_row_elems / largest_col_elems need n_rows / n_cols elements");
+    uspmv_coo_t *coo = nullptr, *parts[3] = {nullptr, nullptr, nullptr};
+    uspmv_detail::check(uspmv_coo_create(local_mtx->n_rows, local_mtx->n_cols, local_mtx->nnz, local_mtx->I.data(),
+                                         local_mtx->J.data(), local_mtx->values.data(), &coo), "partition_precisions");
+    int rc = uspmv_partition_precisions_eq(coo, USPMV_AP_DP_SP, ap_threshold_1, 0.0, largest_row_elems->data(), largest_col_elems->data(), parts);
+    uspmv_coo_free(coo);
+    uspmv_detail::check(rc, "partition_precisions");
+    auto fill = [](uspmv_coo_t *h, auto *out) {
+        int64_t nr, nc, nz; const int32_t *I, *J; const double *V;
+        uspmv_coo_dims(h, &nr, &nc, &nz); uspmv_coo_arrays(h, &I, &J, &V);
+        out->n_rows = nr; out->n_cols = nc; out->nnz = nz; out->is_sorted = true; out->is_symmetric = false;
+        out->I.assign(I, I + nz); out->J.assign(J, J + nz); out->values.assign(V, V + nz);
+        uspmv_coo_free(h);
+    };
+    fill(parts[0], dp_local_mtx);
+    fill(parts[2], sp_local_mtx);
+}
+
 // ---- device kernels: all pointers are DEVICE pointers (as in the reference's CUDA build, where even
 // C and n_chunks live on the device, code/utilities.hpp:3803-3811; here the scalars are by value)
 template <typename VT, typename IT>

@@ -1,4 +1,5 @@
 // sanitizer pass over the host data layer (no HIP): every golden matrix through read / convert / plan / halo / split
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -78,6 +79,17 @@ int main(int argc, char **argv) {
         std::string f = std::string(td && *td ? td : "/tmp") + "/uspmv_sanitize_cache_" + std::to_string((int)getpid()) + ".bin";
         CK(uspmv_coo_save(m, f.c_str()));
         uspmv_coo_t *m2; CK(uspmv_coo_load(f.c_str(), &m2)); uspmv_coo_free(m2); unlink(f.c_str());
+        {   // equilibrated adaptive precision: the scales (a matrix with a zero divisor is a legal refusal), then every kind's split
+            const int32_t *I, *J; const double *V; CK(uspmv_coo_arrays(m, &I, &J, &V));
+            uspmv_coo_t *e = nullptr; CK(uspmv_coo_create(n, nc, nnz, I, J, V, &e));
+            std::vector<double> r((size_t)n), c((size_t)nc);
+            if (uspmv_coo_equilibrate_scales(e, r.data(), c.data()) == USPMV_OK)
+                for (int kind : {USPMV_AP_DP_SP, USPMV_AP_DP_HP, USPMV_AP_SP_HP, USPMV_AP_DP_SP_HP}) {
+                    uspmv_coo_t *parts[3]; CK(uspmv_partition_precisions_eq(e, kind, 1.0, 1e-3, r.data(), c.data(), parts));
+                    for (uspmv_coo_t *p : parts) uspmv_coo_free(p);
+                }
+            uspmv_coo_free(e);
+        }
         if (n <= nc) CK(uspmv_coo_equilibrate(m));
         uspmv_coo_free(m);
         printf("ok %s\n", argv[a]);
@@ -85,6 +97,28 @@ int main(int argc, char **argv) {
     uspmv_coo_t *g = nullptr; CK(uspmv_gen_stencil27(9, 8, 7, 3, 0x5EED, 4.0, 10, 900, &g)); uspmv_coo_free(g);
     CK(uspmv_gen_kkt(5, 0x5EED, 3, 300, &g)); uspmv_coo_free(g);
     CK(uspmv_gen_banded_random(500, 7, 40, 0x5EED, 3.0, 17, 400, &g)); uspmv_coo_free(g);
+    {   // uspmv_coo_equilibrate_scales on rectangular matrices with empty rows and columns (both shapes), and its refusals
+        const int32_t I[6] = {0, 0, 2, 2, 3, 6}, J[6] = {1, 3, 0, 3, 1, 3};
+        for (int wide = 0; wide < 2; ++wide) {
+            const int64_t nr = wide ? 7 : 9, ncol = wide ? 9 : 5;
+            // (good: an explicit zero whose row and column have other entries; zero_row: row 2; zero_col: column 0; inf)
+            const double good[6] = {2.0, 0.0, 1e-3, 4.0, 1.0, -7.0}, zero_row[6] = {2.0, -0.5, 0.0, 0.0, 1.0, -7.0},
+                         zero_col[6] = {2.0, -0.5, 0.0, 4.0, 1.0, -7.0}, inf[6] = {2.0, -0.5, 1e-3, HUGE_VAL, 1.0, -7.0};
+            int expect = USPMV_OK;
+            for (const double *V : {good, zero_row, zero_col, inf}) {
+                uspmv_coo_t *e = nullptr; CK(uspmv_coo_create(nr, ncol, 6, I, J, V, &e));
+                std::vector<double> r((size_t)nr), c((size_t)ncol);
+                if (uspmv_coo_equilibrate_scales(e, r.data(), c.data()) != expect) { fprintf(stderr, "FAIL equilibrate_scales refusal\n"); return 1; }
+                if (expect == USPMV_OK)
+                    for (int kind : {USPMV_AP_DP_SP, USPMV_AP_DP_SP_HP}) {
+                        uspmv_coo_t *parts[3]; CK(uspmv_partition_precisions_eq(e, kind, 0.5, 0.01, r.data(), c.data(), parts));
+                        for (uspmv_coo_t *p : parts) uspmv_coo_free(p);
+                    }
+                uspmv_coo_free(e);
+                expect = USPMV_ERR_INVALID;
+            }
+        }
+    }
     {   // host communicator (one rank) and the exchange plan over its transport
         uspmv_hostcomm_t *hc = nullptr;
         char job[64]; snprintf(job, sizeof job, "san%d", (int)getpid());

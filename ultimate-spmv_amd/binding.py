@@ -57,6 +57,7 @@ _SIGS = {
     "uspmv_coo_write_mtx": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "uspmv_coo_load": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
     "uspmv_coo_equilibrate": (C.c_int, [_vp]),
+    "uspmv_coo_equilibrate_scales": (C.c_int, [_vp, _vp, _vp]),
     "uspmv_coo_create": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, C.POINTER(_vp)]),
     "uspmv_coo_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_coo_arrays": (C.c_int, [_vp, C.POINTER(_i32p), C.POINTER(_i32p), C.POINTER(_f64p)]),
@@ -76,6 +77,12 @@ _SIGS = {
     "uspmv_apply_permutation": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int]),
     "uspmv_partition_precisions": (C.c_int, [_vp, C.c_double, C.POINTER(_vp), C.POINTER(_vp)]),
     "uspmv_partition_precisions_hp": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "uspmv_partition_precisions_eq": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, _vp, _vp, C.POINTER(_vp)]),
+    "uspmv_equilibrate_device": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "uspmv_equilibrate_device_count_atomics": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "uspmv_partition_precisions_device_eq": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "uspmv_convert_to_scs_device_ap_from_arrays_eq": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int, C.c_double, C.c_double, _vp, _vp, C.c_int,
+                                                      _vp, C.POINTER(_vp), _vp, _vp, C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "uspmv_partition_precisions_device": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, C.c_double, C.c_double, _vp, C.POINTER(_vp)]),
     "uspmv_dcoo_arrays": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64)]),
     "uspmv_dcoo_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
@@ -317,6 +324,13 @@ class Coo:
         """equilibrate_matrix (-equilibrate 1, code/utilities.hpp:2667-2685), in place."""
         _ck(lib().uspmv_coo_equilibrate(self.h))
 
+    def equilibrate_scales(self):
+        """The same, in place, returning the two divisor vectors (uspmv_coo_equilibrate_scales): (row_max[n_rows], col_max[n_cols]), what
+        partition_precisions_eq takes.  A non-finite value or a zero divisor is refused (UspmvError, status 1) with the matrix unchanged."""
+        r, c = np.zeros(self.n_rows, np.float64), np.zeros(self.n_cols, np.float64)
+        _ck(lib().uspmv_coo_equilibrate_scales(self.h, _np_ptr(r), _np_ptr(c)))
+        return r, c
+
     def save(self, path):
         """Binary cache of this matrix (uspmv_coo_save)."""
         _ck(lib().uspmv_coo_save(self.h, os.fsencode(path)))
@@ -497,6 +511,17 @@ def partition_precisions_hp(coo, kind, threshold_1, threshold_2=0.0):
     hi, mid, hp = _vp(), _vp(), _vp()
     _ck(lib().uspmv_partition_precisions_hp(coo.h, k, threshold_1, threshold_2, C.byref(hi), C.byref(mid), C.byref(hp)))
     return Coo(hi), (Coo(mid) if mid.value else None), Coo(hp)
+
+
+def partition_precisions_eq(coo, kind, threshold_1, threshold_2, row_max, col_max):
+    """The equilibrated branch of partition_precisions for all four kinds (uspmv_partition_precisions_eq; kind: AP_* or "dp_sp" | "dp_hp" |
+    "sp_hp" | "dp_sp_hp"): coo as Coo.equilibrate_scales() scaled it, row_max / col_max its vectors.  [hi, mid, lo] Coo parts, mid None for
+    the two-part kinds; values stored as doubles holding the part's rounded value."""
+    r, c = np.ascontiguousarray(row_max, np.float64), np.ascontiguousarray(col_max, np.float64)
+    assert r.shape == (coo.n_rows,) and c.shape == (coo.n_cols,)
+    parts = (_vp * 3)()
+    _ck(lib().uspmv_partition_precisions_eq(coo.h, _AP_KINDS.get(kind, kind), threshold_1, threshold_2, _np_ptr(r), _np_ptr(c), parts))
+    return [Coo(_vp(h)) if h else None for h in parts]
 
 
 # ---------------------------------------------------------------------------------------- halo set-up
@@ -1324,7 +1349,39 @@ def _handle_meta(hA, n_rows, nnz):
     return s
 
 
-def partition_precisions_device(d_I, d_J, d_V, n_rows, n_cols, kind, threshold_1, threshold_2=0.0, stream=None):
+def equilibrate_device(d_I, d_J, d_V, n_rows, n_cols, out=None, stream=None):
+    """Coo.equilibrate_scales() of DEVICE-resident COO arrays (uspmv_equilibrate_device; torch int32 / int32 / float64 tensors, entries
+    sorted by row): (V_scaled, row_max, col_max) device tensors, bit for bit the host's.  out: where the scaled values go (may be d_V
+    itself; default a new tensor).  A refusal (UspmvError) leaves `out` as it was."""
+    import torch
+    assert d_I.dtype == torch.int32 and d_J.dtype == torch.int32 and d_V.dtype == torch.float64 and d_I.is_cuda
+    if out is None:
+        out = torch.empty_like(d_V)
+    assert out.dtype == torch.float64 and out.numel() == d_V.numel() and out.is_cuda
+    r = torch.empty(n_rows, dtype=torch.float64, device=d_I.device)
+    c = torch.empty(n_cols, dtype=torch.float64, device=d_I.device)
+    _ck(lib().uspmv_equilibrate_device(_dp(d_I), _dp(d_J), _dp(d_V), _dp(out), n_rows, n_cols, int(d_I.numel()), _dp(r), _dp(c), _stream_ptr(stream)))
+    return out, r, c
+
+
+def equilibrate_device_count_atomics(d_I, d_J, d_V, n_rows, n_cols, row_max, stream=None):
+    """diagnosis: the atomics the column pass of equilibrate_device issues after its skip (uspmv_equilibrate_device_count_atomics), on the
+    UNSCALED values and their row_max"""
+    import torch
+    c = torch.empty(n_cols, dtype=torch.float64, device=d_I.device)
+    n = _i64()
+    _ck(lib().uspmv_equilibrate_device_count_atomics(_dp(d_I), _dp(d_J), _dp(d_V), n_rows, n_cols, int(d_I.numel()), _dp(row_max), _dp(c),
+                                                     _stream_ptr(stream), C.byref(n)))
+    return n.value
+
+
+def partition_precisions_device_eq(d_I, d_J, d_V, n_rows, n_cols, kind, threshold_1, threshold_2, row_max, col_max, stream=None):
+    """partition_precisions_eq of DEVICE-resident COO arrays (uspmv_partition_precisions_device_eq): as partition_precisions_device, with
+    the scaled values in d_V and the float64 device vectors of equilibrate_device."""
+    return partition_precisions_device(d_I, d_J, d_V, n_rows, n_cols, kind, threshold_1, threshold_2, stream, _scales=(row_max, col_max))
+
+
+def partition_precisions_device(d_I, d_J, d_V, n_rows, n_cols, kind, threshold_1, threshold_2=0.0, stream=None, _scales=None):
     """partition_precisions[_hp] of DEVICE-resident COO arrays (torch int32 / int32 / float64 tensors, entries sorted by row; kind: AP_* or
     "dp_sp" | "dp_hp" | "sp_hp" | "dp_sp_hp"): [hi, mid, lo], each an (I, J, V) triple of device tensors -- copies owned by torch, V float64
     holding the part's rounded value -- and mid None for the two-part kinds."""
@@ -1332,8 +1389,14 @@ def partition_precisions_device(d_I, d_J, d_V, n_rows, n_cols, kind, threshold_1
     assert d_I.dtype == torch.int32 and d_J.dtype == torch.int32 and d_V.dtype == torch.float64 and d_I.is_cuda
     parts = (_vp * 3)()
     st = _stream_ptr(stream)
-    _ck(lib().uspmv_partition_precisions_device(_dp(d_I), _dp(d_J), _dp(d_V), n_rows, n_cols, int(d_I.numel()), _AP_KINDS.get(kind, kind),
-                                                threshold_1, threshold_2, st, parts))
+    if _scales is None:
+        _ck(lib().uspmv_partition_precisions_device(_dp(d_I), _dp(d_J), _dp(d_V), n_rows, n_cols, int(d_I.numel()), _AP_KINDS.get(kind, kind),
+                                                    threshold_1, threshold_2, st, parts))
+    else:
+        r, c = _scales
+        assert r.dtype == torch.float64 and c.dtype == torch.float64 and r.is_cuda and c.is_cuda and r.numel() == n_rows and c.numel() == n_cols
+        _ck(lib().uspmv_partition_precisions_device_eq(_dp(d_I), _dp(d_J), _dp(d_V), n_rows, n_cols, int(d_I.numel()), _AP_KINDS.get(kind, kind),
+                                                       threshold_1, threshold_2, _dp(r), _dp(c), st, parts))
     out = []
     try:
         for h in parts:
@@ -1374,8 +1437,17 @@ def gen_stencil27_device(nx, ny, nz, dof=1, seed=0x5EED, magnitude_decades=0.0, 
     return I, J, V
 
 
+def convert_ap_device_from_arrays_eq(d_I, d_J, d_V, n_rows, n_cols, C_, sigma, kind, threshold_1, threshold_2, row_max, col_max, sort=SORT_HOST,
+                                     want_layout=True, stream=None):
+    """convert_ap_device_from_arrays of an equilibrated matrix (uspmv_convert_to_scs_device_ap_from_arrays_eq): d_V the scaled values,
+    row_max / col_max the float64 device vectors of equilibrate_device; the handles of the host route Coo.equilibrate_scales(),
+    partition_precisions_eq, convert_to_scs with the first part's permutation, permute_scs_cols, upload."""
+    return convert_ap_device_from_arrays(d_I, d_J, d_V, n_rows, n_cols, C_, sigma, kind, threshold_1, threshold_2, sort, want_layout, stream,
+                                         _scales=(row_max, col_max))
+
+
 def convert_ap_device_from_arrays(d_I, d_J, d_V, n_rows, n_cols, C_, sigma, kind, threshold_1, threshold_2=0.0, sort=SORT_HOST, want_layout=True,
-                                  stream=None):
+                                  stream=None, _scales=None):
     """The adaptive-precision set-up in one call from DEVICE-resident COO arrays (uspmv_convert_to_scs_device_ap_from_arrays): returns
     (layout-only Scs of the first part or None, [A_hi, A_mid | None, A_lo], old_to_new, new_to_old, part_nnz) -- the handles of the host
     route (partition, convert_to_scs with the first part's permutation, permute_scs_cols with it, upload), ready for optimize_device_ap[_hp]
@@ -1387,9 +1459,17 @@ def convert_ap_device_from_arrays(d_I, d_J, d_V, n_rows, n_cols, C_, sigma, kind
     n2o = torch.empty(max(n_rows, 0), dtype=torch.int32, device=d_I.device)
     hs, hh, hm, hl = _vp(), _vp(), _vp(), _vp()
     cnt = (_i64 * 3)()
-    _ck(lib().uspmv_convert_to_scs_device_ap_from_arrays(_dp(d_I), _dp(d_J), _dp(d_V), n_rows, n_cols, nnz, C_, sigma, _AP_KINDS.get(kind, kind),
-                                                         threshold_1, threshold_2, int(sort), _stream_ptr(stream), C.byref(hs) if want_layout else None,
-                                                         _dp(o2n), _dp(n2o), cnt, C.byref(hh), C.byref(hm), C.byref(hl)))
+    if _scales is None:
+        _ck(lib().uspmv_convert_to_scs_device_ap_from_arrays(_dp(d_I), _dp(d_J), _dp(d_V), n_rows, n_cols, nnz, C_, sigma, _AP_KINDS.get(kind, kind),
+                                                             threshold_1, threshold_2, int(sort), _stream_ptr(stream), C.byref(hs) if want_layout else None,
+                                                             _dp(o2n), _dp(n2o), cnt, C.byref(hh), C.byref(hm), C.byref(hl)))
+    else:
+        r, c = _scales
+        assert r.dtype == torch.float64 and c.dtype == torch.float64 and r.is_cuda and c.is_cuda and r.numel() == n_rows and c.numel() == n_cols
+        _ck(lib().uspmv_convert_to_scs_device_ap_from_arrays_eq(_dp(d_I), _dp(d_J), _dp(d_V), n_rows, n_cols, nnz, C_, sigma, _AP_KINDS.get(kind, kind),
+                                                                threshold_1, threshold_2, _dp(r), _dp(c), int(sort), _stream_ptr(stream),
+                                                                C.byref(hs) if want_layout else None, _dp(o2n), _dp(n2o), cnt, C.byref(hh),
+                                                                C.byref(hm), C.byref(hl)))
     lay = Scs(hs) if want_layout else None
     hand = [DeviceMatrix(_handle_meta(h, n_rows, int(c)), d_I.device, _handle=h) if h else None for h, c in zip((hh, hm, hl), cnt)]
     return lay, hand, o2n, n2o, [int(c) for c in cnt]

@@ -10,6 +10,10 @@
 // rounds of 512, a lane holding two neighbouring entries (one 16-byte load of V, 8-byte loads of I and J where the arrays are aligned).
 // Bytes per entry: (a) reads I, J and V (16: the index checks belong to the pass that runs before anything is written), (c) reads them
 // again and writes the part's I, J and V (32): 48 in all.
+// EQ = true is the equilibrated branch (uspmv_partition_precisions_device_eq): entry (I, J, v) is held against
+// t / (col_max[J] * row_max[I]), and a two-part kind ends in a plain else.  Both passes then gather row_max[I] and col_max[J] as well: 16
+// more bytes per entry and pass where the gathers miss, 80 in all at the most; the vectors of a banded matrix stay in L2.  EQ = false
+// compiles to the unscaled kernels as they were.
 #include "uspmv_device.hpp"
 
 #include "../host/uspmv_f16_round.hpp"
@@ -21,12 +25,13 @@ namespace {
 constexpr int WG = 256, PER_WG = 1024, ROUND = 512;      // entries: 2 rounds x 256 lanes x 2
 
 // part of entry v (0 hi, 1 mid, 2 lo; -1: NaN in a two-part kind) and the value the part stores, as a double
+template <bool EQ>
 __device__ __forceinline__ int ap_classify(const int kind, const double v, const double t1, const double t2, double *stored) {
     const double av = __builtin_fabs(v);
     const bool hp_lo = kind != USPMV_AP_DP_SP;
     if (av >= t1) { *stored = kind == USPMV_AP_SP_HP ? (double)(float)v : v; return 0; }
     if (kind == USPMV_AP_DP_SP_HP && av <= t1 && av >= t2) { *stored = (double)(float)v; return 1; }
-    if (kind == USPMV_AP_DP_SP_HP || av < t1) {
+    if (EQ || kind == USPMV_AP_DP_SP_HP || av < t1) {      // (EQ: the plain else of the equilibrated branch, NaN included)
         if (hp_lo) *stored = __longlong_as_double((long long)uspmv_f16_to_f64_bits(uspmv_f64_bits_to_f16((uint64_t)__double_as_longlong(v))));
         else *stored = (double)(float)v;
         return 2;
@@ -34,26 +39,20 @@ __device__ __forceinline__ int ap_classify(const int kind, const double v, const
     return -1;
 }
 
-// the two entries of this lane in round r: k, k + 1 (n: how many of them exist)
-template <bool VEC>
-__device__ __forceinline__ int load_pair(const int *__restrict__ I, const int *__restrict__ J, const double *__restrict__ V, const long k, const long nnz,
-                                         int i[2], int j[2], double v[2]) {
-    const int n = k + 1 < nnz ? 2 : (k < nnz ? 1 : 0);
-    if (VEC && n == 2) {
-        const int2 a = *(const int2 *)(I + k), b = *(const int2 *)(J + k);
-        const double2 c = *(const double2 *)(V + k);
-        i[0] = a.x; i[1] = a.y; j[0] = b.x; j[1] = b.y; v[0] = c.x; v[1] = c.y;
-    } else {
-        for (int e = 0; e < n; ++e) { i[e] = I[k + e]; j[e] = J[k + e]; v[e] = V[k + e]; }
-    }
-    return n;
+// the thresholds of entry (i, j) in the equilibrated branch: one multiplication, one division each
+__device__ __forceinline__ void eq_thresholds(const double *__restrict__ row_max, const double *__restrict__ col_max, const int i, const int j,
+                                              const double t1, const double t2, double *T1, double *T2) {
+    const double d = col_max[j] * row_max[i];
+    *T1 = t1 / d;
+    *T2 = t2 / d;
 }
 
-template <bool VEC>
+template <bool VEC, bool EQ>
 __global__ void __launch_bounds__(WG) ap_count_kernel(const int *__restrict__ I, const int *__restrict__ J, const double *__restrict__ V, const long nnz,
                                                       const int n_rows, const int n_cols, const int kind, const double t1, const double t2,
                                                       const long n_wg, long *__restrict__ counts, int *__restrict__ flag,
-                                                      unsigned long long *__restrict__ first_nan) {
+                                                      unsigned long long *__restrict__ first_nan, const double *__restrict__ row_max,
+                                                      const double *__restrict__ col_max) {
     __shared__ int wcnt[3][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int mine[3] = {0, 0, 0};
@@ -69,8 +68,9 @@ __global__ void __launch_bounds__(WG) ap_count_kernel(const int *__restrict__ I,
             else if (i[e] < prev) err |= 1;
             if (j[e] < 0 || j[e] >= n_cols) err |= 4;
             prev = i[e];
-            double s;
-            const int c = ap_classify(kind, v[e], t1, t2, &s);
+            double s, T1 = t1, T2 = t2;
+            if (EQ && i[e] >= 0 && i[e] < n_rows && j[e] >= 0 && j[e] < n_cols) eq_thresholds(row_max, col_max, i[e], j[e], t1, t2, &T1, &T2);
+            const int c = ap_classify<EQ>(kind, v[e], T1, T2, &s);
             if (c < 0) atomicMin(first_nan, (unsigned long long)(k + e));
             else ++mine[c];
         }
@@ -87,10 +87,11 @@ __global__ void __launch_bounds__(WG) ap_count_kernel(const int *__restrict__ I,
     if (threadIdx.x < 3) counts[(long)threadIdx.x * n_wg + blockIdx.x] = (long)wcnt[threadIdx.x][0] + wcnt[threadIdx.x][1] + wcnt[threadIdx.x][2] + wcnt[threadIdx.x][3];
 }
 
-template <bool VEC>
+template <bool VEC, bool EQ>
 __global__ void __launch_bounds__(WG) ap_scatter_kernel(const int *__restrict__ I, const int *__restrict__ J, const double *__restrict__ V, const long nnz,
                                                         const int kind, const double t1, const double t2, const long n_wg,
-                                                        const int *__restrict__ base, const ApPartOut out) {
+                                                        const int *__restrict__ base, const ApPartOut out, const double *__restrict__ row_max,
+                                                        const double *__restrict__ col_max) {
     __shared__ int ucnt[3][8];                            // entries of part p in unit (round, wave), units in entry order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long lower = (1ull << lane) - 1;
@@ -100,7 +101,11 @@ __global__ void __launch_bounds__(WG) ap_scatter_kernel(const int *__restrict__ 
         const long k = (long)blockIdx.x * PER_WG + r * ROUND + 2 * threadIdx.x;
         double v[2];
         const int n = load_pair<VEC>(I, J, V, k, nnz, i[r], j[r], v);
-        for (int e = 0; e < 2; ++e) cls[r][e] = e < n ? ap_classify(kind, v[e], t1, t2, &s[r][e]) : -1;
+        for (int e = 0; e < 2; ++e) {
+            double T1 = t1, T2 = t2;
+            if (EQ && e < n) eq_thresholds(row_max, col_max, i[r][e], j[r][e], t1, t2, &T1, &T2);   // (pass (a) has checked the indices)
+            cls[r][e] = e < n ? ap_classify<EQ>(kind, v[e], T1, T2, &s[r][e]) : -1;
+        }
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
             const unsigned long long b0 = __ballot(cls[r][0] == p), b1 = __ballot(cls[r][1] == p);
@@ -138,25 +143,23 @@ static bool pair_aligned(const void *I, const void *J, const void *V) {
 long ap_partition_workgroups(long nnz) { return (nnz + PER_WG - 1) / PER_WG; }
 
 int launch_ap_partition_count(const int *I, const int *J, const double *V, long nnz, int n_rows, int n_cols, int kind, double t1, double t2,
-                              long *d_counts, int *d_flag, unsigned long long *d_first_nan, hipStream_t st) {
+                              long *d_counts, int *d_flag, unsigned long long *d_first_nan, hipStream_t st, const double *row_max, const double *col_max) {
     const long n_wg = ap_partition_workgroups(nnz);
     if (n_wg == 0) return USPMV_OK;
-    if (pair_aligned(I, J, V))
-        hipLaunchKernelGGL(ap_count_kernel<true>, dim3((unsigned)n_wg), dim3(WG), 0, st, I, J, V, nnz, n_rows, n_cols, kind, t1, t2, n_wg, d_counts, d_flag, d_first_nan);
-    else
-        hipLaunchKernelGGL(ap_count_kernel<false>, dim3((unsigned)n_wg), dim3(WG), 0, st, I, J, V, nnz, n_rows, n_cols, kind, t1, t2, n_wg, d_counts, d_flag, d_first_nan);
+    const bool vec = pair_aligned(I, J, V), eq = row_max != nullptr;
+    auto *kern = vec ? (eq ? ap_count_kernel<true, true> : ap_count_kernel<true, false>) : (eq ? ap_count_kernel<false, true> : ap_count_kernel<false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(WG), 0, st, I, J, V, nnz, n_rows, n_cols, kind, t1, t2, n_wg, d_counts, d_flag, d_first_nan, row_max, col_max);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }
 
 int launch_ap_partition_scatter(const int *I, const int *J, const double *V, long nnz, int kind, double t1, double t2, const int *d_base,
-                                const ApPartOut &out, hipStream_t st) {
+                                const ApPartOut &out, hipStream_t st, const double *row_max, const double *col_max) {
     const long n_wg = ap_partition_workgroups(nnz);
     if (n_wg == 0) return USPMV_OK;
-    if (pair_aligned(I, J, V))
-        hipLaunchKernelGGL(ap_scatter_kernel<true>, dim3((unsigned)n_wg), dim3(WG), 0, st, I, J, V, nnz, kind, t1, t2, n_wg, d_base, out);
-    else
-        hipLaunchKernelGGL(ap_scatter_kernel<false>, dim3((unsigned)n_wg), dim3(WG), 0, st, I, J, V, nnz, kind, t1, t2, n_wg, d_base, out);
+    const bool vec = pair_aligned(I, J, V), eq = row_max != nullptr;
+    auto *kern = vec ? (eq ? ap_scatter_kernel<true, true> : ap_scatter_kernel<true, false>) : (eq ? ap_scatter_kernel<false, true> : ap_scatter_kernel<false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(WG), 0, st, I, J, V, nnz, kind, t1, t2, n_wg, d_base, out, row_max, col_max);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }

@@ -315,9 +315,11 @@ namespace {
 bool ap_kind_known(int kind) { return kind == USPMV_AP_DP_HP || kind == USPMV_AP_SP_HP || kind == USPMV_AP_DP_SP_HP || kind == USPMV_AP_DP_SP; }
 
 // the three passes (csrc/ap_partition_kernels.hip); the caller has checked the arguments and the device.  Nothing is written to a part
-// before the index checks and the NaN check of pass (a) have come back clean.
+// before the index checks and the NaN check of pass (a) have come back clean.  d_row_max / d_col_max: the equilibrated branch (both NULL:
+// the unscaled one).
 int partition_device(const char *who, const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols, int64_t nnz,
-                     int kind, double t1, double t2, hipStream_t st, std::unique_ptr<uspmv_dcoo> parts[3]) {
+                     int kind, double t1, double t2, const double *d_row_max, const double *d_col_max, hipStream_t st,
+                     std::unique_ptr<uspmv_dcoo> parts[3]) {
     const bool three = kind == USPMV_AP_DP_SP_HP;
     const long n_wg = ap_partition_workgroups((long)nnz), n_cnt = 3 * n_wg;
     int32_t h_base[4] = {0, 0, 0, 0};                     // where the parts start in the scan, and the total
@@ -334,7 +336,7 @@ int partition_device(const char *who, const int32_t *d_I, const int32_t *d_J, co
         HIP_TRY(first_nan.alloc(8));
         HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
         HIP_TRY(hipMemsetAsync(first_nan, 0xFF, 8, st));
-        if (int rc = launch_ap_partition_count(d_I, d_J, d_V, (long)nnz, (int)n_rows, (int)n_cols, kind, t1, t2, counts, flag, first_nan, st)) return rc;
+        if (int rc = launch_ap_partition_count(d_I, d_J, d_V, (long)nnz, (int)n_rows, (int)n_cols, kind, t1, t2, counts, flag, first_nan, st, d_row_max, d_col_max)) return rc;
         if (int rc = launch_exclusive_scan(counts, n_cnt, part, sums, total, base, st)) return rc;
         int h_flag = 0;
         unsigned long long h_nan = 0;
@@ -357,7 +359,7 @@ int partition_device(const char *who, const int32_t *d_I, const int32_t *d_J, co
             HIP_TRY(parts[p]->V.alloc(8 * n));
             o.I[p] = parts[p]->I; o.J[p] = parts[p]->J; o.V[p] = parts[p]->V; o.n[p] = (long)n;
         }
-        if (int rc = launch_ap_partition_scatter(d_I, d_J, d_V, (long)nnz, kind, t1, t2, base, o, st)) return rc;
+        if (int rc = launch_ap_partition_scatter(d_I, d_J, d_V, (long)nnz, kind, t1, t2, base, o, st, d_row_max, d_col_max)) return rc;
         HIP_TRY(hipStreamSynchronize(st));               // (the scratch of this call is released on return)
     } else {
         for (int p = 0; p < 3; ++p)
@@ -375,17 +377,31 @@ int ap_common_args(const char *who, const int32_t *d_I, const int32_t *d_J, cons
 
 }  // namespace
 
-extern "C" int uspmv_partition_precisions_device(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols, int64_t nnz,
-                                                 int kind, double threshold_1, double threshold_2, void *stream, uspmv_dcoo_t *parts[3]) {
-    const char *who = "uspmv_partition_precisions_device";
+static int partition_precisions_device(const char *who, const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                                       int64_t nnz, int kind, double threshold_1, double threshold_2, const double *d_row_max,
+                                       const double *d_col_max, void *stream, uspmv_dcoo_t *parts[3]) {
     if (!parts) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
     if (int rc = ap_common_args(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind)) return rc;
     if (int rc = require_device()) return rc;
     if (n_rows > INT32_MAX || n_cols > INT32_MAX || nnz > INT32_MAX) return uspmv::fail(USPMV_ERR_OVERFLOW, "%s: rows / columns / entries exceed int32", who);
     std::unique_ptr<uspmv_dcoo> p[3];
-    if (int rc = partition_device(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind, threshold_1, threshold_2, (hipStream_t)stream, p)) return rc;
+    if (int rc = partition_device(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind, threshold_1, threshold_2, d_row_max, d_col_max, (hipStream_t)stream, p)) return rc;
     for (int k = 0; k < 3; ++k) parts[k] = p[k].release();
     return USPMV_OK;
+}
+
+extern "C" int uspmv_partition_precisions_device(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                                                 int kind, double threshold_1, double threshold_2, void *stream, uspmv_dcoo_t *parts[3]) {
+    return partition_precisions_device("uspmv_partition_precisions_device", d_I, d_J, d_V, n_rows, n_cols, nnz, kind, threshold_1, threshold_2, nullptr,
+                                       nullptr, stream, parts);
+}
+
+extern "C" int uspmv_partition_precisions_device_eq(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                                                    int kind, double threshold_1, double threshold_2, const double *d_row_max, const double *d_col_max,
+                                                    void *stream, uspmv_dcoo_t *parts[3]) {
+    const char *who = "uspmv_partition_precisions_device_eq";
+    if (!d_row_max || !d_col_max) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    return partition_precisions_device(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind, threshold_1, threshold_2, d_row_max, d_col_max, stream, parts);
 }
 
 extern "C" int uspmv_dcoo_arrays(const uspmv_dcoo_t *p, const int32_t **d_I, const int32_t **d_J, const double **d_V, int64_t *nnz) {
@@ -410,12 +426,12 @@ extern "C" int uspmv_dcoo_copy(const uspmv_dcoo_t *p, int32_t *d_I, int32_t *d_J
 
 extern "C" void uspmv_dcoo_free(uspmv_dcoo_t *p) { delete p; }
 
-extern "C" int uspmv_convert_to_scs_device_ap_from_arrays(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
-                                                          int64_t nnz, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2,
-                                                          int sort_mode, void *stream, uspmv_scs_t **layout, int32_t *d_old_to_new,
-                                                          int32_t *d_new_to_old, int64_t part_nnz[3], uspmv_dmat_t **hi, uspmv_dmat_t **mid,
-                                                          uspmv_dmat_t **lo) {
-    const char *who = "uspmv_convert_to_scs_device_ap_from_arrays";
+// uspmv_convert_to_scs_device_ap_from_arrays[_eq]: one body, the unscaled function with both vectors NULL
+static int convert_ap_from_arrays(const char *who, const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                                  int64_t nnz, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2,
+                                  const double *d_row_max, const double *d_col_max, int sort_mode, void *stream, uspmv_scs_t **layout,
+                                  int32_t *d_old_to_new, int32_t *d_new_to_old, int64_t part_nnz[3], uspmv_dmat_t **hi, uspmv_dmat_t **mid,
+                                  uspmv_dmat_t **lo) {
     if (int rc = ap_common_args(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind)) return rc;
     const bool three = kind == USPMV_AP_DP_SP_HP;
     if (!hi || !lo || (three && !mid)) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL output for a part the kind has", who);
@@ -428,7 +444,7 @@ extern "C" int uspmv_convert_to_scs_device_ap_from_arrays(const int32_t *d_I, co
         return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: the device-side stable ordering takes sorting scopes of up to 8192 rows (sigma = %lld): use USPMV_SORT_HOST", who, (long long)sigma);
     hipStream_t st = (hipStream_t)stream;
     std::unique_ptr<uspmv_dcoo> p[3];
-    if (int rc = partition_device(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind, threshold_1, threshold_2, st, p)) return rc;
+    if (int rc = partition_device(who, d_I, d_J, d_V, n_rows, n_cols, nnz, kind, threshold_1, threshold_2, d_row_max, d_col_max, st, p)) return rc;
 
     // the first part orders the rows; the others take its permutation for their rows AND for their columns (what uspmv_main.cpp and the
     // host tests do with uspmv_convert_to_scs(fixed_permutation) + uspmv_permute_scs_cols(first part's old_to_new))
@@ -459,4 +475,24 @@ extern "C" int uspmv_convert_to_scs_device_ap_from_arrays(const int32_t *d_I, co
     if (mid) *mid = A[1].release();
     *lo = A[2].release();
     return USPMV_OK;
+}
+
+extern "C" int uspmv_convert_to_scs_device_ap_from_arrays(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                                                          int64_t nnz, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2,
+                                                          int sort_mode, void *stream, uspmv_scs_t **layout, int32_t *d_old_to_new,
+                                                          int32_t *d_new_to_old, int64_t part_nnz[3], uspmv_dmat_t **hi, uspmv_dmat_t **mid,
+                                                          uspmv_dmat_t **lo) {
+    return convert_ap_from_arrays("uspmv_convert_to_scs_device_ap_from_arrays", d_I, d_J, d_V, n_rows, n_cols, nnz, C, sigma, kind, threshold_1,
+                                  threshold_2, nullptr, nullptr, sort_mode, stream, layout, d_old_to_new, d_new_to_old, part_nnz, hi, mid, lo);
+}
+
+extern "C" int uspmv_convert_to_scs_device_ap_from_arrays_eq(const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t n_cols,
+                                                             int64_t nnz, int64_t C, int64_t sigma, int kind, double threshold_1, double threshold_2,
+                                                             const double *d_row_max, const double *d_col_max, int sort_mode, void *stream,
+                                                             uspmv_scs_t **layout, int32_t *d_old_to_new, int32_t *d_new_to_old, int64_t part_nnz[3],
+                                                             uspmv_dmat_t **hi, uspmv_dmat_t **mid, uspmv_dmat_t **lo) {
+    const char *who = "uspmv_convert_to_scs_device_ap_from_arrays_eq";
+    if ((d_row_max == nullptr) != (d_col_max == nullptr)) return uspmv::fail(USPMV_ERR_INVALID, "%s: one of the two divisor vectors is NULL", who);
+    return convert_ap_from_arrays(who, d_I, d_J, d_V, n_rows, n_cols, nnz, C, sigma, kind, threshold_1, threshold_2, d_row_max, d_col_max, sort_mode,
+                                  stream, layout, d_old_to_new, d_new_to_old, part_nnz, hi, mid, lo);
 }

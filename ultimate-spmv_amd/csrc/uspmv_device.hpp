@@ -646,9 +646,18 @@ struct ApPartOut {
 // outside the matrix; *d_first_nan: the first element that fits no part (min over the workgroups); d_base: the scan of d_counts
 long ap_partition_workgroups(long nnz);
 int launch_ap_partition_count(const int *I, const int *J, const double *V, long nnz, int n_rows, int n_cols, int kind, double t1, double t2,
-                              long *d_counts, int *d_flag, unsigned long long *d_first_nan, hipStream_t st);
+                              long *d_counts, int *d_flag, unsigned long long *d_first_nan, hipStream_t st, const double *row_max = nullptr,
+                              const double *col_max = nullptr);
 int launch_ap_partition_scatter(const int *I, const int *J, const double *V, long nnz, int kind, double t1, double t2, const int *d_base,
-                                const ApPartOut &out, hipStream_t st);
+                                const ApPartOut &out, hipStream_t st, const double *row_max = nullptr, const double *col_max = nullptr);
+// (row_max / col_max: device vectors of the equilibrated branch, both NULL for the unscaled one)
+// equilibrate_matrix on the device (equilibrate_kernels.hip).  d_flag bits: 1 rows unsorted, 2 row index / 4 column index outside the matrix,
+// 8 a non-finite value, 16 an entry whose row divisor is 0, 32 a row-scaled value that is 0 (its column's divisor may be: launch_eq_zero_cols)
+int launch_eq_row_max(const int *I, const double *V, long nnz, int n_rows, double *row_max, int *d_flag, hipStream_t st);
+int launch_eq_col_max(const int *I, const int *J, const double *V, long nnz, int n_rows, int n_cols, const double *row_max, double *col_max,
+                      int *d_flag, unsigned long long *d_n_atomics, hipStream_t st);
+int launch_eq_zero_cols(const int *J, long nnz, const double *col_max, int *d_flag, hipStream_t st);
+int launch_eq_scale(const int *I, const int *J, const double *V, double *V_out, long nnz, const double *row_max, const double *col_max, hipStream_t st);
 
 }  // namespace uspmv_dev
 
@@ -660,6 +669,22 @@ int launch_ap_partition_scatter(const int *I, const int *J, const double *V, lon
                                __FILE__, __LINE__);                                                \
     } while (0)
 
+
+// device COO arrays read two neighbouring entries per lane, k and k + 1 (n: how many of them exist); VEC: the arrays are aligned for one
+// 8-byte load of I and J and one 16-byte load of V (ap_partition_kernels.hip, equilibrate_kernels.hip)
+template <bool VEC>
+__device__ __forceinline__ int load_pair(const int *__restrict__ I, const int *__restrict__ J, const double *__restrict__ V, const long k, const long nnz,
+                                         int i[2], int j[2], double v[2]) {
+    const int n = k + 1 < nnz ? 2 : (k < nnz ? 1 : 0);
+    if (VEC && n == 2) {
+        const int2 a = *(const int2 *)(I + k), b = *(const int2 *)(J + k);
+        const double2 c = *(const double2 *)(V + k);
+        i[0] = a.x; i[1] = a.y; j[0] = b.x; j[1] = b.y; v[0] = c.x; v[1] = c.y;
+    } else {
+        for (int e = 0; e < n; ++e) { i[e] = I[k + e]; j[e] = J[k + e]; v[e] = V[k + e]; }
+    }
+    return n;
+}
 
 // ------------------------------------------------------------------------------------------
 template <bool NT, typename T>

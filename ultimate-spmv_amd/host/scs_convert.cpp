@@ -271,6 +271,63 @@ int uspmv_coo_equilibrate(uspmv_coo_t *m) {
     return USPMV_OK;
 }
 
+int uspmv_coo_equilibrate_scales(uspmv_coo_t *m, double *row_max, double *col_max) {
+    // uspmv_coo_equilibrate keeping its two divisor vectors: extract_largest_row_elems, scale_matrix_rows, extract_largest_col_elems,
+    // scale_matrix_cols (code/utilities.hpp:2605-2665) in the order of code/main.cpp:1147-1153, the vectors sized n_rows and n_cols.
+    // Nothing is written to the values before every refusal has been decided.
+    const char *who = "uspmv_coo_equilibrate_scales";
+    if (!m || !row_max || !col_max) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    const int64_t nnz = m->nnz, n_rows = m->n_rows, n_cols = m->n_cols;
+    const int32_t *I = m->I.data(), *J = m->J.data();
+    double *V = m->values.data();
+    std::vector<double> r((size_t)std::max<int64_t>(n_rows, 1), 0.0), c((size_t)std::max<int64_t>(n_cols, 1), 0.0);
+    int64_t bad_value = -1, bad_div = -1;                   // the first element refused, by either rule
+    for (int pass = 0; pass < 2; ++pass) {
+        std::vector<double> &mx = pass == 0 ? r : c;
+        const int32_t *idx = pass == 0 ? I : J;
+#pragma omp parallel
+        {
+            std::vector<double> local(mx.size(), 0.0);
+            int64_t my_value = -1, my_div = -1;
+#pragma omp for schedule(static) nowait
+            for (int64_t k = 0; k < nnz; ++k) {
+                double a = std::fabs(V[k]);
+                if (pass == 0) {
+                    if (!std::isfinite(a) && my_value < 0) my_value = k;
+                } else {
+                    if (r[(size_t)I[k]] == 0.0) { if (my_div < 0) my_div = k; continue; }
+                    a = std::fabs(V[k] / r[(size_t)I[k]]);
+                }
+                if (a > local[(size_t)idx[k]]) local[(size_t)idx[k]] = a;
+            }
+#pragma omp critical
+            {
+                for (size_t q = 0; q < mx.size(); ++q) mx[q] = std::max(mx[q], local[q]);
+                if (my_value >= 0 && (bad_value < 0 || my_value < bad_value)) bad_value = my_value;
+                if (my_div >= 0 && (bad_div < 0 || my_div < bad_div)) bad_div = my_div;
+            }
+        }
+        if (bad_value >= 0) return uspmv::fail(USPMV_ERR_INVALID, "%s: element %lld is not finite", who, (long long)bad_value);
+        if (bad_div >= 0)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: element %lld lies in a row whose largest magnitude is 0 (0 / 0 has no portable bits)", who,
+                               (long long)bad_div);
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < nnz; ++k)
+        if (c[(size_t)J[k]] == 0.0) {
+#pragma omp critical
+            if (bad_div < 0 || k < bad_div) bad_div = k;
+        }
+    if (bad_div >= 0)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: element %lld lies in a column whose largest row-scaled magnitude is 0 (0 / 0 has no portable bits)",
+                           who, (long long)bad_div);
+#pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < nnz; ++k) V[k] = (V[k] / r[(size_t)I[k]]) / c[(size_t)J[k]];
+    std::copy(r.begin(), r.begin() + n_rows, row_max);
+    std::copy(c.begin(), c.begin() + std::max<int64_t>(n_cols, 0), col_max);
+    return USPMV_OK;
+}
+
 int uspmv_apply_permutation(void *out, const void *in, const int32_t *perm, int64_t n, int dtype) {
     if (!out || !in || !perm || n < 0) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_apply_permutation: bad argument");
     if (dtype == USPMV_F64) {
@@ -338,6 +395,37 @@ int uspmv_partition_precisions_hp(const uspmv_coo_t *m, int kind, double thresho
         if (p) p->nnz = (int64_t)p->values.size();
     *hi = a; *hp = h;
     if (mid) *mid = b;
+    return USPMV_OK;
+}
+
+int uspmv_partition_precisions_eq(const uspmv_coo_t *m, int kind, double threshold_1, double threshold_2, const double *row_max,
+                                  const double *col_max, uspmv_coo_t *parts[3]) {
+    // partition_precisions, the config->equilibrate branches (code/utilities.hpp:2883-2896 ap[dp_sp], :2934-2950 ap[dp_hp], :2989-3007
+    // ap[sp_hp], :3046-3078 ap[dp_sp_hp]; library twin code/interface.hpp:691-987): every entry is held against its own thresholds
+    // t / (largest_col_elems[J] * largest_row_elems[I]); a two-part kind ends in a plain else, so a NaN goes to the low part.
+    const char *who = "uspmv_partition_precisions_eq";
+    if (!m || !row_max || !col_max || !parts) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (kind != USPMV_AP_DP_HP && kind != USPMV_AP_SP_HP && kind != USPMV_AP_DP_SP_HP && kind != USPMV_AP_DP_SP)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: unknown kind %d", who, kind);
+    const bool three = kind == USPMV_AP_DP_SP_HP;
+    uspmv_coo *p[3] = {new uspmv_coo, three ? new uspmv_coo : nullptr, new uspmv_coo};
+    for (uspmv_coo *q : p)
+        if (q) { q->n_rows = m->n_rows; q->n_cols = m->n_cols; }
+    auto put = [&](uspmv_coo *q, int64_t k, double v) {
+        q->I.push_back(m->I[(size_t)k]); q->J.push_back(m->J[(size_t)k]); q->values.push_back(v);
+    };
+    for (int64_t k = 0; k < m->nnz; ++k) {
+        const double v = m->values[(size_t)k], av = std::fabs(v);
+        const double d = col_max[m->J[(size_t)k]] * row_max[m->I[(size_t)k]];
+        const double T1 = threshold_1 / d, T2 = threshold_2 / d;
+        if (av >= T1) put(p[0], k, kind == USPMV_AP_SP_HP ? (double)(float)v : v);
+        else if (three && av <= T1 && av >= T2) put(p[1], k, (double)(float)v);
+        else put(p[2], k, kind == USPMV_AP_DP_SP ? (double)(float)v : uspmv_f16_to_f64(uspmv_f64_to_f16(v)));
+    }
+    for (int q = 0; q < 3; ++q) {
+        if (p[q]) p[q]->nnz = (int64_t)p[q]->values.size();
+        parts[q] = p[q];
+    }
     return USPMV_OK;
 }
 

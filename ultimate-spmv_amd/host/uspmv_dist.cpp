@@ -18,7 +18,8 @@
 // analytic row counts); a .mtx file is read by rank 0 alone, which writes one binary block per rank (file names carry the
 // segment's nonce) -- the reference's root-reads-and-scatters (code/mpi_funcs.hpp:739-860) without MPI.
 // -convert device | device_stable: the rank's set-up runs on the device from the block in HBM (uspmv_dist_create_from_arrays_ex); a gen:
-// block is then generated there (uspmv_gen_stencil27_device) and self-checked there (uspmv_dist_check_arrays), any other block is the
+// block is then generated there (uspmv_gen_stencil27_device), scaled there under -equilibrate 1 (uspmv_equilibrate_device) and
+// self-checked there (uspmv_dist_check_arrays, on the scaled arrays), any other block is the
 // host block uploaded -- see "this rank's row block" below and DESIGN.md 6.12.
 //
 // Protocols: the reference's (100 warm-ups, doubling batches until -bench_time, code/main.cpp:408-474) by default;
@@ -137,9 +138,10 @@ int uspmv_run_distributed(const DistConfig &c) {
 
     // ---- this rank's row block (and nothing else)
     //      -convert device | device_stable: the set-up reads the block from HBM.  A gen: block with decades 0 is GENERATED there
-    //      (uspmv_gen_stencil27_device) and the host block never exists, unless something below reads the host block: -equilibrate 1 scales
-    //      it, -rand_x 1 | m takes the min / max of its values, -step_form auto_all self-checks a pad / fused winner against it.  Those runs,
-    //      gen: with decades > 0 (the host's pow) and every .mtx block build the host block as before and UPLOAD it.
+    //      (uspmv_gen_stencil27_device) and the host block never exists, unless something below reads the host block: -rand_x 1 | m takes the
+    //      min / max of its values, -step_form auto_all self-checks a pad / fused winner against it.  Those runs, gen: with decades > 0 (the
+    //      host's pow) and every .mtx block build the host block as before and UPLOAD it.  -equilibrate 1 of a -dp / -sp run scales the
+    //      generated block where it lies (uspmv_equilibrate_device: this rank's rows, global columns, as the host route scales its block).
     //      USPMV_DEVICE_BLOCK=upload forces the uploaded source (A/B of the two sources on one command).
     std::vector<int32_t> wsa((size_t)P + 1, 0), metis_perm;
     uspmv_coo_t *local = nullptr;
@@ -167,7 +169,7 @@ int uspmv_run_distributed(const DistConfig &c) {
             for (int32_t v : counts) nnz_g += v;
             CK(uspmv_seg_from_row_counts(counts.data(), n_rows_g, seg, P, wsa.data()));
         }
-        dev_gen = dev_route && !(dec > 0.0) && !c.equilibrate && c.random_init_x == '0' && c.step_form != "auto_all" &&
+        dev_gen = dev_route && !(dec > 0.0) && !(c.equilibrate && c.ap) && c.random_init_x == '0' && c.step_form != "auto_all" &&
                   !(force_src && !strcmp(force_src, "upload"));
         t_block = std::chrono::steady_clock::now();       // (the partition above is every route's; the block is what the routes build differently)
         if (dev_gen) {
@@ -242,7 +244,14 @@ int uspmv_run_distributed(const DistConfig &c) {
     // -equilibrate 1: every rank scales ITS block (rows, then columns of the row-scaled block), as the reference does after the
     // segmentation (code/main.cpp:1117-1125 on local_mtx)
     t_block = std::chrono::steady_clock::now();
-    if (c.equilibrate) CK(uspmv_coo_equilibrate(local));
+    if (c.equilibrate && dev_gen) {   // the generated block, in place in HBM; the two divisor vectors are not needed afterwards
+        const int64_t n_loc = wsa[(size_t)rank + 1] - wsa[(size_t)rank];
+        double *d_rmax = nullptr, *d_cmax = nullptr;
+        HK(hipMalloc((void **)&d_rmax, 8 * (size_t)std::max<int64_t>(n_loc, 1)));
+        HK(hipMalloc((void **)&d_cmax, 8 * (size_t)std::max<int64_t>(n_cols_g, 1)));
+        CK(uspmv_equilibrate_device(d_I, d_J, d_V, const_cast<double *>(d_V), n_loc, n_cols_g, d_nnz, d_rmax, d_cmax, nullptr));
+        (void)hipFree(d_rmax); (void)hipFree(d_cmax);
+    } else if (c.equilibrate) CK(uspmv_coo_equilibrate(local));
     if (dev_route && !dev_gen) {   // the host block, built and scaled as on the host route, into three device arrays
         const int32_t *ci = nullptr, *cj = nullptr;
         const double *cv = nullptr;

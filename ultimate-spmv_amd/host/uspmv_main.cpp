@@ -83,7 +83,8 @@ void usage() {
             "  -bench_steps <int> -bench_warmup <int> -json <file|-> (fixed-count protocol, JSON report)  -x_prepared <0|1> (bench mode, column-major block vectors: X re-laid out once)\n"
             "  -convert <host|device|device_stable> (where convert_to_scs runs; device_stable: ties of the sigma sort in original order;\n"
             "    multi-rank runs: the whole per-rank set-up on the device, any of -dp|-sp|-ap[dp_sp] -- a gen: block with decades 0 is generated\n"
-            "    in HBM unless -equilibrate 1, -rand_x 1|m or -step_form auto_all need the host block, which is then uploaded, as a .mtx block is)\n"
+            "    in HBM, and scaled there by -equilibrate 1, unless -rand_x 1|m or -step_form auto_all need the host block, which is then\n"
+            "    uploaded, as a .mtx block is)\n"
             "  -tune <key>=<int> (a tuning key of the library, e.g. tlc_idx12=0, spmmv_reorder=1; repeatable)\n"
             "  multi-rank runs: -check_y <0|1> -step_form <auto|auto_all|overlap|plain|pad|fused>  (-ap[dp_sp]: scs, single vector, no auto_all / fused)\n"
             "  -seg_metis [-part_file <file>]: graph partition (built-in level-set partitioner, or part ids from a gpmetis-style file)\n");

@@ -286,14 +286,25 @@ void uspmv_dmat_free(uspmv_dmat_t *m);
  * irregular rows.  Every one of them walks each row's slots in the reference's order (scs_impl_cpu, code/kernels.hpp:218-258): same bits. */
 int uspmv_dmat_optimize(uspmv_dmat_t *m, const uspmv_scs_t *s, int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* Same for an ap[dp_sp] pair (structs with identical row layout): one shared line list per tile, 16-bit
- * indices for both structs; uspmv_spmv_ap then streams 10 + 6 instead of 12 + 8 bytes per non-zero. */
+ * indices for both structs; uspmv_spmv_ap then streams 10 + 6 instead of 12 + 8 bytes per non-zero.
+ * Fallback order: lines -> elements -> sweep.  The shared plan over single x ELEMENTS (one list per 256-row tile over the columns of both
+ * structs, the policy of uspmv_dmat_optimize: max_lines 0, a line plan that is invalid or stages under nine tenths of its tiles, at most a
+ * tenth of the sampled tiles over "tlc_elem_cap", four entries per listed element) is installed on BOTH handles
+ * (uspmv_dmat_plan_granularity = 1 on each, *n_tiles / *n_staged then describe it).  A pair falls to it by itself from 2^20 padded rows
+ * on; a smaller pair goes from the line plan straight to the column-window sweep unless tuning "tlc_elem" is 2 (DESIGN.md 9.9 says why).
+ * Same bits on every plan. */
 int uspmv_dmat_optimize_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, const uspmv_scs_t *s_dp, const uspmv_scs_t *s_sp,
                            int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* Same for the two or three parts of an ap split with an fp16 part (hi: F64 or F32, mid: F32 or NULL, hp: F16; identical row layout):
  * one line list per tile over every part's columns, 16-bit local indices per part.  When the line plan stages fewer than half of the
  * tiles the column-window sweep shared by the parts is tried (uspmv_dmat_optimize_sweep_ap_hp with its defaults) and kept when it covers
  * at least half of its tiles; else the handles stay planless and uspmv_spmv_ap_hp runs its lane-per-row kernel.  n_tiles / n_staged
- * report the line plan's outcome either way; uspmv_dmat_plan_info tells which plan the handles carry. */
+ * report the line plan's outcome either way; uspmv_dmat_plan_info tells which plan the handles carry.
+ * Fallback order: lines -> elements -> sweep.  Between the two, under uspmv_dmat_optimize's policy (max_lines 0, a line plan that is
+ * invalid or stages under nine tenths of its tiles, at most a tenth of the sampled tiles over "tlc_elem_cap" distinct columns -- counted
+ * over all parts --, four entries per listed element; "tlc_elem" 0 never, 2 always tries), the shared plan over single x ELEMENTS is
+ * installed on every part: uspmv_dmat_plan_granularity answers 1 on each handle, *n_tiles / *n_staged describe that plan, the cap is
+ * counted in elements of x (double, float for ap[sp_hp]).  Same bits on every plan. */
 int uspmv_dmat_optimize_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, const uspmv_scs_t *s_hi, const uspmv_scs_t *s_mid,
                               const uspmv_scs_t *s_hp, int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* SpMMV counterpart of uspmv_dmat_optimize (no reference counterpart): plan for block vectors of
@@ -346,7 +357,8 @@ int uspmv_dmat_block_plan_info(const uspmv_dmat_t *m, int64_t meta[10]);
 int uspmv_dmat_block_plan_staged(const uspmv_dmat_t *m, int64_t *rows_staged);
 /* x elements per entry of the tile-local-column plan's lists: 16 (128-byte lines, the default), 1 (single elements: the plan uspmv_dmat_optimize falls
  * to when a tile's columns are scattered over too many lines -- row numberings that are only locally coherent), 0 without such a plan.  Same kernel
- * arithmetic as scs_impl_cpu (code/kernels.hpp:218-258) either way. */
+ * arithmetic as scs_impl_cpu (code/kernels.hpp:218-258) either way.  Every handle of an ap split answers for the plan the split shares,
+ * the parts that hold only their local indices included. */
 int uspmv_dmat_plan_granularity(const uspmv_dmat_t *m, int *elements_per_list_entry);
 /* 1 when that plan runs on rows dealt to its tiles by the matrix graph (private value copy in HBM, y stored through a row map), else 0 */
 int uspmv_dmat_plan_rows_dealt(const uspmv_dmat_t *m, int *dealt);
@@ -379,9 +391,12 @@ int uspmv_dmat_optimize_block_device(uspmv_dmat_t *m, int block_vec_size, int64_
  * uspmv_dmat_plan_granularity answers 1), then the column-window sweep.  Same tuning keys ("tlc_elem", "tlc_elem_cap").  Not here:
  * the element plan on rows dealt to the tiles by the matrix graph ("tlc_elem_rows"), which needs the host struct. */
 int uspmv_dmat_optimize_device(uspmv_dmat_t *m, int max_lines, int64_t *n_tiles, int64_t *n_staged);
-/* The shared plan of an ap[dp_sp] pair (uspmv_dmat_optimize_ap) built on the device from the two handles' own arrays. */
+/* The shared plan of an ap[dp_sp] pair (uspmv_dmat_optimize_ap) built on the device from the two handles' own arrays, in the same
+ * fallback order under the same policy: lines -> elements -> sweep (the element plan built on the device as well, equal to the host
+ * planner's array for array; by itself from 2^20 padded rows on, else under "tlc_elem" 2). */
 int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_lines, int64_t *n_tiles, int64_t *n_staged);
-/* The plan of uspmv_dmat_optimize_ap_hp built on the device from the handles' own arrays (equal to the host planner's array for array). */
+/* The plan of uspmv_dmat_optimize_ap_hp built on the device from the handles' own arrays (equal to the host planner's array for array),
+ * in the same fallback order under the same policy: lines -> elements -> sweep. */
 int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_dmat_t *hp, int max_lines, int64_t *n_tiles, int64_t *n_staged);
 /* host copies of a handle's plan (tests): meta = {n_tiles, n_lines_total, n_col16, max_lines_used}; call with NULL
  * arrays first to size them */

@@ -1172,7 +1172,8 @@ class DeviceMatrix:
         return a.value, b.value
 
     def plan_granularity(self):
-        """x elements per list entry of the tile-local-column plan: 16 (lines), 1 (single elements), 0 (no plan): uspmv_dmat_plan_granularity."""
+        """x elements per list entry of the tile-local-column plan: 16 (lines), 1 (single elements), 0 (no plan): uspmv_dmat_plan_granularity.
+        Every handle of an ap split answers for the plan the split shares."""
         g = C.c_int()
         _ck(lib().uspmv_dmat_plan_granularity(self.h, C.byref(g)))
         return g.value
@@ -1493,7 +1494,9 @@ def dmat_download(A):
 
 
 def optimize_ap(A_dp, A_sp, scs_dp, scs_sp, max_lines=0):
-    """Shared tile-local-column plan for an ap[dp_sp] pair; returns (n_tiles, n_staged_tiles)."""
+    """Shared tile-local-column plan for an ap[dp_sp] pair; returns (n_tiles, n_staged_tiles).  Fallback order lines -> elements -> sweep
+    (uspmv_dmat_optimize_ap): plan_granularity() answers 1 on BOTH handles when the shared plan over single x elements was taken (a pair
+    of 2^20 padded rows or more by itself, a smaller one under set_tuning(tlc_elem=2)), plan_info() kind 2 when the sweep took over."""
     a, b = _i64(), _i64()
     _ck(lib().uspmv_dmat_optimize_ap(A_dp.h, A_sp.h, scs_dp.h, scs_sp.h, max_lines, C.byref(a), C.byref(b)))
     for A in (A_dp, A_sp):
@@ -1502,7 +1505,8 @@ def optimize_ap(A_dp, A_sp, scs_dp, scs_sp, max_lines=0):
 
 
 def optimize_device_ap(A_dp, A_sp, max_lines=0):
-    """Shared tile-local-column plan of an ap[dp_sp] pair built on the device from the handles' own arrays."""
+    """Shared tile-local-column plan of an ap[dp_sp] pair built on the device from the handles' own arrays: optimize_ap's plans in
+    optimize_ap's order (lines -> elements -> sweep), equal to the host planner's array for array."""
     a, b = _i64(), _i64()
     _ck(lib().uspmv_dmat_optimize_device_ap(A_dp.h, A_sp.h, max_lines, C.byref(a), C.byref(b)))
     for A in (A_dp, A_sp):
@@ -1512,8 +1516,10 @@ def optimize_device_ap(A_dp, A_sp, max_lines=0):
 
 def optimize_ap_hp(A_hi, A_mid, A_hp, scs_hi, scs_mid, scs_hp, max_lines=0):
     """Shared tile-local-column plan of the two or three parts of an ap split with an fp16 part (A_mid / scs_mid None for two parts);
-    returns (n_tiles, n_staged_tiles) of that plan.  Fewer than half of the tiles staged: the shared column-window sweep is tried instead
-    (plan_info() kind 2 when it took over), else no plan is installed."""
+    returns (n_tiles, n_staged_tiles) of that plan.  Fallback order lines -> elements -> sweep: under nine tenths of the tiles staged, the
+    shared plan over single x elements is tried (taken: plan_granularity() answers 1 on every handle of the split and the counts describe
+    it); fewer than half of the tiles staged: the shared column-window sweep is tried (plan_info() kind 2 when it took over), else no
+    plan is installed."""
     a, b = _i64(), _i64()
     _ck(lib().uspmv_dmat_optimize_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, scs_hi.h,
                                         scs_mid.h if scs_mid is not None else None, scs_hp.h, max_lines, C.byref(a), C.byref(b)))
@@ -1521,7 +1527,7 @@ def optimize_ap_hp(A_hi, A_mid, A_hp, scs_hi, scs_mid, scs_hp, max_lines=0):
 
 
 def optimize_device_ap_hp(A_hi, A_mid, A_hp, max_lines=0):
-    """The plan of optimize_ap_hp built on the device from the handles' own arrays."""
+    """The plan of optimize_ap_hp built on the device from the handles' own arrays, in the same order (lines -> elements -> sweep)."""
     a, b = _i64(), _i64()
     _ck(lib().uspmv_dmat_optimize_device_ap_hp(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, max_lines, C.byref(a), C.byref(b)))
     return a.value, b.value

@@ -421,7 +421,7 @@ ApHpBlockPath ap_hp_block_path(const uspmv_dmat *hi, const uspmv_dmat *mid, cons
     }
     const uint64_t id = hi->tlc.plan_id;
     const bool planned = hi->tlc.on && id != 0 && hp->tlc.on && hp->tlc.plan_id == id && (!mid || (mid->tlc.on && mid->tlc.plan_id == id));
-    if (!planned || !g_tune.tlc || hi->tlc.max_lines < 1) return {AP_HP_PATH_GENERIC, 0};
+    if (!planned || !g_tune.tlc || hi->tlc.elem || hi->tlc.max_lines < 1) return {AP_HP_PATH_GENERIC, 0};   // (a plan over single x elements: not for block vectors)
     const int bs = tlc_block_bs(hi->tlc, b, x_bytes);
     if (bs < 2) return {AP_HP_PATH_GENERIC, 0};              // not even two vectors of the fullest tile fit LDS
     return {AP_HP_PATH_STAGED, bs};
@@ -429,11 +429,11 @@ ApHpBlockPath ap_hp_block_path(const uspmv_dmat *hi, const uspmv_dmat *mid, cons
 
 // What uspmv_spmmv_ap_hp_tiles runs: the ONE predicate behind the launch and behind uspmv_spmmv_ap_hp_tiles_path.  The staged kernel over
 // the listed tiles -- X staged straight from the caller's layout; column-major X at every ld, in pieces of 16, 8 or 4 bytes -- or lane
-// per row over the tiles' rows: any other width or alignment of X / Y, "tlc" 0, "spmmv_variant" 1, or a plan whose fullest tile leaves no
-// room for two vectors in LDS.  (The caller has checked that the parts share a line plan.)
+// per row over the tiles' rows: any other width or alignment of X / Y, "tlc" 0, "spmmv_variant" 1, a plan over single x elements, or a
+// plan whose fullest tile leaves no room for two vectors in LDS.  (The caller has checked that the parts share a line plan.)
 ApHpBlockPath ap_hp_tiles_path(const uspmv_dmat *hi, int b, bool aligned16) {
     if (g_tune.spmmv_variant == 1 || !aligned16 || (b != 2 && b != 4 && b != 8 && b != 16)) return {AP_HP_PATH_GENERIC, 0};
-    if (!g_tune.tlc || hi->tlc.max_lines < 1) return {AP_HP_PATH_GENERIC, 0};
+    if (!g_tune.tlc || hi->tlc.elem || hi->tlc.max_lines < 1) return {AP_HP_PATH_GENERIC, 0};
     const int bs = tlc_block_bs(hi->tlc, b, hi->dtype == USPMV_F32 ? 4 : 8);
     if (bs < 2) return {AP_HP_PATH_GENERIC, 0};
     return {AP_HP_PATH_STAGED, bs};

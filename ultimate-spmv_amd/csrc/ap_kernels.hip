@@ -12,7 +12,9 @@ namespace {
 // 10 and 6 bytes per non-zero instead of 12 and 8; numerics of scs_ap_impl_cpu, bit-exact.
 // IDS: workgroup b runs tile tile_ids[b] (the interior / boundary lists of the distributed step); an entry < 0 is a conditional entry
 // that was switched off (uspmv_dist's padding re-run) and returns before the barrier, uniformly for the workgroup.
-template <int CT, bool NT, bool IDS = false>
+// ELEM: the shared plan lists single x ELEMENTS (TlcPlan::elem): thread k gathers element k of the tile's list into xs[k], as scs_spmv_tlc's
+// ELEM arm does -- one 8-byte gather per distinct column of the tile; the chains over xs are the same code, same slot order, same bits.
+template <int CT, bool NT, bool IDS = false, bool ELEM = false>
 __global__ void __launch_bounds__(1024) scs_spmv_ap_tlc(const long n_chunks, const int C_rt,
         const int *__restrict__ dp_cp, const int *__restrict__ dp_cl, const int *__restrict__ dp_ci, const double *__restrict__ dp_va,
         const int *__restrict__ sp_cp, const int *__restrict__ sp_cl, const int *__restrict__ sp_ci, const float *__restrict__ sp_va,
@@ -38,13 +40,20 @@ __global__ void __launch_bounds__(1024) scs_spmv_ap_tlc(const long n_chunks, con
     if (valid) { dcs = dp_cp[c]; Ld = dp_cl[c]; scs_ = sp_cp[c]; Ls = sp_cl[c]; dq0 = dp_c16p[c]; sq0 = sp_c16p[c]; }
     double dt = 0.0, st = 0.0;
     if (nl > 0) {
-        const int sub = threadIdx.x & 7, lk = threadIdx.x >> 3;
-        for (int k = lk; k < nl; k += blockDim.x >> 3) {
-            const long idx = (long)tile_lines[lp0 + k] * 16 + sub * 2;
-            vec_t v;
-            if (idx + 2 <= x_len) v = *(const vec_t *)(x + idx);
-            else { v[0] = idx < x_len ? x[idx] : 0.0; v[1] = 0.0; }
-            *(vec_t *)(xs + k * 16 + sub * 2) = v;
+        if constexpr (ELEM) {
+            for (int k = threadIdx.x; k < nl; k += blockDim.x) {
+                const long idx = tile_lines[lp0 + k];
+                xs[k] = idx < x_len ? x[idx] : 0.0;
+            }
+        } else {
+            const int sub = threadIdx.x & 7, lk = threadIdx.x >> 3;
+            for (int k = lk; k < nl; k += blockDim.x >> 3) {
+                const long idx = (long)tile_lines[lp0 + k] * 16 + sub * 2;
+                vec_t v;
+                if (idx + 2 <= x_len) v = *(const vec_t *)(x + idx);
+                else { v[0] = idx < x_len ? x[idx] : 0.0; v[1] = 0.0; }
+                *(vec_t *)(xs + k * 16 + sub * 2) = v;
+            }
         }
         __syncthreads();
         if (Ld > 0) {
@@ -269,8 +278,8 @@ __device__ __forceinline__ double gather_chain(const VT *__restrict__ vp, const 
 // Tile-local-column form: the tile's x lines (the union over all parts) staged once in LDS, then the parts' chains one after the other,
 // each streaming sizeof(VT) + 2 bytes per non-zero.  Tiles without a line list (footprint over the plan's line budget) gather from x.
 // IDS: workgroup b runs tile tile_ids[b] (the interior / boundary lists of the distributed step), an entry < 0 returns before the barrier,
-// uniformly for the workgroup -- as in scs_spmv_ap_tlc.
-template <int CT, bool NT, typename HT, bool MID, bool IDS = false>
+// uniformly for the workgroup -- as in scs_spmv_ap_tlc.  ELEM: the list holds single x elements, staged one per thread (as there).
+template <int CT, bool NT, typename HT, bool MID, bool IDS = false, bool ELEM = false>
 __global__ void __launch_bounds__(1024) scs_spmv_ap_hp_tlc(const long n_chunks, const int C_rt, const ApHpParts P, const HT *__restrict__ x,
                                                            HT *__restrict__ y, const int *__restrict__ tile_line_ptr,
                                                            const int *__restrict__ tile_lines, const long x_len, const int xcd_remap,
@@ -296,13 +305,20 @@ __global__ void __launch_bounds__(1024) scs_spmv_ap_hp_tlc(const long n_chunks, 
             if (k != 1 || MID) { cs[k] = P.cp[k][c]; L[k] = P.cl[k][c]; q0[k] = P.c16p[k][c]; }
     double acc[3] = {0.0, 0.0, 0.0};
     if (nl > 0) {
-        const int sub = threadIdx.x & 7, lk = threadIdx.x >> 3;
-        for (int k = lk; k < nl; k += blockDim.x >> 3) {
-            const long idx = (long)tile_lines[lp0 + k] * 16 + sub * 2;
-            vec_t v;
-            if (idx + 2 <= x_len) v = *(const vec_t *)(x + idx);
-            else { v[0] = idx < x_len ? x[idx] : (HT)0; v[1] = (HT)0; }
-            *(vec_t *)(xs + k * 16 + sub * 2) = v;
+        if constexpr (ELEM) {
+            for (int k = threadIdx.x; k < nl; k += blockDim.x) {
+                const long idx = tile_lines[lp0 + k];
+                xs[k] = idx < x_len ? x[idx] : (HT)0;
+            }
+        } else {
+            const int sub = threadIdx.x & 7, lk = threadIdx.x >> 3;
+            for (int k = lk; k < nl; k += blockDim.x >> 3) {
+                const long idx = (long)tile_lines[lp0 + k] * 16 + sub * 2;
+                vec_t v;
+                if (idx + 2 <= x_len) v = *(const vec_t *)(x + idx);
+                else { v[0] = idx < x_len ? x[idx] : (HT)0; v[1] = (HT)0; }
+                *(vec_t *)(xs + k * 16 + sub * 2) = v;
+            }
         }
         __syncthreads();
         if (L[0] > 0)
@@ -368,11 +384,12 @@ template <typename HT, bool MID>
 int launch_ap_hp_tiles(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *tile_ids, long n_ids, const HT *d_x,
                        HT *d_y, hipStream_t stream) {
     const ApHpParts P = ap_hp_parts(hi, mid, hp);
-    const size_t lds = (size_t)hi->tlc.max_lines * 16 * sizeof(HT);
+    const bool elem = hi->tlc.elem;                               // (max_lines then counts elements)
+    const size_t lds = (size_t)hi->tlc.max_lines * (elem ? 1 : 16) * sizeof(HT);
     const int C = (int)hi->C;
 #define APHP_IDS(CTV, NTV)                                                                                                        \
     do {                                                                                                                         \
-        auto kfn = scs_spmv_ap_hp_tlc<CTV, NTV, HT, MID, true>;                                                                  \
+        auto kfn = elem ? scs_spmv_ap_hp_tlc<CTV, NTV, HT, MID, true, true> : scs_spmv_ap_hp_tlc<CTV, NTV, HT, MID, true>;       \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
         hipLaunchKernelGGL(kfn, dim3((unsigned)n_ids), dim3(hi->tlc.tile_rows), lds, stream, (long)hi->n_chunks, C, P, d_x, d_y,  \
                            hi->tlc.line_ptr.get(), hi->tlc.lines.get(), (long)hi->tlc.x_len, g_tune.xcd_remap, tile_ids);        \
@@ -396,10 +413,11 @@ int launch_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *
     const bool nt = g_tune.nontemporal != 0;
     const int C = (int)hi->C;
     if (path == 2) {
-        const size_t lds = (size_t)hi->tlc.max_lines * 16 * sizeof(HT);
+        const bool elem = hi->tlc.elem;
+        const size_t lds = (size_t)hi->tlc.max_lines * (elem ? 1 : 16) * sizeof(HT);
 #define APHP_TLC(CTV, NTV)                                                                                                       \
     do {                                                                                                                         \
-        auto kfn = scs_spmv_ap_hp_tlc<CTV, NTV, HT, MID>;                                                                        \
+        auto kfn = elem ? scs_spmv_ap_hp_tlc<CTV, NTV, HT, MID, false, true> : scs_spmv_ap_hp_tlc<CTV, NTV, HT, MID>;            \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
         hipLaunchKernelGGL(kfn, dim3((unsigned)hi->tlc.n_tiles), dim3(hi->tlc.tile_rows), lds, stream, (long)hi->n_chunks, C, P,  \
                            d_x, d_y, hi->tlc.line_ptr.get(), hi->tlc.lines.get(), (long)hi->tlc.x_len, g_tune.xcd_remap,         \
@@ -477,11 +495,12 @@ int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int 
 int launch_spmv_ap_tiles(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *tile_ids, long n_ids, const double *d_x, double *d_y,
                          hipStream_t stream) {
     if (n_ids == 0) return USPMV_OK;
-    const size_t lds = (size_t)dp->tlc.max_lines * 16 * sizeof(double);
+    const bool elem = dp->tlc.elem;                               // (max_lines then counts elements)
+    const size_t lds = (size_t)dp->tlc.max_lines * (elem ? 1 : 16) * sizeof(double);
     const int C = (int)dp->C;
 #define APT_IDS_LAUNCH(CTV, NTV)                                                                                      \
     do {                                                                                                              \
-        auto kfn = scs_spmv_ap_tlc<CTV, NTV, true>;                                                                  \
+        auto kfn = elem ? scs_spmv_ap_tlc<CTV, NTV, true, true> : scs_spmv_ap_tlc<CTV, NTV, true>;                   \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(kfn, dim3((unsigned)n_ids), dim3(dp->tlc.tile_rows), lds, stream, (long)dp->n_chunks, C,   \
                            dp->chunk_ptrs, dp->chunk_lengths, dp->col_idxs, (const double *)dp->values, sp->chunk_ptrs, \
@@ -505,11 +524,12 @@ int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x
     }
     if (!d_x_sp && dp->tlc.on && sp->tlc.on && dp->tlc.plan_id != 0 && dp->tlc.plan_id == sp->tlc.plan_id && g_tune.tlc &&
         ((uintptr_t)d_x % 16 == 0)) {
-        const size_t lds = (size_t)dp->tlc.max_lines * 16 * sizeof(double);
+        const bool elem = dp->tlc.elem;
+        const size_t lds = (size_t)dp->tlc.max_lines * (elem ? 1 : 16) * sizeof(double);
         const int C = (int)dp->C;
 #define APT_LAUNCH(CTV, NTV)                                                                                          \
     do {                                                                                                              \
-        auto kfn = scs_spmv_ap_tlc<CTV, NTV>;                                                                        \
+        auto kfn = elem ? scs_spmv_ap_tlc<CTV, NTV, false, true> : scs_spmv_ap_tlc<CTV, NTV>;                        \
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(kfn, dim3((unsigned)dp->tlc.n_tiles), dim3(dp->tlc.tile_rows), lds, (hipStream_t)stream,     \
                            (long)dp->n_chunks, C, dp->chunk_ptrs, dp->chunk_lengths, dp->col_idxs, (const double *)dp->values, \

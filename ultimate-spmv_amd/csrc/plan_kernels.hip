@@ -227,11 +227,29 @@ __global__ void __launch_bounds__(256) plan_write(const long n_chunks, const int
 // which lanes or atomics arrive.  One workgroup per tile, thread <-> row, padding slots counted like the host planner counts them.
 constexpr int ELEM_EMPTY = INT32_MAX;          // (no column index reaches it: n_cols <= INT32_MAX)
 
-// The set of the tile's columns in set[0 .. 2^log2n); *s_cnt = distinct columns entered.  Lanes stop entering once *s_cnt exceeds `cap`
-// (every lane can pass that test at most once more: at most cap + 256 entries, and the launchers size the table beyond that), so
-// min(*s_cnt, cap + 1) is exact.  Returns the largest column of the lane's row.
-__device__ __forceinline__ int tile_elem_set(const long n_chunks, const int C, const int *__restrict__ chunk_ptrs, const int *__restrict__ chunk_lengths,
-                                             const int *__restrict__ col_idxs, const long tile, int *set, const int log2n, const int cap, int *s_cnt) {
+// the one to three structs a tile's element set is filled from (one struct, or the parts of an ap split in the order of the split), and
+// -- write pass -- where each part's local indices go
+struct ElemParts {
+    int n = 0;
+    const int *cp[3] = {nullptr, nullptr, nullptr}, *cl[3] = {nullptr, nullptr, nullptr}, *ci[3] = {nullptr, nullptr, nullptr};
+    const unsigned *c16p[3] = {nullptr, nullptr, nullptr};
+    unsigned short *c16[3] = {nullptr, nullptr, nullptr};
+};
+ElemParts elem_parts(const uspmv_dmat *const parts[3]) {
+    ElemParts P;
+    for (int k = 0; k < 3 && parts[k]; ++k) {
+        P.cp[k] = parts[k]->chunk_ptrs; P.cl[k] = parts[k]->chunk_lengths; P.ci[k] = parts[k]->col_idxs;
+        P.n = k + 1;
+    }
+    return P;
+}
+
+// The set of the tile's columns in set[0 .. 2^log2n) -- of every part of P (the parts of an ap split share one row layout and one set);
+// *s_cnt = distinct columns entered.  Lanes stop entering once *s_cnt exceeds `cap` (every lane can pass that test at most once more,
+// whichever part it is in: at most cap + 256 entries, and the launchers size the table beyond that), so min(*s_cnt, cap + 1) is exact.
+// Returns the largest column of the lane's row.
+__device__ __forceinline__ int tile_elem_set(const long n_chunks, const int C, const ElemParts &P, const long tile, int *set, const int log2n,
+                                             const int cap, int *s_cnt) {
     const unsigned mask = (1u << log2n) - 1u;
     for (unsigned w = threadIdx.x; w <= mask; w += 256) set[w] = ELEM_EMPTY;
     if (threadIdx.x == 0) *s_cnt = 0;
@@ -241,22 +259,25 @@ __device__ __forceinline__ int tile_elem_set(const long n_chunks, const int C, c
     const int i = (int)(row - c * C);
     int mx = 0;
     if (c < n_chunks) {
-        const int cs = chunk_ptrs[c], L = chunk_lengths[c];
-        int last = -1;
-        for (int j = 0; j < L; ++j) {
-            const int col = col_idxs[(long)cs + (long)j * C + i];
-            mx = max(mx, col);
-            if (col == last) continue;                      // (the padding slots of a row repeat one column)
-            last = col;
-            if (__atomic_load_n(s_cnt, __ATOMIC_RELAXED) > cap) continue;
-            unsigned h = ((unsigned)col * 2654435761u) >> (32 - log2n);
-            for (unsigned probe = 0; probe <= mask; ++probe, h = (h + 1u) & mask) {
-                int old = __atomic_load_n(&set[h], __ATOMIC_RELAXED);
-                if (old == ELEM_EMPTY) {
-                    old = atomicCAS(&set[h], ELEM_EMPTY, col);
-                    if (old == ELEM_EMPTY) { atomicAdd(s_cnt, 1); break; }
+        for (int k = 0; k < P.n; ++k) {
+            const int cs = P.cp[k][c], L = P.cl[k][c];
+            const int *__restrict__ ci = P.ci[k];
+            int last = -1;
+            for (int j = 0; j < L; ++j) {
+                const int col = ci[(long)cs + (long)j * C + i];
+                mx = max(mx, col);
+                if (col == last) continue;                      // (the padding slots of a row repeat one column)
+                last = col;
+                if (__atomic_load_n(s_cnt, __ATOMIC_RELAXED) > cap) continue;
+                unsigned h = ((unsigned)col * 2654435761u) >> (32 - log2n);
+                for (unsigned probe = 0; probe <= mask; ++probe, h = (h + 1u) & mask) {
+                    int old = __atomic_load_n(&set[h], __ATOMIC_RELAXED);
+                    if (old == ELEM_EMPTY) {
+                        old = atomicCAS(&set[h], ELEM_EMPTY, col);
+                        if (old == ELEM_EMPTY) { atomicAdd(s_cnt, 1); break; }
+                    }
+                    if (old == col) break;
                 }
-                if (old == col) break;
             }
         }
     }
@@ -265,14 +286,13 @@ __device__ __forceinline__ int tile_elem_set(const long n_chunks, const int C, c
 }
 
 // count pass: n_elems[tile] = distinct columns of the tile, clipped at cap + 1 ("over the cap" stays visible); *max_col as plan_count_lines
-__global__ void __launch_bounds__(256) plan_count_elems(const long n_chunks, const int C, const int *__restrict__ chunk_ptrs,
-        const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs, const int cap, const int log2n, int *__restrict__ n_elems,
-        int *__restrict__ max_col) {
+__global__ void __launch_bounds__(256) plan_count_elems(const long n_chunks, const int C, const ElemParts P, const int cap, const int log2n,
+        int *__restrict__ n_elems, int *__restrict__ max_col) {
     extern __shared__ int elem_set[];
     __shared__ int s_cnt, s_maxcol;
     if (threadIdx.x == 0) s_maxcol = 0;
     const long tile = blockIdx.x;
-    const int mx = tile_elem_set(n_chunks, C, chunk_ptrs, chunk_lengths, col_idxs, tile, elem_set, log2n, cap, &s_cnt);
+    const int mx = tile_elem_set(n_chunks, C, P, tile, elem_set, log2n, cap, &s_cnt);
     if (mx > 0) atomicMax(&s_maxcol, mx);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -281,17 +301,17 @@ __global__ void __launch_bounds__(256) plan_count_elems(const long n_chunks, con
     }
 }
 
-// write pass: the tile's sorted element list at tile_line_ptr[tile] and every slot's rank in it as its 16-bit local index (col16 layout
-// [group of four slots][row i][slot % 4]; zero-filled before, so slots beyond the chunk length, tiles over the cap and empty tiles stay zero)
-__global__ void __launch_bounds__(256) plan_write_elems(const long n_chunks, const int C, const int *__restrict__ chunk_ptrs,
-        const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs, const int *__restrict__ tile_line_ptr,
-        const unsigned *__restrict__ c16_ptrs, int *__restrict__ tile_lines, unsigned short *__restrict__ col16, const int log2n) {
+// write pass: the tile's sorted element list at tile_line_ptr[tile] -- once, whatever the number of parts -- and every slot's rank in it as
+// its 16-bit local index, each part into its own array (col16 layout [group of four slots][row i][slot % 4]; zero-filled before, so slots
+// beyond the chunk length, tiles over the cap and empty tiles stay zero)
+__global__ void __launch_bounds__(256) plan_write_elems(const long n_chunks, const int C, const ElemParts P, const int *__restrict__ tile_line_ptr,
+        int *__restrict__ tile_lines, const int log2n) {
     extern __shared__ int elem_set[];
     __shared__ int s_cnt;
     const long tile = blockIdx.x;
     const int lp0 = tile_line_ptr[tile], n = tile_line_ptr[tile + 1] - lp0;
     if (n == 0) return;                                     // over the cap or empty: the kernel gathers
-    (void)tile_elem_set(n_chunks, C, chunk_ptrs, chunk_lengths, col_idxs, tile, elem_set, log2n, INT32_MAX - 1, &s_cnt);
+    (void)tile_elem_set(n_chunks, C, P, tile, elem_set, log2n, INT32_MAX - 1, &s_cnt);
     const int N = 1 << log2n;                               // (>= 1024: every stage has work for all 256 threads)
     for (int k = 2; k <= N; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -308,20 +328,23 @@ __global__ void __launch_bounds__(256) plan_write_elems(const long n_chunks, con
     const long c = row / C;
     const int i = (int)(row - c * C);
     if (c >= n_chunks) return;
-    const int cs = chunk_ptrs[c], L = chunk_lengths[c];
-    unsigned short *q = col16 + c16_ptrs[c];
-    int last = -1, rank = 0;
-    for (int j = 0; j < L; ++j) {
-        const int col = col_idxs[(long)cs + (long)j * C + i];
-        if (col != last) {
-            int lo = 0, hi = n;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (elem_set[mid] < col) lo = mid + 1; else hi = mid;
+    for (int k = 0; k < P.n; ++k) {
+        const int cs = P.cp[k][c], L = P.cl[k][c];
+        const int *__restrict__ ci = P.ci[k];
+        unsigned short *q = P.c16[k] + P.c16p[k][c];
+        int last = -1, rank = 0;
+        for (int j = 0; j < L; ++j) {
+            const int col = ci[(long)cs + (long)j * C + i];
+            if (col != last) {
+                int lo = 0, hi = n;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (elem_set[mid] < col) lo = mid + 1; else hi = mid;
+                }
+                last = col; rank = min(lo, n - 1);
             }
-            last = col; rank = min(lo, n - 1);
+            q[(long)(j >> 2) * 4 * C + i * 4 + (j & 3)] = (unsigned short)rank;
         }
-        q[(long)(j >> 2) * 4 * C + i * 4 + (j & 3)] = (unsigned short)rank;
     }
 }
 
@@ -416,26 +439,31 @@ static int elem_set_log2(int most) {
     return l;
 }
 
-int launch_plan_count_elems(const uspmv_dmat *A, long n_tiles, int cap, int *d_n_elems, int *d_max_col, hipStream_t st) {
+int launch_plan_count_elems(const uspmv_dmat *const parts[3], long n_tiles, int cap, int *d_n_elems, int *d_max_col, hipStream_t st) {
     if (cap < 1 || cap > 16384) return uspmv::fail(USPMV_ERR_INVALID, "element plan: cap %d outside 1 .. 16384", cap);   // 2^15 slots: 128 of the CU's 160 KiB
+    const uspmv_dmat *A = parts[0];
     const int log2n = elem_set_log2(cap);
     const size_t lds = (size_t)4 << log2n;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)plan_count_elems, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(plan_count_elems, dim3((unsigned)n_tiles), dim3(256), lds, st, (long)A->n_chunks, (int)A->C, A->chunk_ptrs, A->chunk_lengths,
-                       A->col_idxs, cap, log2n, d_n_elems, d_max_col);
+    hipLaunchKernelGGL(plan_count_elems, dim3((unsigned)n_tiles), dim3(256), lds, st, (long)A->n_chunks, (int)A->C, elem_parts(parts), cap, log2n,
+                       d_n_elems, d_max_col);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }
 
-// most_listed: the longest list of tile_line_ptr (the set is sized by it, not by the cap: a shorter sort)
-int launch_plan_write_elems(const uspmv_dmat *A, long n_tiles, int most_listed, const int *d_tile_line_ptr, const unsigned *d_c16_ptrs,
-                            int *d_tile_lines, unsigned short *d_col16, hipStream_t st) {
+// most_listed: the longest list of tile_line_ptr (the set is sized by it, not by the cap: a shorter sort); part k's local indices go to
+// d_col16[k] at d_c16_ptrs[k]
+int launch_plan_write_elems(const uspmv_dmat *const parts[3], long n_tiles, int most_listed, const int *d_tile_line_ptr, int *d_tile_lines,
+                            const unsigned *const d_c16_ptrs[3], unsigned short *const d_col16[3], hipStream_t st) {
     if (most_listed < 1 || most_listed > 16384) return uspmv::fail(USPMV_ERR_INVALID, "element plan: %d elements per tile outside 1 .. 16384", most_listed);
+    const uspmv_dmat *A = parts[0];
+    ElemParts P = elem_parts(parts);
+    for (int k = 0; k < P.n; ++k) { P.c16p[k] = d_c16_ptrs[k]; P.c16[k] = d_col16[k]; }
     const int log2n = elem_set_log2(most_listed);
     const size_t lds = (size_t)4 << log2n;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)plan_write_elems, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(plan_write_elems, dim3((unsigned)n_tiles), dim3(256), lds, st, (long)A->n_chunks, (int)A->C, A->chunk_ptrs, A->chunk_lengths,
-                       A->col_idxs, d_tile_line_ptr, d_c16_ptrs, d_tile_lines, d_col16, log2n);
+    hipLaunchKernelGGL(plan_write_elems, dim3((unsigned)n_tiles), dim3(256), lds, st, (long)A->n_chunks, (int)A->C, P, d_tile_line_ptr, d_tile_lines,
+                       log2n);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }

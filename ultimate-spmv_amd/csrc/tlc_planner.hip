@@ -395,16 +395,21 @@ double sampled_over_cap_frac(int64_t nt, Over over) {
     for (int64_t t = step / 2; t < nt; t += step) { ++seen; n_over += over(t) ? 1 : 0; }
     return seen > 0 ? (double)n_over / (double)seen : 1.0;
 }
-double elements_over_cap_frac(const uspmv_scs *s, int cap, int tile_rows) {
+// (ss[0 .. n): one struct, or the parts of an ap split, which share a row layout -- a tile's columns are the union over the parts)
+double elements_over_cap_frac(const uspmv_scs *const ss[], int n, int cap, int tile_rows) {
+    const uspmv_scs *s = ss[0];
     const int64_t C = s->C, T = std::max<int64_t>(1, tile_rows / C), nt = (s->n_chunks + T - 1) / T;
     std::vector<int32_t> cols;
     return sampled_over_cap_frac(nt, [&](int64_t t) {
         const int64_t c0 = t * T, c1 = std::min<int64_t>(c0 + T, s->n_chunks);
-        cols.assign(s->col_idxs.begin() + s->chunk_ptrs[(size_t)c0], s->col_idxs.begin() + s->chunk_ptrs[(size_t)c1]);
+        cols.clear();
+        for (int k = 0; k < n; ++k)
+            cols.insert(cols.end(), ss[k]->col_idxs.begin() + ss[k]->chunk_ptrs[(size_t)c0], ss[k]->col_idxs.begin() + ss[k]->chunk_ptrs[(size_t)c1]);
         std::sort(cols.begin(), cols.end());
         return (int64_t)(std::unique(cols.begin(), cols.end()) - cols.begin()) > cap;
     });
 }
+double elements_over_cap_frac(const uspmv_scs *s, int cap, int tile_rows) { return elements_over_cap_frac(&s, 1, cap, tile_rows); }
 
 // The element plans: most elements a tile may list (64 KiB of the value type at most), "an element serves four entries or more on
 // average", and when they are tried at all: the caller gave no line budget of its own and the line plan is invalid or leaves a tenth
@@ -450,15 +455,33 @@ int elements_take_over(bool own_budget, const PlanStats &line, bool allowed, int
     return USPMV_OK;
 }
 
-// The element plan's count pass on the device (plan_kernels.hip): per 256-row tile the distinct columns clipped at cap + 1, and the
-// struct's largest column.  O(n_tiles) comes back to the host.  Shapes without a plan: no tiles.
+// The parts of an ap split fall to the element plan by themselves -- "tlc_elem" 1 -- kind by kind, where it was measured faster than what
+// the split runs otherwise by more than the run-to-run spread (tools/ap_numbering_probe.py, profiles/ap_elem/, DESIGN 9.9: all four kinds,
+// 1.16 - 1.80 x on 1.5 M rows); "tlc_elem" 2 tries it whatever the kind and size.  ap[dp_sp] pairs do so only from 2^20 padded rows on (the
+// size from which measured_tile_rows counts a struct as large): tests/test_gpu_elem_plan_device.py pins the pair of the scattered
+// 40^3 x 3 dof stencil (192 000 rows) to lines -> sweep, so below that size a pair keeps those plans.
+bool ap_elements_by_default(int dtype_last, int64_t padded_rows) {
+    return dtype_last != USPMV_F32 || padded_rows >= (int64_t)1 << 20;   // (F32 last: ap[dp_sp]; F16 last: the kinds with an fp16 part)
+}
+bool ap_elements_allowed(const TlcPlanOpts &opts, const uspmv_dmat *first, const uspmv_dmat *last) {
+    return opts.elements && (g_tune.tlc_elem == 2 || ap_elements_by_default(last->dtype, first->n_chunks * first->C));
+}
+int64_t sum_elements(uspmv_dmat *const parts[3]) {
+    int64_t n = 0;
+    for (int k = 0; k < 3; ++k) if (parts[k]) n += parts[k]->n_elements;
+    return n;
+}
+
+// The element plan's count pass on the device (plan_kernels.hip): per 256-row tile the distinct columns -- of all parts together --
+// clipped at cap + 1, and the largest column.  O(n_tiles) comes back to the host.  Shapes without a plan: no tiles.
 struct ElemCounts {
     int cap = 0, max_col = 0;
     std::vector<int32_t> n;
 };
-int device_elem_count(const uspmv_dmat *A, int cap, ElemCounts *o, const char *who) {
+int device_elem_count(uspmv_dmat *const parts[3], int cap, ElemCounts *o, const char *who) {
     *o = {};
     o->cap = cap;
+    const uspmv_dmat *A = parts[0];
     const int64_t C = A->C, nc = A->n_chunks;
     if (C > 256 || 256 % C != 0 || nc < 1) return USPMV_OK;
     const int64_t T = 256 / C, nt = (nc + T - 1) / T;
@@ -466,7 +489,7 @@ int device_elem_count(const uspmv_dmat *A, int cap, ElemCounts *o, const char *w
     hipError_t e = d_n.alloc(4 * (size_t)nt);
     if (e == hipSuccess) e = d_max.zeros(4);
     if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-    if (int rc = launch_plan_count_elems(A, (long)nt, cap, d_n, d_max, nullptr)) return rc;
+    if (int rc = launch_plan_count_elems(parts, (long)nt, cap, d_n, d_max, nullptr)) return rc;
     o->n.resize((size_t)nt);
     e = hipMemcpy(o->n.data(), d_n, 4 * (size_t)nt, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(&o->max_col, d_max, 4, hipMemcpyDeviceToHost);
@@ -474,10 +497,12 @@ int device_elem_count(const uspmv_dmat *A, int cap, ElemCounts *o, const char *w
     return USPMV_OK;
 }
 
-// ... and its write pass, installed on the (plan-less) handle as device_plan_install_rows installs the line plan: owned buffers, O(n_chunks)
-// + O(n_tiles) on the host.  No plan (and USPMV_OK) for arrays beyond 32-bit offsets and when no tile stages; on a failure the handle has none either.
-int device_elem_install(uspmv_dmat *A, const ElemCounts &cnt, ElemStats *st, const char *who) {
-    A->tlc = {};
+// ... and its write pass, installed on the (plan-less) handles as device_plan_install_rows installs the line plan: owned buffers, the
+// element list with the first part, every part its own local indices, O(n_chunks) + O(n_tiles) on the host.  No plan (and USPMV_OK) for
+// arrays beyond 32-bit offsets and when no tile stages; on a failure the handles have none either.
+int device_elem_install(uspmv_dmat *const parts[3], const ElemCounts &cnt, ElemStats *st, const char *who) {
+    uspmv_dmat *const A = parts[0];
+    for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
     *st = {};
     const int64_t C = A->C, nc = A->n_chunks, nt = (int64_t)cnt.n.size();
     if (nt == 0) return USPMV_OK;
@@ -494,57 +519,97 @@ int device_elem_install(uspmv_dmat *A, const ElemCounts &cnt, ElemStats *st, con
     st->n_tiles = nt; st->n_staged = staged;
     if (staged == 0) return USPMV_OK;
     std::vector<int32_t> cl((size_t)nc);
-    std::vector<uint32_t> c16p;
-    int64_t tot16 = 0;
-    HIP_TRY(hipMemcpy(cl.data(), A->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
-    if (!c16_offsets(cl, C, &c16p, &tot16)) return USPMV_OK;
+    std::vector<uint32_t> c16p[3];
+    int64_t tot16[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) {
+        if (!parts[k]) continue;
+        HIP_TRY(hipMemcpy(cl.data(), parts[k]->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
+        if (!c16_offsets(cl, C, &c16p[k], &tot16[k])) return USPMV_OK;
+    }
     hipError_t e = A->tlc.line_ptr.upload(lp.data(), 4 * ((size_t)nt + 1));
     if (e == hipSuccess) e = A->tlc.lines.alloc(4 * (size_t)std::max<int64_t>(total, 1));
-    if (e == hipSuccess) e = A->tlc.c16_ptrs.upload(c16p.data(), 4 * ((size_t)nc + 1));
-    if (e == hipSuccess) e = A->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16, 1));
-    if (e == hipSuccess && launch_plan_write_elems(A, (long)nt, used, A->tlc.line_ptr, A->tlc.c16_ptrs, A->tlc.lines, A->tlc.col16, nullptr) != USPMV_OK) e = hipErrorUnknown;
+    const unsigned *d_c16p[3] = {nullptr, nullptr, nullptr};
+    unsigned short *d_c16[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; ++k) {
+        if (!parts[k]) continue;
+        if (e == hipSuccess) e = parts[k]->tlc.c16_ptrs.upload(c16p[k].data(), 4 * ((size_t)nc + 1));
+        if (e == hipSuccess) e = parts[k]->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16[k], 1));
+        d_c16p[k] = parts[k]->tlc.c16_ptrs; d_c16[k] = parts[k]->tlc.col16;
+    }
+    if (e == hipSuccess && launch_plan_write_elems(parts, (long)nt, used, A->tlc.line_ptr, A->tlc.lines, d_c16p, d_c16, nullptr) != USPMV_OK) e = hipErrorUnknown;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
-        A->tlc = {};
+        for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
         return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
-    uspmv_dmat *const parts[3] = {A, nullptr, nullptr};
     stamp_plan(parts, 256, used, (int64_t)cnt.max_col + 1, nt, staged, /*elem=*/true);
     *st = {true, nt, staged, total, used};
     return USPMV_OK;
 }
 
-// the device planner of one struct or an ap[dp_sp] pair: the plan at the rows per tile uspmv_dmat_optimize[_ap] chooses, then -- one
-// struct only -- its fallback to the plan over single x elements, then its sweep rule
+// The element fallback of the host planner for the parts of a split (ss[k] the host struct of parts[k]): the shared plan over single x
+// elements, built from the structs and installed on every part when elements_take_over takes it.  *elem: taken (the handles then carry it
+// and no sweep plan); otherwise the handles are as they were.
+int host_elements_take_over(uspmv_dmat *const parts[3], const uspmv_scs *const ss[3], bool own_budget, const PlanStats &line, bool allowed,
+                            int64_t *n_tiles, int64_t *n_staged, const char *who, bool *elem) {
+    *elem = false;
+    const int n = ss[2] ? 3 : 2;
+    int64_t n_elements = 0;
+    for (int k = 0; k < n; ++k) n_elements += ss[k]->n_elements;
+    uspmv_tlc_plan q;
+    if (int rc = elements_take_over(own_budget, line, allowed, parts[0]->dtype, n_elements,
+                                    [&](int cap, double *over) { *over = elements_over_cap_frac(ss, n, cap, 256); return USPMV_OK; },
+                                    [&](int cap, ElemStats *o) {
+                                        q = {};
+                                        const int rc2 = uspmv_build_tlc_plan(ss[0], ss[1], cap, 256, &q, /*line_shift=*/0, ss[2]);
+                                        *o = {q.valid, q.n_tiles, q.n_staged_tiles, (int64_t)q.tile_lines.size(), q.max_lines_used};
+                                        return rc2;
+                                    }, elem, n_tiles, n_staged))
+        return rc;
+    if (!*elem) return USPMV_OK;
+    if (int rc = install_host_plan(parts, q, /*elem=*/true, who)) { *elem = false; return rc; }
+    for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->sw = {};
+    return USPMV_OK;
+}
+
+// The element fallback of the device planner, for one struct and for the parts of a split alike: the line plan just built waits in
+// kept[] and comes back onto the handles unless the element plan is taken (also when the attempt fails).  *elem: taken.
+int device_elements_take_over(uspmv_dmat *const parts[3], uspmv_dmat::TlcPlan kept[3], bool own_budget, const PlanStats &line, bool allowed,
+                              int64_t *n_tiles, int64_t *n_staged, const char *who, bool *elem) {
+    ElemCounts cnt;
+    *elem = false;
+    int rc = elements_take_over(own_budget, line, allowed, parts[0]->dtype, sum_elements(parts),
+                                [&](int cap, double *over) {
+                                    const int r = device_elem_count(parts, cap, &cnt, who);
+                                    *over = sampled_over_cap_frac((int64_t)cnt.n.size(), [&](int64_t t) { return cnt.n[(size_t)t] > cap; });
+                                    return r;
+                                },
+                                [&](int, ElemStats *o) { return device_elem_install(parts, cnt, o, who); }, elem, n_tiles, n_staged);
+    if (!rc && *elem && !parts[1]) rc = tlc_pack12(parts[0], nullptr, who);
+    if (rc || !*elem)
+        for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = std::move(kept[k]);
+    if (!rc && *elem)
+        for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->sw = {};
+    return rc;
+}
+
+// the device planner of one struct or an ap[dp_sp] pair: the plan at the rows per tile uspmv_dmat_optimize[_ap] chooses, then its
+// fallback to the plan over single x elements (the pair: ap_elements_allowed), then its sweep rule
 int device_plan_install(uspmv_dmat *A, uspmv_dmat *B, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged, const char *who) {
     uspmv_dmat *const parts[3] = {A, B, nullptr};
     const int R_meas = opts.measure ? measured_tile_rows(A, B, line_budget(max_lines, A->dtype, B != nullptr), who) : 0;
-    uspmv_dmat::TlcPlan kept[2];
+    uspmv_dmat::TlcPlan kept[3];
     PlanStats st;
     const int rc = plan_at_chosen_rows(R_meas, B != nullptr, [&](int R, PlanStats *o) { return device_plan_install_rows(parts, max_lines, R, o, who); },
                                        [&]() { kept[0] = std::move(A->tlc); if (B) kept[1] = std::move(B->tlc); }, &st);
     if (n_tiles) *n_tiles = st.n_tiles;
     if (n_staged) *n_staged = st.n_staged;
     if (rc) return rc;
-    if (!B) {
-        // (the line plan waits in kept[0]: the handle gets it back unless the element plan is taken, also when the attempt fails)
-        ElemCounts cnt;
-        bool elem = false;
-        int rc2 = elements_take_over(max_lines > 0, st, opts.elements, A->dtype, A->n_elements,
-                                     [&](int cap, double *over) {
-                                         const int r = device_elem_count(A, cap, &cnt, who);
-                                         *over = sampled_over_cap_frac((int64_t)cnt.n.size(), [&](int64_t t) { return cnt.n[(size_t)t] > cap; });
-                                         return r;
-                                     },
-                                     [&](int, ElemStats *o) { return device_elem_install(A, cnt, o, who); }, &elem, n_tiles, n_staged);
-        if (!rc2 && elem) rc2 = tlc_pack12(A, nullptr, who);
-        if (rc2 || !elem) A->tlc = std::move(kept[0]);
-        if (rc2) return rc2;
-        if (elem) { A->sw = {}; return USPMV_OK; }
-    } else {
-        A->tlc = std::move(kept[0]);
-        B->tlc = std::move(kept[1]);
-    }
+    bool elem = false;
+    if (int rc2 = device_elements_take_over(parts, kept, max_lines > 0, st, B ? ap_elements_allowed(opts, A, B) : opts.elements,
+                                            n_tiles, n_staged, who, &elem))
+        return rc2;
+    if (elem) return USPMV_OK;
     bool swept = false;
     uspmv_dmat *const ms[2] = {A, B};
     if (int rc2 = sweep_takes_over(ms, nullptr, B ? 2 : 1, st, who, &swept)) return rc2;
@@ -597,6 +662,7 @@ int dmat_optimize_ap(uspmv_dmat *dp, uspmv_dmat *sp, const uspmv_scs *s_dp, cons
     if (int rc = require_device()) return rc;
     dp->tlc = {};
     sp->tlc = {};
+    const bool own_budget = max_lines > 0;                     // (as in uspmv_dmat_optimize: a caller's own line budget keeps the line plan)
     max_lines = line_budget(max_lines, USPMV_F64, true);
     uspmv_tlc_plan p;
     PlanStats st;
@@ -616,8 +682,11 @@ int dmat_optimize_ap(uspmv_dmat *dp, uspmv_dmat *sp, const uspmv_scs *s_dp, cons
         dp->sw = {}; sp->sw = {};
         return p.valid ? install_host_plan(parts, p, /*elem=*/false, who) : USPMV_OK;
     }
+    const uspmv_scs *const ss[3] = {s_dp, s_sp, nullptr};
+    bool elem = false;
+    if (int rc = host_elements_take_over(parts, ss, own_budget, st, ap_elements_allowed(opts, dp, sp), n_tiles, n_staged, who, &elem)) return rc;
+    if (elem) return USPMV_OK;
     bool swept = false;
-    const uspmv_scs *const ss[2] = {s_dp, s_sp};
     if (int rc = sweep_takes_over(parts, ss, 2, st, who, &swept)) return rc;
     if (swept || !p.valid) return USPMV_OK;
     return install_host_plan(parts, p, /*elem=*/false, who);
@@ -752,12 +821,17 @@ int dmat_optimize_ap_hp(uspmv_dmat *hi, uspmv_dmat *mid, uspmv_dmat *hp, const u
     for (uspmv_dmat_t *M : ms) if (M) { M->tlc = {}; M->sw = {}; }
     if (n_tiles) *n_tiles = 0;
     if (n_staged) *n_staged = 0;
+    const bool own_budget = max_lines > 0;
     uspmv_tlc_plan p;
     // (measure off: at the rows per tile of one struct, as in dmat_optimize_ap)
     if (int rc = uspmv_build_tlc_plan(ss[0], ss[1], line_budget(max_lines, hi->dtype, true), plan_tile_rows(opts.measure), &p, 4, ss[2])) return rc;
     if (n_tiles) *n_tiles = p.n_tiles;              // (the line plan's outcome also when the sweep takes over, as in uspmv_dmat_optimize_ap)
     if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
     if (!opts.measure) return p.valid ? install_host_plan(ms, p, /*elem=*/false, who) : USPMV_OK;
+    bool elem = false;
+    if (int rc = host_elements_take_over(ms, ss, own_budget, stats_of(p), ap_elements_allowed(opts, hi, hp), n_tiles, n_staged, who, &elem))
+        return rc;
+    if (elem) return USPMV_OK;
     bool swept = false;
     if (int rc = sweep_takes_over(ms, ss, mid ? 3 : 2, stats_of(p), who, &swept)) return rc;
     if (swept || !p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
@@ -906,6 +980,15 @@ int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_
     if (int rc = device_plan_install_rows(ms, max_lines, plan_tile_rows(true), &st, who)) return rc;
     if (n_tiles) *n_tiles = st.n_tiles;
     if (n_staged) *n_staged = st.n_staged;
+    {   // lines -> elements -> sweep, as the host planner
+        uspmv_dmat::TlcPlan kept[3];
+        for (int k = 0; k < 3; ++k) if (ms[k]) kept[k] = std::move(ms[k]->tlc);
+        bool elem = false;
+        if (int rc = device_elements_take_over(ms, kept, max_lines > 0, st, ap_elements_allowed(TlcPlanOpts{}, hi, hp),
+                                               n_tiles, n_staged, who, &elem))
+            return rc;
+        if (elem) return USPMV_OK;
+    }
     bool swept = false;
     if (int rc = sweep_takes_over(ms, nullptr, mid ? 3 : 2, st, who, &swept)) return rc;
     if (swept || !ap_hp_plan_worth(st.n_tiles, st.n_staged))

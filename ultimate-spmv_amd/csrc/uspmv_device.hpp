@@ -405,7 +405,9 @@ struct Tuning {
     int spmmv_list_plan = 0;   // NEXT optimize_block: also build the one-list-per-tile plan (variants 4 / 5 / 6) when the phased kernel can take the matrix
     int spmmv_idx8 = 1;        // NEXT optimize_block: one-byte phase-local indices when every phase lists <= 256 rows
     int tlc_elem = 1;        // NEXT uspmv_dmat_optimize[_device] (one struct): when the 16-element-line plan stages under nine tenths of the tiles, try the
-                             // plan over single x elements (each distinct column of a tile gathered once into LDS) before the column-window sweep; 2 = always try
+                             // plan over single x elements (each distinct column of a tile gathered once into LDS) before the column-window sweep; 2 = always try.
+                             // The parts of an ap split likewise, one shared plan (uspmv_dmat_optimize_ap[_hp] and their _device forms; an ap[dp_sp] pair under
+                             // 2^20 padded rows only under 2: tlc_planner.hip ap_elements_by_default)
     int tlc_elem_rows = 1;   // ... (host planner only) when the element plan over the caller's row order fails too: 1 = deal the rows to the tiles by the matrix graph first (private value copy + row map)
     int tlc_elem_seg_rows = 65536;  // ... rows of the segments the row dealing clusters independently (larger: numberings that scatter related rows further apart)
     int tlc_elem_cap = 4096; // ... most elements a tile may list (4096: 32 KiB of doubles, local indices still fit 12 bits)
@@ -606,9 +608,10 @@ int launch_plan_write(const uspmv_dmat *A, long n_tiles, const int *d_tile_line_
                       const unsigned *d_c16_ptrs3 = nullptr, unsigned short *d_col16_3 = nullptr);                         // plan_kernels.hip
 // the plan over single x elements on 256-row tiles: distinct columns per tile clipped at cap + 1 (cap <= 16384), then the sorted lists
 // and the slots' ranks; most_listed: the longest list of d_tile_line_ptr
-int launch_plan_count_elems(const uspmv_dmat *A, long n_tiles, int cap, int *d_n_elems, int *d_max_col, hipStream_t st);   // plan_kernels.hip
-int launch_plan_write_elems(const uspmv_dmat *A, long n_tiles, int most_listed, const int *d_tile_line_ptr, const unsigned *d_c16_ptrs,
-                            int *d_tile_lines, unsigned short *d_col16, hipStream_t st);                                    // plan_kernels.hip
+// the plan over single x elements of one struct or of the two or three parts of an ap split (parts[k] NULL from the first missing one on)
+int launch_plan_count_elems(const uspmv_dmat *const parts[3], long n_tiles, int cap, int *d_n_elems, int *d_max_col, hipStream_t st);   // plan_kernels.hip
+int launch_plan_write_elems(const uspmv_dmat *const parts[3], long n_tiles, int most_listed, const int *d_tile_line_ptr, int *d_tile_lines,
+                            const unsigned *const d_c16_ptrs[3], unsigned short *const d_col16[3], hipStream_t st);          // plan_kernels.hip
 int launch_rechunk32(const uspmv_dmat *A, const int *d_cp_new, int *d_ci_new, void *d_va_new, hipStream_t st);             // plan_kernels.hip
 int launch_block_values_gather(const uspmv_dmat *A, const int *d_row_map, const unsigned *d_c16_ptrs, void *d_out, bool group_major, hipStream_t st);   // plan_kernels.hip
 // device-side builder of the phased block plan (block_plan_kernels.hip)

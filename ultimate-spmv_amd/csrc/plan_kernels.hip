@@ -402,8 +402,8 @@ __global__ void __launch_bounds__(256) plan_pack12(const long n_chunks, const in
 
 namespace uspmv_dev {
 
-int launch_plan_count(const uspmv_dmat *A, long n_tiles, int max_lines, int *d_n_lines, int *d_max_col, hipStream_t st, const uspmv_dmat *A2, int tile_rows,
-                      const uspmv_dmat *A3) {
+int launch_plan_count(const uspmv_dmat *const parts[3], long n_tiles, int max_lines, int *d_n_lines, int *d_max_col, int tile_rows, hipStream_t st) {
+    const uspmv_dmat *A = parts[0], *A2 = parts[1], *A3 = parts[2];
     hipLaunchKernelGGL(plan_count_lines, dim3((unsigned)n_tiles), dim3(256), 0, st, (long)A->n_chunks, (int)A->C, A->chunk_ptrs,
                        A->chunk_lengths, A->col_idxs, max_lines, d_n_lines, d_max_col, A2 ? A2->chunk_ptrs : nullptr,
                        A2 ? A2->chunk_lengths : nullptr, A2 ? A2->col_idxs : nullptr, tile_rows / 256, A3 ? A3->chunk_ptrs : nullptr,
@@ -421,13 +421,13 @@ int launch_plan_pack12(const uspmv_dmat *A, const unsigned *d_c16_ptrs, const un
     return USPMV_OK;
 }
 
-int launch_plan_write(const uspmv_dmat *A, long n_tiles, const int *d_tile_line_ptr, const unsigned *d_c16_ptrs, int *d_tile_lines,
-                      unsigned short *d_col16, hipStream_t st, const uspmv_dmat *A2, const unsigned *d_c16_ptrs2, unsigned short *d_col16_2, int tile_rows,
-                      const uspmv_dmat *A3, const unsigned *d_c16_ptrs3, unsigned short *d_col16_3) {
+int launch_plan_write(const uspmv_dmat *const parts[3], long n_tiles, const int *d_tile_line_ptr, int *d_tile_lines, const unsigned *const d_c16_ptrs[3],
+                      unsigned short *const d_col16[3], int tile_rows, hipStream_t st) {
+    const uspmv_dmat *A = parts[0], *A2 = parts[1], *A3 = parts[2];
     hipLaunchKernelGGL(plan_write, dim3((unsigned)n_tiles), dim3(256), 0, st, (long)A->n_chunks, (int)A->C, A->chunk_ptrs,
-                       A->chunk_lengths, A->col_idxs, d_tile_line_ptr, d_c16_ptrs, d_tile_lines, d_col16, A2 ? A2->chunk_ptrs : nullptr,
-                       A2 ? A2->chunk_lengths : nullptr, A2 ? A2->col_idxs : nullptr, d_c16_ptrs2, d_col16_2, tile_rows / 256,
-                       A3 ? A3->chunk_ptrs : nullptr, A3 ? A3->chunk_lengths : nullptr, A3 ? A3->col_idxs : nullptr, d_c16_ptrs3, d_col16_3);
+                       A->chunk_lengths, A->col_idxs, d_tile_line_ptr, d_c16_ptrs[0], d_tile_lines, d_col16[0], A2 ? A2->chunk_ptrs : nullptr,
+                       A2 ? A2->chunk_lengths : nullptr, A2 ? A2->col_idxs : nullptr, d_c16_ptrs[1], d_col16[1], tile_rows / 256,
+                       A3 ? A3->chunk_ptrs : nullptr, A3 ? A3->chunk_lengths : nullptr, A3 ? A3->col_idxs : nullptr, d_c16_ptrs[2], d_col16[2]);
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }

@@ -1,8 +1,12 @@
 // The SpMV planner: uspmv_dmat_optimize and its variants (one struct, the ap[dp_sp] pair, the splits with an fp16 part; from a host
 // struct through host/tlc_plan.cpp or from the handle's device arrays through plan_kernels.hip).  Every decision between the plans
-// -- the line budget, the rows per tile, when the element plan or the column-window sweep takes over -- is written once here, so the host
-// and the device planner of one matrix cannot drift apart (tests/test_gpu_parity.py and tests/test_gpu_elem_plan_device.py compare their
-// plans array for array).  Host-only is the element plan on rows dealt to the tiles by the matrix graph.
+// -- the line budget, the rows per tile, when the element plan or the column-window sweep takes over -- is a predicate written once, and
+// so is their sequence: plan_parts runs lines -> elements -> sweep -> keep or drop for every entry.  What differs between the host and
+// the device planner is a source (HostSource, DeviceSource: how a candidate is built and reaches the handles), what differs between the
+// kinds a row of POLICY (PartsPolicy); the public entries are argument checks and one call.  tests/test_gpu_planner_routes.py pins every
+// entry's route and plan, tests/test_gpu_parity.py and tests/test_gpu_elem_plan_device.py compare the two planners array for array.
+// Outside the driver stays what only a single struct has: the internal C = 32 re-chunking, the 12-bit indices, the additive chunk records,
+// and (a hook of the host source, tried before the sweep) the element plan on rows dealt to the tiles by the matrix graph.
 #include "uspmv_device.hpp"
 
 #include <mutex>
@@ -51,27 +55,28 @@ bool rechunk_worth(int64_t new_elements, int64_t old_elements) {
     return (double)new_elements <= 1.25 * (double)std::max<int64_t>(old_elements, 1) + 4096;
 }
 
-// what a plan built at some rows per tile turned out to be
+// what a plan candidate (over lines at some rows per tile, or over single x elements) turned out to be
 struct PlanStats {
     bool valid = false;
     int64_t n_tiles = 0, n_staged = 0;
-    int lines = 0;                       // of the fullest tile
+    int lines = 0;                       // list entries of the fullest tile
+    int64_t listed = 0;                  // ... of all lists together
 };
-PlanStats stats_of(const uspmv_tlc_plan &p) { return {p.valid, p.n_tiles, p.n_staged_tiles, p.max_lines_used}; }
+PlanStats stats_of(const uspmv_tlc_plan &p) { return {p.valid, p.n_tiles, p.n_staged_tiles, p.max_lines_used, (int64_t)p.tile_lines.size()}; }
 
-// The rows per tile, for the host and the device planner alike: the measured verdict when there is one, else the default by kind, else --
-// when tile_rows_grow asks for it -- the first of 1024 and 512 rows that tile_rows_accept takes.  build(R, &stats) builds a candidate at R
-// rows, keep() makes the last candidate the plan; *st describes the plan kept.
-template <typename Build, typename Keep>
-int plan_at_chosen_rows(int R_meas, bool ap, Build build, Keep keep, PlanStats *st) {
-    const int R0 = R_meas ? R_meas : plan_tile_rows(ap);
-    if (int rc = build(R0, st)) return rc;
-    keep();
-    if (R_meas || !st->valid || !tile_rows_grow(R0, st->lines)) return USPMV_OK;
+// The rows per tile, for the host and the device planner alike: the measured verdict when there is one, else R0 (the default by kind),
+// else -- where the kind grows its tiles and tile_rows_grow asks for it -- the first of 1024 and 512 rows that tile_rows_accept takes.
+// src.line(R, &stats) builds a candidate at R rows, src.keep() makes the last candidate the plan; *st describes the plan kept.
+template <typename Source>
+int plan_at_chosen_rows(int R_meas, int R0, bool grow, Source &src, PlanStats *st) {
+    if (R_meas) R0 = R_meas;
+    if (int rc = src.line(R0, st)) return rc;
+    src.keep();
+    if (R_meas || !grow || !st->valid || !tile_rows_grow(R0, st->lines)) return USPMV_OK;
     for (int R : {1024, 512}) {
         PlanStats q;
-        if (int rc = build(R, &q)) return rc;
-        if (q.valid && tile_rows_accept(q.n_tiles, q.n_staged)) { keep(); *st = q; break; }
+        if (int rc = src.line(R, &q)) return rc;
+        if (q.valid && tile_rows_accept(q.n_tiles, q.n_staged)) { src.keep(); *st = q; break; }
     }
     return USPMV_OK;
 }
@@ -235,70 +240,106 @@ int tlc_additive_install(uspmv_dmat *A, const uspmv_scs *s, const uspmv_tlc_plan
     return USPMV_OK;
 }
 
-// The tile-local-column plan of parts[0] at R rows per tile, built on the device; parts[1] (the sp part of an ap pair, or the hp part of a
-// two-part split) and parts[2] (the hp part of ap[dp_sp_hp]; only with parts[1]) share its line list.  No plan (and USPMV_OK) for shapes
-// without one, arrays beyond 32-bit offsets and matrices of which no tile stages.
-int device_plan_install_rows(uspmv_dmat *const parts[3], int max_lines, const int R, PlanStats *st, const char *who) {
-    uspmv_dmat *const A = parts[0], *const B = parts[1], *const B3 = parts[2];
-    for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
-    *st = {};
-    const int64_t C = A->C, nc = A->n_chunks;
-    if (C > 256 || 256 % C != 0 || nc < 1) return USPMV_OK;                    // shape without a plan
-    max_lines = line_budget(max_lines, A->dtype, B != nullptr);
-    const int64_t T = R / C, nt = (nc + T - 1) / T;
-    std::vector<int32_t> cl((size_t)nc);
-    std::vector<uint32_t> c16p[3];
-    int64_t tot16[3] = {0, 0, 0};
-    for (int k = 0; k < 3; ++k) {                                               // (a single struct: cl keeps its lengths for tlc_pack12)
-        if (!parts[k]) continue;
-        HIP_TRY(hipMemcpy(cl.data(), parts[k]->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
-        if (!c16_offsets(cl, C, &c16p[k], &tot16[k])) return USPMV_OK;
-    }
+// The shape shared by the device-built plans: 256 % C == 0 and at least one chunk; *nt: tiles of R rows
+bool device_plan_shape(const uspmv_dmat *A, int R, int64_t *nt) {
+    if (A->C > 256 || 256 % A->C != 0 || A->n_chunks < 1) return false;
+    const int64_t T = R / A->C;
+    *nt = (A->n_chunks + T - 1) / T;
+    return true;
+}
+
+// The count pass of a device-built plan: per tile the list entries all parts together need (0: the tile gathers), and the largest column.
+// count(d_n, d_max) launches it; O(n_tiles) comes back to the host.
+struct TileCounts {
+    int max_col = 0;
+    std::vector<int32_t> n;
+};
+template <typename Count>
+int device_tile_counts(int64_t nt, Count count, TileCounts *o, const char *who) {
+    *o = {};
     DeviceBuf<int> d_n, d_max;
     hipError_t e = d_n.alloc(4 * (size_t)nt);
     if (e == hipSuccess) e = d_max.zeros(4);
     if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-    int rc = launch_plan_count(A, (long)nt, max_lines, d_n, d_max, nullptr, B, R, B3);
+    if (int rc = count(d_n, d_max)) return rc;
+    o->n.resize((size_t)nt);
+    e = hipMemcpy(o->n.data(), d_n, 4 * (size_t)nt, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&o->max_col, d_max, 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { o->n.clear(); return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
+    return USPMV_OK;
+}
+
+// The install both device-built plans end in, on handles without a plan: the prefix sum over the tiles' counts and its INT32 guard, the
+// offsets of every part's local indices (c16_offsets: 32-bit as well), owned buffers -- the list with the first part, every part its own
+// local indices, padded slots index 0 --, the write pass write(d_c16_ptrs, d_col16), stamp_plan.  O(n_chunks) + O(n_tiles) on the host.
+// No plan (and USPMV_OK) beyond 32-bit offsets and when no tile stages; on a failure the handles have none either.  *cl: the chunk
+// lengths of the last part (a single struct: what tlc_pack12 takes).
+template <typename Write>
+int device_install_tail(uspmv_dmat *const parts[3], const TileCounts &cnt, int cap, int tile_rows, bool elem, Write write, PlanStats *st,
+                        std::vector<int32_t> *cl, const char *who) {
+    uspmv_dmat *const A = parts[0];
+    *st = {};
+    const int64_t nc = A->n_chunks, nt = (int64_t)cnt.n.size();
     std::vector<int32_t> lp((size_t)nt + 1, 0);
-    int max_col = 0;
-    if (!rc) {
-        e = hipMemcpy(lp.data() + 1, d_n, 4 * (size_t)nt, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(&max_col, d_max, 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    d_n.reset(); d_max.reset();
-    if (rc) return rc;
     int64_t staged = 0, total = 0;
     int used = 0;
     for (int64_t t = 0; t < nt; ++t) {
-        const int n = lp[(size_t)t + 1];
+        const int n = cnt.n[(size_t)t] <= cap ? cnt.n[(size_t)t] : 0;         // over the cap: the tile gathers
         staged += n > 0; used = std::max(used, n);
         total += n;
         if (total > INT32_MAX) return USPMV_OK;
         lp[(size_t)t + 1] = (int32_t)total;
     }
+    std::vector<uint32_t> c16p[3];
+    int64_t tot16[3] = {0, 0, 0};
+    cl->resize((size_t)nc);
+    for (int k = 0; k < 3; ++k) {
+        if (!parts[k]) continue;
+        HIP_TRY(hipMemcpy(cl->data(), parts[k]->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
+        if (!c16_offsets(*cl, A->C, &c16p[k], &tot16[k])) return USPMV_OK;
+    }
     st->n_tiles = nt; st->n_staged = staged;
     if (staged == 0) return USPMV_OK;
-    e = A->tlc.line_ptr.upload(lp.data(), 4 * ((size_t)nt + 1));
+    hipError_t e = A->tlc.line_ptr.upload(lp.data(), 4 * ((size_t)nt + 1));
     if (e == hipSuccess) e = A->tlc.lines.alloc(4 * (size_t)std::max<int64_t>(total, 1));
+    const unsigned *d_c16p[3] = {nullptr, nullptr, nullptr};
+    unsigned short *d_c16[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < 3; ++k) {
         if (!parts[k]) continue;
         if (e == hipSuccess) e = parts[k]->tlc.c16_ptrs.upload(c16p[k].data(), 4 * ((size_t)nc + 1));
-        if (e == hipSuccess) e = parts[k]->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16[k], 1));   // padded slots: index 0
+        if (e == hipSuccess) e = parts[k]->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16[k], 1));
+        d_c16p[k] = parts[k]->tlc.c16_ptrs; d_c16[k] = parts[k]->tlc.col16;
     }
-    if (e == hipSuccess && launch_plan_write(A, (long)nt, A->tlc.line_ptr, A->tlc.c16_ptrs, A->tlc.lines, A->tlc.col16, nullptr, B,
-                                             B ? B->tlc.c16_ptrs : nullptr, B ? B->tlc.col16 : nullptr, R, B3,
-                                             B3 ? B3->tlc.c16_ptrs : nullptr, B3 ? B3->tlc.col16 : nullptr) != USPMV_OK)
-        e = hipErrorUnknown;
+    if (e == hipSuccess && write(used, d_c16p, d_c16) != USPMV_OK) e = hipErrorUnknown;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
         for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
         return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
-    stamp_plan(parts, R, used, (int64_t)max_col + 1, nt, staged, /*elem=*/false);
-    st->valid = true; st->lines = used;
-    if (!B) return tlc_pack12(A, &cl, who);
+    stamp_plan(parts, tile_rows, used, (int64_t)cnt.max_col + 1, nt, staged, elem);
+    *st = {true, nt, staged, used, total};
     return USPMV_OK;
+}
+
+// The tile-local-column plan of parts[0] at R rows per tile, built on the device; parts[1] (the sp part of an ap pair, or the hp part of a
+// two-part split) and parts[2] (the hp part of ap[dp_sp_hp]; only with parts[1]) share its line list.  No plan (and USPMV_OK) for shapes
+// without one and where device_install_tail has none.  A single struct gets its 12-bit indices at once (measured_tile_rows times them).
+// budget: lines a tile may list (line_budget).
+int device_plan_install_rows(uspmv_dmat *const parts[3], int budget, const int R, PlanStats *st, const char *who) {
+    uspmv_dmat *const A = parts[0];
+    for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
+    *st = {};
+    int64_t nt = 0;
+    if (!device_plan_shape(A, R, &nt)) return USPMV_OK;
+    TileCounts cnt;                                                            // (a tile over the budget counts 0 lines)
+    if (int rc = device_tile_counts(nt, [&](int *d_n, int *d_max) { return launch_plan_count(parts, (long)nt, budget, d_n, d_max, R, nullptr); }, &cnt, who))
+        return rc;
+    std::vector<int32_t> cl;
+    if (int rc = device_install_tail(parts, cnt, INT32_MAX, R, /*elem=*/false, [&](int, const unsigned *const c16p[3], unsigned short *const c16[3]) {
+            return launch_plan_write(parts, (long)nt, A->tlc.line_ptr, A->tlc.lines, c16p, c16, R, nullptr);
+        }, st, &cl, who))
+        return rc;
+    return st->valid && !parts[1] ? tlc_pack12(A, &cl, who) : USPMV_OK;
 }
 
 // For LARGE single structs the rows per tile are MEASURED (tuning tlc_measure_tile, default on; only when tlc_tile_rows is 0): the plan
@@ -307,7 +348,8 @@ int device_plan_install_rows(uspmv_dmat *const parts[3], int max_lines, const in
 // neighbouring tiles lie -- the 27-point stencil on 253^3 is fastest at 256 rows, the same stencil on 304^3 (planes of 739 instead of
 // 512 KB: more of the x lines miss the XCD's L2) at 512 (1.249 against 1.341 ms, profiles/r03/tile_rows_sweep.txt).  The choice is
 // remembered per (shape, size) for the life of the process, so the host and the device planner of one matrix agree.  0 = no opinion.
-int measured_tile_rows(uspmv_dmat *A, uspmv_dmat *B, int max_lines, const char *who) {
+int measured_tile_rows(uspmv_dmat *const parts[3], int max_lines, const char *who) {
+    uspmv_dmat *const A = parts[0], *const B = parts[1];
     // one measurement at a time, and the verdict table only read / written under the lock (the verdict is keyed on the struct's shape and
     // size, not its content: two matrices with equal counts share it -- the price of host and device planner of ONE matrix agreeing)
     static std::mutex mtx;
@@ -339,7 +381,6 @@ int measured_tile_rows(uspmv_dmat *A, uspmv_dmat *B, int max_lines, const char *
     const int order[4] = {base, base == 256 ? 512 : 256, 1024, base};
     float tmin[3] = {0, 0, 0};                                  // best time seen for 256 / 512 / 1024 rows (0: not usable)
     auto slot_of = [](int R) { return R == 256 ? 0 : R == 512 ? 1 : 2; };
-    uspmv_dmat *const parts[3] = {A, B, nullptr};
     for (int k = 0; k < 4; ++k) {
         const int R = order[k], slot = slot_of(R), bs = slot_of(base);
         if (k == 3) {                                           // re-check the base only when something is about to beat it
@@ -418,13 +459,6 @@ int element_cap(int dtype) { return std::min(g_tune.tlc_elem_cap, (int)(64 * 102
 bool elements_pay(int64_t listed, int64_t n_elements) { return (double)listed * 4.0 <= (double)n_elements; }
 bool line_plan_short(bool own_budget, const PlanStats &line) { return !own_budget && (!line.valid || !stages_nine_tenths(line.n_tiles, line.n_staged)); }
 
-// what an element plan candidate turned out to be
-struct ElemStats {
-    bool valid = false;
-    int64_t n_tiles = 0, n_staged = 0, listed = 0;     // listed: elements of all lists together
-    int most = 0;                                      // of the fullest tile
-};
-
 // The fallback from the line plan to the plan over single x elements on the caller's row order, for the host and the device planner alike.
 // Columns scattered over many lines (x in a numbering that is only loosely related to the rows'): the line plan leaves a tenth of the tiles
 // or more to the gather path.  List the tile's distinct ELEMENTS instead -- taken when (nearly) every tile fits and an element serves
@@ -433,25 +467,25 @@ struct ElemStats {
 // 0.97 / 0.90 / 0.89 of the roofline against 0.74 (line plan, 69 % of the tiles staged) / 0.70 / 0.61 (sweep); 1 dof, 4.2 entries per
 // element: 0.65 against 0.59; on a regular numbering the line plan is 20 % ahead (0.683 against 0.819 ms on the 253^3 stencil), which is
 // why this is a fallback only ("tlc_elem" 2, a measurement aid, always tries).
-// sample(cap, &frac): the share of the sampled tiles over the cap; build(cap, &stats): the candidate, in full (a sort per tile) -- the
-// caller keeps it when *took, and the call then reports the element plan's tiles.
-template <typename Sample, typename Build>
-int elements_take_over(bool own_budget, const PlanStats &line, bool allowed, int dtype, int64_t n_elements, Sample sample, Build build, bool *took,
+// src.sample(cap, &frac): the share of the sampled tiles over the cap; src.elements(cap, &stats): the candidate, in full (a sort per
+// tile) -- the caller installs it when *took, and the call then reports the element plan's tiles.
+template <typename Source>
+int elements_take_over(bool own_budget, const PlanStats &line, bool allowed, int dtype, int64_t n_elements, Source &src, bool *took,
                        int64_t *n_tiles, int64_t *n_staged) {
     *took = false;
     if (!(line_plan_short(own_budget, line) || g_tune.tlc_elem == 2) || !g_tune.tlc_elem || !allowed) return USPMV_OK;
     const int ecap = element_cap(dtype);
     double over = 1.0;
-    if (int rc = sample(ecap, &over)) return rc;
+    if (int rc = src.sample(ecap, &over)) return rc;
     if (over > 0.1) return USPMV_OK;                   // would be turned down anyway (wide irregular rows: the sweep's matrices)
-    ElemStats e;
-    if (int rc = build(ecap, &e)) return rc;
+    PlanStats e;
+    if (int rc = src.elements(ecap, &e)) return rc;
     if (!e.valid || !tile_rows_accept(e.n_tiles, e.n_staged) || !(elements_pay(e.listed, n_elements) || g_tune.tlc_elem == 2)) return USPMV_OK;
     *took = true;
     if (n_tiles) *n_tiles = e.n_tiles;
     if (n_staged) *n_staged = e.n_staged;
     if (verbose()) fprintf(stderr, "[uspmv] tlc plan over single x elements: tiles=%lld staged=%lld max_elements=%d elements_total=%lld (%.1f entries per element)\n",
-                           (long long)e.n_tiles, (long long)e.n_staged, e.most, (long long)e.listed, (double)n_elements / (double)std::max<int64_t>(e.listed, 1));
+                           (long long)e.n_tiles, (long long)e.n_staged, e.lines, (long long)e.listed, (double)n_elements / (double)std::max<int64_t>(e.listed, 1));
     return USPMV_OK;
 }
 
@@ -473,151 +507,193 @@ int64_t sum_elements(uspmv_dmat *const parts[3]) {
 }
 
 // The element plan's count pass on the device (plan_kernels.hip): per 256-row tile the distinct columns -- of all parts together --
-// clipped at cap + 1, and the largest column.  O(n_tiles) comes back to the host.  Shapes without a plan: no tiles.
-struct ElemCounts {
-    int cap = 0, max_col = 0;
-    std::vector<int32_t> n;
-};
-int device_elem_count(uspmv_dmat *const parts[3], int cap, ElemCounts *o, const char *who) {
+// clipped at cap + 1, and the largest column.  Shapes without a plan: no tiles.
+int device_elem_count(uspmv_dmat *const parts[3], int cap, TileCounts *o, const char *who) {
     *o = {};
-    o->cap = cap;
-    const uspmv_dmat *A = parts[0];
-    const int64_t C = A->C, nc = A->n_chunks;
-    if (C > 256 || 256 % C != 0 || nc < 1) return USPMV_OK;
-    const int64_t T = 256 / C, nt = (nc + T - 1) / T;
-    DeviceBuf<int> d_n, d_max;
-    hipError_t e = d_n.alloc(4 * (size_t)nt);
-    if (e == hipSuccess) e = d_max.zeros(4);
-    if (e != hipSuccess) return uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-    if (int rc = launch_plan_count_elems(parts, (long)nt, cap, d_n, d_max, nullptr)) return rc;
-    o->n.resize((size_t)nt);
-    e = hipMemcpy(o->n.data(), d_n, 4 * (size_t)nt, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&o->max_col, d_max, 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { o->n.clear(); return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
-    return USPMV_OK;
+    int64_t nt = 0;
+    if (!device_plan_shape(parts[0], 256, &nt)) return USPMV_OK;
+    return device_tile_counts(nt, [&](int *d_n, int *d_max) { return launch_plan_count_elems(parts, (long)nt, cap, d_n, d_max, nullptr); }, o, who);
 }
 
-// ... and its write pass, installed on the (plan-less) handles as device_plan_install_rows installs the line plan: owned buffers, the
-// element list with the first part, every part its own local indices, O(n_chunks) + O(n_tiles) on the host.  No plan (and USPMV_OK) for
-// arrays beyond 32-bit offsets and when no tile stages; on a failure the handles have none either.
-int device_elem_install(uspmv_dmat *const parts[3], const ElemCounts &cnt, ElemStats *st, const char *who) {
-    uspmv_dmat *const A = parts[0];
+// ... and its write pass, installed on the (plan-less) handles as device_plan_install_rows installs the line plan (device_install_tail)
+int device_elem_install(uspmv_dmat *const parts[3], const TileCounts &cnt, int cap, PlanStats *st, std::vector<int32_t> *cl, const char *who) {
     for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
     *st = {};
-    const int64_t C = A->C, nc = A->n_chunks, nt = (int64_t)cnt.n.size();
-    if (nt == 0) return USPMV_OK;
-    std::vector<int32_t> lp((size_t)nt + 1, 0);
-    int64_t staged = 0, total = 0;
-    int used = 0;
-    for (int64_t t = 0; t < nt; ++t) {
-        const int n = cnt.n[(size_t)t] <= cnt.cap ? cnt.n[(size_t)t] : 0;     // over the cap: the tile gathers
-        staged += n > 0; used = std::max(used, n);
-        total += n;
-        if (total > INT32_MAX) return USPMV_OK;
-        lp[(size_t)t + 1] = (int32_t)total;
-    }
-    st->n_tiles = nt; st->n_staged = staged;
-    if (staged == 0) return USPMV_OK;
-    std::vector<int32_t> cl((size_t)nc);
-    std::vector<uint32_t> c16p[3];
-    int64_t tot16[3] = {0, 0, 0};
-    for (int k = 0; k < 3; ++k) {
-        if (!parts[k]) continue;
-        HIP_TRY(hipMemcpy(cl.data(), parts[k]->chunk_lengths, 4 * (size_t)nc, hipMemcpyDeviceToHost));
-        if (!c16_offsets(cl, C, &c16p[k], &tot16[k])) return USPMV_OK;
-    }
-    hipError_t e = A->tlc.line_ptr.upload(lp.data(), 4 * ((size_t)nt + 1));
-    if (e == hipSuccess) e = A->tlc.lines.alloc(4 * (size_t)std::max<int64_t>(total, 1));
-    const unsigned *d_c16p[3] = {nullptr, nullptr, nullptr};
-    unsigned short *d_c16[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < 3; ++k) {
-        if (!parts[k]) continue;
-        if (e == hipSuccess) e = parts[k]->tlc.c16_ptrs.upload(c16p[k].data(), 4 * ((size_t)nc + 1));
-        if (e == hipSuccess) e = parts[k]->tlc.col16.zeros(2 * (size_t)std::max<int64_t>(tot16[k], 1));
-        d_c16p[k] = parts[k]->tlc.c16_ptrs; d_c16[k] = parts[k]->tlc.col16;
-    }
-    if (e == hipSuccess && launch_plan_write_elems(parts, (long)nt, used, A->tlc.line_ptr, A->tlc.lines, d_c16p, d_c16, nullptr) != USPMV_OK) e = hipErrorUnknown;
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = {};
-        return uspmv::fail(USPMV_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    stamp_plan(parts, 256, used, (int64_t)cnt.max_col + 1, nt, staged, /*elem=*/true);
-    *st = {true, nt, staged, total, used};
-    return USPMV_OK;
+    if (cnt.n.empty()) return USPMV_OK;
+    return device_install_tail(parts, cnt, cap, 256, /*elem=*/true, [&](int most, const unsigned *const c16p[3], unsigned short *const c16[3]) {
+        return launch_plan_write_elems(parts, (long)cnt.n.size(), most, parts[0]->tlc.line_ptr, parts[0]->tlc.lines, c16p, c16, nullptr);
+    }, st, cl, who);
 }
 
-// The element fallback of the host planner for the parts of a split (ss[k] the host struct of parts[k]): the shared plan over single x
-// elements, built from the structs and installed on every part when elements_take_over takes it.  *elem: taken (the handles then carry it
-// and no sweep plan); otherwise the handles are as they were.
-int host_elements_take_over(uspmv_dmat *const parts[3], const uspmv_scs *const ss[3], bool own_budget, const PlanStats &line, bool allowed,
-                            int64_t *n_tiles, int64_t *n_staged, const char *who, bool *elem) {
-    *elem = false;
-    const int n = ss[2] ? 3 : 2;
-    int64_t n_elements = 0;
-    for (int k = 0; k < n; ++k) n_elements += ss[k]->n_elements;
-    uspmv_tlc_plan q;
-    if (int rc = elements_take_over(own_budget, line, allowed, parts[0]->dtype, n_elements,
-                                    [&](int cap, double *over) { *over = elements_over_cap_frac(ss, n, cap, 256); return USPMV_OK; },
-                                    [&](int cap, ElemStats *o) {
-                                        q = {};
-                                        const int rc2 = uspmv_build_tlc_plan(ss[0], ss[1], cap, 256, &q, /*line_shift=*/0, ss[2]);
-                                        *o = {q.valid, q.n_tiles, q.n_staged_tiles, (int64_t)q.tile_lines.size(), q.max_lines_used};
-                                        return rc2;
-                                    }, elem, n_tiles, n_staged))
+// ---- The two sources of a plan: what differs between the host and the device planner, and nothing else.  plan_parts below drives either:
+//   line(R, &stats)        a line-plan candidate at R rows per tile (budget: the lines a tile may list)
+//   keep()                 the last candidate is the line plan to keep
+//   sample(cap, &frac)     the share of the sampled 256-row tiles that list more than cap elements
+//   elements(cap, &stats)  the candidate over single x elements, in full
+//   install_elements()     ... onto the handles; on a failure they carry no plan
+//   dealt_rows(...)        a further element plan only this source has, tried before the sweep
+//   install_line()         the kept line plan onto the handles
+//   structs()              what sweep_takes_over builds from (nullptr: the handles' device arrays)
+
+// The host structs of the parts (ss[k] the struct of parts[k]), through host/tlc_plan.cpp: candidates are host copies, and only the plan
+// that is kept reaches the handles.
+struct HostSource {
+    uspmv_dmat *const *parts;
+    const uspmv_scs *const *ss;
+    const char *who;
+    bool deal_rows = false;              // dmat_optimize: one struct, TlcPlanOpts::deal_rows
+    int budget = 0;
+    uspmv_tlc_plan p, q;                 // the plan kept, the last candidate
+    uspmv_scs rr;                        // the struct on rows dealt to the tiles by the matrix graph, and its row map
+    std::vector<int32_t> rr_map;
+    bool dealt = false;
+
+    int n() const { return ss[2] ? 3 : ss[1] ? 2 : 1; }
+    int line(int R, PlanStats *o) {
+        q = {};
+        const int rc = uspmv_build_tlc_plan(ss[0], ss[1], budget, R, &q, /*line_shift=*/4, ss[2]);
+        *o = stats_of(q);
         return rc;
-    if (!*elem) return USPMV_OK;
-    if (int rc = install_host_plan(parts, q, /*elem=*/true, who)) { *elem = false; return rc; }
-    for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->sw = {};
-    return USPMV_OK;
-}
-
-// The element fallback of the device planner, for one struct and for the parts of a split alike: the line plan just built waits in
-// kept[] and comes back onto the handles unless the element plan is taken (also when the attempt fails).  *elem: taken.
-int device_elements_take_over(uspmv_dmat *const parts[3], uspmv_dmat::TlcPlan kept[3], bool own_budget, const PlanStats &line, bool allowed,
-                              int64_t *n_tiles, int64_t *n_staged, const char *who, bool *elem) {
-    ElemCounts cnt;
-    *elem = false;
-    int rc = elements_take_over(own_budget, line, allowed, parts[0]->dtype, sum_elements(parts),
-                                [&](int cap, double *over) {
-                                    const int r = device_elem_count(parts, cap, &cnt, who);
-                                    *over = sampled_over_cap_frac((int64_t)cnt.n.size(), [&](int64_t t) { return cnt.n[(size_t)t] > cap; });
-                                    return r;
-                                },
-                                [&](int, ElemStats *o) { return device_elem_install(parts, cnt, o, who); }, elem, n_tiles, n_staged);
-    if (!rc && *elem && !parts[1]) rc = tlc_pack12(parts[0], nullptr, who);
-    if (rc || !*elem)
-        for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = std::move(kept[k]);
-    if (!rc && *elem)
-        for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->sw = {};
-    return rc;
-}
-
-// the device planner of one struct or an ap[dp_sp] pair: the plan at the rows per tile uspmv_dmat_optimize[_ap] chooses, then its
-// fallback to the plan over single x elements (the pair: ap_elements_allowed), then its sweep rule
-int device_plan_install(uspmv_dmat *A, uspmv_dmat *B, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged, const char *who) {
-    uspmv_dmat *const parts[3] = {A, B, nullptr};
-    const int R_meas = opts.measure ? measured_tile_rows(A, B, line_budget(max_lines, A->dtype, B != nullptr), who) : 0;
-    uspmv_dmat::TlcPlan kept[3];
-    PlanStats st;
-    const int rc = plan_at_chosen_rows(R_meas, B != nullptr, [&](int R, PlanStats *o) { return device_plan_install_rows(parts, max_lines, R, o, who); },
-                                       [&]() { kept[0] = std::move(A->tlc); if (B) kept[1] = std::move(B->tlc); }, &st);
-    if (n_tiles) *n_tiles = st.n_tiles;
-    if (n_staged) *n_staged = st.n_staged;
-    if (rc) return rc;
-    bool elem = false;
-    if (int rc2 = device_elements_take_over(parts, kept, max_lines > 0, st, B ? ap_elements_allowed(opts, A, B) : opts.elements,
-                                            n_tiles, n_staged, who, &elem))
-        return rc2;
-    if (elem) return USPMV_OK;
-    bool swept = false;
-    uspmv_dmat *const ms[2] = {A, B};
-    if (int rc2 = sweep_takes_over(ms, nullptr, B ? 2 : 1, st, who, &swept)) return rc2;
-    if (swept) {             // (n_tiles / n_staged keep describing the tile-local-column attempt, as in uspmv_dmat_optimize;
-        A->tlc = {};         //  uspmv_dmat_plan_info tells which plan the handle ended up with)
-        if (B) B->tlc = {};
     }
+    void keep() { p = std::move(q); }
+    int sample(int cap, double *over) { *over = elements_over_cap_frac(ss, n(), cap, 256); return USPMV_OK; }
+    int elements(int cap, PlanStats *o) {
+        q = {};
+        const int rc = uspmv_build_tlc_plan(ss[0], ss[1], cap, 256, &q, /*line_shift=*/0, ss[2]);
+        *o = stats_of(q);
+        return rc;
+    }
+    int install_elements() { p = std::move(q); return install_host_plan(parts, p, /*elem=*/true, who); }
+    int install_line() { return install_host_plan(parts, p, /*elem=*/false, who); }
+    const uspmv_scs *const *structs() const { return ss; }
+
+    // When the ROWS of a tile are scattered as well (rows and columns renumbered alike: a tile of 256 consecutive rows is no compact piece of the
+    // mesh any more): deal the rows to the tiles by the matrix graph first, as the block plan does (uspmv_scs_reorder_rows mode 4: rows change places
+    // only with rows of equal-length chunks, every row keeps its slot sequence), then the element plan on that order -- a private copy of the values
+    // (8 / 4 bytes per element of HBM), of the column indices (for the few tiles that do not stage) and a row map for y.
+    int dealt_rows(bool own_budget, const PlanStats &line, bool *took, int64_t *n_tiles, int64_t *n_staged) {
+        const uspmv_scs *s = ss[0];
+        if (!deal_rows || !line_plan_short(own_budget, line) || !g_tune.tlc_elem || !g_tune.tlc_elem_rows || s->n_rows != s->n_cols) return USPMV_OK;
+        // first with the clusters confined to segments of tlc_elem_seg_rows rows (64 Ki: many segments in parallel, and a trial on a sample of them that stops
+        // irregular matrices early); when that leaves some, but not most, of the sampled tiles over the cap -- related rows further apart than a segment --
+        // once more with segments of 2^20 rows (a second or more of clustering per million rows on few threads: only where it looks promising)
+        const int ecap = element_cap(s->dtype);
+        const int64_t seg_stage[2] = {(int64_t)g_tune.tlc_elem_seg_rows, (int64_t)1 << 20};
+        for (int stage = 0; stage < 2 && !dealt; ++stage) {
+            if (stage == 1 && seg_stage[1] <= seg_stage[0]) break;
+            if (uspmv_scs_reorder_rows(s, g_tune.tlc_elem_rows == 4 ? 4 : 2, &rr, &rr_map, g_tune.tlc_elem_rows == 4 ? 64 : 256, seg_stage[stage]) != 1) break;
+            const double over = elements_over_cap_frac(&rr, ecap, 256);
+            q = {};
+            if (over <= 0.1)
+                if (int rc = uspmv_build_tlc_plan(&rr, nullptr, ecap, 256, &q, /*line_shift=*/0)) return rc;
+            if (verbose()) fprintf(stderr, "[uspmv] element plan on the graph-dealt rows (segments of %lld rows): %.0f %% of the sampled tiles over the cap; valid=%d tiles=%lld staged=%lld max_elements=%d (cap %d) elements_total=%zu\n",
+                                   (long long)seg_stage[stage], 100.0 * over, (int)q.valid, (long long)q.n_tiles, (long long)q.n_staged_tiles, q.max_lines_used, ecap, q.tile_lines.size());
+            // (19 of 20 tiles staged is enough here: what would run instead -- sweep or gather kernel -- is 2 x slower on such matrices)
+            if (q.valid && stages_19_of_20(q.n_tiles, q.n_staged_tiles) && elements_pay((int64_t)q.tile_lines.size(), s->n_elements)) dealt = true;
+            else if (over > 0.6) break;                      // most tiles far over the cap: larger segments will not repair that
+        }
+        if (!dealt) return USPMV_OK;
+        if (int rc = install_elements()) return rc;
+        if (verbose()) fprintf(stderr, "[uspmv] tlc plan over single x elements, rows dealt to the tiles by the matrix graph: tiles=%lld max_elements=%d elements_total=%zu (%.1f entries per element)\n",
+                               (long long)p.n_tiles, p.max_lines_used, p.tile_lines.size(), (double)s->n_elements / (double)std::max<size_t>(p.tile_lines.size(), 1));
+        auto &t = parts[0]->tlc;
+        hipError_t e = t.values.upload(rr.values_ptr(), (size_t)rr.n_elements * (rr.dtype == USPMV_F64 ? 8 : 4));
+        if (e == hipSuccess) e = t.row_map.upload(rr_map.data(), rr_map.size() * 4);
+        if (e == hipSuccess && p.n_staged_tiles < p.n_tiles) e = t.cols.upload(rr.col_idxs.data(), (size_t)rr.n_elements * 4);
+        if (e != hipSuccess) {
+            t = {};
+            return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
+        }
+        *took = true;
+        if (n_tiles) *n_tiles = p.n_tiles;
+        if (n_staged) *n_staged = p.n_staged_tiles;
+        return USPMV_OK;
+    }
+};
+
+// The handles' own device arrays, through plan_kernels.hip: every candidate is built on the handles; the line plan to keep waits in kept[]
+// while the element plan is tried, and a failed element attempt puts it back.
+struct DeviceSource {
+    uspmv_dmat *const *parts;
+    const char *who;
+    int budget = 0;
+    uspmv_dmat::TlcPlan kept[3];
+    TileCounts cnt;
+    std::vector<int32_t> cl;             // chunk lengths of the element plan's last part
+
+    int line(int R, PlanStats *o) { return device_plan_install_rows(parts, budget, R, o, who); }
+    void keep() { for (int k = 0; k < 3; ++k) if (parts[k]) { kept[k] = std::move(parts[k]->tlc); parts[k]->tlc = {}; } }
+    int install_line() { for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->tlc = std::move(kept[k]); return USPMV_OK; }
+    int or_line_back(int rc) { if (rc) install_line(); return rc; }
+    int sample(int cap, double *over) {
+        const int rc = device_elem_count(parts, cap, &cnt, who);
+        *over = sampled_over_cap_frac((int64_t)cnt.n.size(), [&](int64_t t) { return cnt.n[(size_t)t] > cap; });
+        return or_line_back(rc);
+    }
+    int elements(int cap, PlanStats *o) { return or_line_back(device_elem_install(parts, cnt, cap, o, &cl, who)); }
+    int install_elements() { return or_line_back(parts[1] ? USPMV_OK : tlc_pack12(parts[0], &cl, who)); }
+    int dealt_rows(bool, const PlanStats &, bool *, int64_t *, int64_t *) { return USPMV_OK; }      // (needs the host struct)
+    const uspmv_scs *const *structs() const { return nullptr; }
+};
+
+// ---- What differs between the kinds, side by side.  With TlcPlanOpts::measure off every kind builds at plan_tile_rows(false), one struct's rows.
+struct PartsPolicy {
+    const char *kind;
+    bool rows_512;           // measure on: plan_tile_rows(true) -- 512 rows per tile, two or three entry streams per row -- not 256
+    bool measured;           // measure on: the verdict of measured_tile_rows goes first (structs of 2^20 padded rows or more)
+    bool grow;               // tiles of 256 rows grow to 1024 / 512 under tile_rows_grow / tile_rows_accept (never beside a measured verdict)
+    bool measure_off_plain;  // measure off: that one candidate, installed whenever it is valid, and neither elements nor sweep
+    bool shared_budget;      // line_budget of a plan the parts share
+    bool keep_if_worth;      // after the fallbacks the line plan stays under ap_hp_plan_worth (else: whenever valid)
+    bool elements_by_kind;   // elements under ap_elements_allowed (else: TlcPlanOpts::elements)
+};
+constexpr PartsPolicy POLICY[3] = {
+    //                           rows_512  measured  grow   measure_off_plain  shared_budget  keep_if_worth  elements_by_kind
+    {"one struct",               false,    true,     true,  false,             false,         false,         false},
+    {"ap[dp_sp]",                true,     true,     false, true,              true,          false,         true},
+    {"split with an fp16 part",  true,     false,    false, true,              true,          true,          true},
+};
+int n_parts(uspmv_dmat *const parts[3]) { return parts[2] ? 3 : parts[1] ? 2 : 1; }
+const PartsPolicy &policy_of(uspmv_dmat *const parts[3]) { return POLICY[!parts[1] ? 0 : parts[n_parts(parts) - 1]->dtype == USPMV_F16 ? 2 : 1]; }
+
+// THE planner: lines -> elements -> sweep, once, for every kind and either source.  The handles end with the plan over single x elements
+// (*n_tiles / *n_staged then describe it), or the column-window sweep, or the line plan where the kind's keep rule holds, or none; but for the
+// element plan *n_tiles / *n_staged describe the line plan, also when the sweep took over or the plan was dropped (uspmv_dmat_plan_info tells
+// what the handles ended up with).
+template <typename Source>
+int plan_parts(uspmv_dmat *const parts[3], Source &src, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged) {
+    const char *who = src.who;
+    const PartsPolicy &pol = policy_of(parts);
+    const int n = n_parts(parts);
+    for (int k = 0; k < n; ++k) { parts[k]->tlc = {}; parts[k]->sw = {}; }
+    const bool own_budget = max_lines > 0;                     // (a caller with a line budget of its own keeps the line plan: no element fallback)
+    src.budget = line_budget(max_lines, parts[0]->dtype, pol.shared_budget);
+    const int R_meas = opts.measure && pol.measured ? measured_tile_rows(parts, src.budget, who) : 0;
+    PlanStats st;
+    if (int rc = plan_at_chosen_rows(R_meas, plan_tile_rows(opts.measure && pol.rows_512), pol.grow, src, &st)) return rc;
+    if (n_tiles) *n_tiles = st.n_tiles;
+    if (n_staged) *n_staged = st.valid ? st.n_staged : 0;
+    if (verbose()) fprintf(stderr, "[uspmv] tlc plan (%s): valid=%d tiles=%lld staged=%lld max_lines=%d lines_total=%lld\n", pol.kind, (int)st.valid,
+                           (long long)st.n_tiles, (long long)st.n_staged, st.lines, (long long)st.listed);
+    bool keep = st.valid;
+    if (opts.measure || !pol.measure_off_plain) {
+        bool took = false;
+        const bool allowed = pol.elements_by_kind ? ap_elements_allowed(opts, parts[0], parts[n - 1]) : opts.elements;
+        if (int rc = elements_take_over(own_budget, st, allowed, parts[0]->dtype, sum_elements(parts), src, &took, n_tiles, n_staged)) return rc;
+        if (took) return src.install_elements();
+        if (int rc = src.dealt_rows(own_budget, st, &took, n_tiles, n_staged)) return rc;
+        if (took) return USPMV_OK;
+        if (int rc = sweep_takes_over(parts, src.structs(), n, st, who, &took)) return rc;
+        keep = keep && !took && (!pol.keep_if_worth || ap_hp_plan_worth(st.n_tiles, st.n_staged));
+    }
+    if (keep) return src.install_line();
+    for (int k = 0; k < n; ++k) parts[k]->tlc = {};          // (a candidate a device source left behind)
     return USPMV_OK;
+}
+
+int plan_parts_device(uspmv_dmat *const parts[3], int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged, const char *who) {
+    DeviceSource src{parts, who};
+    return plan_parts(parts, src, max_lines, opts, n_tiles, n_staged);
 }
 
 }  // namespace
@@ -660,36 +736,10 @@ int dmat_optimize_ap(uspmv_dmat *dp, uspmv_dmat *sp, const uspmv_scs *s_dp, cons
         dp->C != sp->C || dp->n_chunks != sp->n_chunks)
         return uspmv::fail(USPMV_ERR_INVALID, "%s: handles / host structs do not form a dp+sp pair", who);
     if (int rc = require_device()) return rc;
-    dp->tlc = {};
-    sp->tlc = {};
-    const bool own_budget = max_lines > 0;                     // (as in uspmv_dmat_optimize: a caller's own line budget keeps the line plan)
-    max_lines = line_budget(max_lines, USPMV_F64, true);
-    uspmv_tlc_plan p;
-    PlanStats st;
-    auto build = [&](int R, PlanStats *o) {
-        const int rc = uspmv_build_tlc_plan(s_dp, s_sp, max_lines, R, &p);
-        *o = stats_of(p);
-        return rc;
-    };
-    // (measure off: one candidate, at the rows per tile of one struct)
-    if (int rc = opts.measure ? plan_at_chosen_rows(measured_tile_rows(dp, sp, max_lines, who), true, build, []() {}, &st)
-                              : build(plan_tile_rows(false), &st))
-        return rc;
-    if (n_tiles) *n_tiles = p.n_tiles;
-    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
     uspmv_dmat *const parts[3] = {dp, sp, nullptr};
-    if (!opts.measure) {
-        dp->sw = {}; sp->sw = {};
-        return p.valid ? install_host_plan(parts, p, /*elem=*/false, who) : USPMV_OK;
-    }
     const uspmv_scs *const ss[3] = {s_dp, s_sp, nullptr};
-    bool elem = false;
-    if (int rc = host_elements_take_over(parts, ss, own_budget, st, ap_elements_allowed(opts, dp, sp), n_tiles, n_staged, who, &elem)) return rc;
-    if (elem) return USPMV_OK;
-    bool swept = false;
-    if (int rc = sweep_takes_over(parts, ss, 2, st, who, &swept)) return rc;
-    if (swept || !p.valid) return USPMV_OK;
-    return install_host_plan(parts, p, /*elem=*/false, who);
+    HostSource src{parts, ss, who};
+    return plan_parts(parts, src, max_lines, opts, n_tiles, n_staged);
 }
 
 int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged) {
@@ -718,89 +768,14 @@ int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPla
             return USPMV_OK;
         }
     }
-    const bool own_budget = max_lines > 0;                     // (a caller with a line budget of its own keeps the line plan: no element fallback)
-    max_lines = line_budget(max_lines, s->dtype, false);
-    uspmv_tlc_plan p, q;
-    PlanStats st;
-    auto build = [&](int R, PlanStats *o) {
-        q = {};
-        const int rc = uspmv_build_tlc_plan(s, nullptr, max_lines, R, &q);
-        *o = stats_of(q);
-        return rc;
-    };
-    if (int rc = plan_at_chosen_rows(opts.measure ? measured_tile_rows(A, nullptr, max_lines, who) : 0, false, build, [&]() { p = std::move(q); }, &st)) return rc;
-    auto report = [&]() {
-        if (n_tiles) *n_tiles = p.n_tiles;
-        if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
-    };
-    report();
-    if (verbose()) fprintf(stderr, "[uspmv] tlc plan: tile_rows=%d tiles=%lld staged=%lld max_lines=%d lines_total=%zu col16=%zu\n",
-                           p.tile_rows, (long long)p.n_tiles, (long long)p.n_staged_tiles, p.max_lines_used, p.tile_lines.size(), p.col16.size());
-    A->sw = {};
-    // the element plan on the caller's row order (elements_take_over: the policy the device planner shares)
-    const PlanStats line = stats_of(p);
-    const int ecap = element_cap(s->dtype);
-    bool elem = false;
-    if (int rc = elements_take_over(own_budget, line, opts.elements, s->dtype, s->n_elements,
-                                    [&](int cap, double *over) { *over = elements_over_cap_frac(s, cap, 256); return USPMV_OK; },
-                                    [&](int cap, ElemStats *o) {
-                                        q = {};
-                                        const int rc2 = uspmv_build_tlc_plan(s, nullptr, cap, 256, &q, /*line_shift=*/0);
-                                        *o = {q.valid, q.n_tiles, q.n_staged_tiles, (int64_t)q.tile_lines.size(), q.max_lines_used};
-                                        return rc2;
-                                    }, &elem, n_tiles, n_staged))
-        return rc;
-    if (elem) p = std::move(q);
-    // ... and when the ROWS of a tile are scattered as well (rows and columns renumbered alike: a tile of 256 consecutive rows is no compact piece of the
-    // mesh any more): deal the rows to the tiles by the matrix graph first, as the block plan does (uspmv_scs_reorder_rows mode 4: rows change places
-    // only with rows of equal-length chunks, every row keeps its slot sequence), then the element plan on that order -- a private copy of the values
-    // (8 / 4 bytes per element of HBM), of the column indices (for the few tiles that do not stage) and a row map for y.
-    uspmv_scs rr;
-    std::vector<int32_t> rr_map;
-    bool reordered = false;
-    if (!elem && line_plan_short(own_budget, line) && g_tune.tlc_elem && g_tune.tlc_elem_rows && opts.deal_rows && s->n_rows == s->n_cols) {
-        // first with the clusters confined to segments of tlc_elem_seg_rows rows (64 Ki: many segments in parallel, and a trial on a sample of them that stops
-        // irregular matrices early); when that leaves some, but not most, of the sampled tiles over the cap -- related rows further apart than a segment --
-        // once more with segments of 2^20 rows (a second or more of clustering per million rows on few threads: only where it looks promising)
-        const int64_t seg_stage[2] = {(int64_t)g_tune.tlc_elem_seg_rows, (int64_t)1 << 20};
-        for (int stage = 0; stage < 2 && !reordered; ++stage) {
-            if (stage == 1 && seg_stage[1] <= seg_stage[0]) break;
-            if (uspmv_scs_reorder_rows(s, g_tune.tlc_elem_rows == 4 ? 4 : 2, &rr, &rr_map, g_tune.tlc_elem_rows == 4 ? 64 : 256, seg_stage[stage]) != 1) break;
-            const double over = elements_over_cap_frac(&rr, ecap, 256);
-            q = {};
-            if (over <= 0.1)
-                if (int rc = uspmv_build_tlc_plan(&rr, nullptr, ecap, 256, &q, /*line_shift=*/0)) return rc;
-            if (verbose()) fprintf(stderr, "[uspmv] element plan on the graph-dealt rows (segments of %lld rows): %.0f %% of the sampled tiles over the cap; valid=%d tiles=%lld staged=%lld max_elements=%d (cap %d) elements_total=%zu\n",
-                                   (long long)seg_stage[stage], 100.0 * over, (int)q.valid, (long long)q.n_tiles, (long long)q.n_staged_tiles, q.max_lines_used, ecap, q.tile_lines.size());
-            // (19 of 20 tiles staged is enough here: what would run instead -- sweep or gather kernel -- is 2 x slower on such matrices)
-            if (q.valid && stages_19_of_20(q.n_tiles, q.n_staged_tiles) && elements_pay((int64_t)q.tile_lines.size(), s->n_elements)) {
-                p = std::move(q); elem = true; reordered = true;
-                report();
-                if (verbose()) fprintf(stderr, "[uspmv] tlc plan over single x elements, rows dealt to the tiles by the matrix graph: tiles=%lld max_elements=%d elements_total=%zu (%.1f entries per element)\n",
-                                       (long long)p.n_tiles, p.max_lines_used, p.tile_lines.size(), (double)s->n_elements / (double)std::max<size_t>(p.tile_lines.size(), 1));
-            } else if (over > 0.6) break;                    // most tiles far over the cap: larger segments will not repair that
-        }
-    }
-    if (!elem) {
-        bool swept = false;
-        if (int rc = sweep_takes_over(&A, &s, 1, stats_of(p), who, &swept)) return rc;
-        if (swept) return USPMV_OK;
-    }
-    if (!p.valid) return USPMV_OK;                              // nothing worth staging: plain kernel stays
     uspmv_dmat *const parts[3] = {A, nullptr, nullptr};
-    if (int rc = install_host_plan(parts, p, elem, who)) return rc;
-    if (reordered) {
-        hipError_t e = A->tlc.values.upload(rr.values_ptr(), (size_t)rr.n_elements * (rr.dtype == USPMV_F64 ? 8 : 4));
-        if (e == hipSuccess) e = A->tlc.row_map.upload(rr_map.data(), rr_map.size() * 4);
-        if (e == hipSuccess && p.n_staged_tiles < p.n_tiles) e = A->tlc.cols.upload(rr.col_idxs.data(), (size_t)rr.n_elements * 4);
-        if (e != hipSuccess) {
-            A->tlc = {};
-            return uspmv::fail(USPMV_ERR_ALLOC, "%s: device copy failed: %s", who, hipGetErrorString(e));
-        }
-    }
+    const uspmv_scs *const ss[3] = {s, nullptr, nullptr};
+    HostSource src{parts, ss, who, opts.deal_rows};
+    if (int rc = plan_parts(parts, src, max_lines, opts, n_tiles, n_staged)) return rc;
+    // (each of the two does nothing on a handle that ended without a tile-local-column plan)
     if (int rc = tlc_pack12(A, &s->chunk_lengths, who)) return rc;
-    if (reordered || !opts.additive) return USPMV_OK;
-    return tlc_additive_install(A, s, p, max_lines, opts.new_to_old, who);
+    if (src.dealt || !opts.additive) return USPMV_OK;
+    return tlc_additive_install(A, s, src.p, src.budget, opts.new_to_old, who);
 }
 
 int dmat_optimize_ap_hp(uspmv_dmat *hi, uspmv_dmat *mid, uspmv_dmat *hp, const uspmv_scs *s_hi, const uspmv_scs *s_mid, const uspmv_scs *s_hp,
@@ -808,7 +783,7 @@ int dmat_optimize_ap_hp(uspmv_dmat *hi, uspmv_dmat *mid, uspmv_dmat *hp, const u
     const char *who = "uspmv_dmat_optimize_ap_hp";
     if (!s_hi || !s_hp || (mid && !s_mid)) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
     if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
-    const uspmv_scs_t *ss[3] = {s_hi, mid ? s_mid : s_hp, mid ? s_hp : nullptr};
+    const uspmv_scs_t *const ss[3] = {s_hi, mid ? s_mid : s_hp, mid ? s_hp : nullptr};
     uspmv_dmat_t *const ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
     for (int k = 0; k < 3; ++k) {
         if (!ms[k]) continue;
@@ -818,24 +793,8 @@ int dmat_optimize_ap_hp(uspmv_dmat *hi, uspmv_dmat *mid, uspmv_dmat *hp, const u
             return uspmv::fail(USPMV_ERR_INVALID, "%s: handles and host structs do not describe the same parts", who);
     }
     if (int rc = require_device()) return rc;
-    for (uspmv_dmat_t *M : ms) if (M) { M->tlc = {}; M->sw = {}; }
-    if (n_tiles) *n_tiles = 0;
-    if (n_staged) *n_staged = 0;
-    const bool own_budget = max_lines > 0;
-    uspmv_tlc_plan p;
-    // (measure off: at the rows per tile of one struct, as in dmat_optimize_ap)
-    if (int rc = uspmv_build_tlc_plan(ss[0], ss[1], line_budget(max_lines, hi->dtype, true), plan_tile_rows(opts.measure), &p, 4, ss[2])) return rc;
-    if (n_tiles) *n_tiles = p.n_tiles;              // (the line plan's outcome also when the sweep takes over, as in uspmv_dmat_optimize_ap)
-    if (n_staged) *n_staged = p.valid ? p.n_staged_tiles : 0;
-    if (!opts.measure) return p.valid ? install_host_plan(ms, p, /*elem=*/false, who) : USPMV_OK;
-    bool elem = false;
-    if (int rc = host_elements_take_over(ms, ss, own_budget, stats_of(p), ap_elements_allowed(opts, hi, hp), n_tiles, n_staged, who, &elem))
-        return rc;
-    if (elem) return USPMV_OK;
-    bool swept = false;
-    if (int rc = sweep_takes_over(ms, ss, mid ? 3 : 2, stats_of(p), who, &swept)) return rc;
-    if (swept || !p.valid || !ap_hp_plan_worth(p.n_tiles, p.n_staged_tiles)) return USPMV_OK;
-    return install_host_plan(ms, p, /*elem=*/false, who);
+    HostSource src{ms, ss, who};
+    return plan_parts(ms, src, max_lines, opts, n_tiles, n_staged);
 }
 
 }  // namespace uspmv_dev
@@ -897,7 +856,8 @@ int uspmv_dmat_optimize_device_ap(uspmv_dmat_t *dp, uspmv_dmat_t *sp, int max_li
     if (dp->dtype != USPMV_F64 || sp->dtype != USPMV_F32 || dp->C != sp->C || dp->n_chunks != sp->n_chunks)
         return uspmv::fail(USPMV_ERR_INVALID, "%s: handles do not form a dp+sp pair", who);
     if (int rc = require_device()) return rc;
-    return device_plan_install(dp, sp, max_lines, TlcPlanOpts{}, n_tiles, n_staged, who);
+    uspmv_dmat *const parts[3] = {dp, sp, nullptr};
+    return plan_parts_device(parts, max_lines, TlcPlanOpts{}, n_tiles, n_staged, who);
 }
 
 }  // extern "C"
@@ -937,25 +897,24 @@ int uspmv_dev::dmat_optimize_device(uspmv_dmat *A, int max_lines, const TlcPlanO
             if (e == hipSuccess) e = hipMemsetAsync(alt->own.col_idxs, 0, 4 * ne, nullptr);
             if (e == hipSuccess) e = hipMemsetAsync(alt->own.values, 0, vsz * ne, nullptr);
             int rc = e == hipSuccess ? launch_rechunk32(A, alt->chunk_ptrs, alt->own.col_idxs, alt->own.values, nullptr) : uspmv::fail(USPMV_ERR_ALLOC, "%s: %s", who, hipGetErrorString(e));
-            if (!rc) rc = device_plan_install(alt, nullptr, max_lines, opts, n_tiles, n_staged, who);
+            uspmv_dmat *const alt_parts[3] = {alt, nullptr, nullptr};
+            if (!rc) rc = plan_parts_device(alt_parts, max_lines, opts, n_tiles, n_staged, who);
             if (rc) { uspmv_dmat_free(alt); return rc; }
             A->tlc = {};
             A->alt = alt;
             return USPMV_OK;
         }
     }
-    return device_plan_install(A, nullptr, max_lines, opts, n_tiles, n_staged, who);
+    uspmv_dmat *const parts[3] = {A, nullptr, nullptr};
+    return plan_parts_device(parts, max_lines, opts, n_tiles, n_staged, who);
 }
 
 // The line plan shared by the two or three parts of a split (parts[2] NULL: two), as dmat_optimize_ap / _ap_hp install it with `measure`
-// off: at the rows per tile of ONE struct in the caller's row order, kept whenever it stages a tile, no column-window sweep
+// off (PartsPolicy::measure_off_plain), under the default line budget
 int uspmv_dev::dmat_optimize_device_shared(uspmv_dmat *const parts[3], int64_t *n_tiles, int64_t *n_staged, const char *who) {
-    for (int k = 0; k < 3; ++k) if (parts[k]) parts[k]->sw = {};
-    PlanStats st;
-    if (int rc = device_plan_install_rows(parts, 0, plan_tile_rows(false), &st, who)) return rc;
-    if (n_tiles) *n_tiles = st.n_tiles;
-    if (n_staged) *n_staged = st.n_staged;
-    return USPMV_OK;
+    TlcPlanOpts plain;
+    plain.measure = false;
+    return plan_parts_device(parts, 0, plain, n_tiles, n_staged, who);
 }
 
 extern "C" {
@@ -975,25 +934,7 @@ int uspmv_dmat_optimize_device_ap_hp(uspmv_dmat_t *hi, uspmv_dmat_t *mid, uspmv_
     if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
     if (int rc = require_device()) return rc;
     uspmv_dmat_t *const ms[3] = {hi, mid ? mid : hp, mid ? hp : nullptr};
-    for (uspmv_dmat_t *M : ms) if (M) M->sw = {};
-    PlanStats st;
-    if (int rc = device_plan_install_rows(ms, max_lines, plan_tile_rows(true), &st, who)) return rc;
-    if (n_tiles) *n_tiles = st.n_tiles;
-    if (n_staged) *n_staged = st.n_staged;
-    {   // lines -> elements -> sweep, as the host planner
-        uspmv_dmat::TlcPlan kept[3];
-        for (int k = 0; k < 3; ++k) if (ms[k]) kept[k] = std::move(ms[k]->tlc);
-        bool elem = false;
-        if (int rc = device_elements_take_over(ms, kept, max_lines > 0, st, ap_elements_allowed(TlcPlanOpts{}, hi, hp),
-                                               n_tiles, n_staged, who, &elem))
-            return rc;
-        if (elem) return USPMV_OK;
-    }
-    bool swept = false;
-    if (int rc = sweep_takes_over(ms, nullptr, mid ? 3 : 2, st, who, &swept)) return rc;
-    if (swept || !ap_hp_plan_worth(st.n_tiles, st.n_staged))
-        for (uspmv_dmat_t *M : ms) if (M) M->tlc = {};
-    return USPMV_OK;
+    return plan_parts_device(ms, max_lines, TlcPlanOpts{}, n_tiles, n_staged, who);
 }
 
 int uspmv_dmat_plan_download(const uspmv_dmat_t *A, int64_t meta[4], int32_t *tile_line_ptr, int32_t *tile_lines, uint32_t *c16_ptrs,

@@ -294,18 +294,22 @@ namespace uspmv_dev {
 // additive -- the additive chunk records beside the local indices ("tlc_additive"; not for the rank blocks of the distributed object);
 // new_to_old: the permutation of the struct's rows where the struct does not carry it (the internal re-chunking of a narrow struct).
 struct TlcPlanOpts { bool measure = true, elements = true, deal_rows = true, additive = true; const std::vector<int32_t> *new_to_old = nullptr; };
-// uspmv_dmat_optimize with the options spelled out
+// The entries below are argument checks around ONE driver, plan_parts: line plan at the kind's rows per tile -> plan over single x
+// elements -> column-window sweep -> keep or drop the line plan; *n_tiles / *n_staged describe the line plan unless the element plan
+// was taken.  What the kinds differ in is the table POLICY there (rows per tile, keep rule, when elements are allowed), and for the parts
+// of a split (ap[dp_sp], the kinds with an fp16 part) `measure` off means: ONE candidate at the rows per tile of one struct (256) in the
+// caller's row order, installed whenever it is valid, neither elements nor sweep -- what the distributed object needs of them.  A single
+// struct tries the sweep whatever the options say.
+// uspmv_dmat_optimize, uspmv_dmat_optimize_ap and uspmv_dmat_optimize_ap_hp (mid / s_mid NULL for the two-part kinds) with the options
+// spelled out, from the host structs:
 int dmat_optimize(uspmv_dmat *A, const uspmv_scs *s, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged);
-// uspmv_dmat_optimize_ap likewise.  measure off: the shared line plan at the rows per tile of ONE struct (256, not the pair's 512) in the
-// caller's row order, and no fall-through to the column-window sweep -- what the distributed object needs of an ap[dp_sp] pair
 int dmat_optimize_ap(uspmv_dmat *dp, uspmv_dmat *sp, const uspmv_scs *s_dp, const uspmv_scs *s_sp, int max_lines, const TlcPlanOpts &opts,
                      int64_t *n_tiles, int64_t *n_staged);
-// uspmv_dmat_optimize_ap_hp likewise (mid / s_mid NULL for the two-part kinds).  measure off: the shared line plan at 256 rows per tile in
-// the caller's row order, installed whenever it stages a tile, no column-window sweep -- what the distributed object needs of the parts
 int dmat_optimize_ap_hp(uspmv_dmat *hi, uspmv_dmat *mid, uspmv_dmat *hp, const uspmv_scs *s_hi, const uspmv_scs *s_mid, const uspmv_scs *s_hp,
                         int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged);
-// The same plans built on the device from the handles' own arrays (no host struct): uspmv_dmat_optimize_device with measure / elements
-// spelled out, and the line plan shared by the two or three parts of a split (parts[2] NULL: two) as `measure` off gives it above
+// ... and from the handles' own device arrays (no host struct; deal_rows and additive: host only): uspmv_dmat_optimize_device with the
+// options spelled out, and the driver with `measure` off and the default line budget on the two or three parts of a split (parts[2]
+// NULL: two)
 int dmat_optimize_device(uspmv_dmat *A, int max_lines, const TlcPlanOpts &opts, int64_t *n_tiles, int64_t *n_staged);
 int dmat_optimize_device_shared(uspmv_dmat *const parts[3], int64_t *n_tiles, int64_t *n_staged, const char *who);
 
@@ -597,15 +601,13 @@ int launch_spmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const 
 int launch_spmv_ap_hp_tiles(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *tile_ids, long n_ids,
                             const void *d_x, void *d_y, hipStream_t stream);                                       // ap_kernels.hip
 
-// (A2 / the *_2 arrays: optional second struct sharing the plan -- the sp part of an ap[dp_sp] pair; A3 / *_3 a third -- the hp part of
-//  ap[dp_sp_hp])
-int launch_plan_count(const uspmv_dmat *A, long n_tiles, int max_lines, int *d_n_lines, int *d_max_col, hipStream_t st,
-                      const uspmv_dmat *A2 = nullptr, int tile_rows = 256, const uspmv_dmat *A3 = nullptr);                 // plan_kernels.hip
+// The line plan of one struct or of the two or three parts of an ap split (parts[k] NULL from the first missing one on; the sp part of an
+// ap[dp_sp] pair, the hp part(s) of a split with an fp16 part): lines per tile of tile_rows rows, then the lists and part k's local indices
+// (to d_col16[k] at d_c16_ptrs[k])
+int launch_plan_count(const uspmv_dmat *const parts[3], long n_tiles, int max_lines, int *d_n_lines, int *d_max_col, int tile_rows, hipStream_t st);   // plan_kernels.hip
 int launch_plan_pack12(const uspmv_dmat *A, const unsigned *d_c16_ptrs, const unsigned short *d_col16, const unsigned *d_c12_ptrs, unsigned *d_col12, hipStream_t st);   // plan_kernels.hip
-int launch_plan_write(const uspmv_dmat *A, long n_tiles, const int *d_tile_line_ptr, const unsigned *d_c16_ptrs, int *d_tile_lines,
-                      unsigned short *d_col16, hipStream_t st, const uspmv_dmat *A2 = nullptr, const unsigned *d_c16_ptrs2 = nullptr,
-                      unsigned short *d_col16_2 = nullptr, int tile_rows = 256, const uspmv_dmat *A3 = nullptr,
-                      const unsigned *d_c16_ptrs3 = nullptr, unsigned short *d_col16_3 = nullptr);                         // plan_kernels.hip
+int launch_plan_write(const uspmv_dmat *const parts[3], long n_tiles, const int *d_tile_line_ptr, int *d_tile_lines, const unsigned *const d_c16_ptrs[3],
+                      unsigned short *const d_col16[3], int tile_rows, hipStream_t st);                                    // plan_kernels.hip
 // the plan over single x elements on 256-row tiles: distinct columns per tile clipped at cap + 1 (cap <= 16384), then the sorted lists
 // and the slots' ranks; most_listed: the longest list of d_tile_line_ptr
 // the plan over single x elements of one struct or of the two or three parts of an ap split (parts[k] NULL from the first missing one on)

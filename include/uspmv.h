@@ -275,6 +275,45 @@ int uspmv_dmat_wrap(int64_t C, int64_t n_chunks, int64_t n_elements, int dtype, 
                     const int32_t *d_chunk_lengths, const int32_t *d_col_idxs, const void *d_values,
                     uspmv_dmat_t **out);
 void uspmv_dmat_free(uspmv_dmat_t *m);
+/* Numeric refresh (no reference counterpart): the matrix changed numerically, not structurally -- Newton steps, time
+ * stepping, re-assembled blocks -- and the handle keeps its plans.  *actions (may be NULL) receives what the call had to do beyond the
+ * value array itself:
+ *   USPMV_REFRESH_COPIES               private copies of the values re-gathered under their plan's row map (the element plan on rows dealt
+ *                                      to the tiles; the block plans' re-ordered and group-major copies)
+ *   USPMV_REFRESH_RECHUNKED            the internal C = 32 re-chunking of a narrow struct (C in {1, 2, 4, 8, 16}, crs included) re-copied
+ *   USPMV_REFRESH_SWEEP_REBUILT        the column-window sweep plan of a one-struct handle rebuilt by the device builder at the installed
+ *                                      window and rows per tile (its stream strips trailing +0 runs: its SHAPE depends on the values)
+ *   USPMV_REFRESH_BLOCK_SWEEP_DROPPED  the block-vector sweep plan released (host-built only, same stripping rule); uspmv_spmmv then
+ *                                      answers from whatever block plan remains, or from the gather kernel
+ * 0: line, element, 12-bit and additive-record plans on the caller's row order, and a handle without a plan -- their kernels read the
+ * value array in place.  All three calls refuse, before a device is looked for, with USPMV_ERR_UNSUPPORTED: an F16 handle, and a handle
+ * that carries the shared plan of an adaptive-precision split (new values move entries between the parts: set the split up again with
+ * uspmv_convert_to_scs_device_ap_from_arrays); with USPMV_ERR_INVALID: NULL arguments.  They work on `stream` and return when the handle
+ * is consistent; uspmv_spmmv_x_prepared state is untouched; not thread-safe per handle, like every other call on a handle. */
+enum { USPMV_REFRESH_COPIES = 1, USPMV_REFRESH_RECHUNKED = 2, USPMV_REFRESH_SWEEP_REBUILT = 4, USPMV_REFRESH_BLOCK_SWEEP_DROPPED = 8 };
+/* The handle's values array has new contents (same pattern): bring every plan on the handle back in line with it. */
+int uspmv_dmat_values_changed(uspmv_dmat_t *m, void *stream, int *actions);
+/* New values in the handle's own layout and dtype (n_elements; host or device pointer), for handles that OWN their arrays
+ * (uspmv_dmat_upload, the device conversions): copy, then uspmv_dmat_values_changed.  A wrapped handle is refused with
+ * USPMV_ERR_INVALID: its caller writes the array and calls uspmv_dmat_values_changed. */
+int uspmv_dmat_update_values(uspmv_dmat_t *m, const void *values, void *stream, int *actions);
+/* New values as COO arrays in HBM, in the order the handle was converted from: d_I, d_J (int32), d_V (double) sorted by row, the order
+ * inside a row = summation order, as at conversion (d_J is read only when check_pattern is set).  d_row_pos[n_rows]: the position of row i
+ * in the struct -- the struct's old_to_new, or the fixed permutation it was converted with; NULL = the identity.  d_col_perm: what the
+ * columns were permuted with (permute_scs_cols' rule: only columns below n_rows), NULL = as converted; read only when check_pattern is
+ * set.  d_values_dst: NULL = the handle's own array (handles that own their arrays only); for a wrapped handle the WRITABLE pointer to
+ * the array that was wrapped, which must equal the handle's values -- how the caller grants the write uspmv_dmat_wrap's const withheld.
+ * Checks first, through flag words, nothing written before they come back clean: rows in [0, n_rows) (USPMV_ERR_INVALID) and sorted
+ * (USPMV_ERR_UNSUPPORTED), with the texts of uspmv_convert_to_scs_device_from_arrays; ceil(n_rows / C) = n_chunks; every d_row_pos entry
+ * inside the padded rows and no two alike; no row longer than the chunk where it sits; with check_pattern the stored column of every entry
+ * equal to the (permuted) d_J -- USPMV_ERR_INVALID, the text names the first offending entry.  Placement: element (row, slot j) receives
+ * the row's j-th value rounded as at conversion ((float)v for F32); slots beyond a row's entries receive +0 and keep their stored column,
+ * like padding.  Then uspmv_dmat_values_changed.  Device memory beyond the handle: 4 bytes per row + 4 per padded row. */
+int uspmv_dmat_update_values_from_arrays(uspmv_dmat_t *m, const int32_t *d_I, const int32_t *d_J, const double *d_V, int64_t n_rows, int64_t nnz,
+                                         const int32_t *d_row_pos, const int32_t *d_col_perm, int check_pattern, void *d_values_dst, void *stream,
+                                         int *actions);
+/* host twin on a host struct (it carries n_rows and its own old_to_new_idx): same placement, same checks, no device */
+int uspmv_scs_update_values(uspmv_scs_t *s, const uspmv_coo_t *m, const int32_t *col_perm, int check_pattern);
 /* Optional, MI355X-specific: derive a tile-local-column plan from the host struct the handle was made
  * from: per 256-row tile the list of 16-element x lines it touches plus 16-bit LDS-local
  * column indices.  uspmv_spmv then stages the x lines of a tile in LDS and streams 2-byte instead of
@@ -689,6 +728,10 @@ int uspmv_apply_permutation_dev(void *d_out, const void *d_in, const int32_t *d_
  *   "spmmv_unroll" 0 (auto) | 1|2|4|8 slots per batch,
  *   "ablate" 0 | 1 | 2 (measurement only: gathers collapsed / removed, results are wrong). */
 void uspmv_raw_plan_cache_clear(void);
+/* raw-array entry points behind "raw_plan_cache": the caller rewrote the value array at d_values in place (same pattern) -- refresh the
+ * cached plans whose values pointer is d_values (uspmv_dmat_values_changed on each) instead of clearing the cache and planning again;
+ * *n_entries (may be NULL) = how many */
+int uspmv_raw_plan_cache_values_changed(const void *d_values, void *stream, int *n_entries);
 int uspmv_set_tuning(const char *key, int value);
 int uspmv_get_tuning(const char *key, int *value);
 

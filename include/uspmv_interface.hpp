@@ -252,6 +252,22 @@ public:
     void spmmv(const void *d_X, void *d_Y, int b, ST ld, bool rowwise, void *stream = nullptr) const {
         uspmv_detail::check(uspmv_spmmv(h_, d_X, d_Y, b, ld, rowwise ? USPMV_ROWWISE : USPMV_COLWISE, stream), "uspmv_spmmv");
     }
+    // numeric refresh, same pattern and plans kept: after an in-place write of a wrapped value array ...
+    int values_changed(void *stream = nullptr) {
+        int actions = 0;
+        uspmv_detail::check(uspmv_dmat_values_changed(h_, stream, &actions), "uspmv_dmat_values_changed");
+        return actions;
+    }
+    // ... and from COO arrays in HBM with new values, in the order the matrix was converted from.  d_perm: the old_to_new_idx that
+    // from_device_coo handed out (rows and columns were permuted with it; null: the identity); the pattern is checked against it.
+    // values_dst: null for a matrix that owns its arrays, the wrapped value array for wrap().  Returns the USPMV_REFRESH_* actions.
+    int update_values_from_device_coo(const int *d_I, const int *d_J, const double *d_V, ST n_rows, ST nnz, const int *d_perm, void *stream = nullptr,
+                                      void *values_dst = nullptr) {
+        int actions = 0;
+        uspmv_detail::check(uspmv_dmat_update_values_from_arrays(h_, d_I, d_J, d_V, n_rows, nnz, d_perm, d_perm, 1, values_dst, stream, &actions),
+                            "uspmv_dmat_update_values_from_arrays");
+        return actions;
+    }
     ST n_rows_padded() const { return n_rows_padded_; }
     uspmv_dmat_t *handle() const { return h_; }
 

@@ -15,6 +15,7 @@ from .binding import (  # noqa: F401
     partition_precisions, partition_precisions_hp, permute_scs_cols, read_mtx, seg_work_sharing_arr, seg_local_coo, set_tuning, spmmv_x_prepared, spmmv_x_release, spmmv, spmmv_ap, spmmv_ap_path, spmmv_ap_plan_lines, spmmv_ap_sweep_vectors, spmmv_ap_hp, spmmv_ap_hp_path, spmmv_ap_hp_plan_lines, spmmv_ap_hp_sweep_vectors, spmv, spmv_ap, spmv_ap_hp, additive_plan_probe, additive_plan_probe2,
     spmv_chunks, spmv_tiles, uspmv_csr_gpu, uspmv_scs_gpu, DistNative, HostComm, CommPlan, Transport, DistOptions, EXCHANGE_HOST, EXCHANGE_PEER, EXCHANGE_RCCL, runtime_versions, dist_check_reference, comm_unique_id, seg_from_row_counts, gen_stencil27_row_counts,
     halo_discover_device, ONE_PRECISION, gen_stencil27_device,
+    raw_plan_cache_values_changed, REFRESH_COPIES, REFRESH_RECHUNKED, REFRESH_SWEEP_REBUILT, REFRESH_BLOCK_SWEEP_DROPPED,
     partition_precisions_eq, equilibrate_device, equilibrate_device_count_atomics, partition_precisions_device_eq, convert_ap_device_from_arrays_eq,
     halo_discover_ap, spmv_ap_tiles, spmv_ap_chunks, spmmv_ap_tiles, spmmv_ap_chunks, spmmv_ap_tiles_path, dist_check_reference_ap,
     halo_discover_ap_hp, spmv_ap_hp_tiles, spmv_ap_hp_chunks, spmmv_ap_hp_tiles, spmmv_ap_hp_chunks, spmmv_ap_hp_tiles_path, dist_check_reference_ap_hp,

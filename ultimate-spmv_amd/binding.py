@@ -19,6 +19,7 @@ AP_DP_HP, AP_SP_HP, AP_DP_SP_HP = 0, 1, 2     # kinds of uspmv_partition_precisi
 AP_DP_SP = 3                                  # ... and the fourth kind of the device-side set-up (partition_precisions_device)
 ONE_PRECISION = -1                            # kind of a one-precision object (DistNative.from_device_arrays)
 SORT_HOST, SORT_DEVICE_STABLE = 0, 1          # sigma-window ordering of the device-side conversions
+REFRESH_COPIES, REFRESH_RECHUNKED, REFRESH_SWEEP_REBUILT, REFRESH_BLOCK_SWEEP_DROPPED = 1, 2, 4, 8   # actions of DeviceMatrix.values_changed
 COLWISE, ROWWISE = 0, 1
 SEG_ROWS, SEG_NNZ = 0, 1
 
@@ -150,6 +151,11 @@ _SIGS = {
     "uspmv_peek_i32": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "uspmv_apply_permutation_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
     "uspmv_raw_plan_cache_clear": (None, []),
+    "uspmv_raw_plan_cache_values_changed": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
+    "uspmv_dmat_values_changed": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
+    "uspmv_dmat_update_values": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int)]),
+    "uspmv_dmat_update_values_from_arrays": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, C.POINTER(C.c_int)]),
+    "uspmv_scs_update_values": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "uspmv_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "uspmv_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "uspmv_seg_work_sharing_arr": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
@@ -467,6 +473,12 @@ class Scs:
         pc = C.c_int32(-1)
         _ck(lib().uspmv_scs_chunk_classes(self.h, n_local, cls.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(pc)))
         return cls[:self.n_chunks], pc.value
+
+    def update_values(self, coo, col_perm=None, check=True):
+        """New values on the unchanged pattern (uspmv_scs_update_values): coo holds the matrix this struct was converted from with new
+        numbers; col_perm is what the columns were permuted with (None: as converted), read only under check."""
+        cp = None if col_perm is None else np.ascontiguousarray(col_perm, np.int32)
+        _ck(lib().uspmv_scs_update_values(self.h, coo.h, _np_ptr(cp), int(bool(check))))
 
     def __del__(self):
         if getattr(self, "h", None) and _LIB is not None:
@@ -1281,6 +1293,41 @@ class DeviceMatrix:
         self.tile_rows = tr.value          # 0: no plan was built
         return a.value, b.value
 
+    def values_changed(self, stream=None):
+        """The value array has new contents on the same pattern (an in-place write of self.values, say): bring every plan on the handle back
+        in line with it (uspmv_dmat_values_changed).  Returns the actions, a mask of REFRESH_*; 0: the plans read the array in place."""
+        acts = C.c_int(0)
+        _ck(lib().uspmv_dmat_values_changed(self.h, _stream_ptr(stream), C.byref(acts)))
+        return acts.value
+
+    def update_values(self, values, stream=None):
+        """New values in the handle's own layout and dtype (numpy array or torch tensor of n_elements), for handles that own their arrays
+        (uspmv_dmat_update_values); returns the actions."""
+        import torch
+        if isinstance(values, torch.Tensor):
+            assert values.dtype == self.torch_dtype and values.numel() == self.n_elements and values.is_contiguous()
+            ptr = values.data_ptr()
+        else:
+            values = np.ascontiguousarray(values)
+            assert values.dtype.itemsize == {F64: 8, F32: 4, F16: 2}[self.dtype] and values.size == self.n_elements
+            ptr = _np_ptr(values)
+        acts = C.c_int(0)
+        _ck(lib().uspmv_dmat_update_values(self.h, ptr, _stream_ptr(stream), C.byref(acts)))
+        return acts.value
+
+    def update_values_from_coo(self, d_I, d_J, d_V, row_pos=None, col_perm=None, check=True, stream=None):
+        """New values as COO arrays in HBM (torch int32 / int32 / float64, sorted by row, in the order the handle was converted from):
+        uspmv_dmat_update_values_from_arrays.  row_pos: int32 device tensor, the position of every row in the struct (its old_to_new; None:
+        the identity); col_perm: what the columns were permuted with (None: as converted; read only under check).  A DeviceMatrix that wraps
+        torch arrays passes its own values tensor as the destination.  Returns the actions."""
+        import torch
+        assert d_I.dtype == torch.int32 and d_J.dtype == torch.int32 and d_V.dtype == torch.float64 and d_I.is_cuda
+        acts = C.c_int(0)
+        dst = _dp(self.values) if getattr(self, "values", None) is not None else None
+        _ck(lib().uspmv_dmat_update_values_from_arrays(self.h, _dp(d_I), _dp(d_J), _dp(d_V), int(self.n_rows), int(d_I.numel()), _dp(row_pos), _dp(col_perm),
+                                                       int(bool(check)), dst, _stream_ptr(stream), C.byref(acts)))
+        return acts.value
+
     def __del__(self):
         if getattr(self, "h", None) and _LIB is not None:
             _LIB.uspmv_dmat_free(self.h)
@@ -1740,6 +1787,14 @@ def uspmv_scs_gpu(Cc, n_chunks, chunk_ptrs, chunk_lengths, col_idxs, values, x, 
     _ck(f(Cc, n_chunks, _dp(chunk_ptrs), _dp(chunk_lengths), _dp(col_idxs), _dp(values), _dp(x), _dp(y),
           _stream_ptr(stream)))
     return y
+
+
+def raw_plan_cache_values_changed(values_tensor, stream=None):
+    """The value array behind cached raw-array plans ("raw_plan_cache") was rewritten in place: refresh those plans
+    (uspmv_raw_plan_cache_values_changed); returns how many cache entries hold this pointer."""
+    n = C.c_int(0)
+    _ck(lib().uspmv_raw_plan_cache_values_changed(_dp(values_tensor), _stream_ptr(stream), C.byref(n)))
+    return n.value
 
 
 def uspmv_csr_gpu(n_rows, row_ptrs, col_idxs, values, x, y, stream=None):

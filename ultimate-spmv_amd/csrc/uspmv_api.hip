@@ -766,7 +766,8 @@ int uspmv_spmmv_ap_plan_lines(int b, int *max_lines) {
 // seam passes the same device arrays on every call (code/classes_structs.hpp:997-1034), so the first call wraps them,
 // builds the tile-local-column plan on the device and later calls run the plan kernel.  Keyed on the array
 // addresses and shape -- the caller promises not to put a different matrix behind the same pointers
-// (uspmv_raw_plan_cache_clear() after freeing or rewriting them).  Mutex-guarded; a handful of entries.
+// (uspmv_raw_plan_cache_clear() after freeing them; uspmv_raw_plan_cache_values_changed() after rewriting the values of the same
+// pattern: the refresh of csrc/refresh_kernels.hip on every plan behind that pointer).  Mutex-guarded; a handful of entries.
 namespace {
 struct RawKey { const void *cp, *cl, *ci, *va; int64_t C, n_chunks; int dtype; };
 struct RawEntry { RawKey k; uspmv_dmat_t *A; };
@@ -793,6 +794,18 @@ void uspmv_raw_plan_cache_clear(void) {
     std::lock_guard<std::mutex> lock(g_raw_mutex);
     for (RawEntry &e : g_raw_cache) uspmv_dmat_free(e.A);
     g_raw_cache.clear();
+}
+
+int uspmv_raw_plan_cache_values_changed(const void *d_values, void *stream, int *n_entries) {
+    if (n_entries) *n_entries = 0;
+    if (!d_values) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_raw_plan_cache_values_changed: NULL argument");
+    std::lock_guard<std::mutex> lock(g_raw_mutex);
+    for (RawEntry &e : g_raw_cache) {
+        if (e.k.va != d_values) continue;
+        if (int rc = uspmv_dmat_values_changed(e.A, stream, nullptr)) return rc;
+        if (n_entries) ++*n_entries;
+    }
+    return USPMV_OK;
 }
 
 #define RAW_SCS(SUF, VT, DT)                                                                                        \

@@ -245,6 +245,69 @@ int uspmv_permute_scs_cols(uspmv_scs_t *s, const int32_t *perm) {
 
 void uspmv_scs_free(uspmv_scs_t *s) { delete s; }
 
+// Host twin of uspmv_dmat_update_values_from_arrays (csrc/refresh_kernels.hip): the values of m, a matrix with the pattern s was converted
+// from, placed into s -- same checks in the same order, same placement, nothing written before every check has passed.  Row r sits at
+// the struct's own old_to_new_idx[r].
+int uspmv_scs_update_values(uspmv_scs_t *s, const uspmv_coo_t *m, const int32_t *col_perm, int check_pattern) {
+    const char *who = "uspmv_scs_update_values";
+    if (!s || !m) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    if (!uspmv::scs_has_entries(s)) return uspmv::fail(USPMV_ERR_INVALID, "%s: layout-only struct (its entries live on the device: uspmv_dmat_update_values_from_arrays)", who);
+    const int64_t n_rows = s->n_rows, nnz = m->nnz, C = s->C, n_pad = s->n_rows_padded;
+    if (m->n_rows != n_rows)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: the matrix has %lld rows, the struct %lld (the pattern changed)", who, (long long)m->n_rows, (long long)n_rows);
+    const int32_t *I = m->I.data(), *J = m->J.data();
+    for (int64_t k = 0; k < nnz; ++k)
+        if (I[k] < 0 || I[k] >= n_rows) return uspmv::fail(USPMV_ERR_INVALID, "%s: a row index lies outside [0, n_rows)", who);
+    std::vector<int64_t> start((size_t)n_rows + 1, 0);
+    for (int64_t k = 0; k < nnz; ++k) {
+        if (k > 0 && I[k] < I[k - 1])
+            return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: COO entries must be sorted by row (uspmv_read_mtx and the generators produce that order)", who);
+        ++start[(size_t)I[k] + 1];
+    }
+    for (int64_t r = 0; r < n_rows; ++r) start[(size_t)r + 1] += start[(size_t)r];
+    const int32_t *pos = s->old_to_new_idx.data();
+    std::vector<int32_t> row_at((size_t)n_pad, -1);
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const int64_t p = pos[r];
+        if (p < 0 || p >= n_pad) return uspmv::fail(USPMV_ERR_INVALID, "%s: row_pos has an entry outside [0, n_rows_padded)", who);
+        if (start[(size_t)r + 1] - start[(size_t)r] > s->chunk_lengths[(size_t)(p / C)])
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: a row has more entries than the chunk it sits in is long (the pattern changed)", who);
+    }
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (row_at[(size_t)pos[r]] >= 0) return uspmv::fail(USPMV_ERR_INVALID, "%s: row_pos sends two rows to one position", who);
+        row_at[(size_t)pos[r]] = (int32_t)r;
+    }
+    auto slot0 = [&](int64_t q) { return (int64_t)s->chunk_ptrs[(size_t)(q / C)] + q % C; };
+    if (check_pattern) {
+        int64_t bad = -1;
+#pragma omp parallel for schedule(static) reduction(max : bad)
+        for (int64_t r = 0; r < n_rows; ++r) {
+            const int64_t dst = slot0(pos[r]);
+            for (int64_t k = start[(size_t)r]; k < start[(size_t)r + 1]; ++k) {        // (bad = nnz - the FIRST offending entry)
+                int32_t col = J[k];
+                if (col_perm && col >= 0 && col < n_rows) col = col_perm[col];
+                if (s->col_idxs[(size_t)(dst + (k - start[(size_t)r]) * C)] != col) bad = std::max(bad, nnz - k);
+            }
+        }
+        if (bad >= 0)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: entry %lld: its column differs from the stored one (the pattern changed)", who, (long long)(nnz - bad));
+    }
+#pragma omp parallel for schedule(static)
+    for (int64_t q = 0; q < n_pad; ++q) {
+        const int64_t dst = slot0(q), L = s->chunk_lengths[(size_t)(q / C)];
+        const int32_t r = row_at[(size_t)q];
+        const int64_t s0 = r >= 0 ? start[(size_t)r] : 0, n = r >= 0 ? start[(size_t)r + 1] - s0 : 0;
+        for (int64_t j = 0; j < L; ++j) {
+            const double v = j < n ? m->values[(size_t)(s0 + j)] : 0.0;   // +0 beyond the row's entries; the slot keeps its stored column
+            const size_t e = (size_t)(dst + j * C);
+            if (s->dtype == USPMV_F64) s->values_f64[e] = v;
+            else if (s->dtype == USPMV_F32) s->values_f32[e] = (float)v;
+            else s->values_f16[e] = uspmv_f64_to_f16(v);
+        }
+    }
+    return USPMV_OK;
+}
+
 int uspmv_coo_equilibrate(uspmv_coo_t *m) {
     // equilibrate_matrix (code/utilities.hpp:2667-2685, -equilibrate 1 of a one-precision run): every value divided
     // by the largest magnitude of its row, then by the largest magnitude of its column in the row-scaled matrix.

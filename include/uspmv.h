@@ -475,6 +475,37 @@ int uspmv_dmat_set_crs(uspmv_dmat_t *m, int on);
  * code/kernels.hpp:579-775), i.e. the GPU twins of spmv_omp_scs_adv / spmv_omp_scs /
  * spmv_omp_csr.  d_x: padded_vec_size elements; d_y: n_rows_padded elements written. */
 int uspmv_spmv(const uspmv_dmat_t *A, const void *d_x, void *d_y, void *stream);
+/* The fused update y = alpha A x + beta z with two dot products (no reference counterpart): what a residual, a CG step
+ * or a Chebyshev / KPM recurrence does around an SpMV, applied where the kernel stores y instead of in extra passes over the vectors.
+ * Numerics, with t_i exactly what uspmv_spmv stores for row i (the slot-ordered FMA chain) and alpha, beta converted ONCE to the handle's
+ * value type:  beta == 0: y_i = rn(alpha t_i), z is never read (may be NULL, may hold NaN);  else y_i = rn(rn(alpha t_i) + rn(beta z_i)),
+ * three separately rounded operations, never an FMA -- numpy arithmetic in the handle's type restates it bit for bit.  alpha = 1, beta = 0
+ * gives uspmv_spmv's y.  Rows the call does not own stay untouched, as with uspmv_spmv.  Non-finite alpha / beta simply propagate.
+ * dots (both accumulated in double from operands widened to double, one rounding per product): dots[0] = <y,y>, dots[1] = <w,y> over rows
+ * [0, n_dot_rows); bitwise reproducible from call to call on the same handle, plan and tuning: every workgroup stores its two partial
+ * sums at the slot of its logical id in a workspace of the handle, one small kernel on the same stream adds the slots in a fixed order --
+ * no floating-point atomics, no host synchronisation.  The workspace is allocated on first use or by uspmv_spmv_axpby_reserve; a call that
+ * would have to allocate while its stream is capturing returns USPMV_ERR_INVALID.  Not thread-safe per handle.
+ * Refused before anything is launched or written: USPMV_ERR_UNSUPPORTED an F16 handle or a part of an adaptive-precision split;
+ * USPMV_ERR_INVALID NULL op / d_x / d_y, beta != 0 with NULL d_z, d_z overlapping d_y partially (d_z == d_y, in place, is allowed),
+ * n_dot_rows outside [0, rows y may be written].  d_y must NOT overlap d_x (not checked: a planless handle cannot know x's length). */
+typedef struct {
+    double alpha, beta;   /* converted ONCE to the handle's value type; all arithmetic is in that type */
+    const void *d_z;      /* rows-y-may-be-written elements in y's row order; NULL allowed iff beta == 0; may be d_y itself (in place) */
+    const void *d_w;      /* optional, y's row order: the second factor of dots[1]; NULL: dots[1] = 0, w never read */
+    double *d_dots;       /* optional, 2 doubles on the device: dots[0] = <y,y>, dots[1] = <w,y>; NULL: no reduction at all */
+    int64_t n_dot_rows;   /* rows [0, n_dot_rows) of y enter the dots (the caller's n_rows: padding rows stay out) */
+} uspmv_axpby_t;
+int uspmv_spmv_axpby(const uspmv_dmat_t *A, const void *d_x, void *d_y, const uspmv_axpby_t *op, void *stream);
+/* Which way a call with this x goes, by the conditions the launcher uses: 1 fused in the epilogue of the SpMV kernel (every kernel
+ * uspmv_spmv launches under the default tuning), 2 uspmv_spmv followed by one vector pass with the same epilogue (non-default "unroll",
+ * "tail_batch", "nontemporal", "sweep_unroll", "sweep_pair", "spmv_variant", ablations).  An x off the 16-byte grid takes a planned
+ * handle to the lane-per-row kernel, as in uspmv_spmv, which is fused under the default tuning as well.
+ * Same numerics either way; the dots' summation order belongs to the path. */
+int uspmv_spmv_axpby_path(const uspmv_dmat_t *A, const void *d_x, int *path);
+/* Allocate the handle's workspace now (before a stream capture): the partial sums of either path under the current tuning, and the
+ * in-place temporary of path 2 (one vector) where the handle takes path 2 under that tuning. */
+int uspmv_spmv_axpby_reserve(uspmv_dmat_t *A);
 /* Same over a subset of chunks (d_chunk_ids[n_ids], ascending): interior / boundary split used to
  * overlap the halo exchange with the kernel (absent in the reference, code/main.cpp:464-468). */
 int uspmv_spmv_chunks(const uspmv_dmat_t *A, const int32_t *d_chunk_ids, int64_t n_ids, const void *d_x,

@@ -246,6 +246,21 @@ public:
         return d;
     }
     void spmv(const void *d_x, void *d_y, void *stream = nullptr) const { uspmv_detail::check(uspmv_spmv(h_, d_x, d_y, stream), "uspmv_spmv"); }
+    // y = alpha A x + beta z with <y,y> and <w,y> (uspmv_spmv_axpby): d_z may be d_y (in place) and is not read when beta == 0; d_dots:
+    // two doubles on the device or null; n_dot_rows < 0: all rows y may be written.  d_y must not overlap d_x.
+    void spmv_axpby(const void *d_x, void *d_y, double alpha, double beta, const void *d_z = nullptr, const void *d_w = nullptr,
+                    double *d_dots = nullptr, ST n_dot_rows = -1, void *stream = nullptr) const {
+        const uspmv_axpby_t op{alpha, beta, d_z, d_w, d_dots, n_dot_rows < 0 ? (int64_t)n_rows_padded_ : (int64_t)n_dot_rows};
+        uspmv_detail::check(uspmv_spmv_axpby(h_, d_x, d_y, &op, stream), "uspmv_spmv_axpby");
+    }
+    // 1: fused in the SpMV kernel's epilogue, 2: SpMV + one vector pass
+    int spmv_axpby_path(const void *d_x) const {
+        int path = 0;
+        uspmv_detail::check(uspmv_spmv_axpby_path(h_, d_x, &path), "uspmv_spmv_axpby_path");
+        return path;
+    }
+    // the workspace of spmv_axpby now, e.g. before a stream capture
+    void axpby_reserve() { uspmv_detail::check(uspmv_spmv_axpby_reserve(h_), "uspmv_spmv_axpby_reserve"); }
     // a column-major X that does not change between calls (a bench loop): re-laid out once, until x_released() or another X
     void x_prepared(const void *d_X, int b, ST ld, void *stream = nullptr) const { uspmv_detail::check(uspmv_spmmv_x_prepared(h_, d_X, b, ld, stream), "uspmv_spmmv_x_prepared"); }
     void x_released() const { uspmv_detail::check(uspmv_spmmv_x_release(h_), "uspmv_spmmv_x_release"); }

@@ -109,6 +109,9 @@ _SIGS = {
     "uspmv_dmat_set_crs": (C.c_int, [_vp, C.c_int]),
     "uspmv_dmat_optimize": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_spmv": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "uspmv_spmv_axpby": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "uspmv_spmv_axpby_path": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
+    "uspmv_spmv_axpby_reserve": (C.c_int, [_vp]),
     "uspmv_spmv_chunks": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "uspmv_spmv_tiles": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "uspmv_dmat_tile_rows": (C.c_int, [_vp, C.POINTER(C.c_int)]),
@@ -1293,6 +1296,10 @@ class DeviceMatrix:
         self.tile_rows = tr.value          # 0: no plan was built
         return a.value, b.value
 
+    def axpby_reserve(self):
+        """Allocate the workspace of spmv_axpby now, e.g. before a stream capture (uspmv_spmv_axpby_reserve)."""
+        _ck(lib().uspmv_spmv_axpby_reserve(self.h))
+
     def values_changed(self, stream=None):
         """The value array has new contents on the same pattern (an in-place write of self.values, say): bring every plan on the handle back
         in line with it (uspmv_dmat_values_changed).  Returns the actions, a mask of REFRESH_*; 0: the plans read the array in place."""
@@ -1610,6 +1617,33 @@ def spmv(A, x, y, stream=None):
     assert x.dtype == A.torch_dtype and y.dtype == A.torch_dtype and y.numel() >= A.n_rows_padded
     _ck(lib().uspmv_spmv(A.h, _dp(x), _dp(y), _stream_ptr(stream)))
     return y
+
+
+class AxpbyOp(C.Structure):
+    """uspmv_axpby_t"""
+    _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("d_z", C.c_void_p), ("d_w", C.c_void_p), ("d_dots", C.c_void_p),
+                ("n_dot_rows", C.c_int64)]
+
+
+def spmv_axpby(A, x, y, alpha=1.0, beta=0.0, z=None, w=None, dots=None, n_dot_rows=None, stream=None):
+    """y = alpha A x + beta z on the device (uspmv_spmv_axpby): z may be y itself, and is not read when beta == 0.  dots: a 2-element
+    float64 CUDA tensor that receives <y,y> and <w,y> (0 without w) over rows [0, n_dot_rows); n_dot_rows defaults to all rows y may
+    be written."""
+    import torch
+    assert x.dtype == A.torch_dtype and y.dtype == A.torch_dtype and y.numel() >= A.n_rows_padded
+    for v in (z, w):
+        assert v is None or (v.dtype == A.torch_dtype and v.numel() >= A.n_rows_padded and v.is_contiguous())
+    assert dots is None or (dots.dtype == torch.float64 and dots.numel() == 2 and dots.is_cuda and dots.is_contiguous())
+    op = AxpbyOp(float(alpha), float(beta), _dp(z), _dp(w), _dp(dots), A.n_rows_padded if n_dot_rows is None else int(n_dot_rows))
+    _ck(lib().uspmv_spmv_axpby(A.h, _dp(x), _dp(y), C.byref(op), _stream_ptr(stream)))
+    return y
+
+
+def spmv_axpby_path(A, x):
+    """1: spmv_axpby with this x runs fused in the SpMV kernel's epilogue, 2: SpMV + one vector pass (uspmv_spmv_axpby_path)."""
+    p = C.c_int(0)
+    _ck(lib().uspmv_spmv_axpby_path(A.h, _dp(x), C.byref(p)))
+    return p.value
 
 
 def spmv_chunks(A, chunk_ids, x, y, stream=None):

@@ -36,20 +36,26 @@ namespace {
 // IDS: virtual chunk v -> chunk_ids[v] (interior / boundary subsets).
 // ABL != 0: measurement-only ablations (WRONG results): 1 = every gather hits one 512-byte window
 // of x (keeps the instruction stream, removes L1 misses), 2 = no gather at all.
-template <typename VT, int CT, int U, bool NT, bool IDS, int ABL = 0, bool TAILB = false>
+// EP (here and in the kernels below, always the LAST template parameter, off by default): EP = 1 is uspmv_spmv_axpby's path 1 -- the one
+// store site of the kernel stores axpby_row's value and the kernel ends in axpby_reduce, which every thread must reach: lanes the plain
+// form sends home early stay, own no row and add zero terms.  With EP = 0 `ep` is never read and every branch on EP folds away.
+// (z may be y itself, which y's __restrict__ does not cover: the lane that stores a row is the one that read its z, and the stored
+// value depends on that load.)
+template <typename VT, int CT, int U, bool NT, bool IDS, int ABL = 0, bool TAILB = false, int EP = 0>
 __global__ void scs_spmv_rows(const long n_work_chunks, const int C_rt, const int *__restrict__ chunk_ptrs,
                               const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs,
                               const VT *__restrict__ values, const VT *__restrict__ x, VT *__restrict__ y,
-                              const int *__restrict__ chunk_ids, const int xcd_remap, const long n_store) {
+                              const int *__restrict__ chunk_ids, const int xcd_remap, const long n_store, const AxpbyArgs<VT> ep) {
     const int C = CT > 0 ? CT : C_rt;
     const unsigned lb = remap_block(blockIdx.x, gridDim.x, xcd_remap);
     const long vrow = (long)lb * blockDim.x + threadIdx.x;
     const long vc = vrow / C;
     const int i = (int)(vrow - vc * C);
-    if (vc >= n_work_chunks) return;
-    const long c = IDS ? (long)chunk_ids[vc] : vc;
-    const long cs = chunk_ptrs[c];
-    const int L = chunk_lengths[c];
+    if constexpr (EP == 0) { if (vc >= n_work_chunks) return; }
+    const bool live = EP == 0 || vc < n_work_chunks;
+    const long c = !live ? 0 : IDS ? (long)chunk_ids[vc] : vc;
+    const long cs = live ? chunk_ptrs[c] : 0;
+    const int L = live ? chunk_lengths[c] : 0;
     const VT *vp = values + cs + i;
     const int *cp = col_idxs + cs + i;
     VT acc = VT(0);
@@ -96,7 +102,14 @@ __global__ void scs_spmv_rows(const long n_work_chunks, const int C_rt, const in
             acc = fma_t(v, ABL == 0 ? x[ci] : ABL == 1 ? x[ci & 63] : (VT)ci, acc);
         }
     }
-    if (c * C + i < n_store) st_y<NT>(y + (c * C + i), acc);   // n_store < n_rows_padded only for re-chunked structs
+    if constexpr (EP == 0) {
+        if (c * C + i < n_store) st_y<NT>(y + (c * C + i), acc);   // n_store < n_rows_padded only for re-chunked structs
+    } else {
+        extern __shared__ __attribute__((aligned(16))) unsigned char rows_smem[];   // (AXPBY_RED_BYTES, fused launches only)
+        double d0 = 0.0, d1 = 0.0;
+        if (live && c * C + i < n_store) st_y<NT>(y + (c * C + i), axpby_row(ep, c * C + i, acc, d0, d1));
+        axpby_reduce(ep, lb, d0, d1, (double *)rows_smem);
+    }
 }
 
 // Software-pipelined form of scs_spmv_rows (same lane <-> row mapping, same FMA chain, bit-exact):
@@ -211,14 +224,16 @@ __device__ __forceinline__ float ld_sys(const float *p) {
 // same address in all lanes of the chunk.  The other chunks of such a tile read one 16-bit position per entry into the same array, eight
 // per lane and batch, through the same loop; tiles without intervals run as without ADD.  Value loads, slot order and FMA chain are those of the other forms: bit-identical y.
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-template <typename VT, int CT, bool NT, bool IDS, int SYNC = 0, bool I12 = false, bool ELEM = false, bool ADD = false>
+template <typename VT, int CT, bool NT, bool IDS, int SYNC = 0, bool I12 = false, bool ELEM = false, bool ADD = false, int EP = 0>
 __global__ void __launch_bounds__(1024) scs_spmv_tlc(const long n_chunks, const int C_rt, const int *__restrict__ chunk_ptrs,
         const int *__restrict__ chunk_lengths, const int *__restrict__ col_idxs, const VT *__restrict__ values,
         const VT *__restrict__ x_arg, VT *__restrict__ y, const int *__restrict__ tile_line_ptr,
         const int *__restrict__ tile_lines, const unsigned *__restrict__ c16_ptrs,
         const unsigned short *__restrict__ col16, const long x_len, const int *__restrict__ tile_ids,
-        const int xcd_remap, const long n_store, const StepArgs sa, const int *__restrict__ row_map, const AddArgs aa) {
+        const int xcd_remap, const long n_store, const StepArgs sa, const int *__restrict__ row_map, const AddArgs aa,
+        const AxpbyArgs<VT> ep) {
     static_assert(!ADD || (SYNC == 0 && !ELEM && !IDS), "additive chunk records: the plain single-struct launch only");
+    static_assert(EP == 0 || (SYNC == 0 && !IDS), "fused epilogue: the plain launch over all tiles only (no early return ahead of the reduction)");
     extern __shared__ __attribute__((aligned(16))) unsigned char tlc_smem[];
     VT *xs = (VT *)tlc_smem;
     constexpr int EPL = 16 / (int)sizeof(VT);   // elements per 16-byte load
@@ -473,15 +488,27 @@ __global__ void __launch_bounds__(1024) scs_spmv_tlc(const long n_chunks, const 
             acc = fma_t(ld_stream<NT>(vp + (long)j * C), (SYNC == 1 && coh) ? ld_sys(x + cj) : x[cj], acc);
         }
     }
-    if constexpr (ELEM) {
-        if (row_map) {                                       // rows dealt to the tiles by the matrix graph: y through the plan's row map (plain stores: the L2 merges them)
-            if (valid) { const long yr = row_map[row]; if (yr < n_store) y[yr] = acc; }
-            return;
+    if constexpr (EP == 0) {
+        if constexpr (ELEM) {
+            if (row_map) {                                       // rows dealt to the tiles by the matrix graph: y through the plan's row map (plain stores: the L2 merges them)
+                if (valid) { const long yr = row_map[row]; if (yr < n_store) y[yr] = acc; }
+                return;
+            }
         }
+        if (valid && row < n_store) st_y<NT>(y + row, acc);
+    } else {
+        // the same two stores; z, w and the n_dot test go by the row that is STORED (the mapped one on dealt rows)
+        double d0 = 0.0, d1 = 0.0;
+        bool dealt = false;
+        if constexpr (ELEM) dealt = row_map != nullptr;
+        if (dealt) {
+            if (valid) { const long yr = row_map[row]; if (yr < n_store) y[yr] = axpby_row(ep, yr, acc, d0, d1); }
+        } else if (valid && row < n_store) {
+            st_y<NT>(y + row, axpby_row(ep, row, acc, d0, d1));
+        }
+        axpby_reduce(ep, lbt, d0, d1, (double *)tlc_smem);   // (the x window is dead: the front of it)
     }
-    if (valid && row < n_store) st_y<NT>(y + row, acc);
 }
-
 
 // C = 32, one wavefront per chunk, two lanes per row: lane l owns row l & 31 and the slots
 // j == (l >> 5) (mod 2), so every wave-instruction of the matrix stream is one contiguous
@@ -530,10 +557,10 @@ __global__ void scs_spmv_split2(const long n_chunks, const int *__restrict__ chu
 // CRS SpMV: G lanes per row (G = power of two <= 64), lane-strided partial sums, shuffle
 // reduction.  The reference's own loop is `omp simd`-reassociated (code/kernels.hpp:49), so
 // there is no canonical order to be bit-exact with; compared with a tolerance.
-template <typename VT, int G, bool NT>
+template <typename VT, int G, bool NT, int EP = 0>
 __global__ void csr_spmv_vector(const long n_rows, const int *__restrict__ row_ptrs,
                                 const int *__restrict__ col_idxs, const VT *__restrict__ values,
-                                const VT *__restrict__ x, VT *__restrict__ y) {
+                                const VT *__restrict__ x, VT *__restrict__ y, const AxpbyArgs<VT> ep) {
     const long gt = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long row = gt / G;
     const int g = (int)(gt % G);
@@ -544,7 +571,52 @@ __global__ void csr_spmv_vector(const long n_rows, const int *__restrict__ row_p
     }
 #pragma unroll
     for (int o = G / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (row < n_rows && g == 0) y[row] = acc;
+    if constexpr (EP == 0) {
+        if (row < n_rows && g == 0) y[row] = acc;
+    } else {
+        extern __shared__ __attribute__((aligned(16))) unsigned char csr_smem[];   // (AXPBY_RED_BYTES, fused launches only)
+        double d0 = 0.0, d1 = 0.0;
+        if (row < n_rows && g == 0) y[row] = axpby_row(ep, row, acc, d0, d1);
+        axpby_reduce(ep, blockIdx.x, d0, d1, (double *)csr_smem);
+    }
+}
+// Path 2 of uspmv_spmv_axpby: one pass over the stored t = A x (t may be y), V rows per thread through one load of V elements (V = 1
+// where a vector is off the 16-byte grid) -- the same epilogue routine and the same kind of partials as the fused kernels.
+template <typename VT, int V>
+__global__ void __launch_bounds__(256) axpby_pass_kernel(const VT *t, VT *y, const long n, const AxpbyArgs<VT> ep) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pass_smem[];
+    typedef VT vec_t __attribute__((ext_vector_type(V)));
+    const long r0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    double d0 = 0.0, d1 = 0.0;
+    if constexpr (V > 1) {
+        if (r0 + V <= n) {
+            const vec_t tv = *(const vec_t *)(t + r0);
+            vec_t o;
+#pragma unroll
+            for (int e = 0; e < V; ++e) o[e] = axpby_row(ep, r0 + e, tv[e], d0, d1);
+            *(vec_t *)(y + r0) = o;
+        } else {
+            for (long r = r0; r < n; ++r) y[r] = axpby_row(ep, r, t[r], d0, d1);
+        }
+    } else {
+        if (r0 < n) y[r0] = axpby_row(ep, r0, t[r0], d0, d1);
+    }
+    axpby_reduce(ep, blockIdx.x, d0, d1, (double *)pass_smem);
+}
+// the slots' sums in one fixed order: thread k adds slots k, k + 1024, ... in that order, then the threads as in axpby_reduce
+__global__ void __launch_bounds__(1024) axpby_finalize_kernel(const double *__restrict__ part, const long slots, double *__restrict__ dots) {
+    __shared__ double red[2 * 16];
+    double d0 = 0.0, d1 = 0.0;
+    for (long k = threadIdx.x; k < slots; k += 1024) { d0 = add_rn_t(d0, part[2 * k]); d1 = add_rn_t(d1, part[2 * k + 1]); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { d0 = add_rn_t(d0, __shfl_xor(d0, o, 64)); d1 = add_rn_t(d1, __shfl_xor(d1, o, 64)); }
+    if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = d0; red[2 * (threadIdx.x >> 6) + 1] = d1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s0 = 0.0, s1 = 0.0;
+        for (int k = 0; k < 16; ++k) { s0 = add_rn_t(s0, red[2 * k]); s1 = add_rn_t(s1, red[2 * k + 1]); }
+        dots[0] = s0; dots[1] = s1;
+    }
 }
 
 // ------------------------------------------------------------------------------------------ launchers
@@ -564,18 +636,18 @@ void launch_rows_ids(bool ids, unsigned grid, int block, hipStream_t st, long nw
     if (g_tune.tail_batch && U > 1) {
         if (ids)
             hipLaunchKernelGGL((scs_spmv_rows<VT, CT, U, NT, true, 0, true>), dim3(grid), dim3(block), 0, st, nwc, C, A->chunk_ptrs,
-                               A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store);
+                               A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store, AxpbyArgs<VT>{});
         else
             hipLaunchKernelGGL((scs_spmv_rows<VT, CT, U, NT, false, 0, true>), dim3(grid), dim3(block), 0, st, nwc, C, A->chunk_ptrs,
-                               A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store);
+                               A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store, AxpbyArgs<VT>{});
         return;
     }
     if (ids)
         hipLaunchKernelGGL((scs_spmv_rows<VT, CT, U, NT, true>), dim3(grid), dim3(block), 0, st, nwc, C, A->chunk_ptrs,
-                           A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store);
+                           A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store, AxpbyArgs<VT>{});
     else
         hipLaunchKernelGGL((scs_spmv_rows<VT, CT, U, NT, false>), dim3(grid), dim3(block), 0, st, nwc, C, A->chunk_ptrs,
-                           A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store);
+                           A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store, AxpbyArgs<VT>{});
 }
 
 template <typename VT, int CT, int U>
@@ -596,13 +668,29 @@ void launch_rows_unroll(bool ids, unsigned grid, int block, hipStream_t st, long
     }
 }
 
+// the fused form of scs_spmv_rows exists for the default tuning only: unroll 8, non-temporal stream, plain tail
+bool rows_axpby_fused() {
+    return g_tune.unroll == 8 && g_tune.nontemporal && !g_tune.tail_batch && g_tune.spmv_variant == 0 && !g_tune.ablate;
+}
+template <typename VT, int CT>
+void launch_rows_axpby(bool ids, unsigned grid, int block, hipStream_t st, long nwc, int C, const uspmv_dmat *A, const VT *x, VT *y,
+                       const int *chunk_ids, const AxpbyArgs<VT> &ep) {
+    if (ids)
+        hipLaunchKernelGGL((scs_spmv_rows<VT, CT, 8, true, true, 0, false, 1>), dim3(grid), dim3(block), AXPBY_RED_BYTES, st, nwc, C, A->chunk_ptrs,
+                           A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store, ep);
+    else
+        hipLaunchKernelGGL((scs_spmv_rows<VT, CT, 8, true, false, 0, false, 1>), dim3(grid), dim3(block), AXPBY_RED_BYTES, st, nwc, C, A->chunk_ptrs,
+                           A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store, ep);
+}
+
 }  // namespace
 
 namespace uspmv_dev {
 
 template <typename VT>
-int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, const VT *x, VT *y, hipStream_t st) {
+int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep) {
     if (n_tiles == 0) return USPMV_OK;
+    if (ep && (tile_ids || !g_tune.nontemporal)) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_spmv_tlc: no fused instantiation for this launch");
     const int C = (int)A->C;
     unsigned grid = (unsigned)n_tiles;
     const bool elem = A->tlc.elem;
@@ -628,11 +716,26 @@ int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, cons
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(block), lds, st, (long)A->n_chunks, C, A->chunk_ptrs,        \
                            A->chunk_lengths, A->tlc.cols ? A->tlc.cols : A->col_idxs, (const VT *)(A->tlc.values ? A->tlc.values : A->values), x, y, lptr, llist,   \
-                           iptrs, idata, (long)A->tlc.x_len, tile_ids, g_tune.xcd_remap, A->n_store, StepArgs{}, (const int *)A->tlc.row_map, aa);  \
+                           iptrs, idata, (long)A->tlc.x_len, tile_ids, g_tune.xcd_remap, A->n_store, StepArgs{}, (const int *)A->tlc.row_map, aa, AxpbyArgs<VT>{});  \
     } while (0)
 #define TLC_LAUNCH_C(NTV, IDSV) do { if (C == 32) TLC_LAUNCH(32, NTV, IDSV); else TLC_LAUNCH(0, NTV, IDSV); } while (0)
+    // the same choice among the fused instantiations (all tiles, non-temporal stream); the reduction needs the front of the window
+#define TLC_AXPBY(CTV)                                                                                                \
+    do {                                                                                                              \
+        auto kfn = i12 ? scs_spmv_tlc<VT, CTV, true, false, 0, true, false, false, 1> : scs_spmv_tlc<VT, CTV, true, false, 0, false, false, false, 1>; \
+        if (elem) kfn = i12 ? scs_spmv_tlc<VT, CTV, true, false, 0, true, true, false, 1> : scs_spmv_tlc<VT, CTV, true, false, 0, false, true, false, 1>; \
+        if (add) kfn = i12 ? scs_spmv_tlc<VT, CTV, true, false, 0, true, false, true, 1> : scs_spmv_tlc<VT, CTV, true, false, 0, false, false, true, 1>; \
+        const size_t lds_ep = std::max(lds, (size_t)AXPBY_RED_BYTES);                                                 \
+        if (lds_ep > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ep); \
+        hipLaunchKernelGGL(kfn, dim3(grid), dim3(block), lds_ep, st, (long)A->n_chunks, C, A->chunk_ptrs,             \
+                           A->chunk_lengths, A->tlc.cols ? A->tlc.cols : A->col_idxs, (const VT *)(A->tlc.values ? A->tlc.values : A->values), x, y, lptr, llist,   \
+                           iptrs, idata, (long)A->tlc.x_len, (const int *)nullptr, g_tune.xcd_remap, A->n_store, StepArgs{}, (const int *)A->tlc.row_map, aa, *ep);  \
+    } while (0)
+    if (ep) { if (C == 32) TLC_AXPBY(32); else TLC_AXPBY(0); }
+    else
     if (tile_ids) { if (g_tune.nontemporal) TLC_LAUNCH_C(true, true); else TLC_LAUNCH_C(false, true); }
     else { if (g_tune.nontemporal) TLC_LAUNCH_C(true, false); else TLC_LAUNCH_C(false, false); }
+#undef TLC_AXPBY
 #undef TLC_LAUNCH_C
 #undef TLC_LAUNCH
     HIP_TRY(hipGetLastError());
@@ -655,7 +758,7 @@ int launch_spmv_tlc_step(const uspmv_dmat *A, const int *step_ids, const StepArg
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(kfn, dim3((unsigned)n), dim3(A->tlc.tile_rows), lds, st, (long)A->n_chunks, C, A->chunk_ptrs,  \
                            A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, A->tlc.line_ptr, A->tlc.lines,   \
-                           iptrs, idata, (long)A->tlc.x_len, step_ids, g_tune.xcd_remap, A->n_store, sa, (const int *)nullptr, AddArgs{}); \
+                           iptrs, idata, (long)A->tlc.x_len, step_ids, g_tune.xcd_remap, A->n_store, sa, (const int *)nullptr, AddArgs{}, AxpbyArgs<VT>{}); \
     } while (0)
     if (sync == 1) { if (C == 32) TLC_STEP(32, 1); else TLC_STEP(0, 1); }
     else { if (C == 32) TLC_STEP(32, 2); else TLC_STEP(0, 2); }
@@ -665,7 +768,7 @@ int launch_spmv_tlc_step(const uspmv_dmat *A, const int *step_ids, const StepArg
 }
 
 template <typename VT>
-int launch_spmv_scs(const uspmv_dmat *A, const int *chunk_ids, long n_ids, const VT *x, VT *y, hipStream_t st) {
+int launch_spmv_scs(const uspmv_dmat *A, const int *chunk_ids, long n_ids, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep) {
     const bool ids = chunk_ids != nullptr;
     const long nwc = ids ? n_ids : A->n_chunks;
     if (nwc == 0) return USPMV_OK;
@@ -673,11 +776,32 @@ int launch_spmv_scs(const uspmv_dmat *A, const int *chunk_ids, long n_ids, const
     const int block = g_tune.block;
     if (!ids && A->sw.on && A->sw.tile_ids && A->sw.n_parts == 1 && g_tune.sweep && !g_tune.ablate && g_tune.spmv_variant == 0 && ((uintptr_t)x % 16 == 0)) {
         // column-window sweep over the tiles that qualify, lane-per-row gather kernel over the chunks that are left
-        if (int rc = launch_spmv_sweep<VT>(A, x, y, st)) return rc;
-        return A->sw.n_rest ? launch_spmv_scs<VT>(A, A->sw.rest, (long)A->sw.n_rest, x, y, st) : USPMV_OK;
+        if (int rc = launch_spmv_sweep<VT>(A, x, y, st, ep)) return rc;
+        if (!A->sw.n_rest) return USPMV_OK;
+        if (!ep) return launch_spmv_scs<VT>(A, A->sw.rest, (long)A->sw.n_rest, x, y, st);
+        AxpbyArgs<VT> rest = *ep;                 // the second launch of the call owns the slots behind the sweep tiles'
+        rest.slot0 += (unsigned)A->sw.n_tiles;
+        return launch_spmv_scs<VT>(A, A->sw.rest, (long)A->sw.n_rest, x, y, st, &rest);
     }
     if (!ids && A->tlc.on && A->tlc.plan_id == 0 && g_tune.tlc && !g_tune.ablate && g_tune.spmv_variant == 0 && ((uintptr_t)x % 16 == 0))
-        return launch_spmv_tlc<VT>(A, nullptr, A->tlc.n_tiles, x, y, st);
+        return launch_spmv_tlc<VT>(A, nullptr, A->tlc.n_tiles, x, y, st, ep);
+    if (ep) {
+        if (!rows_axpby_fused()) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_spmv_scs: no fused instantiation under this tuning");
+        const unsigned grid = grid_for(nwc * C, block);
+        switch (C) {
+            case 1: launch_rows_axpby<VT, 1>(ids, grid, block, st, nwc, C, A, x, y, chunk_ids, *ep); break;
+            case 2: launch_rows_axpby<VT, 2>(ids, grid, block, st, nwc, C, A, x, y, chunk_ids, *ep); break;
+            case 4: launch_rows_axpby<VT, 4>(ids, grid, block, st, nwc, C, A, x, y, chunk_ids, *ep); break;
+            case 8: launch_rows_axpby<VT, 8>(ids, grid, block, st, nwc, C, A, x, y, chunk_ids, *ep); break;
+            case 16: launch_rows_axpby<VT, 16>(ids, grid, block, st, nwc, C, A, x, y, chunk_ids, *ep); break;
+            case 32: launch_rows_axpby<VT, 32>(ids, grid, block, st, nwc, C, A, x, y, chunk_ids, *ep); break;
+            case 64: launch_rows_axpby<VT, 64>(ids, grid, block, st, nwc, C, A, x, y, chunk_ids, *ep); break;
+            case 128: launch_rows_axpby<VT, 128>(ids, grid, block, st, nwc, C, A, x, y, chunk_ids, *ep); break;
+            default: launch_rows_axpby<VT, 0>(ids, grid, block, st, nwc, C, A, x, y, chunk_ids, *ep); break;
+        }
+        HIP_TRY(hipGetLastError());
+        return USPMV_OK;
+    }
     if (!ids && C == 32 && g_tune.spmv_variant == 1) {
         const unsigned grid = grid_for(nwc * 64, block);
         if (g_tune.nontemporal)
@@ -691,10 +815,10 @@ int launch_spmv_scs(const uspmv_dmat *A, const int *chunk_ids, long n_ids, const
         if (g_tune.ablate && C == 32 && !ids) {  // measurement-only (results are wrong by construction)
             if (g_tune.ablate == 1)
                 hipLaunchKernelGGL((scs_spmv_rows<VT, 32, 8, true, false, 1>), dim3(grid), dim3(block), 0, st, nwc, C, A->chunk_ptrs,
-                                   A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store);
+                                   A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store, AxpbyArgs<VT>{});
             else
                 hipLaunchKernelGGL((scs_spmv_rows<VT, 32, 8, true, false, 2>), dim3(grid), dim3(block), 0, st, nwc, C, A->chunk_ptrs,
-                                   A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store);
+                                   A->chunk_lengths, A->col_idxs, (const VT *)A->values, x, y, chunk_ids, g_tune.xcd_remap, A->n_store, AxpbyArgs<VT>{});
             HIP_TRY(hipGetLastError());
             return USPMV_OK;
         }
@@ -715,44 +839,104 @@ int launch_spmv_scs(const uspmv_dmat *A, const int *chunk_ids, long n_ids, const
 }
 
 template <typename VT, int G>
-void launch_csr_g(long n_rows, const int *rp, const int *ci, const VT *va, const VT *x, VT *y, hipStream_t st) {
+void launch_csr_g(long n_rows, const int *rp, const int *ci, const VT *va, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep) {
     const unsigned grid = grid_for(n_rows * G, 256);
-    if (g_tune.nontemporal)
-        hipLaunchKernelGGL((csr_spmv_vector<VT, G, true>), dim3(grid), dim3(256), 0, st, n_rows, rp, ci, va, x, y);
+    if (ep)   // (non-temporal stream only: spmv_axpby_route)
+        hipLaunchKernelGGL((csr_spmv_vector<VT, G, true, 1>), dim3(grid), dim3(256), AXPBY_RED_BYTES, st, n_rows, rp, ci, va, x, y, *ep);
+    else if (g_tune.nontemporal)
+        hipLaunchKernelGGL((csr_spmv_vector<VT, G, true>), dim3(grid), dim3(256), 0, st, n_rows, rp, ci, va, x, y, AxpbyArgs<VT>{});
     else
-        hipLaunchKernelGGL((csr_spmv_vector<VT, G, false>), dim3(grid), dim3(256), 0, st, n_rows, rp, ci, va, x, y);
+        hipLaunchKernelGGL((csr_spmv_vector<VT, G, false>), dim3(grid), dim3(256), 0, st, n_rows, rp, ci, va, x, y, AxpbyArgs<VT>{});
 }
 
-template <typename VT>
-int launch_csr(long n_rows, long nnz_hint, const int *rp, const int *ci, const VT *va, const VT *x, VT *y,
-               hipStream_t st) {
-    if (n_rows == 0) return USPMV_OK;
+// lanes per row of the csr kernel (tuning "csr_lanes", 0: from the mean row length)
+static int csr_lanes_for(long n_rows, long nnz_hint) {
     int G = g_tune.csr_lanes;
     if (G <= 0) {
         const double avg = nnz_hint > 0 ? (double)nnz_hint / (double)n_rows : 16.0;
         G = 2;
         while (G < 64 && G < avg / 2) G <<= 1;
     }
+    return G;
+}
+
+template <typename VT>
+int launch_csr(long n_rows, long nnz_hint, const int *rp, const int *ci, const VT *va, const VT *x, VT *y,
+               hipStream_t st, const AxpbyArgs<VT> *ep) {
+    if (n_rows == 0) return USPMV_OK;
+    const int G = csr_lanes_for(n_rows, nnz_hint);
     switch (G) {
-        case 1: launch_csr_g<VT, 1>(n_rows, rp, ci, va, x, y, st); break;
-        case 2: launch_csr_g<VT, 2>(n_rows, rp, ci, va, x, y, st); break;
-        case 4: launch_csr_g<VT, 4>(n_rows, rp, ci, va, x, y, st); break;
-        case 8: launch_csr_g<VT, 8>(n_rows, rp, ci, va, x, y, st); break;
-        case 16: launch_csr_g<VT, 16>(n_rows, rp, ci, va, x, y, st); break;
-        case 32: launch_csr_g<VT, 32>(n_rows, rp, ci, va, x, y, st); break;
-        default: launch_csr_g<VT, 64>(n_rows, rp, ci, va, x, y, st); break;
+        case 1: launch_csr_g<VT, 1>(n_rows, rp, ci, va, x, y, st, ep); break;
+        case 2: launch_csr_g<VT, 2>(n_rows, rp, ci, va, x, y, st, ep); break;
+        case 4: launch_csr_g<VT, 4>(n_rows, rp, ci, va, x, y, st, ep); break;
+        case 8: launch_csr_g<VT, 8>(n_rows, rp, ci, va, x, y, st, ep); break;
+        case 16: launch_csr_g<VT, 16>(n_rows, rp, ci, va, x, y, st, ep); break;
+        case 32: launch_csr_g<VT, 32>(n_rows, rp, ci, va, x, y, st, ep); break;
+        default: launch_csr_g<VT, 64>(n_rows, rp, ci, va, x, y, st, ep); break;
     }
     HIP_TRY(hipGetLastError());
     return USPMV_OK;
 }
 
-template int launch_spmv_scs<double>(const uspmv_dmat *, const int *, long, const double *, double *, hipStream_t);
-template int launch_spmv_scs<float>(const uspmv_dmat *, const int *, long, const float *, float *, hipStream_t);
-template int launch_spmv_tlc<double>(const uspmv_dmat *, const int *, long, const double *, double *, hipStream_t);
-template int launch_spmv_tlc<float>(const uspmv_dmat *, const int *, long, const float *, float *, hipStream_t);
+// ---- uspmv_spmv_axpby ----
+int spmv_axpby_route(const uspmv_dmat *M, bool crs, bool x16, long *slots) {
+    long n = 0;
+    int path = 2;
+    const bool dflt = g_tune.nontemporal && g_tune.spmv_variant == 0 && !g_tune.ablate;
+    if (M->n_chunks == 0) {
+        path = 1;                                                       // (nothing is launched)
+    } else if (crs) {
+        if (dflt) { path = 1; n = grid_for((long)M->n_chunks * csr_lanes_for((long)M->n_chunks, (long)M->n_elements), 256); }
+    } else if (M->sw.on && M->sw.tile_ids && M->sw.n_parts == 1 && g_tune.sweep && !g_tune.ablate && g_tune.spmv_variant == 0 && x16) {
+        if (dflt && sweep_axpby_fused(M) && (!M->sw.n_rest || rows_axpby_fused())) {
+            path = 1;
+            n = (long)M->sw.n_tiles + (M->sw.n_rest ? (long)grid_for((long)M->sw.n_rest * M->C, g_tune.block) : 0);
+        }
+    } else if (M->tlc.on && M->tlc.plan_id == 0 && g_tune.tlc && !g_tune.ablate && g_tune.spmv_variant == 0 && x16) {
+        if (dflt) {
+            const bool own_tiles = M->tlc.add_ptrs != nullptr && !M->tlc.elem && !M->tlc.row_map && M->tlc.add_own_tiles;
+            path = 1; n = own_tiles ? (long)M->tlc.add_n_tiles : (long)M->tlc.n_tiles;
+        }
+    } else if (rows_axpby_fused()) {
+        path = 1; n = grid_for((long)M->n_chunks * M->C, g_tune.block);
+    }
+    if (path == 2) n = axpby_pass_slots(M->n_store);
+    if (slots) *slots = n;
+    return path;
+}
+
+// (the scalar form's grid -- vectors off the 16-byte grid --, the larger of the two)
+long axpby_pass_slots(long n) { return (long)grid_for(n, 256); }
+
+template <typename VT>
+int launch_axpby_pass(const VT *t, VT *y, long n, const AxpbyArgs<VT> &ep, hipStream_t st, long *slots) {
+    *slots = 0;
+    if (n == 0) return USPMV_OK;
+    constexpr int V = 16 / (int)sizeof(VT);
+    const bool vec = ((uintptr_t)t | (uintptr_t)y) % 16 == 0;
+    const unsigned grid = vec ? grid_for((n + V - 1) / V, 256) : grid_for(n, 256);
+    if (vec) hipLaunchKernelGGL((axpby_pass_kernel<VT, V>), dim3(grid), dim3(256), AXPBY_RED_BYTES, st, t, y, n, ep);
+    else hipLaunchKernelGGL((axpby_pass_kernel<VT, 1>), dim3(grid), dim3(256), AXPBY_RED_BYTES, st, t, y, n, ep);
+    HIP_TRY(hipGetLastError());
+    *slots = (long)grid;
+    return USPMV_OK;
+}
+
+int launch_axpby_finalize(const double *part, long slots, double *dots, hipStream_t st) {
+    hipLaunchKernelGGL(axpby_finalize_kernel, dim3(1), dim3(1024), 0, st, part, slots, dots);
+    HIP_TRY(hipGetLastError());
+    return USPMV_OK;
+}
+
+template int launch_axpby_pass<double>(const double *, double *, long, const AxpbyArgs<double> &, hipStream_t, long *);
+template int launch_axpby_pass<float>(const float *, float *, long, const AxpbyArgs<float> &, hipStream_t, long *);
+template int launch_spmv_scs<double>(const uspmv_dmat *, const int *, long, const double *, double *, hipStream_t, const AxpbyArgs<double> *);
+template int launch_spmv_scs<float>(const uspmv_dmat *, const int *, long, const float *, float *, hipStream_t, const AxpbyArgs<float> *);
+template int launch_spmv_tlc<double>(const uspmv_dmat *, const int *, long, const double *, double *, hipStream_t, const AxpbyArgs<double> *);
+template int launch_spmv_tlc<float>(const uspmv_dmat *, const int *, long, const float *, float *, hipStream_t, const AxpbyArgs<float> *);
 template int launch_spmv_tlc_step<double>(const uspmv_dmat *, const int *, const StepArgs &, int, const double *, double *, hipStream_t);
 template int launch_spmv_tlc_step<float>(const uspmv_dmat *, const int *, const StepArgs &, int, const float *, float *, hipStream_t);
-template int launch_csr<double>(long, long, const int *, const int *, const double *, const double *, double *, hipStream_t);
-template int launch_csr<float>(long, long, const int *, const int *, const float *, const float *, float *, hipStream_t);
+template int launch_csr<double>(long, long, const int *, const int *, const double *, const double *, double *, hipStream_t, const AxpbyArgs<double> *);
+template int launch_csr<float>(long, long, const int *, const int *, const float *, const float *, float *, hipStream_t, const AxpbyArgs<float> *);
 
 }  // namespace uspmv_dev

@@ -136,14 +136,17 @@ __device__ __forceinline__ SweepPtrs<A0, A1> sweep_window2(const X0 *__restrict_
 
 // RPL rows per lane: a tile is RPL * blockDim.x rows, lane <-> rows tid, tid + blockDim.x, ...  The windows of x are staged once per
 // tile, so RPL = 2 halves the staging traffic per non-zero (the workgroup is already 1 024 threads).
-template <typename VT, bool AP, bool NT, int NBUF, int U, int RPL, int PAIRM = 0>
+// EP = 1: the store epilogue of uspmv_spmv_axpby (uspmv_device.hpp; one struct only).  No thread of a sweep tile leaves early, and the
+// window buffers are dead behind the last window: the reduction takes the front of them.
+template <typename VT, bool AP, bool NT, int NBUF, int U, int RPL, int PAIRM = 0, int EP = 0>
 __global__ void __launch_bounds__(1024) scs_spmv_sweep(const int wlog, const int *__restrict__ tile_ids, const int *__restrict__ t_smin,
         const int *__restrict__ t_S, const unsigned long long *__restrict__ t_cnt_off,
         const unsigned *__restrict__ wave_off, const unsigned char *__restrict__ cnt, const VT *__restrict__ vals, const unsigned short *__restrict__ idx,
         const int *__restrict__ pad_col,
         const unsigned *__restrict__ wave_off_b, const unsigned char *__restrict__ cnt_b, const float *__restrict__ vals_b,
         const unsigned short *__restrict__ idx_b, const int *__restrict__ pad_col_b,
-        const VT *__restrict__ x, VT *__restrict__ y, const long x_len, const long n_store, const int xcd_remap) {
+        const VT *__restrict__ x, VT *__restrict__ y, const long x_len, const long n_store, const int xcd_remap, const AxpbyArgs<VT> ep) {
+    static_assert(EP == 0 || !AP, "fused epilogue: one-precision handles only");
     extern __shared__ __attribute__((aligned(16))) unsigned char sweep_smem[];
     constexpr int EPL = 16 / (int)sizeof(VT);           // elements per 16-byte DMA lane
     constexpr int EPP = 1024 / (int)sizeof(VT);         // elements per 1-KiB piece (one wave-instruction)
@@ -245,6 +248,7 @@ __global__ void __launch_bounds__(1024) scs_spmv_sweep(const int wlog, const int
         }
     }
     // trailing padding of the row, applied once (see sweep_plan.cpp)
+    [[maybe_unused]] double d0 = 0.0, d1 = 0.0;           // (EP: the lane's dot terms over its RPL rows)
 #pragma unroll
     for (int h = 0; h < RPL; ++h) {
         const long row = (long)tile * R + h * T + threadIdx.x;
@@ -255,12 +259,16 @@ __global__ void __launch_bounds__(1024) scs_spmv_sweep(const int wlog, const int
             if (pcb >= 0) acc_b[h] = __builtin_fma((double)0.0f, (double)x[pcb], acc_b[h]);
             acc[h] = (VT)((double)acc[h] + acc_b[h]);
         }
-        if (row < n_store) st_y<NT>(y + row, acc[h]);
+        if constexpr (EP == 0) {
+            if (row < n_store) st_y<NT>(y + row, acc[h]);
+        } else {
+            if (row < n_store) st_y<NT>(y + row, axpby_row(ep, row, acc[h], d0, d1));
+        }
     }
+    if constexpr (EP != 0) axpby_reduce(ep, bt, d0, d1, (double *)sweep_smem);
 }
-
 template <typename VT, bool AP>
-int launch_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st) {
+int launch_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep = nullptr) {
     const auto &w = A->sw;
     const auto &p0 = w.part[0], &p1 = w.part[1];          // (the second part: the sp part of the pair; empty for one struct)
     const long W = 1L << w.wlog;
@@ -279,10 +287,31 @@ int launch_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st) {
         hipLaunchKernelGGL(kfn, dim3((unsigned)w.n_tiles), dim3(threads), lds, st, w.wlog, w.tile_ids.get(), w.smin.get(),   \
                            w.S.get(), (const unsigned long long *)w.cnt_off, p0.wave_off.get(), p0.cnt.get(),                \
                            (const VT *)p0.vals, p0.idx.get(), p0.pad.get(), p1.wave_off.get(), p1.cnt.get(),                 \
-                           (const float *)p1.vals, p1.idx.get(), p1.pad.get(), x, y, (long)w.x_len, (long)A->n_store, remap); \
+                           (const float *)p1.vals, p1.idx.get(), p1.pad.get(), x, y, (long)w.x_len, (long)A->n_store, remap, AxpbyArgs<VT>{}); \
     } while (0)
 #define SW_LAUNCH_R(NTV, NB, UU) do { if (rpl == 4) SW_LAUNCH(NTV, NB, UU, 4); else if (rpl == 2) SW_LAUNCH(NTV, NB, UU, 2); else SW_LAUNCH(NTV, NB, UU, 1); } while (0)
 #define SW_LAUNCH_U(NTV, NB) do { if (g_tune.sweep_unroll >= 8) SW_LAUNCH_R(NTV, NB, 8); else SW_LAUNCH_R(NTV, NB, 4); } while (0)
+    // the fused instantiations: sweep_axpby_fused's tuning (non-temporal, eight rounds, the default pairing)
+#define SW_AXPBY(NB, RP, PM)                                                                                                \
+    do {                                                                                                                    \
+        auto kfn = scs_spmv_sweep<VT, false, true, NB, 8, RP, PM, 1>;                                                                    \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)w.n_tiles), dim3(threads), lds, st, w.wlog, w.tile_ids.get(), w.smin.get(),   \
+                           w.S.get(), (const unsigned long long *)w.cnt_off, p0.wave_off.get(), p0.cnt.get(),                \
+                           (const VT *)p0.vals, p0.idx.get(), p0.pad.get(), (const unsigned *)nullptr, (const unsigned char *)nullptr,          \
+                           (const float *)nullptr, (const unsigned short *)nullptr, (const int *)nullptr, x, y, (long)w.x_len, (long)A->n_store, remap, *ep); \
+    } while (0)
+#define SW_AXPBY_R(NB) do { if (rpl == 4) SW_AXPBY(NB, 4, 2); else if (rpl == 2) SW_AXPBY(NB, 2, 2); else SW_AXPBY(NB, 1, 0); } while (0)
+    if constexpr (!AP) {
+        if (ep) {
+            if (!sweep_axpby_fused(A)) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_sweep: no fused instantiation under this tuning");
+            if (nbuf == 2) SW_AXPBY_R(2); else SW_AXPBY_R(1);
+            HIP_TRY(hipGetLastError());
+            return USPMV_OK;
+        }
+    }
+#undef SW_AXPBY_R
+#undef SW_AXPBY
     if (g_tune.nontemporal) { if (nbuf == 2) SW_LAUNCH_U(true, 2); else SW_LAUNCH_U(true, 1); }
     else { if (nbuf == 2) SW_LAUNCH_U(false, 2); else SW_LAUNCH_U(false, 1); }
 #undef SW_LAUNCH_U
@@ -297,9 +326,14 @@ int launch_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st) {
 namespace uspmv_dev {
 
 template <typename VT>
-int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st) {
+int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep) {
     if (A->sw.n_tiles == 0) return USPMV_OK;
-    return launch_sweep<VT, false>(A, x, y, st);
+    return launch_sweep<VT, false>(A, x, y, st, ep);
+}
+
+bool sweep_axpby_fused(const uspmv_dmat *A) {
+    const int rpl = A->sw.tile_rows / sweep_threads(A->sw);
+    return g_tune.nontemporal && g_tune.sweep_unroll >= 8 && (rpl == 1 || g_tune.sweep_pair == 2);
 }
 
 int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st) {
@@ -307,7 +341,7 @@ int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipSt
     return launch_sweep<double, true>(dp, x, y, st);
 }
 
-template int launch_spmv_sweep<double>(const uspmv_dmat *, const double *, double *, hipStream_t);
-template int launch_spmv_sweep<float>(const uspmv_dmat *, const float *, float *, hipStream_t);
+template int launch_spmv_sweep<double>(const uspmv_dmat *, const double *, double *, hipStream_t, const AxpbyArgs<double> *);
+template int launch_spmv_sweep<float>(const uspmv_dmat *, const float *, float *, hipStream_t, const AxpbyArgs<float> *);
 
 }  // namespace uspmv_dev

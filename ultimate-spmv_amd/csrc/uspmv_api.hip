@@ -496,6 +496,132 @@ int uspmv_spmv(const uspmv_dmat_t *A, const void *d_x, void *d_y, void *stream) 
     return launch_spmv_scs<float>(A, nullptr, 0, (const float *)d_x, (float *)d_y, (hipStream_t)stream);
 }
 
+// ---- y = alpha A x + beta z with <y,y> and <w,y> ----
+extern "C++" {
+namespace {
+
+// the struct uspmv_spmv launches for this handle (its re-chunking where it carries one and the tuning takes it) and whether by the csr kernel
+const uspmv_dmat *axpby_struct(const uspmv_dmat *A, bool *crs) {
+    *crs = false;
+    if (A->alt && g_tune.tlc && g_tune.rechunk && g_tune.spmv_variant == 0 && !g_tune.ablate) return A->alt;
+    *crs = A->crs;
+    return A;
+}
+
+// what the three entry points refuse before a device is looked for: handles uspmv_spmv refuses, and the parts of an adaptive-precision split
+int axpby_refusals(const uspmv_dmat *A, const char *who) {
+    if (int rc = check_dmat(A, who)) return rc;
+    if (A->dtype == USPMV_F16)
+        return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: fp16 handle; fp16 values run only as the hp part of uspmv_spmv_ap_hp", who);
+    for (const uspmv_dmat *M = A; M; M = M->alt)
+        if ((M->tlc.on && M->tlc.plan_id != 0) || (M->sw.on && (M->sw.n_parts > 1 || !M->sw.tile_ids)))
+            return uspmv::fail(USPMV_ERR_UNSUPPORTED, "%s: the handle carries the shared plan of an adaptive-precision split (a part's product is not y; "
+                                                      "run uspmv_spmv_ap[_hp] and apply the update to its result)", who);
+    return USPMV_OK;
+}
+
+// room for `slots` partial pairs (and `tmp_bytes` of the in-place temporary of path 2) on the handle; `st` capturing: no allocation
+int axpby_room(const uspmv_dmat *A, size_t slots, size_t tmp_bytes, hipStream_t st, bool check_capture, const char *who) {
+    const bool grow_part = slots > A->axpby_slots, grow_tmp = tmp_bytes > A->axpby_tmp_bytes;
+    if (!grow_part && !grow_tmp) return USPMV_OK;
+    if (check_capture) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
+        if (cs != hipStreamCaptureStatusNone)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: the stream is capturing and the handle's workspace would have to be allocated; call "
+                                                  "uspmv_spmv_axpby_reserve before the capture (under the tuning the call runs with)", who);
+    }
+    if (grow_part) {
+        A->axpby_slots = 0;
+        HIP_TRY(A->axpby_part.alloc(slots * 2 * sizeof(double)));
+        A->axpby_slots = slots;
+    }
+    if (grow_tmp) {
+        A->axpby_tmp_bytes = 0;
+        HIP_TRY(A->axpby_tmp.alloc(tmp_bytes));
+        A->axpby_tmp_bytes = tmp_bytes;
+    }
+    return USPMV_OK;
+}
+
+template <typename VT>
+int spmv_axpby_typed(const uspmv_dmat *A, const VT *x, VT *y, const uspmv_axpby_t *op, hipStream_t st) {
+    const char *who = "uspmv_spmv_axpby";
+    bool crs = false;
+    const uspmv_dmat *M = axpby_struct(A, &crs);
+    long slots = 0;
+    const int path = spmv_axpby_route(M, crs, (uintptr_t)x % 16 == 0, &slots);
+    const bool dots = op->d_dots != nullptr;
+    const bool in_place = op->beta != 0.0 && op->d_z == (const void *)y;
+    const size_t tmp_bytes = (path == 2 && in_place) ? (size_t)A->n_store * sizeof(VT) : 0;
+    if (int rc = axpby_room(A, dots ? (size_t)slots : 0, tmp_bytes, st, true, who)) return rc;
+    AxpbyArgs<VT> ep;
+    ep.alpha = (VT)op->alpha; ep.beta = (VT)op->beta;
+    ep.z = (const VT *)op->d_z; ep.w = (const VT *)op->d_w;
+    ep.part = dots ? A->axpby_part.get() : nullptr;
+    ep.n_dot = (long)op->n_dot_rows;
+    if (path == 1) {
+        int rc;
+        if (crs) rc = launch_csr<VT>((long)M->n_chunks, (long)M->n_elements, M->chunk_ptrs, M->col_idxs, (const VT *)M->values, x, y, st, &ep);
+        else rc = launch_spmv_scs<VT>(M, nullptr, 0, x, y, st, &ep);
+        if (rc) return rc;
+    } else {
+        // uspmv_spmv's own launch, then one pass over its result (an in-place call: the product goes to the temporary, y still holds z)
+        VT *t = tmp_bytes ? (VT *)A->axpby_tmp.get() : y;
+        if (int rc = uspmv_spmv(A, x, t, st)) return rc;
+        if (int rc = launch_axpby_pass<VT>(t, y, (long)A->n_store, ep, st, &slots)) return rc;
+    }
+    if (dots) return launch_axpby_finalize(ep.part, A->n_chunks == 0 ? 0 : slots, op->d_dots, st);
+    return USPMV_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int uspmv_spmv_axpby(const uspmv_dmat_t *A, const void *d_x, void *d_y, const uspmv_axpby_t *op, void *stream) {
+    const char *who = "uspmv_spmv_axpby";
+    if (int rc = axpby_refusals(A, who)) return rc;
+    if (!op) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL op", who);
+    if (!d_x || !d_y) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL vector", who);
+    if (op->beta != 0.0 && !op->d_z) return uspmv::fail(USPMV_ERR_INVALID, "%s: beta != 0 needs d_z", who);
+    const size_t es = uspmv_dtype_bytes(A->dtype);
+    const long n = A->n_store;
+    if (op->beta != 0.0 && op->d_z != (const void *)d_y) {
+        const uintptr_t z0 = (uintptr_t)op->d_z, y0 = (uintptr_t)d_y, len = (uintptr_t)n * es;
+        if (z0 < y0 + len && y0 < z0 + len)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: d_z overlaps d_y partially (in place means d_z == d_y)", who);
+    }
+    if (op->n_dot_rows < 0 || op->n_dot_rows > n)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: n_dot_rows=%lld outside [0, %lld], the rows y may be written", who, (long long)op->n_dot_rows, (long long)n);
+    if (int rc = require_device()) return rc;
+    if (A->dtype == USPMV_F64) return spmv_axpby_typed<double>(A, (const double *)d_x, (double *)d_y, op, (hipStream_t)stream);
+    return spmv_axpby_typed<float>(A, (const float *)d_x, (float *)d_y, op, (hipStream_t)stream);
+}
+
+int uspmv_spmv_axpby_path(const uspmv_dmat_t *A, const void *d_x, int *path) {
+    const char *who = "uspmv_spmv_axpby_path";
+    if (int rc = axpby_refusals(A, who)) return rc;
+    if (!d_x || !path) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    bool crs = false;
+    const uspmv_dmat *M = axpby_struct(A, &crs);
+    *path = spmv_axpby_route(M, crs, (uintptr_t)d_x % 16 == 0, nullptr);
+    return USPMV_OK;
+}
+
+int uspmv_spmv_axpby_reserve(uspmv_dmat_t *A) {
+    const char *who = "uspmv_spmv_axpby_reserve";
+    if (int rc = axpby_refusals(A, who)) return rc;
+    if (int rc = require_device()) return rc;
+    bool crs = false;
+    const uspmv_dmat *M = axpby_struct(A, &crs);
+    long s1 = 0;
+    const int path = spmv_axpby_route(M, crs, true, &s1);
+    // the larger of the routed path's grid and the vector pass's (an x off the 16-byte grid falls to path 2); the in-place temporary
+    // only where a 16-byte-aligned x already takes path 2
+    const long slots = std::max(s1, axpby_pass_slots((long)A->n_store));
+    return axpby_room(A, (size_t)slots, path == 2 ? (size_t)A->n_store * uspmv_dtype_bytes(A->dtype) : 0, nullptr, false, who);
+}
+
 int uspmv_spmv_chunks(const uspmv_dmat_t *A, const int32_t *d_chunk_ids, int64_t n_ids, const void *d_x, void *d_y,
                       void *stream) {
     if (int rc = check_dmat_one_prec(A, "uspmv_spmv_chunks")) return rc;

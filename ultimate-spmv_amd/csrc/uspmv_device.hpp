@@ -160,6 +160,13 @@ struct uspmv_dmat {
     // 8 the phased kernel, 9 scs_spmmv_sweep, 10 the streamed phased kernel (the "spmmv_variant" numbers where there is one).
     // last_xpass: 0 X as passed, 1 re-laid out in this call, 2 the prepared workspace reused, 3 a re-layout that undid the sigma permutation.
     mutable int last_kernel = 0, last_xpass = 0;
+    // uspmv_spmv_axpby: two doubles per workgroup of the launches that serve one call, summed by its finalize kernel;
+    // axpby_tmp: A x of an in-place call on path 2 (y is z there, so the SpMV cannot write it).  Like ws: grown on demand or by
+    // uspmv_spmv_axpby_reserve, released with the handle, not thread-safe per handle.
+    mutable DeviceBuf<double> axpby_part;
+    mutable size_t axpby_slots = 0;
+    mutable DeviceBuf<void> axpby_tmp;
+    mutable size_t axpby_tmp_bytes = 0;
     // SpMMV in two parts (the halo overlap of uspmv_dist_spmmv, csrc/uspmv_dist_api.hip): chunk-length arrays in which the chunks of the
     // OTHER part carry USPMV_SKIP_LEN -- a kernel that meets it leaves those rows of Y alone.  [order][part - 1]: order 0 = the caller's
     // row order (gather kernels), order 1 = the phased plan's tie-re-ordered rows (scs_spmmv_quadph), classified per 64-row plan tile.
@@ -345,7 +352,21 @@ struct AddArgs {
     const unsigned short *rec = nullptr;
 };
 
-constexpr int USPMV_SKIP_LEN = -4;     // (a multiple of four: no kernel sees a partial group or a tail in it)
+// y = alpha A x + beta z with two dot products (uspmv_spmv_axpby) as the kernels' store epilogue takes it: alpha and
+// beta already in the handle's value type; z, w in y's row order (z is read only when beta != 0, w only when it is there); part: two
+// doubles per workgroup, the workgroup with logical id b writes slot slot0 + b (nullptr: no reduction code runs); rows below n_dot
+// enter the dots.
+template <typename VT>
+struct AxpbyArgs {
+    VT alpha = VT(1), beta = VT(0);
+    const VT *z = nullptr, *w = nullptr;
+    double *part = nullptr;
+    long n_dot = 0;
+    unsigned slot0 = 0;
+};
+constexpr int AXPBY_RED_BYTES = 16 * 2 * 8;   // LDS of the workgroup reduction: 16 waves x 2 doubles, the front of the kernel's dynamic window
+
+constexpr int USPMV_SKIP_LEN = -4;    // (a multiple of four: no kernel sees a partial group or a tail in it)
 
 // the chunk lengths a launcher hands to its kernel: the handle's own, or the selected part's (order 0 caller's rows, 1 phased plan rows)
 inline const int32_t *part_lengths(const uspmv_dmat *A, int order) {
@@ -492,15 +513,27 @@ inline unsigned grid_for(long work_items, int block) { return (unsigned)((work_i
 constexpr size_t BT_LDS_CAP = 80 * 1024;  // LDS per single-wave SpMMV tile (block plan): two tiles per CU at worst
 
 // launch entry points (explicitly instantiated for double and float in their kernel files)
+// ep != nullptr (uspmv_spmv_axpby on path 1 only, spmv_axpby_route): the fused instantiations, which store alpha t + beta z and leave
+// their workgroups' dot partials in ep->part
 template <typename VT>
-int launch_spmv_scs(const uspmv_dmat *A, const int *chunk_ids, long n_ids, const VT *x, VT *y, hipStream_t st);   // spmv_kernels.hip
+int launch_spmv_scs(const uspmv_dmat *A, const int *chunk_ids, long n_ids, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep = nullptr);   // spmv_kernels.hip
 template <typename VT>
-int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, const VT *x, VT *y, hipStream_t st);  // spmv_kernels.hip
+int launch_spmv_tlc(const uspmv_dmat *A, const int *tile_ids, long n_tiles, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep = nullptr);  // spmv_kernels.hip
+// uspmv_spmv_axpby on the struct uspmv_spmv would launch (M: the handle or its re-chunking; crs: the csr kernel): 1 when the launch that
+// serves it has a fused instantiation -- the conditions launch_spmv_scs / launch_csr branch on --, else 2; *slots: workgroups of the
+// launch(es) that serve the call on that path
+int spmv_axpby_route(const uspmv_dmat *M, bool crs, bool x16, long *slots);                                        // spmv_kernels.hip
+// path 2's vector pass over rows [0, n): y = alpha t + beta z from the stored t (t may be y), the same epilogue routine, same partials
+template <typename VT>
+int launch_axpby_pass(const VT *t, VT *y, long n, const AxpbyArgs<VT> &ep, hipStream_t st, long *slots);            // spmv_kernels.hip (*slots: workgroups launched)
+long axpby_pass_slots(long n);   // the most it launches for n rows
+// dots[0 .. 2) = the sums of part[2 k], part[2 k + 1] over k < slots, in one fixed order
+int launch_axpby_finalize(const double *part, long slots, double *dots, hipStream_t st);                           // spmv_kernels.hip
 // the one-launch distributed step over `step_ids` = [early | late | conditional] (sync 1) and its deferred entries (sync 2)
 template <typename VT>
 int launch_spmv_tlc_step(const uspmv_dmat *A, const int *step_ids, const StepArgs &sa, int sync, const VT *x, VT *y, hipStream_t st);
 template <typename VT>
-int launch_csr(long n_rows, long nnz_hint, const int *rp, const int *ci, const VT *va, const VT *x, VT *y, hipStream_t st);  // spmv_kernels.hip
+int launch_csr(long n_rows, long nnz_hint, const int *rp, const int *ci, const VT *va, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep = nullptr);  // spmv_kernels.hip
 template <typename VT>
 int launch_spmmv(const uspmv_dmat *A, const VT *X, VT *Y, int b, long ld, int layout, hipStream_t st);            // spmmv_kernels.hip
 template <typename VT>
@@ -586,7 +619,8 @@ int spmmv_ap_hp_sweep_bs(const uspmv_dmat *hi, int b);
 int launch_spmmv_ap_hp_sweep(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *X, void *Y, int b, long ld,
                              bool colwise, int bs, hipStream_t st);
 template <typename VT>
-int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st);                                    // sweep_kernels.hip (sweep tiles only)
+int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep = nullptr);   // sweep_kernels.hip (sweep tiles only)
+bool sweep_axpby_fused(const uspmv_dmat *A);   // sweep_kernels.hip: the sweep launch of this handle under the current tuning has a fused instantiation
 int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st);                       // sweep_kernels.hip
 int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *d_x,
                           double *d_y, hipStream_t stream);                                                        // ap_kernels.hip
@@ -717,6 +751,57 @@ __device__ __forceinline__ void st_y(T *p, T v) {
 }
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// ---- the store epilogue of uspmv_spmv_axpby (AxpbyArgs above) ----
+// One rounding per operation, whatever -ffp-contract says: the products and sums below carry no `contract` flag, so neither the
+// front end nor the back end fuses them into an FMA.
+template <typename T>
+__device__ __forceinline__ T mul_rn_t(T a, T b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+template <typename T>
+__device__ __forceinline__ T add_rn_t(T a, T b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+// The value row `row` stores when its chain ended in t: rn(alpha t), or rn(rn(alpha t) + rn(beta z[row])) when beta != 0 (z is not
+// read otherwise).  With a partial buffer, rows below n_dot add their terms <y,y> and <w,y> to the lane's d0 / d1: the operands widened
+// to double (exact for floats), one rounding per product.  Called by the lane that stores the row, for rows it may store only.
+template <typename VT>
+__device__ __forceinline__ VT axpby_row(const uspmv_dev::AxpbyArgs<VT> &ep, const long row, const VT t, double &d0, double &d1) {
+    VT v = mul_rn_t(ep.alpha, t);
+    if (ep.beta != VT(0)) v = add_rn_t(v, mul_rn_t(ep.beta, ep.z[row]));
+    if (ep.part && row < ep.n_dot) {
+        const double vd = (double)v;
+        d0 = add_rn_t(d0, mul_rn_t(vd, vd));
+        if (ep.w) d1 = add_rn_t(d1, mul_rn_t((double)ep.w[row], vd));
+    }
+    return v;
+}
+// The workgroup's two partial sums, stored at slot slot0 + lb (lb: the LOGICAL block id, so that the slot does not depend on the
+// dispatch order): the lanes of a wave through cross-lane adds, the waves through LDS in wave order.  EVERY thread of the workgroup
+// calls this (lanes without a row with zero terms); red: AXPBY_RED_BYTES of LDS that are dead once all threads are here -- the front
+// of the kernel's window.  Without a partial buffer (kernel-uniform) nothing runs.  blockDim.x is a multiple of 64.
+template <typename VT>
+__device__ __forceinline__ void axpby_reduce(const uspmv_dev::AxpbyArgs<VT> &ep, const unsigned lb, double d0, double d1, double *red) {
+    if (!ep.part) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        d0 = add_rn_t(d0, __shfl_xor(d0, o, 64));
+        d1 = add_rn_t(d1, __shfl_xor(d1, o, 64));
+    }
+    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();                                      // everybody is through with the window
+    if ((threadIdx.x & 63) == 0) { red[2 * wave] = d0; red[2 * wave + 1] = d1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s0 = 0.0, s1 = 0.0;
+        for (int k = 0; k < nw; ++k) { s0 = add_rn_t(s0, red[2 * k]); s1 = add_rn_t(s1, red[2 * k + 1]); }
+        double *p = ep.part + 2 * ((long)ep.slot0 + lb);
+        p[0] = s0; p[1] = s1;
+    }
+}
 
 // Adaptive precision (ap_kernels.hip, ap_hp_spmmv_kernels.hip, sweep_ap_hp_kernels.hip): one step of a part's chain.  With a double x every
 // product is an FMA in double on the exactly widened value (scs_ap_impl_cpu's convention, hp in the place of sp), with a float x the

@@ -618,6 +618,33 @@ int uspmv_spmv_ap_generic(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const 
  *   ap[sp_hp]     (hi F32, no mid): x, y float; every product sp_v * x and (float)hp_v * x rounded to float, then added to a double
  *                 accumulator per part; y = (float)(sp + hp) */
 int uspmv_spmv_ap_hp(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, void *d_y, void *stream);
+/* The fused update y = alpha A x + beta z with two dot products on the parts of an adaptive-precision split (no reference counterpart;
+ * DESIGN.md 5.13): uspmv_spmv_axpby's operand struct and contract with ONE change -- t_i is what uspmv_spmv_ap / uspmv_spmv_ap_hp stores
+ * for row i on these handles, the parts' slot-ordered chains combined as there: dp + sp, hi + hp, (hi + mid) + hp, or (float)(sp + hp).
+ * alpha and beta are converted ONCE to the type of x and y (double; float for ap[sp_hp], whose z and w are float as well).
+ * beta == 0: y_i = rn(alpha t_i), z is never read (may be NULL, may hold NaN);  else y_i = rn(rn(alpha t_i) + rn(beta z_i)), three
+ * separately rounded operations, never an FMA.  alpha = 1, beta = 0 without dots gives uspmv_spmv_ap[_hp]'s y bit for bit.  d_z may be
+ * d_y (in place).  dots as in uspmv_spmv_axpby: accumulated in double over rows [0, n_dot_rows), one rounding per product, no
+ * floating-point atomics, no host synchronisation; every workgroup stores its two partial sums at the slot of its logical id -- a call
+ * served by two launches (sweep tiles, then the chunks the plan leaves over) gives the second launch the slots behind the first's -- and
+ * one finalize kernel on the same stream adds the slots in a fixed order: bitwise reproducible on the same handles, plan and tuning.
+ * The workspace (the partial sums and, on path 2, the in-place temporary) lives on the FIRST handle (dp / hi); it is allocated on
+ * first use or by the _reserve call, and a call that would have to allocate while its stream is capturing returns USPMV_ERR_INVALID and
+ * names the _reserve call.  Not thread-safe per first handle.
+ * Refused before anything is launched or written: the argument checks of uspmv_spmv_ap / uspmv_spmv_ap_hp (handles that do not form a
+ * split, wrong dtypes, mismatched C or n_chunks), then USPMV_ERR_INVALID for NULL op / d_x / d_y, beta != 0 with NULL d_z, d_z overlapping
+ * d_y partially, n_dot_rows outside [0, n_chunks * C].  d_y must NOT overlap d_x (not checked).  The generic-C variant with a float copy
+ * of x (uspmv_spmv_ap_generic) has no fused form.
+ * _path: 1 fused in the store epilogue of the kernel(s) uspmv_spmv_ap[_hp] launches (every kernel of the default tuning), 2 that call
+ * followed by one vector pass with the same epilogue ("nontemporal" 0; "unroll" < 8 on the pair's lane-per-row kernel; "sweep_unroll" < 8
+ * or "sweep_pair" != 2 on a sweep plan).  An x off the 16-byte grid leaves the plan for the lane-per-row kernel, as in the plain call. */
+int uspmv_spmv_ap_axpby(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const double *d_x, double *d_y, const uspmv_axpby_t *op, void *stream);
+int uspmv_spmv_ap_axpby_path(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const void *d_x, int *path);
+int uspmv_spmv_ap_axpby_reserve(uspmv_dmat_t *dp, const uspmv_dmat_t *sp);
+int uspmv_spmv_ap_hp_axpby(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, void *d_y,
+                           const uspmv_axpby_t *op, void *stream);
+int uspmv_spmv_ap_hp_axpby_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, int *path);
+int uspmv_spmv_ap_hp_axpby_reserve(uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp);
 /* uspmv_spmv_ap_hp restricted to a subset of the rows, for the distributed step of the kinds with an fp16 part (uspmv_dist_create_ap_hp_from_coo):
  * the twins of uspmv_spmv_ap_tiles / _chunks.  Handles as for uspmv_spmv_ap_hp (mid NULL for the two-part kinds), x and y in the type of the hi
  * part.  Every row written carries the bits uspmv_spmv_ap_hp gives it, rows outside the list are not touched.  Entries < 0 are skipped (a

@@ -324,6 +324,27 @@ public:
         if (kind_ == USPMV_AP_DP_SP) uspmv_detail::check(uspmv_spmv_ap(h_[0], h_[2], (const double *)d_x, (double *)d_y, stream), "uspmv_spmv_ap");
         else uspmv_detail::check(uspmv_spmv_ap_hp(h_[0], h_[1], h_[2], d_x, d_y, stream), "uspmv_spmv_ap_hp");
     }
+    // y = alpha A x + beta z with <y,y> and <w,y> (uspmv_spmv_ap_axpby / uspmv_spmv_ap_hp_axpby), A x being what spmv stores: arguments as
+    // on DeviceScs::spmv_axpby, all vectors in the type of x (float for ap[sp_hp], else double).  d_y must not overlap d_x.
+    void spmv_axpby(const void *d_x, void *d_y, double alpha, double beta, const void *d_z = nullptr, const void *d_w = nullptr,
+                    double *d_dots = nullptr, ST n_dot_rows = -1, void *stream = nullptr) const {
+        const uspmv_axpby_t op{alpha, beta, d_z, d_w, d_dots, n_dot_rows < 0 ? (int64_t)n_rows_padded_ : (int64_t)n_dot_rows};
+        if (kind_ == USPMV_AP_DP_SP)
+            uspmv_detail::check(uspmv_spmv_ap_axpby(h_[0], h_[2], (const double *)d_x, (double *)d_y, &op, stream), "uspmv_spmv_ap_axpby");
+        else uspmv_detail::check(uspmv_spmv_ap_hp_axpby(h_[0], h_[1], h_[2], d_x, d_y, &op, stream), "uspmv_spmv_ap_hp_axpby");
+    }
+    // 1: fused in the epilogue of spmv's kernel(s), 2: spmv + one vector pass
+    int spmv_axpby_path(const void *d_x) const {
+        int path = 0;
+        if (kind_ == USPMV_AP_DP_SP) uspmv_detail::check(uspmv_spmv_ap_axpby_path(h_[0], h_[2], d_x, &path), "uspmv_spmv_ap_axpby_path");
+        else uspmv_detail::check(uspmv_spmv_ap_hp_axpby_path(h_[0], h_[1], h_[2], d_x, &path), "uspmv_spmv_ap_hp_axpby_path");
+        return path;
+    }
+    // the workspace of spmv_axpby now, e.g. before a stream capture
+    void axpby_reserve() {
+        if (kind_ == USPMV_AP_DP_SP) uspmv_detail::check(uspmv_spmv_ap_axpby_reserve(h_[0], h_[2]), "uspmv_spmv_ap_axpby_reserve");
+        else uspmv_detail::check(uspmv_spmv_ap_hp_axpby_reserve(h_[0], h_[1], h_[2]), "uspmv_spmv_ap_hp_axpby_reserve");
+    }
     void spmmv(const void *d_X, void *d_Y, int b, ST ld, bool rowwise, void *stream = nullptr) const {
         const int lay = rowwise ? USPMV_ROWWISE : USPMV_COLWISE;
         if (kind_ == USPMV_AP_DP_SP) uspmv_detail::check(uspmv_spmmv_ap(h_[0], h_[2], d_X, d_Y, b, ld, lay, stream), "uspmv_spmmv_ap");

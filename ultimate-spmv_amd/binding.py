@@ -141,6 +141,12 @@ _SIGS = {
     "uspmv_dmat_optimize_sweep_device_ap_hp": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "uspmv_spmmv": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
     "uspmv_spmv_ap": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "uspmv_spmv_ap_axpby": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "uspmv_spmv_ap_axpby_path": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int)]),
+    "uspmv_spmv_ap_axpby_reserve": (C.c_int, [_vp, _vp]),
+    "uspmv_spmv_ap_hp_axpby": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "uspmv_spmv_ap_hp_axpby_path": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int)]),
+    "uspmv_spmv_ap_hp_axpby_reserve": (C.c_int, [_vp, _vp, _vp]),
     "uspmv_spmmv_ap": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _i64, C.c_int, _vp]),
     "uspmv_spmmv_ap_plan_lines": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "uspmv_spmmv_ap_path": (C.c_int, [_vp, _vp, C.c_int, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -1682,6 +1688,58 @@ def spmv_ap(A_dp, A_sp, x, y, stream=None, x_sp=None):
     else:
         _ck(lib().uspmv_spmv_ap_generic(A_dp.h, A_sp.h, _dp(x), _dp(x_sp), _dp(y), _stream_ptr(stream)))
     return y
+
+
+def _axpby_op(A, y, alpha, beta, z, w, dots, n_dot_rows):
+    """the uspmv_axpby_t of a call on the split whose first part is A (x, y, z, w in A's type)"""
+    import torch
+    assert y.dtype == A.torch_dtype and y.numel() >= A.n_rows_padded
+    for v in (z, w):
+        assert v is None or (v.dtype == A.torch_dtype and v.numel() >= A.n_rows_padded and v.is_contiguous())
+    assert dots is None or (dots.dtype == torch.float64 and dots.numel() == 2 and dots.is_cuda and dots.is_contiguous())
+    return AxpbyOp(float(alpha), float(beta), _dp(z), _dp(w), _dp(dots), A.n_rows_padded if n_dot_rows is None else int(n_dot_rows))
+
+
+def spmv_ap_axpby(A_dp, A_sp, x, y, alpha=1.0, beta=0.0, z=None, w=None, dots=None, n_dot_rows=None, stream=None):
+    """y = alpha A x + beta z on the ap[dp_sp] pair (uspmv_spmv_ap_axpby), A x being what spmv_ap stores; arguments as in spmv_axpby,
+    all vectors float64."""
+    assert x.dtype == A_dp.torch_dtype
+    op = _axpby_op(A_dp, y, alpha, beta, z, w, dots, n_dot_rows)
+    _ck(lib().uspmv_spmv_ap_axpby(A_dp.h, A_sp.h, _dp(x), _dp(y), C.byref(op), _stream_ptr(stream)))
+    return y
+
+
+def spmv_ap_axpby_path(A_dp, A_sp, x):
+    """1: spmv_ap_axpby with this x runs fused in the epilogue of spmv_ap's kernel(s), 2: spmv_ap + one vector pass"""
+    p = C.c_int(0)
+    _ck(lib().uspmv_spmv_ap_axpby_path(A_dp.h, A_sp.h, _dp(x), C.byref(p)))
+    return p.value
+
+
+def ap_axpby_reserve(A_dp, A_sp):
+    """Allocate the workspace of spmv_ap_axpby (on A_dp) now, e.g. before a stream capture (uspmv_spmv_ap_axpby_reserve)."""
+    _ck(lib().uspmv_spmv_ap_axpby_reserve(A_dp.h, A_sp.h))
+
+
+def spmv_ap_hp_axpby(A_hi, A_mid, A_hp, x, y, alpha=1.0, beta=0.0, z=None, w=None, dots=None, n_dot_rows=None, stream=None):
+    """y = alpha A x + beta z on a split with an fp16 part (uspmv_spmv_ap_hp_axpby), A x being what spmv_ap_hp stores; arguments as in
+    spmv_axpby, all vectors in A_hi's type (float32 for ap[sp_hp]); A_mid None for the two-part kinds."""
+    assert x.dtype == A_hi.torch_dtype
+    op = _axpby_op(A_hi, y, alpha, beta, z, w, dots, n_dot_rows)
+    _ck(lib().uspmv_spmv_ap_hp_axpby(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(x), _dp(y), C.byref(op), _stream_ptr(stream)))
+    return y
+
+
+def spmv_ap_hp_axpby_path(A_hi, A_mid, A_hp, x):
+    """1: spmv_ap_hp_axpby with this x runs fused in the epilogue of spmv_ap_hp's kernel(s), 2: spmv_ap_hp + one vector pass"""
+    p = C.c_int(0)
+    _ck(lib().uspmv_spmv_ap_hp_axpby_path(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h, _dp(x), C.byref(p)))
+    return p.value
+
+
+def ap_hp_axpby_reserve(A_hi, A_mid, A_hp):
+    """Allocate the workspace of spmv_ap_hp_axpby (on A_hi) now, e.g. before a stream capture (uspmv_spmv_ap_hp_axpby_reserve)."""
+    _ck(lib().uspmv_spmv_ap_hp_axpby_reserve(A_hi.h, A_mid.h if A_mid is not None else None, A_hp.h))
 
 
 def spmmv_ap(A_dp, A_sp, X, Y, b, ld, layout=COLWISE, stream=None):

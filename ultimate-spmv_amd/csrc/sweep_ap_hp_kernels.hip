@@ -14,6 +14,7 @@
 // ap[dp_sp_hp] (a split by magnitude puts most entries there), the two parts of the other kinds.  "sweep_pair" 0: one part after the
 // other.  The streams are addressed as base pointer (wave-uniform kernel argument) + 32-bit element offset per (row of the lane, part):
 // one scalar register each, where the pair kernel's pointers take four.
+#include <cstddef>
 #include "uspmv_device.hpp"
 #include "sweep_common.hpp"
 
@@ -130,12 +131,29 @@ __device__ __forceinline__ HpOffs hp_window2(const XT *__restrict__ xs, const in
     return o;
 }
 
+// scs_spmv_sweep_ap_hp's arguments as they lie in the kernel-argument segment (each at its natural alignment, in the order of the
+// signature -- the layout of this struct): where the fused form finds `ep`
+template <typename HT>
+struct SweepHpKernargs {
+    int wlog, nbuf;
+    const int *tile_ids, *t_smin, *t_S;
+    const unsigned long long *t_cnt_off;
+    SweepParts P;
+    const HT *x;
+    HT *y;
+    long x_len, n_store;
+    int xcd_remap;
+    AxpbyArgs<HT> ep;
+};
+
 // HT: type of x, y and the first part (double, or float for ap[sp_hp]); MID: ap[dp_sp_hp].  RPL rows per lane: a tile is
 // RPL * blockDim.x rows, lane <-> rows tid, tid + blockDim.x, ...  nbuf: LDS buffers (2: window s+1 lands while window s is consumed).
-template <typename HT, bool MID, bool NT, int U, int RPL, int PAIRM>
+// EP = 1: the store epilogue of uspmv_spmv_ap_hp_axpby (uspmv_device.hpp) on the value the plain form stores.  No thread of a sweep tile
+// leaves early, and the window buffers are dead behind the last window: the reduction takes the front of them.
+template <typename HT, bool MID, bool NT, int U, int RPL, int PAIRM, int EP = 0>
 __global__ void __launch_bounds__(1024) scs_spmv_sweep_ap_hp(const int wlog, const int nbuf, const int *__restrict__ tile_ids,
         const int *__restrict__ t_smin, const int *__restrict__ t_S, const unsigned long long *__restrict__ t_cnt_off, const SweepParts P,
-        const HT *__restrict__ x, HT *__restrict__ y, const long x_len, const long n_store, const int xcd_remap) {
+        const HT *__restrict__ x, HT *__restrict__ y, const long x_len, const long n_store, const int xcd_remap, const AxpbyArgs<HT> ep) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sweep_smem[];
     constexpr int EPL = 16 / (int)sizeof(HT);           // elements per 16-byte DMA lane
     constexpr int EPP = 1024 / (int)sizeof(HT);         // elements per 1-KiB piece (one wave-instruction)
@@ -229,6 +247,23 @@ __global__ void __launch_bounds__(1024) scs_spmv_sweep_ap_hp(const int wlog, con
         }
     }
     // trailing padding of every part of the row, applied once in the part's own type (see sweep_plan.cpp)
+    [[maybe_unused]] double d0 = 0.0, d1 = 0.0;           // (EP: the lane's dot terms over its RPL rows)
+    // EP: the epilogue's arguments are read from the kernel-argument segment HERE, behind the last window, and not through `ep`: loaded
+    // at the kernel's entry, their 13 scalar registers stay live across the window loop, and the four-rows-per-lane dp + hp form -- 128
+    // vector registers without them -- then spills scalars into a 129th, i.e. into scratch.  (`ep` itself stays in the signature: it is
+    // what the launch fills.)
+    AxpbyArgs<HT> e;
+    if constexpr (EP != 0) {
+        typedef const char __attribute__((address_space(4))) *karg_t;
+        karg_t kp = (karg_t)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kp));                      // (opaque: the loads below cannot move above this point)
+        kp += offsetof(SweepHpKernargs<HT>, ep);
+#define KARG(T, M) (*(T const __attribute__((address_space(4))) *)(kp + offsetof(AxpbyArgs<HT>, M)))
+        e.alpha = KARG(HT, alpha); e.beta = KARG(HT, beta);
+        e.z = KARG(const HT *, z); e.w = KARG(const HT *, w);
+        e.part = KARG(double *, part); e.n_dot = KARG(long, n_dot); e.slot0 = KARG(unsigned, slot0);
+#undef KARG
+    }
 #pragma unroll
     for (int h = 0; h < RPL; ++h) {
         const long row = (long)tile * R + h * T + threadIdx.x;
@@ -241,12 +276,17 @@ __global__ void __launch_bounds__(1024) scs_spmv_sweep_ap_hp(const int wlog, con
         }
         const int pc2 = P.pad[2][pr];
         if (pc2 >= 0) acc[h][2] = ap_step((unsigned short)0, x[pc2], acc[h][2]);
-        if (row < n_store) st_y<NT>(y + row, ap_hp_y<HT, MID>(acc[h][0], acc[h][1], acc[h][2]));
+        if constexpr (EP == 0) {
+            if (row < n_store) st_y<NT>(y + row, ap_hp_y<HT, MID>(acc[h][0], acc[h][1], acc[h][2]));
+        } else {
+            if (row < n_store) st_y<NT>(y + row, axpby_row(e, row, ap_hp_y<HT, MID>(acc[h][0], acc[h][1], acc[h][2]), d0, d1));
+        }
     }
+    if constexpr (EP != 0) axpby_reduce(e, bt, d0, d1, (double *)sweep_smem);
 }
 
 template <typename HT, bool MID>
-int launch_sweep_hp(const uspmv_dmat *A, const HT *x, HT *y, hipStream_t st) {
+int launch_sweep_hp(const uspmv_dmat *A, const HT *x, HT *y, hipStream_t st, const AxpbyArgs<HT> *ep) {
     const auto &w = A->sw;
     const SweepParts P = sweep_parts(w);
     const long W = 1L << w.wlog;
@@ -261,8 +301,25 @@ int launch_sweep_hp(const uspmv_dmat *A, const HT *x, HT *y, hipStream_t st) {
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
         hipLaunchKernelGGL(kfn, dim3((unsigned)w.n_tiles), dim3(threads), lds, st, w.wlog, nbuf, w.tile_ids.get(), w.smin.get(),  \
                            w.S.get(), (const unsigned long long *)w.cnt_off, P, x, y, (long)w.x_len, (long)A->n_store,           \
-                           g_tune.sweep_remap);                                                                                  \
+                           g_tune.sweep_remap, AxpbyArgs<HT>{});                                                                 \
     } while (0)
+    // the fused instantiations: non-temporal, eight rounds, the default pairing (spmv_ap_hp_axpby_route)
+#define SWH_AXPBY(RP)                                                                                                            \
+    do {                                                                                                                         \
+        auto kfn = scs_spmv_sweep_ap_hp<HT, MID, true, 8, RP, 2, 1>;                                                             \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)w.n_tiles), dim3(threads), lds, st, w.wlog, nbuf, w.tile_ids.get(), w.smin.get(),  \
+                           w.S.get(), (const unsigned long long *)w.cnt_off, P, x, y, (long)w.x_len, (long)A->n_store,           \
+                           g_tune.sweep_remap, *ep);                                                                             \
+    } while (0)
+    if (ep) {
+        if (!(g_tune.nontemporal && g_tune.sweep_unroll >= 8 && g_tune.sweep_pair == 2))
+            return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_sweep_hp: no fused instantiation under this tuning");
+        if (rpl == 4) SWH_AXPBY(4); else if (rpl == 2) SWH_AXPBY(2); else SWH_AXPBY(1);
+        HIP_TRY(hipGetLastError());
+        return USPMV_OK;
+    }
+#undef SWH_AXPBY
 #define SWH_LAUNCH_P(NTV, UU, RP) do { if (g_tune.sweep_pair == 2) SWH_LAUNCH(NTV, UU, RP, 2); else if (g_tune.sweep_pair == 1) SWH_LAUNCH(NTV, UU, RP, 1); else SWH_LAUNCH(NTV, UU, RP, 0); } while (0)
 #define SWH_LAUNCH_R(NTV, UU) do { if (rpl == 4) SWH_LAUNCH_P(NTV, UU, 4); else if (rpl == 2) SWH_LAUNCH_P(NTV, UU, 2); else SWH_LAUNCH_P(NTV, UU, 1); } while (0)
 #define SWH_LAUNCH_U(NTV) do { if (g_tune.sweep_unroll >= 8) SWH_LAUNCH_R(NTV, 8); else SWH_LAUNCH_R(NTV, 4); } while (0)
@@ -279,11 +336,11 @@ int launch_sweep_hp(const uspmv_dmat *A, const HT *x, HT *y, hipStream_t st) {
 
 namespace uspmv_dev {
 
-int launch_spmv_sweep_ap_hp(const uspmv_dmat *hi, bool mid, const void *x, void *y, hipStream_t st) {
+int launch_spmv_sweep_ap_hp(const uspmv_dmat *hi, bool mid, const void *x, void *y, hipStream_t st, const void *ep) {
     if (hi->sw.n_tiles == 0) return USPMV_OK;
-    if (hi->dtype == USPMV_F32) return launch_sweep_hp<float, false>(hi, (const float *)x, (float *)y, st);
-    if (mid) return launch_sweep_hp<double, true>(hi, (const double *)x, (double *)y, st);
-    return launch_sweep_hp<double, false>(hi, (const double *)x, (double *)y, st);
+    if (hi->dtype == USPMV_F32) return launch_sweep_hp<float, false>(hi, (const float *)x, (float *)y, st, (const AxpbyArgs<float> *)ep);
+    if (mid) return launch_sweep_hp<double, true>(hi, (const double *)x, (double *)y, st, (const AxpbyArgs<double> *)ep);
+    return launch_sweep_hp<double, false>(hi, (const double *)x, (double *)y, st, (const AxpbyArgs<double> *)ep);
 }
 
 }  // namespace uspmv_dev

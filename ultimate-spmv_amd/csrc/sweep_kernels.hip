@@ -136,8 +136,9 @@ __device__ __forceinline__ SweepPtrs<A0, A1> sweep_window2(const X0 *__restrict_
 
 // RPL rows per lane: a tile is RPL * blockDim.x rows, lane <-> rows tid, tid + blockDim.x, ...  The windows of x are staged once per
 // tile, so RPL = 2 halves the staging traffic per non-zero (the workgroup is already 1 024 threads).
-// EP = 1: the store epilogue of uspmv_spmv_axpby (uspmv_device.hpp; one struct only).  No thread of a sweep tile leaves early, and the
-// window buffers are dead behind the last window: the reduction takes the front of them.
+// EP = 1: the store epilogue of uspmv_spmv_axpby and, with AP, of uspmv_spmv_ap_axpby (uspmv_device.hpp), applied to the value the
+// plain form stores -- with AP that is acc + acc_b.  No thread of a sweep tile leaves early, and the window buffers are dead behind the
+// last window: the reduction takes the front of them.
 template <typename VT, bool AP, bool NT, int NBUF, int U, int RPL, int PAIRM = 0, int EP = 0>
 __global__ void __launch_bounds__(1024) scs_spmv_sweep(const int wlog, const int *__restrict__ tile_ids, const int *__restrict__ t_smin,
         const int *__restrict__ t_S, const unsigned long long *__restrict__ t_cnt_off,
@@ -146,7 +147,6 @@ __global__ void __launch_bounds__(1024) scs_spmv_sweep(const int wlog, const int
         const unsigned *__restrict__ wave_off_b, const unsigned char *__restrict__ cnt_b, const float *__restrict__ vals_b,
         const unsigned short *__restrict__ idx_b, const int *__restrict__ pad_col_b,
         const VT *__restrict__ x, VT *__restrict__ y, const long x_len, const long n_store, const int xcd_remap, const AxpbyArgs<VT> ep) {
-    static_assert(EP == 0 || !AP, "fused epilogue: one-precision handles only");
     extern __shared__ __attribute__((aligned(16))) unsigned char sweep_smem[];
     constexpr int EPL = 16 / (int)sizeof(VT);           // elements per 16-byte DMA lane
     constexpr int EPP = 1024 / (int)sizeof(VT);         // elements per 1-KiB piece (one wave-instruction)
@@ -302,14 +302,31 @@ int launch_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st, const 
                            (const float *)nullptr, (const unsigned short *)nullptr, (const int *)nullptr, x, y, (long)w.x_len, (long)A->n_store, remap, *ep); \
     } while (0)
 #define SW_AXPBY_R(NB) do { if (rpl == 4) SW_AXPBY(NB, 4, 2); else if (rpl == 2) SW_AXPBY(NB, 2, 2); else SW_AXPBY(NB, 1, 0); } while (0)
-    if constexpr (!AP) {
-        if (ep) {
+    // the pair: the dp and the sp chain of a row side by side at every number of rows per lane ("sweep_pair" 2)
+#define SW_AXPBY_AP(NB, RP)                                                                                                 \
+    do {                                                                                                                    \
+        auto kfn = scs_spmv_sweep<VT, true, true, NB, 8, RP, 2, 1>;                                                         \
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)w.n_tiles), dim3(threads), lds, st, w.wlog, w.tile_ids.get(), w.smin.get(),   \
+                           w.S.get(), (const unsigned long long *)w.cnt_off, p0.wave_off.get(), p0.cnt.get(),                \
+                           (const VT *)p0.vals, p0.idx.get(), p0.pad.get(), p1.wave_off.get(), p1.cnt.get(),                 \
+                           (const float *)p1.vals, p1.idx.get(), p1.pad.get(), x, y, (long)w.x_len, (long)A->n_store, remap, *ep); \
+    } while (0)
+#define SW_AXPBY_AP_R(NB) do { if (rpl == 4) SW_AXPBY_AP(NB, 4); else if (rpl == 2) SW_AXPBY_AP(NB, 2); else SW_AXPBY_AP(NB, 1); } while (0)
+    if (ep) {
+        if constexpr (!AP) {
             if (!sweep_axpby_fused(A)) return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_sweep: no fused instantiation under this tuning");
             if (nbuf == 2) SW_AXPBY_R(2); else SW_AXPBY_R(1);
-            HIP_TRY(hipGetLastError());
-            return USPMV_OK;
+        } else {
+            if (!(g_tune.nontemporal && g_tune.sweep_unroll >= 8 && g_tune.sweep_pair == 2))
+                return uspmv::fail(USPMV_ERR_UNSUPPORTED, "launch_sweep: no fused instantiation of the pair's kernel under this tuning");
+            if (nbuf == 2) SW_AXPBY_AP_R(2); else SW_AXPBY_AP_R(1);
         }
+        HIP_TRY(hipGetLastError());
+        return USPMV_OK;
     }
+#undef SW_AXPBY_AP_R
+#undef SW_AXPBY_AP
 #undef SW_AXPBY_R
 #undef SW_AXPBY
     if (g_tune.nontemporal) { if (nbuf == 2) SW_LAUNCH_U(true, 2); else SW_LAUNCH_U(true, 1); }
@@ -336,9 +353,9 @@ bool sweep_axpby_fused(const uspmv_dmat *A) {
     return g_tune.nontemporal && g_tune.sweep_unroll >= 8 && (rpl == 1 || g_tune.sweep_pair == 2);
 }
 
-int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st) {
+int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st, const AxpbyArgs<double> *ep) {
     if (dp->sw.n_tiles == 0) return USPMV_OK;
-    return launch_sweep<double, true>(dp, x, y, st);
+    return launch_sweep<double, true>(dp, x, y, st, ep);
 }
 
 template int launch_spmv_sweep<double>(const uspmv_dmat *, const double *, double *, hipStream_t, const AxpbyArgs<double> *);

@@ -521,7 +521,9 @@ int axpby_refusals(const uspmv_dmat *A, const char *who) {
 }
 
 // room for `slots` partial pairs (and `tmp_bytes` of the in-place temporary of path 2) on the handle; `st` capturing: no allocation
-int axpby_room(const uspmv_dmat *A, size_t slots, size_t tmp_bytes, hipStream_t st, bool check_capture, const char *who) {
+// (reserve: the call that allocates ahead of a capture, named in the refusal)
+int axpby_room(const uspmv_dmat *A, size_t slots, size_t tmp_bytes, hipStream_t st, bool check_capture, const char *who,
+               const char *reserve = "uspmv_spmv_axpby_reserve") {
     const bool grow_part = slots > A->axpby_slots, grow_tmp = tmp_bytes > A->axpby_tmp_bytes;
     if (!grow_part && !grow_tmp) return USPMV_OK;
     if (check_capture) {
@@ -529,7 +531,7 @@ int axpby_room(const uspmv_dmat *A, size_t slots, size_t tmp_bytes, hipStream_t 
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
         if (cs != hipStreamCaptureStatusNone)
             return uspmv::fail(USPMV_ERR_INVALID, "%s: the stream is capturing and the handle's workspace would have to be allocated; call "
-                                                  "uspmv_spmv_axpby_reserve before the capture (under the tuning the call runs with)", who);
+                                                  "%s before the capture (under the tuning the call runs with)", who, reserve);
     }
     if (grow_part) {
         A->axpby_slots = 0;
@@ -789,6 +791,125 @@ int uspmv_spmv_ap_generic(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const 
                           double *d_y, void *stream) {
     if (!d_x_sp) return uspmv::fail(USPMV_ERR_INVALID, "uspmv_spmv_ap_generic: NULL float x");
     return spmv_ap_impl(dp, sp, d_x, d_x_sp, d_y, stream, "uspmv_spmv_ap_generic");
+}
+
+// ---- y = alpha A x + beta z with <y,y> and <w,y> on the parts of an adaptive-precision split ----
+extern "C++" {
+namespace {
+
+// uspmv_spmv_axpby's own refusals (5.12) on n rows of es bytes
+int ap_axpby_op_refusals(const uspmv_axpby_t *op, const void *d_x, const void *d_y, long n, size_t es, const char *who) {
+    if (!op) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL op", who);
+    if (!d_x || !d_y) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL vector", who);
+    if (op->beta != 0.0 && !op->d_z) return uspmv::fail(USPMV_ERR_INVALID, "%s: beta != 0 needs d_z", who);
+    if (op->beta != 0.0 && op->d_z != d_y) {
+        const uintptr_t z0 = (uintptr_t)op->d_z, y0 = (uintptr_t)d_y, len = (uintptr_t)n * es;
+        if (z0 < y0 + len && y0 < z0 + len)
+            return uspmv::fail(USPMV_ERR_INVALID, "%s: d_z overlaps d_y partially (in place means d_z == d_y)", who);
+    }
+    if (op->n_dot_rows < 0 || op->n_dot_rows > n)
+        return uspmv::fail(USPMV_ERR_INVALID, "%s: n_dot_rows=%lld outside [0, %lld], the rows y may be written", who, (long long)op->n_dot_rows, (long long)n);
+    return USPMV_OK;
+}
+
+// One call on either family: `first` carries the workspace (dp / hi); sp != nullptr: the pair, else (first, mid, hp).
+template <typename HT>
+int spmv_ap_axpby_typed(const uspmv_dmat *first, const uspmv_dmat *sp, const uspmv_dmat *mid, const uspmv_dmat *hp, const HT *x, HT *y,
+                        const uspmv_axpby_t *op, hipStream_t st, const char *who, const char *reserve) {
+    const long n = (long)first->n_chunks * first->C;
+    const bool x16 = (uintptr_t)x % 16 == 0;
+    long slots = 0;
+    const int path = sp ? spmv_ap_axpby_route(first, sp, x16, &slots) : spmv_ap_hp_axpby_route(first, mid, hp, x16, &slots);
+    const bool dots = op->d_dots != nullptr;
+    const bool in_place = op->beta != 0.0 && op->d_z == (const void *)y;
+    const size_t tmp_bytes = (path == 2 && in_place) ? (size_t)n * sizeof(HT) : 0;
+    if (int rc = axpby_room(first, dots ? (size_t)slots : 0, tmp_bytes, st, true, who, reserve)) return rc;
+    AxpbyArgs<HT> ep;
+    ep.alpha = (HT)op->alpha; ep.beta = (HT)op->beta;
+    ep.z = (const HT *)op->d_z; ep.w = (const HT *)op->d_w;
+    ep.part = dots ? first->axpby_part.get() : nullptr;
+    ep.n_dot = (long)op->n_dot_rows;
+    if (n == 0) {
+        slots = 0;
+    } else if (path == 1) {
+        int rc;
+        if constexpr (sizeof(HT) == 8) rc = sp ? launch_spmv_ap(first, sp, x, nullptr, y, st, &ep) : launch_spmv_ap_hp(first, mid, hp, x, y, st, &ep);
+        else rc = launch_spmv_ap_hp(first, mid, hp, x, y, st, &ep);
+        if (rc) return rc;
+    } else {
+        // the plain call's own launch, then one pass over its result (an in-place call: the product goes to the temporary, y still holds z)
+        HT *t = tmp_bytes ? (HT *)first->axpby_tmp.get() : y;
+        int rc;
+        if constexpr (sizeof(HT) == 8) rc = sp ? launch_spmv_ap(first, sp, x, nullptr, t, st) : launch_spmv_ap_hp(first, mid, hp, x, t, st);
+        else rc = launch_spmv_ap_hp(first, mid, hp, x, t, st);
+        if (rc) return rc;
+        if (int rc2 = launch_axpby_pass<HT>(t, y, n, ep, st, &slots)) return rc2;
+    }
+    if (dots) return launch_axpby_finalize(ep.part, slots, op->d_dots, st);
+    return USPMV_OK;
+}
+
+// the workspace of either family under the current tuning: the larger of the routed path's grid and the vector pass's (an x off the
+// 16-byte grid leaves the plan), the in-place temporary only where a 16-byte-aligned x already takes path 2
+int ap_axpby_reserve(uspmv_dmat *first, const uspmv_dmat *sp, const uspmv_dmat *mid, const uspmv_dmat *hp, const char *who) {
+    if (int rc = require_device()) return rc;
+    const long n = (long)first->n_chunks * first->C;
+    long s1 = 0, s0 = 0;
+    const int path = sp ? spmv_ap_axpby_route(first, sp, true, &s1) : spmv_ap_hp_axpby_route(first, mid, hp, true, &s1);
+    if (sp) (void)spmv_ap_axpby_route(first, sp, false, &s0); else (void)spmv_ap_hp_axpby_route(first, mid, hp, false, &s0);
+    const long slots = std::max(std::max(s1, s0), axpby_pass_slots(n));
+    return axpby_room(first, (size_t)slots, path == 2 ? (size_t)n * uspmv_dtype_bytes(first->dtype) : 0, nullptr, false, who);
+}
+
+}  // namespace
+}  // extern "C++"
+
+int uspmv_spmv_ap_axpby(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const double *d_x, double *d_y, const uspmv_axpby_t *op, void *stream) {
+    const char *who = "uspmv_spmv_ap_axpby";
+    if (int rc = check_ap_pair(dp, sp, who)) return rc;
+    if (int rc = ap_axpby_op_refusals(op, d_x, d_y, (long)dp->n_chunks * dp->C, sizeof(double), who)) return rc;
+    if (int rc = require_device()) return rc;
+    return spmv_ap_axpby_typed<double>(dp, sp, nullptr, nullptr, d_x, d_y, op, (hipStream_t)stream, who, "uspmv_spmv_ap_axpby_reserve");
+}
+
+int uspmv_spmv_ap_axpby_path(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const void *d_x, int *path) {
+    const char *who = "uspmv_spmv_ap_axpby_path";
+    if (int rc = check_ap_pair(dp, sp, who)) return rc;
+    if (!d_x || !path) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    *path = spmv_ap_axpby_route(dp, sp, (uintptr_t)d_x % 16 == 0, nullptr);
+    return USPMV_OK;
+}
+
+int uspmv_spmv_ap_axpby_reserve(uspmv_dmat_t *dp, const uspmv_dmat_t *sp) {
+    const char *who = "uspmv_spmv_ap_axpby_reserve";
+    if (int rc = check_ap_pair(dp, sp, who)) return rc;
+    return ap_axpby_reserve(dp, sp, nullptr, nullptr, who);
+}
+
+int uspmv_spmv_ap_hp_axpby(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, void *d_y,
+                           const uspmv_axpby_t *op, void *stream) {
+    const char *who = "uspmv_spmv_ap_hp_axpby";
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    if (int rc = ap_axpby_op_refusals(op, d_x, d_y, (long)hi->n_chunks * hi->C, uspmv_dtype_bytes(hi->dtype), who)) return rc;
+    if (int rc = require_device()) return rc;
+    const char *reserve = "uspmv_spmv_ap_hp_axpby_reserve";
+    if (hi->dtype == USPMV_F32)
+        return spmv_ap_axpby_typed<float>(hi, nullptr, nullptr, hp, (const float *)d_x, (float *)d_y, op, (hipStream_t)stream, who, reserve);
+    return spmv_ap_axpby_typed<double>(hi, nullptr, mid, hp, (const double *)d_x, (double *)d_y, op, (hipStream_t)stream, who, reserve);
+}
+
+int uspmv_spmv_ap_hp_axpby_path(const uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp, const void *d_x, int *path) {
+    const char *who = "uspmv_spmv_ap_hp_axpby_path";
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    if (!d_x || !path) return uspmv::fail(USPMV_ERR_INVALID, "%s: NULL argument", who);
+    *path = spmv_ap_hp_axpby_route(hi, mid, hp, (uintptr_t)d_x % 16 == 0, nullptr);
+    return USPMV_OK;
+}
+
+int uspmv_spmv_ap_hp_axpby_reserve(uspmv_dmat_t *hi, const uspmv_dmat_t *mid, const uspmv_dmat_t *hp) {
+    const char *who = "uspmv_spmv_ap_hp_axpby_reserve";
+    if (int rc = check_ap_hp(hi, mid, hp, who)) return rc;
+    return ap_axpby_reserve(hi, nullptr, mid, hp, who);
 }
 
 int uspmv_spmmv_ap(const uspmv_dmat_t *dp, const uspmv_dmat_t *sp, const void *d_X, void *d_Y, int b, int64_t ld, int layout, void *stream) {

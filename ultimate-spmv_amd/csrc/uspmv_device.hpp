@@ -550,7 +550,10 @@ bool spmmv_stream(const uspmv_dmat *A, const double *X, double *Y, long ld, bool
 bool spmmv_stream(const uspmv_dmat *A, const float *X, float *Y, long ld, bool ycol, hipStream_t st);
 int dmat_stream_schedule(uspmv_dmat *A, int wgs_per_cu);
 int launch_spmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *d_x, const float *d_x_sp, double *d_y,
-                   hipStream_t stream);                                                                           // ap_kernels.hip
+                   hipStream_t stream, const AxpbyArgs<double> *ep = nullptr);                                    // ap_kernels.hip
+// uspmv_spmv_ap_axpby on this pair: 1 when the launch(es) launch_spmv_ap would make have fused instantiations -- its own conditions --,
+// else 2; *slots: workgroups of the launch(es) that serve the call on that path (path 2: of the vector pass)
+int spmv_ap_axpby_route(const uspmv_dmat *dp, const uspmv_dmat *sp, bool x16, long *slots);                        // ap_kernels.hip
 // ap[dp_sp] on block vectors: b = 1 forwards to launch_spmv_ap; B in {2, 4, 8, 16} the pair's column-window sweep plan where it carries one,
 // else the row-major kernels (column-major X through the dp handle's workspace); any other b lane per row with VB vectors per pass
 int launch_spmmv_ap(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, int layout,
@@ -576,7 +579,10 @@ int spmmv_ap_sweep_bs(const uspmv_dmat *dp, int b);
 int launch_spmmv_ap_sweep(const uspmv_dmat *dp, const uspmv_dmat *sp, const double *X, double *Y, int b, long ld, bool colwise, int bs,
                           hipStream_t st);
 // ap with an fp16 part (hi F64 | F32, mid F32 or nullptr, hp F16): the shared tile-local-column plan when all parts carry it, else lane per row
-int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *d_x, void *d_y, hipStream_t stream);   // ap_kernels.hip
+int launch_spmv_ap_hp(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const void *d_x, void *d_y, hipStream_t stream,
+                      const void *ep = nullptr);                                                                    // ap_kernels.hip
+// uspmv_spmv_ap_hp_axpby on these parts, as spmv_ap_axpby_route
+int spmv_ap_hp_axpby_route(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, bool x16, long *slots);   // ap_kernels.hip
 // what launch_spmv_ap_hp runs: 3 the shared column-window sweep, 2 the shared tile-local-column plan, 0 lane per row
 int spmv_ap_hp_path(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, bool x_aligned16);                                   // ap_kernels.hip
 // ... on block vectors (X, Y in the type of the hi part): b = 1 forwards to launch_spmv_ap_hp; b in {2, 4, 8, 16} on 16-byte-aligned
@@ -621,14 +627,17 @@ int launch_spmmv_ap_hp_sweep(const uspmv_dmat *hi, const uspmv_dmat *mid, const 
 template <typename VT>
 int launch_spmv_sweep(const uspmv_dmat *A, const VT *x, VT *y, hipStream_t st, const AxpbyArgs<VT> *ep = nullptr);   // sweep_kernels.hip (sweep tiles only)
 bool sweep_axpby_fused(const uspmv_dmat *A);   // sweep_kernels.hip: the sweep launch of this handle under the current tuning has a fused instantiation
-int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st);                       // sweep_kernels.hip
+// ep != nullptr here and in the launchers of the ap splits below (uspmv_spmv_ap[_hp]_axpby on path 1 only, spmv_ap[_hp]_axpby_route):
+// the fused instantiations; the launchers of the kinds with an fp16 part take it as const AxpbyArgs<HT> * behind a void pointer, HT the
+// type of x and y
+int launch_spmv_sweep_ap(const uspmv_dmat *dp, const double *x, double *y, hipStream_t st, const AxpbyArgs<double> *ep = nullptr);   // sweep_kernels.hip
 int launch_spmv_ap_chunks(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *chunk_ids, long n_ids, const double *d_x,
-                          double *d_y, hipStream_t stream);                                                        // ap_kernels.hip
+                          double *d_y, hipStream_t stream, const AxpbyArgs<double> *ep = nullptr);                 // ap_kernels.hip
 // the tiles in tile_ids of the pair's shared tile-local-column plan (entries < 0 skipped): scs_spmv_ap_tlc over a tile list
 int launch_spmv_ap_tiles(const uspmv_dmat *dp, const uspmv_dmat *sp, const int *tile_ids, long n_ids, const double *d_x, double *d_y,
                          hipStream_t stream);                                                                      // ap_kernels.hip
 // the sweep tiles of a plan shared by the parts of a split with an fp16 part (sweep_ap_hp_kernels.hip) and the chunks it leaves over
-int launch_spmv_sweep_ap_hp(const uspmv_dmat *hi, bool mid, const void *x, void *y, hipStream_t st);
+int launch_spmv_sweep_ap_hp(const uspmv_dmat *hi, bool mid, const void *x, void *y, hipStream_t st, const void *ep = nullptr);
 int launch_spmv_ap_hp_chunks(const uspmv_dmat *hi, const uspmv_dmat *mid, const uspmv_dmat *hp, const int *chunk_ids, long n_ids,
                              const void *d_x, void *d_y, hipStream_t stream);                                      // ap_kernels.hip
 // the tiles in tile_ids of the parts' shared tile-local-column plan (entries < 0 skipped): scs_spmv_ap_hp_tlc over a tile list
